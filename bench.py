@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the DDIM sampler path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C]
+    python bench.py --gpus N --steps K --warmup W [--config C] [--dump-outputs DIR]
 
 Headline (default, --config 2): a "step" is ONE EdgeInference.generate_mel call (4-step DDIM, CFG() decoder: hidden=160, L=4,
 heads=4, n_mels=80) over one synthetic batch of B=256 utterances x T=512 mel frames per GPU (BASELINE.json configs[1]; with N
@@ -12,7 +12,9 @@ value = whole-job mel-frames/s = N*B*T*K / (max-over-ranks wall time of the K st
 
 Protocol: the library is built before anything touches the GPU; W untimed warm-up steps; EXACTLY K steps
 bracketed by barrier + synchronize with all instrumentation off (value, ms_per_step = mean; the per-step HIP-event times of the
-same loop give ms_per_step_median).  Extra legs, rank 0 at N = 1 only, all OUTSIDE the headline loop:
+same loop give ms_per_step_median).  Inputs (weights, tokens, each step's noise seed) depend only on the arguments, so with
+--dump-outputs DIR the mel batch of the last timed step (DIR/mel.npy) can be compared between two builds.  Extra legs, rank 0 at
+N = 1 only, all OUTSIDE the headline loop:
   roofline      a second loop with the library's per-launch HIP events on (edtts_profile_*): dominant kernel = the fused
                 transformer-layer kernel k_layer; achieved = algorithmic FLOPs per launch / its average launch duration.
                 traffic = HBM bytes per k_layer launch from rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE, each in its own
@@ -189,6 +191,9 @@ def main():
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-sample-batch", type=int, default=128)  # ~10-15 s of CPU work on 16 threads
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the mel batch) to DIR/mel.npy as float32 "
+                         "(a fixed, seeded sample of utterances when it exceeds 64 MB)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     C = dict(CONFIGS[args.config])
@@ -197,6 +202,8 @@ def main():
     S = T // 2
     steps = args.steps if args.steps is not None else C["steps"]
     warmup = args.warmup if args.warmup is not None else max(2, min(10, steps // 10))
+    if steps < 1 or warmup < 0:
+        ap.error(f"--steps must be >= 1 and --warmup >= 0 (got {steps}, {warmup})")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))  # plain `python bench.py --gpus N`: this process only launches and relays
@@ -254,7 +261,12 @@ def main():
     from edge_diffusion_tts_amd import CFG, DiffusionSchedule, EdgeDiffusionDecoder, EdgeInference, native, synth_state_dict
     from edge_diffusion_tts_amd.parallel import gather_batch, generate_overlapped
 
-    cfg = CFG(device="cpu" if stub else "cuda", hidden=C["hidden"], layers=C["layers"], heads=C["heads"])
+    # CFG() creates data_root and out_dir as a construction side effect (reference behaviour); the benchmark reads and writes
+    # neither, so they are made in a temporary directory that is gone once CFG exists: bench.py writes nothing to its working
+    # directory, which may be read-only
+    with tempfile.TemporaryDirectory(prefix="edtts_bench_cfg_") as cfg_dirs:
+        cfg = CFG(device="cpu" if stub else "cuda", hidden=C["hidden"], layers=C["layers"], heads=C["heads"],
+                  data_root=os.path.join(cfg_dirs, "data"), out_dir=os.path.join(cfg_dirs, "run"))
     max_len = max(1000, T)
     gen = torch.Generator().manual_seed(2 + rank)
     sem = torch.randint(0, cfg.codebook_size, (B, S), generator=gen).to(dev)
@@ -349,6 +361,9 @@ def main():
     assert out.shape == (world * B, T, cfg.n_mels) and bool(torch.isfinite(out[:2]).all())
     if args.pmc_child:
         return
+    dumped = None
+    if args.dump_outputs and rank == 0:  # now: the legs below reuse the buffers `out` may live in
+        dumped = dump_outputs(args.dump_outputs, {"mel": out})
     per_step = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(steps))
     median_ms = per_step[len(per_step) // 2]
     if world > 1 and C["sampler"] == "ddim":
@@ -393,6 +408,8 @@ def main():
         if C["sampler"] == "ddim":
             result["allgather_ms"] = gather_ms  # median over 5, max over ranks, of the one all-gather per step (own loop)
             result["allgather_bytes"] = world * B * T * cfg.n_mels * 4
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if rehearsal:
         result["note"] = "REHEARSAL: ranks share one GPU, gloo collective -- not a scaling measurement"
     if stub:
@@ -446,6 +463,34 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result))
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each tensor of `arrays` -> d/<name>.npy in float32, at most DUMP_LIMIT_BYTES over all files.  A tensor over its
+    share keeps a fixed sample of its leading-dimension rows (utterances): torch.randperm(rows, seed 0), the first ones that fit,
+    in ascending order -- the same rows on every run of the same shape.  Returns what was written, for the JSON line."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays) - 4096  # (room for the .npy header)
+    info = {"dir": d}
+    for name, t in arrays.items():
+        n, row_bytes = t.shape[0], t[0].numel() * 4
+        keep = min(n, share // row_bytes)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one row of {name} ({row_bytes} B) exceeds the {DUMP_LIMIT_BYTES} B limit")
+        rows = "all"
+        if keep < n:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.index_select(0, idx.to(t.device))
+            rows = f"{keep} of {n}: torch.randperm({n}, seed 0)[:{keep}], ascending"
+        a = t.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
+        np.save(os.path.join(d, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "rows": rows}
+    return info
 
 
 def cpu_baseline(cfg, sd, Bc, T, n_steps):

@@ -1427,6 +1427,36 @@ def test_bench_two_ranks_rehearsal():
     assert abs(d["value"] - 2 * 128 * 512 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` on the real sampler: DIR/mel.npy is, bitwise, what generate_mel returns here for the inputs of
+    the benchmark's last timed step (synthetic weights of seed 0, tokens of seed 2, noise seed 1000 + warm-up + timed steps)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "EDTTS_BENCH_STUB", "EDTTS_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--batch", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                        "--no-pmc", "--no-roofline", "--dump-outputs", str(tmp_path / "dump")], env=env, cwd=tmp_path,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["dumped_outputs"]["mel"] == {"shape": [8, 512, 80], "rows": "all"}
+    mel = torch.from_numpy(np.load(tmp_path / "dump" / "mel.npy"))
+    cfg = CFG(device=DEV, hidden=160, layers=4, heads=4)
+    dec = EdgeDiffusionDecoder(cfg, max_len=1000)
+    dec.load_state_dict(synth_state_dict(cfg, 0, max_pos=1000))
+    dec = dec.to(DEV).eval()
+    sem = torch.randint(0, cfg.codebook_size, (8, 256), generator=torch.Generator().manual_seed(2)).to(DEV)
+    infer = EdgeInference(cfg, DiffusionSchedule(cfg.diff_steps).to(DEV), torch.nn.Identity(), dec)
+    ref = infer.generate_mel(sem, 4, seed=1000 + 1 + 3).cpu()
+    assert mel.dtype == torch.float32 and torch.equal(mel, ref)
+
+
 def test_build_time_instance_192_6_80_vs_oracle():
     """A decoder shape that is not built in (hidden 192, 6 heads of 32, n_mels 80) arrives through the build-time instance list
     (__graft_entry__.DEFAULT_INSTANCES / EDTTS_INSTANCES): single forward and the 4-step sampler against the CPU oracle, and a shape

@@ -152,3 +152,63 @@ def test_bench_parent_interrupted_takes_its_ranks_down():
     for k in kids:
         alive = subprocess.run(["ps", "-p", str(k), "-o", "stat="], capture_output=True, text=True).stdout.strip()
         assert alive == "" or alive.startswith("Z"), f"rank process {k} survived its parent ({alive})"
+
+
+def _stub_mel(seed, rows, T, n_mels=80):
+    """What bench.py's stand-in sampler returns for the global utterances `rows` at a step's noise seed."""
+    return torch.stack([torch.randn(T, n_mels, generator=torch.Generator().manual_seed(seed * 100003 + i)) for i in rows]).clamp_(-3, 3)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: DIR/mel.npy (float32) is the mel batch of the LAST timed step -- bench.py's step i draws its noise with
+    seed 1000 + i, warm-up steps included, so after W warm-up and K timed steps it is seed 1000 + W + K -- and two runs with the
+    same arguments write the same array.  Two ranks: rank 0 writes the gathered batch.  Over 64 MB: a fixed, seeded row sample."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    common = ("--batch", "4", "--frames", "32")
+    d = _run_bench({}, "--gpus", "1", "--steps", "3", "--warmup", "2", *common, "--dump-outputs", str(tmp_path / "a"))
+    _run_bench({}, "--gpus", "1", "--steps", "3", "--warmup", "2", *common, "--dump-outputs", str(tmp_path / "b"))
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["dumped_outputs"]["mel"] == {"shape": [4, 32, 80], "rows": "all"}
+    a, b = np.load(tmp_path / "a" / "mel.npy"), np.load(tmp_path / "b" / "mel.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert torch.equal(torch.from_numpy(a), _stub_mel(1005, range(4), 32))
+
+    _run_bench({}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3", "--frames", "32", "--dump-outputs", str(tmp_path / "c"))
+    assert torch.equal(torch.from_numpy(np.load(tmp_path / "c" / "mel.npy")), _stub_mel(1003, range(6), 32))
+
+    d = _run_bench({}, "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", "100", "--frames", "2048", "--dump-outputs", str(tmp_path / "e"))
+    path = tmp_path / "e" / "mel.npy"
+    keep = d["dumped_outputs"]["mel"]["shape"][0]
+    assert 0 < keep < 100 and os.path.getsize(path) <= 64 * 10**6
+    idx = torch.randperm(100, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    assert torch.equal(torch.from_numpy(np.load(path)), _stub_mel(1001, idx.tolist(), 2048))
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_bench_writes_nothing_to_its_working_directory(tmp_path):
+    """bench.py started from a read-only directory: CFG()'s data and run directories (a construction side effect) must not land
+    in the working directory, for one rank or for spawned ranks; the dump goes only where --dump-outputs names."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, EDTTS_BENCH_STUB="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    cwd = tmp_path / "cwd"
+    cwd.mkdir()
+    cwd.chmod(0o555)
+    try:
+        for gpus in ("1", "2"):
+            r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", gpus, "--steps", "1", "--warmup", "0", "--batch", "2",
+                                "--frames", "32", "--dump-outputs", str(tmp_path / f"dump{gpus}")], env=env, cwd=cwd, capture_output=True,
+                               text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            assert os.listdir(cwd) == [], os.listdir(cwd)
+            assert os.listdir(tmp_path / f"dump{gpus}") == ["mel.npy"]
+    finally:
+        cwd.chmod(0o755)
