@@ -1,0 +1,495 @@
+// edtts_generic.h -- the generic fp32 decoder path: every shape a run-time value (included by edtts_kernels.hip).
+//
+// The fused kernels of edtts_kernels.hip are compiled per decoder shape (hidden, heads, n_mels).  The kernels here take the shape
+// as arguments; they are templated on epilogue, tail and a padded head-dim tile count only, so the build grows by a fixed set of
+// kernels however many shapes run on them.  Selected per decoder with EDTTS_KERNELS_GENERIC / EDTTS_KERNELS_AUTO (include/edtts.h).
+//
+//   k_gen_gemm<EPI>    Y[M,N] = X[M,K] W[N,K]^T on v_mfma_f32_16x16x4_f32, both operands through LDS tiles (zero-filled past K / N),
+//                      masked stores; epilogues: + bias, + bias + positional row (in_proj / context), residual h += acc + bias,
+//                      SwiGLU (a block computes value column j and gate column j together: value * silu(gate) is stored)
+//   k_gen_norm<MODE>   one wave per row, run-time width: RMSNorm x gain (optionally AdaLN (1+scale) y + shift), LayerNorm
+//   k_gen_attn<DT>     flash-style attention for 16 queries x one head per wave: S^T = K Q^T and O^T = V^T P^T on MFMA, fp32 online
+//                      softmax (exp2 domain), head_dim padded to DT 16-wide tiles; self-attention visits only the band |j - i| <= window
+//   k_gen_embed        context = token_emb[sem_idx] + context_pos_emb (clamped indices set EDTTS_IDX_SEM)
+//   k_gen_tail<TAIL>   the sampler updates of the fused tails, elementwise: tail_apply (vector path) or the same helpers per element
+//
+// Activations are plain row-major [rows][features] fp32 in the workspace; weights are the state-dict's own [N][K] matrices.
+#pragma once
+
+namespace edtts_gen {
+
+enum { EPI_BIAS = 0, EPI_PE = 1, EPI_RESID = 2, EPI_SWIGLU = 3 };
+
+struct GemmArgs {
+  const float* X;     // [M][ldx]
+  const float* W;     // [N(x2 for SwiGLU)][K], K contiguous
+  const float* bias;  // [N] (SwiGLU: [2N], value half then gate half) or null
+  float* Y;           // [M][ldy]
+  const float* pe;    // EPI_PE: positional table [*][N], row = m % T
+  int M, N, K, ldx, ldy, T;
+  int vec_x, vec_w, vec_y;  // 16-byte loads / stores allowed (K % 4 == 0 and aligned rows; N, ldy % 4 == 0)
+};
+constexpr int kGBM = 64, kGBN = 64, kGBK = 16, kGLd = kGBK + 1;
+
+template <int EPI>
+__global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
+  __shared__ float xs[kGBM][kGLd];
+  __shared__ float ws[kGBN][kGLd];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fq = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.x * kGBM;
+  const int n0 = blockIdx.y * (EPI == EPI_SWIGLU ? kGBN / 2 : kGBN);
+  // loader: LDS row lr, k offsets lk .. lk + 3 of the current k-tile
+  const int lr = tid >> 2, lk = 4 * (tid & 3);
+  int wrow;
+  bool wok;
+  if (EPI == EPI_SWIGLU) {  // LDS rows 0..31: value rows n0.., rows 32..63: the matching gate rows N + n0..
+    const int j = n0 + (lr & 31);
+    wrow = (lr < 32 ? 0 : a.N) + j;
+    wok = j < a.N;
+  } else {
+    wrow = n0 + lr;
+    wok = wrow < a.N;
+  }
+  const int xrow = m0 + lr;
+  const bool xok = xrow < a.M;
+  const float* xp = a.X + (size_t)(xok ? xrow : 0) * a.ldx;
+  const float* wp = a.W + (size_t)(wok ? wrow : 0) * a.K;
+  // this wave's two weight sub-tiles (LDS rows) and its 32 activation rows
+  const int wn0 = EPI == EPI_SWIGLU ? 16 * (w & 1) : 32 * (w & 1);
+  const int wn1 = EPI == EPI_SWIGLU ? wn0 + 32 : wn0 + 16;
+  const int wm = 32 * (w >> 1);
+  f4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = splat(0.f);
+  for (int k0 = 0; k0 < a.K; k0 += kGBK) {
+    const int k = k0 + lk;
+    f4 xv = splat(0.f), wv = splat(0.f);
+    if (a.vec_x) {
+      if (xok && k < a.K) xv = ldg4(xp + k);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xv[r] = (xok && k + r < a.K) ? xp[k + r] : 0.f;
+    }
+    if (a.vec_w) {
+      if (wok && k < a.K) wv = ldg4(wp + k);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) wv[r] = (wok && k + r < a.K) ? wp[k + r] : 0.f;
+    }
+    __syncthreads();  // the previous k-tile has been consumed by every wave
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      xs[lr][lk + r] = xv[r];
+      ws[lr][lk + r] = wv[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < kGBK / 4; ++s) {
+      const int kk = 4 * s + g;  // A[n = fq][k = g], B[k = g][m = fq]
+      const float a0 = ws[wn0 + fq][kk], a1 = ws[wn1 + fq][kk];
+      const float b0 = xs[wm + fq][kk], b1 = xs[wm + 16 + fq][kk];
+      acc[0][0] = EDTTS_MFMA(a0, b0, acc[0][0]);
+      acc[0][1] = EDTTS_MFMA(a0, b1, acc[0][1]);
+      acc[1][0] = EDTTS_MFMA(a1, b0, acc[1][0]);
+      acc[1][1] = EDTTS_MFMA(a1, b1, acc[1][1]);
+    }
+  }
+  // epilogue: acc[t][u] lane (g, fq) holds Y[m = m0 + wm + 16u + fq][n = 4g + r of weight sub-tile t]
+  if (EPI == EPI_SWIGLU) {
+    const int n = n0 + wn0 + 4 * g;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int m = m0 + wm + 16 * u + fq;
+      if (m >= a.M) continue;
+      f4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool ok = n + r < a.N;
+        const float v = acc[0][u][r] + (a.bias && ok ? a.bias[n + r] : 0.f);
+        const float gt = acc[1][u][r] + (a.bias && ok ? a.bias[a.N + n + r] : 0.f);
+        o[r] = v * silu(gt);
+      }
+      float* yp = a.Y + (size_t)m * a.ldy + n;
+      if (a.vec_y && n + 3 < a.N) {
+        stg4(yp, o);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < a.N) yp[r] = o[r];
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int n = n0 + (t ? wn1 : wn0) + 4 * g;
+    if (n >= a.N) continue;
+    f4 bv = splat(0.f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[r] = (a.bias && n + r < a.N) ? a.bias[n + r] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int m = m0 + wm + 16 * u + fq;
+      if (m >= a.M) continue;
+      f4 o = acc[t][u] + bv;
+      float* yp = a.Y + (size_t)m * a.ldy + n;
+      const bool full = a.vec_y && n + 3 < a.N;
+      if (EPI == EPI_PE) {
+        const float* pp = a.pe + (size_t)(m % a.T) * a.N + n;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < a.N) o[r] += pp[r];
+      }
+      if (EPI == EPI_RESID) {  // h = h + (x W^T + b): the reference's residual order
+        if (full) {
+          stg4(yp, ldg4(yp) + o);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (n + r < a.N) yp[r] = yp[r] + o[r];
+        }
+      } else if (full) {
+        stg4(yp, o);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < a.N) yp[r] = o[r];
+      }
+    }
+  }
+}
+
+// ---- row norms -------------------------------------------------------------------------------------------------------------
+enum { NORM_RMS = 0, NORM_LAYER = 1 };
+struct NormArgs {
+  const float* x;
+  float* y;
+  const float *w, *b;  // gain; LayerNorm bias
+  const float* mod;    // AdaLN: [2W] per batch row = (1 + scale | shift), or null
+  int rows, W, ld, rows_per_b, mod_bstride;
+  float eps;
+};
+EDTTS_DEV float wave_allsum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_gen_norm(NormArgs a) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.rows) return;  // (no block-level synchronisation in this kernel)
+  const float* x = a.x + (size_t)row * a.ld;
+  float* y = a.y + (size_t)row * a.ld;
+  if (MODE == NORM_LAYER) {
+    float s = 0.f;
+    for (int j = lane; j < a.W; j += 64) s += x[j];
+    const float mu = wave_allsum(s) / (float)a.W;
+    float q = 0.f;
+    for (int j = lane; j < a.W; j += 64) {
+      const float d = x[j] - mu;
+      q += d * d;
+    }
+    const float rs = rsqrtf(wave_allsum(q) / (float)a.W + a.eps);
+    for (int j = lane; j < a.W; j += 64) y[j] = (x[j] - mu) * rs * a.w[j] + a.b[j];
+  } else {
+    float q = 0.f;
+    for (int j = lane; j < a.W; j += 64) q += x[j] * x[j];
+    const float rs = rsqrtf(wave_allsum(q) / (float)a.W + a.eps);
+    const float* md = a.mod ? a.mod + (size_t)(row / a.rows_per_b) * a.mod_bstride : nullptr;
+    for (int j = lane; j < a.W; j += 64) {
+      float v = x[j] * rs * a.w[j];
+      if (md) v = v * md[j] + md[a.W + j];
+      y[j] = v;
+    }
+  }
+}
+
+// ---- attention -------------------------------------------------------------------------------------------------------------
+struct AttnArgs {
+  const float* q;   // row b * Tq + i, feature head * DH + d
+  const float *k, *v;  // row b * Tk + j
+  float* o;         // like q
+  int ldq, ldkv, ldo, Tq, Tk, DH, window;  // window < 0: every key
+  float scale;      // log2(e) / sqrt(head_dim): scores in the exp2 domain
+};
+// One wave = 16 queries of one (utterance, head).  S^T tile (16 keys x 16 queries) = K Q^T: lane (g, i) holds the scores of query i
+// against keys 4g + r.  P^T then is the B operand of O^T += V^T P^T as it stands when MFMA step s contracts keys {4g + s}: the V^T
+// operand of lane (g, d) reads V[key 4g + s][d].  Query statistics live on lane & 15; the four lane groups combine with two xor shuffles.
+template <int DT>
+__global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
+  const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
+  const int qi = q0 + fq;
+  const bool qok = qi < a.Tq;
+  const float* qrow = a.q + (size_t)(b * a.Tq + (qok ? qi : 0)) * a.ldq + hd * a.DH;
+  float qv[4 * DT];
+#pragma unroll
+  for (int s = 0; s < 4 * DT; ++s) {
+    const int d = 4 * s + g;
+    qv[s] = (qok && d < a.DH) ? qrow[d] * a.scale : 0.f;
+  }
+  f4 acc[DT];
+#pragma unroll
+  for (int t = 0; t < DT; ++t) acc[t] = splat(0.f);
+  float m = -1e30f, l = 0.f;
+  int lo = 0, hi = a.Tk;
+  if (a.window >= 0) {
+    lo = q0 - a.window > 0 ? q0 - a.window : 0;
+    const int e = q0 + 16 + a.window;
+    hi = e < a.Tk ? e : a.Tk;
+  }
+  const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  for (int j0 = lo; j0 < hi; j0 += 16) {
+    const int kj = j0 + fq;
+    const bool kok = kj < hi;
+    const float* krow = kb + (size_t)(kok ? kj : 0) * a.ldkv;
+    f4 sc = splat(0.f);
+#pragma unroll
+    for (int s = 0; s < 4 * DT; ++s) {
+      const int d = 4 * s + g;
+      const float ka = (kok && d < a.DH) ? krow[d] : 0.f;
+      sc = EDTTS_MFMA(ka, qv[s], sc);
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = j0 + 4 * g + r;
+      const bool ok = key < hi && (a.window < 0 || (key - qi <= a.window && qi - key <= a.window));
+      sc[r] = ok ? sc[r] : -INFINITY;
+      mx = fmaxf(mx, sc[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mn = fmaxf(m, mx);
+    const float alpha = exp2f(m - mn);
+    f4 p;
+    float ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[r] = exp2f(sc[r] - mn);
+      ps += p[r];
+    }
+    ps += __shfl_xor(ps, 16);
+    ps += __shfl_xor(ps, 32);
+    l = l * alpha + ps;
+    m = mn;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) acc[t] *= alpha;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int key = j0 + 4 * g + s;
+      const float* vrow = vb + (size_t)(key < hi ? key : 0) * a.ldkv;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const int d = 16 * t + fq;
+        const float va = (key < hi && d < a.DH) ? vrow[d] : 0.f;
+        acc[t] = EDTTS_MFMA(va, p[s], acc[t]);
+      }
+    }
+  }
+  if (!qok) return;
+  const float inv = 1.0f / l;
+  float* orow = a.o + (size_t)(b * a.Tq + qi) * a.ldo + hd * a.DH;
+#pragma unroll
+  for (int t = 0; t < DT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int d = 16 * t + 4 * g + r;  // acc[t] lane (g, i) holds O^T[d][i]
+      if (d < a.DH) orow[d] = acc[t][r] * inv;
+    }
+}
+
+// ---- context embedding (token ids) ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_gen_embed(const int64_t* sem_idx, const float* tok, const float* cpe, float* ctx, int rows, int S,
+                                                   int H, int n_tok, unsigned* err) {
+  const size_t n = (size_t)rows * H;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / H;
+    const int c = (int)(i - row * H);
+    long tk = (long)sem_idx[row];
+    if (tk < 0 || tk >= n_tok) {  // nn.Embedding would raise IndexError: clamp (never fault) and leave a mark for the host
+      if (c == 0) atomicOr(err, (unsigned)EDTTS_IDX_SEM);
+      tk = tk < 0 ? 0 : n_tok - 1;
+    }
+    ctx[i] = tok[(size_t)tk * H + c] + cpe[(size_t)(row % S) * H + c];
+  }
+}
+
+// ---- sampler tails ---------------------------------------------------------------------------------------------------------------
+// The fused kernels' tail_apply (edtts_kernels.hip) on a stored eps: bitwise the same update.  vec: n % 4 == 0 and 16-byte aligned
+// tensors; otherwise one element per thread through the same per-element helpers (Philox: element e is lane e & 3 of draw e >> 2).
+template <int TAIL>
+EDTTS_DEV void tail_elem(const KArgs& a, size_t idx, float e) {
+  if (TAIL == TAIL_LMS) {
+    const float hn = a.lms.mode >= 2 ? a.h_new[idx] : 0.f, ho = a.lms.mode >= 3 ? a.h_old[idx] : 0.f;
+    float v0, vn;
+    lms_elem(a.x[idx], e, hn, ho, a.lms, v0, vn);
+    a.x0_hist[idx] = v0;
+    if (a.x0_all) a.x0_all[idx] = v0;
+    a.x_prev[idx] = vn;
+  } else if (TAIL == TAIL_VPRED) {
+    const float v = a.v_uncond ? cfg_combine(e, a.v_uncond[idx], a.vp.cfg) : e;
+    a.x_prev[idx] = vpred_elem(a.x[idx], v, a.vp);
+  } else if (TAIL == TAIL_DDPM) {
+    const unsigned long long ge = a.philox_base + idx;
+    const float nz = a.noise ? a.noise[idx] : philox_normal4(a.seed, a.step, ge >> 2)[(int)(ge & 3)];
+    const DdpmCoef cf{a.p_coef1, a.p_coef2, a.p_sd};
+    a.x_prev[idx] = ddpm_elem(a.x[idx], e, nz, cf);
+  } else {
+    float v0, vp;
+    ddim_elem(a.x[idx], e, a.c_s1m, a.c_sab, a.c_sabp, a.c_dir, v0, vp);
+    a.x0[idx] = v0;
+    a.x_prev[idx] = vp;
+  }
+}
+template <int TAIL>
+__global__ __launch_bounds__(256) void k_gen_tail(KArgs a, const float* eps, size_t n, int vec) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  if (vec) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += stride) tail_apply<TAIL>(a, 4 * i, ldg4(eps + 4 * i));
+  } else {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) tail_elem<TAIL>(a, i, eps[i]);
+  }
+}
+
+}  // namespace edtts_gen
+
+// =========================================================================================================
+// GenericLauncher: the static interface of Launcher / Launcher16 on the run-time-shape kernels
+// =========================================================================================================
+struct GenericLauncher {
+  using DdpmStep = DdpmStepArgs;
+  using LmsStep = LmsStepArgs;
+  static int set_attrs() { return EDTTS_OK; }  // (no kernel here needs more than 64 KiB of LDS)
+
+  static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+  template <int EPI>
+  static int gemm(hipStream_t st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
+                  const float* pe = nullptr, int T = 1) {
+    using namespace edtts_gen;
+    GemmArgs a;
+    a.X = X; a.W = W; a.bias = bias; a.Y = Y; a.pe = pe; a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldy = ldy; a.T = T;
+    a.vec_x = (K % 4 == 0) && (ldx % 4 == 0) && al16(X);
+    a.vec_w = (K % 4 == 0) && al16(W);
+    a.vec_y = (ldy % 4 == 0) && al16(Y);
+    const int nb = EPI == EPI_SWIGLU ? kGBN / 2 : kGBN;
+    hipLaunchKernelGGL(k_gen_gemm<EPI>, dim3((M + kGBM - 1) / kGBM, (N + nb - 1) / nb), dim3(256), 0, st, a);
+    LAUNCH_CHECK("k_gen_gemm");
+    return EDTTS_OK;
+  }
+  template <int MODE>
+  static int norm(hipStream_t st, const float* x, float* y, int rows, int W, const float* w, const float* b, float eps,
+                  const float* mod = nullptr, int rows_per_b = 1, int mod_bstride = 0) {
+    edtts_gen::NormArgs a{x, y, w, b, mod, rows, W, W, rows_per_b, mod_bstride, eps};
+    hipLaunchKernelGGL(edtts_gen::k_gen_norm<MODE>, dim3((rows + 3) / 4), dim3(256), 0, st, a);
+    LAUNCH_CHECK("k_gen_norm");
+    return EDTTS_OK;
+  }
+  static int attn(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, float* o,
+                  int Tq, int Tk, int window) {
+    edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH)};
+    const dim3 grid((Tq + 15) / 16, lo.HEADS, B);
+    switch ((lo.DH + 15) / 16) {
+#define EDTTS_GEN_ATTN(DT) case DT: hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a); break
+      EDTTS_GEN_ATTN(1); EDTTS_GEN_ATTN(2); EDTTS_GEN_ATTN(3); EDTTS_GEN_ATTN(4);
+      EDTTS_GEN_ATTN(5); EDTTS_GEN_ATTN(6); EDTTS_GEN_ATTN(7); EDTTS_GEN_ATTN(8);
+#undef EDTTS_GEN_ATTN
+      default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
+    }
+    LAUNCH_CHECK("k_gen_attn");
+    return EDTTS_OK;
+  }
+
+  // context rows (token_emb gather or sem_proj) + context PE, then per layer kv_down -> kv_norm -> kv_up into the K|V cache
+  static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
+                 const float* sem_feat, hipStream_t st) {
+    using namespace edtts_gen;
+    const int rows = B * S, H = lo.H, R = lo.R;
+    float* c = wsb + ws.g_ctx;
+    if (sem_feat) {
+      TRY_G(gemm<EPI_PE>(st, sem_feat, lo.SD, blob + lo.semp, blob + lo.semp_b, c, H, rows, H, lo.SD, blob + lo.cpe, S));
+    } else {
+      unsigned* err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
+      size_t nb = ((size_t)rows * H + 255) / 256;
+      if (nb > 4096) nb = 4096;
+      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, c, rows, S, H, lo.NTOK, err);
+      LAUNCH_CHECK("k_gen_embed");
+    }
+    for (int l = 0; l < lo.L; ++l) {
+      const LayerLayout& y = lo.layer[l];
+      TRY_G(gemm<EPI_BIAS>(st, c, H, blob + y.kvd, nullptr, wsb + ws.g_cr, R, rows, R, H));
+      TRY_G(norm<NORM_RMS>(st, wsb + ws.g_cr, wsb + ws.g_cr, rows, R, blob + y.kvn, nullptr, 1e-6f));
+      TRY_G(gemm<EPI_BIAS>(st, wsb + ws.g_cr, R, blob + y.kvu, nullptr, wsb + ws.g_kv + (size_t)l * rows * 2 * H, 2 * H, rows, 2 * H, R));
+    }
+    return EDTTS_OK;
+  }
+
+  template <int COW = 0>
+  static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
+                     const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
+                     const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
+                     const VpredStepArgs* vp = nullptr) {
+    using namespace edtts_gen;
+    const int M = B * T, H = lo.H, FH = lo.FM * lo.H, MEL = lo.MEL;
+    float *h = wsb + ws.h, *xn = wsb + ws.g_xn, *big = wsb + ws.g_big, *att = wsb + ws.g_att;
+    const size_t row = (size_t)2 * 2 * H;  // one layer's (norm1 | norm3) AdaLN rows
+    TRY_G(gemm<EPI_PE>(st, x, MEL, blob + lo.inp, blob + lo.inp_b, h, H, M, H, MEL, blob + lo.pe, T));
+    for (int l = 0; l < lo.L; ++l) {
+      const LayerLayout& y = lo.layer[l];
+      const float* kv = wsb + ws.g_kv + (size_t)l * B * S * 2 * H;
+      // self-attention branch
+      TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
+      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, big, 3 * H, M, 3 * H, H));
+      TRY_G(attn(st, lo, B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, window));
+      TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
+      // cross-attention branch
+      TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
+      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, big, H, M, H, H));
+      TRY_G(attn(st, lo, B, big, H, kv, kv + H, 2 * H, att, T, S, -1));
+      TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_op, nullptr, h, H, M, H, H));
+      // feed-forward branch
+      TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cond_bstride));
+      TRY_G(gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, big, FH, M, FH, H));
+      TRY_G(gemm<EPI_RESID>(st, big, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH));
+    }
+    TRY_G(norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
+    float* e = tail == TAIL_EPS ? eps : wsb + ws.g_eps;
+    TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, e, MEL, M, MEL, H));
+    if (tail == TAIL_EPS) return EDTTS_OK;
+    KArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.x_prev = x_prev;
+    bool vec = al16(x) && al16(x_prev) && al16(e);
+    if (tail == TAIL_LMS) {
+      a.lms = lms->k; a.h_new = lms->h_new; a.h_old = lms->h_old; a.x0_hist = lms->x0_hist; a.x0_all = lms->x0_all;
+      vec = vec && al16(a.h_new) && al16(a.h_old) && al16(a.x0_hist) && al16(a.x0_all);
+    } else if (tail == TAIL_VPRED) {
+      a.vp = vp->k; a.v_uncond = vp->v_uncond;
+      vec = vec && al16(a.v_uncond);
+    } else if (tail == TAIL_DDPM) {
+      a.p_coef1 = coef[0]; a.p_coef2 = coef[1]; a.p_sd = coef[2];
+      a.noise = ddpm->noise; a.seed = ddpm->seed; a.philox_base = ddpm->base; a.step = ddpm->step;
+      vec = vec && al16(a.noise) && (a.philox_base & 3) == 0;
+    } else {
+      a.x0 = x0;
+      a.c_s1m = coef[0]; a.c_sab = coef[1]; a.c_sabp = coef[2]; a.c_dir = coef[3];
+      vec = vec && al16(x0);
+    }
+    const size_t n = (size_t)M * MEL;
+    vec = vec && n % 4 == 0;
+    size_t nb = ((vec ? n / 4 : n) + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    if (nb < 1) nb = 1;
+    switch (tail) {
+      case TAIL_LMS: hipLaunchKernelGGL(k_gen_tail<TAIL_LMS>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
+      case TAIL_VPRED: hipLaunchKernelGGL(k_gen_tail<TAIL_VPRED>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
+      case TAIL_DDPM: hipLaunchKernelGGL(k_gen_tail<TAIL_DDPM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
+      default: hipLaunchKernelGGL(k_gen_tail<TAIL_DDIM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
+    }
+    LAUNCH_CHECK("k_gen_tail");
+    return EDTTS_OK;
+  }
+};

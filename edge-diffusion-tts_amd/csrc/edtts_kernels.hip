@@ -13,6 +13,7 @@
 //                   TAIL_DDIM: final LayerNorm + out_proj + DDIM update                 schedule.py:157-202
 //   k_ddim / k_ddpm   standalone elementwise updates (HBM-bound)                       schedule.py:157-238
 //   k_dsconv_*    depthwise-separable Conv1d + GroupNorm + GELU (standalone layer)     conv.py:25-64
+//   k_gen_*       the generic run-time-shape fp32 path (edtts_generic.h): GEMM, row norms, attention, sampler tails
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -99,8 +100,10 @@ struct LayerLayout {
   size_t s_qkv;   // stream: QKV of this layer            [3HT n-tiles][HT]
   size_t s_body;  // stream: proj | q_proj | out_proj | ffn   (followed in memory by s_qkv of layer+1 / s_outp)
   size_t s_ffn;   // where the ffn part of s_body starts (entry point of the split FFN kernel)
+  size_t g_proj, g_qp, g_op, g_up, g_down;  // generic layout: the state-dict's [N][K] matrices (qkv at s_qkv)
 };
 struct Layout {
+  int GEN;   // 1: the generic run-time-shape kernels (edtts_generic.h): plain [N][K] weights, no fragment stream
   int BF16;  // 1: bf16 contractions (edtts_bf16.h): the fragment stream holds bf16 fragments of 16 outputs x 32 inputs
   int H, HEADS, MEL, L, DH, DHP, HT, MT, R, RT, SD, NTOK, MAXPOS, MAXCPOS, NSTEP;
   int FM;  // ffn_mult: the FFN's hidden width is FM * H (layers/transformer.py:32-45: Linear(H, 2 FM H) -> SwiGLU -> Linear(FM H, H))
@@ -116,19 +119,41 @@ constexpr size_t kFrag = 256;  // floats per fragment (64 lanes x float4)
 
 static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
+static bool has_instance(const Layout& lo);
+static int make_generic_layout(const EdttsDims* d, Layout* lo);
+
 static int make_layout(const EdttsDims* d, Layout* lo) {
   if (!d) return fail(EDTTS_ERR_ARG, "dims is NULL");
+  // kernel-path bits (include/edtts.h): decided here, once; packing, workspace sizing and the dispatch follow lo->GEN
+  const int kbits = d->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  const int dtype = d->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  if (kbits == (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO))
+    return fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=0x%x: EDTTS_KERNELS_GENERIC and EDTTS_KERNELS_AUTO are exclusive", d->compute_dtype);
+  if (kbits == EDTTS_KERNELS_GENERIC && dtype == EDTTS_BF16)
+    return fail(EDTTS_ERR_UNSUPPORTED, "the generic kernels are fp32 only (compute_dtype=0x%x)", d->compute_dtype);
+  if (kbits && dtype == EDTTS_F32) {
+    bool fused = false;
+    if (kbits == EDTTS_KERNELS_AUTO && d->ffn_mult >= 1 && d->ffn_mult <= 4 && d->layers >= 1 && d->layers <= kMaxLayers &&
+        d->hidden % 32 == 0 && d->n_mels % 16 == 0 && d->semantic_dim % 16 == 0 && d->heads >= 1 && d->hidden % d->heads == 0) {
+      Layout probe;
+      memset(&probe, 0, sizeof(probe));
+      probe.H = d->hidden; probe.HEADS = d->heads; probe.MEL = d->n_mels;
+      fused = has_instance(probe);
+    }
+    if (!fused) return make_generic_layout(d, lo);
+  }
+  // (AUTO with bf16 is the compiled bf16 path: it never falls back to fp32)
   if (d->ffn_mult < 1 || d->ffn_mult > 4) return fail(EDTTS_ERR_UNSUPPORTED, "ffn_mult=%d outside [1, 4]", d->ffn_mult);
   if (d->layers < 1 || d->layers > kMaxLayers) return fail(EDTTS_ERR_UNSUPPORTED, "layers=%d out of [1,%d]", d->layers, kMaxLayers);
   if (d->hidden % 32 || d->n_mels % 16 || d->semantic_dim % 16 || d->heads < 1 || d->hidden % d->heads)
     return fail(EDTTS_ERR_UNSUPPORTED, "hidden=%d heads=%d n_mels=%d semantic_dim=%d: need hidden%%32==0, n_mels%%16==0, semantic_dim%%16==0",
                 d->hidden, d->heads, d->n_mels, d->semantic_dim);
-  if (d->compute_dtype != EDTTS_F32 && d->compute_dtype != EDTTS_BF16)
+  if (dtype != EDTTS_F32 && dtype != EDTTS_BF16)
     return fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=%d (0 = f32, 1 = bf16)", d->compute_dtype);
-  if (d->compute_dtype == EDTTS_BF16 && d->hidden != 32 * d->heads)
+  if (dtype == EDTTS_BF16 && d->hidden != 32 * d->heads)
     return fail(EDTTS_ERR_UNSUPPORTED, "the bf16 instance needs head_dim 32 (hidden=%d heads=%d)", d->hidden, d->heads);
   memset(lo, 0, sizeof(*lo));
-  lo->BF16 = d->compute_dtype == EDTTS_BF16;
+  lo->BF16 = dtype == EDTTS_BF16;
   lo->H = d->hidden; lo->HEADS = d->heads; lo->MEL = d->n_mels; lo->L = d->layers;
   lo->DH = lo->H / lo->HEADS; lo->DHP = (lo->DH + 15) / 16 * 16; lo->HT = lo->H / 16; lo->MT = lo->MEL / 16;
   lo->R = lo->H / 2; lo->RT = lo->R / 16; lo->SD = d->semantic_dim; lo->NTOK = d->codebook_size;
@@ -177,6 +202,46 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
   }
   lo->s_outp = o; o += MT * HT * kFrag;
   o += 4 * HT * kFrag;  // the stream stages two phases (+ slot padding) past the last consumed fragment
+  }
+  lo->total = align64(o);
+  return EDTTS_OK;
+}
+
+// Generic layout: the tables the conditioning / embedding code reads sit where the fused layout keeps them (time MLP and AdaLN
+// projections transposed for k_cond_mlp / k_cond_ada); every other Linear is the state-dict's [N][K] matrix as it is.
+static int make_generic_layout(const EdttsDims* d, Layout* lo) {
+  if (d->ffn_mult < 1 || d->ffn_mult > 4) return fail(EDTTS_ERR_UNSUPPORTED, "ffn_mult=%d outside [1, 4]", d->ffn_mult);
+  if (d->layers < 1 || d->layers > kMaxLayers) return fail(EDTTS_ERR_UNSUPPORTED, "layers=%d out of [1,%d]", d->layers, kMaxLayers);
+  if (d->heads < 1 || d->hidden < 2 || d->hidden % d->heads || d->hidden % 2)
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: hidden=%d heads=%d: need hidden %% heads == 0 and an even hidden", d->hidden, d->heads);
+  if (d->hidden / d->heads > 128)
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128 (hidden=%d heads=%d)", d->hidden / d->heads, d->hidden, d->heads);
+  if (d->n_mels < 1 || d->semantic_dim < 1 || d->codebook_size < 1 || d->max_pos < 1 || d->max_ctx_pos < 1 || d->n_step_emb < 1)
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: n_mels=%d semantic_dim=%d codebook_size=%d and the table sizes must be >= 1",
+                d->n_mels, d->semantic_dim, d->codebook_size);
+  memset(lo, 0, sizeof(*lo));
+  lo->GEN = 1;
+  lo->H = d->hidden; lo->HEADS = d->heads; lo->MEL = d->n_mels; lo->L = d->layers;
+  lo->DH = lo->H / lo->HEADS; lo->DHP = (lo->DH + 15) / 16 * 16;
+  lo->R = lo->H / 2; lo->SD = d->semantic_dim; lo->NTOK = d->codebook_size;
+  lo->MAXPOS = d->max_pos; lo->MAXCPOS = d->max_ctx_pos; lo->NSTEP = d->n_step_emb; lo->FM = d->ffn_mult;
+  const size_t H = lo->H, R = lo->R, SD = lo->SD, MEL = lo->MEL, FH = (size_t)lo->FM * lo->H;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
+  lo->tok = take((size_t)lo->NTOK * H);
+  lo->semp = take(H * SD); lo->semp_b = take(H);
+  lo->t1T = take(H * H); lo->t1b = take(H); lo->t3T = take(H * H); lo->t3b = take(H);
+  lo->step = take((size_t)lo->NSTEP * H);
+  lo->inp = take(H * MEL); lo->inp_b = take(H);
+  lo->pe = take((size_t)lo->MAXPOS * H); lo->cpe = take((size_t)lo->MAXCPOS * H);
+  lo->fnw = take(H); lo->fnb = take(H); lo->s_outp = take(MEL * H); lo->outp_b = take(MEL); lo->freqs = take(H / 2);
+  for (int l = 0; l < lo->L; ++l) {
+    LayerLayout& y = lo->layer[l];
+    y.n1w = take(H); y.ada1T = take(H * 2 * H); y.ada1b = take(2 * H); y.proj_b = take(H); y.n2w = take(H);
+    y.n3w = take(H); y.ada3T = take(H * 2 * H); y.ada3b = take(2 * H); y.up_b = take(2 * FH); y.down_b = take(H);
+    y.kvd = take(R * H); y.kvn = take(R); y.kvu = take(2 * H * R);
+    y.s_qkv = take(3 * H * H); y.g_proj = take(H * H); y.g_qp = take(H * H); y.g_op = take(H * H);
+    y.g_up = take(2 * FH * H); y.g_down = take(H * FH);
   }
   lo->total = align64(o);
   return EDTTS_OK;
@@ -2090,6 +2155,8 @@ __global__ __launch_bounds__(kDfTWide * 4) void k_dsconv_grouped(const float* __
 // =========================================================================================================
 struct Workspace {
   size_t err, h, q, k, vT, kc, vcT, cond, total;  // offsets in floats (err = 0: the index-error word heads every workspace)
+  size_t g_xn, g_big, g_att, g_ctx, g_cr, g_kv, g_eps;  // generic path: norm output, QKV / FFN hidden, attention output, context
+                                                       // rows, kv_down rows, per-layer K|V cache, eps before the sampler tail
   int Tp, Sp, VR;
   unsigned* errp;  // where kernels record clamped indices: word 0 of the CALLER's workspace, also for a sub-batch's slice of it
 };
@@ -2116,6 +2183,20 @@ static int wave_frames(const Layout& lo) {
 
 static void make_workspace(const Layout& lo, int B, int T, int S, int cond_rows, Workspace* w) {
   const size_t H = lo.H;
+  if (lo.GEN) {  // plain row-major activations, no padding
+    memset(w, 0, sizeof(*w));
+    w->Tp = T; w->Sp = S; w->VR = lo.H;
+    const size_t M = (size_t)B * T, CS = (size_t)B * S, FH = (size_t)lo.FM * H;
+    size_t o = 0;
+    auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
+    w->err = take(64);
+    w->h = take(M * H); w->g_xn = take(M * H); w->g_big = take(M * (FH > 3 * H ? FH : 3 * H)); w->g_att = take(M * H);
+    w->g_ctx = take(CS * H); w->g_cr = take(CS * lo.R); w->g_kv = take((size_t)lo.L * CS * 2 * H); w->g_eps = take(M * lo.MEL);
+    w->cond = take((size_t)cond_rows * lo.L * 2 * 2 * H + (size_t)cond_rows * H);
+    w->total = o;
+    w->errp = nullptr;
+    return;
+  }
   const int wf = wave_frames(lo);
   w->Tp = (T + wf - 1) / wf * wf;
   w->Sp = (S + 31) / 32 * 32;
@@ -2193,6 +2274,7 @@ static void plan_sub(const Layout& lo, int B, int T, int S, int cond_rows, int n
 // 30.31 at four; B=256, T=512 fp32 (4 rounds) the same at two and four -- but two halves of ONE round each where the batch has only two
 // rounds (B=128, T=512 fp32: 7.88 ms in one piece, 7.74 cut).
 static int substreams_for(const Layout& lo, int B, int T, int S) {
+  if (lo.GEN) return 1;  // the generic path runs on the caller's stream alone: a captured graph has no parallel branches
   Workspace w;
   make_workspace(lo, 1, T, S, 1, &w);
   const long waves = (long)B * (w.Tp / 32), slots = device_simds();
@@ -2739,13 +2821,21 @@ struct Launcher16 {
   }
 };
 
-// compiled decoder shapes: (hidden, heads, n_mels)
+#define TRY_G(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+#include "edtts_generic.h"
+
+// compiled decoder shapes: (hidden, heads, n_mels).  EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, body) runs `body` with LN = the fused
+// launcher of lo's shape, or the statement MISS16 / MISS32 when none is compiled; EDTTS_DISPATCH adds the generic launcher (lo.GEN)
+// and has_instance() -- the predicate make_layout decides EDTTS_KERNELS_AUTO with -- walks the same chain.
+static int no_instance16(const Layout& lo);
+static int no_instance32(const Layout& lo);
 #ifdef EDTTS_FAST_BUILD  // scratch builds (-DEDTTS_EXPERIMENTS): the default decoder's fp32 instance only
-#define EDTTS_DISPATCH(lo, ...)                                                                          \
-  do {                                                                                                   \
+#define EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, ...)                                                       \
     if (!(lo).BF16 && (lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80, EDTTS_NF_DEFAULT>>; __VA_ARGS__; } \
-    else return fail(EDTTS_ERR_UNSUPPORTED, "EDTTS_FAST_BUILD: only the 160/4/80 fp32 instance is compiled");  \
-  } while (0)
+    else if ((lo).BF16) { MISS16; }                                                                      \
+    else { MISS32; }
+static int no_instance16(const Layout&) { return fail(EDTTS_ERR_UNSUPPORTED, "EDTTS_FAST_BUILD: only the 160/4/80 fp32 instance is compiled"); }
+static int no_instance32(const Layout&) { return fail(EDTTS_ERR_UNSUPPORTED, "EDTTS_FAST_BUILD: only the 160/4/80 fp32 instance is compiled"); }
 #else
 // Further fp32 shapes are a BUILD option, not a source edit: EDTTS_INSTANCES="192x6x80,128x4x80" in the environment of
 // __graft_entry__.build() becomes -DEDTTS_EXTRA_INSTANCES(lo,...)=EDTTS_X(lo,192,6,80,__VA_ARGS__)... (hidden % 32 == 0, head_dim % 16
@@ -2761,24 +2851,36 @@ struct Launcher16 {
 #endif
 #define EDTTS_X16(lo, HH, HD, MM, ...) else if ((lo).H == HH && (lo).HEADS == HD && (lo).MEL == MM) { using LN = Launcher16<edtts16::Cfg16<HH, HD, MM>>; __VA_ARGS__; }
 #define EDTTS_X(lo, HH, HD, MM, ...) else if ((lo).H == HH && (lo).HEADS == HD && (lo).MEL == MM) { using LN = Launcher<Cfg<HH, HD, MM>>; __VA_ARGS__; }
-#define EDTTS_DISPATCH(lo, ...)                                                                          \
-  do {                                                                                                   \
+#define EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, ...)                                                       \
     if ((lo).BF16) {                                                                                     \
       if ((lo).H == 256 && (lo).HEADS == 8 && (lo).MEL == 80) { using LN = Launcher16<edtts16::Cfg16<256, 8, 80, EDTTS16_NF>>; __VA_ARGS__; } \
       else if ((lo).H == 64 && (lo).HEADS == 2 && (lo).MEL == 80) { using LN = Launcher16<edtts16::Cfg16<64, 2, 80>>; __VA_ARGS__; } \
       EDTTS_EXTRA_INSTANCES16(lo, __VA_ARGS__)                                                           \
-      else return fail(EDTTS_ERR_UNSUPPORTED, "no bf16 kernel instance for hidden=%d heads=%d n_mels=%d "  \
-                       "(compiled: 256/8/80, 64/2/80" EDTTS_EXTRA_NAMES16 "; more: EDTTS_INSTANCES_BF16 at build time)", (lo).H, (lo).HEADS, (lo).MEL); \
+      else { MISS16; }                                                                                   \
     }                                                                                                    \
     else if ((lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80, EDTTS_NF_DEFAULT>>; __VA_ARGS__; } \
     else if ((lo).H == 256 && (lo).HEADS == 8 && (lo).MEL == 80) { using LN = Launcher<Cfg<256, 8, 80>>; __VA_ARGS__; }     \
     else if ((lo).H == 32 && (lo).HEADS == 2 && (lo).MEL == 80) { using LN = Launcher<Cfg<32, 2, 80>>; __VA_ARGS__; }       \
     else if ((lo).H == 64 && (lo).HEADS == 4 && (lo).MEL == 16) { using LN = Launcher<Cfg<64, 4, 16>>; __VA_ARGS__; }       \
     EDTTS_EXTRA_INSTANCES(lo, __VA_ARGS__)                                                               \
-    else return fail(EDTTS_ERR_UNSUPPORTED, "no kernel instance for hidden=%d heads=%d n_mels=%d "        \
-                     "(compiled: 160/4/80, 256/8/80, 32/2/80, 64/4/16" EDTTS_EXTRA_NAMES "; more: EDTTS_INSTANCES at build time)", (lo).H, (lo).HEADS, (lo).MEL);   \
-  } while (0)
+    else { MISS32; }
+static int no_instance16(const Layout& lo) {
+  return fail(EDTTS_ERR_UNSUPPORTED, "no bf16 kernel instance for hidden=%d heads=%d n_mels=%d "
+              "(compiled: 256/8/80, 64/2/80" EDTTS_EXTRA_NAMES16 "; more: EDTTS_INSTANCES_BF16 at build time)", lo.H, lo.HEADS, lo.MEL);
+}
+static int no_instance32(const Layout& lo) {
+  return fail(EDTTS_ERR_UNSUPPORTED, "no kernel instance for hidden=%d heads=%d n_mels=%d "
+              "(compiled: 160/4/80, 256/8/80, 32/2/80, 64/4/16" EDTTS_EXTRA_NAMES "; more: EDTTS_INSTANCES at build time)", lo.H, lo.HEADS, lo.MEL);
+}
 #endif
+#define EDTTS_DISPATCH(lo, ...)                                                                          \
+  do {                                                                                                   \
+    if ((lo).GEN) { using LN = GenericLauncher; __VA_ARGS__; }                                           \
+    else { EDTTS_FUSED_CHAIN(lo, return no_instance16(lo), return no_instance32(lo), __VA_ARGS__) }      \
+  } while (0)
+static bool has_instance(const Layout& lo) {
+  EDTTS_FUSED_CHAIN(lo, return false, return false, return true)
+}
 
 static int launch_cond(const Layout& lo, const float* blob, const int64_t* t, const int64_t* step_idx, const int64_t* t_host,
                        int rows, float* cond, float* wsb, hipStream_t st) {
@@ -2834,7 +2936,7 @@ int edtts_workspace_bytes(const EdttsDims* dims, int B, int T, int S, int cond_r
   SubBatches one, two;
   plan_sub(lo, B, T, S, cond_rows, 1, &one);
   size_t total = one.total;
-  for (int n = 2; n <= kMaxSub && n <= B; ++n) {
+  for (int n = 2; n <= kMaxSub && n <= B && !lo.GEN; ++n) {
     plan_sub(lo, B, T, S, cond_rows, n, &two);
     if (two.total > total) total = two.total;
   }
@@ -2868,6 +2970,53 @@ static int transpose_f(hipStream_t st, const float* src, float* dst, int N, int 
 }
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
+// generic layout (make_generic_layout): copies, and the transposes the conditioning kernels read
+static int pack_generic(const Layout& lo, const void* const* slots, float* blob, hipStream_t st) {
+  auto G = [&](int i) { return (const float*)slots[i]; };
+  const size_t H = lo.H, R = lo.R, SD = lo.SD, MEL = lo.MEL, FH = (size_t)lo.FM * lo.H;
+  TRY(copy_f(st, G(G_TOK), blob + lo.tok, (size_t)lo.NTOK * H));
+  TRY(copy_f(st, G(G_SEMP_W), blob + lo.semp, H * SD));
+  TRY(copy_f(st, G(G_SEMP_B), blob + lo.semp_b, H));
+  TRY(transpose_f(st, G(G_T1_W), blob + lo.t1T, (int)H, (int)H));
+  TRY(copy_f(st, G(G_T1_B), blob + lo.t1b, H));
+  TRY(transpose_f(st, G(G_T3_W), blob + lo.t3T, (int)H, (int)H));
+  TRY(copy_f(st, G(G_T3_B), blob + lo.t3b, H));
+  TRY(copy_f(st, G(G_STEP), blob + lo.step, (size_t)lo.NSTEP * H));
+  TRY(copy_f(st, G(G_INP_W), blob + lo.inp, H * MEL));
+  TRY(copy_f(st, G(G_INP_B), blob + lo.inp_b, H));
+  TRY(copy_f(st, G(G_PE), blob + lo.pe, (size_t)lo.MAXPOS * H));
+  TRY(copy_f(st, G(G_CPE), blob + lo.cpe, (size_t)lo.MAXCPOS * H));
+  TRY(copy_f(st, G(G_FN_W), blob + lo.fnw, H));
+  TRY(copy_f(st, G(G_FN_B), blob + lo.fnb, H));
+  TRY(copy_f(st, G(G_OUT_W), blob + lo.s_outp, MEL * H));
+  TRY(copy_f(st, G(G_OUT_B), blob + lo.outp_b, MEL));
+  TRY(copy_f(st, G(G_FREQS), blob + lo.freqs, H / 2));
+  for (int l = 0; l < lo.L; ++l) {
+    const LayerLayout& y = lo.layer[l];
+    auto W = [&](int i) { return (const float*)slots[G_COUNT + l * L_COUNT + i]; };
+    TRY(copy_f(st, W(L_N1_W), blob + y.n1w, H));
+    TRY(transpose_f(st, W(L_N1P_W), blob + y.ada1T, 2 * (int)H, (int)H));
+    TRY(copy_f(st, W(L_N1P_B), blob + y.ada1b, 2 * H));
+    TRY(copy_f(st, W(L_QKV_W), blob + y.s_qkv, 3 * H * H));
+    TRY(copy_f(st, W(L_PROJ_W), blob + y.g_proj, H * H));
+    TRY(copy_f(st, W(L_PROJ_B), blob + y.proj_b, H));
+    TRY(copy_f(st, W(L_N2_W), blob + y.n2w, H));
+    TRY(copy_f(st, W(L_QP_W), blob + y.g_qp, H * H));
+    TRY(copy_f(st, W(L_KVD_W), blob + y.kvd, R * H));
+    TRY(copy_f(st, W(L_KVN_W), blob + y.kvn, R));
+    TRY(copy_f(st, W(L_KVU_W), blob + y.kvu, 2 * H * R));
+    TRY(copy_f(st, W(L_OP_W), blob + y.g_op, H * H));
+    TRY(copy_f(st, W(L_N3_W), blob + y.n3w, H));
+    TRY(transpose_f(st, W(L_N3P_W), blob + y.ada3T, 2 * (int)H, (int)H));
+    TRY(copy_f(st, W(L_N3P_B), blob + y.ada3b, 2 * H));
+    TRY(copy_f(st, W(L_UP_W), blob + y.g_up, 2 * FH * H));
+    TRY(copy_f(st, W(L_UP_B), blob + y.up_b, 2 * FH));
+    TRY(copy_f(st, W(L_DOWN_W), blob + y.g_down, H * FH));
+    TRY(copy_f(st, W(L_DOWN_B), blob + y.down_b, H));
+  }
+  return EDTTS_OK;
+}
+
 int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_slots, void* packed, void* stream) {
   Layout lo;
   TRY(make_layout(dims, &lo));
@@ -2881,6 +3030,7 @@ int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_sl
   const int H = lo.H, HT = lo.HT, MT = lo.MT, R = lo.R, RT = lo.RT, SD = lo.SD, DH = lo.DH, DHP = lo.DHP, FM = lo.FM;
   const int KPT = lo.HEADS * DHP / 16;
   HIP_TRY(hipMemsetAsync(blob, 0, lo.total * sizeof(float), st));
+  if (lo.GEN) return pack_generic(lo, slots, blob, st);
   TRY(copy_f(st, G(G_TOK), blob + lo.tok, (size_t)lo.NTOK * H));
   TRY(pack_gemm(st, G(G_SEMP_W), SD, H, SD, HT, SD / 16, 0, 0, 0, DH, DHP, blob + lo.semp));
   TRY(copy_f(st, G(G_SEMP_B), blob + lo.semp_b, H));
@@ -3127,6 +3277,19 @@ __global__ __launch_bounds__(256) void k_inpaint_inject(float* x, const float* k
   }
 }
 
+// ... one element per thread, for shapes whose rows are not float4-aligned (generic path, n_mels % 4 != 0): the same values (element e
+// of the [B, overlap, MEL] noise tensor is lane e & 3 of Philox draw e >> 2)
+__global__ __launch_bounds__(256) void k_inpaint_inject1(float* x, const float* known, const float* noise, int B, int T, int ov, int MEL,
+                                                         float c_known, float c_noise, unsigned long long seed, unsigned step) {
+  const size_t per = (size_t)ov * MEL, n = (size_t)B * per;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / per, r = i - b * per;
+    float o = known[i];
+    if (c_noise != 0.f) o = qsample_elem(o, c_known, noise ? noise[i] : philox_normal4(seed, step, i >> 2)[(int)(i & 3)], c_noise);
+    x[(b * T) * MEL + r] = o;
+  }
+}
+
 int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
                          const float* sem_features, const float* zero_features, float* x, int num_steps,
                          const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel, int overlap_len,
@@ -3147,11 +3310,12 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
   make_workspace(lo, B, T, S, num_steps, &ws);
   TRY(launch_cond(lo, blob, t_all, step_all, nullptr, num_steps, wsb + ws.cond, wsb, st));
   const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  const bool inject_vec = ((size_t)overlap_len * lo.MEL) % 4 == 0 && ((size_t)T * lo.MEL) % 4 == 0;
   auto inject = [&](float ck, float cn, int step) {
-    const size_t n4 = (size_t)B * overlap_len * lo.MEL / 4;
+    const size_t n4 = (size_t)B * overlap_len * lo.MEL / (inject_vec ? 4 : 1);
     size_t bx = (n4 + 255) / 256;
     if (bx > 2048) bx = 2048;
-    hipLaunchKernelGGL(k_inpaint_inject, dim3((unsigned)bx), dim3(256), 0, st, x, known_mel,
+    hipLaunchKernelGGL(inject_vec ? k_inpaint_inject : k_inpaint_inject1, dim3((unsigned)bx), dim3(256), 0, st, x, known_mel,
                        noise_k ? noise_k + (size_t)step * B * overlap_len * lo.MEL : nullptr, B, T, overlap_len, lo.MEL, ck, cn,
                        (unsigned long long)seed, kStreamInpaintStep + (unsigned)step);
   };

@@ -36,17 +36,25 @@ def _attach(root: nn.Module, key: str, tensor: torch.Tensor, is_buffer: bool) ->
 
 
 class EdgeDiffusionDecoder(nn.Module):
-    def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32"):
+    def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled"):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
         residual stream / norms / softmax in fp32 (the reference's AMP precedent, utils/speed_utils.py:70; compiled for
-        head_dim 32, i.e. BASELINE config 3: hidden=256, heads=8).  Parameters stay fp32 either way."""
+        head_dim 32, i.e. BASELINE config 3: hidden=256, heads=8).  Parameters stay fp32 either way.
+        ``kernels``: "compiled" (default) runs only shapes that are compiled kernel instances; "generic" runs every shape on the
+        run-time-shape fp32 kernels; "auto" takes the compiled instance when there is one and the generic kernels otherwise
+        (include/edtts.h: EDTTS_KERNELS_*).  The generic kernels are fp32 only."""
         super().__init__()
         self.cfg = cfg
         if compute_dtype not in native.COMPUTE_DTYPES:
             raise ValueError(f"compute_dtype must be one of {sorted(native.COMPUTE_DTYPES)}, got {compute_dtype!r}")
         self.compute_dtype = compute_dtype
+        if kernels not in native.KERNELS:
+            raise ValueError(f"kernels must be one of {sorted(native.KERNELS)}, got {kernels!r}")
+        if kernels != "compiled" and native.COMPUTE_DTYPES[compute_dtype] != native.COMPUTE_DTYPES["f32"]:
+            raise ValueError(f"kernels={kernels!r} needs compute_dtype='f32' (the generic kernels are fp32 only), got {compute_dtype!r}")
+        self.kernels = kernels
         self.max_len, self.max_context_len, self.n_step_emb = int(max_len), int(max_context_len), 16
         H = cfg.hidden
         for key, shape in decoder_shapes(cfg, self.max_len, self.max_context_len, self.n_step_emb).items():
@@ -142,7 +150,8 @@ class EdgeDiffusionDecoder(nn.Module):
         c = self.cfg
         window = -1 if c.attn_window_size is None else int(c.attn_window_size)
         return native.EdttsDims(c.hidden, c.layers, c.heads, c.n_mels, c.ffn_mult, c.codebook_size, c.semantic_dim, window,
-                                self.max_len, self.max_context_len, self.n_step_emb, native.COMPUTE_DTYPES[self.compute_dtype])
+                                self.max_len, self.max_context_len, self.n_step_emb,
+                                native.COMPUTE_DTYPES[self.compute_dtype] | native.KERNELS[self.kernels])
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         sd = {k: v for k, v in self.named_parameters()}

@@ -31,6 +31,9 @@ class EdttsDims(C.Structure):
 
 
 COMPUTE_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
+# kernel-path bits ORed into EdttsDims.compute_dtype (include/edtts.h: EDTTS_KERNELS_*): "compiled" = the shape's compiled instance
+# only (an unlisted shape is EDTTS_ERR_UNSUPPORTED), "generic" = the run-time-shape fp32 kernels, "auto" = compiled when built
+KERNELS = {"compiled": 0, "generic": 0x100, "auto": 0x200}
 
 
 class EdttsError(RuntimeError):
@@ -262,6 +265,13 @@ def randn(shape, device, seed: int = 0, stream_id: int = 0, elem_offset: int = 0
         raise EdttsError(f"randn: expected a HIP device, got {out.device} -- the MI355X sampler path has no CPU fallback")
     if out.numel() == 0:  # the empty shard of a rank without utterances: nothing to draw (data_ptr() is NULL)
         return out
+    off, n = int(elem_offset), out.numel()
+    if off % 4 or n % 4:
+        # the library draws whole groups of 4 elements: draw the aligned cover and cut (element values depend only on their
+        # global index, so this is what an aligned call would have produced for them)
+        lo, hi = off - off % 4, -(-(off + n) // 4) * 4
+        cover = randn((hi - lo,), device, seed, stream_id, lo, scale)
+        return cover[off - lo: off - lo + n].reshape(out.shape).clone()
     lib().edtts_randn(out.data_ptr(), out.numel(), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint32(stream_id & 0xFFFFFFFF),
                       C.c_uint64(int(elem_offset)), float(scale), _stream(out.device))
     return out

@@ -34,7 +34,7 @@ extern "C" {
 
 enum {
   EDTTS_OK = 0,
-  EDTTS_ERR_UNSUPPORTED = -1, /* dims have no compiled kernel instance            */
+  EDTTS_ERR_UNSUPPORTED = -1, /* dims have no compiled kernel instance (and no generic path was asked for), or exceed its limits */
   EDTTS_ERR_ARG = -2,         /* null pointer / size out of range (IndexError/RuntimeError analogue) */
   EDTTS_ERR_HIP = -3          /* a HIP runtime call or launch failed              */
 };
@@ -62,10 +62,24 @@ typedef struct EdttsDims {
   int32_t compute_dtype; /* EDTTS_F32: everything fp32 (the reference's arithmetic).  EDTTS_BF16: contractions on bf16 MFMA with
                             fp32 accumulation; residual stream, norms, softmax and sampler updates stay fp32 (the reference's AMP
                             precedent: utils/speed_utils.py:70, train_v2.py:290).  head_dim 32 shapes only (hidden = 32 * heads, hidden % 64
-                            == 0): built in 256/8/80 (BASELINE config 3) and 64/2/80, more through EDTTS_INSTANCES_BF16 at build time. */
+                            == 0): built in 256/8/80 (BASELINE config 3) and 64/2/80, more through EDTTS_INSTANCES_BF16 at build time.
+                            Kernel-path bits may be ORed in (EDTTS_KERNELS_*, below); without them a shape runs only if it is a
+                            compiled kernel instance (EDTTS_ERR_UNSUPPORTED otherwise). */
 } EdttsDims;
 
 enum { EDTTS_F32 = 0, EDTTS_BF16 = 1 };
+
+/* Kernel-path bits of EdttsDims.compute_dtype.  The fused kernels are compiled per decoder shape; the generic kernels take every
+ * shape as run-time values (slower, fp32 only):
+ *   EDTTS_KERNELS_GENERIC  always the generic kernels.  EDTTS_BF16 | EDTTS_KERNELS_GENERIC is EDTTS_ERR_UNSUPPORTED.
+ *   EDTTS_KERNELS_AUTO     the compiled instance when there is one, the generic kernels otherwise.  With EDTTS_BF16 it is the
+ *                          compiled bf16 path (never a silent fall-back to fp32).
+ * Generic limits: hidden % heads == 0, hidden even, head_dim <= 128, any n_mels >= 1 and semantic_dim >= 1, MLA rank hidden / 2,
+ * ffn_mult 1..4, layers <= 32, any window.  The choice is made once per dims: edtts_packed_bytes / edtts_pack_weights /
+ * edtts_workspace_bytes answer for the path that will run (the generic blob holds the state-dict's [N][K] matrices), so a blob or
+ * workspace must be sized and packed with the same bits as the calls that use it.  A generic call runs on `stream` alone
+ * (edtts_substreams_for answers 1). */
+enum { EDTTS_KERNELS_GENERIC = 0x100, EDTTS_KERNELS_AUTO = 0x200 };
 
 int edtts_version(void);
 const char* edtts_last_error(void);
