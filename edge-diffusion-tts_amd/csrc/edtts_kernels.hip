@@ -52,21 +52,32 @@ static int fail(int code, const char* fmt, ...) {
 // =========================================================================================================
 // optional per-launch timing of the dominant kernel (bench.py roofline leg)
 // =========================================================================================================
+#include <atomic>
 #include <initializer_list>
+#include <mutex>
 #include <vector>
+// A diagnostic that any thread may have switched on: `on` is read without the lock on every launch, the records themselves are
+// taken under it (profiling serialises the launches it brackets; it is off by default)
 struct Profiler {
+  std::mutex mu;
+  std::atomic<bool> on{false};
   std::vector<hipEvent_t> start, stop;
   std::vector<int> kinds;  // 0 = fused layer kernel or attention half, 1 = FFN + tail half
-  int used = 0, kind = 0;
-  bool on() const { return !start.empty(); }
+  int used = 0;
 };
 static Profiler g_prof;
-#define PROF_LAUNCH(stream, launch_stmt)                                        \
-  do {                                                                          \
-    const bool rec_ = g_prof.on() && g_prof.used < (int)g_prof.start.size();    \
-    if (rec_) (void)hipEventRecord(g_prof.start[g_prof.used], (stream));         \
-    launch_stmt;                                                                \
-    if (rec_) { g_prof.kinds[g_prof.used] = g_prof.kind; (void)hipEventRecord(g_prof.stop[g_prof.used++], (stream)); } \
+static thread_local int g_prof_kind = 0;  // kind of the launches the calling thread is about to make
+#define PROF_LAUNCH(stream, launch_stmt)                                                       \
+  do {                                                                                         \
+    if (g_prof.on.load(std::memory_order_relaxed)) {                                           \
+      std::lock_guard<std::mutex> prof_lock_(g_prof.mu);                                       \
+      const bool rec_ = g_prof.used < (int)g_prof.start.size();                                \
+      if (rec_) (void)hipEventRecord(g_prof.start[g_prof.used], (stream));                     \
+      launch_stmt;                                                                             \
+      if (rec_) { g_prof.kinds[g_prof.used] = g_prof_kind; (void)hipEventRecord(g_prof.stop[g_prof.used++], (stream)); } \
+    } else {                                                                                   \
+      launch_stmt;                                                                             \
+    }                                                                                          \
   } while (0)
 
 // =========================================================================================================
@@ -2217,15 +2228,19 @@ static void make_workspace(const Layout& lo, int B, int T, int S, int cond_rows,
 }
 
 // SIMDs of the current device = waves of the layer kernels in flight at a time (one per SIMD: they need > 256 registers)
+// (one cache entry per device ordinal, filled by whichever thread asks first: the value is a property of the device, so a race
+// only queries it twice)
 static int device_simds() {
-  static int n[64] = {};
+  static std::atomic<int> n[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1024;
-  if (!n[dev]) {
+  int v = n[dev].load(std::memory_order_relaxed);
+  if (!v) {
     int cus = 0;
-    n[dev] = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? 4 * cus : 1024;
+    v = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? 4 * cus : 1024;
+    n[dev].store(v, std::memory_order_relaxed);
   }
-  return n[dev];
+  return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2246,8 +2261,26 @@ struct SubBatches {
   size_t cond;           // float offset of the conditioning rows (shared by the slices)
   size_t total;          // floats
 };
-static int g_coop = [] { const char* e = getenv("EDTTS_COOP"); return e ? atoi(e) : -1; }();
-static int g_substreams = [] { const char* e = getenv("EDTTS_SUBSTREAMS"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : (v > kMaxSub ? kMaxSub : v); }();
+static std::atomic<int> g_coop{[] { const char* e = getenv("EDTTS_COOP"); return e ? atoi(e) : -1; }()};
+static std::atomic<int> g_substreams{[] { const char* e = getenv("EDTTS_SUBSTREAMS"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : (v > kMaxSub ? kMaxSub : v); }()};
+// The two run-time switches as one call sees them.  edtts_set_* may run on any thread at any time; every entry point that plans or
+// launches a decoder takes ONE snapshot (a Settings object on its stack) and everything below it -- the cut, the workspace slices,
+// the kernel choice of every step -- reads the snapshot, so a call never mixes two settings.
+struct Settings {
+  int substreams, coop;
+};
+static thread_local const Settings* t_settings = nullptr;
+struct SettingsScope {
+  Settings snap;
+  const Settings* prev;
+  SettingsScope() : snap{g_substreams.load(std::memory_order_relaxed), g_coop.load(std::memory_order_relaxed)}, prev(t_settings) {
+    t_settings = &snap;
+  }
+  ~SettingsScope() { t_settings = prev; }
+};
+static Settings current_settings() {
+  return t_settings ? *t_settings : Settings{g_substreams.load(std::memory_order_relaxed), g_coop.load(std::memory_order_relaxed)};
+}
 
 static void plan_sub(const Layout& lo, int B, int T, int S, int cond_rows, int n, SubBatches* sb) {
   sb->n = n;
@@ -2278,10 +2311,11 @@ static int substreams_for(const Layout& lo, int B, int T, int S) {
   Workspace w;
   make_workspace(lo, 1, T, S, 1, &w);
   const long waves = (long)B * (w.Tp / 32), slots = device_simds();
-  if (g_substreams < 2 || B < 2 || waves < 2 * slots) return 1;
+  const int max_sub = current_settings().substreams;
+  if (max_sub < 2 || B < 2 || waves < 2 * slots) return 1;
   long n = waves / (2 * slots);
   if (n < 2) n = 2;
-  if (n > g_substreams) n = g_substreams;
+  if (n > max_sub) n = max_sub;
   if (n > B) n = B;
   return (int)n;
 }
@@ -2290,13 +2324,68 @@ static void plan_call(const Layout& lo, int B, int T, int S, int cond_rows, floa
   for (int j = 0; j < sb->n; ++j) sb->ws[j].errp = reinterpret_cast<unsigned*>(wsb);
 }
 
+// Side streams: one set per (device, caller stream) and thread, so that two caller streams -- on one thread or on two -- never
+// share a side stream or an event (a shared set would chain one caller's sub-batches behind another's, and a capture on one caller
+// stream would pull the other's work into its graph).  A thread keeps at most kSideSets sets and reuses the least recently used
+// one for a new caller stream; at thread exit its sets go to a process-wide pool that the next thread draws from, so a server
+// that starts a thread per request does not create streams without bound.  (No HIP call at thread exit: the sets are handed
+// over, not destroyed.)
 struct SideStream {
+  int dev = -1;                    // device the streams and events belong to (-1: nothing created yet)
+  hipStream_t caller = nullptr;    // caller stream the set serves (valid when bound)
+  bool bound = false;
+  unsigned long long last_use = 0;
   hipStream_t s[kMaxSub - 1] = {};
   hipEvent_t fork = nullptr, join[kMaxSub - 1] = {};
 };
-static thread_local SideStream g_side[64];
-// RAII: fork the side stream off the caller's stream, join it back when the call returns (also on its error paths, so that a
-// stream capture is never left with a dangling branch)
+constexpr int kSideSets = 8;
+static std::mutex g_side_pool_mu;
+static std::vector<SideStream>& side_pool() {
+  static auto* pool = new std::vector<SideStream>;  // (never destroyed: a thread may exit after static destruction began)
+  return *pool;
+}
+struct ThreadSides {
+  SideStream set[kSideSets];
+  unsigned long long tick = 0;
+  ~ThreadSides() {
+    std::lock_guard<std::mutex> lock(g_side_pool_mu);
+    for (SideStream& sd : set)
+      if (sd.dev >= 0) release(sd);
+  }
+  static void release(SideStream& sd) {  // (caller holds g_side_pool_mu)
+    sd.bound = false;
+    side_pool().push_back(sd);
+    sd = SideStream();
+  }
+  SideStream& get(int dev, hipStream_t caller) {
+    SideStream* pick = nullptr;
+    for (SideStream& sd : set) {
+      if (sd.bound && sd.dev == dev && sd.caller == caller) { pick = &sd; break; }
+      if (!pick || (pick->bound && (!sd.bound || sd.last_use < pick->last_use))) pick = &sd;
+    }
+    if (!(pick->bound && pick->dev == dev && pick->caller == caller)) {
+      if (pick->dev != dev) {  // streams of another device (or none): trade them for a pooled set of this device, if any
+        std::lock_guard<std::mutex> lock(g_side_pool_mu);
+        if (pick->dev >= 0) release(*pick);
+        auto& pool = side_pool();
+        for (size_t i = 0; i < pool.size(); ++i)
+          if (pool[i].dev == dev) {
+            *pick = pool[i];
+            pool.erase(pool.begin() + (long)i);
+            break;
+          }
+      }
+      pick->caller = caller;
+      pick->bound = true;
+    }
+    pick->last_use = ++tick;
+    return *pick;
+  }
+};
+static thread_local ThreadSides g_sides;
+// RAII: fork the side streams off the caller's stream, join them back when the call returns (also on its error paths, so that a
+// stream capture is never left with a dangling branch).  Every stream and event is created BEFORE the fork is recorded, and `n`
+// counts the side streams that have been forked so far, so that the destructor joins exactly those.
 struct ForkJoin {
   hipStream_t st[kMaxSub];
   SideStream* side = nullptr;
@@ -2307,20 +2396,20 @@ struct ForkJoin {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return fail(EDTTS_ERR_UNSUPPORTED, "device ordinal %d out of range", dev);
-    SideStream& sd = g_side[dev];
+    SideStream& sd = g_sides.get(dev, main);
+    sd.dev = dev;
     if (!sd.fork) HIP_TRY(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
-    for (int j = 0; j + 1 < sb.n; ++j)
-      if (!sd.s[j]) {
-        HIP_TRY(hipStreamCreateWithFlags(&sd.s[j], hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&sd.join[j], hipEventDisableTiming));
-      }
+    for (int j = 0; j + 1 < sb.n; ++j) {
+      if (!sd.s[j]) HIP_TRY(hipStreamCreateWithFlags(&sd.s[j], hipStreamNonBlocking));
+      if (!sd.join[j]) HIP_TRY(hipEventCreateWithFlags(&sd.join[j], hipEventDisableTiming));
+    }
     HIP_TRY(hipEventRecord(sd.fork, main));
+    side = &sd;
     for (int j = 0; j + 1 < sb.n; ++j) {
       HIP_TRY(hipStreamWaitEvent(sd.s[j], sd.fork, 0));
       st[j + 1] = sd.s[j];
+      n = j + 2;
     }
-    side = &sd;
-    n = sb.n;
     return EDTTS_OK;
   }
   ~ForkJoin() {
@@ -2382,16 +2471,7 @@ struct Launcher {
   static constexpr bool HAS_SMALL = C::NF == 2 && (C::H == 160 || C::H == 256) && !SPLIT;
   using Small = Cfg<C::H, C::HEADS, C::MEL, 1>;
   // one wave of these kernels fills a SIMD (> 256 registers): the device runs 4 * #CUs of them at a time (1024 on an MI355X)
-  static int wave_slots() {
-    static int slots[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1024;
-    if (!slots[dev]) {
-      int cus = 0;
-      slots[dev] = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? 4 * cus : 1024;
-    }
-    return slots[dev];
-  }
+  static int wave_slots() { return device_simds(); }
 
   static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
                  const float* sem_feat, hipStream_t st) {
@@ -2444,7 +2524,7 @@ struct Launcher {
   static constexpr bool HAS_COOP = C::NF == 2 && !SPLIT && ((C::H == 160 && C::HEADS == 4) || (C::H == 256 && C::HEADS == 8)) && C::MEL == 80;
   static constexpr bool HAS_CO22 = HAS_COOP && Coop<C, 2>::FITS;
   static int coop_choice(int B, int Tp) {  // 0: none; 14: NF 1, W 4; 24: NF 2, W 4; 22: NF 2, W 2
-    int co = g_coop;  // (edtts_set_coop: 0 switches the cooperative kernel off, 14 / 24 / 22 force an instance)
+    int co = current_settings().coop;  // (edtts_set_coop: 0 switches the cooperative kernel off, 14 / 24 / 22 force an instance)
     if (co < 0) {
       const int t32 = B * (Tp / 32), slots = wave_slots();
       co = 8 * t32 <= slots ? 14 : (4 * t32 <= slots ? 24 : (2 * t32 <= slots ? 22 : 0));
@@ -2533,11 +2613,11 @@ struct Launcher {
 #endif
       if constexpr (SPLIT) {  // (not instantiated in the product build: EDTTS_NF_FFN defaults to the instance's own NF)
         static_assert(!SPLIT, "the two-launch layer experiment predates the LDS-parked residual tile (see git history)");
-        g_prof.kind = 0;
+        g_prof_kind = 0;
         PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer<C, TAIL_QKV, PART_ATTN>), dim3(g), dim3(C::THREADS), layer_lds(), st, a));
         LAUNCH_CHECK("k_layer<attn>");
         a.stream = blob + y.s_ffn;
-        g_prof.kind = 1;
+        g_prof_kind = 1;
         const int gf = grid_f(B, ws.Tp);
 #define EDTTS_LAUNCH_FFN(TL) PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer<CF, TL, PART_FFN>), dim3(gf), dim3(CF::THREADS), 0, st, a))
         switch (t_eff) {
@@ -2549,7 +2629,7 @@ struct Launcher {
           default: EDTTS_LAUNCH_FFN(TAIL_DDIM); break;
         }
 #undef EDTTS_LAUNCH_FFN
-        g_prof.kind = 0;
+        g_prof_kind = 0;
       } else {
 #define EDTTS_LAUNCH_ALL(TL)                                                                                                            \
   do {                                                                                                                                  \
@@ -2579,11 +2659,11 @@ struct Launcher {
   static int set_attrs() {
     // kernels with > 64 KiB of dynamic LDS need the opt-in attribute
     // (the attribute is per device: one flag per device ordinal, so that a process driving several GPUs opts in on each)
-    static bool done[64] = {};
+    static std::atomic<bool> done[64];  // (two threads may both set the attributes: hipFuncSetAttribute is idempotent)
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return fail(EDTTS_ERR_UNSUPPORTED, "device ordinal %d out of range", dev);
-    if (done[dev]) return EDTTS_OK;
+    if (done[dev].load(std::memory_order_acquire)) return EDTTS_OK;
     if constexpr (HAS_SMALL) {
       int rc = Launcher<Small>::set_attrs();
       if (rc) return rc;
@@ -2609,7 +2689,7 @@ struct Launcher {
       HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_LMS, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_VPRED, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
-    done[dev] = true;
+    done[dev].store(true, std::memory_order_release);
     return EDTTS_OK;
   }
 };
@@ -2644,22 +2724,13 @@ struct Launcher16 {
     (void)B;
     return on && Tp % 64 == 0;
   }
-  static int simds() {
-    static int n[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1024;
-    if (!n[dev]) {
-      int cus = 0;
-      n[dev] = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? 4 * cus : 1024;
-    }
-    return n[dev];
-  }
+  static int simds() { return device_simds(); }
   static int set_attrs() {  // the weight ring takes > 64 KiB of dynamic LDS: opt in once per device
-    static bool done[64] = {};
+    static std::atomic<bool> done[64];  // (two threads may both set the attributes: hipFuncSetAttribute is idempotent)
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return fail(EDTTS_ERR_UNSUPPORTED, "device ordinal %d out of range", dev);
-    if (done[dev]) return EDTTS_OK;
+    if (done[dev].load(std::memory_order_acquire)) return EDTTS_OK;
     if constexpr (HAS_SMALL) {
       int rc = Launcher16<Small>::set_attrs();
       if (rc) return rc;
@@ -2690,7 +2761,7 @@ struct Launcher16 {
     HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_LMS, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_VPRED, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
 #endif
-    done[dev] = true;
+    done[dev].store(true, std::memory_order_release);
     return EDTTS_OK;
   }
   static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
@@ -3114,6 +3185,7 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
 int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const float* x,
                           const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                           float* eps, void* stream) {
+  const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
@@ -3138,6 +3210,7 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
 int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
                    const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host, float* x_work,
                    float* x0_out, void* stream) {
+  const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
   if (!packed || !workspace || !sem_idx || !x_T || !timesteps_host || !coef_host || !x_work || !x0_out)
@@ -3177,6 +3250,7 @@ int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, i
 int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const int64_t* sem_idx,
                            const float* sem_features, const float* x_T, int num_steps, const int64_t* timesteps_host,
                            const float* coef_host, float* hist, float* x0_all, float* x_out, void* stream) {
+  const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
@@ -3225,6 +3299,7 @@ int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* work
 int edtts_sample_ddpm(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
                       const float* x_T, int num_steps, const int64_t* t_all, const float* coef_host, const float* noise_all,
                       uint64_t seed, int64_t batch_offset, float* x_out, void* stream) {
+  const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
   if (!packed || !workspace || !sem_idx || !x_T || !t_all || !coef_host || !x_out) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
@@ -3294,6 +3369,7 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
                          const float* sem_features, const float* zero_features, float* x, int num_steps,
                          const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel, int overlap_len,
                          const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond, void* stream) {
+  const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
   if (!packed || !workspace || !sem_features || !x || !t_all || !step_all || !coef_host) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
@@ -3410,7 +3486,7 @@ int edtts_dsconv_forward(const float* x, const float* dw, const float* pw, const
   // Fused path (z never leaves the registers of one 512-thread block per utterance): the reference's own shape class
   // (C_in <= 80, C_out <= 160, T_out <= 512) -- HBM traffic = x in + y out.
   if (dsconv_takes_fused_path(C_in, C_out, To, ksize, stride)) {
-    static bool attr_done[64] = {};
+    static std::atomic<bool> attr_done[64];
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     const int lds = dsconv_fused_lds_floats<5, 10>() * (int)sizeof(float);
@@ -3418,12 +3494,12 @@ int edtts_dsconv_forward(const float* x, const float* dw, const float* pw, const
     auto kern_wide = k_dsconv_fused<5, 10, 2, kDfTWide>;
     auto kern_grp = (To & 3) == 0 ? k_dsconv_grouped<5, 10, 20, true> : k_dsconv_grouped<5, 10, 20, false>;  // C_out = 160, GroupNorm(8): the layer conv.py builds
     const int lds_grp = dsconv_grouped_lds_floats<5, 10>(8) * (int)sizeof(float);
-    if (dev >= 0 && dev < 64 && !attr_done[dev]) {
+    if (dev >= 0 && dev < 64 && !attr_done[dev].load(std::memory_order_acquire)) {
       HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       HIP_TRY(hipFuncSetAttribute((const void*)kern_wide, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       HIP_TRY(hipFuncSetAttribute((const void*)k_dsconv_grouped<5, 10, 20, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_grp));
       HIP_TRY(hipFuncSetAttribute((const void*)k_dsconv_grouped<5, 10, 20, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_grp));
-      attr_done[dev] = true;
+      attr_done[dev].store(true, std::memory_order_release);
     }
     static const bool no_wide = [] { const char* e = getenv("EDTTS_DSCONV_WAVES8"); return e && e[0] == '1'; }();  // (A/B hook)
     static const bool no_grp = [] { const char* e = getenv("EDTTS_DSCONV_NOGROUP"); return e && e[0] == '1'; }();  // (A/B hook)
@@ -3551,24 +3627,25 @@ int edtts_debug_set_wavelog(void* device_buffer) {
 #endif
 
 int edtts_set_coop(int mode) {
-  const int prev = g_coop;
-  if (mode == -1 || mode == 0 || mode == 14 || mode == 24 || mode == 22) g_coop = mode;
-  return prev;
+  if (mode == -1 || mode == 0 || mode == 14 || mode == 24 || mode == 22) return g_coop.exchange(mode);
+  return g_coop.load();
 }
 
 int edtts_set_substreams(int n) {
-  const int prev = g_substreams;
-  if (n >= 1 && n <= kMaxSub) g_substreams = n;
-  return prev;
+  if (n >= 1 && n <= kMaxSub) return g_substreams.exchange(n);
+  return g_substreams.load();
 }
 
 int edtts_substreams_for(const EdttsDims* dims, int B, int T) {
+  const SettingsScope settings;
   Layout lo;
   if (make_layout(dims, &lo) || B < 1 || T < 1) return 1;
   return substreams_for(lo, B, T, (T + 1) / 2);
 }
 
 int edtts_profile_enable(int max_records) {
+  std::lock_guard<std::mutex> lock(g_prof.mu);
+  g_prof.on.store(false);
   for (hipEvent_t e : g_prof.start) (void)hipEventDestroy(e);
   for (hipEvent_t e : g_prof.stop) (void)hipEventDestroy(e);
   g_prof.start.clear(); g_prof.stop.clear(); g_prof.used = 0;
@@ -3580,11 +3657,13 @@ int edtts_profile_enable(int max_records) {
     g_prof.start.push_back(a); g_prof.stop.push_back(b);
   }
   g_prof.kinds.assign(max_records, 0);
+  g_prof.on.store(max_records > 0);
   return EDTTS_OK;
 }
 
 int edtts_profile_collect(double* ms_by_kind, int* launches_by_kind) {
   if (!ms_by_kind || !launches_by_kind) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  std::lock_guard<std::mutex> lock(g_prof.mu);
   ms_by_kind[0] = ms_by_kind[1] = 0.0;
   launches_by_kind[0] = launches_by_kind[1] = 0;
   for (int i = 0; i < g_prof.used; ++i) {

@@ -9,6 +9,7 @@ dropout is the identity as in ``decoder.eval()``.
 from __future__ import annotations
 
 import math
+import threading
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -69,8 +70,22 @@ class EdgeDiffusionDecoder(nn.Module):
         self._zero_mod = None
         self._packed: Optional[torch.Tensor] = None
         self._packed_sig: Optional[Tuple] = None
+        self._pack_event = None     # recorded on the packing stream right behind the last pack
+        self._pack_waited = set()   # streams that have waited for it
         self._workspaces: Dict[Tuple, torch.Tensor] = {}
         self._pinned_workspaces = set()  # keys handed out during graph capture (never evicted)
+        self._lock = threading.Lock()  # host bookkeeping only (caches, the pack): never held across a GPU wait
+
+    # copies (copy.deepcopy, pickling) get a lock and pack bookkeeping of their own
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_lock", None)
+        state["_pack_event"], state["_pack_waited"] = None, set()
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._lock = threading.Lock()
 
     # same distributions as the reference's default construction (nn.Linear / nn.Embedding defaults, ones for norm
     # gains, zeros for final out_proj and the AdaLN projections -- decoder.py:63-64, transformer.py:61-62)
@@ -195,43 +210,89 @@ class EdgeDiffusionDecoder(nn.Module):
         return refs[0], [d[k] for d, k in refs[1]]
 
     def _ensure_packed(self) -> torch.Tensor:
-        names, tensors = self._slot_tensors()
-        sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        if self._packed is None or sig != self._packed_sig:
-            dev = tensors[0].device
-            for n, t in zip(names, tensors):
-                if t.device != dev or t.dtype != torch.float32:
-                    raise native.EdttsError(f"weight {n}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
-            dims = self.dims()
-            nbytes = native.packed_bytes(dims)
-            if self._packed is None or self._packed.numel() != nbytes or self._packed.device != dev:
-                self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            native.pack_weights(dims, [t.contiguous() for t in tensors], self._packed)
-            self._packed_sig = sig
-        return self._packed
+        """The packed weight blob, (re-)packed on the current stream when a parameter has changed.  A call on another stream waits
+        once per pack for an event recorded behind it, so its first use is ordered after the pack (not while capturing: a capture
+        follows an eager warm-up, and torch.cuda.graph synchronises the device before it starts).  Changing parameters while calls
+        that read the old blob are still in flight on other streams is the caller's to order, as for any module."""
+        with self._lock:
+            names, tensors = self._slot_tensors()
+            sig = tuple((t.data_ptr(), t._version) for t in tensors)
+            if self._packed is None or sig != self._packed_sig:
+                dev = tensors[0].device
+                for n, t in zip(names, tensors):
+                    if t.device != dev or t.dtype != torch.float32:
+                        raise native.EdttsError(f"weight {n}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
+                dims = self.dims()
+                nbytes = native.packed_bytes(dims)
+                if self._packed is None or self._packed.numel() != nbytes or self._packed.device != dev:
+                    self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                native.pack_weights(dims, [t.contiguous() for t in tensors], self._packed)
+                self._packed_sig = sig
+                if self._packed.is_cuda:
+                    stream = torch.cuda.current_stream(dev)
+                    self._pack_event = torch.cuda.Event()
+                    self._pack_event.record(stream)
+                    self._pack_waited = {stream.cuda_stream}
+            elif self._pack_event is not None:
+                stream = torch.cuda.current_stream(self._packed.device)
+                if stream.cuda_stream not in self._pack_waited and not torch.cuda.is_current_stream_capturing():
+                    stream.wait_event(self._pack_event)  # (enqueues a wait; the host does not block)
+                    self._pack_waited.add(stream.cuda_stream)
+            return self._packed
 
     WORKSPACE_CACHE = 8
 
-    def workspace(self, B: int, T: int, S: int, cond_rows: int, device, tag: str = "") -> torch.Tensor:
-        """Cached scratch memory for one (shape, device, tag).  At most WORKSPACE_CACHE entries are kept; the least recently USED one
-        is dropped to make room -- never one that a captured hipGraph points at (a workspace handed out while the stream was
-        capturing is pinned for the life of the decoder: a replay writes into it)."""
-        key = (B, T, S, cond_rows, str(device), tag)
-        ws = self._workspaces.pop(key, None)
-        if ws is None:
-            evictable = [k for k in self._workspaces if k not in self._pinned_workspaces]  # insertion order = least recently used first
-            while len(self._workspaces) >= self.WORKSPACE_CACHE and evictable:
-                del self._workspaces[evictable.pop(0)]
-            nbytes = native.workspace_bytes(self.dims(), B, T, S, cond_rows)
-            ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)  # must start zero-filled (padding lanes)
-        self._workspaces[key] = ws  # (re-)inserted last = most recently used
-        if ws.is_cuda and torch.cuda.is_current_stream_capturing():
-            self._pinned_workspaces.add(key)
-            if len(self._pinned_workspaces) > self.WORKSPACE_CACHE:
-                import warnings
-                warnings.warn(f"EdgeDiffusionDecoder: {len(self._pinned_workspaces)} workspaces are pinned by captured graphs (more than "
-                              f"WORKSPACE_CACHE = {self.WORKSPACE_CACHE}); call release_pinned() for shapes whose graphs are gone",
-                              RuntimeWarning, stacklevel=3)
+    def workspace(self, B: int, T: int, S: int, cond_rows: int, device, tag: str = "", *, stream=None) -> torch.Tensor:
+        """Cached scratch memory for one (shape, device, tag, stream, sub-batch cut).  A workspace belongs to the stream it was made
+        for -- ``stream``, by default the device's current stream: it is allocated and zero-filled there, and calls on another
+        stream get their own, so calls on several streams (from one thread or several) never share one.  The key also holds the
+        number of sub-batches a sampler call of this shape makes under the current edtts_set_substreams setting
+        (native.substreams_for), so a setting change never hands out a workspace laid out for another cut.
+        At most WORKSPACE_CACHE entries are kept; the least recently USED one is dropped to make room -- never one that a captured
+        hipGraph points at (a workspace handed out while the stream was capturing is pinned for the life of the decoder: a replay
+        writes into it).  While capturing, the capturing stream's own workspace is taken if it has one, otherwise the one of the
+        eager warm-up (the most recently used of that shape on any stream), so graphs captured on one stream share a workspace and
+        graphs captured on streams that were each warmed up have one each."""
+        dev = torch.device(device)
+        if dev.type == "cuda":
+            if stream is None:
+                stream = torch.cuda.current_stream(dev)
+            sid = stream.cuda_stream
+        else:
+            sid = None if stream is None else stream.cuda_stream
+        cut = native.substreams_for(self.dims(), B, T)  # (a host query)
+        key = (B, T, S, cond_rows, str(device), tag, sid, cut)
+        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        with self._lock:
+            ws = self._workspaces.pop(key, None)
+            if ws is None and capturing:  # the warm-up's workspace (today's rule) when this stream has none of its own
+                same = [k for k in self._workspaces if k[:6] == key[:6] and k[7] == cut]
+                if same:
+                    key = same[-1]
+                    ws = self._workspaces.pop(key)
+            if ws is None:
+                evictable = [k for k in self._workspaces if k not in self._pinned_workspaces]  # insertion order = least recently used first
+                while len(self._workspaces) >= self.WORKSPACE_CACHE and evictable:
+                    # (an evicted workspace goes back to the caching allocator's pool of the stream it was made on: the next block
+                    # handed out there is ordered behind the calls still reading it)
+                    del self._workspaces[evictable.pop(0)]
+                nbytes = native.workspace_bytes(self.dims(), B, T, S, cond_rows)
+                if dev.type == "cuda" and sid != torch.cuda.current_stream(dev).cuda_stream:
+                    with torch.cuda.stream(stream):
+                        ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+                else:
+                    ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)  # must start zero-filled (padding lanes)
+            self._workspaces[key] = ws  # (re-)inserted last = most recently used
+            if ws.is_cuda and torch.cuda.is_current_stream_capturing():
+                self._pinned_workspaces.add(key)
+                n_pinned = len(self._pinned_workspaces)
+            else:
+                n_pinned = 0
+        if n_pinned > self.WORKSPACE_CACHE:
+            import warnings
+            warnings.warn(f"EdgeDiffusionDecoder: {n_pinned} workspaces are pinned by captured graphs (more than "
+                          f"WORKSPACE_CACHE = {self.WORKSPACE_CACHE}); call release_pinned() for shapes whose graphs are gone",
+                          RuntimeWarning, stacklevel=3)
         return ws
 
     def release_pinned(self, B: Optional[int] = None, T: Optional[int] = None, S: Optional[int] = None) -> int:
@@ -239,10 +300,11 @@ class EdgeDiffusionDecoder(nn.Module):
         A pin is keyed by shape, not by graph, and the decoder cannot see a hipGraph die: call this once the graphs that replay
         into those workspaces have been destroyed (replaying one afterwards would write into freed memory).  Returns the number
         of workspaces released."""
-        keys = [k for k in self._pinned_workspaces if (B is None or k[0] == B) and (T is None or k[1] == T) and (S is None or k[2] == S)]
-        for k in keys:
-            self._pinned_workspaces.discard(k)
-            self._workspaces.pop(k, None)
+        with self._lock:
+            keys = [k for k in self._pinned_workspaces if (B is None or k[0] == B) and (T is None or k[1] == T) and (S is None or k[2] == S)]
+            for k in keys:
+                self._pinned_workspaces.discard(k)
+                self._workspaces.pop(k, None)
         return len(keys)
 
     # ------------------------------------------------------------------------------------------ forward

@@ -86,9 +86,11 @@ class EdgeInference:
         x_T = x_T.to(device=dev, dtype=torch.float32).contiguous()
         ts = list(range(self.cfg.diff_steps - 1, self.cfg.diff_steps - 1 - n, -1))
         key = (n, str(dev))
-        if key not in self._t_cache:  # device copy made once (an H2D copy is not allowed inside graph capture)
-            self._t_cache[key] = torch.tensor(ts, dtype=torch.int64, device=dev)
-        t_all = self._t_cache[key]
+        t_all = self._t_cache.get(key)
+        if t_all is None:  # device copy made once (an H2D copy is not allowed inside graph capture)
+            # (setdefault is atomic: two threads that both made a copy agree on the one kept; the copy is synchronous, so its
+            # contents are there for every stream)
+            t_all = self._t_cache.setdefault(key, torch.tensor(ts, dtype=torch.int64, device=dev))
         coefs = [self.schedule.ddpm_coefficients(t) for t in ts]
         if noise is not None:
             if tuple(noise.shape) != (n, B, T_out, self.cfg.n_mels):

@@ -50,10 +50,12 @@ class InpaintSampler:
         x = x.to(torch.float32).contiguous().clone()
         sem_features = sem_features.to(device=dev, dtype=torch.float32).contiguous()
         key = (tuple(times), step_idx, str(dev))
-        if key not in self._dev_cache:  # (device copies made once: no H2D copy at call time -> capturable)
-            self._dev_cache[key] = (torch.tensor(times, dtype=torch.int64, device=dev),
-                                    torch.full((n,), step_idx, dtype=torch.int64, device=dev))
-        t_all, s_all = self._dev_cache[key]
+        cached = self._dev_cache.get(key)
+        if cached is None:  # (device copies made once: no H2D copy at call time -> capturable; setdefault: one winner per key)
+            # (both are synchronous host-to-device copies, so their contents are there for every stream)
+            cached = self._dev_cache.setdefault(key, (torch.tensor(times, dtype=torch.int64, device=dev),
+                                                      torch.tensor([step_idx] * n, dtype=torch.int64, device=dev)))
+        t_all, s_all = cached
         cf = (C.c_float * (4 * n))(*self._coefs(times))
         packed = dec._ensure_packed()
         ws = dec.workspace(B, T, S, n, dev)

@@ -16,6 +16,12 @@
  *     (a hipStream_t passed as void*; NULL = the null stream).  All calls are graph-capturable.
  *   - return value: 0 on success, a negative EDTTS_ERR_* otherwise; edtts_last_error() returns a
  *     thread-local message for the last failing call.
+ *   - threads and streams: any number of host threads may call the library at the same time, on one stream each or on several,
+ *     as long as no two calls that are in flight together share a workspace or an output.  A packed blob is read-only to every
+ *     call and may be shared; re-packing it must be ordered (by the caller) after every call that reads it.  The library keeps no
+ *     device state outside the caller's buffers; its host state is the two run-time switches (edtts_set_substreams /
+ *     edtts_set_coop, atomic: each call reads both ONCE and plans and runs under that snapshot), per-device attribute caches and
+ *     the side streams of the sub-batch cut (one set per device, caller stream and thread; see below).
  *   - environment switches, read once per process: EDTTS_SUBSTREAMS=1..8 (see edtts_set_substreams, default 4);
  *     EDTTS_DSCONV_UNFUSED=1 forces the three-kernel conv path; EDTTS_DSCONV_NOGROUP=1 / EDTTS_DSCONV_WAVES8=1 select the older
  *     one-kernel forms (A/B hooks: same results within the layer's 1e-5).
@@ -105,7 +111,16 @@ int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_sl
  * Scratch for activations (h, two ping-pong sets of q, k, v^T), the per-call cross-attention K/V cache and the AdaLN rows.
  * cond_rows = number of (t, step_idx) rows the conditioning kernel is run for (B for a plain forward,
  * num_steps for the fused sampler).  The workspace must be ZERO-FILLED once after allocation (padding
- * lanes are read but never written) and may then be reused for any number of calls of the same shape. */
+ * lanes are read but never written) and may then be reused for any number of calls of the same shape.
+ * The byte count covers every form of a call -- the batch in one piece or cut into any number of sub-batches -- so it does not
+ * depend on edtts_set_substreams / edtts_set_coop, and a workspace is never too small for a call under another setting.  Its
+ * LAYOUT does depend on the cut (edtts_substreams_for): each sub-batch takes its own slice, with its own padded rows.  A
+ * workspace that served a call under one cut and then serves a call under another may therefore hold, in lanes the new layout
+ * treats as padding (the padded frames and context rows of each slice), finite values the old layout wrote there.  Padding
+ * lanes only ever meet masked scores and zero weights, so results do not change (bitwise; the GPU tests switch the cut on a
+ * shared workspace); a caller that wants the zero-fill contract to hold literally keeps one workspace per cut, as the Python
+ * host does.  Workspace
+ * word 0 (edtts_index_errors) is per workspace: two calls in flight on two workspaces never see each other's bits. */
 int edtts_workspace_bytes(const EdttsDims* dims, int B, int T, int S, int cond_rows, size_t* out_bytes);
 
 /* Out-of-range indices: where the reference raises IndexError (token ids >= codebook_size, step_idx >= 16), the kernels clamp
@@ -271,7 +286,8 @@ int edtts_griffin_lim(const float* spec, int B, int T, int n_fft, int hop, const
  * hipEvents recorded on the stream it is launched on, up to n launches; n = 0 disables and releases the events.
  * A decoder layer is either one fused launch (kind 0) or two: the attention half (kind 0) and the FFN + tail half
  * (kind 1).  edtts_profile_collect synchronises on the recorded events, returns the summed device time (ms) and
- * the launch count per kind (arrays of 2), and resets the counter.  Not graph-capturable while on. */
+ * the launch count per kind (arrays of 2), and resets the counter.  Not graph-capturable while on.  Any thread may switch it;
+ * while it is on, the bracketed launches of all threads take one lock in turn. */
 int edtts_profile_enable(int max_records);
 int edtts_profile_collect(double* ms_by_kind, int* launches_by_kind);
 
@@ -284,7 +300,10 @@ int edtts_profile_collect(double* ms_by_kind, int* launches_by_kind);
  * waves, at least two, at most n (B = 256: two at T = 512, four at T = 1024).  Results do not depend on the cut (bitwise).
  * n = 1 switches the cut off (per-kernel profiling wants launches that do not share the device); the default is 4 (environment
  * EDTTS_SUBSTREAMS at load time), the maximum 8.  Returns the previous value; values outside [1, 8] only query.
- * edtts_substreams_for: the number of sub-batches a call of that shape makes under the current setting. */
+ * edtts_substreams_for: the number of sub-batches a call of that shape makes under the current setting.
+ * The side streams and fork / join events are owned per (device, caller stream) and per calling thread: two caller streams never
+ * share a side stream, so their cuts run independently and each call joins only its own branches.  A thread keeps up to 8 such
+ * sets (the least recently used one is rebound to a new caller stream); at thread exit they pass to a pool the next thread reuses. */
 int edtts_set_substreams(int n);
 int edtts_substreams_for(const EdttsDims* dims, int B, int T);
 
