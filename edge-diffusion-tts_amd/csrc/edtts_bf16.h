@@ -1064,6 +1064,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_prologue1
   const bool valid = tl.valid;
   const int lane = threadIdx.x & 63, fq = lane & 15, g = lane >> 4;
   const int b = tl.b, m0 = tl.m0;
+  const int Tb = utt_len(a.t_len, b, a.T, a.t_dbl);  // (x past the utterance's length reads as zero, as in its solo call)
   Ring16<C> ring;
   ring.start(a.stream, ring_lds16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane);
   constexpr int NF = C::NF;
@@ -1075,8 +1076,8 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_prologue1
 #pragma unroll
     for (int kt = 0; kt < C::MKT; ++kt) {
       const int c0 = 32 * kt + 4 * g, c1 = c0 + 16;
-      const f4 v0 = (f < a.T && c0 < C::MEL) ? ldg4(xr + c0) : splat(0.f);
-      const f4 v1 = (f < a.T && c1 < C::MEL) ? ldg4(xr + c1) : splat(0.f);
+      const f4 v0 = (f < Tb && c0 < C::MEL) ? ldg4(xr + c0) : splat(0.f);
+      const f4 v1 = (f < Tb && c1 < C::MEL) ? ldg4(xr + c1) : splat(0.f);
       xin[kt][ft] = pack8(v0, v1);
     }
   }
@@ -1126,6 +1127,8 @@ __global__ __launch_bounds__(C::THREADS, EDTTS16_ATT_OCC) void k_attn16(KArgs a)
   constexpr int NF = C::NF;
   const int lane = threadIdx.x & 63, fq = lane & 15, g = lane >> 4;
   const int b = tl.b, m0 = tl.m0;
+  const int Tb = utt_len(a.t_len, b, a.T, a.t_dbl), Sb = utt_len(a.s_len, b, a.S);
+  const int nk_self = m0 < live_end(Tb) ? Tb : a.T;  // (see k_layer16)
   const size_t rowbase = (size_t)b * a.Tp + m0 + fq;
   const __bf16* qbase = reinterpret_cast<const __bf16*>(a.attn_q);
   __bf16* orow = reinterpret_cast<__bf16*>(a.attn_o) + rowbase * C::H + 8 * g;
@@ -1136,10 +1139,10 @@ __global__ __launch_bounds__(C::THREADS, EDTTS16_ATT_OCC) void k_attn16(KArgs a)
   };
   if (SELF)
     attention16<C, true>(qf, reinterpret_cast<const __bf16*>(a.k) + (size_t)b * a.Tp * C::H,
-                         reinterpret_cast<const __bf16*>(a.vT) + (size_t)b * C::H * a.Tp, a.Tp, a.T, a.window, m0, lane, sink);
+                         reinterpret_cast<const __bf16*>(a.vT) + (size_t)b * C::H * a.Tp, a.Tp, nk_self, a.window, m0, lane, sink);
   else
     attention16<C, false>(qf, reinterpret_cast<const __bf16*>(a.kc) + (size_t)b * a.Sp * C::H,
-                          reinterpret_cast<const __bf16*>(a.vcT) + (size_t)b * C::H * a.Sp, a.Sp, a.S, -1, m0, lane, sink);
+                          reinterpret_cast<const __bf16*>(a.vcT) + (size_t)b * C::H * a.Sp, a.Sp, Sb, -1, m0, lane, sink);
 }
 
 // PART16_ALL: the whole layer in one launch.  Split layer: k_attn16<self> | PART16_MID (self out-projection, norm2, cross q) |
@@ -1157,6 +1160,10 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
   const bool valid = tl.valid;  // a padding wave works on a copy of the last tile (ring barriers, DMAs) and stores nothing
   const int lane = threadIdx.x & 63, fq = lane & 15, g = lane >> 4;
   const int b = tl.b, m0 = tl.m0;
+  // per-utterance lengths: a wave must stay in the block's ring, so a tile the solo call does not have is computed anyway (from the
+  // zero input the prologue read, over all T keys as without lengths) and stores only the tail's zeros; nothing reads its rows
+  const int Tb = utt_len(a.t_len, b, a.T, a.t_dbl), Sb = utt_len(a.s_len, b, a.S);
+  const int nk_self = m0 < live_end(Tb) ? Tb : a.T;
   const size_t rowbase = (size_t)b * a.Tp + m0 + fq;
   Ring16<C> ring;
   // weight stream of a layer: self out-projection (HEADS k-tiles of HT fragments) | cross q (KT pairs of n-tiles over KT k-tiles) |
@@ -1218,7 +1225,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
       else return *reinterpret_cast<const bf8*>(qbase + q_at<C>(tile0, lane, hd, ft));
     };
     attention16<C, true>(qf, reinterpret_cast<const __bf16*>(a.k) + (size_t)b * a.Tp * C::H,
-                         reinterpret_cast<const __bf16*>(a.vT) + (size_t)b * C::H * a.Tp, a.Tp, a.T, a.window, m0, lane,
+                         reinterpret_cast<const __bf16*>(a.vT) + (size_t)b * C::H * a.Tp, a.Tp, nk_self, a.window, m0, lane,
                          [&](int, const bf8 (&ob)[NF]) { ktile16<C::HT>(ring, ob, h); }  // h += Wo[:, head] . O
 #ifdef EDTTS_STAMPS
                          , a.stamps ? a.stamps + 8 : nullptr
@@ -1284,7 +1291,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
       else return as_bf8(bufld4(rsp, pvoff, q_soff<C>(hd, ft)));
     };
     attention16<C, false>(qf, reinterpret_cast<const __bf16*>(a.kc) + (size_t)b * a.Sp * C::H,
-                          reinterpret_cast<const __bf16*>(a.vcT) + (size_t)b * C::H * a.Sp, a.Sp, a.S, -1, m0, lane,
+                          reinterpret_cast<const __bf16*>(a.vcT) + (size_t)b * C::H * a.Sp, a.Sp, Sb, -1, m0, lane,
                           [&](int, const bf8 (&ob)[NF]) { ktile16<C::HT>(ring, ob, h); }
 #ifdef EDTTS_STAMPS
                           , a.stamps ? a.stamps + 40 : nullptr
@@ -1376,7 +1383,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
         for (int ft = 0; ft < NF; ++ft) {
           const int f = m0_t + 16 * ft + fq_t;
           if (f >= a.T || !valid) continue;
-          tail_apply<TAIL>(a, ((size_t)b_t * a.T + f) * C::MEL + 16 * nt + 4 * g_t, e[u][ft] + ob);
+          tail_store<TAIL>(a, f, Tb, ((size_t)b_t * a.T + f) * C::MEL + 16 * nt + 4 * g_t, e[u][ft] + ob);
         }
       }
     }

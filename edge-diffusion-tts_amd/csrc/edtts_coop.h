@@ -181,6 +181,10 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
   float* const hp = a.h + rowbase * H + 4 * g;
   const __amdgpu_buffer_rsrc_t rs = make_rsrc(a.stream);
   const unsigned voff = (unsigned)lane * 16u;
+  // per-utterance lengths: the tile's waves share its barriers, so a tile the solo call does not have is computed anyway (from the
+  // zero input the prologue read, over all T keys as without lengths) and stores only the tail's zeros; nothing reads its rows
+  const int Tb = utt_len(a.t_len, b, a.T, a.t_dbl), Sb = utt_len(a.s_len, b, a.S);
+  const int nk_self = m0 < live_end(Tb) ? Tb : a.T;
   // fragment offsets of the layer's stream (edtts_pack_weights: proj | q_proj | out_proj | ffn | tail), in fragments
   constexpr unsigned F_PROJ = 0, F_Q = KPT * HT, F_O = F_Q + HT * HT, F_FFN = F_O + KPT * HT;
   const unsigned f_tail = F_FFN + (unsigned)a.ffn_tiles * 3u * HT;
@@ -217,7 +221,7 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
   // ---- x = x + attn(norm1(x, cond))   (transformer.py:142-146) ---------------------------------------------------------------
   {
     QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * H, H, fq, g);
-    attention_fused<C, true, O_LDS>(ql, a.k + (size_t)b * a.Tp * H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, a.T, a.window, m0, lane,
+    attention_fused<C, true, O_LDS>(ql, a.k + (size_t)b * a.Tp * H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, nk_self, a.window, m0, lane,
                                     no_ring, h, obuf, nop, nullptr, 0, wv, W);
   }
   {
@@ -246,7 +250,7 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
   __syncthreads();
   {
     QLds ql(qtile, H, fq, g);
-    attention_fused<C, false, O_LDS>(ql, a.kc + (size_t)b * a.Sp * H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, a.S, -1, m0, lane, no_ring, h,
+    attention_fused<C, false, O_LDS>(ql, a.kc + (size_t)b * a.Sp * H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane, no_ring, h,
                                      obuf, nop, nullptr, 0, wv, W);
   }
   {
@@ -382,7 +386,7 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
         const int f = m0 + 16 * ft + fq;
         if (!valid || f >= a.T) continue;
         const size_t idx = ((size_t)b * a.T + f) * C::MEL + 16 * nt + 4 * g;
-        tail_apply<TAIL>(a, idx, e[ft] + ob);
+        tail_store<TAIL>(a, f, Tb, idx, e[ft] + ob);
       }
     }
   }
@@ -417,6 +421,7 @@ __global__ __launch_bounds__(64 * W) void k_prologue_co(KArgs a) {
   const bool valid = tile < ntiles;
   tile = valid ? tile : ntiles - 1;
   const int b = tile / tpu, m0 = (tile - b * tpu) * C::WF;
+  const int Tb = utt_len(a.t_len, b, a.T, a.t_dbl);  // (x past the utterance's length reads as zero, as in its solo call)
   f4* const xb = reinterpret_cast<f4*>(smem_co) + lane;
   const __amdgpu_buffer_rsrc_t rs = make_rsrc(a.stream);
   const unsigned voff = (unsigned)lane * 16u;
@@ -428,7 +433,7 @@ __global__ __launch_bounds__(64 * W) void k_prologue_co(KArgs a) {
   for (int ft = 0; ft < NF; ++ft) {
     const int f = m0 + 16 * ft + fq;
 #pragma unroll
-    for (int t = 0; t < MT; ++t) xin[t][ft] = f < a.T ? ldg4(a.x + ((size_t)b * a.T + f) * C::MEL + 16 * t + 4 * g) : splat(0.f);
+    for (int t = 0; t < MT; ++t) xin[t][ft] = f < Tb ? ldg4(a.x + ((size_t)b * a.T + f) * C::MEL + 16 * t + 4 * g) : splat(0.f);
   }
   gi.run(rs, voff, wv, HT, fin, [&xin](int kt, int ft) { return xin[kt][ft]; }, NrFull{}, [&](int nt) { return ldg4(a.inp_b + 16 * nt + 4 * g); },
          [&](int nt, const f4 (&acc)[NF]) {

@@ -213,6 +213,8 @@ struct AttnArgs {
   float* o;         // like q
   int ldq, ldkv, ldo, Tq, Tk, DH, window;  // window < 0: every key
   float scale;      // log2(e) / sqrt(head_dim): scores in the exp2 domain
+  const int64_t *q_len, *k_len;  // per-utterance query / key counts [B] (edtts_*_len), or null: Tq / Tk for all
+  int q_dbl, k_dbl;              // ... given as token counts of which they are twice (see utt_len)
 };
 // One wave = 16 queries of one (utterance, head).  S^T tile (16 keys x 16 queries) = K Q^T: lane (g, i) holds the scores of query i
 // against keys 4g + r.  P^T then is the B operand of O^T += V^T P^T as it stands when MFMA step s contracts keys {4g + s}: the V^T
@@ -221,6 +223,11 @@ template <int DT>
 __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
   const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
+  // Per-utterance lengths: keys past the utterance's count are never read (as in its solo call, whose Tk it is); a block of queries
+  // wholly past its count has no solo counterpart and stores nothing -- those rows are read by no other row (every other step is
+  // row-local), and the output's rows past the count are zeroed at the end of the forward.
+  const int Tk = utt_len(a.k_len, b, a.Tk, a.k_dbl);
+  if (q0 >= utt_len(a.q_len, b, a.Tq, a.q_dbl)) return;
   const int qi = q0 + fq;
   const bool qok = qi < a.Tq;
   const float* qrow = a.q + (size_t)(b * a.Tq + (qok ? qi : 0)) * a.ldq + hd * a.DH;
@@ -234,11 +241,11 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < DT; ++t) acc[t] = splat(0.f);
   float m = -1e30f, l = 0.f;
-  int lo = 0, hi = a.Tk;
+  int lo = 0, hi = Tk;
   if (a.window >= 0) {
     lo = q0 - a.window > 0 ? q0 - a.window : 0;
     const int e = q0 + 16 + a.window;
-    hi = e < a.Tk ? e : a.Tk;
+    hi = e < Tk ? e : Tk;
   }
   const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
   const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
@@ -304,12 +311,13 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
 
 // ---- context embedding (token ids) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_gen_embed(const int64_t* sem_idx, const float* tok, const float* cpe, float* ctx, int rows, int S,
-                                                   int H, int n_tok, unsigned* err) {
+                                                   int H, int n_tok, unsigned* err, const int64_t* s_len) {
   const size_t n = (size_t)rows * H;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t row = i / H;
     const int c = (int)(i - row * H);
-    long tk = (long)sem_idx[row];
+    // (a token past the utterance's length is padding: never read, no index check; its row is never a key)
+    long tk = (s_len && (int)(row % S) >= utt_len_lane(s_len, (int)(row / S), S)) ? 0 : (long)sem_idx[row];
     if (tk < 0 || tk >= n_tok) {  // nn.Embedding would raise IndexError: clamp (never fault) and leave a mark for the host
       if (c == 0) atomicOr(err, (unsigned)EDTTS_IDX_SEM);
       tk = tk < 0 ? 0 : n_tok - 1;
@@ -346,13 +354,41 @@ EDTTS_DEV void tail_elem(const KArgs& a, size_t idx, float e) {
   }
 }
 template <int TAIL>
-__global__ __launch_bounds__(256) void k_gen_tail(KArgs a, const float* eps, size_t n, int vec) {
+EDTTS_DEV void tail_zero_elem(const KArgs& a, size_t idx) {
+  if (TAIL == TAIL_LMS) {
+    a.x0_hist[idx] = 0.f;
+    if (a.x0_all) a.x0_all[idx] = 0.f;
+  } else if (TAIL == TAIL_DDIM) {
+    a.x0[idx] = 0.f;
+  }
+  a.x_prev[idx] = 0.f;
+}
+// element idx of [B][T][MEL] lies past its utterance's frame count (per-utterance lengths; no lengths: never)
+EDTTS_DEV bool past_len(const int64_t* t_len, bool dbl, size_t idx, int T, int MEL) {
+  if (t_len == nullptr) return false;
+  const size_t row = idx / MEL;
+  return (int)(row % T) >= utt_len_lane(t_len, (int)(row / T), T, dbl);
+}
+// (with lengths, vec also needs MEL % 4 == 0: a float4 then never straddles two frames)
+template <int TAIL>
+__global__ __launch_bounds__(256) void k_gen_tail(KArgs a, const float* eps, size_t n, int vec, int MEL) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   if (vec) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += stride) tail_apply<TAIL>(a, 4 * i, ldg4(eps + 4 * i));
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += stride) {
+      if (past_len(a.t_len, a.t_dbl, 4 * i, a.T, MEL)) tail_zero<TAIL>(a, 4 * i);
+      else tail_apply<TAIL>(a, 4 * i, ldg4(eps + 4 * i));
+    }
   } else {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) tail_elem<TAIL>(a, i, eps[i]);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      if (past_len(a.t_len, a.t_dbl, i, a.T, MEL)) tail_zero_elem<TAIL>(a, i);
+      else tail_elem<TAIL>(a, i, eps[i]);
+    }
   }
+}
+// eps rows past each utterance's frame count -> 0 (the forward's own output, TAIL_EPS)
+__global__ __launch_bounds__(256) void k_gen_zero_past(float* y, const int64_t* t_len, int dbl, size_t n, int T, int MEL) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    if (past_len(t_len, dbl, i, T, MEL)) y[i] = 0.f;
 }
 
 }  // namespace edtts_gen
@@ -366,6 +402,7 @@ struct GenericLauncher {
   static int set_attrs() { return EDTTS_OK; }  // (no kernel here needs more than 64 KiB of LDS)
 
   static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+  static unsigned grid_1d(size_t n) { const size_t nb = (n + 255) / 256; return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb)); }
   template <int EPI>
   static int gemm(hipStream_t st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
                   const float* pe = nullptr, int T = 1) {
@@ -389,8 +426,9 @@ struct GenericLauncher {
     return EDTTS_OK;
   }
   static int attn(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, float* o,
-                  int Tq, int Tk, int window) {
-    edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH)};
+                  int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl) {
+    edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
+                          (int)q_dbl, (int)k_dbl};
     const dim3 grid((Tq + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
 #define EDTTS_GEN_ATTN(DT) case DT: hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a); break
@@ -404,8 +442,10 @@ struct GenericLauncher {
   }
 
   // context rows (token_emb gather or sem_proj) + context PE, then per layer kv_down -> kv_norm -> kv_up into the K|V cache
+  // (per-utterance lengths: context rows past S_b are built from whatever the padding holds and are never read -- the attention reads
+  // keys < S_b only, and every other step is row-local)
   static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
-                 const float* sem_feat, hipStream_t st) {
+                 const float* sem_feat, hipStream_t st, const int64_t* s_len = nullptr) {
     using namespace edtts_gen;
     const int rows = B * S, H = lo.H, R = lo.R;
     float* c = wsb + ws.g_ctx;
@@ -415,7 +455,7 @@ struct GenericLauncher {
       unsigned* err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
       size_t nb = ((size_t)rows * H + 255) / 256;
       if (nb > 4096) nb = 4096;
-      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, c, rows, S, H, lo.NTOK, err);
+      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, c, rows, S, H, lo.NTOK, err, s_len);
       LAUNCH_CHECK("k_gen_embed");
     }
     for (int l = 0; l < lo.L; ++l) {
@@ -431,7 +471,7 @@ struct GenericLauncher {
   static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
                      const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
                      const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
-                     const VpredStepArgs* vp = nullptr) {
+                     const VpredStepArgs* vp = nullptr, Lens ln = Lens{}) {
     using namespace edtts_gen;
     const int M = B * T, H = lo.H, FH = lo.FM * lo.H, MEL = lo.MEL;
     float *h = wsb + ws.h, *xn = wsb + ws.g_xn, *big = wsb + ws.g_big, *att = wsb + ws.g_att;
@@ -443,12 +483,12 @@ struct GenericLauncher {
       // self-attention branch
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
       TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, big, 3 * H, M, 3 * H, H));
-      TRY_G(attn(st, lo, B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, window));
+      TRY_G(attn(st, lo, B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, window, ln.t, ln.t, ln.t_dbl, ln.t_dbl));
       TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
       // cross-attention branch
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
       TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, big, H, M, H, H));
-      TRY_G(attn(st, lo, B, big, H, kv, kv + H, 2 * H, att, T, S, -1));
+      TRY_G(attn(st, lo, B, big, H, kv, kv + H, 2 * H, att, T, S, -1, ln.t, ln.s, ln.t_dbl, false));
       TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_op, nullptr, h, H, M, H, H));
       // feed-forward branch
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cond_bstride));
@@ -458,11 +498,18 @@ struct GenericLauncher {
     TRY_G(norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
     float* e = tail == TAIL_EPS ? eps : wsb + ws.g_eps;
     TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, e, MEL, M, MEL, H));
-    if (tail == TAIL_EPS) return EDTTS_OK;
+    if (tail == TAIL_EPS) {
+      if (ln.t) {
+        hipLaunchKernelGGL(k_gen_zero_past, dim3(grid_1d((size_t)M * MEL)), dim3(256), 0, st, eps, ln.t, (int)ln.t_dbl, (size_t)M * MEL, T, MEL);
+        LAUNCH_CHECK("k_gen_zero_past");
+      }
+      return EDTTS_OK;
+    }
     KArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.x_prev = x_prev;
-    bool vec = al16(x) && al16(x_prev) && al16(e);
+    a.T = T; a.t_len = ln.t; a.t_dbl = ln.t_dbl;
+    bool vec = al16(x) && al16(x_prev) && al16(e) && (ln.t == nullptr || MEL % 4 == 0);
     if (tail == TAIL_LMS) {
       a.lms = lms->k; a.h_new = lms->h_new; a.h_old = lms->h_old; a.x0_hist = lms->x0_hist; a.x0_all = lms->x0_all;
       vec = vec && al16(a.h_new) && al16(a.h_old) && al16(a.x0_hist) && al16(a.x0_all);
@@ -484,10 +531,10 @@ struct GenericLauncher {
     if (nb > 4096) nb = 4096;
     if (nb < 1) nb = 1;
     switch (tail) {
-      case TAIL_LMS: hipLaunchKernelGGL(k_gen_tail<TAIL_LMS>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
-      case TAIL_VPRED: hipLaunchKernelGGL(k_gen_tail<TAIL_VPRED>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
-      case TAIL_DDPM: hipLaunchKernelGGL(k_gen_tail<TAIL_DDPM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
-      default: hipLaunchKernelGGL(k_gen_tail<TAIL_DDIM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec); break;
+      case TAIL_LMS: hipLaunchKernelGGL(k_gen_tail<TAIL_LMS>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
+      case TAIL_VPRED: hipLaunchKernelGGL(k_gen_tail<TAIL_VPRED>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
+      case TAIL_DDPM: hipLaunchKernelGGL(k_gen_tail<TAIL_DDPM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
+      default: hipLaunchKernelGGL(k_gen_tail<TAIL_DDIM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
     }
     LAUNCH_CHECK("k_gen_tail");
     return EDTTS_OK;

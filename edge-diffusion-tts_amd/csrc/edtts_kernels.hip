@@ -498,7 +498,28 @@ struct KArgs {
   const float* v_uncond;                  // ... its unconditional prediction (classifier-free guidance), or null
   const float *h_new, *h_old;             // previous x0 predictions (may alias x0_hist: read before write, same lane)
   float *x0_hist, *x0_all;                // where this step's x0 goes (history slot; optional intermediates)
+  const int64_t *t_len, *s_len;           // per-utterance frame / token counts [B] of this (sub-)batch, or null: T / S for all
+  int t_dbl;                              // t_len holds token counts: frames = 2 x tokens (edtts_generate_len / edtts_sample_ddpm_len)
 };
+
+// Per-utterance lengths (edtts_*_len).  Utterance b has n_b = len[b] valid rows, clamped into [1, full] (the entry
+// point flags out-of-range values with EDTTS_IDX_LEN); dbl: len holds token counts and n_b = 2 x clamp(len[b], 1, full / 2).  Without
+// lengths every utterance has the batch-wide `full`.  b is wave-uniform, so this is one scalar load per wave.
+EDTTS_DEV int utt_len_of(int64_t v, int full, bool dbl) {
+  const int hi = dbl ? full >> 1 : full;
+  const int n = v < 1 ? 1 : (v > hi ? hi : (int)v);
+  return dbl ? 2 * n : n;
+}
+EDTTS_DEV int utt_len(const int64_t* len, int b, int full, bool dbl = false) {
+  if (len == nullptr) return full;
+  return utt_len_of(len[__builtin_amdgcn_readfirstlane(b)], full, dbl);
+}
+// ... for an utterance index that differs between lanes (the generic path's elementwise kernels)
+EDTTS_DEV int utt_len_lane(const int64_t* len, int b, int full, bool dbl = false) {
+  return len == nullptr ? full : utt_len_of(len[b], full, dbl);
+}
+// Rows [0, live_end(n_b)) are the 32-row tiles the utterance's solo call computes; its key chunks (32 keys) never reach past them.
+EDTTS_DEV int live_end(int n) { return (n + 31) & ~31; }
 
 // block -> wave tile mapping with an XCD-aware remap: the hardware deals consecutive block ids round-robin over the 8
 // XCDs; remapping gives every XCD a contiguous range of frame tiles, so the K/V halo rows a tile shares with its
@@ -603,6 +624,8 @@ __global__ __launch_bounds__(C::THREADS) void k_prologue(KArgs a) {
   if (!tl.valid) return;
   const int lane = threadIdx.x & 63, fq = lane & 15, g = lane >> 4;
   const int b = tl.b, m0 = tl.m0;
+  const int Tb = utt_len(a.t_len, b, a.T, a.t_dbl);
+  if (m0 >= live_end(Tb)) return;  // a tile the utterance's solo call does not have
   WStream<C> ring;
   ring.prime(a.stream, lane);
   f4 xin[C::MT][NF];
@@ -611,7 +634,7 @@ __global__ __launch_bounds__(C::THREADS) void k_prologue(KArgs a) {
     const int f = m0 + 16 * ft + fq;
 #pragma unroll
     for (int t = 0; t < C::MT; ++t)
-      xin[t][ft] = f < a.T ? ldg4(a.x + ((size_t)b * a.T + f) * C::MEL + 16 * t + 4 * g) : splat(0.f);
+      xin[t][ft] = f < Tb ? ldg4(a.x + ((size_t)b * a.T + f) * C::MEL + 16 * t + 4 * g) : splat(0.f);
   }
   // h = (in_proj(x) + bias) + pe   (decoder.py:96-97).  The HT*MT in_proj fragments head the kernel's stream (n-tile pairs per
   // k-tile) and are consumed as ONE ring phase, so they are prefetched like every other weight.  The accumulators start at the
@@ -728,6 +751,29 @@ EDTTS_DEV void tail_apply(const KArgs& a, size_t idx, f4 ev) {
     stg4(a.x_prev + idx, xp);
   }
 }
+// ... and for a frame past its utterance's length (edtts_*_len): zeros wherever tail_apply would have stored
+template <int TAIL>
+EDTTS_DEV void tail_zero(const KArgs& a, size_t idx) {
+  const f4 z = splat(0.f);
+  if (TAIL == TAIL_EPS) {
+    stg4(a.eps + idx, z);
+  } else if (TAIL == TAIL_LMS) {
+    stg4(a.x0_hist + idx, z);
+    if (a.x0_all) stg4(a.x0_all + idx, z);
+    stg4(a.x_prev + idx, z);
+  } else if (TAIL == TAIL_DDIM) {
+    stg4(a.x0 + idx, z);
+    stg4(a.x_prev + idx, z);
+  } else {
+    stg4(a.x_prev + idx, z);
+  }
+}
+// tail of frame f < T of utterance b (Tb frames valid) at element idx
+template <int TAIL>
+EDTTS_DEV void tail_store(const KArgs& a, int f, int Tb, size_t idx, f4 ev) {
+  if (f < Tb) tail_apply<TAIL>(a, idx, ev);
+  else tail_zero<TAIL>(a, idx);
+}
 
 struct QGlobal {  // q rows in global memory, row-major [Tp][H]: buffer loads (descriptor base = row m0 of the utterance)
   __amdgpu_buffer_rsrc_t rs;
@@ -757,7 +803,7 @@ enum { PART_ALL = 0, PART_ATTN = 1, PART_FFN = 2 };
 //   in the wave's own rows of the h buffer (global), q tiles padded in LDS                                           16.6 ms
 // The first form is used where it fits, the second otherwise (hidden 256: four waves x 32 KiB of residual tiles).
 template <class C, int TAIL, int PART>
-EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b, int m0) {
+EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b, int m0, int Tb, int Sb) {
   constexpr int NF = C::NF;
   const int fq = lane & 15, g = lane >> 4;
   // this wave's parking place for the residual tile, in REGISTER layout (element [nt][ft] of lane l at ((nt*NF + ft)*64 + l) * 16 B:
@@ -832,7 +878,7 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
     if constexpr (!C::DEFER) init_proj_bias();
     if (DIAG_ON(1)) {
       QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * C::H, C::H, fq, g);
-      attention_fused<C, true, C::DEFER ? O_DEFER : O_FUSED>(ql, a.k + (size_t)b * a.Tp * C::H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, a.T, a.window, m0,
+      attention_fused<C, true, C::DEFER ? O_DEFER : O_FUSED>(ql, a.k + (size_t)b * a.Tp * C::H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, Tb, a.window, m0,
                                lane, ring, h, obuf, init_proj_bias, a.stamps ? a.stamps + 8 : nullptr, a.diag_skip);
     }
     if constexpr (C::DEFER) {  // the residual never left the h buffer
@@ -889,11 +935,11 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
     if constexpr (!C::DEFER) zero_h();
     if constexpr (C::Q_IN_LDS) {
       QLds ql(qtile, QLDS, fq, g);
-      attention_fused<C, false, C::DEFER ? O_DEFER : O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, a.S, -1, m0, lane,
+      attention_fused<C, false, C::DEFER ? O_DEFER : O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane,
                                 ring, h, obuf, zero_h, a.stamps ? a.stamps + 40 : nullptr, a.diag_skip);
     } else {
       QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * C::H, C::H, fq, g);
-      attention_fused<C, false, C::DEFER ? O_DEFER : O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, a.S, -1, m0, lane,
+      attention_fused<C, false, C::DEFER ? O_DEFER : O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane,
                                 ring, h, obuf, zero_h);
     }
     if constexpr (C::DEFER) {
@@ -966,7 +1012,7 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
         const int f = m0 + 16 * ft + fq;
         if (f >= a.T) continue;
         const size_t idx = ((size_t)b * a.T + f) * C::MEL + 16 * nt + 4 * g;
-        tail_apply<TAIL>(a, idx, e[ft] + ob);
+        tail_store<TAIL>(a, f, Tb, idx, e[ft] + ob);
       }
     }
   }
@@ -982,6 +1028,18 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
 #ifndef EDTTS_PERSIST
 #define EDTTS_PERSIST 0
 #endif
+// the sampler tail's zeros for a whole skipped tile (frames m0 .. m0 + WF - 1 below T)
+template <class C, int TAIL>
+EDTTS_DEV void tail_zero_tile(const KArgs& a, int b, int m0, int lane) {
+  const int fq = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int ft = 0; ft < C::NF; ++ft) {
+    const int f = m0 + 16 * ft + fq;
+    if (f >= a.T) continue;
+#pragma unroll
+    for (int nt = 0; nt < C::MT; ++nt) tail_zero<TAIL>(a, ((size_t)b * a.T + f) * C::MEL + 16 * nt + 4 * g);
+  }
+}
 template <class C, int TAIL, int PART>
 __global__ __launch_bounds__(C::THREADS, C::DEFER ? 2 : 1) void k_layer(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -991,15 +1049,23 @@ __global__ __launch_bounds__(C::THREADS, C::DEFER ? 2 : 1) void k_layer(KArgs a)
   const int tpu = a.Tp / C::WF, ntiles = a.B * tpu;
   for (int w = remap_block(blockIdx.x, gridDim.x) * C::WAVES + wave; w < ntiles; w += gridDim.x * C::WAVES) {
     const int b = w / tpu;
-    layer_tile<C, TAIL, PART>(a, smem, wave, lane, b, (w - b * tpu) * C::WF);
+    layer_tile<C, TAIL, PART>(a, smem, wave, lane, b, (w - b * tpu) * C::WF, a.T, a.S);  // (experiment: no per-utterance lengths)
   }
 #else
   const TileId tl = wave_tile(a.B, a.Tp, C::WAVES, C::WF);
   if (!tl.valid) return;
+  // (the in-painting sampler's tail has no per-utterance lengths -- edtts_sample_inpaint takes none -- so it keeps its instruction stream)
+  constexpr bool LENS = TAIL != TAIL_VPRED;
+  const int Tb = LENS ? utt_len(a.t_len, tl.b, a.T, a.t_dbl) : a.T;
+  if (LENS && tl.m0 >= live_end(Tb)) {  // a tile the utterance's solo call does not have: only the sampler tail's zeros are left to store
+    if constexpr (TAIL != TAIL_QKV && PART != PART_ATTN) tail_zero_tile<C, TAIL>(a, tl.b, tl.m0, lane);
+    return;
+  }
+  const int Sb = LENS ? utt_len(a.s_len, tl.b, a.S) : a.S;
 #ifdef EDTTS_WAVELOG  // diagnostic builds: when and where every wave of the launch ran (scratch/wavelog.py)
   const unsigned long long wl_r0 = __builtin_amdgcn_s_memrealtime(), wl_c0 = __builtin_amdgcn_s_memtime();
 #endif
-  layer_tile<C, TAIL, PART>(a, smem, wave, lane, tl.b, tl.m0);
+  layer_tile<C, TAIL, PART>(a, smem, wave, lane, tl.b, tl.m0, Tb, Sb);
 #ifdef EDTTS_WAVELOG
   if (a.stamps && lane == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1029,6 +1095,7 @@ struct CtxArgs {
   float *kc, *vcT;  // [L][B][Sp][H], [L][B][VR][Sp]
   unsigned* err;    // index-error word of the workspace
   const float* stream16;  // k_ctx16: bf16 fragment stream (Layout::s_ctx16)
+  const int64_t* s_len;   // per-utterance token counts [B], or null: S for all (rows past them: token id 0 / zero features, as in the solo call)
 };
 // BF16OUT: the cache is written in the bf16 images of edtts_bf16.h (K rows with each head's 32 features in slot order, V^T with
 // each chunk's 32 tokens in slot order); the arithmetic stays fp32 either way (once per call).
@@ -1038,6 +1105,8 @@ __global__ __launch_bounds__(64 * kCtxWaves) void k_ctx(CtxArgs a) {
   if (!tl.valid) return;  // no block-level synchronisation in this kernel
   const int lane = threadIdx.x & 63, fq = lane & 15, g = lane >> 4;
   const int b = tl.b, m0 = tl.m0;
+  const int Sb = utt_len(a.s_len, b, a.S);
+  if (m0 >= live_end(Sb)) return;  // context rows no key chunk of the utterance reaches
   f4 ctx[C::HT][2];
   if (a.sem_feat != nullptr) {
     // context = sem_proj(sem_features)   (decoder.py:83-85)
@@ -1050,7 +1119,7 @@ __global__ __launch_bounds__(64 * kCtxWaves) void k_ctx(CtxArgs a) {
 #pragma unroll
       for (int ft = 0; ft < 2; ++ft) {
         const int s = m0 + 16 * ft + fq;
-        xin[ft] = s < a.S ? ldg4(a.sem_feat + ((size_t)b * a.S + s) * a.SD + 16 * kt + 4 * g) : splat(0.f);
+        xin[ft] = s < Sb ? ldg4(a.sem_feat + ((size_t)b * a.S + s) * a.SD + 16 * kt + 4 * g) : splat(0.f);
       }
 #pragma unroll
       for (int nt = 0; nt < C::HT; ++nt) {
@@ -1066,7 +1135,7 @@ __global__ __launch_bounds__(64 * kCtxWaves) void k_ctx(CtxArgs a) {
 #pragma unroll
     for (int ft = 0; ft < 2; ++ft) {
       const int s = m0 + 16 * ft + fq;
-      long tk = s < a.S ? (long)a.sem_idx[(size_t)b * a.S + s] : 0;
+      long tk = s < Sb ? (long)a.sem_idx[(size_t)b * a.S + s] : 0;
       if (tk < 0 || tk >= a.n_tok) {  // nn.Embedding would raise IndexError: clamp (never fault) and leave a mark for the host
         atomicOr(a.err, (unsigned)EDTTS_IDX_SEM);
         tk = tk < 0 ? 0 : a.n_tok - 1;
@@ -1183,6 +1252,9 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_ctx16(CtxArgs a) {
   const bool valid = tl.valid;  // (a padding wave works on a copy of the last tile -- ring barriers and DMAs -- and stores nothing)
   const int lane = threadIdx.x & 63, fq = lane & 15, g = lane >> 4;
   const int b = tl.b, m0 = tl.m0;
+  // (per-utterance lengths: rows past Sb take token id 0 / zero features as in the solo call; the wave stays in the ring even past
+  // live_end(Sb) -- its rows are never read then, but leaving would break the block's ring barriers)
+  const int Sb = utt_len(a.s_len, b, a.S);
   LdsRing<C> ring;
   ring.start(a.stream16, ring_lds_ctx16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane);
   f4 ctx[C::HT][2];
@@ -1197,7 +1269,7 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_ctx16(CtxArgs a) {
 #pragma unroll
       for (int ft = 0; ft < 2; ++ft) {
         const int s = m0 + 16 * ft + fq;
-        xin[ft] = s < a.S ? ldg4(a.sem_feat + ((size_t)b * a.S + s) * a.SD + 16 * kt + 4 * g) : splat(0.f);
+        xin[ft] = s < Sb ? ldg4(a.sem_feat + ((size_t)b * a.S + s) * a.SD + 16 * kt + 4 * g) : splat(0.f);
       }
 #pragma unroll
       for (int nt = 0; nt < C::HT; ++nt) {
@@ -1213,7 +1285,7 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_ctx16(CtxArgs a) {
 #pragma unroll
     for (int ft = 0; ft < 2; ++ft) {
       const int s = m0 + 16 * ft + fq;
-      long tk = s < a.S ? (long)a.sem_idx[(size_t)b * a.S + s] : 0;
+      long tk = s < Sb ? (long)a.sem_idx[(size_t)b * a.S + s] : 0;
       if (tk < 0 || tk >= a.n_tok) {  // nn.Embedding would raise IndexError: clamp (never fault) and leave a mark for the host
         atomicOr(a.err, (unsigned)EDTTS_IDX_SEM);
         tk = tk < 0 ? 0 : a.n_tok - 1;
@@ -2439,6 +2511,12 @@ struct LmsStepArgs {
   const float *h_new, *h_old;
   float *x0_hist, *x0_all;
 };
+// per-utterance frame / token counts of a (sub-)batch: device int64 [B] each, or null (edtts_*_len)
+struct Lens {
+  const int64_t *t = nullptr, *s = nullptr;
+  bool t_dbl = false;  // t holds token counts (frames = 2 x tokens)
+  Lens at(int off) const { return Lens{t ? t + off : nullptr, s ? s + off : nullptr, t_dbl}; }
+};
 
 #ifdef EDTTS_STAMPS
 static unsigned long long* g_stamps_fwd = nullptr;  // diagnostic builds only, see edtts_debug_set_stamps
@@ -2474,11 +2552,11 @@ struct Launcher {
   static int wave_slots() { return device_simds(); }
 
   static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
-                 const float* sem_feat, hipStream_t st) {
+                 const float* sem_feat, hipStream_t st, const int64_t* s_len = nullptr) {
     CtxArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.S = S; a.Sp = ws.Sp; a.L = lo.L; a.SD = lo.SD; a.n_tok = lo.NTOK; a.max_cpos = lo.MAXCPOS;
-    a.sem_idx = sem_idx; a.sem_feat = sem_feat;
+    a.sem_idx = sem_idx; a.sem_feat = sem_feat; a.s_len = s_len;
     a.tok = blob + lo.tok; a.semp = blob + lo.semp; a.semp_b = blob + lo.semp_b; a.cpe = blob + lo.cpe; a.blob = blob;
     for (int l = 0; l < lo.L; ++l) {
       a.kvd[l] = (unsigned)lo.layer[l].kvd; a.kvn[l] = (unsigned)lo.layer[l].kvn; a.kvu[l] = (unsigned)lo.layer[l].kvu;
@@ -2538,13 +2616,13 @@ struct Launcher {
   static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
                      const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
                      const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
-                     const VpredStepArgs* vp = nullptr) {
+                     const VpredStepArgs* vp = nullptr, Lens ln = Lens{}) {
     if constexpr (HAS_COOP && COW == 0) {
       const int co = coop_choice(B, ws.Tp);
-      if (co == 14) return Launcher<Small>::template forward<4>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp);
-      if (co == 24) return forward<4>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp);
+      if (co == 14) return Launcher<Small>::template forward<4>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp, ln);
+      if (co == 24) return forward<4>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp, ln);
       if constexpr (HAS_CO22) {
-        if (co == 22) return forward<2>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp);
+        if (co == 22) return forward<2>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp, ln);
       }
     }
     // Small grids: with 32 frames per wave fewer waves than SIMDs would be launched (B = 32 at T = 512: 512 waves for 1024 SIMDs;
@@ -2552,11 +2630,12 @@ struct Launcher {
     if constexpr (HAS_SMALL && COW == 0) {
       if (2 * B * (ws.Tp / C::WF) <= wave_slots())  // ... as long as the doubled wave count still runs in one round
         return Launcher<Small>::template forward<0>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st,
-                                                    ddpm, lms, vp);
+                                                    ddpm, lms, vp, ln);
     }
     KArgs a;
     base_args(lo, blob, ws, wsb, B, T, S, window, &a);
     a.x = x; a.cond = cond_row; a.cond_bstride = cond_bstride;
+    a.t_len = ln.t; a.s_len = ln.s; a.t_dbl = ln.t_dbl;
     const int g = grid(B, ws.Tp);
 #if EDTTS_PERSIST
     const int g_layer = g < wave_slots() / C::WAVES ? g : wave_slots() / C::WAVES;
@@ -2765,11 +2844,11 @@ struct Launcher16 {
     return EDTTS_OK;
   }
   static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
-                 const float* sem_feat, hipStream_t st) {
+                 const float* sem_feat, hipStream_t st, const int64_t* s_len = nullptr) {
     CtxArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.S = S; a.Sp = ws.Sp; a.L = lo.L; a.SD = lo.SD; a.n_tok = lo.NTOK; a.max_cpos = lo.MAXCPOS;
-    a.sem_idx = sem_idx; a.sem_feat = sem_feat;
+    a.sem_idx = sem_idx; a.sem_feat = sem_feat; a.s_len = s_len;
     a.tok = blob + lo.tok; a.semp = blob + lo.semp; a.semp_b = blob + lo.semp_b; a.cpe = blob + lo.cpe; a.blob = blob;
     for (int l = 0; l < lo.L; ++l) {
       a.kvd[l] = (unsigned)lo.layer[l].kvd; a.kvn[l] = (unsigned)lo.layer[l].kvn; a.kvu[l] = (unsigned)lo.layer[l].kvu;
@@ -2794,16 +2873,16 @@ struct Launcher16 {
   static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
                      const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
                      const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
-                     const VpredStepArgs* vp = nullptr) {
+                     const VpredStepArgs* vp = nullptr, Lens ln = Lens{}) {
     if constexpr (HAS_WIDE) {
       if (use_wide(B, ws.Tp))
         return Launcher16<Wide>::forward(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st,
-                                         ddpm, lms, vp);
+                                         ddpm, lms, vp, ln);
     }
     if constexpr (HAS_SMALL) {
       if (2 * B * (ws.Tp / C::WF) <= simds())  // (round 4: forced at B = 256, T = 1024 it runs 49.2 ms per call against 33.6)
         return Launcher16<Small>::forward(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st,
-                                          ddpm, lms, vp);
+                                          ddpm, lms, vp, ln);
     }
     KArgs a;
     memset(&a, 0, sizeof(a));
@@ -2813,6 +2892,7 @@ struct Launcher16 {
     a.inp_b = blob + lo.inp_b; a.pe = blob + lo.pe;
     a.fnw = blob + lo.fnw; a.fnb = blob + lo.fnb; a.outp_b = blob + lo.outp_b;
     a.x = x; a.cond = cond_row; a.cond_bstride = cond_bstride;
+    a.t_len = ln.t; a.s_len = ln.s; a.t_dbl = ln.t_dbl;
     const int g = grid(B, ws.Tp);
     const size_t qk_set = (size_t)B * ws.Tp * lo.H / 2, v_set = (size_t)B * ws.VR * ws.Tp / 2;  // bf16: half the floats
     auto set_qkv = [&](int in_set, int out_set) {
@@ -3175,6 +3255,19 @@ int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_sl
   return EDTTS_OK;
 }
 
+// Per-utterance lengths outside [1, T] / [1, S] (edtts_*_len): the kernels clamp them (utt_len); this marks the index-error word.
+__global__ __launch_bounds__(256) void k_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, unsigned* err) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  if ((t_len && (t_len[i] < 1 || t_len[i] > T)) || (s_len && (s_len[i] < 1 || s_len[i] > S))) atomicOr(err, (unsigned)EDTTS_IDX_LEN);
+}
+static int launch_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, float* wsb, hipStream_t st) {
+  if (!t_len && !s_len) return EDTTS_OK;
+  hipLaunchKernelGGL(k_len_check, dim3((B + 255) / 256), dim3(256), 0, st, t_len, s_len, B, T, S, reinterpret_cast<unsigned*>(wsb));
+  LAUNCH_CHECK("k_len_check");
+  return EDTTS_OK;
+}
+
 static int check_shapes(const Layout& lo, int B, int T, int S) {
   if (B < 1 || T < 1 || S < 1) return fail(EDTTS_ERR_ARG, "B=%d T=%d S=%d must be positive", B, T, S);
   if (T > lo.MAXPOS) return fail(EDTTS_ERR_ARG, "T=%d exceeds the positional table (%d rows) -- the reference raises here too", T, lo.MAXPOS);
@@ -3185,6 +3278,12 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
 int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const float* x,
                           const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                           float* eps, void* stream) {
+  return edtts_decoder_forward_len(dims, packed, workspace, B, T, S, x, t, step_idx, sem_idx, sem_features, nullptr, nullptr, eps, stream);
+}
+
+int edtts_decoder_forward_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const float* x,
+                              const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                              const int64_t* t_len, const int64_t* s_len, float* eps, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
@@ -3196,13 +3295,15 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
   float* wsb = (float*)workspace;
   Workspace ws;
   make_workspace(lo, B, T, S, B, &ws);
+  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
   TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, wsb + ws.cond, wsb, st));
   const int bstride = lo.L * 2 * 2 * lo.H;
+  const Lens ln{t_len, s_len};
   EDTTS_DISPATCH(lo, {
     TRY(LN::set_attrs());
-    TRY(LN::ctx(lo, blob, ws, wsb, B, S, sem_features ? nullptr : sem_idx, sem_features, st));
+    TRY(LN::ctx(lo, blob, ws, wsb, B, S, sem_features ? nullptr : sem_idx, sem_features, st, s_len));
     TRY(LN::forward(lo, blob, ws, wsb, B, T, S, dims->window, x, wsb + ws.cond, bstride, TAIL_EPS, eps, nullptr,
-                             nullptr, nullptr, st));
+                             nullptr, nullptr, st, nullptr, nullptr, nullptr, ln));
   });
   return EDTTS_OK;
 }
@@ -3210,6 +3311,13 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
 int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
                    const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host, float* x_work,
                    float* x0_out, void* stream) {
+  return edtts_generate_len(dims, packed, workspace, B, S, sem_idx, nullptr, x_T, num_steps, timesteps_host, coef_host, x_work, x0_out,
+                            stream);
+}
+
+int edtts_generate_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
+                       const int64_t* s_len, const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host,
+                       float* x_work, float* x0_out, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
@@ -3224,15 +3332,17 @@ int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, i
   float* wsb = (float*)workspace;
   SubBatches sb;
   plan_call(lo, B, T, S, num_steps, wsb, &sb);
+  TRY(launch_len_check(nullptr, s_len, B, T, S, wsb, st));
   TRY(launch_cond(lo, blob, nullptr, nullptr, timesteps_host, num_steps, wsb + sb.cond, wsb, st));
   const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
   const size_t per_utt = (size_t)T * lo.MEL;
+  const Lens ln{s_len, s_len, true};  // frames = 2 x tokens (inference.py:31)
   ForkJoin fj;
   TRY(fj.init(sb, st));
   EDTTS_DISPATCH(lo, {
     TRY(LN::set_attrs());
     for (int j = 0; j < sb.n; ++j)
-      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, sem_idx + (size_t)sb.off[j] * S, nullptr, fj.st[j]));
+      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, sem_idx + (size_t)sb.off[j] * S, nullptr, fj.st[j], ln.at(sb.off[j]).s));
     for (int i = 0; i < num_steps; ++i)
       for (int j = 0; j < sb.n; ++j) {
         const size_t o = (size_t)sb.off[j] * per_utt;
@@ -3241,7 +3351,7 @@ int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, i
 #endif
         const float* xin = ((i == 0) ? x_T : x_work) + o;
         TRY(LN::forward(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, xin, wsb + sb.cond + i * row, 0, TAIL_DDIM,
-                        nullptr, x_work + o, x0_out + o, coef_host + 4 * i, fj.st[j]));
+                        nullptr, x_work + o, x0_out + o, coef_host + 4 * i, fj.st[j], nullptr, nullptr, nullptr, ln.at(sb.off[j])));
       }
   });
   return EDTTS_OK;
@@ -3250,6 +3360,14 @@ int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, i
 int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const int64_t* sem_idx,
                            const float* sem_features, const float* x_T, int num_steps, const int64_t* timesteps_host,
                            const float* coef_host, float* hist, float* x0_all, float* x_out, void* stream) {
+  return edtts_sample_multistep_len(dims, packed, workspace, B, T, S, sem_idx, sem_features, nullptr, nullptr, x_T, num_steps,
+                                    timesteps_host, coef_host, hist, x0_all, x_out, stream);
+}
+
+int edtts_sample_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const int64_t* sem_idx,
+                               const float* sem_features, const int64_t* t_len, const int64_t* s_len, const float* x_T, int num_steps,
+                               const int64_t* timesteps_host, const float* coef_host, float* hist, float* x0_all, float* x_out,
+                               void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
@@ -3271,13 +3389,15 @@ int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* work
     const int mode = (int)coef_host[8 * i];
     if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
   }
+  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
+  const Lens ln{t_len, s_len};
   ForkJoin fj;
   TRY(fj.init(sb, st));
   EDTTS_DISPATCH(lo, {
     TRY(LN::set_attrs());
     for (int j = 0; j < sb.n; ++j)
       TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, (sem_features || !sem_idx) ? nullptr : sem_idx + (size_t)sb.off[j] * S,
-                  sem_features ? sem_features + (size_t)sb.off[j] * S * lo.SD : nullptr, fj.st[j]));
+                  sem_features ? sem_features + (size_t)sb.off[j] * S * lo.SD : nullptr, fj.st[j], ln.at(sb.off[j]).s));
     for (int i = 0; i < num_steps; ++i)
       for (int j = 0; j < sb.n; ++j) {
         const size_t o = (size_t)sb.off[j] * per_utt;
@@ -3290,7 +3410,8 @@ int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* work
         ls.h_old = hist + (size_t)(i & 1) * per + o;
         ls.x0_all = x0_all ? x0_all + (size_t)i * per + o : nullptr;
         TRY(LN::forward(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, (i == 0 ? x_T : x_out) + o,
-                        wsb + sb.cond + i * row, 0, TAIL_LMS, nullptr, x_out + o, nullptr, nullptr, fj.st[j], nullptr, &ls));
+                        wsb + sb.cond + i * row, 0, TAIL_LMS, nullptr, x_out + o, nullptr, nullptr, fj.st[j], nullptr, &ls, nullptr,
+                        ln.at(sb.off[j])));
       }
   });
   return EDTTS_OK;
@@ -3299,6 +3420,13 @@ int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* work
 int edtts_sample_ddpm(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
                       const float* x_T, int num_steps, const int64_t* t_all, const float* coef_host, const float* noise_all,
                       uint64_t seed, int64_t batch_offset, float* x_out, void* stream) {
+  return edtts_sample_ddpm_len(dims, packed, workspace, B, S, sem_idx, nullptr, x_T, num_steps, t_all, coef_host, noise_all, seed,
+                               batch_offset, x_out, stream);
+}
+
+int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
+                          const int64_t* s_len, const float* x_T, int num_steps, const int64_t* t_all, const float* coef_host,
+                          const float* noise_all, uint64_t seed, int64_t batch_offset, float* x_out, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
@@ -3316,19 +3444,22 @@ int edtts_sample_ddpm(const EdttsDims* dims, const void* packed, void* workspace
   const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
   const size_t per_step = (size_t)B * T * lo.MEL;
   const size_t per_utt = (size_t)T * lo.MEL;
+  TRY(launch_len_check(nullptr, s_len, B, T, S, wsb, st));
+  const Lens ln{s_len, s_len, true};  // frames = 2 x tokens
   ForkJoin fj;
   TRY(fj.init(sb, st));
   EDTTS_DISPATCH(lo, {
     TRY(LN::set_attrs());
     for (int j = 0; j < sb.n; ++j)
-      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, sem_idx + (size_t)sb.off[j] * S, nullptr, fj.st[j]));
+      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, sem_idx + (size_t)sb.off[j] * S, nullptr, fj.st[j], ln.at(sb.off[j]).s));
     for (int i = 0; i < num_steps; ++i)
       for (int j = 0; j < sb.n; ++j) {
         const size_t o = (size_t)sb.off[j] * per_utt;
         typename LN::DdpmStep ds{noise_all ? noise_all + (size_t)i * per_step + o : nullptr, (unsigned long long)seed,
                                  ((unsigned long long)batch_offset + (unsigned long long)sb.off[j]) * T * lo.MEL, kStreamDdpmStep + (unsigned)i};
         TRY(LN::forward(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, (i == 0 ? x_T : x_out) + o,
-                        wsb + sb.cond + i * row, 0, TAIL_DDPM, nullptr, x_out + o, nullptr, coef_host + 3 * i, fj.st[j], &ds));
+                        wsb + sb.cond + i * row, 0, TAIL_DDPM, nullptr, x_out + o, nullptr, coef_host + 3 * i, fj.st[j], &ds, nullptr,
+                        nullptr, ln.at(sb.off[j])));
       }
   });
   return EDTTS_OK;

@@ -310,14 +310,26 @@ class EdgeDiffusionDecoder(nn.Module):
     # ------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, sem_idx: Optional[torch.Tensor] = None,
-                step_idx: Optional[torch.Tensor] = None, sem_features: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """eps = decoder(x_t [B,T,n_mels], t [B], sem_idx [B,S] | sem_features [B,S,semantic_dim], step_idx [B] | None)."""
+                step_idx: Optional[torch.Tensor] = None, sem_features: Optional[torch.Tensor] = None, *,
+                x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """eps = decoder(x_t [B,T,n_mels], t [B], sem_idx [B,S] | sem_features [B,S,semantic_dim], step_idx [B] | None).
+
+        ``x_lengths`` / ``sem_lengths`` (int64 [B], optional): utterance b has that many valid frames / tokens (a ragged batch,
+        DESIGN.md section 11).  Row b on its frames is then bitwise what the call on utterance b alone returns, nothing past the
+        lengths is read, and eps is 0 past x_lengths[b].  See native.lengths for CPU versus device length tensors."""
         if sem_idx is None and sem_features is None:
             raise ValueError("Either sem_idx or sem_features must be provided")
         B, T, _ = x_t.shape
         S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
+        t_len = native.lengths(x_lengths, B, T, x_t.device, "x_lengths")
+        s_len = native.lengths(sem_lengths, B, S, x_t.device, "sem_lengths")
         packed = self._ensure_packed()
         ws = self.workspace(B, T, S, B, x_t.device)
+        if t_len is not None or s_len is not None:
+            return native.decoder_forward_len(self.dims(), packed, ws, x_t.contiguous(), t.contiguous(),
+                                              None if step_idx is None else step_idx.contiguous(),
+                                              None if sem_features is not None or sem_idx is None else sem_idx.contiguous(),
+                                              None if sem_features is None else sem_features.contiguous(), S, t_len, s_len)
         return native.decoder_forward(self.dims(), packed, ws, x_t.contiguous(), t.contiguous(),
                                       None if step_idx is None else step_idx.contiguous(),
                                       None if sem_features is not None or sem_idx is None else sem_idx.contiguous(),

@@ -28,7 +28,7 @@ class EdgeInference:
     @torch.no_grad()
     def generate_mel(self, sem_idx: torch.Tensor, num_steps: int = 4, temperature: float = 1.0, *,
                      x_T: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                     seed: Optional[int] = None, batch_offset: int = 0) -> torch.Tensor:
+                     seed: Optional[int] = None, batch_offset: int = 0, sem_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Mel [B, 2*S, n_mels] from semantic tokens [B, S] with ``num_steps`` DDIM steps (1..16).
 
         ``x_T`` / ``generator`` / ``seed`` extend the reference signature: the reference draws the start noise from the global
@@ -36,6 +36,11 @@ class EdgeInference:
         ``seed`` the noise comes from the library's counter-based Philox stream at global row ``batch_offset`` (edtts_randn):
         a rank holding rows [lo, hi) of a larger batch passes ``batch_offset=lo`` and draws exactly what one GPU would have
         drawn for those rows.
+
+        ``sem_lengths`` (int64 [B], optional): utterance b has sem_lengths[b] tokens and 2 * sem_lengths[b] frames (a ragged batch,
+        DESIGN.md section 11): row b is then bitwise the call on sem_idx[b:b+1, :S_b] alone with x_T[b:b+1, :2 S_b], and 0 past
+        its frames.  The start noise keeps the padded batch's shape (with ``seed``: the padded batch's draw); only frames
+        < 2 * S_b of it are read.
         """
         if self.encoder is not None and hasattr(self.encoder, "eval"):
             self.encoder.eval()
@@ -58,14 +63,18 @@ class EdgeInference:
             raise IndexError(f"num_steps={num_steps} exceeds the step embedding table ({self.decoder.n_step_emb} rows)")
         coefs = [self.schedule.ddim_coefficients(t, max(t - stride, 0), eta=0.0) for t in timesteps]
 
+        s_len = native.lengths(sem_lengths, B, S, dev, "sem_lengths")
         packed = self.decoder._ensure_packed()
         ws = self.decoder.workspace(B, T_out, S, len(timesteps), dev)
+        if s_len is not None:
+            return native.generate_len(self.decoder.dims(), packed, ws, sem_idx.contiguous(), s_len, x_T, timesteps, coefs)
         return native.generate(self.decoder.dims(), packed, ws, sem_idx.contiguous(), x_T, timesteps, coefs)
 
     @torch.no_grad()
     def sample_ddpm(self, sem_idx: torch.Tensor, num_steps: Optional[int] = None, temperature: float = 1.0, *,
                     x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed: int = 0,
-                    generator: Optional[torch.Generator] = None, batch_offset: int = 0) -> torch.Tensor:
+                    generator: Optional[torch.Generator] = None, batch_offset: int = 0,
+                    sem_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Full-schedule ancestral (DDPM) sampler: for t = T-1 ... T-num_steps: eps = decoder(x, t, sem_idx) (step_idx=None),
         x = schedule.ddpm_step(x, t, eps).  This is the loop BASELINE config 5 names; the reference never wrote it (its
         generate_mel cannot exceed 16 steps) but ships both pieces (train.py:155, schedule.py:204-238).
@@ -73,7 +82,9 @@ class EdgeInference:
         into every step's last layer.  ``noise`` [num_steps, B, 2S, n_mels] injects the per-step draws (parity); otherwise an
         in-kernel Philox generator keyed by (seed, step, global element) supplies them, where ``batch_offset`` is the global index
         of this call's first utterance (a rank sampling rows [lo, hi) of a batch passes lo: shard-count-invariant draws).
-        Graph-capturable; seed and step are baked into a captured graph, so a replay repeats the same noise."""
+        Graph-capturable; seed and step are baked into a captured graph, so a replay repeats the same noise.
+        ``sem_lengths`` (int64 [B], optional): per-utterance token counts, frames = 2 x tokens, as in generate_mel.  The Philox
+        draws stay keyed by the padded [B, 2S, n_mels] layout, so an utterance's noise does not depend on the lengths."""
         B, S = sem_idx.shape
         T_out = 2 * S
         dev = sem_idx.device if sem_idx.is_cuda else torch.device(self.device)
@@ -96,8 +107,11 @@ class EdgeInference:
             if tuple(noise.shape) != (n, B, T_out, self.cfg.n_mels):
                 raise ValueError(f"noise must be [{n}, {B}, {T_out}, {self.cfg.n_mels}]")
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+        s_len = native.lengths(sem_lengths, B, S, dev, "sem_lengths")
         packed = self.decoder._ensure_packed()
         ws = self.decoder.workspace(B, T_out, S, n, dev)
+        if s_len is not None:
+            return native.sample_ddpm_len(self.decoder.dims(), packed, ws, sem_idx, s_len, x_T, t_all, coefs, noise, seed, batch_offset)
         return native.sample_ddpm(self.decoder.dims(), packed, ws, sem_idx, x_T, t_all, coefs, noise, seed, batch_offset)
 
     # alias some callers may expect from the task description; not part of the reference API

@@ -21,7 +21,11 @@ EXPORTED_SYMBOLS = (
     "edtts_ddim_step", "edtts_ddpm_step", "edtts_generate", "edtts_sample_ddpm", "edtts_sample_multistep", "edtts_dsconv_forward", "edtts_profile_enable",
     "edtts_profile_collect", "edtts_randn", "edtts_index_errors", "edtts_sample_inpaint",
     "edtts_mel_to_spec", "edtts_griffin_lim_scratch_floats", "edtts_griffin_lim", "edtts_set_substreams", "edtts_set_coop", "edtts_dsconv_scratch_floats", "edtts_substreams_for",
+    "edtts_decoder_forward_len", "edtts_generate_len", "edtts_sample_ddpm_len", "edtts_sample_multistep_len",
 )
+
+# bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
+EDTTS_IDX_SEM, EDTTS_IDX_STEP, EDTTS_IDX_LEN = 1, 2, 4
 
 
 class EdttsDims(C.Structure):
@@ -80,6 +84,13 @@ def lib() -> C.CDLL:
                                        vp, C.c_uint64, f32, vp, vp]
     L.edtts_sample_multistep.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int64),
                                          C.POINTER(f32), vp, vp, vp, vp]
+    L.edtts_decoder_forward_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.edtts_generate_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int64),
+                                     C.POINTER(f32), vp, vp, vp]
+    L.edtts_sample_ddpm_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, vp, vp, vp, i32, vp, C.POINTER(f32), vp, C.c_uint64,
+                                        C.c_int64, vp, vp]
+    L.edtts_sample_multistep_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32,
+                                             C.POINTER(C.c_int64), C.POINTER(f32), vp, vp, vp, vp]
     L.edtts_dsconv_forward.argtypes = [vp] * 6 + [i32] * 7 + [vp, vp, vp]
     L.edtts_dsconv_scratch_floats.argtypes = [i32] * 7 + [C.POINTER(sz)]
     L.edtts_profile_enable.argtypes = [i32]
@@ -164,6 +175,46 @@ def decoder_forward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tens
     return eps
 
 
+def lengths(n: Optional[torch.Tensor], B: int, hi: int, device, name: str) -> Optional[torch.Tensor]:
+    """Per-utterance lengths for the *_len entry points: None, or an int64 [B] tensor.  A CPU tensor is range-checked here
+    (ValueError outside [1, hi]) and copied to `device` -- not while the stream is capturing (a host-to-device copy cannot be
+    captured: pass a device tensor then).  A device tensor is passed through as it is: the kernels read it at run time (a captured
+    graph serves whatever lengths are copied into it later), clamp values outside [1, hi] and set EDTTS_IDX_LEN."""
+    if n is None:
+        return None
+    if not isinstance(n, torch.Tensor):
+        raise ValueError(f"{name}: expected an int64 tensor of shape [{B}], got {type(n).__name__}")
+    if n.dtype != torch.int64:
+        raise ValueError(f"{name}: expected dtype torch.int64, got {n.dtype}")
+    if tuple(n.shape) != (B,):
+        raise ValueError(f"{name}: expected shape [{B}], got {list(n.shape)}")
+    if n.is_cuda:
+        if device is not None and torch.device(device).type == "cuda" and n.device != torch.device(device):
+            raise ValueError(f"{name}: on {n.device}, the call runs on {device}")
+        return n.contiguous()
+    if B and (int(n.min()) < 1 or int(n.max()) > hi):
+        raise ValueError(f"{name}: lengths must be in [1, {hi}], got [{int(n.min())}, {int(n.max())}]")
+    if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{name}: a CPU length tensor cannot be copied to the device during graph capture; "
+                           "pass a device tensor (and copy new lengths into it before each replay)")
+    return n.to(device)
+
+
+def decoder_forward_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
+                        step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor],
+                        S: int, t_len: Optional[torch.Tensor], s_len: Optional[torch.Tensor]) -> torch.Tensor:
+    """decoder_forward with per-utterance frame / token counts (device int64 [B] or None; see lengths())."""
+    B, T, M = x.shape
+    eps = torch.empty_like(x)
+    lib().edtts_decoder_forward_len(
+        C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(x, torch.float32, "x_t"),
+        _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+        _dev_ptr(sem_features, torch.float32, "sem_features"), _dev_ptr(t_len, torch.int64, "x_lengths"),
+        _dev_ptr(s_len, torch.int64, "sem_lengths"), eps.data_ptr(), _stream(x.device))
+    check_indices(workspace)
+    return eps
+
+
 def generate(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,
              timesteps: Sequence[int], coefs: Sequence[Tuple[float, float, float, float]]) -> torch.Tensor:
     B, S = sem_idx.shape
@@ -177,6 +228,38 @@ def generate(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem
                          _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf, x_work.data_ptr(), x0.data_ptr(), _stream(x_T.device))
     check_indices(workspace)
     return x0
+
+
+def generate_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, s_len: Optional[torch.Tensor],
+                 x_T: torch.Tensor, timesteps: Sequence[int], coefs: Sequence[Tuple[float, float, float, float]]) -> torch.Tensor:
+    """generate with per-utterance token counts s_len (device int64 [B] or None); utterance b has 2 * s_len[b] frames."""
+    B, S = sem_idx.shape
+    n = len(timesteps)
+    ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
+    cf = (C.c_float * (4 * n))(*[float(v) for c in coefs for v in c])
+    x_work = torch.empty_like(x_T)
+    x0 = torch.empty_like(x_T)
+    lib().edtts_generate_len(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+                             _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf,
+                             x_work.data_ptr(), x0.data_ptr(), _stream(x_T.device))
+    check_indices(workspace)
+    return x0
+
+
+def sample_ddpm_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, s_len: Optional[torch.Tensor],
+                    x_T: torch.Tensor, t_all: torch.Tensor, coefs: Sequence[Tuple[float, float, float]], noise_all: Optional[torch.Tensor],
+                    seed: int, batch_offset: int = 0) -> torch.Tensor:
+    """sample_ddpm with per-utterance token counts s_len (device int64 [B] or None); utterance b has 2 * s_len[b] frames."""
+    B, S = sem_idx.shape
+    n = t_all.numel()
+    cf = (C.c_float * (3 * n))(*[float(v) for c in coefs for v in c])
+    out = torch.empty_like(x_T)
+    lib().edtts_sample_ddpm_len(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+                                _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(x_T, torch.float32, "x_T"), n,
+                                _dev_ptr(t_all, torch.int64, "t_all"), cf, _dev_ptr(noise_all, torch.float32, "noise"),
+                                C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_int64(int(batch_offset)), out.data_ptr(), _stream(x_T.device))
+    check_indices(workspace)
+    return out
 
 
 def sample_ddpm(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,
@@ -208,6 +291,27 @@ def sample_multistep(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
     lib().edtts_sample_multistep(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
                                  _dev_ptr(sem_features, torch.float32, "sem_features"), _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf,
                                  hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), out.data_ptr(), _stream(x_T.device))
+    check_indices(workspace)
+    return out, x0_all
+
+
+def sample_multistep_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: Optional[torch.Tensor],
+                         sem_features: Optional[torch.Tensor], S: int, x_T: torch.Tensor, timesteps: Sequence[int],
+                         coefs: Sequence[Sequence[float]], want_intermediates: bool, t_len: Optional[torch.Tensor],
+                         s_len: Optional[torch.Tensor]):
+    """sample_multistep with per-utterance frame / token counts (device int64 [B] or None)."""
+    B, T, M = x_T.shape
+    n = len(timesteps)
+    ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
+    cf = (C.c_float * (8 * n))(*[float(v) for c in coefs for v in c])
+    hist = torch.empty((2, B, T, M), dtype=torch.float32, device=x_T.device)
+    x0_all = torch.empty((n, B, T, M), dtype=torch.float32, device=x_T.device) if want_intermediates else None
+    out = torch.empty_like(x_T)
+    lib().edtts_sample_multistep_len(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S,
+                                     _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"),
+                                     _dev_ptr(t_len, torch.int64, "x_lengths"), _dev_ptr(s_len, torch.int64, "sem_lengths"),
+                                     _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf, hist.data_ptr(),
+                                     None if x0_all is None else x0_all.data_ptr(), out.data_ptr(), _stream(x_T.device))
     check_indices(workspace)
     return out, x0_all
 
@@ -294,7 +398,8 @@ def check_indices(workspace: torch.Tensor) -> None:
         return
     flags = index_errors(workspace)
     if flags:
-        what = [n for b, n in ((1, "sem_idx outside [0, codebook_size)"), (2, "step_idx outside [0, n_step_emb)")) if flags & b]
+        what = [n for b, n in ((EDTTS_IDX_SEM, "sem_idx outside [0, codebook_size)"), (EDTTS_IDX_STEP, "step_idx outside [0, n_step_emb)"),
+                               (EDTTS_IDX_LEN, "a per-utterance length outside [1, T] / [1, S]")) if flags & b]
         raise IndexError("index out of range in the decoder call: " + "; ".join(what))
 
 

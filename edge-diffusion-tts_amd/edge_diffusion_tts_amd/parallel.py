@@ -97,12 +97,27 @@ class _LocalRows:
         return self.rows.new_empty(shape)
 
 
+class _WithLengths:
+    """A four-argument local_generate bound to this rank's rows of sem_lengths: successive calls (the whole shard, or the micro-batches
+    of generate_overlapped in order) take successive rows."""
+
+    def __init__(self, fn: Callable, lengths: torch.Tensor):
+        self.fn, self.lengths, self.pos = fn, lengths, 0
+
+    def __call__(self, sem: torch.Tensor, num_steps: int, x: torch.Tensor):
+        k = sem.shape[0]
+        rows = self.lengths[self.pos:self.pos + k].contiguous()
+        self.pos += k
+        return self.fn(sem, num_steps, x, rows)
+
+
 class ShardedEdgeInference:
     """generate_mel over a process group: every rank passes the SAME global sem_idx (and optionally the same global
     x_T); each computes its contiguous block with `local_generate` and receives the full [B, 2S, n_mels] result.
 
     `local_generate(sem_idx_local, num_steps, x_T_local) -> mel_local` defaults to EdgeInference.generate_mel of the
-    wrapped object.  The start noise depends only on (`seed`, global utterance index), so the result does not depend on the
+    wrapped object.  With ``sem_lengths`` (int64 [B], a ragged batch) each rank's rows of it go along as a fourth argument,
+    ``local_generate(sem, n, x, sem_lengths_local)``; without, the call is the three-argument one.  The start noise depends only on (`seed`, global utterance index), so the result does not depend on the
     number of ranks (bitwise): on the GPU each rank draws ITS rows from the library's counter-based Philox stream at its global
     offset (edtts_randn -- no rank materialises the global noise); CPU tensors (host-logic tests with a stand-in sampler) draw the
     global tensor from a torch generator and slice it."""
@@ -114,12 +129,22 @@ class ShardedEdgeInference:
         self.group = group
         self.micro_batches = int(micro_batches)  # > 1: overlap the all-gather with compute (generate_overlapped; opt-in)
         self._local = local_generate or (lambda sem, n, x: infer.generate_mel(sem, n, x_T=x))
+        self._local_len = local_generate or (lambda sem, n, x, lens: infer.generate_mel(sem, n, x_T=x, sem_lengths=lens))
 
     def generate_mel(self, sem_idx: torch.Tensor, num_steps: int = 4, temperature: float = 1.0, *, x_T: Optional[torch.Tensor] = None,
-                     seed: int = 0, n_mels: Optional[int] = None) -> torch.Tensor:
+                     seed: int = 0, n_mels: Optional[int] = None, sem_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
         B, S = sem_idx.shape
         lo, hi = shard_bounds(B, world, rank)
+        if sem_lengths is not None:
+            if not isinstance(sem_lengths, torch.Tensor) or sem_lengths.dtype != torch.int64 or tuple(sem_lengths.shape) != (B,):
+                raise ValueError(f"sem_lengths: expected an int64 tensor of shape [{B}]")
+            if sem_lengths.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sem_lengths: ShardedEdgeInference is not graph-capturable")
+            lens = sem_lengths
+        else:
+            lens = None
+        local_fn = self._local
         if x_T is None:
             m = n_mels if n_mels is not None else self.infer.cfg.n_mels
             if sem_idx.is_cuda:
@@ -132,12 +157,15 @@ class ShardedEdgeInference:
             else:
                 g = torch.Generator(device=sem_idx.device).manual_seed(seed)
                 x_T = torch.randn(B, 2 * S, m, device=sem_idx.device, generator=g) * temperature
+        if lens is not None:
+            # (the rank's rows of the lengths ride along; generate_overlapped slices them per micro-batch like sem_idx)
+            local_fn = _WithLengths(self._local_len, lens[lo:hi])
         if self.micro_batches > 1 and B % world == 0 and (B // world) % self.micro_batches == 0:
-            return generate_overlapped(self._local, sem_idx[lo:hi], x_T[lo:hi], num_steps, B, self.micro_batches, self.group)
+            return generate_overlapped(local_fn, sem_idx[lo:hi], x_T[lo:hi], num_steps, B, self.micro_batches, self.group)
         if hi == lo:
             # fewer utterances than ranks (e.g. BASELINE config 1, B = 1): this rank has nothing to sample -- the kernels
             # reject B < 1 -- but must still take part in the collective, with an empty shard
             local = x_T.new_empty((0,) + tuple(x_T.shape[1:]))
         else:
-            local = self._local(sem_idx[lo:hi].contiguous(), num_steps, x_T[lo:hi].contiguous())
+            local = local_fn(sem_idx[lo:hi].contiguous(), num_steps, x_T[lo:hi].contiguous())
         return gather_batch(local, B, self.group)

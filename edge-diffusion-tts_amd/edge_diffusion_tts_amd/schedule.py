@@ -237,9 +237,12 @@ class DPMSolverPP:
 
     @torch.no_grad()
     def sample(self, model, x_T: torch.Tensor, sem_features: torch.Tensor, num_steps: int = 10, max_t: Optional[int] = None,
-               return_intermediates: bool = False, *, sem_idx: Optional[torch.Tensor] = None):
+               return_intermediates: bool = False, *, sem_idx: Optional[torch.Tensor] = None,
+               x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None):
         """x_0 = DPM-Solver++(model, x_T [B,T,n_mels], sem_features [B,S,semantic_dim]) in ``num_steps`` (<= 16) steps.
-        ``sem_idx=`` (keyword, a superset of the reference signature) conditions on discrete tokens instead."""
+        ``sem_idx=`` (keyword, a superset of the reference signature) conditions on discrete tokens instead.
+        ``x_lengths`` / ``sem_lengths`` (int64 [B]): per-utterance frame / token counts of a ragged batch (DESIGN.md section 11);
+        x and every intermediate are 0 past an utterance's frames."""
         from . import native
         max_t = max_t or 950
         ts = self.get_time_steps(num_steps, max_t).tolist()
@@ -250,8 +253,17 @@ class DPMSolverPP:
         S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
         if len(ts) > model.n_step_emb:
             raise IndexError(f"num_steps={num_steps} exceeds the step embedding table ({model.n_step_emb} rows)")
+        t_len = native.lengths(x_lengths, B, T, x_T.device, "x_lengths")
+        s_len = native.lengths(sem_lengths, B, S, x_T.device, "sem_lengths")
         packed = model._ensure_packed()
         ws = model.workspace(B, T, S, len(ts), x_T.device)
+        if t_len is not None or s_len is not None:
+            x, x0_all = native.sample_multistep_len(model.dims(), packed, ws, None if sem_features is not None else sem_idx.contiguous(),
+                                                    None if sem_features is None else sem_features.contiguous(), S,
+                                                    x_T.to(torch.float32).contiguous(), ts, coefs, return_intermediates, t_len, s_len)
+            if return_intermediates:
+                return x, list(x0_all.unbind(0))
+            return x
         x, x0_all = native.sample_multistep(model.dims(), packed, ws, None if sem_features is not None else sem_idx.contiguous(),
                                             None if sem_features is None else sem_features.contiguous(), S,
                                             x_T.to(torch.float32).contiguous(), ts, coefs, return_intermediates)

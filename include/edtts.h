@@ -49,7 +49,8 @@ enum {
  * clamped into range by a kernel (the kernels never fault on bad indices). */
 enum {
   EDTTS_IDX_SEM = 1, /* sem_idx outside [0, codebook_size)   (nn.Embedding, models/decoder.py:88) */
-  EDTTS_IDX_STEP = 2 /* step_idx outside [0, n_step_emb)     (models/decoder.py:79-80) */
+  EDTTS_IDX_STEP = 2, /* step_idx outside [0, n_step_emb)     (models/decoder.py:79-80) */
+  EDTTS_IDX_LEN = 4   /* a per-utterance length (edtts_*_len) outside [1, T] / [1, S]; the kernels clamp it */
 };
 
 /* Decoder hyper-parameters: the CFG fields read by models/decoder.py:17-64 plus table sizes. */
@@ -141,6 +142,21 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
                           const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
                           const float* sem_features, float* eps, void* stream);
 
+/* ---- per-utterance lengths (ragged batches) -----------------------------------------------------------------------------
+ * The *_len entry points below take the arguments of their twins plus device int64 [B] length arrays: t_len (frames T_b) and
+ * s_len (tokens S_b); where frames are 2 x tokens (edtts_generate_len, edtts_sample_ddpm_len) s_len alone.  NULL = full length
+ * (T / S for every utterance); the plain entry points are these calls with NULL.  Contract, for 1 <= T_b <= T, 1 <= S_b <= S:
+ *   - row b on frames [0, T_b) is bitwise what the same entry point returns for utterance b alone (B = 1, T = T_b, S = S_b, the
+ *     same t / step_idx / injected noise).  In-kernel Philox noise is keyed by the element's index in the padded [B, T, n_mels]
+ *     layout, as without lengths, so it does not depend on the lengths;
+ *   - nothing past an utterance's lengths is read: not the padding of x / x_T, of sem_features or of sem_idx (no index check there);
+ *   - every output (eps, x0, x, the multistep x0 history and intermediates) is exactly 0 on frames [T_b, T);
+ *   - the lengths are read by the kernels at run time: a captured graph serves any length mix copied into the same arrays.
+ * Values outside [1, T] / [1, S] are clamped into range and set EDTTS_IDX_LEN.  Workspace and blob sizes are those of the twin. */
+int edtts_decoder_forward_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S,
+                              const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                              const float* sem_features, const int64_t* t_len, const int64_t* s_len, float* eps, void* stream);
+
 /* ---- DDIM update  (schedule.py:157-202, DiffusionSchedule.get_ddim_step) --------------------------------
  * alpha_bar [n_table] fp32 table; t, t_prev [B] int64 (t_prev < 0 -> alpha_bar_prev = 1); n_per_batch =
  * T*n_mels; eta >= 0; noise [B,T,n_mels] or NULL (required when eta > 0).  Writes x_prev and x0 (clamped
@@ -170,6 +186,9 @@ int edtts_ddpm_step(const float* alphas, const float* alpha_bar, const float* be
 int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, int B, int S,
                    const int64_t* sem_idx, const float* x_T, int num_steps, const int64_t* timesteps_host,
                    const float* coef_host, float* x_work, float* x0_out, void* stream);
+int edtts_generate_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
+                       const int64_t* s_len, const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host,
+                       float* x_work, float* x0_out, void* stream);
 
 /* ---- full-schedule ancestral sampler  (BASELINE config 5; schedule.py:204-238 applied num_steps times) -----------
  * The loop the reference implies but never wrote: for i = 0 .. num_steps-1, t = t_first - i:
@@ -188,6 +207,9 @@ int edtts_sample_ddpm(const EdttsDims* dims, const void* packed, void* workspace
                       const int64_t* sem_idx, const float* x_T, int num_steps, const int64_t* t_all,
                       const float* coef_host, const float* noise_all, uint64_t seed, int64_t batch_offset, float* x_out,
                       void* stream);
+int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
+                          const int64_t* s_len, const float* x_T, int num_steps, const int64_t* t_all, const float* coef_host,
+                          const float* noise_all, uint64_t seed, int64_t batch_offset, float* x_out, void* stream);
 
 /* ---- start noise  (inference.py:33: torch.randn(B, T_out, n_mels) * temperature) ---------------------------------
  * out[i] = scale * N(0,1) drawn from the Philox4x32-10 stream (seed, stream_id) at GLOBAL element index elem_offset + i, for
@@ -220,6 +242,10 @@ int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* work
                            const int64_t* sem_idx, const float* sem_features, const float* x_T, int num_steps,
                            const int64_t* timesteps_host, const float* coef_host, float* hist, float* x0_all,
                            float* x_out, void* stream);
+int edtts_sample_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S,
+                               const int64_t* sem_idx, const float* sem_features, const int64_t* t_len, const int64_t* s_len,
+                               const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host, float* hist,
+                               float* x0_all, float* x_out, void* stream);
 
 /* ---- long-form in-painting sampler  (/root/reference/inference_pipeline.py:97-140 inpaint_student_sample, :145-196
  * inpaint_teacher_refine) -------------------------------------------------------------------------------------------
