@@ -717,13 +717,15 @@ EDTTS_DEV void tail_apply(const KArgs& a, size_t idx, f4 ev) {
     stg4(a.x_prev + idx, xn);
   } else if (TAIL == TAIL_VPRED) {
     // v-prediction step of the in-painting samplers, optionally with classifier-free guidance (inference_pipeline.py:125-132,179-192)
+    // Without guidance the combine's result is discarded by a select, not skipped by a branch: with the branch and per-utterance
+    // lengths, the 32/2/80 instance split a 16-SGPR kernel-argument tuple and left its 64-byte spill slot in the private segment
+    // (DESIGN.md section 12).  The unguided load reads x again (any valid row would do).
+    const bool guided = a.v_uncond != nullptr;
     const f4 xv = ldg4(a.x + idx);
-    f4 v = ev, xn;
-    if (a.v_uncond) {
-      const f4 vu = ldg4(a.v_uncond + idx);
+    const f4 vu = ldg4((guided ? a.v_uncond : a.x) + idx);
+    f4 v, xn;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = cfg_combine(ev[r], vu[r], a.vp.cfg);
-    }
+    for (int r = 0; r < 4; ++r) v[r] = guided ? cfg_combine(ev[r], vu[r], a.vp.cfg) : ev[r];
 #pragma unroll
     for (int r = 0; r < 4; ++r) xn[r] = vpred_elem(xv[r], v[r], a.vp);
     stg4(a.x_prev + idx, xn);
@@ -1054,14 +1056,12 @@ __global__ __launch_bounds__(C::THREADS, C::DEFER ? 2 : 1) void k_layer(KArgs a)
 #else
   const TileId tl = wave_tile(a.B, a.Tp, C::WAVES, C::WF);
   if (!tl.valid) return;
-  // (the in-painting sampler's tail has no per-utterance lengths -- edtts_sample_inpaint takes none -- so it keeps its instruction stream)
-  constexpr bool LENS = TAIL != TAIL_VPRED;
-  const int Tb = LENS ? utt_len(a.t_len, tl.b, a.T, a.t_dbl) : a.T;
-  if (LENS && tl.m0 >= live_end(Tb)) {  // a tile the utterance's solo call does not have: only the sampler tail's zeros are left to store
+  const int Tb = utt_len(a.t_len, tl.b, a.T, a.t_dbl);
+  if (tl.m0 >= live_end(Tb)) {  // a tile the utterance's solo call does not have: only the sampler tail's zeros are left to store
     if constexpr (TAIL != TAIL_QKV && PART != PART_ATTN) tail_zero_tile<C, TAIL>(a, tl.b, tl.m0, lane);
     return;
   }
-  const int Sb = LENS ? utt_len(a.s_len, tl.b, a.S) : a.S;
+  const int Sb = utt_len(a.s_len, tl.b, a.S);
 #ifdef EDTTS_WAVELOG  // diagnostic builds: when and where every wave of the launch ran (scratch/wavelog.py)
   const unsigned long long wl_r0 = __builtin_amdgcn_s_memrealtime(), wl_c0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -3256,14 +3256,15 @@ int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_sl
 }
 
 // Per-utterance lengths outside [1, T] / [1, S] (edtts_*_len): the kernels clamp them (utt_len); this marks the index-error word.
-__global__ __launch_bounds__(256) void k_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, unsigned* err) {
+// t_min > 1: frame counts below it are flagged too (edtts_sample_inpaint_len: an utterance shorter than the known overlap)
+__global__ __launch_bounds__(256) void k_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, int t_min, unsigned* err) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  if ((t_len && (t_len[i] < 1 || t_len[i] > T)) || (s_len && (s_len[i] < 1 || s_len[i] > S))) atomicOr(err, (unsigned)EDTTS_IDX_LEN);
+  if ((t_len && (t_len[i] < t_min || t_len[i] > T)) || (s_len && (s_len[i] < 1 || s_len[i] > S))) atomicOr(err, (unsigned)EDTTS_IDX_LEN);
 }
-static int launch_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, float* wsb, hipStream_t st) {
+static int launch_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, float* wsb, hipStream_t st, int t_min = 1) {
   if (!t_len && !s_len) return EDTTS_OK;
-  hipLaunchKernelGGL(k_len_check, dim3((B + 255) / 256), dim3(256), 0, st, t_len, s_len, B, T, S, reinterpret_cast<unsigned*>(wsb));
+  hipLaunchKernelGGL(k_len_check, dim3((B + 255) / 256), dim3(256), 0, st, t_len, s_len, B, T, S, t_min, reinterpret_cast<unsigned*>(wsb));
   LAUNCH_CHECK("k_len_check");
   return EDTTS_OK;
 }
@@ -3466,32 +3467,50 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
 }
 
 // x[b][f < overlap][:] = c_known * known[b][f][:] + c_noise * noise   (noise: injected [B, overlap, MEL] or Philox keyed by
-// (seed, step, global element of the [B, overlap, MEL] tensor)); c_noise = 0 -> exact copy of the known frames
+// (seed, step, global element of the [B, overlap, MEL] tensor)); c_noise = 0 -> exact copy of the known frames.
+// Per-row seeds (device uint64 [B], or null): row b draws with seeds[b] at its ROW-LOCAL element index -- the draws of the same call
+// made on row b alone.  Per-row frame counts t_len (or null): row b injects its first min(overlap, T_b) frames only.
 __global__ __launch_bounds__(256) void k_inpaint_inject(float* x, const float* known, const float* noise, int B, int T, int ov, int MEL,
-                                                        float c_known, float c_noise, unsigned long long seed, unsigned step) {
+                                                        float c_known, float c_noise, unsigned long long seed, unsigned step,
+                                                        const unsigned long long* seeds, const int64_t* t_len) {
   const size_t per = (size_t)ov * MEL / 4, n4 = (size_t)B * per;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = i / per, r = i - b * per;
+    const int Tb = t_len ? utt_len_of(t_len[b], T, false) : T;  // (utt_len_lane called from here changed k_gen_embed's code)
+    const size_t live = Tb < ov ? (size_t)Tb * MEL : 4 * per;  // elements of this row's injected frames
+    if (4 * r >= live) continue;
     const f4 kv = ldg4(known + 4 * i);
     f4 o = kv;
     if (c_noise != 0.f) {
-      const f4 nz = noise ? ldg4(noise + 4 * i) : philox_normal4(seed, step, i);
+      const f4 nz = noise ? ldg4(noise + 4 * i) : (seeds ? philox_normal4(seeds[b], step, r) : philox_normal4(seed, step, i));
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = qsample_elem(kv[e], c_known, nz[e], c_noise);
     }
-    stg4(x + (b * T) * MEL + 4 * r, o);
+    if (4 * r + 4 <= live) {
+      stg4(x + (b * T) * MEL + 4 * r, o);
+    } else {  // (a row shorter than the overlap whose last frame ends inside this quad: n_mels % 4 != 0)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (4 * r + e < live) x[(b * T) * MEL + 4 * r + e] = o[e];
+    }
   }
 }
 
 // ... one element per thread, for shapes whose rows are not float4-aligned (generic path, n_mels % 4 != 0): the same values (element e
-// of the [B, overlap, MEL] noise tensor is lane e & 3 of Philox draw e >> 2)
+// of the [B, overlap, MEL] noise tensor is lane e & 3 of Philox draw e >> 2; with per-row seeds e counts from the row's start)
 __global__ __launch_bounds__(256) void k_inpaint_inject1(float* x, const float* known, const float* noise, int B, int T, int ov, int MEL,
-                                                         float c_known, float c_noise, unsigned long long seed, unsigned step) {
+                                                         float c_known, float c_noise, unsigned long long seed, unsigned step,
+                                                         const unsigned long long* seeds, const int64_t* t_len) {
   const size_t per = (size_t)ov * MEL, n = (size_t)B * per;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = i / per, r = i - b * per;
+    const int Tb = t_len ? utt_len_of(t_len[b], T, false) : T;
+    if (Tb < ov && r >= (size_t)Tb * MEL) continue;
     float o = known[i];
-    if (c_noise != 0.f) o = qsample_elem(o, c_known, noise ? noise[i] : philox_normal4(seed, step, i >> 2)[(int)(i & 3)], c_noise);
+    if (c_noise != 0.f) {
+      const float nz = noise ? noise[i] : (seeds ? philox_normal4(seeds[b], step, r >> 2)[(int)(r & 3)] : philox_normal4(seed, step, i >> 2)[(int)(i & 3)]);
+      o = qsample_elem(o, c_known, nz, c_noise);
+    }
     x[(b * T) * MEL + r] = o;
   }
 }
@@ -3500,6 +3519,16 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
                          const float* sem_features, const float* zero_features, float* x, int num_steps,
                          const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel, int overlap_len,
                          const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond, void* stream) {
+  return edtts_sample_inpaint_len(dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all,
+                                  step_all, coef_host, known_mel, overlap_len, noise_k, seed, cfg_scale, v_uncond, nullptr, nullptr, nullptr,
+                                  stream);
+}
+
+int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
+                             const float* sem_features, const float* zero_features, float* x, int num_steps,
+                             const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                             int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                             const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
@@ -3515,8 +3544,10 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
   float* wsu = (float*)workspace_uncond;
   Workspace ws;
   make_workspace(lo, B, T, S, num_steps, &ws);
+  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st, known_mel ? overlap_len : 1));
   TRY(launch_cond(lo, blob, t_all, step_all, nullptr, num_steps, wsb + ws.cond, wsb, st));
   const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  const Lens ln{t_len, s_len};
   const bool inject_vec = ((size_t)overlap_len * lo.MEL) % 4 == 0 && ((size_t)T * lo.MEL) % 4 == 0;
   auto inject = [&](float ck, float cn, int step) {
     const size_t n4 = (size_t)B * overlap_len * lo.MEL / (inject_vec ? 4 : 1);
@@ -3524,12 +3555,12 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
     if (bx > 2048) bx = 2048;
     hipLaunchKernelGGL(inject_vec ? k_inpaint_inject : k_inpaint_inject1, dim3((unsigned)bx), dim3(256), 0, st, x, known_mel,
                        noise_k ? noise_k + (size_t)step * B * overlap_len * lo.MEL : nullptr, B, T, overlap_len, lo.MEL, ck, cn,
-                       (unsigned long long)seed, kStreamInpaintStep + (unsigned)step);
+                       (unsigned long long)seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(seeds), t_len);
   };
   EDTTS_DISPATCH(lo, {
     TRY(LN::set_attrs());
-    TRY(LN::ctx(lo, blob, ws, wsb, B, S, nullptr, sem_features, st));
-    if (guided) TRY(LN::ctx(lo, blob, ws, wsu, B, S, nullptr, zero_features, st));
+    TRY(LN::ctx(lo, blob, ws, wsb, B, S, nullptr, sem_features, st, s_len));
+    if (guided) TRY(LN::ctx(lo, blob, ws, wsu, B, S, nullptr, zero_features, st, s_len));  // (the solo call's zero context has S_b rows)
     for (int i = 0; i < num_steps; ++i) {
       const float* c = coef_host + 4 * i;  // {sqrt_ab[t], sqrt_1mab[t], sqrt(ab[t_next]), sqrt(1 - ab[t_next])}
       if (known_mel) {
@@ -3540,11 +3571,11 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
       if (guided) {
         // the unconditional pass shares nothing with the conditional one but x and the conditioning rows
         TRY(LN::forward(lo, blob, ws, wsu, B, T, S, dims->window, x, wsb + ws.cond + i * row, 0, TAIL_EPS, v_uncond, nullptr, nullptr,
-                        nullptr, st));
+                        nullptr, st, nullptr, nullptr, nullptr, ln));
         vp.v_uncond = v_uncond;
       }
       TRY(LN::forward(lo, blob, ws, wsb, B, T, S, dims->window, x, wsb + ws.cond + i * row, 0, TAIL_VPRED, nullptr, x, nullptr, nullptr,
-                      st, nullptr, nullptr, &vp));
+                      st, nullptr, nullptr, &vp, ln));
     }
     if (known_mel) {
       inject(1.0f, 0.0f, 0);  // final force (inference_pipeline.py:135-136)
@@ -3678,6 +3709,40 @@ int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_
   hipLaunchKernelGGL(k_randn, dim3((unsigned)bx), dim3(256), 0, (hipStream_t)stream, out, n, (unsigned long long)seed, (unsigned)stream_id,
                      (unsigned long long)elem_offset, scale);
   LAUNCH_CHECK("k_randn");
+  return EDTTS_OK;
+}
+
+// row b of [B, n] = the first n draws of the Philox stream (seeds[b], stream_id): element e is lane e & 3 of draw e >> 2, as in k_randn
+__global__ __launch_bounds__(256) void k_randn_rows(float* out, int B, size_t n, const unsigned long long* seeds, unsigned stream_id,
+                                                    float scale) {
+  const size_t q = (n + 3) >> 2, nq = (size_t)B * q;  // quads per row, all quads
+  const bool vec = (n & 3) == 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / q, r = i - b * q;
+    const f4 v = philox_normal4(seeds[b], stream_id, r) * scale;
+    float* o = out + b * n + 4 * r;
+    if (vec) {
+      stg4(o, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (4 * r + e < n) o[e] = v[e];
+    }
+  }
+}
+
+int edtts_randn_rows(float* out, int B, size_t n_per_row, const uint64_t* seeds, uint32_t stream_id, float scale, void* stream) {
+  if (B < 0) return fail(EDTTS_ERR_ARG, "B=%d < 0", B);
+  if (stream_id >= kStreamDdpmStep) return fail(EDTTS_ERR_ARG, "stream_id %u is reserved for the samplers' per-step draws (>= 0x10000)", stream_id);
+  if (B == 0 || n_per_row == 0) return EDTTS_OK;
+  if (!out || !seeds) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if ((n_per_row & 3) == 0 && ((uintptr_t)out & 15)) return fail(EDTTS_ERR_ARG, "out must be 16-byte aligned");
+  const size_t nq = (size_t)B * ((n_per_row + 3) / 4);
+  size_t bx = (nq + 255) / 256;
+  if (bx > 4096) bx = 4096;
+  hipLaunchKernelGGL(k_randn_rows, dim3((unsigned)bx), dim3(256), 0, (hipStream_t)stream, out, B, n_per_row,
+                     reinterpret_cast<const unsigned long long*>(seeds), (unsigned)stream_id, scale);
+  LAUNCH_CHECK("k_randn_rows");
   return EDTTS_OK;
 }
 

@@ -8,11 +8,13 @@ step, optional classifier-free guidance against an all-zero context), each runni
 kernel, guidance combine + x0 / eps / next-x update are fused into the last transformer layer.  ``generate_long`` is the
 reference's chunk loop (:296-367) as written: per-chunk de-normalisation, exp, cross-fade of LINEAR mels with the trapezoid
 window, division by the summed weights (sequential: every chunk is conditioned on the tail of the previous one).
+``generate_long_batch`` runs that loop for many utterances in lockstep: chunk i of every utterance that has one is refined in ONE
+batched call (per-utterance semantic lengths and seeds), and each utterance's result is bitwise its ``generate_long`` alone.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -41,10 +43,16 @@ class InpaintSampler:
         return out
 
     def _run(self, x: torch.Tensor, sem_features: torch.Tensor, times: List[int], step_idx: int, known_mel, overlap_len: int,
-             cfg_scale: float, noise_k, seed: int) -> torch.Tensor:
+             cfg_scale: float, noise_k, seed: int, x_lengths=None, sem_lengths=None, seeds=None) -> torch.Tensor:
         dec = self.decoder
         B, T, M = x.shape
         S = sem_features.shape[1]
+        if (known_mel is not None and isinstance(x_lengths, torch.Tensor) and not x_lengths.is_cuda and B
+                and int(x_lengths.min()) < overlap_len):
+            raise ValueError(f"x_lengths: every utterance needs at least overlap_len = {overlap_len} frames, got {int(x_lengths.min())}")
+        t_len = native.lengths(x_lengths, B, T, x.device, "x_lengths")
+        s_len = native.lengths(sem_lengths, B, S, x.device, "sem_lengths")
+        sd = None if seeds is None else native.seed_tensor(seeds, B, x.device)
         n = len(times)
         dev = x.device
         x = x.to(torch.float32).contiguous().clone()
@@ -74,42 +82,68 @@ class InpaintSampler:
         else:
             noise_k = None
         p = native._dev_ptr
-        native.lib().edtts_sample_inpaint(
+        native.lib().edtts_sample_inpaint_len(
             C.byref(dec.dims()), packed.data_ptr(), ws.data_ptr(), None if ws_u is None else ws_u.data_ptr(), B, T, S,
             p(sem_features, torch.float32, "sem_features"), p(zeros, torch.float32, "zeros"), p(x, torch.float32, "x"), n,
             t_all.data_ptr(), s_all.data_ptr(), cf, p(known_mel, torch.float32, "known_mel"), int(overlap_len),
             p(noise_k, torch.float32, "noise_k"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(cfg_scale),
-            None if v_u is None else v_u.data_ptr(), native._stream(dev))
+            None if v_u is None else v_u.data_ptr(), p(t_len, torch.int64, "x_lengths"), p(s_len, torch.int64, "sem_lengths"),
+            p(sd, torch.int64, "seeds"), native._stream(dev))
         native.check_indices(ws)
         return x
 
     @torch.no_grad()
     def inpaint_student_sample(self, x_shape, sem_features, known_mel=None, overlap_len: int = 0, num_steps: int = 4, *,
-                               x_init: Optional[torch.Tensor] = None, noise_k: Optional[torch.Tensor] = None, seed: int = 0):
+                               x_init: Optional[torch.Tensor] = None, noise_k: Optional[torch.Tensor] = None, seed: int = 0,
+                               x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None,
+                               seeds: Optional[Sequence[int]] = None):
         """inference_pipeline.py:97-140.  ``x_init`` / ``noise_k`` inject the draws the reference takes from torch.randn /
         torch.randn_like (parity); otherwise the start noise comes from the library's Philox stream and the per-step q_sample
-        noise from the in-kernel generator."""
+        noise from the in-kernel generator.
+
+        Ragged batches: ``x_lengths`` / ``sem_lengths`` (int64 [B], see native.lengths) and ``seeds`` (B ints,
+        or a device int64 [B] tensor) make row b bitwise the call on utterance b alone (its first x_lengths[b] frames and
+        sem_lengths[b] feature rows, ``seed=seeds[b]``); frames past x_lengths[b] come out as exact zeros."""
         dev = sem_features.device
-        x = x_init.to(dev) if x_init is not None else native.randn(tuple(x_shape), dev, seed=seed, stream_id=0x51)
+        if x_init is not None:
+            x = x_init.to(dev)
+        elif seeds is not None:  # row b = the solo call's start noise (a prefix of the row when the row is longer)
+            x = native.randn_rows(tuple(x_shape), dev, seeds, stream_id=0x51)
+        else:
+            x = native.randn(tuple(x_shape), dev, seed=seed, stream_id=0x51)
         times = linspace_times(self.cfg.diff_steps - 1, num_steps)
-        return self._run(x, sem_features, times, 3, known_mel, overlap_len if known_mel is not None else 0, 1.0, noise_k, seed)
+        return self._run(x, sem_features, times, 3, known_mel, overlap_len if known_mel is not None else 0, 1.0, noise_k, seed,
+                         x_lengths, sem_lengths, seeds)
 
     @torch.no_grad()
     def inpaint_teacher_refine(self, x_coarse, sem_features, known_mel=None, overlap_len: int = 0, strength: float = 0.2,
                                steps: int = 10, cfg_scale: float = 1.0, *, noise: Optional[torch.Tensor] = None,
-                               noise_k: Optional[torch.Tensor] = None, seed: int = 0):
-        """inference_pipeline.py:145-196: q_sample(x_coarse, t_start = int(T * strength)) then ``steps`` guided v-prediction steps."""
+                               noise_k: Optional[torch.Tensor] = None, seed: int = 0, x_lengths: Optional[torch.Tensor] = None,
+                               sem_lengths: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None):
+        """inference_pipeline.py:145-196: q_sample(x_coarse, t_start = int(T * strength)) then ``steps`` guided v-prediction steps.
+        ``x_lengths`` / ``sem_lengths`` / ``seeds``: as inpaint_student_sample (with ``seeds`` the q_sample noise of row b is the solo
+        call's)."""
         dev = x_coarse.device
         t_start = int(self.cfg.diff_steps * strength)
         if not 0 <= t_start < self.cfg.diff_steps:
             raise IndexError(f"t_start = int(diff_steps * strength) = {t_start} is outside the schedule tables "
                              "(the reference indexes them with it too)")
-        nz = noise.to(dev) if noise is not None else native.randn(tuple(x_coarse.shape), dev, seed=seed, stream_id=0x52)
-        sab = self.schedule._host_t["sqrt_alpha_bar"][t_start].to(dev)
-        s1m = self.schedule._host_t["sqrt_one_minus_alpha_bar"][t_start].to(dev)
+        if noise is not None:
+            nz = noise.to(dev)
+        elif seeds is not None:
+            nz = native.randn_rows(tuple(x_coarse.shape), dev, seeds, stream_id=0x52)
+        else:
+            nz = native.randn(tuple(x_coarse.shape), dev, seed=seed, stream_id=0x52)
+        key = ("q_sample", t_start, str(dev))
+        cached = self._dev_cache.get(key)
+        if cached is None:  # (device copies made once, as in _run: a call with device lengths and seeds is capturable)
+            cached = self._dev_cache.setdefault(key, (self.schedule._host_t["sqrt_alpha_bar"][t_start].to(dev),
+                                                      self.schedule._host_t["sqrt_one_minus_alpha_bar"][t_start].to(dev)))
+        sab, s1m = cached
         x = sab * x_coarse.to(torch.float32) + s1m * nz  # schedule.q_sample (schedule.py:81-84): plain torch on the device
         times = linspace_times(t_start, steps)
-        return self._run(x, sem_features, times, 0, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k, seed)
+        return self._run(x, sem_features, times, 0, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k, seed,
+                         x_lengths, sem_lengths, seeds)
 
     @staticmethod
     def latent_slices(n_chunks: int, hop_samples: int, chunk_samples: int, sample_rate: int) -> List[tuple]:
@@ -170,45 +204,165 @@ class InpaintSampler:
         over-states them (8160 instead of 8000 overlap samples) and the chunk count can come out one short.  A caller that mirrors
         the reference passes its sample counts here and they are used verbatim for the chunk count and the semantic slices; the
         defaults (frames * hop_length) serve callers that think in frames.
-        The chunk loop is sequential by construction (chunk i is conditioned on the tail of chunk i-1)."""
-        dev = sem_features.device
-        M = self.cfg.n_mels
+        The chunk loop is sequential by construction (chunk i is conditioned on the tail of chunk i-1).
+        This is generate_long_batch of one utterance (same results): every check runs before the first chunk, the messages name
+        "utterance 0", and a ``latent_slices`` or ``draws`` list shorter than the chunk count is a ValueError (an IndexError at
+        that chunk before)."""
+        return self.generate_long_batch([sem_features], [total_frames], chunk_frames, overlap_frames, [chunk_stats], seeds=[seed],
+                                        strength=strength, steps=steps, cfg_scale=cfg_scale,
+                                        latent_slices=None if latent_slices is None else [latent_slices], hop_length=hop_length,
+                                        sample_rate=sample_rate, draws=None if draws is None else [draws], chunk_samples=chunk_samples,
+                                        overlap_samples=overlap_samples,
+                                        total_samples=None if total_samples is None else [total_samples])[0]
+
+    def plan_long_batch(self, sem_rows: Sequence[int], total_frames: Sequence[int], chunk_frames: int, overlap_frames: int,
+                        chunk_stats: Sequence, seeds: Sequence[int], *, latent_slices=None, hop_length: Optional[int] = None,
+                        sample_rate: Optional[int] = None, draws=None, chunk_samples: Optional[int] = None,
+                        overlap_samples: Optional[int] = None, total_samples=None) -> List[dict]:
+        """The checks and the chunk plan of generate_long_batch, host only: per utterance a dict with ``n_chunks`` and ``slices`` (the
+        [start, end) feature rows of each chunk, clipped to the utterance's ``sem_rows``).  Raises what generate_long raises, naming the
+        utterance."""
+        N = len(sem_rows)
+
+        def per_utt(name, v, required):
+            if v is None:
+                if required:
+                    raise ValueError(f"{name}: one entry per utterance is required")
+                return [None] * N
+            v = list(v)
+            if len(v) != N:
+                raise ValueError(f"{name}: expected {N} entries (one per utterance), got {len(v)}")
+            return v
+        total_frames = per_utt("total_frames", total_frames, True)
+        chunk_stats = per_utt("chunk_stats", chunk_stats, True)
+        seeds = per_utt("seeds", seeds, True)
+        latent_slices = per_utt("latent_slices", latent_slices, False)
+        draws = per_utt("draws", draws, False)
+        total_samples = per_utt("total_samples", total_samples, False)
         if not 0 <= overlap_frames < chunk_frames:
             raise ValueError(f"need 0 <= overlap_frames < chunk_frames, got {overlap_frames} / {chunk_frames}")
         hop_frames = chunk_frames - overlap_frames
         hop_length = int(hop_length if hop_length is not None else self.cfg.hop_length)
         sample_rate = int(sample_rate if sample_rate is not None else self.cfg.sample_rate)
-        n_chunks, chunk_samples, hop_samples = self.chunk_plan(total_frames, chunk_frames, overlap_frames, hop_length, chunk_samples,
-                                                                overlap_samples, total_samples)
-        if len(chunk_stats) != n_chunks:
-            raise ValueError(f"chunk_stats must hold {n_chunks} (mean, std) pairs, got {len(chunk_stats)}")
-        if latent_slices is None:
-            latent_slices = self.latent_slices(n_chunks, hop_samples, chunk_samples, sample_rate)
-        estimated = total_frames + 1000  # :227 (room for the last, ragged chunk)
-        if (n_chunks - 1) * hop_frames + chunk_frames > estimated:
-            raise ValueError("chunk geometry exceeds the reference's stitching buffer (total_frames + 1000 frames)")
-        final = torch.zeros(M, estimated, device=dev)
-        weights = torch.zeros(1, estimated, device=dev)
+        plans = []
+        for n in range(N):
+            try:
+                n_chunks, c_samples, hop_samples = self.chunk_plan(total_frames[n], chunk_frames, overlap_frames, hop_length, chunk_samples,
+                                                                    overlap_samples, total_samples[n])
+            except ValueError as e:
+                raise ValueError(f"utterance {n}: {e}") from None
+            if len(chunk_stats[n]) != n_chunks:
+                raise ValueError(f"utterance {n}: chunk_stats must hold {n_chunks} (mean, std) pairs, got {len(chunk_stats[n])}")
+            sl = latent_slices[n] if latent_slices[n] is not None else self.latent_slices(n_chunks, hop_samples, c_samples, sample_rate)
+            if len(sl) < n_chunks:
+                raise ValueError(f"utterance {n}: latent_slices must hold {n_chunks} (start, end) pairs, got {len(sl)}")
+            if draws[n] is not None and len(draws[n]) < n_chunks:
+                raise ValueError(f"utterance {n}: draws must hold {n_chunks} dicts, got {len(draws[n])}")
+            if (n_chunks - 1) * hop_frames + chunk_frames > total_frames[n] + 1000:  # :227 (room for the last, ragged chunk)
+                raise ValueError(f"utterance {n}: chunk geometry exceeds the reference's stitching buffer (total_frames + 1000 frames)")
+            rows = int(sem_rows[n])
+            slices = []
+            for i in range(n_chunks):
+                l0, l1 = (int(v) for v in sl[i])
+                a, b = range(rows)[l0:l1].start, range(rows)[l0:l1].stop  # what sem_features[:, l0:l1] selects
+                if b <= a:
+                    raise ValueError(f"utterance {n}: chunk {i}: empty semantic slice [{l0}:{l1}] of {rows} rows")
+                slices.append((a, b))
+            plans.append({"n_chunks": n_chunks, "slices": slices})
+        return plans
+
+    @torch.no_grad()
+    def generate_long_batch(self, sem_features: Sequence[torch.Tensor], total_frames: Sequence[int], chunk_frames: int,
+                            overlap_frames: int, chunk_stats: Sequence, *, seeds: Sequence[int], strength: float = 0.999,
+                            steps: int = 10, cfg_scale: float = 1.0, latent_slices: Optional[Sequence] = None,
+                            hop_length: Optional[int] = None, sample_rate: Optional[int] = None, draws: Optional[Sequence] = None,
+                            chunk_samples: Optional[int] = None, overlap_samples: Optional[int] = None,
+                            total_samples: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """generate_long for N utterances at once.  Lists with one entry per utterance: ``sem_features`` ([1, S_n, semantic_dim]),
+        ``total_frames``, ``chunk_stats`` (that utterance's per-chunk (mean, std) pairs), ``seeds`` and, optionally,
+        ``total_samples``, ``latent_slices`` and ``draws``; the other arguments are generate_long's and shared.  Returns one
+        [n_mels, total_frames_n] LINEAR mel per utterance, in the caller's order.
+
+        Contract: entry n is bitwise generate_long(sem_features[n], total_frames[n], ..., seed=seeds[n]) with that utterance's own
+        total_samples / latent_slices / draws.
+
+        The chunk loop runs in lockstep over the chunk index i.  The utterances are sorted by chunk count, so those that still have
+        a chunk i are a prefix of the batch; their chunk i is ONE inpaint_teacher_refine call of B = that many rows, S = the longest
+        of their semantic slices and sem_lengths = each row's own slice length, with per-row seeds seeds[n] + 2 i (q_sample noise)
+        and seeds[n] + 2 i + 1 (coarse start noise), each row conditioned on its own previous tail.  Rows whose ``draws`` supply
+        different keys at chunk i (parity runs) go in separate calls.  The stitch is batched tensor arithmetic on an
+        [N, n_mels, max(total_frames) + 1000] buffer; all live rows of chunk i start at frame i * (chunk_frames - overlap_frames)."""
+        N = len(sem_features)
+        if N == 0:
+            return []
+        for n, f in enumerate(sem_features):
+            if f.dim() != 3 or f.shape[0] != 1:
+                raise ValueError(f"utterance {n}: sem_features must be [1, S, semantic_dim], got {list(f.shape)}")
+        plans = self.plan_long_batch([f.shape[1] for f in sem_features], total_frames, chunk_frames, overlap_frames, chunk_stats, seeds,
+                                     latent_slices=latent_slices, hop_length=hop_length, sample_rate=sample_rate, draws=draws,
+                                     chunk_samples=chunk_samples, overlap_samples=overlap_samples, total_samples=total_samples)
+        dev = sem_features[0].device
+        M = self.cfg.n_mels
+        hop_frames = chunk_frames - overlap_frames
+        order = sorted(range(N), key=lambda n: -plans[n]["n_chunks"])  # (stable) the live utterances of every chunk are a prefix
+        width = max(int(v) for v in total_frames) + 1000
+        final = torch.zeros(N, M, width, device=dev)
+        weights = torch.zeros(N, 1, width, device=dev)
         window = torch.ones(1, chunk_frames, device=dev)
         if overlap_frames > 0:  # (:253-260; with no overlap the window is flat and no tail is handed on)
             window[0, :overlap_frames] = torch.linspace(0, 1, overlap_frames, device=dev)
             window[0, -overlap_frames:] = torch.linspace(1, 0, overlap_frames, device=dev)
         prev_tail = None
-        for i in range(n_chunks):
-            l0, l1 = latent_slices[i]
-            z = sem_features[:, l0:l1].contiguous()
-            if z.shape[1] == 0:
-                raise ValueError(f"chunk {i}: empty semantic slice [{l0}:{l1}] of {sem_features.shape[1]} rows")
-            d = draws[i] if draws is not None else {}
-            x_coarse = d["x_coarse"].to(dev) if "x_coarse" in d else native.randn((1, chunk_frames, M), dev, seed=seed + 2 * i + 1, stream_id=0x53)
-            x = self.inpaint_teacher_refine(x_coarse, z, prev_tail, overlap_frames if prev_tail is not None else 0, strength, steps,
-                                            cfg_scale, noise=d.get("noise"), noise_k=d.get("noise_k"), seed=seed + 2 * i)
+        for i in range(plans[order[0]]["n_chunks"]):
+            live = [n for n in order if plans[n]["n_chunks"] > i]
+            k = len(live)
+            rows = [plans[n]["slices"][i] for n in live]
+            lens = [b - a for a, b in rows]
+            S = max(lens)
+            if k == 1:
+                sem = sem_features[live[0]][:, rows[0][0]:rows[0][1]].to(torch.float32).contiguous()
+            else:
+                sem = torch.zeros(k, S, sem_features[live[0]].shape[2], dtype=torch.float32, device=dev)
+                for j, (n, (a, b)) in enumerate(zip(live, rows)):
+                    sem[j, :b - a] = sem_features[n][0, a:b]
+            # (device tensors, queued without a host stall; the values are in [1, S] by construction)
+            s_len = None if min(lens) == S else native.host_to_device(torch.tensor(lens, dtype=torch.int64), dev)
+            # rows that inject different reference draws at this chunk run in separate calls (one call when nobody injects)
+            d = [draws[n][i] if draws is not None and draws[n] is not None else {} for n in live]
+            groups = {}
+            for j in range(k):
+                groups.setdefault(tuple(sorted(d[j])), []).append(j)
+            x = torch.empty(k, chunk_frames, M, device=dev) if len(groups) > 1 else None
+            for keys, J in groups.items():
+                whole = len(J) == k
+                pick = (lambda t: t) if whole else (lambda t: t[J])
+                sd = native.seed_tensor([seeds[live[j]] + 2 * i for j in J], len(J), dev)
+                if "x_coarse" in keys:
+                    x_coarse = torch.cat([d[j]["x_coarse"].to(dev) for j in J])
+                else:
+                    x_coarse = native.randn_rows((len(J), chunk_frames, M), dev,
+                                                 native.seed_tensor([seeds[live[j]] + 2 * i + 1 for j in J], len(J), dev), stream_id=0x53)
+                noise = torch.cat([d[j]["noise"].to(dev) for j in J]) if "noise" in keys else None
+                noise_k = torch.cat([d[j]["noise_k"].to(dev) for j in J], dim=1) if "noise_k" in keys and prev_tail is not None else None
+                known = None if prev_tail is None else pick(prev_tail[:k])
+                sl = None if s_len is None else pick(s_len)
+                xg = self.inpaint_teacher_refine(x_coarse, pick(sem).contiguous(), known, overlap_frames if known is not None else 0,
+                                                 strength, steps, cfg_scale, noise=noise, noise_k=noise_k, sem_lengths=sl, seeds=sd)
+                if whole:
+                    x = xg
+                else:
+                    x[J] = xg
             prev_tail = x[:, -overlap_frames:].clone() if overlap_frames > 0 else None
-            mean, std = chunk_stats[i]
-            mean = torch.as_tensor(mean, dtype=torch.float32, device=dev)
-            std = torch.as_tensor(std, dtype=torch.float32, device=dev)
-            lin = torch.exp(x * std + mean).transpose(1, 2).squeeze(0)  # utils/audio.py:17-19, then :353-354
+            mean = torch.cat([torch.broadcast_to(torch.as_tensor(chunk_stats[n][i][0], dtype=torch.float32, device=dev), (1, 1, M))
+                              for n in live])
+            std = torch.cat([torch.broadcast_to(torch.as_tensor(chunk_stats[n][i][1], dtype=torch.float32, device=dev), (1, 1, M))
+                             for n in live])
+            lin = torch.exp(x * std + mean).transpose(1, 2)  # utils/audio.py:17-19, then :353-354
             f0 = i * hop_frames
-            final[:, f0:f0 + chunk_frames] += lin * window
-            weights[:, f0:f0 + chunk_frames] += window
-        return (final / torch.clamp(weights, min=1e-5))[:, :total_frames]
+            final[:k, :, f0:f0 + chunk_frames] += lin * window
+            weights[:k, :, f0:f0 + chunk_frames] += window
+        out = final / torch.clamp(weights, min=1e-5)
+        res = [None] * N
+        for j, n in enumerate(order):
+            res[n] = out[j, :, :int(total_frames[n])]
+        return res

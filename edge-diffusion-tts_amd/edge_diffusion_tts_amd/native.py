@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = (
     "edtts_profile_collect", "edtts_randn", "edtts_index_errors", "edtts_sample_inpaint",
     "edtts_mel_to_spec", "edtts_griffin_lim_scratch_floats", "edtts_griffin_lim", "edtts_set_substreams", "edtts_set_coop", "edtts_dsconv_scratch_floats", "edtts_substreams_for",
     "edtts_decoder_forward_len", "edtts_generate_len", "edtts_sample_ddpm_len", "edtts_sample_multistep_len",
+    "edtts_sample_inpaint_len", "edtts_randn_rows",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -82,6 +83,9 @@ def lib() -> C.CDLL:
     L.edtts_griffin_lim.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, C.c_uint64, vp, vp, vp]
     L.edtts_sample_inpaint.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32), vp, i32,
                                        vp, C.c_uint64, f32, vp, vp]
+    L.edtts_sample_inpaint_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32),
+                                           vp, i32, vp, C.c_uint64, f32, vp, vp, vp, vp, vp]
+    L.edtts_randn_rows.argtypes = [vp, i32, sz, vp, C.c_uint32, f32, vp]
     L.edtts_sample_multistep.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int64),
                                          C.POINTER(f32), vp, vp, vp, vp]
     L.edtts_decoder_forward_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -378,6 +382,53 @@ def randn(shape, device, seed: int = 0, stream_id: int = 0, elem_offset: int = 0
         return cover[off - lo: off - lo + n].reshape(out.shape).clone()
     lib().edtts_randn(out.data_ptr(), out.numel(), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint32(stream_id & 0xFFFFFFFF),
                       C.c_uint64(int(elem_offset)), float(scale), _stream(out.device))
+    return out
+
+
+def seed_tensor(seeds, B: int, device) -> torch.Tensor:
+    """Per-row Philox seeds as the device uint64 [B] array the library reads (the bits of each seed in an int64 tensor): a sequence of
+    B ints is copied to `device` (not while the stream is capturing); an int64 tensor of shape [B] on `device` is used as it is."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype != torch.int64 or tuple(seeds.shape) != (B,):
+            raise ValueError(f"seeds: expected an int64 tensor of shape [{B}], got {seeds.dtype} {list(seeds.shape)}")
+        if not seeds.is_cuda:
+            return seed_tensor(seeds.tolist(), B, device)
+        if seeds.device != torch.device(device):
+            raise ValueError(f"seeds: on {seeds.device}, the call runs on {device}")
+        return seeds.contiguous()
+    seeds = [int(s) for s in seeds]
+    if len(seeds) != B:
+        raise ValueError(f"seeds: expected {B} seeds (one per row), got {len(seeds)}")
+    if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("seeds: a host seed list cannot be copied to the device during graph capture; pass a device int64 tensor")
+    bits = [((s & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63) for s in seeds]  # uint64 bits as int64
+    return host_to_device(torch.tensor(bits, dtype=torch.int64), device)
+
+
+def host_to_device(t: torch.Tensor, device) -> torch.Tensor:
+    """A small host tensor on `device` without stalling the host: a pageable copy would synchronise the current stream (and with it
+    a thread that enqueues for several streams), a copy from pinned memory is queued on the stream."""
+    if torch.device(device).type != "cuda":
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def randn_rows(shape, device, seeds, stream_id: int = 0, scale: float = 1.0) -> torch.Tensor:
+    """[B, ...] standard normals times `scale`, one launch: row b is bitwise randn(shape[1:], seed=seeds[b], stream_id=stream_id)
+    (offset 0), so a longer row begins with a shorter row's draws (include/edtts.h: edtts_randn_rows).  seeds: B ints or a device
+    int64 [B] tensor (see seed_tensor)."""
+    shape = tuple(int(v) for v in shape)
+    if not shape:
+        raise ValueError("randn_rows: shape needs a leading row dimension")
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    if not out.is_cuda:
+        raise EdttsError(f"randn_rows: expected a HIP device, got {out.device} -- the MI355X sampler path has no CPU fallback")
+    B = shape[0]
+    sd = seed_tensor(seeds, B, out.device)
+    if out.numel() == 0:
+        return out
+    lib().edtts_randn_rows(out.data_ptr(), B, out.numel() // B, sd.data_ptr(), C.c_uint32(stream_id & 0xFFFFFFFF), float(scale),
+                           _stream(out.device))
     return out
 
 

@@ -225,6 +225,11 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
  *     0x20000 + step      q_sample noise of the known frames at step `step` inside edtts_sample_inpaint
  * edtts_randn rejects stream_id >= 0x10000. */
 int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_t elem_offset, float scale, void* stream);
+/* One launch for B rows with a seed each: out [B, n_per_row], row b bitwise what edtts_randn(n_per_row, seeds[b], stream_id, offset 0,
+ * scale) draws, so a longer row begins with a shorter row's draws (the host draws of a batched edtts_sample_inpaint_len call).
+ * seeds: device uint64 [B].  n_per_row need not be a multiple of 4 (element e of a row is lane e & 3 of draw e >> 2, as in
+ * edtts_randn); out is 16-byte aligned when it is.  B = 0 or n_per_row = 0 is a no-op. */
+int edtts_randn_rows(float* out, int B, size_t n_per_row, const uint64_t* seeds, uint32_t stream_id, float scale, void* stream);
 
 /* ---- multistep x0-solver sampler  (schedule.py:440-527, DPMSolverPP.sample with the updates of :339-438) -------
  * For step i = 0 .. num_steps-1 (t = timesteps_host[i], step_idx = i as in schedule.py:475-479):
@@ -268,6 +273,19 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
                          const float* sem_features, const float* zero_features, float* x, int num_steps,
                          const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
                          int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond, void* stream);
+/* ... with per-utterance lengths and seeds (the arguments of edtts_sample_inpaint plus three; NULL = as edtts_sample_inpaint):
+ * t_len / s_len: device int64 [B] frame / token counts, as the other *_len entry points (the contract above them holds, with the
+ * same t_all, steps, overlap_len and cfg_scale; the unconditional pass takes the same lengths, its zero context S_b rows).
+ * seeds: device uint64 [B]: row b's in-kernel q_sample noise is Philox keyed by (seeds[b], step, element index WITHIN the row's
+ * [overlap_len, n_mels] block), which is what the call on row b alone with seed = seeds[b] draws; `seed` is then unused.
+ * Row b injects its first min(overlap_len, T_b) known frames, at every step and in the final force; with a known tail, T_b <
+ * overlap_len is flagged with EDTTS_IDX_LEN (the call on that row alone would refuse the overlap).  With seeds = t_len = s_len =
+ * NULL the results are bitwise those of edtts_sample_inpaint. */
+int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
+                             const float* sem_features, const float* zero_features, float* x, int num_steps,
+                             const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                             int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                             const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, void* stream);
 
 /* ---- depthwise-separable Conv1d  (layers/conv.py:25-64, DepthwiseSeparableConv.forward) -----------------
  * Standalone exported layer (named by the north star; the decoder never calls it).
