@@ -1,0 +1,418 @@
+"""Semantic encoder -- API mirror of the reference's models/encoder.py, models/fsq.py and models/vq.py on MI355X.
+
+The trained head after HuBERT (``proj``: Linear, GELU, LayerNorm, [Dropout], Linear; then the FSQ or VQ quantizer) runs as ONE
+kernel per call (edtts_sem_encode, csrc/edtts_semantic.h): features in, token ids, z_q and per-code usage counts out.  Module
+names and state-dict keys are the reference's, so its checkpoints and its own loading lines work unchanged.
+
+HuBERT is a frozen third-party model and stays PyTorch plumbing: pass any module called as ``hubert(wav, output_hidden_states=True)``
+that returns ``.hidden_states`` (transformers' ``HubertModel`` is one).  Without one, the first waveform call loads
+``HubertModel.from_pretrained(cfg.hubert_id, local_files_only=True)`` from the local cache -- never from the network -- and raises
+if it is not there.  Precomputed features ([B, T_feat, 768], as data/dataset_precomputed.py stores them) skip HuBERT entirely:
+``quantize_features`` / ``encode_features``.
+
+Inference only: ``forward`` has the reference's eval semantics in either mode (loss 0, Dropout the identity, no EMA codebook
+update).  Weights are packed for the kernels on first use and re-packed when a parameter changes.
+"""
+from __future__ import annotations
+
+import threading
+from collections import OrderedDict
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from . import native
+
+
+class _PackCache:
+    """The packed blob of one head: (re-)packed on the current stream when a weight tensor or the dims changed."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._sig = None
+        self._blob = None
+
+    def get(self, dims: native.EdttsSemDims, tensors: Sequence[torch.Tensor]) -> torch.Tensor:
+        with self._lock:
+            dkey = (dims.in_dim, dims.semantic_dim, dims.quantizer, dims.codebook_size, dims.n_levels, tuple(dims.levels))
+            sig = (dkey,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+            if self._blob is None or sig != self._sig:
+                dev = tensors[0].device
+                for i, t in enumerate(tensors):
+                    if t.device != dev or t.dtype != torch.float32:
+                        raise native.EdttsError(f"weight {i}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
+                nbytes = native.sem_packed_bytes(dims)
+                if self._blob is None or self._blob.numel() != nbytes or self._blob.device != dev:
+                    self._blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                native.sem_pack(dims, [t.detach().contiguous() for t in tensors], self._blob)
+                self._sig = sig
+            return self._blob
+
+
+def _stats(counts: torch.Tensor):
+    return native.sem_stats(counts)
+
+
+def _flat3(z: torch.Tensor, width: int, name: str) -> torch.Tensor:
+    if z.shape[-1] != width:
+        raise ValueError(f"{name}: expected last dimension {width}, got {list(z.shape)}")
+    return z.float().reshape(1, -1, width)
+
+
+class FSQ(nn.Module):
+    """Finite Scalar Quantization (reference models/fsq.py:FSQ): state-dict keys ``_levels`` and ``_basis``.  forward(z [..., dim]) ->
+    (z_q, indices) on the kernels: the head kernel runs with identity projections, which MFMA applies exactly (one product by 1,
+    the rest by 0)."""
+
+    def __init__(self, levels: List[int]):
+        super().__init__()
+        self.levels = [int(v) for v in levels]
+        self.dim = len(self.levels)
+        self.register_buffer("_levels", torch.tensor(self.levels, dtype=torch.int32))
+        self.register_buffer("_basis", torch.cumprod(torch.tensor([1] + self.levels[:-1], dtype=torch.int64), dim=0))
+        self.codebook_size = 1
+        for v in self.levels:
+            self.codebook_size *= v
+        self._pack = _PackCache()
+        self._eye = {}
+
+    @property
+    def num_codes(self) -> int:
+        return self.codebook_size
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kw):
+        lv = state_dict.get(prefix + "_levels")
+        if lv is not None and lv.numel() == self.dim:
+            self.levels = [int(v) for v in lv.tolist()]
+            self.codebook_size = 1
+            for v in self.levels:
+                self.codebook_size *= v
+        super()._load_from_state_dict(state_dict, prefix, *args, **kw)
+
+    def _dims(self) -> native.EdttsSemDims:
+        return native.sem_dims(0, 16, self.levels)
+
+    def _identity(self, dev) -> List[torch.Tensor]:
+        key = str(dev)
+        if key not in self._eye:
+            D = self.dim
+            if not 1 <= D <= 16:
+                raise native.EdttsError(f"FSQ: {D} levels, the kernels take 1..16")
+            eye = torch.eye(16, dtype=torch.float32)
+            self._eye[key] = [t.to(dev) for t in (eye[:D].contiguous(), torch.zeros(D), eye[:, :D].contiguous(), torch.zeros(16))]
+        return self._eye[key]
+
+    def _run(self, z: torch.Tensor, want_zq: bool):
+        shape = z.shape[:-1]
+        flat = _flat3(z.float(), self.dim, "FSQ input")
+        pad = torch.zeros((1, flat.shape[1], 16), dtype=torch.float32, device=z.device)
+        pad[..., : self.dim] = flat
+        dims = self._dims()
+        blob = self._pack.get(dims, self._identity(z.device))
+        idx, _, zq, _ = native.sem_encode(dims, blob, pad, want_zq=want_zq, want_counts=False)
+        return (zq[0, :, : self.dim].reshape(*shape, self.dim) if want_zq else None), idx.reshape(shape)
+
+    def forward(self, z: torch.Tensor):
+        return self._run(z, True)
+
+    def encode(self, z: torch.Tensor) -> torch.Tensor:
+        return self._run(z, False)[1]
+
+    def indices_to_codes(self, indices: torch.Tensor) -> torch.Tensor:
+        """Codes in [-1, 1] from flat indices, as the reference computes them (its last level is the least significant digit)."""
+        dims = self._dims()
+        blob = self._pack.get(dims, self._identity(indices.device))
+        return native.sem_decode(dims, blob, indices.to(torch.int64))[..., : self.dim]
+
+    decode = indices_to_codes
+
+
+class FSQEncoder(nn.Module):
+    """proj_down -> FSQ -> proj_up (reference models/fsq.py:FSQEncoder); keys ``fsq._levels``, ``fsq._basis``, ``proj_down.*``,
+    ``proj_up.*``."""
+
+    def __init__(self, input_dim: int, levels: List[int] = (8, 6, 5, 5, 5)):
+        super().__init__()
+        self.fsq = FSQ(list(levels))
+        self.fsq_dim = len(levels)
+        self.proj_down = nn.Linear(input_dim, self.fsq_dim)
+        self.proj_up = nn.Linear(self.fsq_dim, input_dim)
+        self._pack = _PackCache()
+
+    @property
+    def codebook_size(self) -> int:
+        return self.fsq.codebook_size
+
+    @property
+    def num_codes(self) -> int:
+        return self.fsq.codebook_size
+
+    def _dims(self, in_dim: int = 0) -> native.EdttsSemDims:
+        return native.sem_dims(in_dim, self.proj_up.out_features, self.fsq.levels)
+
+    def _slots(self) -> List[torch.Tensor]:
+        return [self.proj_down.weight, self.proj_down.bias, self.proj_up.weight, self.proj_up.bias]
+
+    def _quantize(self, z: torch.Tensor, want_zq: bool, want_counts: bool):
+        shape = z.shape[:-1]
+        dims = self._dims()
+        blob = self._pack.get(dims, self._slots())
+        idx, _, zq, counts = native.sem_encode(dims, blob, _flat3(z, dims.semantic_dim, "FSQEncoder input"), want_zq=want_zq,
+                                               want_counts=want_counts)
+        return (None if zq is None else zq.reshape(*shape, -1)), idx.reshape(shape), counts
+
+    @torch.no_grad()
+    def forward(self, z: torch.Tensor):
+        """(z_q, indices, loss = 0, perplexity, used), as FSQEncoder.forward returns them."""
+        zq, idx, counts = self._quantize(z, True, True)
+        ppl, used = _stats(counts)
+        return zq, idx, torch.zeros((), device=z.device), ppl, used
+
+    @torch.no_grad()
+    def encode(self, z: torch.Tensor) -> torch.Tensor:
+        return self._quantize(z, False, False)[1]
+
+    @torch.no_grad()
+    def decode(self, indices: torch.Tensor) -> torch.Tensor:
+        dims = self._dims()
+        return native.sem_decode(dims, self._pack.get(dims, self._slots()), indices.to(torch.int64))
+
+
+class VectorQuantizer(nn.Module):
+    """Nearest-code quantizer (reference models/vq.py:VectorQuantizer); keys ``codebook.weight``, ``ema_cluster_size``, ``ema_w``,
+    ``update_count``.  Inference only: the loss is 0 and the EMA codebook update is not run."""
+
+    def __init__(self, dim: int, codebook_size: int, commit: float = 0.25, decay: float = 0.99, epsilon: float = 1e-5,
+                 reset_unused_every: int = 100):
+        super().__init__()
+        self.dim = dim
+        self.codebook_size = codebook_size
+        self.commit, self.decay, self.epsilon, self.reset_unused_every = commit, decay, epsilon, reset_unused_every
+        self.codebook = nn.Embedding(codebook_size, dim)
+        nn.init.normal_(self.codebook.weight, mean=0.0, std=1.0)
+        self.register_buffer("ema_cluster_size", torch.ones(codebook_size))
+        self.register_buffer("ema_w", self.codebook.weight.detach().clone())
+        self.register_buffer("update_count", torch.tensor(0))
+        self._pack = _PackCache()
+
+    @property
+    def num_codes(self) -> int:
+        return self.codebook_size
+
+    def _dims(self, in_dim: int = 0) -> native.EdttsSemDims:
+        return native.sem_dims(in_dim, self.dim, codebook_size=self.codebook_size)
+
+    def _slots(self) -> List[torch.Tensor]:
+        return [self.codebook.weight]
+
+    def _quantize(self, z: torch.Tensor, want_zq: bool, want_counts: bool):
+        shape = z.shape[:-1]
+        dims = self._dims()
+        blob = self._pack.get(dims, self._slots())
+        idx, _, zq, counts = native.sem_encode(dims, blob, _flat3(z, self.dim, "VectorQuantizer input"), want_zq=want_zq,
+                                               want_counts=want_counts)
+        return (None if zq is None else zq.reshape(*shape, -1)), idx.reshape(shape), counts
+
+    @torch.no_grad()
+    def forward(self, z: torch.Tensor):
+        """(z_q, idx, vq_loss = 0, perplexity, used), as VectorQuantizer.forward returns them in eval mode."""
+        zq, idx, counts = self._quantize(z, True, True)
+        ppl, used = _stats(counts)
+        return zq, idx, torch.zeros((), device=z.device), ppl, used
+
+    @torch.no_grad()
+    def encode(self, z: torch.Tensor) -> torch.Tensor:
+        return self._quantize(z, False, False)[1]
+
+    @torch.no_grad()
+    def decode(self, idx: torch.Tensor) -> torch.Tensor:
+        dims = self._dims()
+        return native.sem_decode(dims, self._pack.get(dims, self._slots()), idx.to(torch.int64))
+
+
+class _Proj(nn.Sequential):
+    """proj of the reference: Linear, GELU, LayerNorm, Linear (models/encoder.py:40-45) or with a Dropout before the last Linear
+    (train_v2.py:54-60, inference_pipeline.py:29-35).  Loading a state dict of either layout switches to that layout."""
+
+    def __init__(self, in_dim: int, dim: int, dropout: Optional[float] = None):
+        layers = [nn.Linear(in_dim, dim), nn.GELU(), nn.LayerNorm(dim)]
+        if dropout is not None:
+            layers.append(nn.Dropout(dropout))
+        super().__init__(*layers, nn.Linear(dim, dim))
+
+    @property
+    def final(self) -> nn.Linear:
+        return self[len(self) - 1]
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kw):
+        has4, has3 = (prefix + "4.weight") in state_dict, (prefix + "3.weight") in state_dict
+        if has4 != has3 and has4 != (len(self) == 5):
+            lin = self.final
+            mods = [self[0], self[1], self[2]] + ([nn.Dropout(0.0)] if has4 else []) + [lin]
+            self._modules = OrderedDict((str(i), m) for i, m in enumerate(mods))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kw)
+
+
+def _missing_hubert(hubert_id: str, err: Exception) -> RuntimeError:
+    return RuntimeError(
+        f"SemanticEncoder: no HuBERT module was given and {hubert_id!r} is not in the local Hugging Face cache ({err}).  This package "
+        "never downloads: put the model in the cache beforehand, pass hubert=<module>, or use quantize_features / encode_features "
+        "on precomputed features.")
+
+
+class SemanticEncoder(nn.Module):
+    """HuBERT features -> proj -> FSQ / VQ (reference models/encoder.py:SemanticEncoder), with the head on the kernels.
+
+    ``hubert``: a module called as ``hubert(wav, output_hidden_states=True)`` returning ``.hidden_states``; the head reads
+    ``hidden_states[cfg.hubert_layer]``.  None: nothing is loaded here; the first waveform call loads
+    ``HubertModel.from_pretrained(cfg.hubert_id, local_files_only=True)`` and raises a RuntimeError if it is not cached."""
+
+    def __init__(self, cfg, hubert: Optional[nn.Module] = None, *, in_dim: int = 768, proj_dropout: bool = False):
+        super().__init__()
+        self.cfg = cfg
+        self.hubert = hubert
+        if hubert is not None:
+            self._freeze(hubert)
+        self.proj = _Proj(in_dim, cfg.semantic_dim, getattr(cfg, "dropout", 0.0) if proj_dropout else None)
+        if getattr(cfg, "use_fsq", False):
+            self.vq = FSQEncoder(cfg.semantic_dim, cfg.fsq_levels)
+        else:
+            self.vq = VectorQuantizer(cfg.semantic_dim, cfg.codebook_size, commit=getattr(cfg, "vq_commit", 0.25))
+        self._pack = _PackCache()
+
+    @property
+    def codebook_size(self) -> int:
+        return self.vq.codebook_size
+
+    @staticmethod
+    def _freeze(m: nn.Module) -> None:
+        m.eval()
+        for p in m.parameters():
+            p.requires_grad = False
+
+    # ------------------------------------------------------------------------------------------ loading
+    @classmethod
+    def from_checkpoint(cls, ckpt_or_path, cfg=None, hubert: Optional[nn.Module] = None, device=None) -> "SemanticEncoder":
+        """Build the head from a reference checkpoint (a dict or a path): ``encoder_proj`` + ``encoder_vq`` (train.py:291-297),
+        ``encoder_proj`` + ``encoder_fsq`` (train_v2.py:335-341), or a full ``encoder`` state dict (train.py:195).  The quantizer
+        kind, its levels / codebook size, semantic_dim, the HuBERT width and the proj layout come from the tensors.  In a full
+        ``encoder`` dict the ``hubert.*`` keys are loaded into ``hubert`` when one is given and ignored otherwise."""
+        from .config import CFG
+        ck = ckpt_or_path
+        if isinstance(ck, (str, bytes)) or hasattr(ck, "__fspath__"):
+            ck = torch.load(ck, map_location="cpu", weights_only=False)
+        if "encoder_proj" in ck:
+            proj_sd = dict(ck["encoder_proj"])
+            q_sd = ck.get("encoder_fsq", ck.get("encoder_vq"))
+            if q_sd is None:
+                raise KeyError("checkpoint has encoder_proj but neither encoder_fsq nor encoder_vq")
+            q_sd, hub_sd = dict(q_sd), {}
+        else:
+            sd = ck["encoder"] if "encoder" in ck else ck
+            proj_sd = {k[len("proj."):]: v for k, v in sd.items() if k.startswith("proj.")}
+            q_sd = {k[len("vq."):]: v for k, v in sd.items() if k.startswith("vq.")}
+            hub_sd = {k[len("hubert."):]: v for k, v in sd.items() if k.startswith("hubert.")}
+            if not proj_sd or not q_sd:
+                raise KeyError("no encoder weights found: expected encoder_proj + encoder_fsq / encoder_vq, or an encoder state dict")
+        if cfg is None:
+            stored = ck.get("cfg") if isinstance(ck, dict) else None
+            if isinstance(stored, dict):
+                cfg = CFG.from_dict(dict(stored))
+            elif stored is not None:
+                cfg = CFG.from_dict({k: getattr(stored, k) for k in CFG.__dataclass_fields__ if hasattr(stored, k) and k != "phase"})
+            else:
+                cfg = CFG(device="cpu")
+        w0 = proj_sd["0.weight"]
+        cfg.semantic_dim = int(w0.shape[0])
+        if "fsq._levels" in q_sd:
+            cfg.use_fsq = True
+            cfg.fsq_levels = [int(v) for v in q_sd["fsq._levels"].tolist()]
+        elif "codebook.weight" in q_sd:
+            cfg.use_fsq = False
+            cfg.codebook_size = int(q_sd["codebook.weight"].shape[0])
+        else:
+            raise KeyError("quantizer state dict has neither fsq._levels (FSQ) nor codebook.weight (VQ)")
+        enc = cls(cfg, hubert, in_dim=int(w0.shape[1]), proj_dropout="4.weight" in proj_sd)
+        enc.proj.load_state_dict(proj_sd)
+        enc.vq.load_state_dict(q_sd)
+        if hubert is not None and hub_sd:
+            hubert.load_state_dict(hub_sd)
+        if device is not None:
+            enc = enc.to(device)
+        return enc.eval()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        if self.hubert is None:  # a full encoder dict carries the backbone: without a HuBERT module its keys are ignored
+            hub = [k for k in state_dict if k.startswith(prefix + "hubert.")]
+            for k in hub:
+                if k in unexpected_keys:
+                    unexpected_keys.remove(k)
+
+    # ------------------------------------------------------------------------------------------ HuBERT
+    def _backbone(self) -> nn.Module:
+        if self.hubert is None:
+            try:
+                from transformers import HubertModel
+            except ImportError as e:
+                raise _missing_hubert(self.cfg.hubert_id, e) from e
+            try:
+                m = HubertModel.from_pretrained(self.cfg.hubert_id, local_files_only=True)
+            except OSError as e:
+                raise _missing_hubert(self.cfg.hubert_id, e) from e
+            self._freeze(m)
+            self.hubert = m.to(self.proj[0].weight.device)
+        return self.hubert
+
+    @torch.no_grad()
+    def extract_hubert(self, wav_16k: torch.Tensor) -> torch.Tensor:
+        """HuBERT features [B, T_feat, 768] of a 16 kHz waveform [B, T_audio]: hidden_states[cfg.hubert_layer]."""
+        out = self._backbone()(wav_16k, output_hidden_states=True)
+        return out.hidden_states[self.cfg.hubert_layer].float()
+
+    # ------------------------------------------------------------------------------------------ the head
+    def _dims(self) -> native.EdttsSemDims:
+        return self.vq._dims(self.proj[0].in_features)
+
+    def _slots(self) -> List[torch.Tensor]:
+        p = self.proj
+        return [p[0].weight, p[0].bias, p[2].weight, p[2].bias, p.final.weight, p.final.bias] + self.vq._slots()
+
+    def _head(self, h: torch.Tensor, lengths, want_zq: bool, want_counts: bool, want_z: bool = False):
+        if h.dim() != 3:
+            raise ValueError(f"features: expected [B, T_feat, {self.proj[0].in_features}], got {list(h.shape)}")
+        dims = self._dims()
+        blob = self._pack.get(dims, self._slots())
+        B, T = h.shape[0], h.shape[1]
+        n = native.lengths(lengths, B, max(T, 1), h.device, "lengths")
+        return native.sem_encode(dims, blob, h.float(), n, want_z=want_z, want_zq=want_zq, want_counts=want_counts)
+
+    @torch.no_grad()
+    def quantize_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """Precomputed HuBERT features h [B, T_feat, 768] -> (z_q [B, T_feat, semantic_dim], idx [B, T_feat], perplexity, used).
+        ``lengths`` (int64 [B]): frames t >= lengths[b] are not read, get idx 0 and z_q 0, and are not counted."""
+        idx, _, zq, counts = self._head(h, lengths, True, True)
+        ppl, used = _stats(counts)
+        return zq, idx, ppl, used
+
+    @torch.no_grad()
+    def encode_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Token ids [B, T_feat] of precomputed HuBERT features (see quantize_features)."""
+        return self._head(h, lengths, False, False)[0]
+
+    @torch.no_grad()
+    def forward(self, wav_16k: torch.Tensor):
+        """(z_q, idx, vq_loss = 0, perplexity, used) of a 16 kHz waveform [B, T_audio], as the reference returns them."""
+        zq, idx, ppl, used = self.quantize_features(self.extract_hubert(wav_16k))
+        return zq, idx, torch.zeros((), device=zq.device), ppl, used
+
+    @torch.no_grad()
+    def encode(self, wav_16k: torch.Tensor) -> torch.Tensor:
+        """Token ids [B, T_feat] of a 16 kHz waveform."""
+        return self.encode_features(self.extract_hubert(wav_16k))
+
+    @torch.no_grad()
+    def decode_tokens(self, idx: torch.Tensor) -> torch.Tensor:
+        """Token ids -> continuous features [..., semantic_dim] (the quantizer's decode)."""
+        return self.vq.decode(idx)

@@ -23,6 +23,7 @@ EXPORTED_SYMBOLS = (
     "edtts_mel_to_spec", "edtts_griffin_lim_scratch_floats", "edtts_griffin_lim", "edtts_set_substreams", "edtts_set_coop", "edtts_dsconv_scratch_floats", "edtts_substreams_for",
     "edtts_decoder_forward_len", "edtts_generate_len", "edtts_sample_ddpm_len", "edtts_sample_multistep_len",
     "edtts_sample_inpaint_len", "edtts_randn_rows",
+    "edtts_sem_packed_bytes", "edtts_sem_num_codes", "edtts_sem_pack", "edtts_sem_encode", "edtts_sem_decode", "edtts_sem_stats",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -33,6 +34,28 @@ class EdttsDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "hidden", "layers", "heads", "n_mels", "ffn_mult", "codebook_size", "semantic_dim", "window", "max_pos",
         "max_ctx_pos", "n_step_emb", "compute_dtype")]
+
+
+SEM_FSQ, SEM_VQ = 0, 1  # EdttsSemDims.quantizer (include/edtts.h: EDTTS_SEM_*)
+
+
+class EdttsSemDims(C.Structure):
+    _fields_ = [("in_dim", C.c_int32), ("semantic_dim", C.c_int32), ("quantizer", C.c_int32), ("codebook_size", C.c_int32),
+                ("n_levels", C.c_int32), ("levels", C.c_int32 * 16)]
+
+
+def sem_dims(in_dim: int, semantic_dim: int, levels: Optional[Sequence[int]] = None, codebook_size: int = 0) -> EdttsSemDims:
+    """Dims of a semantic head: FSQ when `levels` is given, VQ with `codebook_size` codes otherwise; in_dim 0 = no proj."""
+    d = EdttsSemDims()
+    d.in_dim, d.semantic_dim = int(in_dim), int(semantic_dim)
+    if levels is not None:
+        levels = [int(v) for v in levels]
+        d.quantizer, d.n_levels = SEM_FSQ, len(levels)  # more than 16: the library rejects it with its own message
+        for i, v in enumerate(levels[:16]):
+            d.levels[i] = v
+    else:
+        d.quantizer, d.codebook_size = SEM_VQ, int(codebook_size)
+    return d
 
 
 COMPUTE_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -97,6 +120,13 @@ def lib() -> C.CDLL:
                                              C.POINTER(C.c_int64), C.POINTER(f32), vp, vp, vp, vp]
     L.edtts_dsconv_forward.argtypes = [vp] * 6 + [i32] * 7 + [vp, vp, vp]
     L.edtts_dsconv_scratch_floats.argtypes = [i32] * 7 + [C.POINTER(sz)]
+    sdp = C.POINTER(EdttsSemDims)
+    L.edtts_sem_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
+    L.edtts_sem_num_codes.argtypes = [sdp, C.POINTER(C.c_int64)]
+    L.edtts_sem_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
+    L.edtts_sem_encode.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.edtts_sem_decode.argtypes = [sdp, vp, vp, C.c_int64, vp, vp]
+    L.edtts_sem_stats.argtypes = [vp, C.c_int64, vp, vp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -457,6 +487,74 @@ def check_indices(workspace: torch.Tensor) -> None:
 def check_table_index(t: torch.Tensor, n: int, name: str, lo: int = 0) -> None:
     if CHECK_INDICES and not torch.cuda.is_current_stream_capturing() and bool(((t < lo) | (t >= n)).any()):
         raise IndexError(f"{name}: index out of range [{lo}, {n})")
+
+
+# ---------------------------------------------------------------------------------------------- semantic head
+def sem_packed_bytes(dims: EdttsSemDims) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_sem_packed_bytes(C.byref(dims), C.byref(out))
+    return out.value
+
+
+def sem_num_codes(dims: EdttsSemDims) -> int:
+    out = C.c_int64(0)
+    lib().edtts_sem_num_codes(C.byref(dims), C.byref(out))
+    return out.value
+
+
+def sem_pack(dims: EdttsSemDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor) -> None:
+    """Pack the head's weights (state-dict order, include/edtts.h: edtts_sem_pack) into `packed` (uint8 device tensor)."""
+    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    lib().edtts_sem_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def sem_encode(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+               want_z: bool = False, want_zq: bool = True, want_counts: bool = True):
+    """h [B, T, in_dim] (or z [B, T, semantic_dim] when dims.in_dim is 0) -> (idx int64 [B, T], z or None, z_q or None,
+    counts int32 [num_codes] or None), one kernel (include/edtts.h: edtts_sem_encode).  lengths: device int64 [B] or None."""
+    if h.dim() != 3:
+        raise ValueError(f"expected features [B, T, D], got shape {list(h.shape)}")
+    B, T, D = h.shape
+    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
+    if D != want_d:
+        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+    h = _aligned(h)
+    dev = h.device
+    S = dims.semantic_dim
+    idx = torch.empty((B, T), dtype=torch.int64, device=dev)
+    z = torch.empty((B, T, S), dtype=torch.float32, device=dev) if want_z else None
+    zq = torch.empty((B, T, S), dtype=torch.float32, device=dev) if want_zq else None
+    counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=dev) if want_counts else None
+    lib().edtts_sem_encode(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
+                           _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), None if z is None else z.data_ptr(),
+                           None if zq is None else zq.data_ptr(), None if counts is None else counts.data_ptr(), _stream(dev))
+    return idx, z, zq, counts
+
+
+def sem_decode(dims: EdttsSemDims, packed: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """idx int64 [...] -> z_q [..., semantic_dim] (include/edtts.h: edtts_sem_decode).  Ids are clamped into range; with
+    EDTTS_CHECK_INDICES=1 an out-of-range id raises IndexError first."""
+    idx = idx.contiguous()
+    check_table_index(idx, sem_num_codes(dims), "token id")
+    out = torch.empty((*idx.shape, dims.semantic_dim), dtype=torch.float32, device=idx.device)
+    if idx.numel() == 0:
+        return out
+    lib().edtts_sem_decode(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(idx, torch.int64, "idx"), idx.numel(),
+                           out.data_ptr(), _stream(idx.device))
+    return out
+
+
+def sem_stats(counts: torch.Tensor):
+    """counts int32 [num_codes] -> (perplexity fp32 0-dim, used int64 0-dim), both on the device (include/edtts.h: edtts_sem_stats)."""
+    ppl = torch.empty((), dtype=torch.float32, device=counts.device)
+    used = torch.empty((), dtype=torch.int64, device=counts.device)
+    lib().edtts_sem_stats(_dev_ptr(counts, torch.int32, "counts"), counts.numel(), ppl.data_ptr(), used.data_ptr(), _stream(counts.device))
+    return ppl, used
 
 
 def set_substreams(n: int) -> int:

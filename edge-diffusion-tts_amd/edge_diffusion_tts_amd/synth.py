@@ -127,3 +127,57 @@ def synth_state_dict(cfg, seed: int = 0, max_pos: int = 1000, max_ctx_pos: int =
             v = u / math.sqrt(shape[-1])           # linear weights ~ U(-1/sqrt(fan_in), 1/sqrt(fan_in))
         out[key] = torch.from_numpy(np.ascontiguousarray(v.astype(np.float32)))
     return out
+
+
+def _u(shape, seed: int, stream: int, scale: float) -> torch.Tensor:
+    return torch.from_numpy((hash_uniform(shape, seed, stream) * scale).astype(np.float32))
+
+
+def synth_semantic_head(in_dim: int, semantic_dim: int, levels=None, codebook_size: int = 0, seed: int = 0,
+                        dropout_layout: bool = False) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+    """Deterministic weights of a semantic head: (proj state dict, quantizer state dict) with the reference's keys (FSQEncoder when
+    `levels` is given, VectorQuantizer with `codebook_size` codes otherwise).  Scaled so that, on hash_uniform features in [-1, 1),
+    the proj output z has about unit variance (0.5 for VQ), the FSQ pre-activations spread over every level and the VQ codes
+    (standard deviation 0.5) are chosen widely."""
+    S = semantic_dim
+    last = "4" if dropout_layout else "3"
+    vq = levels is None
+    zs = 0.5 if vq else 1.0
+    proj = OrderedDict([
+        ("0.weight", _u((S, in_dim), seed, 100, 3.0 / math.sqrt(in_dim))), ("0.bias", _u((S,), seed, 101, 0.1)),
+        ("2.weight", 1.0 + _u((S,), seed, 102, 0.2)), ("2.bias", _u((S,), seed, 103, 0.1)),
+        (f"{last}.weight", _u((S, S), seed, 104, zs * math.sqrt(3.0 / S))), (f"{last}.bias", _u((S,), seed, 105, 0.1 * zs)),
+    ])
+    if vq:
+        cb = _u((codebook_size, S), seed, 110, 0.5 * math.sqrt(3.0))
+        q = OrderedDict([("codebook.weight", cb), ("ema_cluster_size", torch.ones(codebook_size)), ("ema_w", cb.clone()),
+                         ("update_count", torch.tensor(0))])
+    else:
+        D = len(levels)
+        q = OrderedDict([
+            ("fsq._levels", torch.tensor(list(levels), dtype=torch.int32)),
+            ("fsq._basis", torch.cumprod(torch.tensor([1] + list(levels)[:-1], dtype=torch.int64), dim=0)),
+            ("proj_down.weight", _u((D, S), seed, 120, 1.5 * math.sqrt(3.0 / S))), ("proj_down.bias", _u((D,), seed, 121, 0.2)),
+            ("proj_up.weight", _u((S, D), seed, 122, math.sqrt(3.0 / D))), ("proj_up.bias", _u((S,), seed, 123, 0.1)),
+        ])
+    return proj, q
+
+
+def synth_hubert_features(B: int, T: int, in_dim: int = 768, seed: int = 0) -> torch.Tensor:
+    """Deterministic stand-in HuBERT features [B, T, in_dim] in [-1, 1)."""
+    return _u((B, T, in_dim), seed, 130, 1.0)
+
+
+class HubertStandIn(torch.nn.Module):
+    """A deterministic module with HubertModel's calling convention: hubert(wav, output_hidden_states=True).hidden_states is a
+    list of n_layers + 1 tensors; every one is synth_hubert_features(B, T_audio // 320, in_dim, seed) (one frame per 320 samples,
+    HuBERT's stride), on the waveform's device.  For tests and examples that must not load a real backbone."""
+
+    def __init__(self, in_dim: int = 768, seed: int = 0, n_layers: int = 12):
+        super().__init__()
+        self.in_dim, self.seed, self.n_layers = in_dim, seed, n_layers
+
+    def forward(self, wav, output_hidden_states: bool = True):
+        from types import SimpleNamespace
+        h = synth_hubert_features(wav.shape[0], wav.shape[-1] // 320, self.in_dim, self.seed).to(wav.device)
+        return SimpleNamespace(hidden_states=[h] * (self.n_layers + 1), last_hidden_state=h)

@@ -362,6 +362,45 @@ int edtts_substreams_for(const EdttsDims* dims, int B, int T);
  * only query. */
 int edtts_set_coop(int mode);
 
+/* ---- semantic head  (models/encoder.py:40-57 proj, models/fsq.py FSQEncoder, models/vq.py VectorQuantizer) --------------------
+ * The trained head after the frozen HuBERT backbone: HuBERT features h [B,T,in_dim] -> z = proj(h) [B,T,semantic_dim] ->
+ * FSQ or VQ tokens.  HuBERT itself stays outside the library.  All fp32, eval semantics (Dropout = identity, loss 0).
+ * Limits (EDTTS_ERR_UNSUPPORTED outside): semantic_dim a multiple of 16 in [16, 128]; in_dim a multiple of 16 in [16, 4096], or 0
+ * for the quantizer alone (the input is then z itself and there is no proj); FSQ: 1..16 levels, each in [2, 256], at most 2^24
+ * codes; VQ: codebook_size in [1, 65536]. */
+enum { EDTTS_SEM_FSQ = 0, EDTTS_SEM_VQ = 1 };
+typedef struct EdttsSemDims {
+  int32_t in_dim;        /* HuBERT width (768), or 0: no proj                        */
+  int32_t semantic_dim;  /* CFG.semantic_dim                                         */
+  int32_t quantizer;     /* EDTTS_SEM_FSQ (CFG.use_fsq) or EDTTS_SEM_VQ               */
+  int32_t codebook_size; /* VQ: rows of codebook.weight                              */
+  int32_t n_levels;      /* FSQ: len(CFG.fsq_levels)                                 */
+  int32_t levels[16];    /* FSQ: CFG.fsq_levels; basis = cumprod([1] + levels[:-1])  */
+} EdttsSemDims;
+/* Packed blob: weights in MFMA-fragment order, zero-padded to 16 x 16 tiles, plus the tables the kernels read (|c|^2 of each code,
+ * FSQ half-levels, levels and basis).  slots (host array of device fp32 pointers, state-dict order):
+ *   with a proj (in_dim > 0): proj.0.weight [S][in_dim], proj.0.bias, LayerNorm weight, LayerNorm bias, final Linear weight [S][S],
+ *   its bias; then FSQ: proj_down.weight [D][S], proj_down.bias [D], proj_up.weight [S][D], proj_up.bias [S]; or VQ:
+ *   codebook.weight [K][S].  edtts_sem_num_codes: the number of token ids (prod(levels) or codebook_size). */
+int edtts_sem_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes);
+int edtts_sem_num_codes(const EdttsSemDims* dims, int64_t* out_codes);
+int edtts_sem_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed, void* stream);
+/* Encode: one kernel over h.  idx [B,T] int64 (required); z [B,T,S] (proj output), z_q [B,T,S] and counts int32 [num_codes]
+ * (usage, zeroed by the call, integer atomics) are optional (NULL).  Per frame, in the reference's order: FSQ u = proj_down(z),
+ * zb = tanh(u), q = clamp(rint((zb+1) half), 0, L-1) / half - 1, zq_low = zb + (q - zb), idx = sum rint((zq_low+1) half) basis,
+ * z_q = proj_up(zq_low); VQ dist = (|z|^2 - 2 z.c) + |c|^2, idx = the first minimum (torch.argmin), z_q = z + (c - z).
+ * lengths int64 [B] or NULL: frames t >= lengths[b] (clamped into [1, T]) are not read, get idx 0 and z_q / z 0 and are not
+ * counted; row b is then bitwise the call on row b alone.  h, z, z_q must be 16-byte aligned. */
+int edtts_sem_encode(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths,
+                     int64_t* idx, float* z, float* z_q, int32_t* counts, void* stream);
+/* Decode: idx [n] -> z_q [n,S] (FSQEncoder.decode: indices_to_codes as the reference writes it -- the LAST level is the least
+ * significant digit -- then proj_up; VectorQuantizer.decode: the codebook row, bitwise).  Ids outside [0, num_codes) are clamped
+ * (the host raises IndexError for them when EDTTS_CHECK_INDICES=1). */
+int edtts_sem_decode(const EdttsSemDims* dims, const void* packed, const int64_t* idx, int64_t n, float* z_q, void* stream);
+/* Stats: counts int32 [n_codes] -> perplexity fp32 [1] = exp(-sum p log(max(p, 1e-12))), p = counts / max(sum, 1), and used int64
+ * [1] = #(counts > 0) (fsq.py:189-193, vq.py:101-105).  One block, fixed order: bitwise reproducible. */
+int edtts_sem_stats(const int32_t* counts, int64_t n_codes, float* perplexity, int64_t* used, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
