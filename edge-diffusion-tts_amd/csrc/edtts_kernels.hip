@@ -2975,6 +2975,7 @@ struct Launcher16 {
 #define TRY_G(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 #include "edtts_generic.h"
 #include "edtts_semantic.h"
+#include "edtts_hubert.h"
 
 // compiled decoder shapes: (hidden, heads, n_mels).  EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, body) runs `body` with LN = the fused
 // launcher of lo's shape, or the statement MISS16 / MISS32 when none is compiled; EDTTS_DISPATCH adds the generic launcher (lo.GEN)

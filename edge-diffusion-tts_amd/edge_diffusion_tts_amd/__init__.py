@@ -16,10 +16,11 @@ from .synth import synth_state_dict
 from .longform import InpaintSampler
 from .melpost import GriffinLim, InverseMelScale, MelVocoder, denormalize_mel, normalize_mel
 from .encoder import FSQ, FSQEncoder, SemanticEncoder, VectorQuantizer
+from .hubert import NativeHubert
 
 __all__ = [
     "CFG", "TrainPhase", "get_device", "set_seed", "DiffusionSchedule", "DPMSolverPP", "EdgeDiffusionDecoder", "EdgeInference",
     "DepthwiseSeparableConv", "synth_state_dict", "InpaintSampler",
     "GriffinLim", "InverseMelScale", "MelVocoder", "denormalize_mel", "normalize_mel",
-    "SemanticEncoder", "VectorQuantizer", "FSQ", "FSQEncoder",
+    "SemanticEncoder", "VectorQuantizer", "FSQ", "FSQEncoder", "NativeHubert",
 ]

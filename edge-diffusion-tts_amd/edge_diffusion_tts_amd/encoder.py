@@ -273,6 +273,7 @@ class SemanticEncoder(nn.Module):
         self.cfg = cfg
         self.hubert = hubert
         if hubert is not None:
+            self._check_native(hubert, cfg)
             self._freeze(hubert)
         self.proj = _Proj(in_dim, cfg.semantic_dim, getattr(cfg, "dropout", 0.0) if proj_dropout else None)
         if getattr(cfg, "use_fsq", False):
@@ -284,6 +285,13 @@ class SemanticEncoder(nn.Module):
     @property
     def codebook_size(self) -> int:
         return self.vq.codebook_size
+
+    @staticmethod
+    def _check_native(hubert: nn.Module, cfg) -> None:
+        from .hubert import NativeHubert
+        if isinstance(hubert, NativeHubert) and hubert.num_layers != cfg.hubert_layer:
+            raise ValueError(f"SemanticEncoder: the NativeHubert backbone runs {hubert.num_layers} layers, the head reads "
+                             f"hidden_states[cfg.hubert_layer={cfg.hubert_layer}]")
 
     @staticmethod
     def _freeze(m: nn.Module) -> None:
@@ -365,11 +373,33 @@ class SemanticEncoder(nn.Module):
             self.hubert = m.to(self.proj[0].weight.device)
         return self.hubert
 
+    def _native(self):
+        from .hubert import NativeHubert
+        if isinstance(self.hubert, NativeHubert):
+            self._check_native(self.hubert, self.cfg)
+            return self.hubert
+        return None
+
     @torch.no_grad()
-    def extract_hubert(self, wav_16k: torch.Tensor) -> torch.Tensor:
-        """HuBERT features [B, T_feat, 768] of a 16 kHz waveform [B, T_audio]: hidden_states[cfg.hubert_layer]."""
+    def extract_hubert(self, wav_16k: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """HuBERT features [B, T_feat, 768] of a 16 kHz waveform [B, T_audio]: hidden_states[cfg.hubert_layer].  ``lengths`` (int64
+        [B] sample counts) needs a NativeHubert backbone: row b is then the features of wav[b, :lengths[b]] alone, zero past them."""
+        nat = self._native()
+        if nat is not None:
+            return nat(wav_16k, lengths)
+        if lengths is not None:
+            raise ValueError("SemanticEncoder: per-utterance lengths need a NativeHubert backbone (a torch HuBERT normalises over the "
+                             "padded batch)")
         out = self._backbone()(wav_16k, output_hidden_states=True)
         return out.hidden_states[self.cfg.hubert_layer].float()
+
+    def _features(self, wav_16k: torch.Tensor, lengths):
+        """(features, their per-utterance frame counts on the device or None)"""
+        h = self.extract_hubert(wav_16k, lengths)
+        if lengths is None:
+            return h, None
+        n = native.lengths(lengths, wav_16k.shape[0], wav_16k.shape[1], h.device, "lengths")
+        return h, self.hubert.frames_of(n, wav_16k.shape[1])
 
     # ------------------------------------------------------------------------------------------ the head
     def _dims(self) -> native.EdttsSemDims:
@@ -402,15 +432,16 @@ class SemanticEncoder(nn.Module):
         return self._head(h, lengths, False, False)[0]
 
     @torch.no_grad()
-    def forward(self, wav_16k: torch.Tensor):
-        """(z_q, idx, vq_loss = 0, perplexity, used) of a 16 kHz waveform [B, T_audio], as the reference returns them."""
-        zq, idx, ppl, used = self.quantize_features(self.extract_hubert(wav_16k))
+    def forward(self, wav_16k: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """(z_q, idx, vq_loss = 0, perplexity, used) of a 16 kHz waveform [B, T_audio], as the reference returns them.  ``lengths``
+        (sample counts, NativeHubert backbone only): the head then takes each utterance's own frame count."""
+        zq, idx, ppl, used = self.quantize_features(*self._features(wav_16k, lengths))
         return zq, idx, torch.zeros((), device=zq.device), ppl, used
 
     @torch.no_grad()
-    def encode(self, wav_16k: torch.Tensor) -> torch.Tensor:
-        """Token ids [B, T_feat] of a 16 kHz waveform."""
-        return self.encode_features(self.extract_hubert(wav_16k))
+    def encode(self, wav_16k: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Token ids [B, T_feat] of a 16 kHz waveform (``lengths`` as in forward)."""
+        return self.encode_features(*self._features(wav_16k, lengths))
 
     @torch.no_grad()
     def decode_tokens(self, idx: torch.Tensor) -> torch.Tensor:

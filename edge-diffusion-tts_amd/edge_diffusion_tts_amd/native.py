@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = (
     "edtts_decoder_forward_len", "edtts_generate_len", "edtts_sample_ddpm_len", "edtts_sample_multistep_len",
     "edtts_sample_inpaint_len", "edtts_randn_rows",
     "edtts_sem_packed_bytes", "edtts_sem_num_codes", "edtts_sem_pack", "edtts_sem_encode", "edtts_sem_decode", "edtts_sem_stats",
+    "edtts_hubert_frames", "edtts_hubert_packed_bytes", "edtts_hubert_pack", "edtts_hubert_workspace_bytes", "edtts_hubert_forward",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -56,6 +57,12 @@ def sem_dims(in_dim: int, semantic_dim: int, levels: Optional[Sequence[int]] = N
     else:
         d.quantizer, d.codebook_size = SEM_VQ, int(codebook_size)
     return d
+
+
+class EdttsHubertDims(C.Structure):
+    _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 16), ("conv_kernel", C.c_int32 * 16), ("conv_stride", C.c_int32 * 16),
+                ("hidden", C.c_int32), ("heads", C.c_int32), ("intermediate", C.c_int32), ("num_layers", C.c_int32),
+                ("pos_kernel", C.c_int32), ("pos_groups", C.c_int32), ("layer_norm_eps", C.c_float)]
 
 
 COMPUTE_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -127,6 +134,12 @@ def lib() -> C.CDLL:
     L.edtts_sem_encode.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.edtts_sem_decode.argtypes = [sdp, vp, vp, C.c_int64, vp, vp]
     L.edtts_sem_stats.argtypes = [vp, C.c_int64, vp, vp, vp]
+    hdp = C.POINTER(EdttsHubertDims)
+    L.edtts_hubert_frames.argtypes = [hdp, C.c_int64, C.POINTER(C.c_int64)]
+    L.edtts_hubert_packed_bytes.argtypes = [hdp, C.POINTER(sz)]
+    L.edtts_hubert_pack.argtypes = [hdp, C.POINTER(vp), i32, vp, vp]
+    L.edtts_hubert_workspace_bytes.argtypes = [hdp, i32, i32, C.POINTER(sz)]
+    L.edtts_hubert_forward.argtypes = [hdp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -555,6 +568,40 @@ def sem_stats(counts: torch.Tensor):
     used = torch.empty((), dtype=torch.int64, device=counts.device)
     lib().edtts_sem_stats(_dev_ptr(counts, torch.int32, "counts"), counts.numel(), ppl.data_ptr(), used.data_ptr(), _stream(counts.device))
     return ppl, used
+
+
+# ---------------------------------------------------------------------------------------------- HuBERT backbone
+def hubert_frames(dims: EdttsHubertDims, n_samples: int) -> int:
+    out = C.c_int64(0)
+    lib().edtts_hubert_frames(C.byref(dims), int(n_samples), C.byref(out))
+    return out.value
+
+
+def hubert_packed_bytes(dims: EdttsHubertDims) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_hubert_packed_bytes(C.byref(dims), C.byref(out))
+    return out.value
+
+
+def hubert_workspace_bytes(dims: EdttsHubertDims, B: int, T_audio: int) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_hubert_workspace_bytes(C.byref(dims), int(B), int(T_audio), C.byref(out))
+    return out.value
+
+
+def hubert_pack(dims: EdttsHubertDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor) -> None:
+    """Pack the backbone's weights (include/edtts.h: edtts_hubert_pack, slot order there) into `packed` (uint8 device tensor)."""
+    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    lib().edtts_hubert_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
+
+
+def hubert_forward(dims: EdttsHubertDims, packed: torch.Tensor, wav: torch.Tensor, lengths: Optional[torch.Tensor], out: torch.Tensor,
+                   workspace: torch.Tensor) -> None:
+    """wav [B, T_audio] -> out [B, T_feat, hidden] on the current stream (include/edtts.h: edtts_hubert_forward)."""
+    B, T = wav.shape
+    lib().edtts_hubert_forward(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(wav, torch.float32, "wav"), B, T,
+                               _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(out, torch.float32, "out"),
+                               _dev_ptr(workspace, torch.uint8, "workspace"), _stream(wav.device))
 
 
 def set_substreams(n: int) -> int:

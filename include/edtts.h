@@ -401,6 +401,54 @@ int edtts_sem_decode(const EdttsSemDims* dims, const void* packed, const int64_t
  * [1] = #(counts > 0) (fsq.py:189-193, vq.py:101-105).  One block, fixed order: bitwise reproducible. */
 int edtts_sem_stats(const int32_t* counts, int64_t n_codes, float* perplexity, int64_t* used, void* stream);
 
+/* ---- HuBERT backbone  (transformers HubertModel, feat_extract_norm = "group", do_stable_layer_norm = False: hubert-base) ------------
+ * wav [B, T_audio] fp32 -> HubertModel(wav, output_hidden_states=True).hidden_states[num_layers] [B, T_feat, hidden], eval mode, fp32.
+ * Only the layers up to num_layers are packed and run; num_layers = 0 is the output of the encoder's LayerNorm.  GELU is the erf form
+ * throughout.  The caller (edge_diffusion_tts_amd/hubert.py) checks the layout fields that are not numbers (feat_extract_norm,
+ * do_stable_layer_norm, conv_bias, the activations, feat_proj_layer_norm, conv_pos_batch_norm).
+ * Limits (EDTTS_ERR_UNSUPPORTED outside): 1..16 conv layers, conv_dim[i] % 4 == 0, conv_kernel[0] <= 64; hidden % heads == 0,
+ * head_dim <= 128, hidden and intermediate % 4 == 0, (hidden / pos_groups) % 4 == 0; num_layers in [0, 256]. */
+typedef struct EdttsHubertDims {
+  int32_t n_conv;           /* len(config.conv_dim)                      */
+  int32_t conv_dim[16];     /* config.conv_dim                           */
+  int32_t conv_kernel[16];  /* config.conv_kernel                        */
+  int32_t conv_stride[16];  /* config.conv_stride                        */
+  int32_t hidden;           /* config.hidden_size                        */
+  int32_t heads;            /* config.num_attention_heads                */
+  int32_t intermediate;     /* config.intermediate_size                  */
+  int32_t num_layers;       /* encoder layers to run: hidden_states[num_layers] */
+  int32_t pos_kernel;       /* config.num_conv_pos_embeddings            */
+  int32_t pos_groups;       /* config.num_conv_pos_embedding_groups      */
+  float layer_norm_eps;     /* config.layer_norm_eps (the GroupNorm keeps nn.GroupNorm's 1e-5) */
+} EdttsHubertDims;
+/* Output frames of n_samples (HubertModel._get_feat_extract_output_lengths: per conv floor((n - k) / s) + 1), 0 if none. */
+int edtts_hubert_frames(const EdttsHubertDims* dims, int64_t n_samples, int64_t* out_frames);
+/* Packed blob: conv weights as [co][k][ci] (implicit-GEMM order; conv0 as [k0][C0]), q | k | v as one [3H][H] matrix, everything else as stored.
+ * slots (host array of device fp32 pointers; state-dict tensors, modeling_hubert.py names):
+ *   feature_extractor.conv_layers.0.conv.weight [C0][1][k0], .0.layer_norm.weight, .0.layer_norm.bias (the GroupNorm),
+ *   feature_extractor.conv_layers.i.conv.weight [Ci][Ci-1][ki] for i = 1 .. n_conv - 1,
+ *   feature_projection.layer_norm.weight, .bias, feature_projection.projection.weight [H][C_last], .bias,
+ *   encoder.pos_conv_embed.conv weight [H][H / groups][pos_kernel] WITH THE WEIGHT NORM FOLDED IN (w[:, :, k] = g[k] v[:, :, k] /
+ *   |v[:, :, k]|, torch._weight_norm(v, g, 2)), its bias, encoder.layer_norm.weight, .bias,
+ *   then per layer l < num_layers (encoder.layers.l.): attention.q_proj.weight, .bias, k_proj.weight, .bias, v_proj.weight, .bias,
+ *   out_proj.weight, .bias, layer_norm.weight, .bias, feed_forward.intermediate_dense.weight, .bias, output_dense.weight, .bias,
+ *   final_layer_norm.weight, .bias.   3 + (n_conv - 1) + 8 + 16 num_layers slots. */
+int edtts_hubert_packed_bytes(const EdttsHubertDims* dims, size_t* out_bytes);
+int edtts_hubert_pack(const EdttsHubertDims* dims, const void* const* slots, int n_slots, void* packed, void* stream);
+/* Workspace for one (B, T_audio): conv0's output [B][T0][C0] (stored, not recomputed inside conv1: 1.0 GiB at B = 16 x 10 s), the
+ * conv ping-pong buffers and the encoder's [B T_feat] x (hidden | hidden | max(3 hidden, intermediate)) rows.  EDTTS_ERR_ARG when
+ * T_audio gives no output frame. */
+int edtts_hubert_workspace_bytes(const EdttsHubertDims* dims, int B, int T_audio, size_t* out_bytes);
+/* Forward (replaces modeling_hubert.py HubertModel.forward: HubertFeatureEncoder, HubertFeatureProjection, HubertEncoder up to layer
+ * num_layers; HubertPositionalConvEmbedding + HubertSamePadLayer as one zero-padded conv of T_feat outputs).  out [B, T_feat, hidden].
+ * lengths int64 [B] (samples) or NULL.  With lengths, row b is bitwise the call on wav[b, :lengths[b]] alone: GroupNorm statistics
+ * over its own conv0 frames, the positional conv zero-padded at its own end, attention over its own frames(lengths[b]) keys, output
+ * rows past that count 0, samples past lengths[b] never read.  Values are clamped into [the shortest input with one frame, T_audio].
+ * Without lengths every utterance has T_audio samples (the padded batch of the reference); each row still depends on its row only.
+ * out, packed and workspace 16-byte aligned.  No allocation, no host synchronisation: graph-capturable. */
+int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths,
+                         float* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
