@@ -397,8 +397,6 @@ __global__ __launch_bounds__(256) void k_gen_zero_past(float* y, const int64_t* 
 // GenericLauncher: the static interface of Launcher / Launcher16 on the run-time-shape kernels
 // =========================================================================================================
 struct GenericLauncher {
-  using DdpmStep = DdpmStepArgs;
-  using LmsStep = LmsStepArgs;
   static int set_attrs() { return EDTTS_OK; }  // (no kernel here needs more than 64 KiB of LDS)
 
   static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -444,10 +442,14 @@ struct GenericLauncher {
   // context rows (token_emb gather or sem_proj) + context PE, then per layer kv_down -> kv_norm -> kv_up into the K|V cache
   // (per-utterance lengths: context rows past S_b are built from whatever the padding holds and are never read -- the attention reads
   // keys < S_b only, and every other step is row-local)
-  static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
-                 const float* sem_feat, hipStream_t st, const int64_t* s_len = nullptr) {
+  static int ctx(const CallCtx& cc, const int64_t* sem_idx, const float* sem_feat) {
     using namespace edtts_gen;
-    const int rows = B * S, H = lo.H, R = lo.R;
+    const Layout& lo = cc.lo;
+    const Workspace& ws = cc.ws;
+    const float* blob = cc.blob;
+    float* wsb = cc.wsb;
+    const hipStream_t st = cc.st;
+    const int S = cc.S, rows = cc.B * S, H = lo.H, R = lo.R;
     float* c = wsb + ws.g_ctx;
     if (sem_feat) {
       TRY_G(gemm<EPI_PE>(st, sem_feat, lo.SD, blob + lo.semp, blob + lo.semp_b, c, H, rows, H, lo.SD, blob + lo.cpe, S));
@@ -455,7 +457,7 @@ struct GenericLauncher {
       unsigned* err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
       size_t nb = ((size_t)rows * H + 255) / 256;
       if (nb > 4096) nb = 4096;
-      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, c, rows, S, H, lo.NTOK, err, s_len);
+      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, c, rows, S, H, lo.NTOK, err, cc.ln.s);
       LAUNCH_CHECK("k_gen_embed");
     }
     for (int l = 0; l < lo.L; ++l) {
@@ -467,12 +469,15 @@ struct GenericLauncher {
     return EDTTS_OK;
   }
 
-  template <int COW = 0>
-  static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
-                     const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
-                     const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
-                     const VpredStepArgs* vp = nullptr, Lens ln = Lens{}) {
+  static int forward(const CallCtx& c, const float* x, const float* cond_row, int cond_bstride, const StepTail& tail) {
     using namespace edtts_gen;
+    const Layout& lo = c.lo;
+    const Workspace& ws = c.ws;
+    const float* blob = c.blob;
+    float* wsb = c.wsb;
+    const hipStream_t st = c.st;
+    const Lens& ln = c.ln;
+    const int B = c.B, T = c.T, S = c.S;
     const int M = B * T, H = lo.H, FH = lo.FM * lo.H, MEL = lo.MEL;
     float *h = wsb + ws.h, *xn = wsb + ws.g_xn, *big = wsb + ws.g_big, *att = wsb + ws.g_att;
     const size_t row = (size_t)2 * 2 * H;  // one layer's (norm1 | norm3) AdaLN rows
@@ -483,7 +488,7 @@ struct GenericLauncher {
       // self-attention branch
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
       TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, big, 3 * H, M, 3 * H, H));
-      TRY_G(attn(st, lo, B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, window, ln.t, ln.t, ln.t_dbl, ln.t_dbl));
+      TRY_G(attn(st, lo, B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, c.window, ln.t, ln.t, ln.t_dbl, ln.t_dbl));
       TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
       // cross-attention branch
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
@@ -496,47 +501,42 @@ struct GenericLauncher {
       TRY_G(gemm<EPI_RESID>(st, big, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH));
     }
     TRY_G(norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
-    float* e = tail == TAIL_EPS ? eps : wsb + ws.g_eps;
+    float* e = tail.kind == TAIL_EPS ? tail.eps : wsb + ws.g_eps;
     TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, e, MEL, M, MEL, H));
-    if (tail == TAIL_EPS) {
+    if (tail.kind == TAIL_EPS) {
       if (ln.t) {
-        hipLaunchKernelGGL(k_gen_zero_past, dim3(grid_1d((size_t)M * MEL)), dim3(256), 0, st, eps, ln.t, (int)ln.t_dbl, (size_t)M * MEL, T, MEL);
+        hipLaunchKernelGGL(k_gen_zero_past, dim3(grid_1d((size_t)M * MEL)), dim3(256), 0, st, e, ln.t, (int)ln.t_dbl, (size_t)M * MEL, T, MEL);
         LAUNCH_CHECK("k_gen_zero_past");
       }
       return EDTTS_OK;
     }
     KArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = x; a.x_prev = x_prev;
+    a.x = x;
     a.T = T; a.t_len = ln.t; a.t_dbl = ln.t_dbl;
-    bool vec = al16(x) && al16(x_prev) && al16(e) && (ln.t == nullptr || MEL % 4 == 0);
-    if (tail == TAIL_LMS) {
-      a.lms = lms->k; a.h_new = lms->h_new; a.h_old = lms->h_old; a.x0_hist = lms->x0_hist; a.x0_all = lms->x0_all;
+    set_tail_args(tail, &a);
+    bool vec = al16(x) && al16(a.x_prev) && al16(e) && (ln.t == nullptr || MEL % 4 == 0);
+    if (tail.kind == TAIL_LMS) {
       vec = vec && al16(a.h_new) && al16(a.h_old) && al16(a.x0_hist) && al16(a.x0_all);
-    } else if (tail == TAIL_VPRED) {
-      a.vp = vp->k; a.v_uncond = vp->v_uncond;
+    } else if (tail.kind == TAIL_VPRED) {
       vec = vec && al16(a.v_uncond);
-    } else if (tail == TAIL_DDPM) {
-      a.p_coef1 = coef[0]; a.p_coef2 = coef[1]; a.p_sd = coef[2];
-      a.noise = ddpm->noise; a.seed = ddpm->seed; a.philox_base = ddpm->base; a.step = ddpm->step;
+    } else if (tail.kind == TAIL_DDPM) {
       vec = vec && al16(a.noise) && (a.philox_base & 3) == 0;
     } else {
-      a.x0 = x0;
-      a.c_s1m = coef[0]; a.c_sab = coef[1]; a.c_sabp = coef[2]; a.c_dir = coef[3];
-      vec = vec && al16(x0);
+      vec = vec && al16(a.x0);
     }
     const size_t n = (size_t)M * MEL;
     vec = vec && n % 4 == 0;
     size_t nb = ((vec ? n / 4 : n) + 255) / 256;
     if (nb > 4096) nb = 4096;
     if (nb < 1) nb = 1;
-    switch (tail) {
-      case TAIL_LMS: hipLaunchKernelGGL(k_gen_tail<TAIL_LMS>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
-      case TAIL_VPRED: hipLaunchKernelGGL(k_gen_tail<TAIL_VPRED>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
-      case TAIL_DDPM: hipLaunchKernelGGL(k_gen_tail<TAIL_DDPM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
-      default: hipLaunchKernelGGL(k_gen_tail<TAIL_DDIM>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL); break;
-    }
-    LAUNCH_CHECK("k_gen_tail");
-    return EDTTS_OK;
+    return with_tail(tail.kind, [&](auto t) -> int {
+      constexpr int TL = decltype(t)::value;
+      if constexpr (TL != TAIL_QKV && TL != TAIL_EPS) {  // (TAIL_EPS has returned above; TAIL_QKV is never a forward's tail)
+        hipLaunchKernelGGL(k_gen_tail<TL>, dim3((unsigned)nb), dim3(256), 0, st, a, e, n, (int)vec, MEL);
+        LAUNCH_CHECK("k_gen_tail");
+      }
+      return EDTTS_OK;
+    });
   }
 };

@@ -62,11 +62,9 @@ struct Profiler {
   std::mutex mu;
   std::atomic<bool> on{false};
   std::vector<hipEvent_t> start, stop;
-  std::vector<int> kinds;  // 0 = fused layer kernel or attention half, 1 = FFN + tail half
   int used = 0;
 };
 static Profiler g_prof;
-static thread_local int g_prof_kind = 0;  // kind of the launches the calling thread is about to make
 #define PROF_LAUNCH(stream, launch_stmt)                                                       \
   do {                                                                                         \
     if (g_prof.on.load(std::memory_order_relaxed)) {                                           \
@@ -74,7 +72,7 @@ static thread_local int g_prof_kind = 0;  // kind of the launches the calling th
       const bool rec_ = g_prof.used < (int)g_prof.start.size();                                \
       if (rec_) (void)hipEventRecord(g_prof.start[g_prof.used], (stream));                     \
       launch_stmt;                                                                             \
-      if (rec_) { g_prof.kinds[g_prof.used] = g_prof_kind; (void)hipEventRecord(g_prof.stop[g_prof.used++], (stream)); } \
+      if (rec_) (void)hipEventRecord(g_prof.stop[g_prof.used++], (stream));                    \
     } else {                                                                                   \
       launch_stmt;                                                                             \
     }                                                                                          \
@@ -469,10 +467,7 @@ struct KArgs {
   const float *q, *k, *vT;
   float *q_out, *k_out, *vT_out;
   float *kc, *vcT;  // cross K / V^T cache: kernel-specific base (k_ctx: whole cache; k_layer: this layer's slice)
-  // bf16 split layer (edtts_bf16.h, k_attn16 / k_layer16<.., PART16_MID|POST>): attention input q rows, attention output rows,
-  // where the middle kernel leaves the cross-attention q
-  const float* attn_q;
-  float *attn_o, *qc_out;
+  const void* unused_[3];  // (no reader: keeps every later field at its kernel-argument offset, so the kernels' code is unchanged)
   const int64_t* sem_idx;
   const float* sem_feat;
   const float* cond;  // row base: [L][2][2H] per row
@@ -794,17 +789,12 @@ struct QLds {  // q tile in this wave's LDS region, [32][ld]
   EDTTS_DEV f2 q2(int ft, int col) const { return *reinterpret_cast<const f2*>(b2 + ft * 16 * ld + col); }
 };
 
-// PART 0: the whole block in one launch.  PART 1: attention half (self + cross attention, h written back).  PART 2: FFN + tail
-// half, run with a different frames-per-wave instance (see EDTTS_NF_FFN below): the residual tile crosses HBM once more per
-// layer, which buys the FFN / QKV weight stream twice the MFMAs per fragment without inflating the attention's registers.
-enum { PART_ALL = 0, PART_ATTN = 1, PART_FFN = 2 };
-
 // Where the residual tile waits while a branch accumulates (measured on one MI355X, B=256, T=512, whole generate_mel call):
 //   in LDS, next to the (unpadded) cross-attention q tiles -- 160 KiB per block at H = 160 (Cfg::Q_IN_LDS)           16.42 ms
 //   in LDS, with the cross-attention q rows going through global memory (this wave's dead self-attention q rows)     16.53 ms
 //   in the wave's own rows of the h buffer (global), q tiles padded in LDS                                           16.6 ms
 // The first form is used where it fits, the second otherwise (hidden 256: four waves x 32 KiB of residual tiles).
-template <class C, int TAIL, int PART>
+template <class C, int TAIL>
 EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b, int m0, int Tb, int Sb) {
   constexpr int NF = C::NF;
   const int fq = lane & 15, g = lane >> 4;
@@ -848,7 +838,7 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
 #define DIAG_ON(bit) true
 #endif
   // ---- x = x + attn(norm1(x, cond))   (transformer.py:142-146; q/k/v were produced by the previous kernel) ----
-  if (PART != PART_FFN) {
+  {
 #ifndef EDTTS_H_DMA
 #define EDTTS_H_DMA 0  // measured (B=256, T=512, same device): 0.9293 ms with the DMA vs 0.9281 ms without -- not worth a hidden DMA
 #endif
@@ -892,14 +882,9 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
       add_parked_h();
     }
     STAMPX(a.stamps, 1, a.diag_skip);
-  } else {
-#pragma unroll
-    for (int nt = 0; nt < C::HT; ++nt)
-#pragma unroll
-      for (int ft = 0; ft < NF; ++ft) h[nt][ft] = ldg4(hp + 16 * nt + (size_t)ft * 16 * C::H);
   }
   // ---- x = x + cross_attn(norm2(x), context)   (transformer.py:151, mla.py:118-194) --------------------------
-  if (PART != PART_FFN && DIAG_ON(2)) {
+  if (DIAG_ON(2)) {
     {
       f4 hn[C::HT][NF];
       rms_norm_tile<C::HT, NF>(h, a.n2w, nullptr, g, hn);
@@ -953,10 +938,6 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
       add_parked_h();
     }
     STAMPX(a.stamps, 3, a.diag_skip);
-  }
-  if (PART == PART_ATTN) {  // hand the residual tile to the FFN half
-    park_h();
-    return;
   }
   // ---- x = x + ffn(norm3(x, cond))   (transformer.py:154-158, :13-49) ----------------------------------------
   if (DIAG_ON(4)) {
@@ -1025,11 +1006,6 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
   STAMPX(a.stamps, 6, a.diag_skip);
 }
 
-// EDTTS_PERSIST = 1 (experiment): as many blocks as the device holds at once, each wave walking its tiles in a loop (static
-// assignment: tile, tile + waves in flight, ...) -- saves the block turnover between a wave's tiles.
-#ifndef EDTTS_PERSIST
-#define EDTTS_PERSIST 0
-#endif
 // the sampler tail's zeros for a whole skipped tile (frames m0 .. m0 + WF - 1 below T)
 template <class C, int TAIL>
 EDTTS_DEV void tail_zero_tile(const KArgs& a, int b, int m0, int lane) {
@@ -1042,30 +1018,23 @@ EDTTS_DEV void tail_zero_tile(const KArgs& a, int b, int m0, int lane) {
     for (int nt = 0; nt < C::MT; ++nt) tail_zero<TAIL>(a, ((size_t)b * a.T + f) * C::MEL + 16 * nt + 4 * g);
   }
 }
-template <class C, int TAIL, int PART>
+template <class C, int TAIL>
 __global__ __launch_bounds__(C::THREADS, C::DEFER ? 2 : 1) void k_layer(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if EDTTS_PERSIST
-  const int tpu = a.Tp / C::WF, ntiles = a.B * tpu;
-  for (int w = remap_block(blockIdx.x, gridDim.x) * C::WAVES + wave; w < ntiles; w += gridDim.x * C::WAVES) {
-    const int b = w / tpu;
-    layer_tile<C, TAIL, PART>(a, smem, wave, lane, b, (w - b * tpu) * C::WF, a.T, a.S);  // (experiment: no per-utterance lengths)
-  }
-#else
   const TileId tl = wave_tile(a.B, a.Tp, C::WAVES, C::WF);
   if (!tl.valid) return;
   const int Tb = utt_len(a.t_len, tl.b, a.T, a.t_dbl);
   if (tl.m0 >= live_end(Tb)) {  // a tile the utterance's solo call does not have: only the sampler tail's zeros are left to store
-    if constexpr (TAIL != TAIL_QKV && PART != PART_ATTN) tail_zero_tile<C, TAIL>(a, tl.b, tl.m0, lane);
+    if constexpr (TAIL != TAIL_QKV) tail_zero_tile<C, TAIL>(a, tl.b, tl.m0, lane);
     return;
   }
   const int Sb = utt_len(a.s_len, tl.b, a.S);
 #ifdef EDTTS_WAVELOG  // diagnostic builds: when and where every wave of the launch ran (scratch/wavelog.py)
   const unsigned long long wl_r0 = __builtin_amdgcn_s_memrealtime(), wl_c0 = __builtin_amdgcn_s_memtime();
 #endif
-  layer_tile<C, TAIL, PART>(a, smem, wave, lane, tl.b, tl.m0, Tb, Sb);
+  layer_tile<C, TAIL>(a, smem, wave, lane, tl.b, tl.m0, Tb, Sb);
 #ifdef EDTTS_WAVELOG
   if (a.stamps && lane == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1074,7 +1043,6 @@ __global__ __launch_bounds__(C::THREADS, C::DEFER ? 2 : 1) void k_layer(KArgs a)
     p[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID: wave, simd, pipe, cu, sh, se
     p[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
   }
-#endif
 #endif
 }
 
@@ -1097,9 +1065,7 @@ struct CtxArgs {
   const float* stream16;  // k_ctx16: bf16 fragment stream (Layout::s_ctx16)
   const int64_t* s_len;   // per-utterance token counts [B], or null: S for all (rows past them: token id 0 / zero features, as in the solo call)
 };
-// BF16OUT: the cache is written in the bf16 images of edtts_bf16.h (K rows with each head's 32 features in slot order, V^T with
-// each chunk's 32 tokens in slot order); the arithmetic stays fp32 either way (once per call).
-template <class C, bool BF16OUT = false>  // always instantiated with NF = 2 (32 context tokens per wave)
+template <class C>  // always instantiated with NF = 2 (32 context tokens per wave)
 __global__ __launch_bounds__(64 * kCtxWaves) void k_ctx(CtxArgs a) {
   const TileId tl = wave_tile(a.B, a.Sp, kCtxWaves, 32);
   if (!tl.valid) return;  // no block-level synchronisation in this kernel
@@ -1173,45 +1139,6 @@ __global__ __launch_bounds__(64 * kCtxWaves) void k_ctx(CtxArgs a) {
     // kv = kv_up(c): first H outputs = K, second H = V   (mla.py:150-153)
     FragRing<C::RT> ring;
     ring.prime(a.blob + a.kvu[l], lane);
-    if (BF16OUT) {
-      // tile-contiguous images (edtts_bf16.h): K[head][token tile][16 tokens][32 slots], V^T[head][32-token chunk][d-tile][16 d][32 slots]
-      unsigned short* const kimg = reinterpret_cast<unsigned short*>(a.kc) + ((size_t)l * a.B + b) * a.Sp * C::H;
-      unsigned short* const vimg = reinterpret_cast<unsigned short*>(a.vcT) + ((size_t)l * a.B + b) * a.Sp * C::H;
-      const size_t hstride = (size_t)32 * a.Sp;
-      for (int nt = 0; nt < 2 * C::HT; nt += 2) {
-        f4 acc[2][2] = {{splat(0.f), splat(0.f)}, {splat(0.f), splat(0.f)}};
-        gemm_phase<C::RT>(ring, cn, acc[0]);
-        gemm_phase<C::RT>(ring, cn, acc[1]);
-        if (nt < C::HT) {
-#pragma unroll
-          for (int ft = 0; ft < 2; ++ft) {
-            unsigned short v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              v[r] = f32_to_bf16_bits(acc[0][ft][r]);
-              v[4 + r] = f32_to_bf16_bits(acc[1][ft][r]);
-            }
-            unsigned short* d = kimg + (nt >> 1) * hstride + (size_t)((m0 >> 4) + ft) * 512 + fq * 32 + 8 * g;  // pair nt/2 = head nt/2
-#pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = v[j];
-          }
-        } else {
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            // token 16 ft + fq of the chunk sits at key slot 8 (fq >> 2) + 4 ft + (fq & 3); feature 16 (nt - HT + u) + 4 g + r
-            // = head (nt - HT) / 2, d-tile u, d = 4 g + r
-            unsigned short* d = vimg + ((nt - C::HT) >> 1) * hstride + (size_t)(m0 >> 5) * 1024 + u * 512 + (4 * g) * 32 +
-                                8 * (fq >> 2) + (fq & 3);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              d[r * 32] = f32_to_bf16_bits(acc[u][0][r]);
-              d[r * 32 + 4] = f32_to_bf16_bits(acc[u][1][r]);
-            }
-          }
-        }
-      }
-      continue;
-    }
     float* kdst = a.kc + (((size_t)l * a.B + b) * a.Sp + m0 + fq) * C::H + 4 * g;
     float* vdst = a.vcT + (((size_t)l * a.B + b) * C::VR + 4 * g) * a.Sp + m0 + fq;
     for (int nt = 0; nt < 2 * C::HT; ++nt) {
@@ -2243,26 +2170,9 @@ struct Workspace {
   int Tp, Sp, VR;
   unsigned* errp;  // where kernels record clamped indices: word 0 of the CALLER's workspace, also for a sub-batch's slice of it
 };
-// frame tiles per wave of the default-decoder instance.  Measured (B=256, T=512): NF=4 lifts the FFN phase from 80 % to 88 %
-// MFMA-busy as the bare-stream probe predicts, but the attention phases lose more under the doubled register footprint
-// (hipcc spills / shuffles AGPRs): k_layer 1.105 ms vs 1.046 ms at NF=2.  -DEDTTS_NF_DEFAULT=4 builds the 64-frame variant.
-#ifndef EDTTS_NF_DEFAULT
-#define EDTTS_NF_DEFAULT 2
-#endif
-// Frame tiles per wave of the FFN + tail half when the layer is split into two launches (0 = do not split, the default).
-// Measured at B=256, T=512 with -DEDTTS_NF_FFN=4: the 64-frame FFN half alone reaches 121.6 TFLOP/s (77 % of peak) against
-// ~80 % MFMA-busy inside the fused kernel, but attention half 0.613 ms + FFN half 0.462 ms = 1.075 ms per layer loses to the
-// fused 1.046 ms: the second kernel's start-up (exposed loads of 4096 waves at once) and drain cost more than the stream gains.
-#ifndef EDTTS_NF_FFN
-#define EDTTS_NF_FFN 0
-#endif
-// largest frames-per-wave of any kernel instance that serves these dims: the padded length Tp is a multiple of it
-static int wave_frames(const Layout& lo) {
-  if (lo.BF16) return 32;
-  int nf = (lo.H == 160 && lo.HEADS == 4 && lo.MEL == 80) ? EDTTS_NF_DEFAULT : 2;
-  if (EDTTS_NF_FFN > nf && lo.H <= 192) nf = EDTTS_NF_FFN;
-  return 16 * nf;
-}
+// largest frames-per-wave of any fused kernel instance (32; the 16-frame ones split such a tile): the padded length Tp is a
+// multiple of it
+constexpr int kWaveFrames = 32;
 
 static void make_workspace(const Layout& lo, int B, int T, int S, int cond_rows, Workspace* w) {
   const size_t H = lo.H;
@@ -2280,8 +2190,7 @@ static void make_workspace(const Layout& lo, int B, int T, int S, int cond_rows,
     w->errp = nullptr;
     return;
   }
-  const int wf = wave_frames(lo);
-  w->Tp = (T + wf - 1) / wf * wf;
+  w->Tp = (T + kWaveFrames - 1) / kWaveFrames * kWaveFrames;
   w->Sp = (S + 31) / 32 * 32;
   w->VR = (lo.HEADS - 1) * lo.DH + lo.DHP;
   size_t o = 0;
@@ -2511,11 +2420,70 @@ struct LmsStepArgs {
   const float *h_new, *h_old;
   float *x0_hist, *x0_all;
 };
+// What the last layer of a decoder forward does with its output: return eps (TAIL_EPS) or take one sampler step
+struct StepTail {
+  int kind = TAIL_EPS;
+  float* eps = nullptr;         // TAIL_EPS: the decoder output
+  float* x_prev = nullptr;      // every sampler kind: the updated sample
+  float* x0 = nullptr;          // TAIL_DDIM: the x0 prediction
+  const float* coef = nullptr;  // TAIL_DDIM: 4 scalars, TAIL_DDPM: 3
+  DdpmStepArgs ddpm{};
+  LmsStepArgs lms{};
+  VpredStepArgs vp{};
+};
+static void set_tail_args(const StepTail& t, KArgs* a) {
+  if (t.kind == TAIL_EPS) {
+    a->eps = t.eps;
+    return;
+  }
+  a->x_prev = t.x_prev;
+  if (t.kind == TAIL_LMS) {
+    a->lms = t.lms.k; a->h_new = t.lms.h_new; a->h_old = t.lms.h_old; a->x0_hist = t.lms.x0_hist; a->x0_all = t.lms.x0_all;
+  } else if (t.kind == TAIL_VPRED) {
+    a->vp = t.vp.k; a->v_uncond = t.vp.v_uncond;
+  } else if (t.kind == TAIL_DDPM) {
+    a->p_coef1 = t.coef[0]; a->p_coef2 = t.coef[1]; a->p_sd = t.coef[2];
+    a->noise = t.ddpm.noise; a->seed = t.ddpm.seed; a->philox_base = t.ddpm.base; a->step = t.ddpm.step;
+  } else {
+    a->x0 = t.x0;
+    a->c_s1m = t.coef[0]; a->c_sab = t.coef[1]; a->c_sabp = t.coef[2]; a->c_dir = t.coef[3];
+  }
+}
+// f(std::integral_constant<int, TAIL_*>) for the run-time tail kind: picks the kernel instance of that kind
+template <class F>
+static int with_tail(int kind, F&& f) {
+  switch (kind) {
+    case TAIL_QKV: return f(std::integral_constant<int, TAIL_QKV>{});
+    case TAIL_EPS: return f(std::integral_constant<int, TAIL_EPS>{});
+    case TAIL_LMS: return f(std::integral_constant<int, TAIL_LMS>{});
+    case TAIL_DDPM: return f(std::integral_constant<int, TAIL_DDPM>{});
+    case TAIL_VPRED: return f(std::integral_constant<int, TAIL_VPRED>{});
+    default: return f(std::integral_constant<int, TAIL_DDIM>{});
+  }
+}
+#define TRY_G(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+// ... for every kind (the hipFuncSetAttribute lists)
+template <class F>
+static int for_each_tail(F&& f) {
+  for (int kind : {TAIL_QKV, TAIL_EPS, TAIL_DDIM, TAIL_DDPM, TAIL_LMS, TAIL_VPRED}) TRY_G(with_tail(kind, f));
+  return EDTTS_OK;
+}
 // per-utterance frame / token counts of a (sub-)batch: device int64 [B] each, or null (edtts_*_len)
 struct Lens {
   const int64_t *t = nullptr, *s = nullptr;
   bool t_dbl = false;  // t holds token counts (frames = 2 x tokens)
   Lens at(int off) const { return Lens{t ? t + off : nullptr, s ? s + off : nullptr, t_dbl}; }
+};
+// What every launch of one (sub-)batch shares: shapes, weights, its workspace slice, lengths and stream
+struct CallCtx {
+  const Layout& lo;
+  const float* blob;
+  Workspace ws;
+  float* wsb;  // base of the (sub-)batch's workspace slice
+  int B, T, S, window;
+  Lens ln;
+  hipStream_t st;
 };
 
 #ifdef EDTTS_STAMPS
@@ -2525,6 +2493,101 @@ static unsigned long long* g_stamps_fwd = nullptr;  // diagnostic builds only, s
 static unsigned long long* g_wavelog = nullptr;  // diagnostic builds only: [layer launches of ONE forward][8192 waves][6]
 static thread_local int g_wavelog_base = 0;       // first wave index of the sub-batch being launched
 #endif
+
+// CtxArgs of a context-cache launch (fp32 and bf16 instances)
+static CtxArgs ctx_args(const CallCtx& c, const int64_t* sem_idx, const float* sem_feat) {
+  const Layout& lo = c.lo;
+  CtxArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = c.B; a.S = c.S; a.Sp = c.ws.Sp; a.L = lo.L; a.SD = lo.SD; a.n_tok = lo.NTOK; a.max_cpos = lo.MAXCPOS;
+  a.sem_idx = sem_idx; a.sem_feat = sem_feat; a.s_len = c.ln.s;
+  a.tok = c.blob + lo.tok; a.semp = c.blob + lo.semp; a.semp_b = c.blob + lo.semp_b; a.cpe = c.blob + lo.cpe; a.blob = c.blob;
+  for (int l = 0; l < lo.L; ++l) {
+    a.kvd[l] = (unsigned)lo.layer[l].kvd; a.kvn[l] = (unsigned)lo.layer[l].kvn; a.kvu[l] = (unsigned)lo.layer[l].kvu;
+  }
+  a.kc = c.wsb + c.ws.kc; a.vcT = c.wsb + c.ws.vcT;
+  a.err = c.ws.errp ? c.ws.errp : reinterpret_cast<unsigned*>(c.wsb + c.ws.err);
+  return a;
+}
+
+// KArgs of one forward of the fused kernels (fp32 and bf16 instances).  ES: element size of the q / k / v^T sets and the cross cache
+// in floats' halves -- the bf16 instance holds bf16 there, half as many floats.
+template <int ES>
+struct ForwardArgs {
+  KArgs a;
+  const CallCtx& c;
+  size_t qk_set, v_set;  // floats per q / k set and per v^T set
+  ForwardArgs(const CallCtx& c_, const float* x, const float* cond_row, int cond_bstride) : c(c_) {
+    const Layout& lo = c.lo;
+    const float* blob = c.blob;
+    memset(&a, 0, sizeof(a));
+    a.B = c.B; a.T = c.T; a.Tp = c.ws.Tp; a.S = c.S; a.Sp = c.ws.Sp; a.window = c.window; a.max_pos = lo.MAXPOS;
+    a.max_cpos = lo.MAXCPOS; a.n_tok = lo.NTOK; a.SD = lo.SD; a.L = lo.L; a.ffn_tiles = lo.FM * lo.HT;
+    a.h = c.wsb + c.ws.h;
+    a.inp = blob + lo.inp; a.inp_b = blob + lo.inp_b; a.pe = blob + lo.pe;
+    a.fnw = blob + lo.fnw; a.fnb = blob + lo.fnb; a.outp_b = blob + lo.outp_b;
+#ifdef EDTTS_DIAG
+    const char* e = getenv("EDTTS_DIAG_SKIP");
+    a.diag_skip = e ? atoi(e) : 0;
+#endif
+#ifdef EDTTS_STAMPS
+    {
+      auto env = [](const char* n, int d) { const char* e = getenv(n); return e ? atoi(e) : d; };
+      a.diag_skip = env("EDTTS_STAMP_HEAD", 1) | (env("EDTTS_STAMP_WAVE", 0) << 8) | (env("EDTTS_STAMP_BLOCK", 8) << 16);
+    }
+#endif
+    a.x = x; a.cond = cond_row; a.cond_bstride = cond_bstride;
+    a.t_len = c.ln.t; a.s_len = c.ln.s; a.t_dbl = c.ln.t_dbl;
+    qk_set = (size_t)c.B * c.ws.Tp * lo.H / ES;
+    v_set = (size_t)c.B * c.ws.VR * c.ws.Tp / ES;
+    set_qkv(1, 0);  // the prologue writes set 0
+    a.n1w = blob + lo.layer[0].n1w; a.stream = blob + lo.inp; a.layer = 0;  // stream: inp | qkv(0)
+  }
+  void set_qkv(int in_set, int out_set) {
+    const Workspace& ws = c.ws;
+    a.q = c.wsb + ws.q + in_set * qk_set; a.k = c.wsb + ws.k + in_set * qk_set; a.vT = c.wsb + ws.vT + in_set * v_set;
+    a.q_out = c.wsb + ws.q + out_set * qk_set; a.k_out = c.wsb + ws.k + out_set * qk_set; a.vT_out = c.wsb + ws.vT + out_set * v_set;
+  }
+  // layer l's fields; returns the tail kind of its launch (TAIL_QKV but for the last layer)
+  int layer(int l, const StepTail& tail) {
+    const Layout& lo = c.lo;
+    const LayerLayout& y = lo.layer[l];
+    a.layer = l;
+    set_qkv(l & 1, (l + 1) & 1);  // layer l reads set l%2 and its QKV tail writes set (l+1)%2
+    a.proj_b = c.blob + y.proj_b; a.n2w = c.blob + y.n2w; a.n3w = c.blob + y.n3w; a.up_b = c.blob + y.up_b;
+    a.down_b = c.blob + y.down_b; a.stream = c.blob + y.s_body;
+    a.kc = c.wsb + c.ws.kc + (size_t)l * c.B * c.ws.Sp * lo.H / ES;
+    a.vcT = c.wsb + c.ws.vcT + (size_t)l * c.B * c.ws.VR * c.ws.Sp / ES;
+#ifdef EDTTS_WAVELOG
+    a.stamps = g_wavelog ? g_wavelog + (size_t)6 * 8192 * l : nullptr;
+    a.diag_skip = g_wavelog_base;
+#endif
+#ifdef EDTTS_STAMPS
+    a.stamps = g_stamps_fwd ? g_stamps_fwd + 128 * l : nullptr;
+#endif
+    if (l + 1 < lo.L) {
+      a.n1w = c.blob + lo.layer[l + 1].n1w;
+      return TAIL_QKV;
+    }
+    set_tail_args(tail, &a);
+    return tail.kind;
+  }
+};
+
+// kernels with > 64 KiB of dynamic LDS need the opt-in attribute: LN::set_attrs() once per device
+// (one flag per device ordinal, so that a process driving several GPUs opts in on each)
+template <class LN>
+static int set_attrs_once() {
+  static std::atomic<bool> done[64];  // (two threads may both set the attributes: hipFuncSetAttribute is idempotent)
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail(EDTTS_ERR_UNSUPPORTED, "device ordinal %d out of range", dev);
+  if (done[dev].load(std::memory_order_acquire)) return EDTTS_OK;
+  TRY_G(LN::set_attrs());
+  done[dev].store(true, std::memory_order_release);
+  return EDTTS_OK;
+}
+
 template <class C>
 struct Launcher {
   // One wave of these kernels per SIMD, on EVERY CU: an instance that needs fewer than 257 registers (the 16-frames-per-wave ones
@@ -2538,58 +2601,24 @@ struct Launcher {
     const size_t need = stash_lds<C>() + (C::Q_IN_LDS ? (size_t)C::WAVES * C::WF * C::H * sizeof(float) : 0);
     return need > occupancy_lds() ? need : occupancy_lds();
   }
-  // split layer: attention half with this instance (C), FFN + tail half with CF (more frames per wave)
-  static constexpr bool SPLIT = (EDTTS_NF_FFN > C::NF) && C::H <= 192;
-  using CF = Cfg<C::H, C::HEADS, C::MEL, (SPLIT ? EDTTS_NF_FFN : C::NF)>;
-  static int grid_f(int B, int Tp) { return (B * (Tp / CF::WF) + CF::WAVES - 1) / CF::WAVES; }
   static int grid(int B, int Tp) { return (B * (Tp / C::WF) + C::WAVES - 1) / C::WAVES; }
   static int ctx_grid(int B, int Sp) { return (B * (Sp / 32) + kCtxWaves - 1) / kCtxWaves; }
   using C2 = Cfg<C::H, C::HEADS, C::MEL, 2>;  // geometry of the context kernel
   // the 16-frames-per-wave instance for small grids (built for the default decoder)
-  static constexpr bool HAS_SMALL = C::NF == 2 && (C::H == 160 || C::H == 256) && !SPLIT;
+  static constexpr bool HAS_SMALL = C::NF == 2 && (C::H == 160 || C::H == 256);
   using Small = Cfg<C::H, C::HEADS, C::MEL, 1>;
   // one wave of these kernels fills a SIMD (> 256 registers): the device runs 4 * #CUs of them at a time (1024 on an MI355X)
   static int wave_slots() { return device_simds(); }
 
-  static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
-                 const float* sem_feat, hipStream_t st, const int64_t* s_len = nullptr) {
-    CtxArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.S = S; a.Sp = ws.Sp; a.L = lo.L; a.SD = lo.SD; a.n_tok = lo.NTOK; a.max_cpos = lo.MAXCPOS;
-    a.sem_idx = sem_idx; a.sem_feat = sem_feat; a.s_len = s_len;
-    a.tok = blob + lo.tok; a.semp = blob + lo.semp; a.semp_b = blob + lo.semp_b; a.cpe = blob + lo.cpe; a.blob = blob;
-    for (int l = 0; l < lo.L; ++l) {
-      a.kvd[l] = (unsigned)lo.layer[l].kvd; a.kvn[l] = (unsigned)lo.layer[l].kvn; a.kvu[l] = (unsigned)lo.layer[l].kvu;
-    }
-    a.kc = wsb + ws.kc; a.vcT = wsb + ws.vcT;
-    a.err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
+  static int ctx(const CallCtx& c, const int64_t* sem_idx, const float* sem_feat) {
+    const CtxArgs a = ctx_args(c, sem_idx, sem_feat);
     // one block per token tile group walks all layers -- unless that leaves most of the chip idle (B = 1: one block): then the
     // layers of a tile go to separate blocks
-    const int gx = ctx_grid(B, ws.Sp);
-    const int gy = (gx * 4 <= wave_slots() / 4) ? lo.L : 1;
-    hipLaunchKernelGGL(k_ctx<C2>, dim3(gx, gy), dim3(64 * kCtxWaves), 0, st, a);
+    const int gx = ctx_grid(c.B, c.ws.Sp);
+    const int gy = (gx * 4 <= wave_slots() / 4) ? c.lo.L : 1;
+    hipLaunchKernelGGL(k_ctx<C2>, dim3(gx, gy), dim3(64 * kCtxWaves), 0, c.st, a);
     LAUNCH_CHECK("k_ctx");
     return EDTTS_OK;
-  }
-
-  static void base_args(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S,
-                        int window, KArgs* a) {
-    memset(a, 0, sizeof(*a));
-    a->B = B; a->T = T; a->Tp = ws.Tp; a->S = S; a->Sp = ws.Sp; a->window = window; a->max_pos = lo.MAXPOS;
-    a->max_cpos = lo.MAXCPOS; a->n_tok = lo.NTOK; a->SD = lo.SD; a->L = lo.L; a->ffn_tiles = lo.FM * lo.HT;
-    a->h = wsb + ws.h;
-    a->inp = blob + lo.inp; a->inp_b = blob + lo.inp_b; a->pe = blob + lo.pe;
-    a->fnw = blob + lo.fnw; a->fnb = blob + lo.fnb; a->outp_b = blob + lo.outp_b;
-#ifdef EDTTS_DIAG
-    const char* e = getenv("EDTTS_DIAG_SKIP");
-    a->diag_skip = e ? atoi(e) : 0;
-#endif
-#ifdef EDTTS_STAMPS
-    {
-      auto env = [](const char* n, int d) { const char* e = getenv(n); return e ? atoi(e) : d; };
-      a->diag_skip = env("EDTTS_STAMP_HEAD", 1) | (env("EDTTS_STAMP_WAVE", 0) << 8) | (env("EDTTS_STAMP_BLOCK", 8) << 16);
-    }
-#endif
   }
 
   // The cooperative layer kernel (edtts_coop.h: W waves per frame tile) serves the grids that leave SIMDs idle; compiled for the
@@ -2599,7 +2628,7 @@ struct Launcher {
   //     4 t32 <= SIMDs   32-frame tiles, four waves each
   //     2 t32 <= SIMDs   32-frame tiles, two waves each       (B = 32, T = 512: 1024 waves that keep k_layer's 8 MFMAs per fragment)
   //     else             k_layer, one wave per 32-frame tile
-  static constexpr bool HAS_COOP = C::NF == 2 && !SPLIT && ((C::H == 160 && C::HEADS == 4) || (C::H == 256 && C::HEADS == 8)) && C::MEL == 80;
+  static constexpr bool HAS_COOP = C::NF == 2 && ((C::H == 160 && C::HEADS == 4) || (C::H == 256 && C::HEADS == 8)) && C::MEL == 80;
   static constexpr bool HAS_CO22 = HAS_COOP && Coop<C, 2>::FITS;
   static int coop_choice(int B, int Tp) {  // 0: none; 14: NF 1, W 4; 24: NF 2, W 4; 22: NF 2, W 2
     int co = current_settings().coop;  // (edtts_set_coop: 0 switches the cooperative kernel off, 14 / 24 / 22 force an instance)
@@ -2610,166 +2639,64 @@ struct Launcher {
     return (co == 22 && !HAS_CO22) ? 0 : co;
   }
   // one decoder forward given conditioning rows + context cache already in the workspace
-  using DdpmStep = DdpmStepArgs;
-  using LmsStep = LmsStepArgs;
   template <int COW = 0>
-  static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
-                     const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
-                     const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
-                     const VpredStepArgs* vp = nullptr, Lens ln = Lens{}) {
+  static int forward(const CallCtx& c, const float* x, const float* cond_row, int cond_bstride, const StepTail& tail) {
     if constexpr (HAS_COOP && COW == 0) {
-      const int co = coop_choice(B, ws.Tp);
-      if (co == 14) return Launcher<Small>::template forward<4>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp, ln);
-      if (co == 24) return forward<4>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp, ln);
+      const int co = coop_choice(c.B, c.ws.Tp);
+      if (co == 14) return Launcher<Small>::template forward<4>(c, x, cond_row, cond_bstride, tail);
+      if (co == 24) return forward<4>(c, x, cond_row, cond_bstride, tail);
       if constexpr (HAS_CO22) {
-        if (co == 22) return forward<2>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st, ddpm, lms, vp, ln);
+        if (co == 22) return forward<2>(c, x, cond_row, cond_bstride, tail);
       }
     }
     // Small grids: with 32 frames per wave fewer waves than SIMDs would be launched (B = 32 at T = 512: 512 waves for 1024 SIMDs;
     // B = 1: 8) -- the 16-frames-per-wave instance doubles the number of waves.  Same arithmetic per frame, bitwise.
     if constexpr (HAS_SMALL && COW == 0) {
-      if (2 * B * (ws.Tp / C::WF) <= wave_slots())  // ... as long as the doubled wave count still runs in one round
-        return Launcher<Small>::template forward<0>(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st,
-                                                    ddpm, lms, vp, ln);
+      if (2 * c.B * (c.ws.Tp / C::WF) <= wave_slots())  // ... as long as the doubled wave count still runs in one round
+        return Launcher<Small>::template forward<0>(c, x, cond_row, cond_bstride, tail);
     }
-    KArgs a;
-    base_args(lo, blob, ws, wsb, B, T, S, window, &a);
-    a.x = x; a.cond = cond_row; a.cond_bstride = cond_bstride;
-    a.t_len = ln.t; a.s_len = ln.s; a.t_dbl = ln.t_dbl;
-    const int g = grid(B, ws.Tp);
-#if EDTTS_PERSIST
-    const int g_layer = g < wave_slots() / C::WAVES ? g : wave_slots() / C::WAVES;
-#else
-    const int g_layer = g;
-#endif
-    const size_t qk_set = (size_t)B * ws.Tp * lo.H, v_set = (size_t)B * ws.VR * ws.Tp;
-    auto set_qkv = [&](int in_set, int out_set) {
-      a.q = wsb + ws.q + in_set * qk_set; a.k = wsb + ws.k + in_set * qk_set; a.vT = wsb + ws.vT + in_set * v_set;
-      a.q_out = wsb + ws.q + out_set * qk_set; a.k_out = wsb + ws.k + out_set * qk_set; a.vT_out = wsb + ws.vT + out_set * v_set;
-    };
-    set_qkv(1, 0);  // the prologue writes set 0
-    a.n1w = blob + lo.layer[0].n1w; a.stream = blob + lo.inp; a.layer = 0;  // stream: inp | qkv(0)
+    ForwardArgs<1> f(c, x, cond_row, cond_bstride);
+    const KArgs& a = f.a;
+    const hipStream_t st = c.st;
+    const int g = grid(c.B, c.ws.Tp);
     if constexpr (COW != 0) {
-      hipLaunchKernelGGL((k_prologue_co<C, (COW ? COW : 4)>), dim3(B * (ws.Tp / C::WF)), dim3(64 * (COW ? COW : 4)), C::HT * C::NF * 1024, st, a);
+      hipLaunchKernelGGL((k_prologue_co<C, COW>), dim3(c.B * (c.ws.Tp / C::WF)), dim3(64 * COW), C::HT * C::NF * 1024, st, a);
     } else {
       hipLaunchKernelGGL(k_prologue<C>, dim3(g), dim3(C::THREADS), ring_lds(), st, a);
     }
     LAUNCH_CHECK("k_prologue");
-    for (int l = 0; l < lo.L; ++l) {
-      const LayerLayout& y = lo.layer[l];
-      a.layer = l;
-      set_qkv(l & 1, (l + 1) & 1);  // layer l reads set l%2 and its QKV tail writes set (l+1)%2
-      a.proj_b = blob + y.proj_b; a.n2w = blob + y.n2w; a.n3w = blob + y.n3w; a.up_b = blob + y.up_b;
-      a.down_b = blob + y.down_b; a.stream = blob + y.s_body;
-      a.kc = wsb + ws.kc + (size_t)l * B * ws.Sp * lo.H;
-      a.vcT = wsb + ws.vcT + (size_t)l * B * ws.VR * ws.Sp;
-      int t_eff = tail;
-      if (l + 1 < lo.L) {
-        a.n1w = blob + lo.layer[l + 1].n1w;
-        t_eff = TAIL_QKV;
-      } else if (tail == TAIL_EPS) {
-        a.eps = eps;
-      } else if (tail == TAIL_LMS) {
-        a.x_prev = x_prev;
-        a.lms = lms->k; a.h_new = lms->h_new; a.h_old = lms->h_old; a.x0_hist = lms->x0_hist; a.x0_all = lms->x0_all;
-      } else if (tail == TAIL_VPRED) {
-        a.x_prev = x_prev;
-        a.vp = vp->k; a.v_uncond = vp->v_uncond;
-      } else if (tail == TAIL_DDPM) {
-        a.x_prev = x_prev;
-        a.p_coef1 = coef[0]; a.p_coef2 = coef[1]; a.p_sd = coef[2];
-        a.noise = ddpm->noise; a.seed = ddpm->seed; a.philox_base = ddpm->base; a.step = ddpm->step;
-      } else {
-        a.x_prev = x_prev; a.x0 = x0;
-        a.c_s1m = coef[0]; a.c_sab = coef[1]; a.c_sabp = coef[2]; a.c_dir = coef[3];
-      }
-#ifdef EDTTS_WAVELOG
-      a.stamps = g_wavelog ? g_wavelog + (size_t)6 * 8192 * l : nullptr;
-      a.diag_skip = g_wavelog_base;
-#endif
-#ifdef EDTTS_STAMPS
-      a.stamps = g_stamps_fwd ? g_stamps_fwd + 128 * l : nullptr;
-#endif
-      if constexpr (SPLIT) {  // (not instantiated in the product build: EDTTS_NF_FFN defaults to the instance's own NF)
-        static_assert(!SPLIT, "the two-launch layer experiment predates the LDS-parked residual tile (see git history)");
-        g_prof_kind = 0;
-        PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer<C, TAIL_QKV, PART_ATTN>), dim3(g), dim3(C::THREADS), layer_lds(), st, a));
-        LAUNCH_CHECK("k_layer<attn>");
-        a.stream = blob + y.s_ffn;
-        g_prof_kind = 1;
-        const int gf = grid_f(B, ws.Tp);
-#define EDTTS_LAUNCH_FFN(TL) PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer<CF, TL, PART_FFN>), dim3(gf), dim3(CF::THREADS), 0, st, a))
-        switch (t_eff) {
-          case TAIL_QKV: EDTTS_LAUNCH_FFN(TAIL_QKV); break;
-          case TAIL_EPS: EDTTS_LAUNCH_FFN(TAIL_EPS); break;
-          case TAIL_LMS: EDTTS_LAUNCH_FFN(TAIL_LMS); break;
-          case TAIL_DDPM: EDTTS_LAUNCH_FFN(TAIL_DDPM); break;
-          case TAIL_VPRED: EDTTS_LAUNCH_FFN(TAIL_VPRED); break;
-          default: EDTTS_LAUNCH_FFN(TAIL_DDIM); break;
+    for (int l = 0; l < c.lo.L; ++l) {
+      TRY_G(with_tail(f.layer(l, tail), [&](auto t) -> int {
+        constexpr int TL = decltype(t)::value;
+        if constexpr (COW != 0) {
+          using CO = Coop<C, COW>;
+          const int tiles = c.B * (c.ws.Tp / C::WF);
+          PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer_co<C, TL, COW>), dim3((tiles + CO::TILES - 1) / CO::TILES), dim3(CO::THREADS), CO::LDS_BYTES, st, a));
+        } else {
+          PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer<C, TL>), dim3(g), dim3(C::THREADS), layer_lds(), st, a));
         }
-#undef EDTTS_LAUNCH_FFN
-        g_prof_kind = 0;
-      } else {
-#define EDTTS_LAUNCH_ALL(TL)                                                                                                            \
-  do {                                                                                                                                  \
-    if constexpr (COW != 0) {                                                                                                           \
-      using CO = Coop<C, (COW ? COW : 4)>;                                                                                              \
-      const int tiles = B * (ws.Tp / C::WF);                                                                                            \
-      PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer_co<C, TL, (COW ? COW : 4)>), dim3((tiles + CO::TILES - 1) / CO::TILES), dim3(CO::THREADS), CO::LDS_BYTES, st, a)); \
-    } else {                                                                                                                            \
-      PROF_LAUNCH(st, hipLaunchKernelGGL((k_layer<C, TL, PART_ALL>), dim3(g_layer), dim3(C::THREADS), layer_lds(), st, a));             \
-    }                                                                                                                                   \
-  } while (0)
-        switch (t_eff) {
-          case TAIL_QKV: EDTTS_LAUNCH_ALL(TAIL_QKV); break;
-          case TAIL_EPS: EDTTS_LAUNCH_ALL(TAIL_EPS); break;
-          case TAIL_LMS: EDTTS_LAUNCH_ALL(TAIL_LMS); break;
-          case TAIL_DDPM: EDTTS_LAUNCH_ALL(TAIL_DDPM); break;
-          case TAIL_VPRED: EDTTS_LAUNCH_ALL(TAIL_VPRED); break;
-          default: EDTTS_LAUNCH_ALL(TAIL_DDIM); break;
-        }
-#undef EDTTS_LAUNCH_ALL
-      }
-      LAUNCH_CHECK("k_layer");
+        LAUNCH_CHECK("k_layer");
+        return EDTTS_OK;
+      }));
     }
     return EDTTS_OK;
   }
 
-  static int set_attrs() {
-    // kernels with > 64 KiB of dynamic LDS need the opt-in attribute
-    // (the attribute is per device: one flag per device ordinal, so that a process driving several GPUs opts in on each)
-    static std::atomic<bool> done[64];  // (two threads may both set the attributes: hipFuncSetAttribute is idempotent)
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(EDTTS_ERR_UNSUPPORTED, "device ordinal %d out of range", dev);
-    if (done[dev].load(std::memory_order_acquire)) return EDTTS_OK;
-    if constexpr (HAS_SMALL) {
-      int rc = Launcher<Small>::set_attrs();
-      if (rc) return rc;
-    }
-    if constexpr (HAS_COOP) {
-#define EDTTS_CO_ATTR(CC, WW, TL) HIP_TRY(hipFuncSetAttribute((const void*)k_layer_co<CC, TL, WW>, hipFuncAttributeMaxDynamicSharedMemorySize, Coop<CC, WW>::LDS_BYTES))
-#define EDTTS_CO_ATTRS(CC, WW) EDTTS_CO_ATTR(CC, WW, TAIL_QKV); EDTTS_CO_ATTR(CC, WW, TAIL_EPS); EDTTS_CO_ATTR(CC, WW, TAIL_DDIM); EDTTS_CO_ATTR(CC, WW, TAIL_DDPM); EDTTS_CO_ATTR(CC, WW, TAIL_LMS); EDTTS_CO_ATTR(CC, WW, TAIL_VPRED)
-      EDTTS_CO_ATTRS(Small, 4);
-      EDTTS_CO_ATTRS(C, 4);
-      if constexpr (HAS_CO22) { EDTTS_CO_ATTRS(C, 2); }
-#undef EDTTS_CO_ATTRS
-#undef EDTTS_CO_ATTR
-    }
+  static int set_attrs() {  // (through set_attrs_once)
+    if constexpr (HAS_SMALL) TRY_G(Launcher<Small>::set_attrs());
     const int lds = (int)layer_lds();
     HIP_TRY(hipFuncSetAttribute((const void*)k_prologue<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_lds()));
-    if constexpr (SPLIT) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_QKV, PART_ATTN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    } else {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_QKV, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_EPS, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_DDIM, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_DDPM, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_LMS, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TAIL_VPRED, PART_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    done[dev].store(true, std::memory_order_release);
-    return EDTTS_OK;
+    return for_each_tail([&](auto t) -> int {
+      constexpr int TL = decltype(t)::value;
+      HIP_TRY(hipFuncSetAttribute((const void*)k_layer<C, TL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      if constexpr (HAS_COOP) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_layer_co<Small, TL, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, Coop<Small, 4>::LDS_BYTES));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_layer_co<C, TL, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, Coop<C, 4>::LDS_BYTES));
+        if constexpr (HAS_CO22)
+          HIP_TRY(hipFuncSetAttribute((const void*)k_layer_co<C, TL, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, Coop<C, 2>::LDS_BYTES));
+      }
+      return EDTTS_OK;
+    });
   }
 };
 
@@ -2780,199 +2707,55 @@ struct Launcher {
 #endif
 template <class C>
 struct Launcher16 {
-  using DdpmStep = DdpmStepArgs;
-  using LmsStep = LmsStepArgs;
-  using C2 = Cfg<C::H, C::HEADS, C::MEL, 2>;  // geometry of the (fp32-arithmetic) context kernel
   static int grid(int B, int Tp) { return (B * (Tp / C::WF) + C::WAVES - 1) / C::WAVES; }
   // Small grids: the 16-frames-per-wave instance (two independent four-wave blocks per CU, bitwise the same results) when the
   // 32-frame waves would leave half of the SIMDs without one (B * T <= 16 k frames on an MI355X).
   static constexpr bool HAS_SMALL = C::NF == 2 && C::H == 256;
   using Small = edtts16::Cfg16<C::H, C::HEADS, C::MEL, 1>;
-  // The 64-frames-per-wave instance (every weight fragment read from the LDS ring feeds four MFMAs instead of two, every K / V^T
-  // tile four instead of two): measured at config 3 it runs the FFN and tail phases ~28 % faster and the attention ~8 % slower
-  // (one head per step, twice the context working set per XCD) -- 33.50 vs 33.52 ms per call, DESIGN.md 4.5.  Round 4: it did not
-  // earn its place (the bar was >= 3 % at config 3), so it is NOT part of the product library any more: an experiment build
-  // (-DEDTTS_EXPERIMENTS -DEDTTS16_WIDE_BUILD=1) carries it, and EDTTS16_WIDE=1 in the environment then selects it.
-#ifndef EDTTS16_WIDE_BUILD
-#define EDTTS16_WIDE_BUILD 0  // measured and rejected (same speed, 7 more kernels): -DEDTTS_EXPERIMENTS -DEDTTS16_WIDE_BUILD=1 builds it
-#endif
-  static constexpr bool HAS_WIDE = EDTTS16_WIDE_BUILD && C::NF == 2 && C::H == 256;
-  using Wide = edtts16::Cfg16<C::H, C::HEADS, C::MEL, 4>;
-  static bool use_wide(int B, int Tp) {
-    static const bool on = [] { const char* e = getenv("EDTTS16_WIDE"); return e && e[0] == '1'; }();
-    (void)B;
-    return on && Tp % 64 == 0;
-  }
   static int simds() { return device_simds(); }
-  static int set_attrs() {  // the weight ring takes > 64 KiB of dynamic LDS: opt in once per device
-    static std::atomic<bool> done[64];  // (two threads may both set the attributes: hipFuncSetAttribute is idempotent)
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(EDTTS_ERR_UNSUPPORTED, "device ordinal %d out of range", dev);
-    if (done[dev].load(std::memory_order_acquire)) return EDTTS_OK;
-    if constexpr (HAS_SMALL) {
-      int rc = Launcher16<Small>::set_attrs();
-      if (rc) return rc;
-    }
-    if constexpr (HAS_WIDE) {
-      int rc = Launcher16<Wide>::set_attrs();
-      if (rc) return rc;
-    }
+  static int set_attrs() {  // the weight ring takes > 64 KiB of dynamic LDS (through set_attrs_once)
+    if constexpr (HAS_SMALL) TRY_G(Launcher16<Small>::set_attrs());
     const int lds = C::LDS_BYTES;
     HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_prologue16<C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     if constexpr (C::NF == 2) HIP_TRY(hipFuncSetAttribute((const void*)k_ctx16<C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, TAIL_QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, TAIL_EPS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, TAIL_DDIM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, TAIL_DDPM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, TAIL_LMS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, TAIL_VPRED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-#if EDTTS16_SPLIT_BUILD
-    using namespace edtts16;
-    // (occupancy experiment: EDTTS16_ATT_LDS bytes of unused dynamic LDS per attention block limit the blocks per CU)
-    HIP_TRY(hipFuncSetAttribute((const void*)k_attn16<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_attn16<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_QKV, PART16_MID>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_QKV, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_EPS, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_DDIM, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_DDPM, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_LMS, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_layer16<C, TAIL_VPRED, PART16_POST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-#endif
-    done[dev].store(true, std::memory_order_release);
-    return EDTTS_OK;
+    return for_each_tail([&](auto t) -> int {
+      HIP_TRY(hipFuncSetAttribute((const void*)edtts16::k_layer16<C, decltype(t)::value>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      return EDTTS_OK;
+    });
   }
-  static int ctx(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int S, const int64_t* sem_idx,
-                 const float* sem_feat, hipStream_t st, const int64_t* s_len = nullptr) {
-    CtxArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.S = S; a.Sp = ws.Sp; a.L = lo.L; a.SD = lo.SD; a.n_tok = lo.NTOK; a.max_cpos = lo.MAXCPOS;
-    a.sem_idx = sem_idx; a.sem_feat = sem_feat; a.s_len = s_len;
-    a.tok = blob + lo.tok; a.semp = blob + lo.semp; a.semp_b = blob + lo.semp_b; a.cpe = blob + lo.cpe; a.blob = blob;
-    for (int l = 0; l < lo.L; ++l) {
-      a.kvd[l] = (unsigned)lo.layer[l].kvd; a.kvn[l] = (unsigned)lo.layer[l].kvn; a.kvu[l] = (unsigned)lo.layer[l].kvu;
-    }
-    a.kc = wsb + ws.kc; a.vcT = wsb + ws.vcT;
-    a.err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
-#ifndef EDTTS16_CTX_F32
-#define EDTTS16_CTX_F32 0   // 1: the context cache from the fp32-arithmetic kernel (k_ctx<.., bf16 out>), as before
-#endif
-    if (EDTTS16_CTX_F32) {
-      hipLaunchKernelGGL((k_ctx<C2, true>), dim3((B * (ws.Sp / 32) + kCtxWaves - 1) / kCtxWaves), dim3(64 * kCtxWaves), 0, st, a);
-      LAUNCH_CHECK("k_ctx<bf16 out>");
-    } else if constexpr (C::NF == 2) {  // (the context cache is always built by the 32-token-per-wave launcher)
-      a.stream16 = blob + lo.s_ctx16;
-      hipLaunchKernelGGL((k_ctx16<C>), dim3((B * (ws.Sp / 32) + C::WAVES - 1) / C::WAVES), dim3(C::THREADS), C::LDS_BYTES, st, a);
+  static int ctx(const CallCtx& c, const int64_t* sem_idx, const float* sem_feat) {
+    if constexpr (C::NF == 2) {  // (the context cache is always built by the 32-token-per-wave launcher)
+      CtxArgs a = ctx_args(c, sem_idx, sem_feat);
+      a.stream16 = c.blob + c.lo.s_ctx16;
+      hipLaunchKernelGGL((k_ctx16<C>), dim3((c.B * (c.ws.Sp / 32) + C::WAVES - 1) / C::WAVES), dim3(C::THREADS), C::LDS_BYTES, c.st, a);
       LAUNCH_CHECK("k_ctx16");
+      return EDTTS_OK;
     } else {
       return fail(EDTTS_ERR_UNSUPPORTED, "internal: context cache requested from the 16-frame launcher");
     }
-    return EDTTS_OK;
   }
-  static int forward(const Layout& lo, const float* blob, const Workspace& ws, float* wsb, int B, int T, int S, int window,
-                     const float* x, const float* cond_row, int cond_bstride, int tail, float* eps, float* x_prev, float* x0,
-                     const float* coef, hipStream_t st, const DdpmStep* ddpm = nullptr, const LmsStep* lms = nullptr,
-                     const VpredStepArgs* vp = nullptr, Lens ln = Lens{}) {
-    if constexpr (HAS_WIDE) {
-      if (use_wide(B, ws.Tp))
-        return Launcher16<Wide>::forward(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st,
-                                         ddpm, lms, vp, ln);
-    }
+  static int forward(const CallCtx& c, const float* x, const float* cond_row, int cond_bstride, const StepTail& tail) {
     if constexpr (HAS_SMALL) {
-      if (2 * B * (ws.Tp / C::WF) <= simds())  // (round 4: forced at B = 256, T = 1024 it runs 49.2 ms per call against 33.6)
-        return Launcher16<Small>::forward(lo, blob, ws, wsb, B, T, S, window, x, cond_row, cond_bstride, tail, eps, x_prev, x0, coef, st,
-                                          ddpm, lms, vp, ln);
+      if (2 * c.B * (c.ws.Tp / C::WF) <= simds())  // (round 4: forced at B = 256, T = 1024 it runs 49.2 ms per call against 33.6)
+        return Launcher16<Small>::forward(c, x, cond_row, cond_bstride, tail);
     }
-    KArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B; a.T = T; a.Tp = ws.Tp; a.S = S; a.Sp = ws.Sp; a.window = window; a.max_pos = lo.MAXPOS;
-    a.max_cpos = lo.MAXCPOS; a.n_tok = lo.NTOK; a.SD = lo.SD; a.L = lo.L; a.ffn_tiles = lo.FM * lo.HT;
-    a.h = wsb + ws.h;
-    a.inp_b = blob + lo.inp_b; a.pe = blob + lo.pe;
-    a.fnw = blob + lo.fnw; a.fnb = blob + lo.fnb; a.outp_b = blob + lo.outp_b;
-    a.x = x; a.cond = cond_row; a.cond_bstride = cond_bstride;
-    a.t_len = ln.t; a.s_len = ln.s; a.t_dbl = ln.t_dbl;
-    const int g = grid(B, ws.Tp);
-    const size_t qk_set = (size_t)B * ws.Tp * lo.H / 2, v_set = (size_t)B * ws.VR * ws.Tp / 2;  // bf16: half the floats
-    auto set_qkv = [&](int in_set, int out_set) {
-      a.q = wsb + ws.q + in_set * qk_set; a.k = wsb + ws.k + in_set * qk_set; a.vT = wsb + ws.vT + in_set * v_set;
-      a.q_out = wsb + ws.q + out_set * qk_set; a.k_out = wsb + ws.k + out_set * qk_set; a.vT_out = wsb + ws.vT + out_set * v_set;
-    };
-    set_qkv(1, 0);
-    a.n1w = blob + lo.layer[0].n1w; a.stream = blob + lo.inp; a.layer = 0;  // stream: inp | qkv(0)
+    ForwardArgs<2> f(c, x, cond_row, cond_bstride);
+    const KArgs& a = f.a;
+    const hipStream_t st = c.st;
+    const int g = grid(c.B, c.ws.Tp);
     hipLaunchKernelGGL(edtts16::k_prologue16<C>, dim3(g), dim3(C::THREADS), C::LDS_BYTES, st, a);
     LAUNCH_CHECK("k_prologue16");
-    for (int l = 0; l < lo.L; ++l) {
-      const LayerLayout& y = lo.layer[l];
-      a.layer = l;
-      set_qkv(l & 1, (l + 1) & 1);
-      a.proj_b = blob + y.proj_b; a.n2w = blob + y.n2w; a.n3w = blob + y.n3w; a.up_b = blob + y.up_b;
-      a.down_b = blob + y.down_b; a.stream = blob + y.s_body;
-      a.kc = wsb + ws.kc + (size_t)l * B * ws.Sp * lo.H / 2;
-      a.vcT = wsb + ws.vcT + (size_t)l * B * ws.VR * ws.Sp / 2;
-      int t_eff = tail;
-      if (l + 1 < lo.L) {
-        a.n1w = blob + lo.layer[l + 1].n1w;
-        t_eff = TAIL_QKV;
-      } else if (tail == TAIL_EPS) {
-        a.eps = eps;
-      } else if (tail == TAIL_LMS) {
-        a.x_prev = x_prev;
-        a.lms = lms->k; a.h_new = lms->h_new; a.h_old = lms->h_old; a.x0_hist = lms->x0_hist; a.x0_all = lms->x0_all;
-      } else if (tail == TAIL_VPRED) {
-        a.x_prev = x_prev;
-        a.vp = vp->k; a.v_uncond = vp->v_uncond;
-      } else if (tail == TAIL_DDPM) {
-        a.x_prev = x_prev;
-        a.p_coef1 = coef[0]; a.p_coef2 = coef[1]; a.p_sd = coef[2];
-        a.noise = ddpm->noise; a.seed = ddpm->seed; a.philox_base = ddpm->base; a.step = ddpm->step;
-      } else {
-        a.x_prev = x_prev; a.x0 = x0;
-        a.c_s1m = coef[0]; a.c_sab = coef[1]; a.c_sabp = coef[2]; a.c_dir = coef[3];
-      }
-#ifdef EDTTS_STAMPS
-      a.stamps = g_stamps_fwd ? g_stamps_fwd + 128 * l : nullptr;
-#endif
-#if EDTTS16_SPLIT_BUILD
-      // Split layer (a -DEDTTS16_SPLIT_BUILD=1 library with EDTTS16_SPLIT=1 in the environment; measured and not shipped, DESIGN.md
-      // 4.5): attention in its own launches at three waves per SIMD.  No extra buffers: within a layer the q / O rows live in the
-      // two q sets (in: q -> cross q; out: O of the self-attention -> O of the cross-attention -> the next layer's q, each wave
-      // touching only its own rows).  Bitwise the same results as the fused launch (scratch/split_probe.py).
-      static const bool split = [] { const char* e = getenv("EDTTS16_SPLIT"); return e && e[0] == '1'; }();
-      static const int att_lds = [] { const char* e = getenv("EDTTS16_ATT_LDS"); return e ? atoi(e) : 0; }();
-      if (split) {
-        a.attn_q = a.q; a.attn_o = a.q_out;
-        PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_attn16<C, true>), dim3(g), dim3(C::THREADS), att_lds, st, a));
-        a.qc_out = const_cast<float*>(a.q);
-        PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_layer16<C, TAIL_QKV, edtts16::PART16_MID>), dim3(g), dim3(C::THREADS), C::LDS_BYTES, st, a));
-        a.attn_q = a.q;
-        PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_attn16<C, false>), dim3(g), dim3(C::THREADS), att_lds, st, a));
-      }
-#define EDTTS_LAUNCH16(TL)                                                                                                          \
-  do {                                                                                                                              \
-    if (split) PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_layer16<C, TL, edtts16::PART16_POST>), dim3(g), dim3(C::THREADS), C::LDS_BYTES, st, a)); \
-    else PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_layer16<C, TL>), dim3(g), dim3(C::THREADS), C::LDS_BYTES, st, a));            \
-  } while (0)
-#else
-#define EDTTS_LAUNCH16(TL) PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_layer16<C, TL>), dim3(g), dim3(C::THREADS), C::LDS_BYTES, st, a))
-#endif
-      switch (t_eff) {
-        case TAIL_QKV: EDTTS_LAUNCH16(TAIL_QKV); break;
-        case TAIL_EPS: EDTTS_LAUNCH16(TAIL_EPS); break;
-        case TAIL_LMS: EDTTS_LAUNCH16(TAIL_LMS); break;
-        case TAIL_DDPM: EDTTS_LAUNCH16(TAIL_DDPM); break;
-        case TAIL_VPRED: EDTTS_LAUNCH16(TAIL_VPRED); break;
-        default: EDTTS_LAUNCH16(TAIL_DDIM); break;
-      }
-#undef EDTTS_LAUNCH16
-      LAUNCH_CHECK("k_layer16");
+    for (int l = 0; l < c.lo.L; ++l) {
+      TRY_G(with_tail(f.layer(l, tail), [&](auto t) -> int {
+        PROF_LAUNCH(st, hipLaunchKernelGGL((edtts16::k_layer16<C, decltype(t)::value>), dim3(g), dim3(C::THREADS), C::LDS_BYTES, st, a));
+        LAUNCH_CHECK("k_layer16");
+        return EDTTS_OK;
+      }));
     }
     return EDTTS_OK;
   }
 };
 
-#define TRY_G(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 #include "edtts_generic.h"
 #include "edtts_semantic.h"
 #include "edtts_hubert.h"
@@ -2984,7 +2767,7 @@ static int no_instance16(const Layout& lo);
 static int no_instance32(const Layout& lo);
 #ifdef EDTTS_FAST_BUILD  // scratch builds (-DEDTTS_EXPERIMENTS): the default decoder's fp32 instance only
 #define EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, ...)                                                       \
-    if (!(lo).BF16 && (lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80, EDTTS_NF_DEFAULT>>; __VA_ARGS__; } \
+    if (!(lo).BF16 && (lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80>>; __VA_ARGS__; } \
     else if ((lo).BF16) { MISS16; }                                                                      \
     else { MISS32; }
 static int no_instance16(const Layout&) { return fail(EDTTS_ERR_UNSUPPORTED, "EDTTS_FAST_BUILD: only the 160/4/80 fp32 instance is compiled"); }
@@ -3011,7 +2794,7 @@ static int no_instance32(const Layout&) { return fail(EDTTS_ERR_UNSUPPORTED, "ED
       EDTTS_EXTRA_INSTANCES16(lo, __VA_ARGS__)                                                           \
       else { MISS16; }                                                                                   \
     }                                                                                                    \
-    else if ((lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80, EDTTS_NF_DEFAULT>>; __VA_ARGS__; } \
+    else if ((lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80>>; __VA_ARGS__; } \
     else if ((lo).H == 256 && (lo).HEADS == 8 && (lo).MEL == 80) { using LN = Launcher<Cfg<256, 8, 80>>; __VA_ARGS__; }     \
     else if ((lo).H == 32 && (lo).HEADS == 2 && (lo).MEL == 80) { using LN = Launcher<Cfg<32, 2, 80>>; __VA_ARGS__; }       \
     else if ((lo).H == 64 && (lo).HEADS == 4 && (lo).MEL == 16) { using LN = Launcher<Cfg<64, 4, 16>>; __VA_ARGS__; }       \
@@ -3058,6 +2841,74 @@ static int launch_cond(const Layout& lo, const float* blob, const int64_t* t, co
   LAUNCH_CHECK("k_cond_mlp");
   hipLaunchKernelGGL(k_cond_ada, dim3(rows, 2 * lo.L, (2 * lo.H + 255) / 256), dim3(256), lo.H * sizeof(float), st, a);
   LAUNCH_CHECK("k_cond_ada");
+  return EDTTS_OK;
+}
+
+// Per-utterance lengths outside [1, T] / [1, S] (edtts_*_len): the kernels clamp them (utt_len); this marks the index-error word.
+// t_min > 1: frame counts below it are flagged too (edtts_sample_inpaint_len: an utterance shorter than the known overlap)
+extern "C" __global__ __launch_bounds__(256) void k_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, int t_min, unsigned* err) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  if ((t_len && (t_len[i] < t_min || t_len[i] > T)) || (s_len && (s_len[i] < 1 || s_len[i] > S))) atomicOr(err, (unsigned)EDTTS_IDX_LEN);
+}
+static int launch_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, float* wsb, hipStream_t st, int t_min = 1) {
+  if (!t_len && !s_len) return EDTTS_OK;
+  hipLaunchKernelGGL(k_len_check, dim3((B + 255) / 256), dim3(256), 0, st, t_len, s_len, B, T, S, t_min, reinterpret_cast<unsigned*>(wsb));
+  LAUNCH_CHECK("k_len_check");
+  return EDTTS_OK;
+}
+
+static int check_shapes(const Layout& lo, int B, int T, int S) {
+  if (B < 1 || T < 1 || S < 1) return fail(EDTTS_ERR_ARG, "B=%d T=%d S=%d must be positive", B, T, S);
+  if (T > lo.MAXPOS) return fail(EDTTS_ERR_ARG, "T=%d exceeds the positional table (%d rows) -- the reference raises here too", T, lo.MAXPOS);
+  if (S > lo.MAXCPOS) return fail(EDTTS_ERR_ARG, "S=%d exceeds the context positional table (%d rows)", S, lo.MAXCPOS);
+  return EDTTS_OK;
+}
+
+// What a sampler call runs on besides its per-step tails
+struct SamplerInputs {
+  const int64_t* t_dev = nullptr;   // conditioning: device timesteps of every step (edtts_sample_ddpm) ...
+  const int64_t* t_host = nullptr;  // ... or host ones, row i = (timesteps[i], step index i)
+  const int64_t* sem_idx = nullptr;
+  const float* sem_features = nullptr;
+  Lens ln;                // per-utterance lengths of the whole batch (token counts in ln.t are checked through ln.s)
+  const float* x_T = nullptr;  // step 0 reads it ...
+  const float* x = nullptr;    // ... every later step the sample the previous one wrote
+};
+// The sub-batched step loop of the samplers, after the entry point's own argument checks: conditioning rows of every step, the
+// context cache per sub-batch, then step-major over the sub-batches.  tail_of(i, off, o) builds the tail of step i for the sub-batch
+// that starts at utterance off (element o = off * T * n_mels of a [B, T, n_mels] tensor).
+template <class TailOf>
+static int run_sampler(const EdttsDims* dims, const Layout& lo, const void* packed, void* workspace, int B, int T, int S, int num_steps,
+                       const SamplerInputs& in, void* stream, TailOf&& tail_of) {
+  hipStream_t st = (hipStream_t)stream;
+  const float* blob = (const float*)packed;
+  float* wsb = (float*)workspace;
+  SubBatches sb;
+  plan_call(lo, B, T, S, num_steps, wsb, &sb);
+  TRY(launch_len_check(in.ln.t_dbl ? nullptr : in.ln.t, in.ln.s, B, T, S, wsb, st));
+  TRY(launch_cond(lo, blob, in.t_dev, nullptr, in.t_host, num_steps, wsb + sb.cond, wsb, st));
+  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  const size_t per_utt = (size_t)T * lo.MEL;
+  ForkJoin fj;
+  TRY(fj.init(sb, st));
+  auto call = [&](int j) { return CallCtx{lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, in.ln.at(sb.off[j]), fj.st[j]}; };
+  EDTTS_DISPATCH(lo, {
+    TRY(set_attrs_once<LN>());
+    for (int j = 0; j < sb.n; ++j) {
+      const size_t off = sb.off[j];
+      TRY(LN::ctx(call(j), (in.sem_features || !in.sem_idx) ? nullptr : in.sem_idx + off * S,
+                  in.sem_features ? in.sem_features + off * S * lo.SD : nullptr));
+    }
+    for (int i = 0; i < num_steps; ++i)
+      for (int j = 0; j < sb.n; ++j) {
+        const size_t o = (size_t)sb.off[j] * per_utt;
+#ifdef EDTTS_WAVELOG
+        g_wavelog_base = sb.off[j] * (sb.ws[j].Tp / 32);
+#endif
+        TRY(LN::forward(call(j), (i == 0 ? in.x_T : in.x) + o, wsb + sb.cond + i * row, 0, tail_of(i, sb.off[j], o)));
+      }
+  });
   return EDTTS_OK;
 }
 
@@ -3121,7 +2972,6 @@ static int transpose_f(hipStream_t st, const float* src, float* dst, int N, int 
   LAUNCH_CHECK("k_transpose");
   return EDTTS_OK;
 }
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // generic layout (make_generic_layout): copies, and the transposes the conditioning kernels read
 static int pack_generic(const Layout& lo, const void* const* slots, float* blob, hipStream_t st) {
@@ -3257,27 +3107,6 @@ int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_sl
   return EDTTS_OK;
 }
 
-// Per-utterance lengths outside [1, T] / [1, S] (edtts_*_len): the kernels clamp them (utt_len); this marks the index-error word.
-// t_min > 1: frame counts below it are flagged too (edtts_sample_inpaint_len: an utterance shorter than the known overlap)
-__global__ __launch_bounds__(256) void k_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, int t_min, unsigned* err) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  if ((t_len && (t_len[i] < t_min || t_len[i] > T)) || (s_len && (s_len[i] < 1 || s_len[i] > S))) atomicOr(err, (unsigned)EDTTS_IDX_LEN);
-}
-static int launch_len_check(const int64_t* t_len, const int64_t* s_len, int B, int T, int S, float* wsb, hipStream_t st, int t_min = 1) {
-  if (!t_len && !s_len) return EDTTS_OK;
-  hipLaunchKernelGGL(k_len_check, dim3((B + 255) / 256), dim3(256), 0, st, t_len, s_len, B, T, S, t_min, reinterpret_cast<unsigned*>(wsb));
-  LAUNCH_CHECK("k_len_check");
-  return EDTTS_OK;
-}
-
-static int check_shapes(const Layout& lo, int B, int T, int S) {
-  if (B < 1 || T < 1 || S < 1) return fail(EDTTS_ERR_ARG, "B=%d T=%d S=%d must be positive", B, T, S);
-  if (T > lo.MAXPOS) return fail(EDTTS_ERR_ARG, "T=%d exceeds the positional table (%d rows) -- the reference raises here too", T, lo.MAXPOS);
-  if (S > lo.MAXCPOS) return fail(EDTTS_ERR_ARG, "S=%d exceeds the context positional table (%d rows)", S, lo.MAXCPOS);
-  return EDTTS_OK;
-}
-
 int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const float* x,
                           const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                           float* eps, void* stream) {
@@ -3301,12 +3130,13 @@ int edtts_decoder_forward_len(const EdttsDims* dims, const void* packed, void* w
   TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
   TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, wsb + ws.cond, wsb, st));
   const int bstride = lo.L * 2 * 2 * lo.H;
-  const Lens ln{t_len, s_len};
+  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
+  StepTail tail;
+  tail.eps = eps;
   EDTTS_DISPATCH(lo, {
-    TRY(LN::set_attrs());
-    TRY(LN::ctx(lo, blob, ws, wsb, B, S, sem_features ? nullptr : sem_idx, sem_features, st, s_len));
-    TRY(LN::forward(lo, blob, ws, wsb, B, T, S, dims->window, x, wsb + ws.cond, bstride, TAIL_EPS, eps, nullptr,
-                             nullptr, nullptr, st, nullptr, nullptr, nullptr, ln));
+    TRY(set_attrs_once<LN>());
+    TRY(LN::ctx(c, sem_features ? nullptr : sem_idx, sem_features));
+    TRY(LN::forward(c, x, wsb + ws.cond, bstride, tail));
   });
   return EDTTS_OK;
 }
@@ -3330,34 +3160,15 @@ int edtts_generate_len(const EdttsDims* dims, const void* packed, void* workspac
     return fail(EDTTS_ERR_ARG, "num_steps=%d outside [1,%d] (step_emb rows; the reference raises IndexError)", num_steps, lo.NSTEP);
   const int T = 2 * S;  // inference.py:31
   TRY(check_shapes(lo, B, T, S));
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  SubBatches sb;
-  plan_call(lo, B, T, S, num_steps, wsb, &sb);
-  TRY(launch_len_check(nullptr, s_len, B, T, S, wsb, st));
-  TRY(launch_cond(lo, blob, nullptr, nullptr, timesteps_host, num_steps, wsb + sb.cond, wsb, st));
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
-  const size_t per_utt = (size_t)T * lo.MEL;
-  const Lens ln{s_len, s_len, true};  // frames = 2 x tokens (inference.py:31)
-  ForkJoin fj;
-  TRY(fj.init(sb, st));
-  EDTTS_DISPATCH(lo, {
-    TRY(LN::set_attrs());
-    for (int j = 0; j < sb.n; ++j)
-      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, sem_idx + (size_t)sb.off[j] * S, nullptr, fj.st[j], ln.at(sb.off[j]).s));
-    for (int i = 0; i < num_steps; ++i)
-      for (int j = 0; j < sb.n; ++j) {
-        const size_t o = (size_t)sb.off[j] * per_utt;
-#ifdef EDTTS_WAVELOG
-        g_wavelog_base = sb.off[j] * (sb.ws[j].Tp / 32);
-#endif
-        const float* xin = ((i == 0) ? x_T : x_work) + o;
-        TRY(LN::forward(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, xin, wsb + sb.cond + i * row, 0, TAIL_DDIM,
-                        nullptr, x_work + o, x0_out + o, coef_host + 4 * i, fj.st[j], nullptr, nullptr, nullptr, ln.at(sb.off[j])));
-      }
+  SamplerInputs in;
+  in.t_host = timesteps_host; in.sem_idx = sem_idx;
+  in.ln = Lens{s_len, s_len, true};  // frames = 2 x tokens (inference.py:31)
+  in.x_T = x_T; in.x = x_work;
+  return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int, size_t o) {
+    StepTail tail;
+    tail.kind = TAIL_DDIM; tail.x_prev = x_work + o; tail.x0 = x0_out + o; tail.coef = coef_host + 4 * i;
+    return tail;
   });
-  return EDTTS_OK;
 }
 
 int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const int64_t* sem_idx,
@@ -3379,45 +3190,28 @@ int edtts_sample_multistep_len(const EdttsDims* dims, const void* packed, void* 
   if (num_steps < 1 || num_steps > lo.NSTEP)
     return fail(EDTTS_ERR_ARG, "num_steps=%d outside [1,%d] (step_emb rows; the reference raises IndexError)", num_steps, lo.NSTEP);
   TRY(check_shapes(lo, B, T, S));
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  SubBatches sb;
-  plan_call(lo, B, T, S, num_steps, wsb, &sb);
-  TRY(launch_cond(lo, blob, nullptr, nullptr, timesteps_host, num_steps, wsb + sb.cond, wsb, st));
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
-  const size_t per = (size_t)B * T * lo.MEL;
-  const size_t per_utt = (size_t)T * lo.MEL;
   for (int i = 0; i < num_steps; ++i) {
     const int mode = (int)coef_host[8 * i];
     if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
   }
-  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
-  const Lens ln{t_len, s_len};
-  ForkJoin fj;
-  TRY(fj.init(sb, st));
-  EDTTS_DISPATCH(lo, {
-    TRY(LN::set_attrs());
-    for (int j = 0; j < sb.n; ++j)
-      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, (sem_features || !sem_idx) ? nullptr : sem_idx + (size_t)sb.off[j] * S,
-                  sem_features ? sem_features + (size_t)sb.off[j] * S * lo.SD : nullptr, fj.st[j], ln.at(sb.off[j]).s));
-    for (int i = 0; i < num_steps; ++i)
-      for (int j = 0; j < sb.n; ++j) {
-        const size_t o = (size_t)sb.off[j] * per_utt;
-        const float* c = coef_host + 8 * i;
-        typename LN::LmsStep ls;
-        ls.k.mode = (int)c[0]; ls.k.p0 = c[1]; ls.k.p1 = c[2]; ls.k.c0 = c[3]; ls.k.c1 = c[4]; ls.k.rinv = c[5]; ls.k.cB = c[6]; ls.k.cC = c[7];
-        // history ring of two slots: step i writes slot i%2; newest previous = slot (i-1)%2, the one before = slot i%2
-        ls.x0_hist = hist + (size_t)(i & 1) * per + o;
-        ls.h_new = hist + (size_t)((i + 1) & 1) * per + o;
-        ls.h_old = hist + (size_t)(i & 1) * per + o;
-        ls.x0_all = x0_all ? x0_all + (size_t)i * per + o : nullptr;
-        TRY(LN::forward(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, (i == 0 ? x_T : x_out) + o,
-                        wsb + sb.cond + i * row, 0, TAIL_LMS, nullptr, x_out + o, nullptr, nullptr, fj.st[j], nullptr, &ls, nullptr,
-                        ln.at(sb.off[j])));
-      }
+  SamplerInputs in;
+  in.t_host = timesteps_host; in.sem_idx = sem_idx; in.sem_features = sem_features;
+  in.ln = Lens{t_len, s_len};
+  in.x_T = x_T; in.x = x_out;
+  const size_t per = (size_t)B * T * lo.MEL;
+  return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int, size_t o) {
+    const float* c = coef_host + 8 * i;
+    StepTail tail;
+    tail.kind = TAIL_LMS; tail.x_prev = x_out + o;
+    LmsStepArgs& ls = tail.lms;
+    ls.k.mode = (int)c[0]; ls.k.p0 = c[1]; ls.k.p1 = c[2]; ls.k.c0 = c[3]; ls.k.c1 = c[4]; ls.k.rinv = c[5]; ls.k.cB = c[6]; ls.k.cC = c[7];
+    // history ring of two slots: step i writes slot i%2; newest previous = slot (i-1)%2, the one before = slot i%2
+    ls.x0_hist = hist + (size_t)(i & 1) * per + o;
+    ls.h_new = hist + (size_t)((i + 1) & 1) * per + o;
+    ls.h_old = hist + (size_t)(i & 1) * per + o;
+    ls.x0_all = x0_all ? x0_all + (size_t)i * per + o : nullptr;
+    return tail;
   });
-  return EDTTS_OK;
 }
 
 int edtts_sample_ddpm(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
@@ -3438,34 +3232,18 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
   if (batch_offset < 0) return fail(EDTTS_ERR_ARG, "batch_offset=%lld < 0", (long long)batch_offset);
   const int T = 2 * S;
   TRY(check_shapes(lo, B, T, S));
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  SubBatches sb;
-  plan_call(lo, B, T, S, num_steps, wsb, &sb);
-  TRY(launch_cond(lo, blob, t_all, nullptr, nullptr, num_steps, wsb + sb.cond, wsb, st));  // step_idx = None (train.py:155 usage)
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  SamplerInputs in;
+  in.t_dev = t_all; in.sem_idx = sem_idx;  // step_idx = None (train.py:155 usage)
+  in.ln = Lens{s_len, s_len, true};  // frames = 2 x tokens
+  in.x_T = x_T; in.x = x_out;
   const size_t per_step = (size_t)B * T * lo.MEL;
-  const size_t per_utt = (size_t)T * lo.MEL;
-  TRY(launch_len_check(nullptr, s_len, B, T, S, wsb, st));
-  const Lens ln{s_len, s_len, true};  // frames = 2 x tokens
-  ForkJoin fj;
-  TRY(fj.init(sb, st));
-  EDTTS_DISPATCH(lo, {
-    TRY(LN::set_attrs());
-    for (int j = 0; j < sb.n; ++j)
-      TRY(LN::ctx(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], S, sem_idx + (size_t)sb.off[j] * S, nullptr, fj.st[j], ln.at(sb.off[j]).s));
-    for (int i = 0; i < num_steps; ++i)
-      for (int j = 0; j < sb.n; ++j) {
-        const size_t o = (size_t)sb.off[j] * per_utt;
-        typename LN::DdpmStep ds{noise_all ? noise_all + (size_t)i * per_step + o : nullptr, (unsigned long long)seed,
-                                 ((unsigned long long)batch_offset + (unsigned long long)sb.off[j]) * T * lo.MEL, kStreamDdpmStep + (unsigned)i};
-        TRY(LN::forward(lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, (i == 0 ? x_T : x_out) + o,
-                        wsb + sb.cond + i * row, 0, TAIL_DDPM, nullptr, x_out + o, nullptr, coef_host + 3 * i, fj.st[j], &ds, nullptr,
-                        nullptr, ln.at(sb.off[j])));
-      }
+  return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int off, size_t o) {
+    StepTail tail;
+    tail.kind = TAIL_DDPM; tail.x_prev = x_out + o; tail.coef = coef_host + 3 * i;
+    tail.ddpm = DdpmStepArgs{noise_all ? noise_all + (size_t)i * per_step + o : nullptr, (unsigned long long)seed,
+                             ((unsigned long long)batch_offset + (unsigned long long)off) * T * lo.MEL, kStreamDdpmStep + (unsigned)i};
+    return tail;
   });
-  return EDTTS_OK;
 }
 
 // x[b][f < overlap][:] = c_known * known[b][f][:] + c_noise * noise   (noise: injected [B, overlap, MEL] or Philox keyed by
@@ -3549,7 +3327,9 @@ int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* wo
   TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st, known_mel ? overlap_len : 1));
   TRY(launch_cond(lo, blob, t_all, step_all, nullptr, num_steps, wsb + ws.cond, wsb, st));
   const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
-  const Lens ln{t_len, s_len};
+  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
+  CallCtx cu = c;  // the unconditional pass: its own context cache and activations (workspace_uncond)
+  cu.wsb = wsu;
   const bool inject_vec = ((size_t)overlap_len * lo.MEL) % 4 == 0 && ((size_t)T * lo.MEL) % 4 == 0;
   auto inject = [&](float ck, float cn, int step) {
     const size_t n4 = (size_t)B * overlap_len * lo.MEL / (inject_vec ? 4 : 1);
@@ -3560,24 +3340,26 @@ int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* wo
                        (unsigned long long)seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(seeds), t_len);
   };
   EDTTS_DISPATCH(lo, {
-    TRY(LN::set_attrs());
-    TRY(LN::ctx(lo, blob, ws, wsb, B, S, nullptr, sem_features, st, s_len));
-    if (guided) TRY(LN::ctx(lo, blob, ws, wsu, B, S, nullptr, zero_features, st, s_len));  // (the solo call's zero context has S_b rows)
+    TRY(set_attrs_once<LN>());
+    TRY(LN::ctx(c, nullptr, sem_features));
+    if (guided) TRY(LN::ctx(cu, nullptr, zero_features));  // (the solo call's zero context has S_b rows)
     for (int i = 0; i < num_steps; ++i) {
-      const float* c = coef_host + 4 * i;  // {sqrt_ab[t], sqrt_1mab[t], sqrt(ab[t_next]), sqrt(1 - ab[t_next])}
+      const float* k = coef_host + 4 * i;  // {sqrt_ab[t], sqrt_1mab[t], sqrt(ab[t_next]), sqrt(1 - ab[t_next])}
       if (known_mel) {
-        inject(c[0], c[1], i);  // q_sample(known_mel, t) into the first overlap_len frames (inference_pipeline.py:117-123)
+        inject(k[0], k[1], i);  // q_sample(known_mel, t) into the first overlap_len frames (inference_pipeline.py:117-123)
         LAUNCH_CHECK("k_inpaint_inject");
       }
-      VpredStepArgs vp{{c[0], c[1], c[2], c[3], cfg_scale}, nullptr};
+      StepTail tail;
+      tail.kind = TAIL_VPRED; tail.x_prev = x;
+      tail.vp = VpredStepArgs{{k[0], k[1], k[2], k[3], cfg_scale}, nullptr};
       if (guided) {
         // the unconditional pass shares nothing with the conditional one but x and the conditioning rows
-        TRY(LN::forward(lo, blob, ws, wsu, B, T, S, dims->window, x, wsb + ws.cond + i * row, 0, TAIL_EPS, v_uncond, nullptr, nullptr,
-                        nullptr, st, nullptr, nullptr, nullptr, ln));
-        vp.v_uncond = v_uncond;
+        StepTail eps_tail;
+        eps_tail.eps = v_uncond;
+        TRY(LN::forward(cu, x, wsb + ws.cond + i * row, 0, eps_tail));
+        tail.vp.v_uncond = v_uncond;
       }
-      TRY(LN::forward(lo, blob, ws, wsb, B, T, S, dims->window, x, wsb + ws.cond + i * row, 0, TAIL_VPRED, nullptr, x, nullptr, nullptr,
-                      st, nullptr, nullptr, &vp, ln));
+      TRY(LN::forward(c, x, wsb + ws.cond + i * row, 0, tail));
     }
     if (known_mel) {
       inject(1.0f, 0.0f, 0);  // final force (inference_pipeline.py:135-136)
@@ -3854,7 +3636,6 @@ int edtts_profile_enable(int max_records) {
     HIP_TRY(hipEventCreate(&b));
     g_prof.start.push_back(a); g_prof.stop.push_back(b);
   }
-  g_prof.kinds.assign(max_records, 0);
   g_prof.on.store(max_records > 0);
   return EDTTS_OK;
 }
@@ -3868,8 +3649,8 @@ int edtts_profile_collect(double* ms_by_kind, int* launches_by_kind) {
     HIP_TRY(hipEventSynchronize(g_prof.stop[i]));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, g_prof.start[i], g_prof.stop[i]));
-    ms_by_kind[g_prof.kinds[i] & 1] += ms;
-    launches_by_kind[g_prof.kinds[i] & 1] += 1;
+    ms_by_kind[0] += ms;  // (slot 1, the FFN half of a two-launch layer, stays 0: every layer is one launch)
+    launches_by_kind[0] += 1;
   }
   g_prof.used = 0;
   return EDTTS_OK;

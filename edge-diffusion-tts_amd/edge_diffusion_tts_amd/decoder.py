@@ -325,12 +325,7 @@ class EdgeDiffusionDecoder(nn.Module):
         s_len = native.lengths(sem_lengths, B, S, x_t.device, "sem_lengths")
         packed = self._ensure_packed()
         ws = self.workspace(B, T, S, B, x_t.device)
-        if t_len is not None or s_len is not None:
-            return native.decoder_forward_len(self.dims(), packed, ws, x_t.contiguous(), t.contiguous(),
-                                              None if step_idx is None else step_idx.contiguous(),
-                                              None if sem_features is not None or sem_idx is None else sem_idx.contiguous(),
-                                              None if sem_features is None else sem_features.contiguous(), S, t_len, s_len)
         return native.decoder_forward(self.dims(), packed, ws, x_t.contiguous(), t.contiguous(),
                                       None if step_idx is None else step_idx.contiguous(),
                                       None if sem_features is not None or sem_idx is None else sem_idx.contiguous(),
-                                      None if sem_features is None else sem_features.contiguous(), S)
+                                      None if sem_features is None else sem_features.contiguous(), S, t_len, s_len)

@@ -66,9 +66,7 @@ class EdgeInference:
         s_len = native.lengths(sem_lengths, B, S, dev, "sem_lengths")
         packed = self.decoder._ensure_packed()
         ws = self.decoder.workspace(B, T_out, S, len(timesteps), dev)
-        if s_len is not None:
-            return native.generate_len(self.decoder.dims(), packed, ws, sem_idx.contiguous(), s_len, x_T, timesteps, coefs)
-        return native.generate(self.decoder.dims(), packed, ws, sem_idx.contiguous(), x_T, timesteps, coefs)
+        return native.generate(self.decoder.dims(), packed, ws, sem_idx.contiguous(), x_T, timesteps, coefs, s_len)
 
     @torch.no_grad()
     def sample_ddpm(self, sem_idx: torch.Tensor, num_steps: Optional[int] = None, temperature: float = 1.0, *,
@@ -110,9 +108,7 @@ class EdgeInference:
         s_len = native.lengths(sem_lengths, B, S, dev, "sem_lengths")
         packed = self.decoder._ensure_packed()
         ws = self.decoder.workspace(B, T_out, S, n, dev)
-        if s_len is not None:
-            return native.sample_ddpm_len(self.decoder.dims(), packed, ws, sem_idx, s_len, x_T, t_all, coefs, noise, seed, batch_offset)
-        return native.sample_ddpm(self.decoder.dims(), packed, ws, sem_idx, x_T, t_all, coefs, noise, seed, batch_offset)
+        return native.sample_ddpm(self.decoder.dims(), packed, ws, sem_idx, x_T, t_all, coefs, noise, seed, batch_offset, s_len)
 
     # alias some callers may expect from the task description; not part of the reference API
     generate = generate_mel

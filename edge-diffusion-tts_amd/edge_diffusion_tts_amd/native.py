@@ -209,19 +209,6 @@ def pack_weights(dims: EdttsDims, tensors: Sequence[torch.Tensor], packed: torch
     lib().edtts_pack_weights(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
 
 
-def decoder_forward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
-                    step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor],
-                    S: int) -> torch.Tensor:
-    B, T, M = x.shape
-    eps = torch.empty_like(x)
-    lib().edtts_decoder_forward(
-        C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(x, torch.float32, "x_t"),
-        _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-        _dev_ptr(sem_features, torch.float32, "sem_features"), eps.data_ptr(), _stream(x.device))
-    check_indices(workspace)
-    return eps
-
-
 def lengths(n: Optional[torch.Tensor], B: int, hi: int, device, name: str) -> Optional[torch.Tensor]:
     """Per-utterance lengths for the *_len entry points: None, or an int64 [B] tensor.  A CPU tensor is range-checked here
     (ValueError outside [1, hi]) and copied to `device` -- not while the stream is capturing (a host-to-device copy cannot be
@@ -247,87 +234,69 @@ def lengths(n: Optional[torch.Tensor], B: int, hi: int, device, name: str) -> Op
     return n.to(device)
 
 
-def decoder_forward_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
-                        step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor],
-                        S: int, t_len: Optional[torch.Tensor], s_len: Optional[torch.Tensor]) -> torch.Tensor:
-    """decoder_forward with per-utterance frame / token counts (device int64 [B] or None; see lengths())."""
+def decoder_forward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
+                    step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor],
+                    S: int, t_len: Optional[torch.Tensor] = None, s_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-utterance frame / token counts t_len / s_len: device int64 [B] or None (see lengths()).  Without either the plain
+    export runs, with them the _len one."""
     B, T, M = x.shape
     eps = torch.empty_like(x)
-    lib().edtts_decoder_forward_len(
-        C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(x, torch.float32, "x_t"),
-        _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-        _dev_ptr(sem_features, torch.float32, "sem_features"), _dev_ptr(t_len, torch.int64, "x_lengths"),
-        _dev_ptr(s_len, torch.int64, "sem_lengths"), eps.data_ptr(), _stream(x.device))
+    head = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(x, torch.float32, "x_t"),
+            _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+            _dev_ptr(sem_features, torch.float32, "sem_features"))
+    if t_len is None and s_len is None:
+        lib().edtts_decoder_forward(*head, eps.data_ptr(), _stream(x.device))
+    else:
+        lib().edtts_decoder_forward_len(*head, _dev_ptr(t_len, torch.int64, "x_lengths"), _dev_ptr(s_len, torch.int64, "sem_lengths"),
+                                        eps.data_ptr(), _stream(x.device))
     check_indices(workspace)
     return eps
 
 
 def generate(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,
-             timesteps: Sequence[int], coefs: Sequence[Tuple[float, float, float, float]]) -> torch.Tensor:
-    B, S = sem_idx.shape
-    n = len(timesteps)
-    ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
-    flat = [float(v) for c in coefs for v in c]
-    cf = (C.c_float * (4 * n))(*flat)
-    x_work = torch.empty_like(x_T)
-    x0 = torch.empty_like(x_T)
-    lib().edtts_generate(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                         _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf, x_work.data_ptr(), x0.data_ptr(), _stream(x_T.device))
-    check_indices(workspace)
-    return x0
-
-
-def generate_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, s_len: Optional[torch.Tensor],
-                 x_T: torch.Tensor, timesteps: Sequence[int], coefs: Sequence[Tuple[float, float, float, float]]) -> torch.Tensor:
-    """generate with per-utterance token counts s_len (device int64 [B] or None); utterance b has 2 * s_len[b] frames."""
+             timesteps: Sequence[int], coefs: Sequence[Tuple[float, float, float, float]],
+             s_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """s_len: per-utterance token counts (device int64 [B] or None: the plain export); utterance b has 2 * s_len[b] frames."""
     B, S = sem_idx.shape
     n = len(timesteps)
     ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
     cf = (C.c_float * (4 * n))(*[float(v) for c in coefs for v in c])
     x_work = torch.empty_like(x_T)
     x0 = torch.empty_like(x_T)
-    lib().edtts_generate_len(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                             _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf,
-                             x_work.data_ptr(), x0.data_ptr(), _stream(x_T.device))
+    head = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"))
+    tail = (_dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf, x_work.data_ptr(), x0.data_ptr(), _stream(x_T.device))
+    if s_len is None:
+        lib().edtts_generate(*head, *tail)
+    else:
+        lib().edtts_generate_len(*head, _dev_ptr(s_len, torch.int64, "sem_lengths"), *tail)
     check_indices(workspace)
     return x0
 
 
-def sample_ddpm_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, s_len: Optional[torch.Tensor],
-                    x_T: torch.Tensor, t_all: torch.Tensor, coefs: Sequence[Tuple[float, float, float]], noise_all: Optional[torch.Tensor],
-                    seed: int, batch_offset: int = 0) -> torch.Tensor:
-    """sample_ddpm with per-utterance token counts s_len (device int64 [B] or None); utterance b has 2 * s_len[b] frames."""
+def sample_ddpm(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,
+                t_all: torch.Tensor, coefs: Sequence[Tuple[float, float, float]], noise_all: Optional[torch.Tensor], seed: int,
+                batch_offset: int = 0, s_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """s_len: per-utterance token counts (device int64 [B] or None: the plain export); utterance b has 2 * s_len[b] frames."""
     B, S = sem_idx.shape
     n = t_all.numel()
     cf = (C.c_float * (3 * n))(*[float(v) for c in coefs for v in c])
     out = torch.empty_like(x_T)
-    lib().edtts_sample_ddpm_len(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                                _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(x_T, torch.float32, "x_T"), n,
-                                _dev_ptr(t_all, torch.int64, "t_all"), cf, _dev_ptr(noise_all, torch.float32, "noise"),
-                                C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_int64(int(batch_offset)), out.data_ptr(), _stream(x_T.device))
-    check_indices(workspace)
-    return out
-
-
-def sample_ddpm(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,
-                t_all: torch.Tensor, coefs: Sequence[Tuple[float, float, float]], noise_all: Optional[torch.Tensor], seed: int,
-                batch_offset: int = 0) -> torch.Tensor:
-    B, S = sem_idx.shape
-    n = t_all.numel()
-    flat = [float(v) for c in coefs for v in c]
-    cf = (C.c_float * (3 * n))(*flat)
-    out = torch.empty_like(x_T)
-    lib().edtts_sample_ddpm(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                            _dev_ptr(x_T, torch.float32, "x_T"), n, _dev_ptr(t_all, torch.int64, "t_all"), cf,
-                            _dev_ptr(noise_all, torch.float32, "noise"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_int64(int(batch_offset)),
-                            out.data_ptr(), _stream(x_T.device))
+    head = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"))
+    tail = (_dev_ptr(x_T, torch.float32, "x_T"), n, _dev_ptr(t_all, torch.int64, "t_all"), cf, _dev_ptr(noise_all, torch.float32, "noise"),
+            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_int64(int(batch_offset)), out.data_ptr(), _stream(x_T.device))
+    if s_len is None:
+        lib().edtts_sample_ddpm(*head, *tail)
+    else:
+        lib().edtts_sample_ddpm_len(*head, _dev_ptr(s_len, torch.int64, "sem_lengths"), *tail)
     check_indices(workspace)
     return out
 
 
 def sample_multistep(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: Optional[torch.Tensor],
                      sem_features: Optional[torch.Tensor], S: int, x_T: torch.Tensor, timesteps: Sequence[int],
-                     coefs: Sequence[Sequence[float]], want_intermediates: bool):
+                     coefs: Sequence[Sequence[float]], want_intermediates: bool, t_len: Optional[torch.Tensor] = None,
+                     s_len: Optional[torch.Tensor] = None):
+    """t_len / s_len: per-utterance frame / token counts (device int64 [B] or None; without either the plain export runs)."""
     B, T, M = x_T.shape
     n = len(timesteps)
     ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
@@ -335,30 +304,15 @@ def sample_multistep(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
     hist = torch.empty((2, B, T, M), dtype=torch.float32, device=x_T.device)
     x0_all = torch.empty((n, B, T, M), dtype=torch.float32, device=x_T.device) if want_intermediates else None
     out = torch.empty_like(x_T)
-    lib().edtts_sample_multistep(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                                 _dev_ptr(sem_features, torch.float32, "sem_features"), _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf,
-                                 hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), out.data_ptr(), _stream(x_T.device))
-    check_indices(workspace)
-    return out, x0_all
-
-
-def sample_multistep_len(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: Optional[torch.Tensor],
-                         sem_features: Optional[torch.Tensor], S: int, x_T: torch.Tensor, timesteps: Sequence[int],
-                         coefs: Sequence[Sequence[float]], want_intermediates: bool, t_len: Optional[torch.Tensor],
-                         s_len: Optional[torch.Tensor]):
-    """sample_multistep with per-utterance frame / token counts (device int64 [B] or None)."""
-    B, T, M = x_T.shape
-    n = len(timesteps)
-    ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
-    cf = (C.c_float * (8 * n))(*[float(v) for c in coefs for v in c])
-    hist = torch.empty((2, B, T, M), dtype=torch.float32, device=x_T.device)
-    x0_all = torch.empty((n, B, T, M), dtype=torch.float32, device=x_T.device) if want_intermediates else None
-    out = torch.empty_like(x_T)
-    lib().edtts_sample_multistep_len(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S,
-                                     _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"),
-                                     _dev_ptr(t_len, torch.int64, "x_lengths"), _dev_ptr(s_len, torch.int64, "sem_lengths"),
-                                     _dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf, hist.data_ptr(),
-                                     None if x0_all is None else x0_all.data_ptr(), out.data_ptr(), _stream(x_T.device))
+    head = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, T, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+            _dev_ptr(sem_features, torch.float32, "sem_features"))
+    tail = (_dev_ptr(x_T, torch.float32, "x_T"), n, ts, cf, hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(),
+            out.data_ptr(), _stream(x_T.device))
+    if t_len is None and s_len is None:
+        lib().edtts_sample_multistep(*head, *tail)
+    else:
+        lib().edtts_sample_multistep_len(*head, _dev_ptr(t_len, torch.int64, "x_lengths"), _dev_ptr(s_len, torch.int64, "sem_lengths"),
+                                         *tail)
     check_indices(workspace)
     return out, x0_all
 

@@ -257,16 +257,9 @@ class DPMSolverPP:
         s_len = native.lengths(sem_lengths, B, S, x_T.device, "sem_lengths")
         packed = model._ensure_packed()
         ws = model.workspace(B, T, S, len(ts), x_T.device)
-        if t_len is not None or s_len is not None:
-            x, x0_all = native.sample_multistep_len(model.dims(), packed, ws, None if sem_features is not None else sem_idx.contiguous(),
-                                                    None if sem_features is None else sem_features.contiguous(), S,
-                                                    x_T.to(torch.float32).contiguous(), ts, coefs, return_intermediates, t_len, s_len)
-            if return_intermediates:
-                return x, list(x0_all.unbind(0))
-            return x
         x, x0_all = native.sample_multistep(model.dims(), packed, ws, None if sem_features is not None else sem_idx.contiguous(),
                                             None if sem_features is None else sem_features.contiguous(), S,
-                                            x_T.to(torch.float32).contiguous(), ts, coefs, return_intermediates)
+                                            x_T.to(torch.float32).contiguous(), ts, coefs, return_intermediates, t_len, s_len)
         if return_intermediates:
             return x, list(x0_all.unbind(0))
         return x

@@ -328,8 +328,8 @@ int edtts_griffin_lim(const float* spec, int B, int T, int n_fft, int hop, const
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------------------------------
  * edtts_profile_enable(n > 0): from now on every transformer-layer kernel launch is bracketed by a pair of
  * hipEvents recorded on the stream it is launched on, up to n launches; n = 0 disables and releases the events.
- * A decoder layer is either one fused launch (kind 0) or two: the attention half (kind 0) and the FFN + tail half
- * (kind 1).  edtts_profile_collect synchronises on the recorded events, returns the summed device time (ms) and
+ * A decoder layer is one fused launch (kind 0); kind 1 (the FFN + tail half of a two-launch layer, no longer built)
+ * always reports 0.  edtts_profile_collect synchronises on the recorded events, returns the summed device time (ms) and
  * the launch count per kind (arrays of 2), and resets the counter.  Not graph-capturable while on.  Any thread may switch it;
  * while it is on, the bracketed launches of all threads take one lock in turn. */
 int edtts_profile_enable(int max_records);

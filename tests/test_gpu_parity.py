@@ -1046,50 +1046,6 @@ def test_bf16_full_size_config3_properties():
     assert rms(e16, ref) < BF16_RMS_TOL and max_abs(e16, ref) < BF16_MAX_TOL
 
 
-def test_bf16_wide_instance(golden, tmp_path):
-    """SCRATCH test since round 4: the 64-frame instance was measured at the default instance's speed and left the product library
-    (-DEDTTS_EXPERIMENTS -DEDTTS16_WIDE_BUILD=1 builds it); runs only when EDTTS_TEST_WIDE_LIB names such a build.
-    The 64-frames-per-wave bf16 instance (EDTTS16_WIDE=1; the library reads the switch once per process, hence the child): the
-    config-3 shape against the reference's fp32 golden output and against the default instance on the same input; a 4-step
-    sampler run whose utterances straddle blocks: run twice bitwise equal, probed utterances == the same utterances alone
-    (bitwise), and bf16-level agreement with the default instance."""
-    import os
-    import subprocess
-    import sys
-    wide_lib = os.environ.get("EDTTS_TEST_WIDE_LIB")
-    if not wide_lib:
-        pytest.skip("the 64-frame bf16 instance is an experiment build (set EDTTS_TEST_WIDE_LIB to a -DEDTTS16_WIDE_BUILD=1 library)")
-    out = str(tmp_path / "wide.npz")
-    env = dict(os.environ, EDTTS16_WIDE="1", EDTTS_LIB=wide_lib)
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "bf16_wide_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    w = {k: torch.from_numpy(v) for k, v in np.load(out).items()}
-    g = golden("forward_cfg3")
-    cfg, dec = _cfg3_bf16()
-    e_def = dec(cu(g["x_t"]), cu(g["t"]), cu(g["sem_idx"]), cu(g["step_idx"])).cpu()
-    assert rms(w["eps"], g["eps"]) < BF16_RMS_TOL and max_abs(w["eps"], g["eps"]) < BF16_MAX_TOL
-    assert rms(w["eps"], g["eps"]) <= rms(e_def, g["eps"]) * 1.05
-    if os.environ.get("EDTTS16_WIDE") != "1":  # (unless this process runs the 64-frame instance itself)
-        assert not torch.equal(w["eps"], e_def), "the child did not run another instance" 
-    assert torch.equal(w["big"], w["again"]) and torch.equal(w["alone"], w["big"][[0, 11, 23]])
-    for T2, S2, win, e_rms, e_max, finite in w["geo"].tolist():  # ragged geometries against the CPU oracle (see the child)
-        print(f"wide instance, T={int(T2)} S={int(S2)} window={int(win)}: rms {e_rms:.2e} max {e_max:.2e}")
-        assert finite == 1.0 and e_rms < BF16_RMS_TOL and e_max < BF16_MAX_TOL, (T2, S2, win, e_rms, e_max)
-    infer = EdgeInference(cfg, DiffusionSchedule(cfg.diff_steps).to(DEV), torch.nn.Identity(), dec)
-    gen = torch.Generator().manual_seed(22)
-    sem = torch.randint(0, 512, (24, 384), generator=gen).to(DEV)
-    x = torch.randn(24, 768, 80, generator=gen).to(DEV)
-    ref = infer.generate_mel(sem, 4, x_T=x).cpu()
-    d = (w["big"] - ref).abs()
-    print(f"wide vs default instance, 4-step sampler: rms {rms(w['big'], ref):.2e} median {float(d.median()):.2e} max {float(d.max()):.2e}")
-    # (two bf16 runs differ like either differs from fp32: a heavy tail from the t=999 amplification, SURVEY.md F5.  The bar for the
-    # median is what the reference's own autocast(bf16) run differs from its fp32 run at this decoder shape, doubled for two bf16 runs)
-    gs = golden("bf16_sampler_cfg3")
-    bar = 2.0 * float((gs["out_autocast"].double() - gs["out_f32"].double()).abs().median())
-    assert bool(torch.isfinite(w["big"]).all()) and float(w["big"].abs().max()) <= 3.0 and float(d.median()) < bar, (float(d.median()), bar)
-
-
 def test_bf16_no_cross_block_hazard_when_utterances_straddle_block_rounds():
     """The bf16 twin of test_no_cross_block_hazard...: T = 768 -> 6 blocks per utterance, B = 64 -> 384 blocks; blocks of one launch
     run at different times and a block's QKV tail writes the NEXT layer's K / V^T images while later neighbours still read this
