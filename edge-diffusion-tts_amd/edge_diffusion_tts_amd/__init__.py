@@ -17,10 +17,12 @@ from .longform import InpaintSampler
 from .melpost import GriffinLim, InverseMelScale, MelVocoder, denormalize_mel, normalize_mel
 from .encoder import FSQ, FSQEncoder, SemanticEncoder, VectorQuantizer
 from .hubert import NativeHubert
+from .audio import MelSpectrogram, Resample, chunk_stats_from_audio, resample
 
 __all__ = [
     "CFG", "TrainPhase", "get_device", "set_seed", "DiffusionSchedule", "DPMSolverPP", "EdgeDiffusionDecoder", "EdgeInference",
     "DepthwiseSeparableConv", "synth_state_dict", "InpaintSampler",
     "GriffinLim", "InverseMelScale", "MelVocoder", "denormalize_mel", "normalize_mel",
     "SemanticEncoder", "VectorQuantizer", "FSQ", "FSQEncoder", "NativeHubert",
+    "MelSpectrogram", "Resample", "resample", "chunk_stats_from_audio",
 ]

@@ -170,6 +170,13 @@ class InpaintSampler:
         n_chunks = max(1, -(-(total_samples - overlap_samples) // hop_samples))  # int(np.ceil(...)), :225
         return n_chunks, chunk_samples, hop_samples
 
+    @staticmethod
+    def chunk_stats_from_audio(wavs, chunk_samples: int, overlap_samples: int, mel):
+        """Per utterance the per-chunk (mean, std) pairs that generate_long_batch(..., chunk_stats=...) takes, from the utterances'
+        audio (inference_pipeline.py:354-355) -- audio.chunk_stats_from_audio: one launch for all chunks of all utterances."""
+        from .audio import chunk_stats_from_audio
+        return chunk_stats_from_audio(wavs, chunk_samples, overlap_samples, mel)
+
     @torch.no_grad()
     def generate_long(self, sem_features: torch.Tensor, total_frames: int, chunk_frames: int, overlap_frames: int,
                       chunk_stats, *, strength: float = 0.999, steps: int = 10, cfg_scale: float = 1.0, seed: int = 0,

@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "edtts_sample_inpaint_len", "edtts_randn_rows",
     "edtts_sem_packed_bytes", "edtts_sem_num_codes", "edtts_sem_pack", "edtts_sem_encode", "edtts_sem_decode", "edtts_sem_stats",
     "edtts_hubert_frames", "edtts_hubert_packed_bytes", "edtts_hubert_pack", "edtts_hubert_workspace_bytes", "edtts_hubert_forward",
+    "edtts_melspec", "edtts_mel_segment_stats", "edtts_logmel_stats", "edtts_resample",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -140,6 +141,10 @@ def lib() -> C.CDLL:
     L.edtts_hubert_pack.argtypes = [hdp, C.POINTER(vp), i32, vp, vp]
     L.edtts_hubert_workspace_bytes.argtypes = [hdp, i32, i32, C.POINTER(sz)]
     L.edtts_hubert_forward.argtypes = [hdp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.edtts_melspec.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.edtts_mel_segment_stats.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.edtts_logmel_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+    L.edtts_resample.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32

@@ -449,6 +449,39 @@ int edtts_hubert_workspace_bytes(const EdttsHubertDims* dims, int B, int T_audio
 int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths,
                          float* out, void* workspace, void* stream);
 
+/* ---- audio front end  (the torchaudio ops the reference calls at every entry point: generate_sample.py:75-116,
+ * data/collate.py:34-60, inference_pipeline.py:206-207, 354-355) -------------------------------------------------------------------
+ * edtts_melspec: torchaudio.transforms.MelSpectrogram(n_fft = win_length = 1024, hop, center=True, pad_mode="reflect", periodic Hann
+ * window, onesided, norm=None, mel_scale="htk", power 2 or 1) of wav [B, L] -> mode EDTTS_MEL_POWER: the mel [B, n_mels, T] (torch
+ * layout); EDTTS_MEL_LOG: log(max(mel, 1e-5)) [B, T, n_mels] (frame-major, what collate.py:58-60 and normalize_mel consume).
+ * T = L // hop + 1.  window [1024]; twiddle [512][2] = exp(-2 pi i q / 1024) (the Griffin-Lim table); fb_desc int32 [n_mels][3] =
+ * (first bin, bin count, offset into fb_weights) of each filter's non-zero range of melscale_fbanks(513, ...), fb_weights its values.
+ * lengths int64 [B] (samples) or NULL; values are clamped into [n_fft / 2 + 1, L]; row b is bitwise the call on wav[b, :lengths[b]]
+ * alone (reflect padding at its own end, frames past lengths[b] // hop + 1 written as 0, samples past lengths[b] never read).
+ * edtts_mel_segment_stats: per segment i = segments[i] = (row, start, end) (int64 [n_seg][3]) the mean and unbiased std (clamped at
+ * 1e-5, NaN for a one-frame segment as torch.std) over the frames of the log-mel of wav[row, start : min(end, len_row)] ALONE (its own
+ * reflect padding, (e - s) // hop + 1 frames) -> mean / stdv [n_seg, n_mels] (normalize_mel, utils/audio.py:10-14; the per-chunk
+ * statistics of inference_pipeline.py:349-355).  Nothing else is written.  A segment of fewer than n_fft / 2 + 1 samples gives NaN.
+ * edtts_logmel_stats: the same statistics of segment (b, 0, len_b) of every row, read from the log-mel [B, T, n_mels] that
+ * edtts_melspec(EDTTS_MEL_LOG) wrote for the same wav, L, lengths and hop: bitwise what edtts_mel_segment_stats gives for that segment.
+ * edtts_resample: torchaudio.functional.resample(resampling_method="sinc_interp_hann") with orig / new already divided by their gcd:
+ * y[b][m new + p] = sum_j table[p][j] xpad[m orig + j], xpad = width zeros, x[b, :len_b], zeros; taps = 2 width + orig.  table is
+ * laid out [ceil(taps / 4)][round_up(new, 16)][4] (element (p, j) at ((j / 4) Np + p) 4 + j % 4), zero outside p < new, j < taps.
+ * y [B, L_out], L_out = ceil(new L / orig); lengths int64 [B] or NULL, clamped into [1, L]: row b's outputs past ceil(new len_b /
+ * orig) are 0 and it is bitwise the call on x[b, :len_b] alone.  Limit: 32 orig + taps <= 16384 (EDTTS_ERR_UNSUPPORTED).
+ * All four: no allocation, no host synchronisation (graph-capturable); every output one fixed-order chain, independent of B.
+ * Compiled for n_fft = 1024, n_mels <= 128.  PARITY UNPINNED: torchaudio is not available offline; the tests restate its algorithm. */
+enum { EDTTS_MEL_POWER = 0, EDTTS_MEL_LOG = 1 };
+int edtts_melspec(const float* wav, int B, int L, const int64_t* lengths, int n_fft, int hop, const float* window, const float* twiddle,
+                  const int32_t* fb_desc, const float* fb_weights, int n_mels, int power, int mode, float* out, void* stream);
+int edtts_mel_segment_stats(const float* wav, int B, int L, const int64_t* lengths, const int64_t* segments, int n_seg, int n_fft, int hop,
+                            const float* window, const float* twiddle, const int32_t* fb_desc, const float* fb_weights, int n_mels,
+                            float* mean, float* stdv, void* stream);
+int edtts_logmel_stats(const float* logmel, int B, int T, int n_mels, int L, const int64_t* lengths, int hop, float* mean, float* stdv,
+                       void* stream);
+int edtts_resample(const float* x, int B, int L, const int64_t* lengths, int orig, int new_freq, int width, int taps, const float* table,
+                   int64_t L_out, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
