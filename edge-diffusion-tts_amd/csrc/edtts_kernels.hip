@@ -2759,6 +2759,7 @@ struct Launcher16 {
 #include "edtts_generic.h"
 #include "edtts_semantic.h"
 #include "edtts_hubert.h"
+#include "edtts_hubert16.h"
 #include "edtts_audio.h"
 
 // compiled decoder shapes: (hidden, heads, n_mels).  EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, body) runs `body` with LN = the fused

@@ -12,6 +12,11 @@ the layers past ``num_layers`` are ignored.
 ``lengths`` (int64 [B] sample counts) makes row b equal to the call on ``wav[b:b+1, :lengths[b]]`` alone, bitwise: per-utterance
 GroupNorm statistics, positional-conv padding and attention keys -- which transformers' padded batch cannot give (hubert-base's
 GroupNorm normalises over the whole padded time axis).
+
+``compute_dtype="bf16"`` (default ``"fp32"``) runs every contraction after conv0 -- the conv stack, the feature projection, the
+positional conv, QKV, the attention products, out_proj, the FFN -- on bf16 MFMAs with fp32 accumulators (csrc/edtts_hubert16.h);
+conv0, the GroupNorm, the residual stream, every LayerNorm, GELU, the softmax and the output stay fp32.  The parameters stay fp32
+``nn.Parameter``s under transformers' keys: only the packed blob and the workspace differ.  Every invariance above holds bitwise.
 """
 from __future__ import annotations
 
@@ -53,8 +58,12 @@ class NativeHubert(nn.Module):
 
     WORKSPACE_CACHE = 8
 
-    def __init__(self, config, num_layers: int):
+    def __init__(self, config, num_layers: int, compute_dtype: str = "fp32"):
         super().__init__()
+        if compute_dtype not in native.HUBERT_DTYPES:
+            raise ValueError(f"NativeHubert: compute_dtype={compute_dtype!r}: expected one of {sorted(native.HUBERT_DTYPES)}")
+        self.compute_dtype = compute_dtype
+        self._dt = native.HUBERT_DTYPES[compute_dtype]
         c = {k: _cfg_get(config, k) for k in _DEFAULTS}
         self.config_dict = c
         need = (("feat_extract_norm", "group"), ("do_stable_layer_norm", False), ("conv_bias", False), ("feat_proj_layer_norm", True),
@@ -89,6 +98,8 @@ class NativeHubert(nn.Module):
         d.pos_kernel, d.pos_groups = int(c["num_conv_pos_embeddings"]), int(c["num_conv_pos_embedding_groups"])
         d.layer_norm_eps = float(c["layer_norm_eps"])
         self.dims = d
+        if self._dt:  # the limits only this dtype has (EdttsError naming the field); fp32 meets the library's at the first call, as before
+            native.hubert_packed_bytes(d, self._dt)
         for key, shape in self._shapes():
             self._put(key, shape)
         self._register_load_state_dict_pre_hook(self._normalise_keys)
@@ -174,15 +185,16 @@ class NativeHubert(nn.Module):
 
     # ------------------------------------------------------------------------------------------ construction
     @classmethod
-    def from_hubert(cls, model: nn.Module, num_layers: int) -> "NativeHubert":
+    def from_hubert(cls, model: nn.Module, num_layers: int, compute_dtype: str = "fp32") -> "NativeHubert":
         """From a transformers HubertModel (its config and state_dict); on the model's device."""
-        m = cls(model.config, num_layers)
+        m = cls(model.config, num_layers, compute_dtype=compute_dtype)
         m.load_state_dict(model.state_dict())
         dev = next(model.parameters()).device
         return m.to(dev).eval()
 
     @classmethod
-    def from_pretrained(cls, hubert_id: str, num_layers: int, local_files_only: bool = True) -> "NativeHubert":
+    def from_pretrained(cls, hubert_id: str, num_layers: int, local_files_only: bool = True,
+                        compute_dtype: str = "fp32") -> "NativeHubert":
         """Load ``hubert_id`` from the local Hugging Face cache only (never the network); raises SemanticEncoder's error when the
         model is not there."""
         from .encoder import _missing_hubert
@@ -194,7 +206,7 @@ class NativeHubert(nn.Module):
             model = HubertModel.from_pretrained(hubert_id, local_files_only=True)
         except OSError as e:
             raise _missing_hubert(hubert_id, e) from e
-        return cls.from_hubert(model, num_layers)
+        return cls.from_hubert(model, num_layers, compute_dtype=compute_dtype)
 
     # ------------------------------------------------------------------------------------------ lengths
     def frames(self, n_samples: int) -> int:
@@ -224,16 +236,16 @@ class NativeHubert(nn.Module):
         with self._lock:
             params = list(self.parameters())
             dev = params[0].device
-            sig = (dev,) + tuple((p.data_ptr(), p._version, p.device) for p in params)
+            sig = (dev, self._dt) + tuple((p.data_ptr(), p._version, p.device) for p in params)
             if self._blob is None or sig != self._sig:
                 tensors = self._slots()
                 for i, t in enumerate(tensors):
                     if t.device != dev or t.dtype != torch.float32:
                         raise native.EdttsError(f"NativeHubert weight {i}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
-                nbytes = native.hubert_packed_bytes(self.dims)
+                nbytes = native.hubert_packed_bytes(self.dims, self._dt)
                 if self._blob is None or self._blob.numel() != nbytes or self._blob.device != dev:
                     self._blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                native.hubert_pack(self.dims, [t.detach().contiguous() for t in tensors], self._blob)
+                native.hubert_pack(self.dims, [t.detach().contiguous() for t in tensors], self._blob, self._dt)
                 self._sig = sig
             return self._blob
 
@@ -256,7 +268,7 @@ class NativeHubert(nn.Module):
                 evictable = [k for k in self._workspaces if k not in self._pinned]
                 while len(self._workspaces) >= self.WORKSPACE_CACHE and evictable:
                     del self._workspaces[evictable.pop(0)]
-                ws = torch.empty(native.hubert_workspace_bytes(self.dims, B, T_audio), dtype=torch.uint8, device=dev)
+                ws = torch.empty(native.hubert_workspace_bytes(self.dims, B, T_audio, self._dt), dtype=torch.uint8, device=dev)
             self._workspaces[key] = ws
             if capturing:
                 self._pinned.add(key)
@@ -283,9 +295,9 @@ class NativeHubert(nn.Module):
         wav = wav.float().contiguous()
         blob = self._packed()
         out = torch.empty((B, T, self.hidden_size), dtype=torch.float32, device=wav.device)
-        native.hubert_forward(self.dims, blob, wav, n, out, self.workspace(B, T_audio, wav.device))
+        native.hubert_forward(self.dims, blob, wav, n, out, self.workspace(B, T_audio, wav.device), self._dt)
         return out
 
     def extra_repr(self) -> str:
         d = self.dims
-        return f"hidden={d.hidden}, heads={d.heads}, num_layers={self.num_layers}, conv={list(d.conv_dim)[:d.n_conv]}"
+        return f"hidden={d.hidden}, heads={d.heads}, num_layers={self.num_layers}, conv={list(d.conv_dim)[:d.n_conv]}, compute_dtype={self.compute_dtype}"

@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "edtts_sample_inpaint_len", "edtts_randn_rows",
     "edtts_sem_packed_bytes", "edtts_sem_num_codes", "edtts_sem_pack", "edtts_sem_encode", "edtts_sem_decode", "edtts_sem_stats",
     "edtts_hubert_frames", "edtts_hubert_packed_bytes", "edtts_hubert_pack", "edtts_hubert_workspace_bytes", "edtts_hubert_forward",
+    "edtts_hubert_packed_bytes_dt", "edtts_hubert_pack_dt", "edtts_hubert_workspace_bytes_dt", "edtts_hubert_forward_dt",
     "edtts_melspec", "edtts_mel_segment_stats", "edtts_logmel_stats", "edtts_resample",
 )
 
@@ -141,6 +142,10 @@ def lib() -> C.CDLL:
     L.edtts_hubert_pack.argtypes = [hdp, C.POINTER(vp), i32, vp, vp]
     L.edtts_hubert_workspace_bytes.argtypes = [hdp, i32, i32, C.POINTER(sz)]
     L.edtts_hubert_forward.argtypes = [hdp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.edtts_hubert_packed_bytes_dt.argtypes = [hdp, i32, C.POINTER(sz)]
+    L.edtts_hubert_pack_dt.argtypes = [hdp, i32, C.POINTER(vp), i32, vp, vp]
+    L.edtts_hubert_workspace_bytes_dt.argtypes = [hdp, i32, i32, i32, C.POINTER(sz)]
+    L.edtts_hubert_forward_dt.argtypes = [hdp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.edtts_melspec.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.edtts_mel_segment_stats.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     L.edtts_logmel_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
@@ -536,31 +541,50 @@ def hubert_frames(dims: EdttsHubertDims, n_samples: int) -> int:
     return out.value
 
 
-def hubert_packed_bytes(dims: EdttsHubertDims) -> int:
+# compute dtypes of the HuBERT backbone (include/edtts.h: EDTTS_HUBERT_FP32 / EDTTS_HUBERT_BF16)
+HUBERT_DTYPES = {"fp32": 0, "bf16": 1}
+
+
+def hubert_packed_bytes(dims: EdttsHubertDims, compute_dtype: int = 0) -> int:
     out = C.c_size_t(0)
-    lib().edtts_hubert_packed_bytes(C.byref(dims), C.byref(out))
+    if compute_dtype:
+        lib().edtts_hubert_packed_bytes_dt(C.byref(dims), int(compute_dtype), C.byref(out))
+    else:
+        lib().edtts_hubert_packed_bytes(C.byref(dims), C.byref(out))
     return out.value
 
 
-def hubert_workspace_bytes(dims: EdttsHubertDims, B: int, T_audio: int) -> int:
+def hubert_workspace_bytes(dims: EdttsHubertDims, B: int, T_audio: int, compute_dtype: int = 0) -> int:
     out = C.c_size_t(0)
-    lib().edtts_hubert_workspace_bytes(C.byref(dims), int(B), int(T_audio), C.byref(out))
+    if compute_dtype:
+        lib().edtts_hubert_workspace_bytes_dt(C.byref(dims), int(compute_dtype), int(B), int(T_audio), C.byref(out))
+    else:
+        lib().edtts_hubert_workspace_bytes(C.byref(dims), int(B), int(T_audio), C.byref(out))
     return out.value
 
 
-def hubert_pack(dims: EdttsHubertDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor) -> None:
-    """Pack the backbone's weights (include/edtts.h: edtts_hubert_pack, slot order there) into `packed` (uint8 device tensor)."""
+def hubert_pack(dims: EdttsHubertDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor, compute_dtype: int = 0) -> None:
+    """Pack the backbone's weights (include/edtts.h: edtts_hubert_pack / edtts_hubert_pack_dt, slot order there) into `packed`
+    (uint8 device tensor)."""
     ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
-    lib().edtts_hubert_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
+    if compute_dtype:
+        lib().edtts_hubert_pack_dt(C.byref(dims), int(compute_dtype), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"),
+                                   _stream(packed.device))
+    else:
+        lib().edtts_hubert_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
 
 
 def hubert_forward(dims: EdttsHubertDims, packed: torch.Tensor, wav: torch.Tensor, lengths: Optional[torch.Tensor], out: torch.Tensor,
-                   workspace: torch.Tensor) -> None:
-    """wav [B, T_audio] -> out [B, T_feat, hidden] on the current stream (include/edtts.h: edtts_hubert_forward)."""
+                   workspace: torch.Tensor, compute_dtype: int = 0) -> None:
+    """wav [B, T_audio] -> out [B, T_feat, hidden] on the current stream (include/edtts.h: edtts_hubert_forward / _forward_dt)."""
     B, T = wav.shape
-    lib().edtts_hubert_forward(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(wav, torch.float32, "wav"), B, T,
-                               _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(out, torch.float32, "out"),
-                               _dev_ptr(workspace, torch.uint8, "workspace"), _stream(wav.device))
+    args = (_dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(wav, torch.float32, "wav"), B, T,
+            _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(out, torch.float32, "out"),
+            _dev_ptr(workspace, torch.uint8, "workspace"), _stream(wav.device))
+    if compute_dtype:
+        lib().edtts_hubert_forward_dt(C.byref(dims), int(compute_dtype), *args)
+    else:
+        lib().edtts_hubert_forward(C.byref(dims), *args)
 
 
 def set_substreams(n: int) -> int:

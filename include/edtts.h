@@ -448,6 +448,23 @@ int edtts_hubert_workspace_bytes(const EdttsHubertDims* dims, int B, int T_audio
  * out, packed and workspace 16-byte aligned.  No allocation, no host synchronisation: graph-capturable. */
 int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths,
                          float* out, void* workspace, void* stream);
+/* The backbone with a compute dtype (csrc/edtts_hubert16.h).  compute_dtype EDTTS_HUBERT_FP32: exactly the four calls above (same
+ * kernels, same blob, same workspace).  EDTTS_HUBERT_BF16: the two operands of every contraction after conv0 -- conv1 .. conv_last, the
+ * feature projection, the positional conv (its weight norm folded in fp32 by the caller, as above), QKV, Q K^T, P V, out_proj, the FFN
+ * -- are rounded to bf16 (nearest even) and multiplied on v_mfma_f32_16x16x32_bf16 with fp32 accumulators; conv0, the GroupNorm
+ * statistics, the residual stream, biases, GELU, every LayerNorm, the softmax and the output stay fp32.  slots, out, lengths and the
+ * bitwise invariances are those of the fp32 calls; the blob holds the matrices as bf16 (conv weights [co][k][ci], q | k | v as one
+ * [3H][H]) and conv0 / GroupNorm / biases / norm parameters as fp32, and blob and workspace belong to the dtype they were sized for.
+ * Limits of the bf16 path beyond the fp32 ones (EDTTS_ERR_UNSUPPORTED, the message names the field): conv_dim[i], hidden,
+ * intermediate and hidden / pos_groups multiples of 8 (a 16-byte operand chunk never straddles a conv tap), head_dim a multiple of 32.
+ * Any other compute_dtype: EDTTS_ERR_ARG. */
+#define EDTTS_HUBERT_FP32 0
+#define EDTTS_HUBERT_BF16 1
+int edtts_hubert_packed_bytes_dt(const EdttsHubertDims* dims, int compute_dtype, size_t* out_bytes);
+int edtts_hubert_pack_dt(const EdttsHubertDims* dims, int compute_dtype, const void* const* slots, int n_slots, void* packed, void* stream);
+int edtts_hubert_workspace_bytes_dt(const EdttsHubertDims* dims, int compute_dtype, int B, int T_audio, size_t* out_bytes);
+int edtts_hubert_forward_dt(const EdttsHubertDims* dims, int compute_dtype, const void* packed, const float* wav, int B, int T_audio,
+                            const int64_t* lengths, float* out, void* workspace, void* stream);
 
 /* ---- audio front end  (the torchaudio ops the reference calls at every entry point: generate_sample.py:75-116,
  * data/collate.py:34-60, inference_pipeline.py:206-207, 354-355) -------------------------------------------------------------------

@@ -1,0 +1,115 @@
+"""Host tests (no GPU) of NativeHubert's compute_dtype keyword and the edtts_hubert_*_dt entry points (csrc/edtts_hubert16.h): the
+symbols, construction and validation, the packed and workspace sizes of both dtypes, the limits only the bf16 path has."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from edge_diffusion_tts_amd import NativeHubert, native
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden")
+NEW = ("edtts_hubert_packed_bytes_dt", "edtts_hubert_pack_dt", "edtts_hubert_workspace_bytes_dt", "edtts_hubert_forward_dt")
+# the fp32 sizes of the parent commit, hubert-base at 9 layers: pinned so that the fp32 blob and workspace stay what they were
+FP32_PACKED_9 = 292428800
+
+
+def small_cfg():
+    z = np.load(os.path.join(GOLDEN, "hubert_small.npz"))
+    return json.loads(bytes(z["config"]).decode())
+
+
+def test_new_symbols_are_declared_and_exported():
+    header = open(os.path.join(REPO, "include", "edtts.h")).read()
+    declared = set(re.findall(r"\b(edtts_[a-z_0-9]+)\s*\(", header))
+    L = ctypes.CDLL(native.LIB_PATH)
+    for sym in NEW:
+        assert sym in declared and sym in native.EXPORTED_SYMBOLS and hasattr(L, sym), sym
+    assert "EDTTS_HUBERT_BF16 1" in header and native.HUBERT_DTYPES == {"fp32": 0, "bf16": 1}
+    assert native.lib().edtts_version() == 400  # additive: the ABI version stays
+
+
+def test_keyword_constructs_and_validates():
+    m = NativeHubert({}, 9, compute_dtype="bf16")
+    assert m.compute_dtype == "bf16" and "compute_dtype=bf16" in repr(m)
+    d = NativeHubert({}, 9)
+    assert d.compute_dtype == "fp32" and "compute_dtype=fp32" in repr(d)
+    assert list(m.state_dict().keys()) == list(d.state_dict().keys())
+    assert all(p.dtype == torch.float32 for p in m.parameters())  # parameters stay fp32: only the packed blob differs
+    with pytest.raises(ValueError, match="compute_dtype"):
+        NativeHubert({}, 9, compute_dtype="fp8")
+    with pytest.raises(ValueError, match="compute_dtype"):
+        NativeHubert({}, 9, compute_dtype="fp16")
+    s = NativeHubert(small_cfg(), 3, compute_dtype="bf16")
+    assert s.frames(4800) == NativeHubert(small_cfg(), 3).frames(4800) == 14
+
+
+def test_from_hubert_takes_the_keyword():
+    transformers = pytest.importorskip("transformers")
+    model = transformers.HubertModel(transformers.HubertConfig(**small_cfg())).eval()
+    m = NativeHubert.from_hubert(model, 2, compute_dtype="bf16")
+    assert m.compute_dtype == "bf16" and m.num_layers == 2
+    assert torch.equal(m.state_dict()["encoder.layers.1.attention.q_proj.weight"],
+                       model.state_dict()["encoder.layers.1.attention.q_proj.weight"])
+    with pytest.raises(ValueError):
+        NativeHubert.from_hubert(model, 2, compute_dtype="int8")
+
+
+def test_packed_and_workspace_sizes():
+    f, h = NativeHubert({}, 9), NativeHubert({}, 9, compute_dtype="bf16")
+    pf, ph = native.hubert_packed_bytes(f.dims), native.hubert_packed_bytes(h.dims, 1)
+    assert pf == FP32_PACKED_9, pf
+    assert native.hubert_packed_bytes(f.dims, 0) == pf
+    # every matrix but conv0 halves; what stays fp32 (conv0, GroupNorm, biases, norm parameters) is well under 1 % of the blob
+    assert pf // 2 < ph < pf // 2 + pf // 100
+    out = ctypes.c_size_t(0)
+    native.lib().edtts_hubert_packed_bytes_dt(ctypes.byref(f.dims), 0, ctypes.byref(out))
+    assert out.value == pf
+    wf = native.hubert_workspace_bytes(f.dims, 16, 160000)
+    native.lib().edtts_hubert_workspace_bytes_dt(ctypes.byref(f.dims), 0, 16, 160000, ctypes.byref(out))
+    assert out.value == wf
+    wh = native.hubert_workspace_bytes(h.dims, 16, 160000, 1)
+    print(f"hubert-base B=16 x 10 s workspace: fp32 {wf} B ({wf / 2**30:.3f} GiB), bf16 {wh} B ({wh / 2**30:.3f} GiB)")
+    # conv0's output, the ping-pong buffer, the q | k | v / FFN rows halve; h and the positional conv's output do not; V^T is added
+    assert wf // 2 < wh < wf * 6 // 10
+    # the small fixture too
+    s = NativeHubert(small_cfg(), 3, compute_dtype="bf16")
+    assert native.hubert_packed_bytes(s.dims, 1) < native.hubert_packed_bytes(s.dims)
+    assert native.hubert_workspace_bytes(s.dims, 3, 4800, 1) > 0
+    with pytest.raises(native.EdttsError, match="no output frame"):  # the fp32 call's error, in both dtypes
+        native.hubert_workspace_bytes(s.dims, 1, 100, 1)
+    with pytest.raises(native.EdttsError, match="no output frame"):
+        native.hubert_workspace_bytes(s.dims, 1, 100)
+    with pytest.raises(native.EdttsError, match="compute_dtype"):
+        native.hubert_packed_bytes(s.dims, 7)
+
+
+@pytest.mark.parametrize("change, field", [
+    (dict(hidden_size=48, num_attention_heads=2, num_conv_pos_embedding_groups=2, intermediate_size=96), "head_dim"),
+    (dict(hidden_size=64, num_attention_heads=4), "num_attention_heads"),
+    (dict(conv_dim=[32, 36, 32, 32, 32, 32, 32]), r"conv_dim\[1\]"),
+    (dict(intermediate_size=132), "intermediate_size"),
+    (dict(num_conv_pos_embedding_groups=16), "num_conv_pos_embedding_groups"),
+])
+def test_limits_of_the_bf16_path_name_the_field(change, field):
+    cfg = dict(small_cfg(), **change)
+    NativeHubert(cfg, 3)  # the same config constructs in fp32
+    with pytest.raises(native.EdttsError, match=field):
+        NativeHubert(cfg, 3, compute_dtype="bf16")
+
+
+def test_two_dtypes_share_nothing():
+    f, h = NativeHubert(small_cfg(), 3), NativeHubert(small_cfg(), 3, compute_dtype="bf16")
+    assert f._workspaces is not h._workspaces and f._pinned is not h._pinned and f._lock is not h._lock
+    assert f.WORKSPACE_CACHE == h.WORKSPACE_CACHE == 8
+    # the same errors in both dtypes for what the forward rejects before any kernel runs
+    for m in (f, h):
+        with pytest.raises(native.EdttsError, match="no CPU path"):
+            m(torch.zeros(1, 4800))
+        with pytest.raises(ValueError, match="expected a waveform"):
+            m(torch.zeros(4800))
+        assert m.min_samples() == 400
