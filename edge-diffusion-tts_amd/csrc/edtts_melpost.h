@@ -7,6 +7,15 @@
 // frame); Griffin-Lim is FFT-bound: per iteration and frame one 1024-point inverse and one forward complex FFT (2 x 51 kFLOP)
 // in LDS plus 4 KB (frame buffer) + 8 KB (phase state) + 4 KB (spectrum) of HBM traffic -> ~25 FLOP/B: HBM-bound on MI355X
 // (ridge 20 FLOP/B for fp32 vector math); the iteration state is laid out frame-major so that every access is a contiguous row.
+//
+// Ragged batches (edtts_mel_to_spec_len, edtts_griffin_lim_len): rows padded to a common T carry their own frame
+// count T_b = t_len[b] (clamped into [1, T]; nullptr = T for every row, today's behaviour).  A block of a frame t >= T_b leaves before
+// its first barrier (the whole block takes that branch), the overlap-add and the reflect padding end at the row's own last frame, and
+// the library-drawn phases hash the row's solo element index f T_b + t with the row's own seed, so row b is bitwise the call on
+// spec[b, :, :T_b] alone.  Strides stay those of the padded batch; the state of padded frames is neither written nor read.
+// k_mel_to_spec_smooth is k_mel_to_spec for linear-mel input behind a kh x kw box filter (the reference's long-form tail,
+// inference_pipeline.py:376-399: F.avg_pool2d(lin_mel, (5, 3), stride=1, padding=(2, 1)), count_include_pad), the row's own end
+// being the filter's edge.
 #pragma once
 
 namespace melpost {
@@ -45,24 +54,11 @@ EDTTS_DEV cplx* fft1024(cplx* x, cplx* y, const cplx* __restrict__ tw, int tid) 
   return x;
 }
 
-// spec[b][f][t] = relu(sum_m pinv[f][m] * lin[b][t][m]),  lin = exp(mel_n * std + mean) or the input itself   (torch layout [B, n_freqs, T])
-__global__ __launch_bounds__(kThreads) void k_mel_to_spec(const float* __restrict__ mel, const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                          const float* __restrict__ pinv, int T, int M, int NFQ, float* __restrict__ spec) {
-  extern __shared__ float lin[];  // [16 frames][M]
-  const int b = blockIdx.y, t0 = blockIdx.x * 16;
-  for (int i = threadIdx.x; i < 16 * M; i += kThreads) {
-    const int tl = i / M, m = i % M, t = t0 + tl;
-    float v = 0.f;
-    if (t < T) {
-      v = mel[((size_t)b * T + t) * M + m];
-      // normalised log-mel in (mean / std given): denormalise (utils/audio.py:19) and leave the log domain (generate_sample.py:119);
-      // otherwise the input already is the linear mel spectrogram (plain torchaudio InverseMelScale semantics)
-      if (stdv) v = expf(v * stdv[(size_t)b * M + m] + mean[(size_t)b * M + m]);
-    }
-    lin[i] = v;
-  }
-  __syncthreads();
-  // thread -> (frequency f, 16 frames): the 16 outputs of a frequency are contiguous in the [.., f, t] layout
+constexpr int kSmoothMax = 9, kSmoothMaxMels = 256;  // box filter sides (odd) and mel bins of k_mel_to_spec_smooth (LDS: 40 x n_mels floats)
+
+// The inverse-mel product of one 16-frame tile staged in LDS (lin [16][M]): thread -> (frequency f, 16 frames), the 16 outputs of a
+// frequency being contiguous in the [.., f, t] layout
+EDTTS_DEV void mel_pinv_tile(const float* lin, const float* __restrict__ pinv, int b, int t0, int T, int M, int NFQ, float* __restrict__ spec) {
   for (int f = threadIdx.x; f < NFQ; f += kThreads) {
     float acc[16];
 #pragma unroll
@@ -80,10 +76,68 @@ __global__ __launch_bounds__(kThreads) void k_mel_to_spec(const float* __restric
   }
 }
 
+// spec[b][f][t] = relu(sum_m pinv[f][m] * lin[b][t][m]),  lin = exp(mel_n * std + mean) or the input itself   (torch layout [B, n_freqs, T])
+// t_len: frames t >= t_len[b] are staged as 0 and so written as 0 (their input is never read)
+__global__ __launch_bounds__(kThreads) void k_mel_to_spec(const float* __restrict__ mel, const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                          const float* __restrict__ pinv, int T, int M, int NFQ, const int64_t* __restrict__ t_len,
+                                                          float* __restrict__ spec) {
+  extern __shared__ float lin[];  // [16 frames][M]
+  const int b = blockIdx.y, t0 = blockIdx.x * 16;
+  const int Tb = utt_len(t_len, b, T);
+  for (int i = threadIdx.x; i < 16 * M; i += kThreads) {
+    const int tl = i / M, m = i % M, t = t0 + tl;
+    float v = 0.f;
+    if (t < Tb) {
+      v = mel[((size_t)b * T + t) * M + m];
+      // normalised log-mel in (mean / std given): denormalise (utils/audio.py:19) and leave the log domain (generate_sample.py:119);
+      // otherwise the input already is the linear mel spectrogram (plain torchaudio InverseMelScale semantics)
+      if (stdv) v = expf(v * stdv[(size_t)b * M + m] + mean[(size_t)b * M + m]);
+    }
+    lin[i] = v;
+  }
+  __syncthreads();
+  mel_pinv_tile(lin, pinv, b, t0, T, M, NFQ, spec);
+}
+
+// ... of the box-filtered linear mel: sm[t][m] = (1 / (kh kw)) sum_{|dm| <= kh/2, |dt| <= kw/2} lin[t + dt][m + dm], zeros outside
+// 0 <= m < M, 0 <= t < T_b (avg_pool2d, stride 1, padding (kh/2, kw/2), count_include_pad); kh, kw odd, <= kSmoothMax.  The tile is
+// staged with its frame halo; the sum runs dm-major, dt-minor in ascending order (one fixed chain per element).
+__global__ __launch_bounds__(kThreads) void k_mel_to_spec_smooth(const float* __restrict__ mel, const float* __restrict__ pinv, int T, int M, int NFQ,
+                                                                 const int64_t* __restrict__ t_len, int kh, int kw, float* __restrict__ spec) {
+  extern __shared__ float lin[];  // [16 frames][M] smoothed | [16 + kw - 1 frames][M] raw
+  float* raw = lin + 16 * M;
+  const int b = blockIdx.y, t0 = blockIdx.x * 16, hh = kh >> 1, hw = kw >> 1;
+  const int Tb = utt_len(t_len, b, T);
+  for (int i = threadIdx.x; i < (16 + 2 * hw) * M; i += kThreads) {
+    const int t = t0 - hw + i / M;
+    raw[i] = t >= 0 && t < Tb ? mel[((size_t)b * T + t) * M + i % M] : 0.f;
+  }
+  __syncthreads();
+  const float scale = 1.0f / (float)(kh * kw);
+  for (int i = threadIdx.x; i < 16 * M; i += kThreads) {
+    const int tl = i / M, m = i % M;
+    float s = 0.f;
+    if (t0 + tl < Tb) {
+      const int m_lo = m - hh < 0 ? 0 : m - hh, m_hi = m + hh > M - 1 ? M - 1 : m + hh;
+      for (int mm = m_lo; mm <= m_hi; ++mm)
+        for (int dt = 0; dt <= 2 * hw; ++dt) s += raw[(tl + dt) * M + mm];
+      s *= scale;
+    }
+    lin[i] = s;
+  }
+  __syncthreads();
+  mel_pinv_tile(lin, pinv, b, t0, T, M, NFQ, spec);
+}
+
 // mag[b][t][f] = spec[b][f][t] ^ (1 / power); angles[b][t][f] = angles0 (torch layout [B, n_freqs, T] complex) or uniform draws
+// t_len: the draws of row b are keyed by (seeds[b], f T_b + t), the element index of the row's solo call (B = 1, T = T_b)
 __global__ __launch_bounds__(kThreads) void k_gl_init(const float* __restrict__ spec, const float* __restrict__ angles0, int T, float inv_power,
-                                                      unsigned long long seed, float* __restrict__ mag, cplx* __restrict__ ang, cplx* __restrict__ tprev) {
+                                                      unsigned long long seed, const int64_t* __restrict__ t_len,
+                                                      const unsigned long long* __restrict__ seeds, float* __restrict__ mag, cplx* __restrict__ ang,
+                                                      cplx* __restrict__ tprev) {
   const int b = blockIdx.y, t = blockIdx.x;
+  const int Tb = utt_len(t_len, b, T);
+  if (t >= Tb) return;
   for (int f = threadIdx.x; f < kBins; f += kThreads) {
     const size_t src = ((size_t)b * kBins + f) * T + t, dst = ((size_t)b * T + t) * kBins + f;
     const float s = spec[src];
@@ -92,7 +146,8 @@ __global__ __launch_bounds__(kThreads) void k_gl_init(const float* __restrict__ 
     if (angles0) a = {angles0[2 * src], angles0[2 * src + 1]};
     else {  // torch.rand(complex): real and imaginary parts uniform in [0, 1)
       // counter hash (splitmix64 of (seed, element)) -> two 24-bit uniforms; the reference's draw comes from torch's global RNG
-      unsigned long long z = (seed ^ 0x9E3779B97F4A7C15ull) + (unsigned long long)src * 0xBF58476D1CE4E5B9ull;
+      const unsigned long long sd = t_len ? seeds[b] : seed, el = t_len ? (unsigned long long)f * Tb + t : (unsigned long long)src;
+      unsigned long long z = (sd ^ 0x9E3779B97F4A7C15ull) + el * 0xBF58476D1CE4E5B9ull;
       z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
       a = {(float)(unsigned)(z >> 40) * (1.0f / 16777216.0f), (float)(unsigned)((z >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f)};
     }
@@ -103,9 +158,11 @@ __global__ __launch_bounds__(kThreads) void k_gl_init(const float* __restrict__ 
 
 // frames[b][t][n] = window[n] * irfft(mag * angles)[n]      (torch.istft: per-frame inverse real FFT, "backward" normalisation)
 __global__ __launch_bounds__(kThreads) void k_gl_istft(const float* __restrict__ mag, const cplx* __restrict__ ang, const float* __restrict__ window,
-                                                       const cplx* __restrict__ tw, int T, float* __restrict__ frames) {
+                                                       const cplx* __restrict__ tw, int T, const int64_t* __restrict__ t_len,
+                                                       float* __restrict__ frames) {
   __shared__ cplx bufa[kNfft], bufb[kNfft];
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
+  if (t >= utt_len(t_len, b, T)) return;  // a padded frame: the whole block leaves before the first barrier
   const size_t row = ((size_t)b * T + t) * kBins;
   for (int f = tid; f < kBins; f += kThreads) {
     const float m = mag[row + f];
@@ -121,14 +178,16 @@ __global__ __launch_bounds__(kThreads) void k_gl_istft(const float* __restrict__
 
 // wave[b][p] = sum_t frames[b][t][p - t hop] / sum_t window^2[p - t hop]   over the frames that cover padded position p
 // (torch.istft overlap-add and window-envelope normalisation; ascending t: deterministic)
+// t_len: row b's padded signal is Lp_b = n_fft + hop (T_b - 1) long (row stride Lp); positions past it are left alone
 __global__ __launch_bounds__(kThreads) void k_gl_ola(const float* __restrict__ frames, const float* __restrict__ window, int T, int hop, int Lp,
-                                                     float* __restrict__ wave) {
+                                                     const int64_t* __restrict__ t_len, float* __restrict__ wave) {
   const int b = blockIdx.y;
-  for (int p = blockIdx.x * kThreads + threadIdx.x; p < Lp; p += gridDim.x * kThreads) {
+  const int Tb = utt_len(t_len, b, T), Lpb = kNfft + hop * (Tb - 1);
+  for (int p = blockIdx.x * kThreads + threadIdx.x; p < Lpb; p += gridDim.x * kThreads) {
     int t_lo = (p - (kNfft - 1) + hop - 1) / hop;
     if (p - (kNfft - 1) < 0) t_lo = 0;
     int t_hi = p / hop;
-    if (t_hi > T - 1) t_hi = T - 1;
+    if (t_hi > Tb - 1) t_hi = Tb - 1;
     float s = 0.f, e = 0.f;
     for (int t = t_lo; t <= t_hi; ++t) {
       const int n = p - t * hop;
@@ -143,10 +202,13 @@ __global__ __launch_bounds__(kThreads) void k_gl_ola(const float* __restrict__ f
 // rebuilt = stft(x, center=True, reflect), x = wave[n_fft/2 : n_fft/2 + Lx];  then the momentum phase update
 //   a = rebuilt - mom * tprev;  angles = a / (|a| + 1e-16);  tprev = rebuilt          (torchaudio.functional.griffinlim)
 __global__ __launch_bounds__(kThreads) void k_gl_stft(const float* __restrict__ wave, const float* __restrict__ window, const cplx* __restrict__ tw,
-                                                      int T, int hop, int Lp, float mom, cplx* __restrict__ ang, cplx* __restrict__ tprev) {
+                                                      int T, int hop, int Lp, float mom, const int64_t* __restrict__ t_len, cplx* __restrict__ ang,
+                                                      cplx* __restrict__ tprev) {
   __shared__ cplx bufa[kNfft], bufb[kNfft];
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-  const int Lx = Lp - kNfft;  // = hop * (T - 1)
+  const int Tb = utt_len(t_len, b, T);
+  if (t >= Tb) return;  // a padded frame: the whole block leaves before the first barrier
+  const int Lx = hop * (Tb - 1);  // the row's own signal: the reflection is at its own end
   const float* x = wave + (size_t)b * Lp + kNfft / 2;
   for (int n = tid; n < kNfft; n += kThreads) {
     int idx = t * hop + n - kNfft / 2;
@@ -164,6 +226,15 @@ __global__ __launch_bounds__(kThreads) void k_gl_stft(const float* __restrict__ 
     ang[row + f] = {a.re * inv, a.im * inv};
     tprev[row + f] = rb;
   }
+}
+
+// wave_out[b][i] = wave[b][n_fft / 2 + i] for i < hop (T_b - 1), 0 behind it (torch.istft's trim of the centre padding, per row)
+__global__ __launch_bounds__(kThreads) void k_gl_trim(const float* __restrict__ wave, int T, int hop, int Lp, const int64_t* __restrict__ t_len,
+                                                      float* __restrict__ wave_out) {
+  const int b = blockIdx.y, Lo = hop * (T - 1);
+  const int Lxb = hop * (utt_len(t_len, b, T) - 1);
+  for (int i = blockIdx.x * kThreads + threadIdx.x; i < Lo; i += gridDim.x * kThreads)
+    wave_out[(size_t)b * Lo + i] = i < Lxb ? wave[(size_t)b * Lp + kNfft / 2 + i] : 0.f;
 }
 
 }  // namespace melpost

@@ -197,7 +197,8 @@ class InpaintSampler:
 
         with the trapezoid window of :253-260 (linear fade-in over the first and fade-out over the last ``overlap_frames``
         frames).  Returns the stitched LINEAR mel [n_mels, total_frames] -- what the reference hands to its smoothing /
-        InverseMelScale / Griffin-Lim tail (melpost.py).
+        InverseMelScale / Griffin-Lim tail (:376-399), which is ``MelVocoder.from_linear([mel])`` (melpost.py; it takes the whole
+        list that ``generate_long_batch`` returns in one call).
 
         ``chunk_stats``: one (mean, std) pair per chunk, each broadcastable to [1, 1, n_mels] -- the reference takes them from the
         ground-truth audio of the chunk (normalize_mel of its log-mel, :349-351); that audio front end (torchaudio) is outside the

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "edtts_hubert_frames", "edtts_hubert_packed_bytes", "edtts_hubert_pack", "edtts_hubert_workspace_bytes", "edtts_hubert_forward",
     "edtts_hubert_packed_bytes_dt", "edtts_hubert_pack_dt", "edtts_hubert_workspace_bytes_dt", "edtts_hubert_forward_dt",
     "edtts_melspec", "edtts_mel_segment_stats", "edtts_logmel_stats", "edtts_resample",
+    "edtts_mel_to_spec_len", "edtts_griffin_lim_len",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -113,6 +114,8 @@ def lib() -> C.CDLL:
     L.edtts_mel_to_spec.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.edtts_griffin_lim_scratch_floats.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
     L.edtts_griffin_lim.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, C.c_uint64, vp, vp, vp]
+    L.edtts_mel_to_spec_len.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    L.edtts_griffin_lim_len.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
     L.edtts_sample_inpaint.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32), vp, i32,
                                        vp, C.c_uint64, f32, vp, vp]
     L.edtts_sample_inpaint_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32),

@@ -324,6 +324,27 @@ int edtts_griffin_lim_scratch_floats(int B, int T, int n_fft, int hop, size_t* o
 int edtts_griffin_lim(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
                       float momentum, float power, const float* angles0, uint64_t seed, float* scratch, float* wave_out,
                       void* stream);
+/* ... with per-utterance frame counts (the arguments of the twin plus the ones named here; the twins remain and are unchanged):
+ * t_len: device int64 [B], rows padded to the common T; row b has T_b = t_len[b] frames, clamped into [1, T]; NULL = T for every row.
+ * idx_err: NULL, or one device uint32 the caller owns and zeroes once (edtts_index_errors reads and clears it, as it does a workspace):
+ * a t_len[b] outside [1, T] sets EDTTS_IDX_LEN in it -- for edtts_griffin_lim_len also a T_b with hop*(T_b-1) <= n_fft/2, a row the
+ * call on it alone refuses (it is computed all the same, its reflection clamped into the row).
+ * edtts_mel_to_spec_len: frames t >= T_b are written as 0 and their input is never read; frames are independent, so row b is
+ * bitwise the call on mel_n[b, :T_b] alone.  smooth_h x smooth_w (0 x 0: none; otherwise both odd, <= 9, mean = std = NULL, n_mels <=
+ * 256) first box-filters the linear mel over smooth_h mel bins x smooth_w frames with zeros outside 0 <= m < n_mels, 0 <= t < T_b:
+ * F.avg_pool2d(lin_mel, (h, w), stride=1, padding=(h/2, w/2)) (count_include_pad; inference_pipeline.py:376-399 uses 5 x 3), the
+ * row's own end being the edge -- again bitwise the call on the row alone.
+ * edtts_griffin_lim_len: t_len non-NULL.  Row b's padded signal is n_fft + hop*(T_b-1) long, its STFT reflects at its own end, and
+ * wave_out[b] is hop*(T_b-1) samples followed by zeros up to hop*(T-1).  seeds: device uint64 [B], needed when angles0 is NULL: row
+ * b's draws are keyed by (seeds[b], f*T_b + t), the element index of the call on the row alone (B = 1, T = T_b) -- so row b is
+ * bitwise edtts_griffin_lim on spec[b, :, :T_b] with seed = seeds[b] (or angles0[b, :, :T_b]) in its first hop*(T_b-1) samples.
+ * The [.., T] strides of spec / angles0 and the scratch size (edtts_griffin_lim_scratch_floats(B, T, ..)) are the padded batch's;
+ * the scratch state of padded frames is neither written nor read.  No allocation, no host synchronisation (graph-capturable). */
+int edtts_mel_to_spec_len(const float* mel_n, const float* mean, const float* stdv, const float* pinv, int B, int T, int n_mels,
+                          int n_freqs, const int64_t* t_len, int smooth_h, int smooth_w, void* idx_err, float* spec, void* stream);
+int edtts_griffin_lim_len(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
+                          float momentum, float power, const float* angles0, const int64_t* t_len, const uint64_t* seeds,
+                          void* idx_err, float* scratch, float* wave_out, void* stream);
 
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------------------------------
  * edtts_profile_enable(n > 0): from now on every transformer-layer kernel launch is bracketed by a pair of
