@@ -338,6 +338,26 @@ EDTTS_DEV void tail_elem(const KArgs& a, size_t idx, float e) {
     a.x0_hist[idx] = v0;
     if (a.x0_all) a.x0_all[idx] = v0;
     a.x_prev[idx] = vn;
+  } else if (TAIL == TAIL_VLMS) {
+    const float v = a.v_uncond ? cfg_combine(e, a.v_uncond[idx], a.vp.cfg) : e;
+    const float hn = a.lms.mode >= 2 ? a.h_new[idx] : 0.f, ho = a.lms.mode >= 3 ? a.h_old[idx] : 0.f;
+    float v0, vn;
+    lms_elem(a.x[idx], v, hn, ho, a.lms, v0, vn);
+    a.x0_hist[idx] = v0;
+    if (a.x0_all) a.x0_all[idx] = v0;
+    if (a.known != nullptr) {  // the next step's q_sample of the known frames (vlms_blend, one element: k_inpaint_inject1's values)
+      const size_t row = (size_t)a.T * a.inj_mel, b = idx / row, r = idx - b * row, per = (size_t)a.inj_frames * a.inj_mel;
+      if (r < per) {  // (the caller has checked the frame against the utterance's length)
+        const size_t ki = b * per + r;
+        vn = a.known[ki];
+        if (a.p_coef2 != 0.f) {
+          const float nz = a.noise ? a.noise[ki]
+                                   : (a.seeds ? philox_normal4(a.seeds[b], a.step, r >> 2)[(int)(r & 3)] : philox_normal4(a.seed, a.step, ki >> 2)[(int)(ki & 3)]);
+          vn = qsample_elem(vn, a.p_coef1, nz, a.p_coef2);
+        }
+      }
+    }
+    a.x_prev[idx] = vn;
   } else if (TAIL == TAIL_VPRED) {
     const float v = a.v_uncond ? cfg_combine(e, a.v_uncond[idx], a.vp.cfg) : e;
     a.x_prev[idx] = vpred_elem(a.x[idx], v, a.vp);
@@ -355,7 +375,7 @@ EDTTS_DEV void tail_elem(const KArgs& a, size_t idx, float e) {
 }
 template <int TAIL>
 EDTTS_DEV void tail_zero_elem(const KArgs& a, size_t idx) {
-  if (TAIL == TAIL_LMS) {
+  if (TAIL == TAIL_LMS || TAIL == TAIL_VLMS) {
     a.x0_hist[idx] = 0.f;
     if (a.x0_all) a.x0_all[idx] = 0.f;
   } else if (TAIL == TAIL_DDIM) {
@@ -375,6 +395,14 @@ __global__ __launch_bounds__(256) void k_gen_tail(KArgs a, const float* eps, siz
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   if (vec) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += stride) {
+      if constexpr (TAIL == TAIL_VLMS) {  // (its blend needs the frame: vec then also means MEL % 4 == 0)
+        const size_t row = 4 * i / MEL;
+        const int f = (int)(row % a.T);
+        // (utt_len_lane called from here changed k_gen_embed's code, as from k_inpaint_inject)
+        const int Tb = a.t_len ? utt_len_of(a.t_len[row / a.T], a.T, a.t_dbl) : a.T;
+        tail_store<TAIL>(a, f, Tb, 4 * i, ldg4(eps + 4 * i));
+        continue;
+      }
       if (past_len(a.t_len, a.t_dbl, 4 * i, a.T, MEL)) tail_zero<TAIL>(a, 4 * i);
       else tail_apply<TAIL>(a, 4 * i, ldg4(eps + 4 * i));
     }
@@ -518,6 +546,9 @@ struct GenericLauncher {
     bool vec = al16(x) && al16(a.x_prev) && al16(e) && (ln.t == nullptr || MEL % 4 == 0);
     if (tail.kind == TAIL_LMS) {
       vec = vec && al16(a.h_new) && al16(a.h_old) && al16(a.x0_hist) && al16(a.x0_all);
+    } else if (tail.kind == TAIL_VLMS) {
+      vec = vec && al16(a.v_uncond) && al16(a.h_new) && al16(a.h_old) && al16(a.x0_hist) && al16(a.x0_all) && al16(a.known) &&
+            al16(a.noise) && (a.known == nullptr || MEL % 4 == 0);
     } else if (tail.kind == TAIL_VPRED) {
       vec = vec && al16(a.v_uncond);
     } else if (tail.kind == TAIL_DDPM) {

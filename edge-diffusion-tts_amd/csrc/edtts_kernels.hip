@@ -467,7 +467,11 @@ struct KArgs {
   const float *q, *k, *vT;
   float *q_out, *k_out, *vT_out;
   float *kc, *vcT;  // cross K / V^T cache: kernel-specific base (k_ctx: whole cache; k_layer: this layer's slice)
-  const void* unused_[3];  // (no reader: keeps every later field at its kernel-argument offset, so the kernels' code is unchanged)
+  // in-painting multistep tail (TAIL_VLMS): the known frames blended into the NEXT step's x (these three fields fill 24 bytes that had
+  // no reader, so every later field keeps its kernel-argument offset and the other kernels' code is unchanged)
+  const float* known;               // [B][inj_frames][MEL] or null: no blend
+  const unsigned long long* seeds;  // per-row Philox seeds [B] or null: `seed`, keyed by the element of the whole [B][inj_frames][MEL] tensor
+  int inj_frames, inj_mel;          // overlap_len, n_mels
   const int64_t* sem_idx;
   const float* sem_feat;
   const float* cond;  // row base: [L][2][2H] per row
@@ -485,6 +489,8 @@ struct KArgs {
   float c_s1m, c_sab, c_sabp, c_dir;      // DDIM tail scalars
   float p_coef1, p_coef2, p_sd;           // DDPM tail scalars (schedule.py:227-237)
   const float* noise;                     // DDPM tail: injected noise [B,T,MEL] of this step, or null -> Philox
+                                          // (TAIL_VLMS: p_coef1 / p_coef2 = the blend's c_known / c_noise, noise = its [B,inj_frames,MEL]
+                                          //  draws or null -> Philox (seed | seeds, step))
   unsigned long long seed;
   unsigned long long philox_base;         // global element index of this shard's element 0 (batch_offset * T * MEL)
   unsigned step;
@@ -686,12 +692,12 @@ __global__ __launch_bounds__(C::THREADS) void k_prologue(KArgs a) {
 // =========================================================================================================
 // transformer layer kernel
 // =========================================================================================================
-enum { TAIL_QKV = 0, TAIL_EPS = 1, TAIL_DDIM = 2, TAIL_DDPM = 3, TAIL_LMS = 4, TAIL_VPRED = 5 };
+enum { TAIL_QKV = 0, TAIL_EPS = 1, TAIL_DDIM = 2, TAIL_DDPM = 3, TAIL_LMS = 4, TAIL_VPRED = 5, TAIL_VLMS = 6 };
 
 // What the last layer of a decoder forward does with its eps tile (one f4 = 4 mel bins of one frame at element index idx):
 // store it, or run the sampler's elementwise update on it right away.
 template <int TAIL>
-EDTTS_DEV void tail_apply(const KArgs& a, size_t idx, f4 ev) {
+EDTTS_DEV void tail_apply(const KArgs& a, size_t idx, f4 ev, bool blend = false) {
   if (TAIL == TAIL_EPS) {
     stg4(a.eps + idx, ev);
   } else if (TAIL == TAIL_LMS) {
@@ -710,6 +716,27 @@ EDTTS_DEV void tail_apply(const KArgs& a, size_t idx, f4 ev) {
     stg4(a.x0_hist + idx, x0);
     if (a.x0_all) stg4(a.x0_all + idx, x0);
     stg4(a.x_prev + idx, xn);
+  } else if (TAIL == TAIL_VLMS) {
+    // in-painting multistep step: the guidance combine of TAIL_VPRED (a select, for its reason), then TAIL_LMS's update on the
+    // combined v -- the same lms_elem call, so with no guidance the two tails run the same arithmetic
+    const bool guided = a.v_uncond != nullptr;
+    const f4 xv = ldg4(a.x + idx);
+    const f4 vu = ldg4((guided ? a.v_uncond : a.x) + idx);
+    f4 hn = splat(0.f), ho = splat(0.f);
+    if (a.lms.mode >= 2) hn = ldg4(a.h_new + idx);
+    if (a.lms.mode >= 3) ho = ldg4(a.h_old + idx);
+    f4 x0, xn;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float v = guided ? cfg_combine(ev[r], vu[r], a.vp.cfg) : ev[r];
+      float v0, vn;
+      lms_elem(xv[r], v, hn[r], ho[r], a.lms, v0, vn);
+      x0[r] = v0;
+      xn[r] = vn;
+    }
+    stg4(a.x0_hist + idx, x0);
+    if (a.x0_all) stg4(a.x0_all + idx, x0);
+    if (!blend) stg4(a.x_prev + idx, xn);  // (a blended frame: tail_store writes the next step's q_sample there instead)
   } else if (TAIL == TAIL_VPRED) {
     // v-prediction step of the in-painting samplers, optionally with classifier-free guidance (inference_pipeline.py:125-132,179-192)
     // Without guidance the combine's result is discarded by a select, not skipped by a branch: with the branch and per-utterance
@@ -754,7 +781,7 @@ EDTTS_DEV void tail_zero(const KArgs& a, size_t idx) {
   const f4 z = splat(0.f);
   if (TAIL == TAIL_EPS) {
     stg4(a.eps + idx, z);
-  } else if (TAIL == TAIL_LMS) {
+  } else if (TAIL == TAIL_LMS || TAIL == TAIL_VLMS) {
     stg4(a.x0_hist + idx, z);
     if (a.x0_all) stg4(a.x0_all + idx, z);
     stg4(a.x_prev + idx, z);
@@ -766,10 +793,33 @@ EDTTS_DEV void tail_zero(const KArgs& a, size_t idx) {
   }
 }
 // tail of frame f < T of utterance b (Tb frames valid) at element idx
+// TAIL_VLMS, frame f < min(inj_frames, T_b) of a call with a known tail: what the NEXT step starts from there is not the update but
+// q_sample(known, t_next) (k_inpaint_inject's values: the same draws and the same qsample_elem), after the last step the known frames
+// themselves (c_noise = 0); tail_apply has left x_prev alone there.  idx is a multiple of 4 and inj_mel % 4 == 0 (the callers' vector paths), so a quad lies in one frame.
+EDTTS_DEV void vlms_blend(const KArgs& a, size_t idx) {
+  const size_t row = (size_t)a.T * a.inj_mel, b = idx / row, r = idx - b * row;  // r: element within the row's [inj_frames][MEL] block
+  const size_t ki = b * ((size_t)a.inj_frames * a.inj_mel) + r;
+  const f4 kv = ldg4(a.known + ki);
+  f4 o = kv;
+  if (a.p_coef2 != 0.f) {
+    const unsigned long long sd = a.seeds ? a.seeds[b] : a.seed;
+    const f4 nz = a.noise ? ldg4(a.noise + ki) : philox_normal4(sd, a.step, (a.seeds ? r : ki) >> 2);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = qsample_elem(kv[e], a.p_coef1, nz[e], a.p_coef2);
+  }
+  stg4(a.x_prev + idx, o);
+}
 template <int TAIL>
 EDTTS_DEV void tail_store(const KArgs& a, int f, int Tb, size_t idx, f4 ev) {
-  if (f < Tb) tail_apply<TAIL>(a, idx, ev);
-  else tail_zero<TAIL>(a, idx);
+  if constexpr (TAIL == TAIL_VLMS) {
+    const bool blend = a.known != nullptr && f < Tb && f < a.inj_frames;
+    if (f < Tb) tail_apply<TAIL>(a, idx, ev, blend);
+    else tail_zero<TAIL>(a, idx);
+    if (blend) vlms_blend(a, idx);
+  } else {
+    if (f < Tb) tail_apply<TAIL>(a, idx, ev);
+    else tail_zero<TAIL>(a, idx);
+  }
 }
 
 struct QGlobal {  // q rows in global memory, row-major [Tp][H]: buffer loads (descriptor base = row m0 of the utterance)
@@ -2420,6 +2470,14 @@ struct LmsStepArgs {
   const float *h_new, *h_old;
   float *x0_hist, *x0_all;
 };
+struct BlendStepArgs {  // TAIL_VLMS: the known frames' q_sample for the next step (k_inpaint_inject's arguments); known = null: none
+  const float *known, *noise;
+  int frames, mel;
+  float c_known, c_noise;
+  unsigned long long seed;
+  const unsigned long long* seeds;
+  unsigned step;  // stream id (kStreamInpaintStep + the next step's index)
+};
 // What the last layer of a decoder forward does with its output: return eps (TAIL_EPS) or take one sampler step
 struct StepTail {
   int kind = TAIL_EPS;
@@ -2429,7 +2487,8 @@ struct StepTail {
   const float* coef = nullptr;  // TAIL_DDIM: 4 scalars, TAIL_DDPM: 3
   DdpmStepArgs ddpm{};
   LmsStepArgs lms{};
-  VpredStepArgs vp{};
+  VpredStepArgs vp{};  // (TAIL_VLMS reads its cfg and v_uncond, and lms)
+  BlendStepArgs blend{};
 };
 static void set_tail_args(const StepTail& t, KArgs* a) {
   if (t.kind == TAIL_EPS) {
@@ -2439,6 +2498,11 @@ static void set_tail_args(const StepTail& t, KArgs* a) {
   a->x_prev = t.x_prev;
   if (t.kind == TAIL_LMS) {
     a->lms = t.lms.k; a->h_new = t.lms.h_new; a->h_old = t.lms.h_old; a->x0_hist = t.lms.x0_hist; a->x0_all = t.lms.x0_all;
+  } else if (t.kind == TAIL_VLMS) {
+    a->lms = t.lms.k; a->h_new = t.lms.h_new; a->h_old = t.lms.h_old; a->x0_hist = t.lms.x0_hist; a->x0_all = t.lms.x0_all;
+    a->vp = t.vp.k; a->v_uncond = t.vp.v_uncond;
+    a->known = t.blend.known; a->noise = t.blend.noise; a->inj_frames = t.blend.frames; a->inj_mel = t.blend.mel;
+    a->p_coef1 = t.blend.c_known; a->p_coef2 = t.blend.c_noise; a->seed = t.blend.seed; a->seeds = t.blend.seeds; a->step = t.blend.step;
   } else if (t.kind == TAIL_VPRED) {
     a->vp = t.vp.k; a->v_uncond = t.vp.v_uncond;
   } else if (t.kind == TAIL_DDPM) {
@@ -2458,6 +2522,7 @@ static int with_tail(int kind, F&& f) {
     case TAIL_LMS: return f(std::integral_constant<int, TAIL_LMS>{});
     case TAIL_DDPM: return f(std::integral_constant<int, TAIL_DDPM>{});
     case TAIL_VPRED: return f(std::integral_constant<int, TAIL_VPRED>{});
+    case TAIL_VLMS: return f(std::integral_constant<int, TAIL_VLMS>{});
     default: return f(std::integral_constant<int, TAIL_DDIM>{});
   }
 }
@@ -2466,7 +2531,7 @@ static int with_tail(int kind, F&& f) {
 // ... for every kind (the hipFuncSetAttribute lists)
 template <class F>
 static int for_each_tail(F&& f) {
-  for (int kind : {TAIL_QKV, TAIL_EPS, TAIL_DDIM, TAIL_DDPM, TAIL_LMS, TAIL_VPRED}) TRY_G(with_tail(kind, f));
+  for (int kind : {TAIL_QKV, TAIL_EPS, TAIL_DDIM, TAIL_DDPM, TAIL_LMS, TAIL_VPRED, TAIL_VLMS}) TRY_G(with_tail(kind, f));
   return EDTTS_OK;
 }
 // per-utterance frame / token counts of a (sub-)batch: device int64 [B] each, or null (edtts_*_len)
@@ -3366,6 +3431,88 @@ int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* wo
     if (known_mel) {
       inject(1.0f, 0.0f, 0);  // final force (inference_pipeline.py:135-136)
       LAUNCH_CHECK("k_inpaint_inject");
+    }
+  });
+  return EDTTS_OK;
+}
+
+int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T,
+                                       int S, const float* sem_features, const float* zero_features, float* x, int num_steps,
+                                       const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                                       int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                                       const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, float* hist, float* x0_all,
+                                       void* stream) {
+  const SettingsScope settings;
+  Layout lo;
+  TRY(make_layout(dims, &lo));
+  if (!packed || !workspace || !sem_features || !x || !t_all || !step_all || !coef_host || !hist) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if (num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", num_steps);
+  const bool guided = cfg_scale != 1.0f;
+  if (guided && (!workspace_uncond || !zero_features || !v_uncond)) return fail(EDTTS_ERR_ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond");
+  if (known_mel && (overlap_len < 1 || overlap_len > T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", overlap_len, T);
+  TRY(check_shapes(lo, B, T, S));
+  for (int i = 0; i < num_steps; ++i) {  // (the multistep sampler's own limit: a step cannot look further back than the steps before it)
+    const int mode = (int)coef_host[8 * i];
+    if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const float* blob = (const float*)packed;
+  float* wsb = (float*)workspace;
+  float* wsu = (float*)workspace_uncond;
+  Workspace ws;
+  make_workspace(lo, B, T, S, num_steps, &ws);
+  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st, known_mel ? overlap_len : 1));
+  TRY(launch_cond(lo, blob, t_all, step_all, nullptr, num_steps, wsb + ws.cond, wsb, st));
+  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  const size_t per = (size_t)B * T * lo.MEL, per_k = (size_t)B * overlap_len * lo.MEL;
+  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
+  CallCtx cu = c;  // the unconditional pass: its own context cache and activations (workspace_uncond)
+  cu.wsb = wsu;
+  // the tails blend whole float4s; a shape whose known block is not made of them (generic path, n_mels % 4 != 0) goes through the
+  // generic path's per-element tail, and step 0's blend through k_inpaint_inject1
+  const bool inject_vec = ((size_t)overlap_len * lo.MEL) % 4 == 0 && ((size_t)T * lo.MEL) % 4 == 0;
+  // q_sample's scalars of step i are in its coefficient row: p0 = sqrt_ab[t_i], p1 = -sqrt_1mab[t_i] (v-prediction rows)
+  auto c_known = [&](int i) { return coef_host[8 * i + 1]; };
+  auto c_noise = [&](int i) { return -coef_host[8 * i + 2]; };
+  EDTTS_DISPATCH(lo, {
+    TRY(set_attrs_once<LN>());
+    TRY(LN::ctx(c, nullptr, sem_features));
+    if (guided) TRY(LN::ctx(cu, nullptr, zero_features));
+    if (known_mel) {  // step 0's q_sample of the known frames; every later one is written by the tail of the step before it
+      const size_t n4 = per_k / (inject_vec ? 4 : 1);
+      size_t bx = (n4 + 255) / 256;
+      if (bx > 2048) bx = 2048;
+      hipLaunchKernelGGL(inject_vec ? k_inpaint_inject : k_inpaint_inject1, dim3((unsigned)bx), dim3(256), 0, st, x, known_mel, noise_k, B, T,
+                         overlap_len, lo.MEL, c_known(0), c_noise(0), (unsigned long long)seed, kStreamInpaintStep,
+                         reinterpret_cast<const unsigned long long*>(seeds), t_len);
+      LAUNCH_CHECK("k_inpaint_inject");
+    }
+    for (int i = 0; i < num_steps; ++i) {
+      const float* k = coef_host + 8 * i;
+      StepTail tail;
+      tail.kind = TAIL_VLMS; tail.x_prev = x;
+      LmsStepArgs& ls = tail.lms;
+      ls.k.mode = (int)k[0]; ls.k.p0 = k[1]; ls.k.p1 = k[2]; ls.k.c0 = k[3]; ls.k.c1 = k[4]; ls.k.rinv = k[5]; ls.k.cB = k[6]; ls.k.cC = k[7];
+      // history ring of two slots, as edtts_sample_multistep_len
+      ls.x0_hist = hist + (size_t)(i & 1) * per;
+      ls.h_new = hist + (size_t)((i + 1) & 1) * per;
+      ls.h_old = hist + (size_t)(i & 1) * per;
+      ls.x0_all = x0_all ? x0_all + (size_t)i * per : nullptr;
+      tail.vp.k.cfg = cfg_scale;
+      if (known_mel) {
+        const bool last = i + 1 == num_steps;  // after the last step: the known frames themselves (inference_pipeline.py:135-136)
+        tail.blend = BlendStepArgs{known_mel, (noise_k && !last) ? noise_k + (size_t)(i + 1) * per_k : nullptr, overlap_len, lo.MEL,
+                                   last ? 1.0f : c_known(i + 1), last ? 0.0f : c_noise(i + 1),
+                                   (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(seeds),
+                                   kStreamInpaintStep + (unsigned)(last ? 0 : i + 1)};
+      }
+      if (guided) {
+        StepTail eps_tail;
+        eps_tail.eps = v_uncond;
+        TRY(LN::forward(cu, x, wsb + ws.cond + i * row, 0, eps_tail));
+        tail.vp.v_uncond = v_uncond;
+      }
+      TRY(LN::forward(c, x, wsb + ws.cond + i * row, 0, tail));
     }
   });
   return EDTTS_OK;

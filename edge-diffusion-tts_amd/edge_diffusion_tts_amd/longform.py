@@ -10,6 +10,9 @@ reference's chunk loop (:296-367) as written: per-chunk de-normalisation, exp, c
 window, division by the summed weights (sequential: every chunk is conditioned on the tail of the previous one).
 ``generate_long_batch`` runs that loop for many utterances in lockstep: chunk i of every utterance that has one is refined in ONE
 batched call (per-utterance semantic lengths and seeds), and each utterance's result is bitwise its ``generate_long`` alone.
+``inpaint_dpm_refine`` is the teacher refinement with DPM-Solver++'s multistep update (schedule.py: DPMSolverPP) in place of the
+first-order step -- the sampler the reference builds next to its pipeline and never calls -- as ONE C-ABI call
+(edtts_sample_inpaint_multistep_len); ``generate_long(_batch)(..., solver="dpmpp")`` refines every chunk with it.
 """
 from __future__ import annotations
 
@@ -19,12 +22,30 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import native
-from .schedule import DiffusionSchedule
+from .schedule import DiffusionSchedule, DPMSolverPP
+
+SOLVERS = ("ddim", "dpmpp")
 
 
 def linspace_times(t_start: int, n: int) -> List[int]:
     """torch.linspace(t_start, 0, n + 1).long()[:-1] (inference_pipeline.py:101-102,165-166)."""
     return torch.linspace(t_start, 0, n + 1).long()[:-1].tolist()
+
+
+def strictly_decreasing_times(times: Sequence[int]) -> List[int]:
+    """DPMSolverPP.get_time_steps maps points equally spaced in log-SNR onto table rows.  Near the end of the table the log-SNR falls
+    so fast that several points land on one row (t_start = 999, 15 steps: 999, 999, 999, 998, 998, 997, ...), and a step between two
+    equal times has no log-SNR distance: the reference's own coefficients divide 0 by 0 there.  Each time is therefore capped at one
+    below its predecessor (999, 998, 997, 996, 995, 994, ...): the same number of steps, every one with a distance.  A list that
+    already decreases strictly (t_start = 500; the reference's own max_t = 950 at up to 16 steps) is returned as it is.  ValueError
+    when the table has fewer rows below t_start than steps (the times end at 1)."""
+    out = []
+    for t in times:
+        t = int(t) if not out else min(int(t), out[-1] - 1)
+        if t < 1:
+            raise ValueError(f"{len(times)} steps do not fit between t_start = {int(times[0])} and 1")
+        out.append(t)
+    return out
 
 
 class InpaintSampler:
@@ -42,8 +63,11 @@ class InpaintSampler:
             out += [float(sab[t]), float(s1m[t]), float(torch.sqrt(a)), float(torch.sqrt(1 - a))]
         return out
 
-    def _run(self, x: torch.Tensor, sem_features: torch.Tensor, times: List[int], step_idx: int, known_mel, overlap_len: int,
-             cfg_scale: float, noise_k, seed: int, x_lengths=None, sem_lengths=None, seeds=None) -> torch.Tensor:
+    def _run(self, x: torch.Tensor, sem_features: torch.Tensor, times: List[int], step_idx, known_mel, overlap_len: int,
+             cfg_scale: float, noise_k, seed: int, x_lengths=None, sem_lengths=None, seeds=None, *, lms_rows=None,
+             return_intermediates: bool = False):
+        """One C-ABI call: edtts_sample_inpaint_len, or with ``lms_rows`` (DPMSolverPP.step_coefficients of ``times``)
+        edtts_sample_inpaint_multistep_len.  ``step_idx``: the constant step index, or "index" for 0 .. n-1."""
         dec = self.decoder
         B, T, M = x.shape
         S = sem_features.shape[1]
@@ -62,9 +86,13 @@ class InpaintSampler:
         if cached is None:  # (device copies made once: no H2D copy at call time -> capturable; setdefault: one winner per key)
             # (both are synchronous host-to-device copies, so their contents are there for every stream)
             cached = self._dev_cache.setdefault(key, (torch.tensor(times, dtype=torch.int64, device=dev),
-                                                      torch.tensor([step_idx] * n, dtype=torch.int64, device=dev)))
+                                                      torch.tensor(list(range(n)) if step_idx == "index" else [step_idx] * n,
+                                                                   dtype=torch.int64, device=dev)))
         t_all, s_all = cached
-        cf = (C.c_float * (4 * n))(*self._coefs(times))
+        if lms_rows is None:
+            cf = (C.c_float * (4 * n))(*self._coefs(times))
+        else:
+            cf = (C.c_float * (8 * n))(*[float(v) for row in lms_rows for v in row])
         packed = dec._ensure_packed()
         ws = dec.workspace(B, T, S, n, dev)
         guided = float(cfg_scale) != 1.0
@@ -82,6 +110,18 @@ class InpaintSampler:
         else:
             noise_k = None
         p = native._dev_ptr
+        if lms_rows is not None:
+            hist = torch.empty((2, B, T, M), dtype=torch.float32, device=dev)
+            x0_all = torch.empty((n, B, T, M), dtype=torch.float32, device=dev) if return_intermediates else None
+            native.lib().edtts_sample_inpaint_multistep_len(
+                C.byref(dec.dims()), packed.data_ptr(), ws.data_ptr(), None if ws_u is None else ws_u.data_ptr(), B, T, S,
+                p(sem_features, torch.float32, "sem_features"), p(zeros, torch.float32, "zeros"), p(x, torch.float32, "x"), n,
+                t_all.data_ptr(), s_all.data_ptr(), cf, p(known_mel, torch.float32, "known_mel"), int(overlap_len),
+                p(noise_k, torch.float32, "noise_k"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(cfg_scale),
+                None if v_u is None else v_u.data_ptr(), p(t_len, torch.int64, "x_lengths"), p(s_len, torch.int64, "sem_lengths"),
+                p(sd, torch.int64, "seeds"), hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), native._stream(dev))
+            native.check_indices(ws)
+            return (x, list(x0_all.unbind(0))) if return_intermediates else x
         native.lib().edtts_sample_inpaint_len(
             C.byref(dec.dims()), packed.data_ptr(), ws.data_ptr(), None if ws_u is None else ws_u.data_ptr(), B, T, S,
             p(sem_features, torch.float32, "sem_features"), p(zeros, torch.float32, "zeros"), p(x, torch.float32, "x"), n,
@@ -123,11 +163,22 @@ class InpaintSampler:
         """inference_pipeline.py:145-196: q_sample(x_coarse, t_start = int(T * strength)) then ``steps`` guided v-prediction steps.
         ``x_lengths`` / ``sem_lengths`` / ``seeds``: as inpaint_student_sample (with ``seeds`` the q_sample noise of row b is the solo
         call's)."""
-        dev = x_coarse.device
+        t_start = self._t_start(strength)
+        x = self._refine_start(x_coarse, t_start, noise, seed, seeds)
+        times = linspace_times(t_start, steps)
+        return self._run(x, sem_features, times, 0, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k, seed,
+                         x_lengths, sem_lengths, seeds)
+
+    def _t_start(self, strength: float) -> int:
         t_start = int(self.cfg.diff_steps * strength)
         if not 0 <= t_start < self.cfg.diff_steps:
             raise IndexError(f"t_start = int(diff_steps * strength) = {t_start} is outside the schedule tables "
                              "(the reference indexes them with it too)")
+        return t_start
+
+    def _refine_start(self, x_coarse, t_start: int, noise, seed: int, seeds) -> torch.Tensor:
+        """q_sample(x_coarse, t_start) with injected, per-row or single-seed noise (inference_pipeline.py:160-163)."""
+        dev = x_coarse.device
         if noise is not None:
             nz = noise.to(dev)
         elif seeds is not None:
@@ -140,10 +191,48 @@ class InpaintSampler:
             cached = self._dev_cache.setdefault(key, (self.schedule._host_t["sqrt_alpha_bar"][t_start].to(dev),
                                                       self.schedule._host_t["sqrt_one_minus_alpha_bar"][t_start].to(dev)))
         sab, s1m = cached
-        x = sab * x_coarse.to(torch.float32) + s1m * nz  # schedule.q_sample (schedule.py:81-84): plain torch on the device
-        times = linspace_times(t_start, steps)
-        return self._run(x, sem_features, times, 0, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k, seed,
-                         x_lengths, sem_lengths, seeds)
+        return sab * x_coarse.to(torch.float32) + s1m * nz  # schedule.q_sample (schedule.py:81-84): plain torch on the device
+
+    def dpm_plan(self, strength: float, steps: int, order: int):
+        """(times, coefficient rows) of inpaint_dpm_refine, host only: DPMSolverPP(order, predict_x0=False).get_time_steps(steps,
+        max_t=t_start), made strictly decreasing where they repeat (strictly_decreasing_times), and the solver's step_coefficients of
+        those times.  ValueError for an order outside 1..3, steps < 1, or more steps than table rows below t_start."""
+        if order not in (1, 2, 3):
+            raise ValueError(f"order must be 1, 2 or 3, got {order!r}")
+        if int(steps) < 1:
+            raise ValueError(f"steps must be >= 1, got {steps}")
+        t_start = self._t_start(strength)
+        if t_start < 1:
+            raise ValueError(f"strength {strength}: t_start = {t_start}, DPM-Solver++ visits times in [1, t_start]")
+        key = ("dpm_plan", t_start, int(steps), order)
+        cached = self._dev_cache.get(key)
+        if cached is None:
+            solver = DPMSolverPP(self.schedule, order=order, predict_x0=False)
+            solver.device = "cpu"  # (the times are host integers here; the device copy is _run's, made once)
+            times = strictly_decreasing_times(solver.get_time_steps(int(steps), max_t=t_start).tolist())
+            cached = self._dev_cache.setdefault(key, (times, solver.step_coefficients(times)))
+        return cached
+
+    @torch.no_grad()
+    def inpaint_dpm_refine(self, x_coarse, sem_features, known_mel=None, overlap_len: int = 0, strength: float = 0.999,
+                           steps: int = 15, order: int = 2, cfg_scale: float = 1.0, *, noise: Optional[torch.Tensor] = None,
+                           noise_k: Optional[torch.Tensor] = None, seed: int = 0, x_lengths: Optional[torch.Tensor] = None,
+                           sem_lengths: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None, step_idx=0,
+                           return_intermediates: bool = False):
+        """inpaint_teacher_refine with DPM-Solver++'s multistep update (schedule.py: DPMSolverPP, v-prediction model) in place of the
+        first-order step: the same start point q_sample(x_coarse, t_start), known-tail injection, guidance, lengths and seeds; the
+        visiting times are DPMSolverPP.get_time_steps(steps, max_t=t_start) (strictly_decreasing_times of them), and each step's x0 = clamp(predict_x0_from_v) feeds the
+        first / second / third_order_update over the x0 history (``order``).  One C-ABI call (edtts_sample_inpaint_multistep_len).
+        ``step_idx``: the constant step index handed to the decoder (0: the long-form pipeline's), or "index" for 0 .. steps-1
+        (DPMSolverPP.sample's convention).  ``return_intermediates``: also return the list of every step's x0."""
+        times, rows = self.dpm_plan(strength, steps, order)
+        if step_idx != "index" and not isinstance(step_idx, int):
+            raise ValueError(f"step_idx must be an int or \"index\", got {step_idx!r}")
+        if known_mel is not None and overlap_len > x_coarse.shape[1]:
+            raise ValueError(f"overlap_len = {overlap_len} exceeds the {x_coarse.shape[1]} frames of x_coarse")
+        x = self._refine_start(x_coarse, self._t_start(strength), noise, seed, seeds)
+        return self._run(x, sem_features, times, step_idx, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k,
+                         seed, x_lengths, sem_lengths, seeds, lms_rows=rows, return_intermediates=return_intermediates)
 
     @staticmethod
     def latent_slices(n_chunks: int, hop_samples: int, chunk_samples: int, sample_rate: int) -> List[tuple]:
@@ -183,7 +272,7 @@ class InpaintSampler:
                       latent_slices: Optional[List[tuple]] = None, hop_length: Optional[int] = None,
                       sample_rate: Optional[int] = None, draws: Optional[List[dict]] = None,
                       chunk_samples: Optional[int] = None, overlap_samples: Optional[int] = None,
-                      total_samples: Optional[int] = None) -> torch.Tensor:
+                      total_samples: Optional[int] = None, solver: str = "ddim", order: int = 2) -> torch.Tensor:
         """The reference's context-aware sliding window (inference_pipeline.py:296-367), statement for statement:
 
             for chunk i (hop = chunk_frames - overlap_frames frames apart):
@@ -215,13 +304,15 @@ class InpaintSampler:
         The chunk loop is sequential by construction (chunk i is conditioned on the tail of chunk i-1).
         This is generate_long_batch of one utterance (same results): every check runs before the first chunk, the messages name
         "utterance 0", and a ``latent_slices`` or ``draws`` list shorter than the chunk count is a ValueError (an IndexError at
-        that chunk before)."""
+        that chunk before).
+        ``solver`` / ``order``: "ddim" is the reference's first-order step (inpaint_teacher_refine); "dpmpp" refines every chunk with
+        inpaint_dpm_refine at that order -- fewer steps for the same trajectory length, everything around the per-chunk call as is."""
         return self.generate_long_batch([sem_features], [total_frames], chunk_frames, overlap_frames, [chunk_stats], seeds=[seed],
                                         strength=strength, steps=steps, cfg_scale=cfg_scale,
                                         latent_slices=None if latent_slices is None else [latent_slices], hop_length=hop_length,
                                         sample_rate=sample_rate, draws=None if draws is None else [draws], chunk_samples=chunk_samples,
                                         overlap_samples=overlap_samples,
-                                        total_samples=None if total_samples is None else [total_samples])[0]
+                                        total_samples=None if total_samples is None else [total_samples], solver=solver, order=order)[0]
 
     def plan_long_batch(self, sem_rows: Sequence[int], total_frames: Sequence[int], chunk_frames: int, overlap_frames: int,
                         chunk_stats: Sequence, seeds: Sequence[int], *, latent_slices=None, hop_length: Optional[int] = None,
@@ -285,7 +376,7 @@ class InpaintSampler:
                             steps: int = 10, cfg_scale: float = 1.0, latent_slices: Optional[Sequence] = None,
                             hop_length: Optional[int] = None, sample_rate: Optional[int] = None, draws: Optional[Sequence] = None,
                             chunk_samples: Optional[int] = None, overlap_samples: Optional[int] = None,
-                            total_samples: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+                            total_samples: Optional[Sequence[int]] = None, solver: str = "ddim", order: int = 2) -> List[torch.Tensor]:
         """generate_long for N utterances at once.  Lists with one entry per utterance: ``sem_features`` ([1, S_n, semantic_dim]),
         ``total_frames``, ``chunk_stats`` (that utterance's per-chunk (mean, std) pairs), ``seeds`` and, optionally,
         ``total_samples``, ``latent_slices`` and ``draws``; the other arguments are generate_long's and shared.  Returns one
@@ -298,8 +389,14 @@ class InpaintSampler:
         a chunk i are a prefix of the batch; their chunk i is ONE inpaint_teacher_refine call of B = that many rows, S = the longest
         of their semantic slices and sem_lengths = each row's own slice length, with per-row seeds seeds[n] + 2 i (q_sample noise)
         and seeds[n] + 2 i + 1 (coarse start noise), each row conditioned on its own previous tail.  Rows whose ``draws`` supply
-        different keys at chunk i (parity runs) go in separate calls.  The stitch is batched tensor arithmetic on an
+        different keys at chunk i (parity runs) go in separate calls.  ``solver="dpmpp"`` makes that call inpaint_dpm_refine at
+        ``order`` (same planning, seeds and stitching).  The stitch is batched tensor arithmetic on an
         [N, n_mels, max(total_frames) + 1000] buffer; all live rows of chunk i start at frame i * (chunk_frames - overlap_frames)."""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        dpm_order = order  # (`order` below is the utterances' order)
+        if solver == "dpmpp":
+            self.dpm_plan(strength, steps, dpm_order)  # (its ValueErrors, before the first chunk)
         N = len(sem_features)
         if N == 0:
             return []
@@ -354,8 +451,13 @@ class InpaintSampler:
                 noise_k = torch.cat([d[j]["noise_k"].to(dev) for j in J], dim=1) if "noise_k" in keys and prev_tail is not None else None
                 known = None if prev_tail is None else pick(prev_tail[:k])
                 sl = None if s_len is None else pick(s_len)
-                xg = self.inpaint_teacher_refine(x_coarse, pick(sem).contiguous(), known, overlap_frames if known is not None else 0,
-                                                 strength, steps, cfg_scale, noise=noise, noise_k=noise_k, sem_lengths=sl, seeds=sd)
+                ov = overlap_frames if known is not None else 0
+                if solver == "dpmpp":
+                    xg = self.inpaint_dpm_refine(x_coarse, pick(sem).contiguous(), known, ov, strength, steps, dpm_order, cfg_scale,
+                                                 noise=noise, noise_k=noise_k, sem_lengths=sl, seeds=sd)
+                else:
+                    xg = self.inpaint_teacher_refine(x_coarse, pick(sem).contiguous(), known, ov, strength, steps, cfg_scale,
+                                                     noise=noise, noise_k=noise_k, sem_lengths=sl, seeds=sd)
                 if whole:
                     x = xg
                 else:

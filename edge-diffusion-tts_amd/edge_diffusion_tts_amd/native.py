@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = (
     "edtts_profile_collect", "edtts_randn", "edtts_index_errors", "edtts_sample_inpaint",
     "edtts_mel_to_spec", "edtts_griffin_lim_scratch_floats", "edtts_griffin_lim", "edtts_set_substreams", "edtts_set_coop", "edtts_dsconv_scratch_floats", "edtts_substreams_for",
     "edtts_decoder_forward_len", "edtts_generate_len", "edtts_sample_ddpm_len", "edtts_sample_multistep_len",
-    "edtts_sample_inpaint_len", "edtts_randn_rows",
+    "edtts_sample_inpaint_len", "edtts_randn_rows", "edtts_sample_inpaint_multistep_len",
     "edtts_sem_packed_bytes", "edtts_sem_num_codes", "edtts_sem_pack", "edtts_sem_encode", "edtts_sem_decode", "edtts_sem_stats",
     "edtts_hubert_frames", "edtts_hubert_packed_bytes", "edtts_hubert_pack", "edtts_hubert_workspace_bytes", "edtts_hubert_forward",
     "edtts_hubert_packed_bytes_dt", "edtts_hubert_pack_dt", "edtts_hubert_workspace_bytes_dt", "edtts_hubert_forward_dt",
@@ -120,6 +120,8 @@ def lib() -> C.CDLL:
                                        vp, C.c_uint64, f32, vp, vp]
     L.edtts_sample_inpaint_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32),
                                            vp, i32, vp, C.c_uint64, f32, vp, vp, vp, vp, vp]
+    L.edtts_sample_inpaint_multistep_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp,
+                                                     C.POINTER(f32), vp, i32, vp, C.c_uint64, f32, vp, vp, vp, vp, vp, vp, vp]
     L.edtts_randn_rows.argtypes = [vp, i32, sz, vp, C.c_uint32, f32, vp]
     L.edtts_sample_multistep.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int64),
                                          C.POINTER(f32), vp, vp, vp, vp]

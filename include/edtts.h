@@ -222,7 +222,8 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
  *     [0x00000, 0x10000)  edtts_randn callers (0 = start noise of generate_mel / sample_ddpm; the host-side long-form sampler
  *                         uses 0x51 start noise, 0x52 q_sample noise of the teacher refinement, 0x53 per-chunk coarse noise)
  *     0x10000 + step      ancestral noise of step `step` inside edtts_sample_ddpm
- *     0x20000 + step      q_sample noise of the known frames at step `step` inside edtts_sample_inpaint
+ *     0x20000 + step      q_sample noise of the known frames at step `step` inside edtts_sample_inpaint and
+ *                         edtts_sample_inpaint_multistep_len (one sampler or the other runs on a seed: the same draws)
  * edtts_randn rejects stream_id >= 0x10000. */
 int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_t elem_offset, float scale, void* stream);
 /* One launch for B rows with a seed each: out [B, n_per_row], row b bitwise what edtts_randn(n_per_row, seeds[b], stream_id, offset 0,
@@ -286,6 +287,32 @@ int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* wo
                              const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
                              int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
                              const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, void* stream);
+
+/* ---- long-form in-painting sampler with the multistep x0-solver update  (inference_pipeline.py:145-196 inpaint_teacher_refine with
+ * the step of schedule.py:440-527 DPMSolverPP.sample in place of its first-order one) ----------------------------------------------
+ * The arguments of edtts_sample_inpaint_len, with coef_host in edtts_sample_multistep's layout, plus that sampler's hist and x0_all.
+ * For step i = 0 .. num_steps-1 (t = t_all[i], step_idx = step_all[i]: constant for the long-form pipeline, i for DPMSolverPP.sample):
+ *     if known_mel:  x[:, :overlap_len] = sqrt_ab[t] * known_mel + sqrt_1mab[t] * noise_i        (q_sample of the previous chunk's tail)
+ *     v = decoder(x, t, sem_features, step_idx)
+ *     if cfg_scale != 1:  v = v_u + cfg_scale * (v - v_u),  v_u = decoder(x, t, zero_features, step_idx)   (classifier-free guidance)
+ *     x0 = clamp(p0*x + p1*v, -3, 3)                          (model_to_x0 of a v-prediction model: p0 = sqrt_ab[t], p1 = -sqrt_1mab[t])
+ *     x  = first / second / third_order_update over x0 and the previous two x0 (mode 1 / 2 / 3, as edtts_sample_multistep)
+ * and finally x[:, :overlap_len] = known_mel.  Guidance combine, x0, update, history and the NEXT step's blend (after the last step:
+ * the final force) are fused into the last transformer layer of the conditional pass; step 0's blend is one small launch.
+ * coef_host: float[num_steps*8] = {mode, p0, p1, c0, c1, rinv, cB, cC} per step (DPMSolverPP(predict_x0=False).step_coefficients);
+ * the blend takes sqrt_ab[t] = p0 and sqrt_1mab[t] = -p1 from it.  mode <= i + 1 (a step cannot use more history than there is).
+ * hist: scratch [2,B,T,n_mels]; x0_all: NULL or [num_steps,B,T,n_mels] (every step's clamped x0).  noise_k [num_steps,B,overlap_len,
+ * n_mels] or NULL -> Philox stream 0x20000 + i keyed by (seed, element) or, with seeds, (seeds[b], element within the row's block):
+ * the draws of edtts_sample_inpaint_len.  Lengths, seeds, guidance buffers and workspaces (cond_rows = num_steps) as there: row b of
+ * a ragged batch is bitwise the call on utterance b alone, frames past T_b come out 0 (in x, hist and x0_all), T_b < overlap_len is
+ * flagged with EDTTS_IDX_LEN.  With known_mel = NULL, cfg_scale = 1 and step_all[i] = i the result is bitwise
+ * edtts_sample_multistep_len's. */
+int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T,
+                                       int S, const float* sem_features, const float* zero_features, float* x, int num_steps,
+                                       const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                                       int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                                       const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, float* hist, float* x0_all,
+                                       void* stream);
 
 /* ---- depthwise-separable Conv1d  (layers/conv.py:25-64, DepthwiseSeparableConv.forward) -----------------
  * Standalone exported layer (named by the north star; the decoder never calls it).

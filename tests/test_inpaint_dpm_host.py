@@ -1,0 +1,150 @@
+"""In-painting with DPM-Solver++ (InpaintSampler.inpaint_dpm_refine, generate_long_batch(solver="dpmpp")), host side: the new C
+symbol, the Python surface, the argument checks that run before any device work, the coefficient rows handed to the library and the
+chunk plan.  No GPU needed."""
+import ctypes
+import inspect
+import os
+import re
+
+import pytest
+import torch
+
+from edge_diffusion_tts_amd import CFG, DPMSolverPP, EdgeDiffusionDecoder, InpaintSampler, native
+from edge_diffusion_tts_amd.schedule import DiffusionSchedule
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOL = "edtts_sample_inpaint_multistep_len"
+
+
+def sampler():
+    cfg = CFG(device="cpu")
+    return InpaintSampler(cfg, DiffusionSchedule(cfg.diff_steps), EdgeDiffusionDecoder(cfg)), cfg
+
+
+def test_library_exports_the_entry_point():
+    assert SYMBOL in native.EXPORTED_SYMBOLS
+    lib = ctypes.CDLL(native.LIB_PATH)  # (dlopen only: no device call)
+    assert getattr(lib, SYMBOL) is not None
+    header = open(os.path.join(REPO, "include", "edtts.h")).read()
+    m = re.search(r"\bint\s+" + SYMBOL + r"\s*\(([^)]*)\)", header)
+    assert m, "include/edtts.h does not declare it"
+    # the arguments of edtts_sample_inpaint_len (24, the stream last) with hist and x0_all in front of the stream
+    params = [p.strip() for p in m.group(1).split(",")]
+    assert len(params) == 26
+    assert params[-3:] == ["float* hist", "float* x0_all", "void* stream"]
+    ref = re.search(r"\bint\s+edtts_sample_inpaint_len\s*\(([^)]*)\)", header).group(1)
+    assert [re.sub(r"\s+", " ", p.strip()) for p in ref.split(",")][:-1] == [re.sub(r"\s+", " ", p) for p in params[:-3]]
+    assert lib.edtts_version() == 400
+
+
+def test_python_surface():
+    sig = inspect.signature(InpaintSampler.inpaint_dpm_refine)
+    names = list(sig.parameters)
+    assert names[:9] == ["self", "x_coarse", "sem_features", "known_mel", "overlap_len", "strength", "steps", "order", "cfg_scale"]
+    d = {k: v.default for k, v in sig.parameters.items()}
+    assert (d["strength"], d["steps"], d["order"], d["cfg_scale"], d["step_idx"], d["return_intermediates"]) == (0.999, 15, 2, 1.0, 0, False)
+    for k in ("noise", "noise_k", "seed", "x_lengths", "sem_lengths", "seeds", "step_idx", "return_intermediates"):
+        assert sig.parameters[k].kind is inspect.Parameter.KEYWORD_ONLY, k
+    for fn in (InpaintSampler.generate_long, InpaintSampler.generate_long_batch):
+        p = inspect.signature(fn).parameters
+        assert p["solver"].default == "ddim" and p["order"].default == 2
+        assert p["solver"].kind is inspect.Parameter.KEYWORD_ONLY
+
+
+def test_wrong_arguments_raise_before_any_device_work():
+    smp, cfg = sampler()
+    x = torch.zeros(2, 41, cfg.n_mels)
+    f = torch.zeros(2, 20, cfg.semantic_dim)
+    known = torch.zeros(2, 5, cfg.n_mels)
+    for order in (0, 4, 2.5):
+        with pytest.raises(ValueError, match="order"):
+            smp.inpaint_dpm_refine(x, f, known, 5, 0.5, 5, order, noise=x)
+    for steps in (0, -3):
+        with pytest.raises(ValueError, match="steps"):
+            smp.inpaint_dpm_refine(x, f, known, 5, 0.5, steps, 2, noise=x)
+    with pytest.raises(ValueError, match="overlap_len = 42"):
+        smp.inpaint_dpm_refine(x, f, torch.zeros(2, 42, cfg.n_mels), 42, 0.5, 5, 2, noise=x)
+    with pytest.raises(ValueError, match="step_idx"):
+        smp.inpaint_dpm_refine(x, f, known, 5, 0.5, 5, 2, noise=x, step_idx="steps")
+    # lengths: as inpaint_teacher_refine (a row shorter than the overlap is what the call on that row alone would refuse)
+    with pytest.raises(ValueError, match="overlap_len = 5"):
+        smp.inpaint_dpm_refine(x, f, known, 5, 0.5, 5, 2, noise=x, x_lengths=torch.tensor([41, 4]))
+    with pytest.raises(ValueError, match="sem_lengths"):
+        smp.inpaint_dpm_refine(x, f, known, 5, 0.5, 5, 2, noise=x, sem_lengths=torch.tensor([0, 20]))
+    with pytest.raises(IndexError):  # t_start = 1000: outside the tables, as inpaint_teacher_refine
+        smp.inpaint_dpm_refine(x, f, None, 0, 1.0, 5, 2, noise=x)
+    with pytest.raises(TypeError):  # keyword-only
+        smp.inpaint_dpm_refine(x, f, known, 5, 0.5, 5, 2, 1.0, None)
+
+
+def test_generate_long_batch_checks_solver_and_order():
+    smp, cfg = sampler()
+    feats = [torch.zeros(1, 80, cfg.semantic_dim)]
+    stats = [[(0.0, 1.0)] * smp.chunk_plan(100, 48, 12, 160)[0]]
+    kw = dict(seeds=[1], hop_length=160, sample_rate=8000)
+    with pytest.raises(ValueError, match="solver"):
+        smp.generate_long_batch(feats, [100], 48, 12, stats, solver="euler", **kw)
+    with pytest.raises(ValueError, match="solver"):
+        smp.generate_long(feats[0], 100, 48, 12, stats[0], solver="dpm", hop_length=160, sample_rate=8000)
+    with pytest.raises(ValueError, match="order"):
+        smp.generate_long_batch(feats, [100], 48, 12, stats, solver="dpmpp", order=4, **kw)
+    with pytest.raises(ValueError, match="steps"):
+        smp.generate_long_batch(feats, [100], 48, 12, stats, solver="dpmpp", steps=0, **kw)
+    # the planner's own errors are kept with either solver
+    for solver in ("ddim", "dpmpp"):
+        with pytest.raises(ValueError, match="chunk_stats must hold"):
+            smp.generate_long_batch(feats, [100], 48, 12, [stats[0][:-1]], solver=solver, **kw)
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("strength", [0.999, 0.5])
+def test_coefficient_rows_are_step_coefficients(order, strength):
+    smp, cfg = sampler()
+    for steps in (5, 15):
+        times, rows = smp.dpm_plan(strength, steps, order)
+        solver = DPMSolverPP(smp.schedule, order=order, predict_x0=False)
+        t_start = int(cfg.diff_steps * strength)
+        grid = solver.get_time_steps(steps, max_t=t_start).tolist()
+        # the solver's own times; where its log-SNR grid puts several points on one table row (t_start = 999), each one row lower
+        # than its predecessor, so that no step has a zero log-SNR distance (longform.strictly_decreasing_times)
+        want_t = []
+        for t in grid:
+            want_t.append(t if not want_t else min(t, want_t[-1] - 1))
+        if (strength, steps) == (0.999, 15):
+            assert grid[:5] == [999, 999, 999, 998, 998] and want_t[:5] == [999, 998, 997, 996, 995]  # the reason
+        else:
+            assert want_t == grid
+        assert times == want_t and len(times) == steps and times[0] == t_start and all(a > b for a, b in zip(times, times[1:]))
+        assert min(times) >= 1
+        want = solver.step_coefficients(want_t)
+        assert rows == want  # (python floats of fp32 values: equal, not close)
+        assert [int(r[0]) for r in rows] == [min(i + 1, order) for i in range(steps)]
+        sab, s1m = smp.schedule._host_t["sqrt_alpha_bar"], smp.schedule._host_t["sqrt_one_minus_alpha_bar"]
+        for t, r in zip(times, rows):  # what the library's blend takes from a row: q_sample's two scalars at that step's time
+            assert r[1] == float(sab[t]) and -r[2] == float(s1m[t])
+            assert all(v == v and abs(v) != float("inf") for v in r)
+
+
+def test_plan_is_the_same_for_both_solvers():
+    """The solver changes the per-chunk call only: plan_long_batch has no solver argument, and generate_long_batch reaches it with
+    the same arguments either way."""
+    smp, cfg = sampler()
+    assert "solver" not in inspect.signature(InpaintSampler.plan_long_batch).parameters
+    rows, totals = (80, 50, 128), (100, 60, 150)
+    stats = [[(0.0, 1.0)] * smp.chunk_plan(t, 48, 12, 160)[0] for t in totals]
+    seen = {}
+
+    class Stop(Exception):
+        pass
+
+    real = smp.plan_long_batch
+    for solver in ("ddim", "dpmpp"):
+        def spy(*a, **k):
+            seen[solver] = (a, k, real(*a, **k))
+            raise Stop
+        smp.plan_long_batch = spy
+        with pytest.raises(Stop):
+            smp.generate_long_batch([torch.zeros(1, r, cfg.semantic_dim) for r in rows], list(totals), 48, 12, stats, seeds=[1, 2, 3],
+                                    hop_length=160, sample_rate=8000, solver=solver, steps=5)
+    assert seen["ddim"][0] == seen["dpmpp"][0] and seen["ddim"][1] == seen["dpmpp"][1]
+    assert seen["ddim"][2] == seen["dpmpp"][2] and [p["n_chunks"] for p in seen["ddim"][2]] == [smp.chunk_plan(t, 48, 12, 160)[0] for t in totals]
