@@ -11,6 +11,7 @@
 //   k_gen_attn<DT>     flash-style attention for 16 queries x one head per wave: S^T = K Q^T and O^T = V^T P^T on MFMA, fp32 online
 //                      softmax (exp2 domain), head_dim padded to DT 16-wide tiles; self-attention visits only the band |j - i| <= window
 //   k_gen_embed        context = token_emb[sem_idx] + context_pos_emb (clamped indices set EDTTS_IDX_SEM)
+//                      (the training forward, edtts_generic_bwd.h, also has it store each query's log-sum-exp)
 //   k_gen_tail<TAIL>   the sampler updates of the fused tails, elementwise: tail_apply (vector path) or the same helpers per element
 //
 // Activations are plain row-major [rows][features] fp32 in the workspace; weights are the state-dict's own [N][K] matrices.
@@ -215,6 +216,7 @@ struct AttnArgs {
   float scale;      // log2(e) / sqrt(head_dim): scores in the exp2 domain
   const int64_t *q_len, *k_len;  // per-utterance query / key counts [B] (edtts_*_len), or null: Tq / Tk for all
   int q_dbl, k_dbl;              // ... given as token counts of which they are twice (see utt_len)
+  float* lse;                    // training forward: log-sum-exp (exp2 domain) per [utterance][head][query], or null
 };
 // One wave = 16 queries of one (utterance, head).  S^T tile (16 keys x 16 queries) = K Q^T: lane (g, i) holds the scores of query i
 // against keys 4g + r.  P^T then is the B operand of O^T += V^T P^T as it stands when MFMA step s contracts keys {4g + s}: the V^T
@@ -298,6 +300,7 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
     }
   }
   if (!qok) return;
+  if (a.lse != nullptr && g == 0) a.lse[((size_t)b * gridDim.y + hd) * a.Tq + qi] = m + log2f(l);
   const float inv = 1.0f / l;
   float* orow = a.o + (size_t)(b * a.Tq + qi) * a.ldo + hd * a.DH;
 #pragma unroll
@@ -452,9 +455,9 @@ struct GenericLauncher {
     return EDTTS_OK;
   }
   static int attn(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, float* o,
-                  int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl) {
+                  int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl, float* lse = nullptr) {
     edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
-                          (int)q_dbl, (int)k_dbl};
+                          (int)q_dbl, (int)k_dbl, lse};
     const dim3 grid((Tq + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
 #define EDTTS_GEN_ATTN(DT) case DT: hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a); break

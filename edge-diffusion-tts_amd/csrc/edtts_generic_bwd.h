@@ -1,0 +1,876 @@
+// edtts_generic_bwd.h -- training on the generic fp32 decoder path: a forward that keeps a tape, and its backward (included by
+// edtts_kernels.hip).
+//
+// The generic forward (edtts_generic.h) is a chain of plain row-major steps; this header differentiates it step by step.  Every
+// contraction runs on v_mfma_f32_16x16x4_f32, every reduction has a fixed order (no float atomics): a sum over rows is cut into
+// slabs whose partial results are added in slab order, and a scatter-add has one owner per destination row.
+//
+//   k_bwd_gemm<ACC>       C[M,N] (+)= sum_k A(m,k) B(n,k), both operands with run-time strides, through LDS tiles like k_gen_gemm:
+//                         dX = dY W (A = dY, B = W read column-wise) and dW = dY^T X (A = dY^T, B = X^T; grid.z cuts the row
+//                         sum into slabs of dw_slab_rows(M) rows, one partial [N][K] each)
+//   k_bwd_slabsum         out[j] (+)= sum_s part[s][j], s ascending: the second half of every cut reduction
+//   k_bwd_colsum          bias gradients: column sums of dY per slab of kColRows rows
+//   k_bwd_norm_rows<MODE> dx of RMSNorm x gain (x AdaLN modulation) / LayerNorm, one wave per row; leaves rstd (and the mean)
+//   k_bwd_norm_cols<MODE> per chunk of kNormChunk rows of one utterance: partial gain, (dscale | dshift) or LayerNorm-bias sums
+//   k_bwd_swiglu          value / gate pre-activations -> their gradients, in place
+//   k_bwd_attn_delta      delta = rowsum(dO o O) per (utterance, head, query)
+//   k_bwd_attn_dq<DT>     owns 16 queries of one head: recomputes P from the tape's log-sum-exp, dQ = scale dS K
+//   k_bwd_attn_dkv<DT>    owns 16 keys of one head: dV = P^T dO, dK = scale dS^T Q over the query tiles that meet the band
+//   k_bwd_scatter_rows    embedding gradients: one block owns a table row and adds its positions in position order
+//   k_bwd_time_emb, k_bwd_gelu, k_bwd_gelu_grad   the time MLP's elementwise pieces (its contractions reuse k_bwd_gemm)
+#pragma once
+
+namespace edtts_bwd {
+using edtts_gen::wave_allsum;
+
+constexpr int kDwSlabRows = 256;  // smallest slab of the dW row sum
+constexpr int kColRows = 256;     // rows per partial of a bias gradient
+constexpr int kNormChunk = 64;    // rows per partial of a norm's column sums (chunks never straddle two utterances)
+// rows per dW slab: at most 32 slabs however long the batch
+static int dw_slab_rows(int M) {
+  const int r = ((M + 31) / 32 + 63) / 64 * 64;
+  return r > kDwSlabRows ? r : kDwSlabRows;
+}
+
+struct BGemmArgs {
+  const float *A, *B;
+  float* C;
+  int M, N, K;             // C[m][n] = sum_k A[m sam + k sak] B[n sbn + k sbk]
+  long sam, sak, sbn, sbk;
+  int ldc, kslab;          // block z contracts k in [z kslab, (z + 1) kslab) into C + z cslab   (kslab % 16 == 0)
+  size_t cslab;
+  int va, vb, vc;          // 16-byte loads along k (unit k stride, aligned rows, K % 4 == 0) / 16-byte stores
+};
+template <int ACC>
+__global__ __launch_bounds__(256) void k_bwd_gemm(BGemmArgs a) {
+  using namespace edtts_gen;
+  __shared__ float xs[kGBM][kGLd];
+  __shared__ float ws[kGBN][kGLd];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fq = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.x * kGBM, n0 = blockIdx.y * kGBN;
+  const int kbeg = blockIdx.z * a.kslab;
+  const int kend = kbeg + a.kslab < a.K ? kbeg + a.kslab : a.K;
+  // loaders: an operand with unit k stride is read four k per thread (row = tid / 4); one with unit row stride one row per lane
+  // (row = tid % 64), so that neighbouring threads read neighbouring addresses either way
+  const int alr = a.sak == 1 ? tid >> 2 : tid & 63, alk = a.sak == 1 ? 4 * (tid & 3) : 4 * (tid >> 6);
+  const int blr = a.sbk == 1 ? tid >> 2 : tid & 63, blk = a.sbk == 1 ? 4 * (tid & 3) : 4 * (tid >> 6);
+  const bool aok = m0 + alr < a.M, bok = n0 + blr < a.N;
+  const float* ap = a.A + (size_t)(aok ? m0 + alr : 0) * a.sam;
+  const float* bp = a.B + (size_t)(bok ? n0 + blr : 0) * a.sbn;
+  const int wn0 = 32 * (w & 1), wn1 = wn0 + 16, wm = 32 * (w >> 1);
+  f4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = splat(0.f);
+  for (int k0 = kbeg; k0 < kend; k0 += kGBK) {
+    f4 xv = splat(0.f), wv = splat(0.f);
+    const int ka = k0 + alk, kb = k0 + blk;
+    if (a.va) {
+      if (aok && ka < kend) xv = ldg4(ap + ka);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xv[r] = (aok && ka + r < kend) ? ap[(size_t)(ka + r) * a.sak] : 0.f;
+    }
+    if (a.vb) {
+      if (bok && kb < kend) wv = ldg4(bp + kb);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) wv[r] = (bok && kb + r < kend) ? bp[(size_t)(kb + r) * a.sbk] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      xs[alr][alk + r] = xv[r];
+      ws[blr][blk + r] = wv[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < kGBK / 4; ++s) {
+      const int kk = 4 * s + g;
+      const float a0 = ws[wn0 + fq][kk], a1 = ws[wn1 + fq][kk];
+      const float b0 = xs[wm + fq][kk], b1 = xs[wm + 16 + fq][kk];
+      acc[0][0] = EDTTS_MFMA(a0, b0, acc[0][0]);
+      acc[0][1] = EDTTS_MFMA(a0, b1, acc[0][1]);
+      acc[1][0] = EDTTS_MFMA(a1, b0, acc[1][0]);
+      acc[1][1] = EDTTS_MFMA(a1, b1, acc[1][1]);
+    }
+  }
+  // acc[t][u] lane (g, fq) holds C[m = m0 + wm + 16u + fq][n = n0 + (wn0 | wn1) + 4g + r]
+  float* cb = a.C + (size_t)blockIdx.z * a.cslab;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int n = n0 + (t ? wn1 : wn0) + 4 * g;
+    if (n >= a.N) continue;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int m = m0 + wm + 16 * u + fq;
+      if (m >= a.M) continue;
+      float* cp = cb + (size_t)m * a.ldc + n;
+      if (a.vc && n + 3 < a.N) {
+        stg4(cp, ACC ? ldg4(cp) + acc[t][u] : acc[t][u]);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < a.N) cp[r] = ACC ? cp[r] + acc[t][u][r] : acc[t][u][r];
+      }
+    }
+  }
+}
+
+// out[y ostride + j] (+)= sum_{s < ns} part[(y ns + s) pstride + j], s ascending
+__global__ __launch_bounds__(256) void k_bwd_slabsum(const float* part, float* out, size_t n, int ns, size_t pstride, size_t ostride, int acc) {
+  const int y = blockIdx.y;
+  for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
+    const float* p = part + (size_t)y * ns * pstride + j;
+    float s = p[0];
+    for (int i = 1; i < ns; ++i) s += p[(size_t)i * pstride];
+    float* o = out + (size_t)y * ostride + j;
+    *o = acc ? *o + s : s;
+  }
+}
+
+// part[slab][N]: column sums of rows [slab kColRows, ...) of Y[M][ld]
+__global__ __launch_bounds__(256) void k_bwd_colsum(const float* Y, int ld, int M, int N, float* part) {
+  __shared__ float sm[4][64];
+  const int c = threadIdx.x & 63, rg = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
+  const int r0 = blockIdx.y * kColRows, r1 = r0 + kColRows < M ? r0 + kColRows : M;
+  float s = 0.f;
+  if (col < N)
+    for (int r = r0 + rg; r < r1; r += 4) s += Y[(size_t)r * ld + col];
+  sm[rg][c] = s;
+  __syncthreads();
+  if (rg == 0 && col < N) part[(size_t)blockIdx.y * N + col] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
+}
+
+// ---- row norms ---------------------------------------------------------------------------------------------------------------
+struct NormBwdArgs {
+  const float *x, *dy;
+  float* dx;
+  const float* w;
+  const float* mod;  // AdaLN rows (1 + scale | shift) per utterance, or null
+  float* stat;       // [rows] rstd (RMSNorm) / [rows][2] mean, rstd (LayerNorm)
+  float* part;       // k_bwd_norm_cols: [chunk][3][W]
+  int rows, W, rows_per_b, mod_bstride, acc;
+  float eps;
+};
+template <int MODE>
+__global__ __launch_bounds__(256) void k_bwd_norm_rows(NormBwdArgs a) {
+  using namespace edtts_gen;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.rows) return;
+  const float* x = a.x + (size_t)row * a.W;
+  const float* dy = a.dy + (size_t)row * a.W;
+  float* dx = a.dx + (size_t)row * a.W;
+  if (MODE == NORM_LAYER) {  // y = (x - mu) rs w + b
+    float s = 0.f;
+    for (int j = lane; j < a.W; j += 64) s += x[j];
+    const float mu = wave_allsum(s) / (float)a.W;
+    float q = 0.f;
+    for (int j = lane; j < a.W; j += 64) {
+      const float d = x[j] - mu;
+      q += d * d;
+    }
+    const float rs = rsqrtf(wave_allsum(q) / (float)a.W + a.eps);
+    float s1 = 0.f, s2 = 0.f;
+    for (int j = lane; j < a.W; j += 64) {
+      const float gx = dy[j] * a.w[j];
+      s1 += gx;
+      s2 += gx * ((x[j] - mu) * rs);
+    }
+    const float m1 = wave_allsum(s1) / (float)a.W, m2 = wave_allsum(s2) / (float)a.W;
+    for (int j = lane; j < a.W; j += 64) {
+      const float v = rs * (dy[j] * a.w[j] - m1 - (x[j] - mu) * rs * m2);
+      dx[j] = a.acc ? dx[j] + v : v;
+    }
+    if (lane == 0) {
+      a.stat[2 * (size_t)row] = mu;
+      a.stat[2 * (size_t)row + 1] = rs;
+    }
+  } else {  // y = x rs w (1 + scale) + shift
+    float q = 0.f;
+    for (int j = lane; j < a.W; j += 64) q += x[j] * x[j];
+    const float rs = rsqrtf(wave_allsum(q) / (float)a.W + a.eps);
+    const float* md = a.mod ? a.mod + (size_t)(row / a.rows_per_b) * a.mod_bstride : nullptr;
+    float c = 0.f;
+    for (int j = lane; j < a.W; j += 64) {
+      const float gn = dy[j] * a.w[j] * (md ? md[j] : 1.0f);
+      c += gn * (x[j] * rs);
+    }
+    const float mean = wave_allsum(c) / (float)a.W;
+    for (int j = lane; j < a.W; j += 64) {
+      const float gn = dy[j] * a.w[j] * (md ? md[j] : 1.0f);
+      const float v = rs * (gn - x[j] * rs * mean);
+      dx[j] = a.acc ? dx[j] + v : v;
+    }
+    if (lane == 0) a.stat[row] = rs;
+  }
+}
+// grid (ceil(W / 64), B * chunks per utterance); partial 0: gain gradient, 1: dscale (LayerNorm: bias gradient), 2: dshift
+template <int MODE>
+__global__ __launch_bounds__(256) void k_bwd_norm_cols(NormBwdArgs a) {
+  using namespace edtts_gen;
+  __shared__ float sm[3][4][64];
+  const int c = threadIdx.x & 63, rg = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
+  const int cpb = (a.rows_per_b + kNormChunk - 1) / kNormChunk;
+  const int b = blockIdx.y / cpb, ch = blockIdx.y - b * cpb;
+  const int r0 = b * a.rows_per_b + ch * kNormChunk;
+  const int e = (b + 1) * a.rows_per_b, r1 = r0 + kNormChunk < e ? r0 + kNormChunk : e;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  if (col < a.W) {
+    const float wj = a.w[col];
+    const float* md = a.mod ? a.mod + (size_t)b * a.mod_bstride : nullptr;
+    const float sc = md ? md[col] : 1.0f;
+    for (int r = r0 + rg; r < r1; r += 4) {
+      const float xv = a.x[(size_t)r * a.W + col], d = a.dy[(size_t)r * a.W + col];
+      if (MODE == NORM_LAYER) {
+        s0 += d * ((xv - a.stat[2 * (size_t)r]) * a.stat[2 * (size_t)r + 1]);
+        s1 += d;
+      } else {
+        const float n = xv * a.stat[r];
+        s0 += d * sc * n;
+        s1 += d * (n * wj);
+        s2 += d;
+      }
+    }
+  }
+  sm[0][rg][c] = s0; sm[1][rg][c] = s1; sm[2][rg][c] = s2;
+  __syncthreads();
+  if (rg == 0 && col < a.W) {
+    float* p = a.part + (size_t)blockIdx.y * 3 * a.W + col;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[(size_t)i * a.W] = ((sm[i][0][c] + sm[i][1][c]) + sm[i][2][c]) + sm[i][3][c];
+  }
+}
+
+// ---- SwiGLU ------------------------------------------------------------------------------------------------------------------
+// u [M][2 FH] holds value | gate pre-activations and receives their gradients; da [M][FH] is the gradient of value * silu(gate)
+__global__ __launch_bounds__(256) void k_bwd_swiglu(float* u, const float* da, size_t M, int FH) {
+  const size_t n = M * FH;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / FH;
+    const int c = (int)(i - row * FH);
+    float* ur = u + row * 2 * FH;
+    const float v = ur[c], gt = ur[FH + c], d = da[i];
+    const float sg = 1.0f / (1.0f + expf(-gt));
+    ur[c] = d * (gt * sg);
+    ur[FH + c] = d * v * (sg * (1.0f + gt * (1.0f - sg)));
+  }
+}
+
+// ---- attention ---------------------------------------------------------------------------------------------------------------
+// delta[(b HEADS + hd) Tq + i] = sum_d dO[row][hd DH + d] O[row][hd DH + d]   (row = b Tq + i), d ascending
+__global__ __launch_bounds__(256) void k_bwd_attn_delta(const float* o, const float* dO, float* delta, int B, int Tq, int HEADS, int DH, int ld) {
+  const size_t n = (size_t)B * HEADS * Tq;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t bh = i / Tq;
+    const int q = (int)(i - bh * Tq), hd = (int)(bh % HEADS);
+    const size_t row = (bh / HEADS) * Tq + q;
+    const float* op = o + row * ld + (size_t)hd * DH;
+    const float* dp = dO + row * ld + (size_t)hd * DH;
+    float s = 0.f;
+    for (int d = 0; d < DH; ++d) s += op[d] * dp[d];
+    delta[i] = s;
+  }
+}
+struct AttnBwdArgs {
+  const float *q, *k, *v, *dO;  // rows b Tq + i (q, dO) / b Tk + j (k, v), feature head * DH + d
+  const float *lse, *delta;     // [(b HEADS + head) Tq + i]; lse in the exp2 domain
+  float *dq, *dk, *dv;
+  int ldq, ldkv, ldo, lddq, lddkv, Tq, Tk, DH, window;
+  float scale, scale_nat;       // log2(e) / sqrt(head_dim) (scores as the forward forms them), 1 / sqrt(head_dim)
+};
+// One wave = 16 queries of one (utterance, head), laid out as k_gen_attn: S^T = K Q^T and dP^T = V dO^T tiles hold (key 4g + r,
+// query fq) on lane (g, fq); dS^T is then the B operand of dQ^T += K^T dS^T as P^T is of O^T += V^T P^T in the forward.
+template <int DT>
+__global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
+  const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
+  const int qi = q0 + fq;
+  const bool qok = qi < a.Tq;
+  const size_t qr = (size_t)b * a.Tq + (qok ? qi : 0);
+  const float* qrow = a.q + qr * a.ldq + hd * a.DH;
+  const float* drow = a.dO + qr * a.ldo + hd * a.DH;
+  float qv[4 * DT], dov[4 * DT];
+#pragma unroll
+  for (int s = 0; s < 4 * DT; ++s) {
+    const int d = 4 * s + g;
+    const bool ok = qok && d < a.DH;
+    qv[s] = ok ? qrow[d] * a.scale : 0.f;
+    dov[s] = ok ? drow[d] : 0.f;
+  }
+  const size_t si = ((size_t)b * gridDim.y + hd) * a.Tq + (qok ? qi : 0);
+  const float ls = a.lse[si], dl = a.delta[si];
+  f4 acc[DT];
+#pragma unroll
+  for (int t = 0; t < DT; ++t) acc[t] = splat(0.f);
+  int lo = 0, hi = a.Tk;
+  if (a.window >= 0) {
+    lo = q0 - a.window > 0 ? q0 - a.window : 0;
+    const int e = q0 + 16 + a.window;
+    hi = e < a.Tk ? e : a.Tk;
+  }
+  const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  for (int j0 = lo; j0 < hi; j0 += 16) {
+    const int kj = j0 + fq;
+    const bool kok = kj < hi;
+    const float* krow = kb + (size_t)(kok ? kj : 0) * a.ldkv;
+    const float* vrow = vb + (size_t)(kok ? kj : 0) * a.ldkv;
+    f4 sc = splat(0.f), dp = splat(0.f);
+#pragma unroll
+    for (int s = 0; s < 4 * DT; ++s) {
+      const int d = 4 * s + g;
+      const bool ok = kok && d < a.DH;
+      sc = EDTTS_MFMA(ok ? krow[d] : 0.f, qv[s], sc);
+      dp = EDTTS_MFMA(ok ? vrow[d] : 0.f, dov[s], dp);
+    }
+    f4 ds;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = j0 + 4 * g + r;
+      const bool ok = qok && key < hi && (a.window < 0 || (key - qi <= a.window && qi - key <= a.window));
+      const float p = ok ? exp2f(sc[r] - ls) : 0.f;
+      ds[r] = p * (dp[r] - dl);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int key = j0 + 4 * g + s;
+      const float* kr2 = kb + (size_t)(key < hi ? key : 0) * a.ldkv;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const int d = 16 * t + fq;
+        acc[t] = EDTTS_MFMA((key < hi && d < a.DH) ? kr2[d] : 0.f, ds[s], acc[t]);
+      }
+    }
+  }
+  if (!qok) return;
+  float* orow = a.dq + ((size_t)b * a.Tq + qi) * a.lddq + hd * a.DH;
+#pragma unroll
+  for (int t = 0; t < DT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int d = 16 * t + 4 * g + r;  // acc[t] lane (g, i) holds dQ^T[d][i]
+      if (d < a.DH) orow[d] = acc[t][r] * a.scale_nat;
+    }
+}
+// One wave = 16 keys of one (utterance, head).  S = Q K^T and dP = dO V^T tiles hold (query 4g + r, key fq) on lane (g, fq): P and
+// dS are the B operands of dV^T += dO^T P and dK^T += Q^T dS.  Only the query tiles that meet the band are visited.
+template <int DT>
+__global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
+  const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
+  const int k0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
+  const int kj = k0 + fq;
+  const bool kok = kj < a.Tk;
+  const size_t kr = (size_t)b * a.Tk + (kok ? kj : 0);
+  const float* krow = a.k + kr * a.ldkv + hd * a.DH;
+  const float* vrow = a.v + kr * a.ldkv + hd * a.DH;
+  float kv[4 * DT], vv[4 * DT];
+#pragma unroll
+  for (int s = 0; s < 4 * DT; ++s) {
+    const int d = 4 * s + g;
+    const bool ok = kok && d < a.DH;
+    kv[s] = ok ? krow[d] * a.scale : 0.f;
+    vv[s] = ok ? vrow[d] : 0.f;
+  }
+  f4 ak[DT], av[DT];
+#pragma unroll
+  for (int t = 0; t < DT; ++t) ak[t] = av[t] = splat(0.f);
+  int lo = 0, hi = a.Tq;
+  if (a.window >= 0) {
+    lo = k0 - a.window > 0 ? k0 - a.window : 0;
+    const int e = k0 + 16 + a.window;
+    hi = e < a.Tq ? e : a.Tq;
+  }
+  const float* qb = a.q + (size_t)b * a.Tq * a.ldq + hd * a.DH;
+  const float* db = a.dO + (size_t)b * a.Tq * a.ldo + hd * a.DH;
+  const float* lb = a.lse + ((size_t)b * gridDim.y + hd) * a.Tq;
+  const float* eb = a.delta + ((size_t)b * gridDim.y + hd) * a.Tq;
+  for (int i0 = lo; i0 < hi; i0 += 16) {
+    const int qi = i0 + fq;
+    const bool qok = qi < hi;
+    const float* qrow = qb + (size_t)(qok ? qi : 0) * a.ldq;
+    const float* drow = db + (size_t)(qok ? qi : 0) * a.ldo;
+    f4 sc = splat(0.f), dp = splat(0.f);
+#pragma unroll
+    for (int s = 0; s < 4 * DT; ++s) {
+      const int d = 4 * s + g;
+      const bool ok = qok && d < a.DH;
+      sc = EDTTS_MFMA(ok ? qrow[d] : 0.f, kv[s], sc);
+      dp = EDTTS_MFMA(ok ? drow[d] : 0.f, vv[s], dp);
+    }
+    f4 p, ds;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qq = i0 + 4 * g + r;
+      const bool ok = kok && qq < hi && (a.window < 0 || (kj - qq <= a.window && qq - kj <= a.window));
+      const int qs = qq < hi ? qq : 0;
+      p[r] = ok ? exp2f(sc[r] - lb[qs]) : 0.f;
+      ds[r] = p[r] * (dp[r] - eb[qs]);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int qq = i0 + 4 * g + s;
+      const bool ok = qq < hi;
+      const float* qr2 = qb + (size_t)(ok ? qq : 0) * a.ldq;
+      const float* dr2 = db + (size_t)(ok ? qq : 0) * a.ldo;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const int d = 16 * t + fq;
+        const bool okd = ok && d < a.DH;
+        av[t] = EDTTS_MFMA(okd ? dr2[d] : 0.f, p[s], av[t]);
+        ak[t] = EDTTS_MFMA(okd ? qr2[d] : 0.f, ds[s], ak[t]);
+      }
+    }
+  }
+  if (!kok) return;
+  float* okp = a.dk + ((size_t)b * a.Tk + kj) * a.lddkv + hd * a.DH;
+  float* ovp = a.dv + ((size_t)b * a.Tk + kj) * a.lddkv + hd * a.DH;
+#pragma unroll
+  for (int t = 0; t < DT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int d = 16 * t + 4 * g + r;  // lane (g, j) holds dK^T[d][j], dV^T[d][j]
+      if (d < a.DH) {
+        okp[d] = ak[t][r] * a.scale_nat;
+        ovp[d] = av[t][r];
+      }
+    }
+}
+
+// ---- embeddings ----------------------------------------------------------------------------------------------------------------
+// out[row][c] = sum over positions p (ascending) whose index, clamped as the forward clamps it, is row, of src[p][c]: block = row.
+// The block walks the positions 256 at a time; the ones that hit its row are compacted IN POSITION ORDER into LDS (ballot + prefix
+// count) and every column thread adds them in that order, so a chunk without a hit costs one index load per thread.
+__global__ __launch_bounds__(256) void k_bwd_scatter_rows(const int64_t* idx, int n_pos, int n_rows, const float* src, int H, float* out) {
+  __shared__ int list[256];
+  __shared__ int wcnt[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int cg = 0; cg < H; cg += 1024) {  // four columns per thread and pass (one pass up to hidden 1024)
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < n_pos; c0 += 256) {
+      const int p = c0 + tid;
+      bool hit = false;
+      if (p < n_pos) {
+        long tk = (long)idx[p];
+        tk = tk < 0 ? 0 : (tk >= n_rows ? n_rows - 1 : tk);
+        hit = tk == row;
+      }
+      const unsigned long long bal = __ballot(hit);
+      if (lane == 0) wcnt[w] = __popcll(bal);
+      __syncthreads();
+      const int n0 = wcnt[0], n1 = wcnt[1], n2 = wcnt[2], total = n0 + n1 + n2 + wcnt[3];
+      if (total) {  // (the same for every thread of the block)
+        if (hit) list[(w > 0 ? n0 : 0) + (w > 1 ? n1 : 0) + (w > 2 ? n2 : 0) + __popcll(bal & ((1ull << lane) - 1ull))] = p;
+        __syncthreads();
+        for (int i = 0; i < total; ++i) {
+          const float* sp = src + (size_t)list[i] * H;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int c = cg + tid + 256 * j;
+            if (c < H) acc[j] += sp[c];
+          }
+        }
+      }
+      __syncthreads();  // list and wcnt are rewritten by the next chunk
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = cg + tid + 256 * j;
+      if (c < H) out[(size_t)row * H + c] = acc[j];
+    }
+  }
+}
+
+// ---- time MLP ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bwd_time_emb(const int64_t* t, const float* freqs, int rows, int H, float* e) {
+  const int half = H / 2;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < rows * H; i += gridDim.x * blockDim.x) {
+    const int row = i / H, j = i - row * H;
+    const float arg = (float)t[row] * freqs[j < half ? j : j - half];  // as k_cond_mlp
+    e[i] = j < half ? sinf(arg) : cosf(arg);
+  }
+}
+// a1 [rows][H] += bias (the pre-activation, kept); u = GELU(a1)
+__global__ __launch_bounds__(256) void k_bwd_gelu(float* a1, const float* bias, int rows, int H, float* u) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < rows * H; i += gridDim.x * blockDim.x) {
+    const float x = a1[i] + bias[i % H];
+    a1[i] = x;
+    u[i] = 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
+  }
+}
+// du <- du * GELU'(a1)
+__global__ __launch_bounds__(256) void k_bwd_gelu_grad(float* du, const float* a1, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float x = a1[i];
+    du[i] *= 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
+  }
+}
+
+}  // namespace edtts_bwd
+
+// =========================================================================================================
+// the tape and the backward's scratch (offsets in floats)
+// =========================================================================================================
+struct TapeLayer {
+  size_t crp, kv;             // kv_down rows before kv_norm [B S][R]; K|V rows [B S][2H]
+  size_t h0, h1, h2;          // the residual stream entering norm1 / norm2 / norm3
+  size_t qkv, att1, lse1;     // self-attention: q|k|v rows, attention output, log-sum-exp [B][HEADS][T]
+  size_t qc, att2, lse2;      // cross-attention: query rows, attention output, log-sum-exp
+  size_t act;                 // value * silu(gate) [B T][FM H]
+};
+struct TrainTape {
+  size_t cond;  // AdaLN rows [B][L][2][2H] and, behind them, t_cond [B][H]
+  size_t ctx;   // context rows [B S][H]
+  TapeLayer layer[kMaxLayers];
+  size_t hL;    // the residual stream entering final_norm
+  size_t total;
+};
+static void make_tape(const Layout& lo, int B, int T, int S, TrainTape* t) {
+  const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S, FH = (size_t)lo.FM * H;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
+  t->cond = take((size_t)B * lo.L * 4 * H + (size_t)B * H);
+  t->ctx = take(CS * H);
+  for (int l = 0; l < lo.L; ++l) {
+    TapeLayer& y = t->layer[l];
+    y.crp = take(CS * lo.R); y.kv = take(CS * 2 * H);
+    y.h0 = take(M * H); y.h1 = take(M * H); y.h2 = take(M * H);
+    y.qkv = take(M * 3 * H); y.att1 = take(M * H); y.lse1 = take(M * lo.HEADS);
+    y.qc = take(M * H); y.att2 = take(M * H); y.lse2 = take(M * lo.HEADS);
+    y.act = take(M * FH);
+  }
+  t->hL = take(M * H);
+  t->total = o;
+}
+struct TrainScratch {
+  size_t dh, xn, ga, gq, big, da, stat, delta, dkv, crn, dcr, dcp, dctx;
+  size_t dmod, dtc, e, a1, u1, du1;  // conditioning path, [B] rows
+  size_t part;
+  size_t total;
+};
+static void make_train_scratch(const Layout& lo, int B, int T, int S, TrainScratch* s) {
+  const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S, FH = (size_t)lo.FM * H, R = lo.R;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
+  auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
+  s->dh = take(M * H); s->xn = take(M * H); s->ga = take(M * H); s->gq = take(M * H);
+  s->big = take(M * mx(2 * FH, 3 * H)); s->da = take(M * FH);
+  s->stat = take(2 * mx(M, CS)); s->delta = take(M * lo.HEADS);
+  s->dkv = take(CS * 2 * H); s->crn = take(CS * R); s->dcr = take(CS * R); s->dcp = take(CS * R); s->dctx = take(CS * H);
+  s->dmod = take((size_t)B * lo.L * 4 * H); s->dtc = take((size_t)B * H); s->e = take((size_t)B * H); s->a1 = take((size_t)B * H);
+  s->u1 = take((size_t)B * H); s->du1 = take((size_t)B * H);
+  // partial slabs: the largest of the dW partials (slab count of its row sum x [N][K]), the bias partials and the norm partials
+  size_t part = 0;
+  auto dwp = [&](size_t rows, size_t n, size_t k) {
+    const size_t r = edtts_bwd::dw_slab_rows((int)rows), ns = (rows + r - 1) / r;
+    if (ns > 1) part = mx(part, ns * n * k);
+  };
+  dwp(M, lo.MEL, H); dwp(M, H, FH); dwp(M, 2 * FH, H); dwp(M, H, H); dwp(M, 3 * H, H); dwp(M, H, lo.MEL);   // decoder rows
+  dwp(CS, 2 * H, R); dwp(CS, R, H); dwp(CS, H, lo.SD);                                                     // context rows
+  dwp(B, 2 * H, H); dwp(B, H, H);                                                                          // conditioning rows
+  const size_t cr = edtts_bwd::kColRows;
+  part = mx(part, (M + cr - 1) / cr * mx(2 * FH, (size_t)lo.MEL));  // bias partials: [slabs][N], N <= 2 FH (or n_mels)
+  part = mx(part, (CS + cr - 1) / cr * H);
+  const size_t cpb = ((size_t)mx(T, S) + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
+  part = mx(part, (size_t)B * cpb * 3 * H);                        // norm partials: [chunk][3][W]
+  s->part = take(part);
+  s->total = o;
+}
+
+// =========================================================================================================
+// TrainLauncher: forward with a tape, backward from it
+// =========================================================================================================
+struct TrainLauncher {
+  using G = GenericLauncher;
+  static int copy(hipStream_t st, float* dst, const float* src, size_t n) {
+    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return EDTTS_OK;
+  }
+
+  // GenericLauncher::ctx + GenericLauncher::forward (TAIL_EPS, no lengths): the same launches in the same order; what the backward
+  // needs goes to the tape instead of the workspace, or is copied there.  The AdaLN rows are already in the tape (launch_cond).
+  static int forward(const CallCtx& c, float* tp, const TrainTape& tt, const float* x, const int64_t* sem_idx, const float* sem_feat, float* eps) {
+    using namespace edtts_gen;
+    const Layout& lo = c.lo;
+    const Workspace& ws = c.ws;
+    const float* blob = c.blob;
+    float* wsb = c.wsb;
+    const hipStream_t st = c.st;
+    const int B = c.B, T = c.T, S = c.S, M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL;
+    float* cx = tp + tt.ctx;
+    if (sem_feat) {
+      TRY_G(G::gemm<EPI_PE>(st, sem_feat, lo.SD, blob + lo.semp, blob + lo.semp_b, cx, H, CS, H, lo.SD, blob + lo.cpe, S));
+    } else {
+      unsigned* err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
+      size_t nb = ((size_t)CS * H + 255) / 256;
+      if (nb > 4096) nb = 4096;
+      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, cx, CS, S, H, lo.NTOK, err,
+                         (const int64_t*)nullptr);
+      LAUNCH_CHECK("k_gen_embed");
+    }
+    for (int l = 0; l < lo.L; ++l) {
+      const LayerLayout& y = lo.layer[l];
+      const TapeLayer& z = tt.layer[l];
+      TRY_G(G::gemm<EPI_BIAS>(st, cx, H, blob + y.kvd, nullptr, tp + z.crp, R, CS, R, H));
+      TRY_G(G::norm<NORM_RMS>(st, tp + z.crp, wsb + ws.g_cr, CS, R, blob + y.kvn, nullptr, 1e-6f));
+      TRY_G(G::gemm<EPI_BIAS>(st, wsb + ws.g_cr, R, blob + y.kvu, nullptr, tp + z.kv, 2 * H, CS, 2 * H, R));
+    }
+    float *h = wsb + ws.h, *xn = wsb + ws.g_xn;
+    const float* cond_row = tp + tt.cond;
+    const int cond_bstride = lo.L * 4 * H;
+    const size_t row = (size_t)4 * H;
+    const size_t MH = (size_t)M * H;
+    TRY_G(G::gemm<EPI_PE>(st, x, MEL, blob + lo.inp, blob + lo.inp_b, h, H, M, H, MEL, blob + lo.pe, T));
+    for (int l = 0; l < lo.L; ++l) {
+      const LayerLayout& y = lo.layer[l];
+      const TapeLayer& z = tt.layer[l];
+      float *qkv = tp + z.qkv, *kv = tp + z.kv;
+      TRY_G(copy(st, tp + z.h0, h, MH));
+      TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
+      TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, qkv, 3 * H, M, 3 * H, H));
+      TRY_G(G::attn(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, T, T, c.window, nullptr, nullptr, false, false, tp + z.lse1));
+      TRY_G(G::gemm<EPI_RESID>(st, tp + z.att1, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
+      TRY_G(copy(st, tp + z.h1, h, MH));
+      TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
+      TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, tp + z.qc, H, M, H, H));
+      TRY_G(G::attn(st, lo, B, tp + z.qc, H, kv, kv + H, 2 * H, tp + z.att2, T, S, -1, nullptr, nullptr, false, false, tp + z.lse2));
+      TRY_G(G::gemm<EPI_RESID>(st, tp + z.att2, H, blob + y.g_op, nullptr, h, H, M, H, H));
+      TRY_G(copy(st, tp + z.h2, h, MH));
+      TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cond_bstride));
+      TRY_G(G::gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, tp + z.act, FH, M, FH, H));
+      TRY_G(G::gemm<EPI_RESID>(st, tp + z.act, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH));
+    }
+    TRY_G(copy(st, tp + tt.hL, h, MH));
+    TRY_G(G::norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
+    TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, eps, MEL, M, MEL, H));
+    return EDTTS_OK;
+  }
+
+  // ---- backward helpers ----
+  static bool al16(const void* p) { return G::al16(p); }
+  static int bgemm(hipStream_t st, edtts_bwd::BGemmArgs a, int slabs, bool acc) {
+    const dim3 grid((a.M + 63) / 64, (a.N + 63) / 64, slabs);
+    if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<1>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<0>, grid, dim3(256), 0, st, a);
+    LAUNCH_CHECK("k_bwd_gemm");
+    return EDTTS_OK;
+  }
+  static int slabsum(hipStream_t st, const float* part, float* out, size_t n, int ns, size_t pstride, int ny = 1, size_t ostride = 0, bool acc = false) {
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_slabsum, dim3(G::grid_1d(n), ny), dim3(256), 0, st, part, out, n, ns, pstride, ostride, (int)acc);
+    LAUNCH_CHECK("k_bwd_slabsum");
+    return EDTTS_OK;
+  }
+  // dX[M][K] (+)= dY[M][N] W[N][K]   (wT: the blob keeps W transposed, [K][N])
+  static int dx(hipStream_t st, const float* dY, long ldy, const float* W, int M, int N, int K, float* dX, int ldx, bool acc, bool wT = false) {
+    edtts_bwd::BGemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = dY; a.B = W; a.C = dX; a.M = M; a.N = K; a.K = N;
+    a.sam = ldy; a.sak = 1; a.sbn = wT ? N : 1; a.sbk = wT ? 1 : K;
+    a.ldc = ldx; a.kslab = (N + 15) / 16 * 16; a.cslab = 0;
+    a.va = (N % 4 == 0) && (ldy % 4 == 0) && al16(dY);
+    a.vb = wT && (N % 4 == 0) && al16(W);
+    a.vc = (ldx % 4 == 0) && al16(dX);
+    return bgemm(st, a, 1, acc);
+  }
+  // dW[N][K] = dY[M][N]^T X[M][K]: slabs of dw_slab_rows(M) rows, summed in slab order
+  static int dw(hipStream_t st, const float* dY, long ldy, const float* X, long ldx, int M, int N, int K, float* dW, float* part) {
+    if (!dW) return EDTTS_OK;
+    const int rows = edtts_bwd::dw_slab_rows(M), ns = (M + rows - 1) / rows;
+    edtts_bwd::BGemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = dY; a.B = X; a.C = ns == 1 ? dW : part; a.M = N; a.N = K; a.K = M;
+    a.sam = 1; a.sak = ldy; a.sbn = 1; a.sbk = ldx;
+    a.ldc = K; a.kslab = rows; a.cslab = (size_t)N * K;
+    a.vc = (K % 4 == 0) && al16(a.C);
+    TRY_G(bgemm(st, a, ns, false));
+    if (ns > 1) TRY_G(slabsum(st, part, dW, (size_t)N * K, ns, (size_t)N * K));
+    return EDTTS_OK;
+  }
+  static int colsum(hipStream_t st, const float* Y, int ld, int M, int N, float* out, float* part) {
+    if (!out) return EDTTS_OK;
+    const int ns = (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows;
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_colsum, dim3((N + 63) / 64, ns), dim3(256), 0, st, Y, ld, M, N, part);
+    LAUNCH_CHECK("k_bwd_colsum");
+    return slabsum(st, part, out, (size_t)N, ns, (size_t)N);
+  }
+  // RMSNorm / LayerNorm backward: dx (+)= ..., gain gradient -> dgain (null: skipped), LayerNorm bias gradient -> dbias,
+  // AdaLN (dscale | dshift) -> dmod[b dmod_bstride ...] (null: skipped)
+  template <int MODE>
+  static int norm_bwd(hipStream_t st, const float* x, const float* dy, float* dxp, bool acc, int rows, int W, int rows_per_b, const float* w,
+                      float eps, const float* mod, int mod_bstride, float* stat, float* part, float* dgain, float* dbias, float* dmod,
+                      int dmod_bstride) {
+    edtts_bwd::NormBwdArgs a{x, dy, dxp, w, mod, stat, part, rows, W, rows_per_b, mod_bstride, (int)acc, eps};
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_rows<MODE>, dim3((rows + 3) / 4), dim3(256), 0, st, a);
+    LAUNCH_CHECK("k_bwd_norm_rows");
+    if (!dgain && !dbias && !dmod) return EDTTS_OK;
+    const int cpb = (rows_per_b + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk, nb = rows / rows_per_b;
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<MODE>, dim3((W + 63) / 64, nb * cpb), dim3(256), 0, st, a);
+    LAUNCH_CHECK("k_bwd_norm_cols");
+    if (dgain) TRY_G(slabsum(st, part, dgain, (size_t)W, nb * cpb, (size_t)3 * W));
+    if (dbias) TRY_G(slabsum(st, part + W, dbias, (size_t)W, nb * cpb, (size_t)3 * W));
+    if (dmod) TRY_G(slabsum(st, part + W, dmod, (size_t)2 * W, cpb, (size_t)3 * W, nb, (size_t)dmod_bstride));
+    return EDTTS_OK;
+  }
+  // gradients of one attention call: dq, dk, dv from q, k, v, the output o, its gradient dO and the tape's log-sum-exp
+  static int attn_bwd(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, const float* o,
+                      const float* dO, const float* lse, float* delta, float* dq, int lddq, float* dk, float* dv, int lddkv, int Tq, int Tk,
+                      int window) {
+    const size_t n = (size_t)B * lo.HEADS * Tq;
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, lo.HEADS, lo.DH, lo.H);
+    LAUNCH_CHECK("k_bwd_attn_delta");
+    const float sn = 1.0f / sqrtf((float)lo.DH);
+    edtts_bwd::AttnBwdArgs a{q, k, v, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
+                             1.4426950408889634f / sqrtf((float)lo.DH), sn};
+    const dim3 gq((Tq + 15) / 16, lo.HEADS, B), gk((Tk + 15) / 16, lo.HEADS, B);
+    switch ((lo.DH + 15) / 16) {
+#define EDTTS_BWD_ATTN(DT)                                                                      \
+  case DT:                                                                                      \
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dq<DT>, gq, dim3(64), 0, st, a);                   \
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dkv<DT>, gk, dim3(64), 0, st, a);                  \
+    break
+      EDTTS_BWD_ATTN(1); EDTTS_BWD_ATTN(2); EDTTS_BWD_ATTN(3); EDTTS_BWD_ATTN(4);
+      EDTTS_BWD_ATTN(5); EDTTS_BWD_ATTN(6); EDTTS_BWD_ATTN(7); EDTTS_BWD_ATTN(8);
+#undef EDTTS_BWD_ATTN
+      default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
+    }
+    LAUNCH_CHECK("k_bwd_attn");
+    return EDTTS_OK;
+  }
+
+  // The backward.  Reads the tape, the blob and its arguments; every buffer it writes is in `sc` (its own scratch) or a gradient.
+  // gs: gradient destinations in edtts_pack_weights slot order (null: not wanted).
+  static int backward(const Layout& lo, const float* blob, const float* tp, const TrainTape& tt, float* sc, const TrainScratch& ss, int B, int T,
+                      int S, int window, const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_feat,
+                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t st) {
+    using namespace edtts_gen;
+    const int M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL, L = lo.L;
+    float *dh = sc + ss.dh, *xn = sc + ss.xn, *ga = sc + ss.ga, *gq = sc + ss.gq, *big = sc + ss.big, *da = sc + ss.da;
+    float *stat = sc + ss.stat, *delta = sc + ss.delta, *dkv = sc + ss.dkv, *crn = sc + ss.crn, *dcr = sc + ss.dcr, *dcp = sc + ss.dcp;
+    float *dctx = sc + ss.dctx, *dmod = sc + ss.dmod, *part = sc + ss.part;
+    const float* cond_row = tp + tt.cond;
+    const int cb = L * 4 * H;
+    const size_t row = (size_t)4 * H;
+    auto GG = [&](int i) { return gs[i]; };
+    HIP_TRY(hipMemsetAsync(dctx, 0, (size_t)CS * H * sizeof(float), st));
+    // out_proj and final_norm
+    TRY_G(colsum(st, d_eps, MEL, M, MEL, GG(G_OUT_B), part));
+    TRY_G(G::norm<NORM_LAYER>(st, tp + tt.hL, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
+    TRY_G(dw(st, d_eps, MEL, xn, H, M, MEL, H, GG(G_OUT_W), part));
+    TRY_G(dx(st, d_eps, MEL, blob + lo.s_outp, M, MEL, H, ga, H, false));
+    TRY_G(norm_bwd<NORM_LAYER>(st, tp + tt.hL, ga, dh, false, M, H, T, blob + lo.fnw, 1e-5f, nullptr, 0, stat, part, GG(G_FN_W), GG(G_FN_B),
+                               nullptr, 0));
+    for (int l = L - 1; l >= 0; --l) {
+      const LayerLayout& y = lo.layer[l];
+      const TapeLayer& z = tt.layer[l];
+      auto W = [&](int i) { return gs[G_COUNT + l * L_COUNT + i]; };
+      // feed-forward branch: h3 = h2 + down(value * silu(gate)) + b
+      TRY_G(colsum(st, dh, H, M, H, W(L_DOWN_B), part));
+      TRY_G(dw(st, dh, H, tp + z.act, FH, M, H, FH, W(L_DOWN_W), part));
+      TRY_G(dx(st, dh, H, blob + y.g_down, M, H, FH, da, FH, false));
+      TRY_G(G::norm<NORM_RMS>(st, tp + z.h2, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cb));
+      TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_up, blob + y.up_b, big, 2 * FH, M, 2 * FH, H));
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu, dim3(G::grid_1d((size_t)M * FH)), dim3(256), 0, st, big, da, (size_t)M, FH);
+      LAUNCH_CHECK("k_bwd_swiglu");
+      TRY_G(colsum(st, big, 2 * FH, M, 2 * FH, W(L_UP_B), part));
+      TRY_G(dw(st, big, 2 * FH, xn, H, M, 2 * FH, H, W(L_UP_W), part));
+      TRY_G(dx(st, big, 2 * FH, blob + y.g_up, M, 2 * FH, H, ga, H, false));
+      TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h2, ga, dh, true, M, H, T, blob + y.n3w, 1e-6f, cond_row + l * row + 2 * H, cb, stat, part, W(L_N3_W),
+                               nullptr, dmod + l * row + 2 * H, cb));
+      // cross-attention branch: h2 = h1 + att2 Wop^T
+      TRY_G(dw(st, dh, H, tp + z.att2, H, M, H, H, W(L_OP_W), part));
+      TRY_G(dx(st, dh, H, blob + y.g_op, M, H, H, ga, H, false));
+      TRY_G(attn_bwd(st, lo, B, tp + z.qc, H, tp + z.kv, tp + z.kv + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
+                     S, -1));
+      TRY_G(G::norm<NORM_RMS>(st, tp + z.h1, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
+      TRY_G(dw(st, gq, H, xn, H, M, H, H, W(L_QP_W), part));
+      TRY_G(dx(st, gq, H, blob + y.g_qp, M, H, H, ga, H, false));
+      TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h1, ga, dh, true, M, H, T, blob + y.n2w, 1e-6f, nullptr, 0, stat, part, W(L_N2_W), nullptr, nullptr, 0));
+      // ... and its context chain: context -> kv_down -> kv_norm -> kv_up -> K|V
+      TRY_G(G::norm<NORM_RMS>(st, tp + z.crp, crn, CS, R, blob + y.kvn, nullptr, 1e-6f));
+      TRY_G(dw(st, dkv, 2 * H, crn, R, CS, 2 * H, R, W(L_KVU_W), part));
+      TRY_G(dx(st, dkv, 2 * H, blob + y.kvu, CS, 2 * H, R, dcr, R, false));
+      TRY_G(norm_bwd<NORM_RMS>(st, tp + z.crp, dcr, dcp, false, CS, R, S, blob + y.kvn, 1e-6f, nullptr, 0, stat, part, W(L_KVN_W), nullptr,
+                               nullptr, 0));
+      TRY_G(dw(st, dcp, R, tp + tt.ctx, H, CS, R, H, W(L_KVD_W), part));
+      TRY_G(dx(st, dcp, R, blob + y.kvd, CS, R, H, dctx, H, true));
+      // self-attention branch: h1 = h0 + att1 Wproj^T + b
+      TRY_G(colsum(st, dh, H, M, H, W(L_PROJ_B), part));
+      TRY_G(dw(st, dh, H, tp + z.att1, H, M, H, H, W(L_PROJ_W), part));
+      TRY_G(dx(st, dh, H, blob + y.g_proj, M, H, H, ga, H, false));
+      const float* qkv = tp + z.qkv;
+      TRY_G(attn_bwd(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, ga, tp + z.lse1, delta, big, 3 * H, big + H, big + 2 * H,
+                     3 * H, T, T, window));
+      TRY_G(G::norm<NORM_RMS>(st, tp + z.h0, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cb));
+      TRY_G(dw(st, big, 3 * H, xn, H, M, 3 * H, H, W(L_QKV_W), part));
+      TRY_G(dx(st, big, 3 * H, blob + y.s_qkv, M, 3 * H, H, ga, H, false));
+      TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h0, ga, dh, true, M, H, T, blob + y.n1w, 1e-6f, cond_row + l * row, cb, stat, part, W(L_N1_W), nullptr,
+                               dmod + l * row, cb));
+    }
+    // in_proj
+    TRY_G(colsum(st, dh, H, M, H, GG(G_INP_B), part));
+    TRY_G(dw(st, dh, H, x, MEL, M, H, MEL, GG(G_INP_W), part));
+    if (d_x) TRY_G(dx(st, dh, H, blob + lo.inp, M, H, MEL, d_x, MEL, false));
+    // context sources
+    if (sem_feat) {
+      TRY_G(colsum(st, dctx, H, CS, H, GG(G_SEMP_B), part));
+      TRY_G(dw(st, dctx, H, sem_feat, lo.SD, CS, H, lo.SD, GG(G_SEMP_W), part));
+      if (d_sem) TRY_G(dx(st, dctx, H, blob + lo.semp, CS, H, lo.SD, d_sem, lo.SD, false));
+      if (GG(G_TOK)) HIP_TRY(hipMemsetAsync(GG(G_TOK), 0, (size_t)lo.NTOK * H * sizeof(float), st));  // (does not enter the output)
+    } else {
+      if (GG(G_SEMP_W)) HIP_TRY(hipMemsetAsync(GG(G_SEMP_W), 0, (size_t)H * lo.SD * sizeof(float), st));
+      if (GG(G_SEMP_B)) HIP_TRY(hipMemsetAsync(GG(G_SEMP_B), 0, (size_t)H * sizeof(float), st));
+    }
+    if (!sem_feat && GG(G_TOK)) {
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NTOK), dim3(256), 0, st, sem_idx, CS, lo.NTOK, dctx, H, GG(G_TOK));
+      LAUNCH_CHECK("k_bwd_scatter_rows");
+    }
+    // conditioning path: AdaLN projections, then the time MLP and step_emb
+    if (GG(G_STEP) && !step_idx) HIP_TRY(hipMemsetAsync(GG(G_STEP), 0, (size_t)lo.NSTEP * H * sizeof(float), st));
+    bool any_proj = false;
+    for (int l = 0; l < L; ++l)
+      any_proj = any_proj || gs[G_COUNT + l * L_COUNT + L_N1P_W] || gs[G_COUNT + l * L_COUNT + L_N1P_B] ||
+                 gs[G_COUNT + l * L_COUNT + L_N3P_W] || gs[G_COUNT + l * L_COUNT + L_N3P_B];
+    const bool any_time = GG(G_T1_W) || GG(G_T1_B) || GG(G_T3_W) || GG(G_T3_B) || GG(G_STEP);
+    if (!any_proj && !any_time) return EDTTS_OK;
+    const float* tcond = cond_row + (size_t)B * cb;
+    float *dtc = sc + ss.dtc, *e = sc + ss.e, *a1 = sc + ss.a1, *u1 = sc + ss.u1, *du1 = sc + ss.du1;
+    HIP_TRY(hipMemsetAsync(dtc, 0, (size_t)B * H * sizeof(float), st));
+    for (int l = 0; l < L; ++l) {
+      const LayerLayout& y = lo.layer[l];
+      for (int which = 0; which < 2; ++which) {
+        const float* dm = dmod + l * row + which * 2 * H;
+        float* gw = gs[G_COUNT + l * L_COUNT + (which ? L_N3P_W : L_N1P_W)];
+        float* gb = gs[G_COUNT + l * L_COUNT + (which ? L_N3P_B : L_N1P_B)];
+        TRY_G(colsum(st, dm, cb, B, 2 * H, gb, part));
+        TRY_G(dw(st, dm, cb, tcond, H, B, 2 * H, H, gw, part));
+        TRY_G(dx(st, dm, cb, blob + (which ? y.ada3T : y.ada1T), B, 2 * H, H, dtc, H, true, true));
+      }
+    }
+    if (!any_time) return EDTTS_OK;
+    if (GG(G_STEP) && step_idx) {
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NSTEP), dim3(256), 0, st, step_idx, B, lo.NSTEP, dtc, H, GG(G_STEP));
+      LAUNCH_CHECK("k_bwd_scatter_rows");
+    }
+    // t_cond = W3 GELU(W1 e + b1) + b3: recompute e, the pre-activation and the hidden row
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_time_emb, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, t, blob + lo.freqs, B, H, e);
+    LAUNCH_CHECK("k_bwd_time_emb");
+    {
+      edtts_bwd::BGemmArgs a;  // a1 = e W1^T (the blob keeps W1 transposed)
+      memset(&a, 0, sizeof(a));
+      a.A = e; a.B = blob + lo.t1T; a.C = a1; a.M = B; a.N = H; a.K = H; a.sam = H; a.sak = 1; a.sbn = 1; a.sbk = H; a.ldc = H;
+      a.kslab = (H + 15) / 16 * 16;
+      TRY_G(bgemm(st, a, 1, false));
+    }
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_gelu, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, a1, blob + lo.t1b, B, H, u1);
+    LAUNCH_CHECK("k_bwd_gelu");
+    TRY_G(colsum(st, dtc, H, B, H, GG(G_T3_B), part));
+    TRY_G(dw(st, dtc, H, u1, H, B, H, H, GG(G_T3_W), part));
+    TRY_G(dx(st, dtc, H, blob + lo.t3T, B, H, H, du1, H, false, true));
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_gelu_grad, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, du1, a1, B * H);
+    LAUNCH_CHECK("k_bwd_gelu_grad");
+    TRY_G(colsum(st, du1, H, B, H, GG(G_T1_B), part));
+    TRY_G(dw(st, du1, H, e, H, B, H, H, GG(G_T1_W), part));
+    return EDTTS_OK;
+  }
+};

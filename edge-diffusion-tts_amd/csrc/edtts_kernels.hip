@@ -2822,6 +2822,7 @@ struct Launcher16 {
 };
 
 #include "edtts_generic.h"
+#include "edtts_generic_bwd.h"
 #include "edtts_semantic.h"
 #include "edtts_hubert.h"
 #include "edtts_hubert16.h"
@@ -3206,6 +3207,82 @@ int edtts_decoder_forward_len(const EdttsDims* dims, const void* packed, void* w
     TRY(LN::forward(c, x, wsb + ws.cond, bstride, tail));
   });
   return EDTTS_OK;
+}
+
+// ---- training: forward with a tape, backward from it (edtts_generic_bwd.h) ----------------------------------------------------
+static int train_layout(const EdttsDims* dims, const char* who, Layout* lo) {
+  if (!dims) return fail(EDTTS_ERR_ARG, "dims is NULL");
+  const int kbits = dims->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  if (kbits != EDTTS_KERNELS_GENERIC)
+    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training runs on the generic kernels only (compute_dtype=0x%x lacks EDTTS_KERNELS_GENERIC)", who,
+                dims->compute_dtype);
+  if (dtype != EDTTS_F32) return fail(EDTTS_ERR_UNSUPPORTED, "%s: training is fp32 only (compute_dtype=0x%x)", who, dims->compute_dtype);
+  return make_layout(dims, lo);
+}
+
+int edtts_train_dw_slab_rows(int rows) { return edtts_bwd::dw_slab_rows(rows); }
+
+int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes) {
+  Layout lo;
+  TRY(train_layout(dims, "edtts_train_tape_bytes", &lo));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY(check_shapes(lo, B, T, S));
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  *out_bytes = tt.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes) {
+  Layout lo;
+  TRY(train_layout(dims, "edtts_train_scratch_bytes", &lo));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY(check_shapes(lo, B, T, S));
+  TrainScratch ss;
+  make_train_scratch(lo, B, T, S, &ss);
+  *out_bytes = ss.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S, const float* x,
+                                const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, float* eps,
+                                void* stream) {
+  const SettingsScope settings;
+  Layout lo;
+  TRY(train_layout(dims, "edtts_decoder_forward_train", &lo));
+  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
+  if (!packed || !workspace || !tape || !x || !t || !eps) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  TRY(check_shapes(lo, B, T, S));
+  hipStream_t st = (hipStream_t)stream;
+  const float* blob = (const float*)packed;
+  float* wsb = (float*)workspace;
+  float* tp = (float*)tape;
+  Workspace ws;
+  make_workspace(lo, B, T, S, B, &ws);
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, tp + tt.cond, wsb, st));  // the AdaLN rows and t_cond go straight to the tape
+  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{}, st};
+  return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps);
+}
+
+int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S, const float* x,
+                           const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, const float* d_eps,
+                           void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch, void* stream) {
+  Layout lo;
+  TRY(train_layout(dims, "edtts_decoder_backward", &lo));
+  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
+  if (!packed || !workspace || !tape || !x || !t || !d_eps || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
+  TRY(check_shapes(lo, B, T, S));
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  TrainScratch ss;
+  make_train_scratch(lo, B, T, S, &ss);
+  return TrainLauncher::backward(lo, (const float*)packed, (const float*)tape, tt, (float*)scratch, ss, B, T, S, dims->window, x, t, step_idx,
+                                 sem_features ? nullptr : sem_idx, sem_features, d_eps, reinterpret_cast<float* const*>(grad_slots), d_x,
+                                 d_sem_features, (hipStream_t)stream);
 }
 
 int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,

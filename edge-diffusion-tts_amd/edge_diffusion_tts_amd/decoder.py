@@ -3,8 +3,9 @@
 The module owns parameters and buffers under the reference's state-dict key names, so
 ``load_state_dict(reference_decoder.state_dict())`` works, but it has no sub-module forward code: ``forward`` hands
 device pointers to the C ABI (include/edtts.h, edtts_decoder_forward) where the whole network runs as hand-written
-gfx950 kernels.  Inference only (the reference path this replaces runs under ``torch.no_grad``, inference.py:23);
-dropout is the identity as in ``decoder.eval()``.
+gfx950 kernels.  By default inference only (the reference path this replaces runs under ``torch.no_grad``, inference.py:23);
+dropout is the identity as in ``decoder.eval()``.  ``autograd=True`` (generic fp32 kernels) adds the backward the reference's
+trainers need (train_v2.py train_step, training/consistency.py): DESIGN.md section 19.
 """
 from __future__ import annotations
 
@@ -36,8 +37,52 @@ def _attach(root: nn.Module, key: str, tensor: torch.Tensor, is_buffer: bool) ->
         mod.register_parameter(leaf, nn.Parameter(tensor, requires_grad=False))
 
 
+class _DecoderGrad(torch.autograd.Function):
+    """eps = decoder(...) on the training forward (edtts_decoder_forward_train); backward through edtts_decoder_backward.  The tape is
+    a tensor of this call's own, saved in ctx: any number of forwards may share the decoder's cached workspace before a backward."""
+
+    @staticmethod
+    def forward(ctx, dec, t, sem_idx, step_idx, names, x_t, sem_features, *params):
+        B, T, _ = x_t.shape
+        S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
+        dims = dec.dims()
+        packed = dec._ensure_packed()
+        ws = dec.workspace(B, T, S, B, x_t.device)
+        x = x_t.detach().contiguous()
+        t = t.contiguous()
+        step_idx = None if step_idx is None else step_idx.contiguous()
+        sem_idx = None if sem_features is not None or sem_idx is None else sem_idx.contiguous()
+        feats = None if sem_features is None else sem_features.detach().contiguous()
+        tape = torch.empty(native.train_tape_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
+        eps = native.decoder_forward_train(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, S)
+        ctx.dec, ctx.names, ctx.S, ctx.sig = dec, names, S, dec._packed_sig
+        ctx.inputs = (x, t, step_idx, sem_idx, feats)
+        ctx.save_for_backward(tape, *params)
+        return eps
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_eps):
+        dec = ctx.dec
+        tape, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        x, t, step_idx, sem_idx, feats = ctx.inputs
+        if dec._packed_sig != ctx.sig:
+            raise RuntimeError("EdgeDiffusionDecoder: a parameter was modified between this forward and its backward")
+        B, T, _ = x.shape
+        dims, packed = dec.dims(), dec._packed
+        ws = dec.workspace(B, T, ctx.S, B, x.device)
+        wanted = {n: p for n, p, need in zip(ctx.names, params, ctx.needs_input_grad[7:]) if need and dec._enters_output(n, feats is not None, step_idx is not None)}
+        out = {n: torch.empty_like(p) for n, p in wanted.items()}
+        slots = [out.get(dec._slot_param(n)) for n in native.slot_names(dec.cfg.layers)]
+        d_x = torch.empty_like(x) if ctx.needs_input_grad[5] else None
+        d_f = torch.empty_like(feats) if feats is not None and ctx.needs_input_grad[6] else None
+        native.decoder_backward(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, ctx.S, d_eps.contiguous(), slots, d_x, d_f)
+        return (None, None, None, None, None, d_x, d_f, *[out.get(n) for n in ctx.names])
+
+
 class EdgeDiffusionDecoder(nn.Module):
-    def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled"):
+    def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled",
+                 autograd: bool = False):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
@@ -45,8 +90,16 @@ class EdgeDiffusionDecoder(nn.Module):
         head_dim 32, i.e. BASELINE config 3: hidden=256, heads=8).  Parameters stay fp32 either way.
         ``kernels``: "compiled" (default) runs only shapes that are compiled kernel instances; "generic" runs every shape on the
         run-time-shape fp32 kernels; "auto" takes the compiled instance when there is one and the generic kernels otherwise
-        (include/edtts.h: EDTTS_KERNELS_*).  The generic kernels are fp32 only."""
+        (include/edtts.h: EDTTS_KERNELS_*).  The generic kernels are fp32 only.
+        ``autograd``: False (default) -- ``forward`` is inference only, as before.  True (needs ``kernels="generic"`` and fp32) --
+        the parameters require grad, and a ``forward`` under grad mode whose parameters, ``x_t`` or ``sem_features`` require grad is
+        differentiable: it runs the training forward and hands ``backward()`` to the backward kernels."""
         super().__init__()
+        self.autograd = bool(autograd)
+        if self.autograd and kernels != "generic":
+            raise ValueError(f"autograd=True needs kernels='generic' (the backward differentiates the generic kernels), got {kernels!r}")
+        if self.autograd and native.COMPUTE_DTYPES.get(compute_dtype) != native.COMPUTE_DTYPES["f32"]:
+            raise ValueError(f"autograd=True needs compute_dtype='f32' (the backward is fp32 only), got {compute_dtype!r}")
         self.cfg = cfg
         if compute_dtype not in native.COMPUTE_DTYPES:
             raise ValueError(f"compute_dtype must be one of {sorted(native.COMPUTE_DTYPES)}, got {compute_dtype!r}")
@@ -66,6 +119,9 @@ class EdgeDiffusionDecoder(nn.Module):
             else:
                 _attach(self, key, self._default_init(key, shape), False)
         self._fix_bias_init()
+        if self.autograd:
+            for p in self.parameters():
+                p.requires_grad_(True)
         self.register_buffer("_time_freqs", time_frequencies(H), persistent=False)
         self._zero_mod = None
         self._packed: Optional[torch.Tensor] = None
@@ -307,9 +363,67 @@ class EdgeDiffusionDecoder(nn.Module):
                 self._workspaces.pop(k, None)
         return len(keys)
 
+    # ------------------------------------------------------------------------------------------ autograd
+    def _slot_param(self, slot: str) -> Optional[str]:
+        """The parameter a weight slot's gradient belongs to (None: a buffer, or a slot this decoder fills with a constant)."""
+        if slot in ("pos_emb.pe", "context_pos_emb.pe", "time_freqs"):
+            return None
+        if not self.cfg.use_adaln:  # plain RMSNorm blocks: the gain sits in the AdaLN slot, the modulation slots hold zeros
+            if ".norm1.proj." in slot or ".norm3.proj." in slot:
+                return None
+            return slot.replace(".norm1.norm.weight", ".norm1.weight").replace(".norm3.norm.weight", ".norm3.weight")
+        return slot
+
+    def _enters_output(self, name: str, with_features: bool, with_step: bool) -> bool:
+        """False for the parameters torch itself would leave without a gradient for this call."""
+        if name == "token_emb.weight":
+            return not with_features
+        if name.startswith("sem_proj."):
+            return with_features
+        if name.startswith("time_emb."):
+            return bool(self.cfg.use_adaln)
+        if name == "step_emb.weight":
+            return with_step and bool(self.cfg.use_adaln)
+        return True
+
+    def _named_params(self):
+        """(names, parameters) without walking the module tree on every call: the tree of containers is fixed after construction,
+        so each parameter is resolved once to (its owner's _parameters dict, key) and read from there (see _slot_tensors)."""
+        refs = getattr(self, "_param_refs", None)
+        if refs is None:
+            names, pairs = [], []
+            for prefix, mod in self.named_modules():
+                for leaf in mod._parameters:
+                    names.append(f"{prefix}.{leaf}" if prefix else leaf)
+                    pairs.append((mod._parameters, leaf))
+            refs = self._param_refs = (tuple(names), pairs)
+        return refs[0], tuple(d[k] for d, k in refs[1])
+
+    def _forward_autograd(self, x_t, t, sem_idx, step_idx, sem_features, x_lengths, sem_lengths) -> torch.Tensor:
+        if sem_idx is None and sem_features is None:
+            raise ValueError("Either sem_idx or sem_features must be provided")
+        if x_lengths is not None or sem_lengths is not None:
+            raise ValueError("autograd=True: x_lengths / sem_lengths are not supported by the backward (pad-free batches only)")
+        if self.training and self.cfg.dropout > 0:
+            raise ValueError(f"autograd=True: the kernels have no dropout but cfg.dropout={self.cfg.dropout} and the decoder is in "
+                             "training mode (the reference applies attention and FFN dropout there): set cfg.dropout = 0 or call .eval()")
+        names, params = self._named_params()
+        return _DecoderGrad.apply(self, t, sem_idx, step_idx, names, x_t, sem_features, *params)
+
     # ------------------------------------------------------------------------------------------ forward
-    @torch.no_grad()
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, sem_idx: Optional[torch.Tensor] = None,
+                step_idx: Optional[torch.Tensor] = None, sem_features: Optional[torch.Tensor] = None, *,
+                x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """See ``_forward_inference`` for the arguments.  With ``autograd=True``, under grad mode and with something that requires
+        grad (a parameter, ``x_t`` or ``sem_features``), the result is differentiable; otherwise this is the inference forward."""
+        if self.autograd and torch.is_grad_enabled() and (
+                x_t.requires_grad or (sem_features is not None and sem_features.requires_grad)
+                or any(p.requires_grad for p in self._named_params()[1])):
+            return self._forward_autograd(x_t, t, sem_idx, step_idx, sem_features, x_lengths, sem_lengths)
+        return self._forward_inference(x_t, t, sem_idx, step_idx, sem_features, x_lengths=x_lengths, sem_lengths=sem_lengths)
+
+    @torch.no_grad()
+    def _forward_inference(self, x_t: torch.Tensor, t: torch.Tensor, sem_idx: Optional[torch.Tensor] = None,
                 step_idx: Optional[torch.Tensor] = None, sem_features: Optional[torch.Tensor] = None, *,
                 x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """eps = decoder(x_t [B,T,n_mels], t [B], sem_idx [B,S] | sem_features [B,S,semantic_dim], step_idx [B] | None).

@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "edtts_hubert_packed_bytes_dt", "edtts_hubert_pack_dt", "edtts_hubert_workspace_bytes_dt", "edtts_hubert_forward_dt",
     "edtts_melspec", "edtts_mel_segment_stats", "edtts_logmel_stats", "edtts_resample",
     "edtts_mel_to_spec_len", "edtts_griffin_lim_len",
+    "edtts_train_tape_bytes", "edtts_train_scratch_bytes", "edtts_train_dw_slab_rows", "edtts_decoder_forward_train",
+    "edtts_decoder_backward",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -155,6 +157,13 @@ def lib() -> C.CDLL:
     L.edtts_mel_segment_stats.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
     L.edtts_logmel_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
     L.edtts_resample.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
+    L.edtts_train_tape_bytes.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, C.POINTER(sz)]
+    L.edtts_train_scratch_bytes.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, C.POINTER(sz)]
+    L.edtts_train_dw_slab_rows.argtypes = [i32]
+    L.edtts_train_dw_slab_rows.restype = i32
+    L.edtts_decoder_forward_train.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.edtts_decoder_backward.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
+                                         vp, vp, vp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -165,7 +174,8 @@ def lib() -> C.CDLL:
     L.edtts_profile_collect.argtypes = [C.POINTER(C.c_double), C.POINTER(i32)]  # arrays of 2
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("edtts_version", "edtts_num_global_slots", "edtts_num_layer_slots", "edtts_set_substreams", "edtts_set_coop", "edtts_substreams_for"):
+        if fn.restype is C.c_int and name not in ("edtts_version", "edtts_num_global_slots", "edtts_num_layer_slots", "edtts_set_substreams", "edtts_set_coop", "edtts_substreams_for",
+                                                  "edtts_train_dw_slab_rows"):
             fn.errcheck = _errcheck
     _lib = L
     return L
@@ -266,6 +276,54 @@ def decoder_forward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tens
                                         eps.data_ptr(), _stream(x.device))
     check_indices(workspace)
     return eps
+
+
+# ---------------------------------------------------------------------------------------------- training
+def train_tape_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_train_tape_bytes(C.byref(dims), B, T, S, C.byref(out))
+    return out.value
+
+
+def train_scratch_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_train_scratch_bytes(C.byref(dims), B, T, S, C.byref(out))
+    return out.value
+
+
+def train_dw_slab_rows(rows: int) -> int:
+    """Rows per partial slab of a weight gradient that sums over `rows` rows (include/edtts.h: edtts_train_dw_slab_rows)."""
+    return int(lib().edtts_train_dw_slab_rows(int(rows)))
+
+
+def decoder_forward_train(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, tape: torch.Tensor, x: torch.Tensor,
+                          t: torch.Tensor, step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor],
+                          sem_features: Optional[torch.Tensor], S: int) -> torch.Tensor:
+    """edtts_decoder_forward_train: eps, with the backward's tape written to `tape` (uint8, train_tape_bytes)."""
+    B, T, M = x.shape
+    eps = torch.empty_like(x)
+    lib().edtts_decoder_forward_train(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
+                                      _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"),
+                                      _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+                                      _dev_ptr(sem_features, torch.float32, "sem_features"), eps.data_ptr(), _stream(x.device))
+    check_indices(workspace)
+    return eps
+
+
+def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, tape: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
+                     step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor], S: int,
+                     d_eps: torch.Tensor, grads: Sequence[Optional[torch.Tensor]], d_x: Optional[torch.Tensor],
+                     d_sem_features: Optional[torch.Tensor]) -> None:
+    """edtts_decoder_backward: writes the gradient of every non-None entry of `grads` (slot order), d_x and d_sem_features."""
+    B, T, M = x.shape
+    ptrs = (C.c_void_p * len(grads))(*[_dev_ptr(g, torch.float32, f"grad[{i}]") for i, g in enumerate(grads)])
+    scratch = torch.empty(train_scratch_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
+    lib().edtts_decoder_backward(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
+                                 _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"),
+                                 _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
+                                 _dev_ptr(sem_features, torch.float32, "sem_features"), _dev_ptr(d_eps, torch.float32, "d_eps"), ptrs,
+                                 len(grads), _dev_ptr(d_x, torch.float32, "d_x"),
+                                 _dev_ptr(d_sem_features, torch.float32, "d_sem_features"), scratch.data_ptr(), _stream(x.device))
 
 
 def generate(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,

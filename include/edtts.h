@@ -142,6 +142,45 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
                           const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
                           const float* sem_features, float* eps, void* stream);
 
+/* ---- training: the decoder forward with a tape, and its backward ---------------------------------------------------------
+ * For train.py / train_v2.py / training/consistency.py, whose steps call decoder(x_t, t, ...) under autograd (train_v2.py
+ * train_step; training/consistency.py consistency_loss calls it twice before one backward()).  First version: generic kernels
+ * and fp32 only -- dims.compute_dtype must be EDTTS_F32 | EDTTS_KERNELS_GENERIC, anything else is EDTTS_ERR_UNSUPPORTED with a
+ * message naming the cause -- dropout off (decoder.eval() arithmetic: layers/attention.py and layers/transformer.py apply
+ * dropout only when training) and no per-utterance lengths.  Conventions as everywhere: no allocation, no host synchronisation,
+ * work only on `stream`, graph-capturable.  Every reduction has a fixed order: a backward is bitwise reproducible.
+ *
+ * edtts_train_tape_bytes: size of the caller-owned tape one forward_train call fills and its backward reads (per layer: the
+ * residual stream at the three norms, q|k|v, both attention outputs and their log-sum-exps, the cross K|V and kv_down rows, the
+ * SwiGLU output; plus the context rows, the AdaLN rows and the residual stream entering final_norm).
+ * edtts_train_scratch_bytes: the backward's own scratch (gradient rows and the partial slabs of its cut reductions).
+ * edtts_train_dw_slab_rows: rows per partial slab of a weight gradient summed over `rows` rows (a host query). */
+int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes);
+int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes);
+int edtts_train_dw_slab_rows(int rows);
+
+/* models/decoder.py:66-109 as edtts_decoder_forward runs it on the generic path -- eps is bitwise that call's -- keeping on
+ * `tape` what the backward needs.  Arguments as edtts_decoder_forward; the workspace is that call's (edtts_workspace_bytes with
+ * cond_rows = B) and may be shared by any number of forwards: the backward never reads it. */
+int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                const float* sem_features, float* eps, void* stream);
+
+/* The gradient of models/decoder.py:66-109 (time_emb / step_emb :77-80, token_emb / sem_proj + context_pos_emb :83-93, in_proj +
+ * pos_emb :96-97, the blocks of layers/transformer.py:129-160 with layers/attention.py:77-123, layers/mla.py:118-194 and
+ * layers/transformer.py:13-49,64-68, final_norm + out_proj :105-109) with respect to every weight, x and sem_features, given
+ * d_eps [B,T,n_mels].  x, t, step_idx, sem_idx / sem_features are the forward's arguments; `tape` is the one that forward filled.
+ * grad_slots: host array of n_slots device pointers in edtts_pack_weights slot order; each non-NULL entry receives that tensor's
+ * gradient (written, not accumulated), a NULL entry skips it.  The entries of the positional tables and time_freqs (buffers) are
+ * ignored.  What does not enter the output -- token_emb with sem_features, sem_proj with sem_idx, step_emb without step_idx -- has
+ * a zero gradient: a non-NULL entry is zero-filled (a caller that mirrors torch, which leaves .grad unset there, passes NULL).
+ * d_x [B,T,n_mels] and d_sem_features [B,S,semantic_dim] may be NULL.  `scratch`: edtts_train_scratch_bytes.
+ * Reads only the tape, the blob and its arguments; `workspace` is not read. */
+int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                           const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                           const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
+                           float* d_sem_features, void* scratch, void* stream);
+
 /* ---- per-utterance lengths (ragged batches) -----------------------------------------------------------------------------
  * The *_len entry points below take the arguments of their twins plus device int64 [B] length arrays: t_len (frames T_b) and
  * s_len (tokens S_b); where frames are 2 x tokens (edtts_generate_len, edtts_sample_ddpm_len) s_len alone.  NULL = full length
