@@ -1100,13 +1100,12 @@ EDTTS_DEV float cfg_combine(float vc, float vu, float scale) {
   return vu + s;
 }
 
-// Philox4x32-10 counter-based generator (Salmon et al., SC'11) -> four standard normals per call (Box-Muller).
-// counter = (element index lo, hi, step, 0), key = (seed lo, hi): every (seed, step, element) gets its own stream, so the
-// result does not depend on how elements are distributed over waves / GPUs PROVIDED the caller passes the GLOBAL element index
-// (the sharded callers add their shard's first-element offset: KArgs::philox_base, edtts_randn's elem_offset).
-EDTTS_DEV f4 philox_normal4(unsigned long long seed, unsigned step, unsigned long long index) {
-  unsigned c0 = (unsigned)index, c1 = (unsigned)(index >> 32), c2 = step, c3 = 0u;
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+// Philox4x32-10 counter-based generator (Salmon et al., SC'11): the ten integer rounds, key (k0, k1), counter (c0 .. c3) -> the
+// four output words.  (Known answers: tests/test_dropout_host.py.)
+struct U4 {
+  unsigned x, y, z, w;
+};
+EDTTS_DEV U4 philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
 #pragma unroll
   for (int i = 0; i < 10; ++i) {
     const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
@@ -1114,11 +1113,85 @@ EDTTS_DEV f4 philox_normal4(unsigned long long seed, unsigned step, unsigned lon
     c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
+  return U4{c0, c1, c2, c3};
+}
+// ... -> four standard normals per call (Box-Muller).
+// counter = (element index lo, hi, step, 0), key = (seed lo, hi): every (seed, step, element) gets its own stream, so the
+// result does not depend on how elements are distributed over waves / GPUs PROVIDED the caller passes the GLOBAL element index
+// (the sharded callers add their shard's first-element offset: KArgs::philox_base, edtts_randn's elem_offset).
+EDTTS_DEV f4 philox_normal4(unsigned long long seed, unsigned step, unsigned long long index) {
+  const U4 c = philox4x32_10((unsigned)seed, (unsigned)(seed >> 32), (unsigned)index, (unsigned)(index >> 32), step, 0u);
   const float inv = 2.3283064365386963e-10f;  // 2^-32
-  const float u0 = ((float)c0 + 1.0f) * inv, u1 = (float)c1 * inv, u2 = ((float)c2 + 1.0f) * inv, u3 = (float)c3 * inv;
+  const float u0 = ((float)c.x + 1.0f) * inv, u1 = (float)c.y * inv, u2 = ((float)c.z + 1.0f) * inv, u3 = (float)c.w * inv;
   const float r0 = sqrtf(-2.0f * __logf(u0 > 1.0f ? 1.0f : u0)), r1 = sqrtf(-2.0f * __logf(u2 > 1.0f ? 1.0f : u2));
   const float a0 = 6.28318530717958647692f * u1, a1 = 6.28318530717958647692f * u3;
   return f4{r0 * __cosf(a0), r0 * __sinf(a0), r1 * __cosf(a1), r1 * __sinf(a1)};
+}
+
+// ---- dropout masks (include/edtts.h, "Dropout masks") -------------------------------------------------------
+// One draw = philox4x32_10(key = seed, counter = (c0, c1, 0x30000 + 4 layer + site, c3)) = eight 16-bit fields; field j is bits
+// [16 (j & 1), +16) of word j >> 1.  An element is kept iff its field >= thr and is then multiplied by scale = 1 / (1 - thr / 65536).
+// The mask is a function of the element's position alone: these functions are the only place that maps positions to counter words,
+// and every kernel that applies a mask (forward, backward, edtts_dropout_mask) calls them.
+struct DropArgs {
+  unsigned k0, k1;  // seed lo, hi
+  unsigned c2;      // stream word of this (layer, site)
+  unsigned thr;     // round(p * 65536)
+  float scale;      // 65536 / (65536 - thr)
+};
+EDTTS_DEV unsigned drop_field(const U4& w, int j) {
+  const unsigned v = (j & 4) ? ((j & 2) ? w.w : w.z) : ((j & 2) ? w.y : w.x);
+  return (j & 1) ? v >> 16 : v & 0xffffu;
+}
+EDTTS_DEV float drop_mul(const DropArgs& d, const U4& w, int j) { return drop_field(w, j) >= d.thr ? d.scale : 0.f; }
+// attention probabilities (sites 0, 1): element (bh = utterance * heads + head, query q, key k)
+EDTTS_DEV U4 drop_attn_draw(const DropArgs& d, unsigned bh, int q, int k) {
+  return philox4x32_10(d.k0, d.k1, (unsigned)k >> 2, (unsigned)q >> 1, d.c2, bh);
+}
+EDTTS_DEV int drop_attn_field(int q, int k) { return 4 * (q & 1) + (k & 3); }
+// the multipliers of keys key0 .. key0 + 3 of one query; aligned (key0 % 4 == 0, the same for the whole wave): one draw, else two
+EDTTS_DEV f4 drop_attn_keys4(const DropArgs& d, unsigned bh, int q, int key0, bool aligned) {
+  f4 m;
+  const U4 w0 = drop_attn_draw(d, bh, q, key0);
+  if (aligned) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m[r] = drop_mul(d, w0, drop_attn_field(q, key0 + r));
+  } else {
+    const U4 w1 = drop_attn_draw(d, bh, q, key0 + 4);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int f = drop_attn_field(q, key0 + r);
+      const float m0 = drop_mul(d, w0, f), m1 = drop_mul(d, w1, f);
+      m[r] = ((key0 + r) >> 2) == (key0 >> 2) ? m0 : m1;
+    }
+  }
+  return m;
+}
+// the multipliers of queries q0 .. q0 + 3 of one key; odd (q0 % 2 == 1, the same for the whole wave): three draws, else two
+EDTTS_DEV f4 drop_attn_queries4(const DropArgs& d, unsigned bh, int q0, int key, bool odd) {
+  f4 m;
+  const U4 w0 = drop_attn_draw(d, bh, q0, key);
+  m[0] = drop_mul(d, w0, drop_attn_field(q0, key));
+  if (!odd) {
+    const U4 w1 = drop_attn_draw(d, bh, q0 + 2, key);
+    m[1] = drop_mul(d, w0, drop_attn_field(q0 + 1, key));
+    m[2] = drop_mul(d, w1, drop_attn_field(q0 + 2, key));
+    m[3] = drop_mul(d, w1, drop_attn_field(q0 + 3, key));
+  } else {
+    const U4 w1 = drop_attn_draw(d, bh, q0 + 1, key), w2 = drop_attn_draw(d, bh, q0 + 3, key);
+    m[1] = drop_mul(d, w1, drop_attn_field(q0 + 1, key));
+    m[2] = drop_mul(d, w1, drop_attn_field(q0 + 2, key));
+    m[3] = drop_mul(d, w2, drop_attn_field(q0 + 3, key));
+  }
+  return m;
+}
+// feed-forward activations (sites 2, 3): the multipliers of columns n .. n + 3 (n % 4 == 0) of row m: one draw
+EDTTS_DEV f4 drop_row4(const DropArgs& d, int m, int n) {
+  const U4 w = philox4x32_10(d.k0, d.k1, (unsigned)n >> 3, (unsigned)m, d.c2, 0u);
+  f4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = drop_mul(d, w, (n & 4) + r);
+  return o;
 }
 
 }  // namespace edtts

@@ -29,10 +29,12 @@ struct GemmArgs {
   const float* pe;    // EPI_PE: positional table [*][N], row = m % T
   int M, N, K, ldx, ldy, T;
   int vec_x, vec_w, vec_y;  // 16-byte loads / stores allowed (K % 4 == 0 and aligned rows; N, ldy % 4 == 0)
+  DropArgs dr;              // k_gen_gemm<EPI, true> only: the mask of its epilogue
 };
 constexpr int kGBM = 64, kGBN = 64, kGBK = 16, kGLd = kGBK + 1;
 
-template <int EPI>
+// (DROP: the training forward's dropout, EPI_SWIGLU / EPI_RESID only -- the epilogue multiplies its four columns by drop_row4)
+template <int EPI, bool DROP = false>
 __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
   __shared__ float xs[kGBM][kGLd];
   __shared__ float ws[kGBN][kGLd];
@@ -112,6 +114,11 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
         const float gt = acc[1][u][r] + (a.bias && ok ? a.bias[a.N + n + r] : 0.f);
         o[r] = v * silu(gt);
       }
+      if (DROP) {
+        const f4 dm = drop_row4(a.dr, m, n);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] *= dm[r];
+      }
       float* yp = a.Y + (size_t)m * a.ldy + n;
       if (a.vec_y && n + 3 < a.N) {
         stg4(yp, o);
@@ -142,6 +149,11 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (n + r < a.N) o[r] += pp[r];
+      }
+      if (DROP) {  // h = h + dropout(x W^T + b)
+        const f4 dm = drop_row4(a.dr, m, n);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] *= dm[r];
       }
       if (EPI == EPI_RESID) {  // h = h + (x W^T + b): the reference's residual order
         if (full) {
@@ -217,11 +229,14 @@ struct AttnArgs {
   const int64_t *q_len, *k_len;  // per-utterance query / key counts [B] (edtts_*_len), or null: Tq / Tk for all
   int q_dbl, k_dbl;              // ... given as token counts of which they are twice (see utt_len)
   float* lse;                    // training forward: log-sum-exp (exp2 domain) per [utterance][head][query], or null
+  DropArgs dr;                   // k_gen_attn<DT, true> only: the mask of the probabilities
 };
 // One wave = 16 queries of one (utterance, head).  S^T tile (16 keys x 16 queries) = K Q^T: lane (g, i) holds the scores of query i
 // against keys 4g + r.  P^T then is the B operand of O^T += V^T P^T as it stands when MFMA step s contracts keys {4g + s}: the V^T
 // operand of lane (g, d) reads V[key 4g + s][d].  Query statistics live on lane & 15; the four lane groups combine with two xor shuffles.
-template <int DT>
+// DROP (the training forward's dropout): l and the log-sum-exp come from the undropped probabilities; the B operand of
+// O^T += V^T P^T is p * keep * scale.
+template <int DT, bool DROP = false>
 __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
   const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
@@ -287,6 +302,11 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
     m = mn;
 #pragma unroll
     for (int t = 0; t < DT; ++t) acc[t] *= alpha;
+    if (DROP) {  // (key tiles start at lo + 16 n: aligned for every tile or for none)
+      const f4 dm = drop_attn_keys4(a.dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 4 * g, (lo & 3) == 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) p[r] *= dm[r];
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int key = j0 + 4 * g + s;
@@ -432,9 +452,10 @@ struct GenericLauncher {
 
   static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
   static unsigned grid_1d(size_t n) { const size_t nb = (n + 255) / 256; return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb)); }
+  // dr non-null (EPI_SWIGLU / EPI_RESID): the dropout instantiation, its epilogue masked with *dr
   template <int EPI>
   static int gemm(hipStream_t st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
-                  const float* pe = nullptr, int T = 1) {
+                  const float* pe = nullptr, int T = 1, const edtts::DropArgs* dr = nullptr) {
     using namespace edtts_gen;
     GemmArgs a;
     a.X = X; a.W = W; a.bias = bias; a.Y = Y; a.pe = pe; a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldy = ldy; a.T = T;
@@ -442,7 +463,16 @@ struct GenericLauncher {
     a.vec_w = (K % 4 == 0) && al16(W);
     a.vec_y = (ldy % 4 == 0) && al16(Y);
     const int nb = EPI == EPI_SWIGLU ? kGBN / 2 : kGBN;
-    hipLaunchKernelGGL(k_gen_gemm<EPI>, dim3((M + kGBM - 1) / kGBM, (N + nb - 1) / nb), dim3(256), 0, st, a);
+    a.dr = dr ? *dr : edtts::DropArgs{};
+    const dim3 grid((M + kGBM - 1) / kGBM, (N + nb - 1) / nb);
+    if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
+      if (dr) {
+        hipLaunchKernelGGL((k_gen_gemm<EPI, true>), grid, dim3(256), 0, st, a);
+        LAUNCH_CHECK("k_gen_gemm");
+        return EDTTS_OK;
+      }
+    }
+    hipLaunchKernelGGL(k_gen_gemm<EPI>, grid, dim3(256), 0, st, a);
     LAUNCH_CHECK("k_gen_gemm");
     return EDTTS_OK;
   }
@@ -455,12 +485,17 @@ struct GenericLauncher {
     return EDTTS_OK;
   }
   static int attn(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, float* o,
-                  int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl, float* lse = nullptr) {
+                  int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl, float* lse = nullptr,
+                  const edtts::DropArgs* dr = nullptr) {
     edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
-                          (int)q_dbl, (int)k_dbl, lse};
+                          (int)q_dbl, (int)k_dbl, lse, dr ? *dr : edtts::DropArgs{}};
     const dim3 grid((Tq + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
-#define EDTTS_GEN_ATTN(DT) case DT: hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a); break
+#define EDTTS_GEN_ATTN(DT)                                                                        \
+  case DT:                                                                                        \
+    if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn<DT, true>), grid, dim3(64), 0, st, a);     \
+    else hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a);                 \
+    break
       EDTTS_GEN_ATTN(1); EDTTS_GEN_ATTN(2); EDTTS_GEN_ATTN(3); EDTTS_GEN_ATTN(4);
       EDTTS_GEN_ATTN(5); EDTTS_GEN_ATTN(6); EDTTS_GEN_ATTN(7); EDTTS_GEN_ATTN(8);
 #undef EDTTS_GEN_ATTN

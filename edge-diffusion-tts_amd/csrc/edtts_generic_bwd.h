@@ -18,6 +18,9 @@
 //   k_bwd_attn_dkv<DT>    owns 16 keys of one head: dV = P^T dO, dK = scale dS^T Q over the query tiles that meet the band
 //   k_bwd_scatter_rows    embedding gradients: one block owns a table row and adds its positions in position order
 //   k_bwd_time_emb, k_bwd_gelu, k_bwd_gelu_grad   the time MLP's elementwise pieces (its contractions reuse k_bwd_gemm)
+// Dropout: k_gen_attn<DT, true> / k_gen_gemm<EPI, true> in the forward; k_bwd_attn_dq<DT, true> and
+// k_bwd_attn_dkv<DT, true> regenerate the attention masks, k_bwd_swiglu_drop and k_bwd_drop_rows the feed-forward ones.
+// k_drop_mask writes a mask out.
 #pragma once
 
 namespace edtts_bwd {
@@ -258,6 +261,54 @@ __global__ __launch_bounds__(256) void k_bwd_swiglu(float* u, const float* da, s
   }
 }
 
+// ... with dropout behind value * silu(gate): da is multiplied by that mask (site 2) first.  One thread per four columns.
+__global__ __launch_bounds__(256) void k_bwd_swiglu_drop(float* u, const float* da, size_t M, int FH, DropArgs dr) {
+  const int ng = (FH + 3) / 4;
+  const size_t n = M * ng;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / ng;
+    const int c0 = 4 * (int)(i - row * ng);
+    const f4 dm = drop_row4(dr, (int)row, c0);
+    float* ur = u + row * 2 * FH;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int c = c0 + r;
+      if (c >= FH) break;
+      const float v = ur[c], gt = ur[FH + c], d = da[row * FH + c] * dm[r];
+      const float sg = 1.0f / (1.0f + expf(-gt));
+      ur[c] = d * (gt * sg);
+      ur[FH + c] = d * v * (sg * (1.0f + gt * (1.0f - sg)));
+    }
+  }
+}
+// y[M][W] = x[M][W] o mask: the residual gradient entering the dropped down projection (site 3)
+__global__ __launch_bounds__(256) void k_bwd_drop_rows(const float* x, float* y, size_t M, int W, DropArgs dr) {
+  const int ng = (W + 3) / 4;
+  const size_t n = M * ng;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / ng;
+    const int c0 = 4 * (int)(i - row * ng);
+    const f4 dm = drop_row4(dr, (int)row, c0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (c0 + r < W) y[row * W + c0 + r] = x[row * W + c0 + r] * dm[r];
+  }
+}
+// edtts_dropout_mask: keep bytes of one site through the functions the kernels call.  Attention sites: rows = B heads Tq rows of
+// W = Tk keys (row = bh Tq + q); feed-forward sites: rows = B T rows of W columns.
+__global__ __launch_bounds__(256) void k_drop_mask(uint8_t* keep, size_t rows, int W, int Tq, int attn, DropArgs dr) {
+  const int ng = (W + 3) / 4;
+  const size_t n = rows * ng;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / ng;
+    const int c0 = 4 * (int)(i - row * ng);
+    const f4 dm = attn ? drop_attn_keys4(dr, (unsigned)(row / Tq), (int)(row % Tq), c0, true) : drop_row4(dr, (int)row, c0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (c0 + r < W) keep[row * W + c0 + r] = dm[r] != 0.f ? 1 : 0;
+  }
+}
+
 // ---- attention ---------------------------------------------------------------------------------------------------------------
 // delta[(b HEADS + hd) Tq + i] = sum_d dO[row][hd DH + d] O[row][hd DH + d]   (row = b Tq + i), d ascending
 __global__ __launch_bounds__(256) void k_bwd_attn_delta(const float* o, const float* dO, float* delta, int B, int Tq, int HEADS, int DH, int ld) {
@@ -279,10 +330,12 @@ struct AttnBwdArgs {
   float *dq, *dk, *dv;
   int ldq, ldkv, ldo, lddq, lddkv, Tq, Tk, DH, window;
   float scale, scale_nat;       // log2(e) / sqrt(head_dim) (scores as the forward forms them), 1 / sqrt(head_dim)
+  DropArgs dr;                  // the <DT, true> instantiations only: the forward's mask of the probabilities
 };
 // One wave = 16 queries of one (utterance, head), laid out as k_gen_attn: S^T = K Q^T and dP^T = V dO^T tiles hold (key 4g + r,
 // query fq) on lane (g, fq); dS^T is then the B operand of dQ^T += K^T dS^T as P^T is of O^T += V^T P^T in the forward.
-template <int DT>
+// DROP: O = (P o D) V with D = keep * scale regenerated here; dS = P o (D o dP - delta) (delta = rowsum(dO o O) as without dropout).
+template <int DT, bool DROP = false>
 __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
   const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
@@ -325,6 +378,11 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
       sc = EDTTS_MFMA(ok ? krow[d] : 0.f, qv[s], sc);
       dp = EDTTS_MFMA(ok ? vrow[d] : 0.f, dov[s], dp);
     }
+    if (DROP) {
+      const f4 dm = drop_attn_keys4(a.dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 4 * g, (lo & 3) == 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dp[r] *= dm[r];
+    }
     f4 ds;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -356,7 +414,8 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
 }
 // One wave = 16 keys of one (utterance, head).  S = Q K^T and dP = dO V^T tiles hold (query 4g + r, key fq) on lane (g, fq): P and
 // dS are the B operands of dV^T += dO^T P and dK^T += Q^T dS.  Only the query tiles that meet the band are visited.
-template <int DT>
+// DROP: dV^T += dO^T (P o D), dS as in k_bwd_attn_dq.
+template <int DT, bool DROP = false>
 __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
   const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
   const int k0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
@@ -399,6 +458,12 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
       sc = EDTTS_MFMA(ok ? qrow[d] : 0.f, kv[s], sc);
       dp = EDTTS_MFMA(ok ? drow[d] : 0.f, vv[s], dp);
     }
+    f4 dm;
+    if (DROP) {  // (query tiles start at lo + 16 n: odd for every tile or for none)
+      dm = drop_attn_queries4(a.dr, (unsigned)(b * gridDim.y + hd), i0 + 4 * g, kj, (lo & 1) != 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dp[r] *= dm[r];
+    }
     f4 p, ds;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -407,6 +472,10 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
       const int qs = qq < hi ? qq : 0;
       p[r] = ok ? exp2f(sc[r] - lb[qs]) : 0.f;
       ds[r] = p[r] * (dp[r] - eb[qs]);
+    }
+    if (DROP) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) p[r] *= dm[r];
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -578,6 +647,14 @@ static void make_train_scratch(const Layout& lo, int B, int T, int S, TrainScrat
   s->total = o;
 }
 
+// A validated EdttsDropout (include/edtts.h, "Dropout masks"): the key words, the threshold and the scale of the kept values.
+enum { DROP_ATTN = 0, DROP_CROSS = 1, DROP_ACT = 2, DROP_DOWN = 3 };
+struct DropState {
+  unsigned k0, k1, thr;
+  float scale;
+  DropArgs site(int layer, int site_id) const { return DropArgs{k0, k1, 0x30000u + 4u * (unsigned)layer + (unsigned)site_id, thr, scale}; }
+};
+
 // =========================================================================================================
 // TrainLauncher: forward with a tape, backward from it
 // =========================================================================================================
@@ -590,7 +667,10 @@ struct TrainLauncher {
 
   // GenericLauncher::ctx + GenericLauncher::forward (TAIL_EPS, no lengths): the same launches in the same order; what the backward
   // needs goes to the tape instead of the workspace, or is copied there.  The AdaLN rows are already in the tape (launch_cond).
-  static int forward(const CallCtx& c, float* tp, const TrainTape& tt, const float* x, const int64_t* sem_idx, const float* sem_feat, float* eps) {
+  // drop non-null: the four dropout sites of every block run their masked instantiations (the tape's attention outputs and SwiGLU
+  // output are then the dropped ones); null: exactly the launches described above.
+  static int forward(const CallCtx& c, float* tp, const TrainTape& tt, const float* x, const int64_t* sem_idx, const float* sem_feat, float* eps,
+                     const DropState* drop = nullptr) {
     using namespace edtts_gen;
     const Layout& lo = c.lo;
     const Workspace& ws = c.ws;
@@ -626,20 +706,25 @@ struct TrainLauncher {
       const LayerLayout& y = lo.layer[l];
       const TapeLayer& z = tt.layer[l];
       float *qkv = tp + z.qkv, *kv = tp + z.kv;
+      DropArgs dra[4];
+      for (int i = 0; i < 4; ++i) dra[i] = drop ? drop->site(l, i) : DropArgs{};
+      auto D = [&](int i) -> const DropArgs* { return drop ? &dra[i] : nullptr; };
       TRY_G(copy(st, tp + z.h0, h, MH));
       TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, qkv, 3 * H, M, 3 * H, H));
-      TRY_G(G::attn(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, T, T, c.window, nullptr, nullptr, false, false, tp + z.lse1));
+      TRY_G(G::attn(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, T, T, c.window, nullptr, nullptr, false, false, tp + z.lse1,
+                    D(DROP_ATTN)));
       TRY_G(G::gemm<EPI_RESID>(st, tp + z.att1, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
       TRY_G(copy(st, tp + z.h1, h, MH));
       TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, tp + z.qc, H, M, H, H));
-      TRY_G(G::attn(st, lo, B, tp + z.qc, H, kv, kv + H, 2 * H, tp + z.att2, T, S, -1, nullptr, nullptr, false, false, tp + z.lse2));
+      TRY_G(G::attn(st, lo, B, tp + z.qc, H, kv, kv + H, 2 * H, tp + z.att2, T, S, -1, nullptr, nullptr, false, false, tp + z.lse2,
+                    D(DROP_CROSS)));
       TRY_G(G::gemm<EPI_RESID>(st, tp + z.att2, H, blob + y.g_op, nullptr, h, H, M, H, H));
       TRY_G(copy(st, tp + z.h2, h, MH));
       TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cond_bstride));
-      TRY_G(G::gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, tp + z.act, FH, M, FH, H));
-      TRY_G(G::gemm<EPI_RESID>(st, tp + z.act, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH));
+      TRY_G(G::gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, tp + z.act, FH, M, FH, H, nullptr, 1, D(DROP_ACT)));
+      TRY_G(G::gemm<EPI_RESID>(st, tp + z.act, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH, nullptr, 1, D(DROP_DOWN)));
     }
     TRY_G(copy(st, tp + tt.hL, h, MH));
     TRY_G(G::norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
@@ -715,19 +800,24 @@ struct TrainLauncher {
   // gradients of one attention call: dq, dk, dv from q, k, v, the output o, its gradient dO and the tape's log-sum-exp
   static int attn_bwd(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, const float* o,
                       const float* dO, const float* lse, float* delta, float* dq, int lddq, float* dk, float* dv, int lddkv, int Tq, int Tk,
-                      int window) {
+                      int window, const DropArgs* dr = nullptr) {
     const size_t n = (size_t)B * lo.HEADS * Tq;
     hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, lo.HEADS, lo.DH, lo.H);
     LAUNCH_CHECK("k_bwd_attn_delta");
     const float sn = 1.0f / sqrtf((float)lo.DH);
     edtts_bwd::AttnBwdArgs a{q, k, v, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
-                             1.4426950408889634f / sqrtf((float)lo.DH), sn};
+                             1.4426950408889634f / sqrtf((float)lo.DH), sn, dr ? *dr : DropArgs{}};
     const dim3 gq((Tq + 15) / 16, lo.HEADS, B), gk((Tk + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
 #define EDTTS_BWD_ATTN(DT)                                                                      \
   case DT:                                                                                      \
-    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dq<DT>, gq, dim3(64), 0, st, a);                   \
-    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dkv<DT>, gk, dim3(64), 0, st, a);                  \
+    if (dr) {                                                                                   \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq<DT, true>), gq, dim3(64), 0, st, a);         \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv<DT, true>), gk, dim3(64), 0, st, a);        \
+    } else {                                                                                    \
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dq<DT>, gq, dim3(64), 0, st, a);                 \
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dkv<DT>, gk, dim3(64), 0, st, a);                \
+    }                                                                                           \
     break
       EDTTS_BWD_ATTN(1); EDTTS_BWD_ATTN(2); EDTTS_BWD_ATTN(3); EDTTS_BWD_ATTN(4);
       EDTTS_BWD_ATTN(5); EDTTS_BWD_ATTN(6); EDTTS_BWD_ATTN(7); EDTTS_BWD_ATTN(8);
@@ -742,7 +832,7 @@ struct TrainLauncher {
   // gs: gradient destinations in edtts_pack_weights slot order (null: not wanted).
   static int backward(const Layout& lo, const float* blob, const float* tp, const TrainTape& tt, float* sc, const TrainScratch& ss, int B, int T,
                       int S, int window, const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_feat,
-                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t st) {
+                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t st, const DropState* drop = nullptr) {
     using namespace edtts_gen;
     const int M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL, L = lo.L;
     float *dh = sc + ss.dh, *xn = sc + ss.xn, *ga = sc + ss.ga, *gq = sc + ss.gq, *big = sc + ss.big, *da = sc + ss.da;
@@ -764,13 +854,28 @@ struct TrainLauncher {
       const LayerLayout& y = lo.layer[l];
       const TapeLayer& z = tt.layer[l];
       auto W = [&](int i) { return gs[G_COUNT + l * L_COUNT + i]; };
+      DropArgs dra[4];
+      for (int i = 0; i < 4; ++i) dra[i] = drop ? drop->site(l, i) : DropArgs{};
+      auto D = [&](int i) -> const DropArgs* { return drop ? &dra[i] : nullptr; };
       // feed-forward branch: h3 = h2 + down(value * silu(gate)) + b
-      TRY_G(colsum(st, dh, H, M, H, W(L_DOWN_B), part));
-      TRY_G(dw(st, dh, H, tp + z.act, FH, M, H, FH, W(L_DOWN_W), part));
-      TRY_G(dx(st, dh, H, blob + y.g_down, M, H, FH, da, FH, false));
+      // (dropout: h3 = h2 + mask3 o (down(act) + b) with act = mask2 o (value * silu(gate)) on the tape: the residual gradient is
+      // masked once into gq, free until the cross-attention branch, and that copy feeds the bias sum, dW_down and dX)
+      const float* dd = dh;
+      if (drop) {
+        hipLaunchKernelGGL(edtts_bwd::k_bwd_drop_rows, dim3(G::grid_1d(((size_t)M * H + 3) / 4)), dim3(256), 0, st, dh, gq, (size_t)M, H, dra[DROP_DOWN]);
+        LAUNCH_CHECK("k_bwd_drop_rows");
+        dd = gq;
+      }
+      TRY_G(colsum(st, dd, H, M, H, W(L_DOWN_B), part));
+      TRY_G(dw(st, dd, H, tp + z.act, FH, M, H, FH, W(L_DOWN_W), part));
+      TRY_G(dx(st, dd, H, blob + y.g_down, M, H, FH, da, FH, false));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h2, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cb));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_up, blob + y.up_b, big, 2 * FH, M, 2 * FH, H));
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu, dim3(G::grid_1d((size_t)M * FH)), dim3(256), 0, st, big, da, (size_t)M, FH);
+      if (drop)
+        hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu_drop, dim3(G::grid_1d(((size_t)M * FH + 3) / 4)), dim3(256), 0, st, big, da, (size_t)M, FH,
+                           dra[DROP_ACT]);
+      else
+        hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu, dim3(G::grid_1d((size_t)M * FH)), dim3(256), 0, st, big, da, (size_t)M, FH);
       LAUNCH_CHECK("k_bwd_swiglu");
       TRY_G(colsum(st, big, 2 * FH, M, 2 * FH, W(L_UP_B), part));
       TRY_G(dw(st, big, 2 * FH, xn, H, M, 2 * FH, H, W(L_UP_W), part));
@@ -781,7 +886,7 @@ struct TrainLauncher {
       TRY_G(dw(st, dh, H, tp + z.att2, H, M, H, H, W(L_OP_W), part));
       TRY_G(dx(st, dh, H, blob + y.g_op, M, H, H, ga, H, false));
       TRY_G(attn_bwd(st, lo, B, tp + z.qc, H, tp + z.kv, tp + z.kv + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
-                     S, -1));
+                     S, -1, D(DROP_CROSS)));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h1, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
       TRY_G(dw(st, gq, H, xn, H, M, H, H, W(L_QP_W), part));
       TRY_G(dx(st, gq, H, blob + y.g_qp, M, H, H, ga, H, false));
@@ -800,7 +905,7 @@ struct TrainLauncher {
       TRY_G(dx(st, dh, H, blob + y.g_proj, M, H, H, ga, H, false));
       const float* qkv = tp + z.qkv;
       TRY_G(attn_bwd(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, ga, tp + z.lse1, delta, big, 3 * H, big + H, big + 2 * H,
-                     3 * H, T, T, window));
+                     3 * H, T, T, window, D(DROP_ATTN)));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h0, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cb));
       TRY_G(dw(st, big, 3 * H, xn, H, M, 3 * H, H, W(L_QKV_W), part));
       TRY_G(dx(st, big, 3 * H, blob + y.s_qkv, M, 3 * H, H, ga, H, false));

@@ -3245,12 +3245,37 @@ int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t
   return EDTTS_OK;
 }
 
+// EdttsDropout -> DropState.  *on = false for NULL or p == 0 (the call then makes exactly the launches of its plain twin).
+static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on) {
+  *on = false;
+  if (!drop || drop->p == 0.0f) return EDTTS_OK;
+  const float p = drop->p;
+  const double thr = nearbyint((double)p * 65536.0);  // (ties to even, as round() of the tests' restatement)
+  if (!(p >= 0.0f && p < 1.0f) || thr > 65535.0)
+    return fail(EDTTS_ERR_ARG, "%s: dropout p=%g is outside [0, 1) (needs round(p * 65536) <= 65535)", who, (double)p);
+  ds->k0 = (unsigned)drop->seed;
+  ds->k1 = (unsigned)(drop->seed >> 32);
+  ds->thr = (unsigned)thr;
+  ds->scale = 65536.0f / (float)(65536u - ds->thr);
+  *on = true;
+  return EDTTS_OK;
+}
+
 int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S, const float* x,
                                 const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, float* eps,
                                 void* stream) {
+  return edtts_decoder_forward_train_drop(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, nullptr, stream);
+}
+
+int edtts_decoder_forward_train_drop(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                     const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                     const float* sem_features, float* eps, const EdttsDropout* drop, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(train_layout(dims, "edtts_decoder_forward_train", &lo));
+  DropState ds;
+  bool dropping;
+  TRY(drop_state(drop, "edtts_decoder_forward_train_drop", &ds, &dropping));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
   if (!packed || !workspace || !tape || !x || !t || !eps) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   TRY(check_shapes(lo, B, T, S));
@@ -3264,14 +3289,25 @@ int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void*
   make_tape(lo, B, T, S, &tt);
   TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, tp + tt.cond, wsb, st));  // the AdaLN rows and t_cond go straight to the tape
   const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{}, st};
-  return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps);
+  return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps, dropping ? &ds : nullptr);
 }
 
 int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S, const float* x,
                            const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, const float* d_eps,
                            void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch, void* stream) {
+  return edtts_decoder_backward_drop(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots,
+                                     d_x, d_sem_features, scratch, nullptr, stream);
+}
+
+int edtts_decoder_backward_drop(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                                const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                                const EdttsDropout* drop, void* stream) {
   Layout lo;
   TRY(train_layout(dims, "edtts_decoder_backward", &lo));
+  DropState ds;
+  bool dropping;
+  TRY(drop_state(drop, "edtts_decoder_backward_drop", &ds, &dropping));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
   if (!packed || !workspace || !tape || !x || !t || !d_eps || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
@@ -3282,7 +3318,27 @@ int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* work
   make_train_scratch(lo, B, T, S, &ss);
   return TrainLauncher::backward(lo, (const float*)packed, (const float*)tape, tt, (float*)scratch, ss, B, T, S, dims->window, x, t, step_idx,
                                  sem_features ? nullptr : sem_idx, sem_features, d_eps, reinterpret_cast<float* const*>(grad_slots), d_x,
-                                 d_sem_features, (hipStream_t)stream);
+                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr);
+}
+
+int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+  Layout lo;
+  TRY(train_layout(dims, "edtts_dropout_mask", &lo));
+  if (!drop) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: drop is NULL");
+  DropState ds{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0u, 1.0f};  // (p == 0: threshold 0, everything kept)
+  bool dropping;
+  TRY(drop_state(drop, "edtts_dropout_mask", &ds, &dropping));
+  if (site < DROP_ATTN || site > DROP_DOWN) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: site %d is not one of 0 .. 3", site);
+  if (layer < 0 || layer >= lo.L) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: layer %d outside [0, %d)", layer, lo.L);
+  if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  TRY(check_shapes(lo, B, T, S));
+  const bool attn = site == DROP_ATTN || site == DROP_CROSS;
+  const size_t rows = attn ? (size_t)B * lo.HEADS * T : (size_t)B * T;
+  const int W = site == DROP_ATTN ? T : site == DROP_CROSS ? S : site == DROP_ACT ? lo.FM * lo.H : lo.H;
+  hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * ((W + 3) / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows,
+                     W, T, (int)attn, ds.site(layer, site));
+  LAUNCH_CHECK("k_drop_mask");
+  return EDTTS_OK;
 }
 
 int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,

@@ -5,7 +5,8 @@ The module owns parameters and buffers under the reference's state-dict key name
 device pointers to the C ABI (include/edtts.h, edtts_decoder_forward) where the whole network runs as hand-written
 gfx950 kernels.  By default inference only (the reference path this replaces runs under ``torch.no_grad``, inference.py:23);
 dropout is the identity as in ``decoder.eval()``.  ``autograd=True`` (generic fp32 kernels) adds the backward the reference's
-trainers need (train_v2.py train_step, training/consistency.py): DESIGN.md section 19.
+trainers need (train_v2.py train_step, training/consistency.py): DESIGN.md section 19.  ``train_dropout=True`` adds the reference's
+four dropout sites to that training forward and backward, with masks from the library's Philox stream: DESIGN.md section 20.
 """
 from __future__ import annotations
 
@@ -39,10 +40,12 @@ def _attach(root: nn.Module, key: str, tensor: torch.Tensor, is_buffer: bool) ->
 
 class _DecoderGrad(torch.autograd.Function):
     """eps = decoder(...) on the training forward (edtts_decoder_forward_train); backward through edtts_decoder_backward.  The tape is
-    a tensor of this call's own, saved in ctx: any number of forwards may share the decoder's cached workspace before a backward."""
+    a tensor of this call's own, saved in ctx: any number of forwards may share the decoder's cached workspace before a backward.
+    ``drop``: None, or the (p, seed) pair of this call's dropout masks; it lives in ctx, so the backward regenerates the masks of
+    ITS forward whatever the decoder has run since."""
 
     @staticmethod
-    def forward(ctx, dec, t, sem_idx, step_idx, names, x_t, sem_features, *params):
+    def forward(ctx, dec, t, sem_idx, step_idx, names, drop, x_t, sem_features, *params):
         B, T, _ = x_t.shape
         S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
         dims = dec.dims()
@@ -54,8 +57,8 @@ class _DecoderGrad(torch.autograd.Function):
         sem_idx = None if sem_features is not None or sem_idx is None else sem_idx.contiguous()
         feats = None if sem_features is None else sem_features.detach().contiguous()
         tape = torch.empty(native.train_tape_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
-        eps = native.decoder_forward_train(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, S)
-        ctx.dec, ctx.names, ctx.S, ctx.sig = dec, names, S, dec._packed_sig
+        eps = native.decoder_forward_train(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, S, drop)
+        ctx.dec, ctx.names, ctx.S, ctx.sig, ctx.drop = dec, names, S, dec._packed_sig, drop
         ctx.inputs = (x, t, step_idx, sem_idx, feats)
         ctx.save_for_backward(tape, *params)
         return eps
@@ -71,18 +74,18 @@ class _DecoderGrad(torch.autograd.Function):
         B, T, _ = x.shape
         dims, packed = dec.dims(), dec._packed
         ws = dec.workspace(B, T, ctx.S, B, x.device)
-        wanted = {n: p for n, p, need in zip(ctx.names, params, ctx.needs_input_grad[7:]) if need and dec._enters_output(n, feats is not None, step_idx is not None)}
+        wanted = {n: p for n, p, need in zip(ctx.names, params, ctx.needs_input_grad[8:]) if need and dec._enters_output(n, feats is not None, step_idx is not None)}
         out = {n: torch.empty_like(p) for n, p in wanted.items()}
         slots = [out.get(dec._slot_param(n)) for n in native.slot_names(dec.cfg.layers)]
-        d_x = torch.empty_like(x) if ctx.needs_input_grad[5] else None
-        d_f = torch.empty_like(feats) if feats is not None and ctx.needs_input_grad[6] else None
-        native.decoder_backward(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, ctx.S, d_eps.contiguous(), slots, d_x, d_f)
-        return (None, None, None, None, None, d_x, d_f, *[out.get(n) for n in ctx.names])
+        d_x = torch.empty_like(x) if ctx.needs_input_grad[6] else None
+        d_f = torch.empty_like(feats) if feats is not None and ctx.needs_input_grad[7] else None
+        native.decoder_backward(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, ctx.S, d_eps.contiguous(), slots, d_x, d_f, ctx.drop)
+        return (None, None, None, None, None, None, d_x, d_f, *[out.get(n) for n in ctx.names])
 
 
 class EdgeDiffusionDecoder(nn.Module):
     def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled",
-                 autograd: bool = False):
+                 autograd: bool = False, train_dropout: bool = False):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
@@ -93,9 +96,22 @@ class EdgeDiffusionDecoder(nn.Module):
         (include/edtts.h: EDTTS_KERNELS_*).  The generic kernels are fp32 only.
         ``autograd``: False (default) -- ``forward`` is inference only, as before.  True (needs ``kernels="generic"`` and fp32) --
         the parameters require grad, and a ``forward`` under grad mode whose parameters, ``x_t`` or ``sem_features`` require grad is
-        differentiable: it runs the training forward and hands ``backward()`` to the backward kernels."""
+        differentiable: it runs the training forward and hands ``backward()`` to the backward kernels.
+        ``train_dropout``: False (default) -- a differentiable forward in training mode with ``cfg.dropout > 0`` raises, as before.
+        True (needs ``autograd=True``) -- that forward applies the reference's dropout (attention probabilities of both attentions,
+        after SwiGLU, after the FFN's down projection) with ``p = cfg.dropout``; each such forward draws a 63-bit seed on the host
+        from ``self.dropout_generator`` (a CPU ``torch.Generator``; None, the default: torch's default CPU generator, so
+        ``torch.manual_seed`` makes a run repeatable), keeps it for its own backward and shows it as ``self.last_dropout_seed``.
+        The masks are the library's (include/edtts.h, "Dropout masks"), not torch's random stream.  ``.eval()``, ``cfg.dropout ==
+        0`` and calls that are not differentiable are unchanged; in particular a training-mode call under ``torch.no_grad()`` runs
+        the inference forward WITHOUT dropout (the reference would drop there too): DESIGN.md section 20."""
         super().__init__()
         self.autograd = bool(autograd)
+        self.train_dropout = bool(train_dropout)
+        if self.train_dropout and not self.autograd:
+            raise ValueError("train_dropout=True needs autograd=True (dropout belongs to the training forward and its backward)")
+        self.dropout_generator: Optional[torch.Generator] = None
+        self.last_dropout_seed: Optional[int] = None
         if self.autograd and kernels != "generic":
             raise ValueError(f"autograd=True needs kernels='generic' (the backward differentiates the generic kernels), got {kernels!r}")
         if self.autograd and native.COMPUTE_DTYPES.get(compute_dtype) != native.COMPUTE_DTYPES["f32"]:
@@ -404,11 +420,17 @@ class EdgeDiffusionDecoder(nn.Module):
             raise ValueError("Either sem_idx or sem_features must be provided")
         if x_lengths is not None or sem_lengths is not None:
             raise ValueError("autograd=True: x_lengths / sem_lengths are not supported by the backward (pad-free batches only)")
-        if self.training and self.cfg.dropout > 0:
+        drop = None
+        if self.training and self.cfg.dropout > 0 and self.train_dropout:
+            # (a host draw from a CPU generator: no device work, no synchronisation)
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator).item())
+            drop = (float(self.cfg.dropout), seed)
+            self.last_dropout_seed = seed
+        elif self.training and self.cfg.dropout > 0:
             raise ValueError(f"autograd=True: the kernels have no dropout but cfg.dropout={self.cfg.dropout} and the decoder is in "
                              "training mode (the reference applies attention and FFN dropout there): set cfg.dropout = 0 or call .eval()")
         names, params = self._named_params()
-        return _DecoderGrad.apply(self, t, sem_idx, step_idx, names, x_t, sem_features, *params)
+        return _DecoderGrad.apply(self, t, sem_idx, step_idx, names, drop, x_t, sem_features, *params)
 
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, sem_idx: Optional[torch.Tensor] = None,

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "edtts_mel_to_spec_len", "edtts_griffin_lim_len",
     "edtts_train_tape_bytes", "edtts_train_scratch_bytes", "edtts_train_dw_slab_rows", "edtts_decoder_forward_train",
     "edtts_decoder_backward",
+    "edtts_decoder_forward_train_drop", "edtts_decoder_backward_drop", "edtts_dropout_mask",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -40,6 +41,14 @@ class EdttsDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "hidden", "layers", "heads", "n_mels", "ffn_mult", "codebook_size", "semantic_dim", "window", "max_pos",
         "max_ctx_pos", "n_step_emb", "compute_dtype")]
+
+
+class EdttsDropout(C.Structure):
+    """include/edtts.h: EdttsDropout -- drop probability and Philox key of one training forward and its backward."""
+    _fields_ = [("p", C.c_float), ("seed", C.c_uint64)]
+
+
+DROP_SITES = {"attn": 0, "cross_attn": 1, "ffn_act": 2, "ffn_out": 3}  # include/edtts.h, "Dropout masks": site ids
 
 
 SEM_FSQ, SEM_VQ = 0, 1  # EdttsSemDims.quantizer (include/edtts.h: EDTTS_SEM_*)
@@ -164,6 +173,11 @@ def lib() -> C.CDLL:
     L.edtts_decoder_forward_train.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.edtts_decoder_backward.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
                                          vp, vp, vp, vp]
+    dpp = C.POINTER(EdttsDropout)
+    L.edtts_decoder_forward_train_drop.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, dpp, vp]
+    L.edtts_decoder_backward_drop.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
+                                              vp, vp, vp, dpp, vp]
+    L.edtts_dropout_mask.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, i32, i32, dpp, vp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -296,16 +310,29 @@ def train_dw_slab_rows(rows: int) -> int:
     return int(lib().edtts_train_dw_slab_rows(int(rows)))
 
 
+def _dropout(drop) -> Optional[EdttsDropout]:
+    """None, an EdttsDropout or a (p, seed) pair -> None or an EdttsDropout."""
+    if drop is None or isinstance(drop, EdttsDropout):
+        return drop
+    p, seed = drop
+    return EdttsDropout(float(p), int(seed))
+
+
 def decoder_forward_train(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, tape: torch.Tensor, x: torch.Tensor,
                           t: torch.Tensor, step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor],
-                          sem_features: Optional[torch.Tensor], S: int) -> torch.Tensor:
-    """edtts_decoder_forward_train: eps, with the backward's tape written to `tape` (uint8, train_tape_bytes)."""
+                          sem_features: Optional[torch.Tensor], S: int, drop=None) -> torch.Tensor:
+    """edtts_decoder_forward_train: eps, with the backward's tape written to `tape` (uint8, train_tape_bytes).  ``drop``: None (the
+    plain export), or an EdttsDropout / (p, seed) pair -> edtts_decoder_forward_train_drop."""
     B, T, M = x.shape
     eps = torch.empty_like(x)
-    lib().edtts_decoder_forward_train(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
-                                      _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"),
-                                      _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                                      _dev_ptr(sem_features, torch.float32, "sem_features"), eps.data_ptr(), _stream(x.device))
+    drop = _dropout(drop)
+    args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
+            _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"),
+            _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"), eps.data_ptr())
+    if drop is None:
+        lib().edtts_decoder_forward_train(*args, _stream(x.device))
+    else:
+        lib().edtts_decoder_forward_train_drop(*args, C.byref(drop), _stream(x.device))
     check_indices(workspace)
     return eps
 
@@ -313,17 +340,37 @@ def decoder_forward_train(dims: EdttsDims, packed: torch.Tensor, workspace: torc
 def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, tape: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
                      step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor], S: int,
                      d_eps: torch.Tensor, grads: Sequence[Optional[torch.Tensor]], d_x: Optional[torch.Tensor],
-                     d_sem_features: Optional[torch.Tensor]) -> None:
-    """edtts_decoder_backward: writes the gradient of every non-None entry of `grads` (slot order), d_x and d_sem_features."""
+                     d_sem_features: Optional[torch.Tensor], drop=None) -> None:
+    """edtts_decoder_backward: writes the gradient of every non-None entry of `grads` (slot order), d_x and d_sem_features.
+    ``drop``: what the forward that filled `tape` was given (None: the plain export, else edtts_decoder_backward_drop)."""
     B, T, M = x.shape
     ptrs = (C.c_void_p * len(grads))(*[_dev_ptr(g, torch.float32, f"grad[{i}]") for i, g in enumerate(grads)])
     scratch = torch.empty(train_scratch_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
-    lib().edtts_decoder_backward(C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
-                                 _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"),
-                                 _dev_ptr(step_idx, torch.int64, "step_idx"), _dev_ptr(sem_idx, torch.int64, "sem_idx"),
-                                 _dev_ptr(sem_features, torch.float32, "sem_features"), _dev_ptr(d_eps, torch.float32, "d_eps"), ptrs,
-                                 len(grads), _dev_ptr(d_x, torch.float32, "d_x"),
-                                 _dev_ptr(d_sem_features, torch.float32, "d_sem_features"), scratch.data_ptr(), _stream(x.device))
+    drop = _dropout(drop)
+    args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
+            _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"),
+            _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"),
+            _dev_ptr(d_eps, torch.float32, "d_eps"), ptrs, len(grads), _dev_ptr(d_x, torch.float32, "d_x"),
+            _dev_ptr(d_sem_features, torch.float32, "d_sem_features"), scratch.data_ptr())
+    if drop is None:
+        lib().edtts_decoder_backward(*args, _stream(x.device))
+    else:
+        lib().edtts_decoder_backward_drop(*args, C.byref(drop), _stream(x.device))
+
+
+def dropout_mask(dims: EdttsDims, site: int, layer: int, B: int, T: int, S: int, p: float, seed: int, device="cuda") -> torch.Tensor:
+    """edtts_dropout_mask: the keep mask (uint8, 1 = kept) of one dropout site of one layer, from the device functions the training
+    kernels call: [B, heads, T, T] (site 0), [B, heads, T, S] (1), [B * T, ffn_mult * hidden] (2) or [B * T, hidden] (3)."""
+    shape = {0: (B, dims.heads, T, T), 1: (B, dims.heads, T, S), 2: (B * T, dims.ffn_mult * dims.hidden), 3: (B * T, dims.hidden)}.get(int(site))
+    if shape is None:
+        raise ValueError(f"site must be one of 0 .. 3 (DROP_SITES), got {site!r}")
+    drop = EdttsDropout(float(p), int(seed))
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise EdttsError(f"dropout_mask: expected a HIP device, got {dev} -- there is no CPU fallback")
+    keep = torch.empty(shape, dtype=torch.uint8, device=dev)
+    lib().edtts_dropout_mask(C.byref(dims), int(site), int(layer), B, T, S, C.byref(drop), keep.data_ptr(), _stream(dev))
+    return keep
 
 
 def generate(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, sem_idx: torch.Tensor, x_T: torch.Tensor,

@@ -146,8 +146,8 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
  * For train.py / train_v2.py / training/consistency.py, whose steps call decoder(x_t, t, ...) under autograd (train_v2.py
  * train_step; training/consistency.py consistency_loss calls it twice before one backward()).  First version: generic kernels
  * and fp32 only -- dims.compute_dtype must be EDTTS_F32 | EDTTS_KERNELS_GENERIC, anything else is EDTTS_ERR_UNSUPPORTED with a
- * message naming the cause -- dropout off (decoder.eval() arithmetic: layers/attention.py and layers/transformer.py apply
- * dropout only when training) and no per-utterance lengths.  Conventions as everywhere: no allocation, no host synchronisation,
+ * message naming the cause -- and no per-utterance lengths.  These entry points run the decoder.eval() arithmetic (dropout off:
+ * layers/attention.py and layers/transformer.py apply dropout only when training); the *_drop twins below add the dropout.  Conventions as everywhere: no allocation, no host synchronisation,
  * work only on `stream`, graph-capturable.  Every reduction has a fixed order: a backward is bitwise reproducible.
  *
  * edtts_train_tape_bytes: size of the caller-owned tape one forward_train call fills and its backward reads (per layer: the
@@ -180,6 +180,45 @@ int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* work
                            const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
                            const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
                            float* d_sem_features, void* scratch, void* stream);
+
+/* ---- training with dropout: Philox masks in the forward and the backward ------------------------------
+ * The reference's trainers run decoder.train() with CFG.dropout = 0.2, which drops at four places of every block: the
+ * self-attention probabilities after the softmax (layers/attention.py:106-119), the cross-attention probabilities
+ * (layers/mla.py:174-190), the SwiGLU output (layers/transformer.py:43) and the FFN's down projection (:45).  The *_drop entry
+ * points run that arithmetic with masks of the library's own: torch's random stream is not reproduced.
+ *
+ * Dropout masks.  thr = round(p * 65536) (ties to even); valid are 0 <= p < 1 with thr <= 65535, anything else is EDTTS_ERR_ARG
+ * with a message naming p.  The effective probability is p_eff = thr / 65536 (p = 0.2: 13107 / 65536).  An element is KEPT iff its
+ * 16-bit field is >= thr; kept values are multiplied by 1 / (1 - p_eff).  One draw is Philox4x32-10 with key = (seed lo, seed hi) and
+ * counter = (c0, c1, c2, c3) -- the rounds of the noise generator above -- and yields eight 16-bit fields: field j is bits
+ * [16 (j & 1), +16) of output word j >> 1.  Site ids: 0 self-attention probabilities, 1 cross-attention probabilities, 2 after
+ * SwiGLU (width ffn_mult * hidden), 3 after ffn.net.3 (width hidden).  The stream word is c2 = 0x30000 + 4 * layer + site, and
+ *     sites 0, 1, utterance b, head h, query q, key k:   c0 = k >> 2, c1 = q >> 1, c3 = b * heads + h, field 4 * (q & 1) + (k & 3)
+ *     sites 2, 3, row m = b * T + t, column n:           c0 = n >> 3, c1 = m,      c3 = 0,             field n & 7
+ * A mask is a pure function of (seed, site, layer, position): it does not depend on tile shapes, wave counts or launch geometry,
+ * the backward regenerates it instead of reading it back, and a test can rebuild it on the host.
+ *
+ * drop == NULL or drop->p == 0: exactly the launches of the plain entry point, bitwise its results (the plain entry points ARE these
+ * calls with NULL).  The backward must be given the EdttsDropout its forward was given.  Tape and scratch sizes are those of the
+ * plain calls (the dropped activations take the place of the undropped ones on the tape).  The seed travels BY VALUE in the
+ * kernel arguments: no allocation, no host synchronisation, work only on `stream`, and a captured graph replays the masks it was
+ * captured with (re-capture, or update the kernel node parameters, to advance them).
+ *
+ * edtts_dropout_mask writes the keep mask of one (site, layer) as 0 / 1 bytes through the device functions the kernels call:
+ * [B, heads, T, T] (site 0), [B, heads, T, S] (site 1), [B * T, ffn_mult * hidden] (site 2) or [B * T, hidden] (site 3). */
+typedef struct EdttsDropout {
+  float p;       /* drop probability, see above */
+  uint64_t seed; /* Philox key */
+} EdttsDropout;
+int edtts_decoder_forward_train_drop(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                     const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                     const float* sem_features, float* eps, const EdttsDropout* drop, void* stream);
+int edtts_decoder_backward_drop(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
+                                float* d_sem_features, void* scratch, const EdttsDropout* drop, void* stream);
+int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep,
+                       void* stream);
 
 /* ---- per-utterance lengths (ragged batches) -----------------------------------------------------------------------------
  * The *_len entry points below take the arguments of their twins plus device int64 [B] length arrays: t_len (frames T_b) and
@@ -263,6 +302,8 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
  *     0x10000 + step      ancestral noise of step `step` inside edtts_sample_ddpm
  *     0x20000 + step      q_sample noise of the known frames at step `step` inside edtts_sample_inpaint and
  *                         edtts_sample_inpaint_multistep_len (one sampler or the other runs on a seed: the same draws)
+ *     0x30000 + 4 * layer + site   dropout masks of the training forward and backward (edtts_decoder_forward_train_drop; layers
+ *                         <= 32: [0x30000, 0x30080)), keyed by position as described there, not by global element
  * edtts_randn rejects stream_id >= 0x10000. */
 int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_t elem_offset, float scale, void* stream);
 /* One launch for B rows with a seed each: out [B, n_per_row], row b bitwise what edtts_randn(n_per_row, seeds[b], stream_id, offset 0,

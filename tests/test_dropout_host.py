@@ -1,0 +1,220 @@
+"""Training with dropout, host side (no GPU): the mask contract of include/edtts.h ("Dropout masks") as tests/dropout_util.py
+restates it, the masked oracle against the reference's own gradients under those masks (tests/golden/train_dropout.npz, made by
+tests/golden/make_golden_dropout.py), the train_dropout option's validation, and the C ABI's new entry points."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import dropout_util as U
+from conftest import REPO
+from edge_diffusion_tts_amd import CFG, EdgeDiffusionDecoder, native, synth_state_dict
+from oracle import edtts_oracle as O
+from train_util import case, rel_err
+
+NEW_SYMBOLS = ("edtts_decoder_forward_train_drop", "edtts_decoder_backward_drop", "edtts_dropout_mask")
+
+
+def test_philox_known_answers():
+    kat = (((0, 0, 0, 0), (0, 0), "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),
+           ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, "408f276d 41c83b0e a20bc7c6 6d5451fd"),
+           ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0), "d16cfe09 94fdcceb 5001e420 24126ea1"))
+    for counter, key, want in kat:
+        assert " ".join("%08x" % int(w) for w in U.philox4x32_10(key, counter)) == want
+
+
+def test_field_extraction_and_block_keying():
+    words = tuple(np.uint64(v) for v in (0x11112222, 0x33334444, 0x55556666, 0x77778888))
+    assert [int(U.field(words, j)) for j in range(8)] == [0x2222, 0x1111, 0x4444, 0x3333, 0x6666, 0x5555, 0x8888, 0x7777]
+    seed, layer = 0x0123456789ABCDEF, 1
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    # attention: element (b, h, q, k) is field 4 (q & 1) + (k & 3) of the draw (k >> 2, q >> 1, stream, b heads + h)
+    B, heads, T = 2, 3, 11
+    keep = U.attn_keep(seed, 0.5, layer, U.SITE_CROSS, B, heads, T, 9)
+    for b, h, q, k in ((0, 0, 0, 0), (1, 2, 7, 5), (1, 0, 10, 8), (0, 1, 3, 3)):
+        w = U.philox4x32_10(key, (k >> 2, q >> 1, 0x30000 + 4 * layer + 1, b * heads + h))
+        j = 4 * (q & 1) + (k & 3)
+        fld = (int(w[j >> 1]) >> (16 * (j & 1))) & 0xFFFF
+        assert bool(keep[b, h, q, k]) == (fld >= 32768), (b, h, q, k)
+        # (q, k) and (q ^ 1, k) share a draw, (q, k ^ 4) does not
+        w1 = U.philox4x32_10(key, (k >> 2, (q ^ 1) >> 1, 0x30000 + 4 * layer + 1, b * heads + h))
+        w4 = U.philox4x32_10(key, ((k ^ 4) >> 2, q >> 1, 0x30000 + 4 * layer + 1, b * heads + h))
+        assert [int(a) for a in w1] == [int(a) for a in w] and [int(a) for a in w4] != [int(a) for a in w]
+    # feed-forward: element (m, n) is field n & 7 of the draw (n >> 3, m, stream, 0)
+    keep = U.row_keep(seed, 0.5, layer, U.SITE_ACT, 7, 50)
+    for m, n in ((0, 0), (6, 49), (3, 8), (5, 23)):
+        w = U.philox4x32_10(key, (n >> 3, m, 0x30000 + 4 * layer + 2, 0))
+        j = n & 7
+        assert bool(keep[m, n]) == ((int(w[j >> 1]) >> (16 * (j & 1))) & 0xFFFF >= 32768), (m, n)
+    # sites, layers and seeds are separate streams
+    a = U.row_keep(seed, 0.5, 0, U.SITE_DOWN, 16, 64)
+    assert not np.array_equal(a, U.row_keep(seed, 0.5, 1, U.SITE_DOWN, 16, 64))
+    assert not np.array_equal(a, U.row_keep(seed, 0.5, 0, U.SITE_ACT, 16, 64))
+    assert not np.array_equal(a, U.row_keep(seed + 1, 0.5, 0, U.SITE_DOWN, 16, 64))
+    assert not np.array_equal(a, U.row_keep(seed + (1 << 32), 0.5, 0, U.SITE_DOWN, 16, 64))
+    assert np.array_equal(a, U.row_keep(seed, 0.5, 0, U.SITE_DOWN, 32, 80)[:16, :64])  # a function of position, not of the shape
+
+
+def test_threshold_scale_and_keep_counts():
+    assert U.threshold(0.2) == 13107 and U.threshold(0.0) == 0 and U.threshold(0.5) == 32768
+    assert U.scale(0.2) == 65536.0 / (65536 - 13107)
+    for bad in (-0.1, 1.0, 1.5, 0.99999999):
+        with pytest.raises(ValueError):
+            U.threshold(bad)
+    for p in (0.1, 0.2, 0.5):
+        q = 1.0 - U.threshold(p) / 65536.0
+        for keep in (U.attn_keep(11, p, 0, U.SITE_ATTN, 3, 4, 50, 50), U.attn_keep(12, p, 1, U.SITE_CROSS, 2, 5, 19, 9),
+                     U.row_keep(13, p, 1, U.SITE_ACT, 150, 288), U.row_keep(14, p, 0, U.SITE_DOWN, 750, 160)):
+            n = keep.size
+            assert abs(keep.sum() - n * q) <= 4.0 * math.sqrt(n * q * (1.0 - q)), (p, keep.shape, keep.mean())
+
+
+def test_masked_oracle_without_dropout_is_the_oracle():
+    for name in ("G1", "G2"):
+        cfg, sd, inp = case(name)
+        kw = dict(heads=cfg.heads, window=cfg.attn_window_size)
+        a = U.decoder_forward(sd, inp["x"], inp["t"], inp["sem"], inp["si"], inp["f"], p=0.0, seed=5, **kw)
+        b = O.decoder_forward(sd, inp["x"], inp["t"], inp["sem"], inp["si"], inp["f"], **kw)
+        assert torch.equal(a, b)
+        c = U.decoder_forward(sd, inp["x"], inp["t"], inp["sem"], inp["si"], inp["f"], p=0.2, seed=5, **kw)
+        assert float((c - b).abs().max()) > 0.05 * float(b.abs().max())  # ... and with it, it moves
+
+
+def golden_objective(g, dtype):
+    """tests/test_train_host.py: golden_objective, for the dropout fixture."""
+    hidden, heads, layers = (int(v) for v in g["cfg"])
+    cfg = CFG(device="cpu", hidden=hidden, heads=heads, layers=layers, dropout=float(g["p"]))
+    sd = synth_state_dict(cfg, 7)
+    tabs = {k: v.to(dtype) for k, v in O.schedule_tables(cfg.diff_steps).items()}
+    t = g["t"]
+    sab = tabs["sqrt_alpha_bar"][t][:, None, None]
+    s1m = tabs["sqrt_one_minus_alpha_bar"][t][:, None, None]
+    x0, noise = g["x0"].to(dtype), g["noise"].to(dtype)
+    inp = dict(x=sab * x0 + s1m * noise, t=t, si=torch.zeros(len(t), dtype=torch.long), sem=None, f=g["feats"])
+    v_target = sab * noise - s1m * x0
+    return cfg, sd, inp, lambda fwd, x: torch.nn.functional.mse_loss(fwd(t), v_target)
+
+
+def test_masked_oracle_reproduces_the_reference_gradients_under_the_masks(golden):
+    g = golden("train_dropout")
+    p, seed = float(g["p"]), int(g["seed"])
+    assert abs(p - 0.2) < 1e-7
+    out = {}
+    for dtype in (torch.float64, torch.float32):
+        cfg, sd, inp, loss_fn = golden_objective(g, dtype)
+        out[dtype] = U.oracle_grads(cfg, sd, inp, dtype, p, (seed,), loss_fn=loss_fn)
+    loss64, g64, _ = out[torch.float64]
+    loss32, g32, _ = out[torch.float32]
+    names = sorted(k[4:] for k in g if k.startswith("g64."))
+    assert names == sorted(k for k, v in g64.items() if v is not None and k not in ("d_x", "d_sem_features"))
+    assert abs(float(loss64) - float(g["loss64"])) <= 1e-12 * abs(float(g["loss64"]))
+    assert abs(float(loss32) - float(g["loss64"])) <= 2 * max(abs(float(g["loss32"]) - float(g["loss64"])), 2.0 ** -24 * float(g["loss64"]))
+    e_or, e_ref = {}, {}
+    for k in names:
+        ref64 = g["g64." + k]
+        assert rel_err(g64[k], ref64) < 1e-11, k  # the sites, the masks and the scaling are the reference's
+        e_ref[k] = rel_err(g["g32." + k], ref64)
+        e_or[k] = rel_err(g32[k], ref64)
+        print(f"{k}: oracle fp32 {e_or[k]:.2e}  reference fp32 {e_ref[k]:.2e}")
+    med = float(torch.tensor(sorted(e_ref.values())).median())
+    bad = {k: (e_or[k], e_ref[k]) for k in names if not e_or[k] <= 2 * max(e_ref[k], med)}
+    assert not bad, bad
+    # the fixture is not the eval arithmetic: the no-dropout gradients of the same objective are far away
+    cfg, sd, inp, loss_fn = golden_objective(g, torch.float64)
+    _, g0, _ = U.oracle_grads(cfg, sd, inp, torch.float64, 0.0, (seed,), loss_fn=loss_fn)
+    assert max(rel_err(g0[k], g["g64." + k]) for k in names) > 1e-2
+
+
+def test_train_dropout_option_validation():
+    cfg = CFG(device="cpu")  # dropout 0.2
+    with pytest.raises(ValueError, match="train_dropout=True needs autograd=True"):
+        EdgeDiffusionDecoder(cfg, kernels="generic", train_dropout=True)
+    with pytest.raises(ValueError, match="kernels='generic'"):
+        EdgeDiffusionDecoder(cfg, autograd=True, train_dropout=True)
+    dec = EdgeDiffusionDecoder(cfg, kernels="generic", autograd=True, train_dropout=True)
+    assert dec.train_dropout and dec.dropout_generator is None and dec.last_dropout_seed is None
+    assert EdgeDiffusionDecoder(cfg, kernels="generic", autograd=True).train_dropout is False
+    x, t, sem = torch.zeros(1, 8, cfg.n_mels), torch.zeros(1, dtype=torch.long), torch.zeros(1, 4, dtype=torch.long)
+    dec.train()
+    with pytest.raises(ValueError, match="x_lengths / sem_lengths"):
+        dec(x, t, sem, x_lengths=torch.tensor([8]))
+    with pytest.raises(ValueError, match="x_lengths / sem_lengths"):
+        dec(x, t, sem, sem_lengths=torch.tensor([4]))
+    with pytest.raises(ValueError, match="Either sem_idx or sem_features"):
+        dec(x, t)
+    assert dec.last_dropout_seed is None  # (refused calls draw nothing)
+    # the training-mode call draws its seed on the host, then reaches the library's device check (there is no CPU path)
+    dec.dropout_generator = torch.Generator().manual_seed(3)
+    with pytest.raises(native.EdttsError, match="no CPU fallback"):
+        dec(x, t, sem)
+    assert dec.last_dropout_seed == U.seeds_of(3)[0] and 0 <= dec.last_dropout_seed < 2 ** 63
+    # without a generator of its own the draw is torch's default CPU generator's: torch.manual_seed repeats it
+    dec.dropout_generator = None
+    seen = []
+    for _ in range(2):
+        torch.manual_seed(99)
+        with pytest.raises(native.EdttsError, match="no CPU fallback"):
+            dec(x, t, sem)
+        seen.append(dec.last_dropout_seed)
+    assert seen[0] == seen[1] != U.seeds_of(3)[0]
+
+
+def test_new_symbols_are_declared_exported_and_bound():
+    with open(os.path.join(REPO, "include", "edtts.h")) as f:
+        header = f.read()
+    L = native.lib()
+    assert L.edtts_version() == 400
+    for sym in NEW_SYMBOLS:
+        assert re.search(r"\bint " + sym + r"\(", header), sym
+        assert sym in native.EXPORTED_SYMBOLS, sym
+        assert getattr(L, sym).argtypes, sym
+    assert "typedef struct EdttsDropout" in header and "0x30000 + 4 * layer + site" in header
+    assert [n for n, _ in native.EdttsDropout._fields_] == ["p", "seed"] and ctypes.sizeof(native.EdttsDropout) == 16
+
+
+def test_p_outside_the_range_is_refused_before_any_device_work():
+    """The library checks EdttsDropout before its pointers: with every pointer NULL a valid p reaches the pointer check, an invalid
+    one its own message."""
+    L = native.lib()
+    dims = EdgeDiffusionDecoder(CFG(device="cpu"), kernels="generic").dims()
+    d = ctypes.byref(dims)
+
+    def calls(drop):
+        dr = ctypes.byref(drop)
+        return ((L.edtts_decoder_forward_train_drop, (d, None, None, None, 2, 64, 32, None, None, None, None, None, None, dr, None)),
+                (L.edtts_decoder_backward_drop, (d, None, None, None, 2, 64, 32, None, None, None, None, None, None, None, 0, None, None, None, dr, None)),
+                (L.edtts_dropout_mask, (d, 0, 0, 2, 64, 32, dr, None, None)))
+
+    for bad in (1.0, 1.5, -0.25, float("nan"), 0.99999994):  # (the last: round(p * 65536) = 65536)
+        for fn, args in calls(native.EdttsDropout(bad, 1)):
+            with pytest.raises(native.EdttsError, match=r"dropout p="):
+                fn(*args)
+    for ok in (0.0, 0.2, 0.9999):
+        for fn, args in calls(native.EdttsDropout(ok, 1)):
+            with pytest.raises((native.EdttsError, ValueError), match=r"NULL pointer|Either sem_idx"):
+                fn(*args)
+    with pytest.raises(native.EdttsError, match="site 4"):
+        L.edtts_dropout_mask(d, 4, 0, 2, 64, 32, ctypes.byref(native.EdttsDropout(0.2, 1)), None, None)
+    with pytest.raises(native.EdttsError, match="layer"):
+        L.edtts_dropout_mask(d, 0, dims.layers, 2, 64, 32, ctypes.byref(native.EdttsDropout(0.2, 1)), None, None)
+    with pytest.raises(native.EdttsError, match="generic kernels only"):
+        L.edtts_dropout_mask(ctypes.byref(EdgeDiffusionDecoder(CFG(device="cpu")).dims()), 0, 0, 2, 64, 32,
+                             ctypes.byref(native.EdttsDropout(0.2, 1)), None, None)
+
+
+def test_size_queries_are_unchanged():
+    """The dropped activations replace the undropped ones on the tape, and the backward's masked copy lives in a scratch region that
+    is free at that point: the sizes are those of DESIGN.md section 19 (tests/test_train_host.py restates the tape's)."""
+    c = CFG(device="cpu")
+    gen = EdgeDiffusionDecoder(c, kernels="generic", autograd=True, train_dropout=True).dims()
+    up = lambda n: (n + 63) // 64 * 64
+    for B, T, S in ((2, 64, 32), (8, 173, 100)):
+        H, M, CS, FH = c.hidden, B * T, B * S, c.ffn_mult * c.hidden
+        per_layer = (up(CS * (H // 2)) + up(CS * 2 * H) + 3 * up(M * H) + up(M * 3 * H) + 3 * up(M * H) + 2 * up(M * c.heads) + up(M * FH))
+        floats = up(B * c.layers * 4 * H + B * H) + up(CS * H) + c.layers * per_layer + up(M * H)
+        assert native.train_tape_bytes(gen, B, T, S) == 4 * floats
+    assert not hasattr(native.lib(), "edtts_train_scratch_bytes_drop")  # (no larger scratch was needed)
