@@ -2824,6 +2824,7 @@ struct Launcher16 {
 #include "edtts_generic.h"
 #include "edtts_generic_bwd.h"
 #include "edtts_semantic.h"
+#include "edtts_semantic_bwd.h"
 #include "edtts_hubert.h"
 #include "edtts_hubert16.h"
 #include "edtts_audio.h"

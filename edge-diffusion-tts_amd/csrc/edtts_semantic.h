@@ -13,6 +13,8 @@
 //                  use that order (k_sem_pack), so the whole chain stays in registers.  Weights stream through a double-buffered
 //                  16 KiB LDS chunk that the block's four waves share (W1 is 384 KiB at the defaults); each feature row is read
 //                  from HBM once, by the one wave whose frames it holds.  Usage counts: one integer atomicAdd per valid frame.
+//                  k_sem_encode<true> is the training forward (edtts_semantic_bwd.h): the same chain, which also
+//                  writes the backward's tape and multiplies the LayerNorm output by the head's dropout mask.
 //   k_sem_decode   idx -> z_q, one thread per output element (FSQEncoder.decode / VectorQuantizer.decode; ids clamped)
 //   k_sem_stats    counts -> (perplexity, used) in one block, fixed order, fp64 accumulation
 //   k_sem_pack     state-dict matrices -> fragment order (zero-padded to 16 x 16 tiles), vectors padded, |c|^2 per code
@@ -153,6 +155,19 @@ struct EncArgs {
   size_t w1, b1, lng, lnb, w3, b3, wd, bd, wu, bu, half, lev, basis, cb, cc, cbraw;
 };
 
+// ... plus what the training forward writes and its dropout site (k_sem_encode<true> only: the inference kernel's arguments stay as
+// they are)
+struct EncTrainArgs : EncArgs {
+  float* t_y1;   // tape: proj.0 output before GELU [N][S] (in_dim > 0)
+  float* t_zb;   // tape: tanh(proj_down(z)) [N][16]
+  DropArgs dr;   // the mask between LayerNorm and the last Linear
+  int dropping;
+};
+template <bool TRAIN>
+struct EncArgsOf { using type = EncArgs; };
+template <>
+struct EncArgsOf<true> { using type = EncTrainArgs; };
+
 // Copy `n` f4 (n <= kChunk) of a packed stream into registers: thread tid holds elements tid + 256 i.
 EDTTS_DEV void chunk_load(const f4* __restrict__ src, int n, f4 (&r)[4]) {
 #pragma unroll
@@ -261,7 +276,8 @@ EDTTS_DEV float group_sum(float v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void k_sem_encode(EncArgs a) {
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void k_sem_encode(typename EncArgsOf<TRAIN>::type a) {
   __shared__ f4 buf[2][kChunk];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, grp = lane >> 4;
   const int frame = blockIdx.x * kFrames + 16 * w + (lane & 15);
@@ -284,6 +300,13 @@ __global__ __launch_bounds__(256) void k_sem_encode(EncArgs a) {
       for (int r = 0; r < 4; ++r) y[t][r] = t < nt ? p[a.b1 + 16 * t + 4 * grp + r] : 0.f;
     const float* hrow = a.h + (size_t)(ok ? frame : 0) * a.in_dim;
     stream_w1(reinterpret_cast<const f4*>(p + a.w1), a.kb1, nt, hrow, ok, y, buf);
+    if constexpr (TRAIN) {
+      if (frame < a.N) {
+#pragma unroll
+        for (int t = 0; t < kMaxNT; ++t)
+          if (t < nt) stg4(a.t_y1 + (size_t)frame * S + 4 * grp + 16 * t, ok ? y[t] : splat(0.f));
+      }
+    }
     float s = 0.f;
 #pragma unroll
     for (int t = 0; t < kMaxNT; ++t)
@@ -313,6 +336,13 @@ __global__ __launch_bounds__(256) void k_sem_encode(EncArgs a) {
         const int f = 16 * t + 4 * grp + r;
         y[t][r] = t < nt ? (y[t][r] - mean) * rstd * p[a.lng + f] + p[a.lnb + f] : 0.f;
       }
+    if constexpr (TRAIN) {
+      if (a.dropping) {
+#pragma unroll
+        for (int t = 0; t < kMaxNT; ++t)
+          if (t < nt) y[t] = y[t] * drop_row4(a.dr, frame, 16 * t + 4 * grp);
+      }
+    }
 #pragma unroll
     for (int t = 0; t < kMaxNT; ++t) z[t] = splat(0.f);
     stream_rt(reinterpret_cast<const f4*>(p + a.w3), nt, nt, p + a.b3, S, y, buf, [&](int rt, f4 acc) {
@@ -343,12 +373,14 @@ __global__ __launch_bounds__(256) void k_sem_encode(EncArgs a) {
     stream_rt(reinterpret_cast<const f4*>(p + a.wd), 1, nt, p + a.bd, a.D, z, buf, [&](int, f4 u) {
       const int* lev = reinterpret_cast<const int*>(p + a.lev);
       const long long* basis = reinterpret_cast<const long long*>(p + a.basis);
+      [[maybe_unused]] f4 zbv = splat(0.f);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int d = 4 * grp + r;
         if (d < a.D) {
           const float half = p[a.half + d];
           const float zb = tanhf(u[r]);
+          if constexpr (TRAIN) zbv[r] = zb;
           float q = rintf((zb + 1.0f) * half);                       // torch.round: half to even
           q = fminf(fmaxf(q, 0.0f), (float)(lev[d] - 1));
           q = q / half - 1.0f;
@@ -356,6 +388,9 @@ __global__ __launch_bounds__(256) void k_sem_encode(EncArgs a) {
           zl[0][r] = zq;
           part += (int)rintf((zq + 1.0f) * half) * (int)basis[d];    // codes_to_indices, recomputed from zq_low
         }
+      }
+      if constexpr (TRAIN) {
+        if (frame < a.N) stg4(a.t_zb + (size_t)frame * 16 + 4 * grp, ok ? zbv : splat(0.f));
       }
     });
     part += __shfl_xor(part, 16);
@@ -590,7 +625,7 @@ int edtts_sem_encode(const EdttsSemDims* dims, const void* packed, const float* 
   a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
   a.wd = L.wd; a.bd = L.bd; a.wu = L.wu; a.bu = L.bu; a.half = L.half; a.lev = L.lev; a.basis = L.basis;
   a.cb = L.cb; a.cc = L.cc; a.cbraw = L.cbraw;
-  hipLaunchKernelGGL(k_sem_encode, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_sem_encode<false>, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
   LAUNCH_CHECK("k_sem_encode");
   return EDTTS_OK;
 }

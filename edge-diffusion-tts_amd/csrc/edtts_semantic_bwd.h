@@ -1,0 +1,480 @@
+// edtts_semantic_bwd.h -- training the semantic head: proj and FSQEncoder under autograd (included by edtts_kernels.hip behind
+// edtts_semantic.h).
+//
+// The training forward is k_sem_encode<true> (edtts_semantic.h): the inference chain, which also writes the tape
+//   y1 = proj.0(h) before GELU [M][S], z [M][S] (both only with a proj), zb = tanh(proj_down(z)) [M][16]       (M = B T_feat)
+// and multiplies the LayerNorm output by the head's dropout mask (stream word 0x40000, positions as drop_row4 maps them).
+//
+//   k_sem_bwd_frames   the frame-local part of the backward in the forward's layout (64 frames per block, frame = lane & 15, the
+//                      TRANSPOSED weights as the A operand, streamed through LDS by stream_rt):  G = d z_q ->
+//                      d zq_low = Wu^T G -> du = d zq_low o (1 - zb^2) (the straight-through line passes the gradient to zb
+//                      unchanged) -> dz = Wd^T du -> da = W3^T dz -> x dropout multiplier (regenerated) -> LayerNorm backward
+//                      (statistics recomputed from y1 in fp64; the per-frame sums cross the four lane groups with __shfl_xor) ->
+//                      erf-GELU derivative -> dy1.  It leaves du, zq_low, dz, the post-dropout LayerNorm output a, the masked da, x^ and dy1
+//                      for the sums over frames, zero for frames at or past lengths[b].
+//   k_sem_pack_fragT   the transposed matrices in fragment order (the training blob)
+// The sums over frames reuse section 19's kernels (TrainLauncher::dw / colsum, k_bwd_norm_cols): fixed orders, no float atomics.
+#pragma once
+
+namespace edtts_sem {
+
+// Training blob (floats): Wu^T [16][S], Wd^T [S][16], W3^T [S][S], each rt-major in fragment order.
+struct SemTrainLayout {
+  size_t wuT, wdT, w3T, total;
+};
+static void sem_train_layout(const SemLayout& L, SemTrainLayout& R) {
+  size_t o = 0;
+  auto take = [&](size_t floats) { size_t r = o; o += (floats + 3) & ~(size_t)3; return r; };
+  R.wuT = take((size_t)L.nt * 64 * 4);
+  R.wdT = take((size_t)L.nt * 64 * 4);
+  R.w3T = L.in_dim ? take((size_t)L.nt * L.nt * 64 * 4) : 0;
+  R.total = o;
+}
+// Tape (floats): with a proj y1 | z | zb, without one zb alone (z is then the caller's input).
+struct SemTape {
+  size_t y1, z, zb, total;
+};
+static void sem_tape(const SemLayout& L, size_t M, SemTape& t) {
+  const size_t MS = L.in_dim ? M * L.S : 0;
+  t.y1 = 0;
+  t.z = MS;
+  t.zb = 2 * MS;
+  t.total = 2 * MS + 16 * M;
+}
+// The backward's scratch (floats): du | zq_low [M][16], dz | gm [M][S], with a proj a | dam | xh | dy1 [M][S] and stat [M][2], then
+// the partial sums of the reductions.
+struct SemScratch {
+  size_t du, zql, dz, gm, a, dam, xh, dy1, stat, part, total;
+};
+static void sem_scratch(const SemLayout& L, int B, int T, SemScratch& s) {
+  const size_t M = (size_t)B * T, S = L.S, MS = M * S;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
+  auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
+  s.du = take(16 * M); s.zql = take(16 * M); s.dz = take(MS); s.gm = take(MS);
+  s.a = s.dam = s.xh = s.dy1 = s.stat = 0;
+  if (L.in_dim) {
+    s.a = take(MS); s.dam = take(MS); s.xh = take(MS); s.dy1 = take(MS); s.stat = take(2 * M);
+  }
+  size_t part = 0;
+  auto dwp = [&](size_t n, size_t k) {
+    const size_t r = edtts_bwd::dw_slab_rows((int)M), ns = (M + r - 1) / r;
+    if (ns > 1) part = mx(part, ns * n * k);
+  };
+  dwp(S, 16); dwp(16, S);
+  if (L.in_dim) { dwp(S, S); dwp(S, L.in_dim); }
+  part = mx(part, (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows * S);                                        // bias partials
+  if (L.in_dim) part = mx(part, (size_t)B * (((size_t)T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk) * 3 * S);  // LayerNorm partials
+  s.part = take(part);
+  s.total = o;
+}
+
+// dst (fragment order, rt-major) <- M^T for M [K][R] row-major: the packed matrix has R rows and K columns
+__global__ void k_sem_pack_fragT(const float* __restrict__ M, int R, int K, int nrt, int nkb, float* __restrict__ dst) {
+  const long long n = (long long)nrt * nkb * 256;
+  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(e & 3), lane = (int)((e >> 2) & 63);
+    const long long t = e >> 8;
+    const int rt = (int)(t / nkb), kb = (int)(t % nkb);
+    const int r = 16 * rt + (lane & 15), k = 16 * kb + 4 * (lane >> 4) + j;
+    dst[e] = (r < R && k < K) ? M[(size_t)k * R + r] : 0.f;
+  }
+}
+
+struct SemBwdArgs {
+  const float* p;           // the inference blob: LayerNorm gain and bias, FSQ tables
+  const float* pt;          // the training blob
+  const float* g;           // d z_q [N][S]
+  const long long* len;     // [B] or null
+  const float *t_y1, *t_zb; // tape
+  float *du, *zql, *dz, *gm, *a, *dam, *xh, *dy1, *stat;  // dz null: not wanted (in_dim 0); gm null: no lengths
+  int N, T, in_dim, S, nt, D;
+  size_t lng, lnb, half, lev, wuT, wdT, w3T;
+  DropArgs dr;
+  int dropping;
+};
+
+// group_sum in fp64
+EDTTS_DEV double group_sum_d(double v) {
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
+  __shared__ f4 buf[2][kChunk];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, grp = lane >> 4;
+  const int frame = blockIdx.x * kFrames + 16 * w + (lane & 15);
+  const bool in = frame < a.N;
+  bool ok = in;
+  if (ok && a.len) {
+    const int b = frame / a.T, t = frame - b * a.T;
+    long long n = a.len[b];
+    n = n < 1 ? 1 : (n > a.T ? a.T : n);
+    ok = t < n;
+  }
+  const float* p = a.p;
+  const float* pt = a.pt;
+  const int S = a.S, nt = a.nt;
+  const size_t rd = (size_t)(ok ? frame : 0);           // the row this lane reads (frames that are not ok read nothing of their own)
+  const size_t orow = (size_t)frame * S + 4 * grp;      // ... and writes (only when `in`)
+  const size_t drow = (size_t)frame * 16 + 4 * grp;
+  // ---- G = d z_q as B fragments
+  f4 X[kMaxNT];
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t) X[t] = (ok && t < nt) ? ldg4(a.g + rd * S + 4 * grp + 16 * t) : splat(0.f);
+  if (a.gm && in) {
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t)
+      if (t < nt) stg4(a.gm + orow + 16 * t, X[t]);
+  }
+  // ---- d zq_low = Wu^T G (one 16-row tile); du = d zq_low o (1 - zb^2); zq_low recomputed from zb as the forward computes it
+  f4 dzl = splat(0.f);
+  stream_rt(reinterpret_cast<const f4*>(pt + a.wuT), 1, nt, nullptr, 0, X, buf, [&](int, f4 acc) { dzl = acc; });
+  {
+    const f4 zb = ok ? ldg4(a.t_zb + rd * 16 + 4 * grp) : splat(0.f);
+    const int* lev = reinterpret_cast<const int*>(p + a.lev);
+    f4 du = splat(0.f), zq = splat(0.f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int d = 4 * grp + r;
+      if (ok && d < a.D) {
+        const float half = p[a.half + d];
+        float q = rintf((zb[r] + 1.0f) * half);
+        q = fminf(fmaxf(q, 0.0f), (float)(lev[d] - 1));
+        q = q / half - 1.0f;
+        zq[r] = zb[r] + (q - zb[r]);
+        du[r] = dzl[r] * (1.0f - zb[r] * zb[r]);
+      }
+    }
+    if (in) {
+      stg4(a.du + drow, du);
+      stg4(a.zql + drow, zq);
+    }
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t) X[t] = splat(0.f);
+    X[0] = du;
+  }
+  // ---- dz = Wd^T du
+  f4 dz[kMaxNT];
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t) dz[t] = splat(0.f);
+  stream_rt(reinterpret_cast<const f4*>(pt + a.wdT), nt, 1, nullptr, 0, X, buf, [&](int rt, f4 acc) {
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t)
+      if (t == rt) dz[t] = acc;
+  });
+  if (a.dz && in) {
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t)
+      if (t < nt) stg4(a.dz + orow + 16 * t, dz[t]);
+  }
+  if (!a.in_dim) return;  // the quantizer alone: dz is the input gradient
+  // ---- da = W3^T dz
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t) X[t] = splat(0.f);
+  stream_rt(reinterpret_cast<const f4*>(pt + a.w3T), nt, nt, nullptr, 0, dz, buf, [&](int rt, f4 acc) {
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t)
+      if (t == rt) X[t] = acc;
+  });
+  // ---- LayerNorm statistics from y1.  The gain gradient sums da o x^ over frames and x^ = (g - mean) rstd multiplies every rounding
+  // of g = GELU(y1) by rstd (several units when a frame's activations lie close together), so GELU, its derivative, the statistics
+  // and the two per-frame sums of the LayerNorm backward are evaluated in fp64 here and rounded once: y1 then holds GELU'(y1).
+  f4 y1[kMaxNT], xh[kMaxNT];
+  double s = 0.0;
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t) {
+    y1[t] = (ok && t < nt) ? ldg4(a.t_y1 + rd * S + 4 * grp + 16 * t) : splat(0.f);
+    xh[t] = splat(0.f);
+    if (t < nt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double yv = (double)y1[t][r];
+        const double cdf = 0.5 * (1.0 + erf(yv * 0.70710678118654752440));
+        xh[t][r] = (float)(yv * cdf);
+        y1[t][r] = (float)(cdf + yv * 0.39894228040143267794 * exp(-0.5 * yv * yv));
+        s += (double)xh[t][r];
+      }
+    }
+  }
+  const double mean = group_sum_d(s) / (double)S;
+  double v = 0.0;
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t)
+    if (t < nt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double d = (double)xh[t][r] - mean;
+        v = fma(d, d, v);
+      }
+    }
+  const double rstd_d = 1.0 / sqrt(group_sum_d(v) / (double)S + 1e-5);
+  const float rstd = (float)rstd_d;
+  // ---- x dropout multiplier; a = (x^ gain + bias) o mask; gx = da o gain and its two per-frame sums
+  double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t) {
+    if (t < nt) {
+      const f4 dm = a.dropping ? drop_row4(a.dr, frame, 16 * t + 4 * grp) : splat(1.0f);
+      f4 av, dam;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int f = 16 * t + 4 * grp + r;
+        const float xv = (float)(((double)xh[t][r] - mean) * rstd_d);
+        xh[t][r] = ok ? xv : 0.f;
+        av[r] = ok ? (xv * p[a.lng + f] + p[a.lnb + f]) * dm[r] : 0.f;
+        dam[r] = X[t][r] * dm[r];  // (zero for frames that are not ok: G is)
+        X[t][r] = dam[r] * p[a.lng + f];
+        s1 += (double)X[t][r];
+        s2 += (double)X[t][r] * (double)xh[t][r];
+      }
+      if (in) {
+        stg4(a.a + orow + 16 * t, av);
+        stg4(a.dam + orow + 16 * t, dam);
+        stg4(a.xh + orow + 16 * t, xh[t]);
+      }
+    }
+  }
+  const float m1 = (float)(group_sum_d(s1) / (double)S), m2 = (float)(group_sum_d(s2) / (double)S);
+  // ---- LayerNorm backward, then the GELU derivative
+  if (in) {
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t)
+      if (t < nt) {
+        f4 dy;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dy[r] = rstd * (X[t][r] - m1 - xh[t][r] * m2) * y1[t][r];
+        stg4(a.dy1 + orow + 16 * t, dy);
+      }
+    if (grp == 0) {  // k_bwd_norm_cols reads (x - mean) rstd: x^ is stored, so its statistics are (0, 1)
+      a.stat[2 * (size_t)frame] = 0.f;
+      a.stat[2 * (size_t)frame + 1] = 1.0f;
+    }
+  }
+}
+
+}  // namespace edtts_sem
+
+// =========================================================================================================
+// launchers and the C ABI
+// =========================================================================================================
+static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on);
+
+// dims -> layouts of a trainable head (FSQ only)
+static int sem_train_dims(const EdttsSemDims* dims, const char* who, edtts_sem::SemLayout& L) {
+  TRY_G(edtts_sem::sem_layout(dims, L));
+  if (L.vq)
+    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training covers the FSQ quantizer only (the VQ path with its codebook loss and EMA update is not built)", who);
+  return EDTTS_OK;
+}
+// the head's one dropout site: stream word 0x40000 (include/edtts.h, "Philox stream ids")
+static int sem_drop(const edtts_sem::SemLayout& L, const EdttsDropout* drop, const char* who, DropArgs* dr, bool* on) {
+  DropState ds{};
+  TRY_G(drop_state(drop, who, &ds, on));
+  if (*on && !L.in_dim) return fail(EDTTS_ERR_ARG, "%s: dropout p=%g given, but a head without proj (in_dim 0) has no dropout site", who, (double)drop->p);
+  *dr = DropArgs{ds.k0, ds.k1, 0x40000u, ds.thr, ds.scale};
+  return EDTTS_OK;
+}
+static int sem_shape(int B, int T) {
+  if (B < 0 || T < 0 || (long long)B * T > 0x7fffffffLL - edtts_sem::kFrames) return fail(EDTTS_ERR_ARG, "B=%d T=%d out of range", B, T);
+  return EDTTS_OK;
+}
+
+extern "C" {
+
+int edtts_sem_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_train_packed_bytes", L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  edtts_sem::SemTrainLayout R;
+  edtts_sem::sem_train_layout(L, R);
+  *out_bytes = R.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_sem_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_train_pack", L));
+  const int want = (L.in_dim ? 6 : 0) + 4;
+  if (!slots || !packed_train) return fail(EDTTS_ERR_ARG, "slots/packed_train is NULL");
+  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", want, n_slots);
+  for (int i = 0; i < n_slots; ++i)
+    if (!slots[i]) return fail(EDTTS_ERR_ARG, "weight slot %d is NULL", i);
+  SemTrainLayout R;
+  sem_train_layout(L, R);
+  hipStream_t st = (hipStream_t)stream;
+  float* P = (float*)packed_train;
+  const float* const* s = (const float* const*)slots;
+  const int q = L.in_dim ? 6 : 0;
+  auto fragT = [&](const float* M, int Rr, int K, int nrt, int nkb, size_t off) -> int {
+    const long long n = (long long)nrt * nkb * 256;
+    hipLaunchKernelGGL(k_sem_pack_fragT, dim3((unsigned)min((n + 255) / 256, 4096LL)), dim3(256), 0, st, M, Rr, K, nrt, nkb, P + off);
+    LAUNCH_CHECK("k_sem_pack_fragT");
+    return EDTTS_OK;
+  };
+  TRY_G(fragT(s[q + 2], L.D, L.S, 1, L.nt, R.wuT));  // proj_up.weight [S][D]   -> Wu^T [D][S]
+  TRY_G(fragT(s[q], L.S, L.D, L.nt, 1, R.wdT));      // proj_down.weight [D][S] -> Wd^T [S][D]
+  if (L.in_dim) TRY_G(fragT(s[4], L.S, L.S, L.nt, L.nt, R.w3T));
+  return EDTTS_OK;
+}
+
+int edtts_sem_train_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_train_tape_bytes", L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY_G(sem_shape(B, T));
+  edtts_sem::SemTape tt;
+  edtts_sem::sem_tape(L, (size_t)B * T, tt);
+  *out_bytes = tt.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_sem_train_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_train_scratch_bytes", L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY_G(sem_shape(B, T));
+  edtts_sem::SemScratch ss;
+  edtts_sem::sem_scratch(L, B, T, ss);
+  *out_bytes = ss.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                           float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, void* stream) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_encode_train", L));
+  DropArgs dr{};
+  bool dropping;
+  TRY_G(sem_drop(L, drop, "edtts_sem_encode_train", &dr, &dropping));
+  TRY_G(sem_shape(B, T));
+  if (!packed || !h || !idx || !tape) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)L.n_codes * sizeof(int32_t), st));
+  const int N = B * T;
+  if (N == 0) return EDTTS_OK;
+  SemTape tt;
+  sem_tape(L, (size_t)N, tt);
+  float* tp = (float*)tape;
+  EncTrainArgs a{};
+  a.p = (const float*)packed;
+  a.h = h;
+  a.len = (const long long*)lengths;
+  a.idx = (long long*)idx;
+  a.z = L.in_dim ? tp + tt.z : nullptr;
+  a.zq = z_q;
+  a.counts = counts;
+  a.N = N; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.kb1 = L.kb1; a.vq = 0; a.D = L.D; a.K = 0;
+  a.nrt_codes = 0;
+  a.n_codes = L.n_codes;
+  a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
+  a.wd = L.wd; a.bd = L.bd; a.wu = L.wu; a.bu = L.bu; a.half = L.half; a.lev = L.lev; a.basis = L.basis;
+  a.t_y1 = tp + tt.y1;
+  a.t_zb = tp + tt.zb;
+  a.dr = dr;
+  a.dropping = dropping;
+  hipLaunchKernelGGL(k_sem_encode<true>, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  LAUNCH_CHECK("k_sem_encode<train>");
+  return EDTTS_OK;
+}
+
+int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
+                       const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                       const EdttsDropout* drop, void* stream) {
+  using namespace edtts_sem;
+  using TL = TrainLauncher;
+  SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_backward", L));
+  DropArgs dr{};
+  bool dropping;
+  TRY_G(sem_drop(L, drop, "edtts_sem_backward", &dr, &dropping));
+  TRY_G(sem_shape(B, T));
+  const int want = (L.in_dim ? 6 : 0) + 4;
+  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", want, n_slots);
+  if (L.in_dim && d_z) return fail(EDTTS_ERR_ARG, "edtts_sem_backward: d_z is the input gradient of a head without proj (in_dim 0)");
+  if (!packed || !packed_train || !tape || !h || !d_zq || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  hipStream_t st = (hipStream_t)stream;
+  float* const* gs = reinterpret_cast<float* const*>(grad_slots);
+  const int S = L.S, D = L.D, M = B * T, q = L.in_dim ? 6 : 0;
+  if (M == 0) {  // empty sums
+    const size_t n[10] = {(size_t)S * L.in_dim, (size_t)S, (size_t)S, (size_t)S, (size_t)S * S, (size_t)S,
+                          (size_t)D * S, (size_t)D, (size_t)S * D, (size_t)S};
+    for (int i = 0; i < want; ++i)
+      if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n[i + (L.in_dim ? 0 : 6)] * sizeof(float), st));
+    return EDTTS_OK;
+  }
+  SemTrainLayout R;
+  sem_train_layout(L, R);
+  SemTape tt;
+  sem_tape(L, (size_t)M, tt);
+  SemScratch ss;
+  sem_scratch(L, B, T, ss);
+  const float* tp = (const float*)tape;
+  float* sc = (float*)scratch;
+  SemBwdArgs a{};
+  a.p = (const float*)packed;
+  a.pt = (const float*)packed_train;
+  a.g = d_zq;
+  a.len = (const long long*)lengths;
+  a.t_y1 = tp + tt.y1;
+  a.t_zb = tp + tt.zb;
+  a.du = sc + ss.du; a.zql = sc + ss.zql;
+  a.dz = L.in_dim ? sc + ss.dz : d_z;
+  a.gm = lengths ? sc + ss.gm : nullptr;
+  a.a = sc + ss.a; a.dam = sc + ss.dam; a.xh = sc + ss.xh; a.dy1 = sc + ss.dy1; a.stat = sc + ss.stat;
+  a.N = M; a.T = T; a.in_dim = L.in_dim; a.S = S; a.nt = L.nt; a.D = D;
+  a.lng = L.lng; a.lnb = L.lnb; a.half = L.half; a.lev = L.lev;
+  a.wuT = R.wuT; a.wdT = R.wdT; a.w3T = R.w3T;
+  a.dr = dr;
+  a.dropping = dropping;
+  hipLaunchKernelGGL(k_sem_bwd_frames, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  LAUNCH_CHECK("k_sem_bwd_frames");
+  // the sums over frames, in state-dict slot order
+  float* part = sc + ss.part;
+  const float* G = lengths ? sc + ss.gm : d_zq;
+  const float* z = L.in_dim ? tp + tt.z : h;
+  if (L.in_dim) {
+    TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));  // proj.0.weight = dy1^T h
+    TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
+    if (gs[2] || gs[3]) {                                                  // LayerNorm gain = sum dam o x^, bias = sum dam
+      using namespace edtts_gen;
+      const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
+      edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
+      LAUNCH_CHECK("k_bwd_norm_cols");
+      if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
+      if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
+    }
+    TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));               // final Linear weight = dz^T a
+    TRY_G(TL::colsum(st, a.dz, S, M, S, gs[5], part));
+  }
+  TRY_G(TL::dw(st, a.du, 16, z, S, M, D, S, gs[q], part));                  // proj_down.weight = du^T z
+  TRY_G(TL::colsum(st, a.du, 16, M, D, gs[q + 1], part));
+  TRY_G(TL::dw(st, G, S, a.zql, 16, M, S, D, gs[q + 2], part));             // proj_up.weight = G^T zq_low
+  TRY_G(TL::colsum(st, G, S, M, S, gs[q + 3], part));
+  return EDTTS_OK;
+}
+
+int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_dims(dims, "edtts_sem_dropout_mask", L));
+  if (!drop) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: drop is NULL");
+  if (!L.in_dim) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: a head without proj (in_dim 0) has no dropout site");
+  DropArgs dr{};
+  bool dropping;
+  TRY_G(sem_drop(L, drop, "edtts_sem_dropout_mask", &dr, &dropping));
+  if (!dropping) dr = DropArgs{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0x40000u, 0u, 1.0f};  // p == 0: everything kept
+  TRY_G(sem_shape(B, T));
+  if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  const size_t rows = (size_t)B * T;
+  if (rows == 0) return EDTTS_OK;
+  hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * (L.S / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows, L.S,
+                     T, 0, dr);
+  LAUNCH_CHECK("k_drop_mask");
+  return EDTTS_OK;
+}
+
+}  // extern "C"

@@ -10,8 +10,12 @@ that returns ``.hidden_states`` (transformers' ``HubertModel`` is one).  Without
 if it is not there.  Precomputed features ([B, T_feat, 768], as data/dataset_precomputed.py stores them) skip HuBERT entirely:
 ``quantize_features`` / ``encode_features``.
 
-Inference only: ``forward`` has the reference's eval semantics in either mode (loss 0, Dropout the identity, no EMA codebook
-update).  Weights are packed for the kernels on first use and re-packed when a parameter changes.
+By default inference only: ``forward`` has the reference's eval semantics in either mode (loss 0, Dropout the identity, no EMA
+codebook update).  ``autograd=True`` (FSQ heads) makes the head trainable as train_v2.train_step trains it: under grad mode
+``forward`` / ``quantize_features`` / ``forward_features`` run the training forward (edtts_sem_encode_train) and ``backward()`` the
+backward kernels (edtts_sem_backward), with FSQ's straight-through estimator; ``train_dropout=True`` adds proj's ``nn.Dropout`` with
+masks from the library's Philox stream.  Weights are packed for the kernels on first use and re-packed when a
+parameter changes.
 """
 from __future__ import annotations
 
@@ -28,12 +32,18 @@ from . import native
 class _PackCache:
     """The packed blob of one head: (re-)packed on the current stream when a weight tensor or the dims changed."""
 
-    def __init__(self):
+    def __init__(self, train: bool = False):
         self._lock = threading.Lock()
         self._sig = None
         self._blob = None
+        self._train = train  # the training-only blob (transposed matrices for the backward) instead of the inference blob
+
+    @property
+    def sig(self):
+        return self._sig
 
     def get(self, dims: native.EdttsSemDims, tensors: Sequence[torch.Tensor]) -> torch.Tensor:
+        nbytes_of, pack = (native.sem_train_packed_bytes, native.sem_train_pack) if self._train else (native.sem_packed_bytes, native.sem_pack)
         with self._lock:
             dkey = (dims.in_dim, dims.semantic_dim, dims.quantizer, dims.codebook_size, dims.n_levels, tuple(dims.levels))
             sig = (dkey,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
@@ -42,10 +52,10 @@ class _PackCache:
                 for i, t in enumerate(tensors):
                     if t.device != dev or t.dtype != torch.float32:
                         raise native.EdttsError(f"weight {i}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
-                nbytes = native.sem_packed_bytes(dims)
+                nbytes = nbytes_of(dims)
                 if self._blob is None or self._blob.numel() != nbytes or self._blob.device != dev:
                     self._blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                native.sem_pack(dims, [t.detach().contiguous() for t in tensors], self._blob)
+                pack(dims, [t.detach().contiguous() for t in tensors], self._blob)
                 self._sig = sig
             return self._blob
 
@@ -58,6 +68,44 @@ def _flat3(z: torch.Tensor, width: int, name: str) -> torch.Tensor:
     if z.shape[-1] != width:
         raise ValueError(f"{name}: expected last dimension {width}, got {list(z.shape)}")
     return z.float().reshape(1, -1, width)
+
+
+class _SemGrad(torch.autograd.Function):
+    """(z_q, idx, counts) of a head on the training forward (edtts_sem_encode_train); backward through edtts_sem_backward.  The tape
+    is a tensor of this call's own, saved in ctx; ``drop`` (None or this call's (p, seed)) lives in ctx too, so the backward
+    regenerates the mask of ITS forward.  ``owner``: the module whose ``_slots()`` / ``_pack`` / ``_tpack`` describe the head."""
+
+    @staticmethod
+    def forward(ctx, owner, dims, lengths, drop, h, *params):
+        slots = owner._slots()
+        blob = owner._pack.get(dims, slots)
+        tblob = owner._tpack.get(dims, slots)
+        x = native._aligned(h.detach().float())
+        B, T = x.shape[0], x.shape[1]
+        if lengths is not None and B * T:  # the weight-gradient products multiply the rows past the lengths by zeros: make them finite
+            x = x.masked_fill((torch.arange(T, device=x.device)[None, :] >= lengths.clamp(1, T)[:, None])[..., None], 0.0)
+        tape = torch.empty(native.sem_train_tape_bytes(dims, B, T), dtype=torch.uint8, device=x.device)
+        idx, zq, counts = native.sem_encode_train(dims, blob, x, tape, lengths, True, drop)
+        ctx.owner, ctx.dims, ctx.lengths, ctx.drop, ctx.sig = owner, dims, lengths, drop, (owner._pack.sig, owner._tpack.sig)
+        ctx.x = x
+        ctx.save_for_backward(tape, *params)
+        ctx.mark_non_differentiable(idx, counts)
+        return zq, idx, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_zq, _d_idx, _d_counts):
+        owner, dims = ctx.owner, ctx.dims
+        tape, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        slots = owner._slots()
+        blob = owner._pack.get(dims, slots)
+        tblob = owner._tpack.get(dims, slots)
+        if (owner._pack.sig, owner._tpack.sig) != ctx.sig:
+            raise RuntimeError(f"{type(owner).__name__}: a parameter was modified between this forward and its backward")
+        grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[5:])]
+        d_z = torch.empty_like(ctx.x) if dims.in_dim == 0 and ctx.needs_input_grad[4] else None
+        native.sem_backward(dims, blob, tblob, tape, ctx.x, ctx.lengths, native._aligned(d_zq.float()), grads, d_z, ctx.drop)
+        return (None, None, None, None, d_z, *grads)
 
 
 class FSQ(nn.Module):
@@ -132,13 +180,17 @@ class FSQEncoder(nn.Module):
     """proj_down -> FSQ -> proj_up (reference models/fsq.py:FSQEncoder); keys ``fsq._levels``, ``fsq._basis``, ``proj_down.*``,
     ``proj_up.*``."""
 
-    def __init__(self, input_dim: int, levels: List[int] = (8, 6, 5, 5, 5)):
+    def __init__(self, input_dim: int, levels: List[int] = (8, 6, 5, 5, 5), autograd: bool = False):
+        """``autograd``: False (default) -- inference only, as before.  True -- under grad mode ``forward`` is differentiable with
+        respect to ``proj_down``, ``proj_up`` and the input ``z`` (FSQ's straight-through estimator)."""
         super().__init__()
+        self.autograd = bool(autograd)
         self.fsq = FSQ(list(levels))
         self.fsq_dim = len(levels)
         self.proj_down = nn.Linear(input_dim, self.fsq_dim)
         self.proj_up = nn.Linear(self.fsq_dim, input_dim)
         self._pack = _PackCache()
+        self._tpack = _PackCache(train=True)
 
     @property
     def codebook_size(self) -> int:
@@ -162,11 +214,19 @@ class FSQEncoder(nn.Module):
                                                want_counts=want_counts)
         return (None if zq is None else zq.reshape(*shape, -1)), idx.reshape(shape), counts
 
-    @torch.no_grad()
     def forward(self, z: torch.Tensor):
-        """(z_q, indices, loss = 0, perplexity, used), as FSQEncoder.forward returns them."""
-        zq, idx, counts = self._quantize(z, True, True)
-        ppl, used = _stats(counts)
+        """(z_q, indices, loss = 0, perplexity, used), as FSQEncoder.forward returns them.  With ``autograd=True`` and under grad
+        mode z_q carries the graph."""
+        if self.autograd and torch.is_grad_enabled():
+            shape = z.shape[:-1]
+            dims = self._dims()
+            zq, idx, counts = _SemGrad.apply(self, dims, None, None, _flat3(z, dims.semantic_dim, "FSQEncoder input"), *self._slots())
+            zq, idx = zq.reshape(*shape, -1), idx.reshape(shape)
+        else:
+            with torch.no_grad():
+                zq, idx, counts = self._quantize(z, True, True)
+        with torch.no_grad():
+            ppl, used = _stats(counts)
         return zq, idx, torch.zeros((), device=z.device), ppl, used
 
     @torch.no_grad()
@@ -268,8 +328,33 @@ class SemanticEncoder(nn.Module):
     ``hidden_states[cfg.hubert_layer]``.  None: nothing is loaded here; the first waveform call loads
     ``HubertModel.from_pretrained(cfg.hubert_id, local_files_only=True)`` and raises a RuntimeError if it is not cached."""
 
-    def __init__(self, cfg, hubert: Optional[nn.Module] = None, *, in_dim: int = 768, proj_dropout: bool = False):
+    def __init__(self, cfg, hubert: Optional[nn.Module] = None, *, in_dim: int = 768, proj_dropout: bool = False,
+                 autograd: bool = False, train_dropout: bool = False):
+        """``autograd``: False (default) -- inference only, as before.  True (FSQ only; a VQ quantizer raises a ValueError: its
+        codebook and commitment losses, EMA update and dead-code reset are not built) -- ``forward``, ``quantize_features`` and
+        ``forward_features`` under grad mode return a z_q that carries the graph to proj and the quantizer's projections.  No
+        gradient goes into HuBERT (the reference detaches its features).
+        ``train_dropout``: False (default) -- a differentiable call in training mode with the Dropout layout and ``p > 0`` raises.
+        True (needs ``autograd=True`` and the Dropout layout) -- that call applies ``proj[3]`` with the library's Philox masks: each
+        draws a 63-bit seed on the host from ``self.dropout_generator`` (a CPU ``torch.Generator``; None: torch's default one),
+        keeps it for its own backward and shows it as ``self.last_dropout_seed``, as EdgeDiffusionDecoder does."""
         super().__init__()
+        self.autograd = bool(autograd)
+        self.train_dropout = bool(train_dropout)
+        if self.autograd and not getattr(cfg, "use_fsq", False):
+            raise ValueError("autograd=True covers the FSQ quantizer only (cfg.use_fsq): the VQ path -- VectorQuantizer in training mode "
+                             "with its codebook loss, commitment loss, EMA update and dead-code reset -- is not built")
+        if self.train_dropout and not self.autograd:
+            raise ValueError("train_dropout=True needs autograd=True (dropout belongs to the training forward and its backward)")
+        if self.train_dropout and not proj_dropout:
+            raise ValueError("train_dropout=True needs the Dropout layout of proj (proj_dropout=True: Linear, GELU, LayerNorm, Dropout, "
+                             "Linear as train_v2.py builds it)")
+        if self.train_dropout:
+            p = float(getattr(cfg, "dropout", 0.0))
+            if not (0.0 <= p < 1.0) or round(p * 65536.0) > 65535:
+                raise ValueError(f"train_dropout=True: cfg.dropout={p} is outside [0, 1) (the mask contract needs round(p * 65536) <= 65535)")
+        self.dropout_generator: Optional[torch.Generator] = None
+        self.last_dropout_seed: Optional[int] = None
         self.cfg = cfg
         self.hubert = hubert
         if hubert is not None:
@@ -277,14 +362,20 @@ class SemanticEncoder(nn.Module):
             self._freeze(hubert)
         self.proj = _Proj(in_dim, cfg.semantic_dim, getattr(cfg, "dropout", 0.0) if proj_dropout else None)
         if getattr(cfg, "use_fsq", False):
-            self.vq = FSQEncoder(cfg.semantic_dim, cfg.fsq_levels)
+            self.vq = FSQEncoder(cfg.semantic_dim, cfg.fsq_levels, autograd=self.autograd)
         else:
             self.vq = VectorQuantizer(cfg.semantic_dim, cfg.codebook_size, commit=getattr(cfg, "vq_commit", 0.25))
         self._pack = _PackCache()
+        self._tpack = _PackCache(train=True)
 
     @property
     def codebook_size(self) -> int:
         return self.vq.codebook_size
+
+    def get_trainable_params(self) -> list:
+        """proj and quantizer parameters (reference models/encoder.py:129-131, train_v2.py:80-81): what the trainer's optimiser gets
+        next to ``decoder.parameters()``.  HuBERT is frozen."""
+        return list(self.proj.parameters()) + list(self.vq.parameters())
 
     @staticmethod
     def _check_native(hubert: nn.Module, cfg) -> None:
@@ -418,25 +509,57 @@ class SemanticEncoder(nn.Module):
         n = native.lengths(lengths, B, max(T, 1), h.device, "lengths")
         return native.sem_encode(dims, blob, h.float(), n, want_z=want_z, want_zq=want_zq, want_counts=want_counts)
 
-    @torch.no_grad()
+    def _head_autograd(self, h: torch.Tensor, lengths):
+        """(z_q with the graph, idx, counts) of a differentiable call."""
+        if h.dim() != 3:
+            raise ValueError(f"features: expected [B, T_feat, {self.proj[0].in_features}], got {list(h.shape)}")
+        drop = None
+        layer = self.proj[3] if len(self.proj) == 5 else None
+        if self.training and layer is not None and layer.p > 0:
+            if not self.train_dropout:
+                raise ValueError(f"autograd=True: proj has a Dropout with p={layer.p} and the encoder is in training mode (the reference "
+                                 "drops there), but train_dropout is off: construct with train_dropout=True, or set proj[3].p = 0 or "
+                                 "call .eval()")
+            # (a host draw from a CPU generator: no device work, no synchronisation)
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator).item())
+            drop = (float(layer.p), seed)
+            self.last_dropout_seed = seed
+        n = native.lengths(lengths, h.shape[0], max(h.shape[1], 1), h.device, "lengths")
+        return _SemGrad.apply(self, self._dims(), n, drop, h.detach(), *self._slots())
+
+    def _differentiable(self) -> bool:
+        return self.autograd and torch.is_grad_enabled()
+
     def quantize_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None):
         """Precomputed HuBERT features h [B, T_feat, 768] -> (z_q [B, T_feat, semantic_dim], idx [B, T_feat], perplexity, used).
-        ``lengths`` (int64 [B]): frames t >= lengths[b] are not read, get idx 0 and z_q 0, and are not counted."""
-        idx, _, zq, counts = self._head(h, lengths, True, True)
-        ppl, used = _stats(counts)
+        ``lengths`` (int64 [B]): frames t >= lengths[b] are not read, get idx 0 and z_q 0, and are not counted.  With
+        ``autograd=True`` and under grad mode z_q carries the graph (the features themselves get no gradient)."""
+        if self._differentiable():
+            zq, idx, counts = self._head_autograd(h, lengths)
+        else:
+            with torch.no_grad():
+                idx, _, zq, counts = self._head(h, lengths, True, True)
+        with torch.no_grad():
+            ppl, used = _stats(counts)
         return zq, idx, ppl, used
+
+    def forward_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """``forward`` from precomputed HuBERT features: (z_q, idx, vq_loss = 0, perplexity, used)."""
+        zq, idx, ppl, used = self.quantize_features(h, lengths)
+        return zq, idx, torch.zeros((), device=zq.device), ppl, used
 
     @torch.no_grad()
     def encode_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Token ids [B, T_feat] of precomputed HuBERT features (see quantize_features)."""
         return self._head(h, lengths, False, False)[0]
 
-    @torch.no_grad()
     def forward(self, wav_16k: torch.Tensor, lengths: Optional[torch.Tensor] = None):
         """(z_q, idx, vq_loss = 0, perplexity, used) of a 16 kHz waveform [B, T_audio], as the reference returns them.  ``lengths``
-        (sample counts, NativeHubert backbone only): the head then takes each utterance's own frame count."""
-        zq, idx, ppl, used = self.quantize_features(*self._features(wav_16k, lengths))
-        return zq, idx, torch.zeros((), device=zq.device), ppl, used
+        (sample counts, NativeHubert backbone only): the head then takes each utterance's own frame count.  HuBERT runs without
+        grad in every mode; see ``quantize_features`` for ``autograd=True``."""
+        with torch.no_grad():
+            feats = self._features(wav_16k, lengths)
+        return self.forward_features(*feats)
 
     @torch.no_grad()
     def encode(self, wav_16k: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:

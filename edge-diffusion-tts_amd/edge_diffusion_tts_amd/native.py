@@ -31,6 +31,8 @@ EXPORTED_SYMBOLS = (
     "edtts_train_tape_bytes", "edtts_train_scratch_bytes", "edtts_train_dw_slab_rows", "edtts_decoder_forward_train",
     "edtts_decoder_backward",
     "edtts_decoder_forward_train_drop", "edtts_decoder_backward_drop", "edtts_dropout_mask",
+    "edtts_sem_train_packed_bytes", "edtts_sem_train_pack", "edtts_sem_train_tape_bytes", "edtts_sem_train_scratch_bytes",
+    "edtts_sem_encode_train", "edtts_sem_backward", "edtts_sem_dropout_mask",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -178,6 +180,13 @@ def lib() -> C.CDLL:
     L.edtts_decoder_backward_drop.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
                                               vp, vp, vp, dpp, vp]
     L.edtts_dropout_mask.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, i32, i32, dpp, vp, vp]
+    L.edtts_sem_train_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
+    L.edtts_sem_train_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
+    L.edtts_sem_train_tape_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
+    L.edtts_sem_train_scratch_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
+    L.edtts_sem_encode_train.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, dpp, vp]
+    L.edtts_sem_backward.argtypes = [sdp, vp, vp, vp, vp, i32, i32, vp, vp, C.POINTER(vp), i32, vp, vp, dpp, vp]
+    L.edtts_sem_dropout_mask.argtypes = [sdp, i32, i32, dpp, vp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -642,6 +651,83 @@ def sem_stats(counts: torch.Tensor):
     used = torch.empty((), dtype=torch.int64, device=counts.device)
     lib().edtts_sem_stats(_dev_ptr(counts, torch.int32, "counts"), counts.numel(), ppl.data_ptr(), used.data_ptr(), _stream(counts.device))
     return ppl, used
+
+
+# ---------------------------------------------------------------------------------------------- semantic head, training
+SEM_DROP_STREAM = 0x40000  # include/edtts.h, "Philox stream ids": the head's dropout site
+
+
+def sem_train_packed_bytes(dims: EdttsSemDims) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_sem_train_packed_bytes(C.byref(dims), C.byref(out))
+    return out.value
+
+
+def sem_train_pack(dims: EdttsSemDims, tensors: Sequence[torch.Tensor], packed_train: torch.Tensor) -> None:
+    """The training-only blob (the transposed matrices the backward streams); slots as sem_pack."""
+    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    lib().edtts_sem_train_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed_train, torch.uint8, "packed_train"),
+                               _stream(packed_train.device))
+
+
+def sem_train_tape_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_sem_train_tape_bytes(C.byref(dims), B, T, C.byref(out))
+    return out.value
+
+
+def sem_train_scratch_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
+    out = C.c_size_t(0)
+    lib().edtts_sem_train_scratch_bytes(C.byref(dims), B, T, C.byref(out))
+    return out.value
+
+
+def sem_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, tape: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                     want_counts: bool = True, drop=None):
+    """edtts_sem_encode_train: h [B, T, in_dim] (z [B, T, semantic_dim] when dims.in_dim is 0; contiguous, 16-byte aligned) ->
+    (idx, z_q, counts or None) as sem_encode, with the backward's tape written to `tape` (uint8, sem_train_tape_bytes).  ``drop``:
+    None, an EdttsDropout or a (p, seed) pair."""
+    B, T, D = h.shape
+    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
+    if D != want_d:
+        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+    dev = h.device
+    idx = torch.empty((B, T), dtype=torch.int64, device=dev)
+    zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
+    counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=dev) if want_counts else None
+    drop = _dropout(drop)
+    lib().edtts_sem_encode_train(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
+                                 _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), zq.data_ptr(),
+                                 None if counts is None else counts.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"),
+                                 None if drop is None else C.byref(drop), _stream(dev))
+    return idx, zq, counts
+
+
+def sem_backward(dims: EdttsSemDims, packed: torch.Tensor, packed_train: torch.Tensor, tape: torch.Tensor, h: torch.Tensor,
+                 lengths: Optional[torch.Tensor], d_zq: torch.Tensor, grads: Sequence[Optional[torch.Tensor]],
+                 d_z: Optional[torch.Tensor] = None, drop=None) -> None:
+    """edtts_sem_backward: writes the gradient of every non-None entry of `grads` (slot order) and d_z (dims.in_dim == 0).  ``drop``:
+    what the forward that filled `tape` was given."""
+    B, T, _ = h.shape
+    ptrs = (C.c_void_p * len(grads))(*[_dev_ptr(g, torch.float32, f"grad[{i}]") for i, g in enumerate(grads)])
+    scratch = torch.empty(sem_train_scratch_bytes(dims, B, T), dtype=torch.uint8, device=h.device)
+    drop = _dropout(drop)
+    lib().edtts_sem_backward(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(packed_train, torch.uint8, "packed_train"),
+                             _dev_ptr(tape, torch.uint8, "tape"), _dev_ptr(h, torch.float32, "features"), B, T,
+                             _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(d_zq, torch.float32, "d_zq"), ptrs, len(grads),
+                             _dev_ptr(d_z, torch.float32, "d_z"), scratch.data_ptr(), None if drop is None else C.byref(drop),
+                             _stream(h.device))
+
+
+def sem_dropout_mask(dims: EdttsSemDims, B: int, T: int, p: float, seed: int, device="cuda") -> torch.Tensor:
+    """edtts_sem_dropout_mask: the keep mask (uint8, 1 = kept) [B * T, semantic_dim] of the head's dropout site."""
+    drop = EdttsDropout(float(p), int(seed))
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise EdttsError(f"sem_dropout_mask: expected a HIP device, got {dev} -- there is no CPU fallback")
+    keep = torch.empty((B * T, dims.semantic_dim), dtype=torch.uint8, device=dev)
+    lib().edtts_sem_dropout_mask(C.byref(dims), B, T, C.byref(drop), keep.data_ptr(), _stream(dev))
+    return keep
 
 
 # ---------------------------------------------------------------------------------------------- HuBERT backbone

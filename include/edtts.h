@@ -304,6 +304,7 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
  *                         edtts_sample_inpaint_multistep_len (one sampler or the other runs on a seed: the same draws)
  *     0x30000 + 4 * layer + site   dropout masks of the training forward and backward (edtts_decoder_forward_train_drop; layers
  *                         <= 32: [0x30000, 0x30080)), keyed by position as described there, not by global element
+ *     0x40000             dropout mask of the semantic head's proj (edtts_sem_encode_train), keyed by position as sites 2 and 3
  * edtts_randn rejects stream_id >= 0x10000. */
 int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_t elem_offset, float scale, void* stream);
 /* One launch for B rows with a seed each: out [B, n_per_row], row b bitwise what edtts_randn(n_per_row, seeds[b], stream_id, offset 0,
@@ -528,6 +529,45 @@ int edtts_sem_decode(const EdttsSemDims* dims, const void* packed, const int64_t
 /* Stats: counts int32 [n_codes] -> perplexity fp32 [1] = exp(-sum p log(max(p, 1e-12))), p = counts / max(sum, 1), and used int64
  * [1] = #(counts > 0) (fsq.py:189-193, vq.py:101-105).  One block, fixed order: bitwise reproducible. */
 int edtts_sem_stats(const int32_t* counts, int64_t n_codes, float* perplexity, int64_t* used, void* stream);
+
+/* ---- training the semantic head  (train_v2.py train_step: proj and FSQEncoder are trained with the decoder) ------------------------
+ * FSQ only (EDTTS_ERR_UNSUPPORTED for EDTTS_SEM_VQ: the codebook and commitment losses, the EMA update and the dead-code reset are
+ * not built), fp32.  The straight-through estimator is FSQ.forward's: zq_low = zb + (q - zb).detach(), so d zb = d zq_low.
+ *
+ * edtts_sem_encode_train is edtts_sem_encode (idx, z_q, counts as there) that also writes the backward's tape, M = B * T rows:
+ *     in_dim > 0:  y1 = proj.0(h) before GELU [M][S] | z [M][S] | zb = tanh(proj_down(z)) [M][16]    (2 M S + 16 M floats)
+ *     in_dim = 0:  zb [M][16]                                                                     (16 M floats; z is the input)
+ * Everything else (LayerNorm statistics, the LayerNorm output, zq_low, 1 - zb^2) is recomputed by the backward.  Without dropout,
+ * idx and z_q are bitwise edtts_sem_encode's.
+ *
+ * Dropout: one more site of the mask contract above ("Dropout masks"), the nn.Dropout between LayerNorm and the last Linear of the
+ * five-module proj (in_dim > 0 only; a drop with p > 0 and in_dim = 0 is EDTTS_ERR_ARG).  Stream word c2 = 0x40000; row
+ * m = b * T + t, column n: c0 = n >> 3, c1 = m, c3 = 0, field n & 7 -- as sites 2 and 3.  thr, p_eff, the kept values' factor and the
+ * EDTTS_ERR_ARG rule for p are the contract's.  drop == NULL or p == 0: the undropped launches, bitwise.  The backward must be
+ * given what its forward was given and regenerates the mask.  edtts_sem_dropout_mask: the keep mask [B * T, S] as 0 / 1 bytes
+ * through the same device function.
+ *
+ * The backward needs three transposed matrices (proj_up^T, proj_down^T, final Linear^T) in fragment order: a second, training-only
+ * blob (edtts_sem_train_packed_bytes / edtts_sem_train_pack, slots as edtts_sem_pack); the inference blob is unchanged.
+ *
+ * edtts_sem_backward: d_zq [B,T,S] -> the gradient of every non-NULL entry of grad_slots (state-dict slot order, as edtts_sem_pack:
+ * 10 slots with a proj, 4 without) and, with in_dim = 0, d_z [B,T,S] (optional).  h is what the forward was given.  One frame-local
+ * kernel (MFMA, the transposed weights as the A operand) and then sums over frames in fixed orders -- rows ascending inside a slab
+ * of edtts_train_dw_slab_rows(M) rows, slabs ascending -- without float atomics: two backwards are bitwise equal.  d_h is never
+ * computed.  It reads the tape, the two blobs, h, lengths and d_zq and writes only gradients and `scratch`
+ * (edtts_sem_train_scratch_bytes), so forwards that run between a forward and its backward do not disturb it.
+ * lengths: as edtts_sem_encode; frames at or past lengths[b] contribute exactly nothing and get d_z 0 (h itself must be finite there:
+ * the weight-gradient products multiply those rows by zeros).  Argument errors are reported before any pointer is looked at. */
+int edtts_sem_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes);
+int edtts_sem_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream);
+int edtts_sem_train_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes);
+int edtts_sem_train_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes);
+int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths,
+                           int64_t* idx, float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, void* stream);
+int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
+                       int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z,
+                       void* scratch, const EdttsDropout* drop, void* stream);
+int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream);
 
 /* ---- HuBERT backbone  (transformers HubertModel, feat_extract_norm = "group", do_stable_layer_norm = False: hubert-base) ------------
  * wav [B, T_audio] fp32 -> HubertModel(wav, output_hidden_states=True).hidden_states[num_layers] [B, T_feat, hidden], eval mode, fp32.
