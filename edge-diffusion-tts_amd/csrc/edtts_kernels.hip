@@ -2275,17 +2275,17 @@ static int device_simds() {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Sub-batches on two streams.  A layer launch of a large batch is a whole number of rounds of one wave per SIMD, and every
+// Sub-batches on several streams.  A layer launch of a large batch is a whole number of rounds of one wave per SIMD, and every
 // launch ends with SIMDs idling while the last waves finish (round 3, B=256, T=512: 3.7 % of the kernel, the spread of the
 // sum of four wave lifetimes over 1024 SIMDs); the next launch cannot start before, because it reads K / V rows of its
-// neighbours.  Utterances are independent, though: the samplers cut a large batch into two halves that walk the same
-// launch sequence on two streams (the caller's and a library-owned one, forked and joined with events: capturable), so one
-// half's waves fill the SIMDs the other half's finishing launch leaves idle.  Each half is an ordinary call on its own slice
-// of the caller's workspace; results do not depend on the cut (every utterance is computed alone, bitwise).
+// neighbours.  Utterances are independent, though: the samplers cut a large batch into up to kMaxSub sub-batches (substreams_for)
+// that walk the same launch sequence on one stream each (the caller's and library-owned ones, forked and joined with events:
+// capturable), so one sub-batch's waves fill the SIMDs another's finishing launch leaves idle.  Each sub-batch is an ordinary call on
+// its own slice of the caller's workspace; results do not depend on the cut (every utterance is computed alone, bitwise).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kMaxSub = 8;
 struct SubBatches {
-  int n;                 // 1 (no cut) or 2
+  int n;                 // number of sub-batches: 1 (no cut) .. kMaxSub
   int B[kMaxSub], off[kMaxSub];
   Workspace ws[kMaxSub];
   size_t base[kMaxSub];  // float offset of slice j in the caller's workspace
@@ -2496,10 +2496,9 @@ static void set_tail_args(const StepTail& t, KArgs* a) {
     return;
   }
   a->x_prev = t.x_prev;
-  if (t.kind == TAIL_LMS) {
+  if (t.kind == TAIL_LMS || t.kind == TAIL_VLMS) {
     a->lms = t.lms.k; a->h_new = t.lms.h_new; a->h_old = t.lms.h_old; a->x0_hist = t.lms.x0_hist; a->x0_all = t.lms.x0_all;
-  } else if (t.kind == TAIL_VLMS) {
-    a->lms = t.lms.k; a->h_new = t.lms.h_new; a->h_old = t.lms.h_old; a->x0_hist = t.lms.x0_hist; a->x0_all = t.lms.x0_all;
+    if (t.kind == TAIL_LMS) return;
     a->vp = t.vp.k; a->v_uncond = t.vp.v_uncond;
     a->known = t.blend.known; a->noise = t.blend.noise; a->inj_frames = t.blend.frames; a->inj_mel = t.blend.mel;
     a->p_coef1 = t.blend.c_known; a->p_coef2 = t.blend.c_noise; a->seed = t.blend.seed; a->seeds = t.blend.seeds; a->step = t.blend.step;
@@ -2981,6 +2980,80 @@ static int run_sampler(const EdttsDims* dims, const Layout& lo, const void* pack
   return EDTTS_OK;
 }
 
+// The multistep samplers' rows of coef_host: {mode, p0, p1, c0, c1, rinv, cB, cC}; a step cannot look further back than the steps before it
+static int check_lms_modes(const float* coef_host, int num_steps) {
+  for (int i = 0; i < num_steps; ++i) {
+    const int mode = (int)coef_host[8 * i];
+    if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
+  }
+  return EDTTS_OK;
+}
+// LmsStepArgs of step i from its coefficient row c.  hist is a ring of two slots of `per` floats: step i writes slot i%2; newest
+// previous = slot (i-1)%2, the one before = slot i%2.  o: element offset of the (sub-)batch in a [B, T, n_mels] tensor.
+static LmsStepArgs lms_step_args(const float* c, float* hist, float* x0_all, size_t per, int i, size_t o) {
+  LmsStepArgs ls;
+  ls.k = LmsCoef{(int)c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]};
+  ls.x0_hist = hist + (size_t)(i & 1) * per + o;
+  ls.h_new = hist + (size_t)((i + 1) & 1) * per + o;
+  ls.h_old = hist + (size_t)(i & 1) * per + o;
+  ls.x0_all = x0_all ? x0_all + (size_t)i * per + o : nullptr;
+  return ls;
+}
+
+// What the in-painting entry points share: the arguments of edtts_sample_inpaint_len, in its order (include/edtts.h)
+struct InpaintArgs {
+  const EdttsDims* dims; const void* packed; void *workspace, *workspace_uncond; int B, T, S;
+  const float *sem_features, *zero_features; float* x; int num_steps; const int64_t *t_all, *step_all;
+  const float *coef_host, *known_mel; int overlap_len; const float* noise_k; uint64_t seed; float cfg_scale; float* v_uncond;
+  const int64_t *t_len, *s_len; const uint64_t* seeds; void* stream;
+};
+// The step loop of the in-painting samplers, in one piece on the caller's stream (no sub-batches: a captured call stays one chain):
+// the shared argument checks (own_ptrs: the entry point's further pointers are there; own_checks(): its further checks, made last),
+// the conditioning rows of every step, the context cache (guided: a second one in workspace_uncond) and per step the unconditional
+// forward into v_uncond (guided), then the conditional one with tail_of(i), whose vp.v_uncond is set here.  With a known tail,
+// inject_before(i) runs ahead of step i and inject_after() behind the last one.
+template <class Checks, class InjectBefore, class TailOf, class InjectAfter>
+static int run_inpaint(const InpaintArgs& a, const Layout& lo, bool own_ptrs, Checks&& own_checks, InjectBefore&& inject_before,
+                       TailOf&& tail_of, InjectAfter&& inject_after) {
+  if (!a.packed || !a.workspace || !a.sem_features || !a.x || !a.t_all || !a.step_all || !a.coef_host || !own_ptrs) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if (a.num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", a.num_steps);
+  const bool guided = a.cfg_scale != 1.0f;
+  if (guided && (!a.workspace_uncond || !a.zero_features || !a.v_uncond)) return fail(EDTTS_ERR_ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond");
+  if (a.known_mel && (a.overlap_len < 1 || a.overlap_len > a.T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", a.overlap_len, a.T);
+  TRY(check_shapes(lo, a.B, a.T, a.S));
+  TRY(own_checks());
+  hipStream_t st = (hipStream_t)a.stream;
+  const float* blob = (const float*)a.packed;
+  float* wsb = (float*)a.workspace;
+  Workspace ws;
+  make_workspace(lo, a.B, a.T, a.S, a.num_steps, &ws);
+  TRY(launch_len_check(a.t_len, a.s_len, a.B, a.T, a.S, wsb, st, a.known_mel ? a.overlap_len : 1));
+  TRY(launch_cond(lo, blob, a.t_all, a.step_all, nullptr, a.num_steps, wsb + ws.cond, wsb, st));
+  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  const CallCtx c{lo, blob, ws, wsb, a.B, a.T, a.S, a.dims->window, Lens{a.t_len, a.s_len}, st};
+  CallCtx cu = c;  // the unconditional pass: its own context cache and activations (workspace_uncond)
+  cu.wsb = (float*)a.workspace_uncond;
+  EDTTS_DISPATCH(lo, {
+    TRY(set_attrs_once<LN>());
+    TRY(LN::ctx(c, nullptr, a.sem_features));
+    if (guided) TRY(LN::ctx(cu, nullptr, a.zero_features));  // (the solo call's zero context has S_b rows)
+    for (int i = 0; i < a.num_steps; ++i) {
+      if (a.known_mel) TRY(inject_before(i));
+      StepTail tail = tail_of(i);
+      if (guided) {
+        // the unconditional pass shares nothing with the conditional one but x and the conditioning rows
+        StepTail eps_tail;
+        eps_tail.eps = a.v_uncond;
+        TRY(LN::forward(cu, a.x, wsb + ws.cond + i * row, 0, eps_tail));
+        tail.vp.v_uncond = a.v_uncond;
+      }
+      TRY(LN::forward(c, a.x, wsb + ws.cond + i * row, 0, tail));
+    }
+    if (a.known_mel) TRY(inject_after());
+  });
+  return EDTTS_OK;
+}
+
 extern "C" {
 
 int edtts_version(void) { return EDTTS_VERSION; }
@@ -3391,26 +3464,16 @@ int edtts_sample_multistep_len(const EdttsDims* dims, const void* packed, void* 
   if (num_steps < 1 || num_steps > lo.NSTEP)
     return fail(EDTTS_ERR_ARG, "num_steps=%d outside [1,%d] (step_emb rows; the reference raises IndexError)", num_steps, lo.NSTEP);
   TRY(check_shapes(lo, B, T, S));
-  for (int i = 0; i < num_steps; ++i) {
-    const int mode = (int)coef_host[8 * i];
-    if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
-  }
+  TRY(check_lms_modes(coef_host, num_steps));
   SamplerInputs in;
   in.t_host = timesteps_host; in.sem_idx = sem_idx; in.sem_features = sem_features;
   in.ln = Lens{t_len, s_len};
   in.x_T = x_T; in.x = x_out;
   const size_t per = (size_t)B * T * lo.MEL;
   return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int, size_t o) {
-    const float* c = coef_host + 8 * i;
     StepTail tail;
     tail.kind = TAIL_LMS; tail.x_prev = x_out + o;
-    LmsStepArgs& ls = tail.lms;
-    ls.k.mode = (int)c[0]; ls.k.p0 = c[1]; ls.k.p1 = c[2]; ls.k.c0 = c[3]; ls.k.c1 = c[4]; ls.k.rinv = c[5]; ls.k.cB = c[6]; ls.k.cC = c[7];
-    // history ring of two slots: step i writes slot i%2; newest previous = slot (i-1)%2, the one before = slot i%2
-    ls.x0_hist = hist + (size_t)(i & 1) * per + o;
-    ls.h_new = hist + (size_t)((i + 1) & 1) * per + o;
-    ls.h_old = hist + (size_t)(i & 1) * per + o;
-    ls.x0_all = x0_all ? x0_all + (size_t)i * per + o : nullptr;
+    tail.lms = lms_step_args(coef_host + 8 * i, hist, x0_all, per, i, o);
     return tail;
   });
 }
@@ -3505,6 +3568,18 @@ int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* worksp
                                   stream);
 }
 
+// One launch of k_inpaint_inject (whole float4s) or, for a known block that is not made of them (generic path, n_mels % 4 != 0),
+// k_inpaint_inject1: q_sample of the known frames with step `step`'s noise (injected: block `step` of noise_k) and stream id.
+static void launch_inject(const InpaintArgs& a, int mel, float c_known, float c_noise, int step) {
+  const size_t per_k = (size_t)a.B * a.overlap_len * mel;
+  const bool vec = ((size_t)a.overlap_len * mel) % 4 == 0 && ((size_t)a.T * mel) % 4 == 0;
+  const size_t bx = (per_k / (vec ? 4 : 1) + 255) / 256;
+  hipLaunchKernelGGL(vec ? k_inpaint_inject : k_inpaint_inject1, dim3(bx > 2048 ? 2048u : (unsigned)bx), dim3(256), 0, (hipStream_t)a.stream, a.x, a.known_mel,
+                     a.noise_k ? a.noise_k + (size_t)step * per_k : nullptr, a.B, a.T, a.overlap_len, mel, c_known, c_noise,
+                     (unsigned long long)a.seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(a.seeds),
+                     a.t_len);
+}
+
 int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
                              const float* sem_features, const float* zero_features, float* x, int num_steps,
                              const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
@@ -3513,61 +3588,28 @@ int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* wo
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
-  if (!packed || !workspace || !sem_features || !x || !t_all || !step_all || !coef_host) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", num_steps);
-  const bool guided = cfg_scale != 1.0f;
-  if (guided && (!workspace_uncond || !zero_features || !v_uncond)) return fail(EDTTS_ERR_ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond");
-  if (known_mel && (overlap_len < 1 || overlap_len > T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", overlap_len, T);
-  TRY(check_shapes(lo, B, T, S));
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  float* wsu = (float*)workspace_uncond;
-  Workspace ws;
-  make_workspace(lo, B, T, S, num_steps, &ws);
-  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st, known_mel ? overlap_len : 1));
-  TRY(launch_cond(lo, blob, t_all, step_all, nullptr, num_steps, wsb + ws.cond, wsb, st));
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
-  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
-  CallCtx cu = c;  // the unconditional pass: its own context cache and activations (workspace_uncond)
-  cu.wsb = wsu;
-  const bool inject_vec = ((size_t)overlap_len * lo.MEL) % 4 == 0 && ((size_t)T * lo.MEL) % 4 == 0;
-  auto inject = [&](float ck, float cn, int step) {
-    const size_t n4 = (size_t)B * overlap_len * lo.MEL / (inject_vec ? 4 : 1);
-    size_t bx = (n4 + 255) / 256;
-    if (bx > 2048) bx = 2048;
-    hipLaunchKernelGGL(inject_vec ? k_inpaint_inject : k_inpaint_inject1, dim3((unsigned)bx), dim3(256), 0, st, x, known_mel,
-                       noise_k ? noise_k + (size_t)step * B * overlap_len * lo.MEL : nullptr, B, T, overlap_len, lo.MEL, ck, cn,
-                       (unsigned long long)seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(seeds), t_len);
-  };
-  EDTTS_DISPATCH(lo, {
-    TRY(set_attrs_once<LN>());
-    TRY(LN::ctx(c, nullptr, sem_features));
-    if (guided) TRY(LN::ctx(cu, nullptr, zero_features));  // (the solo call's zero context has S_b rows)
-    for (int i = 0; i < num_steps; ++i) {
-      const float* k = coef_host + 4 * i;  // {sqrt_ab[t], sqrt_1mab[t], sqrt(ab[t_next]), sqrt(1 - ab[t_next])}
-      if (known_mel) {
-        inject(k[0], k[1], i);  // q_sample(known_mel, t) into the first overlap_len frames (inference_pipeline.py:117-123)
+  const InpaintArgs a{dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all, step_all,
+                      coef_host, known_mel, overlap_len, noise_k, seed, cfg_scale, v_uncond, t_len, s_len, seeds, stream};
+  // coef_host rows: {sqrt_ab[t], sqrt_1mab[t], sqrt(ab[t_next]), sqrt(1 - ab[t_next])}
+  return run_inpaint(
+      a, lo, true, [] { return EDTTS_OK; },
+      [&](int i) -> int {  // q_sample(known_mel, t) into the first overlap_len frames (inference_pipeline.py:117-123)
+        launch_inject(a, lo.MEL, coef_host[4 * i], coef_host[4 * i + 1], i);
         LAUNCH_CHECK("k_inpaint_inject");
-      }
-      StepTail tail;
-      tail.kind = TAIL_VPRED; tail.x_prev = x;
-      tail.vp = VpredStepArgs{{k[0], k[1], k[2], k[3], cfg_scale}, nullptr};
-      if (guided) {
-        // the unconditional pass shares nothing with the conditional one but x and the conditioning rows
-        StepTail eps_tail;
-        eps_tail.eps = v_uncond;
-        TRY(LN::forward(cu, x, wsb + ws.cond + i * row, 0, eps_tail));
-        tail.vp.v_uncond = v_uncond;
-      }
-      TRY(LN::forward(c, x, wsb + ws.cond + i * row, 0, tail));
-    }
-    if (known_mel) {
-      inject(1.0f, 0.0f, 0);  // final force (inference_pipeline.py:135-136)
-      LAUNCH_CHECK("k_inpaint_inject");
-    }
-  });
-  return EDTTS_OK;
+        return EDTTS_OK;
+      },
+      [&](int i) {
+        const float* k = coef_host + 4 * i;
+        StepTail tail;
+        tail.kind = TAIL_VPRED; tail.x_prev = x;
+        tail.vp = VpredStepArgs{{k[0], k[1], k[2], k[3], cfg_scale}, nullptr};
+        return tail;
+      },
+      [&]() -> int {  // final force (inference_pipeline.py:135-136)
+        launch_inject(a, lo.MEL, 1.0f, 0.0f, 0);
+        LAUNCH_CHECK("k_inpaint_inject");
+        return EDTTS_OK;
+      });
 }
 
 int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T,
@@ -3579,77 +3621,40 @@ int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed
   const SettingsScope settings;
   Layout lo;
   TRY(make_layout(dims, &lo));
-  if (!packed || !workspace || !sem_features || !x || !t_all || !step_all || !coef_host || !hist) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", num_steps);
-  const bool guided = cfg_scale != 1.0f;
-  if (guided && (!workspace_uncond || !zero_features || !v_uncond)) return fail(EDTTS_ERR_ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond");
-  if (known_mel && (overlap_len < 1 || overlap_len > T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", overlap_len, T);
-  TRY(check_shapes(lo, B, T, S));
-  for (int i = 0; i < num_steps; ++i) {  // (the multistep sampler's own limit: a step cannot look further back than the steps before it)
-    const int mode = (int)coef_host[8 * i];
-    if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  float* wsu = (float*)workspace_uncond;
-  Workspace ws;
-  make_workspace(lo, B, T, S, num_steps, &ws);
-  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st, known_mel ? overlap_len : 1));
-  TRY(launch_cond(lo, blob, t_all, step_all, nullptr, num_steps, wsb + ws.cond, wsb, st));
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
+  const InpaintArgs a{dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all, step_all,
+                      coef_host, known_mel, overlap_len, noise_k, seed, cfg_scale, v_uncond, t_len, s_len, seeds, stream};
   const size_t per = (size_t)B * T * lo.MEL, per_k = (size_t)B * overlap_len * lo.MEL;
-  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
-  CallCtx cu = c;  // the unconditional pass: its own context cache and activations (workspace_uncond)
-  cu.wsb = wsu;
-  // the tails blend whole float4s; a shape whose known block is not made of them (generic path, n_mels % 4 != 0) goes through the
-  // generic path's per-element tail, and step 0's blend through k_inpaint_inject1
-  const bool inject_vec = ((size_t)overlap_len * lo.MEL) % 4 == 0 && ((size_t)T * lo.MEL) % 4 == 0;
   // q_sample's scalars of step i are in its coefficient row: p0 = sqrt_ab[t_i], p1 = -sqrt_1mab[t_i] (v-prediction rows)
   auto c_known = [&](int i) { return coef_host[8 * i + 1]; };
   auto c_noise = [&](int i) { return -coef_host[8 * i + 2]; };
-  EDTTS_DISPATCH(lo, {
-    TRY(set_attrs_once<LN>());
-    TRY(LN::ctx(c, nullptr, sem_features));
-    if (guided) TRY(LN::ctx(cu, nullptr, zero_features));
-    if (known_mel) {  // step 0's q_sample of the known frames; every later one is written by the tail of the step before it
-      const size_t n4 = per_k / (inject_vec ? 4 : 1);
-      size_t bx = (n4 + 255) / 256;
-      if (bx > 2048) bx = 2048;
-      hipLaunchKernelGGL(inject_vec ? k_inpaint_inject : k_inpaint_inject1, dim3((unsigned)bx), dim3(256), 0, st, x, known_mel, noise_k, B, T,
-                         overlap_len, lo.MEL, c_known(0), c_noise(0), (unsigned long long)seed, kStreamInpaintStep,
-                         reinterpret_cast<const unsigned long long*>(seeds), t_len);
-      LAUNCH_CHECK("k_inpaint_inject");
-    }
-    for (int i = 0; i < num_steps; ++i) {
-      const float* k = coef_host + 8 * i;
-      StepTail tail;
-      tail.kind = TAIL_VLMS; tail.x_prev = x;
-      LmsStepArgs& ls = tail.lms;
-      ls.k.mode = (int)k[0]; ls.k.p0 = k[1]; ls.k.p1 = k[2]; ls.k.c0 = k[3]; ls.k.c1 = k[4]; ls.k.rinv = k[5]; ls.k.cB = k[6]; ls.k.cC = k[7];
-      // history ring of two slots, as edtts_sample_multistep_len
-      ls.x0_hist = hist + (size_t)(i & 1) * per;
-      ls.h_new = hist + (size_t)((i + 1) & 1) * per;
-      ls.h_old = hist + (size_t)(i & 1) * per;
-      ls.x0_all = x0_all ? x0_all + (size_t)i * per : nullptr;
-      tail.vp.k.cfg = cfg_scale;
-      if (known_mel) {
-        const bool last = i + 1 == num_steps;  // after the last step: the known frames themselves (inference_pipeline.py:135-136)
-        tail.blend = BlendStepArgs{known_mel, (noise_k && !last) ? noise_k + (size_t)(i + 1) * per_k : nullptr, overlap_len, lo.MEL,
-                                   last ? 1.0f : c_known(i + 1), last ? 0.0f : c_noise(i + 1),
-                                   (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(seeds),
-                                   kStreamInpaintStep + (unsigned)(last ? 0 : i + 1)};
-      }
-      if (guided) {
-        StepTail eps_tail;
-        eps_tail.eps = v_uncond;
-        TRY(LN::forward(cu, x, wsb + ws.cond + i * row, 0, eps_tail));
-        tail.vp.v_uncond = v_uncond;
-      }
-      TRY(LN::forward(c, x, wsb + ws.cond + i * row, 0, tail));
-    }
-  });
-  return EDTTS_OK;
+  return run_inpaint(
+      a, lo, hist != nullptr, [&] { return check_lms_modes(coef_host, num_steps); },
+      [&](int i) -> int {  // step 0's q_sample of the known frames; every later one is written by the tail of the step before it
+        if (i > 0) return EDTTS_OK;
+        launch_inject(a, lo.MEL, c_known(0), c_noise(0), 0);
+        LAUNCH_CHECK("k_inpaint_inject");
+        return EDTTS_OK;
+      },
+      [&](int i) {
+        StepTail tail;
+        tail.kind = TAIL_VLMS; tail.x_prev = x;
+        tail.lms = lms_step_args(coef_host + 8 * i, hist, x0_all, per, i, 0);
+        tail.vp.k.cfg = cfg_scale;
+        if (known_mel) {  // (whole float4s; a known block that is not made of them goes through the generic path's per-element tail)
+          const bool last = i + 1 == num_steps;  // after the last step: the known frames themselves (inference_pipeline.py:135-136)
+          tail.blend = BlendStepArgs{known_mel, (noise_k && !last) ? noise_k + (size_t)(i + 1) * per_k : nullptr, overlap_len, lo.MEL,
+                                     last ? 1.0f : c_known(i + 1), last ? 0.0f : c_noise(i + 1),
+                                     (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(seeds),
+                                     kStreamInpaintStep + (unsigned)(last ? 0 : i + 1)};
+        }
+        return tail;
+      },
+      [] { return EDTTS_OK; });
+}
+
+static unsigned step_blocks(const StepArgs& a) {  // blocks per utterance of k_ddim / k_ddpm
+  const size_t bx = ((a.vec4 ? a.n_per_batch / 4 : a.n_per_batch) + 255) / 256;
+  return bx > 2048 ? 2048u : (bx < 1 ? 1u : (unsigned)bx);
 }
 
 int edtts_ddim_step(const float* alpha_bar, int n_table, const float* x, const float* eps, const int64_t* t,
@@ -3663,10 +3668,7 @@ int edtts_ddim_step(const float* alpha_bar, int n_table, const float* x, const f
   a.alpha_bar = alpha_bar; a.n_table = n_table; a.x = x; a.eps = eps; a.t = t; a.t_prev = t_prev;
   a.n_per_batch = n_per_batch; a.eta = eta; a.noise = eta > 0.f ? noise : nullptr; a.x_prev = x_prev; a.x0 = x0;
   a.vec4 = step_vec4(n_per_batch, {x, eps, a.noise, x_prev, x0});
-  size_t bx = ((a.vec4 ? n_per_batch / 4 : n_per_batch) + 255) / 256;
-  if (bx > 2048) bx = 2048;
-  if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(k_ddim, dim3((unsigned)bx, B), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_ddim, dim3(step_blocks(a), B), dim3(256), 0, (hipStream_t)stream, a);
   LAUNCH_CHECK("k_ddim");
   return EDTTS_OK;
 }
@@ -3681,10 +3683,7 @@ int edtts_ddpm_step(const float* alphas, const float* alpha_bar, const float* be
   a.alphas = alphas; a.alpha_bar = alpha_bar; a.betas = betas; a.post_var = post_var; a.n_table = n_table;
   a.x = x; a.eps = eps; a.t = t; a.n_per_batch = n_per_batch; a.noise = noise; a.x_prev = x_prev;
   a.vec4 = step_vec4(n_per_batch, {x, eps, noise, x_prev});
-  size_t bx = ((a.vec4 ? n_per_batch / 4 : n_per_batch) + 255) / 256;
-  if (bx > 2048) bx = 2048;
-  if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(k_ddpm, dim3((unsigned)bx, B), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_ddpm, dim3(step_blocks(a), B), dim3(256), 0, (hipStream_t)stream, a);
   LAUNCH_CHECK("k_ddpm");
   return EDTTS_OK;
 }

@@ -16,7 +16,6 @@ first-order step -- the sampler the reference builds next to its pipeline and ne
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional, Sequence
 
 import torch
@@ -66,8 +65,8 @@ class InpaintSampler:
     def _run(self, x: torch.Tensor, sem_features: torch.Tensor, times: List[int], step_idx, known_mel, overlap_len: int,
              cfg_scale: float, noise_k, seed: int, x_lengths=None, sem_lengths=None, seeds=None, *, lms_rows=None,
              return_intermediates: bool = False):
-        """One C-ABI call: edtts_sample_inpaint_len, or with ``lms_rows`` (DPMSolverPP.step_coefficients of ``times``)
-        edtts_sample_inpaint_multistep_len.  ``step_idx``: the constant step index, or "index" for 0 .. n-1."""
+        """One C-ABI call (native.sample_inpaint): edtts_sample_inpaint_len, or with ``lms_rows`` (DPMSolverPP.step_coefficients of
+        ``times``) edtts_sample_inpaint_multistep_len.  ``step_idx``: the constant step index, or "index" for 0 .. n-1."""
         dec = self.decoder
         B, T, M = x.shape
         S = sem_features.shape[1]
@@ -89,10 +88,6 @@ class InpaintSampler:
                                                       torch.tensor(list(range(n)) if step_idx == "index" else [step_idx] * n,
                                                                    dtype=torch.int64, device=dev)))
         t_all, s_all = cached
-        if lms_rows is None:
-            cf = (C.c_float * (4 * n))(*self._coefs(times))
-        else:
-            cf = (C.c_float * (8 * n))(*[float(v) for row in lms_rows for v in row])
         packed = dec._ensure_packed()
         ws = dec.workspace(B, T, S, n, dev)
         guided = float(cfg_scale) != 1.0
@@ -109,28 +104,10 @@ class InpaintSampler:
                     raise ValueError(f"noise_k must be [{n}, {B}, {overlap_len}, {M}]")
         else:
             noise_k = None
-        p = native._dev_ptr
-        if lms_rows is not None:
-            hist = torch.empty((2, B, T, M), dtype=torch.float32, device=dev)
-            x0_all = torch.empty((n, B, T, M), dtype=torch.float32, device=dev) if return_intermediates else None
-            native.lib().edtts_sample_inpaint_multistep_len(
-                C.byref(dec.dims()), packed.data_ptr(), ws.data_ptr(), None if ws_u is None else ws_u.data_ptr(), B, T, S,
-                p(sem_features, torch.float32, "sem_features"), p(zeros, torch.float32, "zeros"), p(x, torch.float32, "x"), n,
-                t_all.data_ptr(), s_all.data_ptr(), cf, p(known_mel, torch.float32, "known_mel"), int(overlap_len),
-                p(noise_k, torch.float32, "noise_k"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(cfg_scale),
-                None if v_u is None else v_u.data_ptr(), p(t_len, torch.int64, "x_lengths"), p(s_len, torch.int64, "sem_lengths"),
-                p(sd, torch.int64, "seeds"), hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), native._stream(dev))
-            native.check_indices(ws)
-            return (x, list(x0_all.unbind(0))) if return_intermediates else x
-        native.lib().edtts_sample_inpaint_len(
-            C.byref(dec.dims()), packed.data_ptr(), ws.data_ptr(), None if ws_u is None else ws_u.data_ptr(), B, T, S,
-            p(sem_features, torch.float32, "sem_features"), p(zeros, torch.float32, "zeros"), p(x, torch.float32, "x"), n,
-            t_all.data_ptr(), s_all.data_ptr(), cf, p(known_mel, torch.float32, "known_mel"), int(overlap_len),
-            p(noise_k, torch.float32, "noise_k"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(cfg_scale),
-            None if v_u is None else v_u.data_ptr(), p(t_len, torch.int64, "x_lengths"), p(s_len, torch.int64, "sem_lengths"),
-            p(sd, torch.int64, "seeds"), native._stream(dev))
-        native.check_indices(ws)
-        return x
+        x, x0_all = native.sample_inpaint(dec.dims(), packed, ws, ws_u, sem_features, zeros, x, t_all, s_all,
+                                          self._coefs(times) if lms_rows is None else None, known_mel, overlap_len, noise_k, seed, cfg_scale,
+                                          v_u, t_len, s_len, sd, lms_rows=lms_rows, want_intermediates=return_intermediates)
+        return (x, list(x0_all.unbind(0))) if lms_rows is not None and return_intermediates else x
 
     @torch.no_grad()
     def inpaint_student_sample(self, x_shape, sem_features, known_mel=None, overlap_len: int = 0, num_steps: int = 4, *,

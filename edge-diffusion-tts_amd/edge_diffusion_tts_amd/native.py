@@ -231,6 +231,18 @@ def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _size_query(fn, *args, ctype=C.c_size_t) -> int:
+    """fn(*args, &out) -> out: the library's size and count queries."""
+    out = ctype(0)
+    fn(*args, C.byref(out))
+    return out.value
+
+
+def _slot_ptrs(tensors: Sequence[Optional[torch.Tensor]], what: str):
+    """The void* array of a slot list (fp32 device tensors, None -> NULL); `what` names an entry in error messages."""
+    return (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"{what}[{i}]") for i, t in enumerate(tensors)])
+
+
 def slot_names(n_layers: int) -> List[str]:
     L = lib()
     names = [L.edtts_global_slot_name(i).decode() for i in range(L.edtts_num_global_slots())]
@@ -241,19 +253,15 @@ def slot_names(n_layers: int) -> List[str]:
 
 
 def packed_bytes(dims: EdttsDims) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_packed_bytes(C.byref(dims), C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_packed_bytes, C.byref(dims))
 
 
 def workspace_bytes(dims: EdttsDims, B: int, T: int, S: int, cond_rows: int) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_workspace_bytes(C.byref(dims), B, T, S, cond_rows, C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_workspace_bytes, C.byref(dims), B, T, S, cond_rows)
 
 
 def pack_weights(dims: EdttsDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor) -> None:
-    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    ptrs = _slot_ptrs(tensors, "weight")
     lib().edtts_pack_weights(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
 
 
@@ -303,15 +311,11 @@ def decoder_forward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tens
 
 # ---------------------------------------------------------------------------------------------- training
 def train_tape_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_train_tape_bytes(C.byref(dims), B, T, S, C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_train_tape_bytes, C.byref(dims), B, T, S)
 
 
 def train_scratch_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_train_scratch_bytes(C.byref(dims), B, T, S, C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_train_scratch_bytes, C.byref(dims), B, T, S)
 
 
 def train_dw_slab_rows(rows: int) -> int:
@@ -353,7 +357,7 @@ def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
     """edtts_decoder_backward: writes the gradient of every non-None entry of `grads` (slot order), d_x and d_sem_features.
     ``drop``: what the forward that filled `tape` was given (None: the plain export, else edtts_decoder_backward_drop)."""
     B, T, M = x.shape
-    ptrs = (C.c_void_p * len(grads))(*[_dev_ptr(g, torch.float32, f"grad[{i}]") for i, g in enumerate(grads)])
+    ptrs = _slot_ptrs(grads, "grad")
     scratch = torch.empty(train_scratch_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
     drop = _dropout(drop)
     args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
@@ -444,6 +448,37 @@ def sample_multistep(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
                                          *tail)
     check_indices(workspace)
     return out, x0_all
+
+
+def sample_inpaint(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, workspace_uncond: Optional[torch.Tensor],
+                   sem_features: torch.Tensor, zero_features: Optional[torch.Tensor], x: torch.Tensor, t_all: torch.Tensor,
+                   step_all: torch.Tensor, coefs: Optional[Sequence[float]], known_mel: Optional[torch.Tensor], overlap_len: int,
+                   noise_k: Optional[torch.Tensor], seed: int, cfg_scale: float, v_uncond: Optional[torch.Tensor],
+                   t_len: Optional[torch.Tensor] = None, s_len: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None,
+                   lms_rows: Optional[Sequence[Sequence[float]]] = None, want_intermediates: bool = False):
+    """The in-painting samplers, in place on x [B, T, n_mels]: edtts_sample_inpaint_len with `coefs` (4 floats per step, flat), or with
+    `lms_rows` (8 floats per step; `coefs` is not read: None) edtts_sample_inpaint_multistep_len.  t_all / step_all: device int64
+    [num_steps]; t_len / s_len / seeds: device int64 [B] or None.  Returns (x, x0_all): every step's x0 [num_steps, B, T, n_mels]
+    when lms_rows and want_intermediates, else None."""
+    B, T, M = x.shape
+    n = t_all.numel()
+    f = torch.float32
+    cf = (C.c_float * (4 * n))(*coefs) if lms_rows is None else (C.c_float * (8 * n))(*[float(v) for row in lms_rows for v in row])
+    args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), None if workspace_uncond is None else workspace_uncond.data_ptr(),
+            B, T, sem_features.shape[1], _dev_ptr(sem_features, f, "sem_features"), _dev_ptr(zero_features, f, "zeros"), _dev_ptr(x, f, "x"),
+            n, t_all.data_ptr(), step_all.data_ptr(), cf, _dev_ptr(known_mel, f, "known_mel"), int(overlap_len),
+            _dev_ptr(noise_k, f, "noise_k"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(cfg_scale),
+            None if v_uncond is None else v_uncond.data_ptr(), _dev_ptr(t_len, torch.int64, "x_lengths"),
+            _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(seeds, torch.int64, "seeds"))
+    x0_all = None
+    if lms_rows is None:
+        lib().edtts_sample_inpaint_len(*args, _stream(x.device))
+    else:
+        hist = torch.empty((2, B, T, M), dtype=f, device=x.device)
+        x0_all = torch.empty((n, B, T, M), dtype=f, device=x.device) if want_intermediates else None
+        lib().edtts_sample_inpaint_multistep_len(*args, hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), _stream(x.device))
+    check_indices(workspace)
+    return x, x0_all
 
 
 def ddim_step(alpha_bar: torch.Tensor, x_t: torch.Tensor, t: torch.Tensor, t_prev: torch.Tensor, eps: torch.Tensor, eta: float,
@@ -587,20 +622,16 @@ def check_table_index(t: torch.Tensor, n: int, name: str, lo: int = 0) -> None:
 
 # ---------------------------------------------------------------------------------------------- semantic head
 def sem_packed_bytes(dims: EdttsSemDims) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_sem_packed_bytes(C.byref(dims), C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_sem_packed_bytes, C.byref(dims))
 
 
 def sem_num_codes(dims: EdttsSemDims) -> int:
-    out = C.c_int64(0)
-    lib().edtts_sem_num_codes(C.byref(dims), C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_sem_num_codes, C.byref(dims), ctype=C.c_int64)
 
 
 def sem_pack(dims: EdttsSemDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor) -> None:
     """Pack the head's weights (state-dict order, include/edtts.h: edtts_sem_pack) into `packed` (uint8 device tensor)."""
-    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    ptrs = _slot_ptrs(tensors, "weight")
     lib().edtts_sem_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
 
 
@@ -658,28 +689,22 @@ SEM_DROP_STREAM = 0x40000  # include/edtts.h, "Philox stream ids": the head's dr
 
 
 def sem_train_packed_bytes(dims: EdttsSemDims) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_sem_train_packed_bytes(C.byref(dims), C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_sem_train_packed_bytes, C.byref(dims))
 
 
 def sem_train_pack(dims: EdttsSemDims, tensors: Sequence[torch.Tensor], packed_train: torch.Tensor) -> None:
     """The training-only blob (the transposed matrices the backward streams); slots as sem_pack."""
-    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    ptrs = _slot_ptrs(tensors, "weight")
     lib().edtts_sem_train_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed_train, torch.uint8, "packed_train"),
                                _stream(packed_train.device))
 
 
 def sem_train_tape_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_sem_train_tape_bytes(C.byref(dims), B, T, C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_sem_train_tape_bytes, C.byref(dims), B, T)
 
 
 def sem_train_scratch_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
-    out = C.c_size_t(0)
-    lib().edtts_sem_train_scratch_bytes(C.byref(dims), B, T, C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_sem_train_scratch_bytes, C.byref(dims), B, T)
 
 
 def sem_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, tape: torch.Tensor, lengths: Optional[torch.Tensor] = None,
@@ -709,7 +734,7 @@ def sem_backward(dims: EdttsSemDims, packed: torch.Tensor, packed_train: torch.T
     """edtts_sem_backward: writes the gradient of every non-None entry of `grads` (slot order) and d_z (dims.in_dim == 0).  ``drop``:
     what the forward that filled `tape` was given."""
     B, T, _ = h.shape
-    ptrs = (C.c_void_p * len(grads))(*[_dev_ptr(g, torch.float32, f"grad[{i}]") for i, g in enumerate(grads)])
+    ptrs = _slot_ptrs(grads, "grad")
     scratch = torch.empty(sem_train_scratch_bytes(dims, B, T), dtype=torch.uint8, device=h.device)
     drop = _dropout(drop)
     lib().edtts_sem_backward(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(packed_train, torch.uint8, "packed_train"),
@@ -732,9 +757,7 @@ def sem_dropout_mask(dims: EdttsSemDims, B: int, T: int, p: float, seed: int, de
 
 # ---------------------------------------------------------------------------------------------- HuBERT backbone
 def hubert_frames(dims: EdttsHubertDims, n_samples: int) -> int:
-    out = C.c_int64(0)
-    lib().edtts_hubert_frames(C.byref(dims), int(n_samples), C.byref(out))
-    return out.value
+    return _size_query(lib().edtts_hubert_frames, C.byref(dims), int(n_samples), ctype=C.c_int64)
 
 
 # compute dtypes of the HuBERT backbone (include/edtts.h: EDTTS_HUBERT_FP32 / EDTTS_HUBERT_BF16)
@@ -742,27 +765,21 @@ HUBERT_DTYPES = {"fp32": 0, "bf16": 1}
 
 
 def hubert_packed_bytes(dims: EdttsHubertDims, compute_dtype: int = 0) -> int:
-    out = C.c_size_t(0)
     if compute_dtype:
-        lib().edtts_hubert_packed_bytes_dt(C.byref(dims), int(compute_dtype), C.byref(out))
-    else:
-        lib().edtts_hubert_packed_bytes(C.byref(dims), C.byref(out))
-    return out.value
+        return _size_query(lib().edtts_hubert_packed_bytes_dt, C.byref(dims), int(compute_dtype))
+    return _size_query(lib().edtts_hubert_packed_bytes, C.byref(dims))
 
 
 def hubert_workspace_bytes(dims: EdttsHubertDims, B: int, T_audio: int, compute_dtype: int = 0) -> int:
-    out = C.c_size_t(0)
     if compute_dtype:
-        lib().edtts_hubert_workspace_bytes_dt(C.byref(dims), int(compute_dtype), int(B), int(T_audio), C.byref(out))
-    else:
-        lib().edtts_hubert_workspace_bytes(C.byref(dims), int(B), int(T_audio), C.byref(out))
-    return out.value
+        return _size_query(lib().edtts_hubert_workspace_bytes_dt, C.byref(dims), int(compute_dtype), int(B), int(T_audio))
+    return _size_query(lib().edtts_hubert_workspace_bytes, C.byref(dims), int(B), int(T_audio))
 
 
 def hubert_pack(dims: EdttsHubertDims, tensors: Sequence[torch.Tensor], packed: torch.Tensor, compute_dtype: int = 0) -> None:
     """Pack the backbone's weights (include/edtts.h: edtts_hubert_pack / edtts_hubert_pack_dt, slot order there) into `packed`
     (uint8 device tensor)."""
-    ptrs = (C.c_void_p * len(tensors))(*[_dev_ptr(t, torch.float32, f"weight[{i}]") for i, t in enumerate(tensors)])
+    ptrs = _slot_ptrs(tensors, "weight")
     if compute_dtype:
         lib().edtts_hubert_pack_dt(C.byref(dims), int(compute_dtype), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"),
                                    _stream(packed.device))

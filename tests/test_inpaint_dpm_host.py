@@ -148,3 +148,55 @@ def test_plan_is_the_same_for_both_solvers():
                                     hop_length=160, sample_rate=8000, solver=solver, steps=5)
     assert seen["ddim"][0] == seen["dpmpp"][0] and seen["ddim"][1] == seen["dpmpp"][1]
     assert seen["ddim"][2] == seen["dpmpp"][2] and [p["n_chunks"] for p in seen["ddim"][2]] == [smp.chunk_plan(t, 48, 12, 160)[0] for t in totals]
+
+
+def _inpaint_call(symbol, cfg, modes=(1, 1), **over):
+    """The argument list of one in-painting export at B=2, S=4 with every pointer a (never dereferenced) small integer, `over`
+    replacing arguments by name."""
+    dims = EdgeDiffusionDecoder(cfg).dims()
+    ptr = iter(range(64, 4096, 64))
+    coef = (ctypes.c_float * 16)(*([1.0] * 16))
+    coef[0], coef[8] = modes
+    a = dict(dims=ctypes.byref(dims), packed=next(ptr), workspace=next(ptr), workspace_uncond=None, B=2, T=8, S=4, sem_features=next(ptr),
+             zero_features=None, x=next(ptr), num_steps=2, t_all=next(ptr), step_all=next(ptr), coef_host=coef, known_mel=None,
+             overlap_len=0, noise_k=None, seed=ctypes.c_uint64(0), cfg_scale=1.0, v_uncond=None)
+    if symbol != "edtts_sample_inpaint":
+        a.update(t_len=None, s_len=None, seeds=None)
+    if symbol == SYMBOL:
+        a.update(hist=next(ptr), x0_all=None)
+    a["stream"] = None
+    assert set(over) <= set(a), over
+    a.update(over)
+    return [ctypes.c_void_p(v) if isinstance(v, int) and k not in ("B", "T", "S", "num_steps", "overlap_len") else v for k, v in a.items()], dims
+
+
+def test_inpaint_entry_points_keep_their_errors():
+    """Every invalid call below returns before the first HIP call (no GPU needed), with the code and the message the entry points
+    had when each carried its own copy of the checks: the first failing check stays the first."""
+    cfg = CFG(device="cpu")
+    max_pos = EdgeDiffusionDecoder(cfg).dims().max_pos
+    ARG = -2  # EDTTS_ERR_ARG
+    null = (ARG, "NULL pointer argument")
+    known = 4096
+    table = []
+    for sym in ("edtts_sample_inpaint", "edtts_sample_inpaint_len", SYMBOL):
+        table += [
+            (sym, dict(packed=None), null),
+            (sym, dict(num_steps=0), (ARG, "num_steps=0 < 1")),
+            (sym, dict(cfg_scale=1.5), (ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond")),
+            (sym, dict(known_mel=known, overlap_len=0), (ARG, "overlap_len=0 outside [1,8]")),
+            (sym, dict(known_mel=known, overlap_len=9), (ARG, "overlap_len=9 outside [1,8]")),
+            (sym, dict(T=max_pos + 1), (ARG, f"T={max_pos + 1} exceeds the positional table ({max_pos} rows) -- the reference raises here too")),
+        ]
+    table += [
+        (SYMBOL, dict(hist=None), null),
+        (SYMBOL, dict(modes=(0, 1)), (ARG, "step 0: bad solver mode 0")),
+        (SYMBOL, dict(modes=(2, 1)), (ARG, "step 0: bad solver mode 2")),
+    ]
+    L = native.lib()
+    for sym, over, (code, text) in table:
+        args, _keep = _inpaint_call(sym, cfg, **over)
+        with pytest.raises(native.EdttsError) as e:
+            getattr(L, sym)(*args)
+        got = (int(re.search(r"\(code (-?\d+)\)", str(e.value)).group(1)), L.edtts_last_error().decode())
+        assert got == (code, text), (sym, over, got)
