@@ -35,6 +35,40 @@ static int dw_slab_rows(int M) {
   return r > kDwSlabRows ? r : kDwSlabRows;
 }
 
+// Per-utterance lengths in the backward.  Rows are laid out [utterance][rpb rows]; utterance b has
+// utt_len(len, b, rpb) live rows and the rest is padding that is never loaded.
+// (len is non-null in all of these; utt_len_of directly, as elsewhere: a further caller of utt_len_lane changes k_gen_embed's code)
+EDTTS_DEV int row_count(const int64_t* len, int b, int rpb) { return utt_len_of(len[b], rpb, false); }
+// row r is live (r below the row count)
+EDTTS_DEV bool row_live(const int64_t* len, int rpb, int r) {
+  const int b = r / rpb;
+  return r - b * rpb < row_count(len, b, rpb);
+}
+// some row of [r0, r1) is live (r0 < r1 <= row count): the first utterance's live rows reach r0, or the next utterance begins
+// before r1 (every utterance has a live row 0)
+EDTTS_DEV bool rows_any_live(const int64_t* len, int rpb, int r0, int r1) {
+  const int b = r0 / rpb;
+  return r0 - b * rpb < row_count(len, b, rpb) || (b + 1) * rpb < r1;
+}
+// bit i: row r + i is live (rows at or past `total` are not)
+EDTTS_DEV unsigned rows_live4(const int64_t* len, int rpb, int r, int total) {
+  if (r >= total) return 0u;
+  int b = r / rpb, pos = r - b * rpb, n = row_count(len, b, rpb);
+  unsigned m = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (r + i >= total) break;
+    if (pos >= rpb) {
+      pos = 0;
+      n = row_count(len, ++b, rpb);
+    }
+    if (pos < n) m |= 1u << i;
+    ++pos;
+  }
+  return m;
+}
+
+enum { LEN_ROWS = 1, LEN_K = 2 };
 struct BGemmArgs {
   const float *A, *B;
   float* C;
@@ -43,8 +77,13 @@ struct BGemmArgs {
   int ldc, kslab;          // block z contracts k in [z kslab, (z + 1) kslab) into C + z cslab   (kslab % 16 == 0)
   size_t cslab;
   int va, vb, vc;          // 16-byte loads along k (unit k stride, aligned rows, K % 4 == 0) / 16-byte stores
+  // k_bwd_gemm<ACC, true>: per-utterance lengths of rpb rows each.  LEN_ROWS: m is the row (dX) -- dead rows of A load as 0, so
+  // dead rows of C get 0 (ACC: stay as they are), and a tile of 64 dead rows contracts nothing; LEN_K: k is the row (dW) -- dead
+  // k load as 0 in both operands and a k-step of 16 dead rows is skipped.  Every test that skips is the same for the whole block.
+  const int64_t* len;
+  int rpb, lmode;
 };
-template <int ACC>
+template <int ACC, bool LEN = false>
 __global__ __launch_bounds__(256) void k_bwd_gemm(BGemmArgs a) {
   using namespace edtts_gen;
   __shared__ float xs[kGBM][kGLd];
@@ -52,12 +91,17 @@ __global__ __launch_bounds__(256) void k_bwd_gemm(BGemmArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fq = lane & 15, g = lane >> 4;
   const int m0 = blockIdx.x * kGBM, n0 = blockIdx.y * kGBN;
   const int kbeg = blockIdx.z * a.kslab;
-  const int kend = kbeg + a.kslab < a.K ? kbeg + a.kslab : a.K;
+  int kend = kbeg + a.kslab < a.K ? kbeg + a.kslab : a.K;
   // loaders: an operand with unit k stride is read four k per thread (row = tid / 4); one with unit row stride one row per lane
   // (row = tid % 64), so that neighbouring threads read neighbouring addresses either way
   const int alr = a.sak == 1 ? tid >> 2 : tid & 63, alk = a.sak == 1 ? 4 * (tid & 3) : 4 * (tid >> 6);
   const int blr = a.sbk == 1 ? tid >> 2 : tid & 63, blk = a.sbk == 1 ? 4 * (tid & 3) : 4 * (tid >> 6);
-  const bool aok = m0 + alr < a.M, bok = n0 + blr < a.N;
+  bool aok = m0 + alr < a.M;
+  const bool bok = n0 + blr < a.N;
+  if (LEN && a.lmode == LEN_ROWS) {
+    if (!rows_any_live(a.len, a.rpb, m0, m0 + kGBM < a.M ? m0 + kGBM : a.M)) kend = kbeg;  // (block-uniform: no k-step, zeros stored)
+    aok = aok && row_live(a.len, a.rpb, m0 + alr);
+  }
   const float* ap = a.A + (size_t)(aok ? m0 + alr : 0) * a.sam;
   const float* bp = a.B + (size_t)(bok ? n0 + blr : 0) * a.sbn;
   const int wn0 = 32 * (w & 1), wn1 = wn0 + 16, wm = 32 * (w >> 1);
@@ -69,17 +113,27 @@ __global__ __launch_bounds__(256) void k_bwd_gemm(BGemmArgs a) {
   for (int k0 = kbeg; k0 < kend; k0 += kGBK) {
     f4 xv = splat(0.f), wv = splat(0.f);
     const int ka = k0 + alk, kb = k0 + blk;
-    if (a.va) {
-      if (aok && ka < kend) xv = ldg4(ap + ka);
-    } else {
+    if (LEN && a.lmode == LEN_K) {  // (never with 16-byte loads along k: the rows are strided there)
+      if (!rows_any_live(a.len, a.rpb, k0, k0 + kGBK < kend ? k0 + kGBK : kend)) continue;  // (block-uniform, ahead of the barriers)
+      const unsigned la = rows_live4(a.len, a.rpb, ka, kend), lb = rows_live4(a.len, a.rpb, kb, kend);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) xv[r] = (aok && ka + r < kend) ? ap[(size_t)(ka + r) * a.sak] : 0.f;
-    }
-    if (a.vb) {
-      if (bok && kb < kend) wv = ldg4(bp + kb);
+      for (int r = 0; r < 4; ++r) {
+        xv[r] = (aok && (la >> r & 1u)) ? ap[(size_t)(ka + r) * a.sak] : 0.f;
+        wv[r] = (bok && (lb >> r & 1u)) ? bp[(size_t)(kb + r) * a.sbk] : 0.f;
+      }
     } else {
+      if (a.va) {
+        if (aok && ka < kend) xv = ldg4(ap + ka);
+      } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) wv[r] = (bok && kb + r < kend) ? bp[(size_t)(kb + r) * a.sbk] : 0.f;
+        for (int r = 0; r < 4; ++r) xv[r] = (aok && ka + r < kend) ? ap[(size_t)(ka + r) * a.sak] : 0.f;
+      }
+      if (a.vb) {
+        if (bok && kb < kend) wv = ldg4(bp + kb);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wv[r] = (bok && kb + r < kend) ? bp[(size_t)(kb + r) * a.sbk] : 0.f;
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -134,13 +188,20 @@ __global__ __launch_bounds__(256) void k_bwd_slabsum(const float* part, float* o
 }
 
 // part[slab][N]: column sums of rows [slab kColRows, ...) of Y[M][ld]
-__global__ __launch_bounds__(256) void k_bwd_colsum(const float* Y, int ld, int M, int N, float* part) {
+// (len non-null: rows past their utterance's count, rpb rows each, are not loaded)
+__global__ __launch_bounds__(256) void k_bwd_colsum(const float* Y, int ld, int M, int N, float* part, const int64_t* len, int rpb) {
   __shared__ float sm[4][64];
   const int c = threadIdx.x & 63, rg = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
   const int r0 = blockIdx.y * kColRows, r1 = r0 + kColRows < M ? r0 + kColRows : M;
   float s = 0.f;
-  if (col < N)
-    for (int r = r0 + rg; r < r1; r += 4) s += Y[(size_t)r * ld + col];
+  if (col < N) {
+    if (len == nullptr) {
+      for (int r = r0 + rg; r < r1; r += 4) s += Y[(size_t)r * ld + col];
+    } else {
+      for (int r = r0 + rg; r < r1; r += 4)
+        if (row_live(len, rpb, r)) s += Y[(size_t)r * ld + col];
+    }
+  }
   sm[rg][c] = s;
   __syncthreads();
   if (rg == 0 && col < N) part[(size_t)blockIdx.y * N + col] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
@@ -156,15 +217,21 @@ struct NormBwdArgs {
   float* part;       // k_bwd_norm_cols: [chunk][3][W]
   int rows, W, rows_per_b, mod_bstride, acc;
   float eps;
+  const int64_t* len;  // per-utterance live rows of rows_per_b, or null
 };
 template <int MODE>
 __global__ __launch_bounds__(256) void k_bwd_norm_rows(NormBwdArgs a) {
   using namespace edtts_gen;
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= a.rows) return;
+  if (row >= a.rows) return;  // (no block-level synchronisation in this kernel: a wave may leave)
   const float* x = a.x + (size_t)row * a.W;
   const float* dy = a.dy + (size_t)row * a.W;
   float* dx = a.dx + (size_t)row * a.W;
+  if (a.len != nullptr && !row_live(a.len, a.rows_per_b, row)) {  // a padding row: x, dy and stat are not touched, dx is 0
+    if (!a.acc)
+      for (int j = lane; j < a.W; j += 64) dx[j] = 0.f;
+    return;
+  }
   if (MODE == NORM_LAYER) {  // y = (x - mu) rs w + b
     float s = 0.f;
     for (int j = lane; j < a.W; j += 64) s += x[j];
@@ -218,8 +285,8 @@ __global__ __launch_bounds__(256) void k_bwd_norm_cols(NormBwdArgs a) {
   const int cpb = (a.rows_per_b + kNormChunk - 1) / kNormChunk;
   const int b = blockIdx.y / cpb, ch = blockIdx.y - b * cpb;
   const int r0 = b * a.rows_per_b + ch * kNormChunk;
-  const int e = (b + 1) * a.rows_per_b, r1 = r0 + kNormChunk < e ? r0 + kNormChunk : e;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  const int e = b * a.rows_per_b + utt_len(a.len, b, a.rows_per_b), r1 = r0 + kNormChunk < e ? r0 + kNormChunk : e;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;  // (a chunk wholly past the utterance's count sums nothing and stores zeros)
   if (col < a.W) {
     const float wj = a.w[col];
     const float* md = a.mod ? a.mod + (size_t)b * a.mod_bstride : nullptr;
@@ -311,11 +378,17 @@ __global__ __launch_bounds__(256) void k_drop_mask(uint8_t* keep, size_t rows, i
 
 // ---- attention ---------------------------------------------------------------------------------------------------------------
 // delta[(b HEADS + hd) Tq + i] = sum_d dO[row][hd DH + d] O[row][hd DH + d]   (row = b Tq + i), d ascending
-__global__ __launch_bounds__(256) void k_bwd_attn_delta(const float* o, const float* dO, float* delta, int B, int Tq, int HEADS, int DH, int ld) {
+// (q_len non-null: a query past its utterance's count gets 0 without a load)
+__global__ __launch_bounds__(256) void k_bwd_attn_delta(const float* o, const float* dO, float* delta, int B, int Tq, int HEADS, int DH, int ld,
+                                                        const int64_t* q_len) {
   const size_t n = (size_t)B * HEADS * Tq;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t bh = i / Tq;
     const int q = (int)(i - bh * Tq), hd = (int)(bh % HEADS);
+    if (q_len != nullptr && q >= row_count(q_len, (int)(bh / HEADS), Tq)) {
+      delta[i] = 0.f;
+      continue;
+    }
     const size_t row = (bh / HEADS) * Tq + q;
     const float* op = o + row * ld + (size_t)hd * DH;
     const float* dp = dO + row * ld + (size_t)hd * DH;
@@ -331,6 +404,7 @@ struct AttnBwdArgs {
   int ldq, ldkv, ldo, lddq, lddkv, Tq, Tk, DH, window;
   float scale, scale_nat;       // log2(e) / sqrt(head_dim) (scores as the forward forms them), 1 / sqrt(head_dim)
   DropArgs dr;                  // the <DT, true> instantiations only: the forward's mask of the probabilities
+  const int64_t *q_len, *k_len; // per-utterance query / key counts [B], or null: Tq / Tk for all (as AttnArgs)
 };
 // One wave = 16 queries of one (utterance, head), laid out as k_gen_attn: S^T = K Q^T and dP^T = V dO^T tiles hold (key 4g + r,
 // query fq) on lane (g, fq); dS^T is then the B operand of dQ^T += K^T dS^T as P^T is of O^T += V^T P^T in the forward.
@@ -340,7 +414,18 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
   const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
   const int qi = q0 + fq;
-  const bool qok = qi < a.Tq;
+  // Per-utterance lengths: queries and keys are bounded by the utterance's counts, with the forward's lo / hi sequence; nothing past
+  // them is loaded.  The dq rows of padding queries are stored as zeros (the destination is reused scratch that the next dX / dW
+  // reads); a block wholly past the count does only that (one wave per block: leaving early is safe).
+  const int Tqb = utt_len(a.q_len, b, a.Tq), Tkb = utt_len(a.k_len, b, a.Tk);
+  if (q0 >= Tqb) {
+    if (qi < a.Tq) {
+      float* zrow = a.dq + ((size_t)b * a.Tq + qi) * a.lddq + hd * a.DH;
+      for (int d = g; d < a.DH; d += 4) zrow[d] = 0.f;
+    }
+    return;
+  }
+  const bool qok = qi < Tqb;
   const size_t qr = (size_t)b * a.Tq + (qok ? qi : 0);
   const float* qrow = a.q + qr * a.ldq + hd * a.DH;
   const float* drow = a.dO + qr * a.ldo + hd * a.DH;
@@ -357,11 +442,11 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
   f4 acc[DT];
 #pragma unroll
   for (int t = 0; t < DT; ++t) acc[t] = splat(0.f);
-  int lo = 0, hi = a.Tk;
+  int lo = 0, hi = Tkb;
   if (a.window >= 0) {
     lo = q0 - a.window > 0 ? q0 - a.window : 0;
     const int e = q0 + 16 + a.window;
-    hi = e < a.Tk ? e : a.Tk;
+    hi = e < Tkb ? e : Tkb;
   }
   const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
   const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
@@ -402,14 +487,14 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
       }
     }
   }
-  if (!qok) return;
+  if (qi >= a.Tq) return;
   float* orow = a.dq + ((size_t)b * a.Tq + qi) * a.lddq + hd * a.DH;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int d = 16 * t + 4 * g + r;  // acc[t] lane (g, i) holds dQ^T[d][i]
-      if (d < a.DH) orow[d] = acc[t][r] * a.scale_nat;
+      if (d < a.DH) orow[d] = qok ? acc[t][r] * a.scale_nat : 0.f;
     }
 }
 // One wave = 16 keys of one (utterance, head).  S = Q K^T and dP = dO V^T tiles hold (query 4g + r, key fq) on lane (g, fq): P and
@@ -420,7 +505,18 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
   const int lane = threadIdx.x, fq = lane & 15, g = lane >> 4;
   const int k0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
   const int kj = k0 + fq;
-  const bool kok = kj < a.Tk;
+  // Per-utterance lengths: as in k_bwd_attn_dq -- the query walk ends at the utterance's query count, the dk / dv rows of padding
+  // keys are stored as zeros, and a block wholly past the key count does only that.
+  const int Tqb = utt_len(a.q_len, b, a.Tq), Tkb = utt_len(a.k_len, b, a.Tk);
+  if (k0 >= Tkb) {
+    if (kj < a.Tk) {
+      float* zk = a.dk + ((size_t)b * a.Tk + kj) * a.lddkv + hd * a.DH;
+      float* zv = a.dv + ((size_t)b * a.Tk + kj) * a.lddkv + hd * a.DH;
+      for (int d = g; d < a.DH; d += 4) zk[d] = zv[d] = 0.f;
+    }
+    return;
+  }
+  const bool kok = kj < Tkb;
   const size_t kr = (size_t)b * a.Tk + (kok ? kj : 0);
   const float* krow = a.k + kr * a.ldkv + hd * a.DH;
   const float* vrow = a.v + kr * a.ldkv + hd * a.DH;
@@ -435,11 +531,11 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
   f4 ak[DT], av[DT];
 #pragma unroll
   for (int t = 0; t < DT; ++t) ak[t] = av[t] = splat(0.f);
-  int lo = 0, hi = a.Tq;
+  int lo = 0, hi = Tqb;
   if (a.window >= 0) {
     lo = k0 - a.window > 0 ? k0 - a.window : 0;
     const int e = k0 + 16 + a.window;
-    hi = e < a.Tq ? e : a.Tq;
+    hi = e < Tqb ? e : Tqb;
   }
   const float* qb = a.q + (size_t)b * a.Tq * a.ldq + hd * a.DH;
   const float* db = a.dO + (size_t)b * a.Tq * a.ldo + hd * a.DH;
@@ -492,7 +588,7 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
       }
     }
   }
-  if (!kok) return;
+  if (kj >= a.Tk) return;
   float* okp = a.dk + ((size_t)b * a.Tk + kj) * a.lddkv + hd * a.DH;
   float* ovp = a.dv + ((size_t)b * a.Tk + kj) * a.lddkv + hd * a.DH;
 #pragma unroll
@@ -501,8 +597,8 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
     for (int r = 0; r < 4; ++r) {
       const int d = 16 * t + 4 * g + r;  // lane (g, j) holds dK^T[d][j], dV^T[d][j]
       if (d < a.DH) {
-        okp[d] = ak[t][r] * a.scale_nat;
-        ovp[d] = av[t][r];
+        okp[d] = kok ? ak[t][r] * a.scale_nat : 0.f;
+        ovp[d] = kok ? av[t][r] : 0.f;
       }
     }
 }
@@ -511,7 +607,10 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
 // out[row][c] = sum over positions p (ascending) whose index, clamped as the forward clamps it, is row, of src[p][c]: block = row.
 // The block walks the positions 256 at a time; the ones that hit its row are compacted IN POSITION ORDER into LDS (ballot + prefix
 // count) and every column thread adds them in that order, so a chunk without a hit costs one index load per thread.
-__global__ __launch_bounds__(256) void k_bwd_scatter_rows(const int64_t* idx, int n_pos, int n_rows, const float* src, int H, float* out) {
+// len non-null: positions come rpb per utterance and the ones at or past the utterance's count are not scanned (the forward gave them
+// id 0 without reading idx, and their src rows are zero).
+__global__ __launch_bounds__(256) void k_bwd_scatter_rows(const int64_t* idx, int n_pos, int n_rows, const float* src, int H, float* out,
+                                                          const int64_t* len, int rpb) {
   __shared__ int list[256];
   __shared__ int wcnt[4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -520,7 +619,7 @@ __global__ __launch_bounds__(256) void k_bwd_scatter_rows(const int64_t* idx, in
     for (int c0 = 0; c0 < n_pos; c0 += 256) {
       const int p = c0 + tid;
       bool hit = false;
-      if (p < n_pos) {
+      if (p < n_pos && (len == nullptr || row_live(len, rpb, p))) {
         long tk = (long)idx[p];
         tk = tk < 0 ? 0 : (tk >= n_rows ? n_rows - 1 : tk);
         hit = tk == row;
@@ -658,6 +757,11 @@ struct DropState {
 // =========================================================================================================
 // TrainLauncher: forward with a tape, backward from it
 // =========================================================================================================
+// A row set with per-utterance lengths: rpb rows per utterance of which len[b] are live (len null: all of them)
+struct RowLens {
+  const int64_t* len = nullptr;
+  int rpb = 0;
+};
 struct TrainLauncher {
   using G = GenericLauncher;
   static int copy(hipStream_t st, float* dst, const float* src, size_t n) {
@@ -665,8 +769,11 @@ struct TrainLauncher {
     return EDTTS_OK;
   }
 
-  // GenericLauncher::ctx + GenericLauncher::forward (TAIL_EPS, no lengths): the same launches in the same order; what the backward
+  // GenericLauncher::ctx + GenericLauncher::forward (TAIL_EPS): the same launches in the same order; what the backward
   // needs goes to the tape instead of the workspace, or is copied there.  The AdaLN rows are already in the tape (launch_cond).
+  // Per-utterance lengths (c.ln) enter where they enter there: the embedding's padding ids, both attentions' key counts and query
+  // skip, and eps zeroed past T_b -- so eps is bitwise edtts_decoder_forward_len's.  Tape rows past the lengths hold whatever the
+  // row-local steps made of the padding (or nothing at all: skipped query blocks); the backward never loads them.
   // drop non-null: the four dropout sites of every block run their masked instantiations (the tape's attention outputs and SwiGLU
   // output are then the dropped ones); null: exactly the launches described above.
   static int forward(const CallCtx& c, float* tp, const TrainTape& tt, const float* x, const int64_t* sem_idx, const float* sem_feat, float* eps,
@@ -677,6 +784,7 @@ struct TrainLauncher {
     const float* blob = c.blob;
     float* wsb = c.wsb;
     const hipStream_t st = c.st;
+    const Lens& ln = c.ln;
     const int B = c.B, T = c.T, S = c.S, M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL;
     float* cx = tp + tt.ctx;
     if (sem_feat) {
@@ -686,7 +794,7 @@ struct TrainLauncher {
       size_t nb = ((size_t)CS * H + 255) / 256;
       if (nb > 4096) nb = 4096;
       hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, cx, CS, S, H, lo.NTOK, err,
-                         (const int64_t*)nullptr);
+                         ln.s);
       LAUNCH_CHECK("k_gen_embed");
     }
     for (int l = 0; l < lo.L; ++l) {
@@ -712,13 +820,13 @@ struct TrainLauncher {
       TRY_G(copy(st, tp + z.h0, h, MH));
       TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, qkv, 3 * H, M, 3 * H, H));
-      TRY_G(G::attn(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, T, T, c.window, nullptr, nullptr, false, false, tp + z.lse1,
+      TRY_G(G::attn(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, T, T, c.window, ln.t, ln.t, false, false, tp + z.lse1,
                     D(DROP_ATTN)));
       TRY_G(G::gemm<EPI_RESID>(st, tp + z.att1, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
       TRY_G(copy(st, tp + z.h1, h, MH));
       TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, tp + z.qc, H, M, H, H));
-      TRY_G(G::attn(st, lo, B, tp + z.qc, H, kv, kv + H, 2 * H, tp + z.att2, T, S, -1, nullptr, nullptr, false, false, tp + z.lse2,
+      TRY_G(G::attn(st, lo, B, tp + z.qc, H, kv, kv + H, 2 * H, tp + z.att2, T, S, -1, ln.t, ln.s, false, false, tp + z.lse2,
                     D(DROP_CROSS)));
       TRY_G(G::gemm<EPI_RESID>(st, tp + z.att2, H, blob + y.g_op, nullptr, h, H, M, H, H));
       TRY_G(copy(st, tp + z.h2, h, MH));
@@ -729,6 +837,10 @@ struct TrainLauncher {
     TRY_G(copy(st, tp + tt.hL, h, MH));
     TRY_G(G::norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
     TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, eps, MEL, M, MEL, H));
+    if (ln.t) {
+      hipLaunchKernelGGL(k_gen_zero_past, dim3(G::grid_1d((size_t)M * MEL)), dim3(256), 0, st, eps, ln.t, 0, (size_t)M * MEL, T, MEL);
+      LAUNCH_CHECK("k_gen_zero_past");
+    }
     return EDTTS_OK;
   }
 
@@ -736,7 +848,10 @@ struct TrainLauncher {
   static bool al16(const void* p) { return G::al16(p); }
   static int bgemm(hipStream_t st, edtts_bwd::BGemmArgs a, int slabs, bool acc) {
     const dim3 grid((a.M + 63) / 64, (a.N + 63) / 64, slabs);
-    if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<1>, grid, dim3(256), 0, st, a);
+    if (a.len) {
+      if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<1, true>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<0, true>), grid, dim3(256), 0, st, a);
+    } else if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<1>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<0>, grid, dim3(256), 0, st, a);
     LAUNCH_CHECK("k_bwd_gemm");
     return EDTTS_OK;
@@ -747,7 +862,9 @@ struct TrainLauncher {
     return EDTTS_OK;
   }
   // dX[M][K] (+)= dY[M][N] W[N][K]   (wT: the blob keeps W transposed, [K][N])
-  static int dx(hipStream_t st, const float* dY, long ldy, const float* W, int M, int N, int K, float* dX, int ldx, bool acc, bool wT = false) {
+  // (rl: the M rows' lengths -- dead rows of dY are not loaded, dead rows of dX are 0)
+  static int dx(hipStream_t st, const float* dY, long ldy, const float* W, int M, int N, int K, float* dX, int ldx, bool acc, bool wT = false,
+                RowLens rl = RowLens{}) {
     edtts_bwd::BGemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = dY; a.B = W; a.C = dX; a.M = M; a.N = K; a.K = N;
@@ -756,10 +873,13 @@ struct TrainLauncher {
     a.va = (N % 4 == 0) && (ldy % 4 == 0) && al16(dY);
     a.vb = wT && (N % 4 == 0) && al16(W);
     a.vc = (ldx % 4 == 0) && al16(dX);
+    a.len = rl.len; a.rpb = rl.rpb; a.lmode = edtts_bwd::LEN_ROWS;
     return bgemm(st, a, 1, acc);
   }
   // dW[N][K] = dY[M][N]^T X[M][K]: slabs of dw_slab_rows(M) rows, summed in slab order
-  static int dw(hipStream_t st, const float* dY, long ldy, const float* X, long ldx, int M, int N, int K, float* dW, float* part) {
+  // (rl: the M rows' lengths -- dead rows of dY and X are not loaded)
+  static int dw(hipStream_t st, const float* dY, long ldy, const float* X, long ldx, int M, int N, int K, float* dW, float* part,
+                RowLens rl = RowLens{}) {
     if (!dW) return EDTTS_OK;
     const int rows = edtts_bwd::dw_slab_rows(M), ns = (M + rows - 1) / rows;
     edtts_bwd::BGemmArgs a;
@@ -768,14 +888,15 @@ struct TrainLauncher {
     a.sam = 1; a.sak = ldy; a.sbn = 1; a.sbk = ldx;
     a.ldc = K; a.kslab = rows; a.cslab = (size_t)N * K;
     a.vc = (K % 4 == 0) && al16(a.C);
+    a.len = rl.len; a.rpb = rl.rpb; a.lmode = edtts_bwd::LEN_K;
     TRY_G(bgemm(st, a, ns, false));
     if (ns > 1) TRY_G(slabsum(st, part, dW, (size_t)N * K, ns, (size_t)N * K));
     return EDTTS_OK;
   }
-  static int colsum(hipStream_t st, const float* Y, int ld, int M, int N, float* out, float* part) {
+  static int colsum(hipStream_t st, const float* Y, int ld, int M, int N, float* out, float* part, RowLens rl = RowLens{}) {
     if (!out) return EDTTS_OK;
     const int ns = (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows;
-    hipLaunchKernelGGL(edtts_bwd::k_bwd_colsum, dim3((N + 63) / 64, ns), dim3(256), 0, st, Y, ld, M, N, part);
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_colsum, dim3((N + 63) / 64, ns), dim3(256), 0, st, Y, ld, M, N, part, rl.len, rl.rpb);
     LAUNCH_CHECK("k_bwd_colsum");
     return slabsum(st, part, out, (size_t)N, ns, (size_t)N);
   }
@@ -784,8 +905,8 @@ struct TrainLauncher {
   template <int MODE>
   static int norm_bwd(hipStream_t st, const float* x, const float* dy, float* dxp, bool acc, int rows, int W, int rows_per_b, const float* w,
                       float eps, const float* mod, int mod_bstride, float* stat, float* part, float* dgain, float* dbias, float* dmod,
-                      int dmod_bstride) {
-    edtts_bwd::NormBwdArgs a{x, dy, dxp, w, mod, stat, part, rows, W, rows_per_b, mod_bstride, (int)acc, eps};
+                      int dmod_bstride, const int64_t* len = nullptr) {
+    edtts_bwd::NormBwdArgs a{x, dy, dxp, w, mod, stat, part, rows, W, rows_per_b, mod_bstride, (int)acc, eps, len};
     hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_rows<MODE>, dim3((rows + 3) / 4), dim3(256), 0, st, a);
     LAUNCH_CHECK("k_bwd_norm_rows");
     if (!dgain && !dbias && !dmod) return EDTTS_OK;
@@ -800,13 +921,13 @@ struct TrainLauncher {
   // gradients of one attention call: dq, dk, dv from q, k, v, the output o, its gradient dO and the tape's log-sum-exp
   static int attn_bwd(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, const float* o,
                       const float* dO, const float* lse, float* delta, float* dq, int lddq, float* dk, float* dv, int lddkv, int Tq, int Tk,
-                      int window, const DropArgs* dr = nullptr) {
+                      int window, const DropArgs* dr = nullptr, const int64_t* q_len = nullptr, const int64_t* k_len = nullptr) {
     const size_t n = (size_t)B * lo.HEADS * Tq;
-    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, lo.HEADS, lo.DH, lo.H);
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, lo.HEADS, lo.DH, lo.H, q_len);
     LAUNCH_CHECK("k_bwd_attn_delta");
     const float sn = 1.0f / sqrtf((float)lo.DH);
     edtts_bwd::AttnBwdArgs a{q, k, v, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
-                             1.4426950408889634f / sqrtf((float)lo.DH), sn, dr ? *dr : DropArgs{}};
+                             1.4426950408889634f / sqrtf((float)lo.DH), sn, dr ? *dr : DropArgs{}, q_len, k_len};
     const dim3 gq((Tq + 15) / 16, lo.HEADS, B), gk((Tk + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
 #define EDTTS_BWD_ATTN(DT)                                                                      \
@@ -832,8 +953,12 @@ struct TrainLauncher {
   // gs: gradient destinations in edtts_pack_weights slot order (null: not wanted).
   static int backward(const Layout& lo, const float* blob, const float* tp, const TrainTape& tt, float* sc, const TrainScratch& ss, int B, int T,
                       int S, int window, const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_feat,
-                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t st, const DropState* drop = nullptr) {
+                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t st, const DropState* drop = nullptr,
+                      const Lens& ln = Lens{}) {
     using namespace edtts_gen;
+    // Per-utterance lengths: tr / sr mask every contraction over decoder / context rows and zero the dead
+    // rows of every dX; the elementwise steps in between run on all rows (what they make of a dead row is never loaded again).
+    const RowLens tr{ln.t, T}, sr{ln.s, S};
     const int M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL, L = lo.L;
     float *dh = sc + ss.dh, *xn = sc + ss.xn, *ga = sc + ss.ga, *gq = sc + ss.gq, *big = sc + ss.big, *da = sc + ss.da;
     float *stat = sc + ss.stat, *delta = sc + ss.delta, *dkv = sc + ss.dkv, *crn = sc + ss.crn, *dcr = sc + ss.dcr, *dcp = sc + ss.dcp;
@@ -844,12 +969,12 @@ struct TrainLauncher {
     auto GG = [&](int i) { return gs[i]; };
     HIP_TRY(hipMemsetAsync(dctx, 0, (size_t)CS * H * sizeof(float), st));
     // out_proj and final_norm
-    TRY_G(colsum(st, d_eps, MEL, M, MEL, GG(G_OUT_B), part));
+    TRY_G(colsum(st, d_eps, MEL, M, MEL, GG(G_OUT_B), part, tr));
     TRY_G(G::norm<NORM_LAYER>(st, tp + tt.hL, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
-    TRY_G(dw(st, d_eps, MEL, xn, H, M, MEL, H, GG(G_OUT_W), part));
-    TRY_G(dx(st, d_eps, MEL, blob + lo.s_outp, M, MEL, H, ga, H, false));
+    TRY_G(dw(st, d_eps, MEL, xn, H, M, MEL, H, GG(G_OUT_W), part, tr));
+    TRY_G(dx(st, d_eps, MEL, blob + lo.s_outp, M, MEL, H, ga, H, false, false, tr));
     TRY_G(norm_bwd<NORM_LAYER>(st, tp + tt.hL, ga, dh, false, M, H, T, blob + lo.fnw, 1e-5f, nullptr, 0, stat, part, GG(G_FN_W), GG(G_FN_B),
-                               nullptr, 0));
+                               nullptr, 0, ln.t));
     for (int l = L - 1; l >= 0; --l) {
       const LayerLayout& y = lo.layer[l];
       const TapeLayer& z = tt.layer[l];
@@ -866,9 +991,9 @@ struct TrainLauncher {
         LAUNCH_CHECK("k_bwd_drop_rows");
         dd = gq;
       }
-      TRY_G(colsum(st, dd, H, M, H, W(L_DOWN_B), part));
-      TRY_G(dw(st, dd, H, tp + z.act, FH, M, H, FH, W(L_DOWN_W), part));
-      TRY_G(dx(st, dd, H, blob + y.g_down, M, H, FH, da, FH, false));
+      TRY_G(colsum(st, dd, H, M, H, W(L_DOWN_B), part, tr));
+      TRY_G(dw(st, dd, H, tp + z.act, FH, M, H, FH, W(L_DOWN_W), part, tr));
+      TRY_G(dx(st, dd, H, blob + y.g_down, M, H, FH, da, FH, false, false, tr));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h2, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cb));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_up, blob + y.up_b, big, 2 * FH, M, 2 * FH, H));
       if (drop)
@@ -877,57 +1002,57 @@ struct TrainLauncher {
       else
         hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu, dim3(G::grid_1d((size_t)M * FH)), dim3(256), 0, st, big, da, (size_t)M, FH);
       LAUNCH_CHECK("k_bwd_swiglu");
-      TRY_G(colsum(st, big, 2 * FH, M, 2 * FH, W(L_UP_B), part));
-      TRY_G(dw(st, big, 2 * FH, xn, H, M, 2 * FH, H, W(L_UP_W), part));
-      TRY_G(dx(st, big, 2 * FH, blob + y.g_up, M, 2 * FH, H, ga, H, false));
+      TRY_G(colsum(st, big, 2 * FH, M, 2 * FH, W(L_UP_B), part, tr));
+      TRY_G(dw(st, big, 2 * FH, xn, H, M, 2 * FH, H, W(L_UP_W), part, tr));
+      TRY_G(dx(st, big, 2 * FH, blob + y.g_up, M, 2 * FH, H, ga, H, false, false, tr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h2, ga, dh, true, M, H, T, blob + y.n3w, 1e-6f, cond_row + l * row + 2 * H, cb, stat, part, W(L_N3_W),
-                               nullptr, dmod + l * row + 2 * H, cb));
+                               nullptr, dmod + l * row + 2 * H, cb, ln.t));
       // cross-attention branch: h2 = h1 + att2 Wop^T
-      TRY_G(dw(st, dh, H, tp + z.att2, H, M, H, H, W(L_OP_W), part));
-      TRY_G(dx(st, dh, H, blob + y.g_op, M, H, H, ga, H, false));
+      TRY_G(dw(st, dh, H, tp + z.att2, H, M, H, H, W(L_OP_W), part, tr));
+      TRY_G(dx(st, dh, H, blob + y.g_op, M, H, H, ga, H, false, false, tr));
       TRY_G(attn_bwd(st, lo, B, tp + z.qc, H, tp + z.kv, tp + z.kv + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
-                     S, -1, D(DROP_CROSS)));
+                     S, -1, D(DROP_CROSS), ln.t, ln.s));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h1, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
-      TRY_G(dw(st, gq, H, xn, H, M, H, H, W(L_QP_W), part));
-      TRY_G(dx(st, gq, H, blob + y.g_qp, M, H, H, ga, H, false));
-      TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h1, ga, dh, true, M, H, T, blob + y.n2w, 1e-6f, nullptr, 0, stat, part, W(L_N2_W), nullptr, nullptr, 0));
+      TRY_G(dw(st, gq, H, xn, H, M, H, H, W(L_QP_W), part, tr));
+      TRY_G(dx(st, gq, H, blob + y.g_qp, M, H, H, ga, H, false, false, tr));
+      TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h1, ga, dh, true, M, H, T, blob + y.n2w, 1e-6f, nullptr, 0, stat, part, W(L_N2_W), nullptr, nullptr, 0, ln.t));
       // ... and its context chain: context -> kv_down -> kv_norm -> kv_up -> K|V
       TRY_G(G::norm<NORM_RMS>(st, tp + z.crp, crn, CS, R, blob + y.kvn, nullptr, 1e-6f));
-      TRY_G(dw(st, dkv, 2 * H, crn, R, CS, 2 * H, R, W(L_KVU_W), part));
-      TRY_G(dx(st, dkv, 2 * H, blob + y.kvu, CS, 2 * H, R, dcr, R, false));
+      TRY_G(dw(st, dkv, 2 * H, crn, R, CS, 2 * H, R, W(L_KVU_W), part, sr));
+      TRY_G(dx(st, dkv, 2 * H, blob + y.kvu, CS, 2 * H, R, dcr, R, false, false, sr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.crp, dcr, dcp, false, CS, R, S, blob + y.kvn, 1e-6f, nullptr, 0, stat, part, W(L_KVN_W), nullptr,
-                               nullptr, 0));
-      TRY_G(dw(st, dcp, R, tp + tt.ctx, H, CS, R, H, W(L_KVD_W), part));
-      TRY_G(dx(st, dcp, R, blob + y.kvd, CS, R, H, dctx, H, true));
+                               nullptr, 0, ln.s));
+      TRY_G(dw(st, dcp, R, tp + tt.ctx, H, CS, R, H, W(L_KVD_W), part, sr));
+      TRY_G(dx(st, dcp, R, blob + y.kvd, CS, R, H, dctx, H, true, false, sr));
       // self-attention branch: h1 = h0 + att1 Wproj^T + b
-      TRY_G(colsum(st, dh, H, M, H, W(L_PROJ_B), part));
-      TRY_G(dw(st, dh, H, tp + z.att1, H, M, H, H, W(L_PROJ_W), part));
-      TRY_G(dx(st, dh, H, blob + y.g_proj, M, H, H, ga, H, false));
+      TRY_G(colsum(st, dh, H, M, H, W(L_PROJ_B), part, tr));
+      TRY_G(dw(st, dh, H, tp + z.att1, H, M, H, H, W(L_PROJ_W), part, tr));
+      TRY_G(dx(st, dh, H, blob + y.g_proj, M, H, H, ga, H, false, false, tr));
       const float* qkv = tp + z.qkv;
       TRY_G(attn_bwd(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, ga, tp + z.lse1, delta, big, 3 * H, big + H, big + 2 * H,
-                     3 * H, T, T, window, D(DROP_ATTN)));
+                     3 * H, T, T, window, D(DROP_ATTN), ln.t, ln.t));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h0, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cb));
-      TRY_G(dw(st, big, 3 * H, xn, H, M, 3 * H, H, W(L_QKV_W), part));
-      TRY_G(dx(st, big, 3 * H, blob + y.s_qkv, M, 3 * H, H, ga, H, false));
+      TRY_G(dw(st, big, 3 * H, xn, H, M, 3 * H, H, W(L_QKV_W), part, tr));
+      TRY_G(dx(st, big, 3 * H, blob + y.s_qkv, M, 3 * H, H, ga, H, false, false, tr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h0, ga, dh, true, M, H, T, blob + y.n1w, 1e-6f, cond_row + l * row, cb, stat, part, W(L_N1_W), nullptr,
-                               dmod + l * row, cb));
+                               dmod + l * row, cb, ln.t));
     }
     // in_proj
-    TRY_G(colsum(st, dh, H, M, H, GG(G_INP_B), part));
-    TRY_G(dw(st, dh, H, x, MEL, M, H, MEL, GG(G_INP_W), part));
-    if (d_x) TRY_G(dx(st, dh, H, blob + lo.inp, M, H, MEL, d_x, MEL, false));
+    TRY_G(colsum(st, dh, H, M, H, GG(G_INP_B), part, tr));
+    TRY_G(dw(st, dh, H, x, MEL, M, H, MEL, GG(G_INP_W), part, tr));
+    if (d_x) TRY_G(dx(st, dh, H, blob + lo.inp, M, H, MEL, d_x, MEL, false, false, tr));
     // context sources
     if (sem_feat) {
-      TRY_G(colsum(st, dctx, H, CS, H, GG(G_SEMP_B), part));
-      TRY_G(dw(st, dctx, H, sem_feat, lo.SD, CS, H, lo.SD, GG(G_SEMP_W), part));
-      if (d_sem) TRY_G(dx(st, dctx, H, blob + lo.semp, CS, H, lo.SD, d_sem, lo.SD, false));
+      TRY_G(colsum(st, dctx, H, CS, H, GG(G_SEMP_B), part, sr));
+      TRY_G(dw(st, dctx, H, sem_feat, lo.SD, CS, H, lo.SD, GG(G_SEMP_W), part, sr));
+      if (d_sem) TRY_G(dx(st, dctx, H, blob + lo.semp, CS, H, lo.SD, d_sem, lo.SD, false, false, sr));
       if (GG(G_TOK)) HIP_TRY(hipMemsetAsync(GG(G_TOK), 0, (size_t)lo.NTOK * H * sizeof(float), st));  // (does not enter the output)
     } else {
       if (GG(G_SEMP_W)) HIP_TRY(hipMemsetAsync(GG(G_SEMP_W), 0, (size_t)H * lo.SD * sizeof(float), st));
       if (GG(G_SEMP_B)) HIP_TRY(hipMemsetAsync(GG(G_SEMP_B), 0, (size_t)H * sizeof(float), st));
     }
     if (!sem_feat && GG(G_TOK)) {
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NTOK), dim3(256), 0, st, sem_idx, CS, lo.NTOK, dctx, H, GG(G_TOK));
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NTOK), dim3(256), 0, st, sem_idx, CS, lo.NTOK, dctx, H, GG(G_TOK), ln.s, S);
       LAUNCH_CHECK("k_bwd_scatter_rows");
     }
     // conditioning path: AdaLN projections, then the time MLP and step_emb
@@ -954,7 +1079,8 @@ struct TrainLauncher {
     }
     if (!any_time) return EDTTS_OK;
     if (GG(G_STEP) && step_idx) {
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NSTEP), dim3(256), 0, st, step_idx, B, lo.NSTEP, dtc, H, GG(G_STEP));
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NSTEP), dim3(256), 0, st, step_idx, B, lo.NSTEP, dtc, H, GG(G_STEP),
+                         (const int64_t*)nullptr, 0);
       LAUNCH_CHECK("k_bwd_scatter_rows");
     }
     // t_cond = W3 GELU(W1 e + b1) + b3: recompute e, the pre-activation and the hidden row

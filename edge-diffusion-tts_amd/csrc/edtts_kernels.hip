@@ -3344,6 +3344,14 @@ int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void*
 int edtts_decoder_forward_train_drop(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
                                      const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
                                      const float* sem_features, float* eps, const EdttsDropout* drop, void* stream) {
+  return edtts_decoder_forward_train_len(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, drop, nullptr,
+                                         nullptr, stream);
+}
+
+int edtts_decoder_forward_train_len(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                    const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                    const float* sem_features, float* eps, const EdttsDropout* drop, const int64_t* t_len,
+                                    const int64_t* s_len, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY(train_layout(dims, "edtts_decoder_forward_train", &lo));
@@ -3361,8 +3369,9 @@ int edtts_decoder_forward_train_drop(const EdttsDims* dims, const void* packed, 
   make_workspace(lo, B, T, S, B, &ws);
   TrainTape tt;
   make_tape(lo, B, T, S, &tt);
+  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
   TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, tp + tt.cond, wsb, st));  // the AdaLN rows and t_cond go straight to the tape
-  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{}, st};
+  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
   return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps, dropping ? &ds : nullptr);
 }
 
@@ -3377,6 +3386,14 @@ int edtts_decoder_backward_drop(const EdttsDims* dims, const void* packed, void*
                                 const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                                 const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
                                 const EdttsDropout* drop, void* stream) {
+  return edtts_decoder_backward_len(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots,
+                                    d_x, d_sem_features, scratch, drop, nullptr, nullptr, stream);
+}
+
+int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                               const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                               const EdttsDropout* drop, const int64_t* t_len, const int64_t* s_len, void* stream) {
   Layout lo;
   TRY(train_layout(dims, "edtts_decoder_backward", &lo));
   DropState ds;
@@ -3390,9 +3407,10 @@ int edtts_decoder_backward_drop(const EdttsDims* dims, const void* packed, void*
   make_tape(lo, B, T, S, &tt);
   TrainScratch ss;
   make_train_scratch(lo, B, T, S, &ss);
+  TRY(launch_len_check(t_len, s_len, B, T, S, (float*)workspace, (hipStream_t)stream));  // (the index-error word: the only use of `workspace`)
   return TrainLauncher::backward(lo, (const float*)packed, (const float*)tape, tt, (float*)scratch, ss, B, T, S, dims->window, x, t, step_idx,
                                  sem_features ? nullptr : sem_idx, sem_features, d_eps, reinterpret_cast<float* const*>(grad_slots), d_x,
-                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr);
+                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr, Lens{t_len, s_len});
 }
 
 int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep, void* stream) {

@@ -7,6 +7,7 @@ gfx950 kernels.  By default inference only (the reference path this replaces run
 dropout is the identity as in ``decoder.eval()``.  ``autograd=True`` (generic fp32 kernels) adds the backward the reference's
 trainers need (train_v2.py train_step, training/consistency.py): DESIGN.md section 19.  ``train_dropout=True`` adds the reference's
 four dropout sites to that training forward and backward, with masks from the library's Philox stream: DESIGN.md section 20.
+``train_lengths=True`` lets that forward take ``x_lengths`` / ``sem_lengths`` (ragged training batches): DESIGN.md section 22.
 """
 from __future__ import annotations
 
@@ -42,10 +43,11 @@ class _DecoderGrad(torch.autograd.Function):
     """eps = decoder(...) on the training forward (edtts_decoder_forward_train); backward through edtts_decoder_backward.  The tape is
     a tensor of this call's own, saved in ctx: any number of forwards may share the decoder's cached workspace before a backward.
     ``drop``: None, or the (p, seed) pair of this call's dropout masks; it lives in ctx, so the backward regenerates the masks of
-    ITS forward whatever the decoder has run since."""
+    ITS forward whatever the decoder has run since.  ``lens``: (t_len, s_len), device int64 [B] or None each (train_lengths=True),
+    kept in ctx for the backward as well."""
 
     @staticmethod
-    def forward(ctx, dec, t, sem_idx, step_idx, names, drop, x_t, sem_features, *params):
+    def forward(ctx, dec, t, sem_idx, step_idx, names, drop, x_t, sem_features, lens, *params):
         B, T, _ = x_t.shape
         S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
         dims = dec.dims()
@@ -57,8 +59,8 @@ class _DecoderGrad(torch.autograd.Function):
         sem_idx = None if sem_features is not None or sem_idx is None else sem_idx.contiguous()
         feats = None if sem_features is None else sem_features.detach().contiguous()
         tape = torch.empty(native.train_tape_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
-        eps = native.decoder_forward_train(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, S, drop)
-        ctx.dec, ctx.names, ctx.S, ctx.sig, ctx.drop = dec, names, S, dec._packed_sig, drop
+        eps = native.decoder_forward_train(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, S, drop, *lens)
+        ctx.dec, ctx.names, ctx.S, ctx.sig, ctx.drop, ctx.lens = dec, names, S, dec._packed_sig, drop, lens
         ctx.inputs = (x, t, step_idx, sem_idx, feats)
         ctx.save_for_backward(tape, *params)
         return eps
@@ -74,18 +76,19 @@ class _DecoderGrad(torch.autograd.Function):
         B, T, _ = x.shape
         dims, packed = dec.dims(), dec._packed
         ws = dec.workspace(B, T, ctx.S, B, x.device)
-        wanted = {n: p for n, p, need in zip(ctx.names, params, ctx.needs_input_grad[8:]) if need and dec._enters_output(n, feats is not None, step_idx is not None)}
+        wanted = {n: p for n, p, need in zip(ctx.names, params, ctx.needs_input_grad[9:]) if need and dec._enters_output(n, feats is not None, step_idx is not None)}
         out = {n: torch.empty_like(p) for n, p in wanted.items()}
         slots = [out.get(dec._slot_param(n)) for n in native.slot_names(dec.cfg.layers)]
         d_x = torch.empty_like(x) if ctx.needs_input_grad[6] else None
         d_f = torch.empty_like(feats) if feats is not None and ctx.needs_input_grad[7] else None
-        native.decoder_backward(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, ctx.S, d_eps.contiguous(), slots, d_x, d_f, ctx.drop)
-        return (None, None, None, None, None, None, d_x, d_f, *[out.get(n) for n in ctx.names])
+        native.decoder_backward(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, ctx.S, d_eps.contiguous(), slots, d_x, d_f, ctx.drop,
+                                *ctx.lens)
+        return (None, None, None, None, None, None, d_x, d_f, None, *[out.get(n) for n in ctx.names])
 
 
 class EdgeDiffusionDecoder(nn.Module):
     def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled",
-                 autograd: bool = False, train_dropout: bool = False):
+                 autograd: bool = False, train_dropout: bool = False, train_lengths: bool = False):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
@@ -104,10 +107,17 @@ class EdgeDiffusionDecoder(nn.Module):
         ``torch.manual_seed`` makes a run repeatable), keeps it for its own backward and shows it as ``self.last_dropout_seed``.
         The masks are the library's (include/edtts.h, "Dropout masks"), not torch's random stream.  ``.eval()``, ``cfg.dropout ==
         0`` and calls that are not differentiable are unchanged; in particular a training-mode call under ``torch.no_grad()`` runs
-        the inference forward WITHOUT dropout (the reference would drop there too): DESIGN.md section 20."""
+        the inference forward WITHOUT dropout (the reference would drop there too): DESIGN.md section 20.
+        ``train_lengths``: False (default) -- a differentiable forward given ``x_lengths`` / ``sem_lengths`` raises, as before.  True
+        (needs ``autograd=True``) -- that forward takes them (a ragged training batch): eps is bitwise the inference forward's with
+        the same lengths (0 past ``x_lengths[b]``), the backward reads nothing past the lengths, padding contributes exactly nothing
+        to any gradient, and ``x_t.grad`` / ``sem_features.grad`` are 0 there.  Composes with ``train_dropout``: DESIGN.md section 22."""
         super().__init__()
         self.autograd = bool(autograd)
         self.train_dropout = bool(train_dropout)
+        self.train_lengths = bool(train_lengths)
+        if self.train_lengths and not self.autograd:
+            raise ValueError("train_lengths=True needs autograd=True (the lengths belong to the training forward and its backward)")
         if self.train_dropout and not self.autograd:
             raise ValueError("train_dropout=True needs autograd=True (dropout belongs to the training forward and its backward)")
         self.dropout_generator: Optional[torch.Generator] = None
@@ -418,8 +428,14 @@ class EdgeDiffusionDecoder(nn.Module):
     def _forward_autograd(self, x_t, t, sem_idx, step_idx, sem_features, x_lengths, sem_lengths) -> torch.Tensor:
         if sem_idx is None and sem_features is None:
             raise ValueError("Either sem_idx or sem_features must be provided")
+        lens = (None, None)
         if x_lengths is not None or sem_lengths is not None:
-            raise ValueError("autograd=True: x_lengths / sem_lengths are not supported by the backward (pad-free batches only)")
+            if not self.train_lengths:
+                raise ValueError("autograd=True: x_lengths / sem_lengths are not supported by the backward (pad-free batches only) "
+                                 "unless the decoder was built with train_lengths=True")
+            B, T, _ = x_t.shape
+            S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
+            lens = (native.lengths(x_lengths, B, T, x_t.device, "x_lengths"), native.lengths(sem_lengths, B, S, x_t.device, "sem_lengths"))
         drop = None
         if self.training and self.cfg.dropout > 0 and self.train_dropout:
             # (a host draw from a CPU generator: no device work, no synchronisation)
@@ -430,7 +446,7 @@ class EdgeDiffusionDecoder(nn.Module):
             raise ValueError(f"autograd=True: the kernels have no dropout but cfg.dropout={self.cfg.dropout} and the decoder is in "
                              "training mode (the reference applies attention and FFN dropout there): set cfg.dropout = 0 or call .eval()")
         names, params = self._named_params()
-        return _DecoderGrad.apply(self, t, sem_idx, step_idx, names, drop, x_t, sem_features, *params)
+        return _DecoderGrad.apply(self, t, sem_idx, step_idx, names, drop, x_t, sem_features, lens, *params)
 
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, sem_idx: Optional[torch.Tensor] = None,

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "edtts_decoder_forward_train_drop", "edtts_decoder_backward_drop", "edtts_dropout_mask",
     "edtts_sem_train_packed_bytes", "edtts_sem_train_pack", "edtts_sem_train_tape_bytes", "edtts_sem_train_scratch_bytes",
     "edtts_sem_encode_train", "edtts_sem_backward", "edtts_sem_dropout_mask",
+    "edtts_decoder_forward_train_len", "edtts_decoder_backward_len",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -180,6 +181,9 @@ def lib() -> C.CDLL:
     L.edtts_decoder_backward_drop.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
                                               vp, vp, vp, dpp, vp]
     L.edtts_dropout_mask.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, i32, i32, dpp, vp, vp]
+    L.edtts_decoder_forward_train_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, dpp, vp, vp, vp]
+    L.edtts_decoder_backward_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
+                                             vp, vp, vp, dpp, vp, vp, vp]
     L.edtts_sem_train_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
     L.edtts_sem_train_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
     L.edtts_sem_train_tape_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
@@ -333,16 +337,21 @@ def _dropout(drop) -> Optional[EdttsDropout]:
 
 def decoder_forward_train(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, tape: torch.Tensor, x: torch.Tensor,
                           t: torch.Tensor, step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor],
-                          sem_features: Optional[torch.Tensor], S: int, drop=None) -> torch.Tensor:
+                          sem_features: Optional[torch.Tensor], S: int, drop=None, t_len: Optional[torch.Tensor] = None,
+                          s_len: Optional[torch.Tensor] = None) -> torch.Tensor:
     """edtts_decoder_forward_train: eps, with the backward's tape written to `tape` (uint8, train_tape_bytes).  ``drop``: None (the
-    plain export), or an EdttsDropout / (p, seed) pair -> edtts_decoder_forward_train_drop."""
+    plain export), or an EdttsDropout / (p, seed) pair -> edtts_decoder_forward_train_drop.  ``t_len`` / ``s_len``: per-utterance
+    frame / token counts, device int64 [B] or None (see lengths()); with either, edtts_decoder_forward_train_len runs."""
     B, T, M = x.shape
     eps = torch.empty_like(x)
     drop = _dropout(drop)
     args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
             _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"),
             _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"), eps.data_ptr())
-    if drop is None:
+    if t_len is not None or s_len is not None:
+        lib().edtts_decoder_forward_train_len(*args, None if drop is None else C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
+                                              _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
+    elif drop is None:
         lib().edtts_decoder_forward_train(*args, _stream(x.device))
     else:
         lib().edtts_decoder_forward_train_drop(*args, C.byref(drop), _stream(x.device))
@@ -353,19 +362,29 @@ def decoder_forward_train(dims: EdttsDims, packed: torch.Tensor, workspace: torc
 def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, tape: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
                      step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor], S: int,
                      d_eps: torch.Tensor, grads: Sequence[Optional[torch.Tensor]], d_x: Optional[torch.Tensor],
-                     d_sem_features: Optional[torch.Tensor], drop=None) -> None:
+                     d_sem_features: Optional[torch.Tensor], drop=None, t_len: Optional[torch.Tensor] = None,
+                     s_len: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> None:
     """edtts_decoder_backward: writes the gradient of every non-None entry of `grads` (slot order), d_x and d_sem_features.
-    ``drop``: what the forward that filled `tape` was given (None: the plain export, else edtts_decoder_backward_drop)."""
+    ``drop``: what the forward that filled `tape` was given (None: the plain export, else edtts_decoder_backward_drop).
+    ``t_len`` / ``s_len``: the lengths that forward was given (device int64 [B] or None; with either, edtts_decoder_backward_len
+    runs).  ``scratch``: the caller's own (uint8, at least train_scratch_bytes) instead of one allocated here."""
     B, T, M = x.shape
     ptrs = _slot_ptrs(grads, "grad")
-    scratch = torch.empty(train_scratch_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
+    nbytes = train_scratch_bytes(dims, B, T, S)
+    if scratch is None:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    elif _dev_ptr(scratch, torch.uint8, "scratch") is None or scratch.numel() < nbytes:
+        raise EdttsError(f"scratch: expected at least {nbytes} bytes, got {scratch.numel()}")
     drop = _dropout(drop)
     args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
             _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"),
             _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"),
             _dev_ptr(d_eps, torch.float32, "d_eps"), ptrs, len(grads), _dev_ptr(d_x, torch.float32, "d_x"),
             _dev_ptr(d_sem_features, torch.float32, "d_sem_features"), scratch.data_ptr())
-    if drop is None:
+    if t_len is not None or s_len is not None:
+        lib().edtts_decoder_backward_len(*args, None if drop is None else C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
+                                         _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
+    elif drop is None:
         lib().edtts_decoder_backward(*args, _stream(x.device))
     else:
         lib().edtts_decoder_backward_drop(*args, C.byref(drop), _stream(x.device))

@@ -146,7 +146,7 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
  * For train.py / train_v2.py / training/consistency.py, whose steps call decoder(x_t, t, ...) under autograd (train_v2.py
  * train_step; training/consistency.py consistency_loss calls it twice before one backward()).  First version: generic kernels
  * and fp32 only -- dims.compute_dtype must be EDTTS_F32 | EDTTS_KERNELS_GENERIC, anything else is EDTTS_ERR_UNSUPPORTED with a
- * message naming the cause -- and no per-utterance lengths.  These entry points run the decoder.eval() arithmetic (dropout off:
+ * message naming the cause -- and no per-utterance lengths (those: the *_train_len / *_backward_len calls further down).  These entry points run the decoder.eval() arithmetic (dropout off:
  * layers/attention.py and layers/transformer.py apply dropout only when training); the *_drop twins below add the dropout.  Conventions as everywhere: no allocation, no host synchronisation,
  * work only on `stream`, graph-capturable.  Every reduction has a fixed order: a backward is bitwise reproducible.
  *
@@ -234,6 +234,41 @@ int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T,
 int edtts_decoder_forward_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S,
                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
                               const float* sem_features, const int64_t* t_len, const int64_t* s_len, float* eps, void* stream);
+
+/* ---- training on ragged batches: per-utterance lengths in the training forward and the backward ----------
+ * The arguments of the *_drop twins plus t_len / s_len (device int64 [B], frames T_b / tokens S_b) before `stream`.  drop may be
+ * NULL (no dropout); each length array may be NULL (full length).  The four entry points above ARE these calls with NULL lengths,
+ * bitwise.  Tape and scratch sizes are those of the plain calls (edtts_train_tape_bytes / edtts_train_scratch_bytes).  Argument errors
+ * are reported before any pointer is looked at.  Values outside [1, T] / [1, S] are clamped into range and set EDTTS_IDX_LEN in the
+ * workspace's index-error word (the backward writes that word and nothing else of `workspace`).
+ * Contract, for 1 <= T_b <= T and 1 <= S_b <= S, both independent per utterance:
+ *   1. forward: eps is bitwise edtts_decoder_forward_len on the generic path with the same lengths -- so row b on frames [0, T_b)
+ *      is bitwise its solo call, and eps is exactly 0 on [T_b, T);
+ *   2. nothing past an utterance's lengths enters a result, in the forward or the backward: not the padding of x, sem_features,
+ *      sem_idx (no index check there) or d_eps, and not the tape's or the scratch's rows past the lengths.  NaN in that padding, any
+ *      int64 in the padding of sem_idx, a tape or scratch pre-filled with 0xFF bytes: no output bit changes.  (The tape's rows past
+ *      the lengths hold whatever the forward's row-local steps made of the padding, or were never written; every sum over rows in
+ *      the backward predicates its loads on the row being live instead of relying on a zero gradient there);
+ *   3. input gradients: d_x[b, :T_b] and d_sem_features[b, :S_b] are bitwise those of the backward called on utterance b alone
+ *      (B = 1, T = T_b, S = S_b, the same t / step_idx, d_eps[b, :T_b]); both are exactly 0 past the lengths;
+ *   4. weight gradients are the sum over utterances of the solo gradients -- padding rows and tokens contribute exactly nothing.  Not
+ *      bitwise the solo sum (the slab boundaries of the cut reductions differ), but bitwise reproducible (fixed reduction orders, no
+ *      float atomics) and bitwise independent of what the padding holds;
+ *   5. full lengths (T_b = T, S_b = S for all b) give bitwise the gradients of the call without lengths;
+ *   6. dropout: the masks stay keyed by the padded layout (c3 = b * heads + h, c1 = b * T + t), so an utterance's masks do not
+ *      depend on anybody's lengths; but because the key contains b, the solo equalities of 1 and 3 do NOT hold under dropout.
+ *      2, 4 and 5 hold unchanged; 3 becomes: the rows of d_x / d_sem_features of utterance b do not depend on the other
+ *      utterances' lengths or contents.
+ * The lengths are read by the kernels at run time: a captured graph serves any length mix copied into the same arrays. */
+int edtts_decoder_forward_train_len(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                    const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                    const float* sem_features, float* eps, const EdttsDropout* drop, const int64_t* t_len,
+                                    const int64_t* s_len, void* stream);
+int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                               const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
+                               float* d_sem_features, void* scratch, const EdttsDropout* drop, const int64_t* t_len,
+                               const int64_t* s_len, void* stream);
 
 /* ---- DDIM update  (schedule.py:157-202, DiffusionSchedule.get_ddim_step) --------------------------------
  * alpha_bar [n_table] fp32 table; t, t_prev [B] int64 (t_prev < 0 -> alpha_bar_prev = 1); n_per_batch =
