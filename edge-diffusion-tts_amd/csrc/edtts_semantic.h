@@ -162,6 +162,8 @@ struct EncTrainArgs : EncArgs {
   float* t_zb;   // tape: tanh(proj_down(z)) [N][16]
   DropArgs dr;   // the mask between LayerNorm and the last Linear
   int dropping;
+  float* t_r;    // VQ tape: r = c - z [N][S]
+  float* t_sq;   // VQ tape: sum_s r^2 per frame [N]
 };
 template <bool TRAIN>
 struct EncArgsOf { using type = EncArgs; };
@@ -430,14 +432,37 @@ __global__ __launch_bounds__(256) void k_sem_encode(typename EncArgsOf<TRAIN>::t
     }
     if (bi == 0x7fffffff) bi = 0;  // every distance NaN
     code = bi;
-    if (a.zq && frame < a.N) {
-      const float* crow = p + a.cbraw + (size_t)bi * S + 4 * grp;
+    if constexpr (TRAIN) {
+      // the training forward (edtts_semantic_bwd.h): next to the gather, the residual r = c - z and its
+      // per-frame sum of squares go to the tape (the loss and both gradients are functions of r alone)
+      float q = 0.f;
+      if (frame < a.N) {
+        const float* crow = p + a.cbraw + (size_t)bi * S + 4 * grp;
 #pragma unroll
-      for (int t = 0; t < kMaxNT; ++t)
-        if (t < nt) {
-          const f4 c = ldg4(crow + 16 * t);
-          stg4(a.zq + orow + 16 * t, ok ? z[t] + (c - z[t]) : splat(0.f));
-        }
+        for (int t = 0; t < kMaxNT; ++t)
+          if (t < nt) {
+            const f4 c = ldg4(crow + 16 * t);
+            const f4 r = c - z[t];
+            stg4(a.zq + orow + 16 * t, ok ? z[t] + r : splat(0.f));
+            stg4(a.t_r + orow + 16 * t, ok ? r : splat(0.f));
+            if (ok) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) q = fmaf(r[j], r[j], q);
+            }
+          }
+      }
+      q = group_sum(q);  // every lane group of a frame then holds the same value: one store
+      if (grp == 0 && frame < a.N) a.t_sq[frame] = q;
+    } else {
+      if (a.zq && frame < a.N) {
+        const float* crow = p + a.cbraw + (size_t)bi * S + 4 * grp;
+#pragma unroll
+        for (int t = 0; t < kMaxNT; ++t)
+          if (t < nt) {
+            const f4 c = ldg4(crow + 16 * t);
+            stg4(a.zq + orow + 16 * t, ok ? z[t] + (c - z[t]) : splat(0.f));
+          }
+      }
     }
   }
   if (grp == 0 && frame < a.N) {

@@ -92,6 +92,8 @@ struct SemBwdArgs {
   size_t lng, lnb, half, lev, wuT, wdT, w3T;
   DropArgs dr;
   int dropping;
+  const float* t_r;         // k_sem_bwd_frames<true>: the VQ tape's r = c - z [N][S]
+  const float* coef;        // ... and coef[0] = g commit 2 / (N S) on the device (g: the incoming gradient of vq_loss)
 };
 
 // group_sum in fp64
@@ -101,6 +103,9 @@ EDTTS_DEV double group_sum_d(double v) {
   return v;
 }
 
+// VQ: the head of the chain is dz = G - coef r (G = d z_q through the straight-through line, null: 0; the commitment loss's share
+// from the tape's r), and everything from dz onward is the FSQ instantiation's.
+template <bool VQ>
 __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
   __shared__ f4 buf[2][kChunk];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, grp = lane >> 4;
@@ -119,8 +124,18 @@ __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
   const size_t rd = (size_t)(ok ? frame : 0);           // the row this lane reads (frames that are not ok read nothing of their own)
   const size_t orow = (size_t)frame * S + 4 * grp;      // ... and writes (only when `in`)
   const size_t drow = (size_t)frame * 16 + 4 * grp;
+  f4 X[kMaxNT], dz[kMaxNT];
+  if constexpr (VQ) {
+    const float coef = a.coef[0];
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t) {
+      const f4 G = (ok && a.g && t < nt) ? ldg4(a.g + rd * S + 4 * grp + 16 * t) : splat(0.f);
+      const f4 r = (ok && t < nt) ? ldg4(a.t_r + rd * S + 4 * grp + 16 * t) : splat(0.f);
+      dz[t] = G - coef * r;
+      X[t] = splat(0.f);
+    }
+  } else {
   // ---- G = d z_q as B fragments
-  f4 X[kMaxNT];
 #pragma unroll
   for (int t = 0; t < kMaxNT; ++t) X[t] = (ok && t < nt) ? ldg4(a.g + rd * S + 4 * grp + 16 * t) : splat(0.f);
   if (a.gm && in) {
@@ -156,7 +171,6 @@ __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
     X[0] = du;
   }
   // ---- dz = Wd^T du
-  f4 dz[kMaxNT];
 #pragma unroll
   for (int t = 0; t < kMaxNT; ++t) dz[t] = splat(0.f);
   stream_rt(reinterpret_cast<const f4*>(pt + a.wdT), nt, 1, nullptr, 0, X, buf, [&](int rt, f4 acc) {
@@ -164,6 +178,7 @@ __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
     for (int t = 0; t < kMaxNT; ++t)
       if (t == rt) dz[t] = acc;
   });
+  }
   if (a.dz && in) {
 #pragma unroll
     for (int t = 0; t < kMaxNT; ++t)
@@ -430,7 +445,7 @@ int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void*
   a.wuT = R.wuT; a.wdT = R.wdT; a.w3T = R.w3T;
   a.dr = dr;
   a.dropping = dropping;
-  hipLaunchKernelGGL(k_sem_bwd_frames, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_sem_bwd_frames<false>, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
   LAUNCH_CHECK("k_sem_bwd_frames");
   // the sums over frames, in state-dict slot order
   float* part = sc + ss.part;
@@ -474,6 +489,446 @@ int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDr
   hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * (L.S / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows, L.S,
                      T, 0, dr);
   LAUNCH_CHECK("k_drop_mask");
+  return EDTTS_OK;
+}
+
+}  // extern "C"
+
+// =========================================================================================================
+// training the VQ head: VectorQuantizer in training mode under autograd
+// =========================================================================================================
+// The training forward is k_sem_encode<true> with a.vq set: the inference chain, which also writes the tape
+//   y1 | z (both only with a proj) | r = c - z, each [M][S], then sq [M] = sum_s r^2 per frame           (M = B T_feat)
+// (r, not c: the EMA update overwrites the codebook before the backward runs, and both gradients are functions of r alone).
+//
+//   k_sem_vq_loss     sq -> vq_loss = L + commit L, L = sum sq / (N S): one block, fixed order, fp64 accumulation, rounded once
+//   k_sem_codesum     out[K][S] = sum_m [idx[m] = k] X[m][:] as a one-hot GEMM on v_mfma_f32_16x16x4_f32: the one-hot A operand is
+//                     made in registers from idx (a product by 1.0 or 0.0 is exact), a block owns one tile of 16 codes and one
+//                     slab of dw_slab_rows(M) rows, which its four waves walk 64 rows at a time; a 4-row k-step in which no id
+//                     falls into the tile is skipped (one ballot per 64 rows).  Waves are added in wave order, slabs in ascending
+//                     order by k_bwd_slabsum: no float atomics.
+//                     X = z for ema_w, X = r for the codebook gradient.
+//   k_sem_vq_ema      counts and the code sums of z -> ema_cluster_size, ema_w, codebook.weight (one wave per code)
+//   k_sem_vq_coef     N from the lengths and g = d vq_loss -> coef[0] = g commit 2 / (N S), coef[1] = g 2 / (N S)
+//   k_sem_vq_dcb      d codebook = coef[1] x the code sums of r (rows of unused codes: exactly 0)
+//   k_sem_bwd_frames<true>   dz = G - coef[0] r, then the proj backward of the FSQ instantiation
+namespace edtts_sem {
+
+// Training blob (floats): W3^T [S][S] rt-major in fragment order (nothing without a proj).
+static size_t sem_vq_train_floats(const SemLayout& L) { return L.in_dim ? (size_t)L.nt * L.nt * 64 * 4 : 0; }
+// Tape (floats): with a proj y1 | z | r, without one r alone; then sq [M].
+struct SemVqTape {
+  size_t y1, z, r, sq, total;
+};
+static void sem_vq_tape(const SemLayout& L, size_t M, SemVqTape& t) {
+  const size_t MS = M * L.S;
+  t.y1 = 0;
+  t.z = L.in_dim ? MS : 0;
+  t.r = L.in_dim ? 2 * MS : 0;
+  t.sq = t.r + MS;
+  t.total = t.sq + M;
+}
+// Scratch of the EMA update and the backward (floats): coef [4], csum [K][S] (the summed slabs), with a proj dz | a | dam | xh | dy1
+// [M][S] and stat [M][2], then the partial sums of the reductions.
+struct SemVqScratch {
+  size_t coef, csum, dz, a, dam, xh, dy1, stat, part, total;
+};
+static void sem_vq_scratch(const SemLayout& L, int B, int T, SemVqScratch& s) {
+  const size_t M = (size_t)B * T, S = L.S, MS = M * S;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
+  auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
+  s.coef = take(4);
+  s.csum = take((size_t)L.K * S);
+  s.dz = s.a = s.dam = s.xh = s.dy1 = s.stat = 0;
+  if (L.in_dim) {
+    s.dz = take(MS); s.a = take(MS); s.dam = take(MS); s.xh = take(MS); s.dy1 = take(MS); s.stat = take(2 * M);
+  }
+  const size_t r = edtts_bwd::dw_slab_rows((int)M), ns = (M + r - 1) / r;
+  size_t part = ns > 1 ? ns * (size_t)L.K * S : 0;                                                              // code-sum slabs
+  if (L.in_dim) {
+    if (ns > 1) part = mx(part, ns * S * mx(S, (size_t)L.in_dim));                                              // dW slabs
+    part = mx(part, (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows * S);                                   // bias partials
+    part = mx(part, (size_t)B * (((size_t)T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk) * 3 * S);     // LayerNorm partials
+  }
+  s.part = take(part);
+  s.total = o;
+}
+
+// the number of valid frames: sum of the clamped lengths (len null: B T), every thread of the block gets it
+EDTTS_DEV long long vq_valid_frames(const long long* len, int B, int T, long long* sl) {
+  const int tid = threadIdx.x;
+  long long n = 0;
+  if (len) {
+    for (int b = tid; b < B; b += 256) {
+      const long long v = len[b];
+      n += v < 1 ? 1 : (v > T ? T : v);
+    }
+  }
+  sl[tid] = n;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sl[tid] += sl[tid + o];
+    __syncthreads();
+  }
+  const long long tot = len ? sl[0] : (long long)B * T;
+  __syncthreads();
+  return tot;
+}
+
+// loss[0] = L + commit L with L = (sum_m sq[m]) / (N S) (training == 0: 0).  sq of a frame past its length is 0.
+__global__ __launch_bounds__(256) void k_sem_vq_loss(const float* __restrict__ sq, int M, const long long* __restrict__ len, int B, int T, int S,
+                                                     float commit, int training, float* __restrict__ loss) {
+  __shared__ double sd[256];
+  __shared__ long long sl[256];
+  const int tid = threadIdx.x;
+  const long long N = vq_valid_frames(len, B, T, sl);
+  double s = 0.0;
+  for (int m = tid; m < M; m += 256) s += (double)sq[m];
+  sd[tid] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sd[tid] += sd[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float L = N > 0 ? (float)(sd[0] / ((double)N * (double)S)) : 0.f;
+    *loss = training ? L + commit * L : 0.f;
+  }
+}
+
+// coef[0] = g commit 2 / (N S), coef[1] = g 2 / (N S); g = *d_loss (null: 0)
+__global__ __launch_bounds__(256) void k_sem_vq_coef(const float* __restrict__ d_loss, const long long* __restrict__ len, int B, int T, int S,
+                                                     float commit, float* __restrict__ coef) {
+  __shared__ long long sl[256];
+  const long long N = vq_valid_frames(len, B, T, sl);
+  if (threadIdx.x == 0) {
+    const double g = d_loss ? (double)*d_loss : 0.0;
+    const double c = N > 0 ? g * 2.0 / ((double)N * (double)S) : 0.0;
+    coef[0] = (float)(c * (double)commit);
+    coef[1] = (float)c;
+  }
+}
+
+struct CodeSumArgs {
+  const long long* idx;   // [M]
+  const float* X;         // [M][S]
+  const long long* len;   // [B] or null
+  float* out;             // [slab][K][S]
+  int M, T, S, nt, K, nrt_codes, slab_rows;
+};
+// grid (nrt_codes, slabs): block (x, y) owns code tile x of slab y.  Its four waves take the slab's 64-row chunks in turn (wave w:
+// chunks w, w + 4, ...), rows ascending through the MFMA's fixed k order, and the four partial tiles are added through LDS in wave
+// order ((w0 + w1) + w2) + w3: the result is a function of the inputs alone.
+__global__ __launch_bounds__(256) void k_sem_codesum(CodeSumArgs a) {
+  __shared__ float red[3][kMaxNT * 4][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fq = lane & 15, g = lane >> 4;
+  const int tile = blockIdx.x;
+  const int r0 = blockIdx.y * a.slab_rows, r1 = r0 + a.slab_rows < a.M ? r0 + a.slab_rows : a.M;
+  const int S = a.S, nt = a.nt;
+  f4 acc[kMaxNT];
+#pragma unroll
+  for (int t = 0; t < kMaxNT; ++t) acc[t] = splat(0.f);
+  for (int base = r0 + 64 * w; base < r1; base += 256) {
+    // lane l: the id of row base + l, -1 when the row is past the slab or past its utterance's length
+    const int m = base + lane;
+    int id = -1;
+    if (m < r1) {
+      bool live = true;
+      if (a.len) {
+        const int b = m / a.T, t = m - b * a.T;
+        long long n = a.len[b];
+        n = n < 1 ? 1 : (n > a.T ? a.T : n);
+        live = t < n;
+      }
+      if (live) id = (int)a.idx[m];
+    }
+    const unsigned long long hits = __ballot(id >= 0 && (id >> 4) == tile);
+    if (hits == 0ull) continue;
+#pragma unroll 1
+    for (int q = 0; q < 16; ++q) {
+      const int rid = __shfl(id, 4 * q + g);  // the id of this lane's row of the k-step (every lane takes part)
+      if (((hits >> (4 * q)) & 0xfull) == 0ull) continue;  // (wave-uniform)
+      const float one = rid == 16 * tile + fq ? 1.0f : 0.0f;
+      const float* xp = a.X + (size_t)(base + 4 * q + g) * S + fq;
+#pragma unroll
+      for (int t = 0; t < kMaxNT; ++t)
+        if (t < nt) acc[t] = EDTTS_MFMA(one, rid >= 0 ? xp[16 * t] : 0.f, acc[t]);
+    }
+  }
+  if (w > 0) {
+#pragma unroll
+    for (int t = 0; t < kMaxNT; ++t)
+      if (t < nt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[w - 1][4 * t + r][lane] = acc[t][r];
+      }
+  }
+  __syncthreads();
+  if (w > 0) return;
+  // acc[t][r] = out[code 16 tile + 4 g + r][feature 16 t + fq]
+  float* o = a.out + (size_t)blockIdx.y * a.K * S;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int c = 16 * tile + 4 * g + r;
+    if (c < a.K) {
+#pragma unroll
+      for (int t = 0; t < kMaxNT; ++t)
+        if (t < nt) o[(size_t)c * S + 16 * t + fq] = ((acc[t][r] + red[0][4 * t + r][lane]) + red[1][4 * t + r][lane]) + red[2][4 * t + r][lane];
+    }
+  }
+}
+
+// One wave per code k: n' = ema_cluster_size[k] decay + (1 - decay) counts[k]; ema_w[k] = ema_w[k] decay + (1 - decay) csum[k];
+// codebook[k] = ema_w[k] / max(n', epsilon).  Every lane reads the old n before lane 0 stores the new one (one load instruction).
+__global__ __launch_bounds__(256) void k_sem_vq_ema(const int* __restrict__ counts, const float* __restrict__ csum, int K, int S, float decay,
+                                                    float alpha, float epsilon, float* __restrict__ ecs, float* __restrict__ ema_w,
+                                                    float* __restrict__ codebook) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= K) return;
+  const float n_new = fmaf(alpha, (float)counts[k], ecs[k] * decay);
+  const float den = fmaxf(n_new, epsilon);
+  for (int s = lane; s < S; s += 64) {
+    const size_t e = (size_t)k * S + s;
+    const float wv = fmaf(alpha, csum[e], ema_w[e] * decay);
+    ema_w[e] = wv;
+    codebook[e] = wv / den;
+  }
+  if (lane == 0) ecs[k] = n_new;
+}
+
+// out[e] = coef[1] csum[e]
+__global__ void k_sem_vq_dcb(const float* __restrict__ csum, const float* __restrict__ coef, size_t n, float* __restrict__ out) {
+  const float c = coef[1];
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) out[e] = c * csum[e];
+}
+
+// csum[K][S] = sum over the live rows m of [idx[m] = k] X[m][:]
+static int vq_codesum(hipStream_t st, const SemLayout& L, const long long* idx, const float* X, const long long* len, int M, int T, float* csum,
+                      float* part) {
+  const int rows = edtts_bwd::dw_slab_rows(M), ns = (M + rows - 1) / rows;
+  CodeSumArgs a{idx, X, len, ns == 1 ? csum : part, M, T, L.S, L.nt, L.K, L.nrt_codes, rows};
+  hipLaunchKernelGGL(k_sem_codesum, dim3(L.nrt_codes, ns), dim3(256), 0, st, a);
+  LAUNCH_CHECK("k_sem_codesum");
+  if (ns > 1) TRY_G(TrainLauncher::slabsum(st, part, csum, (size_t)L.K * L.S, ns, (size_t)L.K * L.S));
+  return EDTTS_OK;
+}
+
+}  // namespace edtts_sem
+
+// dims -> layout of a trainable VQ head
+static int sem_vq_dims(const EdttsSemDims* dims, const char* who, edtts_sem::SemLayout& L) {
+  TRY_G(edtts_sem::sem_layout(dims, L));
+  if (!L.vq) return fail(EDTTS_ERR_UNSUPPORTED, "%s: the VQ quantizer only (an FSQ head trains through edtts_sem_encode_train / edtts_sem_backward)", who);
+  return EDTTS_OK;
+}
+static int sem_vq_commit(double commit, const char* who) {
+  if (!(commit >= 0.0) || !(commit <= 1e6)) return fail(EDTTS_ERR_ARG, "%s: commit=%g outside [0, 1e6]", who, commit);
+  return EDTTS_OK;
+}
+
+extern "C" {
+
+int edtts_sem_vq_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_train_packed_bytes", L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  *out_bytes = edtts_sem::sem_vq_train_floats(L) * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_sem_vq_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_train_pack", L));
+  const int want = (L.in_dim ? 6 : 0) + 1;
+  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", want, n_slots);
+  if (!L.in_dim) return EDTTS_OK;  // nothing to pack
+  if (!slots || !packed_train) return fail(EDTTS_ERR_ARG, "slots/packed_train is NULL");
+  for (int i = 0; i < n_slots; ++i)
+    if (!slots[i]) return fail(EDTTS_ERR_ARG, "weight slot %d is NULL", i);
+  const long long n = (long long)L.nt * L.nt * 256;
+  hipLaunchKernelGGL(k_sem_pack_fragT, dim3((unsigned)min((n + 255) / 256, 4096LL)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)slots[4], L.S, L.S, L.nt, L.nt, (float*)packed_train);
+  LAUNCH_CHECK("k_sem_pack_fragT");
+  return EDTTS_OK;
+}
+
+int edtts_sem_vq_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_tape_bytes", L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY_G(sem_shape(B, T));
+  edtts_sem::SemVqTape tt;
+  edtts_sem::sem_vq_tape(L, (size_t)B * T, tt);
+  *out_bytes = tt.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_sem_vq_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_scratch_bytes", L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY_G(sem_shape(B, T));
+  edtts_sem::SemVqScratch ss;
+  edtts_sem::sem_vq_scratch(L, B, T, ss);
+  *out_bytes = ss.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_sem_vq_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                              float* z_q, int32_t* counts, float* loss, void* tape, int training, double commit, const EdttsDropout* drop,
+                              void* stream) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_encode_train", L));
+  TRY_G(sem_vq_commit(commit, "edtts_sem_vq_encode_train"));
+  DropArgs dr{};
+  bool dropping;
+  TRY_G(sem_drop(L, drop, "edtts_sem_vq_encode_train", &dr, &dropping));
+  TRY_G(sem_shape(B, T));
+  const int N = B * T;
+  if (!packed || !loss || (N > 0 && (!h || !idx || !z_q || !tape))) return fail(EDTTS_ERR_ARG, "NULL pointer argument");  // (no frames: nothing to point at)
+  hipStream_t st = (hipStream_t)stream;
+  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)L.n_codes * sizeof(int32_t), st));
+  if (N == 0) {
+    HIP_TRY(hipMemsetAsync(loss, 0, sizeof(float), st));
+    return EDTTS_OK;
+  }
+  SemVqTape tt;
+  sem_vq_tape(L, (size_t)N, tt);
+  float* tp = (float*)tape;
+  EncTrainArgs a{};
+  a.p = (const float*)packed;
+  a.h = h;
+  a.len = (const long long*)lengths;
+  a.idx = (long long*)idx;
+  a.z = L.in_dim ? tp + tt.z : nullptr;
+  a.zq = z_q;
+  a.counts = counts;
+  a.N = N; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.kb1 = L.kb1; a.vq = 1; a.D = 0; a.K = L.K;
+  a.nrt_codes = L.nrt_codes;
+  a.n_codes = L.n_codes;
+  a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
+  a.cb = L.cb; a.cc = L.cc; a.cbraw = L.cbraw;
+  a.t_y1 = tp + tt.y1;
+  a.t_zb = nullptr;
+  a.t_r = tp + tt.r;
+  a.t_sq = tp + tt.sq;
+  a.dr = dr;
+  a.dropping = dropping;
+  hipLaunchKernelGGL(k_sem_encode<true>, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  LAUNCH_CHECK("k_sem_encode<train, vq>");
+  hipLaunchKernelGGL(k_sem_vq_loss, dim3(1), dim3(256), 0, st, tp + tt.sq, N, (const long long*)lengths, B, T, L.S, (float)commit, training,
+                     loss);
+  LAUNCH_CHECK("k_sem_vq_loss");
+  return EDTTS_OK;
+}
+
+int edtts_sem_vq_ema_update(const EdttsSemDims* dims, const int64_t* idx, const float* z, int B, int T, const int64_t* lengths,
+                            const int32_t* counts, double decay, double epsilon, float* ema_cluster_size, float* ema_w, float* codebook,
+                            void* scratch, void* stream) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_ema_update", L));
+  if (!(decay > 0.0) || !(decay <= 1.0)) return fail(EDTTS_ERR_ARG, "edtts_sem_vq_ema_update: decay=%g outside (0, 1]", decay);
+  if (!(epsilon >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_sem_vq_ema_update: epsilon=%g < 0", epsilon);
+  TRY_G(sem_shape(B, T));
+  if (!counts || !ema_cluster_size || !ema_w || !codebook || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  const int M = B * T;
+  if (M > 0 && (!idx || !z)) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  hipStream_t st = (hipStream_t)stream;
+  SemVqScratch ss;
+  sem_vq_scratch(L, B, T, ss);
+  float* sc = (float*)scratch;
+  if (M == 0) HIP_TRY(hipMemsetAsync(sc + ss.csum, 0, (size_t)L.K * L.S * sizeof(float), st));
+  else TRY_G(vq_codesum(st, L, (const long long*)idx, z, (const long long*)lengths, M, T, sc + ss.csum, sc + ss.part));
+  hipLaunchKernelGGL(k_sem_vq_ema, dim3((L.K + 3) / 4), dim3(256), 0, st, counts, sc + ss.csum, L.K, L.S, (float)decay, (float)(1.0 - decay),
+                     (float)epsilon, ema_cluster_size, ema_w, codebook);
+  LAUNCH_CHECK("k_sem_vq_ema");
+  return EDTTS_OK;
+}
+
+int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h,
+                          const int64_t* idx, int B, int T, const int64_t* lengths, const float* d_zq, const float* d_loss, double commit,
+                          void* const* grad_slots, int n_slots, float* d_z, void* scratch, const EdttsDropout* drop, void* stream) {
+  using namespace edtts_sem;
+  using TL = TrainLauncher;
+  SemLayout L;
+  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_backward", L));
+  TRY_G(sem_vq_commit(commit, "edtts_sem_vq_backward"));
+  DropArgs dr{};
+  bool dropping;
+  TRY_G(sem_drop(L, drop, "edtts_sem_vq_backward", &dr, &dropping));
+  TRY_G(sem_shape(B, T));
+  const int want = (L.in_dim ? 6 : 0) + 1;
+  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", want, n_slots);
+  if (L.in_dim && d_z) return fail(EDTTS_ERR_ARG, "edtts_sem_vq_backward: d_z is the input gradient of a head without proj (in_dim 0)");
+  const int S = L.S, M = B * T, q = L.in_dim ? 6 : 0;
+  if (!grad_slots || (M > 0 && (!tape || !h || !idx || !scratch || (L.in_dim && (!packed || !packed_train)))))
+    return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  hipStream_t st = (hipStream_t)stream;
+  float* const* gs = reinterpret_cast<float* const*>(grad_slots);
+  if (M == 0) {  // empty sums
+    const size_t n[7] = {(size_t)S * L.in_dim, (size_t)S, (size_t)S, (size_t)S, (size_t)S * S, (size_t)S, (size_t)L.K * S};
+    for (int i = 0; i < want; ++i)
+      if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n[i + (L.in_dim ? 0 : 6)] * sizeof(float), st));
+    return EDTTS_OK;
+  }
+  SemVqTape tt;
+  sem_vq_tape(L, (size_t)M, tt);
+  SemVqScratch ss;
+  sem_vq_scratch(L, B, T, ss);
+  const float* tp = (const float*)tape;
+  float* sc = (float*)scratch;
+  hipLaunchKernelGGL(k_sem_vq_coef, dim3(1), dim3(256), 0, st, d_loss, (const long long*)lengths, B, T, S, (float)commit, sc + ss.coef);
+  LAUNCH_CHECK("k_sem_vq_coef");
+  if (L.in_dim || d_z) {
+    SemBwdArgs a{};
+    a.p = (const float*)packed;
+    a.pt = (const float*)packed_train;
+    a.g = d_zq;
+    a.len = (const long long*)lengths;
+    a.t_y1 = tp + tt.y1;
+    a.t_r = tp + tt.r;
+    a.coef = sc + ss.coef;
+    a.dz = L.in_dim ? sc + ss.dz : d_z;
+    a.a = sc + ss.a; a.dam = sc + ss.dam; a.xh = sc + ss.xh; a.dy1 = sc + ss.dy1; a.stat = sc + ss.stat;
+    a.N = M; a.T = T; a.in_dim = L.in_dim; a.S = S; a.nt = L.nt;
+    a.lng = L.lng; a.lnb = L.lnb;
+    a.w3T = 0;
+    a.dr = dr;
+    a.dropping = dropping;
+    hipLaunchKernelGGL(k_sem_bwd_frames<true>, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+    LAUNCH_CHECK("k_sem_bwd_frames<vq>");
+    float* part = sc + ss.part;
+    if (L.in_dim) {  // the sums over frames, in state-dict slot order (as edtts_sem_backward)
+      TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));
+      TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
+      if (gs[2] || gs[3]) {
+        using namespace edtts_gen;
+        const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
+        edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
+        hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
+        LAUNCH_CHECK("k_bwd_norm_cols");
+        if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
+        if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
+      }
+      TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));
+      TRY_G(TL::colsum(st, a.dz, S, M, S, gs[5], part));
+    }
+  }
+  if (gs[q]) {  // d codebook = coef[1] sum_{m: idx[m] = k} r_m: the decoder's gradient never reaches the codebook
+    const size_t n = (size_t)L.K * S;
+    if (!d_loss) {
+      HIP_TRY(hipMemsetAsync(gs[q], 0, n * sizeof(float), st));
+    } else {
+      TRY_G(vq_codesum(st, L, (const long long*)idx, tp + tt.r, (const long long*)lengths, M, T, sc + ss.csum, sc + ss.part));
+      hipLaunchKernelGGL(k_sem_vq_dcb, dim3(GenericLauncher::grid_1d(n)), dim3(256), 0, st, sc + ss.csum, sc + ss.coef, n, gs[q]);
+      LAUNCH_CHECK("k_sem_vq_dcb");
+    }
+  }
   return EDTTS_OK;
 }
 

@@ -14,8 +14,10 @@ By default inference only: ``forward`` has the reference's eval semantics in eit
 codebook update).  ``autograd=True`` (FSQ heads) makes the head trainable as train_v2.train_step trains it: under grad mode
 ``forward`` / ``quantize_features`` / ``forward_features`` run the training forward (edtts_sem_encode_train) and ``backward()`` the
 backward kernels (edtts_sem_backward), with FSQ's straight-through estimator; ``train_dropout=True`` adds proj's ``nn.Dropout`` with
-masks from the library's Philox stream.  Weights are packed for the kernels on first use and re-packed when a
-parameter changes.
+masks from the library's Philox stream.  ``autograd=True, train_vq=True`` does the same for a VQ head as
+train.py trains it: VectorQuantizer's codebook and commitment losses, straight-through estimator, EMA codebook update and dead-code
+reset (edtts_sem_vq_*).  fp32 only: bf16 / autocast training is not built.  Weights are packed for the kernels
+on first use and re-packed when a parameter changes.
 """
 from __future__ import annotations
 
@@ -32,22 +34,35 @@ from . import native
 class _PackCache:
     """The packed blob of one head: (re-)packed on the current stream when a weight tensor or the dims changed."""
 
-    def __init__(self, train: bool = False):
+    def __init__(self, train: bool = False, vq: bool = False):
         self._lock = threading.Lock()
         self._sig = None
         self._blob = None
         self._train = train  # the training-only blob (transposed matrices for the backward) instead of the inference blob
+        self._vq = vq        # ... of a VQ head (edtts_sem_vq_train_pack)
+        self._stale = False
 
     @property
     def sig(self):
         return self._sig
 
+    @staticmethod
+    def sig_of(dims: native.EdttsSemDims, tensors: Sequence[torch.Tensor]):
+        dkey = (dims.in_dim, dims.semantic_dim, dims.quantizer, dims.codebook_size, dims.n_levels, tuple(dims.levels))
+        return (dkey,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+
+    def invalidate(self) -> None:
+        """The next get() packs again although no tensor's version moved (the EMA kernel writes into the codebook's storage)."""
+        with self._lock:
+            self._stale = True
+
     def get(self, dims: native.EdttsSemDims, tensors: Sequence[torch.Tensor]) -> torch.Tensor:
         nbytes_of, pack = (native.sem_train_packed_bytes, native.sem_train_pack) if self._train else (native.sem_packed_bytes, native.sem_pack)
+        if self._train and self._vq:
+            nbytes_of, pack = native.sem_vq_train_packed_bytes, native.sem_vq_train_pack
         with self._lock:
-            dkey = (dims.in_dim, dims.semantic_dim, dims.quantizer, dims.codebook_size, dims.n_levels, tuple(dims.levels))
-            sig = (dkey,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
-            if self._blob is None or sig != self._sig:
+            sig = self.sig_of(dims, tensors)
+            if self._blob is None or sig != self._sig or self._stale:
                 dev = tensors[0].device
                 for i, t in enumerate(tensors):
                     if t.device != dev or t.dtype != torch.float32:
@@ -57,6 +72,7 @@ class _PackCache:
                     self._blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 pack(dims, [t.detach().contiguous() for t in tensors], self._blob)
                 self._sig = sig
+                self._stale = False
             return self._blob
 
 
@@ -106,6 +122,61 @@ class _SemGrad(torch.autograd.Function):
         d_z = torch.empty_like(ctx.x) if dims.in_dim == 0 and ctx.needs_input_grad[4] else None
         native.sem_backward(dims, blob, tblob, tape, ctx.x, ctx.lengths, native._aligned(d_zq.float()), grads, d_z, ctx.drop)
         return (None, None, None, None, d_z, *grads)
+
+
+class _VQGrad(torch.autograd.Function):
+    """(z_q, vq_loss, idx, counts) of a VQ head on the training forward (edtts_sem_vq_encode_train), then -- module in training mode,
+    decay > 0 -- VectorQuantizer's EMA update and dead-code reset; backward through edtts_sem_vq_backward.  The reference's order
+    (models/vq.py:86-93): the loss and both gradients refer to the codebook the forward was given, which the EMA update has
+    overwritten by the time the backward runs, so the tape carries r = c - z and the backward reads nothing of the codebook.
+    ``owner``: the module whose ``_slots()`` / ``_pack`` / ``_tpack`` describe the head; ``vq``: its VectorQuantizer."""
+
+    @staticmethod
+    def forward(ctx, owner, vq, dims, lengths, drop, h, *params):
+        slots = owner._slots()
+        blob = owner._pack.get(dims, slots)
+        tblob = owner._tpack.get(dims, slots)
+        x = native._aligned(h.detach().float())
+        B, T = x.shape[0], x.shape[1]
+        if lengths is not None and B * T:  # the weight-gradient products multiply the rows past the lengths by zeros: make them finite
+            x = x.masked_fill((torch.arange(T, device=x.device)[None, :] >= lengths.clamp(1, T)[:, None])[..., None], 0.0)
+        training = bool(vq.training)
+        commit = float(vq.commit)
+        tape = torch.empty(native.sem_vq_tape_bytes(dims, B, T), dtype=torch.uint8, device=x.device)
+        idx, zq, counts, loss = native.sem_vq_encode_train(dims, blob, x, tape, lengths, training, commit, drop)
+        # the versions as the forward saw them: the EMA's own write (no version moves, the caches are only marked stale) must not
+        # look like a modified parameter to the backward
+        ctx.owner, ctx.dims, ctx.lengths, ctx.drop, ctx.sig = owner, dims, lengths, drop, _PackCache.sig_of(dims, slots)
+        ctx.blob, ctx.tblob, ctx.commit, ctx.training = blob, tblob, commit, training
+        ctx.x = x
+        if training and vq.decay > 0:
+            S = dims.semantic_dim
+            # z: the tape's second region with a proj (y1 | z | r | sq, include/edtts.h), the input itself without one
+            z = tape.view(torch.float32)[B * T * S: 2 * B * T * S].view(B, T, S) if dims.in_dim else x
+            vq._ema_update(dims, idx, z, lengths, counts)
+            owner._pack.invalidate()
+            vq._pack.invalidate()
+        ctx.save_for_backward(tape, idx, *params)
+        ctx.mark_non_differentiable(idx, counts)
+        ctx.set_materialize_grads(False)
+        return zq, loss, idx, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_zq, d_loss, _d_idx, _d_counts):
+        owner, dims = ctx.owner, ctx.dims
+        tape, idx, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
+        if _PackCache.sig_of(dims, owner._slots()) != ctx.sig:
+            raise RuntimeError(f"{type(owner).__name__}: a parameter was modified between this forward and its backward")
+        grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[6:])]
+        d_z = torch.empty_like(ctx.x) if dims.in_dim == 0 and ctx.needs_input_grad[5] else None
+        if d_zq is not None:
+            d_zq = native._aligned(d_zq.float())
+        if d_loss is not None:
+            d_loss = d_loss.float().reshape(()).contiguous() if ctx.training else None  # (eval: vq_loss is the constant 0)
+        # (the proj regions of the forward's blobs are what the backward reads: the checked versions are the ones they were packed from)
+        native.sem_vq_backward(dims, ctx.blob, ctx.tblob, tape, ctx.x, idx, ctx.lengths, d_zq, d_loss, ctx.commit, grads, d_z, ctx.drop)
+        return (None, None, None, None, None, d_z, *grads)
 
 
 class FSQ(nn.Module):
@@ -241,20 +312,31 @@ class FSQEncoder(nn.Module):
 
 class VectorQuantizer(nn.Module):
     """Nearest-code quantizer (reference models/vq.py:VectorQuantizer); keys ``codebook.weight``, ``ema_cluster_size``, ``ema_w``,
-    ``update_count``.  Inference only: the loss is 0 and the EMA codebook update is not run."""
+    ``update_count``.  By default inference only: the loss is 0 and the EMA codebook update is not run."""
 
     def __init__(self, dim: int, codebook_size: int, commit: float = 0.25, decay: float = 0.99, epsilon: float = 1e-5,
-                 reset_unused_every: int = 100):
+                 reset_unused_every: int = 100, autograd: bool = False):
+        """``autograd``: False (default) -- inference only, as before.  True -- under grad mode ``forward`` is the reference's
+        training forward: z_q carries the straight-through gradient to ``z``; in training mode vq_loss =
+        codebook loss + commit x commitment loss carries the graph to ``z`` and ``codebook.weight``, and (decay > 0) the EMA update
+        of ``ema_cluster_size`` / ``ema_w`` / ``codebook.weight`` and the dead-code reset run; in eval mode vq_loss is 0 and no
+        buffer changes.  The reset's permutation is drawn on the host, ``torch.randperm(N, generator=self.reset_generator)`` (a CPU
+        ``torch.Generator``; None: torch's default one), only on a reset step with a dead code."""
         super().__init__()
         self.dim = dim
         self.codebook_size = codebook_size
         self.commit, self.decay, self.epsilon, self.reset_unused_every = commit, decay, epsilon, reset_unused_every
+        self.autograd = bool(autograd)
         self.codebook = nn.Embedding(codebook_size, dim)
         nn.init.normal_(self.codebook.weight, mean=0.0, std=1.0)
         self.register_buffer("ema_cluster_size", torch.ones(codebook_size))
         self.register_buffer("ema_w", self.codebook.weight.detach().clone())
         self.register_buffer("update_count", torch.tensor(0))
         self._pack = _PackCache()
+        self._tpack = _PackCache(train=True, vq=True)
+        self.reset_generator: Optional[torch.Generator] = None
+        self._count_host: Optional[int] = None  # host mirror of update_count: a step that does not reset never synchronises
+        self._count_sig = None
 
     @property
     def num_codes(self) -> int:
@@ -274,12 +356,81 @@ class VectorQuantizer(nn.Module):
                                                want_counts=want_counts)
         return (None if zq is None else zq.reshape(*shape, -1)), idx.reshape(shape), counts
 
+    # ------------------------------------------------------------------------------------------ training
+    def _bump_count(self) -> int:
+        """update_count += 1 on the device and in the host mirror (re-read when the buffer was loaded or moved); returns it."""
+        u = self.update_count
+        sig = (u.data_ptr(), u._version, u.device)
+        if self._count_host is None or sig != self._count_sig:
+            self._count_host = int(u)
+        u += 1
+        self._count_host += 1
+        self._count_sig = (u.data_ptr(), u._version, u.device)
+        return self._count_host
+
     @torch.no_grad()
-    def forward(self, z: torch.Tensor):
-        """(z_q, idx, vq_loss = 0, perplexity, used), as VectorQuantizer.forward returns them in eval mode."""
-        zq, idx, counts = self._quantize(z, True, True)
-        ppl, used = _stats(counts)
-        return zq, idx, torch.zeros((), device=z.device), ppl, used
+    def _ema_update(self, dims, idx: torch.Tensor, z: torch.Tensor, lengths, counts: torch.Tensor) -> None:
+        """VectorQuantizer._ema_update (models/vq.py:109-145) after a training forward: idx [B, T], z [B, T, dim] fp32, counts the
+        usage of this batch.  The EMA lines run in one kernel chain on the buffers' and the codebook's storage (no version moves: the
+        caller marks the pack caches stale); the reset is torch plumbing on the reset steps only."""
+        w = self.codebook.weight
+        for t, name in ((self.ema_cluster_size, "ema_cluster_size"), (self.ema_w, "ema_w"), (w, "codebook.weight")):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != idx.device:
+                raise native.EdttsError(f"VectorQuantizer: {name} must be a contiguous fp32 tensor on {idx.device}")
+        native.sem_vq_ema_update(dims, idx, z, lengths, counts, self.decay, self.epsilon, self.ema_cluster_size, self.ema_w, w.data)
+        count = self._bump_count()
+        if not (self.reset_unused_every > 0 and count % self.reset_unused_every == 0):
+            return
+        dead = self.ema_cluster_size < 1.0
+        num_dead = int(dead.sum())  # (a host synchronisation on the reset steps, as the reference's .item())
+        B, T = idx.shape
+        if lengths is None:
+            rows_of = None
+            n_valid = B * T
+        else:
+            valid = torch.arange(T, device=idx.device)[None, :] < lengths.clamp(1, max(T, 1))[:, None]
+            rows_of = valid.reshape(-1).nonzero(as_tuple=True)[0]
+            n_valid = int(rows_of.numel())
+        if num_dead == 0 or n_valid == 0:
+            return
+        num_replace = min(num_dead, n_valid)
+        pick = torch.randperm(n_valid, generator=self.reset_generator)[:num_replace].to(idx.device)
+        rows = pick if rows_of is None else rows_of[pick]
+        new = z.reshape(-1, self.dim).index_select(0, rows)
+        dead_idx = dead.nonzero(as_tuple=True)[0][:num_replace]
+        w.data.index_copy_(0, dead_idx, new)
+        self.ema_w.index_copy_(0, dead_idx, new)
+        self.ema_cluster_size.index_fill_(0, dead_idx, 1.0)
+
+    def forward(self, z: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """(z_q, idx, vq_loss, perplexity, used), as VectorQuantizer.forward returns them.  Without ``autograd`` or outside grad
+        mode: eval semantics (vq_loss = 0).  ``lengths`` (int64 [B], z [B, T, dim]): frames t >= lengths[b] are not read."""
+        if self.autograd and torch.is_grad_enabled():
+            shape = z.shape[:-1]
+            dims = self._dims()
+            if lengths is not None:
+                if z.dim() != 3:
+                    raise ValueError(f"VectorQuantizer: lengths need z [B, T, {self.dim}], got {list(z.shape)}")
+                if z.shape[-1] != self.dim:
+                    raise ValueError(f"VectorQuantizer input: expected last dimension {self.dim}, got {list(z.shape)}")
+                zz = z.float()
+                lengths = native.lengths(lengths, z.shape[0], max(z.shape[1], 1), z.device, "lengths")
+            else:
+                zz = _flat3(z, self.dim, "VectorQuantizer input")
+            zq, loss, idx, counts = _VQGrad.apply(self, self, dims, lengths, None, zz, *self._slots())
+            zq, idx = zq.reshape(*shape, -1), idx.reshape(shape)
+        else:
+            with torch.no_grad():
+                if lengths is not None:
+                    dims = self._dims()
+                    n = native.lengths(lengths, z.shape[0], max(z.shape[1], 1), z.device, "lengths")
+                    idx, _, zq, counts = native.sem_encode(dims, self._pack.get(dims, self._slots()), z.float(), n)
+                else:
+                    zq, idx, counts = self._quantize(z, True, True)
+            loss = torch.zeros((), device=z.device)
+        with torch.no_grad():
+            ppl, used = _stats(counts)
+        return zq, idx, loss, ppl, used
 
     @torch.no_grad()
     def encode(self, z: torch.Tensor) -> torch.Tensor:
@@ -329,11 +480,16 @@ class SemanticEncoder(nn.Module):
     ``HubertModel.from_pretrained(cfg.hubert_id, local_files_only=True)`` and raises a RuntimeError if it is not cached."""
 
     def __init__(self, cfg, hubert: Optional[nn.Module] = None, *, in_dim: int = 768, proj_dropout: bool = False,
-                 autograd: bool = False, train_dropout: bool = False):
-        """``autograd``: False (default) -- inference only, as before.  True (FSQ only; a VQ quantizer raises a ValueError: its
-        codebook and commitment losses, EMA update and dead-code reset are not built) -- ``forward``, ``quantize_features`` and
+                 autograd: bool = False, train_dropout: bool = False, train_vq: bool = False):
+        """``autograd``: False (default) -- inference only, as before.  True -- ``forward``, ``quantize_features`` and
         ``forward_features`` under grad mode return a z_q that carries the graph to proj and the quantizer's projections.  No
-        gradient goes into HuBERT (the reference detaches its features).
+        gradient goes into HuBERT (the reference detaches its features).  On a VQ config ``autograd=True`` alone raises a
+        ValueError: the VQ path is asked for by name with ``train_vq=True``.
+        ``train_vq``: False (default).  True (needs ``autograd=True`` and a VQ config, ``cfg.use_fsq`` false) -- the head trains as
+        train.py trains it: in training mode ``forward`` / ``forward_features`` return VectorQuantizer's vq_loss (codebook loss +
+        ``cfg.vq_commit`` x commitment loss) with the graph to proj and ``vq.codebook.weight``, and every such call runs the EMA
+        codebook update and, every ``vq.reset_unused_every`` updates, the dead-code reset (its permutation from
+        ``self.vq.reset_generator``); in eval mode vq_loss is 0 and no buffer changes.  fp32 only.
         ``train_dropout``: False (default) -- a differentiable call in training mode with the Dropout layout and ``p > 0`` raises.
         True (needs ``autograd=True`` and the Dropout layout) -- that call applies ``proj[3]`` with the library's Philox masks: each
         draws a 63-bit seed on the host from ``self.dropout_generator`` (a CPU ``torch.Generator``; None: torch's default one),
@@ -341,9 +497,15 @@ class SemanticEncoder(nn.Module):
         super().__init__()
         self.autograd = bool(autograd)
         self.train_dropout = bool(train_dropout)
-        if self.autograd and not getattr(cfg, "use_fsq", False):
-            raise ValueError("autograd=True covers the FSQ quantizer only (cfg.use_fsq): the VQ path -- VectorQuantizer in training mode "
-                             "with its codebook loss, commitment loss, EMA update and dead-code reset -- is not built")
+        self.train_vq = bool(train_vq)
+        is_fsq = bool(getattr(cfg, "use_fsq", False))
+        if self.train_vq and not self.autograd:
+            raise ValueError("train_vq=True needs autograd=True (the VQ losses, EMA update and dead-code reset belong to the training forward)")
+        if self.train_vq and is_fsq:
+            raise ValueError("train_vq=True needs a VQ config (cfg.use_fsq is set: an FSQ head trains with autograd=True alone)")
+        if self.autograd and not is_fsq and not self.train_vq:
+            raise ValueError("autograd=True alone covers the FSQ quantizer (cfg.use_fsq): the VQ path -- VectorQuantizer in training mode "
+                             "with its codebook loss, commitment loss, EMA update and dead-code reset -- is switched on with train_vq=True")
         if self.train_dropout and not self.autograd:
             raise ValueError("train_dropout=True needs autograd=True (dropout belongs to the training forward and its backward)")
         if self.train_dropout and not proj_dropout:
@@ -364,9 +526,9 @@ class SemanticEncoder(nn.Module):
         if getattr(cfg, "use_fsq", False):
             self.vq = FSQEncoder(cfg.semantic_dim, cfg.fsq_levels, autograd=self.autograd)
         else:
-            self.vq = VectorQuantizer(cfg.semantic_dim, cfg.codebook_size, commit=getattr(cfg, "vq_commit", 0.25))
+            self.vq = VectorQuantizer(cfg.semantic_dim, cfg.codebook_size, commit=getattr(cfg, "vq_commit", 0.25), autograd=self.train_vq)
         self._pack = _PackCache()
-        self._tpack = _PackCache(train=True)
+        self._tpack = _PackCache(train=True, vq=not is_fsq)
 
     @property
     def codebook_size(self) -> int:
@@ -510,7 +672,7 @@ class SemanticEncoder(nn.Module):
         return native.sem_encode(dims, blob, h.float(), n, want_z=want_z, want_zq=want_zq, want_counts=want_counts)
 
     def _head_autograd(self, h: torch.Tensor, lengths):
-        """(z_q with the graph, idx, counts) of a differentiable call."""
+        """(z_q with the graph, idx, counts, vq_loss -- None for FSQ) of a differentiable call."""
         if h.dim() != 3:
             raise ValueError(f"features: expected [B, T_feat, {self.proj[0].in_features}], got {list(h.shape)}")
         drop = None
@@ -525,28 +687,37 @@ class SemanticEncoder(nn.Module):
             drop = (float(layer.p), seed)
             self.last_dropout_seed = seed
         n = native.lengths(lengths, h.shape[0], max(h.shape[1], 1), h.device, "lengths")
-        return _SemGrad.apply(self, self._dims(), n, drop, h.detach(), *self._slots())
+        if self.train_vq:
+            zq, loss, idx, counts = _VQGrad.apply(self, self.vq, self._dims(), n, drop, h.detach(), *self._slots())
+            return zq, idx, counts, loss
+        return (*_SemGrad.apply(self, self._dims(), n, drop, h.detach(), *self._slots()), None)
 
     def _differentiable(self) -> bool:
         return self.autograd and torch.is_grad_enabled()
 
-    def quantize_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        """Precomputed HuBERT features h [B, T_feat, 768] -> (z_q [B, T_feat, semantic_dim], idx [B, T_feat], perplexity, used).
-        ``lengths`` (int64 [B]): frames t >= lengths[b] are not read, get idx 0 and z_q 0, and are not counted.  With
-        ``autograd=True`` and under grad mode z_q carries the graph (the features themselves get no gradient)."""
+    def _quantize_loss(self, h: torch.Tensor, lengths):
+        loss = None
         if self._differentiable():
-            zq, idx, counts = self._head_autograd(h, lengths)
+            zq, idx, counts, loss = self._head_autograd(h, lengths)
         else:
             with torch.no_grad():
                 idx, _, zq, counts = self._head(h, lengths, True, True)
         with torch.no_grad():
             ppl, used = _stats(counts)
+        return zq, idx, (torch.zeros((), device=zq.device) if loss is None else loss), ppl, used
+
+    def quantize_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """Precomputed HuBERT features h [B, T_feat, 768] -> (z_q [B, T_feat, semantic_dim], idx [B, T_feat], perplexity, used).
+        ``lengths`` (int64 [B]): frames t >= lengths[b] are not read, get idx 0 and z_q 0, and are not counted.  With
+        ``autograd=True`` and under grad mode z_q carries the graph (the features themselves get no gradient); with ``train_vq=True``
+        the call is a training forward like ``forward_features`` (EMA update included), only its vq_loss is not returned."""
+        zq, idx, _, ppl, used = self._quantize_loss(h, lengths)
         return zq, idx, ppl, used
 
     def forward_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        """``forward`` from precomputed HuBERT features: (z_q, idx, vq_loss = 0, perplexity, used)."""
-        zq, idx, ppl, used = self.quantize_features(h, lengths)
-        return zq, idx, torch.zeros((), device=zq.device), ppl, used
+        """``forward`` from precomputed HuBERT features: (z_q, idx, vq_loss, perplexity, used); vq_loss is 0 except for a
+        ``train_vq=True`` head in training mode under grad."""
+        return self._quantize_loss(h, lengths)
 
     @torch.no_grad()
     def encode_features(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -554,7 +725,8 @@ class SemanticEncoder(nn.Module):
         return self._head(h, lengths, False, False)[0]
 
     def forward(self, wav_16k: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        """(z_q, idx, vq_loss = 0, perplexity, used) of a 16 kHz waveform [B, T_audio], as the reference returns them.  ``lengths``
+        """(z_q, idx, vq_loss, perplexity, used) of a 16 kHz waveform [B, T_audio], as the reference returns them (vq_loss: see
+        ``forward_features``).  ``lengths``
         (sample counts, NativeHubert backbone only): the head then takes each utterance's own frame count.  HuBERT runs without
         grad in every mode; see ``quantize_features`` for ``autograd=True``."""
         with torch.no_grad():

@@ -33,6 +33,8 @@ EXPORTED_SYMBOLS = (
     "edtts_decoder_forward_train_drop", "edtts_decoder_backward_drop", "edtts_dropout_mask",
     "edtts_sem_train_packed_bytes", "edtts_sem_train_pack", "edtts_sem_train_tape_bytes", "edtts_sem_train_scratch_bytes",
     "edtts_sem_encode_train", "edtts_sem_backward", "edtts_sem_dropout_mask",
+    "edtts_sem_vq_train_packed_bytes", "edtts_sem_vq_train_pack", "edtts_sem_vq_tape_bytes", "edtts_sem_vq_scratch_bytes",
+    "edtts_sem_vq_encode_train", "edtts_sem_vq_ema_update", "edtts_sem_vq_backward",
     "edtts_decoder_forward_train_len", "edtts_decoder_backward_len",
 )
 
@@ -191,6 +193,13 @@ def lib() -> C.CDLL:
     L.edtts_sem_encode_train.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, dpp, vp]
     L.edtts_sem_backward.argtypes = [sdp, vp, vp, vp, vp, i32, i32, vp, vp, C.POINTER(vp), i32, vp, vp, dpp, vp]
     L.edtts_sem_dropout_mask.argtypes = [sdp, i32, i32, dpp, vp, vp]
+    L.edtts_sem_vq_train_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
+    L.edtts_sem_vq_train_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
+    L.edtts_sem_vq_tape_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
+    L.edtts_sem_vq_scratch_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
+    L.edtts_sem_vq_encode_train.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, C.c_double, dpp, vp]
+    L.edtts_sem_vq_ema_update.argtypes = [sdp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    L.edtts_sem_vq_backward.argtypes = [sdp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, C.c_double, C.POINTER(vp), i32, vp, vp, dpp, vp]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -772,6 +781,79 @@ def sem_dropout_mask(dims: EdttsSemDims, B: int, T: int, p: float, seed: int, de
     keep = torch.empty((B * T, dims.semantic_dim), dtype=torch.uint8, device=dev)
     lib().edtts_sem_dropout_mask(C.byref(dims), B, T, C.byref(drop), keep.data_ptr(), _stream(dev))
     return keep
+
+
+# ---------------------------------------------------------------------------------------------- VQ head, training
+def sem_vq_train_packed_bytes(dims: EdttsSemDims) -> int:
+    return _size_query(lib().edtts_sem_vq_train_packed_bytes, C.byref(dims))
+
+
+def sem_vq_train_pack(dims: EdttsSemDims, tensors: Sequence[torch.Tensor], packed_train: torch.Tensor) -> None:
+    """The VQ head's training-only blob (the final Linear's transpose; nothing when dims.in_dim is 0); slots as sem_pack."""
+    ptrs = _slot_ptrs(tensors, "weight")
+    lib().edtts_sem_vq_train_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed_train, torch.uint8, "packed_train"),
+                                  _stream(packed_train.device))
+
+
+def sem_vq_tape_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
+    return _size_query(lib().edtts_sem_vq_tape_bytes, C.byref(dims), B, T)
+
+
+def sem_vq_scratch_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
+    return _size_query(lib().edtts_sem_vq_scratch_bytes, C.byref(dims), B, T)
+
+
+def sem_vq_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, tape: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                        training: bool = True, commit: float = 0.25, drop=None):
+    """edtts_sem_vq_encode_train: h [B, T, in_dim] (z [B, T, semantic_dim] when dims.in_dim is 0; contiguous, 16-byte aligned) ->
+    (idx, z_q, counts, vq_loss 0-dim) with the backward's tape written to `tape` (uint8, sem_vq_tape_bytes).  ``drop``: None, an
+    EdttsDropout or a (p, seed) pair."""
+    B, T, D = h.shape
+    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
+    if D != want_d:
+        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+    dev = h.device
+    idx = torch.empty((B, T), dtype=torch.int64, device=dev)
+    zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
+    counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    drop = _dropout(drop)
+    lib().edtts_sem_vq_encode_train(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
+                                    _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), zq.data_ptr(), counts.data_ptr(),
+                                    loss.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), int(bool(training)), float(commit),
+                                    None if drop is None else C.byref(drop), _stream(dev))
+    return idx, zq, counts, loss
+
+
+def sem_vq_ema_update(dims: EdttsSemDims, idx: torch.Tensor, z: torch.Tensor, lengths: Optional[torch.Tensor], counts: torch.Tensor,
+                      decay: float, epsilon: float, ema_cluster_size: torch.Tensor, ema_w: torch.Tensor, codebook: torch.Tensor) -> None:
+    """edtts_sem_vq_ema_update: the three EMA lines of VectorQuantizer._ema_update, in place on the two buffers and the codebook's
+    storage.  idx [B, T], z [B, T, semantic_dim]."""
+    B, T = idx.shape
+    scratch = torch.empty(sem_vq_scratch_bytes(dims, B, T), dtype=torch.uint8, device=idx.device)
+    f = torch.float32
+    lib().edtts_sem_vq_ema_update(C.byref(dims), _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(z, f, "z"), B, T,
+                                  _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(counts, torch.int32, "counts"), float(decay),
+                                  float(epsilon), _dev_ptr(ema_cluster_size, f, "ema_cluster_size"), _dev_ptr(ema_w, f, "ema_w"),
+                                  _dev_ptr(codebook, f, "codebook"), scratch.data_ptr(), _stream(idx.device))
+
+
+def sem_vq_backward(dims: EdttsSemDims, packed: Optional[torch.Tensor], packed_train: Optional[torch.Tensor], tape: torch.Tensor,
+                    h: torch.Tensor, idx: torch.Tensor, lengths: Optional[torch.Tensor], d_zq: Optional[torch.Tensor],
+                    d_loss: Optional[torch.Tensor], commit: float, grads: Sequence[Optional[torch.Tensor]],
+                    d_z: Optional[torch.Tensor] = None, drop=None) -> None:
+    """edtts_sem_vq_backward: writes the gradient of every non-None entry of `grads` (slot order) and d_z (dims.in_dim == 0).
+    d_zq / d_loss None: zero.  ``drop``: what the forward that filled `tape` was given."""
+    B, T, _ = h.shape
+    ptrs = _slot_ptrs(grads, "grad")
+    scratch = torch.empty(sem_vq_scratch_bytes(dims, B, T), dtype=torch.uint8, device=h.device)
+    drop = _dropout(drop)
+    f = torch.float32
+    lib().edtts_sem_vq_backward(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(packed_train, torch.uint8, "packed_train"),
+                                _dev_ptr(tape, torch.uint8, "tape"), _dev_ptr(h, f, "features"), _dev_ptr(idx, torch.int64, "idx"), B, T,
+                                _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(d_zq, f, "d_zq"), _dev_ptr(d_loss, f, "d_loss"),
+                                float(commit), ptrs, len(grads), _dev_ptr(d_z, f, "d_z"), scratch.data_ptr(),
+                                None if drop is None else C.byref(drop), _stream(h.device))
 
 
 # ---------------------------------------------------------------------------------------------- HuBERT backbone

@@ -566,8 +566,8 @@ int edtts_sem_decode(const EdttsSemDims* dims, const void* packed, const int64_t
 int edtts_sem_stats(const int32_t* counts, int64_t n_codes, float* perplexity, int64_t* used, void* stream);
 
 /* ---- training the semantic head  (train_v2.py train_step: proj and FSQEncoder are trained with the decoder) ------------------------
- * FSQ only (EDTTS_ERR_UNSUPPORTED for EDTTS_SEM_VQ: the codebook and commitment losses, the EMA update and the dead-code reset are
- * not built), fp32.  The straight-through estimator is FSQ.forward's: zq_low = zb + (q - zb).detach(), so d zb = d zq_low.
+ * These entries train the FSQ head (EDTTS_ERR_UNSUPPORTED for EDTTS_SEM_VQ: a VQ head trains through the edtts_sem_vq_* entries
+ * below), fp32; bf16 / autocast training is not built.  The straight-through estimator is FSQ.forward's: zq_low = zb + (q - zb).detach(), so d zb = d zq_low.
  *
  * edtts_sem_encode_train is edtts_sem_encode (idx, z_q, counts as there) that also writes the backward's tape, M = B * T rows:
  *     in_dim > 0:  y1 = proj.0(h) before GELU [M][S] | z [M][S] | zb = tanh(proj_down(z)) [M][16]    (2 M S + 16 M floats)
@@ -603,6 +603,53 @@ int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void*
                        int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z,
                        void* scratch, const EdttsDropout* drop, void* stream);
 int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream);
+
+/* ---- training the VQ head  (train.py: VectorQuantizer.forward in training mode, models/vq.py:86-93, 109-145) ----------------------
+ * EDTTS_SEM_VQ only (EDTTS_ERR_UNSUPPORTED for EDTTS_SEM_FSQ), fp32.  With flat = the N valid frames of z and C the codebook the
+ * forward was given:  idx = first argmin((|z|^2 - 2 z.c) + |c|^2), c = C[idx], z_q = z + (c - z), r = c - z,
+ *     L = mean(r^2) over the N S valid elements, vq_loss = L + commit L  (codebook loss + commit x commitment loss: equal values),
+ *     d z = G - g commit 2 r / (N S)  (G = d z_q: the straight-through estimator; g = d vq_loss),
+ *     d C[k] = g 2 / (N S) sum_{m: idx[m] = k} r_m  (the gradient of z_q never reaches the codebook).
+ * N = sum of the lengths clamped into [1, T] (B T without lengths), computed on the device.
+ *
+ * edtts_sem_vq_encode_train is edtts_sem_encode (idx, z_q, counts as there; without dropout idx and z_q are bitwise its) that also
+ * writes loss[1] = L + commit L (training == 0: 0; L = the fp64 sum of the per-frame sums in a fixed order / (N S), rounded once) and
+ * the backward's tape, M = B * T rows:
+ *     in_dim > 0:  y1 = proj.0(h) before GELU [M][S] | z [M][S] | r [M][S] | sq [M] = sum_s r^2      (3 M S + M floats)
+ *     in_dim = 0:  r [M][S] | sq [M]                                                               (M S + M floats; z is the input)
+ * The tape holds r and not c because the EMA update overwrites the codebook between the forward and its backward: the backward
+ * reads nothing of the codebook.  Dropout: the site of edtts_sem_encode_train (stream word 0x40000).
+ *
+ * edtts_sem_vq_ema_update (the caller runs it after the forward when the module trains and decay > 0), n[k] = counts[k]:
+ *     ema_cluster_size = ema_cluster_size decay + (1 - decay) n;  ema_w = ema_w decay + (1 - decay) sum_{m: idx[m] = k} z_m;
+ *     codebook = ema_w / max(ema_cluster_size, epsilon)[:, None]            (1 - decay is formed in double and rounded once)
+ * written in place.  z [B,T,S]: the tape's z with a proj, the forward's input without one.  The inference blob is NOT refreshed:
+ * the caller packs again (edtts_sem_pack) before the next encode.  The per-code sums are a one-hot GEMM on MFMA over slabs of
+ * edtts_train_dw_slab_rows(M) rows, slabs added in ascending order: no float atomics, bitwise reproducible.  update_count and the
+ * dead-code reset are the caller's (edge_diffusion_tts_amd/encoder.py).
+ *
+ * edtts_sem_vq_backward: d_zq [B,T,S] (NULL: 0) and d_loss (device scalar; NULL: 0) -> the gradient of every non-NULL entry of
+ * grad_slots (state-dict slot order as edtts_sem_pack: 7 slots with a proj, 1 without) and, with in_dim = 0, d_z [B,T,S] (optional).
+ * h, idx, lengths, commit, drop: what the forward was given / returned.  The training blob (edtts_sem_vq_train_packed_bytes /
+ * edtts_sem_vq_train_pack, slots as edtts_sem_pack) holds the final Linear's transpose in fragment order: 0 bytes with in_dim = 0
+ * (packed and packed_train may then be NULL).  Rows of unused codes in the codebook gradient are exactly 0.  One scratch size
+ * (edtts_sem_vq_scratch_bytes) serves the EMA update and the backward.  Frames at or past lengths[b] contribute nothing to the
+ * loss, the counts, the code sums or any gradient.  M = 0: loss 0 and zero gradients.  Argument errors are reported before any
+ * pointer is looked at. */
+int edtts_sem_vq_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes);
+int edtts_sem_vq_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream);
+int edtts_sem_vq_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes);
+int edtts_sem_vq_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes);
+int edtts_sem_vq_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths,
+                              int64_t* idx, float* z_q, int32_t* counts, float* loss, void* tape, int training, double commit,
+                              const EdttsDropout* drop, void* stream);
+int edtts_sem_vq_ema_update(const EdttsSemDims* dims, const int64_t* idx, const float* z, int B, int T, const int64_t* lengths,
+                            const int32_t* counts, double decay, double epsilon, float* ema_cluster_size, float* ema_w,
+                            float* codebook, void* scratch, void* stream);
+int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h,
+                          const int64_t* idx, int B, int T, const int64_t* lengths, const float* d_zq, const float* d_loss,
+                          double commit, void* const* grad_slots, int n_slots, float* d_z, void* scratch, const EdttsDropout* drop,
+                          void* stream);
 
 /* ---- HuBERT backbone  (transformers HubertModel, feat_extract_norm = "group", do_stable_layer_norm = False: hubert-base) ------------
  * wav [B, T_audio] fp32 -> HubertModel(wav, output_hidden_states=True).hidden_states[num_layers] [B, T_feat, hidden], eval mode, fp32.

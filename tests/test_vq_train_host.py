@@ -1,0 +1,181 @@
+"""Host-side tests of the VQ head's training path: the conditions the GPU tests rely on, the restated oracle
+against the reference's own run, the C ABI surface and the constructor errors.  No GPU."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+import vq_train_util as U
+from edge_diffusion_tts_amd import CFG, native
+from edge_diffusion_tts_amd.encoder import SemanticEncoder, VectorQuantizer
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("edtts_sem_vq_train_packed_bytes", "edtts_sem_vq_train_pack", "edtts_sem_vq_tape_bytes", "edtts_sem_vq_scratch_bytes",
+               "edtts_sem_vq_encode_train", "edtts_sem_vq_ema_update", "edtts_sem_vq_backward")
+# Oracle vs fixture: both are fp32 runs of the same operations on the CPU, so they differ by at most the matrix products' summation
+# order: measured 0 (bitwise equal) where the fixture was made; the bar is 4 x one fp32 rounding of the largest entry (2^-23), the
+# smallest difference a reordered sum can show.
+GOLDEN_TOL = 4 * 2.0 ** -23
+
+
+@pytest.mark.parametrize("name", sorted(U.CASES))
+def test_margin_conditions(name):
+    """In fp64, in every variant the GPU tests use (no dropout over two forwards, each dropout seed, the ragged batch, the three-step
+    run with a reset): the two smallest distances of every valid frame are >= 1e-3 apart, on a reset step every code's
+    |ema_cluster_size - 1| is >= 1e-4, and the fp32 and fp64 oracle agree on every idx.  FEATURE_SEED is the first seed >= 100 with
+    that property."""
+    for seed in range(100, U.FEATURE_SEED[name] + 1):
+        gap, dead, same = U.margins(name, seed)
+        print(f"{name} feature seed {seed}: gap {gap:.2e}, reset margin {dead}, idx equal {same}")
+        ok = gap >= U.MIN_GAP and same and (dead is None or dead >= U.MIN_DEAD)
+        assert ok == (seed == U.FEATURE_SEED[name]), (name, seed, gap, dead, same)
+    if name in U.MULTI:  # the reset is exercised: it happens, replaces some but not all codes
+        r64 = U.run(name, torch.float64, steps=3, reset_unused_every=2, sgd=True)
+        assert [r["reset"] for r in r64] == [False, True, False] and [r["count"] for r in r64] == [1, 2, 3]
+        assert 0 < len(r64[1]["rows"]) < U.CASES[name][2]
+    r64 = U.run(name, torch.float64, steps=2)
+    assert len(torch.unique(r64[0]["idx"])) > 1
+    assert float((r64[0]["cb"] - U.case(name)[7]["codebook.weight"].double()).abs().max()) > 1e-3  # the EMA moves the codebook
+
+
+def test_oracle_reproduces_the_reference_run(golden):
+    """tests/golden/train_vq.npz (the reference's VectorQuantizer in .train() behind models/encoder.py's proj, three forwards /
+    backwards, reset_unused_every = 2): the restated oracle in fp32 gives its idx and update_count exactly and its floats to
+    GOLDEN_TOL."""
+    g = golden("train_vq")
+    in_dim, S, K, B, T, steps, every = (int(v) for v in g["dims"])
+    assert float(g["gap"]) >= U.MIN_GAP and float(g["dead_margin"]) >= U.MIN_DEAD
+    proj_sd = {k[len("w.proj."):]: g[k] for k in g if k.startswith("w.proj.")}
+    q_sd = {k[len("w.vq."):]: g[k] for k in g if k.startswith("w.vq.")}
+    head = U.Head(U.weights_of(proj_sd, q_sd), q_sd, torch.float32, reset_unused_every=every)
+    worst, resets = 0.0, 0
+    for s in range(steps):
+        r = head.step(g["h"], g["C"], loss_w=float(g["loss_w"]), perm=lambda n, s=s: g[f"perm.{s}"][:n])
+        assert torch.equal(r["idx"], g[f"idx.{s}"].reshape(-1)), s
+        assert r["count"] == int(g[f"count.{s}"]) == s + 1
+        resets += bool(r["reset"]) and r["rows"] is not None
+        for k in ("loss", "ecs", "ema_w", "cb"):
+            worst = max(worst, U.rel_err(r[k], g[f"{k}.{s}"]))
+        for k in ("w1", "b1", "lng", "lnb", "w3", "b3", "cb"):
+            worst = max(worst, U.rel_err(r["g." + k], g[f"g.{k}.{s}"]))
+            assert float(g[f"g.{k}.{s}"].abs().max()) > 0
+    print(f"oracle vs the reference's run: worst relative error {worst:.2e} over {steps} steps ({resets} with replaced codes)")
+    assert resets == 1
+    assert worst <= GOLDEN_TOL
+
+
+def test_c_abi_surface():
+    with open(os.path.join(REPO, "include", "edtts.h")) as f:
+        declared = set(re.findall(r"\b(edtts_\w+)\s*\(", f.read()))
+    L = native.lib()
+    for sym in NEW_SYMBOLS:
+        assert sym in declared and sym in native.EXPORTED_SYMBOLS and hasattr(L, sym), sym
+
+
+@pytest.mark.parametrize("name", sorted(U.CASES))
+def test_byte_sizes(name):
+    """tape = 4 (3 M S + M) bytes with a proj, 4 (M S + M) without; the training blob is W3^T in 16 x 16
+    fragment tiles (0 bytes without a proj); scratch = 4 (4 + K S [+ 5 M S + 2 M] + part), every term rounded up to 4 floats, part
+    the largest partial-sum buffer."""
+    in_dim, S, K, p, B, T = U.CASES[name]
+    dims = native.sem_dims(in_dim, S, None, K)
+    M = B * T
+    assert native.sem_vq_tape_bytes(dims, B, T) == 4 * ((3 if in_dim else 1) * M * S + M)
+    nt = S // 16
+    assert native.sem_vq_train_packed_bytes(dims) == (4 * 256 * nt * nt if in_dim else 0)
+    r4 = lambda n: (n + 3) // 4 * 4  # noqa: E731
+    rows = native.train_dw_slab_rows(M)
+    ns = (M + rows - 1) // rows
+    part = ns * K * S if ns > 1 else 0
+    if in_dim:
+        if ns > 1:
+            part = max(part, ns * S * max(S, in_dim))
+        part = max(part, (M + 255) // 256 * S, B * ((T + 63) // 64) * 3 * S)
+    want = 4 + r4(K * S) + ((5 * r4(M * S) + r4(2 * M)) if in_dim else 0) + r4(part)
+    assert native.sem_vq_scratch_bytes(dims, B, T) == 4 * want
+    assert native.sem_vq_tape_bytes(dims, 0, 7) == 0
+
+
+def test_argument_errors_before_pointers():
+    """FSQ dims, a wrong slot count, an invalid p, commit or decay are reported with every pointer NULL; and the four FSQ training
+    entries still refuse VQ dims with their message."""
+    L = native.lib()
+    vq = native.sem_dims(64, 32, None, 128)
+    alone = native.sem_dims(0, 32, None, 128)
+    fsq = native.sem_dims(64, 32, [3, 3])
+    out = C.c_size_t(0)
+    enc = lambda d, commit=0.25, drop=None: L.edtts_sem_vq_encode_train(C.byref(d), None, None, 1, 1, None, None, None, None, None, None, 1,  # noqa: E731
+                                                                       commit, drop, None)
+    ema = lambda d, decay=0.99, eps=1e-5: L.edtts_sem_vq_ema_update(C.byref(d), None, None, 1, 1, None, None, decay, eps, None, None, None,  # noqa: E731
+                                                                    None, None)
+    bwd = lambda d, n, commit=0.25, drop=None: L.edtts_sem_vq_backward(C.byref(d), None, None, None, None, None, 1, 1, None, None, None,  # noqa: E731
+                                                                       commit, None, n, None, None, drop, None)
+    calls = (lambda d: L.edtts_sem_vq_train_packed_bytes(C.byref(d), C.byref(out)), lambda d: L.edtts_sem_vq_train_pack(C.byref(d), None, 7, None, None),
+             lambda d: L.edtts_sem_vq_tape_bytes(C.byref(d), 1, 1, C.byref(out)), lambda d: L.edtts_sem_vq_scratch_bytes(C.byref(d), 1, 1, C.byref(out)),
+             enc, ema, lambda d: bwd(d, 7))
+    for fn in calls:
+        with pytest.raises(native.EdttsError, match="VQ quantizer only"):
+            fn(fsq)
+    with pytest.raises(native.EdttsError, match="expected 7 weight slots"):
+        L.edtts_sem_vq_train_pack(C.byref(vq), None, 1, None, None)
+    with pytest.raises(native.EdttsError, match="expected 7 gradient slots"):
+        bwd(vq, 1)
+    with pytest.raises(native.EdttsError, match="expected 1 gradient slots"):
+        bwd(alone, 7)
+    for p in (1.0, -0.1, 0.999995):
+        bad = native.EdttsDropout(p, 1)
+        with pytest.raises(native.EdttsError, match="dropout p="):
+            enc(vq, drop=C.byref(bad))
+        with pytest.raises(native.EdttsError, match="dropout p="):
+            bwd(vq, 7, drop=C.byref(bad))
+    with pytest.raises(native.EdttsError, match="no dropout site"):
+        enc(alone, drop=C.byref(native.EdttsDropout(0.5, 1)))
+    for commit in (-1.0, float("nan")):
+        with pytest.raises(native.EdttsError, match="commit="):
+            enc(vq, commit=commit)
+        with pytest.raises(native.EdttsError, match="commit="):
+            bwd(vq, 7, commit=commit)
+    for decay in (0.0, 1.5, float("nan")):
+        with pytest.raises(native.EdttsError, match="decay="):
+            ema(vq, decay=decay)
+    with pytest.raises(native.EdttsError, match="epsilon="):
+        ema(vq, eps=-1.0)
+    for B, T in ((-1, 1), (1 << 16, 1 << 16)):
+        with pytest.raises(native.EdttsError, match="out of range"):
+            L.edtts_sem_vq_encode_train(C.byref(vq), None, None, B, T, None, None, None, None, None, None, 1, 0.25, None, None)
+    for fn in (enc, ema, lambda d: bwd(d, 7)):
+        with pytest.raises(native.EdttsError, match="NULL pointer"):
+            fn(vq)
+    # the FSQ entries keep their refusal
+    for fn, args in ((L.edtts_sem_train_packed_bytes, (C.byref(vq), C.byref(out))),
+                     (L.edtts_sem_train_tape_bytes, (C.byref(vq), 1, 1, C.byref(out))),
+                     (L.edtts_sem_encode_train, (C.byref(vq), None, None, 1, 1, None, None, None, None, None, None, None)),
+                     (L.edtts_sem_backward, (C.byref(vq), None, None, None, None, 1, 1, None, None, None, 0, None, None, None, None))):
+        with pytest.raises(native.EdttsError, match="FSQ quantizer only"):
+            fn(*args)
+
+
+def test_constructor_errors_and_defaults():
+    fsq = CFG(device="cpu", use_fsq=True, fsq_levels=[3, 3], semantic_dim=32)
+    vq = CFG(device="cpu", use_fsq=False, semantic_dim=32, codebook_size=64)
+    with pytest.raises(ValueError, match="train_vq=True needs autograd=True"):
+        SemanticEncoder(vq, in_dim=64, train_vq=True)
+    with pytest.raises(ValueError, match="needs a VQ config"):
+        SemanticEncoder(fsq, in_dim=64, autograd=True, train_vq=True)
+    with pytest.raises(ValueError, match=r"VQ path.*train_vq=True"):
+        SemanticEncoder(vq, in_dim=64, autograd=True)
+    enc = SemanticEncoder(vq, in_dim=64, autograd=True, train_vq=True)
+    assert enc.train_vq and enc.autograd and enc.vq.autograd and enc.vq.reset_generator is None
+    want = [p for p in enc.proj.parameters()] + [enc.vq.codebook.weight]
+    got = enc.get_trainable_params()
+    assert len(got) == len(want) == 7 and all(a is b for a, b in zip(got, want)) and all(p.requires_grad for p in got)
+    # autograd=False modules are what they were
+    plain = SemanticEncoder(vq, in_dim=64)
+    assert plain.autograd is False and plain.train_vq is False and plain.vq.autograd is False
+    q = VectorQuantizer(32, 64)
+    assert q.autograd is False and sorted(q.state_dict()) == ["codebook.weight", "ema_cluster_size", "ema_w", "update_count"]
+    assert (q.commit, q.decay, q.epsilon, q.reset_unused_every) == (0.25, 0.99, 1e-5, 100)
+    assert sorted(enc.vq.state_dict()) == sorted(q.state_dict())
+    assert SemanticEncoder(fsq, in_dim=64, autograd=True).train_vq is False
