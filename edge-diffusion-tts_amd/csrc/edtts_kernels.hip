@@ -2827,6 +2827,7 @@ struct Launcher16 {
 #include "edtts_hubert.h"
 #include "edtts_hubert16.h"
 #include "edtts_audio.h"
+#include "edtts_optim.h"
 
 // compiled decoder shapes: (hidden, heads, n_mels).  EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, body) runs `body` with LN = the fused
 // launcher of lo's shape, or the statement MISS16 / MISS32 when none is compiled; EDTTS_DISPATCH adds the generic launcher (lo.GEN)
@@ -3115,49 +3116,63 @@ static int transpose_f(hipStream_t st, const float* src, float* dst, int N, int 
   return EDTTS_OK;
 }
 
-// generic layout (make_generic_layout): copies, and the transposes the conditioning kernels read
-static int pack_generic(const Layout& lo, const void* const* slots, float* blob, hipStream_t st) {
-  auto G = [&](int i) { return (const float*)slots[i]; };
+// generic layout (make_generic_layout): where a weight slot goes -- offset in floats, the slot's [rows][cols], and whether the blob
+// holds its transpose (the matrices the conditioning kernels read).  pack_generic and edtts_generic_slot_dest both read this.
+struct SlotDest {
+  size_t off, rows, cols;
+  bool tr;
+};
+static SlotDest generic_slot_dest(const Layout& lo, int slot) {
   const size_t H = lo.H, R = lo.R, SD = lo.SD, MEL = lo.MEL, FH = (size_t)lo.FM * lo.H;
-  TRY(copy_f(st, G(G_TOK), blob + lo.tok, (size_t)lo.NTOK * H));
-  TRY(copy_f(st, G(G_SEMP_W), blob + lo.semp, H * SD));
-  TRY(copy_f(st, G(G_SEMP_B), blob + lo.semp_b, H));
-  TRY(transpose_f(st, G(G_T1_W), blob + lo.t1T, (int)H, (int)H));
-  TRY(copy_f(st, G(G_T1_B), blob + lo.t1b, H));
-  TRY(transpose_f(st, G(G_T3_W), blob + lo.t3T, (int)H, (int)H));
-  TRY(copy_f(st, G(G_T3_B), blob + lo.t3b, H));
-  TRY(copy_f(st, G(G_STEP), blob + lo.step, (size_t)lo.NSTEP * H));
-  TRY(copy_f(st, G(G_INP_W), blob + lo.inp, H * MEL));
-  TRY(copy_f(st, G(G_INP_B), blob + lo.inp_b, H));
-  TRY(copy_f(st, G(G_PE), blob + lo.pe, (size_t)lo.MAXPOS * H));
-  TRY(copy_f(st, G(G_CPE), blob + lo.cpe, (size_t)lo.MAXCPOS * H));
-  TRY(copy_f(st, G(G_FN_W), blob + lo.fnw, H));
-  TRY(copy_f(st, G(G_FN_B), blob + lo.fnb, H));
-  TRY(copy_f(st, G(G_OUT_W), blob + lo.s_outp, MEL * H));
-  TRY(copy_f(st, G(G_OUT_B), blob + lo.outp_b, MEL));
-  TRY(copy_f(st, G(G_FREQS), blob + lo.freqs, H / 2));
-  for (int l = 0; l < lo.L; ++l) {
-    const LayerLayout& y = lo.layer[l];
-    auto W = [&](int i) { return (const float*)slots[G_COUNT + l * L_COUNT + i]; };
-    TRY(copy_f(st, W(L_N1_W), blob + y.n1w, H));
-    TRY(transpose_f(st, W(L_N1P_W), blob + y.ada1T, 2 * (int)H, (int)H));
-    TRY(copy_f(st, W(L_N1P_B), blob + y.ada1b, 2 * H));
-    TRY(copy_f(st, W(L_QKV_W), blob + y.s_qkv, 3 * H * H));
-    TRY(copy_f(st, W(L_PROJ_W), blob + y.g_proj, H * H));
-    TRY(copy_f(st, W(L_PROJ_B), blob + y.proj_b, H));
-    TRY(copy_f(st, W(L_N2_W), blob + y.n2w, H));
-    TRY(copy_f(st, W(L_QP_W), blob + y.g_qp, H * H));
-    TRY(copy_f(st, W(L_KVD_W), blob + y.kvd, R * H));
-    TRY(copy_f(st, W(L_KVN_W), blob + y.kvn, R));
-    TRY(copy_f(st, W(L_KVU_W), blob + y.kvu, 2 * H * R));
-    TRY(copy_f(st, W(L_OP_W), blob + y.g_op, H * H));
-    TRY(copy_f(st, W(L_N3_W), blob + y.n3w, H));
-    TRY(transpose_f(st, W(L_N3P_W), blob + y.ada3T, 2 * (int)H, (int)H));
-    TRY(copy_f(st, W(L_N3P_B), blob + y.ada3b, 2 * H));
-    TRY(copy_f(st, W(L_UP_W), blob + y.g_up, 2 * FH * H));
-    TRY(copy_f(st, W(L_UP_B), blob + y.up_b, 2 * FH));
-    TRY(copy_f(st, W(L_DOWN_W), blob + y.g_down, H * FH));
-    TRY(copy_f(st, W(L_DOWN_B), blob + y.down_b, H));
+  if (slot < G_COUNT) {
+    switch (slot) {
+      case G_TOK: return {lo.tok, (size_t)lo.NTOK, H, false};
+      case G_SEMP_W: return {lo.semp, H, SD, false};
+      case G_SEMP_B: return {lo.semp_b, 1, H, false};
+      case G_T1_W: return {lo.t1T, H, H, true};
+      case G_T1_B: return {lo.t1b, 1, H, false};
+      case G_T3_W: return {lo.t3T, H, H, true};
+      case G_T3_B: return {lo.t3b, 1, H, false};
+      case G_STEP: return {lo.step, (size_t)lo.NSTEP, H, false};
+      case G_INP_W: return {lo.inp, H, MEL, false};
+      case G_INP_B: return {lo.inp_b, 1, H, false};
+      case G_PE: return {lo.pe, (size_t)lo.MAXPOS, H, false};
+      case G_CPE: return {lo.cpe, (size_t)lo.MAXCPOS, H, false};
+      case G_FN_W: return {lo.fnw, 1, H, false};
+      case G_FN_B: return {lo.fnb, 1, H, false};
+      case G_OUT_W: return {lo.s_outp, MEL, H, false};
+      case G_OUT_B: return {lo.outp_b, 1, MEL, false};
+      default: return {lo.freqs, 1, H / 2, false};  // G_FREQS
+    }
+  }
+  const LayerLayout& y = lo.layer[(slot - G_COUNT) / L_COUNT];
+  switch ((slot - G_COUNT) % L_COUNT) {
+    case L_N1_W: return {y.n1w, 1, H, false};
+    case L_N1P_W: return {y.ada1T, 2 * H, H, true};
+    case L_N1P_B: return {y.ada1b, 1, 2 * H, false};
+    case L_QKV_W: return {y.s_qkv, 3 * H, H, false};
+    case L_PROJ_W: return {y.g_proj, H, H, false};
+    case L_PROJ_B: return {y.proj_b, 1, H, false};
+    case L_N2_W: return {y.n2w, 1, H, false};
+    case L_QP_W: return {y.g_qp, H, H, false};
+    case L_KVD_W: return {y.kvd, R, H, false};
+    case L_KVN_W: return {y.kvn, 1, R, false};
+    case L_KVU_W: return {y.kvu, 2 * H, R, false};
+    case L_OP_W: return {y.g_op, H, H, false};
+    case L_N3_W: return {y.n3w, 1, H, false};
+    case L_N3P_W: return {y.ada3T, 2 * H, H, true};
+    case L_N3P_B: return {y.ada3b, 1, 2 * H, false};
+    case L_UP_W: return {y.g_up, 2 * FH, H, false};
+    case L_UP_B: return {y.up_b, 1, 2 * FH, false};
+    case L_DOWN_W: return {y.g_down, H, FH, false};
+    default: return {y.down_b, 1, H, false};  // L_DOWN_B
+  }
+}
+static int pack_generic(const Layout& lo, const void* const* slots, float* blob, hipStream_t st) {
+  for (int i = 0; i < G_COUNT + lo.L * L_COUNT; ++i) {
+    const SlotDest d = generic_slot_dest(lo, i);
+    if (d.tr) TRY(transpose_f(st, (const float*)slots[i], blob + d.off, (int)d.rows, (int)d.cols));
+    else TRY(copy_f(st, (const float*)slots[i], blob + d.off, d.rows * d.cols));
   }
   return EDTTS_OK;
 }
@@ -4007,6 +4022,140 @@ int edtts_profile_collect(double* ms_by_kind, int* launches_by_kind) {
     launches_by_kind[0] += 1;
   }
   g_prof.used = 0;
+  return EDTTS_OK;
+}
+
+// ---- optimiser step (edtts_optim.h) ------------------------------------------------------------------------------------------------
+int edtts_optim_chunk_size(void) { return edtts_opt::kOptChunk; }
+
+int edtts_optim_chunk_table(const int64_t* numels, int n_tensors, int cap, int32_t* tensor, int64_t* offset, int32_t* count, int* n_chunks) {
+  if (!numels || !n_chunks || n_tensors < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: NULL pointer argument or n_tensors < 0");
+  long long n = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    if (numels[i] < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: numels[%d] = %lld < 0", i, (long long)numels[i]);
+    for (long long o = 0; o < numels[i]; o += edtts_opt::kOptChunk, ++n) {
+      if (n >= cap) continue;  // (counted, not written)
+      if (!tensor || !offset || !count) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: cap > 0 needs the three output arrays");
+      const long long left = numels[i] - o;
+      tensor[n] = i;
+      offset[n] = o;
+      count[n] = (int32_t)(left < edtts_opt::kOptChunk ? left : edtts_opt::kOptChunk);
+    }
+  }
+  if (n > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_chunk_table: %lld chunks", n);
+  *n_chunks = (int)n;
+  return EDTTS_OK;
+}
+
+int edtts_optim_scratch_bytes(int n_chunks, int n_groups, size_t* out_bytes) {
+  if (!out_bytes || n_chunks < 0 || n_groups < 1) return fail(EDTTS_ERR_ARG, "edtts_optim_scratch_bytes: n_chunks=%d n_groups=%d", n_chunks, n_groups);
+  edtts_opt::OptScratch s;
+  edtts_opt::opt_scratch((size_t)n_chunks, (size_t)n_groups, &s);
+  *out_bytes = s.total;
+  return EDTTS_OK;
+}
+
+int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
+                     void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace edtts_opt;
+  if (n_tensors < 0 || n_groups < 1 || (n_tensors && !tensors) || !groups || !scratch)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: NULL pointer argument, n_tensors=%d or n_groups=%d", n_tensors, n_groups);
+  if (flags & ~(EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE | EDTTS_OPT_ZERO_GRADS | EDTTS_OPT_EMA_ONLY))
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: unknown flag bits 0x%x", flags);
+  const bool ema_only = flags & EDTTS_OPT_EMA_ONLY;
+  if (ema_only && (flags & ~EDTTS_OPT_EMA_ONLY)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: EDTTS_OPT_EMA_ONLY excludes the other flags");
+  if ((flags & EDTTS_OPT_CLIP) && !(max_norm >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: max_norm=%g", max_norm);
+  long long n_chunks = 0;
+  int n_live = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const EdttsOptimTensor& t = tensors[i];
+    if (t.numel < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has numel %lld", i, (long long)t.numel);
+    if (t.numel == 0) continue;
+    if (!t.p || (!ema_only && (!t.g || !t.m || !t.v)) || (ema_only && !t.ema))
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a NULL p, g, m, v or (EDTTS_OPT_EMA_ONLY) ema", i);
+    if (((size_t)t.p | (size_t)t.g | (size_t)t.m | (size_t)t.v | (size_t)t.ema | (size_t)t.mirror | (size_t)t.ema_mirror) & 3)
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a pointer that is not 4-byte aligned", i);
+    if (t.group < 0 || t.group >= n_groups) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d names group %d of %d", i, t.group, n_groups);
+    if (t.rows < 0 || t.cols < 0 || (t.rows > 0 && (int64_t)t.rows * t.cols != t.numel))
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: rows=%d cols=%d do not make numel=%lld", i, t.rows, t.cols, (long long)t.numel);
+    if (t.ema_mirror && !t.ema) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has an ema_mirror without an ema", i);
+    if (t.ema && !(t.ema_decay >= 0.f && t.ema_decay <= 1.f)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: ema_decay=%g", i, (double)t.ema_decay);
+    n_chunks += opt_chunks_of(t.numel);
+    ++n_live;
+  }
+  if (n_chunks == 0) return EDTTS_OK;  // nothing to step: as torch, no state changes (the step counter included)
+  if (n_chunks > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_step: %lld chunks", n_chunks);
+  OptScratch ls;
+  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
+  if (ls.total > scratch_bytes)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: %lld chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  char* sc = (char*)scratch;
+  const size_t up_bytes = ls.total - ls.groups;  // groups | tensors | chunks, as they lie in the scratch
+
+  std::lock_guard<std::mutex> lock(g_opt_mu);
+  OptSlot& slot = g_opt_ring[g_opt_next];
+  g_opt_next = (g_opt_next + 1) % kOptRing;
+  if (slot.pending) {
+    HIP_TRY(hipEventSynchronize(slot.ev));  // (returns at once unless kOptRing steps are outstanding)
+    slot.pending = false;
+  }
+  if (slot.cap < up_bytes) {
+    if (slot.host) HIP_TRY(hipHostFree(slot.host));
+    slot.host = nullptr;
+    slot.cap = 0;
+    HIP_TRY(hipHostMalloc(&slot.host, up_bytes + up_bytes / 2, hipHostMallocDefault));
+    slot.cap = up_bytes + up_bytes / 2;
+  }
+  if (slot.ev) (void)hipEventDestroy(slot.ev);  // (an event belongs to the device that was current when it was made: a new one per step)
+  slot.ev = nullptr;
+  HIP_TRY(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+  char* up = (char*)slot.host;
+  memset(up, 0, up_bytes);
+  memcpy(up, groups, (size_t)n_groups * sizeof(EdttsOptimGroup));
+  OptTensor* ht = (OptTensor*)(up + (ls.tensors - ls.groups));
+  OptChunk* hc = (OptChunk*)(up + (ls.chunks - ls.groups));
+  int ti = 0;
+  long long ci = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const EdttsOptimTensor& t = tensors[i];
+    if (t.numel == 0) continue;
+    ht[ti] = OptTensor{t.p, t.g, t.m, t.v, t.ema, t.mirror, t.ema_mirror, t.group, t.rows, t.cols, (float)(1.0 - (double)t.ema_decay)};
+    for (long long o = 0; o < t.numel; o += kOptChunk, ++ci) {
+      const long long left = t.numel - o;
+      hc[ci] = OptChunk{o, ti, (int)(left < kOptChunk ? left : kOptChunk)};
+    }
+    ++ti;
+  }
+  HIP_TRY(hipMemcpyAsync(sc + ls.groups, up, up_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(slot.ev, st));
+  slot.pending = true;
+  OptArgs a{(EdttsOptimState*)sc, (OptBias*)(sc + ls.bias), (float*)(sc + ls.partial), (const EdttsOptimGroup*)(sc + ls.groups),
+            (const OptTensor*)(sc + ls.tensors), (const OptChunk*)(sc + ls.chunks), (int)n_chunks, n_groups, flags, (float)max_norm};
+  if (!ema_only) {
+    const int have_norm = (flags & (EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE)) ? 1 : 0;
+    if (have_norm) {
+      hipLaunchKernelGGL(k_opt_sqsum, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
+      LAUNCH_CHECK("k_opt_sqsum");
+    }
+    hipLaunchKernelGGL(k_opt_finish, dim3(1), dim3(kOptThreads), 0, st, a, have_norm);
+    LAUNCH_CHECK("k_opt_finish");
+  }
+  hipLaunchKernelGGL(k_opt_adamw, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
+  LAUNCH_CHECK("k_opt_adamw");
+  return EDTTS_OK;
+}
+
+int edtts_generic_slot_dest(const EdttsDims* dims, int slot, size_t* offset_floats, int* rows, int* cols, int* transposed) {
+  Layout lo;
+  TRY(train_layout(dims, "edtts_generic_slot_dest", &lo));
+  if (!offset_floats || !rows || !cols || !transposed) return fail(EDTTS_ERR_ARG, "edtts_generic_slot_dest: NULL pointer argument");
+  if (slot < 0 || slot >= G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "edtts_generic_slot_dest: slot %d of %d", slot, G_COUNT + lo.L * L_COUNT);
+  const SlotDest d = generic_slot_dest(lo, slot);
+  *offset_floats = d.off;
+  *rows = (int)d.rows;
+  *cols = (int)d.cols;
+  *transposed = d.tr ? 1 : 0;
   return EDTTS_OK;
 }
 

@@ -18,6 +18,7 @@ from .melpost import GriffinLim, InverseMelScale, MelVocoder, denormalize_mel, n
 from .encoder import FSQ, FSQEncoder, SemanticEncoder, VectorQuantizer
 from .hubert import NativeHubert
 from .audio import MelSpectrogram, Resample, chunk_stats_from_audio, resample
+from .optim import FusedAdamW
 
 __all__ = [
     "CFG", "TrainPhase", "get_device", "set_seed", "DiffusionSchedule", "DPMSolverPP", "EdgeDiffusionDecoder", "EdgeInference",
@@ -25,4 +26,5 @@ __all__ = [
     "GriffinLim", "InverseMelScale", "MelVocoder", "denormalize_mel", "normalize_mel",
     "SemanticEncoder", "VectorQuantizer", "FSQ", "FSQEncoder", "NativeHubert",
     "MelSpectrogram", "Resample", "resample", "chunk_stats_from_audio",
+    "FusedAdamW",
 ]

@@ -322,6 +322,46 @@ class EdgeDiffusionDecoder(nn.Module):
                     self._pack_waited.add(stream.cuda_stream)
             return self._packed
 
+    # ------------------------------------------------------------------------------------------ blob mirror (optim.FusedAdamW)
+    def _sig(self) -> Tuple:
+        return tuple((t.data_ptr(), t._version) for t in self._slot_tensors()[1])
+
+    def _mirror_map(self) -> Optional[Dict[str, Tuple[int, int, int, bool]]]:
+        """{parameter name: (offset in floats, rows, cols, transposed)} of the packed blob, from the library's own layout
+        (native.generic_slot_dest); None for a decoder whose blob is not the generic fp32 one (fragment-order blobs are not mirrored)."""
+        if self.kernels != "generic" or native.COMPUTE_DTYPES[self.compute_dtype] != native.COMPUTE_DTYPES["f32"]:
+            return None
+        dims, out = self.dims(), {}
+        for i, slot in enumerate(native.slot_names(self.cfg.layers)):
+            name = self._slot_param(slot)
+            if name is not None:
+                out[name] = native.generic_slot_dest(dims, i)
+        return out
+
+    def _mirror_target(self) -> Optional[torch.Tensor]:
+        """The packed blob if it is current -- packed, and packed from the tensors as they stand -- else None.  The current stream is
+        ordered behind the pack, so an optimiser step enqueued on it may write the new values into the blob."""
+        with self._lock:
+            if self._packed is None or self._packed_sig != self._sig():
+                return None
+            if self._pack_event is not None:
+                stream = torch.cuda.current_stream(self._packed.device)
+                if stream.cuda_stream not in self._pack_waited:
+                    stream.wait_event(self._pack_event)
+                    self._pack_waited.add(stream.cuda_stream)
+            return self._packed
+
+    def _mirror_commit(self) -> None:
+        """After a step that wrote every updated parameter into the blob as well and bumped the parameters' versions: the blob is
+        current again.  Takes the signature of the tensors as they stand and records the pack event on the current stream."""
+        with self._lock:
+            self._packed_sig = self._sig()
+            if self._packed.is_cuda:
+                stream = torch.cuda.current_stream(self._packed.device)
+                self._pack_event = torch.cuda.Event()
+                self._pack_event.record(stream)
+                self._pack_waited = {stream.cuda_stream}
+
     WORKSPACE_CACHE = 8
 
     def workspace(self, B: int, T: int, S: int, cond_rows: int, device, tag: str = "", *, stream=None) -> torch.Tensor:

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "edtts_sem_vq_train_packed_bytes", "edtts_sem_vq_train_pack", "edtts_sem_vq_tape_bytes", "edtts_sem_vq_scratch_bytes",
     "edtts_sem_vq_encode_train", "edtts_sem_vq_ema_update", "edtts_sem_vq_backward",
     "edtts_decoder_forward_train_len", "edtts_decoder_backward_len",
+    "edtts_optim_chunk_size", "edtts_optim_chunk_table", "edtts_optim_scratch_bytes", "edtts_optim_step", "edtts_generic_slot_dest",
 )
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
@@ -76,6 +77,24 @@ def sem_dims(in_dim: int, semantic_dim: int, levels: Optional[Sequence[int]] = N
     else:
         d.quantizer, d.codebook_size = SEM_VQ, int(codebook_size)
     return d
+
+
+class EdttsOptimState(C.Structure):
+    """include/edtts.h: EdttsOptimState -- the head of an optimiser scratch."""
+    _fields_ = [("step", C.c_int64), ("skipped", C.c_int64), ("total_norm", C.c_float), ("clip_coef", C.c_float), ("skip", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class EdttsOptimGroup(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+class EdttsOptimTensor(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("p", "g", "m", "v", "ema", "mirror", "ema_mirror")] + [
+        ("numel", C.c_int64), ("group", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("ema_decay", C.c_float)]
+
+
+OPT_CLIP, OPT_SKIP_NONFINITE, OPT_ZERO_GRADS, OPT_EMA_ONLY = 1, 2, 4, 8  # include/edtts.h: EDTTS_OPT_*
 
 
 class EdttsHubertDims(C.Structure):
@@ -200,6 +219,12 @@ def lib() -> C.CDLL:
     L.edtts_sem_vq_encode_train.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, C.c_double, dpp, vp]
     L.edtts_sem_vq_ema_update.argtypes = [sdp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     L.edtts_sem_vq_backward.argtypes = [sdp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, C.c_double, C.POINTER(vp), i32, vp, vp, dpp, vp]
+    L.edtts_optim_chunk_size.restype = i32
+    L.edtts_optim_chunk_table.argtypes = [C.POINTER(C.c_int64), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                          C.POINTER(i32)]
+    L.edtts_optim_scratch_bytes.argtypes = [i32, i32, C.POINTER(sz)]
+    L.edtts_optim_step.argtypes = [C.POINTER(EdttsOptimTensor), i32, C.POINTER(EdttsOptimGroup), i32, C.c_double, i32, vp, sz, vp]
+    L.edtts_generic_slot_dest.argtypes = [C.POINTER(EdttsDims), i32, C.POINTER(sz), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.edtts_profile_enable.argtypes = [i32]
     L.edtts_set_substreams.argtypes = [i32]
     L.edtts_set_substreams.restype = i32
@@ -211,7 +236,7 @@ def lib() -> C.CDLL:
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("edtts_version", "edtts_num_global_slots", "edtts_num_layer_slots", "edtts_set_substreams", "edtts_set_coop", "edtts_substreams_for",
-                                                  "edtts_train_dw_slab_rows"):
+                                                  "edtts_train_dw_slab_rows", "edtts_optim_chunk_size"):
             fn.errcheck = _errcheck
     _lib = L
     return L
@@ -646,6 +671,44 @@ def check_indices(workspace: torch.Tensor) -> None:
 def check_table_index(t: torch.Tensor, n: int, name: str, lo: int = 0) -> None:
     if CHECK_INDICES and not torch.cuda.is_current_stream_capturing() and bool(((t < lo) | (t >= n)).any()):
         raise IndexError(f"{name}: index out of range [{lo}, {n})")
+
+
+# ---------------------------------------------------------------------------------------------- optimiser step
+def optim_chunk_size() -> int:
+    """Elements per chunk of the optimiser's multi-tensor table (include/edtts.h: edtts_optim_chunk_size)."""
+    return int(lib().edtts_optim_chunk_size())
+
+
+def optim_chunk_table(numels: Sequence[int]) -> List[Tuple[int, int, int]]:
+    """The library's cutting of a list of tensor sizes into chunks: [(tensor index, first element, count)], a host query."""
+    n = len(numels)
+    arr = (C.c_int64 * max(n, 1))(*[int(v) for v in numels])
+    total = C.c_int(0)
+    lib().edtts_optim_chunk_table(arr, n, 0, None, None, None, C.byref(total))
+    cap = max(total.value, 1)
+    ti, off, cnt = (C.c_int32 * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
+    lib().edtts_optim_chunk_table(arr, n, total.value, ti, off, cnt, C.byref(total))
+    return [(ti[i], off[i], cnt[i]) for i in range(total.value)]
+
+
+def optim_scratch_bytes(n_chunks: int, n_groups: int) -> int:
+    return _size_query(lib().edtts_optim_scratch_bytes, int(n_chunks), int(n_groups))
+
+
+def optim_step(tensors, n_tensors: int, groups, n_groups: int, max_norm: Optional[float], flags: int, scratch: torch.Tensor) -> None:
+    """edtts_optim_step on the current stream of the scratch's device.  `tensors` / `groups`: ctypes arrays of EdttsOptimTensor /
+    EdttsOptimGroup holding device pointers the caller has validated (fp32, contiguous, on that device)."""
+    if max_norm is not None:
+        flags |= OPT_CLIP
+    lib().edtts_optim_step(tensors, n_tensors, groups, n_groups, 0.0 if max_norm is None else float(max_norm), flags,
+                           _dev_ptr(scratch, torch.uint8, "scratch"), scratch.numel(), _stream(scratch.device))
+
+
+def generic_slot_dest(dims: EdttsDims, slot: int) -> Tuple[int, int, int, bool]:
+    """(offset in floats, rows, cols, transposed) of weight slot `slot` in the generic fp32 blob (include/edtts.h)."""
+    off, rows, cols, tr = C.c_size_t(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().edtts_generic_slot_dest(C.byref(dims), int(slot), C.byref(off), C.byref(rows), C.byref(cols), C.byref(tr))
+    return off.value, rows.value, cols.value, bool(tr.value)
 
 
 # ---------------------------------------------------------------------------------------------- semantic head

@@ -651,7 +651,80 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
                           double commit, void* const* grad_slots, int n_slots, float* d_z, void* scratch, const EdttsDropout* drop,
                           void* stream);
 
-/* ---- HuBERT backbone  (transformers HubertModel, feat_extract_norm = "group", do_stable_layer_norm = False: hubert-base) ------------
+/* ---- the optimiser step  (train_v2.py:299-309 and edge_diffusion_tts/train.py:160-170,245-249,279-281: clip_grad_norm_(params,
+ * cfg.grad_clip) then AdamW.step(); training/consistency.py:45-50: ConsistencyTrainer.update_teacher, lerp_ over every parameter) ---
+ * One pass over a list of fp32 tensors: clip by the global gradient norm, AdamW, optionally an EMA target,
+ * a second copy of the new values ("mirror": the generic decoder's packed blob, so that the next forward packs nothing) and the
+ * zeroing of the gradient.  Two or three launches and one small host-to-device copy per step; no host synchronisation, no
+ * allocation of device memory, everything on `stream`.
+ *
+ * Arithmetic, per element, torch.optim.AdamW's single-tensor form in its order (host scalars are doubles, rounded to fp32 where
+ * they meet a tensor):  g *= clip_coef;  p *= 1 - lr wd;  m = m + (1 - beta1)(g - m);  v = beta2 v + (1 - beta2) g g;
+ *     p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),   bc1 = 1 - beta1^step, bc2 = 1 - beta2^step  (fp64, on the device);
+ *     ema += (p_new - ema)(1 - ema_decay)   (lerp_);   mirror[i or its transposed place] = p_new;  ema_mirror likewise = ema_new.
+ * g itself is only read (or zeroed with EDTTS_OPT_ZERO_GRADS): unlike clip_grad_norm_, the scaled gradient is not stored.
+ * total_norm = sqrt(sum g^2) over every tensor of the call: fp32 sums of squares per chunk in a fixed order, the chunks added in
+ * ascending order in fp64 -- no float atomics, a step is bitwise reproducible.  clip_coef = min(1, max_norm / (total_norm + 1e-6)),
+ * a NaN staying a NaN as in torch.
+ *
+ * One device-resident step counter serves every tensor of a scratch (EdttsOptimState.step, incremented by each step before its
+ * bias corrections are formed); the host never reads it on the way.  With EDTTS_OPT_SKIP_NONFINITE a step whose total_norm is not
+ * finite stores nothing at all -- p, m, v, ema, the mirrors and g keep their bits, step stays -- and adds one to `skipped`.
+ *
+ * scratch: edtts_optim_scratch_bytes bytes for the largest number of chunks and groups a step will bring; the caller zero-fills
+ * it once (step = skipped = 0) and keeps it for the optimiser's life.  It begins with an EdttsOptimState that the caller may read
+ * (after ordering itself behind the stream).  A chunk is at most edtts_optim_chunk_size elements of one tensor; chunk starts are
+ * multiples of that size, hence of 4.  edtts_optim_chunk_table is the step's own cutting of a list of numels, as a host query: it
+ * writes the first `cap` chunks (tensor index, first element, count) and the total number of chunks (cap = 0: the count alone).
+ *
+ * A step may be issued while earlier ones have not run: the table of pointers travels through a pinned ring of 8 slots, ordered
+ * by events (only with more than 8 steps outstanding does the host wait for the oldest copy).  Steps that share a scratch must
+ * be issued on one stream, or ordered by the caller.  Tensors with numel 0 are skipped; a call without any element returns at
+ * once and changes nothing.  Pointers must be 4-byte aligned; a tensor whose pointers are all 16-byte aligned takes 16-byte
+ * loads and stores.  Not graph-capturable as a unit (lr is a host argument and the table is copied from the host). */
+typedef struct EdttsOptimState {
+  int64_t step;      /* steps taken (skipped ones not counted)                               */
+  int64_t skipped;   /* steps skipped by EDTTS_OPT_SKIP_NONFINITE                            */
+  float total_norm;  /* of the last step that computed one                                   */
+  float clip_coef;   /* of the last step (1 without EDTTS_OPT_CLIP)                          */
+  int32_t skip;      /* 1 when the last step was skipped                                     */
+  int32_t reserved;
+} EdttsOptimState;
+typedef struct EdttsOptimGroup {
+  double lr, beta1, beta2, eps, weight_decay;
+} EdttsOptimGroup;
+typedef struct EdttsOptimTensor {
+  float* p;           /* parameter [numel]                                                                            */
+  float* g;           /* gradient                                                                                     */
+  float* m;           /* exp_avg                                                                                      */
+  float* v;           /* exp_avg_sq                                                                                   */
+  float* ema;         /* EMA target [numel] or NULL                                                                   */
+  float* mirror;      /* second destination of the new p or NULL (blob + offset in floats)                            */
+  float* ema_mirror;  /* second destination of the new ema or NULL (needs ema)                                        */
+  int64_t numel;
+  int32_t group;      /* index into groups                                                                            */
+  int32_t rows, cols; /* rows > 0: p is [rows][cols] and both mirrors hold the transpose [cols][rows]; 0, 0: plain    */
+  float ema_decay;    /* in [0, 1]                                                                                    */
+} EdttsOptimTensor;
+enum {
+  EDTTS_OPT_CLIP = 1,           /* max_norm is given (otherwise no clipping; total_norm is then only computed for SKIP_NONFINITE) */
+  EDTTS_OPT_SKIP_NONFINITE = 2,
+  EDTTS_OPT_ZERO_GRADS = 4,     /* g = 0 behind the update */
+  EDTTS_OPT_EMA_ONLY = 8        /* no optimiser arithmetic: ema (required) and ema_mirror from p as it stands; g, m, v unused; excludes
+                                   the other flags and leaves the state alone */
+};
+int edtts_optim_chunk_size(void);
+int edtts_optim_chunk_table(const int64_t* numels, int n_tensors, int cap, int32_t* tensor, int64_t* offset, int32_t* count, int* n_chunks);
+int edtts_optim_scratch_bytes(int n_chunks, int n_groups, size_t* out_bytes);
+int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
+                     void* scratch, size_t scratch_bytes, void* stream);
+/* Where edtts_pack_weights puts weight slot `slot` of a generic fp32 layout (dims.compute_dtype = EDTTS_F32 | EDTTS_KERNELS_GENERIC;
+ * anything else is EDTTS_ERR_UNSUPPORTED): its offset in floats, the slot's [rows][cols] (a vector: 1 x n) and whether the blob
+ * holds its transpose [cols][rows] (time_emb.1 / .3 and the two AdaLN projections of a layer).  Layout arithmetic from the same
+ * table the packing reads; no GPU call. */
+int edtts_generic_slot_dest(const EdttsDims* dims, int slot, size_t* offset_floats, int* rows, int* cols, int* transposed);
+
+/* ---- HuBERT backbone (transformers HubertModel, feat_extract_norm = "group", do_stable_layer_norm = False: hubert-base) ------------
  * wav [B, T_audio] fp32 -> HubertModel(wav, output_hidden_states=True).hidden_states[num_layers] [B, T_feat, hidden], eval mode, fp32.
  * Only the layers up to num_layers are packed and run; num_layers = 0 is the output of the encoder's LayerNorm.  GELU is the erf form
  * throughout.  The caller (edge_diffusion_tts_amd/hubert.py) checks the layout fields that are not numbers (feat_extract_norm,
