@@ -444,6 +444,43 @@ __global__ __launch_bounds__(256) void k_gen_zero_past(float* y, const int64_t* 
 
 }  // namespace edtts_gen
 
+// A validated EdttsDropout (include/edtts.h, "Dropout masks"): the key words, the threshold and the scale of the kept values.
+enum { DROP_ATTN = 0, DROP_CROSS = 1, DROP_ACT = 2, DROP_DOWN = 3 };
+struct DropState {
+  unsigned k0, k1, thr;
+  float scale;
+  DropArgs site(int layer, int site_id) const { return DropArgs{k0, k1, 0x30000u + 4u * (unsigned)layer + (unsigned)site_id, thr, scale}; }
+};
+
+// Where one forward's intermediates go.  Inference reuses a few workspace buffers for all of them; the training forward
+// (edtts_generic_bwd.h) points them into its tape and also asks for the snapshots and the log-sum-exps.
+struct FwdLayerBufs {
+  float *crp, *crn, *kv;     // kv_down rows [B S][R] before / after kv_norm; K|V rows [B S][2H]
+  float *qkv, *att1, *lse1;  // self-attention: q|k|v rows, attention output, log-sum-exp [B][HEADS][T] or null
+  float *qc, *att2, *lse2;   // cross-attention: query rows, attention output, log-sum-exp or null
+  float* act;                // value * silu(gate) [B T][FM H]
+  float *h0, *h1, *h2;       // or null: copies of the residual stream entering norm1 / norm2 / norm3
+};
+struct FwdBufs {
+  float* ctx;  // context rows [B S][H]
+  FwdLayerBufs layer[kMaxLayers];
+  float* hL;   // or null: a copy of the residual stream entering final_norm
+  FwdBufs() = default;
+  // the workspace's buffers: kv_norm in place, one buffer for q|k|v, the cross queries and the SwiGLU output, one for both
+  // attention outputs; no snapshot, no log-sum-exp
+  explicit FwdBufs(const CallCtx& c) : ctx(c.wsb + c.ws.g_ctx), hL(nullptr) {
+    float *cr = c.wsb + c.ws.g_cr, *big = c.wsb + c.ws.g_big, *att = c.wsb + c.ws.g_att;
+    for (int l = 0; l < c.lo.L; ++l) {
+      FwdLayerBufs& z = layer[l];
+      z.crp = z.crn = cr;
+      z.kv = c.wsb + c.ws.g_kv + (size_t)l * c.B * c.S * 2 * c.lo.H;
+      z.qkv = z.qc = z.act = big;
+      z.att1 = z.att2 = att;
+      z.lse1 = z.lse2 = z.h0 = z.h1 = z.h2 = nullptr;
+    }
+  }
+};
+
 // =========================================================================================================
 // GenericLauncher: the static interface of Launcher / Launcher16 on the run-time-shape kernels
 // =========================================================================================================
@@ -505,10 +542,16 @@ struct GenericLauncher {
     return EDTTS_OK;
   }
 
-  // context rows (token_emb gather or sem_proj) + context PE, then per layer kv_down -> kv_norm -> kv_up into the K|V cache
+  static int copy(hipStream_t st, float* dst, const float* src, size_t n) {
+    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return EDTTS_OK;
+  }
+
+  // context rows (token_emb gather or sem_proj) + context PE, then per layer kv_down -> kv_norm -> kv_up into the K|V rows
   // (per-utterance lengths: context rows past S_b are built from whatever the padding holds and are never read -- the attention reads
   // keys < S_b only, and every other step is row-local)
-  static int ctx(const CallCtx& cc, const int64_t* sem_idx, const float* sem_feat) {
+  static int ctx(const CallCtx& cc, const int64_t* sem_idx, const float* sem_feat) { return ctx(cc, FwdBufs(cc), sem_idx, sem_feat); }
+  static int ctx(const CallCtx& cc, const FwdBufs& fb, const int64_t* sem_idx, const float* sem_feat) {
     using namespace edtts_gen;
     const Layout& lo = cc.lo;
     const Workspace& ws = cc.ws;
@@ -516,7 +559,7 @@ struct GenericLauncher {
     float* wsb = cc.wsb;
     const hipStream_t st = cc.st;
     const int S = cc.S, rows = cc.B * S, H = lo.H, R = lo.R;
-    float* c = wsb + ws.g_ctx;
+    float* c = fb.ctx;
     if (sem_feat) {
       TRY_G(gemm<EPI_PE>(st, sem_feat, lo.SD, blob + lo.semp, blob + lo.semp_b, c, H, rows, H, lo.SD, blob + lo.cpe, S));
     } else {
@@ -528,14 +571,21 @@ struct GenericLauncher {
     }
     for (int l = 0; l < lo.L; ++l) {
       const LayerLayout& y = lo.layer[l];
-      TRY_G(gemm<EPI_BIAS>(st, c, H, blob + y.kvd, nullptr, wsb + ws.g_cr, R, rows, R, H));
-      TRY_G(norm<NORM_RMS>(st, wsb + ws.g_cr, wsb + ws.g_cr, rows, R, blob + y.kvn, nullptr, 1e-6f));
-      TRY_G(gemm<EPI_BIAS>(st, wsb + ws.g_cr, R, blob + y.kvu, nullptr, wsb + ws.g_kv + (size_t)l * rows * 2 * H, 2 * H, rows, 2 * H, R));
+      const FwdLayerBufs& z = fb.layer[l];
+      TRY_G(gemm<EPI_BIAS>(st, c, H, blob + y.kvd, nullptr, z.crp, R, rows, R, H));
+      TRY_G(norm<NORM_RMS>(st, z.crp, z.crn, rows, R, blob + y.kvn, nullptr, 1e-6f));
+      TRY_G(gemm<EPI_BIAS>(st, z.crn, R, blob + y.kvu, nullptr, z.kv, 2 * H, rows, 2 * H, R));
     }
     return EDTTS_OK;
   }
 
   static int forward(const CallCtx& c, const float* x, const float* cond_row, int cond_bstride, const StepTail& tail) {
+    return forward(c, FwdBufs(c), x, cond_row, cond_bstride, tail);
+  }
+  // drop non-null: the four dropout sites of every block run their masked instantiations (the attention outputs and the SwiGLU
+  // output in fb are then the dropped ones)
+  static int forward(const CallCtx& c, const FwdBufs& fb, const float* x, const float* cond_row, int cond_bstride, const StepTail& tail,
+                     const DropState* drop = nullptr) {
     using namespace edtts_gen;
     const Layout& lo = c.lo;
     const Workspace& ws = c.ws;
@@ -545,27 +595,36 @@ struct GenericLauncher {
     const Lens& ln = c.ln;
     const int B = c.B, T = c.T, S = c.S;
     const int M = B * T, H = lo.H, FH = lo.FM * lo.H, MEL = lo.MEL;
-    float *h = wsb + ws.h, *xn = wsb + ws.g_xn, *big = wsb + ws.g_big, *att = wsb + ws.g_att;
+    float *h = wsb + ws.h, *xn = wsb + ws.g_xn;
     const size_t row = (size_t)2 * 2 * H;  // one layer's (norm1 | norm3) AdaLN rows
+    auto snap = [&](float* dst) { return dst ? copy(st, dst, h, (size_t)M * H) : EDTTS_OK; };  // the residual stream as it stands
     TRY_G(gemm<EPI_PE>(st, x, MEL, blob + lo.inp, blob + lo.inp_b, h, H, M, H, MEL, blob + lo.pe, T));
     for (int l = 0; l < lo.L; ++l) {
       const LayerLayout& y = lo.layer[l];
-      const float* kv = wsb + ws.g_kv + (size_t)l * B * S * 2 * H;
+      const FwdLayerBufs& z = fb.layer[l];
+      DropArgs dra[4];
+      for (int i = 0; i < 4; ++i) dra[i] = drop ? drop->site(l, i) : DropArgs{};
+      auto D = [&](int i) -> const DropArgs* { return drop ? &dra[i] : nullptr; };
       // self-attention branch
+      TRY_G(snap(z.h0));
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
-      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, big, 3 * H, M, 3 * H, H));
-      TRY_G(attn(st, lo, B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, c.window, ln.t, ln.t, ln.t_dbl, ln.t_dbl));
-      TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
+      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, z.qkv, 3 * H, M, 3 * H, H));
+      TRY_G(attn(st, lo, B, z.qkv, 3 * H, z.qkv + H, z.qkv + 2 * H, 3 * H, z.att1, T, T, c.window, ln.t, ln.t, ln.t_dbl, ln.t_dbl, z.lse1,
+                 D(DROP_ATTN)));
+      TRY_G(gemm<EPI_RESID>(st, z.att1, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
       // cross-attention branch
+      TRY_G(snap(z.h1));
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
-      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, big, H, M, H, H));
-      TRY_G(attn(st, lo, B, big, H, kv, kv + H, 2 * H, att, T, S, -1, ln.t, ln.s, ln.t_dbl, false));
-      TRY_G(gemm<EPI_RESID>(st, att, H, blob + y.g_op, nullptr, h, H, M, H, H));
+      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, z.qc, H, M, H, H));
+      TRY_G(attn(st, lo, B, z.qc, H, z.kv, z.kv + H, 2 * H, z.att2, T, S, -1, ln.t, ln.s, ln.t_dbl, false, z.lse2, D(DROP_CROSS)));
+      TRY_G(gemm<EPI_RESID>(st, z.att2, H, blob + y.g_op, nullptr, h, H, M, H, H));
       // feed-forward branch
+      TRY_G(snap(z.h2));
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cond_bstride));
-      TRY_G(gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, big, FH, M, FH, H));
-      TRY_G(gemm<EPI_RESID>(st, big, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH));
+      TRY_G(gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, z.act, FH, M, FH, H, nullptr, 1, D(DROP_ACT)));
+      TRY_G(gemm<EPI_RESID>(st, z.act, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH, nullptr, 1, D(DROP_DOWN)));
     }
+    TRY_G(snap(fb.hL));
     TRY_G(norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
     float* e = tail.kind == TAIL_EPS ? tail.eps : wsb + ws.g_eps;
     TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, e, MEL, M, MEL, H));

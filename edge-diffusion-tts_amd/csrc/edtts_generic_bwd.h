@@ -746,14 +746,6 @@ static void make_train_scratch(const Layout& lo, int B, int T, int S, TrainScrat
   s->total = o;
 }
 
-// A validated EdttsDropout (include/edtts.h, "Dropout masks"): the key words, the threshold and the scale of the kept values.
-enum { DROP_ATTN = 0, DROP_CROSS = 1, DROP_ACT = 2, DROP_DOWN = 3 };
-struct DropState {
-  unsigned k0, k1, thr;
-  float scale;
-  DropArgs site(int layer, int site_id) const { return DropArgs{k0, k1, 0x30000u + 4u * (unsigned)layer + (unsigned)site_id, thr, scale}; }
-};
-
 // =========================================================================================================
 // TrainLauncher: forward with a tape, backward from it
 // =========================================================================================================
@@ -764,84 +756,30 @@ struct RowLens {
 };
 struct TrainLauncher {
   using G = GenericLauncher;
-  static int copy(hipStream_t st, float* dst, const float* src, size_t n) {
-    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return EDTTS_OK;
-  }
-
-  // GenericLauncher::ctx + GenericLauncher::forward (TAIL_EPS): the same launches in the same order; what the backward
-  // needs goes to the tape instead of the workspace, or is copied there.  The AdaLN rows are already in the tape (launch_cond).
+  // The generic forward with its intermediates in the tape: what the backward needs is written there directly, or copied there
+  // (the residual stream); kv_norm's output stays in the workspace.  The AdaLN rows are already in the tape (launch_cond).
   // Per-utterance lengths (c.ln) enter where they enter there: the embedding's padding ids, both attentions' key counts and query
   // skip, and eps zeroed past T_b -- so eps is bitwise edtts_decoder_forward_len's.  Tape rows past the lengths hold whatever the
   // row-local steps made of the padding (or nothing at all: skipped query blocks); the backward never loads them.
-  // drop non-null: the four dropout sites of every block run their masked instantiations (the tape's attention outputs and SwiGLU
-  // output are then the dropped ones); null: exactly the launches described above.
+  // drop non-null: the tape's attention outputs and SwiGLU output are the dropped ones.
   static int forward(const CallCtx& c, float* tp, const TrainTape& tt, const float* x, const int64_t* sem_idx, const float* sem_feat, float* eps,
                      const DropState* drop = nullptr) {
-    using namespace edtts_gen;
-    const Layout& lo = c.lo;
-    const Workspace& ws = c.ws;
-    const float* blob = c.blob;
-    float* wsb = c.wsb;
-    const hipStream_t st = c.st;
-    const Lens& ln = c.ln;
-    const int B = c.B, T = c.T, S = c.S, M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL;
-    float* cx = tp + tt.ctx;
-    if (sem_feat) {
-      TRY_G(G::gemm<EPI_PE>(st, sem_feat, lo.SD, blob + lo.semp, blob + lo.semp_b, cx, H, CS, H, lo.SD, blob + lo.cpe, S));
-    } else {
-      unsigned* err = ws.errp ? ws.errp : reinterpret_cast<unsigned*>(wsb + ws.err);
-      size_t nb = ((size_t)CS * H + 255) / 256;
-      if (nb > 4096) nb = 4096;
-      hipLaunchKernelGGL(k_gen_embed, dim3((unsigned)nb), dim3(256), 0, st, sem_idx, blob + lo.tok, blob + lo.cpe, cx, CS, S, H, lo.NTOK, err,
-                         ln.s);
-      LAUNCH_CHECK("k_gen_embed");
-    }
-    for (int l = 0; l < lo.L; ++l) {
-      const LayerLayout& y = lo.layer[l];
+    FwdBufs fb;
+    fb.ctx = tp + tt.ctx;
+    fb.hL = tp + tt.hL;
+    for (int l = 0; l < c.lo.L; ++l) {
       const TapeLayer& z = tt.layer[l];
-      TRY_G(G::gemm<EPI_BIAS>(st, cx, H, blob + y.kvd, nullptr, tp + z.crp, R, CS, R, H));
-      TRY_G(G::norm<NORM_RMS>(st, tp + z.crp, wsb + ws.g_cr, CS, R, blob + y.kvn, nullptr, 1e-6f));
-      TRY_G(G::gemm<EPI_BIAS>(st, wsb + ws.g_cr, R, blob + y.kvu, nullptr, tp + z.kv, 2 * H, CS, 2 * H, R));
+      FwdLayerBufs& f = fb.layer[l];
+      f.crp = tp + z.crp; f.crn = c.wsb + c.ws.g_cr; f.kv = tp + z.kv;
+      f.qkv = tp + z.qkv; f.att1 = tp + z.att1; f.lse1 = tp + z.lse1;
+      f.qc = tp + z.qc; f.att2 = tp + z.att2; f.lse2 = tp + z.lse2;
+      f.act = tp + z.act;
+      f.h0 = tp + z.h0; f.h1 = tp + z.h1; f.h2 = tp + z.h2;
     }
-    float *h = wsb + ws.h, *xn = wsb + ws.g_xn;
-    const float* cond_row = tp + tt.cond;
-    const int cond_bstride = lo.L * 4 * H;
-    const size_t row = (size_t)4 * H;
-    const size_t MH = (size_t)M * H;
-    TRY_G(G::gemm<EPI_PE>(st, x, MEL, blob + lo.inp, blob + lo.inp_b, h, H, M, H, MEL, blob + lo.pe, T));
-    for (int l = 0; l < lo.L; ++l) {
-      const LayerLayout& y = lo.layer[l];
-      const TapeLayer& z = tt.layer[l];
-      float *qkv = tp + z.qkv, *kv = tp + z.kv;
-      DropArgs dra[4];
-      for (int i = 0; i < 4; ++i) dra[i] = drop ? drop->site(l, i) : DropArgs{};
-      auto D = [&](int i) -> const DropArgs* { return drop ? &dra[i] : nullptr; };
-      TRY_G(copy(st, tp + z.h0, h, MH));
-      TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
-      TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, qkv, 3 * H, M, 3 * H, H));
-      TRY_G(G::attn(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, T, T, c.window, ln.t, ln.t, false, false, tp + z.lse1,
-                    D(DROP_ATTN)));
-      TRY_G(G::gemm<EPI_RESID>(st, tp + z.att1, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));
-      TRY_G(copy(st, tp + z.h1, h, MH));
-      TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
-      TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_qp, nullptr, tp + z.qc, H, M, H, H));
-      TRY_G(G::attn(st, lo, B, tp + z.qc, H, kv, kv + H, 2 * H, tp + z.att2, T, S, -1, ln.t, ln.s, false, false, tp + z.lse2,
-                    D(DROP_CROSS)));
-      TRY_G(G::gemm<EPI_RESID>(st, tp + z.att2, H, blob + y.g_op, nullptr, h, H, M, H, H));
-      TRY_G(copy(st, tp + z.h2, h, MH));
-      TRY_G(G::norm<NORM_RMS>(st, h, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cond_bstride));
-      TRY_G(G::gemm<EPI_SWIGLU>(st, xn, H, blob + y.g_up, blob + y.up_b, tp + z.act, FH, M, FH, H, nullptr, 1, D(DROP_ACT)));
-      TRY_G(G::gemm<EPI_RESID>(st, tp + z.act, FH, blob + y.g_down, blob + y.down_b, h, H, M, H, FH, nullptr, 1, D(DROP_DOWN)));
-    }
-    TRY_G(copy(st, tp + tt.hL, h, MH));
-    TRY_G(G::norm<NORM_LAYER>(st, h, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
-    TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + lo.s_outp, blob + lo.outp_b, eps, MEL, M, MEL, H));
-    if (ln.t) {
-      hipLaunchKernelGGL(k_gen_zero_past, dim3(G::grid_1d((size_t)M * MEL)), dim3(256), 0, st, eps, ln.t, 0, (size_t)M * MEL, T, MEL);
-      LAUNCH_CHECK("k_gen_zero_past");
-    }
-    return EDTTS_OK;
+    StepTail tail;
+    tail.eps = eps;
+    TRY_G(G::ctx(c, fb, sem_idx, sem_feat));
+    return G::forward(c, fb, x, tp + tt.cond, c.lo.L * 4 * c.lo.H, tail, drop);
   }
 
   // ---- backward helpers ----

@@ -546,6 +546,30 @@ __global__ __launch_bounds__(256) void k_sem_stats(const int* __restrict__ count
   }
 }
 
+// The start of an encode call, inference or training: `counts` zeroed, the kernel's arguments from the layout and the call's
+// pointers, and *blocks = its grid (0: no frames, nothing to launch).  The layout holds zeros in the other quantizer's fields
+// (sem_layout starts from SemLayout{}): an FSQ head gets vq = K = nrt_codes = 0 and no codebook offsets, a VQ head D = 0.
+static int enc_begin(const SemLayout& L, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx, float* z,
+                     float* z_q, int32_t* counts, hipStream_t st, EncArgs& a, unsigned* blocks) {
+  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)L.n_codes * sizeof(int32_t), st));
+  const int N = B * T;
+  *blocks = (unsigned)((N + kFrames - 1) / kFrames);
+  a.p = (const float*)packed;
+  a.h = h;
+  a.len = (const long long*)lengths;
+  a.idx = (long long*)idx;
+  a.z = z;
+  a.zq = z_q;
+  a.counts = counts;
+  a.N = N; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.kb1 = L.kb1; a.vq = L.vq; a.D = L.D; a.K = L.K;
+  a.nrt_codes = L.nrt_codes;
+  a.n_codes = L.n_codes;
+  a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
+  a.wd = L.wd; a.bd = L.bd; a.wu = L.wu; a.bu = L.bu; a.half = L.half; a.lev = L.lev; a.basis = L.basis;
+  a.cb = L.cb; a.cc = L.cc; a.cbraw = L.cbraw;
+  return EDTTS_OK;
+}
+
 }  // namespace edtts_sem
 
 extern "C" {
@@ -633,24 +657,11 @@ int edtts_sem_encode(const EdttsSemDims* dims, const void* packed, const float* 
   if (!packed || !h || !idx) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   if (B < 0 || T < 0 || (long long)B * T > 0x7fffffffLL - kFrames) return fail(EDTTS_ERR_ARG, "B=%d T=%d out of range", B, T);
   hipStream_t st = (hipStream_t)stream;
-  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)L.n_codes * sizeof(int32_t), st));
-  const int N = B * T;
-  if (N == 0) return EDTTS_OK;
   EncArgs a{};
-  a.p = (const float*)packed;
-  a.h = h;
-  a.len = (const long long*)lengths;
-  a.idx = (long long*)idx;
-  a.z = z;
-  a.zq = z_q;
-  a.counts = counts;
-  a.N = N; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.kb1 = L.kb1; a.vq = L.vq; a.D = L.D; a.K = L.K;
-  a.nrt_codes = L.nrt_codes;
-  a.n_codes = L.n_codes;
-  a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
-  a.wd = L.wd; a.bd = L.bd; a.wu = L.wu; a.bu = L.bu; a.half = L.half; a.lev = L.lev; a.basis = L.basis;
-  a.cb = L.cb; a.cc = L.cc; a.cbraw = L.cbraw;
-  hipLaunchKernelGGL(k_sem_encode<false>, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  unsigned blocks;
+  TRY_G(enc_begin(L, packed, h, B, T, lengths, idx, z, z_q, counts, st, a, &blocks));
+  if (blocks == 0) return EDTTS_OK;
+  hipLaunchKernelGGL(k_sem_encode<false>, dim3(blocks), dim3(256), 0, st, a);
   LAUNCH_CHECK("k_sem_encode");
   return EDTTS_OK;
 }

@@ -280,7 +280,7 @@ static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, 
 static int sem_train_dims(const EdttsSemDims* dims, const char* who, edtts_sem::SemLayout& L) {
   TRY_G(edtts_sem::sem_layout(dims, L));
   if (L.vq)
-    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training covers the FSQ quantizer only (the VQ path with its codebook loss and EMA update is not built)", who);
+    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training covers the FSQ quantizer only (a VQ head trains through edtts_sem_vq_*)", who);
   return EDTTS_OK;
 }
 // the head's one dropout site: stream word 0x40000 (include/edtts.h, "Philox stream ids")
@@ -294,6 +294,38 @@ static int sem_drop(const edtts_sem::SemLayout& L, const EdttsDropout* drop, con
 static int sem_shape(int B, int T) {
   if (B < 0 || T < 0 || (long long)B * T > 0x7fffffffLL - edtts_sem::kFrames) return fail(EDTTS_ERR_ARG, "B=%d T=%d out of range", B, T);
   return EDTTS_OK;
+}
+// No frames: every sum over frames is empty.  gs holds proj's six slots (only with a proj), then the quantizer's own, of `quant` floats.
+static int sem_zero_grads(hipStream_t st, const edtts_sem::SemLayout& L, float* const* gs, std::initializer_list<size_t> quant) {
+  const size_t S = L.S;
+  int i = 0;
+  auto zero = [&](size_t n) -> int {
+    if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n * sizeof(float), st));
+    ++i;
+    return EDTTS_OK;
+  };
+  if (L.in_dim)
+    for (size_t n : {S * L.in_dim, S, S, S, S * S, S}) TRY_G(zero(n));
+  for (size_t n : quant) TRY_G(zero(n));
+  return EDTTS_OK;
+}
+// proj's gradient sums over the M = B T frames that k_sem_bwd_frames left in `a`, in state-dict slot order (gs[0 .. 5])
+static int sem_proj_sums(hipStream_t st, const edtts_sem::SemLayout& L, const edtts_sem::SemBwdArgs& a, const float* h, int B, int T,
+                         float* const* gs, float* part) {
+  using TL = TrainLauncher;
+  const int S = L.S, M = B * T;
+  TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));  // proj.0.weight = dy1^T h
+  TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
+  if (gs[2] || gs[3]) {                                                  // LayerNorm gain = sum dam o x^, bias = sum dam
+    const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
+    edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<edtts_gen::NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
+    LAUNCH_CHECK("k_bwd_norm_cols");
+    if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
+    if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
+  }
+  TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));               // final Linear weight = dz^T a
+  return TL::colsum(st, a.dz, S, M, S, gs[5], part);
 }
 
 extern "C" {
@@ -368,30 +400,18 @@ int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const f
   TRY_G(sem_shape(B, T));
   if (!packed || !h || !idx || !tape) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   hipStream_t st = (hipStream_t)stream;
-  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)L.n_codes * sizeof(int32_t), st));
-  const int N = B * T;
-  if (N == 0) return EDTTS_OK;
   SemTape tt;
-  sem_tape(L, (size_t)N, tt);
+  sem_tape(L, (size_t)B * T, tt);
   float* tp = (float*)tape;
   EncTrainArgs a{};
-  a.p = (const float*)packed;
-  a.h = h;
-  a.len = (const long long*)lengths;
-  a.idx = (long long*)idx;
-  a.z = L.in_dim ? tp + tt.z : nullptr;
-  a.zq = z_q;
-  a.counts = counts;
-  a.N = N; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.kb1 = L.kb1; a.vq = 0; a.D = L.D; a.K = 0;
-  a.nrt_codes = 0;
-  a.n_codes = L.n_codes;
-  a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
-  a.wd = L.wd; a.bd = L.bd; a.wu = L.wu; a.bu = L.bu; a.half = L.half; a.lev = L.lev; a.basis = L.basis;
+  unsigned blocks;
+  TRY_G(enc_begin(L, packed, h, B, T, lengths, idx, L.in_dim ? tp + tt.z : nullptr, z_q, counts, st, a, &blocks));
+  if (blocks == 0) return EDTTS_OK;
   a.t_y1 = tp + tt.y1;
   a.t_zb = tp + tt.zb;
   a.dr = dr;
   a.dropping = dropping;
-  hipLaunchKernelGGL(k_sem_encode<true>, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_sem_encode<true>, dim3(blocks), dim3(256), 0, st, a);
   LAUNCH_CHECK("k_sem_encode<train>");
   return EDTTS_OK;
 }
@@ -414,13 +434,7 @@ int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void*
   hipStream_t st = (hipStream_t)stream;
   float* const* gs = reinterpret_cast<float* const*>(grad_slots);
   const int S = L.S, D = L.D, M = B * T, q = L.in_dim ? 6 : 0;
-  if (M == 0) {  // empty sums
-    const size_t n[10] = {(size_t)S * L.in_dim, (size_t)S, (size_t)S, (size_t)S, (size_t)S * S, (size_t)S,
-                          (size_t)D * S, (size_t)D, (size_t)S * D, (size_t)S};
-    for (int i = 0; i < want; ++i)
-      if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n[i + (L.in_dim ? 0 : 6)] * sizeof(float), st));
-    return EDTTS_OK;
-  }
+  if (M == 0) return sem_zero_grads(st, L, gs, {(size_t)D * S, (size_t)D, (size_t)S * D, (size_t)S});
   SemTrainLayout R;
   sem_train_layout(L, R);
   SemTape tt;
@@ -451,21 +465,7 @@ int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void*
   float* part = sc + ss.part;
   const float* G = lengths ? sc + ss.gm : d_zq;
   const float* z = L.in_dim ? tp + tt.z : h;
-  if (L.in_dim) {
-    TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));  // proj.0.weight = dy1^T h
-    TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
-    if (gs[2] || gs[3]) {                                                  // LayerNorm gain = sum dam o x^, bias = sum dam
-      using namespace edtts_gen;
-      const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
-      edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
-      LAUNCH_CHECK("k_bwd_norm_cols");
-      if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
-      if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
-    }
-    TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));               // final Linear weight = dz^T a
-    TRY_G(TL::colsum(st, a.dz, S, M, S, gs[5], part));
-  }
+  if (L.in_dim) TRY_G(sem_proj_sums(st, L, a, h, B, T, gs, part));
   TRY_G(TL::dw(st, a.du, 16, z, S, M, D, S, gs[q], part));                  // proj_down.weight = du^T z
   TRY_G(TL::colsum(st, a.du, 16, M, D, gs[q + 1], part));
   TRY_G(TL::dw(st, G, S, a.zql, 16, M, S, D, gs[q + 2], part));             // proj_up.weight = G^T zq_low
@@ -791,34 +791,22 @@ int edtts_sem_vq_encode_train(const EdttsSemDims* dims, const void* packed, cons
   const int N = B * T;
   if (!packed || !loss || (N > 0 && (!h || !idx || !z_q || !tape))) return fail(EDTTS_ERR_ARG, "NULL pointer argument");  // (no frames: nothing to point at)
   hipStream_t st = (hipStream_t)stream;
-  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)L.n_codes * sizeof(int32_t), st));
-  if (N == 0) {
+  SemVqTape tt;
+  sem_vq_tape(L, (size_t)N, tt);
+  float* tp = (float*)tape;  // (null only when there are no frames: every offset is then 0, and nothing is launched)
+  EncTrainArgs a{};
+  unsigned blocks;
+  TRY_G(enc_begin(L, packed, h, B, T, lengths, idx, L.in_dim ? tp + tt.z : nullptr, z_q, counts, st, a, &blocks));
+  if (blocks == 0) {
     HIP_TRY(hipMemsetAsync(loss, 0, sizeof(float), st));
     return EDTTS_OK;
   }
-  SemVqTape tt;
-  sem_vq_tape(L, (size_t)N, tt);
-  float* tp = (float*)tape;
-  EncTrainArgs a{};
-  a.p = (const float*)packed;
-  a.h = h;
-  a.len = (const long long*)lengths;
-  a.idx = (long long*)idx;
-  a.z = L.in_dim ? tp + tt.z : nullptr;
-  a.zq = z_q;
-  a.counts = counts;
-  a.N = N; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.kb1 = L.kb1; a.vq = 1; a.D = 0; a.K = L.K;
-  a.nrt_codes = L.nrt_codes;
-  a.n_codes = L.n_codes;
-  a.w1 = L.w1; a.b1 = L.b1; a.lng = L.lng; a.lnb = L.lnb; a.w3 = L.w3; a.b3 = L.b3;
-  a.cb = L.cb; a.cc = L.cc; a.cbraw = L.cbraw;
   a.t_y1 = tp + tt.y1;
-  a.t_zb = nullptr;
   a.t_r = tp + tt.r;
   a.t_sq = tp + tt.sq;
   a.dr = dr;
   a.dropping = dropping;
-  hipLaunchKernelGGL(k_sem_encode<true>, dim3((N + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_sem_encode<true>, dim3(blocks), dim3(256), 0, st, a);
   LAUNCH_CHECK("k_sem_encode<train, vq>");
   hipLaunchKernelGGL(k_sem_vq_loss, dim3(1), dim3(256), 0, st, tp + tt.sq, N, (const long long*)lengths, B, T, L.S, (float)commit, training,
                      loss);
@@ -854,7 +842,6 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
                           const int64_t* idx, int B, int T, const int64_t* lengths, const float* d_zq, const float* d_loss, double commit,
                           void* const* grad_slots, int n_slots, float* d_z, void* scratch, const EdttsDropout* drop, void* stream) {
   using namespace edtts_sem;
-  using TL = TrainLauncher;
   SemLayout L;
   TRY_G(sem_vq_dims(dims, "edtts_sem_vq_backward", L));
   TRY_G(sem_vq_commit(commit, "edtts_sem_vq_backward"));
@@ -870,12 +857,7 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
     return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   hipStream_t st = (hipStream_t)stream;
   float* const* gs = reinterpret_cast<float* const*>(grad_slots);
-  if (M == 0) {  // empty sums
-    const size_t n[7] = {(size_t)S * L.in_dim, (size_t)S, (size_t)S, (size_t)S, (size_t)S * S, (size_t)S, (size_t)L.K * S};
-    for (int i = 0; i < want; ++i)
-      if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n[i + (L.in_dim ? 0 : 6)] * sizeof(float), st));
-    return EDTTS_OK;
-  }
+  if (M == 0) return sem_zero_grads(st, L, gs, {(size_t)L.K * S});
   SemVqTape tt;
   sem_vq_tape(L, (size_t)M, tt);
   SemVqScratch ss;
@@ -902,22 +884,7 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
     a.dropping = dropping;
     hipLaunchKernelGGL(k_sem_bwd_frames<true>, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
     LAUNCH_CHECK("k_sem_bwd_frames<vq>");
-    float* part = sc + ss.part;
-    if (L.in_dim) {  // the sums over frames, in state-dict slot order (as edtts_sem_backward)
-      TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));
-      TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
-      if (gs[2] || gs[3]) {
-        using namespace edtts_gen;
-        const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
-        edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
-        hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
-        LAUNCH_CHECK("k_bwd_norm_cols");
-        if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
-        if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
-      }
-      TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));
-      TRY_G(TL::colsum(st, a.dz, S, M, S, gs[5], part));
-    }
+    if (L.in_dim) TRY_G(sem_proj_sums(st, L, a, h, B, T, gs, sc + ss.part));
   }
   if (gs[q]) {  // d codebook = coef[1] sum_{m: idx[m] = k} r_m: the decoder's gradient never reaches the codebook
     const size_t n = (size_t)L.K * S;

@@ -86,6 +86,15 @@ def _flat3(z: torch.Tensor, width: int, name: str) -> torch.Tensor:
     return z.float().reshape(1, -1, width)
 
 
+def _train_input(h: torch.Tensor, lengths: Optional[torch.Tensor]):
+    """(x, B, T): a training forward's input as the kernels take it -- detached, fp32, aligned, rows past the lengths zeroed."""
+    x = native._aligned(h.detach().float())
+    B, T = x.shape[0], x.shape[1]
+    if lengths is not None and B * T:  # the weight-gradient products multiply the rows past the lengths by zeros: make them finite
+        x = x.masked_fill((torch.arange(T, device=x.device)[None, :] >= lengths.clamp(1, T)[:, None])[..., None], 0.0)
+    return x, B, T
+
+
 class _SemGrad(torch.autograd.Function):
     """(z_q, idx, counts) of a head on the training forward (edtts_sem_encode_train); backward through edtts_sem_backward.  The tape
     is a tensor of this call's own, saved in ctx; ``drop`` (None or this call's (p, seed)) lives in ctx too, so the backward
@@ -96,10 +105,7 @@ class _SemGrad(torch.autograd.Function):
         slots = owner._slots()
         blob = owner._pack.get(dims, slots)
         tblob = owner._tpack.get(dims, slots)
-        x = native._aligned(h.detach().float())
-        B, T = x.shape[0], x.shape[1]
-        if lengths is not None and B * T:  # the weight-gradient products multiply the rows past the lengths by zeros: make them finite
-            x = x.masked_fill((torch.arange(T, device=x.device)[None, :] >= lengths.clamp(1, T)[:, None])[..., None], 0.0)
+        x, B, T = _train_input(h, lengths)
         tape = torch.empty(native.sem_train_tape_bytes(dims, B, T), dtype=torch.uint8, device=x.device)
         idx, zq, counts = native.sem_encode_train(dims, blob, x, tape, lengths, True, drop)
         ctx.owner, ctx.dims, ctx.lengths, ctx.drop, ctx.sig = owner, dims, lengths, drop, (owner._pack.sig, owner._tpack.sig)
@@ -136,10 +142,7 @@ class _VQGrad(torch.autograd.Function):
         slots = owner._slots()
         blob = owner._pack.get(dims, slots)
         tblob = owner._tpack.get(dims, slots)
-        x = native._aligned(h.detach().float())
-        B, T = x.shape[0], x.shape[1]
-        if lengths is not None and B * T:  # the weight-gradient products multiply the rows past the lengths by zeros: make them finite
-            x = x.masked_fill((torch.arange(T, device=x.device)[None, :] >= lengths.clamp(1, T)[:, None])[..., None], 0.0)
+        x, B, T = _train_input(h, lengths)
         training = bool(vq.training)
         commit = float(vq.commit)
         tape = torch.empty(native.sem_vq_tape_bytes(dims, B, T), dtype=torch.uint8, device=x.device)
