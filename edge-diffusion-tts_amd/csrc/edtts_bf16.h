@@ -46,10 +46,10 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 namespace edtts16 {
 using namespace edtts;
 
-// NF_ = 16-frame tiles per wave.  NF = 2: four waves per block (one per SIMD, up to 512 registers each).  NF = 1: EIGHT waves per
-// block, two per SIMD (<= 256 registers each): one wave's waits and softmax arithmetic run under the other's MFMAs -- with one
-// wave per SIMD 27 % of the cycles were s_waitcnt time and 24 % issue stalls -- at the price of LDS bandwidth (every wave reads
-// every weight fragment: 8 KiB per fragment and block).
+// NF_ = 16-frame tiles per wave.  NF = 2: four waves per block (one per SIMD, up to 512 registers each).  NF = 1: W1 = 4 waves per
+// block too, two independent blocks per CU: the launcher's choice for small grids (Launcher16::HAS_SMALL).  (The eight-wave NF = 1
+// block -- two waves per SIMD, <= 256 registers each -- was measured and rejected: the ring's barrier keeps them in lockstep,
+// DESIGN.md 4.5.)
 template <int H_, int HEADS_, int MEL_, int NF_ = 2>
 struct Cfg16 {
   static constexpr int H = H_, HEADS = HEADS_, MEL = MEL_, NF = NF_;
@@ -62,23 +62,17 @@ struct Cfg16 {
   static constexpr int MTP = (MT + 1) / 2;      // n-tile PAIRS of the mel dim (the last one may be half empty)
   static constexpr int R = H / 2;
   static constexpr int VR = H;                  // rows of a v^T buffer
-#ifndef EDTTS16_W1
-#define EDTTS16_W1 4   // waves per block of the NF = 1 variant: 8 = one block per CU, two waves per SIMD in lockstep; 4 = two independent blocks per CU
-#endif
-  static constexpr int WAVES = NF == 1 ? EDTTS16_W1 : 4, THREADS = 64 * WAVES;
+  static constexpr int W1 = 4;  // waves per block of the NF = 1 variant: 8 = one block per CU, two waves per SIMD in lockstep; 4 = two independent blocks per CU
+  static constexpr int WAVES = NF == 1 ? W1 : 4, THREADS = 64 * WAVES;
   // (the eight-wave NF = 1 block is the two-waves-per-SIMD experiment: 256 registers each; the four-wave one -- the run-time choice
   // for small grids -- keeps the whole register file: under a 256-register cap it spills to scratch)
   static constexpr int MIN_WAVES_PER_SIMD = (NF == 1 && WAVES == 8) ? 2 : 1;
   // Weight stream: every GEMM unit of the kernels (an n-tile pair over all k-tiles, or one k-tile over all n-tiles) consumes
   // exactly PH = HT fragments (1 KiB each) -- one PHASE.  The block shares one LDS ring of NS phase slots (see LdsRing).
   static constexpr int PH = HT;                 // fragments per phase
-#ifndef EDTTS16_QLDS
-#define EDTTS16_QLDS 1   // cross-attention q of all heads parked in LDS (1) or in the wave's rows of the q buffer (0)
-#endif
   // cross-attention q operands of a wave's frames, all heads: [head][frame tile][lane] x 16 B -- written once after the q
   // projection, read back head by head (64 registers less during the cross-attention; the ring gives up one slot for it)
-  static constexpr bool QLDS = EDTTS16_QLDS;
-  static constexpr int QLDS_BYTES = QLDS ? WAVES * HEADS * NF * 1024 : 0;
+  static constexpr int QLDS_BYTES = WAVES * HEADS * NF * 1024;
   static constexpr int NS_MAX = (NF == 1 && WAVES == 4) ? 4 : 6;  // ring slots (phases): NS - 1 phases are in flight ahead of the consumers
   static constexpr int UPB_FLOATS = 8 * H;          // room for the FFN up bias at the largest ffn_mult (4): 2 * 4 * H floats
   static constexpr int PARAM_FLOATS = UPB_FLOATS + MEL;  // FFN up bias (stream order) + out_proj bias, staged in LDS (see k_layer16)
@@ -113,24 +107,15 @@ EDTTS_DEV bf8 ldg_bf8(const __bf16* base, unsigned byte_off) {
 // Private images.  The residual tile h (fp32) and the q rows (bf16) of a wave's frames are written and read back only by the wave
 // that owns those frames, lane for lane -- so inside the tile's span of the buffer they are stored as the REGISTER IMAGE,
 // [n-tile | head][frame tile][lane] x 16 bytes: every access of a wave is one contiguous KiB instead of 16 row segments of 64 B.
-// (EDTTS16_IMG 0: row-major [frame][H], as the fp32 kernels keep them.)  tile0 = ((b * Tp + m0) * H: the span starts where the
-// row-major rows of the tile would.
-#ifndef EDTTS16_IMG
-#define EDTTS16_IMG 1
-#endif
+// tile0 = ((b * Tp + m0) * H: the span starts where the row-major rows of the tile would.
 template <class C>
 EDTTS_DEV size_t h_at(size_t tile0, int lane, int nt, int ft) {  // floats
-  if (EDTTS16_IMG) return tile0 + (size_t)(nt * C::NF + ft) * 256 + lane * 4;
-  return tile0 + (size_t)((lane & 15) + 16 * ft) * C::H + 16 * nt + 4 * (lane >> 4);
+  return tile0 + (size_t)(nt * C::NF + ft) * 256 + lane * 4;
 }
 template <class C>
 EDTTS_DEV size_t q_at(size_t tile0, int lane, int hd, int ft) {  // bf16 elements
-  if (EDTTS16_IMG) return tile0 + (size_t)(hd * C::NF + ft) * 512 + lane * 8;
-  return tile0 + (size_t)((lane & 15) + 16 * ft) * C::H + hd * C::DH + 8 * (lane >> 4);
+  return tile0 + (size_t)(hd * C::NF + ft) * 512 + lane * 8;
 }
-// (the same as a per-lane byte offset + a wave-uniform byte offset, for buffer loads / stores from the tile's base)
-template <class C> EDTTS_DEV unsigned q_voff(int lane) { return EDTTS16_IMG ? lane * 16u : (unsigned)((lane & 15) * C::H + 8 * (lane >> 4)) * 2u; }
-template <class C> EDTTS_DEV unsigned q_soff(int hd, int ft) { return EDTTS16_IMG ? (unsigned)(hd * C::NF + ft) * 1024u : (unsigned)(ft * 16 * C::H + hd * C::DH) * 2u; }
 
 // ---------------------------------------------------------------------------------------------------------
 // Block-shared weight ring in LDS.  At bf16 rate a 1-KiB fragment feeds only 2 MFMAs = 32 cycles of one wave: four waves
@@ -170,12 +155,8 @@ struct LdsRing {
     static_assert(SHARE * (NS - 2) <= 63, "vmcnt immediate");
     // all but the SHARE * (NS - 2) youngest vector-memory operations done => the DMAs of phase `next` (and everything older) landed
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SHARE * (NS - 2)) : "memory");
-#ifndef EDTTS16_ABLATE_BARRIER  // timing ablations only (results wrong by construction)
     __builtin_amdgcn_s_barrier();
-#endif
-#ifndef EDTTS16_ABLATE_DMA
     issue(next + NS - 1);
-#endif
     const f4* p = lds + (next % NS) * PH * 64 + lane;
     ++next;
     return p;
@@ -400,31 +381,14 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
     c = clampc(c);
     return c < 32 && ((imask >> c) & 1u) != 0u;
   };
-  auto mask_init = [&](int c, f4 (&S)[2][NF], const float (&vis)[NF]) {
-    c = clampc(c);
-    const int k0 = (kt_lo + 2 * c) << 4;
-#pragma unroll
-    for (int ft = 0; ft < NF; ++ft) {
-      const int d0 = k0 + 4 * g - (m0 + 16 * ft + fq) - lo_d[ft];
-      const unsigned sp = span[ft] >= 0 ? (unsigned)span[ft] : 0u;
-      const int bias = span[ft] >= 0 ? 0 : (1 << 30);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) S[t][ft][r] = (unsigned)(d0 + bias + 16 * t + r) <= sp ? vis[ft] : NEG_INF;
-    }
-  };
   // step s = 0: the diagonal chunk; steps 1 .. nchunk-1: the other chunks in ascending order
   auto chunk_of = [&](int st) { return st >= nchunk ? nchunk - 1 : (st == 0 ? cdiag : (st <= cdiag ? st - 1 : st)); };
 
-#ifndef EDTTS16_HP
-#define EDTTS16_HP 2   // heads per attention step (1: the single-head step below)
-#endif
-#if EDTTS16_HP == 2
   // TWO HEADS PER STEP.  Both heads of a pair walk the same chunks with the same masks, so the interior test, the mask predicates,
   // the loop control and the rescale branch are paid once per 2 x 16 scores, and the step holds two independent
   // MFMA -> exp2 -> pack -> MFMA chains for the scheduler to interleave: with one wave per SIMD nothing else hides their latencies
-  // (stand-alone attention, 4.5: a second instruction stream per SIMD is worth 1.45x).
+  // (stand-alone attention, 4.5: a second instruction stream per SIMD is worth 1.45x).  (The single-head step, with K / V^T prefetch
+  // depth 2 or 4, measured 44.3 - 45.0 ms per call: DESIGN.md 4.5.)
   constexpr int HP = 2;
   static_assert(C::HEADS % HP == 0, "head pairs");
   constexpr int KD = 2;  // K / V^T tiles are requested KD steps ahead into KD register buffer sets
@@ -441,15 +405,11 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
     }
   };
   prefetch(0);
-  // EDTTS16_MFMA_SUM (round 4): the softmax row sums come out of the matrix pipe -- one more MFMA per head and query tile and step with an
+  // Round 4: the softmax row sums come out of the matrix pipe -- one more MFMA per head and query tile and step with an
   // all-ones A operand leaves sum_k P[k][query] in every C/D register of the lane's query -- instead of 8 v_add per head and tile (the
   // partial sums and their accumulation) plus the sum-based rescale test; the test reads the scores' maximum (v_max3 chains) instead.
   // The step is bound by its VALU issue, the MFMA pipe idles three quarters of it.  The sums are those of the bf16-rounded P the P V
   // product itself uses.
-#ifndef EDTTS16_MFMA_SUM
-#define EDTTS16_MFMA_SUM 1
-#endif
-  constexpr bool MSUM = EDTTS16_MFMA_SUM;
   f4 ones_bits = as_f4(bf8{(__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f});
   asm volatile("" : "+a"(ones_bits));  // four AGPRs for the life of the attention (an MFMA's A operand may be an AGPR)
   for (int hd = 0; hd < C::HEADS; hd += HP) {
@@ -465,7 +425,7 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
     auto step = [&](bool first, int c, int cnext2, bf8 (&KA)[HP][2], bf8 (&VA)[HP][2]) {
       if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
       f4 S[HP][2][NF];
-      const bool dummy = c < 0;  // (EDTTS16_EVEN_STEPS: the padding step of an odd step count: every position masked)
+      const bool dummy = c < 0;  // (the padding step of an odd step count: every position masked)
       if (dummy) c = nchunk - 1;
       if (!dummy && chunk_is_interior(c)) {
 #pragma unroll
@@ -502,13 +462,12 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
 #pragma unroll
       for (int h = 0; h < HP; ++h) load_k(hd + h, cnext2, KA[h]);  // (re-reads a valid tile past the last step)
       if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
-      f4 P[HP][2][NF], ps[HP][NF];
-      auto exp_and_sum = [&](int h, int ft, float m) {
+      f4 P[HP][2][NF];
+      auto exp_scores = [&](int h, int ft, float m) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) P[h][t][ft][r] = fast_exp2(S[h][t][ft][r] - m);
-        if constexpr (!MSUM) ps[h][ft] = P[h][0][ft] + P[h][1][ft];
       };
       if (first) {
 #pragma unroll
@@ -523,40 +482,26 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
             nm[h][ft] = -m;
             NM[h][ft] = splat(-m);
             asm volatile("" : "+a"(NM[h][ft]));  // the -m tile lives in AGPRs: it is an accumulator input and nothing else (else 16 v_accvgpr_write per step)
-            exp_and_sum(h, ft, m);
+            exp_scores(h, ft, m);
           }
       } else {
-        const float lim = 4294967296.f;  // 2^32 (kDefer)
-        // one test for the whole step: all probabilities are >= 0, so the sum over both heads and query tiles exceeds the limit
-        // (or is not finite) whenever one row's does -- a false positive only moves reference points early
-        bool over;
-        if constexpr (MSUM) {
-          float mx = S[0][0][0][0];  // some score above its reference point by more than 32 octaves <=> some P > 2^32
+        // one test for the whole step, on the maximum over both heads and query tiles: some score above its reference point by
+        // more than 32 octaves (kDefer) <=> some P > 2^32 -- a false positive only moves reference points early
+        float mx = S[0][0][0][0];
 #pragma unroll
-          for (int h = 0; h < HP; ++h)
+        for (int h = 0; h < HP; ++h)
 #pragma unroll
-            for (int ft = 0; ft < NF; ++ft) {
-              exp_and_sum(h, ft, 0.f);
+          for (int ft = 0; ft < NF; ++ft) {
+            exp_scores(h, ft, 0.f);
 #pragma unroll
-              for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, S[h][t][ft][r]);
-            }
-          over = !(mx <= 32.f);
-          (void)lim;
-        } else {
-          f4 tot = splat(0.f);
-#pragma unroll
-          for (int h = 0; h < HP; ++h)
-#pragma unroll
-            for (int ft = 0; ft < NF; ++ft) {
-              exp_and_sum(h, ft, 0.f);
-              tot += ps[h][ft];
-            }
-          over = !(hsum(tot) <= lim);
-        }
+              for (int r = 0; r < 4; ++r) mx = fmaxf(mx, S[h][t][ft][r]);
+          }
+        const bool over = !(mx <= 32.f);
         if (__any(over)) {
-          // rare path (inputs through a volatile asm: see the single-head step)
+          // Rare path.  Its inputs pass through a volatile asm: hipcc otherwise executes the whole path speculatively in EVERY step
+          // (if-conversion: the ISA showed 32 v_exp, 24 v_max and 16 v_sub per step instead of 16 / 0 / 0).
           f4 T[HP][2][NF];
 #pragma unroll
           for (int h = 0; h < HP; ++h)
@@ -586,7 +531,6 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
               for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) P[h][t][ft][r] = fast_exp2(T[h][t][ft][r] - dl);
-              if constexpr (!MSUM) ps[h][ft] = P[h][0][ft] + P[h][1][ft];
             }
         }
       }
@@ -594,10 +538,7 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
 #pragma unroll
       for (int h = 0; h < HP; ++h)
 #pragma unroll
-        for (int ft = 0; ft < NF; ++ft) {
-          if constexpr (!MSUM) lvec[h][ft] += ps[h][ft];
-          pb[h][ft] = pack8(P[h][0][ft], P[h][1][ft]);
-        }
+        for (int ft = 0; ft < NF; ++ft) pb[h][ft] = pack8(P[h][0][ft], P[h][1][ft]);
       if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
@@ -605,12 +546,10 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
         for (int ft = 0; ft < NF; ++ft)
 #pragma unroll
           for (int h = 0; h < HP; ++h) O[h][dt][ft] = EDTTS_MFMA16(VA[h][dt], pb[h][ft], O[h][dt][ft]);
-      if constexpr (MSUM) {
 #pragma unroll
-        for (int ft = 0; ft < NF; ++ft)
+      for (int ft = 0; ft < NF; ++ft)
 #pragma unroll
-          for (int h = 0; h < HP; ++h) lvec[h][ft] = EDTTS_MFMA16(as_bf8(ones_bits), pb[h][ft], lvec[h][ft]);
-      }
+        for (int h = 0; h < HP; ++h) lvec[h][ft] = EDTTS_MFMA16(as_bf8(ones_bits), pb[h][ft], lvec[h][ft]);
 #pragma unroll
       for (int h = 0; h < HP; ++h) load_v(hd + h, cnext2, VA[h]);
       if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
@@ -621,22 +560,16 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
     // (Measured before: the conditional step computed under its condition with its requests made unconditional: no gain;
     // unconditional step pairs plus a tail step, a fourth copy of the step: 53.6 ms, 202 spilled registers.)
     step(true, chunk_of(0), chunk_of(KD), KA0, VA0);
-#ifndef EDTTS16_EVEN_STEPS
-#define EDTTS16_EVEN_STEPS 1   // 1: padded step pairs; 0: never
-#endif
-    constexpr bool EVEN = EDTTS16_EVEN_STEPS != 0;
     for (int st = 1; st < nchunk; st += 2) {
       step(false, chunk_of(st), chunk_of(st + 2), KA1, VA1);
-      // EVEN: always two steps per iteration (no branch around a load): a step past the end runs fully masked
-      if constexpr (EVEN) step(false, st + 1 < nchunk ? chunk_of(st + 1) : -1, chunk_of(st + 3), KA0, VA0);
-      else if (st + 1 < nchunk) step(false, chunk_of(st + 1), chunk_of(st + 3), KA0, VA0);
+      step(false, st + 1 < nchunk ? chunk_of(st + 1) : -1, chunk_of(st + 3), KA0, VA0);  // (-1: past the end, fully masked)
     }
     bf8 ob[HP][NF];
 #pragma unroll
     for (int h = 0; h < HP; ++h)
 #pragma unroll
       for (int ft = 0; ft < NF; ++ft) {
-        const float lt = MSUM ? lvec[h][ft][0] : group_sum(hsum(lvec[h][ft]));  // (MSUM: every C/D row holds the query's total)
+        const float lt = lvec[h][ft][0];  // (every C/D row holds the query's total)
         const float inv = lt > 0.f ? 1.0f / lt : 0.f;
         ob[h][ft] = pack8(O[h][0][ft] * inv, O[h][1][ft] * inv);
       }
@@ -644,164 +577,6 @@ EDTTS_DEV void attention16(QF&& qf, const __bf16* __restrict__ Kb, const __bf16*
 #pragma unroll
     for (int h = 0; h < HP; ++h) sink(hd + h, ob[h]);
   }
-#else
-#ifndef EDTTS16_KVDEPTH
-#define EDTTS16_KVDEPTH 2
-#endif
-  // K / V^T operands are requested EDTTS16_KVDEPTH steps ahead into as many register buffers (2; 4 is a build option).  In-kernel
-  // stamps (scratch/stamps_bf16.py) show some steps waiting 1 000 - 2 000 cycles for their tiles at either depth, and the call time
-  // is the same (44.3 - 45.0 ms): the extra 32 registers of depth 4 cost in accumulator moves what the distance gains.
-  constexpr int KD = EDTTS16_KVDEPTH;
-  static_assert(KD == 2 || KD == 4, "K/V prefetch depth");
-  bf8 KA0[2], VA0[2], KA1[2], VA1[2], KA2[2], VA2[2], KA3[2], VA3[2], q[NF];
-  auto prefetch = [&](int hd) {
-#pragma unroll
-    for (int ft = 0; ft < NF; ++ft) q[ft] = qf(hd, ft);
-    load_k(hd, chunk_of(0), KA0);
-    load_v(hd, chunk_of(0), VA0);
-    load_k(hd, chunk_of(1), KA1);
-    load_v(hd, chunk_of(1), VA1);
-    if (KD == 4) {
-      load_k(hd, chunk_of(2), KA2);
-      load_v(hd, chunk_of(2), VA2);
-      load_k(hd, chunk_of(3), KA3);
-      load_v(hd, chunk_of(3), VA3);
-    }
-  };
-  prefetch(0);
-  for (int hd = 0; hd < C::HEADS; ++hd) {
-    f4 O[2][NF], lvec[NF], NM[NF];
-    float nm[NF];
-#pragma unroll
-    for (int ft = 0; ft < NF; ++ft) {
-      O[0][ft] = O[1][ft] = lvec[ft] = NM[ft] = splat(0.f);
-      nm[ft] = 0.f;
-    }
-    auto step = [&](bool first, int c, int cnext2, bf8 (&KA)[2], bf8 (&VA)[2]) {
-      if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
-      f4 S[2][NF];
-      if (chunk_is_interior(c)) {
-        // the reference tile rides in as the C operand itself (written as S = NM; S = mfma(.., S) it cost 16 accumulator moves
-        // and as many reads per step); first step: NM = 0
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int ft = 0; ft < NF; ++ft) S[t][ft] = EDTTS_MFMA16(KA[t], q[ft], NM[ft]);
-      } else {
-        mask_init(c, S, nm);  // first step: nm = 0
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int ft = 0; ft < NF; ++ft) S[t][ft] = EDTTS_MFMA16(KA[t], q[ft], S[t][ft]);
-      }
-      load_k(hd, cnext2, KA);  // (re-reads a valid tile past the last step)
-      if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
-      f4 P[2][NF], ps[NF];
-      auto lane_max = [&](int ft) {
-        f4 mv = S[0][ft];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mv[r] = fmaxf(mv[r], S[1][ft][r]);
-        return hmax(mv);
-      };
-      auto exp_and_sum = [&](int ft, float m) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) P[t][ft][r] = fast_exp2(S[t][ft][r] - m);
-        ps[ft] = P[0][ft] + P[1][ft];
-      };
-      if (first) {
-#pragma unroll
-        for (int ft = 0; ft < NF; ++ft) {
-          const float gm = group_max(lane_max(ft));
-          const float m = gm > -1e30f ? gm : 0.f;
-          nm[ft] = -m;
-          NM[ft] = splat(-m);
-          exp_and_sum(ft, m);
-        }
-      } else {
-        const float lim = 4294967296.f;  // 2^32 (kDefer)
-        bool over = false;
-#pragma unroll
-        for (int ft = 0; ft < NF; ++ft) {
-          exp_and_sum(ft, 0.f);
-          over = over || !(hsum(ps[ft]) <= lim);
-        }
-        if (__any(over)) {
-          // Rare path.  Its inputs pass through a volatile asm: hipcc otherwise executes the whole path speculatively in EVERY step
-          // (if-conversion: the ISA showed 32 v_exp, 24 v_max and 16 v_sub per step instead of 16 / 0 / 0).
-          f4 T[2][NF];
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int ft = 0; ft < NF; ++ft) {
-              T[t][ft] = S[t][ft];
-              asm volatile("" : "+v"(T[t][ft]));
-            }
-#pragma unroll
-          for (int ft = 0; ft < NF; ++ft) {
-            f4 mv = T[0][ft];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mv[r] = fmaxf(mv[r], T[1][ft][r]);
-            const float dl = fmaxf(0.f, group_max(hmax(mv)));
-            const float alpha = fast_exp2(-dl);
-            nm[ft] -= dl;
-            NM[ft] = splat(nm[ft]);
-            lvec[ft] *= alpha;
-            O[0][ft] *= alpha;
-            O[1][ft] *= alpha;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) P[t][ft][r] = fast_exp2(T[t][ft][r] - dl);
-            ps[ft] = P[0][ft] + P[1][ft];
-          }
-        }
-      }
-      bf8 pb[NF];
-#pragma unroll
-      for (int ft = 0; ft < NF; ++ft) {
-        lvec[ft] += ps[ft];
-        pb[ft] = pack8(P[0][ft], P[1][ft]);
-      }
-      if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int ft = 0; ft < NF; ++ft) O[dt][ft] = EDTTS_MFMA16(VA[dt], pb[ft], O[dt][ft]);
-      load_v(hd, cnext2, VA);
-      if (hd == EDTTS_STAMP_HEAD) STAMPX16(stamps, sidx++);
-    };
-    // (Measured alternatives, same device: groups of KD unconditional steps + a load-free tail so that hipcc's waitcnt pass sees
-    // the same number of outstanding loads on every path -- KD=2: 50.1 ms, KD=4: 46.2 ms against 45.7 ms for this loop; fully
-    // unrolled 16-step runs: 59 ms (spills); a skewed step that issues the score MFMAs of chunk s+1 ahead of the softmax of chunk s
-    // (matrix pipe under the VALU clump): 47.2 ms -- its 16 extra accumulators cost more in AGPR<->VGPR moves than the overlap
-    // gains.  The step is bound by its instruction count at one wave per SIMD, not by the distance of its loads.)
-    step(true, chunk_of(0), chunk_of(KD), KA0, VA0);
-    if (KD == 2) {
-      for (int st = 1; st < nchunk; st += 2) {
-        step(false, chunk_of(st), chunk_of(st + 2), KA1, VA1);
-        if (st + 1 < nchunk) step(false, chunk_of(st + 1), chunk_of(st + 3), KA0, VA0);
-      }
-    } else {
-      for (int st = 1; st < nchunk; st += 4) {
-        step(false, chunk_of(st), chunk_of(st + 4), KA1, VA1);
-        if (st + 1 < nchunk) step(false, chunk_of(st + 1), chunk_of(st + 5), KA2, VA2);
-        if (st + 2 < nchunk) step(false, chunk_of(st + 2), chunk_of(st + 6), KA3, VA3);
-        if (st + 3 < nchunk) step(false, chunk_of(st + 3), chunk_of(st + 7), KA0, VA0);
-      }
-    }
-    bf8 ob[NF];
-#pragma unroll
-    for (int ft = 0; ft < NF; ++ft) {
-      const float lt = group_sum(hsum(lvec[ft]));
-      const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-      ob[ft] = pack8(O[0][ft] * inv, O[1][ft] * inv);
-    }
-    if (hd + 1 < C::HEADS) prefetch(hd + 1);
-    sink(hd, ob);
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -922,11 +697,6 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_prologue1
 // =========================================================================================================
 // transformer layer kernel (bf16 contractions)
 // =========================================================================================================
-// (register-pressure probes: -DEDTTS_EXPERIMENTS -DEDTTS16_PHASES=<mask> compiles only the masked phases of the layer -- 1 self-attention,
-// 2 cross-attention, 4 FFN, 8 tail; results wrong by construction)
-#ifndef EDTTS16_PHASES
-#define EDTTS16_PHASES 15
-#endif
 template <class C, int TAIL>
 __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) f4 ring_lds16[];
@@ -965,7 +735,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
   }
   STAMP16(0);
   // ---- x = x + attn(norm1(x, cond))   (transformer.py:142-146; q / k / v^T were produced by the previous kernel) ----
-  if (EDTTS16_PHASES & 1) {
+  {
     const __bf16* qbase = reinterpret_cast<const __bf16*>(a.q);
     auto qf = [&](int hd, int ft) { return *reinterpret_cast<const bf8*>(qbase + q_at<C>(tile0, lane, hd, ft)); };
     attention16<C, true>(qf, reinterpret_cast<const __bf16*>(a.k) + (size_t)b * a.Tp * C::H,
@@ -978,14 +748,11 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
   }
   STAMP16(1);
   // ---- x = x + cross_attn(norm2(x), context)   (transformer.py:151, mla.py:118-194) ----
-  if (EDTTS16_PHASES & 2) {
+  {
     // cross-attention q of all heads: written once after the q projection, read back head by head (64 / 128 registers less during
-    // the cross-attention).  QLDS: in this wave's LDS slice; else in this wave's own rows of the layer's q buffer, which
-    // its self-attention has finished with (no other wave reads q rows; a padding wave stores nothing and reads what it finds).
+    // the cross-attention), in this wave's LDS slice.  (Parking them in the wave's rows of the q buffer instead: DESIGN.md 4.5.)
     f4* const qlds = ring_lds16 + C::NS * C::PH * 64 + (C::PARAM_FLOATS + 3) / 4 +
                      (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * C::HEADS * NF) * 64 + lane;
-    const __amdgpu_buffer_rsrc_t rsp = make_rsrc(reinterpret_cast<const __bf16*>(a.q) + tile0);
-    const unsigned pvoff = q_voff<C>(lane);
     {
       bf8 hn[C::KT][NF];
       rms_norm_pack<C>(h, a.n2w, nullptr, g, hn);
@@ -995,21 +762,12 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
         for (int ft = 0; ft < NF; ++ft) acc[0][ft] = acc[1][ft] = splat(0.f);
         gemm16_pair<C::KT, false>(ring, hn, acc[0], acc[1]);
 #pragma unroll
-        for (int ft = 0; ft < NF; ++ft) {
-          if constexpr (C::QLDS) qlds[(p * NF + ft) * 64] = as_f4(pack8(acc[0][ft], acc[1][ft]));
-          else if (valid)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, pack8(acc[0][ft], acc[1][ft])),
-                                                   rsp, pvoff, q_soff<C>(p, ft), 0);
-        }
+        for (int ft = 0; ft < NF; ++ft) qlds[(p * NF + ft) * 64] = as_f4(pack8(acc[0][ft], acc[1][ft]));
       }
     }
-    // (the parked rows are read back by the lanes that wrote them; the stores have left the wave before the first read is issued)
-    if constexpr (!C::QLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // (the parked rows are read back by the lanes that wrote them)
     STAMP16(2);
-    auto qf = [&](int hd, int ft) {
-      if constexpr (C::QLDS) return as_bf8(qlds[(hd * NF + ft) * 64]);
-      else return as_bf8(bufld4(rsp, pvoff, q_soff<C>(hd, ft)));
-    };
+    auto qf = [&](int hd, int ft) { return as_bf8(qlds[(hd * NF + ft) * 64]); };
     attention16<C, false>(qf, reinterpret_cast<const __bf16*>(a.kc) + (size_t)b * a.Sp * C::H,
                           reinterpret_cast<const __bf16*>(a.vcT) + (size_t)b * C::H * a.Sp, a.Sp, Sb, -1, m0, lane,
                           [&](int, const bf8 (&ob)[NF]) { ktile16<C::HT>(ring, ob, h); }
@@ -1020,7 +778,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
   }
   STAMP16(3);
   // ---- x = x + ffn(norm3(x, cond))   (transformer.py:154-158, :13-49) ----
-  if (EDTTS16_PHASES & 4) {
+  {
     bf8 hn[C::KT][NF];
     rms_norm_pack<C>(h, a.n3w, a.cond + (size_t)b * a.cond_bstride + ((size_t)a.layer * 2 + 1) * 2 * C::H, g, hn);
 #pragma unroll
@@ -1058,14 +816,7 @@ __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) void k_layer16(K
   }
   STAMP16(4);
   // ---- tail ----
-  if (!(EDTTS16_PHASES & 8)) {
-    f4 t = splat(0.f);
-#pragma unroll
-    for (int nt = 0; nt < C::HT; ++nt)
-#pragma unroll
-      for (int ft = 0; ft < NF; ++ft) t += h[nt][ft];
-    if (valid) stg4(a.h + h_at<C>(tile0, lane, 0, 0), t);
-  } else if (TAIL == TAIL_QKV) {
+  if (TAIL == TAIL_QKV) {
     if (valid) {
 #pragma unroll
       for (int nt = 0; nt < C::HT; ++nt)

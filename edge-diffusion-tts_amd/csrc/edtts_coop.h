@@ -210,7 +210,6 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
 #pragma unroll
     for (int ft = 0; ft < NF; ++ft) h[nt][ft] = ldg4(hp + 16 * nt + (size_t)ft * 16 * H);
   WStream<C> no_ring;  // (attention_fused's projection is not used here)
-  auto nop = []() {};
   auto add_branch = [&]() {  // h = branch (from LDS) + residual, as k_layer adds them
 #pragma unroll
     for (int nt = 0; nt < HT; ++nt)
@@ -222,7 +221,7 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
   {
     QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * H, H, fq, g);
     attention_fused<C, true, O_LDS>(ql, a.k + (size_t)b * a.Tp * H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, nk_self, a.window, m0, lane,
-                                    no_ring, h, obuf, nop, nullptr, 0, wv, W);
+                                    no_ring, h, obuf, []() {}, nullptr, 0, wv, W);
   }
   {
     auto fr = [&](int nt, int k) { return (F_PROJ + (unsigned)(k * HT + nt)) * 1024u; };
@@ -251,7 +250,7 @@ EDTTS_DEV void coop_layer_tile(const KArgs& a, char* lds, int wv, int lane, int 
   {
     QLds ql(qtile, H, fq, g);
     attention_fused<C, false, O_LDS>(ql, a.kc + (size_t)b * a.Sp * H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane, no_ring, h,
-                                     obuf, nop, nullptr, 0, wv, W);
+                                     obuf, []() {}, nullptr, 0, wv, W);
   }
   {
     auto fr = [&](int nt, int k) { return (F_O + (unsigned)(k * HT + nt)) * 1024u; };

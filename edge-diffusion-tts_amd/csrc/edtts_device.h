@@ -17,36 +17,33 @@
 #include <stdint.h>
 #include <type_traits>
 
-// Every EDTTS_* / EDTTS16_* macro that is not part of the public header is a tuning, ablation or diagnostic switch of scratch/:
-// some change results ("wrong by construction"), some select measured-and-rejected variants, some only move a default.  None may
-// reach a product build by accident: setting ANY of them from the command line needs -DEDTTS_EXPERIMENTS next to it.  (This test
-// sits above every `#ifndef X / #define X default`, so `defined(X)` here means "set from outside".)
-#if !defined(EDTTS_EXPERIMENTS) && (                                                                                               \
-    defined(EDTTS_ABLATE_QKVSTORES) || defined(EDTTS_ABLATE_KVLOADS) || defined(EDTTS_DIAG) || defined(EDTTS_KV2) ||                \
-    defined(EDTTS_H_DMA) || defined(EDTTS_SPLITLOAD) || defined(EDTTS_STAMPS) || defined(EDTTS_DS_ABL) ||                           \
-    defined(EDTTS_FAST_BUILD) || defined(EDTTS_W2) || defined(EDTTS_WAVELOG) || defined(EDTTS_PIN_MASK) || defined(EDTTS_HANDOVER) || defined(EDTTS_DS_BURST) || defined(EDTTS16_MFMA_SUM) || defined(EDTTS_DS_STAMPS) || defined(EDTTS_TAIL_RING2) || defined(EDTTS_RB) || defined(EDTTS_WMAX) ||        \
-    defined(EDTTS_STAMP_THREAD) || defined(EDTTS_STAMP_HEAD) ||                                                                     \
-    defined(EDTTS16_ABLATE_BARRIER) || defined(EDTTS16_ABLATE_DMA) || defined(EDTTS16_PHASES) || defined(EDTTS16_NF) ||             \
-    defined(EDTTS16_W1) || defined(EDTTS16_QLDS) || defined(EDTTS16_KVDEPTH) || defined(EDTTS16_IMG) || defined(EDTTS16_HP) ||      \
-    defined(EDTTS16_EVEN_STEPS))
-#error "tuning / ablation / diagnostic / measured-and-rejected variant switches are scratch-only: add -DEDTTS_EXPERIMENTS"
+// Every EDTTS_* / EDTTS16_* macro that is not part of the public header is a diagnostic or build switch of scratch/: the stamp and
+// wave-log builds only observe, EDTTS_FAST_BUILD compiles fewer instances.  None may reach a product build by accident: setting ANY
+// of them from the command line needs -DEDTTS_EXPERIMENTS next to it.
+#if !defined(EDTTS_EXPERIMENTS) &&                                                                                                  \
+    (defined(EDTTS_STAMPS) || defined(EDTTS_STAMP_HEAD) || defined(EDTTS_STAMP_THREAD) || defined(EDTTS_WAVELOG) ||                 \
+     defined(EDTTS_DS_STAMPS) || defined(EDTTS_FAST_BUILD))
+#error "diagnostic and build switches are scratch-only: add -DEDTTS_EXPERIMENTS"
+#endif
+// The tuning knobs, timing ablations and measured-and-rejected variants that used to be switches here have all been decided
+// (DESIGN.md records each verdict) and their code is gone: a script that still passes one must fail, not measure the product build.
+#if defined(EDTTS_W2) || defined(EDTTS_KV2) || defined(EDTTS_SPLITLOAD) || defined(EDTTS_SPLIT_ON) || defined(EDTTS_HANDOVER) ||    \
+    defined(EDTTS_H_DMA) || defined(EDTTS_TAIL_RING2) || defined(EDTTS_DS_BURST) || defined(EDTTS_PIN_MASK) ||                      \
+    defined(EDTTS_WMAX) || defined(EDTTS_RB) || defined(EDTTS_ABLATE_QKVSTORES) || defined(EDTTS_ABLATE_KVLOADS) ||                 \
+    defined(EDTTS_DS_ABL) || defined(EDTTS_DIAG) || defined(EDTTS16_HP) || defined(EDTTS16_KVDEPTH) ||                              \
+    defined(EDTTS16_MFMA_SUM) || defined(EDTTS16_EVEN_STEPS) || defined(EDTTS16_QLDS) || defined(EDTTS16_IMG) ||                    \
+    defined(EDTTS16_W1) || defined(EDTTS16_NF) || defined(EDTTS16_ABLATE_BARRIER) || defined(EDTTS16_ABLATE_DMA) ||                 \
+    defined(EDTTS16_PHASES)
+#error "this switch is retired, see DESIGN.md: its variant was decided and the code removed (last present in c6f336d)"
 #endif
 
-#ifndef EDTTS_PIN_MASK
 // Instruction types that may cross the scheduling pin IN FRONT of a K / V^T re-request inside an MFMA run (the pin behind it stays
 // total).  0x4 = SALU: the request's address arithmetic (7-12 scalar instructions per burst) then sits in the shadow of the run's
 // first MFMAs instead of in a clump between two MFMA groups whose excess over one MFMA's 32 cycles is exposed.  Round 4, same
 // device, three interleaved runs: 0.9084 vs 0.9140 ms per layer launch (0: round 3's total pin).  Results bitwise unchanged.
-#define EDTTS_PIN_MASK 0x4
-#endif
-#ifndef EDTTS_W2
-#define EDTTS_W2 0  // measured and rejected (round 4): the default decoder's 32-frame instance at TWO waves per SIMD (<= 256 registers: attention outputs wait in LDS for one projection over all heads, residual through global memory, no AGPR-class pins)
-#endif
-#if EDTTS_W2
-#define EDTTS_PIN_ACC(x) asm volatile("" : "+v"(x))
-#else
+constexpr int kPinMask = 0x4;
+// keeps an MFMA accumulator input in the AGPR class
 #define EDTTS_PIN_ACC(x) asm volatile("" : "+a"(x))
-#endif
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -88,23 +85,18 @@ struct Cfg {
   // Waves per block.  The waves of a block never synchronise, so the block size only sets how many waves must FINISH before the
   // CU's freed SIMDs get new work: two-wave blocks (two resident per CU at H = 160) measured 0.6 % faster than four-wave ones
   // (B=256, T=512: 0.9455 vs 0.9517 ms per layer launch), one-wave blocks the same as two.  LDS: each wave parks HT*NF KiB.
-#ifndef EDTTS_WMAX
-#define EDTTS_WMAX 2
-#endif
+  static constexpr int WMAX = 2;
   static constexpr int WAVES0 = (HT * NF * 4 <= 160) ? 4 : 2;
   // (The 16-frames-per-wave instances run ONE-wave blocks: they fit 256 registers, and with two-wave blocks the dispatcher put the
   // two waves of a CU's second block onto the same two SIMDs as the first -- B=32, T=512: 0.225 ms per layer launch against 0.154
   // with four-wave or one-wave blocks; one-wave blocks also spread a tiny grid over the most CUs: B=1, T=256 at 0.107 ms per
   // layer launch against 0.125 with four-wave blocks.  The 32-frame instances need > 256 registers: one wave per SIMD is all
   // that fits, whatever the block size.)
-  static constexpr int WAVES = NF == 1 ? 1 : (WAVES0 < EDTTS_WMAX ? WAVES0 : EDTTS_WMAX);
+  static constexpr int WAVES = NF == 1 ? 1 : (WAVES0 < WMAX ? WAVES0 : WMAX);
   // the cross-attention q tile goes through LDS when it fits next to the parked residual tiles (160 KiB per block at H = 160,
   // NF = 2), else through this wave's (already consumed) self-attention q rows in global memory
-  static constexpr bool Q_IN_LDS = !(EDTTS_W2 && NF == 2) && WF * H * 4 * 2 <= 40 * 1024;  // per wave: a quarter of the CU's 160 KiB (four waves per CU, in 1, 2 or 4 blocks)
+  static constexpr bool Q_IN_LDS = WF * H * 4 * 2 <= 40 * 1024;  // per wave: a quarter of the CU's 160 KiB (four waves per CU, in 1, 2 or 4 blocks)
   static constexpr int THREADS = 64 * WAVES;
-  // DEFER: the per-head attention outputs O^T wait in LDS (B-operand layout) and ONE projection over all heads follows the last
-  // head, so the 16*NF*HT-register branch tile is not live during the attention steps (see attention_fused)
-  static constexpr bool DEFER = EDTTS_W2 && NF == 2 && H == 160;
   static constexpr int OHEAD_BYTES = DFULL * NF * 1024 + (DREM ? NF * 512 : 0);  // LDS bytes of one head's O^T tiles (remainder rows as f2)
   static_assert(NF == 1 || NF == 2 || NF == 4, "frame tiles per wave");
   static_assert(H % 32 == 0 && MEL % 16 == 0 && H % HEADS == 0, "dims");
@@ -122,27 +114,6 @@ EDTTS_DEV f4 ldg4_sbase(const float* base, unsigned byte_off) {
 }
 EDTTS_DEV f2 ldg2_sbase(const float* base, unsigned byte_off) {
   return *reinterpret_cast<const f2*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-// LDS-DMA of a register-layout tile: for every (nt, ft) one global_load_lds_dwordx4 moves this lane's float4 at
-// src[16 nt + ft * 16 * ld] to lds_wave[(nt * NF + ft) * 64 + lane] (64 lanes x 16 B land lane-contiguous) without passing through
-// registers.  lds_wave is wave-uniform; src is this lane's pointer (row fq, feature quad g).
-// Written as inline asm ON PURPOSE: with the builtin, hipcc's waitcnt pass cannot count an outstanding LDS-DMA and turns every
-// later wait of the attention loop into s_waitcnt vmcnt(0) (the K / V^T requests of the next step are then waited for at once).
-// Hidden from the pass, the DMAs are just OLDER entries of the in-order vmcnt queue: every counted wait the compiler emits for
-// a later load also covers them (conservatively), so by the first use of ANY load issued after this call the tile has landed --
-// the caller reads it many thousands of cycles later.  (s_nop: one wait state between the SALU write of M0 and the DMA.)
-template <int NT, int NF>
-EDTTS_DEV void dma_tile_to_lds(const float* src, int ld, f4* lds_wave) {
-  typedef __attribute__((address_space(3))) char* lds_char_t;
-  const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_t)(char*)lds_wave);
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int ft = 0; ft < NF; ++ft) {
-      const float* p = src + 16 * nt + (size_t)ft * 16 * ld;
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(p), "s"(base + (unsigned)(nt * NF + ft) * 1024u) : "m0", "memory");
-    }
 }
 
 // Buffer loads: address = descriptor base (4 SGPRs) + wave-uniform byte offset in an SGPR (soffset) + per-lane byte offset in ONE
@@ -202,10 +173,7 @@ EDTTS_DEV float hmax(f4 v) { return fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
 // Refill burst: round 2 used 4 (an interruption of the MFMA run by VMEM issue cost ~20 cycles + 3 per load with the global_load
 // forms); with buffer loads (no address VALU) smaller bursts win because every slot is re-requested sooner: B=256, T=512 layer launch
 // 0.9280 ms at 4, 0.9186 at 2, 0.9184 at 1 (same device, interleaved runs).
-#ifndef EDTTS_RB
-#define EDTTS_RB 2
-#endif
-constexpr int kRefillBurst = EDTTS_RB;
+constexpr int kRefillBurst = 2;
 template <int RN>
 struct FragRing {
   static constexpr int RN_ = RN;
@@ -407,7 +375,6 @@ EDTTS_DEV f4 swiglu_tile(f4 v, f4 gt, f4 vb, f4 gb) {
 // ring the QKV-tail instance spilled (76 B/lane of scratch); 8 fragments = 64 MFMAs of prefetch distance.
 template <class C> constexpr int wstream_ring() {
   constexpr int full = ((C::HT * 2) / C::NF >= 2 && C::HT % ((C::HT * 2) / C::NF) == 0) ? (C::HT * 2) / C::NF : C::HT;
-  if (EDTTS_W2 && C::NF == 2 && C::H == 160) return 5;  // (half the prefetch distance in the wave's own MFMAs, the same in time at two waves per SIMD)
   return (C::HT >= 16 && full % 2 == 0) ? full / 2 : full;
 }
 template <class C> using WStream = FragRing<wstream_ring<C>()>;
@@ -420,23 +387,14 @@ EDTTS_DEV void scale_acc(f4& o, float alpha) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float x = o[r], t;
-#if EDTTS_W2
-    asm volatile("s_nop 15\n\tv_mul_f32 %0, %0, %2\n\ts_nop 3" : "+v"(x), "=&v"(t) : "v"(alpha));
-#else
     asm volatile("s_nop 15\n\tv_accvgpr_read_b32 %1, %0\n\ts_nop 1\n\tv_mul_f32 %1, %1, %2\n\ts_nop 1\n\tv_accvgpr_write_b32 %0, %1\n\ts_nop 3"
                  : "+a"(x), "=&v"(t)
                  : "v"(alpha));
-#endif
     o[r] = x;
   }
 }
 
-// -DEDTTS_KV2=1: double-buffered K / V^T fragments (tiles of step s + 2 requested while step s computes).  Measured on MI355X
-// (B=256, T=512): k_layer 0.992 ms against 0.954 ms with the single buffers -- the 44 extra registers cost more in accumulator
-// shuffling than the 5.7 % of s_waitcnt time they could hide (the bf16 kernel, whose steps are 5x shorter, does gain from it).
-#ifndef EDTTS_KV2
-#define EDTTS_KV2 0
-#endif
+// (Double-buffered K / V^T fragments were measured and rejected for the fp32 kernel: 0.992 against 0.954 ms)
 constexpr int kChunk = 2;  // key tiles (16 keys each) per online-softmax step
 constexpr float kDefer = 32.f;  // octaves a chunk may exceed the softmax reference point before it is moved
 
@@ -466,15 +424,15 @@ struct VFrag {  // V^T fragments (MFMA A operand of P V) of one chunk of key til
 // ---------------------------------------------------------------------------------------------------------
 // OMODE: what happens to a head's normalised output O^T --
 //   O_FUSED  project it at once: h += Wo[:, head] . O  (the product kernels)
-//   O_DEFER  park it in LDS (obuf, B-operand layout) and run ONE projection over all heads behind the last head (EDTTS_W2)
 //   O_LDS    park it in LDS and return: the caller projects (cooperative kernel, edtts_coop.h: heads hd0, hd0 + hstep, ... of a
 //            tile are this wave's, the projection is split over the waves by OUTPUT tiles)
-enum { O_FUSED = 0, O_DEFER = 1, O_LDS = 2 };
-template <class C, bool SELF, int OMODE, class QLoad, class BeforeProject>
+// `unused`: the place of a callback that only the retired deferred projection called.  Dropping the parameter is not neutral: hipcc
+// then moves one scalar add in k_layer_co<Cfg<160, 4, 80, 2>, *, 2>, so it stays until that kernel's code changes for another reason.
+enum { O_FUSED = 0, O_LDS = 1 };
+template <class C, bool SELF, int OMODE, class QLoad, class Unused>
 EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, const float* __restrict__ VTb, int ldv,
                                int nkeys, int window, int m0w, int lane, WStream<C>& ring, f4 (&h)[C::HT][C::NF],
-                               char* obuf, BeforeProject&& before_project,
-                               unsigned long long* stamps = nullptr, int stamp_sel = 0, int hd0 = 0, int hstep = 1) {
+                               char* obuf, Unused&& unused, unsigned long long* stamps = nullptr, int stamp_sel = 0, int hd0 = 0, int hstep = 1) {
   int sidx = 0;  // (EDTTS_STAMPS diagnostic builds: four stamps per step of the selected head)
   (void)sidx; (void)stamps; (void)stamp_sel;
   constexpr int DH = C::DH, DFULL = C::DFULL, DREM = C::DREM, DT = C::DT, H = C::H, CH = kChunk, NF = C::NF;
@@ -567,11 +525,6 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
       }
     }
   };
-#ifndef EDTTS_SPLITLOAD
-#define EDTTS_SPLITLOAD 1
-#endif
-#define EDTTS_SPLIT_ON (EDTTS_SPLITLOAD && !EDTTS_KV2)
-#if EDTTS_SPLIT_ON
   // The same requests in pieces, for re-requesting a buffer piece by piece as soon as the MFMAs that read that piece have been
   // issued (see step): group a of the K fragments of both key tiles (a == DFULL: the 8-feature remainder), key tile t of V^T.
   auto chunk_tile = [&](const Geo& q, int c, int t) {
@@ -595,7 +548,6 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
       f.v[t][dt] = bufld4(rsV, (DREM && dt == DT - 1) ? voff_rem : voff, so);
     }
   };
-#endif
   // Mask of chunk c as the INITIAL accumulator of its K Q^T product: 0 where the key is visible, -inf elsewhere
   // (-inf + finite products = -inf), so no VALU work sits between the MFMA results and the softmax.  Interior chunks (every
   // key inside the band of every query of the half and below klim: 3 of the 5 chunks at window 64, all of the cross-attention
@@ -684,14 +636,6 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
   f2 qr_n[QT];
   KVFrag<C> KA;
   VFrag<C> VA;
-#if EDTTS_KV2
-  KVFrag<C> KB;  // second K / V^T buffer: the tiles of step s + 2 are requested while step s computes
-  VFrag<C> VB;
-#endif
-  // step s = 0: the diagonal chunk; steps 1 .. nchunk-1: the other chunks in ascending order
-  auto chunk_at = [&](const Geo& q, int st) {
-    return st >= q.nchunk ? q.nchunk - 1 : (st == 0 ? q.cdiag : (st <= q.cdiag ? st - 1 : st));
-  };
   auto load_q = [&](int hd, int half) {
 #pragma unroll
     for (int ft = 0; ft < QT; ++ft) {
@@ -704,10 +648,6 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
     load_q(hd, half);
     load_k(q, hd, q.cdiag, KA);  // the first step processes the diagonal chunk
     load_v(q, hd, q.cdiag, VA);
-#if EDTTS_KV2
-    load_k(q, hd, chunk_at(q, 1), KB);
-    load_v(q, hd, chunk_at(q, 1), VB);
-#endif
     __builtin_amdgcn_sched_barrier(0);
   };
   if (hd0 < C::HEADS) prefetch(geo[0], hd0, 0);
@@ -757,24 +697,15 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
 #ifdef EDTTS_STAMPS
         if (hd == STAMP_SEL_HEAD(stamp_sel)) STAMPX(stamps, sidx++, stamp_sel);
 #endif
-#if EDTTS_SPLIT_ON
         // Each K fragment group is re-requested right after the score MFMAs that read it were issued (3 bursts of 2 requests inside
         // the 40-MFMA run instead of one burst of 6 behind it): the group the next step needs FIRST is in flight ~1 000 cycles
         // longer.  PMC: s_waitcnt took 6 % of the wave's cycles, most of it here (profiles/r03_diag_phases.txt).
         qk(fold_tag, q, c, KA, qa, qr, S, NM, nm, [&](int a) {
-          __builtin_amdgcn_sched_barrier(EDTTS_PIN_MASK);
+          __builtin_amdgcn_sched_barrier(kPinMask);
           load_k_group(q, hd_req, cnext, KA, a);
           __builtin_amdgcn_sched_barrier(0);
         });
         __builtin_amdgcn_sched_barrier(0);
-#else
-        qk(fold_tag, q, c, KA, qa, qr, S, NM, nm, [](int) {});
-        __builtin_amdgcn_sched_barrier(0);
-#ifndef EDTTS_ABLATE_KVLOADS  // timing ablation only
-        load_k(q, hd_req, cnext, KA);  // (the last step re-reads its own tiles)
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-#endif
 #ifdef EDTTS_STAMPS
         if (hd == STAMP_SEL_HEAD(stamp_sel)) STAMPX(stamps, sidx++, stamp_sel);
 #endif
@@ -862,16 +793,11 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
             for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
               for (int ft = 0; ft < QT; ++ft) O[dt][QT * hf + ft] = EDTTS_MFMA(VA.v[t][dt][r], P[t][ft][r], O[dt][QT * hf + ft]);
-#if EDTTS_SPLIT_ON
-          __builtin_amdgcn_sched_barrier(EDTTS_PIN_MASK);
+          __builtin_amdgcn_sched_barrier(kPinMask);
           load_v_tile(q, hd_req, cnext, VA, t);  // this key tile's V^T fragments have been read: re-request them now
           __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         __builtin_amdgcn_sched_barrier(0);
-#if !EDTTS_SPLIT_ON && !defined(EDTTS_ABLATE_KVLOADS)
-        load_v(q, hd_req, cnext, VA);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #ifdef EDTTS_STAMPS
         if (hd == STAMP_SEL_HEAD(stamp_sel)) STAMPX(stamps, sidx++, stamp_sel);
@@ -880,32 +806,21 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
       // step s = 0: the diagonal chunk; steps 1 .. nchunk-1: the other chunks in ascending order
       const int cd = q.cdiag;
       auto chunk_of = [&](int st) { return st >= nchunk ? nchunk - 1 : (st == 0 ? cd : (st <= cd ? st - 1 : st)); };
-#if EDTTS_KV2
-      step(No{}, cd, chunk_of(2), KA, VA, hd);
-      for (int st = 1; st < nchunk; st += 2) {
-        step(Yes{}, chunk_of(st), chunk_of(st + 2), KB, VB, hd);
-        if (st + 1 < nchunk) step(Yes{}, chunk_of(st + 1), chunk_of(st + 3), KA, VA, hd);
-      }
-#else
       // (Requesting the NEXT head's first q / K / V^T tiles from the head's last step instead of from its projection phase -- so
       // that the phase's weight-ring waits do not queue behind HBM-latency requests in the in-order vmcnt -- was built and measured:
       // 0.9369 vs 0.9307 ms per launch, slower; the per-step q re-request it needs costs more than the phase gains.)
-#ifndef EDTTS_HANDOVER
-#define EDTTS_HANDOVER 1
-#endif
-      // EDTTS_HANDOVER (round 4): a head's LAST step requests the NEXT head's first K / V^T tiles instead of re-reading its own -- the
+      // Handover (round 4): a head's LAST step requests the NEXT head's first K / V^T tiles instead of re-reading its own -- the
       // requests are issued anyway, and the next head starts on chunk cd too (same geometry) -- and only the q fragments are fetched
       // from the projection phase: the phase's ring refills then queue behind 5 q requests (rows this XCD wrote: L2 hits) instead of 17
       // HBM-latency ones in the in-order vmcnt.  Same device, three interleaved runs: k_layer 0.9014-0.9062 ms against 0.9150-0.9168, the
       // whole call 15.02-15.09 against 15.26-15.31 ms; results bitwise unchanged.  (Round 3's attempt re-requested q in every step
       // and lost 0.7 %.)
-      constexpr bool HANDOVER = EDTTS_HANDOVER && NHALF == 1;
+      constexpr bool HANDOVER = NHALF == 1;
       const bool more = HANDOVER && hd + hstep < C::HEADS;
       auto req_head = [&](int st) { return (more && st == nchunk - 1) ? hd + hstep : hd; };
       auto req_chunk = [&](int st) { return (more && st == nchunk - 1) ? cd : chunk_of(st + 1); };
       step(No{}, cd, req_chunk(0), KA, VA, req_head(0));
       for (int st = 1; st < nchunk; ++st) step(Yes{}, chunk_of(st), req_chunk(st), KA, VA, req_head(st));
-#endif
       // normalise this half's rows
 #pragma unroll
       for (int ft = 0; ft < QT; ++ft) {
@@ -920,14 +835,14 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
     if (hd == STAMP_SEL_HEAD(stamp_sel)) STAMPX(stamps, sidx++, stamp_sel);  // (normalisation done: start of the projection phases)
 #endif
     if (hd + hstep < C::HEADS) {
-      if constexpr (EDTTS_HANDOVER && NHALF == 1) {
+      if constexpr (NHALF == 1) {
         load_q(hd + hstep, 0);  // (its K / V^T tiles were requested by the last step)
         __builtin_amdgcn_sched_barrier(0);
       } else {
         prefetch(geo[0], hd + hstep, 0);
       }
     }
-    if constexpr (OMODE != O_FUSED) {
+    if constexpr (OMODE == O_LDS) {
       // this head's O^T tiles wait in LDS as they stand (C/D layout = the projection's B operand: lane-contiguous, conflict-free)
       char* ob = obuf + hd * C::OHEAD_BYTES;
 #pragma unroll
@@ -947,28 +862,6 @@ EDTTS_DEV void attention_fused(QLoad&& qload, const float* __restrict__ Kb, cons
 #ifdef EDTTS_STAMPS
     if (hd == STAMP_SEL_HEAD(stamp_sel)) STAMPX(stamps, sidx++, stamp_sel);  // end of the head
 #endif
-  }
-  if constexpr (OMODE == O_DEFER) {
-    // one projection over all heads, in the order the per-head phases have (same accumulation order: bitwise the same result)
-    before_project();
-    for (int hd = 0; hd < C::HEADS; ++hd) {
-      const char* ob = obuf + hd * C::OHEAD_BYTES;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        f4 in[NF];
-#pragma unroll
-        for (int ft = 0; ft < NF; ++ft) {
-          if (DREM && dt == DT - 1) {
-            const f2 t = reinterpret_cast<const f2*>(ob + DFULL * NF * 1024 + ft * 512)[lane];
-            in[ft] = f4{t[0], t[1], 0.f, 0.f};
-          } else {
-            in[ft] = reinterpret_cast<const f4*>(ob + (dt * NF + ft) * 1024)[lane];
-          }
-        }
-        if (DREM && dt == DT - 1) ktile_phase<C::HT, WStream<C>::RN_, NF, 2>(ring, in, h);
-        else ktile_phase<C::HT>(ring, in, h);
-      }
-    }
   }
 }
 

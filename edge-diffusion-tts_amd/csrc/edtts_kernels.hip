@@ -478,7 +478,7 @@ struct KArgs {
   int cond_bstride;   // floats between batch rows (0 = one row shared by the batch)
   int layer;
   int ffn_tiles;  // 16-wide tiles of the FFN's hidden width: ffn_mult * H / 16
-  int diag_skip;  // EDTTS_DIAG builds only: bit0 self-attn, bit1 q_proj+cross-attn, bit2 ffn, bit3 tail
+  int diag_skip;  // diagnostic builds only: the wave selector of EDTTS_STAMPS (STAMPX), the slot base of EDTTS_WAVELOG
   unsigned long long* stamps;  // EDTTS_STAMPS builds only: s_memtime stamps of block 0 / wave 0 (see edtts_debug_set_stamps)
   // weights
   const float *tok, *semp, *semp_b, *cpe, *inp, *inp_b, *pe;
@@ -551,17 +551,14 @@ EDTTS_DEV TileId wave_tile(int B, int Tp, int waves_per_block, int wave_frames) 
 // QKV of one layer from the normalised tile hn: stores q, k row-major [B][Tp][H] and v transposed [B][VR][Tp]
 // (layers/attention.py:91-93: rows of qkv.weight are q | k | v, each head-major)
 // ---------------------------------------------------------------------------------------------------------
-#ifndef EDTTS_TAIL_RING2
-#define EDTTS_TAIL_RING2 1  // round 4, same device, three interleaved runs: k_layer 0.9084-0.9121 ms against 0.9133-0.9165 with the kernel's own ring (0)
-#endif
 template <class C>
 EDTTS_DEV void qkv_tail(WStream<C>& ring0, const f4 (&hn)[C::HT][C::NF], const KArgs& a, int b, int m0, int lane) {
   constexpr int NF = C::NF;
   static_assert(C::HT % 2 == 0, "hidden must be a multiple of 32 (n-tile pairs)");
-#if EDTTS_TAIL_RING2
   // The tail's stores sit in the same in-order vmcnt queue as the ring's loads: a fragment requested right behind a store burst cannot
   // be consumed before the stores are acknowledged.  Nothing but the normalised tile is live here, so the tail runs on a ring of twice
-  // the length (twice the distance between a request and its use): the old ring's slots are its first half.
+  // the length (twice the distance between a request and its use): the old ring's slots are its first half.  (Round 4, same device,
+  // three interleaved runs: k_layer 0.9084-0.9121 ms against 0.9133-0.9165 with the kernel's own ring.)
   constexpr int RN0 = WStream<C>::RN_;
   static_assert((2 * C::HT) % (2 * RN0) == 0, "a pair phase must be a whole number of turns of the doubled ring");
   FragRing<2 * RN0> ring;
@@ -571,9 +568,6 @@ EDTTS_DEV void qkv_tail(WStream<C>& ring0, const f4 (&hn)[C::HT][C::NF], const K
 #pragma unroll
   for (int i = RN0; i < 2 * RN0; ++i) ring.r[i] = ring.frag(i);
   __builtin_amdgcn_sched_barrier(0);
-#else
-  WStream<C>& ring = ring0;
-#endif
   const int fq = lane & 15, g = lane >> 4;
   const size_t rowbase = (size_t)b * a.Tp + m0 + fq;
   // One loop per output so that the number of stores between two ring waits is a compile-time fact of each loop: the
@@ -588,9 +582,6 @@ EDTTS_DEV void qkv_tail(WStream<C>& ring0, const f4 (&hn)[C::HT][C::NF], const K
 #pragma unroll
       for (int ft = 0; ft < NF; ++ft) acc[0][ft] = acc[1][ft] = splat(0.f);
       gemm_phase_pair<C::HT>(ring, hn, acc[0], acc[1]);
-#ifdef EDTTS_ABLATE_QKVSTORES  // timing ablation only (results wrong by construction)
-      if (a.T > 0) continue;
-#endif
       // streaming stores: the q / k / v^T rows are consumed by the NEXT launch (plain stores measured the same: 0.9225-0.9242 vs
       // 0.9197-0.9227 ms per launch)
 #pragma unroll
@@ -851,8 +842,6 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
   // this wave's parking place for the residual tile, in REGISTER layout (element [nt][ft] of lane l at ((nt*NF + ft)*64 + l) * 16 B:
   // conflict-free b128 accesses, no padding)
   f4* const stash = reinterpret_cast<f4*>(smem) + (size_t)wave * C::HT * NF * 64 + lane;
-  char* const obuf = reinterpret_cast<char*>(smem) + (size_t)wave * C::HT * NF * 1024;  // (C::DEFER: the heads' O^T tiles share the parking place)
-  static_assert(!C::DEFER || C::HEADS * C::OHEAD_BYTES <= C::HT * NF * 1024, "attention outputs must fit the wave's parking place");
   constexpr int QLDS = C::H;  // q rows unpadded: stash + q tiles fill the CU's 160 KiB exactly at H = 160 (q is read a few times per head)
   float* qtile = smem + (size_t)C::WAVES * C::HT * NF * 256 + (size_t)wave * C::WF * QLDS;  // (only touched when C::Q_IN_LDS)
   const size_t rowbase = (size_t)b * a.Tp + m0 + fq;
@@ -882,33 +871,17 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
 #pragma unroll
       for (int ft = 0; ft < NF; ++ft) h[nt][ft] += stash[(nt * NF + ft) * 64];
   };
-#ifdef EDTTS_DIAG
-#define DIAG_ON(bit) (!(a.diag_skip & (bit)))
-#else
-#define DIAG_ON(bit) true
-#endif
   // ---- x = x + attn(norm1(x, cond))   (transformer.py:142-146; q/k/v were produced by the previous kernel) ----
   {
-#ifndef EDTTS_H_DMA
-#define EDTTS_H_DMA 0  // measured (B=256, T=512, same device): 0.9293 ms with the DMA vs 0.9281 ms without -- not worth a hidden DMA
-#endif
-#if EDTTS_H_DMA
-    // The residual goes from the h buffer straight to its parking place by LDS-DMA: one global_load_lds_dwordx4 per (nt, ft) lands
-    // lane-contiguous = the register layout of the stash, without passing through registers, and NOTHING waits for it before the
-    // branch is added back at the end of the self-attention (round 2 loaded it into registers, waited, and wrote it to LDS before
-    // the first head's q / K / V^T requests could even be issued: ~3 k cycles of exposed latency per launch, stamps of r03).
-    dma_tile_to_lds<C::HT, NF>(hp, C::H, reinterpret_cast<f4*>(smem) + (size_t)wave * C::HT * NF * 64);
-#else
     // the residual goes from the h buffer straight to its parking place (the loads fly together with the first head's q / K / V^T)
-    if constexpr (!C::DEFER) {
+    // (the same move by LDS-DMA, past the registers, measured 0.9293 against 0.9281 ms: not worth a hidden DMA)
 #pragma unroll
-      for (int nt = 0; nt < C::HT; ++nt)
+    for (int nt = 0; nt < C::HT; ++nt)
 #pragma unroll
-        for (int ft = 0; ft < NF; ++ft) h[nt][ft] = ldg4(hp + 16 * nt + (size_t)ft * 16 * C::H);
-      park_h();
-    }
-#endif
+      for (int ft = 0; ft < NF; ++ft) h[nt][ft] = ldg4(hp + 16 * nt + (size_t)ft * 16 * C::H);
+    park_h();
     // branch tile starts at the projection bias (attention.py:123); the residual itself stays parked until the branch is done
+    // (a lambda, like zero_h below, because hipcc schedules the hidden-32 / 192 / 256 instances differently around a plain loop)
     auto init_proj_bias = [&]() {
 #pragma unroll
       for (int nt = 0; nt < C::HT; ++nt) {
@@ -917,35 +890,19 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
         for (int ft = 0; ft < NF; ++ft) h[nt][ft] = pb;
       }
     };
-    if constexpr (!C::DEFER) init_proj_bias();
-    if (DIAG_ON(1)) {
-      QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * C::H, C::H, fq, g);
-      attention_fused<C, true, C::DEFER ? O_DEFER : O_FUSED>(ql, a.k + (size_t)b * a.Tp * C::H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, Tb, a.window, m0,
-                               lane, ring, h, obuf, init_proj_bias, a.stamps ? a.stamps + 8 : nullptr, a.diag_skip);
-    }
-    if constexpr (C::DEFER) {  // the residual never left the h buffer
-#pragma unroll
-      for (int nt = 0; nt < C::HT; ++nt)
-#pragma unroll
-        for (int ft = 0; ft < NF; ++ft) h[nt][ft] += ldg4(hp + 16 * nt + (size_t)ft * 16 * C::H);
-    } else {
-      add_parked_h();
-    }
+    init_proj_bias();
+    QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * C::H, C::H, fq, g);
+    attention_fused<C, true, O_FUSED>(ql, a.k + (size_t)b * a.Tp * C::H, a.vT + (size_t)b * C::VR * a.Tp, a.Tp, Tb, a.window, m0, lane, ring, h,
+                                      nullptr, []() {}, a.stamps ? a.stamps + 8 : nullptr, a.diag_skip);  // (no O^T parking place; unused slot)
+    add_parked_h();
     STAMPX(a.stamps, 1, a.diag_skip);
   }
   // ---- x = x + cross_attn(norm2(x), context)   (transformer.py:151, mla.py:118-194) --------------------------
-  if (DIAG_ON(2)) {
+  {
     {
       f4 hn[C::HT][NF];
       rms_norm_tile<C::HT, NF>(h, a.n2w, nullptr, g, hn);
-      if constexpr (C::DEFER) {  // LDS holds the attention outputs: the residual waits in this wave's own rows of the h buffer
-#pragma unroll
-        for (int nt = 0; nt < C::HT; ++nt)
-#pragma unroll
-          for (int ft = 0; ft < NF; ++ft) stg4(hp + 16 * nt + (size_t)ft * 16 * C::H, h[nt][ft]);
-      } else {
-        park_h();
-      }
+      park_h();
       for (int nt = 0; nt < C::HT; nt += 2) {
         f4 acc[2][NF];
 #pragma unroll
@@ -969,28 +926,21 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
 #pragma unroll
         for (int ft = 0; ft < NF; ++ft) h[nt][ft] = splat(0.f);
     };
-    if constexpr (!C::DEFER) zero_h();
+    zero_h();
     if constexpr (C::Q_IN_LDS) {
       QLds ql(qtile, QLDS, fq, g);
-      attention_fused<C, false, C::DEFER ? O_DEFER : O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane,
-                                ring, h, obuf, zero_h, a.stamps ? a.stamps + 40 : nullptr, a.diag_skip);
+      attention_fused<C, false, O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane, ring, h,
+                                         nullptr, []() {}, a.stamps ? a.stamps + 40 : nullptr, a.diag_skip);
     } else {
       QGlobal ql(a.q + ((size_t)b * a.Tp + m0) * C::H, C::H, fq, g);
-      attention_fused<C, false, C::DEFER ? O_DEFER : O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane,
-                                ring, h, obuf, zero_h);
+      attention_fused<C, false, O_FUSED>(ql, a.kc + (size_t)b * a.Sp * C::H, a.vcT + (size_t)b * C::VR * a.Sp, a.Sp, Sb, -1, m0, lane, ring, h,
+                                         nullptr, []() {});
     }
-    if constexpr (C::DEFER) {
-#pragma unroll
-      for (int nt = 0; nt < C::HT; ++nt)
-#pragma unroll
-        for (int ft = 0; ft < NF; ++ft) h[nt][ft] += ldg4(hp + 16 * nt + (size_t)ft * 16 * C::H);
-    } else {
-      add_parked_h();
-    }
+    add_parked_h();
     STAMPX(a.stamps, 3, a.diag_skip);
   }
   // ---- x = x + ffn(norm3(x, cond))   (transformer.py:154-158, :13-49) ----------------------------------------
-  if (DIAG_ON(4)) {
+  {
     f4 hn[C::HT][NF];
     const float* mod = a.cond + (size_t)b * a.cond_bstride + ((size_t)a.layer * 2 + 1) * 2 * C::H;
     rms_norm_tile<C::HT, NF>(h, a.n3w, mod, g, hn);
@@ -1017,7 +967,6 @@ EDTTS_DEV void layer_tile(const KArgs& a, float* smem, int wave, int lane, int b
     STAMPX(a.stamps, 4, a.diag_skip);
   }
   // ---- tail ---------------------------------------------------------------------------------------------------
-  if (!DIAG_ON(8)) return;
   if (TAIL == TAIL_QKV) {
     {  // (padding waves have returned)
       float* hp = a.h + rowbase * C::H + 4 * g;
@@ -1069,7 +1018,7 @@ EDTTS_DEV void tail_zero_tile(const KArgs& a, int b, int m0, int lane) {
   }
 }
 template <class C, int TAIL>
-__global__ __launch_bounds__(C::THREADS, C::DEFER ? 2 : 1) void k_layer(KArgs a) {
+__global__ __launch_bounds__(C::THREADS, 1) void k_layer(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1627,9 +1576,6 @@ extern "C" int edtts_debug_read_ds_stamps(unsigned long long* host) { return (in
 #define DS_SUB(t, i) do { } while (0)
 #define DS_TILE(t) DS_STAMP(2 + (t))
 #endif
-#ifndef EDTTS_DS_ABL
-#define EDTTS_DS_ABL 0   // timing ablations (-DEDTTS_EXPERIMENTS; results wrong): 1 no erf, 2 no stores, 4 no MFMAs, 8 no input staging, 16 no statistics
-#endif
 template <int KT, int CT, int NP, int TP>
 __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict__ x, const float* __restrict__ dw, const float* __restrict__ pw,
                                                              const float* __restrict__ pb, const float* __restrict__ gw, const float* __restrict__ gb,
@@ -1647,14 +1593,11 @@ __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict
     const int co = i / Cip, ci = i % Cip;
     wsm[co * WLD + ci] = (co < Co && ci < Ci) ? pw[(size_t)co * Ci + ci] : 0.f;
   }
-  // Sixteen-wave form (EDTTS_DS_BURST, round 4): a wave requests ALL its rows of a pass in one burst (its 5 channels x 5 segments
+  // Sixteen-wave form (round 4): a wave requests ALL its rows of a pass in one burst (its 5 channels x 5 segments
   // are in flight together instead of three load -> LDS round trips), and the rows of pass p + 1 are requested BEFORE the taps and
   // MFMAs of pass p and parked in registers until the staging tile is free -- the second pass's z registers are not live yet.  The
   // depthwise taps then come from LDS: a global load inside the pass would make its s_waitcnt wait for the whole burst (in-order vmcnt).
-#ifndef EDTTS_DS_BURST
-#define EDTTS_DS_BURST 1
-#endif
-  constexpr bool BURST = EDTTS_DS_BURST && TP == kDfTWide;
+  constexpr bool BURST = TP == kDfTWide;
   constexpr int SEG = (kDfXld + 63) / 64;
   constexpr int NB = (Cip + 2 * kDfWaves - 1) / (2 * kDfWaves);
   float* dws = xs + Cip * kDfXld;        // [Cip][kDfTapLd] depthwise taps (BURST)
@@ -1670,7 +1613,7 @@ __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict
 #pragma unroll
         for (int u = 0; u < SEG; ++u) {
           const int tl = lane + 64 * u, ts = t0 + tl;
-          vrow[BURST ? i : 0][h][u] = ((EDTTS_DS_ABL & 8) == 0 && ci < Ci && tl < nin && ts >= 0 && ts < T) ? xr[ts] : 0.f;
+          vrow[BURST ? i : 0][h][u] = (ci < Ci && tl < nin && ts >= 0 && ts < T) ? xr[ts] : 0.f;
         }
       }
   };
@@ -1725,7 +1668,7 @@ __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict
 #pragma unroll
           for (int u = 0; u < SEG; ++u) {
             const int tl = lane + 64 * u, ts = t0 + tl;
-            v[h][u] = ((EDTTS_DS_ABL & 8) == 0 && ci < Ci && tl < nin && ts >= 0 && ts < T) ? xr[ts] : 0.f;
+            v[h][u] = (ci < Ci && tl < nin && ts >= 0 && ts < T) ? xr[ts] : 0.f;
           }
         }
 #pragma unroll
@@ -1764,10 +1707,7 @@ __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict
       for (int kt = 0; kt < KT; ++kt) {
         const f4 w = *reinterpret_cast<const f4*>(wsm + (16 * ct + fq) * WLD + 16 * kt + 4 * g);  // B operand: column = channel 16 ct + fq
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (EDTTS_DS_ABL & 4) acc[ct][p][r] += at[kt][r] * w[r];
-          else acc[ct][p] = EDTTS_MFMA(at[kt][r], w[r], acc[ct][p]);
-        }
+        for (int r = 0; r < 4; ++r) acc[ct][p] = EDTTS_MFMA(at[kt][r], w[r], acc[ct][p]);
       }
     }
   }
@@ -1832,16 +1772,10 @@ __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict
     }
     __syncthreads();
   };
-  if (EDTTS_DS_ABL & 16) {
-    __syncthreads();
-    if (threadIdx.x < 2 * groups) gst[threadIdx.x] = (threadIdx.x & 1) ? 1.f : 0.f;
-    __syncthreads();
-  } else {
-    channel_reduce(std::integral_constant<bool, false>{});
-    DS_STAMP(10);
-    channel_reduce(std::integral_constant<bool, true>{});
-    DS_STAMP(11);
-  }
+  channel_reduce(std::integral_constant<bool, false>{});
+  DS_STAMP(10);
+  channel_reduce(std::integral_constant<bool, true>{});
+  DS_STAMP(11);
   // ---- y = GELU(GroupNorm(z)): 16-byte stores where the row allows it ----
   const bool vec = (To & 3) == 0;
   int fq_e = fq;  // a fresh opaque copy of the lane's channel coordinate: hipcc otherwise keeps the ten channel indices of the bias
@@ -1859,9 +1793,8 @@ __global__ __launch_bounds__(TP * 4) void k_dsconv_fused(const float* __restrict
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float v = (acc[ct][p][r] - mu) * rs * w + bb;
-        o[r] = (EDTTS_DS_ABL & 1) ? v : 0.5f * v * (1.0f + erf_as(v * 0.70710678118654752440f));
+        o[r] = 0.5f * v * (1.0f + erf_as(v * 0.70710678118654752440f));
       }
-      if ((EDTTS_DS_ABL & 2) && o[0] != 12345.f) continue;
       if (vec && t0 + 3 < To) stg4(yr + t0, o);
       else {
 #pragma unroll
@@ -2590,10 +2523,6 @@ struct ForwardArgs {
     a.h = c.wsb + c.ws.h;
     a.inp = blob + lo.inp; a.inp_b = blob + lo.inp_b; a.pe = blob + lo.pe;
     a.fnw = blob + lo.fnw; a.fnb = blob + lo.fnb; a.outp_b = blob + lo.outp_b;
-#ifdef EDTTS_DIAG
-    const char* e = getenv("EDTTS_DIAG_SKIP");
-    a.diag_skip = e ? atoi(e) : 0;
-#endif
 #ifdef EDTTS_STAMPS
     {
       auto env = [](const char* n, int d) { const char* e = getenv(n); return e ? atoi(e) : d; };
@@ -2658,7 +2587,7 @@ struct Launcher {
   // after round 3's register savings: 232) would otherwise be packed two waves per SIMD onto HALF of the CUs by the dispatcher
   // (measured: B=32, T=512 at 0.232 ms per layer launch instead of 0.155).  Every launch therefore claims a quarter of the CU's
   // 160 KiB of LDS per wave, whether it uses it or not.
-  static size_t occupancy_lds() { return C::DEFER ? 0 : (size_t)C::WAVES * 40 * 1024; }  // (the two-waves-per-SIMD experiment wants eight waves per CU)
+  static size_t occupancy_lds() { return (size_t)C::WAVES * 40 * 1024; }
   static size_t ring_lds() { return occupancy_lds(); }
   template <class CC> static size_t stash_lds() { return (size_t)CC::WAVES * CC::HT * CC::NF * 1024; }  // residual parking place
   static size_t layer_lds() {
@@ -2766,9 +2695,7 @@ struct Launcher {
 
 // ---- bf16 instance (edtts_bf16.h) ----------------------------------------------------------------------------
 // frame tiles per wave of the hidden-256 bf16 instance: 2 = four waves per block, 1 = eight (two per SIMD)
-#ifndef EDTTS16_NF
-#define EDTTS16_NF 2
-#endif
+constexpr int kNF16 = 2;
 template <class C>
 struct Launcher16 {
   static int grid(int B, int Tp) { return (B * (Tp / C::WF) + C::WAVES - 1) / C::WAVES; }
@@ -2858,7 +2785,7 @@ static int no_instance32(const Layout&) { return fail(EDTTS_ERR_UNSUPPORTED, "ED
 #define EDTTS_X(lo, HH, HD, MM, ...) else if ((lo).H == HH && (lo).HEADS == HD && (lo).MEL == MM) { using LN = Launcher<Cfg<HH, HD, MM>>; __VA_ARGS__; }
 #define EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, ...)                                                       \
     if ((lo).BF16) {                                                                                     \
-      if ((lo).H == 256 && (lo).HEADS == 8 && (lo).MEL == 80) { using LN = Launcher16<edtts16::Cfg16<256, 8, 80, EDTTS16_NF>>; __VA_ARGS__; } \
+      if ((lo).H == 256 && (lo).HEADS == 8 && (lo).MEL == 80) { using LN = Launcher16<edtts16::Cfg16<256, 8, 80, kNF16>>; __VA_ARGS__; } \
       else if ((lo).H == 64 && (lo).HEADS == 2 && (lo).MEL == 80) { using LN = Launcher16<edtts16::Cfg16<64, 2, 80>>; __VA_ARGS__; } \
       EDTTS_EXTRA_INSTANCES16(lo, __VA_ARGS__)                                                           \
       else { MISS16; }                                                                                   \
