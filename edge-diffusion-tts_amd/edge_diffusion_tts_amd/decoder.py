@@ -12,13 +12,13 @@ four dropout sites to that training forward and backward, with masks from the li
 from __future__ import annotations
 
 import math
-import threading
 from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import native
+from ._cache import PackedBlob, WorkspaceCache
 from .synth import decoder_shapes, sinusoidal_table, time_frequencies
 
 
@@ -37,6 +37,15 @@ def _attach(root: nn.Module, key: str, tensor: torch.Tensor, is_buffer: bool) ->
         mod.register_buffer(leaf, tensor)
     else:
         mod.register_parameter(leaf, nn.Parameter(tensor, requires_grad=False))
+
+
+# the decoder blob's byte-count query and pack call, looked up in native at call time (tests count packs by wrapping native.pack_weights)
+def _packed_bytes(dims):
+    return native.packed_bytes(dims)
+
+
+def _pack_weights(dims, tensors, blob):
+    native.pack_weights(dims, tensors, blob)
 
 
 class _DecoderGrad(torch.autograd.Function):
@@ -60,7 +69,7 @@ class _DecoderGrad(torch.autograd.Function):
         feats = None if sem_features is None else sem_features.detach().contiguous()
         tape = torch.empty(native.train_tape_bytes(dims, B, T, S), dtype=torch.uint8, device=x.device)
         eps = native.decoder_forward_train(dims, packed, ws, tape, x, t, step_idx, sem_idx, feats, S, drop, *lens)
-        ctx.dec, ctx.names, ctx.S, ctx.sig, ctx.drop, ctx.lens = dec, names, S, dec._packed_sig, drop, lens
+        ctx.dec, ctx.names, ctx.S, ctx.sig, ctx.drop, ctx.lens = dec, names, S, dec._blob.sig, drop, lens
         ctx.inputs = (x, t, step_idx, sem_idx, feats)
         ctx.save_for_backward(tape, *params)
         return eps
@@ -71,7 +80,7 @@ class _DecoderGrad(torch.autograd.Function):
         dec = ctx.dec
         tape, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         x, t, step_idx, sem_idx, feats = ctx.inputs
-        if dec._packed_sig != ctx.sig:
+        if dec._blob.sig != ctx.sig:
             raise RuntimeError("EdgeDiffusionDecoder: a parameter was modified between this forward and its backward")
         B, T, _ = x.shape
         dims, packed = dec.dims(), dec._packed
@@ -150,24 +159,8 @@ class EdgeDiffusionDecoder(nn.Module):
                 p.requires_grad_(True)
         self.register_buffer("_time_freqs", time_frequencies(H), persistent=False)
         self._zero_mod = None
-        self._packed: Optional[torch.Tensor] = None
-        self._packed_sig: Optional[Tuple] = None
-        self._pack_event = None     # recorded on the packing stream right behind the last pack
-        self._pack_waited = set()   # streams that have waited for it
-        self._workspaces: Dict[Tuple, torch.Tensor] = {}
-        self._pinned_workspaces = set()  # keys handed out during graph capture (never evicted)
-        self._lock = threading.Lock()  # host bookkeeping only (caches, the pack): never held across a GPU wait
-
-    # copies (copy.deepcopy, pickling) get a lock and pack bookkeeping of their own
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_lock", None)
-        state["_pack_event"], state["_pack_waited"] = None, set()
-        return state
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self._lock = threading.Lock()
+        self._blob = PackedBlob(_packed_bytes, _pack_weights)  # (_cache.py: copies get bookkeeping of their own)
+        self._ws = WorkspaceCache()
 
     # same distributions as the reference's default construction (nn.Linear / nn.Embedding defaults, ones for norm
     # gains, zeros for final out_proj and the AdaLN projections -- decoder.py:63-64, transformer.py:61-62)
@@ -292,40 +285,17 @@ class EdgeDiffusionDecoder(nn.Module):
         return refs[0], [d[k] for d, k in refs[1]]
 
     def _ensure_packed(self) -> torch.Tensor:
-        """The packed weight blob, (re-)packed on the current stream when a parameter has changed.  A call on another stream waits
-        once per pack for an event recorded behind it, so its first use is ordered after the pack (not while capturing: a capture
-        follows an eager warm-up, and torch.cuda.graph synchronises the device before it starts).  Changing parameters while calls
-        that read the old blob are still in flight on other streams is the caller's to order, as for any module."""
-        with self._lock:
-            names, tensors = self._slot_tensors()
-            sig = tuple((t.data_ptr(), t._version) for t in tensors)
-            if self._packed is None or sig != self._packed_sig:
-                dev = tensors[0].device
-                for n, t in zip(names, tensors):
-                    if t.device != dev or t.dtype != torch.float32:
-                        raise native.EdttsError(f"weight {n}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
-                dims = self.dims()
-                nbytes = native.packed_bytes(dims)
-                if self._packed is None or self._packed.numel() != nbytes or self._packed.device != dev:
-                    self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                native.pack_weights(dims, [t.contiguous() for t in tensors], self._packed)
-                self._packed_sig = sig
-                if self._packed.is_cuda:
-                    stream = torch.cuda.current_stream(dev)
-                    self._pack_event = torch.cuda.Event()
-                    self._pack_event.record(stream)
-                    self._pack_waited = {stream.cuda_stream}
-            elif self._pack_event is not None:
-                stream = torch.cuda.current_stream(self._packed.device)
-                if stream.cuda_stream not in self._pack_waited and not torch.cuda.is_current_stream_capturing():
-                    stream.wait_event(self._pack_event)  # (enqueues a wait; the host does not block)
-                    self._pack_waited.add(stream.cuda_stream)
-            return self._packed
+        """The packed weight blob, (re-)packed on the current stream when a parameter has changed; a call on another stream is
+        ordered behind the pack (PackedBlob.get).  Changing parameters while calls that read the old blob are
+        still in flight on other streams is the caller's to order, as for any module."""
+        names, tensors = self._slot_tensors()
+        return self._blob.get(self.dims(), tensors, names=names)
+
+    _packed = property(lambda self: self._blob.blob)
+    _workspaces = property(lambda self: self._ws.entries)
+    _pinned_workspaces = property(lambda self: self._ws.pinned)
 
     # ------------------------------------------------------------------------------------------ blob mirror (optim.FusedAdamW)
-    def _sig(self) -> Tuple:
-        return tuple((t.data_ptr(), t._version) for t in self._slot_tensors()[1])
-
     def _mirror_map(self) -> Optional[Dict[str, Tuple[int, int, int, bool]]]:
         """{parameter name: (offset in floats, rows, cols, transposed)} of the packed blob, from the library's own layout
         (native.generic_slot_dest); None for a decoder whose blob is not the generic fp32 one (fragment-order blobs are not mirrored)."""
@@ -341,93 +311,37 @@ class EdgeDiffusionDecoder(nn.Module):
     def _mirror_target(self) -> Optional[torch.Tensor]:
         """The packed blob if it is current -- packed, and packed from the tensors as they stand -- else None.  The current stream is
         ordered behind the pack, so an optimiser step enqueued on it may write the new values into the blob."""
-        with self._lock:
-            if self._packed is None or self._packed_sig != self._sig():
-                return None
-            if self._pack_event is not None:
-                stream = torch.cuda.current_stream(self._packed.device)
-                if stream.cuda_stream not in self._pack_waited:
-                    stream.wait_event(self._pack_event)
-                    self._pack_waited.add(stream.cuda_stream)
-            return self._packed
+        return self._blob.current(self.dims(), self._slot_tensors()[1])
 
     def _mirror_commit(self) -> None:
         """After a step that wrote every updated parameter into the blob as well and bumped the parameters' versions: the blob is
         current again.  Takes the signature of the tensors as they stand and records the pack event on the current stream."""
-        with self._lock:
-            self._packed_sig = self._sig()
-            if self._packed.is_cuda:
-                stream = torch.cuda.current_stream(self._packed.device)
-                self._pack_event = torch.cuda.Event()
-                self._pack_event.record(stream)
-                self._pack_waited = {stream.cuda_stream}
+        self._blob.commit(self.dims(), self._slot_tensors()[1])
 
     WORKSPACE_CACHE = 8
 
     def workspace(self, B: int, T: int, S: int, cond_rows: int, device, tag: str = "", *, stream=None) -> torch.Tensor:
-        """Cached scratch memory for one (shape, device, tag, stream, sub-batch cut).  A workspace belongs to the stream it was made
-        for -- ``stream``, by default the device's current stream: it is allocated and zero-filled there, and calls on another
-        stream get their own, so calls on several streams (from one thread or several) never share one.  The key also holds the
-        number of sub-batches a sampler call of this shape makes under the current edtts_set_substreams setting
-        (native.substreams_for), so a setting change never hands out a workspace laid out for another cut.
-        At most WORKSPACE_CACHE entries are kept; the least recently USED one is dropped to make room -- never one that a captured
-        hipGraph points at (a workspace handed out while the stream was capturing is pinned for the life of the decoder: a replay
-        writes into it).  While capturing, the capturing stream's own workspace is taken if it has one, otherwise the one of the
-        eager warm-up (the most recently used of that shape on any stream), so graphs captured on one stream share a workspace and
-        graphs captured on streams that were each warmed up have one each."""
-        dev = torch.device(device)
-        if dev.type == "cuda":
-            if stream is None:
-                stream = torch.cuda.current_stream(dev)
-            sid = stream.cuda_stream
-        else:
-            sid = None if stream is None else stream.cuda_stream
-        cut = native.substreams_for(self.dims(), B, T)  # (a host query)
-        key = (B, T, S, cond_rows, str(device), tag, sid, cut)
-        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        with self._lock:
-            ws = self._workspaces.pop(key, None)
-            if ws is None and capturing:  # the warm-up's workspace (today's rule) when this stream has none of its own
-                same = [k for k in self._workspaces if k[:6] == key[:6] and k[7] == cut]
-                if same:
-                    key = same[-1]
-                    ws = self._workspaces.pop(key)
-            if ws is None:
-                evictable = [k for k in self._workspaces if k not in self._pinned_workspaces]  # insertion order = least recently used first
-                while len(self._workspaces) >= self.WORKSPACE_CACHE and evictable:
-                    # (an evicted workspace goes back to the caching allocator's pool of the stream it was made on: the next block
-                    # handed out there is ordered behind the calls still reading it)
-                    del self._workspaces[evictable.pop(0)]
-                nbytes = native.workspace_bytes(self.dims(), B, T, S, cond_rows)
-                if dev.type == "cuda" and sid != torch.cuda.current_stream(dev).cuda_stream:
-                    with torch.cuda.stream(stream):
-                        ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-                else:
-                    ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)  # must start zero-filled (padding lanes)
-            self._workspaces[key] = ws  # (re-)inserted last = most recently used
-            if ws.is_cuda and torch.cuda.is_current_stream_capturing():
-                self._pinned_workspaces.add(key)
-                n_pinned = len(self._pinned_workspaces)
-            else:
-                n_pinned = 0
-        if n_pinned > self.WORKSPACE_CACHE:
-            import warnings
-            warnings.warn(f"EdgeDiffusionDecoder: {n_pinned} workspaces are pinned by captured graphs (more than "
-                          f"WORKSPACE_CACHE = {self.WORKSPACE_CACHE}); call release_pinned() for shapes whose graphs are gone",
-                          RuntimeWarning, stacklevel=3)
-        return ws
+        """Cached scratch memory for one (shape, device, tag, sub-batch cut, stream): WorkspaceCache's rules (one per stream, at most
+        WORKSPACE_CACHE kept, pinned while a captured graph may replay into it).  A workspace is allocated and zero-filled on the
+        stream it belongs to -- ``stream``, by default the device's current stream.  The key also holds the number of sub-batches a
+        sampler call of this shape makes under the current edtts_set_substreams setting (native.substreams_for), so a setting change
+        never hands out a workspace laid out for another cut."""
+        dims = self.dims()
+
+        def alloc():
+            nbytes = native.workspace_bytes(dims, B, T, S, cond_rows)
+            if stream is not None and torch.device(device).type == "cuda" and stream.cuda_stream != torch.cuda.current_stream(device).cuda_stream:
+                with torch.cuda.stream(stream):
+                    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+            return torch.zeros(nbytes, dtype=torch.uint8, device=device)  # must start zero-filled (padding lanes)
+
+        head = (B, T, S, cond_rows, str(device), tag, native.substreams_for(dims, B, T))  # (the cut: a host query)
+        return self._ws.get(self, head, device, stream, alloc)
 
     def release_pinned(self, B: Optional[int] = None, T: Optional[int] = None, S: Optional[int] = None) -> int:
-        """Un-pin (and drop) the workspaces that were handed out during graph capture -- all of them, or those of one (B, T, S).
-        A pin is keyed by shape, not by graph, and the decoder cannot see a hipGraph die: call this once the graphs that replay
-        into those workspaces have been destroyed (replaying one afterwards would write into freed memory).  Returns the number
-        of workspaces released."""
-        with self._lock:
-            keys = [k for k in self._pinned_workspaces if (B is None or k[0] == B) and (T is None or k[1] == T) and (S is None or k[2] == S)]
-            for k in keys:
-                self._pinned_workspaces.discard(k)
-                self._workspaces.pop(k, None)
-        return len(keys)
+        """Un-pin (and drop) the workspaces that were handed out during graph capture -- all of them, or those of one (B, T, S): call
+        this once the graphs that replay into them have been destroyed (WorkspaceCache.release_pinned).  Returns their number."""
+        return self._ws.release_pinned(lambda k: (B is None or k[0] == B) and (T is None or k[1] == T) and (S is None or k[2] == S))
 
     # ------------------------------------------------------------------------------------------ autograd
     def _slot_param(self, slot: str) -> Optional[str]:

@@ -21,59 +21,20 @@ on first use and re-packed when a parameter changes.
 """
 from __future__ import annotations
 
-import threading
 from collections import OrderedDict
-from typing import List, Optional, Sequence
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from . import native
+from ._cache import PackedBlob
 
 
-class _PackCache:
-    """The packed blob of one head: (re-)packed on the current stream when a weight tensor or the dims changed."""
-
-    def __init__(self, train: bool = False, vq: bool = False):
-        self._lock = threading.Lock()
-        self._sig = None
-        self._blob = None
-        self._train = train  # the training-only blob (transposed matrices for the backward) instead of the inference blob
-        self._vq = vq        # ... of a VQ head (edtts_sem_vq_train_pack)
-        self._stale = False
-
-    @property
-    def sig(self):
-        return self._sig
-
-    @staticmethod
-    def sig_of(dims: native.EdttsSemDims, tensors: Sequence[torch.Tensor]):
-        dkey = (dims.in_dim, dims.semantic_dim, dims.quantizer, dims.codebook_size, dims.n_levels, tuple(dims.levels))
-        return (dkey,) + tuple((t.data_ptr(), t._version, t.device) for t in tensors)
-
-    def invalidate(self) -> None:
-        """The next get() packs again although no tensor's version moved (the EMA kernel writes into the codebook's storage)."""
-        with self._lock:
-            self._stale = True
-
-    def get(self, dims: native.EdttsSemDims, tensors: Sequence[torch.Tensor]) -> torch.Tensor:
-        nbytes_of, pack = (native.sem_train_packed_bytes, native.sem_train_pack) if self._train else (native.sem_packed_bytes, native.sem_pack)
-        if self._train and self._vq:
-            nbytes_of, pack = native.sem_vq_train_packed_bytes, native.sem_vq_train_pack
-        with self._lock:
-            sig = self.sig_of(dims, tensors)
-            if self._blob is None or sig != self._sig or self._stale:
-                dev = tensors[0].device
-                for i, t in enumerate(tensors):
-                    if t.device != dev or t.dtype != torch.float32:
-                        raise native.EdttsError(f"weight {i}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
-                nbytes = nbytes_of(dims)
-                if self._blob is None or self._blob.numel() != nbytes or self._blob.device != dev:
-                    self._blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                pack(dims, [t.detach().contiguous() for t in tensors], self._blob)
-                self._sig = sig
-                self._stale = False
-            return self._blob
+# (byte-count query, pack call) of a head's inference blob and of its training-only blob (transposed matrices for the backward), FSQ / VQ
+_SEM = (native.sem_packed_bytes, native.sem_pack)
+_SEM_TRAIN = (native.sem_train_packed_bytes, native.sem_train_pack)
+_SEM_VQ_TRAIN = (native.sem_vq_train_packed_bytes, native.sem_vq_train_pack)
 
 
 def _stats(counts: torch.Tensor):
@@ -149,7 +110,7 @@ class _VQGrad(torch.autograd.Function):
         idx, zq, counts, loss = native.sem_vq_encode_train(dims, blob, x, tape, lengths, training, commit, drop)
         # the versions as the forward saw them: the EMA's own write (no version moves, the caches are only marked stale) must not
         # look like a modified parameter to the backward
-        ctx.owner, ctx.dims, ctx.lengths, ctx.drop, ctx.sig = owner, dims, lengths, drop, _PackCache.sig_of(dims, slots)
+        ctx.owner, ctx.dims, ctx.lengths, ctx.drop, ctx.sig = owner, dims, lengths, drop, PackedBlob.signature(dims, slots)
         ctx.blob, ctx.tblob, ctx.commit, ctx.training = blob, tblob, commit, training
         ctx.x = x
         if training and vq.decay > 0:
@@ -169,7 +130,7 @@ class _VQGrad(torch.autograd.Function):
     def backward(ctx, d_zq, d_loss, _d_idx, _d_counts):
         owner, dims = ctx.owner, ctx.dims
         tape, idx, params = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
-        if _PackCache.sig_of(dims, owner._slots()) != ctx.sig:
+        if PackedBlob.signature(dims, owner._slots()) != ctx.sig:
             raise RuntimeError(f"{type(owner).__name__}: a parameter was modified between this forward and its backward")
         grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[6:])]
         d_z = torch.empty_like(ctx.x) if dims.in_dim == 0 and ctx.needs_input_grad[5] else None
@@ -196,7 +157,7 @@ class FSQ(nn.Module):
         self.codebook_size = 1
         for v in self.levels:
             self.codebook_size *= v
-        self._pack = _PackCache()
+        self._pack = PackedBlob(*_SEM)
         self._eye = {}
 
     @property
@@ -263,8 +224,8 @@ class FSQEncoder(nn.Module):
         self.fsq_dim = len(levels)
         self.proj_down = nn.Linear(input_dim, self.fsq_dim)
         self.proj_up = nn.Linear(self.fsq_dim, input_dim)
-        self._pack = _PackCache()
-        self._tpack = _PackCache(train=True)
+        self._pack = PackedBlob(*_SEM)
+        self._tpack = PackedBlob(*_SEM_TRAIN)
 
     @property
     def codebook_size(self) -> int:
@@ -335,8 +296,8 @@ class VectorQuantizer(nn.Module):
         self.register_buffer("ema_cluster_size", torch.ones(codebook_size))
         self.register_buffer("ema_w", self.codebook.weight.detach().clone())
         self.register_buffer("update_count", torch.tensor(0))
-        self._pack = _PackCache()
-        self._tpack = _PackCache(train=True, vq=True)
+        self._pack = PackedBlob(*_SEM)
+        self._tpack = PackedBlob(*_SEM_VQ_TRAIN)
         self.reset_generator: Optional[torch.Generator] = None
         self._count_host: Optional[int] = None  # host mirror of update_count: a step that does not reset never synchronises
         self._count_sig = None
@@ -530,8 +491,8 @@ class SemanticEncoder(nn.Module):
             self.vq = FSQEncoder(cfg.semantic_dim, cfg.fsq_levels, autograd=self.autograd)
         else:
             self.vq = VectorQuantizer(cfg.semantic_dim, cfg.codebook_size, commit=getattr(cfg, "vq_commit", 0.25), autograd=self.train_vq)
-        self._pack = _PackCache()
-        self._tpack = _PackCache(train=True, vq=not is_fsq)
+        self._pack = PackedBlob(*_SEM)
+        self._tpack = PackedBlob(*(_SEM_TRAIN if is_fsq else _SEM_VQ_TRAIN))
 
     @property
     def codebook_size(self) -> int:

@@ -20,13 +20,14 @@ conv0, the GroupNorm, the residual stream, every LayerNorm, GELU, the softmax an
 """
 from __future__ import annotations
 
-import threading
-from typing import Dict, List, Optional, Tuple
+from functools import partial
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import native
+from ._cache import PackedBlob, WorkspaceCache
 
 # transformers.HubertConfig defaults (hubert-base) for fields a dict may leave out
 _DEFAULTS = dict(
@@ -103,11 +104,9 @@ class NativeHubert(nn.Module):
         for key, shape in self._shapes():
             self._put(key, shape)
         self._register_load_state_dict_pre_hook(self._normalise_keys)
-        self._lock = threading.Lock()
-        self._sig = None
-        self._blob = None
-        self._workspaces: "Dict[tuple, torch.Tensor]" = {}
-        self._pinned = set()
+        self._blob = PackedBlob(partial(native.hubert_packed_bytes, compute_dtype=self._dt),
+                                partial(native.hubert_pack, compute_dtype=self._dt), "NativeHubert weight")
+        self._ws = WorkspaceCache()
 
     # ------------------------------------------------------------------------------------------ parameters
     def _shapes(self) -> List[Tuple[str, tuple]]:
@@ -233,46 +232,25 @@ class NativeHubert(nn.Module):
 
     # ------------------------------------------------------------------------------------------ the forward
     def _packed(self) -> torch.Tensor:
-        with self._lock:
-            params = list(self.parameters())
-            dev = params[0].device
-            sig = (dev, self._dt) + tuple((p.data_ptr(), p._version, p.device) for p in params)
-            if self._blob is None or sig != self._sig:
-                tensors = self._slots()
-                for i, t in enumerate(tensors):
-                    if t.device != dev or t.dtype != torch.float32:
-                        raise native.EdttsError(f"NativeHubert weight {i}: expected fp32 on {dev}, got {t.dtype} on {t.device}")
-                nbytes = native.hubert_packed_bytes(self.dims, self._dt)
-                if self._blob is None or self._blob.numel() != nbytes or self._blob.device != dev:
-                    self._blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                native.hubert_pack(self.dims, [t.detach().contiguous() for t in tensors], self._blob, self._dt)
-                self._sig = sig
-            return self._blob
+        """The packed blob (PackedBlob.get).  The signature is taken over the parameters; what is packed is
+        _slots(), which folds the weight norm into a fresh tensor, so it is built on a miss only."""
+        return self._blob.get(self.dims, list(self.parameters()), packs=self._slots)
+
+    _workspaces = property(lambda self: self._ws.entries)
+    _pinned = property(lambda self: self._ws.pinned)
 
     def workspace(self, B: int, T_audio: int, device) -> torch.Tensor:
-        """Cached scratch memory per (B, T_audio, device, stream), as EdgeDiffusionDecoder.workspace: calls on
-        several streams never share one; while a stream captures a graph it takes its own workspace or, failing that, the most
-        recently used one of that shape (the eager warm-up's), which then stays pinned for the module's life."""
+        """Cached scratch memory per (B, T_audio, device, stream), as EdgeDiffusionDecoder.workspace (WorkspaceCache, DESIGN.md section
+        10): calls on several streams never share one; while a stream captures a graph it takes its own workspace or, failing that,
+        the most recently used one of that shape (the eager warm-up's), which then stays pinned until release_pinned."""
         dev = torch.device(device)
-        sid = torch.cuda.current_stream(dev).cuda_stream
-        key = (B, T_audio, str(dev), sid)
-        capturing = torch.cuda.is_current_stream_capturing()
-        with self._lock:
-            ws = self._workspaces.pop(key, None)
-            if ws is None and capturing:
-                same = [k for k in self._workspaces if k[:3] == key[:3]]
-                if same:
-                    key = same[-1]
-                    ws = self._workspaces.pop(key)
-            if ws is None:
-                evictable = [k for k in self._workspaces if k not in self._pinned]
-                while len(self._workspaces) >= self.WORKSPACE_CACHE and evictable:
-                    del self._workspaces[evictable.pop(0)]
-                ws = torch.empty(native.hubert_workspace_bytes(self.dims, B, T_audio, self._dt), dtype=torch.uint8, device=dev)
-            self._workspaces[key] = ws
-            if capturing:
-                self._pinned.add(key)
-            return ws
+        return self._ws.get(self, (B, T_audio, str(dev)), dev, None, lambda: torch.empty(
+            native.hubert_workspace_bytes(self.dims, B, T_audio, self._dt), dtype=torch.uint8, device=dev))
+
+    def release_pinned(self, B: Optional[int] = None, T_audio: Optional[int] = None) -> int:
+        """Un-pin (and drop) the workspaces handed out during graph capture -- all, or those of one (B, T_audio) -- once their graphs
+        have been destroyed (WorkspaceCache.release_pinned).  Returns their number."""
+        return self._ws.release_pinned(lambda k: (B is None or k[0] == B) and (T_audio is None or k[1] == T_audio))
 
     @torch.no_grad()
     def forward(self, wav: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -43,7 +43,17 @@ EXPORTED_SYMBOLS = (
 EDTTS_IDX_SEM, EDTTS_IDX_STEP, EDTTS_IDX_LEN = 1, 2, 4
 
 
-class EdttsDims(C.Structure):
+class _Dims(C.Structure):
+    """A dims struct compares by value: _cache.PackedBlob keys a packed blob by the dims it was packed for."""
+
+    def __eq__(self, other):
+        return type(other) is type(self) and bytes(self) == bytes(other)
+
+    def __hash__(self):
+        return hash(bytes(self))
+
+
+class EdttsDims(_Dims):
     _fields_ = [(n, C.c_int32) for n in (
         "hidden", "layers", "heads", "n_mels", "ffn_mult", "codebook_size", "semantic_dim", "window", "max_pos",
         "max_ctx_pos", "n_step_emb", "compute_dtype")]
@@ -60,7 +70,7 @@ DROP_SITES = {"attn": 0, "cross_attn": 1, "ffn_act": 2, "ffn_out": 3}  # include
 SEM_FSQ, SEM_VQ = 0, 1  # EdttsSemDims.quantizer (include/edtts.h: EDTTS_SEM_*)
 
 
-class EdttsSemDims(C.Structure):
+class EdttsSemDims(_Dims):
     _fields_ = [("in_dim", C.c_int32), ("semantic_dim", C.c_int32), ("quantizer", C.c_int32), ("codebook_size", C.c_int32),
                 ("n_levels", C.c_int32), ("levels", C.c_int32 * 16)]
 
@@ -97,7 +107,7 @@ class EdttsOptimTensor(C.Structure):
 OPT_CLIP, OPT_SKIP_NONFINITE, OPT_ZERO_GRADS, OPT_EMA_ONLY = 1, 2, 4, 8  # include/edtts.h: EDTTS_OPT_*
 
 
-class EdttsHubertDims(C.Structure):
+class EdttsHubertDims(_Dims):
     _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 16), ("conv_kernel", C.c_int32 * 16), ("conv_stride", C.c_int32 * 16),
                 ("hidden", C.c_int32), ("heads", C.c_int32), ("intermediate", C.c_int32), ("num_layers", C.c_int32),
                 ("pos_kernel", C.c_int32), ("pos_groups", C.c_int32), ("layer_norm_eps", C.c_float)]

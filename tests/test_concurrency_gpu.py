@@ -199,7 +199,7 @@ def test_graphs_captured_on_two_streams_replay_concurrently():
         with torch.cuda.graph(gr, stream=s):
             static_out.append(infer.generate_mel(sem, 4, x_T=x))
     ws = [dec.workspace(B, 2 * S, S, 4, x1.device, stream=s) for s in streams]
-    assert ws[0].data_ptr() != ws[1].data_ptr() and all(k[-2] in (s.cuda_stream for s in streams) for k in dec._pinned_workspaces)
+    assert ws[0].data_ptr() != ws[1].data_ptr() and all(k[-1] in (s.cuda_stream for s in streams) for k in dec._pinned_workspaces)
     assert len(dec._pinned_workspaces) == 2
     for _ in range(3):
         static_out[0].zero_(); static_out[1].zero_()
@@ -232,6 +232,98 @@ def test_first_call_on_a_second_stream_waits_for_the_pack():
         out2 = infer.generate_mel(sem, 4, x_T=x)
     torch.cuda.synchronize()
     assert torch.equal(out1, expect) and torch.equal(out2, expect)
+
+
+def stale_blob_race(module, fresh, change, call):
+    """The other modules' packed blobs are ordered across streams like the decoder's (_cache.PackedBlob).  The blob is packed from
+    W1 by a warm call; one weight is changed in place (W2); stream s1 is kept busy and then makes the call, which re-packs behind
+    the busy work; s2 makes the same call right away, and so do two more streams (streams that share a hardware queue run in
+    submission order whether they wait or not, and a process here has four queues).  Without the wait for the pack they read a
+    valid but stale blob (W1's), never unwritten memory.  Returns (s1's result, the other streams' results, the result of ``fresh``,
+    a module loaded with W2)."""
+    call(module)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        change(module)
+    torch.cuda.synchronize()
+    fresh.load_state_dict(module.state_dict())
+    expect = call(fresh)
+    torch.cuda.synchronize()
+    s1, others = torch.cuda.Stream(), [torch.cuda.Stream() for _ in range(3)]
+    with torch.cuda.stream(s1):
+        big = torch.randn(4096, 4096, device=DEV)
+        for _ in range(20):  # (keeps s1 busy for a while: the re-pack behind it starts late)
+            big = (big @ big).tanh_()
+        out1 = call(module)
+    outs = []
+    for s in others:
+        with torch.cuda.stream(s):
+            outs.append(call(module))
+    torch.cuda.synchronize()
+    return out1, outs, expect
+
+
+def test_hubert_call_on_a_second_stream_waits_for_the_repack():
+    import json
+    import os
+    import numpy as np
+    from edge_diffusion_tts_amd import NativeHubert
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hubert_small.npz"))  # (as test_hubert_gpu.small_model(3))
+    sd = {k[2:]: torch.from_numpy(z[k].astype(np.float32)) for k in z.files if k.startswith("w:")}
+    wav = torch.from_numpy(z["wav"].astype(np.float32)).to(DEV)
+
+    def small_model():
+        m = NativeHubert(json.loads(bytes(z["config"]).decode()), 3)
+        m.load_state_dict(sd)
+        return m.to(DEV).eval()
+
+    def change(m):
+        m._get("encoder.layer_norm.weight").mul_(1.5)
+        m._get("feature_projection.projection.bias").add_(0.25)
+    out1, outs, expect = stale_blob_race(small_model(), small_model(), change, lambda m: m(wav))
+    assert torch.equal(out1, expect) and all(torch.equal(o, expect) for o in outs)
+
+
+def semantic_head(quantizer, **kw):
+    from edge_diffusion_tts_amd import SemanticEncoder
+    from edge_diffusion_tts_amd.synth import synth_semantic_head
+    cfg = CFG(device=DEV) if quantizer == "fsq" else CFG(device=DEV, use_fsq=False, codebook_size=64)
+    proj_sd, q_sd = synth_semantic_head(64, cfg.semantic_dim, cfg.fsq_levels if quantizer == "fsq" else None, 64)
+    enc = SemanticEncoder(cfg, in_dim=64, **kw)
+    enc.proj.load_state_dict(proj_sd)
+    enc.vq.load_state_dict(q_sd)
+    return enc.to(DEV).eval()
+
+
+def flip_last_linear(enc):
+    enc.proj.final.weight.mul_(-1.0)
+    enc.proj.final.bias.add_(0.25)
+
+
+@pytest.mark.parametrize("quantizer", ["fsq", "vq"])
+def test_quantize_features_on_a_second_stream_waits_for_the_repack(quantizer):
+    from edge_diffusion_tts_amd.synth import synth_hubert_features
+    h = synth_hubert_features(2, 50, 64, 3).to(DEV)
+    out1, outs, (zq, idx, *_) = stale_blob_race(semantic_head(quantizer), semantic_head(quantizer), flip_last_linear,
+                                                lambda m: m.quantize_features(h))
+    for k, (zq_k, idx_k, *_) in enumerate([out1] + outs):
+        assert torch.equal(idx_k, idx) and torch.equal(zq_k, zq), k
+
+
+def test_semantic_training_step_on_a_second_stream_waits_for_the_repack():
+    """autograd=True, FSQ: the forward and the backward read the inference blob and the training-only blob (_pack and _tpack)."""
+    from edge_diffusion_tts_amd.synth import synth_hubert_features
+    h = synth_hubert_features(2, 50, 64, 3).to(DEV)
+    C = torch.randn(2, 50, 128, generator=torch.Generator().manual_seed(4)).to(DEV)
+
+    def step(m):
+        zq = m.quantize_features(h)[0]
+        return (zq.detach(), *torch.autograd.grad((zq * C).sum(), m.get_trainable_params()))
+    out1, outs, expect = stale_blob_race(semantic_head("fsq", autograd=True), semantic_head("fsq", autograd=True), flip_last_linear, step)
+    assert len(expect) == 11 and all(bool(g.abs().sum() > 0) for g in expect)
+    for k, out in enumerate([out1] + outs):
+        for j, (a, e) in enumerate(zip(out, expect)):
+            assert torch.equal(a, e), (k, j)
 
 
 def test_index_errors_stay_with_their_stream():

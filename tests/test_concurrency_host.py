@@ -102,6 +102,7 @@ def test_decoder_copies_get_their_own_lock():
     dec = EdgeDiffusionDecoder(CFG(device="cpu"))
     dec.workspace(1, 32, 16, 1, "cpu")
     twin = copy.deepcopy(dec)
-    assert twin._lock is not dec._lock and twin._pack_event is None
+    assert twin._blob is not dec._blob and twin._blob._lock is not dec._blob._lock and twin._blob._event is None
+    assert twin._ws is not dec._ws and twin._ws._lock is not dec._ws._lock
     assert twin.workspace(1, 32, 16, 1, "cpu") is not dec.workspace(1, 32, 16, 1, "cpu")
     assert torch.equal(twin.in_proj.weight, dec.in_proj.weight)

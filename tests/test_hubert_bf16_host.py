@@ -104,7 +104,8 @@ def test_limits_of_the_bf16_path_name_the_field(change, field):
 
 def test_two_dtypes_share_nothing():
     f, h = NativeHubert(small_cfg(), 3), NativeHubert(small_cfg(), 3, compute_dtype="bf16")
-    assert f._workspaces is not h._workspaces and f._pinned is not h._pinned and f._lock is not h._lock
+    assert f._workspaces is not h._workspaces and f._pinned is not h._pinned and f._ws._lock is not h._ws._lock
+    assert f._blob is not h._blob and f._blob._lock is not h._blob._lock
     assert f.WORKSPACE_CACHE == h.WORKSPACE_CACHE == 8
     # the same errors in both dtypes for what the forward rejects before any kernel runs
     for m in (f, h):
