@@ -19,17 +19,16 @@ torchaudio itself.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import native
+from .native import EDTTS_MEL_LOG, EDTTS_MEL_POWER
 from .melpost import melscale_fbanks
 
 N_FFT = 1024
-EDTTS_MEL_POWER, EDTTS_MEL_LOG = 0, 1  # include/edtts.h
 
 
 # ---------------------------------------------------------------------------------------------------- host tables
@@ -126,12 +125,8 @@ def _resample(waveform, plan, lengths):
     if B == 0 or L == 0:
         raise ValueError("resample: empty waveform")
     L_out = resampled_length(L, o, n)
-    y = torch.empty(B, L_out, dtype=torch.float32, device=x.device)
     lens = native.lengths(lengths, B, L, x.device, "lengths")
-    native.lib().edtts_resample(native._dev_ptr(x, torch.float32, "waveform"), B, L, native._dev_ptr(lens, torch.int64, "lengths"), o, n,
-                                width, taps, native._dev_ptr(table, torch.float32, "table"), C.c_int64(L_out), y.data_ptr(),
-                                native._stream(x.device))
-    y = y.reshape(shape[:-1] + (L_out,))
+    y = native.resample(x, lens, o, n, width, taps, table, L_out).reshape(shape[:-1] + (L_out,))
     if lengths is None:
         return y
     return y, (lens.clamp(1, L) * n + (o - 1)) // o
@@ -223,19 +218,10 @@ class MelSpectrogram(torch.nn.Module):
         return x, native.lengths(lengths, B, L, x.device, "lengths")
 
     def _tables(self):
-        p = native._dev_ptr
-        return (p(self.window, torch.float32, "window"), p(self.twiddle, torch.float32, "twiddle"), p(self.fb_desc, torch.int32, "fb_desc"),
-                p(self.fb_weights, torch.float32, "fb_weights"))
+        return self.window, self.twiddle, self.fb_desc, self.fb_weights
 
     def _melspec(self, x, lens, mode):
-        B, L = x.shape
-        T = self.frames(L)
-        out = torch.empty((B, self.n_mels, T) if mode == EDTTS_MEL_POWER else (B, T, self.n_mels), dtype=torch.float32, device=x.device)
-        win, tw, desc, w = self._tables()
-        native.lib().edtts_melspec(native._dev_ptr(x, torch.float32, "waveform"), B, L, native._dev_ptr(lens, torch.int64, "lengths"),
-                                   self.n_fft, self.hop_length, win, tw, desc, w, self.n_mels, int(self.power), mode, out.data_ptr(),
-                                   native._stream(x.device))
-        return out
+        return native.melspec(x, lens, self.n_fft, self.hop_length, self._tables(), self.n_mels, int(self.power), mode)
 
     @torch.no_grad()
     def forward(self, waveform: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -262,12 +248,7 @@ class MelSpectrogram(torch.nn.Module):
             raise NotImplementedError("log_mel / stats are built for power=2.0 (what the reference uses)")
         x, lens = self._rows(wav, lengths)
         lm = self._melspec(x, lens, EDTTS_MEL_LOG)
-        B, T, M = lm.shape
-        mean = torch.empty(B, 1, M, dtype=torch.float32, device=lm.device)
-        std = torch.empty_like(mean)
-        native.lib().edtts_logmel_stats(lm.data_ptr(), B, T, M, x.shape[1], native._dev_ptr(lens, torch.int64, "lengths"), self.hop_length,
-                                        mean.data_ptr(), std.data_ptr(), native._stream(lm.device))
-        return mean, std
+        return native.logmel_stats(lm, x.shape[1], lens, self.hop_length)
 
     @torch.no_grad()
     def segment_stats(self, wav: torch.Tensor, rows, starts, ends, lengths: Optional[torch.Tensor] = None):
@@ -290,14 +271,7 @@ class MelSpectrogram(torch.nn.Module):
                 if s < 0 or min(e, L) - s <= self.n_fft // 2:
                     raise ValueError(f"segment {i}: [{s}, {e}) of a {L}-sample row is not longer than the reflect padding {self.n_fft // 2}")
             seg = torch.tensor(list(zip(rows, starts, ends)), dtype=torch.int64).to(x.device)
-        n_seg = seg.shape[0]
-        mean = torch.empty(n_seg, 1, self.n_mels, dtype=torch.float32, device=x.device)
-        std = torch.empty_like(mean)
-        win, tw, desc, w = self._tables()
-        native.lib().edtts_mel_segment_stats(x.data_ptr(), B, L, native._dev_ptr(lens, torch.int64, "lengths"), seg.data_ptr(), n_seg,
-                                             self.n_fft, self.hop_length, win, tw, desc, w, self.n_mels, mean.data_ptr(), std.data_ptr(),
-                                             native._stream(x.device))
-        return mean, std
+        return native.mel_segment_stats(x, lens, seg, self.n_fft, self.hop_length, self._tables(), self.n_mels)
 
 
 def chunk_segments(totals: Sequence[int], chunk_samples: int, overlap_samples: int) -> List[List[Tuple[int, int]]]:

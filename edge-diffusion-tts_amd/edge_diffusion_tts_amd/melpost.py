@@ -15,7 +15,6 @@ published algorithm (the test suite's CPU oracle), not against outputs of the re
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -102,18 +101,9 @@ class InverseMelScale(torch.nn.Module):
             raise ValueError(f"expected {self.n_mels} mel bins, got {M}")
         if smooth is not None and mean is not None:
             raise ValueError("smooth: the box filter takes the linear mel spectrogram, not the normalised log-mel of from_normalized")
-        kh, kw = check_smooth(smooth, M) if smooth is not None else (0, 0)
+        box = check_smooth(smooth, M) if smooth is not None else None
         lens = native.lengths(lengths, B, T, mel_btm.device, "lengths")
-        p = native._dev_ptr
-        spec = torch.empty(B, self.n_stft, T, dtype=torch.float32, device=mel_btm.device)
-        head = (p(mel_btm, torch.float32, "mel"), p(mean, torch.float32, "mean"), p(std, torch.float32, "std"),
-                p(self.pinv, torch.float32, "pinv"), B, T, M, self.n_stft)
-        if lens is None and smooth is None:
-            native.lib().edtts_mel_to_spec(*head, spec.data_ptr(), native._stream(mel_btm.device))
-            return spec
-        native.lib().edtts_mel_to_spec_len(*head, p(lens, torch.int64, "lengths"), kh, kw,
-                                           None if lens is None else p(self.idx_err, torch.int32, "idx_err"), spec.data_ptr(),
-                                           native._stream(mel_btm.device))
+        spec = native.mel_to_spec(mel_btm, mean, std, self.pinv, lens, box, self.idx_err)
         if lens is not None:
             native.check_indices(self.idx_err)
         return spec
@@ -168,18 +158,8 @@ class GriffinLim(torch.nn.Module):
             raise ValueError("seeds: per-row seeds come with lengths (without lengths the batch draws from `seed`)")
         if lengths is not None:
             return self._forward_len(spec, shape, angles0, seed, lengths, seeds)
-        n = C.c_size_t(0)
-        native.lib().edtts_griffin_lim_scratch_floats(B, T, self.n_fft, self.hop, C.byref(n))
-        scratch = torch.empty(n.value, dtype=torch.float32, device=spec.device)
-        wave = torch.empty(B, self.hop * (T - 1), dtype=torch.float32, device=spec.device)
-        a0 = None
-        if angles0 is not None:
-            a0 = torch.view_as_real(angles0.reshape(B, F, T).to(torch.complex64)).contiguous()
-        p = native._dev_ptr
-        native.lib().edtts_griffin_lim(p(spec, torch.float32, "specgram"), B, T, self.n_fft, self.hop, p(self.window, torch.float32, "window"),
-                                       p(self.twiddle, torch.float32, "twiddle"), self.n_iter, float(self.momentum), float(self.power),
-                                       p(a0, torch.float32, "angles0"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), scratch.data_ptr(),
-                                       wave.data_ptr(), native._stream(spec.device))
+        a0 = None if angles0 is None else torch.view_as_real(angles0.reshape(B, F, T).to(torch.complex64)).contiguous()
+        wave = native.griffin_lim(spec, self.n_fft, self.hop, self.window, self.twiddle, self.n_iter, self.momentum, self.power, a0, seed)
         return wave.reshape(shape[:-2] + (wave.shape[-1],))
 
     def _forward_len(self, spec, shape, angles0, seed, lengths, seeds):
@@ -195,19 +175,9 @@ class GriffinLim(torch.nn.Module):
             sd = native.seed_tensor([seed] * B if seeds is None else seeds, B, spec.device)
         elif seeds is not None:
             native.seed_tensor(seeds, B, "cpu" if not isinstance(seeds, torch.Tensor) else seeds.device)  # shape check only: unused
-        n = C.c_size_t(0)
-        native.lib().edtts_griffin_lim_scratch_floats(B, T, self.n_fft, self.hop, C.byref(n))
-        scratch = torch.empty(n.value, dtype=torch.float32, device=spec.device)
-        wave = torch.empty(B, self.hop * (T - 1), dtype=torch.float32, device=spec.device)
-        a0 = None
-        if angles0 is not None:
-            a0 = torch.view_as_real(angles0.reshape(B, F, T).to(torch.complex64)).contiguous()
-        p = native._dev_ptr
-        native.lib().edtts_griffin_lim_len(p(spec, torch.float32, "specgram"), B, T, self.n_fft, self.hop, p(self.window, torch.float32, "window"),
-                                           p(self.twiddle, torch.float32, "twiddle"), self.n_iter, float(self.momentum), float(self.power),
-                                           p(a0, torch.float32, "angles0"), p(lens, torch.int64, "lengths"), p(sd, torch.int64, "seeds"),
-                                           p(self.idx_err, torch.int32, "idx_err"), scratch.data_ptr(), wave.data_ptr(),
-                                           native._stream(spec.device))
+        a0 = None if angles0 is None else torch.view_as_real(angles0.reshape(B, F, T).to(torch.complex64)).contiguous()
+        wave = native.griffin_lim(spec, self.n_fft, self.hop, self.window, self.twiddle, self.n_iter, self.momentum, self.power, a0,
+                                  t_len=lens, seeds=sd, idx_err=self.idx_err)
         native.check_indices(self.idx_err)
         return wave.reshape(shape[:-2] + (wave.shape[-1],)), (lens.clamp(1, T) - 1) * self.hop
 

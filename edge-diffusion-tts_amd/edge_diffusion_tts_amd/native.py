@@ -1,7 +1,9 @@
 """ctypes binding of libedtts_hip.so (C ABI declared in include/edtts.h).
 
-This is the only door between the Python host classes and the HIP kernels.  There is NO fallback: if the
-shared library is missing, or a tensor is not a contiguous fp32/int64 tensor on a HIP device, the call raises.
+This is the only door between the Python host classes and the HIP kernels: no other module of the package imports ctypes or
+calls lib().  Every export is bound from one table (_ABI) that tests/test_abi_host.py compares with the header.  There is NO
+fallback: if the shared library is missing, or a tensor is not a contiguous tensor of the expected dtype on a HIP device, the call
+raises.
 """
 from __future__ import annotations
 
@@ -13,31 +15,6 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EDTTS_LIB", os.path.join(os.path.dirname(_PKG_DIR), "lib", "libedtts_hip.so"))
-
-# every symbol include/edtts.h declares (tests check that the built library exports all of them)
-EXPORTED_SYMBOLS = (
-    "edtts_version", "edtts_last_error", "edtts_num_global_slots", "edtts_num_layer_slots", "edtts_global_slot_name",
-    "edtts_layer_slot_name", "edtts_packed_bytes", "edtts_pack_weights", "edtts_workspace_bytes", "edtts_decoder_forward",
-    "edtts_ddim_step", "edtts_ddpm_step", "edtts_generate", "edtts_sample_ddpm", "edtts_sample_multistep", "edtts_dsconv_forward", "edtts_profile_enable",
-    "edtts_profile_collect", "edtts_randn", "edtts_index_errors", "edtts_sample_inpaint",
-    "edtts_mel_to_spec", "edtts_griffin_lim_scratch_floats", "edtts_griffin_lim", "edtts_set_substreams", "edtts_set_coop", "edtts_dsconv_scratch_floats", "edtts_substreams_for",
-    "edtts_decoder_forward_len", "edtts_generate_len", "edtts_sample_ddpm_len", "edtts_sample_multistep_len",
-    "edtts_sample_inpaint_len", "edtts_randn_rows", "edtts_sample_inpaint_multistep_len",
-    "edtts_sem_packed_bytes", "edtts_sem_num_codes", "edtts_sem_pack", "edtts_sem_encode", "edtts_sem_decode", "edtts_sem_stats",
-    "edtts_hubert_frames", "edtts_hubert_packed_bytes", "edtts_hubert_pack", "edtts_hubert_workspace_bytes", "edtts_hubert_forward",
-    "edtts_hubert_packed_bytes_dt", "edtts_hubert_pack_dt", "edtts_hubert_workspace_bytes_dt", "edtts_hubert_forward_dt",
-    "edtts_melspec", "edtts_mel_segment_stats", "edtts_logmel_stats", "edtts_resample",
-    "edtts_mel_to_spec_len", "edtts_griffin_lim_len",
-    "edtts_train_tape_bytes", "edtts_train_scratch_bytes", "edtts_train_dw_slab_rows", "edtts_decoder_forward_train",
-    "edtts_decoder_backward",
-    "edtts_decoder_forward_train_drop", "edtts_decoder_backward_drop", "edtts_dropout_mask",
-    "edtts_sem_train_packed_bytes", "edtts_sem_train_pack", "edtts_sem_train_tape_bytes", "edtts_sem_train_scratch_bytes",
-    "edtts_sem_encode_train", "edtts_sem_backward", "edtts_sem_dropout_mask",
-    "edtts_sem_vq_train_packed_bytes", "edtts_sem_vq_train_pack", "edtts_sem_vq_tape_bytes", "edtts_sem_vq_scratch_bytes",
-    "edtts_sem_vq_encode_train", "edtts_sem_vq_ema_update", "edtts_sem_vq_backward",
-    "edtts_decoder_forward_train_len", "edtts_decoder_backward_len",
-    "edtts_optim_chunk_size", "edtts_optim_chunk_table", "edtts_optim_scratch_bytes", "edtts_optim_step", "edtts_generic_slot_dest",
-)
 
 # bits of the index-error word (include/edtts.h: EDTTS_IDX_*)
 EDTTS_IDX_SEM, EDTTS_IDX_STEP, EDTTS_IDX_LEN = 1, 2, 4
@@ -123,11 +100,114 @@ class EdttsError(RuntimeError):
     pass
 
 
+# ---------------------------------------------------------------------------------------------- the C ABI, one entry per export
+# Kinds of return: a status int (0 or a negative EDTTS_ERR_*: lib() gives it _errcheck), a plain int value, a const char*.
+_STATUS, _VALUE, _STR = "status", "value", "str"
+EDTTS_ERR_ARG = -2  # include/edtts.h: the one error code _errcheck tells apart
+
+vp, i32, i64, u32, u64, sz, f32, f64 = (C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float, C.c_double)
+p_vp, p_i32, p_i64, p_sz, p_f32, p_f64 = (C.POINTER(t) for t in (vp, i32, i64, sz, f32, f64))
+dp, sdp, hdp, drp = (C.POINTER(t) for t in (EdttsDims, EdttsSemDims, EdttsHubertDims, EdttsDropout))
+
+# include/edtts.h in its order: name -> (kind of return, argument types).  tests/test_abi_host.py compares every entry with the
+# header's prototype, so a new export is one prototype there and one line here.
+_ABI = {
+    "edtts_version": (_VALUE, ()),
+    "edtts_last_error": (_STR, ()),
+    "edtts_num_global_slots": (_VALUE, ()),
+    "edtts_num_layer_slots": (_VALUE, ()),
+    "edtts_global_slot_name": (_STR, (i32,)),
+    "edtts_layer_slot_name": (_STR, (i32,)),
+    "edtts_packed_bytes": (_STATUS, (dp, p_sz)),
+    "edtts_pack_weights": (_STATUS, (dp, p_vp, i32, vp, vp)),
+    "edtts_workspace_bytes": (_STATUS, (dp, i32, i32, i32, i32, p_sz)),
+    "edtts_index_errors": (_STATUS, (vp, p_i32, vp)),
+    "edtts_decoder_forward": (_STATUS, (dp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)),
+    "edtts_train_tape_bytes": (_STATUS, (dp, i32, i32, i32, p_sz)),
+    "edtts_train_scratch_bytes": (_STATUS, (dp, i32, i32, i32, p_sz)),
+    "edtts_train_dw_slab_rows": (_VALUE, (i32,)),
+    "edtts_decoder_forward_train": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)),
+    "edtts_decoder_backward": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, vp)),
+    "edtts_decoder_forward_train_drop": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, drp, vp)),
+    "edtts_decoder_backward_drop": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, drp, vp)),
+    "edtts_dropout_mask": (_STATUS, (dp, i32, i32, i32, i32, i32, drp, vp, vp)),
+    "edtts_decoder_forward_len": (_STATUS, (dp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp)),
+    "edtts_decoder_forward_train_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, drp, vp, vp, vp)),
+    "edtts_decoder_backward_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, drp, vp, vp,
+                                             vp)),
+    "edtts_ddim_step": (_STATUS, (vp, i32, vp, vp, vp, vp, i32, sz, f32, vp, vp, vp, vp)),
+    "edtts_ddpm_step": (_STATUS, (vp, vp, vp, vp, i32, vp, vp, vp, i32, sz, vp, vp, vp)),
+    "edtts_generate": (_STATUS, (dp, vp, vp, i32, i32, vp, vp, i32, p_i64, p_f32, vp, vp, vp)),
+    "edtts_generate_len": (_STATUS, (dp, vp, vp, i32, i32, vp, vp, vp, i32, p_i64, p_f32, vp, vp, vp)),
+    "edtts_sample_ddpm": (_STATUS, (dp, vp, vp, i32, i32, vp, vp, i32, vp, p_f32, vp, u64, i64, vp, vp)),
+    "edtts_sample_ddpm_len": (_STATUS, (dp, vp, vp, i32, i32, vp, vp, vp, i32, vp, p_f32, vp, u64, i64, vp, vp)),
+    "edtts_randn": (_STATUS, (vp, sz, u64, u32, u64, f32, vp)),
+    "edtts_randn_rows": (_STATUS, (vp, i32, sz, vp, u32, f32, vp)),
+    "edtts_sample_multistep": (_STATUS, (dp, vp, vp, i32, i32, i32, vp, vp, vp, i32, p_i64, p_f32, vp, vp, vp, vp)),
+    "edtts_sample_multistep_len": (_STATUS, (dp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, p_i64, p_f32, vp, vp, vp, vp)),
+    "edtts_sample_inpaint": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, i32, vp, u64, f32, vp, vp)),
+    "edtts_sample_inpaint_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, i32, vp, u64, f32, vp,
+                                           vp, vp, vp, vp)),
+    "edtts_sample_inpaint_multistep_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, i32, vp, u64, f32,
+                                                     vp, vp, vp, vp, vp, vp, vp)),
+    "edtts_dsconv_scratch_floats": (_STATUS, (i32, i32, i32, i32, i32, i32, i32, p_sz)),
+    "edtts_dsconv_forward": (_STATUS, (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp)),
+    "edtts_mel_to_spec": (_STATUS, (vp, vp, vp, vp, i32, i32, i32, i32, vp, vp)),
+    "edtts_griffin_lim_scratch_floats": (_STATUS, (i32, i32, i32, i32, p_sz)),
+    "edtts_griffin_lim": (_STATUS, (vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, u64, vp, vp, vp)),
+    "edtts_mel_to_spec_len": (_STATUS, (vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp)),
+    "edtts_griffin_lim_len": (_STATUS, (vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp)),
+    "edtts_profile_enable": (_STATUS, (i32,)),
+    "edtts_profile_collect": (_STATUS, (p_f64, p_i32)),  # arrays of 2
+    "edtts_set_substreams": (_VALUE, (i32,)),
+    "edtts_substreams_for": (_VALUE, (dp, i32, i32)),
+    "edtts_set_coop": (_VALUE, (i32,)),
+    "edtts_sem_packed_bytes": (_STATUS, (sdp, p_sz)),
+    "edtts_sem_num_codes": (_STATUS, (sdp, p_i64)),
+    "edtts_sem_pack": (_STATUS, (sdp, p_vp, i32, vp, vp)),
+    "edtts_sem_encode": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp)),
+    "edtts_sem_decode": (_STATUS, (sdp, vp, vp, i64, vp, vp)),
+    "edtts_sem_stats": (_STATUS, (vp, i64, vp, vp, vp)),
+    "edtts_sem_train_packed_bytes": (_STATUS, (sdp, p_sz)),
+    "edtts_sem_train_pack": (_STATUS, (sdp, p_vp, i32, vp, vp)),
+    "edtts_sem_train_tape_bytes": (_STATUS, (sdp, i32, i32, p_sz)),
+    "edtts_sem_train_scratch_bytes": (_STATUS, (sdp, i32, i32, p_sz)),
+    "edtts_sem_encode_train": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, drp, vp)),
+    "edtts_sem_backward": (_STATUS, (sdp, vp, vp, vp, vp, i32, i32, vp, vp, p_vp, i32, vp, vp, drp, vp)),
+    "edtts_sem_dropout_mask": (_STATUS, (sdp, i32, i32, drp, vp, vp)),
+    "edtts_sem_vq_train_packed_bytes": (_STATUS, (sdp, p_sz)),
+    "edtts_sem_vq_train_pack": (_STATUS, (sdp, p_vp, i32, vp, vp)),
+    "edtts_sem_vq_tape_bytes": (_STATUS, (sdp, i32, i32, p_sz)),
+    "edtts_sem_vq_scratch_bytes": (_STATUS, (sdp, i32, i32, p_sz)),
+    "edtts_sem_vq_encode_train": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, f64, drp, vp)),
+    "edtts_sem_vq_ema_update": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, f64, f64, vp, vp, vp, vp, vp)),
+    "edtts_sem_vq_backward": (_STATUS, (sdp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f64, p_vp, i32, vp, vp, drp, vp)),
+    "edtts_optim_chunk_size": (_VALUE, ()),
+    "edtts_optim_chunk_table": (_STATUS, (p_i64, i32, i32, p_i32, p_i64, p_i32, p_i32)),
+    "edtts_optim_scratch_bytes": (_STATUS, (i32, i32, p_sz)),
+    "edtts_optim_step": (_STATUS, (C.POINTER(EdttsOptimTensor), i32, C.POINTER(EdttsOptimGroup), i32, f64, i32, vp, sz, vp)),
+    "edtts_generic_slot_dest": (_STATUS, (dp, i32, p_sz, p_i32, p_i32, p_i32)),
+    "edtts_hubert_frames": (_STATUS, (hdp, i64, p_i64)),
+    "edtts_hubert_packed_bytes": (_STATUS, (hdp, p_sz)),
+    "edtts_hubert_pack": (_STATUS, (hdp, p_vp, i32, vp, vp)),
+    "edtts_hubert_workspace_bytes": (_STATUS, (hdp, i32, i32, p_sz)),
+    "edtts_hubert_forward": (_STATUS, (hdp, vp, vp, i32, i32, vp, vp, vp, vp)),
+    "edtts_hubert_packed_bytes_dt": (_STATUS, (hdp, i32, p_sz)),
+    "edtts_hubert_pack_dt": (_STATUS, (hdp, i32, p_vp, i32, vp, vp)),
+    "edtts_hubert_workspace_bytes_dt": (_STATUS, (hdp, i32, i32, i32, p_sz)),
+    "edtts_hubert_forward_dt": (_STATUS, (hdp, i32, vp, vp, i32, i32, vp, vp, vp, vp)),
+    "edtts_melspec": (_STATUS, (vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp)),
+    "edtts_mel_segment_stats": (_STATUS, (vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp)),
+    "edtts_logmel_stats": (_STATUS, (vp, i32, i32, i32, i32, vp, i32, vp, vp, vp)),
+    "edtts_resample": (_STATUS, (vp, i32, i32, vp, i32, i32, i32, i32, vp, i64, vp, vp)),
+}
+EXPORTED_SYMBOLS = tuple(_ABI)  # every symbol include/edtts.h declares (tests check that the built library exports all of them)
+
 _lib = None
 
 
 def lib() -> C.CDLL:
-    """Load the HIP library (once).  Raises if it has not been built -- there is no CPU path."""
+    """Load the HIP library (once) and bind every export from _ABI.  Raises if it has not been built -- there is no CPU path."""
     global _lib
     if _lib is not None:
         return _lib
@@ -136,117 +216,11 @@ def lib() -> C.CDLL:
             f"HIP extension not found at {LIB_PATH}; build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  The sampler path has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, i32, sz, f32 = C.c_void_p, C.c_int, C.c_size_t, C.c_float
-    L.edtts_version.restype = i32
-    L.edtts_last_error.restype = C.c_char_p
-    L.edtts_num_global_slots.restype = i32
-    L.edtts_num_layer_slots.restype = i32
-    L.edtts_global_slot_name.restype = C.c_char_p
-    L.edtts_global_slot_name.argtypes = [i32]
-    L.edtts_layer_slot_name.restype = C.c_char_p
-    L.edtts_layer_slot_name.argtypes = [i32]
-    L.edtts_packed_bytes.argtypes = [C.POINTER(EdttsDims), C.POINTER(sz)]
-    L.edtts_pack_weights.argtypes = [C.POINTER(EdttsDims), C.POINTER(vp), i32, vp, vp]
-    L.edtts_workspace_bytes.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, i32, C.POINTER(sz)]
-    L.edtts_decoder_forward.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.edtts_ddim_step.argtypes = [vp, i32, vp, vp, vp, vp, i32, sz, f32, vp, vp, vp, vp]
-    L.edtts_ddpm_step.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, sz, vp, vp, vp]
-    L.edtts_generate.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, vp, vp, i32, C.POINTER(C.c_int64),
-                                 C.POINTER(f32), vp, vp, vp]
-    L.edtts_sample_ddpm.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, vp, vp, i32, vp, C.POINTER(f32), vp, C.c_uint64, C.c_int64, vp, vp]
-    L.edtts_randn.argtypes = [vp, sz, C.c_uint64, C.c_uint32, C.c_uint64, f32, vp]
-    L.edtts_index_errors.argtypes = [vp, C.POINTER(i32), vp]
-    L.edtts_mel_to_spec.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.edtts_griffin_lim_scratch_floats.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
-    L.edtts_griffin_lim.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, C.c_uint64, vp, vp, vp]
-    L.edtts_mel_to_spec_len.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
-    L.edtts_griffin_lim_len.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
-    L.edtts_sample_inpaint.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32), vp, i32,
-                                       vp, C.c_uint64, f32, vp, vp]
-    L.edtts_sample_inpaint_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(f32),
-                                           vp, i32, vp, C.c_uint64, f32, vp, vp, vp, vp, vp]
-    L.edtts_sample_inpaint_multistep_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp,
-                                                     C.POINTER(f32), vp, i32, vp, C.c_uint64, f32, vp, vp, vp, vp, vp, vp, vp]
-    L.edtts_randn_rows.argtypes = [vp, i32, sz, vp, C.c_uint32, f32, vp]
-    L.edtts_sample_multistep.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int64),
-                                         C.POINTER(f32), vp, vp, vp, vp]
-    L.edtts_decoder_forward_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.edtts_generate_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int64),
-                                     C.POINTER(f32), vp, vp, vp]
-    L.edtts_sample_ddpm_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, vp, vp, vp, i32, vp, C.POINTER(f32), vp, C.c_uint64,
-                                        C.c_int64, vp, vp]
-    L.edtts_sample_multistep_len.argtypes = [C.POINTER(EdttsDims), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32,
-                                             C.POINTER(C.c_int64), C.POINTER(f32), vp, vp, vp, vp]
-    L.edtts_dsconv_forward.argtypes = [vp] * 6 + [i32] * 7 + [vp, vp, vp]
-    L.edtts_dsconv_scratch_floats.argtypes = [i32] * 7 + [C.POINTER(sz)]
-    sdp = C.POINTER(EdttsSemDims)
-    L.edtts_sem_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
-    L.edtts_sem_num_codes.argtypes = [sdp, C.POINTER(C.c_int64)]
-    L.edtts_sem_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
-    L.edtts_sem_encode.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.edtts_sem_decode.argtypes = [sdp, vp, vp, C.c_int64, vp, vp]
-    L.edtts_sem_stats.argtypes = [vp, C.c_int64, vp, vp, vp]
-    hdp = C.POINTER(EdttsHubertDims)
-    L.edtts_hubert_frames.argtypes = [hdp, C.c_int64, C.POINTER(C.c_int64)]
-    L.edtts_hubert_packed_bytes.argtypes = [hdp, C.POINTER(sz)]
-    L.edtts_hubert_pack.argtypes = [hdp, C.POINTER(vp), i32, vp, vp]
-    L.edtts_hubert_workspace_bytes.argtypes = [hdp, i32, i32, C.POINTER(sz)]
-    L.edtts_hubert_forward.argtypes = [hdp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.edtts_hubert_packed_bytes_dt.argtypes = [hdp, i32, C.POINTER(sz)]
-    L.edtts_hubert_pack_dt.argtypes = [hdp, i32, C.POINTER(vp), i32, vp, vp]
-    L.edtts_hubert_workspace_bytes_dt.argtypes = [hdp, i32, i32, i32, C.POINTER(sz)]
-    L.edtts_hubert_forward_dt.argtypes = [hdp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.edtts_melspec.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.edtts_mel_segment_stats.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
-    L.edtts_logmel_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
-    L.edtts_resample.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, C.c_int64, vp, vp]
-    L.edtts_train_tape_bytes.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, C.POINTER(sz)]
-    L.edtts_train_scratch_bytes.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, C.POINTER(sz)]
-    L.edtts_train_dw_slab_rows.argtypes = [i32]
-    L.edtts_train_dw_slab_rows.restype = i32
-    L.edtts_decoder_forward_train.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.edtts_decoder_backward.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
-                                         vp, vp, vp, vp]
-    dpp = C.POINTER(EdttsDropout)
-    L.edtts_decoder_forward_train_drop.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, dpp, vp]
-    L.edtts_decoder_backward_drop.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
-                                              vp, vp, vp, dpp, vp]
-    L.edtts_dropout_mask.argtypes = [C.POINTER(EdttsDims), i32, i32, i32, i32, i32, dpp, vp, vp]
-    L.edtts_decoder_forward_train_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, dpp, vp, vp, vp]
-    L.edtts_decoder_backward_len.argtypes = [C.POINTER(EdttsDims), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp), i32,
-                                             vp, vp, vp, dpp, vp, vp, vp]
-    L.edtts_sem_train_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
-    L.edtts_sem_train_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
-    L.edtts_sem_train_tape_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
-    L.edtts_sem_train_scratch_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
-    L.edtts_sem_encode_train.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, dpp, vp]
-    L.edtts_sem_backward.argtypes = [sdp, vp, vp, vp, vp, i32, i32, vp, vp, C.POINTER(vp), i32, vp, vp, dpp, vp]
-    L.edtts_sem_dropout_mask.argtypes = [sdp, i32, i32, dpp, vp, vp]
-    L.edtts_sem_vq_train_packed_bytes.argtypes = [sdp, C.POINTER(sz)]
-    L.edtts_sem_vq_train_pack.argtypes = [sdp, C.POINTER(vp), i32, vp, vp]
-    L.edtts_sem_vq_tape_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
-    L.edtts_sem_vq_scratch_bytes.argtypes = [sdp, i32, i32, C.POINTER(sz)]
-    L.edtts_sem_vq_encode_train.argtypes = [sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, C.c_double, dpp, vp]
-    L.edtts_sem_vq_ema_update.argtypes = [sdp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
-    L.edtts_sem_vq_backward.argtypes = [sdp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, C.c_double, C.POINTER(vp), i32, vp, vp, dpp, vp]
-    L.edtts_optim_chunk_size.restype = i32
-    L.edtts_optim_chunk_table.argtypes = [C.POINTER(C.c_int64), i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                          C.POINTER(i32)]
-    L.edtts_optim_scratch_bytes.argtypes = [i32, i32, C.POINTER(sz)]
-    L.edtts_optim_step.argtypes = [C.POINTER(EdttsOptimTensor), i32, C.POINTER(EdttsOptimGroup), i32, C.c_double, i32, vp, sz, vp]
-    L.edtts_generic_slot_dest.argtypes = [C.POINTER(EdttsDims), i32, C.POINTER(sz), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.edtts_profile_enable.argtypes = [i32]
-    L.edtts_set_substreams.argtypes = [i32]
-    L.edtts_set_substreams.restype = i32
-    L.edtts_set_coop.argtypes = [i32]
-    L.edtts_set_coop.restype = i32
-    L.edtts_substreams_for.argtypes = [C.POINTER(EdttsDims), i32, i32]
-    L.edtts_substreams_for.restype = i32
-    L.edtts_profile_collect.argtypes = [C.POINTER(C.c_double), C.POINTER(i32)]  # arrays of 2
-    for name in EXPORTED_SYMBOLS:
+    for name, (kind, argtypes) in _ABI.items():
         fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("edtts_version", "edtts_num_global_slots", "edtts_num_layer_slots", "edtts_set_substreams", "edtts_set_coop", "edtts_substreams_for",
-                                                  "edtts_train_dw_slab_rows", "edtts_optim_chunk_size"):
+        fn.argtypes = list(argtypes)
+        fn.restype = C.c_char_p if kind == _STR else C.c_int
+        if kind == _STATUS:
             fn.errcheck = _errcheck
     _lib = L
     return L
@@ -255,8 +229,8 @@ def lib() -> C.CDLL:
 def _errcheck(rc, func, args):
     if rc != 0:
         msg = _lib.edtts_last_error().decode() if _lib is not None else "?"
-        # -2 = argument errors: the reference raises ValueError / IndexError / RuntimeError for these
-        if rc == -2 and "Either sem_idx or sem_features" in msg:
+        # argument errors: the reference raises ValueError / IndexError / RuntimeError for these
+        if rc == EDTTS_ERR_ARG and "Either sem_idx or sem_features" in msg:
             raise ValueError(msg)
         raise EdttsError(f"{func.__name__} failed (code {rc}): {msg}")
     return rc
@@ -277,6 +251,11 @@ def _dev_ptr(t: Optional[torch.Tensor], dtype: torch.dtype, name: str) -> Option
 
 def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _u64(v: int):
+    """A Python int (a seed: any size, any sign) as the uint64 of its low 64 bits."""
+    return C.c_uint64(v & 0xFFFFFFFFFFFFFFFF)
 
 
 def _size_query(fn, *args, ctype=C.c_size_t) -> int:
@@ -479,7 +458,7 @@ def sample_ddpm(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tensor, 
     out = torch.empty_like(x_T)
     head = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), B, S, _dev_ptr(sem_idx, torch.int64, "sem_idx"))
     tail = (_dev_ptr(x_T, torch.float32, "x_T"), n, _dev_ptr(t_all, torch.int64, "t_all"), cf, _dev_ptr(noise_all, torch.float32, "noise"),
-            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_int64(int(batch_offset)), out.data_ptr(), _stream(x_T.device))
+            _u64(seed), C.c_int64(int(batch_offset)), out.data_ptr(), _stream(x_T.device))
     if s_len is None:
         lib().edtts_sample_ddpm(*head, *tail)
     else:
@@ -530,7 +509,7 @@ def sample_inpaint(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tenso
     args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), None if workspace_uncond is None else workspace_uncond.data_ptr(),
             B, T, sem_features.shape[1], _dev_ptr(sem_features, f, "sem_features"), _dev_ptr(zero_features, f, "zeros"), _dev_ptr(x, f, "x"),
             n, t_all.data_ptr(), step_all.data_ptr(), cf, _dev_ptr(known_mel, f, "known_mel"), int(overlap_len),
-            _dev_ptr(noise_k, f, "noise_k"), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), float(cfg_scale),
+            _dev_ptr(noise_k, f, "noise_k"), _u64(seed), float(cfg_scale),
             None if v_uncond is None else v_uncond.data_ptr(), _dev_ptr(t_len, torch.int64, "x_lengths"),
             _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(seeds, torch.int64, "seeds"))
     x0_all = None
@@ -578,15 +557,111 @@ def dsconv_forward(x, dw, pw, pb, gn_w, gn_b, groups: int, stride: int = 1) -> t
     if To < 1:
         raise EdttsError(f"dsconv: no output frames for T={T}, kernel_size={ks}, stride={stride}")
     y = torch.empty(B, Co, To, device=x.device, dtype=torch.float32)
-    need = C.c_size_t(0)
-    lib().edtts_dsconv_scratch_floats(B, Ci, Co, T, ks, int(stride), groups, C.byref(need))  # 0: the one-kernel path
-    scratch = torch.empty(need.value, device=x.device, dtype=torch.float32) if need.value else None
+    need = _size_query(lib().edtts_dsconv_scratch_floats, B, Ci, Co, T, ks, int(stride), groups)  # 0: the one-kernel path
+    scratch = torch.empty(need, device=x.device, dtype=torch.float32) if need else None
     f = torch.float32
     lib().edtts_dsconv_forward(_dev_ptr(x, f, "x"), _dev_ptr(dw, f, "depthwise.weight"), _dev_ptr(pw, f, "pointwise.weight"),
                                _dev_ptr(pb, f, "pointwise.bias"), _dev_ptr(gn_w, f, "norm.weight"), _dev_ptr(gn_b, f, "norm.bias"),
                                B, Ci, Co, T, ks, int(stride), groups, None if scratch is None else scratch.data_ptr(), y.data_ptr(),
                                _stream(x.device))
     return y
+
+
+# ---------------------------------------------------------------------------------------------- mel post-processing, audio front end
+def mel_to_spec(mel: torch.Tensor, mean: Optional[torch.Tensor], std: Optional[torch.Tensor], pinv: torch.Tensor,
+                t_len: Optional[torch.Tensor] = None, smooth: Optional[Tuple[int, int]] = None,
+                idx_err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mel [B, T, n_mels] (mean / std [B, n_mels] or None), pinv [n_freqs, n_mels] -> spec [B, n_freqs, T] (include/edtts.h:
+    edtts_mel_to_spec).  With t_len (device int64 [B]) or smooth = (mel bins, frames) edtts_mel_to_spec_len runs; idx_err: the int32
+    word a bad t_len is flagged in."""
+    B, T, M = mel.shape
+    f = torch.float32
+    spec = torch.empty(B, pinv.shape[0], T, dtype=f, device=mel.device)
+    head = (_dev_ptr(mel, f, "mel"), _dev_ptr(mean, f, "mean"), _dev_ptr(std, f, "std"), _dev_ptr(pinv, f, "pinv"), B, T, M, pinv.shape[0])
+    if t_len is None and smooth is None:
+        lib().edtts_mel_to_spec(*head, spec.data_ptr(), _stream(mel.device))
+    else:
+        kh, kw = smooth if smooth is not None else (0, 0)
+        lib().edtts_mel_to_spec_len(*head, _dev_ptr(t_len, torch.int64, "lengths"), kh, kw,
+                                    None if t_len is None else _dev_ptr(idx_err, torch.int32, "idx_err"), spec.data_ptr(),
+                                    _stream(mel.device))
+    return spec
+
+
+def griffin_lim(spec: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, twiddle: torch.Tensor, n_iter: int, momentum: float,
+                power: float, angles0: Optional[torch.Tensor], seed: int = 0, t_len: Optional[torch.Tensor] = None,
+                seeds: Optional[torch.Tensor] = None, idx_err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """spec [B, n_fft // 2 + 1, T] -> wave [B, hop * (T - 1)] (include/edtts.h: edtts_griffin_lim).  angles0: fp32 [B, F, T, 2] or None
+    (library draws from `seed`).  With t_len (device int64 [B]) edtts_griffin_lim_len runs: seeds (device int64 [B]) replace `seed`,
+    idx_err is the int32 word a bad length is flagged in."""
+    B, _, T = spec.shape
+    f = torch.float32
+    scratch = torch.empty(_size_query(lib().edtts_griffin_lim_scratch_floats, B, T, n_fft, hop), dtype=f, device=spec.device)
+    wave = torch.empty(B, hop * (T - 1), dtype=f, device=spec.device)
+    head = (_dev_ptr(spec, f, "specgram"), B, T, n_fft, hop, _dev_ptr(window, f, "window"), _dev_ptr(twiddle, f, "twiddle"), n_iter,
+            float(momentum), float(power), _dev_ptr(angles0, f, "angles0"))
+    tail = (scratch.data_ptr(), wave.data_ptr(), _stream(spec.device))
+    if t_len is None:
+        lib().edtts_griffin_lim(*head, _u64(seed), *tail)
+    else:
+        lib().edtts_griffin_lim_len(*head, _dev_ptr(t_len, torch.int64, "lengths"), _dev_ptr(seeds, torch.int64, "seeds"),
+                                    _dev_ptr(idx_err, torch.int32, "idx_err"), *tail)
+    return wave
+
+
+def resample(x: torch.Tensor, t_len: Optional[torch.Tensor], orig: int, new: int, width: int, taps: int, table: torch.Tensor,
+             L_out: int) -> torch.Tensor:
+    """x [B, L] -> y [B, L_out] through the polyphase `table` (include/edtts.h: edtts_resample); t_len: device int64 [B] or None."""
+    B, L = x.shape
+    y = torch.empty(B, L_out, dtype=torch.float32, device=x.device)
+    lib().edtts_resample(_dev_ptr(x, torch.float32, "waveform"), B, L, _dev_ptr(t_len, torch.int64, "lengths"), orig, new, width, taps,
+                         _dev_ptr(table, torch.float32, "table"), L_out, y.data_ptr(), _stream(x.device))
+    return y
+
+
+EDTTS_MEL_POWER, EDTTS_MEL_LOG = 0, 1  # include/edtts.h: the `mode` of edtts_melspec
+
+
+def melspec(x: torch.Tensor, t_len: Optional[torch.Tensor], n_fft: int, hop: int, tables, n_mels: int, power: int, mode: int) -> torch.Tensor:
+    """x [B, L] -> the mel [B, n_mels, T] (mode EDTTS_MEL_POWER) or the log-mel [B, T, n_mels] (EDTTS_MEL_LOG), T = L // hop + 1
+    (include/edtts.h: edtts_melspec).  tables: (window, twiddle, fb_desc, fb_weights); t_len: device int64 [B] samples or None."""
+    B, L = x.shape
+    T = L // hop + 1
+    f = torch.float32
+    out = torch.empty((B, n_mels, T) if mode == EDTTS_MEL_POWER else (B, T, n_mels), dtype=f, device=x.device)
+    window, twiddle, fb_desc, fb_weights = tables
+    lib().edtts_melspec(_dev_ptr(x, f, "waveform"), B, L, _dev_ptr(t_len, torch.int64, "lengths"), n_fft, hop, _dev_ptr(window, f, "window"),
+                        _dev_ptr(twiddle, f, "twiddle"), _dev_ptr(fb_desc, torch.int32, "fb_desc"), _dev_ptr(fb_weights, f, "fb_weights"),
+                        n_mels, power, mode, out.data_ptr(), _stream(x.device))
+    return out
+
+
+def logmel_stats(logmel: torch.Tensor, L: int, t_len: Optional[torch.Tensor], hop: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean, std), each [B, 1, n_mels], of every row's own frames of the log-mel [B, T, n_mels] that melspec wrote for L-sample rows
+    (include/edtts.h: edtts_logmel_stats)."""
+    B, T, M = logmel.shape
+    mean = torch.empty(B, 1, M, dtype=torch.float32, device=logmel.device)
+    std = torch.empty_like(mean)
+    lib().edtts_logmel_stats(_dev_ptr(logmel, torch.float32, "logmel"), B, T, M, L, _dev_ptr(t_len, torch.int64, "lengths"), hop,
+                             mean.data_ptr(), std.data_ptr(), _stream(logmel.device))
+    return mean, std
+
+
+def mel_segment_stats(x: torch.Tensor, t_len: Optional[torch.Tensor], segments: torch.Tensor, n_fft: int, hop: int, tables,
+                      n_mels: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean, std), each [n_seg, 1, n_mels], of the log-mel of every (row, start, end) of `segments` (device int64 [n_seg, 3]) taken
+    as a waveform of its own (include/edtts.h: edtts_mel_segment_stats).  tables: as melspec."""
+    B, L = x.shape
+    n_seg = segments.shape[0]
+    mean = torch.empty(n_seg, 1, n_mels, dtype=torch.float32, device=x.device)
+    std = torch.empty_like(mean)
+    window, twiddle, fb_desc, fb_weights = tables
+    f = torch.float32
+    lib().edtts_mel_segment_stats(_dev_ptr(x, f, "waveform"), B, L, _dev_ptr(t_len, torch.int64, "lengths"),
+                                  _dev_ptr(segments, torch.int64, "segments"), n_seg, n_fft, hop, _dev_ptr(window, f, "window"),
+                                  _dev_ptr(twiddle, f, "twiddle"), _dev_ptr(fb_desc, torch.int32, "fb_desc"),
+                                  _dev_ptr(fb_weights, f, "fb_weights"), n_mels, mean.data_ptr(), std.data_ptr(), _stream(x.device))
+    return mean, std
 
 
 def randn(shape, device, seed: int = 0, stream_id: int = 0, elem_offset: int = 0, scale: float = 1.0) -> torch.Tensor:
@@ -604,7 +679,7 @@ def randn(shape, device, seed: int = 0, stream_id: int = 0, elem_offset: int = 0
         lo, hi = off - off % 4, -(-(off + n) // 4) * 4
         cover = randn((hi - lo,), device, seed, stream_id, lo, scale)
         return cover[off - lo: off - lo + n].reshape(out.shape).clone()
-    lib().edtts_randn(out.data_ptr(), out.numel(), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint32(stream_id & 0xFFFFFFFF),
+    lib().edtts_randn(out.data_ptr(), out.numel(), _u64(seed), C.c_uint32(stream_id & 0xFFFFFFFF),
                       C.c_uint64(int(elem_offset)), float(scale), _stream(out.device))
     return out
 
@@ -736,6 +811,12 @@ def sem_pack(dims: EdttsSemDims, tensors: Sequence[torch.Tensor], packed: torch.
     lib().edtts_sem_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
 
 
+def _check_sem_width(dims: EdttsSemDims, D: int) -> None:
+    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
+    if D != want_d:
+        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+
+
 def _aligned(t: torch.Tensor) -> torch.Tensor:
     t = t.contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone()
@@ -748,9 +829,7 @@ def sem_encode(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, length
     if h.dim() != 3:
         raise ValueError(f"expected features [B, T, D], got shape {list(h.shape)}")
     B, T, D = h.shape
-    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
-    if D != want_d:
-        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+    _check_sem_width(dims, D)
     h = _aligned(h)
     dev = h.device
     S = dims.semantic_dim
@@ -814,9 +893,7 @@ def sem_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, 
     (idx, z_q, counts or None) as sem_encode, with the backward's tape written to `tape` (uint8, sem_train_tape_bytes).  ``drop``:
     None, an EdttsDropout or a (p, seed) pair."""
     B, T, D = h.shape
-    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
-    if D != want_d:
-        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+    _check_sem_width(dims, D)
     dev = h.device
     idx = torch.empty((B, T), dtype=torch.int64, device=dev)
     zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
@@ -882,9 +959,7 @@ def sem_vq_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tenso
     (idx, z_q, counts, vq_loss 0-dim) with the backward's tape written to `tape` (uint8, sem_vq_tape_bytes).  ``drop``: None, an
     EdttsDropout or a (p, seed) pair."""
     B, T, D = h.shape
-    want_d = dims.in_dim if dims.in_dim else dims.semantic_dim
-    if D != want_d:
-        raise ValueError(f"feature width {D} does not match the head's input width {want_d}")
+    _check_sem_width(dims, D)
     dev = h.device
     idx = torch.empty((B, T), dtype=torch.int64, device=dev)
     zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
