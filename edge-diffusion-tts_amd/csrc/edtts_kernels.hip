@@ -2755,6 +2755,7 @@ struct Launcher16 {
 #include "edtts_hubert16.h"
 #include "edtts_audio.h"
 #include "edtts_optim.h"
+#include "edtts_objective.h"
 
 // compiled decoder shapes: (hidden, heads, n_mels).  EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, body) runs `body` with LN = the fused
 // launcher of lo's shape, or the statement MISS16 / MISS32 when none is compiled; EDTTS_DISPATCH adds the generic launcher (lo.GEN)

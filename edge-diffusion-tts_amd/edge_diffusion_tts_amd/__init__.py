@@ -19,6 +19,7 @@ from .encoder import FSQ, FSQEncoder, SemanticEncoder, VectorQuantizer
 from .hubert import NativeHubert
 from .audio import MelSpectrogram, Resample, chunk_stats_from_audio, resample
 from .optim import FusedAdamW
+from .objective import DiffusionObjective
 
 __all__ = [
     "CFG", "TrainPhase", "get_device", "set_seed", "DiffusionSchedule", "DPMSolverPP", "EdgeDiffusionDecoder", "EdgeInference",
@@ -26,5 +27,5 @@ __all__ = [
     "GriffinLim", "InverseMelScale", "MelVocoder", "denormalize_mel", "normalize_mel",
     "SemanticEncoder", "VectorQuantizer", "FSQ", "FSQEncoder", "NativeHubert",
     "MelSpectrogram", "Resample", "resample", "chunk_stats_from_audio",
-    "FusedAdamW",
+    "FusedAdamW", "DiffusionObjective",
 ]

@@ -82,6 +82,8 @@ class EdttsOptimTensor(C.Structure):
 
 
 OPT_CLIP, OPT_SKIP_NONFINITE, OPT_ZERO_GRADS, OPT_EMA_ONLY = 1, 2, 4, 8  # include/edtts.h: EDTTS_OPT_*
+EDTTS_OBJ_V, EDTTS_OBJ_EPS, EDTTS_OBJ_DISTILL, EDTTS_OBJ_CONSISTENCY = 0, 1, 2, 3  # include/edtts.h: the kinds of edtts_objective_loss
+OBJ_NOISE_STREAM = 0x54  # include/edtts.h, "Philox stream ids": training q_sample noise
 
 
 class EdttsHubertDims(_Dims):
@@ -200,6 +202,11 @@ _ABI = {
     "edtts_mel_segment_stats": (_STATUS, (vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp)),
     "edtts_logmel_stats": (_STATUS, (vp, i32, i32, i32, i32, vp, i32, vp, vp, vp)),
     "edtts_resample": (_STATUS, (vp, i32, i32, vp, i32, i32, i32, i32, vp, i64, vp, vp)),
+    "edtts_objective_scratch_bytes": (_STATUS, (i32, i32, i32, p_sz)),
+    "edtts_objective_stats": (_STATUS, (vp, i32, i32, i32, vp, vp, vp, vp)),
+    "edtts_objective_prepare": (_STATUS, (vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp)),
+    "edtts_objective_loss": (_STATUS, (i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp, vp)),
+    "edtts_objective_scale": (_STATUS, (vp, vp, sz, vp, vp)),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)  # every symbol include/edtts.h declares (tests check that the built library exports all of them)
 
@@ -787,6 +794,96 @@ def optim_step(tensors, n_tensors: int, groups, n_groups: int, max_norm: Optiona
         flags |= OPT_CLIP
     lib().edtts_optim_step(tensors, n_tensors, groups, n_groups, 0.0 if max_norm is None else float(max_norm), flags,
                            _dev_ptr(scratch, torch.uint8, "scratch"), scratch.numel(), _stream(scratch.device))
+
+
+# ---------------------------------------------------------------------------------------------- training objective
+class ObjBatch:
+    """The arguments that define a prepared batch for edtts_objective_prepare / edtts_objective_loss (include/edtts.h, "training
+    objective"), validated once: mel [B, T, M] fp32; t int64 [B]; tables fp32 [4, n_table]; mean / std [B, 1, M] or None; lengths and
+    seeds device int64 [B] or None; noise [B, T, M] or None.  Everything contiguous on mel's device."""
+
+    def __init__(self, mel, t, tables, mean=None, std=None, lengths=None, seeds=None, noise=None):
+        f = torch.float32
+        _dev_ptr(mel, f, "mel")
+        if mel.dim() != 3:
+            raise EdttsError(f"mel: expected [B, T, n_mels], got {list(mel.shape)}")
+        B, T, M = mel.shape
+        self.mel, self.t, self.tables, self.mean, self.std, self.lengths, self.seeds, self.noise = mel, t, tables, mean, std, lengths, seeds, noise
+        self.B, self.T, self.M = B, T, M
+        for name, v, dt, shape in (("t", t, torch.int64, (B,)), ("tables", tables, f, (4, tables.shape[-1] if tables is not None else 0)),
+                                   ("mean", mean, f, (B, 1, M)), ("std", std, f, (B, 1, M)), ("lengths", lengths, torch.int64, (B,)),
+                                   ("seeds", seeds, torch.int64, (B,)), ("noise", noise, f, (B, T, M))):
+            if v is None:
+                continue
+            _dev_ptr(v, dt, name)
+            if tuple(v.shape) != shape:
+                raise EdttsError(f"{name}: expected shape {list(shape)}, got {list(v.shape)}")
+            if v.device != mel.device:
+                raise EdttsError(f"{name}: on {v.device}, the call runs on {mel.device}")
+        if seeds is None and noise is None:
+            raise EdttsError("objective: either seeds or noise must be given")
+
+    def head(self):
+        """(mel, B, T, n_mels, lengths, t, tables, n_table, mean, std, seeds, noise) as the two calls take them."""
+        ptr = lambda v: None if v is None else v.data_ptr()
+        return (self.mel.data_ptr(), self.B, self.T, self.M, ptr(self.lengths), self.t.data_ptr(), self.tables.data_ptr(),
+                self.tables.shape[1], ptr(self.mean), ptr(self.std), ptr(self.seeds), ptr(self.noise))
+
+
+def objective_scratch_bytes(B: int, T: int, n_mels: int) -> int:
+    return _size_query(lib().edtts_objective_scratch_bytes, int(B), int(T), int(n_mels))
+
+
+def objective_stats(mel: torch.Tensor, lengths: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """normalize_mel's (mean, std), each [B, 1, n_mels], over every row's live frames (include/edtts.h: edtts_objective_stats)."""
+    _dev_ptr(mel, torch.float32, "mel")
+    B, T, M = mel.shape
+    mean = torch.empty(B, 1, M, dtype=torch.float32, device=mel.device)
+    std = torch.empty_like(mean)
+    lib().edtts_objective_stats(mel.data_ptr(), B, T, M, _dev_ptr(lengths, torch.int64, "lengths"), mean.data_ptr(), std.data_ptr(),
+                                _stream(mel.device))
+    return mean, std
+
+
+def objective_prepare(batch: ObjBatch, kind: int, parts: bool = False):
+    """edtts_objective_prepare: x_t, and with ``parts`` also (mel_n, noise, target), each [B, T, n_mels]."""
+    x_t = torch.empty_like(batch.mel)
+    extra = tuple(torch.empty_like(batch.mel) for _ in range(3)) if parts else (None, None, None)
+    lib().edtts_objective_prepare(*batch.head(), int(kind), x_t.data_ptr(), *[None if e is None else e.data_ptr() for e in extra],
+                                  _stream(x_t.device))
+    return (x_t, *extra) if parts else x_t
+
+
+def objective_loss(kind: int, batch: ObjBatch, pred: torch.Tensor, pred2: Optional[torch.Tensor], t2: Optional[torch.Tensor],
+                   want_unit: bool, want_unit2: bool, scratch: torch.Tensor):
+    """edtts_objective_loss -> (out fp32 [8]: loss | 3 terms | x0_mse | x0_cos | 0 | 0, unit or None, unit2 or None)."""
+    f = torch.float32
+    for name, p in (("pred", pred), ("pred2", pred2)):
+        if p is None:
+            continue
+        _dev_ptr(p, f, name)
+        if p.dim() != 3 or p.shape[0] != batch.B or p.shape[2] != batch.M or p.device != batch.mel.device:
+            raise EdttsError(f"{name}: expected [{batch.B}, T_pred, {batch.M}] on {batch.mel.device}, got {list(p.shape)} on {p.device}")
+    if t2 is not None and (_dev_ptr(t2, torch.int64, "t2") is None or tuple(t2.shape) != (batch.B,)):
+        raise EdttsError(f"t2: expected shape [{batch.B}], got {list(t2.shape)}")
+    out = torch.empty(8, dtype=f, device=pred.device)
+    unit = torch.empty_like(pred) if want_unit else None
+    unit2 = torch.empty_like(pred2) if want_unit2 else None
+    ptr = lambda v: None if v is None else v.data_ptr()
+    lib().edtts_objective_loss(int(kind), *batch.head(), pred.data_ptr(), pred.shape[1], ptr(pred2), 0 if pred2 is None else pred2.shape[1],
+                               ptr(t2), ptr(unit), ptr(unit2), _dev_ptr(scratch, torch.uint8, "scratch"), scratch.numel(), out.data_ptr(),
+                               _stream(pred.device))
+    return out, unit, unit2
+
+
+def objective_scale(unit: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+    """d_pred = unit * grad_out (a 0-dim fp32 device tensor, read on the device: no synchronisation)."""
+    d = torch.empty_like(unit)
+    if grad_out.numel() != 1 or grad_out.device != unit.device:
+        raise EdttsError(f"grad_out: expected one element on {unit.device}, got {list(grad_out.shape)} on {grad_out.device}")
+    lib().edtts_objective_scale(_dev_ptr(unit, torch.float32, "unit"), _dev_ptr(grad_out.contiguous(), torch.float32, "grad_out"),
+                                unit.numel(), d.data_ptr(), _stream(unit.device))
+    return d
 
 
 def generic_slot_dest(dims: EdttsDims, slot: int) -> Tuple[int, int, int, bool]:

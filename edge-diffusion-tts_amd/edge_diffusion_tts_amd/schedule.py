@@ -6,7 +6,7 @@ to the oracle's, then moved with ``.to(device)``.  ``get_ddim_step`` (schedule.p
 (schedule.py:204-238) run as hand-written HIP kernels through the C ABI (include/edtts.h: edtts_ddim_step,
 edtts_ddpm_step); there is no CPU fallback for them -- CPU tensors raise.
 The light-weight algebra helpers (q_sample, predict_*, get_v_target) are not part of the sampler hot loop
-and stay ordinary torch expressions.
+and stay ordinary torch expressions; the training loop's use of them runs on kernels in DiffusionObjective (objective.py).
 """
 from __future__ import annotations
 

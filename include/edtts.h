@@ -333,7 +333,8 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
  * Philox stream ids.  Every draw of the library is keyed (seed, stream id, global element).  The id space is split so that two
  * draws made with one seed can never coincide:
  *     [0x00000, 0x10000)  edtts_randn callers (0 = start noise of generate_mel / sample_ddpm; the host-side long-form sampler
- *                         uses 0x51 start noise, 0x52 q_sample noise of the teacher refinement, 0x53 per-chunk coarse noise)
+ *                         uses 0x51 start noise, 0x52 q_sample noise of the teacher refinement, 0x53 per-chunk coarse noise;
+ *                         0x54 training q_sample noise: edtts_objective_prepare / edtts_objective_loss, element e of a row)
  *     0x10000 + step      ancestral noise of step `step` inside edtts_sample_ddpm
  *     0x20000 + step      q_sample noise of the known frames at step `step` inside edtts_sample_inpaint and
  *                         edtts_sample_inpaint_multistep_len (one sampler or the other runs on a seed: the same draws)
@@ -821,6 +822,48 @@ int edtts_logmel_stats(const float* logmel, int B, int T, int n_mels, int L, con
                        void* stream);
 int edtts_resample(const float* x, int B, int L, const int64_t* lengths, int orig, int new_freq, int width, int taps, const float* table,
                    int64_t L_out, float* y, void* stream);
+
+/* ---- training objective  (train_v2.py:107-163, edge_diffusion_tts/train.py:143-158, training/consistency.py:60-122) ------------------
+ * What stands between the decoder's prediction and the optimiser: normalize_mel, q_sample, the target, F.mse_loss with its gradient,
+ * and the logging metrics, for a batch mel [B, T, n_mels] (raw log-mel with mean / stdv [B, n_mels]; already normalised with both NULL).
+ *   mel_n  = (mel - mean) / stdv                         x_t    = sqrt_ab[t] mel_n + sqrt_1mab[t] noise
+ *   target = sqrt_ab[t] noise - sqrt_1mab[t] mel_n  (EDTTS_OBJ_V)   or   noise  (EDTTS_OBJ_EPS)
+ * every operation rounded on its own, in the reference's order.  tables: fp32 [4][n_table] = sqrt_alpha_bar | sqrt_one_minus_alpha_bar |
+ * sqrt_recip_alpha_bar | sqrt_recip_alpha_bar_minus_one; t int64 [B], clamped into the table.
+ * noise: a tensor [B, T, n_mels], or NULL: then element e of row b is lane e & 3 of draw e >> 2 of the Philox stream (seeds[b], 0x54),
+ * bitwise edtts_randn_rows(B, T n_mels, seeds, 0x54, 1).  It is generated in registers, and edtts_objective_loss generates it again
+ * instead of reading it back.  lengths int64 [B] or NULL, clamped into [1, T]: the live frames of each row.
+ * edtts_objective_stats: normalize_mel's mean and unbiased std (clamped at 1e-5; NaN for a one-frame row, as torch.std) of every
+ *   (row, mel bin) over the row's live frames, accumulated in fp64 in a fixed order -> mean / stdv [B, n_mels].
+ * edtts_objective_prepare: x_t [B, T, n_mels], and mel_n / noise_out / target (same shape) where the pointer is not NULL.
+ * edtts_objective_loss: pred [B, T_pred, n_mels]; the means run over the first Tm = min(T, T_pred[, T_pred2]) frames (the reference's
+ *   "align sequence lengths"), with lengths over the sum_b min(len_b, Tm) n_mels live elements.  With x0(p, t) = sqrt_ab[t] x_t -
+ *   sqrt_1mab[t] p (predict_x0_from_v; for EDTTS_OBJ_EPS predict_x0_from_eps):
+ *     EDTTS_OBJ_V / EDTTS_OBJ_EPS   mse(pred, target)
+ *     EDTTS_OBJ_DISTILL             mse(x0(pred, t), x0(pred2, t)), pred2 the teacher's prediction (no gradient)
+ *     EDTTS_OBJ_CONSISTENCY         mse(x0_1, x0_2) + 0.5 (mse(x0_1, mel_n) + mse(x0_2, mel_n)), x0_1 = x0(pred, t), x0_2 = x0(pred2, t2)
+ *                                   on x_t2 = q_sample(mel_n, t2, the same noise); x0_2 is detached in the first term
+ *   unit [B, T_pred, n_mels] (and unit2 [B, T_pred2, n_mels], EDTTS_OBJ_CONSISTENCY only): d loss / d pred (d pred2) for an upstream
+ *   gradient of 1; NULL: not written.  out: fp32 [8] = loss | the three terms as means (unused ones 0) | x0_mse = mse(x0_1, mel_n) |
+ *   x0_cos = mean over rows of F.cosine_similarity of the flattened live elements (eps 1e-8) | 0 | 0.
+ *   scratch: edtts_objective_scratch_bytes(B, max(T_pred, T_pred2), n_mels) bytes, 8-byte aligned, any contents.
+ * edtts_objective_scale: d_pred[i] = unit[i] * grad_out[0] for i < n; grad_out is read on the device.
+ * Contract of all calls: no allocation, no host synchronisation (graph-capturable).  Nothing past a row's length is ever loaded: NaN in
+ * the padding of mel, noise, pred or pred2 or in the scratch changes no bit.  x_t, mel_n, noise_out, target, unit and unit2 are exactly
+ * 0 past the lengths.  A row is bitwise the same alone or in any batch; every sum has one fixed order (per thread in quad order, lanes
+ * by butterfly, waves in wave order, then in fp64 a row's chunks in ascending order and the rows in ascending order).  The float4 path
+ * (all pointers 16-byte aligned, T n_mels and T_pred n_mels multiples of 4) and the per-element path give the same bits. */
+enum { EDTTS_OBJ_V = 0, EDTTS_OBJ_EPS = 1, EDTTS_OBJ_DISTILL = 2, EDTTS_OBJ_CONSISTENCY = 3 };
+int edtts_objective_scratch_bytes(int B, int T, int n_mels, size_t* out_bytes);
+int edtts_objective_stats(const float* mel, int B, int T, int n_mels, const int64_t* lengths, float* mean, float* stdv, void* stream);
+int edtts_objective_prepare(const float* mel, int B, int T, int n_mels, const int64_t* lengths, const int64_t* t, const float* tables,
+                            int n_table, const float* mean, const float* stdv, const uint64_t* seeds, const float* noise, int kind,
+                            float* x_t, float* mel_n, float* noise_out, float* target, void* stream);
+int edtts_objective_loss(int kind, const float* mel, int B, int T, int n_mels, const int64_t* lengths, const int64_t* t,
+                         const float* tables, int n_table, const float* mean, const float* stdv, const uint64_t* seeds,
+                         const float* noise, const float* pred, int T_pred, const float* pred2, int T_pred2, const int64_t* t2,
+                         float* unit, float* unit2, void* scratch, size_t scratch_bytes, float* out, void* stream);
+int edtts_objective_scale(const float* unit, const float* grad_out, size_t n, float* d_pred, void* stream);
 
 #ifdef __cplusplus
 }
