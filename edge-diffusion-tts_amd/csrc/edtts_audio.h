@@ -21,8 +21,6 @@
 // Welford chain per wave over the frames t = w, w + W, ... (W = kStatWaves) followed by Chan's combination of the W partials in wave
 // order -- independent of B, of the grid and of the other segments.  The frame math is compiled with fp contraction off, so the
 // fused <1> and the two-kernel path produce the same bits.  No float atomics.
-#pragma once
-
 namespace edtts_audio {
 using melpost::cplx;
 

@@ -21,8 +21,6 @@
 //   [d-tile][16 d][32 key-slots] with the keys of a chunk in slot order (position 8 g' + 4 t + r <-> key 16 t + 4 g' + r), which is
 //   what a lane of the SWAPPED product (activations as A, weights as B: C/D = [frame][feature]) holds.  Every K / v^T operand
 //   tile is one contiguous KiB: one 16-byte store per lane when written, one fully coalesced load per wave when read.
-#pragma once
-
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 typedef float f2v __attribute__((ext_vector_type(2)));

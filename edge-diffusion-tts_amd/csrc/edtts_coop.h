@@ -16,9 +16,6 @@
 // A block is the W waves of one tile.  (The two-wave blocks of W = 2 need > 256 registers per wave and 60 KiB of LDS: two blocks
 // per CU, on different SIMDs.)  Weight fragments are read straight from the packed stream of k_layer (edtts_pack_weights) at
 // computed offsets -- no second weight layout.
-#pragma once
-#include "edtts_device.h"
-
 namespace edtts {
 
 template <class C, int W>

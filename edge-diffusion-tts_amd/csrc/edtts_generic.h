@@ -15,8 +15,6 @@
 //   k_gen_tail<TAIL>   the sampler updates of the fused tails, elementwise: tail_apply (vector path) or the same helpers per element
 //
 // Activations are plain row-major [rows][features] fp32 in the workspace; weights are the state-dict's own [N][K] matrices.
-#pragma once
-
 namespace edtts_gen {
 
 enum { EPI_BIAS = 0, EPI_PE = 1, EPI_RESID = 2, EPI_SWIGLU = 3 };

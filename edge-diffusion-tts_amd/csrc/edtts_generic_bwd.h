@@ -21,8 +21,8 @@
 // Dropout: k_gen_attn<DT, true> / k_gen_gemm<EPI, true> in the forward; k_bwd_attn_dq<DT, true> and
 // k_bwd_attn_dkv<DT, true> regenerate the attention masks, k_bwd_swiglu_drop and k_bwd_drop_rows the feed-forward ones.
 // k_drop_mask writes a mask out.
-#pragma once
-
+// Behind the kernels: the tape and scratch layouts, TrainLauncher, and the C ABI of training (edtts_train_*,
+// edtts_decoder_forward_train*, edtts_decoder_backward*, edtts_dropout_mask).
 namespace edtts_bwd {
 using edtts_gen::wave_allsum;
 
@@ -1043,3 +1043,148 @@ struct TrainLauncher {
     return EDTTS_OK;
   }
 };
+
+// =========================================================================================================
+// the C ABI of training: a forward that keeps a tape, the backward from it, the dropout masks
+// =========================================================================================================
+// EdttsDropout -> DropState.  *on = false for NULL or p == 0 (the call then makes exactly the launches of its plain twin).
+static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on) {
+  *on = false;
+  if (!drop || drop->p == 0.0f) return EDTTS_OK;
+  const float p = drop->p;
+  const double thr = nearbyint((double)p * 65536.0);  // (ties to even, as round() of the tests' restatement)
+  if (!(p >= 0.0f && p < 1.0f) || thr > 65535.0)
+    return fail(EDTTS_ERR_ARG, "%s: dropout p=%g is outside [0, 1) (needs round(p * 65536) <= 65535)", who, (double)p);
+  ds->k0 = (unsigned)drop->seed;
+  ds->k1 = (unsigned)(drop->seed >> 32);
+  ds->thr = (unsigned)thr;
+  ds->scale = 65536.0f / (float)(65536u - ds->thr);
+  *on = true;
+  return EDTTS_OK;
+}
+
+extern "C" {
+
+int edtts_train_dw_slab_rows(int rows) { return edtts_bwd::dw_slab_rows(rows); }
+
+int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes) {
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_train_tape_bytes", &lo));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY_G(check_shapes(lo, B, T, S));
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  *out_bytes = tt.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes) {
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_train_scratch_bytes", &lo));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  TRY_G(check_shapes(lo, B, T, S));
+  TrainScratch ss;
+  make_train_scratch(lo, B, T, S, &ss);
+  *out_bytes = ss.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S, const float* x,
+                                const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, float* eps,
+                                void* stream) {
+  return edtts_decoder_forward_train_drop(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, nullptr, stream);
+}
+
+int edtts_decoder_forward_train_drop(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                     const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                     const float* sem_features, float* eps, const EdttsDropout* drop, void* stream) {
+  return edtts_decoder_forward_train_len(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, drop, nullptr,
+                                         nullptr, stream);
+}
+
+int edtts_decoder_forward_train_len(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                    const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                    const float* sem_features, float* eps, const EdttsDropout* drop, const int64_t* t_len,
+                                    const int64_t* s_len, void* stream) {
+  const SettingsScope settings;
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_decoder_forward_train", &lo));
+  DropState ds;
+  bool dropping;
+  TRY_G(drop_state(drop, "edtts_decoder_forward_train_drop", &ds, &dropping));
+  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
+  if (!packed || !workspace || !tape || !x || !t || !eps) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  TRY_G(check_shapes(lo, B, T, S));
+  hipStream_t st = (hipStream_t)stream;
+  const float* blob = (const float*)packed;
+  float* wsb = (float*)workspace;
+  float* tp = (float*)tape;
+  Workspace ws;
+  make_workspace(lo, B, T, S, B, &ws);
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  TRY_G(launch_len_check(t_len, s_len, B, T, S, wsb, st));
+  TRY_G(launch_cond(lo, blob, t, step_idx, nullptr, B, tp + tt.cond, wsb, st));  // the AdaLN rows and t_cond go straight to the tape
+  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
+  return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps, dropping ? &ds : nullptr);
+}
+
+int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S, const float* x,
+                           const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, const float* d_eps,
+                           void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch, void* stream) {
+  return edtts_decoder_backward_drop(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots,
+                                     d_x, d_sem_features, scratch, nullptr, stream);
+}
+
+int edtts_decoder_backward_drop(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                                const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                                const EdttsDropout* drop, void* stream) {
+  return edtts_decoder_backward_len(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots,
+                                    d_x, d_sem_features, scratch, drop, nullptr, nullptr, stream);
+}
+
+int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                               const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                               const EdttsDropout* drop, const int64_t* t_len, const int64_t* s_len, void* stream) {
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_decoder_backward", &lo));
+  DropState ds;
+  bool dropping;
+  TRY_G(drop_state(drop, "edtts_decoder_backward_drop", &ds, &dropping));
+  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
+  if (!packed || !workspace || !tape || !x || !t || !d_eps || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
+  TRY_G(check_shapes(lo, B, T, S));
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  TrainScratch ss;
+  make_train_scratch(lo, B, T, S, &ss);
+  TRY_G(launch_len_check(t_len, s_len, B, T, S, (float*)workspace, (hipStream_t)stream));  // (the index-error word: the only use of `workspace`)
+  return TrainLauncher::backward(lo, (const float*)packed, (const float*)tape, tt, (float*)scratch, ss, B, T, S, dims->window, x, t, step_idx,
+                                 sem_features ? nullptr : sem_idx, sem_features, d_eps, reinterpret_cast<float* const*>(grad_slots), d_x,
+                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr, Lens{t_len, s_len});
+}
+
+int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_dropout_mask", &lo));
+  if (!drop) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: drop is NULL");
+  DropState ds{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0u, 1.0f};  // (p == 0: threshold 0, everything kept)
+  bool dropping;
+  TRY_G(drop_state(drop, "edtts_dropout_mask", &ds, &dropping));
+  if (site < DROP_ATTN || site > DROP_DOWN) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: site %d is not one of 0 .. 3", site);
+  if (layer < 0 || layer >= lo.L) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: layer %d outside [0, %d)", layer, lo.L);
+  if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  TRY_G(check_shapes(lo, B, T, S));
+  const bool attn = site == DROP_ATTN || site == DROP_CROSS;
+  const size_t rows = attn ? (size_t)B * lo.HEADS * T : (size_t)B * T;
+  const int W = site == DROP_ATTN ? T : site == DROP_CROSS ? S : site == DROP_ACT ? lo.FM * lo.H : lo.H;
+  hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * ((W + 3) / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows,
+                     W, T, (int)attn, ds.site(layer, site));
+  LAUNCH_CHECK("k_drop_mask");
+  return EDTTS_OK;
+}
+
+}  // extern "C"

@@ -21,8 +21,6 @@
 // floats) with the next tile's loads in flight during the current tile's MFMAs (two LDS buffers, one barrier per K tile).  Within a
 // 16-wide k-block lane group g holds k = 4 g .. 4 g + 3 (one ds_read_b128 per operand serves four MFMA steps).  Every output element
 // is the same k-ordered chain whatever its tile, its tile size or the batch it is in: results are bitwise independent of B, T and TW.
-#pragma once
-
 namespace edtts_hub {
 
 constexpr int kMaxConv = 16;  // feature-encoder conv layers

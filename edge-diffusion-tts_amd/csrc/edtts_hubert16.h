@@ -28,8 +28,6 @@
 // (the contraction order of an MFMA is free), so P never leaves registers.  V^T comes from k_hub_vt, which writes
 // [utterance][head][d][key slot] with exactly that order inside every 32-key chunk and zeros for keys past the utterance's count:
 // the A operand is one 16-byte load per lane, and neither K rows nor V rows past the count are read.
-#pragma once
-
 namespace edtts_hub {
 
 constexpr int kBK16 = 32;         // GEMM K tile (one MFMA k-step)

@@ -1,25 +1,20 @@
-// edtts_kernels.hip -- gfx950 kernels + C ABI (include/edtts.h) of the DDIM sampler path.
+// edtts_kernels.hip -- the one translation unit of libedtts_hip.so: gfx950 kernels + the C ABI of include/edtts.h.
 //
-// Kernel inventory (all fp32, MFMA = v_mfma_f32_16x16x4_f32, see edtts_device.h for the register data model):
-//   k_pack_gemm / k_copy / k_transpose   weight re-packing into MFMA fragment order (once per weight load)
-//   k_cond_mlp/_ada  time MLP + step embedding; all AdaLN (1+scale, shift) rows         decoder.py:77-80, transformer.py:64-66
-//   k_ctx         context embedding + per-layer low-rank cross K / V^T cache           decoder.py:83-93, mla.py:143-153
-//   k_prologue    in_proj + positional table, AdaRMSNorm(layer 0), QKV(layer 0)        decoder.py:96-97, attention.py:91-93
-//   k_layer<TAIL> one DiffusionTransformerBlock for a 32-frame wave tile, fully in registers:
-//                 banded self-attention (+proj, residual), RMSNorm + q_proj + cross-attention (+out_proj, residual),
-//                 AdaRMSNorm + SwiGLU FFN (+residual)  (transformer.py:129-160), then the tail:
-//                   TAIL_QKV : AdaRMSNorm + QKV of the NEXT layer
-//                   TAIL_EPS : final LayerNorm + out_proj -> eps                        decoder.py:108-109
-//                   TAIL_DDIM: final LayerNorm + out_proj + DDIM update                 schedule.py:157-202
-//   k_ddim / k_ddpm   standalone elementwise updates (HBM-bound)                       schedule.py:157-238
-//   k_dsconv_*    depthwise-separable Conv1d + GroupNorm + GELU (standalone layer)     conv.py:25-64
-//   k_gen_*       the generic run-time-shape fp32 path (edtts_generic.h): GEMM, row norms, attention, sampler tails
+// In this file, in order: error plumbing and the launch profiler; weight slots, the packed blob's layouts; the packing kernels; the
+// decoder forward of the compiled shapes (k_cond_*, KArgs, tails, k_prologue, k_layer, + edtts_coop.h, edtts_bf16.h, k_ctx / k_ctx16);
+// k_dsconv_*; the host side (workspace, settings, sub-batches, StepTail, CallCtx, Launcher / Launcher16); edtts_generic.h; the chain
+// of compiled shapes (EDTTS_DISPATCH), launch_cond, the length and shape checks; the units that hold a whole subsystem each (the
+// include list behind check_shapes); and the extern "C" block with the entry points of everything that is defined in this file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <atomic>
+#include <initializer_list>
+#include <mutex>
+#include <vector>
 
 #include "../../include/edtts.h"
 #include "edtts_device.h"
@@ -52,10 +47,6 @@ static int fail(int code, const char* fmt, ...) {
 // =========================================================================================================
 // optional per-launch timing of the dominant kernel (bench.py roofline leg)
 // =========================================================================================================
-#include <atomic>
-#include <initializer_list>
-#include <mutex>
-#include <vector>
 // A diagnostic that any thread may have switched on: `on` is read without the lock on every launch, the records themselves are
 // taken under it (profiling serialises the launches it brackets; it is off by default)
 struct Profiler {
@@ -129,7 +120,46 @@ constexpr size_t kFrag = 256;  // floats per fragment (64 lanes x float4)
 static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 static bool has_instance(const Layout& lo);
-static int make_generic_layout(const EdttsDims* d, Layout* lo);
+
+// Generic layout: the tables the conditioning / embedding code reads sit where the fused layout keeps them (time MLP and AdaLN
+// projections transposed for k_cond_mlp / k_cond_ada); every other Linear is the state-dict's [N][K] matrix as it is.
+static int make_generic_layout(const EdttsDims* d, Layout* lo) {
+  if (d->ffn_mult < 1 || d->ffn_mult > 4) return fail(EDTTS_ERR_UNSUPPORTED, "ffn_mult=%d outside [1, 4]", d->ffn_mult);
+  if (d->layers < 1 || d->layers > kMaxLayers) return fail(EDTTS_ERR_UNSUPPORTED, "layers=%d out of [1,%d]", d->layers, kMaxLayers);
+  if (d->heads < 1 || d->hidden < 2 || d->hidden % d->heads || d->hidden % 2)
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: hidden=%d heads=%d: need hidden %% heads == 0 and an even hidden", d->hidden, d->heads);
+  if (d->hidden / d->heads > 128)
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128 (hidden=%d heads=%d)", d->hidden / d->heads, d->hidden, d->heads);
+  if (d->n_mels < 1 || d->semantic_dim < 1 || d->codebook_size < 1 || d->max_pos < 1 || d->max_ctx_pos < 1 || d->n_step_emb < 1)
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: n_mels=%d semantic_dim=%d codebook_size=%d and the table sizes must be >= 1",
+                d->n_mels, d->semantic_dim, d->codebook_size);
+  memset(lo, 0, sizeof(*lo));
+  lo->GEN = 1;
+  lo->H = d->hidden; lo->HEADS = d->heads; lo->MEL = d->n_mels; lo->L = d->layers;
+  lo->DH = lo->H / lo->HEADS; lo->DHP = (lo->DH + 15) / 16 * 16;
+  lo->R = lo->H / 2; lo->SD = d->semantic_dim; lo->NTOK = d->codebook_size;
+  lo->MAXPOS = d->max_pos; lo->MAXCPOS = d->max_ctx_pos; lo->NSTEP = d->n_step_emb; lo->FM = d->ffn_mult;
+  const size_t H = lo->H, R = lo->R, SD = lo->SD, MEL = lo->MEL, FH = (size_t)lo->FM * lo->H;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
+  lo->tok = take((size_t)lo->NTOK * H);
+  lo->semp = take(H * SD); lo->semp_b = take(H);
+  lo->t1T = take(H * H); lo->t1b = take(H); lo->t3T = take(H * H); lo->t3b = take(H);
+  lo->step = take((size_t)lo->NSTEP * H);
+  lo->inp = take(H * MEL); lo->inp_b = take(H);
+  lo->pe = take((size_t)lo->MAXPOS * H); lo->cpe = take((size_t)lo->MAXCPOS * H);
+  lo->fnw = take(H); lo->fnb = take(H); lo->s_outp = take(MEL * H); lo->outp_b = take(MEL); lo->freqs = take(H / 2);
+  for (int l = 0; l < lo->L; ++l) {
+    LayerLayout& y = lo->layer[l];
+    y.n1w = take(H); y.ada1T = take(H * 2 * H); y.ada1b = take(2 * H); y.proj_b = take(H); y.n2w = take(H);
+    y.n3w = take(H); y.ada3T = take(H * 2 * H); y.ada3b = take(2 * H); y.up_b = take(2 * FH); y.down_b = take(H);
+    y.kvd = take(R * H); y.kvn = take(R); y.kvu = take(2 * H * R);
+    y.s_qkv = take(3 * H * H); y.g_proj = take(H * H); y.g_qp = take(H * H); y.g_op = take(H * H);
+    y.g_up = take(2 * FH * H); y.g_down = take(H * FH);
+  }
+  lo->total = align64(o);
+  return EDTTS_OK;
+}
 
 static int make_layout(const EdttsDims* d, Layout* lo) {
   if (!d) return fail(EDTTS_ERR_ARG, "dims is NULL");
@@ -216,44 +246,16 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
   return EDTTS_OK;
 }
 
-// Generic layout: the tables the conditioning / embedding code reads sit where the fused layout keeps them (time MLP and AdaLN
-// projections transposed for k_cond_mlp / k_cond_ada); every other Linear is the state-dict's [N][K] matrix as it is.
-static int make_generic_layout(const EdttsDims* d, Layout* lo) {
-  if (d->ffn_mult < 1 || d->ffn_mult > 4) return fail(EDTTS_ERR_UNSUPPORTED, "ffn_mult=%d outside [1, 4]", d->ffn_mult);
-  if (d->layers < 1 || d->layers > kMaxLayers) return fail(EDTTS_ERR_UNSUPPORTED, "layers=%d out of [1,%d]", d->layers, kMaxLayers);
-  if (d->heads < 1 || d->hidden < 2 || d->hidden % d->heads || d->hidden % 2)
-    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: hidden=%d heads=%d: need hidden %% heads == 0 and an even hidden", d->hidden, d->heads);
-  if (d->hidden / d->heads > 128)
-    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128 (hidden=%d heads=%d)", d->hidden / d->heads, d->hidden, d->heads);
-  if (d->n_mels < 1 || d->semantic_dim < 1 || d->codebook_size < 1 || d->max_pos < 1 || d->max_ctx_pos < 1 || d->n_step_emb < 1)
-    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: n_mels=%d semantic_dim=%d codebook_size=%d and the table sizes must be >= 1",
-                d->n_mels, d->semantic_dim, d->codebook_size);
-  memset(lo, 0, sizeof(*lo));
-  lo->GEN = 1;
-  lo->H = d->hidden; lo->HEADS = d->heads; lo->MEL = d->n_mels; lo->L = d->layers;
-  lo->DH = lo->H / lo->HEADS; lo->DHP = (lo->DH + 15) / 16 * 16;
-  lo->R = lo->H / 2; lo->SD = d->semantic_dim; lo->NTOK = d->codebook_size;
-  lo->MAXPOS = d->max_pos; lo->MAXCPOS = d->max_ctx_pos; lo->NSTEP = d->n_step_emb; lo->FM = d->ffn_mult;
-  const size_t H = lo->H, R = lo->R, SD = lo->SD, MEL = lo->MEL, FH = (size_t)lo->FM * lo->H;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
-  lo->tok = take((size_t)lo->NTOK * H);
-  lo->semp = take(H * SD); lo->semp_b = take(H);
-  lo->t1T = take(H * H); lo->t1b = take(H); lo->t3T = take(H * H); lo->t3b = take(H);
-  lo->step = take((size_t)lo->NSTEP * H);
-  lo->inp = take(H * MEL); lo->inp_b = take(H);
-  lo->pe = take((size_t)lo->MAXPOS * H); lo->cpe = take((size_t)lo->MAXCPOS * H);
-  lo->fnw = take(H); lo->fnb = take(H); lo->s_outp = take(MEL * H); lo->outp_b = take(MEL); lo->freqs = take(H / 2);
-  for (int l = 0; l < lo->L; ++l) {
-    LayerLayout& y = lo->layer[l];
-    y.n1w = take(H); y.ada1T = take(H * 2 * H); y.ada1b = take(2 * H); y.proj_b = take(H); y.n2w = take(H);
-    y.n3w = take(H); y.ada3T = take(H * 2 * H); y.ada3b = take(2 * H); y.up_b = take(2 * FH); y.down_b = take(H);
-    y.kvd = take(R * H); y.kvn = take(R); y.kvu = take(2 * H * R);
-    y.s_qkv = take(3 * H * H); y.g_proj = take(H * H); y.g_qp = take(H * H); y.g_op = take(H * H);
-    y.g_up = take(2 * FH * H); y.g_down = take(H * FH);
-  }
-  lo->total = align64(o);
-  return EDTTS_OK;
+// The layout of a call that trains (edtts_generic_bwd.h) or asks where a trainable slot lies: the generic fp32 path only
+static int train_layout(const EdttsDims* dims, const char* who, Layout* lo) {
+  if (!dims) return fail(EDTTS_ERR_ARG, "dims is NULL");
+  const int kbits = dims->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  if (kbits != EDTTS_KERNELS_GENERIC)
+    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training runs on the generic kernels only (compute_dtype=0x%x lacks EDTTS_KERNELS_GENERIC)", who,
+                dims->compute_dtype);
+  if (dtype != EDTTS_F32) return fail(EDTTS_ERR_UNSUPPORTED, "%s: training is fp32 only (compute_dtype=0x%x)", who, dims->compute_dtype);
+  return make_layout(dims, lo);
 }
 
 // =========================================================================================================
@@ -1047,7 +1049,6 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_layer(KArgs a) {
 
 #include "edtts_coop.h"
 #include "edtts_bf16.h"
-#include "edtts_melpost.h"
 
 // =========================================================================================================
 // context kernel: ctx = token_emb[sem_idx] (or sem_proj(features)) + pe_ctx ; per layer K / V^T cache
@@ -1309,87 +1310,6 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_ctx16(CtxArgs a) {
     }
   }
   ring.drain();
-}
-
-
-// =========================================================================================================
-// standalone DDIM / DDPM updates (HBM-bound: read x, eps ; write x_prev, x0 = 16 B/element)
-// =========================================================================================================
-struct StepArgs {
-  const float *alphas, *alpha_bar, *betas, *post_var;
-  int n_table;
-  const float *x, *eps, *noise;
-  const int64_t *t, *t_prev;
-  size_t n_per_batch;
-  float eta;
-  float *x_prev, *x0;
-  int vec4;  // 1: n_per_batch % 4 == 0 and every tensor 16-byte aligned -> float4 accesses; 0: scalar path
-};
-// the float4 path of the stand-alone update kernels needs every batch row base 16-byte aligned
-static int step_vec4(size_t n_per_batch, std::initializer_list<const void*> ptrs) {
-  uintptr_t m = 0;
-  for (const void* p : ptrs) m |= (uintptr_t)p;
-  return (n_per_batch & 3) == 0 && (m & 15) == 0;
-}
-EDTTS_DEV long clamp_idx(long v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
-__global__ __launch_bounds__(256) void k_ddim(StepArgs a) {
-  const int b = blockIdx.y;
-  // per-batch scalars, evaluated with the reference's operation sequence (schedule.py:179-196)
-  const float ab = a.alpha_bar[clamp_idx((long)a.t[b], a.n_table)];
-  const long tp = (long)a.t_prev[b];
-  const float abp = tp >= 0 ? a.alpha_bar[clamp_idx(tp, a.n_table)] : 1.0f;
-  const DdimCoef cf = ddim_coef(ab, abp, a.eta);
-  const float s1m = cf.s1m, sab = cf.sab, sabp = cf.sabp, cdir = cf.cdir, sigma = cf.sigma;
-  const size_t base = (size_t)b * a.n_per_batch;
-  const size_t n4 = a.vec4 ? a.n_per_batch >> 2 : 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t o = base + 4 * i;
-    const f4 xv = ldg4(a.x + o), e = ldg4(a.eps + o);
-    f4 nz = splat(0.f);
-    if (a.noise) nz = ldg4(a.noise + o);
-    f4 x0, xp;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float v, p;
-      ddim_elem(xv[r], e[r], s1m, sab, sabp, cdir, v, p);
-      if (a.noise) p = add_mul_rn(p, sigma, nz[r]);
-      x0[r] = v;
-      xp[r] = p;
-    }
-    stg4(a.x0 + o, x0);
-    stg4(a.x_prev + o, xp);
-  }
-  // scalar path: everything when n_per_batch % 4 != 0 or a tensor is not 16-byte aligned (never on the sampler's own tensors)
-  for (size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_per_batch; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t o = base + i;
-    float v, p;
-    ddim_elem(a.x[o], a.eps[o], s1m, sab, sabp, cdir, v, p);
-    if (a.noise) p = add_mul_rn(p, sigma, a.noise[o]);
-    a.x0[o] = v;
-    a.x_prev[o] = p;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_ddpm(StepArgs a) {
-  const int b = blockIdx.y;
-  const long tt = clamp_idx((long)a.t[b], a.n_table);
-  const float al = a.alphas[tt], ab = a.alpha_bar[tt], be = a.betas[tt];
-  const DdpmCoef cf = ddpm_coef(al, ab, be, a.post_var[tt], (long)a.t[b] > 0);
-  const size_t base = (size_t)b * a.n_per_batch;
-  const size_t n4 = a.vec4 ? a.n_per_batch >> 2 : 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t o = base + 4 * i;
-    const f4 xv = ldg4(a.x + o), e = ldg4(a.eps + o), nz = ldg4(a.noise + o);
-    f4 xp;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) xp[r] = ddpm_elem(xv[r], e[r], nz[r], cf);
-    stg4(a.x_prev + o, xp);
-  }
-  for (size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_per_batch; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t o = base + i;  // scalar path (see k_ddim)
-    a.x_prev[o] = ddpm_elem(a.x[o], a.eps[o], a.noise[o], cf);
-  }
 }
 
 // =========================================================================================================
@@ -2459,7 +2379,6 @@ static int with_tail(int kind, F&& f) {
   }
 }
 #define TRY_G(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 // ... for every kind (the hipFuncSetAttribute lists)
 template <class F>
 static int for_each_tail(F&& f) {
@@ -2748,20 +2667,10 @@ struct Launcher16 {
 };
 
 #include "edtts_generic.h"
-#include "edtts_generic_bwd.h"
-#include "edtts_semantic.h"
-#include "edtts_semantic_bwd.h"
-#include "edtts_hubert.h"
-#include "edtts_hubert16.h"
-#include "edtts_audio.h"
-#include "edtts_optim.h"
-#include "edtts_objective.h"
 
 // compiled decoder shapes: (hidden, heads, n_mels).  EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, body) runs `body` with LN = the fused
 // launcher of lo's shape, or the statement MISS16 / MISS32 when none is compiled; EDTTS_DISPATCH adds the generic launcher (lo.GEN)
 // and has_instance() -- the predicate make_layout decides EDTTS_KERNELS_AUTO with -- walks the same chain.
-static int no_instance16(const Layout& lo);
-static int no_instance32(const Layout& lo);
 #ifdef EDTTS_FAST_BUILD  // scratch builds (-DEDTTS_EXPERIMENTS): the default decoder's fp32 instance only
 #define EDTTS_FUSED_CHAIN(lo, MISS16, MISS32, ...)                                                       \
     if (!(lo).BF16 && (lo).H == 160 && (lo).HEADS == 4 && (lo).MEL == 80) { using LN = Launcher<Cfg<160, 4, 80>>; __VA_ARGS__; } \
@@ -2862,126 +2771,21 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
   return EDTTS_OK;
 }
 
-// What a sampler call runs on besides its per-step tails
-struct SamplerInputs {
-  const int64_t* t_dev = nullptr;   // conditioning: device timesteps of every step (edtts_sample_ddpm) ...
-  const int64_t* t_host = nullptr;  // ... or host ones, row i = (timesteps[i], step index i)
-  const int64_t* sem_idx = nullptr;
-  const float* sem_features = nullptr;
-  Lens ln;                // per-utterance lengths of the whole batch (token counts in ln.t are checked through ln.s)
-  const float* x_T = nullptr;  // step 0 reads it ...
-  const float* x = nullptr;    // ... every later step the sample the previous one wrote
-};
-// The sub-batched step loop of the samplers, after the entry point's own argument checks: conditioning rows of every step, the
-// context cache per sub-batch, then step-major over the sub-batches.  tail_of(i, off, o) builds the tail of step i for the sub-batch
-// that starts at utterance off (element o = off * T * n_mels of a [B, T, n_mels] tensor).
-template <class TailOf>
-static int run_sampler(const EdttsDims* dims, const Layout& lo, const void* packed, void* workspace, int B, int T, int S, int num_steps,
-                       const SamplerInputs& in, void* stream, TailOf&& tail_of) {
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  SubBatches sb;
-  plan_call(lo, B, T, S, num_steps, wsb, &sb);
-  TRY(launch_len_check(in.ln.t_dbl ? nullptr : in.ln.t, in.ln.s, B, T, S, wsb, st));
-  TRY(launch_cond(lo, blob, in.t_dev, nullptr, in.t_host, num_steps, wsb + sb.cond, wsb, st));
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
-  const size_t per_utt = (size_t)T * lo.MEL;
-  ForkJoin fj;
-  TRY(fj.init(sb, st));
-  auto call = [&](int j) { return CallCtx{lo, blob, sb.ws[j], wsb + sb.base[j], sb.B[j], T, S, dims->window, in.ln.at(sb.off[j]), fj.st[j]}; };
-  EDTTS_DISPATCH(lo, {
-    TRY(set_attrs_once<LN>());
-    for (int j = 0; j < sb.n; ++j) {
-      const size_t off = sb.off[j];
-      TRY(LN::ctx(call(j), (in.sem_features || !in.sem_idx) ? nullptr : in.sem_idx + off * S,
-                  in.sem_features ? in.sem_features + off * S * lo.SD : nullptr));
-    }
-    for (int i = 0; i < num_steps; ++i)
-      for (int j = 0; j < sb.n; ++j) {
-        const size_t o = (size_t)sb.off[j] * per_utt;
-#ifdef EDTTS_WAVELOG
-        g_wavelog_base = sb.off[j] * (sb.ws[j].Tp / 32);
-#endif
-        TRY(LN::forward(call(j), (i == 0 ? in.x_T : in.x) + o, wsb + sb.cond + i * row, 0, tail_of(i, sb.off[j], o)));
-      }
-  });
-  return EDTTS_OK;
-}
-
-// The multistep samplers' rows of coef_host: {mode, p0, p1, c0, c1, rinv, cB, cC}; a step cannot look further back than the steps before it
-static int check_lms_modes(const float* coef_host, int num_steps) {
-  for (int i = 0; i < num_steps; ++i) {
-    const int mode = (int)coef_host[8 * i];
-    if (mode < 1 || mode > 3 || mode > i + 1) return fail(EDTTS_ERR_ARG, "step %d: bad solver mode %d", i, mode);
-  }
-  return EDTTS_OK;
-}
-// LmsStepArgs of step i from its coefficient row c.  hist is a ring of two slots of `per` floats: step i writes slot i%2; newest
-// previous = slot (i-1)%2, the one before = slot i%2.  o: element offset of the (sub-)batch in a [B, T, n_mels] tensor.
-static LmsStepArgs lms_step_args(const float* c, float* hist, float* x0_all, size_t per, int i, size_t o) {
-  LmsStepArgs ls;
-  ls.k = LmsCoef{(int)c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]};
-  ls.x0_hist = hist + (size_t)(i & 1) * per + o;
-  ls.h_new = hist + (size_t)((i + 1) & 1) * per + o;
-  ls.h_old = hist + (size_t)(i & 1) * per + o;
-  ls.x0_all = x0_all ? x0_all + (size_t)i * per + o : nullptr;
-  return ls;
-}
-
-// What the in-painting entry points share: the arguments of edtts_sample_inpaint_len, in its order (include/edtts.h)
-struct InpaintArgs {
-  const EdttsDims* dims; const void* packed; void *workspace, *workspace_uncond; int B, T, S;
-  const float *sem_features, *zero_features; float* x; int num_steps; const int64_t *t_all, *step_all;
-  const float *coef_host, *known_mel; int overlap_len; const float* noise_k; uint64_t seed; float cfg_scale; float* v_uncond;
-  const int64_t *t_len, *s_len; const uint64_t* seeds; void* stream;
-};
-// The step loop of the in-painting samplers, in one piece on the caller's stream (no sub-batches: a captured call stays one chain):
-// the shared argument checks (own_ptrs: the entry point's further pointers are there; own_checks(): its further checks, made last),
-// the conditioning rows of every step, the context cache (guided: a second one in workspace_uncond) and per step the unconditional
-// forward into v_uncond (guided), then the conditional one with tail_of(i), whose vp.v_uncond is set here.  With a known tail,
-// inject_before(i) runs ahead of step i and inject_after() behind the last one.
-template <class Checks, class InjectBefore, class TailOf, class InjectAfter>
-static int run_inpaint(const InpaintArgs& a, const Layout& lo, bool own_ptrs, Checks&& own_checks, InjectBefore&& inject_before,
-                       TailOf&& tail_of, InjectAfter&& inject_after) {
-  if (!a.packed || !a.workspace || !a.sem_features || !a.x || !a.t_all || !a.step_all || !a.coef_host || !own_ptrs) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (a.num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", a.num_steps);
-  const bool guided = a.cfg_scale != 1.0f;
-  if (guided && (!a.workspace_uncond || !a.zero_features || !a.v_uncond)) return fail(EDTTS_ERR_ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond");
-  if (a.known_mel && (a.overlap_len < 1 || a.overlap_len > a.T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", a.overlap_len, a.T);
-  TRY(check_shapes(lo, a.B, a.T, a.S));
-  TRY(own_checks());
-  hipStream_t st = (hipStream_t)a.stream;
-  const float* blob = (const float*)a.packed;
-  float* wsb = (float*)a.workspace;
-  Workspace ws;
-  make_workspace(lo, a.B, a.T, a.S, a.num_steps, &ws);
-  TRY(launch_len_check(a.t_len, a.s_len, a.B, a.T, a.S, wsb, st, a.known_mel ? a.overlap_len : 1));
-  TRY(launch_cond(lo, blob, a.t_all, a.step_all, nullptr, a.num_steps, wsb + ws.cond, wsb, st));
-  const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
-  const CallCtx c{lo, blob, ws, wsb, a.B, a.T, a.S, a.dims->window, Lens{a.t_len, a.s_len}, st};
-  CallCtx cu = c;  // the unconditional pass: its own context cache and activations (workspace_uncond)
-  cu.wsb = (float*)a.workspace_uncond;
-  EDTTS_DISPATCH(lo, {
-    TRY(set_attrs_once<LN>());
-    TRY(LN::ctx(c, nullptr, a.sem_features));
-    if (guided) TRY(LN::ctx(cu, nullptr, a.zero_features));  // (the solo call's zero context has S_b rows)
-    for (int i = 0; i < a.num_steps; ++i) {
-      if (a.known_mel) TRY(inject_before(i));
-      StepTail tail = tail_of(i);
-      if (guided) {
-        // the unconditional pass shares nothing with the conditional one but x and the conditioning rows
-        StepTail eps_tail;
-        eps_tail.eps = a.v_uncond;
-        TRY(LN::forward(cu, a.x, wsb + ws.cond + i * row, 0, eps_tail));
-        tail.vp.v_uncond = a.v_uncond;
-      }
-      TRY(LN::forward(c, a.x, wsb + ws.cond + i * row, 0, tail));
-    }
-    if (a.known_mel) TRY(inject_after());
-  });
-  return EDTTS_OK;
-}
+// The units that hold a whole subsystem each -- kernels, host helpers, extern "C" entry points -- included here, behind the
+// launchers and the pre-launch steps above that their entry points call (launch_cond, launch_len_check, check_shapes, EDTTS_DISPATCH)
+// Every header of this directory is included exactly once, in dependency order (tests/test_host_cpu.py checks it by a text scan), so
+// the units carry no include guard: a second inclusion is a redefinition error, not a silent no-op.
+#include "edtts_melpost.h"       // mel -> spectrogram, Griffin-Lim (edtts_audio.h uses its FFT)
+#include "edtts_generic_bwd.h"   // training the decoder; drop_state, which edtts_semantic_bwd.h calls
+#include "edtts_semantic.h"      // SemanticEncoder: proj, FSQ / VQ <- edtts_generic.h: DropArgs
+#include "edtts_semantic_bwd.h"  // ... its training <- edtts_generic_bwd.h: k_bwd_*, drop_state
+#include "edtts_hubert.h"        // NativeHubert, fp32 <- edtts_generic.h: k_gen_norm, k_gen_attn
+#include "edtts_hubert16.h"      // ... its bf16 MFMA path <- edtts_hubert.h
+#include "edtts_audio.h"         // MelSpectrogram, log-mel statistics, Resample <- edtts_melpost.h: melpost::cplx
+#include "edtts_optim.h"         // FusedAdamW: k_opt_*, edtts_optim_*
+#include "edtts_objective.h"     // DiffusionObjective: k_obj_*, edtts_objective_*
+#include "edtts_samplers.h"      // the samplers: step kernels, step loops, edtts_generate*, edtts_sample_*, edtts_randn*
+#include "edtts_debug.h"         // edtts_profile_*, the diagnostic builds' exports (g_prof, g_stamps_fwd, g_wavelog are defined above)
 
 extern "C" {
 
@@ -3099,15 +2903,15 @@ static SlotDest generic_slot_dest(const Layout& lo, int slot) {
 static int pack_generic(const Layout& lo, const void* const* slots, float* blob, hipStream_t st) {
   for (int i = 0; i < G_COUNT + lo.L * L_COUNT; ++i) {
     const SlotDest d = generic_slot_dest(lo, i);
-    if (d.tr) TRY(transpose_f(st, (const float*)slots[i], blob + d.off, (int)d.rows, (int)d.cols));
-    else TRY(copy_f(st, (const float*)slots[i], blob + d.off, d.rows * d.cols));
+    if (d.tr) TRY_G(transpose_f(st, (const float*)slots[i], blob + d.off, (int)d.rows, (int)d.cols));
+    else TRY_G(copy_f(st, (const float*)slots[i], blob + d.off, d.rows * d.cols));
   }
   return EDTTS_OK;
 }
 
 int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_slots, void* packed, void* stream) {
   Layout lo;
-  TRY(make_layout(dims, &lo));
+  TRY_G(make_layout(dims, &lo));
   if (!slots || !packed) return fail(EDTTS_ERR_ARG, "slots/packed is NULL");
   if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
   for (int i = 0; i < n_slots; ++i)
@@ -3119,75 +2923,75 @@ int edtts_pack_weights(const EdttsDims* dims, const void* const* slots, int n_sl
   const int KPT = lo.HEADS * DHP / 16;
   HIP_TRY(hipMemsetAsync(blob, 0, lo.total * sizeof(float), st));
   if (lo.GEN) return pack_generic(lo, slots, blob, st);
-  TRY(copy_f(st, G(G_TOK), blob + lo.tok, (size_t)lo.NTOK * H));
-  TRY(pack_gemm(st, G(G_SEMP_W), SD, H, SD, HT, SD / 16, 0, 0, 0, DH, DHP, blob + lo.semp));
-  TRY(copy_f(st, G(G_SEMP_B), blob + lo.semp_b, H));
-  TRY(transpose_f(st, G(G_T1_W), blob + lo.t1T, H, H));
-  TRY(copy_f(st, G(G_T1_B), blob + lo.t1b, H));
-  TRY(transpose_f(st, G(G_T3_W), blob + lo.t3T, H, H));
-  TRY(copy_f(st, G(G_T3_B), blob + lo.t3b, H));
-  TRY(copy_f(st, G(G_STEP), blob + lo.step, (size_t)lo.NSTEP * H));
+  TRY_G(copy_f(st, G(G_TOK), blob + lo.tok, (size_t)lo.NTOK * H));
+  TRY_G(pack_gemm(st, G(G_SEMP_W), SD, H, SD, HT, SD / 16, 0, 0, 0, DH, DHP, blob + lo.semp));
+  TRY_G(copy_f(st, G(G_SEMP_B), blob + lo.semp_b, H));
+  TRY_G(transpose_f(st, G(G_T1_W), blob + lo.t1T, H, H));
+  TRY_G(copy_f(st, G(G_T1_B), blob + lo.t1b, H));
+  TRY_G(transpose_f(st, G(G_T3_W), blob + lo.t3T, H, H));
+  TRY_G(copy_f(st, G(G_T3_B), blob + lo.t3b, H));
+  TRY_G(copy_f(st, G(G_STEP), blob + lo.step, (size_t)lo.NSTEP * H));
   const int KT16 = H / 32, MKT16 = (lo.MEL + 31) / 32, MTP16 = (MT + 1) / 2;  // bf16 fragment grid (edtts_bf16.h)
-  if (lo.BF16) TRY(pack_gemm16(st, G(G_INP_W), lo.MEL, H, lo.MEL, HT, MKT16, 1, blob + lo.inp));  // k-major, head of the stream
+  if (lo.BF16) TRY_G(pack_gemm16(st, G(G_INP_W), lo.MEL, H, lo.MEL, HT, MKT16, 1, blob + lo.inp));  // k-major, head of the stream
   else
-  TRY(pack_gemm(st, G(G_INP_W), lo.MEL, H, lo.MEL, HT, MT, 0, 0, 4, DH, DHP, blob + lo.inp));  // n-tile pairs, head of the stream
-  TRY(copy_f(st, G(G_INP_B), blob + lo.inp_b, H));
-  TRY(copy_f(st, G(G_PE), blob + lo.pe, (size_t)lo.MAXPOS * H));
-  TRY(copy_f(st, G(G_CPE), blob + lo.cpe, (size_t)lo.MAXCPOS * H));
-  TRY(copy_f(st, G(G_FN_W), blob + lo.fnw, H));
-  TRY(copy_f(st, G(G_FN_B), blob + lo.fnb, H));
-  if (lo.BF16) TRY(pack_gemm16(st, G(G_OUT_W), H, lo.MEL, H, 2 * MTP16, KT16, 0, blob + lo.s_outp));  // n-tile pairs (rows >= n_mels: zero)
+  TRY_G(pack_gemm(st, G(G_INP_W), lo.MEL, H, lo.MEL, HT, MT, 0, 0, 4, DH, DHP, blob + lo.inp));  // n-tile pairs, head of the stream
+  TRY_G(copy_f(st, G(G_INP_B), blob + lo.inp_b, H));
+  TRY_G(copy_f(st, G(G_PE), blob + lo.pe, (size_t)lo.MAXPOS * H));
+  TRY_G(copy_f(st, G(G_CPE), blob + lo.cpe, (size_t)lo.MAXCPOS * H));
+  TRY_G(copy_f(st, G(G_FN_W), blob + lo.fnw, H));
+  TRY_G(copy_f(st, G(G_FN_B), blob + lo.fnb, H));
+  if (lo.BF16) TRY_G(pack_gemm16(st, G(G_OUT_W), H, lo.MEL, H, 2 * MTP16, KT16, 0, blob + lo.s_outp));  // n-tile pairs (rows >= n_mels: zero)
   else
-  TRY(pack_gemm(st, G(G_OUT_W), H, lo.MEL, H, MT, HT, 0, 0, 0, DH, DHP, blob + lo.s_outp));
-  TRY(copy_f(st, G(G_OUT_B), blob + lo.outp_b, lo.MEL));
-  TRY(copy_f(st, G(G_FREQS), blob + lo.freqs, H / 2));
+  TRY_G(pack_gemm(st, G(G_OUT_W), H, lo.MEL, H, MT, HT, 0, 0, 0, DH, DHP, blob + lo.s_outp));
+  TRY_G(copy_f(st, G(G_OUT_B), blob + lo.outp_b, lo.MEL));
+  TRY_G(copy_f(st, G(G_FREQS), blob + lo.freqs, H / 2));
   for (int l = 0; l < lo.L; ++l) {
     const LayerLayout& y = lo.layer[l];
     auto W = [&](int i) { return (const float*)slots[G_COUNT + l * L_COUNT + i]; };
-    TRY(copy_f(st, W(L_N1_W), blob + y.n1w, H));
-    TRY(transpose_f(st, W(L_N1P_W), blob + y.ada1T, 2 * H, H));
-    TRY(copy_f(st, W(L_N1P_B), blob + y.ada1b, 2 * H));
-    TRY(copy_f(st, W(L_PROJ_B), blob + y.proj_b, H));
-    TRY(copy_f(st, W(L_N2_W), blob + y.n2w, H));
-    TRY(copy_f(st, W(L_N3_W), blob + y.n3w, H));
-    TRY(transpose_f(st, W(L_N3P_W), blob + y.ada3T, 2 * H, H));
-    TRY(copy_f(st, W(L_N3P_B), blob + y.ada3b, 2 * H));
+    TRY_G(copy_f(st, W(L_N1_W), blob + y.n1w, H));
+    TRY_G(transpose_f(st, W(L_N1P_W), blob + y.ada1T, 2 * H, H));
+    TRY_G(copy_f(st, W(L_N1P_B), blob + y.ada1b, 2 * H));
+    TRY_G(copy_f(st, W(L_PROJ_B), blob + y.proj_b, H));
+    TRY_G(copy_f(st, W(L_N2_W), blob + y.n2w, H));
+    TRY_G(copy_f(st, W(L_N3_W), blob + y.n3w, H));
+    TRY_G(transpose_f(st, W(L_N3P_W), blob + y.ada3T, 2 * H, H));
+    TRY_G(copy_f(st, W(L_N3P_B), blob + y.ada3b, 2 * H));
     hipLaunchKernelGGL(k_pack_upbias, dim3((2 * FM * H + 255) / 256), dim3(256), 0, st, W(L_UP_B), blob + y.up_b, FM * H);
     LAUNCH_CHECK("k_pack_upbias");
-    TRY(copy_f(st, W(L_DOWN_B), blob + y.down_b, H));
-    TRY(pack_gemm(st, W(L_KVD_W), H, R, H, RT, HT, 0, 0, 0, DH, DHP, blob + y.kvd));
-    TRY(copy_f(st, W(L_KVN_W), blob + y.kvn, R));
-    TRY(pack_gemm(st, W(L_KVU_W), R, 2 * H, R, 2 * HT, RT, 0, 0, 0, DH, DHP, blob + y.kvu));
+    TRY_G(copy_f(st, W(L_DOWN_B), blob + y.down_b, H));
+    TRY_G(pack_gemm(st, W(L_KVD_W), H, R, H, RT, HT, 0, 0, 0, DH, DHP, blob + y.kvd));
+    TRY_G(copy_f(st, W(L_KVN_W), blob + y.kvn, R));
+    TRY_G(pack_gemm(st, W(L_KVU_W), R, 2 * H, R, 2 * HT, RT, 0, 0, 0, DH, DHP, blob + y.kvu));
     // fragment stream
     // the query rows carry the softmax scale: scores come out of K Q^T in the exp2 domain, log2(e) / sqrt(head_dim)
     const float qscale = 1.4426950408889634f / sqrtf((float)DH);
     if (lo.BF16) {
       float* c16 = blob + lo.s_ctx16 + (size_t)l * ctx16_frags(lo) * kFrag;
-      TRY(pack_gemm16(st, W(L_KVD_W), H, R, H, RT, KT16, 0, c16));                                   // kv_down as n-tile pairs
-      TRY(pack_gemm16(st, W(L_KVU_W), R, 2 * H, R, 2 * HT, R / 32, 0, c16 + (size_t)RT * KT16 * kFrag));  // kv_up: K heads | V heads
-      TRY(pack_gemm16(st, W(L_QKV_W), H, 3 * H, H, 3 * HT, KT16, 0, blob + y.s_qkv, 0, 0, H, qscale));  // q | k | v as n-tile pairs
+      TRY_G(pack_gemm16(st, W(L_KVD_W), H, R, H, RT, KT16, 0, c16));                                   // kv_down as n-tile pairs
+      TRY_G(pack_gemm16(st, W(L_KVU_W), R, 2 * H, R, 2 * HT, R / 32, 0, c16 + (size_t)RT * KT16 * kFrag));  // kv_up: K heads | V heads
+      TRY_G(pack_gemm16(st, W(L_QKV_W), H, 3 * H, H, 3 * HT, KT16, 0, blob + y.s_qkv, 0, 0, H, qscale));  // q | k | v as n-tile pairs
       float* s16 = blob + y.s_body;
-      TRY(pack_gemm16(st, W(L_PROJ_W), H, H, H, HT, KT16, 1, s16));                       // k-major: k-tile = head
+      TRY_G(pack_gemm16(st, W(L_PROJ_W), H, H, H, HT, KT16, 1, s16));                       // k-major: k-tile = head
       s16 += (size_t)HT * KT16 * kFrag;
-      TRY(pack_gemm16(st, W(L_QP_W), H, H, H, HT, KT16, 0, s16, 0, 0, H, qscale));
+      TRY_G(pack_gemm16(st, W(L_QP_W), H, H, H, HT, KT16, 0, s16, 0, 0, H, qscale));
       s16 += (size_t)HT * KT16 * kFrag;
-      TRY(pack_gemm16(st, W(L_OP_W), H, H, H, HT, KT16, 1, s16));
+      TRY_G(pack_gemm16(st, W(L_OP_W), H, H, H, HT, KT16, 1, s16));
       s16 += (size_t)HT * KT16 * kFrag;
       const int blk = 4 * KT16 + HT;  // per down k-tile: value/gate fragments of its two hidden tiles, then HT down fragments
-      TRY(pack_gemm16(st, W(L_UP_W), H, 2 * FM * H, H, 2 * FM * HT, KT16, 2, s16, blk, 4 * KT16));
-      TRY(pack_gemm16(st, W(L_DOWN_W), FM * H, H, FM * H, HT, FM * HT / 2, 3, s16, blk, 4 * KT16));
+      TRY_G(pack_gemm16(st, W(L_UP_W), H, 2 * FM * H, H, 2 * FM * HT, KT16, 2, s16, blk, 4 * KT16));
+      TRY_G(pack_gemm16(st, W(L_DOWN_W), FM * H, H, FM * H, HT, FM * HT / 2, 3, s16, blk, 4 * KT16));
       continue;
     }
-    TRY(pack_gemm(st, W(L_QKV_W), H, 3 * H, H, 3 * HT, HT, 0, 0, 4, DH, DHP, blob + y.s_qkv, H, qscale));  // n-tile pairs
+    TRY_G(pack_gemm(st, W(L_QKV_W), H, 3 * H, H, 3 * HT, HT, 0, 0, 4, DH, DHP, blob + y.s_qkv, H, qscale));  // n-tile pairs
     float* s = blob + y.s_body;
-    TRY(pack_gemm(st, W(L_PROJ_W), H, H, lo.HEADS * DHP, HT, KPT, 0, 1, 1, DH, DHP, s));
+    TRY_G(pack_gemm(st, W(L_PROJ_W), H, H, lo.HEADS * DHP, HT, KPT, 0, 1, 1, DH, DHP, s));
     s += (size_t)KPT * HT * kFrag;
-    TRY(pack_gemm(st, W(L_QP_W), H, H, H, HT, HT, 0, 0, 4, DH, DHP, s, H, qscale));
+    TRY_G(pack_gemm(st, W(L_QP_W), H, H, H, HT, HT, 0, 0, 4, DH, DHP, s, H, qscale));
     s += (size_t)HT * HT * kFrag;
-    TRY(pack_gemm(st, W(L_OP_W), H, H, lo.HEADS * DHP, HT, KPT, 0, 1, 1, DH, DHP, s));
+    TRY_G(pack_gemm(st, W(L_OP_W), H, H, lo.HEADS * DHP, HT, KPT, 0, 1, 1, DH, DHP, s));
     s += (size_t)KPT * HT * kFrag;
-    TRY(pack_gemm(st, W(L_UP_W), H, 2 * FM * H, H, 2 * FM * HT, HT, 1, 0, 2, DH, DHP, s));     // value/gate tiles interleaved
-    TRY(pack_gemm(st, W(L_DOWN_W), FM * H, H, FM * H, HT, FM * HT, 0, 0, 3, DH, DHP, s));  // k-tile j after its up tiles
+    TRY_G(pack_gemm(st, W(L_UP_W), H, 2 * FM * H, H, 2 * FM * HT, HT, 1, 0, 2, DH, DHP, s));     // value/gate tiles interleaved
+    TRY_G(pack_gemm(st, W(L_DOWN_W), FM * H, H, FM * H, HT, FM * HT, 0, 0, 3, DH, DHP, s));  // k-tile j after its up tiles
   }
   return EDTTS_OK;
 }
@@ -3203,449 +3007,26 @@ int edtts_decoder_forward_len(const EdttsDims* dims, const void* packed, void* w
                               const int64_t* t_len, const int64_t* s_len, float* eps, void* stream) {
   const SettingsScope settings;
   Layout lo;
-  TRY(make_layout(dims, &lo));
+  TRY_G(make_layout(dims, &lo));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
   if (!packed || !workspace || !x || !t || !eps) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  TRY(check_shapes(lo, B, T, S));
+  TRY_G(check_shapes(lo, B, T, S));
   hipStream_t st = (hipStream_t)stream;
   const float* blob = (const float*)packed;
   float* wsb = (float*)workspace;
   Workspace ws;
   make_workspace(lo, B, T, S, B, &ws);
-  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
-  TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, wsb + ws.cond, wsb, st));
+  TRY_G(launch_len_check(t_len, s_len, B, T, S, wsb, st));
+  TRY_G(launch_cond(lo, blob, t, step_idx, nullptr, B, wsb + ws.cond, wsb, st));
   const int bstride = lo.L * 2 * 2 * lo.H;
   const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
   StepTail tail;
   tail.eps = eps;
   EDTTS_DISPATCH(lo, {
-    TRY(set_attrs_once<LN>());
-    TRY(LN::ctx(c, sem_features ? nullptr : sem_idx, sem_features));
-    TRY(LN::forward(c, x, wsb + ws.cond, bstride, tail));
+    TRY_G(set_attrs_once<LN>());
+    TRY_G(LN::ctx(c, sem_features ? nullptr : sem_idx, sem_features));
+    TRY_G(LN::forward(c, x, wsb + ws.cond, bstride, tail));
   });
-  return EDTTS_OK;
-}
-
-// ---- training: forward with a tape, backward from it (edtts_generic_bwd.h) ----------------------------------------------------
-static int train_layout(const EdttsDims* dims, const char* who, Layout* lo) {
-  if (!dims) return fail(EDTTS_ERR_ARG, "dims is NULL");
-  const int kbits = dims->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
-  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
-  if (kbits != EDTTS_KERNELS_GENERIC)
-    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training runs on the generic kernels only (compute_dtype=0x%x lacks EDTTS_KERNELS_GENERIC)", who,
-                dims->compute_dtype);
-  if (dtype != EDTTS_F32) return fail(EDTTS_ERR_UNSUPPORTED, "%s: training is fp32 only (compute_dtype=0x%x)", who, dims->compute_dtype);
-  return make_layout(dims, lo);
-}
-
-int edtts_train_dw_slab_rows(int rows) { return edtts_bwd::dw_slab_rows(rows); }
-
-int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes) {
-  Layout lo;
-  TRY(train_layout(dims, "edtts_train_tape_bytes", &lo));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  TRY(check_shapes(lo, B, T, S));
-  TrainTape tt;
-  make_tape(lo, B, T, S, &tt);
-  *out_bytes = tt.total * sizeof(float);
-  return EDTTS_OK;
-}
-
-int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes) {
-  Layout lo;
-  TRY(train_layout(dims, "edtts_train_scratch_bytes", &lo));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  TRY(check_shapes(lo, B, T, S));
-  TrainScratch ss;
-  make_train_scratch(lo, B, T, S, &ss);
-  *out_bytes = ss.total * sizeof(float);
-  return EDTTS_OK;
-}
-
-// EdttsDropout -> DropState.  *on = false for NULL or p == 0 (the call then makes exactly the launches of its plain twin).
-static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on) {
-  *on = false;
-  if (!drop || drop->p == 0.0f) return EDTTS_OK;
-  const float p = drop->p;
-  const double thr = nearbyint((double)p * 65536.0);  // (ties to even, as round() of the tests' restatement)
-  if (!(p >= 0.0f && p < 1.0f) || thr > 65535.0)
-    return fail(EDTTS_ERR_ARG, "%s: dropout p=%g is outside [0, 1) (needs round(p * 65536) <= 65535)", who, (double)p);
-  ds->k0 = (unsigned)drop->seed;
-  ds->k1 = (unsigned)(drop->seed >> 32);
-  ds->thr = (unsigned)thr;
-  ds->scale = 65536.0f / (float)(65536u - ds->thr);
-  *on = true;
-  return EDTTS_OK;
-}
-
-int edtts_decoder_forward_train(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S, const float* x,
-                                const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, float* eps,
-                                void* stream) {
-  return edtts_decoder_forward_train_drop(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, nullptr, stream);
-}
-
-int edtts_decoder_forward_train_drop(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
-                                     const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
-                                     const float* sem_features, float* eps, const EdttsDropout* drop, void* stream) {
-  return edtts_decoder_forward_train_len(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, drop, nullptr,
-                                         nullptr, stream);
-}
-
-int edtts_decoder_forward_train_len(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
-                                    const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
-                                    const float* sem_features, float* eps, const EdttsDropout* drop, const int64_t* t_len,
-                                    const int64_t* s_len, void* stream) {
-  const SettingsScope settings;
-  Layout lo;
-  TRY(train_layout(dims, "edtts_decoder_forward_train", &lo));
-  DropState ds;
-  bool dropping;
-  TRY(drop_state(drop, "edtts_decoder_forward_train_drop", &ds, &dropping));
-  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
-  if (!packed || !workspace || !tape || !x || !t || !eps) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  TRY(check_shapes(lo, B, T, S));
-  hipStream_t st = (hipStream_t)stream;
-  const float* blob = (const float*)packed;
-  float* wsb = (float*)workspace;
-  float* tp = (float*)tape;
-  Workspace ws;
-  make_workspace(lo, B, T, S, B, &ws);
-  TrainTape tt;
-  make_tape(lo, B, T, S, &tt);
-  TRY(launch_len_check(t_len, s_len, B, T, S, wsb, st));
-  TRY(launch_cond(lo, blob, t, step_idx, nullptr, B, tp + tt.cond, wsb, st));  // the AdaLN rows and t_cond go straight to the tape
-  const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
-  return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps, dropping ? &ds : nullptr);
-}
-
-int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S, const float* x,
-                           const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, const float* d_eps,
-                           void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch, void* stream) {
-  return edtts_decoder_backward_drop(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots,
-                                     d_x, d_sem_features, scratch, nullptr, stream);
-}
-
-int edtts_decoder_backward_drop(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
-                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
-                                const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
-                                const EdttsDropout* drop, void* stream) {
-  return edtts_decoder_backward_len(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots,
-                                    d_x, d_sem_features, scratch, drop, nullptr, nullptr, stream);
-}
-
-int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
-                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
-                               const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
-                               const EdttsDropout* drop, const int64_t* t_len, const int64_t* s_len, void* stream) {
-  Layout lo;
-  TRY(train_layout(dims, "edtts_decoder_backward", &lo));
-  DropState ds;
-  bool dropping;
-  TRY(drop_state(drop, "edtts_decoder_backward_drop", &ds, &dropping));
-  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
-  if (!packed || !workspace || !tape || !x || !t || !d_eps || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
-  TRY(check_shapes(lo, B, T, S));
-  TrainTape tt;
-  make_tape(lo, B, T, S, &tt);
-  TrainScratch ss;
-  make_train_scratch(lo, B, T, S, &ss);
-  TRY(launch_len_check(t_len, s_len, B, T, S, (float*)workspace, (hipStream_t)stream));  // (the index-error word: the only use of `workspace`)
-  return TrainLauncher::backward(lo, (const float*)packed, (const float*)tape, tt, (float*)scratch, ss, B, T, S, dims->window, x, t, step_idx,
-                                 sem_features ? nullptr : sem_idx, sem_features, d_eps, reinterpret_cast<float* const*>(grad_slots), d_x,
-                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr, Lens{t_len, s_len});
-}
-
-int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep, void* stream) {
-  Layout lo;
-  TRY(train_layout(dims, "edtts_dropout_mask", &lo));
-  if (!drop) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: drop is NULL");
-  DropState ds{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0u, 1.0f};  // (p == 0: threshold 0, everything kept)
-  bool dropping;
-  TRY(drop_state(drop, "edtts_dropout_mask", &ds, &dropping));
-  if (site < DROP_ATTN || site > DROP_DOWN) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: site %d is not one of 0 .. 3", site);
-  if (layer < 0 || layer >= lo.L) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: layer %d outside [0, %d)", layer, lo.L);
-  if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  TRY(check_shapes(lo, B, T, S));
-  const bool attn = site == DROP_ATTN || site == DROP_CROSS;
-  const size_t rows = attn ? (size_t)B * lo.HEADS * T : (size_t)B * T;
-  const int W = site == DROP_ATTN ? T : site == DROP_CROSS ? S : site == DROP_ACT ? lo.FM * lo.H : lo.H;
-  hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * ((W + 3) / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows,
-                     W, T, (int)attn, ds.site(layer, site));
-  LAUNCH_CHECK("k_drop_mask");
-  return EDTTS_OK;
-}
-
-int edtts_generate(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
-                   const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host, float* x_work,
-                   float* x0_out, void* stream) {
-  return edtts_generate_len(dims, packed, workspace, B, S, sem_idx, nullptr, x_T, num_steps, timesteps_host, coef_host, x_work, x0_out,
-                            stream);
-}
-
-int edtts_generate_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
-                       const int64_t* s_len, const float* x_T, int num_steps, const int64_t* timesteps_host, const float* coef_host,
-                       float* x_work, float* x0_out, void* stream) {
-  const SettingsScope settings;
-  Layout lo;
-  TRY(make_layout(dims, &lo));
-  if (!packed || !workspace || !sem_idx || !x_T || !timesteps_host || !coef_host || !x_work || !x0_out)
-    return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (num_steps < 1 || num_steps > lo.NSTEP)
-    return fail(EDTTS_ERR_ARG, "num_steps=%d outside [1,%d] (step_emb rows; the reference raises IndexError)", num_steps, lo.NSTEP);
-  const int T = 2 * S;  // inference.py:31
-  TRY(check_shapes(lo, B, T, S));
-  SamplerInputs in;
-  in.t_host = timesteps_host; in.sem_idx = sem_idx;
-  in.ln = Lens{s_len, s_len, true};  // frames = 2 x tokens (inference.py:31)
-  in.x_T = x_T; in.x = x_work;
-  return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int, size_t o) {
-    StepTail tail;
-    tail.kind = TAIL_DDIM; tail.x_prev = x_work + o; tail.x0 = x0_out + o; tail.coef = coef_host + 4 * i;
-    return tail;
-  });
-}
-
-int edtts_sample_multistep(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const int64_t* sem_idx,
-                           const float* sem_features, const float* x_T, int num_steps, const int64_t* timesteps_host,
-                           const float* coef_host, float* hist, float* x0_all, float* x_out, void* stream) {
-  return edtts_sample_multistep_len(dims, packed, workspace, B, T, S, sem_idx, sem_features, nullptr, nullptr, x_T, num_steps,
-                                    timesteps_host, coef_host, hist, x0_all, x_out, stream);
-}
-
-int edtts_sample_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int T, int S, const int64_t* sem_idx,
-                               const float* sem_features, const int64_t* t_len, const int64_t* s_len, const float* x_T, int num_steps,
-                               const int64_t* timesteps_host, const float* coef_host, float* hist, float* x0_all, float* x_out,
-                               void* stream) {
-  const SettingsScope settings;
-  Layout lo;
-  TRY(make_layout(dims, &lo));
-  if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
-  if (!packed || !workspace || !x_T || !timesteps_host || !coef_host || !hist || !x_out) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (num_steps < 1 || num_steps > lo.NSTEP)
-    return fail(EDTTS_ERR_ARG, "num_steps=%d outside [1,%d] (step_emb rows; the reference raises IndexError)", num_steps, lo.NSTEP);
-  TRY(check_shapes(lo, B, T, S));
-  TRY(check_lms_modes(coef_host, num_steps));
-  SamplerInputs in;
-  in.t_host = timesteps_host; in.sem_idx = sem_idx; in.sem_features = sem_features;
-  in.ln = Lens{t_len, s_len};
-  in.x_T = x_T; in.x = x_out;
-  const size_t per = (size_t)B * T * lo.MEL;
-  return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int, size_t o) {
-    StepTail tail;
-    tail.kind = TAIL_LMS; tail.x_prev = x_out + o;
-    tail.lms = lms_step_args(coef_host + 8 * i, hist, x0_all, per, i, o);
-    return tail;
-  });
-}
-
-int edtts_sample_ddpm(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
-                      const float* x_T, int num_steps, const int64_t* t_all, const float* coef_host, const float* noise_all,
-                      uint64_t seed, int64_t batch_offset, float* x_out, void* stream) {
-  return edtts_sample_ddpm_len(dims, packed, workspace, B, S, sem_idx, nullptr, x_T, num_steps, t_all, coef_host, noise_all, seed,
-                               batch_offset, x_out, stream);
-}
-
-int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* workspace, int B, int S, const int64_t* sem_idx,
-                          const int64_t* s_len, const float* x_T, int num_steps, const int64_t* t_all, const float* coef_host,
-                          const float* noise_all, uint64_t seed, int64_t batch_offset, float* x_out, void* stream) {
-  const SettingsScope settings;
-  Layout lo;
-  TRY(make_layout(dims, &lo));
-  if (!packed || !workspace || !sem_idx || !x_T || !t_all || !coef_host || !x_out) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", num_steps);
-  if (batch_offset < 0) return fail(EDTTS_ERR_ARG, "batch_offset=%lld < 0", (long long)batch_offset);
-  const int T = 2 * S;
-  TRY(check_shapes(lo, B, T, S));
-  SamplerInputs in;
-  in.t_dev = t_all; in.sem_idx = sem_idx;  // step_idx = None (train.py:155 usage)
-  in.ln = Lens{s_len, s_len, true};  // frames = 2 x tokens
-  in.x_T = x_T; in.x = x_out;
-  const size_t per_step = (size_t)B * T * lo.MEL;
-  return run_sampler(dims, lo, packed, workspace, B, T, S, num_steps, in, stream, [&](int i, int off, size_t o) {
-    StepTail tail;
-    tail.kind = TAIL_DDPM; tail.x_prev = x_out + o; tail.coef = coef_host + 3 * i;
-    tail.ddpm = DdpmStepArgs{noise_all ? noise_all + (size_t)i * per_step + o : nullptr, (unsigned long long)seed,
-                             ((unsigned long long)batch_offset + (unsigned long long)off) * T * lo.MEL, kStreamDdpmStep + (unsigned)i};
-    return tail;
-  });
-}
-
-// x[b][f < overlap][:] = c_known * known[b][f][:] + c_noise * noise   (noise: injected [B, overlap, MEL] or Philox keyed by
-// (seed, step, global element of the [B, overlap, MEL] tensor)); c_noise = 0 -> exact copy of the known frames.
-// Per-row seeds (device uint64 [B], or null): row b draws with seeds[b] at its ROW-LOCAL element index -- the draws of the same call
-// made on row b alone.  Per-row frame counts t_len (or null): row b injects its first min(overlap, T_b) frames only.
-__global__ __launch_bounds__(256) void k_inpaint_inject(float* x, const float* known, const float* noise, int B, int T, int ov, int MEL,
-                                                        float c_known, float c_noise, unsigned long long seed, unsigned step,
-                                                        const unsigned long long* seeds, const int64_t* t_len) {
-  const size_t per = (size_t)ov * MEL / 4, n4 = (size_t)B * per;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / per, r = i - b * per;
-    const int Tb = t_len ? utt_len_of(t_len[b], T, false) : T;  // (utt_len_lane called from here changed k_gen_embed's code)
-    const size_t live = Tb < ov ? (size_t)Tb * MEL : 4 * per;  // elements of this row's injected frames
-    if (4 * r >= live) continue;
-    const f4 kv = ldg4(known + 4 * i);
-    f4 o = kv;
-    if (c_noise != 0.f) {
-      const f4 nz = noise ? ldg4(noise + 4 * i) : (seeds ? philox_normal4(seeds[b], step, r) : philox_normal4(seed, step, i));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = qsample_elem(kv[e], c_known, nz[e], c_noise);
-    }
-    if (4 * r + 4 <= live) {
-      stg4(x + (b * T) * MEL + 4 * r, o);
-    } else {  // (a row shorter than the overlap whose last frame ends inside this quad: n_mels % 4 != 0)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (4 * r + e < live) x[(b * T) * MEL + 4 * r + e] = o[e];
-    }
-  }
-}
-
-// ... one element per thread, for shapes whose rows are not float4-aligned (generic path, n_mels % 4 != 0): the same values (element e
-// of the [B, overlap, MEL] noise tensor is lane e & 3 of Philox draw e >> 2; with per-row seeds e counts from the row's start)
-__global__ __launch_bounds__(256) void k_inpaint_inject1(float* x, const float* known, const float* noise, int B, int T, int ov, int MEL,
-                                                         float c_known, float c_noise, unsigned long long seed, unsigned step,
-                                                         const unsigned long long* seeds, const int64_t* t_len) {
-  const size_t per = (size_t)ov * MEL, n = (size_t)B * per;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / per, r = i - b * per;
-    const int Tb = t_len ? utt_len_of(t_len[b], T, false) : T;
-    if (Tb < ov && r >= (size_t)Tb * MEL) continue;
-    float o = known[i];
-    if (c_noise != 0.f) {
-      const float nz = noise ? noise[i] : (seeds ? philox_normal4(seeds[b], step, r >> 2)[(int)(r & 3)] : philox_normal4(seed, step, i >> 2)[(int)(i & 3)]);
-      o = qsample_elem(o, c_known, nz, c_noise);
-    }
-    x[(b * T) * MEL + r] = o;
-  }
-}
-
-int edtts_sample_inpaint(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
-                         const float* sem_features, const float* zero_features, float* x, int num_steps,
-                         const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel, int overlap_len,
-                         const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond, void* stream) {
-  return edtts_sample_inpaint_len(dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all,
-                                  step_all, coef_host, known_mel, overlap_len, noise_k, seed, cfg_scale, v_uncond, nullptr, nullptr, nullptr,
-                                  stream);
-}
-
-// One launch of k_inpaint_inject (whole float4s) or, for a known block that is not made of them (generic path, n_mels % 4 != 0),
-// k_inpaint_inject1: q_sample of the known frames with step `step`'s noise (injected: block `step` of noise_k) and stream id.
-static void launch_inject(const InpaintArgs& a, int mel, float c_known, float c_noise, int step) {
-  const size_t per_k = (size_t)a.B * a.overlap_len * mel;
-  const bool vec = ((size_t)a.overlap_len * mel) % 4 == 0 && ((size_t)a.T * mel) % 4 == 0;
-  const size_t bx = (per_k / (vec ? 4 : 1) + 255) / 256;
-  hipLaunchKernelGGL(vec ? k_inpaint_inject : k_inpaint_inject1, dim3(bx > 2048 ? 2048u : (unsigned)bx), dim3(256), 0, (hipStream_t)a.stream, a.x, a.known_mel,
-                     a.noise_k ? a.noise_k + (size_t)step * per_k : nullptr, a.B, a.T, a.overlap_len, mel, c_known, c_noise,
-                     (unsigned long long)a.seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(a.seeds),
-                     a.t_len);
-}
-
-int edtts_sample_inpaint_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
-                             const float* sem_features, const float* zero_features, float* x, int num_steps,
-                             const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
-                             int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
-                             const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, void* stream) {
-  const SettingsScope settings;
-  Layout lo;
-  TRY(make_layout(dims, &lo));
-  const InpaintArgs a{dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all, step_all,
-                      coef_host, known_mel, overlap_len, noise_k, seed, cfg_scale, v_uncond, t_len, s_len, seeds, stream};
-  // coef_host rows: {sqrt_ab[t], sqrt_1mab[t], sqrt(ab[t_next]), sqrt(1 - ab[t_next])}
-  return run_inpaint(
-      a, lo, true, [] { return EDTTS_OK; },
-      [&](int i) -> int {  // q_sample(known_mel, t) into the first overlap_len frames (inference_pipeline.py:117-123)
-        launch_inject(a, lo.MEL, coef_host[4 * i], coef_host[4 * i + 1], i);
-        LAUNCH_CHECK("k_inpaint_inject");
-        return EDTTS_OK;
-      },
-      [&](int i) {
-        const float* k = coef_host + 4 * i;
-        StepTail tail;
-        tail.kind = TAIL_VPRED; tail.x_prev = x;
-        tail.vp = VpredStepArgs{{k[0], k[1], k[2], k[3], cfg_scale}, nullptr};
-        return tail;
-      },
-      [&]() -> int {  // final force (inference_pipeline.py:135-136)
-        launch_inject(a, lo.MEL, 1.0f, 0.0f, 0);
-        LAUNCH_CHECK("k_inpaint_inject");
-        return EDTTS_OK;
-      });
-}
-
-int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T,
-                                       int S, const float* sem_features, const float* zero_features, float* x, int num_steps,
-                                       const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
-                                       int overlap_len, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
-                                       const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, float* hist, float* x0_all,
-                                       void* stream) {
-  const SettingsScope settings;
-  Layout lo;
-  TRY(make_layout(dims, &lo));
-  const InpaintArgs a{dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all, step_all,
-                      coef_host, known_mel, overlap_len, noise_k, seed, cfg_scale, v_uncond, t_len, s_len, seeds, stream};
-  const size_t per = (size_t)B * T * lo.MEL, per_k = (size_t)B * overlap_len * lo.MEL;
-  // q_sample's scalars of step i are in its coefficient row: p0 = sqrt_ab[t_i], p1 = -sqrt_1mab[t_i] (v-prediction rows)
-  auto c_known = [&](int i) { return coef_host[8 * i + 1]; };
-  auto c_noise = [&](int i) { return -coef_host[8 * i + 2]; };
-  return run_inpaint(
-      a, lo, hist != nullptr, [&] { return check_lms_modes(coef_host, num_steps); },
-      [&](int i) -> int {  // step 0's q_sample of the known frames; every later one is written by the tail of the step before it
-        if (i > 0) return EDTTS_OK;
-        launch_inject(a, lo.MEL, c_known(0), c_noise(0), 0);
-        LAUNCH_CHECK("k_inpaint_inject");
-        return EDTTS_OK;
-      },
-      [&](int i) {
-        StepTail tail;
-        tail.kind = TAIL_VLMS; tail.x_prev = x;
-        tail.lms = lms_step_args(coef_host + 8 * i, hist, x0_all, per, i, 0);
-        tail.vp.k.cfg = cfg_scale;
-        if (known_mel) {  // (whole float4s; a known block that is not made of them goes through the generic path's per-element tail)
-          const bool last = i + 1 == num_steps;  // after the last step: the known frames themselves (inference_pipeline.py:135-136)
-          tail.blend = BlendStepArgs{known_mel, (noise_k && !last) ? noise_k + (size_t)(i + 1) * per_k : nullptr, overlap_len, lo.MEL,
-                                     last ? 1.0f : c_known(i + 1), last ? 0.0f : c_noise(i + 1),
-                                     (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(seeds),
-                                     kStreamInpaintStep + (unsigned)(last ? 0 : i + 1)};
-        }
-        return tail;
-      },
-      [] { return EDTTS_OK; });
-}
-
-static unsigned step_blocks(const StepArgs& a) {  // blocks per utterance of k_ddim / k_ddpm
-  const size_t bx = ((a.vec4 ? a.n_per_batch / 4 : a.n_per_batch) + 255) / 256;
-  return bx > 2048 ? 2048u : (bx < 1 ? 1u : (unsigned)bx);
-}
-
-int edtts_ddim_step(const float* alpha_bar, int n_table, const float* x, const float* eps, const int64_t* t,
-                    const int64_t* t_prev, int B, size_t n_per_batch, float eta, const float* noise, float* x_prev, float* x0,
-                    void* stream) {
-  if (!alpha_bar || !x || !eps || !t || !t_prev || !x_prev || !x0) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (eta > 0.f && !noise) return fail(EDTTS_ERR_ARG, "eta > 0 needs a noise tensor");
-  if (B < 1 || n_per_batch < 1 || n_table < 1) return fail(EDTTS_ERR_ARG, "bad sizes");
-  StepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.alpha_bar = alpha_bar; a.n_table = n_table; a.x = x; a.eps = eps; a.t = t; a.t_prev = t_prev;
-  a.n_per_batch = n_per_batch; a.eta = eta; a.noise = eta > 0.f ? noise : nullptr; a.x_prev = x_prev; a.x0 = x0;
-  a.vec4 = step_vec4(n_per_batch, {x, eps, a.noise, x_prev, x0});
-  hipLaunchKernelGGL(k_ddim, dim3(step_blocks(a), B), dim3(256), 0, (hipStream_t)stream, a);
-  LAUNCH_CHECK("k_ddim");
-  return EDTTS_OK;
-}
-
-int edtts_ddpm_step(const float* alphas, const float* alpha_bar, const float* betas, const float* post_var, int n_table,
-                    const float* x, const float* eps, const int64_t* t, int B, size_t n_per_batch, const float* noise,
-                    float* x_prev, void* stream) {
-  if (!alphas || !alpha_bar || !betas || !post_var || !x || !eps || !t || !noise || !x_prev) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (B < 1 || n_per_batch < 1 || n_table < 1) return fail(EDTTS_ERR_ARG, "bad sizes");
-  StepArgs a;
-  memset(&a, 0, sizeof(a));
-  a.alphas = alphas; a.alpha_bar = alpha_bar; a.betas = betas; a.post_var = post_var; a.n_table = n_table;
-  a.x = x; a.eps = eps; a.t = t; a.n_per_batch = n_per_batch; a.noise = noise; a.x_prev = x_prev;
-  a.vec4 = step_vec4(n_per_batch, {x, eps, noise, x_prev});
-  hipLaunchKernelGGL(k_ddpm, dim3(step_blocks(a), B), dim3(256), 0, (hipStream_t)stream, a);
-  LAUNCH_CHECK("k_ddpm");
   return EDTTS_OK;
 }
 
@@ -3715,64 +3096,6 @@ int edtts_dsconv_forward(const float* x, const float* dw, const float* pw, const
   return EDTTS_OK;
 }
 
-// standard normals from the Philox stream of (seed, stream_id), element i of the GLOBAL tensor at out[i - elem_offset]
-__global__ __launch_bounds__(256) void k_randn(float* out, size_t n, unsigned long long seed, unsigned stream_id,
-                                               unsigned long long elem_offset, float scale) {
-  const size_t n4 = n >> 2;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f4 v = philox_normal4(seed, stream_id, (elem_offset >> 2) + i);
-    stg4(out + 4 * i, v * scale);
-  }
-}
-
-int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_t elem_offset, float scale, void* stream) {
-  if ((n & 3) || (elem_offset & 3)) return fail(EDTTS_ERR_ARG, "n=%zu and elem_offset=%llu must be multiples of 4", n, (unsigned long long)elem_offset);
-  if (stream_id >= kStreamDdpmStep) return fail(EDTTS_ERR_ARG, "stream_id %u is reserved for the samplers' per-step draws (>= 0x10000)", stream_id);
-  if (n == 0) return EDTTS_OK;  // an empty shard (fewer utterances than ranks): its zero-element tensor has a NULL data pointer
-  if (!out) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if ((uintptr_t)out & 15) return fail(EDTTS_ERR_ARG, "out must be 16-byte aligned");
-  size_t bx = (n / 4 + 255) / 256;
-  if (bx > 4096) bx = 4096;
-  hipLaunchKernelGGL(k_randn, dim3((unsigned)bx), dim3(256), 0, (hipStream_t)stream, out, n, (unsigned long long)seed, (unsigned)stream_id,
-                     (unsigned long long)elem_offset, scale);
-  LAUNCH_CHECK("k_randn");
-  return EDTTS_OK;
-}
-
-// row b of [B, n] = the first n draws of the Philox stream (seeds[b], stream_id): element e is lane e & 3 of draw e >> 2, as in k_randn
-__global__ __launch_bounds__(256) void k_randn_rows(float* out, int B, size_t n, const unsigned long long* seeds, unsigned stream_id,
-                                                    float scale) {
-  const size_t q = (n + 3) >> 2, nq = (size_t)B * q;  // quads per row, all quads
-  const bool vec = (n & 3) == 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / q, r = i - b * q;
-    const f4 v = philox_normal4(seeds[b], stream_id, r) * scale;
-    float* o = out + b * n + 4 * r;
-    if (vec) {
-      stg4(o, v);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (4 * r + e < n) o[e] = v[e];
-    }
-  }
-}
-
-int edtts_randn_rows(float* out, int B, size_t n_per_row, const uint64_t* seeds, uint32_t stream_id, float scale, void* stream) {
-  if (B < 0) return fail(EDTTS_ERR_ARG, "B=%d < 0", B);
-  if (stream_id >= kStreamDdpmStep) return fail(EDTTS_ERR_ARG, "stream_id %u is reserved for the samplers' per-step draws (>= 0x10000)", stream_id);
-  if (B == 0 || n_per_row == 0) return EDTTS_OK;
-  if (!out || !seeds) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if ((n_per_row & 3) == 0 && ((uintptr_t)out & 15)) return fail(EDTTS_ERR_ARG, "out must be 16-byte aligned");
-  const size_t nq = (size_t)B * ((n_per_row + 3) / 4);
-  size_t bx = (nq + 255) / 256;
-  if (bx > 4096) bx = 4096;
-  hipLaunchKernelGGL(k_randn_rows, dim3((unsigned)bx), dim3(256), 0, (hipStream_t)stream, out, B, n_per_row,
-                     reinterpret_cast<const unsigned long long*>(seeds), (unsigned)stream_id, scale);
-  LAUNCH_CHECK("k_randn_rows");
-  return EDTTS_OK;
-}
-
 int edtts_index_errors(void* workspace, int* flags_host, void* stream) {
   if (!workspace || !flags_host) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   hipStream_t st = (hipStream_t)stream;
@@ -3783,125 +3106,6 @@ int edtts_index_errors(void* workspace, int* flags_host, void* stream) {
   *flags_host = (int)v;
   return EDTTS_OK;
 }
-
-// The index-error word of the mel post-processing *_len entry points: one device uint32 the caller owns (read and cleared by
-// edtts_index_errors, like Workspace::err); rows whose frame count is outside [t_min, T] set EDTTS_IDX_LEN in it.
-static int melpost_len_check(const int64_t* t_len, int B, int T, int t_min, void* idx_err, hipStream_t st) {
-  if (!t_len || !idx_err) return EDTTS_OK;
-  return launch_len_check(t_len, nullptr, B, T, 0, reinterpret_cast<float*>(idx_err), st, t_min);
-}
-
-int edtts_mel_to_spec(const float* mel_n, const float* mean, const float* stdv, const float* pinv, int B, int T, int n_mels, int n_freqs,
-                      float* spec, void* stream) {
-  return edtts_mel_to_spec_len(mel_n, mean, stdv, pinv, B, T, n_mels, n_freqs, nullptr, 0, 0, nullptr, spec, stream);
-}
-
-int edtts_mel_to_spec_len(const float* mel_n, const float* mean, const float* stdv, const float* pinv, int B, int T, int n_mels, int n_freqs,
-                          const int64_t* t_len, int smooth_h, int smooth_w, void* idx_err, float* spec, void* stream) {
-  if (!mel_n || !pinv || !spec || (!mean != !stdv)) return fail(EDTTS_ERR_ARG, "NULL pointer argument (mean and std come together)");
-  if (B < 1 || T < 1 || n_mels < 1 || n_freqs < 1 || n_mels > 512) return fail(EDTTS_ERR_ARG, "bad sizes");
-  const bool smooth = smooth_h != 0 || smooth_w != 0;
-  if (smooth) {
-    if (smooth_h < 1 || smooth_w < 1 || !(smooth_h & 1) || !(smooth_w & 1) || smooth_h > melpost::kSmoothMax || smooth_w > melpost::kSmoothMax)
-      return fail(EDTTS_ERR_ARG, "smooth %d x %d: the box filter's sides are odd and in [1, %d] (0 x 0: none)", smooth_h, smooth_w,
-                  melpost::kSmoothMax);
-    if (mean) return fail(EDTTS_ERR_ARG, "smoothing takes the linear mel spectrogram (mean and std NULL)");
-    if (n_mels > melpost::kSmoothMaxMels) return fail(EDTTS_ERR_ARG, "smoothing is built for n_mels <= %d, got %d", melpost::kSmoothMaxMels, n_mels);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  TRY(melpost_len_check(t_len, B, T, 1, idx_err, st));
-  const dim3 grid((T + 15) / 16, B);
-  if (smooth) {
-    hipLaunchKernelGGL(melpost::k_mel_to_spec_smooth, grid, dim3(melpost::kThreads), (size_t)(32 + smooth_w - 1) * n_mels * sizeof(float), st, mel_n,
-                       pinv, T, n_mels, n_freqs, t_len, smooth_h, smooth_w, spec);
-    LAUNCH_CHECK("k_mel_to_spec_smooth");
-  } else {
-    hipLaunchKernelGGL(melpost::k_mel_to_spec, grid, dim3(melpost::kThreads), 16 * n_mels * sizeof(float), st, mel_n, mean, stdv, pinv, T, n_mels,
-                       n_freqs, t_len, spec);
-    LAUNCH_CHECK("k_mel_to_spec");
-  }
-  return EDTTS_OK;
-}
-
-int edtts_griffin_lim_scratch_floats(int B, int T, int n_fft, int hop, size_t* out_floats) {
-  if (!out_floats || B < 1 || T < 2 || hop < 1) return fail(EDTTS_ERR_ARG, "bad sizes");
-  if (n_fft != melpost::kNfft) return fail(EDTTS_ERR_UNSUPPORTED, "n_fft=%d (compiled: %d)", n_fft, melpost::kNfft);
-  const size_t bt = (size_t)B * T, Lp = (size_t)n_fft + (size_t)hop * (T - 1);
-  *out_floats = bt * melpost::kBins * 5 + bt * n_fft + (size_t)B * Lp;  // mag | angles | tprev | frames | padded signal
-  return EDTTS_OK;
-}
-
-// Both Griffin-Lim entry points.  t_len == nullptr: every row has T frames, the draws are keyed by (seed, element of the batch).
-static int griffin_lim_run(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
-                           float momentum, float power, const float* angles0, uint64_t seed, const int64_t* t_len, const uint64_t* seeds,
-                           void* idx_err, float* scratch, float* wave_out, void* stream) {
-  if (!spec || !window || !twiddle || !scratch || !wave_out) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (B < 1 || T < 2 || hop < 1 || hop > n_fft || n_iter < 0 || power <= 0.f) return fail(EDTTS_ERR_ARG, "bad sizes");
-  if (n_fft != melpost::kNfft) return fail(EDTTS_ERR_UNSUPPORTED, "n_fft=%d (compiled: %d, win_length = n_fft)", n_fft, melpost::kNfft);
-  if (hop * (T - 1) <= n_fft / 2) return fail(EDTTS_ERR_ARG, "signal of %d samples is shorter than the reflect padding (torch.stft raises too)", hop * (T - 1));
-  using namespace melpost;
-  hipStream_t st = (hipStream_t)stream;
-  // the shortest row the solo call accepts: hop (T_b - 1) > n_fft / 2; shorter device-side lengths are flagged (and only clamped into [1, T])
-  TRY(melpost_len_check(t_len, B, T, (n_fft / 2) / hop + 2, idx_err, st));
-  const size_t bt = (size_t)B * T;
-  const int Lp = n_fft + hop * (T - 1);
-  float* mag = scratch;
-  cplx* ang = reinterpret_cast<cplx*>(mag + bt * kBins);
-  cplx* tprev = ang + bt * kBins;
-  float* frames = reinterpret_cast<float*>(tprev + bt * kBins);
-  float* wave = frames + bt * n_fft;
-  const cplx* tw = reinterpret_cast<const cplx*>(twiddle);
-  const float mom = momentum / (1.0f + momentum);
-  hipLaunchKernelGGL(k_gl_init, dim3(T, B), dim3(kThreads), 0, st, spec, angles0, T, 1.0f / power, (unsigned long long)seed, t_len,
-                     reinterpret_cast<const unsigned long long*>(seeds), mag, ang, tprev);
-  LAUNCH_CHECK("k_gl_init");
-  int gx = (Lp + kThreads - 1) / kThreads;
-  for (int it = 0; it <= n_iter; ++it) {
-    hipLaunchKernelGGL(k_gl_istft, dim3(T, B), dim3(kThreads), 0, st, mag, ang, window, tw, T, t_len, frames);
-    hipLaunchKernelGGL(k_gl_ola, dim3(gx, B), dim3(kThreads), 0, st, frames, window, T, hop, Lp, t_len, wave);
-    if (it < n_iter) hipLaunchKernelGGL(k_gl_stft, dim3(T, B), dim3(kThreads), 0, st, wave, window, tw, T, hop, Lp, mom, t_len, ang, tprev);
-  }
-  LAUNCH_CHECK("griffin-lim kernels");
-  // torch.istft trims the centre padding: n_fft / 2 at the start, and (length = None) as much at the end
-  if (t_len) {
-    hipLaunchKernelGGL(k_gl_trim, dim3((hop * (T - 1) + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, wave, T, hop, Lp, t_len, wave_out);
-    LAUNCH_CHECK("k_gl_trim");
-    return EDTTS_OK;
-  }
-  HIP_TRY(hipMemcpy2DAsync(wave_out, (size_t)hop * (T - 1) * sizeof(float), wave + n_fft / 2, (size_t)Lp * sizeof(float),
-                           (size_t)hop * (T - 1) * sizeof(float), B, hipMemcpyDeviceToDevice, st));
-  return EDTTS_OK;
-}
-
-int edtts_griffin_lim(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
-                      float momentum, float power, const float* angles0, uint64_t seed, float* scratch, float* wave_out, void* stream) {
-  return griffin_lim_run(spec, B, T, n_fft, hop, window, twiddle, n_iter, momentum, power, angles0, seed, nullptr, nullptr, nullptr, scratch,
-                         wave_out, stream);
-}
-
-int edtts_griffin_lim_len(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
-                          float momentum, float power, const float* angles0, const int64_t* t_len, const uint64_t* seeds, void* idx_err,
-                          float* scratch, float* wave_out, void* stream) {
-  if (!t_len) return fail(EDTTS_ERR_ARG, "t_len is NULL (edtts_griffin_lim is the call without lengths)");
-  if (!angles0 && !seeds) return fail(EDTTS_ERR_ARG, "seeds is NULL: without angles0, t_len and seeds come together");
-  return griffin_lim_run(spec, B, T, n_fft, hop, window, twiddle, n_iter, momentum, power, angles0, 0, t_len, seeds, idx_err, scratch, wave_out,
-                         stream);
-}
-
-#ifdef EDTTS_STAMPS
-// Diagnostic builds only (-DEDTTS_STAMPS; scratch/stamps_bf16.py): where block 0 / wave 0 of the bf16 layer kernel spends its cycles.
-int edtts_debug_set_stamps(void* device_buffer) {
-  g_stamps_fwd = (unsigned long long*)device_buffer;
-  return EDTTS_OK;
-}
-#endif
-
-#ifdef EDTTS_WAVELOG
-int edtts_debug_set_wavelog(void* device_buffer) {
-  g_wavelog = (unsigned long long*)device_buffer;
-  return EDTTS_OK;
-}
-#endif
 
 int edtts_set_coop(int mode) {
   if (mode == -1 || mode == 0 || mode == 14 || mode == 24 || mode == 22) return g_coop.exchange(mode);
@@ -3920,163 +3124,9 @@ int edtts_substreams_for(const EdttsDims* dims, int B, int T) {
   return substreams_for(lo, B, T, (T + 1) / 2);
 }
 
-int edtts_profile_enable(int max_records) {
-  std::lock_guard<std::mutex> lock(g_prof.mu);
-  g_prof.on.store(false);
-  for (hipEvent_t e : g_prof.start) (void)hipEventDestroy(e);
-  for (hipEvent_t e : g_prof.stop) (void)hipEventDestroy(e);
-  g_prof.start.clear(); g_prof.stop.clear(); g_prof.used = 0;
-  if (max_records < 0) return fail(EDTTS_ERR_ARG, "max_records < 0");
-  for (int i = 0; i < max_records; ++i) {
-    hipEvent_t a, b;
-    HIP_TRY(hipEventCreate(&a));
-    HIP_TRY(hipEventCreate(&b));
-    g_prof.start.push_back(a); g_prof.stop.push_back(b);
-  }
-  g_prof.on.store(max_records > 0);
-  return EDTTS_OK;
-}
-
-int edtts_profile_collect(double* ms_by_kind, int* launches_by_kind) {
-  if (!ms_by_kind || !launches_by_kind) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  std::lock_guard<std::mutex> lock(g_prof.mu);
-  ms_by_kind[0] = ms_by_kind[1] = 0.0;
-  launches_by_kind[0] = launches_by_kind[1] = 0;
-  for (int i = 0; i < g_prof.used; ++i) {
-    HIP_TRY(hipEventSynchronize(g_prof.stop[i]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, g_prof.start[i], g_prof.stop[i]));
-    ms_by_kind[0] += ms;  // (slot 1, the FFN half of a two-launch layer, stays 0: every layer is one launch)
-    launches_by_kind[0] += 1;
-  }
-  g_prof.used = 0;
-  return EDTTS_OK;
-}
-
-// ---- optimiser step (edtts_optim.h) ------------------------------------------------------------------------------------------------
-int edtts_optim_chunk_size(void) { return edtts_opt::kOptChunk; }
-
-int edtts_optim_chunk_table(const int64_t* numels, int n_tensors, int cap, int32_t* tensor, int64_t* offset, int32_t* count, int* n_chunks) {
-  if (!numels || !n_chunks || n_tensors < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: NULL pointer argument or n_tensors < 0");
-  long long n = 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    if (numels[i] < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: numels[%d] = %lld < 0", i, (long long)numels[i]);
-    for (long long o = 0; o < numels[i]; o += edtts_opt::kOptChunk, ++n) {
-      if (n >= cap) continue;  // (counted, not written)
-      if (!tensor || !offset || !count) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: cap > 0 needs the three output arrays");
-      const long long left = numels[i] - o;
-      tensor[n] = i;
-      offset[n] = o;
-      count[n] = (int32_t)(left < edtts_opt::kOptChunk ? left : edtts_opt::kOptChunk);
-    }
-  }
-  if (n > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_chunk_table: %lld chunks", n);
-  *n_chunks = (int)n;
-  return EDTTS_OK;
-}
-
-int edtts_optim_scratch_bytes(int n_chunks, int n_groups, size_t* out_bytes) {
-  if (!out_bytes || n_chunks < 0 || n_groups < 1) return fail(EDTTS_ERR_ARG, "edtts_optim_scratch_bytes: n_chunks=%d n_groups=%d", n_chunks, n_groups);
-  edtts_opt::OptScratch s;
-  edtts_opt::opt_scratch((size_t)n_chunks, (size_t)n_groups, &s);
-  *out_bytes = s.total;
-  return EDTTS_OK;
-}
-
-int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
-                     void* scratch, size_t scratch_bytes, void* stream) {
-  using namespace edtts_opt;
-  if (n_tensors < 0 || n_groups < 1 || (n_tensors && !tensors) || !groups || !scratch)
-    return fail(EDTTS_ERR_ARG, "edtts_optim_step: NULL pointer argument, n_tensors=%d or n_groups=%d", n_tensors, n_groups);
-  if (flags & ~(EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE | EDTTS_OPT_ZERO_GRADS | EDTTS_OPT_EMA_ONLY))
-    return fail(EDTTS_ERR_ARG, "edtts_optim_step: unknown flag bits 0x%x", flags);
-  const bool ema_only = flags & EDTTS_OPT_EMA_ONLY;
-  if (ema_only && (flags & ~EDTTS_OPT_EMA_ONLY)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: EDTTS_OPT_EMA_ONLY excludes the other flags");
-  if ((flags & EDTTS_OPT_CLIP) && !(max_norm >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: max_norm=%g", max_norm);
-  long long n_chunks = 0;
-  int n_live = 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    const EdttsOptimTensor& t = tensors[i];
-    if (t.numel < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has numel %lld", i, (long long)t.numel);
-    if (t.numel == 0) continue;
-    if (!t.p || (!ema_only && (!t.g || !t.m || !t.v)) || (ema_only && !t.ema))
-      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a NULL p, g, m, v or (EDTTS_OPT_EMA_ONLY) ema", i);
-    if (((size_t)t.p | (size_t)t.g | (size_t)t.m | (size_t)t.v | (size_t)t.ema | (size_t)t.mirror | (size_t)t.ema_mirror) & 3)
-      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a pointer that is not 4-byte aligned", i);
-    if (t.group < 0 || t.group >= n_groups) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d names group %d of %d", i, t.group, n_groups);
-    if (t.rows < 0 || t.cols < 0 || (t.rows > 0 && (int64_t)t.rows * t.cols != t.numel))
-      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: rows=%d cols=%d do not make numel=%lld", i, t.rows, t.cols, (long long)t.numel);
-    if (t.ema_mirror && !t.ema) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has an ema_mirror without an ema", i);
-    if (t.ema && !(t.ema_decay >= 0.f && t.ema_decay <= 1.f)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: ema_decay=%g", i, (double)t.ema_decay);
-    n_chunks += opt_chunks_of(t.numel);
-    ++n_live;
-  }
-  if (n_chunks == 0) return EDTTS_OK;  // nothing to step: as torch, no state changes (the step counter included)
-  if (n_chunks > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_step: %lld chunks", n_chunks);
-  OptScratch ls;
-  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
-  if (ls.total > scratch_bytes)
-    return fail(EDTTS_ERR_ARG, "edtts_optim_step: %lld chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  char* sc = (char*)scratch;
-  const size_t up_bytes = ls.total - ls.groups;  // groups | tensors | chunks, as they lie in the scratch
-
-  std::lock_guard<std::mutex> lock(g_opt_mu);
-  OptSlot& slot = g_opt_ring[g_opt_next];
-  g_opt_next = (g_opt_next + 1) % kOptRing;
-  if (slot.pending) {
-    HIP_TRY(hipEventSynchronize(slot.ev));  // (returns at once unless kOptRing steps are outstanding)
-    slot.pending = false;
-  }
-  if (slot.cap < up_bytes) {
-    if (slot.host) HIP_TRY(hipHostFree(slot.host));
-    slot.host = nullptr;
-    slot.cap = 0;
-    HIP_TRY(hipHostMalloc(&slot.host, up_bytes + up_bytes / 2, hipHostMallocDefault));
-    slot.cap = up_bytes + up_bytes / 2;
-  }
-  if (slot.ev) (void)hipEventDestroy(slot.ev);  // (an event belongs to the device that was current when it was made: a new one per step)
-  slot.ev = nullptr;
-  HIP_TRY(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
-  char* up = (char*)slot.host;
-  memset(up, 0, up_bytes);
-  memcpy(up, groups, (size_t)n_groups * sizeof(EdttsOptimGroup));
-  OptTensor* ht = (OptTensor*)(up + (ls.tensors - ls.groups));
-  OptChunk* hc = (OptChunk*)(up + (ls.chunks - ls.groups));
-  int ti = 0;
-  long long ci = 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    const EdttsOptimTensor& t = tensors[i];
-    if (t.numel == 0) continue;
-    ht[ti] = OptTensor{t.p, t.g, t.m, t.v, t.ema, t.mirror, t.ema_mirror, t.group, t.rows, t.cols, (float)(1.0 - (double)t.ema_decay)};
-    for (long long o = 0; o < t.numel; o += kOptChunk, ++ci) {
-      const long long left = t.numel - o;
-      hc[ci] = OptChunk{o, ti, (int)(left < kOptChunk ? left : kOptChunk)};
-    }
-    ++ti;
-  }
-  HIP_TRY(hipMemcpyAsync(sc + ls.groups, up, up_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(slot.ev, st));
-  slot.pending = true;
-  OptArgs a{(EdttsOptimState*)sc, (OptBias*)(sc + ls.bias), (float*)(sc + ls.partial), (const EdttsOptimGroup*)(sc + ls.groups),
-            (const OptTensor*)(sc + ls.tensors), (const OptChunk*)(sc + ls.chunks), (int)n_chunks, n_groups, flags, (float)max_norm};
-  if (!ema_only) {
-    const int have_norm = (flags & (EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE)) ? 1 : 0;
-    if (have_norm) {
-      hipLaunchKernelGGL(k_opt_sqsum, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
-      LAUNCH_CHECK("k_opt_sqsum");
-    }
-    hipLaunchKernelGGL(k_opt_finish, dim3(1), dim3(kOptThreads), 0, st, a, have_norm);
-    LAUNCH_CHECK("k_opt_finish");
-  }
-  hipLaunchKernelGGL(k_opt_adamw, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
-  LAUNCH_CHECK("k_opt_adamw");
-  return EDTTS_OK;
-}
-
 int edtts_generic_slot_dest(const EdttsDims* dims, int slot, size_t* offset_floats, int* rows, int* cols, int* transposed) {
   Layout lo;
-  TRY(train_layout(dims, "edtts_generic_slot_dest", &lo));
+  TRY_G(train_layout(dims, "edtts_generic_slot_dest", &lo));
   if (!offset_floats || !rows || !cols || !transposed) return fail(EDTTS_ERR_ARG, "edtts_generic_slot_dest: NULL pointer argument");
   if (slot < 0 || slot >= G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "edtts_generic_slot_dest: slot %d of %d", slot, G_COUNT + lo.L * L_COUNT);
   const SlotDest d = generic_slot_dest(lo, slot);

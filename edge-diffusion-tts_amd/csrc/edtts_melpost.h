@@ -1,7 +1,8 @@
 // edtts_melpost.h -- mel post-processing kernels: the step right after the sampler in the
 // reference's scripts (generate_sample.py:115-145, inference_pipeline.py:382-396): denormalize_mel (utils/audio.py:17-19) -> exp
 // -> torchaudio InverseMelScale (minimum-norm least squares = multiplication by the pseudo-inverse of the mel filter bank, relu)
-// -> torchaudio GriffinLim (n_iter x [istft -> stft -> momentum phase update], final istft).  Included by edtts_kernels.hip.
+// -> torchaudio GriffinLim (n_iter x [istft -> stft -> momentum phase update], final istft).  Included by edtts_kernels.hip, behind
+// launch_len_check, which the launchers and the C ABI at the end of this file (edtts_mel_to_spec*, edtts_griffin_lim*) call.
 //
 // Bounds: the inverse-mel product is a small GEMM ([513 x 80] per frame: 82 kFLOP/frame, HBM traffic 320 B in / 2 KB out per
 // frame); Griffin-Lim is FFT-bound: per iteration and frame one 1024-point inverse and one forward complex FFT (2 x 51 kFLOP)
@@ -16,8 +17,6 @@
 // k_mel_to_spec_smooth is k_mel_to_spec for linear-mel input behind a kh x kw box filter (the reference's long-form tail,
 // inference_pipeline.py:376-399: F.avg_pool2d(lin_mel, (5, 3), stride=1, padding=(2, 1)), count_include_pad), the row's own end
 // being the filter's edge.
-#pragma once
-
 namespace melpost {
 using namespace edtts;
 
@@ -238,3 +237,114 @@ __global__ __launch_bounds__(kThreads) void k_gl_trim(const float* __restrict__ 
 }
 
 }  // namespace melpost
+
+// =========================================================================================================
+// launchers and the C ABI
+// =========================================================================================================
+// The index-error word of the mel post-processing *_len entry points: one device uint32 the caller owns (read and cleared by
+// edtts_index_errors, like Workspace::err); rows whose frame count is outside [t_min, T] set EDTTS_IDX_LEN in it.
+static int melpost_len_check(const int64_t* t_len, int B, int T, int t_min, void* idx_err, hipStream_t st) {
+  if (!t_len || !idx_err) return EDTTS_OK;
+  return launch_len_check(t_len, nullptr, B, T, 0, reinterpret_cast<float*>(idx_err), st, t_min);
+}
+
+// Both Griffin-Lim entry points.  t_len == nullptr: every row has T frames, the draws are keyed by (seed, element of the batch).
+static int griffin_lim_run(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
+                           float momentum, float power, const float* angles0, uint64_t seed, const int64_t* t_len, const uint64_t* seeds,
+                           void* idx_err, float* scratch, float* wave_out, void* stream) {
+  if (!spec || !window || !twiddle || !scratch || !wave_out) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if (B < 1 || T < 2 || hop < 1 || hop > n_fft || n_iter < 0 || power <= 0.f) return fail(EDTTS_ERR_ARG, "bad sizes");
+  if (n_fft != melpost::kNfft) return fail(EDTTS_ERR_UNSUPPORTED, "n_fft=%d (compiled: %d, win_length = n_fft)", n_fft, melpost::kNfft);
+  if (hop * (T - 1) <= n_fft / 2) return fail(EDTTS_ERR_ARG, "signal of %d samples is shorter than the reflect padding (torch.stft raises too)", hop * (T - 1));
+  using namespace melpost;
+  hipStream_t st = (hipStream_t)stream;
+  // the shortest row the solo call accepts: hop (T_b - 1) > n_fft / 2; shorter device-side lengths are flagged (and only clamped into [1, T])
+  TRY_G(melpost_len_check(t_len, B, T, (n_fft / 2) / hop + 2, idx_err, st));
+  const size_t bt = (size_t)B * T;
+  const int Lp = n_fft + hop * (T - 1);
+  float* mag = scratch;
+  cplx* ang = reinterpret_cast<cplx*>(mag + bt * kBins);
+  cplx* tprev = ang + bt * kBins;
+  float* frames = reinterpret_cast<float*>(tprev + bt * kBins);
+  float* wave = frames + bt * n_fft;
+  const cplx* tw = reinterpret_cast<const cplx*>(twiddle);
+  const float mom = momentum / (1.0f + momentum);
+  hipLaunchKernelGGL(k_gl_init, dim3(T, B), dim3(kThreads), 0, st, spec, angles0, T, 1.0f / power, (unsigned long long)seed, t_len,
+                     reinterpret_cast<const unsigned long long*>(seeds), mag, ang, tprev);
+  LAUNCH_CHECK("k_gl_init");
+  int gx = (Lp + kThreads - 1) / kThreads;
+  for (int it = 0; it <= n_iter; ++it) {
+    hipLaunchKernelGGL(k_gl_istft, dim3(T, B), dim3(kThreads), 0, st, mag, ang, window, tw, T, t_len, frames);
+    hipLaunchKernelGGL(k_gl_ola, dim3(gx, B), dim3(kThreads), 0, st, frames, window, T, hop, Lp, t_len, wave);
+    if (it < n_iter) hipLaunchKernelGGL(k_gl_stft, dim3(T, B), dim3(kThreads), 0, st, wave, window, tw, T, hop, Lp, mom, t_len, ang, tprev);
+  }
+  LAUNCH_CHECK("griffin-lim kernels");
+  // torch.istft trims the centre padding: n_fft / 2 at the start, and (length = None) as much at the end
+  if (t_len) {
+    hipLaunchKernelGGL(k_gl_trim, dim3((hop * (T - 1) + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, wave, T, hop, Lp, t_len, wave_out);
+    LAUNCH_CHECK("k_gl_trim");
+    return EDTTS_OK;
+  }
+  HIP_TRY(hipMemcpy2DAsync(wave_out, (size_t)hop * (T - 1) * sizeof(float), wave + n_fft / 2, (size_t)Lp * sizeof(float),
+                           (size_t)hop * (T - 1) * sizeof(float), B, hipMemcpyDeviceToDevice, st));
+  return EDTTS_OK;
+}
+
+extern "C" {
+
+int edtts_mel_to_spec(const float* mel_n, const float* mean, const float* stdv, const float* pinv, int B, int T, int n_mels, int n_freqs,
+                      float* spec, void* stream) {
+  return edtts_mel_to_spec_len(mel_n, mean, stdv, pinv, B, T, n_mels, n_freqs, nullptr, 0, 0, nullptr, spec, stream);
+}
+
+int edtts_mel_to_spec_len(const float* mel_n, const float* mean, const float* stdv, const float* pinv, int B, int T, int n_mels, int n_freqs,
+                          const int64_t* t_len, int smooth_h, int smooth_w, void* idx_err, float* spec, void* stream) {
+  if (!mel_n || !pinv || !spec || (!mean != !stdv)) return fail(EDTTS_ERR_ARG, "NULL pointer argument (mean and std come together)");
+  if (B < 1 || T < 1 || n_mels < 1 || n_freqs < 1 || n_mels > 512) return fail(EDTTS_ERR_ARG, "bad sizes");
+  const bool smooth = smooth_h != 0 || smooth_w != 0;
+  if (smooth) {
+    if (smooth_h < 1 || smooth_w < 1 || !(smooth_h & 1) || !(smooth_w & 1) || smooth_h > melpost::kSmoothMax || smooth_w > melpost::kSmoothMax)
+      return fail(EDTTS_ERR_ARG, "smooth %d x %d: the box filter's sides are odd and in [1, %d] (0 x 0: none)", smooth_h, smooth_w,
+                  melpost::kSmoothMax);
+    if (mean) return fail(EDTTS_ERR_ARG, "smoothing takes the linear mel spectrogram (mean and std NULL)");
+    if (n_mels > melpost::kSmoothMaxMels) return fail(EDTTS_ERR_ARG, "smoothing is built for n_mels <= %d, got %d", melpost::kSmoothMaxMels, n_mels);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  TRY_G(melpost_len_check(t_len, B, T, 1, idx_err, st));
+  const dim3 grid((T + 15) / 16, B);
+  if (smooth) {
+    hipLaunchKernelGGL(melpost::k_mel_to_spec_smooth, grid, dim3(melpost::kThreads), (size_t)(32 + smooth_w - 1) * n_mels * sizeof(float), st, mel_n,
+                       pinv, T, n_mels, n_freqs, t_len, smooth_h, smooth_w, spec);
+    LAUNCH_CHECK("k_mel_to_spec_smooth");
+  } else {
+    hipLaunchKernelGGL(melpost::k_mel_to_spec, grid, dim3(melpost::kThreads), 16 * n_mels * sizeof(float), st, mel_n, mean, stdv, pinv, T, n_mels,
+                       n_freqs, t_len, spec);
+    LAUNCH_CHECK("k_mel_to_spec");
+  }
+  return EDTTS_OK;
+}
+
+int edtts_griffin_lim_scratch_floats(int B, int T, int n_fft, int hop, size_t* out_floats) {
+  if (!out_floats || B < 1 || T < 2 || hop < 1) return fail(EDTTS_ERR_ARG, "bad sizes");
+  if (n_fft != melpost::kNfft) return fail(EDTTS_ERR_UNSUPPORTED, "n_fft=%d (compiled: %d)", n_fft, melpost::kNfft);
+  const size_t bt = (size_t)B * T, Lp = (size_t)n_fft + (size_t)hop * (T - 1);
+  *out_floats = bt * melpost::kBins * 5 + bt * n_fft + (size_t)B * Lp;  // mag | angles | tprev | frames | padded signal
+  return EDTTS_OK;
+}
+
+int edtts_griffin_lim(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
+                      float momentum, float power, const float* angles0, uint64_t seed, float* scratch, float* wave_out, void* stream) {
+  return griffin_lim_run(spec, B, T, n_fft, hop, window, twiddle, n_iter, momentum, power, angles0, seed, nullptr, nullptr, nullptr, scratch,
+                         wave_out, stream);
+}
+
+int edtts_griffin_lim_len(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
+                          float momentum, float power, const float* angles0, const int64_t* t_len, const uint64_t* seeds, void* idx_err,
+                          float* scratch, float* wave_out, void* stream) {
+  if (!t_len) return fail(EDTTS_ERR_ARG, "t_len is NULL (edtts_griffin_lim is the call without lengths)");
+  if (!angles0 && !seeds) return fail(EDTTS_ERR_ARG, "seeds is NULL: without angles0, t_len and seeds come together");
+  return griffin_lim_run(spec, B, T, n_fft, hop, window, twiddle, n_iter, momentum, power, angles0, 0, t_len, seeds, idx_err, scratch, wave_out,
+                         stream);
+}
+
+}  // extern "C"

@@ -18,8 +18,6 @@
 //                  x0_mse, x0_cos
 //   k_obj_scale    d_pred = unit * grad_out[0] (grad_out read on the device)
 // No float atomics, no inline assembly, no scratch memory.  Nothing past a row's length is ever loaded.
-#pragma once
-
 namespace edtts_obj {
 
 constexpr int kObjThreads = 256;

@@ -13,9 +13,7 @@
 //   k_opt_adamw    one block per chunk: the update (float4 when every pointer of the tensor is 16-byte aligned, scalar otherwise
 //                  and for the tail), the EMA target, the mirrors (plain or transposed), the zeroing of g.  Nothing when the skip
 //                  flag is up.
-// No float atomics, no inline assembly, no scratch memory.
-#pragma once
-
+// No float atomics, no inline assembly, no scratch memory.  The C ABI (edtts_optim_*) is at the end of this file.
 namespace edtts_opt {
 
 constexpr int kOptChunk = 8192;   // elements per chunk (exported: edtts_optim_chunk_size)
@@ -270,3 +268,130 @@ static OptSlot g_opt_ring[kOptRing];
 static int g_opt_next = 0;
 
 }  // namespace edtts_opt
+
+// =========================================================================================================
+// the C ABI
+// =========================================================================================================
+extern "C" {
+
+int edtts_optim_chunk_size(void) { return edtts_opt::kOptChunk; }
+
+int edtts_optim_chunk_table(const int64_t* numels, int n_tensors, int cap, int32_t* tensor, int64_t* offset, int32_t* count, int* n_chunks) {
+  if (!numels || !n_chunks || n_tensors < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: NULL pointer argument or n_tensors < 0");
+  long long n = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    if (numels[i] < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: numels[%d] = %lld < 0", i, (long long)numels[i]);
+    for (long long o = 0; o < numels[i]; o += edtts_opt::kOptChunk, ++n) {
+      if (n >= cap) continue;  // (counted, not written)
+      if (!tensor || !offset || !count) return fail(EDTTS_ERR_ARG, "edtts_optim_chunk_table: cap > 0 needs the three output arrays");
+      const long long left = numels[i] - o;
+      tensor[n] = i;
+      offset[n] = o;
+      count[n] = (int32_t)(left < edtts_opt::kOptChunk ? left : edtts_opt::kOptChunk);
+    }
+  }
+  if (n > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_chunk_table: %lld chunks", n);
+  *n_chunks = (int)n;
+  return EDTTS_OK;
+}
+
+int edtts_optim_scratch_bytes(int n_chunks, int n_groups, size_t* out_bytes) {
+  if (!out_bytes || n_chunks < 0 || n_groups < 1) return fail(EDTTS_ERR_ARG, "edtts_optim_scratch_bytes: n_chunks=%d n_groups=%d", n_chunks, n_groups);
+  edtts_opt::OptScratch s;
+  edtts_opt::opt_scratch((size_t)n_chunks, (size_t)n_groups, &s);
+  *out_bytes = s.total;
+  return EDTTS_OK;
+}
+
+int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
+                     void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace edtts_opt;
+  if (n_tensors < 0 || n_groups < 1 || (n_tensors && !tensors) || !groups || !scratch)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: NULL pointer argument, n_tensors=%d or n_groups=%d", n_tensors, n_groups);
+  if (flags & ~(EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE | EDTTS_OPT_ZERO_GRADS | EDTTS_OPT_EMA_ONLY))
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: unknown flag bits 0x%x", flags);
+  const bool ema_only = flags & EDTTS_OPT_EMA_ONLY;
+  if (ema_only && (flags & ~EDTTS_OPT_EMA_ONLY)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: EDTTS_OPT_EMA_ONLY excludes the other flags");
+  if ((flags & EDTTS_OPT_CLIP) && !(max_norm >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: max_norm=%g", max_norm);
+  long long n_chunks = 0;
+  int n_live = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const EdttsOptimTensor& t = tensors[i];
+    if (t.numel < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has numel %lld", i, (long long)t.numel);
+    if (t.numel == 0) continue;
+    if (!t.p || (!ema_only && (!t.g || !t.m || !t.v)) || (ema_only && !t.ema))
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a NULL p, g, m, v or (EDTTS_OPT_EMA_ONLY) ema", i);
+    if (((size_t)t.p | (size_t)t.g | (size_t)t.m | (size_t)t.v | (size_t)t.ema | (size_t)t.mirror | (size_t)t.ema_mirror) & 3)
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a pointer that is not 4-byte aligned", i);
+    if (t.group < 0 || t.group >= n_groups) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d names group %d of %d", i, t.group, n_groups);
+    if (t.rows < 0 || t.cols < 0 || (t.rows > 0 && (int64_t)t.rows * t.cols != t.numel))
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: rows=%d cols=%d do not make numel=%lld", i, t.rows, t.cols, (long long)t.numel);
+    if (t.ema_mirror && !t.ema) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has an ema_mirror without an ema", i);
+    if (t.ema && !(t.ema_decay >= 0.f && t.ema_decay <= 1.f)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: ema_decay=%g", i, (double)t.ema_decay);
+    n_chunks += opt_chunks_of(t.numel);
+    ++n_live;
+  }
+  if (n_chunks == 0) return EDTTS_OK;  // nothing to step: as torch, no state changes (the step counter included)
+  if (n_chunks > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_step: %lld chunks", n_chunks);
+  OptScratch ls;
+  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
+  if (ls.total > scratch_bytes)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: %lld chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  char* sc = (char*)scratch;
+  const size_t up_bytes = ls.total - ls.groups;  // groups | tensors | chunks, as they lie in the scratch
+
+  std::lock_guard<std::mutex> lock(g_opt_mu);
+  OptSlot& slot = g_opt_ring[g_opt_next];
+  g_opt_next = (g_opt_next + 1) % kOptRing;
+  if (slot.pending) {
+    HIP_TRY(hipEventSynchronize(slot.ev));  // (returns at once unless kOptRing steps are outstanding)
+    slot.pending = false;
+  }
+  if (slot.cap < up_bytes) {
+    if (slot.host) HIP_TRY(hipHostFree(slot.host));
+    slot.host = nullptr;
+    slot.cap = 0;
+    HIP_TRY(hipHostMalloc(&slot.host, up_bytes + up_bytes / 2, hipHostMallocDefault));
+    slot.cap = up_bytes + up_bytes / 2;
+  }
+  if (slot.ev) (void)hipEventDestroy(slot.ev);  // (an event belongs to the device that was current when it was made: a new one per step)
+  slot.ev = nullptr;
+  HIP_TRY(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+  char* up = (char*)slot.host;
+  memset(up, 0, up_bytes);
+  memcpy(up, groups, (size_t)n_groups * sizeof(EdttsOptimGroup));
+  OptTensor* ht = (OptTensor*)(up + (ls.tensors - ls.groups));
+  OptChunk* hc = (OptChunk*)(up + (ls.chunks - ls.groups));
+  int ti = 0;
+  long long ci = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const EdttsOptimTensor& t = tensors[i];
+    if (t.numel == 0) continue;
+    ht[ti] = OptTensor{t.p, t.g, t.m, t.v, t.ema, t.mirror, t.ema_mirror, t.group, t.rows, t.cols, (float)(1.0 - (double)t.ema_decay)};
+    for (long long o = 0; o < t.numel; o += kOptChunk, ++ci) {
+      const long long left = t.numel - o;
+      hc[ci] = OptChunk{o, ti, (int)(left < kOptChunk ? left : kOptChunk)};
+    }
+    ++ti;
+  }
+  HIP_TRY(hipMemcpyAsync(sc + ls.groups, up, up_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(slot.ev, st));
+  slot.pending = true;
+  OptArgs a{(EdttsOptimState*)sc, (OptBias*)(sc + ls.bias), (float*)(sc + ls.partial), (const EdttsOptimGroup*)(sc + ls.groups),
+            (const OptTensor*)(sc + ls.tensors), (const OptChunk*)(sc + ls.chunks), (int)n_chunks, n_groups, flags, (float)max_norm};
+  if (!ema_only) {
+    const int have_norm = (flags & (EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE)) ? 1 : 0;
+    if (have_norm) {
+      hipLaunchKernelGGL(k_opt_sqsum, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
+      LAUNCH_CHECK("k_opt_sqsum");
+    }
+    hipLaunchKernelGGL(k_opt_finish, dim3(1), dim3(kOptThreads), 0, st, a, have_norm);
+    LAUNCH_CHECK("k_opt_finish");
+  }
+  hipLaunchKernelGGL(k_opt_adamw, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
+  LAUNCH_CHECK("k_opt_adamw");
+  return EDTTS_OK;
+}
+
+}  // extern "C"

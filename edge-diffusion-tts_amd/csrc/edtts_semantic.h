@@ -18,8 +18,6 @@
 //   k_sem_decode   idx -> z_q, one thread per output element (FSQEncoder.decode / VectorQuantizer.decode; ids clamped)
 //   k_sem_stats    counts -> (perplexity, used) in one block, fixed order, fp64 accumulation
 //   k_sem_pack     state-dict matrices -> fragment order (zero-padded to 16 x 16 tiles), vectors padded, |c|^2 per code
-#pragma once
-
 namespace edtts_sem {
 
 constexpr int kFrames = 64;      // frames per block (4 waves x 16)

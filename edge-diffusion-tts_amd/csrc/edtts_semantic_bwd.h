@@ -14,8 +14,6 @@
 //                      for the sums over frames, zero for frames at or past lengths[b].
 //   k_sem_pack_fragT   the transposed matrices in fragment order (the training blob)
 // The sums over frames reuse section 19's kernels (TrainLauncher::dw / colsum, k_bwd_norm_cols): fixed orders, no float atomics.
-#pragma once
-
 namespace edtts_sem {
 
 // Training blob (floats): Wu^T [16][S], Wd^T [S][16], W3^T [S][S], each rt-major in fragment order.
@@ -274,8 +272,6 @@ __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
 // =========================================================================================================
 // launchers and the C ABI
 // =========================================================================================================
-static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on);
-
 // dims -> layouts of a trainable head (FSQ only)
 static int sem_train_dims(const EdttsSemDims* dims, const char* who, edtts_sem::SemLayout& L) {
   TRY_G(edtts_sem::sem_layout(dims, L));

@@ -218,6 +218,44 @@ def test_build_depends_on_every_kernel_source(tmp_path):
     assert G._source_hash() == h0
 
 
+def test_every_kernel_header_is_compiled_exactly_once():
+    """The library is ONE translation unit: edtts_kernels.hip and the headers its #include "..." lines reach.  _sources() hashes every
+    file under csrc/, so a header nothing includes would make the build stamp depend on text that is never compiled; and the units
+    carry no include guard, their order being the file map.  A plain text scan -- which is why no #include "..." may stand behind an
+    #if: the scan (and a reader) would count a header that only some builds compile."""
+    csrc = os.path.join(REPO, "edge-diffusion-tts_amd", "csrc")
+    seen, conditional = [], []
+
+    def walk(path):
+        depth = 0
+        with open(path) as f:
+            lines = f.read().split("\n")
+        for line in lines:
+            d = re.match(r'[ \t]*#[ \t]*(if|ifdef|ifndef|endif|include)\b[ \t]*(?:"([^"]+)")?', line)
+            if not d:
+                continue
+            if d.group(1) == "endif":
+                depth -= 1
+            elif d.group(1) != "include":
+                depth += 1
+            elif d.group(2):
+                target = os.path.normpath(os.path.join(os.path.dirname(path), d.group(2)))
+                assert os.path.exists(target), (path, d.group(2))
+                seen.append(target)
+                if depth:
+                    conditional.append((os.path.basename(path), d.group(2)))
+                if os.path.dirname(target) == csrc and seen.count(target) == 1:
+                    walk(target)
+        assert depth == 0, path
+
+    walk(os.path.join(csrc, "edtts_kernels.hip"))
+    headers = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
+    assert os.path.join(csrc, "edtts_device.h") in headers
+    assert conditional == [], "#include \"...\" lines behind a preprocessor condition"
+    assert [h for h in headers if h not in seen] == [], "headers under csrc/ that edtts_kernels.hip never reaches"
+    assert sorted({h for h in seen if seen.count(h) > 1}) == [], "headers included more than once"
+
+
 def test_no_product_kernel_uses_scratch():
     """The compile's -Rpass-analysis=kernel-resource-usage report (kept next to the library by build()): every kernel of the shipped
     library lives in registers -- a spilling instance is a build error (round 2 shipped one with 76 B/lane)."""
