@@ -171,6 +171,10 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
     }
   }
 }
+// the same product with both operands rounded to bf16 on their way into LDS (edtts_generic16.h)
+template <int EPI, bool DROP = false>
+__global__ __launch_bounds__(256) void k_gen_gemm16(GemmArgs a);
+
 
 // ---- row norms -------------------------------------------------------------------------------------------------------------
 enum { NORM_RMS = 0, NORM_LAYER = 1 };
@@ -482,6 +486,16 @@ struct FwdBufs {
 // =========================================================================================================
 // GenericLauncher: the static interface of Launcher / Launcher16 on the run-time-shape kernels
 // =========================================================================================================
+// The stream of a `linear` site together with the arithmetic of its product: fp32 MFMAs (k_gen_gemm, k_bwd_gemm) or, for a layout
+// with EDTTS_MATMUL_BF16, the bf16 ones of edtts_generic16.h.  The decoder's launch lists build one from their layout and hand it to
+// every gemm / dx / dw; a plain hipStream_t (the semantic head's calls) means fp32.
+struct MmStream {
+  hipStream_t st;
+  bool bf16;
+  MmStream(hipStream_t s, bool b = false) : st(s), bf16(b) {}
+  operator hipStream_t() const { return st; }
+};
+
 struct GenericLauncher {
   static int set_attrs() { return EDTTS_OK; }  // (no kernel here needs more than 64 KiB of LDS)
 
@@ -489,7 +503,7 @@ struct GenericLauncher {
   static unsigned grid_1d(size_t n) { const size_t nb = (n + 255) / 256; return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb)); }
   // dr non-null (EPI_SWIGLU / EPI_RESID): the dropout instantiation, its epilogue masked with *dr
   template <int EPI>
-  static int gemm(hipStream_t st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
+  static int gemm(MmStream st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
                   const float* pe = nullptr, int T = 1, const edtts::DropArgs* dr = nullptr) {
     using namespace edtts_gen;
     GemmArgs a;
@@ -502,12 +516,14 @@ struct GenericLauncher {
     const dim3 grid((M + kGBM - 1) / kGBM, (N + nb - 1) / nb);
     if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
       if (dr) {
-        hipLaunchKernelGGL((k_gen_gemm<EPI, true>), grid, dim3(256), 0, st, a);
+        if (st.bf16) hipLaunchKernelGGL((k_gen_gemm16<EPI, true>), grid, dim3(256), 0, st.st, a);
+        else hipLaunchKernelGGL((k_gen_gemm<EPI, true>), grid, dim3(256), 0, st.st, a);
         LAUNCH_CHECK("k_gen_gemm");
         return EDTTS_OK;
       }
     }
-    hipLaunchKernelGGL(k_gen_gemm<EPI>, grid, dim3(256), 0, st, a);
+    if (st.bf16) hipLaunchKernelGGL(k_gen_gemm16<EPI>, grid, dim3(256), 0, st.st, a);
+    else hipLaunchKernelGGL(k_gen_gemm<EPI>, grid, dim3(256), 0, st.st, a);
     LAUNCH_CHECK("k_gen_gemm");
     return EDTTS_OK;
   }
@@ -555,7 +571,7 @@ struct GenericLauncher {
     const Workspace& ws = cc.ws;
     const float* blob = cc.blob;
     float* wsb = cc.wsb;
-    const hipStream_t st = cc.st;
+    const MmStream st{cc.st, lo.MM16 != 0};
     const int S = cc.S, rows = cc.B * S, H = lo.H, R = lo.R;
     float* c = fb.ctx;
     if (sem_feat) {
@@ -589,7 +605,7 @@ struct GenericLauncher {
     const Workspace& ws = c.ws;
     const float* blob = c.blob;
     float* wsb = c.wsb;
-    const hipStream_t st = c.st;
+    const MmStream st{c.st, lo.MM16 != 0};
     const Lens& ln = c.ln;
     const int B = c.B, T = c.T, S = c.S;
     const int M = B * T, H = lo.H, FH = lo.FM * lo.H, MEL = lo.MEL;

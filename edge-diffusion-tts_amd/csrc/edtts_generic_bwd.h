@@ -175,6 +175,10 @@ __global__ __launch_bounds__(256) void k_bwd_gemm(BGemmArgs a) {
   }
 }
 
+// the same product with both operands rounded to bf16 on their way into LDS (edtts_generic16.h)
+template <int ACC, bool LEN = false>
+__global__ __launch_bounds__(256) void k_bwd_gemm16(BGemmArgs a);
+
 // out[y ostride + j] (+)= sum_{s < ns} part[(y ns + s) pstride + j], s ascending
 __global__ __launch_bounds__(256) void k_bwd_slabsum(const float* part, float* out, size_t n, int ns, size_t pstride, size_t ostride, int acc) {
   const int y = blockIdx.y;
@@ -784,13 +788,19 @@ struct TrainLauncher {
 
   // ---- backward helpers ----
   static bool al16(const void* p) { return G::al16(p); }
-  static int bgemm(hipStream_t st, edtts_bwd::BGemmArgs a, int slabs, bool acc) {
+  static int bgemm(MmStream st, edtts_bwd::BGemmArgs a, int slabs, bool acc) {
     const dim3 grid((a.M + 63) / 64, (a.N + 63) / 64, slabs);
-    if (a.len) {
-      if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<1, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<0, true>), grid, dim3(256), 0, st, a);
-    } else if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<1>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<0>, grid, dim3(256), 0, st, a);
+    if (st.bf16) {
+      if (a.len) {
+        if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<1, true>), grid, dim3(256), 0, st.st, a);
+        else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, true>), grid, dim3(256), 0, st.st, a);
+      } else if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm16<1>, grid, dim3(256), 0, st.st, a);
+      else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm16<0>, grid, dim3(256), 0, st.st, a);
+    } else if (a.len) {
+      if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<1, true>), grid, dim3(256), 0, st.st, a);
+      else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<0, true>), grid, dim3(256), 0, st.st, a);
+    } else if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<1>, grid, dim3(256), 0, st.st, a);
+    else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<0>, grid, dim3(256), 0, st.st, a);
     LAUNCH_CHECK("k_bwd_gemm");
     return EDTTS_OK;
   }
@@ -801,7 +811,7 @@ struct TrainLauncher {
   }
   // dX[M][K] (+)= dY[M][N] W[N][K]   (wT: the blob keeps W transposed, [K][N])
   // (rl: the M rows' lengths -- dead rows of dY are not loaded, dead rows of dX are 0)
-  static int dx(hipStream_t st, const float* dY, long ldy, const float* W, int M, int N, int K, float* dX, int ldx, bool acc, bool wT = false,
+  static int dx(MmStream st, const float* dY, long ldy, const float* W, int M, int N, int K, float* dX, int ldx, bool acc, bool wT = false,
                 RowLens rl = RowLens{}) {
     edtts_bwd::BGemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -816,7 +826,7 @@ struct TrainLauncher {
   }
   // dW[N][K] = dY[M][N]^T X[M][K]: slabs of dw_slab_rows(M) rows, summed in slab order
   // (rl: the M rows' lengths -- dead rows of dY and X are not loaded)
-  static int dw(hipStream_t st, const float* dY, long ldy, const float* X, long ldx, int M, int N, int K, float* dW, float* part,
+  static int dw(MmStream st, const float* dY, long ldy, const float* X, long ldx, int M, int N, int K, float* dW, float* part,
                 RowLens rl = RowLens{}) {
     if (!dW) return EDTTS_OK;
     const int rows = edtts_bwd::dw_slab_rows(M), ns = (M + rows - 1) / rows;
@@ -891,9 +901,10 @@ struct TrainLauncher {
   // gs: gradient destinations in edtts_pack_weights slot order (null: not wanted).
   static int backward(const Layout& lo, const float* blob, const float* tp, const TrainTape& tt, float* sc, const TrainScratch& ss, int B, int T,
                       int S, int window, const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_feat,
-                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t st, const DropState* drop = nullptr,
+                      const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t stream, const DropState* drop = nullptr,
                       const Lens& ln = Lens{}) {
     using namespace edtts_gen;
+    const MmStream st{stream, lo.MM16 != 0};  // every dx / dw / recomputation below follows the layout's matmul_dtype
     // Per-utterance lengths: tr / sr mask every contraction over decoder / context rows and zero the dead
     // rows of every dX; the elementwise steps in between run on all rows (what they make of a dead row is never loaded again).
     const RowLens tr{ln.t, T}, sr{ln.s, S};

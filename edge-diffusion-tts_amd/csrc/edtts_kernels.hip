@@ -105,6 +105,7 @@ struct LayerLayout {
 struct Layout {
   int GEN;   // 1: the generic run-time-shape kernels (edtts_generic.h): plain [N][K] weights, no fragment stream
   int BF16;  // 1: bf16 contractions (edtts_bf16.h): the fragment stream holds bf16 fragments of 16 outputs x 32 inputs
+  int MM16;  // 1 (GEN only, EDTTS_MATMUL_BF16): every `linear` of the generic path on bf16 MFMAs (edtts_generic16.h); same blob
   int H, HEADS, MEL, L, DH, DHP, HT, MT, R, RT, SD, NTOK, MAXPOS, MAXCPOS, NSTEP;
   int FM;  // ffn_mult: the FFN's hidden width is FM * H (layers/transformer.py:32-45: Linear(H, 2 FM H) -> SwiGLU -> Linear(FM H, H))
   size_t tok, semp, semp_b, t1T, t1b, t3T, t3b, step, inp, inp_b, pe, cpe, fnw, fnb, outp_b, freqs;
@@ -161,11 +162,21 @@ static int make_generic_layout(const EdttsDims* d, Layout* lo) {
   return EDTTS_OK;
 }
 
+// EDTTS_MATMUL_BF16 has one legal spelling (include/edtts.h); false: the error text is set
+static bool matmul_bit_ok(const EdttsDims* d) {
+  if (!(d->compute_dtype & EDTTS_MATMUL_BF16) || d->compute_dtype == (EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16)) return true;
+  fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=0x%x: EDTTS_MATMUL_BF16 is legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16",
+       d->compute_dtype);
+  return false;
+}
+
 static int make_layout(const EdttsDims* d, Layout* lo) {
   if (!d) return fail(EDTTS_ERR_ARG, "dims is NULL");
   // kernel-path bits (include/edtts.h): decided here, once; packing, workspace sizing and the dispatch follow lo->GEN
   const int kbits = d->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
-  const int dtype = d->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  const int dtype = d->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO | EDTTS_MATMUL_BF16);
+  const bool mm16 = (d->compute_dtype & EDTTS_MATMUL_BF16) != 0;
+  if (!matmul_bit_ok(d)) return EDTTS_ERR_UNSUPPORTED;
   if (kbits == (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO))
     return fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=0x%x: EDTTS_KERNELS_GENERIC and EDTTS_KERNELS_AUTO are exclusive", d->compute_dtype);
   if (kbits == EDTTS_KERNELS_GENERIC && dtype == EDTTS_BF16)
@@ -179,7 +190,11 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
       probe.H = d->hidden; probe.HEADS = d->heads; probe.MEL = d->n_mels;
       fused = has_instance(probe);
     }
-    if (!fused) return make_generic_layout(d, lo);
+    if (!fused) {
+      const int rc = make_generic_layout(d, lo);
+      if (rc == EDTTS_OK) lo->MM16 = mm16;
+      return rc;
+    }
   }
   // (AUTO with bf16 is the compiled bf16 path: it never falls back to fp32)
   if (d->ffn_mult < 1 || d->ffn_mult > 4) return fail(EDTTS_ERR_UNSUPPORTED, "ffn_mult=%d outside [1, 4]", d->ffn_mult);
@@ -247,10 +262,12 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
 }
 
 // The layout of a call that trains (edtts_generic_bwd.h) or asks where a trainable slot lies: the generic fp32 path only
+// (fp32 storage; EDTTS_MATMUL_BF16 passes through to make_layout, which allows it exactly here)
 static int train_layout(const EdttsDims* dims, const char* who, Layout* lo) {
   if (!dims) return fail(EDTTS_ERR_ARG, "dims is NULL");
+  if (!matmul_bit_ok(dims)) return EDTTS_ERR_UNSUPPORTED;
   const int kbits = dims->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
-  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
+  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO | EDTTS_MATMUL_BF16);
   if (kbits != EDTTS_KERNELS_GENERIC)
     return fail(EDTTS_ERR_UNSUPPORTED, "%s: training runs on the generic kernels only (compute_dtype=0x%x lacks EDTTS_KERNELS_GENERIC)", who,
                 dims->compute_dtype);
@@ -2724,6 +2741,7 @@ static bool has_instance(const Layout& lo) {
   EDTTS_FUSED_CHAIN(lo, return false, return false, return true)
 }
 
+static int launch_cond16(const Layout& lo, const CondArgs& a, int rows, hipStream_t stream);  // edtts_generic16.h
 static int launch_cond(const Layout& lo, const float* blob, const int64_t* t, const int64_t* step_idx, const int64_t* t_host,
                        int rows, float* cond, float* wsb, hipStream_t st) {
   CondArgs a;
@@ -2743,6 +2761,7 @@ static int launch_cond(const Layout& lo, const float* blob, const int64_t* t, co
   a.cond = cond;
   a.err = reinterpret_cast<unsigned*>(wsb);  // Workspace::err = 0
   a.tcond = cond + (size_t)rows * lo.L * 2 * 2 * lo.H;  // scratch right behind the rows (see make_workspace)
+  if (lo.MM16) return launch_cond16(lo, a, rows, st);  // the same rows with their products on bf16 MFMAs
   hipLaunchKernelGGL(k_cond_mlp, dim3(rows), dim3(256), 2 * lo.H * sizeof(float), st, a);
   LAUNCH_CHECK("k_cond_mlp");
   hipLaunchKernelGGL(k_cond_ada, dim3(rows, 2 * lo.L, (2 * lo.H + 255) / 256), dim3(256), lo.H * sizeof(float), st, a);
@@ -2777,6 +2796,7 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
 // the units carry no include guard: a second inclusion is a redefinition error, not a silent no-op.
 #include "edtts_melpost.h"       // mel -> spectrogram, Griffin-Lim (edtts_audio.h uses its FFT)
 #include "edtts_generic_bwd.h"   // training the decoder; drop_state, which edtts_semantic_bwd.h calls
+#include "edtts_generic16.h"     // ... and both on bf16 MFMAs (EDTTS_MATMUL_BF16) <- edtts_generic.h, edtts_generic_bwd.h, edtts_bf16.h
 #include "edtts_semantic.h"      // SemanticEncoder: proj, FSQ / VQ <- edtts_generic.h: DropArgs
 #include "edtts_semantic_bwd.h"  // ... its training <- edtts_generic_bwd.h: k_bwd_*, drop_state
 #include "edtts_hubert.h"        // NativeHubert, fp32 <- edtts_generic.h: k_gen_norm, k_gen_attn

@@ -97,7 +97,7 @@ class _DecoderGrad(torch.autograd.Function):
 
 class EdgeDiffusionDecoder(nn.Module):
     def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled",
-                 autograd: bool = False, train_dropout: bool = False, train_lengths: bool = False):
+                 autograd: bool = False, train_dropout: bool = False, train_lengths: bool = False, matmul_dtype: str = "f32"):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
@@ -120,8 +120,20 @@ class EdgeDiffusionDecoder(nn.Module):
         ``train_lengths``: False (default) -- a differentiable forward given ``x_lengths`` / ``sem_lengths`` raises, as before.  True
         (needs ``autograd=True``) -- that forward takes them (a ragged training batch): eps is bitwise the inference forward's with
         the same lengths (0 past ``x_lengths[b]``), the backward reads nothing past the lengths, padding contributes exactly nothing
-        to any gradient, and ``x_t.grad`` / ``sem_features.grad`` are 0 there.  Composes with ``train_dropout``: DESIGN.md section 22."""
+        to any gradient, and ``x_t.grad`` / ``sem_features.grad`` are 0 there.  Composes with ``train_dropout``: DESIGN.md section 22.
+        ``matmul_dtype``: "f32" (default) or "bf16" (needs ``kernels="generic"``) -- mixed precision on the generic kernels: every
+        contraction the reference writes as a Linear, in the forward, the samplers' eps, the backward's dX and dW and its
+        recomputed SwiGLU pre-activations, rounds both operands to bf16 and runs on bf16 MFMAs with fp32 accumulators.  Storage
+        (which is what ``compute_dtype`` names) stays fp32: parameters, blob, tape, residual stream, norms, biases, softmax and both
+        attentions, every output and gradient.  It rounds strictly less than ``torch.autocast`` does, so no GradScaler is needed.
+        Composes with ``autograd``, ``train_dropout`` and ``train_lengths``: DESIGN.md section 26."""
         super().__init__()
+        if matmul_dtype not in native.MATMUL_DTYPES:
+            raise ValueError(f"matmul_dtype must be one of {sorted(native.MATMUL_DTYPES)}, got {matmul_dtype!r}")
+        if native.MATMUL_DTYPES[matmul_dtype] and kernels != "generic":
+            raise ValueError(f"matmul_dtype={matmul_dtype!r} needs kernels='generic' (the bf16 products are built for the generic "
+                             f"kernels only), got kernels={kernels!r}")
+        self.matmul_dtype = matmul_dtype
         self.autograd = bool(autograd)
         self.train_dropout = bool(train_dropout)
         self.train_lengths = bool(train_lengths)
@@ -241,7 +253,8 @@ class EdgeDiffusionDecoder(nn.Module):
         window = -1 if c.attn_window_size is None else int(c.attn_window_size)
         return native.EdttsDims(c.hidden, c.layers, c.heads, c.n_mels, c.ffn_mult, c.codebook_size, c.semantic_dim, window,
                                 self.max_len, self.max_context_len, self.n_step_emb,
-                                native.COMPUTE_DTYPES[self.compute_dtype] | native.KERNELS[self.kernels])
+                                native.COMPUTE_DTYPES[self.compute_dtype] | native.KERNELS[self.kernels]
+                                | native.MATMUL_DTYPES[self.matmul_dtype])
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         sd = {k: v for k, v in self.named_parameters()}

@@ -96,6 +96,9 @@ COMPUTE_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 # kernel-path bits ORed into EdttsDims.compute_dtype (include/edtts.h: EDTTS_KERNELS_*): "compiled" = the shape's compiled instance
 # only (an unlisted shape is EDTTS_ERR_UNSUPPORTED), "generic" = the run-time-shape fp32 kernels, "auto" = compiled when built
 KERNELS = {"compiled": 0, "generic": 0x100, "auto": 0x200}
+# matmul-precision bit of EdttsDims.compute_dtype (include/edtts.h): every `linear` of the generic path on bf16 MFMAs, storage fp32
+EDTTS_MATMUL_BF16 = 0x400
+MATMUL_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": EDTTS_MATMUL_BF16, "bfloat16": EDTTS_MATMUL_BF16}
 
 
 class EdttsError(RuntimeError):

@@ -88,6 +88,17 @@ enum { EDTTS_F32 = 0, EDTTS_BF16 = 1 };
  * (edtts_substreams_for answers 1). */
 enum { EDTTS_KERNELS_GENERIC = 0x100, EDTTS_KERNELS_AUTO = 0x200 };
 
+/* Matmul-precision bit of EdttsDims.compute_dtype (mixed-precision training and inference on the generic kernels, DESIGN.md section
+ * 26).  Legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16; every other combination that carries it -- with
+ * EDTTS_BF16, without EDTTS_KERNELS_GENERIC, with EDTTS_KERNELS_AUTO whatever it would resolve to -- is EDTTS_ERR_UNSUPPORTED with a
+ * message naming the bit.  With it every contraction the reference writes as a Linear -- in edtts_decoder_forward*, the training
+ * forwards and backwards (dX, dW and the recomputed SwiGLU pre-activations; the _drop and _len forms too) and the samplers' eps --
+ * rounds both operands to bf16 (nearest even) and multiplies on bf16 MFMAs with fp32 accumulators.  Storage does not change:
+ * parameters, the packed blob, the tape, the residual stream, norms, AdaLN, biases and their gradients, softmax and both attentions,
+ * the slab sums and every output stay fp32, and edtts_packed_bytes, edtts_workspace_bytes, edtts_train_tape_bytes,
+ * edtts_train_scratch_bytes and edtts_generic_slot_dest answer as they do without the bit. */
+enum { EDTTS_MATMUL_BF16 = 0x400 };
+
 int edtts_version(void);
 const char* edtts_last_error(void);
 
