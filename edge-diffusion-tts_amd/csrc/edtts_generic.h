@@ -333,6 +333,9 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
       if (d < a.DH) orow[d] = acc[t][r] * inv;
     }
 }
+// the same attention with both contractions on bf16 MFMAs, four query tiles per block (edtts_generic_attn16.h)
+template <int DT, bool DROP = false>
+__global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a);
 
 // ---- context embedding (token ids) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_gen_embed(const int64_t* sem_idx, const float* tok, const float* cpe, float* ctx, int rows, int S,
@@ -540,6 +543,22 @@ struct GenericLauncher {
                   const edtts::DropArgs* dr = nullptr) {
     edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
                           (int)q_dbl, (int)k_dbl, lse, dr ? *dr : edtts::DropArgs{}};
+    if (lo.ATT16) {  // EDTTS_ATTN_BF16: the same arguments, 64 queries per block
+      const dim3 grid16((Tq + 63) / 64, lo.HEADS, B);
+      switch ((lo.DH + 15) / 16) {
+#define EDTTS_GEN_ATTN16(DT)                                                                           \
+  case DT:                                                                                             \
+    if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, true>), grid16, dim3(256), 0, st, a);     \
+    else hipLaunchKernelGGL(edtts_gen::k_gen_attn16<DT>, grid16, dim3(256), 0, st, a);                 \
+    break
+        EDTTS_GEN_ATTN16(1); EDTTS_GEN_ATTN16(2); EDTTS_GEN_ATTN16(3); EDTTS_GEN_ATTN16(4);
+        EDTTS_GEN_ATTN16(5); EDTTS_GEN_ATTN16(6); EDTTS_GEN_ATTN16(7); EDTTS_GEN_ATTN16(8);
+#undef EDTTS_GEN_ATTN16
+        default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
+      }
+      LAUNCH_CHECK("k_gen_attn16");
+      return EDTTS_OK;
+    }
     const dim3 grid((Tq + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
 #define EDTTS_GEN_ATTN(DT)                                                                        \

@@ -606,6 +606,11 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
       }
     }
 }
+// the same two kernels with every contraction on bf16 MFMAs, four query / key tiles per block (edtts_generic_attn16.h)
+template <int DT, bool DROP = false>
+__global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a);
+template <int DT, bool DROP = false>
+__global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a);
 
 // ---- embeddings ----------------------------------------------------------------------------------------------------------------
 // out[row][c] = sum over positions p (ascending) whose index, clamped as the forward clamps it, is row, of src[p][c]: block = row.
@@ -876,6 +881,27 @@ struct TrainLauncher {
     const float sn = 1.0f / sqrtf((float)lo.DH);
     edtts_bwd::AttnBwdArgs a{q, k, v, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
                              1.4426950408889634f / sqrtf((float)lo.DH), sn, dr ? *dr : DropArgs{}, q_len, k_len};
+    if (lo.ATT16) {  // EDTTS_ATTN_BF16: the same arguments, 64 queries / keys per block
+      const dim3 gq16((Tq + 63) / 64, lo.HEADS, B), gk16((Tk + 63) / 64, lo.HEADS, B);
+      switch ((lo.DH + 15) / 16) {
+#define EDTTS_BWD_ATTN16(DT)                                                                        \
+  case DT:                                                                                          \
+    if (dr) {                                                                                       \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, true>), gq16, dim3(256), 0, st, a);        \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, true>), gk16, dim3(256), 0, st, a);       \
+    } else {                                                                                        \
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dq16<DT>, gq16, dim3(256), 0, st, a);                \
+      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dkv16<DT>, gk16, dim3(256), 0, st, a);               \
+    }                                                                                               \
+    break
+        EDTTS_BWD_ATTN16(1); EDTTS_BWD_ATTN16(2); EDTTS_BWD_ATTN16(3); EDTTS_BWD_ATTN16(4);
+        EDTTS_BWD_ATTN16(5); EDTTS_BWD_ATTN16(6); EDTTS_BWD_ATTN16(7); EDTTS_BWD_ATTN16(8);
+#undef EDTTS_BWD_ATTN16
+        default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
+      }
+      LAUNCH_CHECK("k_bwd_attn16");
+      return EDTTS_OK;
+    }
     const dim3 gq((Tq + 15) / 16, lo.HEADS, B), gk((Tk + 15) / 16, lo.HEADS, B);
     switch ((lo.DH + 15) / 16) {
 #define EDTTS_BWD_ATTN(DT)                                                                      \

@@ -106,6 +106,7 @@ struct Layout {
   int GEN;   // 1: the generic run-time-shape kernels (edtts_generic.h): plain [N][K] weights, no fragment stream
   int BF16;  // 1: bf16 contractions (edtts_bf16.h): the fragment stream holds bf16 fragments of 16 outputs x 32 inputs
   int MM16;  // 1 (GEN only, EDTTS_MATMUL_BF16): every `linear` of the generic path on bf16 MFMAs (edtts_generic16.h); same blob
+  int ATT16; // 1 (GEN only, EDTTS_ATTN_BF16): both attention contractions and their backward on bf16 MFMAs (edtts_generic_attn16.h)
   int H, HEADS, MEL, L, DH, DHP, HT, MT, R, RT, SD, NTOK, MAXPOS, MAXCPOS, NSTEP;
   int FM;  // ffn_mult: the FFN's hidden width is FM * H (layers/transformer.py:32-45: Linear(H, 2 FM H) -> SwiGLU -> Linear(FM H, H))
   size_t tok, semp, semp_b, t1T, t1b, t3T, t3b, step, inp, inp_b, pe, cpe, fnw, fnb, outp_b, freqs;
@@ -162,11 +163,20 @@ static int make_generic_layout(const EdttsDims* d, Layout* lo) {
   return EDTTS_OK;
 }
 
-// EDTTS_MATMUL_BF16 has one legal spelling (include/edtts.h); false: the error text is set
+// EDTTS_MATMUL_BF16 and EDTTS_ATTN_BF16 have one legal spelling each, with or without the other (include/edtts.h); false: the error
+// text is set
+constexpr int kMixedBits = EDTTS_MATMUL_BF16 | EDTTS_ATTN_BF16;
 static bool matmul_bit_ok(const EdttsDims* d) {
-  if (!(d->compute_dtype & EDTTS_MATMUL_BF16) || d->compute_dtype == (EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16)) return true;
-  fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=0x%x: EDTTS_MATMUL_BF16 is legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16",
-       d->compute_dtype);
+  const int rest = d->compute_dtype & ~kMixedBits;  // what the two bits ride on
+  if (!(d->compute_dtype & kMixedBits) || rest == (EDTTS_F32 | EDTTS_KERNELS_GENERIC)) return true;
+  if (d->compute_dtype & EDTTS_ATTN_BF16)
+    fail(EDTTS_ERR_UNSUPPORTED,
+         "compute_dtype=0x%x: EDTTS_ATTN_BF16 is legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_ATTN_BF16, with or without "
+         "EDTTS_MATMUL_BF16",
+         d->compute_dtype);
+  else
+    fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=0x%x: EDTTS_MATMUL_BF16 is legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16",
+         d->compute_dtype);
   return false;
 }
 
@@ -174,8 +184,8 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
   if (!d) return fail(EDTTS_ERR_ARG, "dims is NULL");
   // kernel-path bits (include/edtts.h): decided here, once; packing, workspace sizing and the dispatch follow lo->GEN
   const int kbits = d->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
-  const int dtype = d->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO | EDTTS_MATMUL_BF16);
-  const bool mm16 = (d->compute_dtype & EDTTS_MATMUL_BF16) != 0;
+  const int dtype = d->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO | kMixedBits);
+  const bool mm16 = (d->compute_dtype & EDTTS_MATMUL_BF16) != 0, att16 = (d->compute_dtype & EDTTS_ATTN_BF16) != 0;
   if (!matmul_bit_ok(d)) return EDTTS_ERR_UNSUPPORTED;
   if (kbits == (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO))
     return fail(EDTTS_ERR_UNSUPPORTED, "compute_dtype=0x%x: EDTTS_KERNELS_GENERIC and EDTTS_KERNELS_AUTO are exclusive", d->compute_dtype);
@@ -192,7 +202,10 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
     }
     if (!fused) {
       const int rc = make_generic_layout(d, lo);
-      if (rc == EDTTS_OK) lo->MM16 = mm16;
+      if (rc == EDTTS_OK) {
+        lo->MM16 = mm16;
+        lo->ATT16 = att16;
+      }
       return rc;
     }
   }
@@ -262,12 +275,12 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
 }
 
 // The layout of a call that trains (edtts_generic_bwd.h) or asks where a trainable slot lies: the generic fp32 path only
-// (fp32 storage; EDTTS_MATMUL_BF16 passes through to make_layout, which allows it exactly here)
+// (fp32 storage; EDTTS_MATMUL_BF16 and EDTTS_ATTN_BF16 pass through to make_layout, which allows them exactly here)
 static int train_layout(const EdttsDims* dims, const char* who, Layout* lo) {
   if (!dims) return fail(EDTTS_ERR_ARG, "dims is NULL");
   if (!matmul_bit_ok(dims)) return EDTTS_ERR_UNSUPPORTED;
   const int kbits = dims->compute_dtype & (EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO);
-  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO | EDTTS_MATMUL_BF16);
+  const int dtype = dims->compute_dtype & ~(EDTTS_KERNELS_GENERIC | EDTTS_KERNELS_AUTO | kMixedBits);
   if (kbits != EDTTS_KERNELS_GENERIC)
     return fail(EDTTS_ERR_UNSUPPORTED, "%s: training runs on the generic kernels only (compute_dtype=0x%x lacks EDTTS_KERNELS_GENERIC)", who,
                 dims->compute_dtype);
@@ -2797,6 +2810,7 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
 #include "edtts_melpost.h"       // mel -> spectrogram, Griffin-Lim (edtts_audio.h uses its FFT)
 #include "edtts_generic_bwd.h"   // training the decoder; drop_state, which edtts_semantic_bwd.h calls
 #include "edtts_generic16.h"     // ... and both on bf16 MFMAs (EDTTS_MATMUL_BF16) <- edtts_generic.h, edtts_generic_bwd.h, edtts_bf16.h
+#include "edtts_generic_attn16.h"  // ... their attention on bf16 MFMAs (EDTTS_ATTN_BF16) <- edtts_generic.h, edtts_generic_bwd.h, edtts_bf16.h
 #include "edtts_semantic.h"      // SemanticEncoder: proj, FSQ / VQ <- edtts_generic.h: DropArgs
 #include "edtts_semantic_bwd.h"  // ... its training <- edtts_generic_bwd.h: k_bwd_*, drop_state
 #include "edtts_hubert.h"        // NativeHubert, fp32 <- edtts_generic.h: k_gen_norm, k_gen_attn

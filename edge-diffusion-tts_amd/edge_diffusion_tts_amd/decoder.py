@@ -97,7 +97,8 @@ class _DecoderGrad(torch.autograd.Function):
 
 class EdgeDiffusionDecoder(nn.Module):
     def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled",
-                 autograd: bool = False, train_dropout: bool = False, train_lengths: bool = False, matmul_dtype: str = "f32"):
+                 autograd: bool = False, train_dropout: bool = False, train_lengths: bool = False, matmul_dtype: str = "f32",
+                 attn_dtype: str = "f32"):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
@@ -126,8 +127,19 @@ class EdgeDiffusionDecoder(nn.Module):
         recomputed SwiGLU pre-activations, rounds both operands to bf16 and runs on bf16 MFMAs with fp32 accumulators.  Storage
         (which is what ``compute_dtype`` names) stays fp32: parameters, blob, tape, residual stream, norms, biases, softmax and both
         attentions, every output and gradient.  It rounds strictly less than ``torch.autocast`` does, so no GradScaler is needed.
-        Composes with ``autograd``, ``train_dropout`` and ``train_lengths``: DESIGN.md section 26."""
+        Composes with ``autograd``, ``train_dropout`` and ``train_lengths``: DESIGN.md section 26.
+        ``attn_dtype``: "f32" (default) or "bf16" (needs ``kernels="generic"``) -- the other half of mixed precision, independent of
+        ``matmul_dtype``: both attentions of every block, forward and backward, run their contractions (q k^T, p v, dO v^T, and the
+        products that make dQ, dK and dV) on bf16 MFMAs with fp32 accumulators, as ``torch.autocast`` runs them.  Only the operands
+        of those products are rounded; the scale, mask, softmax statistics, log-sum-exp, delta and every stored tensor stay fp32, and
+        the dropout masks are the same.  Composes with everything ``matmul_dtype`` composes with: DESIGN.md section 27."""
         super().__init__()
+        if attn_dtype not in native.ATTN_DTYPES:
+            raise ValueError(f"attn_dtype must be one of {sorted(native.ATTN_DTYPES)}, got {attn_dtype!r}")
+        if native.ATTN_DTYPES[attn_dtype] and kernels != "generic":
+            raise ValueError(f"attn_dtype={attn_dtype!r} needs kernels='generic' (the bf16 attention kernels are built for the generic "
+                             f"kernels only), got kernels={kernels!r}")
+        self.attn_dtype = attn_dtype
         if matmul_dtype not in native.MATMUL_DTYPES:
             raise ValueError(f"matmul_dtype must be one of {sorted(native.MATMUL_DTYPES)}, got {matmul_dtype!r}")
         if native.MATMUL_DTYPES[matmul_dtype] and kernels != "generic":
@@ -254,7 +266,7 @@ class EdgeDiffusionDecoder(nn.Module):
         return native.EdttsDims(c.hidden, c.layers, c.heads, c.n_mels, c.ffn_mult, c.codebook_size, c.semantic_dim, window,
                                 self.max_len, self.max_context_len, self.n_step_emb,
                                 native.COMPUTE_DTYPES[self.compute_dtype] | native.KERNELS[self.kernels]
-                                | native.MATMUL_DTYPES[self.matmul_dtype])
+                                | native.MATMUL_DTYPES[self.matmul_dtype] | native.ATTN_DTYPES[self.attn_dtype])
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         sd = {k: v for k, v in self.named_parameters()}

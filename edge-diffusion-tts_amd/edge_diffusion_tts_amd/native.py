@@ -99,6 +99,9 @@ KERNELS = {"compiled": 0, "generic": 0x100, "auto": 0x200}
 # matmul-precision bit of EdttsDims.compute_dtype (include/edtts.h): every `linear` of the generic path on bf16 MFMAs, storage fp32
 EDTTS_MATMUL_BF16 = 0x400
 MATMUL_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": EDTTS_MATMUL_BF16, "bfloat16": EDTTS_MATMUL_BF16}
+# attention-precision bit (include/edtts.h): both attentions' contractions, forward and backward, on bf16 MFMAs, storage fp32
+EDTTS_ATTN_BF16 = 0x800
+ATTN_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": EDTTS_ATTN_BF16, "bfloat16": EDTTS_ATTN_BF16}
 
 
 class EdttsError(RuntimeError):

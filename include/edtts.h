@@ -99,6 +99,23 @@ enum { EDTTS_KERNELS_GENERIC = 0x100, EDTTS_KERNELS_AUTO = 0x200 };
  * edtts_train_scratch_bytes and edtts_generic_slot_dest answer as they do without the bit. */
 enum { EDTTS_MATMUL_BF16 = 0x400 };
 
+/* Attention-precision bit of EdttsDims.compute_dtype (the other half of mixed precision on the generic kernels).
+ * Legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_ATTN_BF16, with or without EDTTS_MATMUL_BF16; every other combination that
+ * carries it -- with EDTTS_BF16, without EDTTS_KERNELS_GENERIC, with EDTTS_KERNELS_AUTO whatever it would resolve to -- is
+ * EDTTS_ERR_UNSUPPORTED with a message naming the bit.  With it both attentions of every block, in every forward, training forward,
+ * backward (the _drop and _len forms too) and sampler entry point, run their contractions on bf16 MFMAs with fp32 accumulators.
+ * Rounding contract (nearest even, operands only, nothing is stored as bf16):
+ *   forward   S = bf16(q) bf16(k)^T, then * log2(e) / sqrt(head_dim) in fp32 (the operands are the stored values, not pre-scaled
+ *             ones); mask, running maximum, exp2, the row sum l and the log-sum-exp in fp32 from the unrounded probabilities;
+ *             O = bf16(P~) bf16(v) / l, P~ the unnormalised probability (times keep * scale first under dropout)
+ *   backward  delta = rowsum(dO o O) in fp32, unrounded; dP = bf16(dO) bf16(v)^T; P recomputed in fp32 from the recomputed S and the
+ *             tape's log-sum-exp; dV = bf16(P o D)^T bf16(dO); dS = P o (D o dP - delta) in fp32; dQ = bf16(dS) bf16(k) / sqrt(head_dim);
+ *             dK = bf16(dS)^T bf16(q) / sqrt(head_dim); all accumulators and stores fp32
+ * Storage does not change: q | k | v, both attention outputs, the cross K | V rows and the log-sum-exps stay fp32 in the same layout,
+ * the dropout masks (edtts_dropout_mask) do not depend on the bit, and edtts_packed_bytes, edtts_workspace_bytes,
+ * edtts_train_tape_bytes, edtts_train_scratch_bytes and edtts_generic_slot_dest answer as they do without it. */
+enum { EDTTS_ATTN_BF16 = 0x800 };
+
 int edtts_version(void);
 const char* edtts_last_error(void);
 
