@@ -171,8 +171,9 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
     }
   }
 }
-// the same product with both operands rounded to bf16 on their way into LDS (edtts_generic16.h)
-template <int EPI, bool DROP = false>
+// the same product with both operands rounded to bf16 on their way into LDS (edtts_generic16.h); TX / TY = __bf16: X holds / Y gets
+// bf16 elements (Layout::TAPE16) -- GemmArgs' pointers then name buffers of __bf16, ldx / ldy still count elements
+template <int EPI, bool DROP = false, typename TX = float, typename TY = float>
 __global__ __launch_bounds__(256) void k_gen_gemm16(GemmArgs a);
 
 
@@ -334,7 +335,8 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
     }
 }
 // the same attention with both contractions on bf16 MFMAs, four query tiles per block (edtts_generic_attn16.h)
-template <int DT, bool DROP = false>
+// (TQ = __bf16: q, k and v hold bf16 elements, Layout::TAPE16; AttnArgs' pointers name the buffers, ldq / ldkv count elements)
+template <int DT, bool DROP = false, typename TQ = float>
 __global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a);
 
 // ---- context embedding (token ids) ---------------------------------------------------------------------------------------------
@@ -459,11 +461,24 @@ struct DropState {
 
 // Where one forward's intermediates go.  Inference reuses a few workspace buffers for all of them; the training forward
 // (edtts_generic_bwd.h) points them into its tape and also asks for the snapshots and the log-sum-exps.
+// An activation buffer together with its element type: fp32, or -- the four buffers that Layout::TAPE16 narrows (EDTTS_TAPE_BF16,
+// DESIGN.md section 28) -- bf16.  `+` and every ld / pitch that goes with it count ELEMENTS, so the launch lists read the same for
+// both; gemm / attn / attn_bwd / dw pick the instantiation from `h`.  A plain float pointer converts to an fp32 one.
+struct Act {
+  const float* p;  // the buffer (h: its bytes hold __bf16)
+  bool h;
+  Act(const float* q = nullptr, bool half = false) : p(q), h(half) {}
+  Act operator+(size_t n) const { return h ? Act(reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(p) + n), true) : Act(p + n); }
+  float* w() const { return const_cast<float*>(p); }  // (as an output: every Act a launch list writes was made from a float*)
+};
 struct FwdLayerBufs {
-  float *crp, *crn, *kv;     // kv_down rows [B S][R] before / after kv_norm; K|V rows [B S][2H]
-  float *qkv, *att1, *lse1;  // self-attention: q|k|v rows, attention output, log-sum-exp [B][HEADS][T] or null
-  float *qc, *att2, *lse2;   // cross-attention: query rows, attention output, log-sum-exp or null
-  float* act;                // value * silu(gate) [B T][FM H]
+  float *crp, *crn;          // kv_down rows [B S][R] before / after kv_norm
+  Act kv;                    // K|V rows [B S][2H]
+  Act qkv;                   // self-attention: q|k|v rows
+  float *att1, *lse1;        // ... attention output, log-sum-exp [B][HEADS][T] or null
+  Act qc;                    // cross-attention: query rows
+  float *att2, *lse2;        // ... attention output, log-sum-exp or null
+  Act act;                   // value * silu(gate) [B T][FM H]
   float *h0, *h1, *h2;       // or null: copies of the residual stream entering norm1 / norm2 / norm3
 };
 struct FwdBufs {
@@ -472,14 +487,15 @@ struct FwdBufs {
   float* hL;   // or null: a copy of the residual stream entering final_norm
   FwdBufs() = default;
   // the workspace's buffers: kv_norm in place, one buffer for q|k|v, the cross queries and the SwiGLU output, one for both
-  // attention outputs; no snapshot, no log-sum-exp
+  // attention outputs; no snapshot, no log-sum-exp  (TAPE16: the same offsets, of which the bf16 rows fill the first half)
   explicit FwdBufs(const CallCtx& c) : ctx(c.wsb + c.ws.g_ctx), hL(nullptr) {
+    const bool t16 = c.lo.TAPE16 != 0;
     float *cr = c.wsb + c.ws.g_cr, *big = c.wsb + c.ws.g_big, *att = c.wsb + c.ws.g_att;
     for (int l = 0; l < c.lo.L; ++l) {
       FwdLayerBufs& z = layer[l];
       z.crp = z.crn = cr;
-      z.kv = c.wsb + c.ws.g_kv + (size_t)l * c.B * c.S * 2 * c.lo.H;
-      z.qkv = z.qc = z.act = big;
+      z.kv = Act(c.wsb + c.ws.g_kv + (size_t)l * c.B * c.S * 2 * c.lo.H, t16);
+      z.qkv = z.qc = z.act = Act(big, t16);
       z.att1 = z.att2 = att;
       z.lse1 = z.lse2 = z.h0 = z.h1 = z.h2 = nullptr;
     }
@@ -505,18 +521,46 @@ struct GenericLauncher {
   static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
   static unsigned grid_1d(size_t n) { const size_t nb = (n + 255) / 256; return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb)); }
   // dr non-null (EPI_SWIGLU / EPI_RESID): the dropout instantiation, its epilogue masked with *dr
+  // X.h / Y.h (Layout::TAPE16): the bf16-load / bf16-store instantiation of k_gen_gemm16 -- there is one for exactly the sites that
+  // the narrowed buffers have (Y of EPI_BIAS and EPI_SWIGLU, X of EPI_RESID); anything else is an error, never a conversion
   template <int EPI>
-  static int gemm(MmStream st, const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
+  static int gemm(MmStream st, Act X, int ldx, const float* W, const float* bias, Act Y, int ldy, int M, int N, int K,
                   const float* pe = nullptr, int T = 1, const edtts::DropArgs* dr = nullptr) {
     using namespace edtts_gen;
     GemmArgs a;
-    a.X = X; a.W = W; a.bias = bias; a.Y = Y; a.pe = pe; a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldy = ldy; a.T = T;
-    a.vec_x = (K % 4 == 0) && (ldx % 4 == 0) && al16(X);
+    a.X = X.p; a.W = W; a.bias = bias; a.Y = Y.w(); a.pe = pe; a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldy = ldy; a.T = T;
+    // 16-byte loads: four fp32 or eight bf16; stores of four columns: 16 bytes of fp32 or 8 bytes of bf16
+    a.vec_x = X.h ? (K % 8 == 0) && (ldx % 8 == 0) && al16(X.p) : (K % 4 == 0) && (ldx % 4 == 0) && al16(X.p);
     a.vec_w = (K % 4 == 0) && al16(W);
-    a.vec_y = (ldy % 4 == 0) && al16(Y);
+    a.vec_y = Y.h ? (ldy % 4 == 0) && ((uintptr_t)Y.p & 7) == 0 : (ldy % 4 == 0) && al16(Y.p);
     const int nb = EPI == EPI_SWIGLU ? kGBN / 2 : kGBN;
     a.dr = dr ? *dr : edtts::DropArgs{};
     const dim3 grid((M + kGBM - 1) / kGBM, (N + nb - 1) / nb);
+    if (X.h || Y.h) {
+      if (!st.bf16) return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: a bf16 activation buffer needs the bf16 products (EDTTS_MATMUL_BF16)");
+      if constexpr (EPI == EPI_BIAS) {
+        if (!X.h && Y.h) {
+          hipLaunchKernelGGL((k_gen_gemm16<EPI_BIAS, false, float, __bf16>), grid, dim3(256), 0, st.st, a);
+          LAUNCH_CHECK("k_gen_gemm16");
+          return EDTTS_OK;
+        }
+      } else if constexpr (EPI == EPI_SWIGLU) {
+        if (!X.h && Y.h) {
+          if (dr) hipLaunchKernelGGL((k_gen_gemm16<EPI_SWIGLU, true, float, __bf16>), grid, dim3(256), 0, st.st, a);
+          else hipLaunchKernelGGL((k_gen_gemm16<EPI_SWIGLU, false, float, __bf16>), grid, dim3(256), 0, st.st, a);
+          LAUNCH_CHECK("k_gen_gemm16");
+          return EDTTS_OK;
+        }
+      } else if constexpr (EPI == EPI_RESID) {
+        if (X.h && !Y.h) {
+          if (dr) hipLaunchKernelGGL((k_gen_gemm16<EPI_RESID, true, __bf16, float>), grid, dim3(256), 0, st.st, a);
+          else hipLaunchKernelGGL((k_gen_gemm16<EPI_RESID, false, __bf16, float>), grid, dim3(256), 0, st.st, a);
+          LAUNCH_CHECK("k_gen_gemm16");
+          return EDTTS_OK;
+        }
+      }
+      return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: no product with epilogue %d reads bf16=%d and stores bf16=%d", EPI, (int)X.h, (int)Y.h);
+    }
     if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
       if (dr) {
         if (st.bf16) hipLaunchKernelGGL((k_gen_gemm16<EPI, true>), grid, dim3(256), 0, st.st, a);
@@ -538,18 +582,24 @@ struct GenericLauncher {
     LAUNCH_CHECK("k_gen_norm");
     return EDTTS_OK;
   }
-  static int attn(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, float* o,
+  // (q, k, v of one element type: fp32, or bf16 with Layout::TAPE16, which only the bf16 attention reads)
+  static int attn(hipStream_t st, const Layout& lo, int B, Act q, int ldq, Act k, Act v, int ldkv, float* o,
                   int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl, float* lse = nullptr,
                   const edtts::DropArgs* dr = nullptr) {
-    edtts_gen::AttnArgs a{q, k, v, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
+    if (q.h != k.h || q.h != v.h || (q.h && !lo.ATT16))
+      return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: bf16 q, k, v rows need the bf16 attention (EDTTS_ATTN_BF16), all three of them");
+    edtts_gen::AttnArgs a{q.p, k.p, v.p, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
                           (int)q_dbl, (int)k_dbl, lse, dr ? *dr : edtts::DropArgs{}};
     if (lo.ATT16) {  // EDTTS_ATTN_BF16: the same arguments, 64 queries per block
       const dim3 grid16((Tq + 63) / 64, lo.HEADS, B);
       switch ((lo.DH + 15) / 16) {
-#define EDTTS_GEN_ATTN16(DT)                                                                           \
-  case DT:                                                                                             \
-    if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, true>), grid16, dim3(256), 0, st, a);     \
-    else hipLaunchKernelGGL(edtts_gen::k_gen_attn16<DT>, grid16, dim3(256), 0, st, a);                 \
+#define EDTTS_GEN_ATTN16(DT)                                                                                          \
+  case DT:                                                                                                            \
+    if (q.h) {                                                                                                        \
+      if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, true, __bf16>), grid16, dim3(256), 0, st, a);           \
+      else hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, false, __bf16>), grid16, dim3(256), 0, st, a);             \
+    } else if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, true>), grid16, dim3(256), 0, st, a);              \
+    else hipLaunchKernelGGL(edtts_gen::k_gen_attn16<DT>, grid16, dim3(256), 0, st, a);                                \
     break
         EDTTS_GEN_ATTN16(1); EDTTS_GEN_ATTN16(2); EDTTS_GEN_ATTN16(3); EDTTS_GEN_ATTN16(4);
         EDTTS_GEN_ATTN16(5); EDTTS_GEN_ATTN16(6); EDTTS_GEN_ATTN16(7); EDTTS_GEN_ATTN16(8);
@@ -641,7 +691,7 @@ struct GenericLauncher {
       // self-attention branch
       TRY_G(snap(z.h0));
       TRY_G(norm<NORM_RMS>(st, h, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cond_bstride));
-      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, z.qkv, 3 * H, M, 3 * H, H));
+      TRY_G(gemm<EPI_BIAS>(st, xn, H, blob + y.s_qkv, nullptr, z.qkv, 3 * H, M, 3 * H, H));  // (z.qkv, z.qc, z.kv, z.act: fp32 or bf16 rows)
       TRY_G(attn(st, lo, B, z.qkv, 3 * H, z.qkv + H, z.qkv + 2 * H, 3 * H, z.att1, T, T, c.window, ln.t, ln.t, ln.t_dbl, ln.t_dbl, z.lse1,
                  D(DROP_ATTN)));
       TRY_G(gemm<EPI_RESID>(st, z.att1, H, blob + y.g_proj, blob + y.proj_b, h, H, M, H, H));

@@ -4,10 +4,15 @@
 //
 // What is rounded: the two operands of a product, fp32 in global memory, to bf16 (round to nearest even, v_cvt_pk_bf16_f32) in
 // registers on their way into LDS.  Products on v_mfma_f32_16x16x32_bf16, accumulators fp32, epilogues and stores those of the fp32
-// kernels (gemm_epilogue / bgemm_store restate them).  Nothing is stored as bf16 in global memory.
+// kernels (gemm_epilogue / bgemm_store restate them).  Nothing is stored as bf16 in global memory -- unless the decoder also carries
+// EDTTS_TAPE_BF16 (Layout::TAPE16): the four activation buffers that only these loaders and the attention's read
+// (q|k|v, the cross queries, the cross K|V, the SwiGLU output) then hold bf16(x), which is the operand the loaders form from x.  The
+// kernels take the element type of such an operand as a template parameter that defaults to float: an instantiation with float is
+// the kernel of before, statement for statement.  TX = __bf16 loads X without converting; TY = __bf16 rounds the epilogue's four
+// columns with the loaders' conversion and stores them as 8 bytes (or 2-byte elements where the pitch or the edge forbids it).
 //
-//   k_gen_gemm16<EPI, DROP>  k_gen_gemm's product: same GemmArgs, grid, 64 x 64 block tile and wave tiles, K tiles of 32
-//   k_bwd_gemm16<ACC, LEN>   k_bwd_gemm's product: same BGemmArgs, grid and slabs, run-time strides on both operands
+//   k_gen_gemm16<EPI, DROP, TX, TY>  k_gen_gemm's product: same GemmArgs, grid, 64 x 64 block tile and wave tiles, K tiles of 32
+//   k_bwd_gemm16<ACC, LEN, TB>       k_bwd_gemm's product: same BGemmArgs, grid and slabs, run-time strides on both operands
 //   launch_cond16            the conditioning rows (time MLP, AdaLN projections) as k_bwd_gemm16 products
 //
 // LDS: two buffers of [X | W][64 rows][32 k] bf16; lane (fq, g) reads k = 8g .. 8g + 7 of row fq as one ds_read_b128 (the operand
@@ -59,6 +64,26 @@ EDTTS_DEV bf8 load8_row(const float* p, int k, int kend, bool ok, int vec) {
   }
   return edtts16::pack8(lo, hi);
 }
+// Elements that are bf16 already.  A 2-byte load goes into a register of its own and the eight are paired afterwards, as the fp32
+// loaders convert afterwards: inserting each into a packed vector as it arrives makes every load wait for the one before it (measured:
+// dW_down 245 -> 672 us per step at B = 64 x 512).
+EDTTS_DEV unsigned ld_bf16(const __bf16* p, bool ok) { return ok ? (unsigned)*reinterpret_cast<const unsigned short*>(p) : 0u; }
+EDTTS_DEV bf8 pair8(const unsigned (&e)[8]) {
+  typedef unsigned u4v __attribute__((ext_vector_type(4)));
+  return __builtin_bit_cast(bf8, u4v{e[0] | e[1] << 16, e[2] | e[3] << 16, e[4] | e[5] << 16, e[6] | e[7] << 16});
+}
+// ... of a row that holds bf16 already (vec: kend % 8 == 0 and 16-byte aligned rows, so the eight lie wholly inside or outside)
+EDTTS_DEV bf8 load8_row(const __bf16* p, int k, int kend, bool ok, int vec) {
+  if (vec) {
+    bf8 v = edtts16::as_bf8(splat(0.f));
+    if (ok && k < kend) v = *reinterpret_cast<const bf8*>(p + k);
+    return v;
+  }
+  unsigned e[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) e[r] = ld_bf16(p + k + r, ok && k + r < kend);
+  return pair8(e);
+}
 // ... of a row whose k has stride sk; bit i of live: k + i is loaded
 EDTTS_DEV bf8 gather8(const float* p, long sk, int k, int kend, bool ok, unsigned live) {
   f4 lo, hi;
@@ -68,6 +93,35 @@ EDTTS_DEV bf8 gather8(const float* p, long sk, int k, int kend, bool ok, unsigne
     hi[r] = (ok && k + 4 + r < kend && (live >> (r + 4) & 1u)) ? p[(size_t)(k + 4 + r) * sk] : 0.f;
   }
   return edtts16::pack8(lo, hi);
+}
+EDTTS_DEV bf8 gather8(const __bf16* p, long sk, int k, int kend, bool ok, unsigned live) {
+  unsigned e[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) e[r] = ld_bf16(p + (size_t)(k + r) * sk, ok && k + r < kend && (live >> r & 1u));
+  return pair8(e);
+}
+// four consecutive n of an output row: fp32 as they are; bf16 rounded as the loaders round (pack4 is pack8's conversion), one 8-byte
+// store where `full` (8-byte aligned, all four inside N), else the first `left` of them as 2-byte elements
+EDTTS_DEV void store_row4(float* yp, f4 o, bool full, int left) {
+  if (full) {
+    stg4(yp, o);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < left) yp[r] = o[r];
+  }
+}
+EDTTS_DEV void store_row4(__bf16* yp, f4 o, bool full, int left) {
+  typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+  const edtts16::f2s pk = edtts16::pack4(o);
+  if (full) {
+    *reinterpret_cast<edtts16::f2s*>(yp) = pk;
+  } else {
+    const bf4 b = __builtin_bit_cast(bf4, pk);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < left) yp[r] = b[r];
+  }
 }
 // one K tile of the block's 64 x 64 product from LDS buffer [X | W][64][kG16Ld]: the wave tiles of k_gen_gemm
 EDTTS_DEV void mfma_tile16(const __bf16 (*t)[kGBM][kG16Ld], f4 (&acc)[2][2], int wm, int wn0, int wn1, int fq, int g) {
@@ -81,7 +135,8 @@ EDTTS_DEV void mfma_tile16(const __bf16 (*t)[kGBM][kG16Ld], f4 (&acc)[2][2], int
 
 // k_gen_gemm's epilogue, statement for statement (that kernel keeps its own copy so that its code does not move): the accumulators
 // have its layout -- acc[t][u] lane (g, fq) holds Y[m = m0 + wm + 16u + fq][n = 4g + r of weight sub-tile t] (LDS rows wn0 / wn1)
-template <int EPI, bool DROP>
+// (TY = __bf16: the stores go through store_row4; the float instantiation keeps its statements)
+template <int EPI, bool DROP, typename TY = float>
 EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, int n0, int wm, int wn0, int wn1, int fq, int g) {
   if (EPI == EPI_SWIGLU) {
     const int n = n0 + wn0 + 4 * g;
@@ -101,6 +156,10 @@ EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, i
         const f4 dm = drop_row4(a.dr, m, n);
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] *= dm[r];
+      }
+      if constexpr (sizeof(TY) == 2) {
+        store_row4(reinterpret_cast<__bf16*>(a.Y) + (size_t)m * a.ldy + n, o, a.vec_y && n + 3 < a.N, a.N - n);
+        continue;
       }
       float* yp = a.Y + (size_t)m * a.ldy + n;
       if (a.vec_y && n + 3 < a.N) {
@@ -138,6 +197,11 @@ EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, i
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] *= dm[r];
       }
+      if constexpr (sizeof(TY) == 2) {
+        static_assert((EPI == EPI_BIAS && !DROP) || EPI == EPI_SWIGLU /* (returned above) */, "bf16 stores: the q|k|v, cross query, K|V and SwiGLU rows only");
+        store_row4(reinterpret_cast<__bf16*>(a.Y) + (size_t)m * a.ldy + n, o, full, a.N - n);
+        continue;
+      }
       if (EPI == EPI_RESID) {  // h = h + (x W^T + b): the reference's residual order
         if (full) {
           stg4(yp, ldg4(yp) + o);
@@ -157,7 +221,7 @@ EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, i
   }
 }
 
-template <int EPI, bool DROP>
+template <int EPI, bool DROP, typename TX, typename TY>
 __global__ __launch_bounds__(256) void k_gen_gemm16(GemmArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 lds[2][2][kGBM][kG16Ld];  // [buffer][X | W][row][k]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fq = lane & 15, g = lane >> 4;
@@ -177,7 +241,7 @@ __global__ __launch_bounds__(256) void k_gen_gemm16(GemmArgs a) {
   }
   const int xrow = m0 + lr;
   const bool xok = xrow < a.M;
-  const float* xp = a.X + (size_t)(xok ? xrow : 0) * a.ldx;
+  const TX* xp = reinterpret_cast<const TX*>(a.X) + (size_t)(xok ? xrow : 0) * a.ldx;  // (GemmArgs names the buffer; TX its elements)
   const float* wp = a.W + (size_t)(wok ? wrow : 0) * a.K;
   const int wn0 = EPI == EPI_SWIGLU ? 16 * (w & 1) : 32 * (w & 1);
   const int wn1 = EPI == EPI_SWIGLU ? wn0 + 32 : wn0 + 16;
@@ -206,7 +270,7 @@ __global__ __launch_bounds__(256) void k_gen_gemm16(GemmArgs a) {
     if (more) store(buf ^ 1);  // (read last by the previous tile's MFMAs, which every wave left at the barrier below)
     __syncthreads();
   }
-  gemm_epilogue<EPI, DROP>(a, acc, m0, n0, wm, wn0, wn1, fq, g);
+  gemm_epilogue<EPI, DROP, TY>(a, acc, m0, n0, wm, wn0, wn1, fq, g);
 }
 
 }  // namespace edtts_gen
@@ -238,7 +302,7 @@ EDTTS_DEV void bgemm_store(const BGemmArgs& a, const f4 (&acc)[2][2], int m0, in
   }
 }
 
-template <int ACC, bool LEN>
+template <int ACC, bool LEN, typename TB>
 __global__ __launch_bounds__(256) void k_bwd_gemm16(BGemmArgs a) {
   using namespace edtts_gen;
   __shared__ __attribute__((aligned(16))) __bf16 lds[2][2][kGBM][kG16Ld];  // [buffer][A | B][row][k]: A in X's place, B in W's
@@ -257,7 +321,7 @@ __global__ __launch_bounds__(256) void k_bwd_gemm16(BGemmArgs a) {
     aok = aok && row_live(a.len, a.rpb, m0 + alr);
   }
   const float* ap = a.A + (size_t)(aok ? m0 + alr : 0) * a.sam;
-  const float* bp = a.B + (size_t)(bok ? n0 + blr : 0) * a.sbn;
+  const TB* bp = reinterpret_cast<const TB*>(a.B) + (size_t)(bok ? n0 + blr : 0) * a.sbn;  // (TB = __bf16: dW_down's X^T, the tape's act)
   const int wn0 = 32 * (w & 1), wn1 = wn0 + 16, wm = 32 * (w >> 1);
   f4 acc[2][2];
 #pragma unroll

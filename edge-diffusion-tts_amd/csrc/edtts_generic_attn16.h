@@ -1,11 +1,14 @@
 // edtts_generic_attn16.h -- the generic path's attention, forward and backward, on bf16 MFMAs (included by edtts_kernels.hip after
 // edtts_generic.h, edtts_generic_bwd.h, edtts_bf16.h and edtts_generic16.h).  Selected per decoder with
 // EDTTS_ATTN_BF16 (Layout::ATT16): GenericLauncher::attn and TrainLauncher::attn_bwd pick these kernels or the fp32 ones, the launch
-// lists stay single.  AttnArgs / AttnBwdArgs are the fp32 kernels'; nothing is stored as bf16 in global memory.
+// lists stay single.  AttnArgs / AttnBwdArgs are the fp32 kernels'; nothing is stored as bf16 in global memory by these kernels.
+// With EDTTS_TAPE_BF16 (Layout::TAPE16) q, k and v ARRIVE as bf16: TQ = __bf16, the loaders of those three copy
+// instead of converting (bf16(bf16(x)) = bf16(x): the operand is the one formed from fp32 rows, bit for bit); dO, the log-sum-exp,
+// delta and every store stay fp32, and LDS images, the walk, barriers, dropout counters and MFMAs are the same statements.
 //
-//   k_gen_attn16<DT, DROP>      k_gen_attn's attention: a block = four waves = 64 adjacent queries of one (utterance, head)
-//   k_bwd_attn_dq16<DT, DROP>   k_bwd_attn_dq's dQ: the same block
-//   k_bwd_attn_dkv16<DT, DROP>  k_bwd_attn_dkv's dK / dV: a block = 64 adjacent keys
+//   k_gen_attn16<DT, DROP, TQ>      k_gen_attn's attention: a block = four waves = 64 adjacent queries of one (utterance, head)
+//   k_bwd_attn_dq16<DT, DROP, TQ>   k_bwd_attn_dq's dQ: the same block
+//   k_bwd_attn_dkv16<DT, DROP, TQ>  k_bwd_attn_dkv's dK / dV: a block = 64 adjacent keys
 //
 // Rounding contract (include/edtts.h, EDTTS_ATTN_BF16): only MFMA operands are rounded (nearest even, v_cvt_pk_bf16_f32).
 //   S = bf16(q) bf16(k)^T, * log2(e) / sqrt(d) in fp32 -- the operands are the stored values, so all three kernels form the same S up to
@@ -96,8 +99,27 @@ EDTTS_DEV bf8 a16_row(const float* base, int ld, int row, int rend, int d0, int 
   const bool ok = row < rend;
   return load8_row(base + (size_t)(ok ? row : 0) * ld, d0, DH, ok, vec);
 }
+// The same two loaders for q, k, v rows that hold bf16 already (TQ = __bf16, Layout::TAPE16): the stored value IS the operand, so
+// nothing is converted.  vec: ld % 8 == 0, head_dim % 8 == 0 and a 16-byte aligned base -- one 16-byte load of eight elements.
+EDTTS_DEV bf8 a16_gather(const __bf16* base, int ld, int r0, int rend, int d, int DH, int gs) {
+  unsigned e[8];  // (each load into a register of its own, paired afterwards: ld_bf16 / pair8, edtts_generic16.h)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int ra = r0 + 4 * gs + r, rb = ra + 16;
+    e[r] = ld_bf16(base + (size_t)ra * ld + d, d < DH && ra < rend);
+    e[4 + r] = ld_bf16(base + (size_t)rb * ld + d, d < DH && rb < rend);
+  }
+  return pair8(e);
+}
+EDTTS_DEV bf8 a16_row(const __bf16* base, int ld, int row, int rend, int d0, int DH, int vec) {
+  const bool ok = row < rend;
+  return load8_row(base + (size_t)(ok ? row : 0) * ld, d0, DH, ok, vec);
+}
+// ld | head_dim must be a multiple of this + 1 for the 16-byte loads of a row of T
+template <typename T>
+constexpr int a16_vm() { return sizeof(T) == 2 ? 7 : 3; }
 
-template <int DT, bool DROP>
+template <int DT, bool DROP, typename TQ>
 __global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a) {
   constexpr int KS = A16<DT>::KS, RP = A16<DT>::RP, NI = A16<DT>::NI;
   __shared__ __attribute__((aligned(16))) __bf16 Ks[32][RP];          // K rows of the step
@@ -109,8 +131,8 @@ __global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a) {
   if (Q0 >= Tqb) return;  // (the whole block: no barrier is left waiting)
   const int q0 = Q0 + 16 * w, qi = q0 + fq;
   const bool wlive = q0 < Tqb;  // wave-uniform
-  const int vq = ((a.ldq | a.DH) & 3) == 0 && a16_al(a.q), vkv = ((a.ldkv | a.DH) & 3) == 0 && a16_al(a.k) && a16_al(a.v);
-  const float* qrow = a.q + (size_t)(b * a.Tq + (qi < Tqb ? qi : 0)) * a.ldq + hd * a.DH;
+  const int vq = ((a.ldq | a.DH) & a16_vm<TQ>()) == 0 && a16_al(a.q), vkv = ((a.ldkv | a.DH) & a16_vm<TQ>()) == 0 && a16_al(a.k) && a16_al(a.v);
+  const TQ* qrow = reinterpret_cast<const TQ*>(a.q) + (size_t)(b * a.Tq + (qi < Tqb ? qi : 0)) * a.ldq + hd * a.DH;
   bf8 qb[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) qb[ks] = load8_row(qrow, 32 * ks + 8 * g, a.DH, qi < Tqb, vq);
@@ -124,8 +146,8 @@ __global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a) {
     const int e = Q0 + kA16Q + a.window;
     hi = e < Tk ? e : Tk;
   }
-  const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
-  const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const TQ* kb = reinterpret_cast<const TQ*>(a.k) + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const TQ* vb = reinterpret_cast<const TQ*>(a.v) + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
   bf8 st[KS];  // this thread's items of the next step: [0, NI) K row-major, [NI, 2 NI) V^T
   auto load = [&](int j0) {
 #pragma unroll
@@ -237,13 +259,14 @@ using edtts_gen::a16_gather;
 using edtts_gen::a16_rm;
 using edtts_gen::a16_row;
 using edtts_gen::a16_tr;
+using edtts_gen::a16_vm;
 using edtts_gen::kA16Q;
 using edtts_gen::kA16TP;
 using edtts_gen::load8_row;
 
 // The block of k_gen_attn16: S^T = K Q^T and dP^T = V dO^T tiles hold (key 16t + 4g + r, query fq) on lane (g, fq); the packed dS^T
 // is the B operand of dQ^T += K^T dS^T.  Staged per step: K and V row-major, K^T in slot order.
-template <int DT, bool DROP>
+template <int DT, bool DROP, typename TQ>
 __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a) {
   constexpr int KS = A16<DT>::KS, RP = A16<DT>::RP, NI = A16<DT>::NI, NIT = (3 * NI + 255) / 256;
   __shared__ __attribute__((aligned(16))) __bf16 Ks[32][RP];
@@ -263,10 +286,10 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a) {
     return;
   }
   const bool wlive = q0 < Tqb, qok = qi < Tqb;
-  const int vq = ((a.ldq | a.DH) & 3) == 0 && a16_al(a.q), vo = ((a.ldo | a.DH) & 3) == 0 && a16_al(a.dO);
-  const int vkv = ((a.ldkv | a.DH) & 3) == 0 && a16_al(a.k) && a16_al(a.v);
+  const int vq = ((a.ldq | a.DH) & a16_vm<TQ>()) == 0 && a16_al(a.q), vo = ((a.ldo | a.DH) & 3) == 0 && a16_al(a.dO);
+  const int vkv = ((a.ldkv | a.DH) & a16_vm<TQ>()) == 0 && a16_al(a.k) && a16_al(a.v);
   const size_t qr = (size_t)b * a.Tq + (qok ? qi : 0);
-  const float* qrow = a.q + qr * a.ldq + hd * a.DH;
+  const TQ* qrow = reinterpret_cast<const TQ*>(a.q) + qr * a.ldq + hd * a.DH;
   const float* drow = a.dO + qr * a.ldo + hd * a.DH;
   bf8 qb[KS], dob[KS];
 #pragma unroll
@@ -285,8 +308,8 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a) {
     const int e = Q0 + kA16Q + a.window;
     hi = e < Tkb ? e : Tkb;
   }
-  const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
-  const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const TQ* kb = reinterpret_cast<const TQ*>(a.k) + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const TQ* vb = reinterpret_cast<const TQ*>(a.v) + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
   bf8 st[NIT];  // items [0, NI) K, [NI, 2 NI) V, [2 NI, 3 NI) K^T
   auto load = [&](int j0) {
 #pragma unroll
@@ -369,7 +392,7 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a) {
 // A block = 64 adjacent keys of one (utterance, head), a wave = 16 of them.  S = Q K^T and dP = dO V^T tiles hold (query 16t + 4g + r,
 // key fq) on lane (g, fq); the packed P o D and dS are the B operands of dV^T += dO^T (P o D) and dK^T += Q^T dS.  Staged per step of 32
 // queries: Q and dO row-major, Q^T and dO^T in slot order, and the queries' log-sum-exp and delta.
-template <int DT, bool DROP>
+template <int DT, bool DROP, typename TQ>
 __global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a) {
   constexpr int KS = A16<DT>::KS, RP = A16<DT>::RP, NI = A16<DT>::NI, NIT = 2 * KS;  // 4 NI items over 256 threads
   __shared__ __attribute__((aligned(16))) __bf16 Qs[32][RP];
@@ -392,11 +415,11 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a) {
     return;
   }
   const bool wlive = k0 < Tkb, kok = kj < Tkb;
-  const int vq = ((a.ldq | a.DH) & 3) == 0 && a16_al(a.q), vo = ((a.ldo | a.DH) & 3) == 0 && a16_al(a.dO);
-  const int vkv = ((a.ldkv | a.DH) & 3) == 0 && a16_al(a.k) && a16_al(a.v);
+  const int vq = ((a.ldq | a.DH) & a16_vm<TQ>()) == 0 && a16_al(a.q), vo = ((a.ldo | a.DH) & 3) == 0 && a16_al(a.dO);
+  const int vkv = ((a.ldkv | a.DH) & a16_vm<TQ>()) == 0 && a16_al(a.k) && a16_al(a.v);
   const size_t kr = (size_t)b * a.Tk + (kok ? kj : 0);
-  const float* krow = a.k + kr * a.ldkv + hd * a.DH;
-  const float* vrow = a.v + kr * a.ldkv + hd * a.DH;
+  const TQ* krow = reinterpret_cast<const TQ*>(a.k) + kr * a.ldkv + hd * a.DH;
+  const TQ* vrow = reinterpret_cast<const TQ*>(a.v) + kr * a.ldkv + hd * a.DH;
   bf8 kb[KS], vb[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -412,7 +435,7 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a) {
     const int e = K0 + kA16Q + a.window;
     hi = e < Tqb ? e : Tqb;
   }
-  const float* qb = a.q + (size_t)b * a.Tq * a.ldq + hd * a.DH;
+  const TQ* qb = reinterpret_cast<const TQ*>(a.q) + (size_t)b * a.Tq * a.ldq + hd * a.DH;
   const float* db = a.dO + (size_t)b * a.Tq * a.ldo + hd * a.DH;
   const float* lb = a.lse + ((size_t)b * gridDim.y + hd) * a.Tq;
   const float* eb = a.delta + ((size_t)b * gridDim.y + hd) * a.Tq;

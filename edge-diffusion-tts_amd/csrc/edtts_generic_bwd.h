@@ -176,7 +176,8 @@ __global__ __launch_bounds__(256) void k_bwd_gemm(BGemmArgs a) {
 }
 
 // the same product with both operands rounded to bf16 on their way into LDS (edtts_generic16.h)
-template <int ACC, bool LEN = false>
+// (TB = __bf16: B holds bf16 elements, Layout::TAPE16 -- dW_down's X is the tape's SwiGLU output; sbn / sbk count elements)
+template <int ACC, bool LEN = false, typename TB = float>
 __global__ __launch_bounds__(256) void k_bwd_gemm16(BGemmArgs a);
 
 // out[y ostride + j] (+)= sum_{s < ns} part[(y ns + s) pstride + j], s ascending
@@ -607,9 +608,10 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
     }
 }
 // the same two kernels with every contraction on bf16 MFMAs, four query / key tiles per block (edtts_generic_attn16.h)
-template <int DT, bool DROP = false>
+// (TQ = __bf16: q, k and v hold bf16 elements, Layout::TAPE16; dO, the log-sum-exp, delta and every gradient stay fp32)
+template <int DT, bool DROP = false, typename TQ = float>
 __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a);
-template <int DT, bool DROP = false>
+template <int DT, bool DROP = false, typename TQ = float>
 __global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a);
 
 // ---- embeddings ----------------------------------------------------------------------------------------------------------------
@@ -689,6 +691,8 @@ __global__ __launch_bounds__(256) void k_bwd_gelu_grad(float* du, const float* a
 // =========================================================================================================
 // the tape and the backward's scratch (offsets in floats)
 // =========================================================================================================
+// Layout::TAPE16 (EDTTS_TAPE_BF16): kv, qkv, qc and act hold __bf16 -- n elements take (n + 1) / 2 floats of the
+// tape; their offsets still count floats (every region starts on a multiple of 64 floats = 256 bytes), their pitches elements.
 struct TapeLayer {
   size_t crp, kv;             // kv_down rows before kv_norm [B S][R]; K|V rows [B S][2H]
   size_t h0, h1, h2;          // the residual stream entering norm1 / norm2 / norm3
@@ -707,15 +711,16 @@ static void make_tape(const Layout& lo, int B, int T, int S, TrainTape* t) {
   const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S, FH = (size_t)lo.FM * H;
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
+  auto take16 = [&](size_t n) { return take(lo.TAPE16 ? (n + 1) / 2 : n); };  // a region the bit narrows: n elements
   t->cond = take((size_t)B * lo.L * 4 * H + (size_t)B * H);
   t->ctx = take(CS * H);
   for (int l = 0; l < lo.L; ++l) {
     TapeLayer& y = t->layer[l];
-    y.crp = take(CS * lo.R); y.kv = take(CS * 2 * H);
+    y.crp = take(CS * lo.R); y.kv = take16(CS * 2 * H);
     y.h0 = take(M * H); y.h1 = take(M * H); y.h2 = take(M * H);
-    y.qkv = take(M * 3 * H); y.att1 = take(M * H); y.lse1 = take(M * lo.HEADS);
-    y.qc = take(M * H); y.att2 = take(M * H); y.lse2 = take(M * lo.HEADS);
-    y.act = take(M * FH);
+    y.qkv = take16(M * 3 * H); y.att1 = take(M * H); y.lse1 = take(M * lo.HEADS);
+    y.qc = take16(M * H); y.att2 = take(M * H); y.lse2 = take(M * lo.HEADS);
+    y.act = take16(M * FH);
   }
   t->hL = take(M * H);
   t->total = o;
@@ -776,13 +781,14 @@ struct TrainLauncher {
     FwdBufs fb;
     fb.ctx = tp + tt.ctx;
     fb.hL = tp + tt.hL;
+    const bool t16 = c.lo.TAPE16 != 0;
     for (int l = 0; l < c.lo.L; ++l) {
       const TapeLayer& z = tt.layer[l];
       FwdLayerBufs& f = fb.layer[l];
-      f.crp = tp + z.crp; f.crn = c.wsb + c.ws.g_cr; f.kv = tp + z.kv;
-      f.qkv = tp + z.qkv; f.att1 = tp + z.att1; f.lse1 = tp + z.lse1;
-      f.qc = tp + z.qc; f.att2 = tp + z.att2; f.lse2 = tp + z.lse2;
-      f.act = tp + z.act;
+      f.crp = tp + z.crp; f.crn = c.wsb + c.ws.g_cr; f.kv = Act(tp + z.kv, t16);
+      f.qkv = Act(tp + z.qkv, t16); f.att1 = tp + z.att1; f.lse1 = tp + z.lse1;
+      f.qc = Act(tp + z.qc, t16); f.att2 = tp + z.att2; f.lse2 = tp + z.lse2;
+      f.act = Act(tp + z.act, t16);
       f.h0 = tp + z.h0; f.h1 = tp + z.h1; f.h2 = tp + z.h2;
     }
     StepTail tail;
@@ -793,9 +799,14 @@ struct TrainLauncher {
 
   // ---- backward helpers ----
   static bool al16(const void* p) { return G::al16(p); }
-  static int bgemm(MmStream st, edtts_bwd::BGemmArgs a, int slabs, bool acc) {
+  // (b16: B holds bf16 elements -- dW_down's X with Layout::TAPE16, the one such call)
+  static int bgemm(MmStream st, edtts_bwd::BGemmArgs a, int slabs, bool acc, bool b16 = false) {
     const dim3 grid((a.M + 63) / 64, (a.N + 63) / 64, slabs);
-    if (st.bf16) {
+    if (b16) {
+      if (!st.bf16 || acc) return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: a bf16 operand needs the bf16 products, not accumulating");
+      if (a.len) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, true, __bf16>), grid, dim3(256), 0, st.st, a);
+      else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, false, __bf16>), grid, dim3(256), 0, st.st, a);
+    } else if (st.bf16) {
       if (a.len) {
         if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<1, true>), grid, dim3(256), 0, st.st, a);
         else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, true>), grid, dim3(256), 0, st.st, a);
@@ -831,18 +842,19 @@ struct TrainLauncher {
   }
   // dW[N][K] = dY[M][N]^T X[M][K]: slabs of dw_slab_rows(M) rows, summed in slab order
   // (rl: the M rows' lengths -- dead rows of dY and X are not loaded)
-  static int dw(MmStream st, const float* dY, long ldy, const float* X, long ldx, int M, int N, int K, float* dW, float* part,
+  // (X: fp32 rows, or the tape's bf16 SwiGLU output)
+  static int dw(MmStream st, const float* dY, long ldy, Act X, long ldx, int M, int N, int K, float* dW, float* part,
                 RowLens rl = RowLens{}) {
     if (!dW) return EDTTS_OK;
     const int rows = edtts_bwd::dw_slab_rows(M), ns = (M + rows - 1) / rows;
     edtts_bwd::BGemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.A = dY; a.B = X; a.C = ns == 1 ? dW : part; a.M = N; a.N = K; a.K = M;
+    a.A = dY; a.B = X.p; a.C = ns == 1 ? dW : part; a.M = N; a.N = K; a.K = M;
     a.sam = 1; a.sak = ldy; a.sbn = 1; a.sbk = ldx;
     a.ldc = K; a.kslab = rows; a.cslab = (size_t)N * K;
     a.vc = (K % 4 == 0) && al16(a.C);
     a.len = rl.len; a.rpb = rl.rpb; a.lmode = edtts_bwd::LEN_K;
-    TRY_G(bgemm(st, a, ns, false));
+    TRY_G(bgemm(st, a, ns, false, X.h));
     if (ns > 1) TRY_G(slabsum(st, part, dW, (size_t)N * K, ns, (size_t)N * K));
     return EDTTS_OK;
   }
@@ -872,21 +884,30 @@ struct TrainLauncher {
     return EDTTS_OK;
   }
   // gradients of one attention call: dq, dk, dv from q, k, v, the output o, its gradient dO and the tape's log-sum-exp
-  static int attn_bwd(hipStream_t st, const Layout& lo, int B, const float* q, int ldq, const float* k, const float* v, int ldkv, const float* o,
+  // (q, k, v of one element type, as GenericLauncher::attn)
+  static int attn_bwd(hipStream_t st, const Layout& lo, int B, Act q, int ldq, Act k, Act v, int ldkv, const float* o,
                       const float* dO, const float* lse, float* delta, float* dq, int lddq, float* dk, float* dv, int lddkv, int Tq, int Tk,
                       int window, const DropArgs* dr = nullptr, const int64_t* q_len = nullptr, const int64_t* k_len = nullptr) {
+    if (q.h != k.h || q.h != v.h || (q.h && !lo.ATT16))
+      return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: bf16 q, k, v rows need the bf16 attention (EDTTS_ATTN_BF16), all three of them");
     const size_t n = (size_t)B * lo.HEADS * Tq;
     hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, lo.HEADS, lo.DH, lo.H, q_len);
     LAUNCH_CHECK("k_bwd_attn_delta");
     const float sn = 1.0f / sqrtf((float)lo.DH);
-    edtts_bwd::AttnBwdArgs a{q, k, v, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
+    edtts_bwd::AttnBwdArgs a{q.p, k.p, v.p, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
                              1.4426950408889634f / sqrtf((float)lo.DH), sn, dr ? *dr : DropArgs{}, q_len, k_len};
     if (lo.ATT16) {  // EDTTS_ATTN_BF16: the same arguments, 64 queries / keys per block
       const dim3 gq16((Tq + 63) / 64, lo.HEADS, B), gk16((Tk + 63) / 64, lo.HEADS, B);
       switch ((lo.DH + 15) / 16) {
 #define EDTTS_BWD_ATTN16(DT)                                                                        \
   case DT:                                                                                          \
-    if (dr) {                                                                                       \
+    if (q.h && dr) {                                                                                \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, true, __bf16>), gq16, dim3(256), 0, st, a);  \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, true, __bf16>), gk16, dim3(256), 0, st, a); \
+    } else if (q.h) {                                                                               \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, false, __bf16>), gq16, dim3(256), 0, st, a);  \
+      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, false, __bf16>), gk16, dim3(256), 0, st, a); \
+    } else if (dr) {                                                                                \
       hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, true>), gq16, dim3(256), 0, st, a);        \
       hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, true>), gk16, dim3(256), 0, st, a);       \
     } else {                                                                                        \
@@ -934,6 +955,7 @@ struct TrainLauncher {
     // Per-utterance lengths: tr / sr mask every contraction over decoder / context rows and zero the dead
     // rows of every dX; the elementwise steps in between run on all rows (what they make of a dead row is never loaded again).
     const RowLens tr{ln.t, T}, sr{ln.s, S};
+    auto T16 = [&](size_t off) { return Act(tp + off, lo.TAPE16 != 0); };  // one of the tape's four narrowed regions (make_tape)
     const int M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL, L = lo.L;
     float *dh = sc + ss.dh, *xn = sc + ss.xn, *ga = sc + ss.ga, *gq = sc + ss.gq, *big = sc + ss.big, *da = sc + ss.da;
     float *stat = sc + ss.stat, *delta = sc + ss.delta, *dkv = sc + ss.dkv, *crn = sc + ss.crn, *dcr = sc + ss.dcr, *dcp = sc + ss.dcp;
@@ -967,7 +989,7 @@ struct TrainLauncher {
         dd = gq;
       }
       TRY_G(colsum(st, dd, H, M, H, W(L_DOWN_B), part, tr));
-      TRY_G(dw(st, dd, H, tp + z.act, FH, M, H, FH, W(L_DOWN_W), part, tr));
+      TRY_G(dw(st, dd, H, T16(z.act), FH, M, H, FH, W(L_DOWN_W), part, tr));
       TRY_G(dx(st, dd, H, blob + y.g_down, M, H, FH, da, FH, false, false, tr));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h2, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cb));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_up, blob + y.up_b, big, 2 * FH, M, 2 * FH, H));
@@ -985,7 +1007,7 @@ struct TrainLauncher {
       // cross-attention branch: h2 = h1 + att2 Wop^T
       TRY_G(dw(st, dh, H, tp + z.att2, H, M, H, H, W(L_OP_W), part, tr));
       TRY_G(dx(st, dh, H, blob + y.g_op, M, H, H, ga, H, false, false, tr));
-      TRY_G(attn_bwd(st, lo, B, tp + z.qc, H, tp + z.kv, tp + z.kv + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
+      TRY_G(attn_bwd(st, lo, B, T16(z.qc), H, T16(z.kv), T16(z.kv) + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
                      S, -1, D(DROP_CROSS), ln.t, ln.s));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h1, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
       TRY_G(dw(st, gq, H, xn, H, M, H, H, W(L_QP_W), part, tr));
@@ -1003,7 +1025,7 @@ struct TrainLauncher {
       TRY_G(colsum(st, dh, H, M, H, W(L_PROJ_B), part, tr));
       TRY_G(dw(st, dh, H, tp + z.att1, H, M, H, H, W(L_PROJ_W), part, tr));
       TRY_G(dx(st, dh, H, blob + y.g_proj, M, H, H, ga, H, false, false, tr));
-      const float* qkv = tp + z.qkv;
+      const Act qkv = T16(z.qkv);
       TRY_G(attn_bwd(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, ga, tp + z.lse1, delta, big, 3 * H, big + H, big + 2 * H,
                      3 * H, T, T, window, D(DROP_ATTN), ln.t, ln.t));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h0, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cb));
@@ -1112,6 +1134,40 @@ int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* o
   TrainTape tt;
   make_tape(lo, B, T, S, &tt);
   *out_bytes = tt.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_train_tape_region(const EdttsDims* dims, int B, int T, int S, int layer, int which, size_t* offset_bytes, size_t* bytes,
+                            int* elem_bytes) {
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_train_tape_region", &lo));
+  if (!offset_bytes || !bytes || !elem_bytes) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  TRY_G(check_shapes(lo, B, T, S));
+  if (layer < 0 || layer >= lo.L) return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: layer %d outside [0, %d)", layer, lo.L);
+  TrainTape tt;
+  make_tape(lo, B, T, S, &tt);
+  const TapeLayer& z = tt.layer[layer];
+  const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S;
+  size_t off, n;
+  bool narrow = false;
+  switch (which) {
+    case EDTTS_TAPE_CRP: off = z.crp; n = CS * lo.R; break;
+    case EDTTS_TAPE_KV: off = z.kv; n = CS * 2 * H; narrow = true; break;
+    case EDTTS_TAPE_H0: off = z.h0; n = M * H; break;
+    case EDTTS_TAPE_H1: off = z.h1; n = M * H; break;
+    case EDTTS_TAPE_H2: off = z.h2; n = M * H; break;
+    case EDTTS_TAPE_QKV: off = z.qkv; n = M * 3 * H; narrow = true; break;
+    case EDTTS_TAPE_ATT1: off = z.att1; n = M * H; break;
+    case EDTTS_TAPE_LSE1: off = z.lse1; n = M * lo.HEADS; break;
+    case EDTTS_TAPE_QC: off = z.qc; n = M * H; narrow = true; break;
+    case EDTTS_TAPE_ATT2: off = z.att2; n = M * H; break;
+    case EDTTS_TAPE_LSE2: off = z.lse2; n = M * lo.HEADS; break;
+    case EDTTS_TAPE_ACT: off = z.act; n = M * lo.FM * H; narrow = true; break;
+    default: return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: which=%d is not one of EDTTS_TAPE_CRP .. EDTTS_TAPE_ACT", which);
+  }
+  *elem_bytes = narrow && lo.TAPE16 ? 2 : 4;
+  *offset_bytes = off * sizeof(float);
+  *bytes = n * (size_t)*elem_bytes;
   return EDTTS_OK;
 }
 

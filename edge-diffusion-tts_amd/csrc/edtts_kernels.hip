@@ -107,6 +107,7 @@ struct Layout {
   int BF16;  // 1: bf16 contractions (edtts_bf16.h): the fragment stream holds bf16 fragments of 16 outputs x 32 inputs
   int MM16;  // 1 (GEN only, EDTTS_MATMUL_BF16): every `linear` of the generic path on bf16 MFMAs (edtts_generic16.h); same blob
   int ATT16; // 1 (GEN only, EDTTS_ATTN_BF16): both attention contractions and their backward on bf16 MFMAs (edtts_generic_attn16.h)
+  int TAPE16;  // 1 (MM16 and ATT16 only, EDTTS_TAPE_BF16): q|k|v, the cross queries, the cross K|V and the SwiGLU output are stored as bf16
   int H, HEADS, MEL, L, DH, DHP, HT, MT, R, RT, SD, NTOK, MAXPOS, MAXCPOS, NSTEP;
   int FM;  // ffn_mult: the FFN's hidden width is FM * H (layers/transformer.py:32-45: Linear(H, 2 FM H) -> SwiGLU -> Linear(FM H, H))
   size_t tok, semp, semp_b, t1T, t1b, t3T, t3b, step, inp, inp_b, pe, cpe, fnw, fnb, outp_b, freqs;
@@ -163,11 +164,18 @@ static int make_generic_layout(const EdttsDims* d, Layout* lo) {
   return EDTTS_OK;
 }
 
-// EDTTS_MATMUL_BF16 and EDTTS_ATTN_BF16 have one legal spelling each, with or without the other (include/edtts.h); false: the error
-// text is set
-constexpr int kMixedBits = EDTTS_MATMUL_BF16 | EDTTS_ATTN_BF16;
+// EDTTS_MATMUL_BF16 and EDTTS_ATTN_BF16 have one legal spelling each, with or without the other; EDTTS_TAPE_BF16 only with both
+// (include/edtts.h); false: the error text is set
+constexpr int kMixedBits = EDTTS_MATMUL_BF16 | EDTTS_ATTN_BF16 | EDTTS_TAPE_BF16;
 static bool matmul_bit_ok(const EdttsDims* d) {
-  const int rest = d->compute_dtype & ~kMixedBits;  // what the two bits ride on
+  if ((d->compute_dtype & EDTTS_TAPE_BF16) && d->compute_dtype != (EDTTS_F32 | EDTTS_KERNELS_GENERIC | kMixedBits)) {
+    fail(EDTTS_ERR_UNSUPPORTED,
+         "compute_dtype=0x%x: EDTTS_TAPE_BF16 is legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC | EDTTS_MATMUL_BF16 | EDTTS_ATTN_BF16 | "
+         "EDTTS_TAPE_BF16 (a buffer with an fp32 reader cannot be narrowed)",
+         d->compute_dtype);
+    return false;
+  }
+  const int rest = d->compute_dtype & ~kMixedBits;  // what the bits ride on
   if (!(d->compute_dtype & kMixedBits) || rest == (EDTTS_F32 | EDTTS_KERNELS_GENERIC)) return true;
   if (d->compute_dtype & EDTTS_ATTN_BF16)
     fail(EDTTS_ERR_UNSUPPORTED,
@@ -205,6 +213,7 @@ static int make_layout(const EdttsDims* d, Layout* lo) {
       if (rc == EDTTS_OK) {
         lo->MM16 = mm16;
         lo->ATT16 = att16;
+        lo->TAPE16 = (d->compute_dtype & EDTTS_TAPE_BF16) != 0;  // (matmul_bit_ok: then mm16 and att16)
       }
       return rc;
     }

@@ -98,7 +98,7 @@ class _DecoderGrad(torch.autograd.Function):
 class EdgeDiffusionDecoder(nn.Module):
     def __init__(self, cfg, max_len: int = 1000, max_context_len: int = 512, compute_dtype: str = "f32", kernels: str = "compiled",
                  autograd: bool = False, train_dropout: bool = False, train_lengths: bool = False, matmul_dtype: str = "f32",
-                 attn_dtype: str = "f32"):
+                 attn_dtype: str = "f32", tape_dtype: str = "f32"):
         """``max_len`` / ``max_context_len`` size the two sinusoidal tables (reference: 1000 / 512, decoder.py:38,41);
         they are pure functions of position, so larger values only lift the reference's length limit.
         ``compute_dtype``: "f32" (the reference's arithmetic) or "bf16" -- contractions on bf16 MFMA with fp32 accumulation,
@@ -132,8 +132,25 @@ class EdgeDiffusionDecoder(nn.Module):
         ``matmul_dtype``: both attentions of every block, forward and backward, run their contractions (q k^T, p v, dO v^T, and the
         products that make dQ, dK and dV) on bf16 MFMAs with fp32 accumulators, as ``torch.autocast`` runs them.  Only the operands
         of those products are rounded; the scale, mask, softmax statistics, log-sum-exp, delta and every stored tensor stay fp32, and
-        the dropout masks are the same.  Composes with everything ``matmul_dtype`` composes with: DESIGN.md section 27."""
+        the dropout masks are the same.  Composes with everything ``matmul_dtype`` composes with: DESIGN.md section 27.
+        ``tape_dtype``: "f32" (default) or "bf16" (needs ``kernels="generic"``, ``matmul_dtype="bf16"`` AND ``attn_dtype="bf16"``) --
+        the four per-layer activations that, with both of those on, are read only by loaders that round to bf16 (q|k|v, the
+        cross-attention queries, the cross K|V rows and the SwiGLU output) are stored as bf16, on the training tape and in the
+        inference workspace alike.  Rounding to bf16 is idempotent, so eps, every gradient and every sampler output are BITWISE those
+        of ``tape_dtype="f32"``; what changes is the tape (11 H -> 8 H floats per frame and layer at ffn_mult 2) and the traffic of
+        those buffers.  Everything else stays fp32.  Composes with everything the other two compose with: DESIGN.md section 28."""
         super().__init__()
+        if tape_dtype not in native.TAPE_DTYPES:
+            raise ValueError(f"tape_dtype must be one of {sorted(native.TAPE_DTYPES)}, got {tape_dtype!r}")
+        if native.TAPE_DTYPES[tape_dtype]:
+            missing = ([f"kernels='generic' (got kernels={kernels!r})"] if kernels != "generic" else []) + [
+                f"{k}='bf16' (got {k}={v!r})" for k, v, table in (("matmul_dtype", matmul_dtype, native.MATMUL_DTYPES),
+                                                                  ("attn_dtype", attn_dtype, native.ATTN_DTYPES))
+                if not table.get(v)]
+            if missing:
+                raise ValueError(f"tape_dtype={tape_dtype!r} needs " + " and ".join(missing) + ": a buffer with an fp32 reader cannot be "
+                                 "stored as bf16 without changing results")
+        self.tape_dtype = tape_dtype
         if attn_dtype not in native.ATTN_DTYPES:
             raise ValueError(f"attn_dtype must be one of {sorted(native.ATTN_DTYPES)}, got {attn_dtype!r}")
         if native.ATTN_DTYPES[attn_dtype] and kernels != "generic":
@@ -266,7 +283,8 @@ class EdgeDiffusionDecoder(nn.Module):
         return native.EdttsDims(c.hidden, c.layers, c.heads, c.n_mels, c.ffn_mult, c.codebook_size, c.semantic_dim, window,
                                 self.max_len, self.max_context_len, self.n_step_emb,
                                 native.COMPUTE_DTYPES[self.compute_dtype] | native.KERNELS[self.kernels]
-                                | native.MATMUL_DTYPES[self.matmul_dtype] | native.ATTN_DTYPES[self.attn_dtype])
+                                | native.MATMUL_DTYPES[self.matmul_dtype] | native.ATTN_DTYPES[self.attn_dtype]
+                                | native.TAPE_DTYPES[self.tape_dtype])
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         sd = {k: v for k, v in self.named_parameters()}

@@ -102,6 +102,15 @@ MATMUL_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": EDTTS_MATMUL_BF16, "
 # attention-precision bit (include/edtts.h): both attentions' contractions, forward and backward, on bf16 MFMAs, storage fp32
 EDTTS_ATTN_BF16 = 0x800
 ATTN_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": EDTTS_ATTN_BF16, "bfloat16": EDTTS_ATTN_BF16}
+# activation-storage bit (include/edtts.h): q|k|v, the cross queries, the cross K|V and the SwiGLU output stored as bf16; only with both
+# bits above
+EDTTS_TAPE_BF16 = 0x1000
+TAPE_DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": EDTTS_TAPE_BF16, "bfloat16": EDTTS_TAPE_BF16}
+# the per-layer members of the training tape, as edtts_train_tape_region names them (include/edtts.h: EDTTS_TAPE_*)
+TAPE_REGIONS = ("crp", "kv", "h0", "h1", "h2", "qkv", "att1", "lse1", "qc", "att2", "lse2", "act")
+(EDTTS_TAPE_CRP, EDTTS_TAPE_KV, EDTTS_TAPE_H0, EDTTS_TAPE_H1, EDTTS_TAPE_H2, EDTTS_TAPE_QKV, EDTTS_TAPE_ATT1, EDTTS_TAPE_LSE1,
+ EDTTS_TAPE_QC, EDTTS_TAPE_ATT2, EDTTS_TAPE_LSE2, EDTTS_TAPE_ACT) = range(12)
+TAPE_NARROWED = ("kv", "qkv", "qc", "act")  # what EDTTS_TAPE_BF16 stores as bf16
 
 
 class EdttsError(RuntimeError):
@@ -134,6 +143,7 @@ _ABI = {
     "edtts_train_tape_bytes": (_STATUS, (dp, i32, i32, i32, p_sz)),
     "edtts_train_scratch_bytes": (_STATUS, (dp, i32, i32, i32, p_sz)),
     "edtts_train_dw_slab_rows": (_VALUE, (i32,)),
+    "edtts_train_tape_region": (_STATUS, (dp, i32, i32, i32, i32, i32, p_sz, p_sz, p_i32)),
     "edtts_decoder_forward_train": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp)),
     "edtts_decoder_backward": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, vp)),
     "edtts_decoder_forward_train_drop": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, drp, vp)),
@@ -352,6 +362,16 @@ def decoder_forward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tens
 # ---------------------------------------------------------------------------------------------- training
 def train_tape_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
     return _size_query(lib().edtts_train_tape_bytes, C.byref(dims), B, T, S)
+
+
+def train_tape_region(dims: EdttsDims, B: int, T: int, S: int, layer: int, which) -> tuple:
+    """(offset in bytes, bytes, bytes per element) of one per-layer member of the training tape; ``which``: a name of TAPE_REGIONS or
+    its EDTTS_TAPE_* number (include/edtts.h: edtts_train_tape_region)."""
+    if isinstance(which, str):
+        which = TAPE_REGIONS.index(which)
+    off, n, eb = sz(), sz(), i32()
+    lib().edtts_train_tape_region(C.byref(dims), B, T, S, int(layer), int(which), C.byref(off), C.byref(n), C.byref(eb))
+    return int(off.value), int(n.value), int(eb.value)
 
 
 def train_scratch_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:

@@ -116,6 +116,25 @@ enum { EDTTS_MATMUL_BF16 = 0x400 };
  * edtts_train_tape_bytes, edtts_train_scratch_bytes and edtts_generic_slot_dest answer as they do without it. */
 enum { EDTTS_ATTN_BF16 = 0x800 };
 
+/* Activation-storage bit of EdttsDims.compute_dtype.  Legal only as EDTTS_F32 | EDTTS_KERNELS_GENERIC |
+ * EDTTS_MATMUL_BF16 | EDTTS_ATTN_BF16 | EDTTS_TAPE_BF16; every other combination that carries it is EDTTS_ERR_UNSUPPORTED with a
+ * message naming the bit (a buffer with an fp32 reader cannot be narrowed without changing results, and one rule is simpler than
+ * four partial ones).  With both other bits, four activation buffers of every layer are read only by loaders that round to bf16:
+ *   q|k|v         [B T][3 hidden]         written by the QKV projection, read by the self-attention, forward and backward
+ *   cross q       [B T][hidden]           written by q_proj, read by the cross-attention, forward and backward
+ *   cross K|V     [B S][2 hidden]         written by kv_up, read by the cross-attention, forward and backward
+ *   SwiGLU output [B T][ffn_mult hidden]  written by the FFN's up projection (after its dropout), read by the down projection and dW_down
+ * Storage contract: with the bit these four hold __bf16, rounded to nearest even by the conversion those loaders use
+ * (v_cvt_pk_bf16_f32), with row pitches counted in elements as before (3 hidden, hidden, 2 hidden, ffn_mult hidden).  Rounding to
+ * bf16 is idempotent, so every consumer forms the operand it forms without the bit: eps, every gradient and every sampler output are
+ * BITWISE those of the same dims without it.  Everything else stays fp32: the residual stream and its snapshots, both attention
+ * outputs (delta reads them unrounded), the kv_down rows, the context and AdaLN rows, the log-sum-exps, every gradient and output.
+ * edtts_train_tape_bytes shrinks by those four regions' halves (each region stays 256-byte aligned; edtts_train_tape_region says
+ * where each lies).  edtts_workspace_bytes, edtts_train_scratch_bytes, edtts_packed_bytes and edtts_generic_slot_dest answer as they do
+ * without the bit: the inference forward and the samplers honour the bit through the same launch list and use the first half of the
+ * workspace's q|k|v / SwiGLU buffer and of each layer's K|V buffer.  The dropout masks do not depend on the bit. */
+enum { EDTTS_TAPE_BF16 = 0x1000 };
+
 int edtts_version(void);
 const char* edtts_last_error(void);
 
@@ -186,6 +205,28 @@ int edtts_decoder_forward(const EdttsDims* dims, const void* packed, void* works
 int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes);
 int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes);
 int edtts_train_dw_slab_rows(int rows);
+
+/* Where one per-layer member of the tape lies (a host query, for tests and tools): *offset_bytes from the tape's start (a multiple of
+ * 256), *bytes = elements x *elem_bytes without the alignment padding behind it, *elem_bytes = 4, or 2 for the four regions that
+ * EDTTS_TAPE_BF16 narrows when dims carries that bit.  Rows and pitches: KV [B S][2 hidden]; CRP [B S][hidden / 2]; H0, H1, H2, QC,
+ * ATT1, ATT2 [B T][hidden]; QKV [B T][3 hidden]; LSE1, LSE2 [B][heads][T]; ACT [B T][ffn_mult hidden].  EDTTS_ERR_ARG for a layer or
+ * `which` out of range. */
+enum {
+  EDTTS_TAPE_CRP = 0,  /* kv_down rows before kv_norm */
+  EDTTS_TAPE_KV = 1,   /* cross K|V rows (narrowed) */
+  EDTTS_TAPE_H0 = 2,   /* the residual stream entering norm1 / norm2 / norm3 */
+  EDTTS_TAPE_H1 = 3,
+  EDTTS_TAPE_H2 = 4,
+  EDTTS_TAPE_QKV = 5,  /* q|k|v rows (narrowed) */
+  EDTTS_TAPE_ATT1 = 6, /* self-attention output and its log-sum-exp */
+  EDTTS_TAPE_LSE1 = 7,
+  EDTTS_TAPE_QC = 8,   /* cross-attention query rows (narrowed) */
+  EDTTS_TAPE_ATT2 = 9, /* cross-attention output and its log-sum-exp */
+  EDTTS_TAPE_LSE2 = 10,
+  EDTTS_TAPE_ACT = 11  /* SwiGLU output (narrowed) */
+};
+int edtts_train_tape_region(const EdttsDims* dims, int B, int T, int S, int layer, int which, size_t* offset_bytes, size_t* bytes,
+                            int* elem_bytes);
 
 /* models/decoder.py:66-109 as edtts_decoder_forward runs it on the generic path -- eps is bitwise that call's -- keeping on
  * `tape` what the backward needs.  Arguments as edtts_decoder_forward; the workspace is that call's (edtts_workspace_bytes with
