@@ -1163,7 +1163,12 @@ int edtts_train_tape_region(const EdttsDims* dims, int B, int T, int S, int laye
     case EDTTS_TAPE_ATT2: off = z.att2; n = M * H; break;
     case EDTTS_TAPE_LSE2: off = z.lse2; n = M * lo.HEADS; break;
     case EDTTS_TAPE_ACT: off = z.act; n = M * lo.FM * H; narrow = true; break;
-    default: return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: which=%d is not one of EDTTS_TAPE_CRP .. EDTTS_TAPE_ACT", which);
+    // the whole-model members: the same answer for every layer
+    case EDTTS_TAPE_COND: off = tt.cond; n = (size_t)B * lo.L * 4 * H; break;
+    case EDTTS_TAPE_TCOND: off = tt.cond + (size_t)B * lo.L * 4 * H; n = (size_t)B * H; break;
+    case EDTTS_TAPE_CTX: off = tt.ctx; n = CS * H; break;
+    case EDTTS_TAPE_HL: off = tt.hL; n = M * H; break;
+    default: return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: which=%d is not one of EDTTS_TAPE_CRP .. EDTTS_TAPE_HL", which);
   }
   *elem_bytes = narrow && lo.TAPE16 ? 2 : 4;
   *offset_bytes = off * sizeof(float);

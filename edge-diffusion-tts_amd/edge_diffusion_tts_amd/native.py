@@ -111,6 +111,9 @@ TAPE_REGIONS = ("crp", "kv", "h0", "h1", "h2", "qkv", "att1", "lse1", "qc", "att
 (EDTTS_TAPE_CRP, EDTTS_TAPE_KV, EDTTS_TAPE_H0, EDTTS_TAPE_H1, EDTTS_TAPE_H2, EDTTS_TAPE_QKV, EDTTS_TAPE_ATT1, EDTTS_TAPE_LSE1,
  EDTTS_TAPE_QC, EDTTS_TAPE_ATT2, EDTTS_TAPE_LSE2, EDTTS_TAPE_ACT) = range(12)
 TAPE_NARROWED = ("kv", "qkv", "qc", "act")  # what EDTTS_TAPE_BF16 stores as bf16
+# the whole-model members (always fp32; edtts_train_tape_region answers the same for every layer)
+TAPE_GLOBALS = ("cond", "tcond", "ctx", "hl")
+EDTTS_TAPE_COND, EDTTS_TAPE_TCOND, EDTTS_TAPE_CTX, EDTTS_TAPE_HL = range(12, 16)
 
 
 class EdttsError(RuntimeError):
@@ -365,10 +368,11 @@ def train_tape_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
 
 
 def train_tape_region(dims: EdttsDims, B: int, T: int, S: int, layer: int, which) -> tuple:
-    """(offset in bytes, bytes, bytes per element) of one per-layer member of the training tape; ``which``: a name of TAPE_REGIONS or
-    its EDTTS_TAPE_* number (include/edtts.h: edtts_train_tape_region)."""
+    """(offset in bytes, bytes, bytes per element) of one member of the training tape; ``which``: a name of TAPE_REGIONS (per layer)
+    or TAPE_GLOBALS (whole model: any layer in range gives the same answer), or its EDTTS_TAPE_* number (include/edtts.h:
+    edtts_train_tape_region)."""
     if isinstance(which, str):
-        which = TAPE_REGIONS.index(which)
+        which = (TAPE_REGIONS + TAPE_GLOBALS).index(which)
     off, n, eb = sz(), sz(), i32()
     lib().edtts_train_tape_region(C.byref(dims), B, T, S, int(layer), int(which), C.byref(off), C.byref(n), C.byref(eb))
     return int(off.value), int(n.value), int(eb.value)

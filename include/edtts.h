@@ -206,11 +206,14 @@ int edtts_train_tape_bytes(const EdttsDims* dims, int B, int T, int S, size_t* o
 int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t* out_bytes);
 int edtts_train_dw_slab_rows(int rows);
 
-/* Where one per-layer member of the tape lies (a host query, for tests and tools): *offset_bytes from the tape's start (a multiple of
- * 256), *bytes = elements x *elem_bytes without the alignment padding behind it, *elem_bytes = 4, or 2 for the four regions that
- * EDTTS_TAPE_BF16 narrows when dims carries that bit.  Rows and pitches: KV [B S][2 hidden]; CRP [B S][hidden / 2]; H0, H1, H2, QC,
- * ATT1, ATT2 [B T][hidden]; QKV [B T][3 hidden]; LSE1, LSE2 [B][heads][T]; ACT [B T][ffn_mult hidden].  EDTTS_ERR_ARG for a layer or
- * `which` out of range. */
+/* Where one member of the tape lies (a host query, for tests and tools): *offset_bytes from the tape's start (a multiple of
+ * 256, TCOND excepted: it lies right behind the AdaLN rows), *bytes = elements x *elem_bytes without the alignment padding behind it,
+ * *elem_bytes = 4, or 2 for the four regions that EDTTS_TAPE_BF16 narrows when dims carries that bit.  Per-layer members, rows and
+ * pitches: KV [B S][2 hidden]; CRP [B S][hidden / 2]; H0, H1, H2, QC, ATT1, ATT2 [B T][hidden]; QKV [B T][3 hidden]; LSE1, LSE2
+ * [B][heads][T] (exp2 domain: m + log2 l of the scores times log2(e) / sqrt(head_dim)); ACT [B T][ffn_mult hidden].  Whole-model
+ * members, always fp32 (`layer` must still be in range; the answer does not depend on it): COND [B][layers][2][2 hidden], per layer
+ * the AdaLN rows of norm1 then norm3, each (1 + scale) then shift; TCOND [B][hidden]; CTX [B S][hidden]; HL [B T][hidden].
+ * EDTTS_ERR_ARG for a layer or `which` out of range. */
 enum {
   EDTTS_TAPE_CRP = 0,  /* kv_down rows before kv_norm */
   EDTTS_TAPE_KV = 1,   /* cross K|V rows (narrowed) */
@@ -223,7 +226,11 @@ enum {
   EDTTS_TAPE_QC = 8,   /* cross-attention query rows (narrowed) */
   EDTTS_TAPE_ATT2 = 9, /* cross-attention output and its log-sum-exp */
   EDTTS_TAPE_LSE2 = 10,
-  EDTTS_TAPE_ACT = 11  /* SwiGLU output (narrowed) */
+  EDTTS_TAPE_ACT = 11, /* SwiGLU output (narrowed) */
+  EDTTS_TAPE_COND = 12,  /* AdaLN rows of every layer */
+  EDTTS_TAPE_TCOND = 13, /* t_cond, behind the AdaLN rows */
+  EDTTS_TAPE_CTX = 14,   /* context rows */
+  EDTTS_TAPE_HL = 15     /* the residual stream entering final_norm */
 };
 int edtts_train_tape_region(const EdttsDims* dims, int B, int T, int S, int layer, int which, size_t* offset_bytes, size_t* bytes,
                             int* elem_bytes);

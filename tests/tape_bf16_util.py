@@ -20,8 +20,10 @@ BIT = native.EDTTS_TAPE_BF16
 
 
 def region_shape(cfg, B, T, S, which):
-    """(rows, elements per row) of a per-layer tape member (include/edtts.h: edtts_train_tape_region)."""
+    """(rows, elements per row) of a tape member, per-layer or whole-model (include/edtts.h: edtts_train_tape_region)."""
     H = cfg.hidden
+    if which in native.TAPE_GLOBALS:
+        return {"cond": (B * cfg.layers * 2, 2 * H), "tcond": (B, H), "ctx": (B * S, H), "hl": (B * T, H)}[which]
     return {"crp": (B * S, H // 2), "kv": (B * S, 2 * H), "h0": (B * T, H), "h1": (B * T, H), "h2": (B * T, H), "qkv": (B * T, 3 * H),
             "att1": (B * T, H), "lse1": (B * cfg.heads, T), "qc": (B * T, H), "att2": (B * T, H), "lse2": (B * cfg.heads, T),
             "act": (B * T, cfg.ffn_mult * H)}[which]

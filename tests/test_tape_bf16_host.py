@@ -136,7 +136,8 @@ def test_refusals_without_the_bit_keep_their_words():
 
 def test_region_query_checks_its_arguments():
     d = dec("bf16", name="G2").dims()
-    for layer, which in ((-1, 0), (2, 0), (0, -1), (0, len(native.TAPE_REGIONS))):
+    # (the numbers behind the per-layer members name the whole-model ones, native.TAPE_GLOBALS; the first number past those is refused)
+    for layer, which in ((-1, 0), (2, 0), (0, -1), (0, len(native.TAPE_REGIONS) + len(native.TAPE_GLOBALS)), (2, len(native.TAPE_REGIONS))):
         with pytest.raises((native.EdttsError, ValueError)):
             native.train_tape_region(d, 2, 19, 9, layer, which)
 
