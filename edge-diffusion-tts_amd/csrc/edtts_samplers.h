@@ -4,11 +4,13 @@
 //
 //   k_ddim / k_ddpm            stand-alone elementwise updates (HBM-bound)                         schedule.py:157-238
 //   k_inpaint_inject(1)        q_sample of the known frames of an in-painting call                 inference_pipeline.py:117-123
+//   k_inpaint_inject_mask(1)   ... of the frames a per-frame mask names (known frames anywhere, not a prefix)
 //   k_randn / k_randn_rows     standard normals from the library's Philox streams
 //   run_sampler                the sub-batched step loop of edtts_generate / edtts_sample_multistep / edtts_sample_ddpm
-//   run_inpaint                the step loop of the two in-painting samplers, on the caller's stream alone
+//   run_inpaint                the step loop of the in-painting samplers, on the caller's stream alone
 // C ABI: edtts_generate(_len), edtts_sample_multistep(_len), edtts_sample_ddpm(_len), edtts_sample_inpaint(_len),
-// edtts_sample_inpaint_multistep_len, edtts_ddim_step, edtts_ddpm_step, edtts_randn, edtts_randn_rows.
+// edtts_sample_inpaint_multistep_len, edtts_sample_inpaint_mask_len, edtts_sample_inpaint_multistep_mask_len, edtts_ddim_step,
+// edtts_ddpm_step, edtts_randn, edtts_randn_rows.
 
 // =========================================================================================================
 // standalone DDIM / DDPM updates (HBM-bound: read x, eps ; write x_prev, x0 = 16 B/element)
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(256) void k_ddpm(StepArgs a) {
   }
 }
 
-// The next four kernels have C linkage: their symbols in the code object are the plain names (k_inpaint_inject, k_randn, ...), as
+// The next six kernels have C linkage: their symbols in the code object are the plain names (k_inpaint_inject, k_randn, ...), as
 // they were when the kernels stood inside edtts_kernels.hip's extern "C" block.  Outside such a block the names would be mangled.
 extern "C" {
 
@@ -140,6 +142,53 @@ __global__ __launch_bounds__(256) void k_inpaint_inject1(float* x, const float* 
       o = qsample_elem(o, c_known, nz, c_noise);
     }
     x[(b * T) * MEL + r] = o;
+  }
+}
+
+// The same q_sample at the frames a mask names: x[b][f][:] = c_known * known[b][f][:] + c_noise * noise wherever keep[b][f] != 0 and
+// f < T_b; known, noise and x are [B, T, MEL], keep is [B, T].  The keep byte is read first: at a frame that is not kept, or past the
+// row's length, neither known nor noise is loaded.  Philox keys: with per-row seeds (seeds[b], step, row-local element f * MEL + m) --
+// the word k_inpaint_inject draws for the same (b, f, m) --, else (seed, step, global element b * T * MEL + f * MEL + m).
+// MEL % 4 == 0 (a quad lies in one frame; every row of the three tensors starts on a float4).
+__global__ __launch_bounds__(256) void k_inpaint_inject_mask(float* x, const float* known, const float* noise, const unsigned char* keep,
+                                                             int B, int T, int MEL, float c_known, float c_noise, unsigned long long seed,
+                                                             unsigned step, const unsigned long long* seeds, const int64_t* t_len) {
+  const size_t q = (size_t)MEL / 4, per = (size_t)T * q, n4 = (size_t)B * per;  // quads per frame, per row, in all
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t fr = i / q;  // frame b * T + f
+    if (!keep[fr]) continue;
+    const size_t b = fr / T;
+    const int Tb = t_len ? utt_len_of(t_len[b], T, false) : T;
+    if (fr - b * T >= (size_t)Tb) continue;
+    const f4 kv = ldg4(known + 4 * i);
+    f4 o = kv;
+    if (c_noise != 0.f) {
+      const f4 nz = noise ? ldg4(noise + 4 * i) : (seeds ? philox_normal4(seeds[b], step, i - b * per) : philox_normal4(seed, step, i));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = qsample_elem(kv[e], c_known, nz[e], c_noise);
+    }
+    stg4(x + 4 * i, o);
+  }
+}
+
+// ... one element per thread, for n_mels % 4 != 0 (generic path: a quad of the row straddles frames): the same values (element e is
+// lane e & 3 of Philox draw e >> 2; with per-row seeds e counts from the row's start)
+__global__ __launch_bounds__(256) void k_inpaint_inject_mask1(float* x, const float* known, const float* noise, const unsigned char* keep,
+                                                              int B, int T, int MEL, float c_known, float c_noise, unsigned long long seed,
+                                                              unsigned step, const unsigned long long* seeds, const int64_t* t_len) {
+  const size_t per = (size_t)T * MEL, n = (size_t)B * per;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t fr = i / MEL;
+    if (!keep[fr]) continue;
+    const size_t b = fr / T, r = i - b * per;
+    const int Tb = t_len ? utt_len_of(t_len[b], T, false) : T;
+    if (fr - b * T >= (size_t)Tb) continue;
+    float o = known[i];
+    if (c_noise != 0.f) {
+      const float nz = noise ? noise[i] : (seeds ? philox_normal4(seeds[b], step, r >> 2)[(int)(r & 3)] : philox_normal4(seed, step, i >> 2)[(int)(i & 3)]);
+      o = qsample_elem(o, c_known, nz, c_noise);
+    }
+    x[i] = o;
   }
 }
 
@@ -250,6 +299,7 @@ struct InpaintArgs {
   const float *sem_features, *zero_features; float* x; int num_steps; const int64_t *t_all, *step_all;
   const float *coef_host, *known_mel; int overlap_len; const float* noise_k; uint64_t seed; float cfg_scale; float* v_uncond;
   const int64_t *t_len, *s_len; const uint64_t* seeds; void* stream;
+  const uint8_t* keep = nullptr;  // the *_mask_len entry points: [B, T], known_mel and noise_k are whole [B, T, n_mels] tensors, overlap_len unused
 };
 // The step loop of the in-painting samplers, in one piece on the caller's stream (no sub-batches: a captured call stays one chain):
 // the shared argument checks (own_ptrs: the entry point's further pointers are there; own_checks(): its further checks, made last),
@@ -263,7 +313,8 @@ static int run_inpaint(const InpaintArgs& a, const Layout& lo, bool own_ptrs, Ch
   if (a.num_steps < 1) return fail(EDTTS_ERR_ARG, "num_steps=%d < 1", a.num_steps);
   const bool guided = a.cfg_scale != 1.0f;
   if (guided && (!a.workspace_uncond || !a.zero_features || !a.v_uncond)) return fail(EDTTS_ERR_ARG, "cfg_scale != 1 needs workspace_uncond, zero_features and v_uncond");
-  if (a.known_mel && (a.overlap_len < 1 || a.overlap_len > a.T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", a.overlap_len, a.T);
+  const bool prefix = a.known_mel && !a.keep;  // the known frames are the first overlap_len of every row
+  if (prefix && (a.overlap_len < 1 || a.overlap_len > a.T)) return fail(EDTTS_ERR_ARG, "overlap_len=%d outside [1,%d]", a.overlap_len, a.T);
   TRY_G(check_shapes(lo, a.B, a.T, a.S));
   TRY_G(own_checks());
   hipStream_t st = (hipStream_t)a.stream;
@@ -271,7 +322,7 @@ static int run_inpaint(const InpaintArgs& a, const Layout& lo, bool own_ptrs, Ch
   float* wsb = (float*)a.workspace;
   Workspace ws;
   make_workspace(lo, a.B, a.T, a.S, a.num_steps, &ws);
-  TRY_G(launch_len_check(a.t_len, a.s_len, a.B, a.T, a.S, wsb, st, a.known_mel ? a.overlap_len : 1));
+  TRY_G(launch_len_check(a.t_len, a.s_len, a.B, a.T, a.S, wsb, st, prefix ? a.overlap_len : 1));
   TRY_G(launch_cond(lo, blob, a.t_all, a.step_all, nullptr, a.num_steps, wsb + ws.cond, wsb, st));
   const size_t row = (size_t)lo.L * 2 * 2 * lo.H;
   const CallCtx c{lo, blob, ws, wsb, a.B, a.T, a.S, a.dims->window, Lens{a.t_len, a.s_len}, st};
@@ -308,6 +359,23 @@ static void launch_inject(const InpaintArgs& a, int mel, float c_known, float c_
                      a.noise_k ? a.noise_k + (size_t)step * per_k : nullptr, a.B, a.T, a.overlap_len, mel, c_known, c_noise,
                      (unsigned long long)a.seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(a.seeds),
                      a.t_len);
+}
+
+// ... of k_inpaint_inject_mask (n_mels % 4 == 0) or k_inpaint_inject_mask1: the same for the frames a.keep names, over the whole
+// [B, T, n_mels] tensors (block `step` of an injected noise_k is that large)
+static void launch_inject_mask(const InpaintArgs& a, int mel, float c_known, float c_noise, int step) {
+  const size_t per = (size_t)a.B * a.T * mel;
+  const bool vec = step_vec4((size_t)mel, {a.x, a.known_mel, a.noise_k});
+  const size_t bx = (per / (vec ? 4 : 1) + 255) / 256;
+  hipLaunchKernelGGL(vec ? k_inpaint_inject_mask : k_inpaint_inject_mask1, dim3(bx > 2048 ? 2048u : (unsigned)bx), dim3(256), 0, (hipStream_t)a.stream, a.x,
+                     a.known_mel, a.noise_k ? a.noise_k + (size_t)step * per : nullptr, a.keep, a.B, a.T, mel, c_known, c_noise,
+                     (unsigned long long)a.seed, kStreamInpaintStep + (unsigned)step, reinterpret_cast<const unsigned long long*>(a.seeds),
+                     a.t_len);
+}
+// known_mel and keep come together or not at all (neither: the plain sampler)
+static int check_mask_args(const float* known_mel, const uint8_t* keep) {
+  if ((known_mel == nullptr) != (keep == nullptr)) return fail(EDTTS_ERR_ARG, "known_mel and keep must both be given or both be NULL");
+  return EDTTS_OK;
 }
 
 static unsigned step_blocks(const StepArgs& a) {  // blocks per utterance of k_ddim / k_ddpm
@@ -491,6 +559,72 @@ int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed
         return tail;
       },
       [] { return EDTTS_OK; });
+}
+
+int edtts_sample_inpaint_mask_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
+                                  const float* sem_features, const float* zero_features, float* x, int num_steps,
+                                  const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                                  const uint8_t* keep, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                                  const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, void* stream) {
+  const SettingsScope settings;
+  Layout lo;
+  TRY_G(make_layout(dims, &lo));
+  TRY_G(check_mask_args(known_mel, keep));
+  const InpaintArgs a{dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all, step_all,
+                      coef_host, known_mel, 0, noise_k, seed, cfg_scale, v_uncond, t_len, s_len, seeds, stream, keep};
+  return run_inpaint(
+      a, lo, true, [] { return EDTTS_OK; },
+      [&](int i) -> int {  // q_sample(known_mel, t) into the kept frames
+        launch_inject_mask(a, lo.MEL, coef_host[4 * i], coef_host[4 * i + 1], i);
+        LAUNCH_CHECK("k_inpaint_inject_mask");
+        return EDTTS_OK;
+      },
+      [&](int i) {
+        const float* k = coef_host + 4 * i;
+        StepTail tail;
+        tail.kind = TAIL_VPRED; tail.x_prev = x;
+        tail.vp = VpredStepArgs{{k[0], k[1], k[2], k[3], cfg_scale}, nullptr};
+        return tail;
+      },
+      [&]() -> int {  // final force
+        launch_inject_mask(a, lo.MEL, 1.0f, 0.0f, 0);
+        LAUNCH_CHECK("k_inpaint_inject_mask");
+        return EDTTS_OK;
+      });
+}
+
+int edtts_sample_inpaint_multistep_mask_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B,
+                                            int T, int S, const float* sem_features, const float* zero_features, float* x, int num_steps,
+                                            const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                                            const uint8_t* keep, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                                            const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, float* hist, float* x0_all,
+                                            void* stream) {
+  const SettingsScope settings;
+  Layout lo;
+  TRY_G(make_layout(dims, &lo));
+  TRY_G(check_mask_args(known_mel, keep));
+  const InpaintArgs a{dims, packed, workspace, workspace_uncond, B, T, S, sem_features, zero_features, x, num_steps, t_all, step_all,
+                      coef_host, known_mel, 0, noise_k, seed, cfg_scale, v_uncond, t_len, s_len, seeds, stream, keep};
+  const size_t per = (size_t)B * T * lo.MEL;
+  return run_inpaint(
+      a, lo, hist != nullptr, [&] { return check_lms_modes(coef_host, num_steps); },
+      [&](int i) -> int {  // every step's q_sample is a launch of its own: the tails carry no blend (their kernels know prefixes only)
+        launch_inject_mask(a, lo.MEL, coef_host[8 * i + 1], -coef_host[8 * i + 2], i);
+        LAUNCH_CHECK("k_inpaint_inject_mask");
+        return EDTTS_OK;
+      },
+      [&](int i) {
+        StepTail tail;
+        tail.kind = TAIL_VLMS; tail.x_prev = x;
+        tail.lms = lms_step_args(coef_host + 8 * i, hist, x0_all, per, i, 0);
+        tail.vp.k.cfg = cfg_scale;
+        return tail;
+      },
+      [&]() -> int {  // final force
+        launch_inject_mask(a, lo.MEL, 1.0f, 0.0f, 0);
+        LAUNCH_CHECK("k_inpaint_inject_mask");
+        return EDTTS_OK;
+      });
 }
 
 int edtts_ddim_step(const float* alpha_bar, int n_table, const float* x, const float* eps, const int64_t* t,

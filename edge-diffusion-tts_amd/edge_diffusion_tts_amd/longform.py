@@ -13,6 +13,9 @@ batched call (per-utterance semantic lengths and seeds), and each utterance's re
 ``inpaint_dpm_refine`` is the teacher refinement with DPM-Solver++'s multistep update (schedule.py: DPMSolverPP) in place of the
 first-order step -- the sampler the reference builds next to its pipeline and never calls -- as ONE C-ABI call
 (edtts_sample_inpaint_multistep_len); ``generate_long(_batch)(..., solver="dpmpp")`` refines every chunk with it.
+All three samplers take ``keep=``, a per-frame mask of the known frames in place of the known prefix (the reference's rule does not
+depend on where they sit; edtts_sample_inpaint_mask_len, edtts_sample_inpaint_multistep_mask_len), and ``edit`` re-synthesises
+stretches of an utterance with everything around them kept.
 """
 from __future__ import annotations
 
@@ -62,14 +65,57 @@ class InpaintSampler:
             out += [float(sab[t]), float(s1m[t]), float(torch.sqrt(a)), float(torch.sqrt(1 - a))]
         return out
 
+    @staticmethod
+    def _check_keep(keep, known_mel, overlap_len: int, noise_k, shape, n: int) -> None:
+        """The argument rules of ``keep=`` for a call on ``shape`` = (B, T, n_mels) with ``n`` steps: ValueError, before any launch."""
+        if keep is None:
+            return
+        B, T, M = (int(v) for v in shape)
+        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"keep must be a bool or uint8 tensor of shape [{B}, {T}], got "
+                             f"{keep.dtype if isinstance(keep, torch.Tensor) else type(keep).__name__}")
+        if tuple(keep.shape) != (B, T):
+            raise ValueError(f"keep must be [{B}, {T}], got {list(keep.shape)}")
+        if known_mel is None:
+            raise ValueError("keep= needs known_mel (the mel whose kept frames are held)")
+        if tuple(known_mel.shape) != (B, T, M):
+            raise ValueError(f"with keep=, known_mel must be [{B}, {T}, {M}], got {list(known_mel.shape)}")
+        if overlap_len != 0:
+            raise ValueError(f"with keep=, overlap_len must be 0 (the mask says which frames are known), got {overlap_len}")
+        if noise_k is not None and tuple(noise_k.shape) != (n, B, T, M):
+            raise ValueError(f"with keep=, noise_k must be [{n}, {B}, {T}, {M}], got {list(noise_k.shape)}")
+
+    @staticmethod
+    def keep_mask(B: int, T: int, intervals, device=None) -> torch.Tensor:
+        """The ``keep=`` mask of the in-painting samplers from frame intervals: ``intervals[b]`` is a sequence of half-open
+        (start, end) pairs, 0 <= start <= end <= T, and frame f of row b is kept when it lies in one of them.  Returns a bool
+        [B, T] tensor on ``device``.  ValueError for a list that is not B long or an interval outside [0, T]."""
+        intervals = list(intervals)
+        if len(intervals) != B:
+            raise ValueError(f"intervals: expected {B} entries (one list of (start, end) pairs per row), got {len(intervals)}")
+        mask = torch.zeros(B, T, dtype=torch.bool)
+        for b, row in enumerate(intervals):
+            for pair in row:
+                try:
+                    lo, hi = (int(v) for v in pair)
+                except (TypeError, ValueError):
+                    raise ValueError(f"intervals[{b}]: expected (start, end) pairs, got {pair!r}") from None
+                if not 0 <= lo <= hi <= T:
+                    raise ValueError(f"intervals[{b}]: need 0 <= start <= end <= {T}, got ({lo}, {hi})")
+                mask[b, lo:hi] = True
+        return mask if device is None else mask.to(device)
+
     def _run(self, x: torch.Tensor, sem_features: torch.Tensor, times: List[int], step_idx, known_mel, overlap_len: int,
              cfg_scale: float, noise_k, seed: int, x_lengths=None, sem_lengths=None, seeds=None, *, lms_rows=None,
-             return_intermediates: bool = False):
+             return_intermediates: bool = False, keep=None):
         """One C-ABI call (native.sample_inpaint): edtts_sample_inpaint_len, or with ``lms_rows`` (DPMSolverPP.step_coefficients of
-        ``times``) edtts_sample_inpaint_multistep_len.  ``step_idx``: the constant step index, or "index" for 0 .. n-1."""
+        ``times``) edtts_sample_inpaint_multistep_len.  ``step_idx``: the constant step index, or "index" for 0 .. n-1.
+        ``keep`` (bool or uint8 [B, T]): the known frames are those it names, of a ``known_mel`` [B, T, n_mels] -- the *_mask_len
+        twin of either entry point."""
         dec = self.decoder
         B, T, M = x.shape
         S = sem_features.shape[1]
+        self._check_keep(keep, known_mel, overlap_len, noise_k, (B, T, M), len(times))
         if (known_mel is not None and isinstance(x_lengths, torch.Tensor) and not x_lengths.is_cuda and B
                 and int(x_lengths.min()) < overlap_len):
             raise ValueError(f"x_lengths: every utterance needs at least overlap_len = {overlap_len} frames, got {int(x_lengths.min())}")
@@ -96,31 +142,41 @@ class InpaintSampler:
         v_u = torch.empty_like(x) if guided else None
         if known_mel is not None:
             known_mel = known_mel.to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(known_mel.shape) != (B, overlap_len, M):
-                raise ValueError(f"known_mel must be [{B}, {overlap_len}, {M}], got {tuple(known_mel.shape)}")
+            k_frames = T if keep is not None else overlap_len
+            if tuple(known_mel.shape) != (B, k_frames, M):
+                raise ValueError(f"known_mel must be [{B}, {k_frames}, {M}], got {tuple(known_mel.shape)}")
             if noise_k is not None:
                 noise_k = noise_k.to(device=dev, dtype=torch.float32).contiguous()
-                if tuple(noise_k.shape) != (n, B, overlap_len, M):
-                    raise ValueError(f"noise_k must be [{n}, {B}, {overlap_len}, {M}]")
+                if tuple(noise_k.shape) != (n, B, k_frames, M):
+                    raise ValueError(f"noise_k must be [{n}, {B}, {k_frames}, {M}]")
         else:
             noise_k = None
+        if keep is not None:  # (a bool tensor is bytes of 0 / 1: reinterpreted, not converted; a device tensor is not copied)
+            keep = keep.to(dev).contiguous()
+            keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
         x, x0_all = native.sample_inpaint(dec.dims(), packed, ws, ws_u, sem_features, zeros, x, t_all, s_all,
                                           self._coefs(times) if lms_rows is None else None, known_mel, overlap_len, noise_k, seed, cfg_scale,
-                                          v_u, t_len, s_len, sd, lms_rows=lms_rows, want_intermediates=return_intermediates)
+                                          v_u, t_len, s_len, sd, lms_rows=lms_rows, want_intermediates=return_intermediates, keep=keep)
         return (x, list(x0_all.unbind(0))) if lms_rows is not None and return_intermediates else x
 
     @torch.no_grad()
     def inpaint_student_sample(self, x_shape, sem_features, known_mel=None, overlap_len: int = 0, num_steps: int = 4, *,
                                x_init: Optional[torch.Tensor] = None, noise_k: Optional[torch.Tensor] = None, seed: int = 0,
                                x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None,
-                               seeds: Optional[Sequence[int]] = None):
+                               seeds: Optional[Sequence[int]] = None, keep: Optional[torch.Tensor] = None):
         """inference_pipeline.py:97-140.  ``x_init`` / ``noise_k`` inject the draws the reference takes from torch.randn /
         torch.randn_like (parity); otherwise the start noise comes from the library's Philox stream and the per-step q_sample
         noise from the in-kernel generator.
 
         Ragged batches: ``x_lengths`` / ``sem_lengths`` (int64 [B], see native.lengths) and ``seeds`` (B ints,
         or a device int64 [B] tensor) make row b bitwise the call on utterance b alone (its first x_lengths[b] frames and
-        sem_lengths[b] feature rows, ``seed=seeds[b]``); frames past x_lengths[b] come out as exact zeros."""
+        sem_lengths[b] feature rows, ``seed=seeds[b]``); frames past x_lengths[b] come out as exact zeros.
+
+        ``keep`` (bool or uint8 [B, T]): the known frames are the ones it names, anywhere in the utterance,
+        of a ``known_mel`` [B, T, n_mels]; ``overlap_len`` stays 0 and ``noise_k`` is [num_steps, B, T, n_mels].  Kept frames come
+        out bitwise ``known_mel``; kept frames past x_lengths[b] are ignored; ``keep[b, f] = f < ov`` with ``seeds`` is bitwise the
+        prefix call.  InpaintSampler.keep_mask builds the mask from frame intervals."""
+        self._check_keep(keep, known_mel, overlap_len, noise_k, x_shape, num_steps)
         dev = sem_features.device
         if x_init is not None:
             x = x_init.to(dev)
@@ -130,21 +186,23 @@ class InpaintSampler:
             x = native.randn(tuple(x_shape), dev, seed=seed, stream_id=0x51)
         times = linspace_times(self.cfg.diff_steps - 1, num_steps)
         return self._run(x, sem_features, times, 3, known_mel, overlap_len if known_mel is not None else 0, 1.0, noise_k, seed,
-                         x_lengths, sem_lengths, seeds)
+                         x_lengths, sem_lengths, seeds, keep=keep)
 
     @torch.no_grad()
     def inpaint_teacher_refine(self, x_coarse, sem_features, known_mel=None, overlap_len: int = 0, strength: float = 0.2,
                                steps: int = 10, cfg_scale: float = 1.0, *, noise: Optional[torch.Tensor] = None,
                                noise_k: Optional[torch.Tensor] = None, seed: int = 0, x_lengths: Optional[torch.Tensor] = None,
-                               sem_lengths: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None):
+                               sem_lengths: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None,
+                               keep: Optional[torch.Tensor] = None):
         """inference_pipeline.py:145-196: q_sample(x_coarse, t_start = int(T * strength)) then ``steps`` guided v-prediction steps.
-        ``x_lengths`` / ``sem_lengths`` / ``seeds``: as inpaint_student_sample (with ``seeds`` the q_sample noise of row b is the solo
-        call's)."""
+        ``x_lengths`` / ``sem_lengths`` / ``seeds`` / ``keep``: as inpaint_student_sample (with ``seeds`` the q_sample noise of row b
+        is the solo call's)."""
+        self._check_keep(keep, known_mel, overlap_len, noise_k, x_coarse.shape, steps)
         t_start = self._t_start(strength)
         x = self._refine_start(x_coarse, t_start, noise, seed, seeds)
         times = linspace_times(t_start, steps)
         return self._run(x, sem_features, times, 0, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k, seed,
-                         x_lengths, sem_lengths, seeds)
+                         x_lengths, sem_lengths, seeds, keep=keep)
 
     def _t_start(self, strength: float) -> int:
         t_start = int(self.cfg.diff_steps * strength)
@@ -195,21 +253,54 @@ class InpaintSampler:
                            steps: int = 15, order: int = 2, cfg_scale: float = 1.0, *, noise: Optional[torch.Tensor] = None,
                            noise_k: Optional[torch.Tensor] = None, seed: int = 0, x_lengths: Optional[torch.Tensor] = None,
                            sem_lengths: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None, step_idx=0,
-                           return_intermediates: bool = False):
+                           return_intermediates: bool = False, keep: Optional[torch.Tensor] = None):
         """inpaint_teacher_refine with DPM-Solver++'s multistep update (schedule.py: DPMSolverPP, v-prediction model) in place of the
         first-order step: the same start point q_sample(x_coarse, t_start), known-tail injection, guidance, lengths and seeds; the
         visiting times are DPMSolverPP.get_time_steps(steps, max_t=t_start) (strictly_decreasing_times of them), and each step's x0 = clamp(predict_x0_from_v) feeds the
         first / second / third_order_update over the x0 history (``order``).  One C-ABI call (edtts_sample_inpaint_multistep_len).
         ``step_idx``: the constant step index handed to the decoder (0: the long-form pipeline's), or "index" for 0 .. steps-1
-        (DPMSolverPP.sample's convention).  ``return_intermediates``: also return the list of every step's x0."""
+        (DPMSolverPP.sample's convention).  ``return_intermediates``: also return the list of every step's x0.
+        ``keep``: as inpaint_student_sample (edtts_sample_inpaint_multistep_mask_len: each step's q_sample of the kept frames is a
+        small launch of its own between the steps)."""
         times, rows = self.dpm_plan(strength, steps, order)
+        self._check_keep(keep, known_mel, overlap_len, noise_k, x_coarse.shape, len(times))
         if step_idx != "index" and not isinstance(step_idx, int):
             raise ValueError(f"step_idx must be an int or \"index\", got {step_idx!r}")
         if known_mel is not None and overlap_len > x_coarse.shape[1]:
             raise ValueError(f"overlap_len = {overlap_len} exceeds the {x_coarse.shape[1]} frames of x_coarse")
         x = self._refine_start(x_coarse, self._t_start(strength), noise, seed, seeds)
         return self._run(x, sem_features, times, step_idx, known_mel, overlap_len if known_mel is not None else 0, cfg_scale, noise_k,
-                         seed, x_lengths, sem_lengths, seeds, lms_rows=rows, return_intermediates=return_intermediates)
+                         seed, x_lengths, sem_lengths, seeds, lms_rows=rows, return_intermediates=return_intermediates, keep=keep)
+
+    @torch.no_grad()
+    def edit(self, mel_n: torch.Tensor, sem_features: torch.Tensor, regenerate, *, num_steps: int = 4, refine: Optional[str] = "dpmpp",
+             steps: Optional[int] = None, order: int = 2, strength: Optional[float] = None, cfg_scale: float = 1.0,
+             x_lengths: Optional[torch.Tensor] = None, sem_lengths: Optional[torch.Tensor] = None,
+             seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Re-synthesise stretches of an utterance and keep the rest (speech editing: ``sem_features`` are the edited utterance's
+        features, ``mel_n`` [B, T, n_mels] its normalised mel before the edit).  ``regenerate[b]``: half-open (start, end) frame
+        intervals of row b to synthesise anew (keep_mask's format); every other frame is kept, bitwise, with context on both sides.
+        The student sample (``num_steps``) under that mask, then the refinement under the same mask: ``refine="dpmpp"``
+        (inpaint_dpm_refine; ``steps`` 15, ``order``, ``strength`` 0.999 unless given), ``"ddim"`` (inpaint_teacher_refine; ``steps``
+        10, ``strength`` 0.2 unless given) or None (the student sample is returned).  ``cfg_scale`` guides the refinement.
+        ValueError for another ``refine``, before any launch."""
+        if refine not in SOLVERS + (None,):
+            raise ValueError(f"refine must be one of {SOLVERS} or None, got {refine!r}")
+        B, T, M = mel_n.shape
+        keep = ~self.keep_mask(B, T, regenerate, mel_n.device)
+        if refine == "dpmpp":  # (the refinement's own argument errors, before the student sample runs)
+            strength, steps = 0.999 if strength is None else strength, 15 if steps is None else steps
+            self.dpm_plan(strength, steps, order)
+        elif refine == "ddim":
+            strength, steps = 0.2 if strength is None else strength, 10 if steps is None else steps
+            self._t_start(strength)
+        kw = dict(x_lengths=x_lengths, sem_lengths=sem_lengths, seeds=seeds, keep=keep)
+        x = self.inpaint_student_sample((B, T, M), sem_features, mel_n, 0, num_steps, **kw)
+        if refine == "dpmpp":
+            return self.inpaint_dpm_refine(x, sem_features, mel_n, 0, strength, steps, order, cfg_scale, **kw)
+        if refine == "ddim":
+            return self.inpaint_teacher_refine(x, sem_features, mel_n, 0, strength, steps, cfg_scale, **kw)
+        return x
 
     @staticmethod
     def latent_slices(n_chunks: int, hop_samples: int, chunk_samples: int, sample_rate: int) -> List[tuple]:

@@ -171,6 +171,10 @@ _ABI = {
                                            vp, vp, vp, vp)),
     "edtts_sample_inpaint_multistep_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, i32, vp, u64, f32,
                                                      vp, vp, vp, vp, vp, vp, vp)),
+    "edtts_sample_inpaint_mask_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, vp, vp, u64, f32, vp,
+                                                vp, vp, vp, vp)),
+    "edtts_sample_inpaint_multistep_mask_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, vp, vp, u64,
+                                                          f32, vp, vp, vp, vp, vp, vp, vp)),
     "edtts_dsconv_scratch_floats": (_STATUS, (i32, i32, i32, i32, i32, i32, i32, p_sz)),
     "edtts_dsconv_forward": (_STATUS, (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp)),
     "edtts_mel_to_spec": (_STATUS, (vp, vp, vp, vp, i32, i32, i32, i32, vp, vp)),
@@ -534,28 +538,33 @@ def sample_inpaint(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Tenso
                    step_all: torch.Tensor, coefs: Optional[Sequence[float]], known_mel: Optional[torch.Tensor], overlap_len: int,
                    noise_k: Optional[torch.Tensor], seed: int, cfg_scale: float, v_uncond: Optional[torch.Tensor],
                    t_len: Optional[torch.Tensor] = None, s_len: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None,
-                   lms_rows: Optional[Sequence[Sequence[float]]] = None, want_intermediates: bool = False):
+                   lms_rows: Optional[Sequence[Sequence[float]]] = None, want_intermediates: bool = False,
+                   keep: Optional[torch.Tensor] = None):
     """The in-painting samplers, in place on x [B, T, n_mels]: edtts_sample_inpaint_len with `coefs` (4 floats per step, flat), or with
     `lms_rows` (8 floats per step; `coefs` is not read: None) edtts_sample_inpaint_multistep_len.  t_all / step_all: device int64
-    [num_steps]; t_len / s_len / seeds: device int64 [B] or None.  Returns (x, x0_all): every step's x0 [num_steps, B, T, n_mels]
-    when lms_rows and want_intermediates, else None."""
+    [num_steps]; t_len / s_len / seeds: device int64 [B] or None.  With `keep` (device uint8 [B, T]; known_mel [B, T, n_mels], noise_k
+    [num_steps, B, T, n_mels], overlap_len not read) the *_mask_len twin of either.  Returns (x, x0_all): every step's x0
+    [num_steps, B, T, n_mels] when lms_rows and want_intermediates, else None."""
     B, T, M = x.shape
     n = t_all.numel()
     f = torch.float32
     cf = (C.c_float * (4 * n))(*coefs) if lms_rows is None else (C.c_float * (8 * n))(*[float(v) for row in lms_rows for v in row])
     args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), None if workspace_uncond is None else workspace_uncond.data_ptr(),
             B, T, sem_features.shape[1], _dev_ptr(sem_features, f, "sem_features"), _dev_ptr(zero_features, f, "zeros"), _dev_ptr(x, f, "x"),
-            n, t_all.data_ptr(), step_all.data_ptr(), cf, _dev_ptr(known_mel, f, "known_mel"), int(overlap_len),
+            n, t_all.data_ptr(), step_all.data_ptr(), cf, _dev_ptr(known_mel, f, "known_mel"),
+            int(overlap_len) if keep is None else _dev_ptr(keep, torch.uint8, "keep"),
             _dev_ptr(noise_k, f, "noise_k"), _u64(seed), float(cfg_scale),
             None if v_uncond is None else v_uncond.data_ptr(), _dev_ptr(t_len, torch.int64, "x_lengths"),
             _dev_ptr(s_len, torch.int64, "sem_lengths"), _dev_ptr(seeds, torch.int64, "seeds"))
     x0_all = None
+    L = lib()
     if lms_rows is None:
-        lib().edtts_sample_inpaint_len(*args, _stream(x.device))
+        (L.edtts_sample_inpaint_len if keep is None else L.edtts_sample_inpaint_mask_len)(*args, _stream(x.device))
     else:
         hist = torch.empty((2, B, T, M), dtype=f, device=x.device)
         x0_all = torch.empty((n, B, T, M), dtype=f, device=x.device) if want_intermediates else None
-        lib().edtts_sample_inpaint_multistep_len(*args, hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), _stream(x.device))
+        fn = L.edtts_sample_inpaint_multistep_len if keep is None else L.edtts_sample_inpaint_multistep_mask_len
+        fn(*args, hist.data_ptr(), None if x0_all is None else x0_all.data_ptr(), _stream(x.device))
     check_indices(workspace)
     return x, x0_all
 

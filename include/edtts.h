@@ -507,6 +507,39 @@ int edtts_sample_inpaint_multistep_len(const EdttsDims* dims, const void* packed
                                        const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, float* hist, float* x0_all,
                                        void* stream);
 
+/* ---- in-painting anywhere: the two samplers above with a per-frame mask in place of the known prefix ------------------------------
+ * The reference's rule does not depend on where the known frames sit (inference_pipeline.py:117-123,135-136: x[mask] = q_sample(
+ * known, t) before every step, x[mask] = known after the last); its pipeline only ever fills a prefix of the mask.  These entry
+ * points take the whole mask: the arguments of edtts_sample_inpaint_len / edtts_sample_inpaint_multistep_len, except that
+ *     known_mel is [B,T,n_mels]                  (read at kept frames only),
+ *     keep      is device uint8 [B,T] in place of overlap_len: non-zero = the frame is known,
+ *     noise_k   is [num_steps,B,T,n_mels] or NULL -> Philox  (read at kept frames only).
+ * keep and known_mel are both given or both NULL (one without the other: EDTTS_ERR_ARG); both NULL is the plain sampler.  There is no
+ * minimum utterance length: t_len[b] in [1, T] as everywhere, and a kept frame at or past t_len[b] is ignored (those frames come out
+ * 0).  Each step's q_sample and the final force are one small launch each (k_inpaint_inject_mask); the multistep tails carry no blend.
+ * The whole call is one chain on the caller's stream and makes no host-to-device copy, so it can be captured.
+ * Philox draws: with seeds, (seeds[b], 0x20000 + step, element f*n_mels + m within the row); without, (seed, 0x20000 + step, element
+ * b*T*n_mels + f*n_mels + m).  Contract:
+ *   1. keep[b][f] = (f < ov) with seeds given is bitwise the prefix entry point called with known_mel[:, :ov] and overlap_len = ov
+ *      (lengths, guidance and every solver mode included); without seeds this holds for B = 1.
+ *   2. Kept frames below t_len[b] come out bitwise known_mel.
+ *   3. An all-zero keep is bitwise the call with known_mel = keep = NULL; an all-ones keep returns known_mel.
+ *   4. known_mel and noise_k are not read at frames that are not kept or lie past t_len[b] (NaN there changes no bit).
+ *   5. Row b of a ragged batch with seeds is bitwise the call on utterance b alone (its first t_len[b] frames, seed = seeds[b]).
+ *   6. Two calls give equal results.
+ * The entry points above are untouched: their results are bit for bit what they were. */
+int edtts_sample_inpaint_mask_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B, int T, int S,
+                                  const float* sem_features, const float* zero_features, float* x, int num_steps,
+                                  const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                                  const uint8_t* keep, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                                  const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, void* stream);
+int edtts_sample_inpaint_multistep_mask_len(const EdttsDims* dims, const void* packed, void* workspace, void* workspace_uncond, int B,
+                                            int T, int S, const float* sem_features, const float* zero_features, float* x, int num_steps,
+                                            const int64_t* t_all, const int64_t* step_all, const float* coef_host, const float* known_mel,
+                                            const uint8_t* keep, const float* noise_k, uint64_t seed, float cfg_scale, float* v_uncond,
+                                            const int64_t* t_len, const int64_t* s_len, const uint64_t* seeds, float* hist, float* x0_all,
+                                            void* stream);
+
 /* ---- depthwise-separable Conv1d  (layers/conv.py:25-64, DepthwiseSeparableConv.forward) -----------------
  * Standalone exported layer (named by the north star; the decoder never calls it).
  * x [B,C_in,T] channel-first; dw [C_in,k] depthwise taps (Conv1d(k, stride, padding = k/2, groups = C_in, no bias),
