@@ -514,15 +514,37 @@ struct MmStream {
   MmStream(hipStream_t s, bool b = false) : st(s), bf16(b) {}
   operator hipStream_t() const { return st; }
 };
+// The shape of an attention call: row width (all heads), heads, head_dim, and whether the bf16 attention (EDTTS_ATTN_BF16) runs it.
+// The decoder's is its layout's; HuBERT's fp32 forward brings its own.
+struct AttnShape {
+  int H, HEADS, DH;
+  bool att16;
+  AttnShape(int h, int heads, int dh, bool a16 = false) : H(h), HEADS(heads), DH(dh), att16(a16) {}
+  AttnShape(const Layout& lo) : H(lo.H), HEADS(lo.HEADS), DH(lo.DH), att16(lo.ATT16 != 0) {}
+};
 
 struct GenericLauncher {
   static int set_attrs() { return EDTTS_OK; }  // (no kernel here needs more than 64 KiB of LDS)
 
   static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
   static unsigned grid_1d(size_t n) { const size_t nb = (n + 255) / 256; return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb)); }
+  // The instances of a `linear` site's product that exist, over (bf16 products, dropout, bf16 loads, bf16 stores) -- gemm instantiates
+  // no other and refuses what falls outside: the dropout epilogue belongs to EPI_SWIGLU and EPI_RESID; bf16 rows (Layout::TAPE16) are
+  // k_gen_gemm16's alone, stored by EPI_BIAS and EPI_SWIGLU and loaded by EPI_RESID -- exactly the sites that the narrowed buffers have
+  static constexpr bool drop_epi(int epi) { return epi == edtts_gen::EPI_SWIGLU || epi == edtts_gen::EPI_RESID; }
+  template <int EPI, bool MM16, bool DROP, class TX, class TY>
+  static constexpr bool gemm_instance() {
+    constexpr bool xh = std::is_same<TX, __bf16>::value, yh = std::is_same<TY, __bf16>::value;
+    return (!DROP || drop_epi(EPI)) && (!xh || (MM16 && EPI == edtts_gen::EPI_RESID)) &&
+           (!yh || (MM16 && (EPI == edtts_gen::EPI_BIAS || EPI == edtts_gen::EPI_SWIGLU)));
+  }
+  template <int EPI, bool MM16, bool DROP, class TX, class TY>
+  static constexpr auto gemm_kernel() {
+    if constexpr (MM16) return &edtts_gen::k_gen_gemm16<EPI, DROP, TX, TY>;
+    else return &edtts_gen::k_gen_gemm<EPI, DROP>;
+  }
   // dr non-null (EPI_SWIGLU / EPI_RESID): the dropout instantiation, its epilogue masked with *dr
-  // X.h / Y.h (Layout::TAPE16): the bf16-load / bf16-store instantiation of k_gen_gemm16 -- there is one for exactly the sites that
-  // the narrowed buffers have (Y of EPI_BIAS and EPI_SWIGLU, X of EPI_RESID); anything else is an error, never a conversion
+  // X.h / Y.h (Layout::TAPE16): the bf16-load / bf16-store instantiation; one that gemm_instance lacks is an error, never a conversion
   template <int EPI>
   static int gemm(MmStream st, Act X, int ldx, const float* W, const float* bias, Act Y, int ldy, int M, int N, int K,
                   const float* pe = nullptr, int T = 1, const edtts::DropArgs* dr = nullptr) {
@@ -536,43 +558,22 @@ struct GenericLauncher {
     const int nb = EPI == EPI_SWIGLU ? kGBN / 2 : kGBN;
     a.dr = dr ? *dr : edtts::DropArgs{};
     const dim3 grid((M + kGBM - 1) / kGBM, (N + nb - 1) / nb);
-    if (X.h || Y.h) {
-      if (!st.bf16) return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: a bf16 activation buffer needs the bf16 products (EDTTS_MATMUL_BF16)");
-      if constexpr (EPI == EPI_BIAS) {
-        if (!X.h && Y.h) {
-          hipLaunchKernelGGL((k_gen_gemm16<EPI_BIAS, false, float, __bf16>), grid, dim3(256), 0, st.st, a);
-          LAUNCH_CHECK("k_gen_gemm16");
+    if ((X.h || Y.h) && !st.bf16)
+      return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: a bf16 activation buffer needs the bf16 products (EDTTS_MATMUL_BF16)");
+    return with_flag(st.bf16, [&](auto mm) { return with_flag(dr && drop_epi(EPI), [&](auto dropping) {
+      return with_elem(X.h, [&](auto ex) { return with_elem(Y.h, [&](auto ey) -> int {
+        using TX = typename decltype(ex)::type;
+        using TY = typename decltype(ey)::type;
+        constexpr bool MM16 = decltype(mm)::value, DROP = decltype(dropping)::value;
+        if constexpr (gemm_instance<EPI, MM16, DROP, TX, TY>()) {
+          hipLaunchKernelGGL((gemm_kernel<EPI, MM16, DROP, TX, TY>()), grid, dim3(256), 0, st.st, a);
+          LAUNCH_CHECK("k_gen_gemm");
           return EDTTS_OK;
+        } else {
+          return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: no product with epilogue %d reads bf16=%d and stores bf16=%d", EPI, (int)X.h, (int)Y.h);
         }
-      } else if constexpr (EPI == EPI_SWIGLU) {
-        if (!X.h && Y.h) {
-          if (dr) hipLaunchKernelGGL((k_gen_gemm16<EPI_SWIGLU, true, float, __bf16>), grid, dim3(256), 0, st.st, a);
-          else hipLaunchKernelGGL((k_gen_gemm16<EPI_SWIGLU, false, float, __bf16>), grid, dim3(256), 0, st.st, a);
-          LAUNCH_CHECK("k_gen_gemm16");
-          return EDTTS_OK;
-        }
-      } else if constexpr (EPI == EPI_RESID) {
-        if (X.h && !Y.h) {
-          if (dr) hipLaunchKernelGGL((k_gen_gemm16<EPI_RESID, true, __bf16, float>), grid, dim3(256), 0, st.st, a);
-          else hipLaunchKernelGGL((k_gen_gemm16<EPI_RESID, false, __bf16, float>), grid, dim3(256), 0, st.st, a);
-          LAUNCH_CHECK("k_gen_gemm16");
-          return EDTTS_OK;
-        }
-      }
-      return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: no product with epilogue %d reads bf16=%d and stores bf16=%d", EPI, (int)X.h, (int)Y.h);
-    }
-    if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
-      if (dr) {
-        if (st.bf16) hipLaunchKernelGGL((k_gen_gemm16<EPI, true>), grid, dim3(256), 0, st.st, a);
-        else hipLaunchKernelGGL((k_gen_gemm<EPI, true>), grid, dim3(256), 0, st.st, a);
-        LAUNCH_CHECK("k_gen_gemm");
-        return EDTTS_OK;
-      }
-    }
-    if (st.bf16) hipLaunchKernelGGL(k_gen_gemm16<EPI>, grid, dim3(256), 0, st.st, a);
-    else hipLaunchKernelGGL(k_gen_gemm<EPI>, grid, dim3(256), 0, st.st, a);
-    LAUNCH_CHECK("k_gen_gemm");
-    return EDTTS_OK;
+      }); });
+    }); });
   }
   template <int MODE>
   static int norm(hipStream_t st, const float* x, float* y, int rows, int W, const float* w, const float* b, float eps,
@@ -582,47 +583,33 @@ struct GenericLauncher {
     LAUNCH_CHECK("k_gen_norm");
     return EDTTS_OK;
   }
+  // k_gen_attn (a wave = 16 queries) or, for the bf16 attention, k_gen_attn16 (four waves = 64 queries), which alone reads bf16 rows
+  template <int DT, bool ATT16, bool DROP, class TQ>
+  static constexpr auto attn_kernel() {
+    if constexpr (ATT16) return &edtts_gen::k_gen_attn16<DT, DROP, TQ>;
+    else return &edtts_gen::k_gen_attn<DT, DROP>;
+  }
   // (q, k, v of one element type: fp32, or bf16 with Layout::TAPE16, which only the bf16 attention reads)
-  static int attn(hipStream_t st, const Layout& lo, int B, Act q, int ldq, Act k, Act v, int ldkv, float* o,
+  static int attn(hipStream_t st, const AttnShape& as, int B, Act q, int ldq, Act k, Act v, int ldkv, float* o,
                   int Tq, int Tk, int window, const int64_t* q_len, const int64_t* k_len, bool q_dbl, bool k_dbl, float* lse = nullptr,
                   const edtts::DropArgs* dr = nullptr) {
-    if (q.h != k.h || q.h != v.h || (q.h && !lo.ATT16))
+    if (q.h != k.h || q.h != v.h || (q.h && !as.att16))
       return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: bf16 q, k, v rows need the bf16 attention (EDTTS_ATTN_BF16), all three of them");
-    edtts_gen::AttnArgs a{q.p, k.p, v.p, o, ldq, ldkv, lo.H, Tq, Tk, lo.DH, window, 1.4426950408889634f / sqrtf((float)lo.DH), q_len, k_len,
+    edtts_gen::AttnArgs a{q.p, k.p, v.p, o, ldq, ldkv, as.H, Tq, Tk, as.DH, window, 1.4426950408889634f / sqrtf((float)as.DH), q_len, k_len,
                           (int)q_dbl, (int)k_dbl, lse, dr ? *dr : edtts::DropArgs{}};
-    if (lo.ATT16) {  // EDTTS_ATTN_BF16: the same arguments, 64 queries per block
-      const dim3 grid16((Tq + 63) / 64, lo.HEADS, B);
-      switch ((lo.DH + 15) / 16) {
-#define EDTTS_GEN_ATTN16(DT)                                                                                          \
-  case DT:                                                                                                            \
-    if (q.h) {                                                                                                        \
-      if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, true, __bf16>), grid16, dim3(256), 0, st, a);           \
-      else hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, false, __bf16>), grid16, dim3(256), 0, st, a);             \
-    } else if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn16<DT, true>), grid16, dim3(256), 0, st, a);              \
-    else hipLaunchKernelGGL(edtts_gen::k_gen_attn16<DT>, grid16, dim3(256), 0, st, a);                                \
-    break
-        EDTTS_GEN_ATTN16(1); EDTTS_GEN_ATTN16(2); EDTTS_GEN_ATTN16(3); EDTTS_GEN_ATTN16(4);
-        EDTTS_GEN_ATTN16(5); EDTTS_GEN_ATTN16(6); EDTTS_GEN_ATTN16(7); EDTTS_GEN_ATTN16(8);
-#undef EDTTS_GEN_ATTN16
-        default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
-      }
-      LAUNCH_CHECK("k_gen_attn16");
-      return EDTTS_OK;
-    }
-    const dim3 grid((Tq + 15) / 16, lo.HEADS, B);
-    switch ((lo.DH + 15) / 16) {
-#define EDTTS_GEN_ATTN(DT)                                                                        \
-  case DT:                                                                                        \
-    if (dr) hipLaunchKernelGGL((edtts_gen::k_gen_attn<DT, true>), grid, dim3(64), 0, st, a);     \
-    else hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a);                 \
-    break
-      EDTTS_GEN_ATTN(1); EDTTS_GEN_ATTN(2); EDTTS_GEN_ATTN(3); EDTTS_GEN_ATTN(4);
-      EDTTS_GEN_ATTN(5); EDTTS_GEN_ATTN(6); EDTTS_GEN_ATTN(7); EDTTS_GEN_ATTN(8);
-#undef EDTTS_GEN_ATTN
-      default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
-    }
-    LAUNCH_CHECK("k_gen_attn");
-    return EDTTS_OK;
+    const int qpb = as.att16 ? 64 : 16;  // queries per block: one wave each 16 of them
+    const dim3 grid((Tq + qpb - 1) / qpb, as.HEADS, B), block(4 * qpb);
+    return with_head_tiles<8>(as.DH, [&](auto dt) { return with_flag(as.att16, [&](auto a16) {
+      return with_flag(dr != nullptr, [&](auto dropping) { return with_elem(q.h, [&](auto eq) -> int {
+        using TQ = typename decltype(eq)::type;
+        constexpr bool ATT16 = decltype(a16)::value;
+        if constexpr (ATT16 || std::is_same<TQ, float>::value) {  // (bf16 rows without the bf16 attention: refused above)
+          hipLaunchKernelGGL((attn_kernel<decltype(dt)::value, ATT16, decltype(dropping)::value, TQ>()), grid, block, 0, st, a);
+          LAUNCH_CHECK("k_gen_attn");
+        }
+        return EDTTS_OK;
+      }); });
+    }); });
   }
 
   static int copy(hipStream_t st, float* dst, const float* src, size_t n) {

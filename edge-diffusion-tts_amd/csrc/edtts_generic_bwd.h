@@ -691,39 +691,73 @@ __global__ __launch_bounds__(256) void k_bwd_gelu_grad(float* du, const float* a
 // =========================================================================================================
 // the tape and the backward's scratch (offsets in floats)
 // =========================================================================================================
-// Layout::TAPE16 (EDTTS_TAPE_BF16): kv, qkv, qc and act hold __bf16 -- n elements take (n + 1) / 2 floats of the
+// Layout::TAPE16 (EDTTS_TAPE_BF16): the Narrowed members hold __bf16 -- n elements take (n + 1) / 2 floats of the
 // tape; their offsets still count floats (every region starts on a multiple of 64 floats = 256 bytes), their pitches elements.
+struct Narrowed {
+  size_t off;
+  bool h;  // this tape's elements are bf16
+};
+static Act operator+(const float* tp, const Narrowed& r) { return Act(tp + r.off, r.h); }
 struct TapeLayer {
-  size_t crp, kv;             // kv_down rows before kv_norm [B S][R]; K|V rows [B S][2H]
+  size_t crp;                 // kv_down rows before kv_norm [B S][R]
+  Narrowed kv;                // K|V rows [B S][2H]
   size_t h0, h1, h2;          // the residual stream entering norm1 / norm2 / norm3
-  size_t qkv, att1, lse1;     // self-attention: q|k|v rows, attention output, log-sum-exp [B][HEADS][T]
-  size_t qc, att2, lse2;      // cross-attention: query rows, attention output, log-sum-exp
-  size_t act;                 // value * silu(gate) [B T][FM H]
+  Narrowed qkv;               // self-attention: q|k|v rows ...
+  size_t att1, lse1;          // ... attention output, log-sum-exp [B][HEADS][T]
+  Narrowed qc;                // cross-attention: query rows ...
+  size_t att2, lse2;          // ... attention output, log-sum-exp
+  Narrowed act;               // value * silu(gate) [B T][FM H]
 };
 struct TrainTape {
-  size_t cond;  // AdaLN rows [B][L][2][2H] and, behind them, t_cond [B][H]
-  size_t ctx;   // context rows [B S][H]
+  size_t cond, tcond;  // AdaLN rows [B][L][2][2H] and, right behind them, t_cond [B][H]
+  size_t ctx;          // context rows [B S][H]
   TapeLayer layer[kMaxLayers];
-  size_t hL;    // the residual stream entering final_norm
+  size_t hL;           // the residual stream entering final_norm
   size_t total;
 };
-static void make_tape(const Layout& lo, int B, int T, int S, TrainTape* t) {
-  const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S, FH = (size_t)lo.FM * H;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
-  auto take16 = [&](size_t n) { return take(lo.TAPE16 ? (n + 1) / 2 : n); };  // a region the bit narrows: n elements
-  t->cond = take((size_t)B * lo.L * 4 * H + (size_t)B * H);
-  t->ctx = take(CS * H);
+// The tape's regions, stated once: f(which, layer, member, n) for each of them in tape order -- `which` its EDTTS_TAPE_* name, `layer`
+// its layer (-1: a whole-model member), `member` its place in *t, n its element count.  make_tape lays the tape out from it,
+// edtts_train_tape_region answers from it; the forward and the backward reach the regions through the members it filled.
+template <class Tape, class F>
+static void tape_regions(const Layout& lo, int B, int T, int S, Tape& t, F&& f) {
+  const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S;
+  f(EDTTS_TAPE_COND, -1, t.cond, (size_t)B * lo.L * 4 * H);
+  f(EDTTS_TAPE_TCOND, -1, t.tcond, (size_t)B * H);
+  f(EDTTS_TAPE_CTX, -1, t.ctx, CS * H);
   for (int l = 0; l < lo.L; ++l) {
-    TapeLayer& y = t->layer[l];
-    y.crp = take(CS * lo.R); y.kv = take16(CS * 2 * H);
-    y.h0 = take(M * H); y.h1 = take(M * H); y.h2 = take(M * H);
-    y.qkv = take16(M * 3 * H); y.att1 = take(M * H); y.lse1 = take(M * lo.HEADS);
-    y.qc = take16(M * H); y.att2 = take(M * H); y.lse2 = take(M * lo.HEADS);
-    y.act = take16(M * FH);
+    auto& y = t.layer[l];
+    f(EDTTS_TAPE_CRP, l, y.crp, CS * lo.R);
+    f(EDTTS_TAPE_KV, l, y.kv, CS * 2 * H);
+    f(EDTTS_TAPE_H0, l, y.h0, M * H);
+    f(EDTTS_TAPE_H1, l, y.h1, M * H);
+    f(EDTTS_TAPE_H2, l, y.h2, M * H);
+    f(EDTTS_TAPE_QKV, l, y.qkv, M * 3 * H);
+    f(EDTTS_TAPE_ATT1, l, y.att1, M * H);
+    f(EDTTS_TAPE_LSE1, l, y.lse1, M * lo.HEADS);
+    f(EDTTS_TAPE_QC, l, y.qc, M * H);
+    f(EDTTS_TAPE_ATT2, l, y.att2, M * H);
+    f(EDTTS_TAPE_LSE2, l, y.lse2, M * lo.HEADS);
+    f(EDTTS_TAPE_ACT, l, y.act, M * lo.FM * H);
   }
-  t->hL = take(M * H);
-  t->total = o;
+  f(EDTTS_TAPE_HL, -1, t.hL, M * H);
+}
+// a member at float offset o: the floats its n elements take
+static size_t tape_place(size_t& m, size_t o, size_t n, bool) { m = o; return n; }
+static size_t tape_place(Narrowed& m, size_t o, size_t n, bool t16) { m = Narrowed{o, t16}; return t16 ? (n + 1) / 2 : n; }
+// ... and back: its offset and the bytes of one element
+struct TapePlace {
+  size_t off;
+  int elem_bytes;
+};
+static TapePlace tape_place_of(size_t m) { return TapePlace{m, 4}; }
+static TapePlace tape_place_of(const Narrowed& m) { return TapePlace{m.off, m.h ? 2 : 4}; }
+static void make_tape(const Layout& lo, int B, int T, int S, TrainTape* t) {
+  size_t o = 0;
+  tape_regions(lo, B, T, S, *t, [&](int which, int, auto& m, size_t n) {
+    if (which != EDTTS_TAPE_TCOND) o = align64(o);  // (t_cond lies right behind the AdaLN rows)
+    o += tape_place(m, o, n, lo.TAPE16 != 0);
+  });
+  t->total = align64(o);
 }
 struct TrainScratch {
   size_t dh, xn, ga, gq, big, da, stat, delta, dkv, crn, dcr, dcp, dctx;
@@ -781,14 +815,13 @@ struct TrainLauncher {
     FwdBufs fb;
     fb.ctx = tp + tt.ctx;
     fb.hL = tp + tt.hL;
-    const bool t16 = c.lo.TAPE16 != 0;
     for (int l = 0; l < c.lo.L; ++l) {
       const TapeLayer& z = tt.layer[l];
       FwdLayerBufs& f = fb.layer[l];
-      f.crp = tp + z.crp; f.crn = c.wsb + c.ws.g_cr; f.kv = Act(tp + z.kv, t16);
-      f.qkv = Act(tp + z.qkv, t16); f.att1 = tp + z.att1; f.lse1 = tp + z.lse1;
-      f.qc = Act(tp + z.qc, t16); f.att2 = tp + z.att2; f.lse2 = tp + z.lse2;
-      f.act = Act(tp + z.act, t16);
+      f.crp = tp + z.crp; f.crn = c.wsb + c.ws.g_cr; f.kv = tp + z.kv;
+      f.qkv = tp + z.qkv; f.att1 = tp + z.att1; f.lse1 = tp + z.lse1;
+      f.qc = tp + z.qc; f.att2 = tp + z.att2; f.lse2 = tp + z.lse2;
+      f.act = tp + z.act;
       f.h0 = tp + z.h0; f.h1 = tp + z.h1; f.h2 = tp + z.h2;
     }
     StepTail tail;
@@ -799,26 +832,31 @@ struct TrainLauncher {
 
   // ---- backward helpers ----
   static bool al16(const void* p) { return G::al16(p); }
-  // (b16: B holds bf16 elements -- dW_down's X with Layout::TAPE16, the one such call)
+  // The instances of the backward's product that exist, over (bf16 products, accumulating, row lengths, bf16 operand B): B holds bf16
+  // elements in one call only -- dW_down's X with Layout::TAPE16 -- which k_bwd_gemm16 serves, not accumulating
+  template <bool MM16, int ACC, class TB>
+  static constexpr bool bgemm_instance() { return std::is_same<TB, float>::value || (MM16 && !ACC); }
+  template <bool MM16, int ACC, bool LEN, class TB>
+  static constexpr auto bgemm_kernel() {
+    if constexpr (MM16) return &edtts_bwd::k_bwd_gemm16<ACC, LEN, TB>;
+    else return &edtts_bwd::k_bwd_gemm<ACC, LEN>;
+  }
   static int bgemm(MmStream st, edtts_bwd::BGemmArgs a, int slabs, bool acc, bool b16 = false) {
     const dim3 grid((a.M + 63) / 64, (a.N + 63) / 64, slabs);
-    if (b16) {
-      if (!st.bf16 || acc) return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: a bf16 operand needs the bf16 products, not accumulating");
-      if (a.len) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, true, __bf16>), grid, dim3(256), 0, st.st, a);
-      else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, false, __bf16>), grid, dim3(256), 0, st.st, a);
-    } else if (st.bf16) {
-      if (a.len) {
-        if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<1, true>), grid, dim3(256), 0, st.st, a);
-        else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm16<0, true>), grid, dim3(256), 0, st.st, a);
-      } else if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm16<1>, grid, dim3(256), 0, st.st, a);
-      else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm16<0>, grid, dim3(256), 0, st.st, a);
-    } else if (a.len) {
-      if (acc) hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<1, true>), grid, dim3(256), 0, st.st, a);
-      else hipLaunchKernelGGL((edtts_bwd::k_bwd_gemm<0, true>), grid, dim3(256), 0, st.st, a);
-    } else if (acc) hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<1>, grid, dim3(256), 0, st.st, a);
-    else hipLaunchKernelGGL(edtts_bwd::k_bwd_gemm<0>, grid, dim3(256), 0, st.st, a);
-    LAUNCH_CHECK("k_bwd_gemm");
-    return EDTTS_OK;
+    return with_flag(st.bf16, [&](auto mm) { return with_flag(acc, [&](auto accum) {
+      return with_flag(a.len != nullptr, [&](auto lens) { return with_elem(b16, [&](auto eb) -> int {
+        using TB = typename decltype(eb)::type;
+        constexpr bool MM16 = decltype(mm)::value;
+        constexpr int ACC = decltype(accum)::value;
+        if constexpr (bgemm_instance<MM16, ACC, TB>()) {
+          hipLaunchKernelGGL((bgemm_kernel<MM16, ACC, decltype(lens)::value, TB>()), grid, dim3(256), 0, st.st, a);
+          LAUNCH_CHECK("k_bwd_gemm");
+          return EDTTS_OK;
+        } else {
+          return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: a bf16 operand needs the bf16 products, not accumulating");
+        }
+      }); });
+    }); });
   }
   static int slabsum(hipStream_t st, const float* part, float* out, size_t n, int ns, size_t pstride, int ny = 1, size_t ostride = 0, bool acc = false) {
     hipLaunchKernelGGL(edtts_bwd::k_bwd_slabsum, dim3(G::grid_1d(n), ny), dim3(256), 0, st, part, out, n, ns, pstride, ostride, (int)acc);
@@ -865,6 +903,14 @@ struct TrainLauncher {
     LAUNCH_CHECK("k_bwd_colsum");
     return slabsum(st, part, out, (size_t)N, ns, (size_t)N);
   }
+  // The gradients of one `linear` site Y[M][N] = X[M][K] W[N][K]^T + b from dY (pitch ldy; X, dW and dX are dense): the bias column
+  // sum -> db, dW = dY^T X and dX (+)= dY W, launched in that order; a null destination skips its launch.
+  static int linear_bwd(MmStream st, const float* dY, int ldy, Act X, const float* W, int M, int N, int K, float* db, float* dW, float* dX,
+                        float* part, RowLens rl = RowLens{}, bool acc = false, bool wT = false) {
+    TRY_G(colsum(st, dY, ldy, M, N, db, part, rl));
+    TRY_G(dw(st, dY, ldy, X, K, M, N, K, dW, part, rl));
+    return dX ? dx(st, dY, ldy, W, M, N, K, dX, K, acc, wT, rl) : EDTTS_OK;
+  }
   // RMSNorm / LayerNorm backward: dx (+)= ..., gain gradient -> dgain (null: skipped), LayerNorm bias gradient -> dbias,
   // AdaLN (dscale | dshift) -> dmod[b dmod_bstride ...] (null: skipped)
   template <int MODE>
@@ -883,65 +929,45 @@ struct TrainLauncher {
     if (dmod) TRY_G(slabsum(st, part + W, dmod, (size_t)2 * W, cpb, (size_t)3 * W, nb, (size_t)dmod_bstride));
     return EDTTS_OK;
   }
+  // k_bwd_attn_dq / _dkv (a wave = 16 queries / keys) or, for the bf16 attention, their 64-row twins, which alone read bf16 rows
+  template <int DT, bool ATT16, bool DROP, class TQ>
+  static constexpr auto attn_dq_kernel() {
+    if constexpr (ATT16) return &edtts_bwd::k_bwd_attn_dq16<DT, DROP, TQ>;
+    else return &edtts_bwd::k_bwd_attn_dq<DT, DROP>;
+  }
+  template <int DT, bool ATT16, bool DROP, class TQ>
+  static constexpr auto attn_dkv_kernel() {
+    if constexpr (ATT16) return &edtts_bwd::k_bwd_attn_dkv16<DT, DROP, TQ>;
+    else return &edtts_bwd::k_bwd_attn_dkv<DT, DROP>;
+  }
   // gradients of one attention call: dq, dk, dv from q, k, v, the output o, its gradient dO and the tape's log-sum-exp
   // (q, k, v of one element type, as GenericLauncher::attn)
-  static int attn_bwd(hipStream_t st, const Layout& lo, int B, Act q, int ldq, Act k, Act v, int ldkv, const float* o,
+  static int attn_bwd(hipStream_t st, const AttnShape& as, int B, Act q, int ldq, Act k, Act v, int ldkv, const float* o,
                       const float* dO, const float* lse, float* delta, float* dq, int lddq, float* dk, float* dv, int lddkv, int Tq, int Tk,
                       int window, const DropArgs* dr = nullptr, const int64_t* q_len = nullptr, const int64_t* k_len = nullptr) {
-    if (q.h != k.h || q.h != v.h || (q.h && !lo.ATT16))
+    if (q.h != k.h || q.h != v.h || (q.h && !as.att16))
       return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: bf16 q, k, v rows need the bf16 attention (EDTTS_ATTN_BF16), all three of them");
-    const size_t n = (size_t)B * lo.HEADS * Tq;
-    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, lo.HEADS, lo.DH, lo.H, q_len);
+    const size_t n = (size_t)B * as.HEADS * Tq;
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_delta, dim3(G::grid_1d(n)), dim3(256), 0, st, o, dO, delta, B, Tq, as.HEADS, as.DH, as.H, q_len);
     LAUNCH_CHECK("k_bwd_attn_delta");
-    const float sn = 1.0f / sqrtf((float)lo.DH);
-    edtts_bwd::AttnBwdArgs a{q.p, k.p, v.p, dO, lse, delta, dq, dk, dv, ldq, ldkv, lo.H, lddq, lddkv, Tq, Tk, lo.DH, window,
-                             1.4426950408889634f / sqrtf((float)lo.DH), sn, dr ? *dr : DropArgs{}, q_len, k_len};
-    if (lo.ATT16) {  // EDTTS_ATTN_BF16: the same arguments, 64 queries / keys per block
-      const dim3 gq16((Tq + 63) / 64, lo.HEADS, B), gk16((Tk + 63) / 64, lo.HEADS, B);
-      switch ((lo.DH + 15) / 16) {
-#define EDTTS_BWD_ATTN16(DT)                                                                        \
-  case DT:                                                                                          \
-    if (q.h && dr) {                                                                                \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, true, __bf16>), gq16, dim3(256), 0, st, a);  \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, true, __bf16>), gk16, dim3(256), 0, st, a); \
-    } else if (q.h) {                                                                               \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, false, __bf16>), gq16, dim3(256), 0, st, a);  \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, false, __bf16>), gk16, dim3(256), 0, st, a); \
-    } else if (dr) {                                                                                \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq16<DT, true>), gq16, dim3(256), 0, st, a);        \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv16<DT, true>), gk16, dim3(256), 0, st, a);       \
-    } else {                                                                                        \
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dq16<DT>, gq16, dim3(256), 0, st, a);                \
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dkv16<DT>, gk16, dim3(256), 0, st, a);               \
-    }                                                                                               \
-    break
-        EDTTS_BWD_ATTN16(1); EDTTS_BWD_ATTN16(2); EDTTS_BWD_ATTN16(3); EDTTS_BWD_ATTN16(4);
-        EDTTS_BWD_ATTN16(5); EDTTS_BWD_ATTN16(6); EDTTS_BWD_ATTN16(7); EDTTS_BWD_ATTN16(8);
-#undef EDTTS_BWD_ATTN16
-        default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
-      }
-      LAUNCH_CHECK("k_bwd_attn16");
-      return EDTTS_OK;
-    }
-    const dim3 gq((Tq + 15) / 16, lo.HEADS, B), gk((Tk + 15) / 16, lo.HEADS, B);
-    switch ((lo.DH + 15) / 16) {
-#define EDTTS_BWD_ATTN(DT)                                                                      \
-  case DT:                                                                                      \
-    if (dr) {                                                                                   \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dq<DT, true>), gq, dim3(64), 0, st, a);         \
-      hipLaunchKernelGGL((edtts_bwd::k_bwd_attn_dkv<DT, true>), gk, dim3(64), 0, st, a);        \
-    } else {                                                                                    \
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dq<DT>, gq, dim3(64), 0, st, a);                 \
-      hipLaunchKernelGGL(edtts_bwd::k_bwd_attn_dkv<DT>, gk, dim3(64), 0, st, a);                \
-    }                                                                                           \
-    break
-      EDTTS_BWD_ATTN(1); EDTTS_BWD_ATTN(2); EDTTS_BWD_ATTN(3); EDTTS_BWD_ATTN(4);
-      EDTTS_BWD_ATTN(5); EDTTS_BWD_ATTN(6); EDTTS_BWD_ATTN(7); EDTTS_BWD_ATTN(8);
-#undef EDTTS_BWD_ATTN
-      default: return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > 128", lo.DH);
-    }
-    LAUNCH_CHECK("k_bwd_attn");
-    return EDTTS_OK;
+    const float sn = 1.0f / sqrtf((float)as.DH);
+    edtts_bwd::AttnBwdArgs a{q.p, k.p, v.p, dO, lse, delta, dq, dk, dv, ldq, ldkv, as.H, lddq, lddkv, Tq, Tk, as.DH, window,
+                             1.4426950408889634f / sqrtf((float)as.DH), sn, dr ? *dr : DropArgs{}, q_len, k_len};
+    const int rpb = as.att16 ? 64 : 16;  // queries / keys per block: one wave each 16 of them
+    const dim3 gq((Tq + rpb - 1) / rpb, as.HEADS, B), gk((Tk + rpb - 1) / rpb, as.HEADS, B), block(4 * rpb);
+    return with_head_tiles<8>(as.DH, [&](auto dt) { return with_flag(as.att16, [&](auto a16) {
+      return with_flag(dr != nullptr, [&](auto dropping) { return with_elem(q.h, [&](auto eq) -> int {
+        using TQ = typename decltype(eq)::type;
+        constexpr int DT = decltype(dt)::value;
+        constexpr bool ATT16 = decltype(a16)::value, DROP = decltype(dropping)::value;
+        if constexpr (ATT16 || std::is_same<TQ, float>::value) {  // (bf16 rows without the bf16 attention: refused above)
+          hipLaunchKernelGGL((attn_dq_kernel<DT, ATT16, DROP, TQ>()), gq, block, 0, st, a);
+          hipLaunchKernelGGL((attn_dkv_kernel<DT, ATT16, DROP, TQ>()), gk, block, 0, st, a);
+          LAUNCH_CHECK("k_bwd_attn");
+        }
+        return EDTTS_OK;
+      }); });
+    }); });
   }
 
   // The backward.  Reads the tape, the blob and its arguments; every buffer it writes is in `sc` (its own scratch) or a gradient.
@@ -955,7 +981,6 @@ struct TrainLauncher {
     // Per-utterance lengths: tr / sr mask every contraction over decoder / context rows and zero the dead
     // rows of every dX; the elementwise steps in between run on all rows (what they make of a dead row is never loaded again).
     const RowLens tr{ln.t, T}, sr{ln.s, S};
-    auto T16 = [&](size_t off) { return Act(tp + off, lo.TAPE16 != 0); };  // one of the tape's four narrowed regions (make_tape)
     const int M = B * T, CS = B * S, H = lo.H, R = lo.R, FH = lo.FM * lo.H, MEL = lo.MEL, L = lo.L;
     float *dh = sc + ss.dh, *xn = sc + ss.xn, *ga = sc + ss.ga, *gq = sc + ss.gq, *big = sc + ss.big, *da = sc + ss.da;
     float *stat = sc + ss.stat, *delta = sc + ss.delta, *dkv = sc + ss.dkv, *crn = sc + ss.crn, *dcr = sc + ss.dcr, *dcp = sc + ss.dcp;
@@ -968,8 +993,7 @@ struct TrainLauncher {
     // out_proj and final_norm
     TRY_G(colsum(st, d_eps, MEL, M, MEL, GG(G_OUT_B), part, tr));
     TRY_G(G::norm<NORM_LAYER>(st, tp + tt.hL, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
-    TRY_G(dw(st, d_eps, MEL, xn, H, M, MEL, H, GG(G_OUT_W), part, tr));
-    TRY_G(dx(st, d_eps, MEL, blob + lo.s_outp, M, MEL, H, ga, H, false, false, tr));
+    TRY_G(linear_bwd(st, d_eps, MEL, xn, blob + lo.s_outp, M, MEL, H, nullptr, GG(G_OUT_W), ga, part, tr));  // (its bias: summed above)
     TRY_G(norm_bwd<NORM_LAYER>(st, tp + tt.hL, ga, dh, false, M, H, T, blob + lo.fnw, 1e-5f, nullptr, 0, stat, part, GG(G_FN_W), GG(G_FN_B),
                                nullptr, 0, ln.t));
     for (int l = L - 1; l >= 0; --l) {
@@ -988,9 +1012,7 @@ struct TrainLauncher {
         LAUNCH_CHECK("k_bwd_drop_rows");
         dd = gq;
       }
-      TRY_G(colsum(st, dd, H, M, H, W(L_DOWN_B), part, tr));
-      TRY_G(dw(st, dd, H, T16(z.act), FH, M, H, FH, W(L_DOWN_W), part, tr));
-      TRY_G(dx(st, dd, H, blob + y.g_down, M, H, FH, da, FH, false, false, tr));
+      TRY_G(linear_bwd(st, dd, H, tp + z.act, blob + y.g_down, M, H, FH, W(L_DOWN_B), W(L_DOWN_W), da, part, tr));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h2, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cb));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_up, blob + y.up_b, big, 2 * FH, M, 2 * FH, H));
       if (drop)
@@ -999,50 +1021,37 @@ struct TrainLauncher {
       else
         hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu, dim3(G::grid_1d((size_t)M * FH)), dim3(256), 0, st, big, da, (size_t)M, FH);
       LAUNCH_CHECK("k_bwd_swiglu");
-      TRY_G(colsum(st, big, 2 * FH, M, 2 * FH, W(L_UP_B), part, tr));
-      TRY_G(dw(st, big, 2 * FH, xn, H, M, 2 * FH, H, W(L_UP_W), part, tr));
-      TRY_G(dx(st, big, 2 * FH, blob + y.g_up, M, 2 * FH, H, ga, H, false, false, tr));
+      TRY_G(linear_bwd(st, big, 2 * FH, xn, blob + y.g_up, M, 2 * FH, H, W(L_UP_B), W(L_UP_W), ga, part, tr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h2, ga, dh, true, M, H, T, blob + y.n3w, 1e-6f, cond_row + l * row + 2 * H, cb, stat, part, W(L_N3_W),
                                nullptr, dmod + l * row + 2 * H, cb, ln.t));
       // cross-attention branch: h2 = h1 + att2 Wop^T
-      TRY_G(dw(st, dh, H, tp + z.att2, H, M, H, H, W(L_OP_W), part, tr));
-      TRY_G(dx(st, dh, H, blob + y.g_op, M, H, H, ga, H, false, false, tr));
-      TRY_G(attn_bwd(st, lo, B, T16(z.qc), H, T16(z.kv), T16(z.kv) + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
+      TRY_G(linear_bwd(st, dh, H, tp + z.att2, blob + y.g_op, M, H, H, nullptr, W(L_OP_W), ga, part, tr));
+      TRY_G(attn_bwd(st, lo, B, tp + z.qc, H, tp + z.kv, (tp + z.kv) + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
                      S, -1, D(DROP_CROSS), ln.t, ln.s));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h1, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
-      TRY_G(dw(st, gq, H, xn, H, M, H, H, W(L_QP_W), part, tr));
-      TRY_G(dx(st, gq, H, blob + y.g_qp, M, H, H, ga, H, false, false, tr));
+      TRY_G(linear_bwd(st, gq, H, xn, blob + y.g_qp, M, H, H, nullptr, W(L_QP_W), ga, part, tr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h1, ga, dh, true, M, H, T, blob + y.n2w, 1e-6f, nullptr, 0, stat, part, W(L_N2_W), nullptr, nullptr, 0, ln.t));
       // ... and its context chain: context -> kv_down -> kv_norm -> kv_up -> K|V
       TRY_G(G::norm<NORM_RMS>(st, tp + z.crp, crn, CS, R, blob + y.kvn, nullptr, 1e-6f));
-      TRY_G(dw(st, dkv, 2 * H, crn, R, CS, 2 * H, R, W(L_KVU_W), part, sr));
-      TRY_G(dx(st, dkv, 2 * H, blob + y.kvu, CS, 2 * H, R, dcr, R, false, false, sr));
+      TRY_G(linear_bwd(st, dkv, 2 * H, crn, blob + y.kvu, CS, 2 * H, R, nullptr, W(L_KVU_W), dcr, part, sr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.crp, dcr, dcp, false, CS, R, S, blob + y.kvn, 1e-6f, nullptr, 0, stat, part, W(L_KVN_W), nullptr,
                                nullptr, 0, ln.s));
-      TRY_G(dw(st, dcp, R, tp + tt.ctx, H, CS, R, H, W(L_KVD_W), part, sr));
-      TRY_G(dx(st, dcp, R, blob + y.kvd, CS, R, H, dctx, H, true, false, sr));
+      TRY_G(linear_bwd(st, dcp, R, tp + tt.ctx, blob + y.kvd, CS, R, H, nullptr, W(L_KVD_W), dctx, part, sr, true));  // (dctx: summed over layers)
       // self-attention branch: h1 = h0 + att1 Wproj^T + b
-      TRY_G(colsum(st, dh, H, M, H, W(L_PROJ_B), part, tr));
-      TRY_G(dw(st, dh, H, tp + z.att1, H, M, H, H, W(L_PROJ_W), part, tr));
-      TRY_G(dx(st, dh, H, blob + y.g_proj, M, H, H, ga, H, false, false, tr));
-      const Act qkv = T16(z.qkv);
+      TRY_G(linear_bwd(st, dh, H, tp + z.att1, blob + y.g_proj, M, H, H, W(L_PROJ_B), W(L_PROJ_W), ga, part, tr));
+      const Act qkv = tp + z.qkv;
       TRY_G(attn_bwd(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, ga, tp + z.lse1, delta, big, 3 * H, big + H, big + 2 * H,
                      3 * H, T, T, window, D(DROP_ATTN), ln.t, ln.t));
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h0, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cb));
-      TRY_G(dw(st, big, 3 * H, xn, H, M, 3 * H, H, W(L_QKV_W), part, tr));
-      TRY_G(dx(st, big, 3 * H, blob + y.s_qkv, M, 3 * H, H, ga, H, false, false, tr));
+      TRY_G(linear_bwd(st, big, 3 * H, xn, blob + y.s_qkv, M, 3 * H, H, nullptr, W(L_QKV_W), ga, part, tr));
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h0, ga, dh, true, M, H, T, blob + y.n1w, 1e-6f, cond_row + l * row, cb, stat, part, W(L_N1_W), nullptr,
                                dmod + l * row, cb, ln.t));
     }
     // in_proj
-    TRY_G(colsum(st, dh, H, M, H, GG(G_INP_B), part, tr));
-    TRY_G(dw(st, dh, H, x, MEL, M, H, MEL, GG(G_INP_W), part, tr));
-    if (d_x) TRY_G(dx(st, dh, H, blob + lo.inp, M, H, MEL, d_x, MEL, false, false, tr));
+    TRY_G(linear_bwd(st, dh, H, x, blob + lo.inp, M, H, MEL, GG(G_INP_B), GG(G_INP_W), d_x, part, tr));
     // context sources
     if (sem_feat) {
-      TRY_G(colsum(st, dctx, H, CS, H, GG(G_SEMP_B), part, sr));
-      TRY_G(dw(st, dctx, H, sem_feat, lo.SD, CS, H, lo.SD, GG(G_SEMP_W), part, sr));
-      if (d_sem) TRY_G(dx(st, dctx, H, blob + lo.semp, CS, H, lo.SD, d_sem, lo.SD, false, false, sr));
+      TRY_G(linear_bwd(st, dctx, H, sem_feat, blob + lo.semp, CS, H, lo.SD, GG(G_SEMP_B), GG(G_SEMP_W), d_sem, part, sr));
       if (GG(G_TOK)) HIP_TRY(hipMemsetAsync(GG(G_TOK), 0, (size_t)lo.NTOK * H * sizeof(float), st));  // (does not enter the output)
     } else {
       if (GG(G_SEMP_W)) HIP_TRY(hipMemsetAsync(GG(G_SEMP_W), 0, (size_t)H * lo.SD * sizeof(float), st));
@@ -1060,7 +1069,7 @@ struct TrainLauncher {
                  gs[G_COUNT + l * L_COUNT + L_N3P_W] || gs[G_COUNT + l * L_COUNT + L_N3P_B];
     const bool any_time = GG(G_T1_W) || GG(G_T1_B) || GG(G_T3_W) || GG(G_T3_B) || GG(G_STEP);
     if (!any_proj && !any_time) return EDTTS_OK;
-    const float* tcond = cond_row + (size_t)B * cb;
+    const float* tcond = tp + tt.tcond;
     float *dtc = sc + ss.dtc, *e = sc + ss.e, *a1 = sc + ss.a1, *u1 = sc + ss.u1, *du1 = sc + ss.du1;
     HIP_TRY(hipMemsetAsync(dtc, 0, (size_t)B * H * sizeof(float), st));
     for (int l = 0; l < L; ++l) {
@@ -1069,9 +1078,7 @@ struct TrainLauncher {
         const float* dm = dmod + l * row + which * 2 * H;
         float* gw = gs[G_COUNT + l * L_COUNT + (which ? L_N3P_W : L_N1P_W)];
         float* gb = gs[G_COUNT + l * L_COUNT + (which ? L_N3P_B : L_N1P_B)];
-        TRY_G(colsum(st, dm, cb, B, 2 * H, gb, part));
-        TRY_G(dw(st, dm, cb, tcond, H, B, 2 * H, H, gw, part));
-        TRY_G(dx(st, dm, cb, blob + (which ? y.ada3T : y.ada1T), B, 2 * H, H, dtc, H, true, true));
+        TRY_G(linear_bwd(st, dm, cb, tcond, blob + (which ? y.ada3T : y.ada1T), B, 2 * H, H, gb, gw, dtc, part, RowLens{}, true, true));
       }
     }
     if (!any_time) return EDTTS_OK;
@@ -1092,14 +1099,10 @@ struct TrainLauncher {
     }
     hipLaunchKernelGGL(edtts_bwd::k_bwd_gelu, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, a1, blob + lo.t1b, B, H, u1);
     LAUNCH_CHECK("k_bwd_gelu");
-    TRY_G(colsum(st, dtc, H, B, H, GG(G_T3_B), part));
-    TRY_G(dw(st, dtc, H, u1, H, B, H, H, GG(G_T3_W), part));
-    TRY_G(dx(st, dtc, H, blob + lo.t3T, B, H, H, du1, H, false, true));
+    TRY_G(linear_bwd(st, dtc, H, u1, blob + lo.t3T, B, H, H, GG(G_T3_B), GG(G_T3_W), du1, part, RowLens{}, false, true));
     hipLaunchKernelGGL(edtts_bwd::k_bwd_gelu_grad, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, du1, a1, B * H);
     LAUNCH_CHECK("k_bwd_gelu_grad");
-    TRY_G(colsum(st, du1, H, B, H, GG(G_T1_B), part));
-    TRY_G(dw(st, du1, H, e, H, B, H, H, GG(G_T1_W), part));
-    return EDTTS_OK;
+    return linear_bwd(st, du1, H, e, nullptr, B, H, H, GG(G_T1_B), GG(G_T1_W), nullptr, part);
   }
 };
 
@@ -1146,33 +1149,16 @@ int edtts_train_tape_region(const EdttsDims* dims, int B, int T, int S, int laye
   if (layer < 0 || layer >= lo.L) return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: layer %d outside [0, %d)", layer, lo.L);
   TrainTape tt;
   make_tape(lo, B, T, S, &tt);
-  const TapeLayer& z = tt.layer[layer];
-  const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S;
-  size_t off, n;
-  bool narrow = false;
-  switch (which) {
-    case EDTTS_TAPE_CRP: off = z.crp; n = CS * lo.R; break;
-    case EDTTS_TAPE_KV: off = z.kv; n = CS * 2 * H; narrow = true; break;
-    case EDTTS_TAPE_H0: off = z.h0; n = M * H; break;
-    case EDTTS_TAPE_H1: off = z.h1; n = M * H; break;
-    case EDTTS_TAPE_H2: off = z.h2; n = M * H; break;
-    case EDTTS_TAPE_QKV: off = z.qkv; n = M * 3 * H; narrow = true; break;
-    case EDTTS_TAPE_ATT1: off = z.att1; n = M * H; break;
-    case EDTTS_TAPE_LSE1: off = z.lse1; n = M * lo.HEADS; break;
-    case EDTTS_TAPE_QC: off = z.qc; n = M * H; narrow = true; break;
-    case EDTTS_TAPE_ATT2: off = z.att2; n = M * H; break;
-    case EDTTS_TAPE_LSE2: off = z.lse2; n = M * lo.HEADS; break;
-    case EDTTS_TAPE_ACT: off = z.act; n = M * lo.FM * H; narrow = true; break;
-    // the whole-model members: the same answer for every layer
-    case EDTTS_TAPE_COND: off = tt.cond; n = (size_t)B * lo.L * 4 * H; break;
-    case EDTTS_TAPE_TCOND: off = tt.cond + (size_t)B * lo.L * 4 * H; n = (size_t)B * H; break;
-    case EDTTS_TAPE_CTX: off = tt.ctx; n = CS * H; break;
-    case EDTTS_TAPE_HL: off = tt.hL; n = M * H; break;
-    default: return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: which=%d is not one of EDTTS_TAPE_CRP .. EDTTS_TAPE_HL", which);
-  }
-  *elem_bytes = narrow && lo.TAPE16 ? 2 : 4;
-  *offset_bytes = off * sizeof(float);
-  *bytes = n * (size_t)*elem_bytes;
+  TapePlace at{0, 0};
+  size_t n = 0;
+  const TrainTape& ct = tt;
+  tape_regions(lo, B, T, S, ct, [&](int w, int l, const auto& m, size_t count) {  // (the whole-model members: the same answer for every layer)
+    if (w == which && (l < 0 || l == layer)) { at = tape_place_of(m); n = count; }
+  });
+  if (!at.elem_bytes) return fail(EDTTS_ERR_ARG, "edtts_train_tape_region: which=%d is not one of EDTTS_TAPE_CRP .. EDTTS_TAPE_HL", which);
+  *elem_bytes = at.elem_bytes;
+  *offset_bytes = at.off * sizeof(float);
+  *bytes = n * (size_t)at.elem_bytes;
   return EDTTS_OK;
 }
 

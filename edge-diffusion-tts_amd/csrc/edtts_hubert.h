@@ -558,17 +558,8 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
   for (int l = 0; l < L.L; ++l) {
     const float* Y = P + (size_t)l * L.layer;
     TRY_G(hub_dense<HEPI_BIAS>(st, h, Y + L.qkv_w, Y + L.qkv_b, big, nullptr, M, 3 * H, H));
-    edtts_gen::AttnArgs a{big, big + H, big + 2 * H, att, 3 * H, 3 * H, H, T, T, L.DH, -1,
-                          1.4426950408889634f / sqrtf((float)L.DH), flen, flen, 0, 0};
-    const dim3 grid((T + 15) / 16, L.heads, B);
-    switch ((L.DH + 15) / 16) {
-#define EDTTS_HUB_ATTN(DT) case DT: hipLaunchKernelGGL(edtts_gen::k_gen_attn<DT>, grid, dim3(64), 0, st, a); break
-      EDTTS_HUB_ATTN(1); EDTTS_HUB_ATTN(2); EDTTS_HUB_ATTN(3); EDTTS_HUB_ATTN(4);
-      EDTTS_HUB_ATTN(5); EDTTS_HUB_ATTN(6); EDTTS_HUB_ATTN(7); EDTTS_HUB_ATTN(8);
-#undef EDTTS_HUB_ATTN
-      default: return fail(EDTTS_ERR_UNSUPPORTED, "head_dim=%d > 128", L.DH);
-    }
-    LAUNCH_CHECK("k_gen_attn");
+    TRY_G(GenericLauncher::attn(st, AttnShape(H, L.heads, L.DH), B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, -1, flen, flen, false,
+                                false));
     TRY_G(hub_dense<HEPI_RESID>(st, att, Y + L.o_w, Y + L.o_b, h, h, M, H, H));
     TRY_G(hub_norm(st, h, h, M, H, Y + L.ln1_w, Y + L.ln1_b, L.eps));
     TRY_G(hub_dense<HEPI_GELU>(st, h, Y + L.ff1_w, Y + L.ff1_b, big, nullptr, M, L.I, H));

@@ -509,14 +509,16 @@ static int hub_forward16(const HubLayout& L, const void* packed, const float* wa
     hipLaunchKernelGGL(k_hub_vt, dim3(ws.Tp / 32, L.heads, B), dim3(256), 0, st, aa);
     LAUNCH_CHECK("k_hub_vt");
     const dim3 grid((T + 63) / 64, L.heads, B);
-    switch (L.DH / 32) {
-      case 1: hipLaunchKernelGGL(k_hub_attn16<1>, grid, dim3(256), 0, st, aa); break;
-      case 2: hipLaunchKernelGGL(k_hub_attn16<2>, grid, dim3(256), 0, st, aa); break;
-      case 3: hipLaunchKernelGGL(k_hub_attn16<3>, grid, dim3(256), 0, st, aa); break;
-      case 4: hipLaunchKernelGGL(k_hub_attn16<4>, grid, dim3(256), 0, st, aa); break;
-      default: return fail(EDTTS_ERR_UNSUPPORTED, "head_dim=%d: compute_dtype bf16 needs a multiple of 32 up to 128", L.DH);
-    }
-    LAUNCH_CHECK("k_hub_attn16");
+    TRY_G(with_head_tiles<8>(L.DH, [&](auto dt) -> int {  // head_dim = 32 KT: an even count of 16-wide tiles (hub_layout16)
+      constexpr int DT = decltype(dt)::value;
+      if constexpr (DT % 2 == 0) {
+        hipLaunchKernelGGL(k_hub_attn16<DT / 2>, grid, dim3(256), 0, st, aa);
+        LAUNCH_CHECK("k_hub_attn16");
+        return EDTTS_OK;
+      } else {
+        return fail(EDTTS_ERR_UNSUPPORTED, "head_dim=%d: compute_dtype bf16 needs a multiple of 32 up to 128", L.DH);
+      }
+    }));
     TRY_G((hub_dense16<HEPI_RESID, true, false>(st, att16, PW(y + L.o_w), P + y + L.o_b, h, h, M, H, H)));
     TRY_G(hub_norm(st, h, h, M, H, P + y + L.ln1_w, P + y + L.ln1_b, L.eps));
     TRY_G((hub_dense16<HEPI_GELU, false, true>(st, h, PW(y + L.ff1_w), P + y + L.ff1_b, big, nullptr, M, L.I, H)));

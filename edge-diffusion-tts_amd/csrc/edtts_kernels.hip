@@ -2417,6 +2417,31 @@ static int with_tail(int kind, F&& f) {
     default: return f(std::integral_constant<int, TAIL_DDIM>{});
   }
 }
+// ... and its kin for the other run-time values that name a kernel instance:
+// f(std::bool_constant<b>) for a run-time flag
+template <class F>
+static int with_flag(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(Elem<float>) or f(Elem<__bf16>) for the element type of a buffer (bf16: whether it holds __bf16)
+template <class T>
+struct Elem {
+  using type = T;
+};
+template <class F>
+static int with_elem(bool bf16, F&& f) {
+  return bf16 ? f(Elem<__bf16>{}) : f(Elem<float>{});
+}
+// f(std::integral_constant<int, DT>) for DT = ceil(head_dim / 16) in 1 .. MAX: the smallest head-dim tile count that holds the head
+template <int MAX, int DT = 1, class F>
+static int with_head_tiles(int head_dim, F&& f) {
+  if constexpr (DT > MAX) {
+    return fail(EDTTS_ERR_UNSUPPORTED, "generic kernels: head_dim=%d > %d", head_dim, 16 * MAX);
+  } else {
+    if ((head_dim + 15) / 16 == DT) return f(std::integral_constant<int, DT>{});
+    return with_head_tiles<MAX, DT + 1>(head_dim, f);
+  }
+}
 #define TRY_G(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 // ... for every kind (the hipFuncSetAttribute lists)
 template <class F>
