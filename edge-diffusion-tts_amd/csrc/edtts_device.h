@@ -994,11 +994,11 @@ EDTTS_DEV float cfg_combine(float vc, float vu, float scale) {
 }
 
 // Philox4x32-10 counter-based generator (Salmon et al., SC'11): the ten integer rounds, key (k0, k1), counter (c0 .. c3) -> the
-// four output words.  (Known answers: tests/test_dropout_host.py.)
+// four output words.  (Known answers: tests/test_dropout_host.py.)  Also a host function: edtts_keys_host (edtts_keys.h) calls it.
 struct U4 {
   unsigned x, y, z, w;
 };
-EDTTS_DEV U4 philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
+__host__ EDTTS_DEV U4 philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
 #pragma unroll
   for (int i = 0; i < 10; ++i) {
     const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
@@ -1031,7 +1031,17 @@ struct DropArgs {
   unsigned c2;      // stream word of this (layer, site)
   unsigned thr;     // round(p * 65536)
   float scale;      // 65536 / (65536 - thr)
+  const unsigned* key = nullptr;  // EdttsDropoutDev: the seed's two words in device memory (k0, k1 are then not read)
 };
+// The arguments a kernel draws with: with a device key, its two words loaded once (one address for every lane: a scalar load) in
+// place of the by-value seed.  Every kernel that applies a mask calls this before its first draw.
+EDTTS_DEV DropArgs drop_live(DropArgs d) {
+  if (d.key) {
+    d.k0 = d.key[0];
+    d.k1 = d.key[1];
+  }
+  return d;
+}
 EDTTS_DEV unsigned drop_field(const U4& w, int j) {
   const unsigned v = (j & 4) ? ((j & 2) ? w.w : w.z) : ((j & 2) ? w.y : w.x);
   return (j & 1) ? v >> 16 : v & 0xffffu;

@@ -98,6 +98,7 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
     }
   }
   // epilogue: acc[t][u] lane (g, fq) holds Y[m = m0 + wm + 16u + fq][n = 4g + r of weight sub-tile t]
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   if (EPI == EPI_SWIGLU) {
     const int n = n0 + wn0 + 4 * g;
 #pragma unroll
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
         o[r] = v * silu(gt);
       }
       if (DROP) {
-        const f4 dm = drop_row4(a.dr, m, n);
+        const f4 dm = drop_row4(dr, m, n);
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] *= dm[r];
       }
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(256) void k_gen_gemm(GemmArgs a) {
           if (n + r < a.N) o[r] += pp[r];
       }
       if (DROP) {  // h = h + dropout(x W^T + b)
-        const f4 dm = drop_row4(a.dr, m, n);
+        const f4 dm = drop_row4(dr, m, n);
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] *= dm[r];
       }
@@ -269,6 +270,7 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
   }
   const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
   const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   for (int j0 = lo; j0 < hi; j0 += 16) {
     const int kj = j0 + fq;
     const bool kok = kj < hi;
@@ -306,7 +308,7 @@ __global__ __launch_bounds__(64) void k_gen_attn(AttnArgs a) {
 #pragma unroll
     for (int t = 0; t < DT; ++t) acc[t] *= alpha;
     if (DROP) {  // (key tiles start at lo + 16 n: aligned for every tile or for none)
-      const f4 dm = drop_attn_keys4(a.dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 4 * g, (lo & 3) == 0);
+      const f4 dm = drop_attn_keys4(dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 4 * g, (lo & 3) == 0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) p[r] *= dm[r];
     }
@@ -456,7 +458,8 @@ enum { DROP_ATTN = 0, DROP_CROSS = 1, DROP_ACT = 2, DROP_DOWN = 3 };
 struct DropState {
   unsigned k0, k1, thr;
   float scale;
-  DropArgs site(int layer, int site_id) const { return DropArgs{k0, k1, 0x30000u + 4u * (unsigned)layer + (unsigned)site_id, thr, scale}; }
+  const unsigned* key = nullptr;  // EdttsDropoutDev: the key in device memory instead of (k0, k1)
+  DropArgs site(int layer, int site_id) const { return DropArgs{k0, k1, 0x30000u + 4u * (unsigned)layer + (unsigned)site_id, thr, scale, key}; }
 };
 
 // Where one forward's intermediates go.  Inference reuses a few workspace buffers for all of them; the training forward

@@ -138,6 +138,7 @@ EDTTS_DEV void mfma_tile16(const __bf16 (*t)[kGBM][kG16Ld], f4 (&acc)[2][2], int
 // (TY = __bf16: the stores go through store_row4; the float instantiation keeps its statements)
 template <int EPI, bool DROP, typename TY = float>
 EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, int n0, int wm, int wn0, int wn1, int fq, int g) {
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   if (EPI == EPI_SWIGLU) {
     const int n = n0 + wn0 + 4 * g;
 #pragma unroll
@@ -153,7 +154,7 @@ EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, i
         o[r] = v * silu(gt);
       }
       if (DROP) {
-        const f4 dm = drop_row4(a.dr, m, n);
+        const f4 dm = drop_row4(dr, m, n);
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] *= dm[r];
       }
@@ -193,7 +194,7 @@ EDTTS_DEV void gemm_epilogue(const GemmArgs& a, const f4 (&acc)[2][2], int m0, i
           if (n + r < a.N) o[r] += pp[r];
       }
       if (DROP) {  // h = h + dropout(x W^T + b)
-        const f4 dm = drop_row4(a.dr, m, n);
+        const f4 dm = drop_row4(dr, m, n);
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] *= dm[r];
       }

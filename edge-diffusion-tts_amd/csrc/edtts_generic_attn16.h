@@ -180,6 +180,7 @@ __global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a) {
     }
   };
   if (lo < hi) load(lo);
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   for (int j0 = lo; j0 < hi; j0 += 32) {
     __syncthreads();  // every wave is done reading the previous step
     store();
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(256) void k_gen_attn16(AttnArgs a) {
     if (DROP) {  // (steps start at multiples of 32: one draw per four keys)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const f4 dm = a16_drop_keys4(a.dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 16 * t + 4 * g);
+        const f4 dm = a16_drop_keys4(dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 16 * t + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) p[t][r] *= dm[r];
       }
@@ -342,6 +343,7 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a) {
     }
   };
   if (lo < hi) load(lo);
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   for (int j0 = lo; j0 < hi; j0 += 32) {
     __syncthreads();
     store();
@@ -362,7 +364,7 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dq16(AttnBwdArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (DROP) {
-        const f4 dm = a16_drop_keys4(a.dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 16 * t + 4 * g);
+        const f4 dm = a16_drop_keys4(dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 16 * t + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) dp[t][r] *= dm[r];
       }
@@ -477,6 +479,7 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a) {
     if (tid < 64) stat[tid >> 5][tid & 31] = sv;
   };
   if (lo < hi) load(lo);
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   for (int i0 = lo; i0 < hi; i0 += 32) {
     __syncthreads();
     store();
@@ -498,7 +501,7 @@ __global__ __launch_bounds__(256) void k_bwd_attn_dkv16(AttnBwdArgs a) {
     for (int t = 0; t < 2; ++t) {
       f4 dm;
       if (DROP) {  // (steps start at multiples of 32: even)
-        dm = a16_drop_queries4(a.dr, (unsigned)(b * gridDim.y + hd), i0 + 16 * t + 4 * g, kj);
+        dm = a16_drop_queries4(dr, (unsigned)(b * gridDim.y + hd), i0 + 16 * t + 4 * g, kj);
 #pragma unroll
         for (int r = 0; r < 4; ++r) dp[t][r] *= dm[r];
       }

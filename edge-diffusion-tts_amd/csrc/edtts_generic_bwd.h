@@ -334,7 +334,8 @@ __global__ __launch_bounds__(256) void k_bwd_swiglu(float* u, const float* da, s
 }
 
 // ... with dropout behind value * silu(gate): da is multiplied by that mask (site 2) first.  One thread per four columns.
-__global__ __launch_bounds__(256) void k_bwd_swiglu_drop(float* u, const float* da, size_t M, int FH, DropArgs dr) {
+__global__ __launch_bounds__(256) void k_bwd_swiglu_drop(float* u, const float* da, size_t M, int FH, DropArgs dr_in) {
+  const DropArgs dr = drop_live(dr_in);
   const int ng = (FH + 3) / 4;
   const size_t n = M * ng;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -354,7 +355,8 @@ __global__ __launch_bounds__(256) void k_bwd_swiglu_drop(float* u, const float* 
   }
 }
 // y[M][W] = x[M][W] o mask: the residual gradient entering the dropped down projection (site 3)
-__global__ __launch_bounds__(256) void k_bwd_drop_rows(const float* x, float* y, size_t M, int W, DropArgs dr) {
+__global__ __launch_bounds__(256) void k_bwd_drop_rows(const float* x, float* y, size_t M, int W, DropArgs dr_in) {
+  const DropArgs dr = drop_live(dr_in);
   const int ng = (W + 3) / 4;
   const size_t n = M * ng;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -368,7 +370,8 @@ __global__ __launch_bounds__(256) void k_bwd_drop_rows(const float* x, float* y,
 }
 // edtts_dropout_mask: keep bytes of one site through the functions the kernels call.  Attention sites: rows = B heads Tq rows of
 // W = Tk keys (row = bh Tq + q); feed-forward sites: rows = B T rows of W columns.
-__global__ __launch_bounds__(256) void k_drop_mask(uint8_t* keep, size_t rows, int W, int Tq, int attn, DropArgs dr) {
+__global__ __launch_bounds__(256) void k_drop_mask(uint8_t* keep, size_t rows, int W, int Tq, int attn, DropArgs dr_in) {
+  const DropArgs dr = drop_live(dr_in);
   const int ng = (W + 3) / 4;
   const size_t n = rows * ng;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -455,6 +458,7 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
   }
   const float* kb = a.k + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
   const float* vb = a.v + (size_t)b * a.Tk * a.ldkv + hd * a.DH;
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   for (int j0 = lo; j0 < hi; j0 += 16) {
     const int kj = j0 + fq;
     const bool kok = kj < hi;
@@ -469,7 +473,7 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dq(AttnBwdArgs a) {
       dp = EDTTS_MFMA(ok ? vrow[d] : 0.f, dov[s], dp);
     }
     if (DROP) {
-      const f4 dm = drop_attn_keys4(a.dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 4 * g, (lo & 3) == 0);
+      const f4 dm = drop_attn_keys4(dr, (unsigned)(b * gridDim.y + hd), qi, j0 + 4 * g, (lo & 3) == 0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) dp[r] *= dm[r];
     }
@@ -546,6 +550,7 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
   const float* db = a.dO + (size_t)b * a.Tq * a.ldo + hd * a.DH;
   const float* lb = a.lse + ((size_t)b * gridDim.y + hd) * a.Tq;
   const float* eb = a.delta + ((size_t)b * gridDim.y + hd) * a.Tq;
+  const DropArgs dr = DROP ? drop_live(a.dr) : DropArgs{};
   for (int i0 = lo; i0 < hi; i0 += 16) {
     const int qi = i0 + fq;
     const bool qok = qi < hi;
@@ -561,7 +566,7 @@ __global__ __launch_bounds__(64) void k_bwd_attn_dkv(AttnBwdArgs a) {
     }
     f4 dm;
     if (DROP) {  // (query tiles start at lo + 16 n: odd for every tile or for none)
-      dm = drop_attn_queries4(a.dr, (unsigned)(b * gridDim.y + hd), i0 + 4 * g, kj, (lo & 1) != 0);
+      dm = drop_attn_queries4(dr, (unsigned)(b * gridDim.y + hd), i0 + 4 * g, kj, (lo & 1) != 0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) dp[r] *= dm[r];
     }
@@ -1110,7 +1115,8 @@ struct TrainLauncher {
 // the C ABI of training: a forward that keeps a tape, the backward from it, the dropout masks
 // =========================================================================================================
 // EdttsDropout -> DropState.  *on = false for NULL or p == 0 (the call then makes exactly the launches of its plain twin).
-static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on) {
+// key: the seed in device memory (the *_dev entry points; drop->seed is then not read), or nullptr.
+static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, bool* on, const uint64_t* key = nullptr) {
   *on = false;
   if (!drop || drop->p == 0.0f) return EDTTS_OK;
   const float p = drop->p;
@@ -1119,11 +1125,32 @@ static int drop_state(const EdttsDropout* drop, const char* who, DropState* ds, 
     return fail(EDTTS_ERR_ARG, "%s: dropout p=%g is outside [0, 1) (needs round(p * 65536) <= 65535)", who, (double)p);
   ds->k0 = (unsigned)drop->seed;
   ds->k1 = (unsigned)(drop->seed >> 32);
+  ds->key = reinterpret_cast<const unsigned*>(key);
   ds->thr = (unsigned)thr;
   ds->scale = 65536.0f / (float)(65536u - ds->thr);
   *on = true;
   return EDTTS_OK;
 }
+
+// EdttsDropoutDev -> the EdttsDropout (seed 0) and the device key that drop_state takes
+static int drop_dev(const EdttsDropoutDev* dev, const char* who, EdttsDropout* host, const uint64_t** key) {
+  *host = EdttsDropout{dev ? dev->p : 0.0f, 0};
+  *key = dev ? dev->key : nullptr;
+  if (dev && !dev->key) return fail(EDTTS_ERR_ARG, "%s: drop->key is NULL", who);
+  if (dev && ((size_t)dev->key & 7)) return fail(EDTTS_ERR_ARG, "%s: drop->key is not 8-byte aligned", who);
+  return EDTTS_OK;
+}
+
+static int decoder_forward_train_impl(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                      const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                      const float* sem_features, float* eps, const EdttsDropout* drop, const uint64_t* key,
+                                      const int64_t* t_len, const int64_t* s_len, void* stream);
+static int decoder_backward_impl(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                 const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                                 const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                                 const EdttsDropout* drop, const uint64_t* key, const int64_t* t_len, const int64_t* s_len, void* stream);
+static int dropout_mask_impl(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, const uint64_t* key,
+                             uint8_t* keep, void* stream);
 
 extern "C" {
 
@@ -1190,12 +1217,33 @@ int edtts_decoder_forward_train_len(const EdttsDims* dims, const void* packed, v
                                     const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
                                     const float* sem_features, float* eps, const EdttsDropout* drop, const int64_t* t_len,
                                     const int64_t* s_len, void* stream) {
+  return decoder_forward_train_impl(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, drop, nullptr, t_len,
+                                    s_len, stream);
+}
+
+int edtts_decoder_forward_train_dev(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                    const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                    const float* sem_features, float* eps, const EdttsDropoutDev* drop, const int64_t* t_len,
+                                    const int64_t* s_len, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_decoder_forward_train_dev", &host, &key));
+  return decoder_forward_train_impl(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, eps, drop ? &host : nullptr,
+                                    key, t_len, s_len, stream);
+}
+
+}  // extern "C"
+
+static int decoder_forward_train_impl(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                      const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                      const float* sem_features, float* eps, const EdttsDropout* drop, const uint64_t* key,
+                                      const int64_t* t_len, const int64_t* s_len, void* stream) {
   const SettingsScope settings;
   Layout lo;
   TRY_G(train_layout(dims, "edtts_decoder_forward_train", &lo));
   DropState ds;
   bool dropping;
-  TRY_G(drop_state(drop, "edtts_decoder_forward_train_drop", &ds, &dropping));
+  TRY_G(drop_state(drop, "edtts_decoder_forward_train_drop", &ds, &dropping, key));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
   if (!packed || !workspace || !tape || !x || !t || !eps) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   TRY_G(check_shapes(lo, B, T, S));
@@ -1212,6 +1260,8 @@ int edtts_decoder_forward_train_len(const EdttsDims* dims, const void* packed, v
   const CallCtx c{lo, blob, ws, wsb, B, T, S, dims->window, Lens{t_len, s_len}, st};
   return TrainLauncher::forward(c, tp, tt, x, sem_features ? nullptr : sem_idx, sem_features, eps, dropping ? &ds : nullptr);
 }
+
+extern "C" {
 
 int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S, const float* x,
                            const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features, const float* d_eps,
@@ -1232,11 +1282,44 @@ int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* 
                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                                const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
                                const EdttsDropout* drop, const int64_t* t_len, const int64_t* s_len, void* stream) {
+  return decoder_backward_impl(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots, d_x,
+                               d_sem_features, scratch, drop, nullptr, t_len, s_len, stream);
+}
+
+int edtts_decoder_backward_dev(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                               const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                               const EdttsDropoutDev* drop, const int64_t* t_len, const int64_t* s_len, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_decoder_backward_dev", &host, &key));
+  return decoder_backward_impl(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots, d_x,
+                               d_sem_features, scratch, drop ? &host : nullptr, key, t_len, s_len, stream);
+}
+
+int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+  return dropout_mask_impl(dims, site, layer, B, T, S, drop, nullptr, keep, stream);
+}
+
+int edtts_dropout_mask_dev(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropoutDev* drop, uint8_t* keep,
+                           void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_dropout_mask_dev", &host, &key));
+  return dropout_mask_impl(dims, site, layer, B, T, S, drop ? &host : nullptr, key, keep, stream);
+}
+
+}  // extern "C"
+
+static int decoder_backward_impl(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                 const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                                 const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                                 const EdttsDropout* drop, const uint64_t* key, const int64_t* t_len, const int64_t* s_len, void* stream) {
   Layout lo;
   TRY_G(train_layout(dims, "edtts_decoder_backward", &lo));
   DropState ds;
   bool dropping;
-  TRY_G(drop_state(drop, "edtts_decoder_backward_drop", &ds, &dropping));
+  TRY_G(drop_state(drop, "edtts_decoder_backward_drop", &ds, &dropping, key));
   if (!sem_idx && !sem_features) return fail(EDTTS_ERR_ARG, "Either sem_idx or sem_features must be provided");
   if (!packed || !workspace || !tape || !x || !t || !d_eps || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
@@ -1251,13 +1334,14 @@ int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* 
                                  d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr, Lens{t_len, s_len});
 }
 
-int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+static int dropout_mask_impl(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, const uint64_t* key,
+                             uint8_t* keep, void* stream) {
   Layout lo;
   TRY_G(train_layout(dims, "edtts_dropout_mask", &lo));
   if (!drop) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: drop is NULL");
-  DropState ds{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0u, 1.0f};  // (p == 0: threshold 0, everything kept)
+  DropState ds{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0u, 1.0f, reinterpret_cast<const unsigned*>(key)};  // (p == 0: threshold 0, everything kept)
   bool dropping;
-  TRY_G(drop_state(drop, "edtts_dropout_mask", &ds, &dropping));
+  TRY_G(drop_state(drop, "edtts_dropout_mask", &ds, &dropping, key));
   if (site < DROP_ATTN || site > DROP_DOWN) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: site %d is not one of 0 .. 3", site);
   if (layer < 0 || layer >= lo.L) return fail(EDTTS_ERR_ARG, "edtts_dropout_mask: layer %d outside [0, %d)", layer, lo.L);
   if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
@@ -1270,5 +1354,3 @@ int edtts_dropout_mask(const EdttsDims* dims, int site, int layer, int B, int T,
   LAUNCH_CHECK("k_drop_mask");
   return EDTTS_OK;
 }
-
-}  // extern "C"

@@ -2851,6 +2851,7 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
 #include "edtts_hubert16.h"      // ... its bf16 MFMA path <- edtts_hubert.h
 #include "edtts_audio.h"         // MelSpectrogram, log-mel statistics, Resample <- edtts_melpost.h: melpost::cplx
 #include "edtts_optim.h"         // FusedAdamW: k_opt_*, edtts_optim_*
+#include "edtts_keys.h"          // KeyStream: k_keys_advance, edtts_keys_* <- edtts_device.h: philox4x32_10
 #include "edtts_objective.h"     // DiffusionObjective: k_obj_*, edtts_objective_*
 #include "edtts_samplers.h"      // the samplers: step kernels, step loops, edtts_generate*, edtts_sample_*, edtts_randn*
 #include "edtts_debug.h"         // edtts_profile_*, the diagnostic builds' exports (g_prof, g_stamps_fwd, g_wavelog are defined above)

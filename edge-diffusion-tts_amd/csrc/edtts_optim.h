@@ -35,7 +35,7 @@ struct OptArgs {
   EdttsOptimState* state;
   OptBias* bias;
   float* partial;
-  const EdttsOptimGroup* groups;
+  EdttsOptimGroup* groups;  // (k_opt_finish of a resident step writes lr)
   const OptTensor* tensors;
   const OptChunk* chunks;
   int n_chunks, n_groups, flags;
@@ -105,7 +105,21 @@ EDTTS_DEV double opt_ipow(double b, long long n) {
   return r;
 }
 
-__global__ __launch_bounds__(kOptThreads) void k_opt_finish(OptArgs a, int have_norm) {
+// train_v2.cosine_lr_schedule at step n in fp64, in Python's order of operations (no contraction into fused multiply-adds)
+EDTTS_DEV double opt_sched_lr(const EdttsOptimSchedule& s, long long n) {
+#pragma clang fp contract(off)
+  if (n < s.warmup_steps) {
+    const long long w = s.warmup_steps > 1 ? s.warmup_steps : 1;
+    return s.base_lr * (double)n / (double)w;
+  }
+  const long long span = s.total_steps - s.warmup_steps > 1 ? s.total_steps - s.warmup_steps : 1;
+  const double progress = (double)(n - s.warmup_steps) / (double)span;
+  return s.min_lr + 0.5 * (s.base_lr - s.min_lr) * (1.0 + cos(3.141592653589793 * progress));
+}
+
+// lr_dev (fp64 [n_groups], device) or sched.kind != EDTTS_SCHED_NONE: the resident step's learning rate, stored into the groups
+// of the scratch before the step sizes are formed from it (edtts_optim_step passes neither: the uploaded lr holds).
+__global__ __launch_bounds__(kOptThreads) void k_opt_finish(OptArgs a, int have_norm, const double* lr_dev, EdttsOptimSchedule sched) {
   __shared__ float buf[1024];
   const int tid = threadIdx.x;
   double acc = 0.0;
@@ -128,6 +142,10 @@ __global__ __launch_bounds__(kOptThreads) void k_opt_finish(OptArgs a, int have_
     if (coef > 1.f) coef = 1.f;
   }
   const bool bad = (a.flags & EDTTS_OPT_SKIP_NONFINITE) && !(fabsf(tn) <= 3.402823466e38f);
+  if (lr_dev || sched.kind != EDTTS_SCHED_NONE) {  // (a skipped step has its lr too: the schedule's position is step + skipped)
+    const double lr_s = sched.kind != EDTTS_SCHED_NONE ? opt_sched_lr(sched, st->step + st->skipped) : 0.0;
+    for (int i = 0; i < a.n_groups; ++i) a.groups[i].lr = lr_dev ? lr_dev[i] : lr_s;
+  }
   st->total_norm = tn;
   st->clip_coef = coef;
   st->skip = bad ? 1 : 0;
@@ -303,44 +321,43 @@ int edtts_optim_scratch_bytes(int n_chunks, int n_groups, size_t* out_bytes) {
   return EDTTS_OK;
 }
 
-int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
-                     void* scratch, size_t scratch_bytes, void* stream) {
+// The checks of a step's arguments and the count of its chunks (`who` names the entry point in messages).
+static int opt_validate(const char* who, const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups,
+                        double max_norm, int flags, const void* scratch, long long* n_chunks_out) {
   using namespace edtts_opt;
   if (n_tensors < 0 || n_groups < 1 || (n_tensors && !tensors) || !groups || !scratch)
-    return fail(EDTTS_ERR_ARG, "edtts_optim_step: NULL pointer argument, n_tensors=%d or n_groups=%d", n_tensors, n_groups);
+    return fail(EDTTS_ERR_ARG, "%s: NULL pointer argument, n_tensors=%d or n_groups=%d", who, n_tensors, n_groups);
   if (flags & ~(EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE | EDTTS_OPT_ZERO_GRADS | EDTTS_OPT_EMA_ONLY))
-    return fail(EDTTS_ERR_ARG, "edtts_optim_step: unknown flag bits 0x%x", flags);
+    return fail(EDTTS_ERR_ARG, "%s: unknown flag bits 0x%x", who, flags);
   const bool ema_only = flags & EDTTS_OPT_EMA_ONLY;
-  if (ema_only && (flags & ~EDTTS_OPT_EMA_ONLY)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: EDTTS_OPT_EMA_ONLY excludes the other flags");
-  if ((flags & EDTTS_OPT_CLIP) && !(max_norm >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: max_norm=%g", max_norm);
+  if (ema_only && (flags & ~EDTTS_OPT_EMA_ONLY)) return fail(EDTTS_ERR_ARG, "%s: EDTTS_OPT_EMA_ONLY excludes the other flags", who);
+  if ((flags & EDTTS_OPT_CLIP) && !(max_norm >= 0.0)) return fail(EDTTS_ERR_ARG, "%s: max_norm=%g", who, max_norm);
   long long n_chunks = 0;
-  int n_live = 0;
   for (int i = 0; i < n_tensors; ++i) {
     const EdttsOptimTensor& t = tensors[i];
-    if (t.numel < 0) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has numel %lld", i, (long long)t.numel);
+    if (t.numel < 0) return fail(EDTTS_ERR_ARG, "%s: tensor %d has numel %lld", who, i, (long long)t.numel);
     if (t.numel == 0) continue;
     if (!t.p || (!ema_only && (!t.g || !t.m || !t.v)) || (ema_only && !t.ema))
-      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a NULL p, g, m, v or (EDTTS_OPT_EMA_ONLY) ema", i);
+      return fail(EDTTS_ERR_ARG, "%s: tensor %d has a NULL p, g, m, v or (EDTTS_OPT_EMA_ONLY) ema", who, i);
     if (((size_t)t.p | (size_t)t.g | (size_t)t.m | (size_t)t.v | (size_t)t.ema | (size_t)t.mirror | (size_t)t.ema_mirror) & 3)
-      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has a pointer that is not 4-byte aligned", i);
-    if (t.group < 0 || t.group >= n_groups) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d names group %d of %d", i, t.group, n_groups);
+      return fail(EDTTS_ERR_ARG, "%s: tensor %d has a pointer that is not 4-byte aligned", who, i);
+    if (t.group < 0 || t.group >= n_groups) return fail(EDTTS_ERR_ARG, "%s: tensor %d names group %d of %d", who, i, t.group, n_groups);
     if (t.rows < 0 || t.cols < 0 || (t.rows > 0 && (int64_t)t.rows * t.cols != t.numel))
-      return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: rows=%d cols=%d do not make numel=%lld", i, t.rows, t.cols, (long long)t.numel);
-    if (t.ema_mirror && !t.ema) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d has an ema_mirror without an ema", i);
-    if (t.ema && !(t.ema_decay >= 0.f && t.ema_decay <= 1.f)) return fail(EDTTS_ERR_ARG, "edtts_optim_step: tensor %d: ema_decay=%g", i, (double)t.ema_decay);
+      return fail(EDTTS_ERR_ARG, "%s: tensor %d: rows=%d cols=%d do not make numel=%lld", who, i, t.rows, t.cols, (long long)t.numel);
+    if (t.ema_mirror && !t.ema) return fail(EDTTS_ERR_ARG, "%s: tensor %d has an ema_mirror without an ema", who, i);
+    if (t.ema && !(t.ema_decay >= 0.f && t.ema_decay <= 1.f)) return fail(EDTTS_ERR_ARG, "%s: tensor %d: ema_decay=%g", who, i, (double)t.ema_decay);
     n_chunks += opt_chunks_of(t.numel);
-    ++n_live;
   }
-  if (n_chunks == 0) return EDTTS_OK;  // nothing to step: as torch, no state changes (the step counter included)
-  if (n_chunks > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "edtts_optim_step: %lld chunks", n_chunks);
-  OptScratch ls;
-  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
-  if (ls.total > scratch_bytes)
-    return fail(EDTTS_ERR_ARG, "edtts_optim_step: %lld chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  char* sc = (char*)scratch;
-  const size_t up_bytes = ls.total - ls.groups;  // groups | tensors | chunks, as they lie in the scratch
+  if (n_chunks > 0x7fffffff) return fail(EDTTS_ERR_UNSUPPORTED, "%s: %lld chunks", who, n_chunks);
+  *n_chunks_out = n_chunks;
+  return EDTTS_OK;
+}
 
+// The table (groups | tensors | chunks) of validated arguments into the scratch, through the pinned ring, behind `st`'s work.
+static int opt_upload_table(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups,
+                            const edtts_opt::OptScratch& ls, char* sc, hipStream_t st) {
+  using namespace edtts_opt;
+  const size_t up_bytes = ls.total - ls.groups;  // groups | tensors | chunks, as they lie in the scratch
   std::lock_guard<std::mutex> lock(g_opt_mu);
   OptSlot& slot = g_opt_ring[g_opt_next];
   g_opt_next = (g_opt_next + 1) % kOptRing;
@@ -378,20 +395,85 @@ int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const Edtts
   HIP_TRY(hipMemcpyAsync(sc + ls.groups, up, up_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(hipEventRecord(slot.ev, st));
   slot.pending = true;
-  OptArgs a{(EdttsOptimState*)sc, (OptBias*)(sc + ls.bias), (float*)(sc + ls.partial), (const EdttsOptimGroup*)(sc + ls.groups),
+  return EDTTS_OK;
+}
+
+// The two or three launches of a step on the table that lies in the scratch.
+static int opt_launch(long long n_chunks, int n_groups, double max_norm, int flags, const edtts_opt::OptScratch& ls, char* sc,
+                      const double* lr_dev, const EdttsOptimSchedule& sched, hipStream_t st) {
+  using namespace edtts_opt;
+  OptArgs a{(EdttsOptimState*)sc, (OptBias*)(sc + ls.bias), (float*)(sc + ls.partial), (EdttsOptimGroup*)(sc + ls.groups),
             (const OptTensor*)(sc + ls.tensors), (const OptChunk*)(sc + ls.chunks), (int)n_chunks, n_groups, flags, (float)max_norm};
-  if (!ema_only) {
+  if (!(flags & EDTTS_OPT_EMA_ONLY)) {
     const int have_norm = (flags & (EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE)) ? 1 : 0;
     if (have_norm) {
       hipLaunchKernelGGL(k_opt_sqsum, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
       LAUNCH_CHECK("k_opt_sqsum");
     }
-    hipLaunchKernelGGL(k_opt_finish, dim3(1), dim3(kOptThreads), 0, st, a, have_norm);
+    hipLaunchKernelGGL(k_opt_finish, dim3(1), dim3(kOptThreads), 0, st, a, have_norm, lr_dev, sched);
     LAUNCH_CHECK("k_opt_finish");
   }
   hipLaunchKernelGGL(k_opt_adamw, dim3((unsigned)n_chunks), dim3(kOptThreads), 0, st, a);
   LAUNCH_CHECK("k_opt_adamw");
   return EDTTS_OK;
+}
+
+int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
+                     void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace edtts_opt;
+  long long n_chunks = 0;
+  TRY_G(opt_validate("edtts_optim_step", tensors, n_tensors, groups, n_groups, max_norm, flags, scratch, &n_chunks));
+  if (n_chunks == 0) return EDTTS_OK;  // nothing to step: as torch, no state changes (the step counter included)
+  OptScratch ls;
+  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
+  if (ls.total > scratch_bytes)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step: %lld chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
+  TRY_G(opt_upload_table(tensors, n_tensors, groups, n_groups, ls, (char*)scratch, (hipStream_t)stream));
+  return opt_launch(n_chunks, n_groups, max_norm, flags, ls, (char*)scratch, nullptr, EdttsOptimSchedule{}, (hipStream_t)stream);
+}
+
+int edtts_optim_upload(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, int flags, void* scratch,
+                       size_t scratch_bytes, int* n_chunks_out, size_t* groups_offset, void* stream) {
+  using namespace edtts_opt;
+  if (!n_chunks_out || !groups_offset) return fail(EDTTS_ERR_ARG, "edtts_optim_upload: NULL n_chunks or groups_offset");
+  if (flags & EDTTS_OPT_EMA_ONLY) return fail(EDTTS_ERR_ARG, "edtts_optim_upload: EDTTS_OPT_EMA_ONLY has no resident form");
+  long long n_chunks = 0;
+  TRY_G(opt_validate("edtts_optim_upload", tensors, n_tensors, groups, n_groups, 0.0, flags, scratch, &n_chunks));
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(EDTTS_ERR_ARG, "edtts_optim_upload: the stream is capturing (upload outside the capture)");
+  OptScratch ls;
+  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
+  if (ls.total > scratch_bytes)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_upload: %lld chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
+  if (n_chunks) TRY_G(opt_upload_table(tensors, n_tensors, groups, n_groups, ls, (char*)scratch, (hipStream_t)stream));
+  *n_chunks_out = (int)n_chunks;
+  *groups_offset = ls.groups;
+  return EDTTS_OK;
+}
+
+int edtts_optim_step_resident(int n_chunks, int n_groups, double max_norm, int flags, void* scratch, size_t scratch_bytes, const double* lr_dev,
+                              const EdttsOptimSchedule* sched, void* stream) {
+  using namespace edtts_opt;
+  if (n_chunks < 0 || n_groups < 1 || !scratch) return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: NULL scratch, n_chunks=%d or n_groups=%d", n_chunks, n_groups);
+  if (flags & ~(EDTTS_OPT_CLIP | EDTTS_OPT_SKIP_NONFINITE | EDTTS_OPT_ZERO_GRADS))
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: flag bits 0x%x (EDTTS_OPT_EMA_ONLY has no resident form)", flags);
+  if ((flags & EDTTS_OPT_CLIP) && !(max_norm >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: max_norm=%g", max_norm);
+  if ((size_t)lr_dev & 7) return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: lr_dev is not 8-byte aligned");
+  EdttsOptimSchedule sc{};
+  if (sched) {
+    sc = *sched;
+    if (sc.kind != EDTTS_SCHED_NONE && sc.kind != EDTTS_SCHED_COSINE) return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: schedule kind %d", sc.kind);
+    if (sc.kind == EDTTS_SCHED_COSINE && (!(sc.base_lr >= 0.0) || !(sc.min_lr >= 0.0) || sc.warmup_steps < 0 || sc.total_steps < 0))
+      return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: cosine schedule with base_lr=%g min_lr=%g warmup_steps=%lld total_steps=%lld", sc.base_lr,
+                  sc.min_lr, (long long)sc.warmup_steps, (long long)sc.total_steps);
+  }
+  if (n_chunks == 0) return EDTTS_OK;
+  OptScratch ls;
+  opt_scratch((size_t)n_chunks, (size_t)n_groups, &ls);
+  if (ls.total > scratch_bytes)
+    return fail(EDTTS_ERR_ARG, "edtts_optim_step_resident: %d chunks in %d groups need %zu bytes of scratch, got %zu", n_chunks, n_groups, ls.total, scratch_bytes);
+  return opt_launch(n_chunks, n_groups, max_norm, flags, ls, (char*)scratch, lr_dev, sc, (hipStream_t)stream);
 }
 
 }  // extern "C"

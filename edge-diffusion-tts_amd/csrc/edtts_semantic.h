@@ -338,9 +338,10 @@ __global__ __launch_bounds__(256) void k_sem_encode(typename EncArgsOf<TRAIN>::t
       }
     if constexpr (TRAIN) {
       if (a.dropping) {
+        const DropArgs dr = drop_live(a.dr);
 #pragma unroll
         for (int t = 0; t < kMaxNT; ++t)
-          if (t < nt) y[t] = y[t] * drop_row4(a.dr, frame, 16 * t + 4 * grp);
+          if (t < nt) y[t] = y[t] * drop_row4(dr, frame, 16 * t + 4 * grp);
       }
     }
 #pragma unroll

@@ -226,10 +226,11 @@ __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
   const float rstd = (float)rstd_d;
   // ---- x dropout multiplier; a = (x^ gain + bias) o mask; gx = da o gain and its two per-frame sums
   double s1 = 0.0, s2 = 0.0;
+  const DropArgs dr = a.dropping ? drop_live(a.dr) : DropArgs{};
 #pragma unroll
   for (int t = 0; t < kMaxNT; ++t) {
     if (t < nt) {
-      const f4 dm = a.dropping ? drop_row4(a.dr, frame, 16 * t + 4 * grp) : splat(1.0f);
+      const f4 dm = a.dropping ? drop_row4(dr, frame, 16 * t + 4 * grp) : splat(1.0f);
       f4 av, dam;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -280,11 +281,12 @@ static int sem_train_dims(const EdttsSemDims* dims, const char* who, edtts_sem::
   return EDTTS_OK;
 }
 // the head's one dropout site: stream word 0x40000 (include/edtts.h, "Philox stream ids")
-static int sem_drop(const edtts_sem::SemLayout& L, const EdttsDropout* drop, const char* who, DropArgs* dr, bool* on) {
+static int sem_drop(const edtts_sem::SemLayout& L, const EdttsDropout* drop, const char* who, DropArgs* dr, bool* on,
+                    const uint64_t* key = nullptr) {
   DropState ds{};
-  TRY_G(drop_state(drop, who, &ds, on));
+  TRY_G(drop_state(drop, who, &ds, on, key));
   if (*on && !L.in_dim) return fail(EDTTS_ERR_ARG, "%s: dropout p=%g given, but a head without proj (in_dim 0) has no dropout site", who, (double)drop->p);
-  *dr = DropArgs{ds.k0, ds.k1, 0x40000u, ds.thr, ds.scale};
+  *dr = DropArgs{ds.k0, ds.k1, 0x40000u, ds.thr, ds.scale, ds.key};
   return EDTTS_OK;
 }
 static int sem_shape(int B, int T) {
@@ -323,6 +325,15 @@ static int sem_proj_sums(hipStream_t st, const edtts_sem::SemLayout& L, const ed
   TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));               // final Linear weight = dz^T a
   return TL::colsum(st, a.dz, S, M, S, gs[5], part);
 }
+
+// The bodies of the three entry points that draw masks: `key` is the seed in device memory (the *_dev twins) or nullptr.
+static int sem_encode_train_impl(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                                 float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, const uint64_t* key, void* stream);
+static int sem_backward_impl(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
+                             int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                             const EdttsDropout* drop, const uint64_t* key, void* stream);
+static int sem_dropout_mask_impl(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, const uint64_t* key, uint8_t* keep,
+                                 void* stream);
 
 extern "C" {
 
@@ -387,12 +398,54 @@ int edtts_sem_train_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t
 
 int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
                            float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, void* stream) {
+  return sem_encode_train_impl(dims, packed, h, B, T, lengths, idx, z_q, counts, tape, drop, nullptr, stream);
+}
+
+int edtts_sem_encode_train_dev(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                               float* z_q, int32_t* counts, void* tape, const EdttsDropoutDev* drop, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_sem_encode_train_dev", &host, &key));
+  return sem_encode_train_impl(dims, packed, h, B, T, lengths, idx, z_q, counts, tape, drop ? &host : nullptr, key, stream);
+}
+
+int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
+                       const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                       const EdttsDropout* drop, void* stream) {
+  return sem_backward_impl(dims, packed, packed_train, tape, h, B, T, lengths, d_zq, grad_slots, n_slots, d_z, scratch, drop, nullptr, stream);
+}
+
+int edtts_sem_backward_dev(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
+                           const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                           const EdttsDropoutDev* drop, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_sem_backward_dev", &host, &key));
+  return sem_backward_impl(dims, packed, packed_train, tape, h, B, T, lengths, d_zq, grad_slots, n_slots, d_z, scratch, drop ? &host : nullptr,
+                           key, stream);
+}
+
+int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+  return sem_dropout_mask_impl(dims, B, T, drop, nullptr, keep, stream);
+}
+
+int edtts_sem_dropout_mask_dev(const EdttsSemDims* dims, int B, int T, const EdttsDropoutDev* drop, uint8_t* keep, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_sem_dropout_mask_dev", &host, &key));
+  return sem_dropout_mask_impl(dims, B, T, drop ? &host : nullptr, key, keep, stream);
+}
+
+}  // extern "C"
+
+static int sem_encode_train_impl(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                                 float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, const uint64_t* key, void* stream) {
   using namespace edtts_sem;
   SemLayout L;
   TRY_G(sem_train_dims(dims, "edtts_sem_encode_train", L));
   DropArgs dr{};
   bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_encode_train", &dr, &dropping));
+  TRY_G(sem_drop(L, drop, "edtts_sem_encode_train", &dr, &dropping, key));
   TRY_G(sem_shape(B, T));
   if (!packed || !h || !idx || !tape) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   hipStream_t st = (hipStream_t)stream;
@@ -412,16 +465,16 @@ int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const f
   return EDTTS_OK;
 }
 
-int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
-                       const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
-                       const EdttsDropout* drop, void* stream) {
+static int sem_backward_impl(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
+                             int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                             const EdttsDropout* drop, const uint64_t* key, void* stream) {
   using namespace edtts_sem;
   using TL = TrainLauncher;
   SemLayout L;
   TRY_G(sem_train_dims(dims, "edtts_sem_backward", L));
   DropArgs dr{};
   bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_backward", &dr, &dropping));
+  TRY_G(sem_drop(L, drop, "edtts_sem_backward", &dr, &dropping, key));
   TRY_G(sem_shape(B, T));
   const int want = (L.in_dim ? 6 : 0) + 4;
   if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", want, n_slots);
@@ -469,14 +522,15 @@ int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void*
   return EDTTS_OK;
 }
 
-int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+static int sem_dropout_mask_impl(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, const uint64_t* key, uint8_t* keep,
+                                 void* stream) {
   edtts_sem::SemLayout L;
   TRY_G(sem_train_dims(dims, "edtts_sem_dropout_mask", L));
   if (!drop) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: drop is NULL");
   if (!L.in_dim) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: a head without proj (in_dim 0) has no dropout site");
   DropArgs dr{};
   bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_dropout_mask", &dr, &dropping));
+  TRY_G(sem_drop(L, drop, "edtts_sem_dropout_mask", &dr, &dropping, key));
   if (!dropping) dr = DropArgs{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0x40000u, 0u, 1.0f};  // p == 0: everything kept
   TRY_G(sem_shape(B, T));
   if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
@@ -487,8 +541,6 @@ int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDr
   LAUNCH_CHECK("k_drop_mask");
   return EDTTS_OK;
 }
-
-}  // extern "C"
 
 // =========================================================================================================
 // training the VQ head: VectorQuantizer in training mode under autograd

@@ -20,6 +20,7 @@ from .hubert import NativeHubert
 from .audio import MelSpectrogram, Resample, chunk_stats_from_audio, resample
 from .optim import FusedAdamW
 from .objective import DiffusionObjective
+from .graph_train import GraphedTrainStep, KeyStream
 
 __all__ = [
     "CFG", "TrainPhase", "get_device", "set_seed", "DiffusionSchedule", "DPMSolverPP", "EdgeDiffusionDecoder", "EdgeInference",
@@ -27,5 +28,5 @@ __all__ = [
     "GriffinLim", "InverseMelScale", "MelVocoder", "denormalize_mel", "normalize_mel",
     "SemanticEncoder", "VectorQuantizer", "FSQ", "FSQEncoder", "NativeHubert",
     "MelSpectrogram", "Resample", "resample", "chunk_stats_from_audio",
-    "FusedAdamW", "DiffusionObjective",
+    "FusedAdamW", "DiffusionObjective", "GraphedTrainStep", "KeyStream",
 ]

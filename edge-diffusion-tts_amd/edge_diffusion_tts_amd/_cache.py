@@ -3,12 +3,35 @@ parameter changes and ordered across streams, and a bounded cache of per-stream 
 lock of their own that is never held across a GPU wait, and a copy or a pickle of either starts empty with a new lock."""
 from __future__ import annotations
 
+import contextlib
 import threading
 import warnings
 
 import torch
 
 from .native import EdttsError
+
+
+# Graph capture (DESIGN.md section 32).  A replay bumps no tensor version, so a blob packed from trainable tensors that no optimiser
+# mirrors would be stale on the second replay: while a stream is capturing, such a blob is packed INSIDE the capture, so every
+# replay packs from the parameters as they then stand.  Whether a call trains is the caller's to say (get(trainable=True): the
+# differentiable forwards and their backwards -- torch runs both with grad mode off, so it cannot be read there); an inference
+# call's capture is as before.  Once per capture is enough, and who captures says where a capture begins: capture_scope()
+# (GraphedTrainStep opens one per graph).  Outside any scope every trainable get() under capture packs.
+_capture_epoch = 0
+_in_scope = False
+
+
+@contextlib.contextmanager
+def capture_scope():
+    """One graph capture: a trainable, unmirrored PackedBlob is packed once inside it, at its first get()."""
+    global _capture_epoch, _in_scope
+    _capture_epoch += 1
+    prev, _in_scope = _in_scope, True
+    try:
+        yield
+    finally:
+        _in_scope = prev
 
 
 class PackedBlob:
@@ -31,6 +54,8 @@ class PackedBlob:
         self.sig = None         # signature of the last pack
         self._event = None      # recorded on the packing stream right behind the last pack (GPU blobs only)
         self._waited = set()    # streams that have waited for it
+        self.mirrored = False   # an optimiser writes every update into the blob as well (FusedAdamW.attach_decoder)
+        self._cap_epoch = None  # the capture scope that has packed it
 
     @staticmethod
     def signature(key, tensors):
@@ -41,7 +66,8 @@ class PackedBlob:
 
     def _record(self) -> None:
         self._event, self._waited = None, set()
-        if self.blob.is_cuda:
+        # (not while capturing: an event recorded inside a capture cannot order an eager stream, and the pack has not run)
+        if self.blob.is_cuda and not torch.cuda.is_current_stream_capturing():
             stream = torch.cuda.current_stream(self.blob.device)
             self._event = torch.cuda.Event()
             self._event.record(stream)
@@ -54,15 +80,17 @@ class PackedBlob:
                 stream.wait_event(self._event)  # (enqueues a wait; the host does not block)
                 self._waited.add(stream.cuda_stream)
 
-    def get(self, key, tensors, packs=None, names=None) -> torch.Tensor:
+    def get(self, key, tensors, packs=None, names=None, trainable: bool = False) -> torch.Tensor:
         """The blob, (re-)packed on the current stream when ``key`` or a tensor's storage, version or device changed.  A call on
         another stream waits once per pack for the event recorded behind it, so its first use is ordered after the pack (not while
         capturing: a capture follows an eager warm-up, and torch.cuda.graph synchronises the device before it starts).
         ``packs``: a callable that returns the tensors to pack where they are not ``tensors`` themselves, called on a miss only;
-        ``names``: what to call each of them in an error, by default its index."""
+        ``names``: what to call each of them in an error, by default its index.  ``trainable``: the call belongs to a training
+        step (a differentiable forward or its backward): under graph capture the blob is then packed inside the capture unless an
+        optimiser mirrors it or no tensor requires grad (see capture_scope)."""
         with self._lock:
             sig = self.signature(key, tensors)
-            if self.blob is None or sig != self.sig:
+            if self.blob is None or sig != self.sig or (trainable and self._pack_in_capture(tensors)):
                 src = tensors if packs is None else packs()
                 dev = src[0].device
                 for i, t in enumerate(src):
@@ -77,6 +105,17 @@ class PackedBlob:
             else:
                 self._wait_once(False)
             return self.blob
+
+    def _pack_in_capture(self, tensors) -> bool:
+        """A trainable get(): True when the stream is capturing and the blob must be packed inside the capture (see capture_scope)."""
+        if self.mirrored or not self.blob.is_cuda or not torch.cuda.is_current_stream_capturing():
+            return False
+        if _in_scope and self._cap_epoch == _capture_epoch:
+            return False
+        if not any(t.requires_grad for t in tensors):
+            return False
+        self._cap_epoch = _capture_epoch
+        return True
 
     def invalidate(self) -> None:
         """The next get() packs again although no tensor's version moved (a kernel wrote into a packed tensor's storage)."""

@@ -60,7 +60,7 @@ class _DecoderGrad(torch.autograd.Function):
         B, T, _ = x_t.shape
         S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
         dims = dec.dims()
-        packed = dec._ensure_packed()
+        packed = dec._ensure_packed(trainable=True)
         ws = dec.workspace(B, T, S, B, x_t.device)
         x = x_t.detach().contiguous()
         t = t.contiguous()
@@ -115,6 +115,10 @@ class EdgeDiffusionDecoder(nn.Module):
         after SwiGLU, after the FFN's down projection) with ``p = cfg.dropout``; each such forward draws a 63-bit seed on the host
         from ``self.dropout_generator`` (a CPU ``torch.Generator``; None, the default: torch's default CPU generator, so
         ``torch.manual_seed`` makes a run repeatable), keeps it for its own backward and shows it as ``self.last_dropout_seed``.
+        With ``self.dropout_keys = (key_stream, first_slot)`` (a ``KeyStream``) each such forward instead takes a slot of the
+        stream -- ``first_slot`` for this module's first forward since the stream's last ``advance()``, the next one for its second,
+        and so on -- a key in device memory that the kernels read when they run, so a captured step draws new masks on every
+        replay; ``last_dropout_seed`` is then None.
         The masks are the library's (include/edtts.h, "Dropout masks"), not torch's random stream.  ``.eval()``, ``cfg.dropout ==
         0`` and calls that are not differentiable are unchanged; in particular a training-mode call under ``torch.no_grad()`` runs
         the inference forward WITHOUT dropout (the reference would drop there too): DESIGN.md section 20.
@@ -172,6 +176,7 @@ class EdgeDiffusionDecoder(nn.Module):
             raise ValueError("train_dropout=True needs autograd=True (dropout belongs to the training forward and its backward)")
         self.dropout_generator: Optional[torch.Generator] = None
         self.last_dropout_seed: Optional[int] = None
+        self.dropout_keys = None  # (KeyStream, first slot): dropout keys from device memory instead of host draws
         if self.autograd and kernels != "generic":
             raise ValueError(f"autograd=True needs kernels='generic' (the backward differentiates the generic kernels), got {kernels!r}")
         if self.autograd and native.COMPUTE_DTYPES.get(compute_dtype) != native.COMPUTE_DTYPES["f32"]:
@@ -327,12 +332,13 @@ class EdgeDiffusionDecoder(nn.Module):
             refs = self._slot_refs = (names, pairs)
         return refs[0], [d[k] for d, k in refs[1]]
 
-    def _ensure_packed(self) -> torch.Tensor:
+    def _ensure_packed(self, trainable: bool = False) -> torch.Tensor:
         """The packed weight blob, (re-)packed on the current stream when a parameter has changed; a call on another stream is
         ordered behind the pack (PackedBlob.get).  Changing parameters while calls that read the old blob are
-        still in flight on other streams is the caller's to order, as for any module."""
+        still in flight on other streams is the caller's to order, as for any module.  ``trainable``: PackedBlob.get's (the
+        differentiable forward passes True: under graph capture an unmirrored blob is packed inside the capture)."""
         names, tensors = self._slot_tensors()
-        return self._blob.get(self.dims(), tensors, names=names)
+        return self._blob.get(self.dims(), tensors, names=names, trainable=trainable)
 
     _packed = property(lambda self: self._blob.blob)
     _workspaces = property(lambda self: self._ws.entries)
@@ -434,7 +440,10 @@ class EdgeDiffusionDecoder(nn.Module):
             S = sem_features.shape[1] if sem_features is not None else sem_idx.shape[1]
             lens = (native.lengths(x_lengths, B, T, x_t.device, "x_lengths"), native.lengths(sem_lengths, B, S, x_t.device, "sem_lengths"))
         drop = None
-        if self.training and self.cfg.dropout > 0 and self.train_dropout:
+        if self.training and self.cfg.dropout > 0 and self.train_dropout and self.dropout_keys is not None:
+            drop = native.DropKey(float(self.cfg.dropout), self.dropout_keys[0].take(self, self.dropout_keys[1]))  # (kept in ctx for this forward's backward)
+            self.last_dropout_seed = None
+        elif self.training and self.cfg.dropout > 0 and self.train_dropout:
             # (a host draw from a CPU generator: no device work, no synchronisation)
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator).item())
             drop = (float(self.cfg.dropout), seed)

@@ -64,8 +64,8 @@ class _SemGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, owner, dims, lengths, drop, h, *params):
         slots = owner._slots()
-        blob = owner._pack.get(dims, slots)
-        tblob = owner._tpack.get(dims, slots)
+        blob = owner._pack.get(dims, slots, trainable=True)  # (under graph capture: packed inside the capture, _cache.capture_scope)
+        tblob = owner._tpack.get(dims, slots, trainable=True)
         x, B, T = _train_input(h, lengths)
         tape = torch.empty(native.sem_train_tape_bytes(dims, B, T), dtype=torch.uint8, device=x.device)
         idx, zq, counts = native.sem_encode_train(dims, blob, x, tape, lengths, True, drop)
@@ -81,8 +81,8 @@ class _SemGrad(torch.autograd.Function):
         owner, dims = ctx.owner, ctx.dims
         tape, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         slots = owner._slots()
-        blob = owner._pack.get(dims, slots)
-        tblob = owner._tpack.get(dims, slots)
+        blob = owner._pack.get(dims, slots, trainable=True)
+        tblob = owner._tpack.get(dims, slots, trainable=True)
         if (owner._pack.sig, owner._tpack.sig) != ctx.sig:
             raise RuntimeError(f"{type(owner).__name__}: a parameter was modified between this forward and its backward")
         grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[5:])]
@@ -457,7 +457,10 @@ class SemanticEncoder(nn.Module):
         ``train_dropout``: False (default) -- a differentiable call in training mode with the Dropout layout and ``p > 0`` raises.
         True (needs ``autograd=True`` and the Dropout layout) -- that call applies ``proj[3]`` with the library's Philox masks: each
         draws a 63-bit seed on the host from ``self.dropout_generator`` (a CPU ``torch.Generator``; None: torch's default one),
-        keeps it for its own backward and shows it as ``self.last_dropout_seed``, as EdgeDiffusionDecoder does."""
+        keeps it for its own backward and shows it as ``self.last_dropout_seed``, as EdgeDiffusionDecoder does.  With
+        ``self.dropout_keys = (key_stream, first_slot)`` the forward takes a slot of the stream instead -- ``first_slot`` for this
+        module's first forward since the stream's last ``advance()``, then the next (a key in device memory, DESIGN.md section
+        32; FSQ head only) -- and ``last_dropout_seed`` is None."""
         super().__init__()
         self.autograd = bool(autograd)
         self.train_dropout = bool(train_dropout)
@@ -481,6 +484,7 @@ class SemanticEncoder(nn.Module):
                 raise ValueError(f"train_dropout=True: cfg.dropout={p} is outside [0, 1) (the mask contract needs round(p * 65536) <= 65535)")
         self.dropout_generator: Optional[torch.Generator] = None
         self.last_dropout_seed: Optional[int] = None
+        self.dropout_keys = None  # (KeyStream, first slot): the dropout key from device memory instead of a host draw
         self.cfg = cfg
         self.hubert = hubert
         if hubert is not None:
@@ -646,10 +650,17 @@ class SemanticEncoder(nn.Module):
                 raise ValueError(f"autograd=True: proj has a Dropout with p={layer.p} and the encoder is in training mode (the reference "
                                  "drops there), but train_dropout is off: construct with train_dropout=True, or set proj[3].p = 0 or "
                                  "call .eval()")
-            # (a host draw from a CPU generator: no device work, no synchronisation)
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator).item())
-            drop = (float(layer.p), seed)
-            self.last_dropout_seed = seed
+            if self.dropout_keys is not None:
+                if self.train_vq:
+                    raise ValueError("dropout_keys: the VQ head's training forward takes host seeds only (train_vq=True stays outside "
+                                     "a captured step)")
+                drop = native.DropKey(float(layer.p), self.dropout_keys[0].take(self, self.dropout_keys[1]))
+                self.last_dropout_seed = None
+            else:
+                # (a host draw from a CPU generator: no device work, no synchronisation)
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator).item())
+                drop = (float(layer.p), seed)
+                self.last_dropout_seed = seed
         n = native.lengths(lengths, h.shape[0], max(h.shape[1], 1), h.device, "lengths")
         if self.train_vq:
             zq, loss, idx, counts = _VQGrad.apply(self, self.vq, self._dims(), n, drop, h.detach(), *self._slots())

@@ -41,6 +41,11 @@ class EdttsDropout(C.Structure):
     _fields_ = [("p", C.c_float), ("seed", C.c_uint64)]
 
 
+class EdttsDropoutDev(C.Structure):
+    """include/edtts.h: EdttsDropoutDev -- drop probability (host) and a pointer to the Philox key in device memory."""
+    _fields_ = [("p", C.c_float), ("key", C.c_void_p)]
+
+
 DROP_SITES = {"attn": 0, "cross_attn": 1, "ffn_act": 2, "ffn_out": 3}  # include/edtts.h, "Dropout masks": site ids
 
 
@@ -81,7 +86,19 @@ class EdttsOptimTensor(C.Structure):
         ("numel", C.c_int64), ("group", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("ema_decay", C.c_float)]
 
 
+class EdttsOptimSchedule(C.Structure):
+    """include/edtts.h: EdttsOptimSchedule -- the learning-rate schedule a resident step evaluates on the device."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("base_lr", C.c_double), ("min_lr", C.c_double),
+                ("warmup_steps", C.c_int64), ("total_steps", C.c_int64)]
+
+
 OPT_CLIP, OPT_SKIP_NONFINITE, OPT_ZERO_GRADS, OPT_EMA_ONLY = 1, 2, 4, 8  # include/edtts.h: EDTTS_OPT_*
+# layout facts for callers that read a table back as bytes (optim.py): record sizes and (name, offset, size) of every field
+OPTIM_GROUP_BYTES, OPTIM_TENSOR_BYTES = C.sizeof(EdttsOptimGroup), C.sizeof(EdttsOptimTensor)
+OPTIM_GROUP_LR_OFFSET = EdttsOptimGroup.lr.offset
+OPTIM_TENSOR_FIELDS = tuple((n, getattr(EdttsOptimTensor, n).offset, getattr(EdttsOptimTensor, n).size) for n, _ in EdttsOptimTensor._fields_)
+EDTTS_SCHED_NONE, EDTTS_SCHED_COSINE = 0, 1
+KEY_STREAM = 0x50000  # include/edtts.h, "Philox stream ids": the key stream's word
 EDTTS_OBJ_V, EDTTS_OBJ_EPS, EDTTS_OBJ_DISTILL, EDTTS_OBJ_CONSISTENCY = 0, 1, 2, 3  # include/edtts.h: the kinds of edtts_objective_loss
 OBJ_NOISE_STREAM = 0x54  # include/edtts.h, "Philox stream ids": training q_sample noise
 
@@ -127,7 +144,7 @@ EDTTS_ERR_ARG = -2  # include/edtts.h: the one error code _errcheck tells apart
 
 vp, i32, i64, u32, u64, sz, f32, f64 = (C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float, C.c_double)
 p_vp, p_i32, p_i64, p_sz, p_f32, p_f64 = (C.POINTER(t) for t in (vp, i32, i64, sz, f32, f64))
-dp, sdp, hdp, drp = (C.POINTER(t) for t in (EdttsDims, EdttsSemDims, EdttsHubertDims, EdttsDropout))
+dp, sdp, hdp, drp, ddp = (C.POINTER(t) for t in (EdttsDims, EdttsSemDims, EdttsHubertDims, EdttsDropout, EdttsDropoutDev))
 
 # include/edtts.h in its order: name -> (kind of return, argument types).  tests/test_abi_host.py compares every entry with the
 # header's prototype, so a new export is one prototype there and one line here.
@@ -156,6 +173,10 @@ _ABI = {
     "edtts_decoder_forward_train_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, drp, vp, vp, vp)),
     "edtts_decoder_backward_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, drp, vp, vp,
                                              vp)),
+    "edtts_decoder_forward_train_dev": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, ddp, vp, vp, vp)),
+    "edtts_decoder_backward_dev": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, ddp, vp, vp,
+                                             vp)),
+    "edtts_dropout_mask_dev": (_STATUS, (dp, i32, i32, i32, i32, i32, ddp, vp, vp)),
     "edtts_ddim_step": (_STATUS, (vp, i32, vp, vp, vp, vp, i32, sz, f32, vp, vp, vp, vp)),
     "edtts_ddpm_step": (_STATUS, (vp, vp, vp, vp, i32, vp, vp, vp, i32, sz, vp, vp, vp)),
     "edtts_generate": (_STATUS, (dp, vp, vp, i32, i32, vp, vp, i32, p_i64, p_f32, vp, vp, vp)),
@@ -164,6 +185,8 @@ _ABI = {
     "edtts_sample_ddpm_len": (_STATUS, (dp, vp, vp, i32, i32, vp, vp, vp, i32, vp, p_f32, vp, u64, i64, vp, vp)),
     "edtts_randn": (_STATUS, (vp, sz, u64, u32, u64, f32, vp)),
     "edtts_randn_rows": (_STATUS, (vp, i32, sz, vp, u32, f32, vp)),
+    "edtts_keys_advance": (_STATUS, (vp, i32, vp, vp)),
+    "edtts_keys_host": (_STATUS, (u64, u64, i64, i32, C.POINTER(u64))),
     "edtts_sample_multistep": (_STATUS, (dp, vp, vp, i32, i32, i32, vp, vp, vp, i32, p_i64, p_f32, vp, vp, vp, vp)),
     "edtts_sample_multistep_len": (_STATUS, (dp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, p_i64, p_f32, vp, vp, vp, vp)),
     "edtts_sample_inpaint": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, p_f32, vp, i32, vp, u64, f32, vp, vp)),
@@ -200,6 +223,9 @@ _ABI = {
     "edtts_sem_encode_train": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, drp, vp)),
     "edtts_sem_backward": (_STATUS, (sdp, vp, vp, vp, vp, i32, i32, vp, vp, p_vp, i32, vp, vp, drp, vp)),
     "edtts_sem_dropout_mask": (_STATUS, (sdp, i32, i32, drp, vp, vp)),
+    "edtts_sem_encode_train_dev": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, ddp, vp)),
+    "edtts_sem_backward_dev": (_STATUS, (sdp, vp, vp, vp, vp, i32, i32, vp, vp, p_vp, i32, vp, vp, ddp, vp)),
+    "edtts_sem_dropout_mask_dev": (_STATUS, (sdp, i32, i32, ddp, vp, vp)),
     "edtts_sem_vq_train_packed_bytes": (_STATUS, (sdp, p_sz)),
     "edtts_sem_vq_train_pack": (_STATUS, (sdp, p_vp, i32, vp, vp)),
     "edtts_sem_vq_tape_bytes": (_STATUS, (sdp, i32, i32, p_sz)),
@@ -211,6 +237,8 @@ _ABI = {
     "edtts_optim_chunk_table": (_STATUS, (p_i64, i32, i32, p_i32, p_i64, p_i32, p_i32)),
     "edtts_optim_scratch_bytes": (_STATUS, (i32, i32, p_sz)),
     "edtts_optim_step": (_STATUS, (C.POINTER(EdttsOptimTensor), i32, C.POINTER(EdttsOptimGroup), i32, f64, i32, vp, sz, vp)),
+    "edtts_optim_upload": (_STATUS, (C.POINTER(EdttsOptimTensor), i32, C.POINTER(EdttsOptimGroup), i32, i32, vp, sz, p_i32, p_sz, vp)),
+    "edtts_optim_step_resident": (_STATUS, (i32, i32, f64, i32, vp, sz, vp, C.POINTER(EdttsOptimSchedule), vp)),
     "edtts_generic_slot_dest": (_STATUS, (dp, i32, p_sz, p_i32, p_i32, p_i32)),
     "edtts_hubert_frames": (_STATUS, (hdp, i64, p_i64)),
     "edtts_hubert_packed_bytes": (_STATUS, (hdp, p_sz)),
@@ -391,10 +419,25 @@ def train_dw_slab_rows(rows: int) -> int:
     return int(lib().edtts_train_dw_slab_rows(int(rows)))
 
 
-def _dropout(drop) -> Optional[EdttsDropout]:
-    """None, an EdttsDropout or a (p, seed) pair -> None or an EdttsDropout."""
-    if drop is None or isinstance(drop, EdttsDropout):
+class DropKey:
+    """Dropout with its Philox key in device memory: drop probability ``p`` (a host value) and ``key``, a 1-element int64 device
+    tensor (a KeyStream slot) that the kernels read when they run (include/edtts.h: EdttsDropoutDev)."""
+
+    def __init__(self, p: float, key: torch.Tensor):
+        if not isinstance(key, torch.Tensor) or key.dtype != torch.int64 or key.numel() != 1 or not key.is_cuda:
+            raise EdttsError("DropKey: key must be a 1-element int64 tensor on the HIP device")
+        self.p, self.key = float(p), key
+
+    def struct(self) -> EdttsDropoutDev:
+        return EdttsDropoutDev(self.p, self.key.data_ptr())
+
+
+def _dropout(drop):
+    """None, an EdttsDropout, a (p, seed) pair or a DropKey -> None, an EdttsDropout or an EdttsDropoutDev."""
+    if drop is None or isinstance(drop, (EdttsDropout, EdttsDropoutDev)):
         return drop
+    if isinstance(drop, DropKey):
+        return drop.struct()
     p, seed = drop
     return EdttsDropout(float(p), int(seed))
 
@@ -404,15 +447,19 @@ def decoder_forward_train(dims: EdttsDims, packed: torch.Tensor, workspace: torc
                           sem_features: Optional[torch.Tensor], S: int, drop=None, t_len: Optional[torch.Tensor] = None,
                           s_len: Optional[torch.Tensor] = None) -> torch.Tensor:
     """edtts_decoder_forward_train: eps, with the backward's tape written to `tape` (uint8, train_tape_bytes).  ``drop``: None (the
-    plain export), or an EdttsDropout / (p, seed) pair -> edtts_decoder_forward_train_drop.  ``t_len`` / ``s_len``: per-utterance
-    frame / token counts, device int64 [B] or None (see lengths()); with either, edtts_decoder_forward_train_len runs."""
+    plain export), or an EdttsDropout / (p, seed) pair -> edtts_decoder_forward_train_drop, or a DropKey ->
+    edtts_decoder_forward_train_dev.  ``t_len`` / ``s_len``: per-utterance frame / token counts, device int64 [B] or None (see
+    lengths()); with either, edtts_decoder_forward_train_len runs."""
     B, T, M = x.shape
     eps = torch.empty_like(x)
     drop = _dropout(drop)
     args = (C.byref(dims), packed.data_ptr(), workspace.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), B, T, S,
             _dev_ptr(x, torch.float32, "x_t"), _dev_ptr(t, torch.int64, "t"), _dev_ptr(step_idx, torch.int64, "step_idx"),
             _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"), eps.data_ptr())
-    if t_len is not None or s_len is not None:
+    if isinstance(drop, EdttsDropoutDev):
+        lib().edtts_decoder_forward_train_dev(*args, C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
+                                              _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
+    elif t_len is not None or s_len is not None:
         lib().edtts_decoder_forward_train_len(*args, None if drop is None else C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
                                               _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
     elif drop is None:
@@ -445,7 +492,10 @@ def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
             _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"),
             _dev_ptr(d_eps, torch.float32, "d_eps"), ptrs, len(grads), _dev_ptr(d_x, torch.float32, "d_x"),
             _dev_ptr(d_sem_features, torch.float32, "d_sem_features"), scratch.data_ptr())
-    if t_len is not None or s_len is not None:
+    if isinstance(drop, EdttsDropoutDev):
+        lib().edtts_decoder_backward_dev(*args, C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
+                                         _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
+    elif t_len is not None or s_len is not None:
         lib().edtts_decoder_backward_len(*args, None if drop is None else C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
                                          _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
     elif drop is None:
@@ -454,18 +504,23 @@ def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
         lib().edtts_decoder_backward_drop(*args, C.byref(drop), _stream(x.device))
 
 
-def dropout_mask(dims: EdttsDims, site: int, layer: int, B: int, T: int, S: int, p: float, seed: int, device="cuda") -> torch.Tensor:
+def dropout_mask(dims: EdttsDims, site: int, layer: int, B: int, T: int, S: int, p: float, seed, device="cuda") -> torch.Tensor:
     """edtts_dropout_mask: the keep mask (uint8, 1 = kept) of one dropout site of one layer, from the device functions the training
-    kernels call: [B, heads, T, T] (site 0), [B, heads, T, S] (1), [B * T, ffn_mult * hidden] (2) or [B * T, hidden] (3)."""
+    kernels call: [B, heads, T, T] (site 0), [B, heads, T, S] (1), [B * T, ffn_mult * hidden] (2) or [B * T, hidden] (3).  ``seed``: an
+    int, or a 1-element int64 device tensor holding it (edtts_dropout_mask_dev)."""
     shape = {0: (B, dims.heads, T, T), 1: (B, dims.heads, T, S), 2: (B * T, dims.ffn_mult * dims.hidden), 3: (B * T, dims.hidden)}.get(int(site))
     if shape is None:
         raise ValueError(f"site must be one of 0 .. 3 (DROP_SITES), got {site!r}")
-    drop = EdttsDropout(float(p), int(seed))
     dev = torch.device(device)
     if dev.type != "cuda":
         raise EdttsError(f"dropout_mask: expected a HIP device, got {dev} -- there is no CPU fallback")
     keep = torch.empty(shape, dtype=torch.uint8, device=dev)
-    lib().edtts_dropout_mask(C.byref(dims), int(site), int(layer), B, T, S, C.byref(drop), keep.data_ptr(), _stream(dev))
+    if isinstance(seed, torch.Tensor):
+        drop = DropKey(p, seed).struct()
+        lib().edtts_dropout_mask_dev(C.byref(dims), int(site), int(layer), B, T, S, C.byref(drop), keep.data_ptr(), _stream(dev))
+    else:
+        drop = EdttsDropout(float(p), int(seed))
+        lib().edtts_dropout_mask(C.byref(dims), int(site), int(layer), B, T, S, C.byref(drop), keep.data_ptr(), _stream(dev))
     return keep
 
 
@@ -835,6 +890,96 @@ def optim_step(tensors, n_tensors: int, groups, n_groups: int, max_norm: Optiona
                            _dev_ptr(scratch, torch.uint8, "scratch"), scratch.numel(), _stream(scratch.device))
 
 
+def optim_upload(tensors, n_tensors: int, groups, n_groups: int, flags: int, scratch: torch.Tensor) -> Tuple[int, int]:
+    """edtts_optim_upload: validate and copy the step's table into the scratch (not under capture) -> (number of chunks, byte offset
+    of the EdttsOptimGroup array in the scratch)."""
+    n_chunks, off = C.c_int(0), C.c_size_t(0)
+    lib().edtts_optim_upload(tensors, n_tensors, groups, n_groups, flags, _dev_ptr(scratch, torch.uint8, "scratch"), scratch.numel(),
+                             C.byref(n_chunks), C.byref(off), _stream(scratch.device))
+    return n_chunks.value, off.value
+
+
+def optim_schedule(kind: str, base_lr: float, min_lr: float, warmup_steps: int, total_steps: int) -> EdttsOptimSchedule:
+    """An EdttsOptimSchedule; kind: "cosine" (train_v2.cosine_lr_schedule)."""
+    kinds = {"cosine": EDTTS_SCHED_COSINE}
+    if kind not in kinds:
+        raise ValueError(f"schedule kind must be one of {sorted(kinds)}, got {kind!r}")
+    if not float(base_lr) >= 0.0 or not float(min_lr) >= 0.0 or int(warmup_steps) < 0 or int(total_steps) < 0:
+        raise ValueError(f"schedule: base_lr={base_lr} min_lr={min_lr} warmup_steps={warmup_steps} total_steps={total_steps}")
+    return EdttsOptimSchedule(kinds[kind], 0, float(base_lr), float(min_lr), int(warmup_steps), int(total_steps))
+
+
+def optim_step_resident(n_chunks: int, n_groups: int, max_norm: Optional[float], flags: int, scratch: torch.Tensor,
+                        lr_dev: Optional[torch.Tensor] = None, sched: Optional[EdttsOptimSchedule] = None) -> None:
+    """edtts_optim_step_resident on the current stream of the scratch's device: the step on the table optim_upload left in the
+    scratch (capturable).  lr_dev: fp64 [n_groups] device tensor or None; sched: an EdttsOptimSchedule or None."""
+    if max_norm is not None:
+        flags |= OPT_CLIP
+    if lr_dev is not None and (_dev_ptr(lr_dev, torch.float64, "lr_dev") is None or lr_dev.numel() != n_groups):
+        raise EdttsError(f"lr_dev: expected {n_groups} fp64 values, got {lr_dev.numel()}")
+    lib().edtts_optim_step_resident(int(n_chunks), int(n_groups), 0.0 if max_norm is None else float(max_norm), flags,
+                                    _dev_ptr(scratch, torch.uint8, "scratch"), scratch.numel(),
+                                    None if lr_dev is None else lr_dev.data_ptr(), None if sched is None else C.byref(sched),
+                                    _stream(scratch.device))
+
+
+# ---------------------------------------------------------------------------------------------- key stream
+def keys_host(base: int, counter: int, first: int, n: int) -> List[int]:
+    """edtts_keys_host: keys first .. first + n - 1 of call `counter` of the key stream with base seed `base`; no GPU call."""
+    out = (C.c_uint64 * max(int(n), 1))()
+    lib().edtts_keys_host(_u64(base), _u64(counter), C.c_int64(int(first)), int(n), out)
+    return [int(out[i]) for i in range(int(n))]
+
+
+class KeyStream:
+    """A device array of 63-bit Philox keys that one launch regenerates (include/edtts.h: edtts_keys_advance): ``n_slots`` dropout
+    keys followed by ``n_rows`` per-row noise seeds.  ``advance()`` is capturable: every replay of a graph that holds it writes the
+    keys of the next call counter.  ``take(owner, first_slot)`` hands a module its slots -- first_slot, first_slot + 1, ... for its
+    first, second, ... differentiable forward since the last ``advance()``, which returns every module's cursor to 0."""
+
+    def __init__(self, seed: int, n_slots: int, n_rows: int = 0, device="cuda"):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise EdttsError(f"KeyStream: expected a HIP device, got {dev} -- there is no CPU fallback")
+        if int(n_slots) < 0 or int(n_rows) < 0 or int(n_slots) + int(n_rows) < 1:
+            raise ValueError(f"KeyStream: n_slots={n_slots} n_rows={n_rows}")
+        self.seed, self.n_slots, self.n_rows = int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_slots), int(n_rows)
+        bits = ((self.seed ^ (1 << 63)) - (1 << 63))  # the uint64 bits as an int64
+        self.state = host_to_device(torch.tensor([bits, 0], dtype=torch.int64), dev)
+        self.keys = torch.zeros(self.n_slots + self.n_rows, dtype=torch.int64, device=dev)
+        self._cursors: dict = {}  # id(module) -> forwards it has made since the last advance()
+
+    def advance(self) -> None:
+        lib().edtts_keys_advance(self.keys.data_ptr(), self.keys.numel(), self.state.data_ptr(), _stream(self.keys.device))
+        self._cursors = {}
+
+    def slot(self, k: int) -> torch.Tensor:
+        if not 0 <= int(k) < self.n_slots:
+            raise IndexError(f"KeyStream: slot {k} outside [0, {self.n_slots})")
+        return self.keys[int(k):int(k) + 1]
+
+    def take(self, owner, first_slot: int = 0) -> torch.Tensor:
+        """Slot first_slot + (forwards `owner` has made since the last advance())."""
+        n = self._cursors.get(id(owner), 0)
+        k = int(first_slot) + n
+        if not 0 <= k < self.n_slots:
+            raise RuntimeError(f"KeyStream: {type(owner).__name__} asks for slot {k} (first_slot {first_slot}, forward {n + 1} since "
+                               f"advance()) of {self.n_slots}: one slot per differentiable forward of a step")
+        self._cursors[id(owner)] = n + 1
+        return self.slot(k)
+
+    def rows(self) -> torch.Tensor:
+        return self.keys[self.n_slots:]
+
+    def keys_at(self, counter: int) -> List[int]:
+        """What advance() wrote when the call counter stood at `counter`, recomputed on the host."""
+        return keys_host(self.seed, counter, 0, self.n_slots + self.n_rows)
+
+    def counter(self) -> int:
+        """Calls of advance() that have run (reads the device counter: synchronises)."""
+        return int(self.state[1].item()) & 0xFFFFFFFFFFFFFFFF
+
+
 # ---------------------------------------------------------------------------------------------- training objective
 class ObjBatch:
     """The arguments that define a prepared batch for edtts_objective_prepare / edtts_objective_loss (include/edtts.h, "training
@@ -1035,10 +1180,11 @@ def sem_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, 
     zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
     counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=dev) if want_counts else None
     drop = _dropout(drop)
-    lib().edtts_sem_encode_train(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
-                                 _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), zq.data_ptr(),
-                                 None if counts is None else counts.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"),
-                                 None if drop is None else C.byref(drop), _stream(dev))
+    fn = lib().edtts_sem_encode_train_dev if isinstance(drop, EdttsDropoutDev) else lib().edtts_sem_encode_train
+    fn(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
+       _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), zq.data_ptr(),
+       None if counts is None else counts.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"),
+       None if drop is None else C.byref(drop), _stream(dev))
     return idx, zq, counts
 
 
@@ -1051,21 +1197,27 @@ def sem_backward(dims: EdttsSemDims, packed: torch.Tensor, packed_train: torch.T
     ptrs = _slot_ptrs(grads, "grad")
     scratch = torch.empty(sem_train_scratch_bytes(dims, B, T), dtype=torch.uint8, device=h.device)
     drop = _dropout(drop)
-    lib().edtts_sem_backward(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(packed_train, torch.uint8, "packed_train"),
-                             _dev_ptr(tape, torch.uint8, "tape"), _dev_ptr(h, torch.float32, "features"), B, T,
-                             _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(d_zq, torch.float32, "d_zq"), ptrs, len(grads),
-                             _dev_ptr(d_z, torch.float32, "d_z"), scratch.data_ptr(), None if drop is None else C.byref(drop),
-                             _stream(h.device))
+    fn = lib().edtts_sem_backward_dev if isinstance(drop, EdttsDropoutDev) else lib().edtts_sem_backward
+    fn(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(packed_train, torch.uint8, "packed_train"),
+       _dev_ptr(tape, torch.uint8, "tape"), _dev_ptr(h, torch.float32, "features"), B, T,
+       _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(d_zq, torch.float32, "d_zq"), ptrs, len(grads),
+       _dev_ptr(d_z, torch.float32, "d_z"), scratch.data_ptr(), None if drop is None else C.byref(drop),
+       _stream(h.device))
 
 
-def sem_dropout_mask(dims: EdttsSemDims, B: int, T: int, p: float, seed: int, device="cuda") -> torch.Tensor:
-    """edtts_sem_dropout_mask: the keep mask (uint8, 1 = kept) [B * T, semantic_dim] of the head's dropout site."""
-    drop = EdttsDropout(float(p), int(seed))
+def sem_dropout_mask(dims: EdttsSemDims, B: int, T: int, p: float, seed, device="cuda") -> torch.Tensor:
+    """edtts_sem_dropout_mask: the keep mask (uint8, 1 = kept) [B * T, semantic_dim] of the head's dropout site.  ``seed``: an int, or a
+    1-element int64 device tensor holding it (edtts_sem_dropout_mask_dev)."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise EdttsError(f"sem_dropout_mask: expected a HIP device, got {dev} -- there is no CPU fallback")
     keep = torch.empty((B * T, dims.semantic_dim), dtype=torch.uint8, device=dev)
-    lib().edtts_sem_dropout_mask(C.byref(dims), B, T, C.byref(drop), keep.data_ptr(), _stream(dev))
+    if isinstance(seed, torch.Tensor):
+        drop = DropKey(p, seed).struct()
+        lib().edtts_sem_dropout_mask_dev(C.byref(dims), B, T, C.byref(drop), keep.data_ptr(), _stream(dev))
+    else:
+        drop = EdttsDropout(float(p), int(seed))
+        lib().edtts_sem_dropout_mask(C.byref(dims), B, T, C.byref(drop), keep.data_ptr(), _stream(dev))
     return keep
 
 

@@ -8,13 +8,14 @@ an attached ``EdgeDiffusionDecoder(kernels="generic")``, so the next forward pac
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import native
 
-__all__ = ["FusedAdamW", "CHUNK", "build_chunks"]
+__all__ = ["FusedAdamW", "CHUNK", "build_chunks", "cosine_lr"]
 
 
 def __getattr__(name):  # CHUNK comes from the library (edtts_optim_chunk_size): read on first use, so importing needs no build
@@ -26,6 +27,15 @@ def __getattr__(name):  # CHUNK comes from the library (edtts_optim_chunk_size):
 def build_chunks(numels) -> List[Tuple[int, int, int]]:
     """[(tensor index, first element, count)]: how a step cuts tensors of these sizes (the library's own table builder)."""
     return native.optim_chunk_table(list(numels))
+
+
+def cosine_lr(step: int, total_steps: int, warmup_steps: int, base_lr: float, min_lr: float = 1e-6) -> float:
+    """The learning rate ``train_v2.cosine_lr_schedule`` sets at ``step``: linear warm-up, then a cosine from base_lr to min_lr (the
+    formula continues past total_steps).  ``FusedAdamW.device_lr_schedule("cosine", ...)`` evaluates it on the device."""
+    if step < warmup_steps:
+        return base_lr * step / max(warmup_steps, 1)
+    progress = (step - warmup_steps) / max(total_steps - warmup_steps, 1)
+    return min_lr + 0.5 * (base_lr - min_lr) * (1 + math.cos(math.pi * progress))
 
 
 def _n_chunks(numel: int, chunk: int) -> int:
@@ -47,11 +57,22 @@ class FusedAdamW(torch.optim.Optimizer):
     without elements.  ONE device-resident step counter serves all parameters (it feeds the bias corrections): torch's per-parameter
     ``step`` is that counter for every parameter in ``state_dict()``, and ``load_state_dict()`` raises on unequal steps.
     Parameters must be contiguous fp32 tensors on one HIP device when ``step()`` runs; anything else raises.
-    ``step()`` never synchronises; ``state_dict()`` reads the counter and may."""
+    ``step()`` never synchronises; ``state_dict()`` reads the counter and may.
+
+    ``capturable=True``: the step runs on a table that stays in device memory (``edtts_optim_upload`` once, then
+    ``edtts_optim_step_resident``: no copy, no event, no host allocation), so it can be captured in a graph.
+    The first step must be eager: it allocates the state and uploads the table.  Every later step compares the live pointers and
+    hyper-parameters with the uploaded ones on the host; on a change it uploads again when the stream is not capturing and raises
+    ``RuntimeError`` when it is.  ``group["lr"]`` may be a float (baked in at upload) or a 0-dim fp64 device tensor, read by the
+    kernels at run time (``fill_`` it between replays, torch's capturable convention); ``device_lr_schedule`` makes the step
+    compute its own learning rate from its device-resident counters.  Results are bitwise those of ``capturable=False``."""
 
     def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 *, max_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False):
-        if not 0.0 <= lr:
+                 *, max_norm: Optional[float] = None, skip_nonfinite: bool = False, zero_grads: bool = False, capturable: bool = False):
+        if isinstance(lr, torch.Tensor):
+            if not capturable:
+                raise ValueError("FusedAdamW: a tensor lr needs capturable=True")
+        elif not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
             raise ValueError(f"Invalid epsilon value: {eps}")
@@ -74,6 +95,13 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ema: Dict = {}         # student parameter -> (teacher tensor, decay)
         self._ema_pairs: List = []   # every (student, teacher, decay) of attach_ema, for update_ema
         self._ema_scratch: Optional[torch.Tensor] = None
+        self.capturable = bool(capturable)
+        self._uploaded = None        # capturable: what the table in the scratch was built from
+        self._n_chunks = 0           # ... its number of chunks, and where its groups lie in the scratch
+        self._groups_offset = 0
+        self._lr_dev: Optional[torch.Tensor] = None   # fp64 [n_groups]: the run-time learning rates (tensor lrs are copied in each step)
+        self._sched = None           # device_lr_schedule
+        self._stepped = ([], [])     # the parameters and the mirrored decoders of the last step (replay_bookkeeping)
 
     # ------------------------------------------------------------------------------------------ attachments
     def attach_decoder(self, decoder) -> bool:
@@ -86,6 +114,7 @@ class FusedAdamW(torch.optim.Optimizer):
             return False
         idx = len(self._decoders)
         self._decoders.append(decoder)
+        decoder._blob.mirrored = True  # (under graph capture: a blob that a step keeps current is not packed inside the graph)
         for name, p in decoder.named_parameters():
             if name in table:
                 self._mirror[p] = (idx, *table[name])
@@ -122,6 +151,66 @@ class FusedAdamW(torch.optim.Optimizer):
             raise native.EdttsError(f"FusedAdamW: {what}: on {t.device}, the step runs on {dev}")
         return t.data_ptr()
 
+    def device_lr_schedule(self, kind: str, base_lr: float, min_lr: float = 1e-6, warmup_steps: int = 0, total_steps: int = 1) -> None:
+        """``capturable=True`` only: every step sets every group's lr itself, on the device, from the schedule evaluated at
+        n = steps taken + steps skipped before it.  ``"cosine"`` is ``train_v2.cosine_lr_schedule`` in fp64 (``cosine_lr`` is the
+        same formula on the host).  ``group["lr"]`` is then not read; ``current_lr()`` shows the values in force."""
+        if not self.capturable:
+            raise ValueError("FusedAdamW.device_lr_schedule needs capturable=True")
+        self._sched = native.optim_schedule(kind, base_lr, min_lr, warmup_steps, total_steps)
+
+    def current_lr(self) -> List[float]:
+        """``capturable=True``: each group's learning rate as the last step left it on the device (synchronises); before the first
+        step, the groups' own values."""
+        if not self.capturable or self._uploaded is None:
+            return [float(g["lr"]) for g in self.param_groups]
+        n, size, at = len(self.param_groups), native.OPTIM_GROUP_BYTES, native.OPTIM_GROUP_LR_OFFSET
+        raw = self._scratch[self._groups_offset:self._groups_offset + size * n].cpu().reshape(n, size)
+        return [float(v) for v in raw[:, at:at + 8].contiguous().view(torch.float64).reshape(n)]
+
+    def _resident_step(self, tab, n: int, groups, flags: int, scratch: torch.Tensor) -> None:
+        capturing = torch.cuda.is_current_stream_capturing()
+        n_groups = len(self.param_groups)
+        lrs = [g["lr"] for g in self.param_groups]
+        for lr in lrs:
+            if isinstance(lr, torch.Tensor) and (lr.dtype != torch.float64 or lr.dim() != 0 or lr.device != scratch.device):
+                raise native.EdttsError(f"FusedAdamW: a tensor lr must be a 0-dim fp64 tensor on {scratch.device}, got {lr.dtype} "
+                                        f"{list(lr.shape)} on {lr.device}")
+        # (the table as bytes: ctypes zero-fills its padding, so equal tables are equal bytes)
+        key = (bytes(tab), bytes(groups), tuple(isinstance(lr, torch.Tensor) for lr in lrs), flags)
+        if key != self._uploaded:
+            if capturing:
+                raise RuntimeError(f"FusedAdamW(capturable=True): the step's table changed under graph capture ({self._table_diff(key)}); "
+                                   "a captured step needs the pointers and hyper-parameters of the last eager step (keep the "
+                                   "gradients allocated: zero_grads=True, no zero_grad(set_to_none=True))")
+            self._n_chunks, self._groups_offset = native.optim_upload(tab, n, groups, n_groups, flags, scratch)
+            if self._lr_dev is None or self._lr_dev.device != scratch.device or self._lr_dev.numel() != n_groups:
+                self._lr_dev = torch.zeros(n_groups, dtype=torch.float64, device=scratch.device)
+            floats = torch.tensor([0.0 if isinstance(lr, torch.Tensor) else float(lr) for lr in lrs], dtype=torch.float64)
+            self._lr_dev.copy_(native.host_to_device(floats, scratch.device))
+            self._uploaded = key
+        lr_dev = None
+        if self._sched is None and any(isinstance(lr, torch.Tensor) for lr in lrs):
+            for g, lr in enumerate(lrs):
+                if isinstance(lr, torch.Tensor):
+                    self._lr_dev[g].copy_(lr)  # (device to device on the current stream: capturable)
+            lr_dev = self._lr_dev
+        native.optim_step_resident(self._n_chunks, n_groups, self.max_norm, flags, scratch, lr_dev, self._sched)
+
+    def _table_diff(self, key) -> str:
+        """What differs between the table of this step and the uploaded one, for an error message."""
+        old_t, old_g, old_kind, old_flags = self._uploaded
+        if len(key[0]) != len(old_t):
+            return "the number of tensors with a gradient"
+        size = native.OPTIM_TENSOR_BYTES
+        for i in range(0, len(key[0]), size):
+            if key[0][i:i + size] != old_t[i:i + size]:
+                field = next((f for f, at, n in native.OPTIM_TENSOR_FIELDS if key[0][i + at:i + at + n] != old_t[i + at:i + at + n]), "padding")
+                return f"tensor {i // size}: {field}"
+        if key[1] != old_g or key[2] != old_kind:
+            return "a group's lr, betas, eps or weight_decay"
+        return "the flags"
+
     def _ensure_scratch(self, dev) -> torch.Tensor:
         if self._scratch is None or self._scratch.device != dev:
             chunk = native.optim_chunk_size()
@@ -129,6 +218,7 @@ class FusedAdamW(torch.optim.Optimizer):
             step = self._read_step()
             self._scratch = torch.zeros(native.optim_scratch_bytes(n, len(self.param_groups)), dtype=torch.uint8, device=dev)
             self._scratch_chunks = n
+            self._uploaded = None  # (a new scratch holds no table)
             if step:
                 self._write_step(step)
         return self._scratch
@@ -159,6 +249,10 @@ class FusedAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         if closure is not None:
             raise ValueError("FusedAdamW.step: a closure is not supported (compute the loss and call backward() first)")
+        if self.capturable and self._uploaded is None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            # (before anything is allocated: memory made under capture would never be zero-filled)
+            raise RuntimeError("FusedAdamW(capturable=True): the first step() ran under graph capture; run one eager step first (it "
+                               "allocates the optimiser state and uploads the table of pointers)")
         live, dev = [], None
         for gi, group in enumerate(self.param_groups):
             if group.get("amsgrad") or group.get("maximize"):
@@ -186,6 +280,10 @@ class FusedAdamW(torch.optim.Optimizer):
             e.g = self._check(g, "gradient", dev)
             st = self.state[p]
             if "exp_avg" not in st:
+                if self.capturable and torch.cuda.is_current_stream_capturing():
+                    # (before its state is allocated: memory made under capture would never be zero-filled)
+                    raise RuntimeError(f"FusedAdamW(capturable=True): the step's table changed under graph capture (parameter {i} of the "
+                                       "step has a gradient for the first time); a captured step needs the tensors of the last eager step")
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
             e.m = self._check(st["exp_avg"], "exp_avg", dev)
@@ -208,24 +306,35 @@ class FusedAdamW(torch.optim.Optimizer):
         groups = (native.EdttsOptimGroup * len(self.param_groups))()
         for gi, group in enumerate(self.param_groups):
             q = groups[gi]
-            q.lr, q.eps, q.weight_decay = float(group["lr"]), float(group["eps"]), float(group["weight_decay"])
+            lr = group["lr"]
+            q.lr = 0.0 if self.capturable and isinstance(lr, torch.Tensor) else float(lr)
+            q.eps, q.weight_decay = float(group["eps"]), float(group["weight_decay"])
             q.beta1, q.beta2 = float(group["betas"][0]), float(group["betas"][1])
         scratch = self._ensure_scratch(dev)
         flags = (native.OPT_SKIP_NONFINITE if self.skip_nonfinite else 0) | (native.OPT_ZERO_GRADS if self.zero_grads else 0)
-        native.optim_step(tab, n, groups, len(self.param_groups), self.max_norm, flags, scratch)
-        # every cache keyed on the parameters' versions (the decoder blob, the semantic-head blobs) sees an in-place update
+        if self.capturable:
+            self._resident_step(tab, n, groups, flags, scratch)
+        else:
+            native.optim_step(tab, n, groups, len(self.param_groups), self.max_norm, flags, scratch)
+        self._stepped = ([p for _, p, _ in live], [d for d, blob in zip(self._decoders, blobs) if blob is not None])
+        self.replay_bookkeeping()
+        if self.max_norm is None:
+            return None
+        return scratch[16:20].view(torch.float32).reshape(()).clone()
+
+    def replay_bookkeeping(self) -> None:
+        """The host side of the last ``step()`` once more: what a replay of a graph that captured that step leaves undone.  Every
+        cache keyed on the parameters' versions (the decoder blob, the semantic-head blobs) sees an in-place update, and the
+        decoders whose blob the step mirrored are current again."""
+        params, decoders = self._stepped
         bump = torch.autograd.graph.increment_version
-        for _, p, _ in live:
+        for p in params:
             bump(p)
             ema = self._ema.get(p)
             if ema is not None:
                 bump(ema[0])
-        for d, blob in zip(self._decoders, blobs):
-            if blob is not None:
-                d._mirror_commit()
-        if self.max_norm is None:
-            return None
-        return scratch[16:20].view(torch.float32).reshape(()).clone()
+        for d in decoders:
+            d._mirror_commit()
 
     @torch.no_grad()
     def update_ema(self) -> None:

@@ -276,9 +276,10 @@ int edtts_decoder_backward(const EdttsDims* dims, const void* packed, void* work
  *
  * drop == NULL or drop->p == 0: exactly the launches of the plain entry point, bitwise its results (the plain entry points ARE these
  * calls with NULL).  The backward must be given the EdttsDropout its forward was given.  Tape and scratch sizes are those of the
- * plain calls (the dropped activations take the place of the undropped ones on the tape).  The seed travels BY VALUE in the
- * kernel arguments: no allocation, no host synchronisation, work only on `stream`, and a captured graph replays the masks it was
- * captured with (re-capture, or update the kernel node parameters, to advance them).
+ * plain calls (the dropped activations take the place of the undropped ones on the tape).  With an EdttsDropout the seed travels
+ * BY VALUE in the kernel arguments: no allocation, no host synchronisation, work only on `stream`, and a captured graph replays
+ * the masks it was captured with.  With an EdttsDropoutDev (the *_dev entry points below, "dropout key in device memory") the
+ * kernels read the seed from device memory when they run, so a captured graph draws the masks of whatever key its replay finds.
  *
  * edtts_dropout_mask writes the keep mask of one (site, layer) as 0 / 1 bytes through the device functions the kernels call:
  * [B, heads, T, T] (site 0), [B, heads, T, S] (site 1), [B * T, ffn_mult * hidden] (site 2) or [B * T, hidden] (site 3). */
@@ -345,6 +346,31 @@ int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* 
                                const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
                                float* d_sem_features, void* scratch, const EdttsDropout* drop, const int64_t* t_len,
                                const int64_t* s_len, void* stream);
+
+/* ---- dropout key in device memory --------------------------------------------------------------------
+ * The *_dev twins take the arguments of edtts_decoder_forward_train_len, edtts_decoder_backward_len and edtts_dropout_mask with an
+ * EdttsDropoutDev in place of the EdttsDropout: p (and with it thr and the scale) stays a host value, the Philox key is one uint64
+ * in device memory (8-byte aligned; NULL is EDTTS_ERR_ARG) that every kernel which applies a mask loads once, at an address that is
+ * the same for all lanes, before its first draw.  A mask stays the pure function of (key, site, layer, position) described above:
+ * with *key == seed every result is bitwise the EdttsDropout call's.  The key must hold the same value when the backward runs as
+ * when its forward ran.  drop == NULL or p == 0: the plain launches.  Nothing else differs: no allocation, no synchronisation, and
+ * the calls are graph-capturable with a key that changes between replays (edtts_keys_advance writes such keys). */
+struct EdttsDropoutDev {
+  float p;             /* drop probability, as EdttsDropout.p */
+  const uint64_t* key; /* device memory: the Philox key */
+};
+typedef struct EdttsDropoutDev EdttsDropoutDev;
+int edtts_decoder_forward_train_dev(const EdttsDims* dims, const void* packed, void* workspace, void* tape, int B, int T, int S,
+                                    const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                    const float* sem_features, float* eps, const EdttsDropoutDev* drop, const int64_t* t_len,
+                                    const int64_t* s_len, void* stream);
+int edtts_decoder_backward_dev(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                               const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                               const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
+                               float* d_sem_features, void* scratch, const EdttsDropoutDev* drop, const int64_t* t_len,
+                               const int64_t* s_len, void* stream);
+int edtts_dropout_mask_dev(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropoutDev* drop, uint8_t* keep,
+                           void* stream);
 
 /* ---- DDIM update  (schedule.py:157-202, DiffusionSchedule.get_ddim_step) --------------------------------
  * alpha_bar [n_table] fp32 table; t, t_prev [B] int64 (t_prev < 0 -> alpha_bar_prev = 1); n_per_batch =
@@ -417,6 +443,7 @@ int edtts_sample_ddpm_len(const EdttsDims* dims, const void* packed, void* works
  *     0x30000 + 4 * layer + site   dropout masks of the training forward and backward (edtts_decoder_forward_train_drop; layers
  *                         <= 32: [0x30000, 0x30080)), keyed by position as described there, not by global element
  *     0x40000             dropout mask of the semantic head's proj (edtts_sem_encode_train), keyed by position as sites 2 and 3
+ *     0x50000             the key stream (edtts_keys_advance): counter = (slot, call lo, 0x50000, call hi), see there
  * edtts_randn rejects stream_id >= 0x10000. */
 int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_t elem_offset, float scale, void* stream);
 /* One launch for B rows with a seed each: out [B, n_per_row], row b bitwise what edtts_randn(n_per_row, seeds[b], stream_id, offset 0,
@@ -424,6 +451,18 @@ int edtts_randn(float* out, size_t n, uint64_t seed, uint32_t stream_id, uint64_
  * seeds: device uint64 [B].  n_per_row need not be a multiple of 4 (element e of a row is lane e & 3 of draw e >> 2, as in
  * edtts_randn); out is 16-byte aligned when it is.  B = 0 or n_per_row = 0 is a no-op. */
 int edtts_randn_rows(float* out, int B, size_t n_per_row, const uint64_t* seeds, uint32_t stream_id, float scale, void* stream);
+
+/* ---- key stream: Philox keys that a captured graph regenerates on every replay -------------------------
+ * state: device uint64 [2] = (base seed, call counter c); keys: device uint64 [n].  edtts_keys_advance writes
+ *     keys[i] = K(base, c, i) for i in [0, n)   and then   state[1] = c + 1
+ * in one launch of one block (a block-stride loop; a barrier stands between the last read of c and its store).  With
+ * w = philox4x32_10(key = (base lo, base hi), counter = (i, c lo, 0x50000, c hi)):  K = (w[0] | w[1] << 32) with bit 63 cleared --
+ * 63 bits, a legal int64 row seed for edtts_objective_prepare and a key for EdttsDropoutDev.  No allocation, no host
+ * synchronisation, graph-capturable: every replay finds the counter its predecessor left and writes the next keys.
+ * edtts_keys_host is the same function on the host (no GPU call): out[j] = K(base, counter, first + j) for j in [0, n), so the keys
+ * of any replay can be recomputed.  first + n <= 2^32. */
+int edtts_keys_advance(uint64_t* keys, int n, uint64_t* state, void* stream);
+int edtts_keys_host(uint64_t base, uint64_t counter, int64_t first, int n, uint64_t* out);
 
 /* ---- multistep x0-solver sampler  (schedule.py:440-527, DPMSolverPP.sample with the updates of :339-438) -------
  * For step i = 0 .. num_steps-1 (t = timesteps_host[i], step_idx = i as in schedule.py:475-479):
@@ -713,6 +752,13 @@ int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void*
                        int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z,
                        void* scratch, const EdttsDropout* drop, void* stream);
 int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream);
+/* ... with the key in device memory ("dropout key in device memory" above): bitwise the calls above when *key == seed. */
+int edtts_sem_encode_train_dev(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths,
+                               int64_t* idx, float* z_q, int32_t* counts, void* tape, const EdttsDropoutDev* drop, void* stream);
+int edtts_sem_backward_dev(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
+                           int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z,
+                           void* scratch, const EdttsDropoutDev* drop, void* stream);
+int edtts_sem_dropout_mask_dev(const EdttsSemDims* dims, int B, int T, const EdttsDropoutDev* drop, uint8_t* keep, void* stream);
 
 /* ---- training the VQ head  (train.py: VectorQuantizer.forward in training mode, models/vq.py:86-93, 109-145) ----------------------
  * EDTTS_SEM_VQ only (EDTTS_ERR_UNSUPPORTED for EDTTS_SEM_FSQ), fp32.  With flat = the N valid frames of z and C the codebook the
@@ -791,7 +837,21 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
  * by events (only with more than 8 steps outstanding does the host wait for the oldest copy).  Steps that share a scratch must
  * be issued on one stream, or ordered by the caller.  Tensors with numel 0 are skipped; a call without any element returns at
  * once and changes nothing.  Pointers must be 4-byte aligned; a tensor whose pointers are all 16-byte aligned takes 16-byte
- * loads and stores.  Not graph-capturable as a unit (lr is a host argument and the table is copied from the host). */
+ * loads and stores.  edtts_optim_step is not graph-capturable (lr is a host argument and the table is copied from the host); the
+ * resident pair below is.
+ *
+ * Resident step.  edtts_optim_upload validates tensors / groups exactly as edtts_optim_step does and copies the same table into the
+ * scratch (not capturable: EDTTS_ERR_ARG while `stream` is capturing); it returns the number of chunks, which the resident step
+ * needs besides the scratch, and the byte offset of the EdttsOptimGroup array inside the scratch (where a caller may read the
+ * learning rates in force).  edtts_optim_step_resident then launches the step's kernels on the table that lies in the scratch: no
+ * copy, no event, no host allocation -- capturable, and bitwise edtts_optim_step on the same table.  The learning rate: with lr_dev
+ * (device fp64 [n_groups]) group g takes lr_dev[g]; otherwise with sched (kind != EDTTS_SCHED_NONE) every group takes the schedule's
+ * value; both may be NULL and then the uploaded lr holds.  The value is stored into the scratch's groups before the step sizes are
+ * formed from it, on a skipped step too.  EDTTS_SCHED_COSINE is train_v2.cosine_lr_schedule in fp64, evaluated at
+ * n = state.step + state.skipped as they stand before this step's increment (a skipped step still advances the schedule, as the
+ * reference's global_step does):  n < warmup_steps: base_lr * n / max(warmup_steps, 1);  otherwise
+ * min_lr + 0.5 * (base_lr - min_lr) * (1 + cos(pi * (n - warmup_steps) / max(total_steps - warmup_steps, 1))), past total_steps too.
+ * EDTTS_OPT_EMA_ONLY has no resident form. */
 typedef struct EdttsOptimState {
   int64_t step;      /* steps taken (skipped ones not counted)                               */
   int64_t skipped;   /* steps skipped by EDTTS_OPT_SKIP_NONFINITE                            */
@@ -828,6 +888,21 @@ int edtts_optim_chunk_table(const int64_t* numels, int n_tensors, int cap, int32
 int edtts_optim_scratch_bytes(int n_chunks, int n_groups, size_t* out_bytes);
 int edtts_optim_step(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, double max_norm, int flags,
                      void* scratch, size_t scratch_bytes, void* stream);
+enum {
+  EDTTS_SCHED_NONE = 0,
+  EDTTS_SCHED_COSINE = 1
+};
+struct EdttsOptimSchedule {
+  int32_t kind;         /* EDTTS_SCHED_* */
+  int32_t reserved;
+  double base_lr, min_lr;
+  int64_t warmup_steps, total_steps;
+};
+typedef struct EdttsOptimSchedule EdttsOptimSchedule;
+int edtts_optim_upload(const EdttsOptimTensor* tensors, int n_tensors, const EdttsOptimGroup* groups, int n_groups, int flags, void* scratch,
+                       size_t scratch_bytes, int* n_chunks, size_t* groups_offset, void* stream);
+int edtts_optim_step_resident(int n_chunks, int n_groups, double max_norm, int flags, void* scratch, size_t scratch_bytes, const double* lr_dev,
+                              const EdttsOptimSchedule* sched, void* stream);
 /* Where edtts_pack_weights puts weight slot `slot` of a generic fp32 layout (dims.compute_dtype = EDTTS_F32 | EDTTS_KERNELS_GENERIC;
  * anything else is EDTTS_ERR_UNSUPPORTED): its offset in floats, the slot's [rows][cols] (a vector: 1 x n) and whether the blob
  * holds its transpose [cols][rows] (time_emb.1 / .3 and the two AdaLN projections of a layer).  Layout arithmetic from the same
