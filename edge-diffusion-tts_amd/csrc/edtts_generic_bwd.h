@@ -770,17 +770,20 @@ struct TrainScratch {
   size_t part;
   size_t total;
 };
-static void make_train_scratch(const Layout& lo, int B, int T, int S, TrainScratch* s) {
+// The scratch's members, stated once: f(which, member, n) for each of them in scratch order -- `which` its EDTTS_SCRATCH_* name,
+// `member` its place in *s, n its float count.  make_train_scratch lays the scratch out from it, edtts_train_scratch_region answers
+// from it; the backward reaches the members through the offsets it filled.
+template <class Scratch, class F>
+static void scratch_regions(const Layout& lo, int B, int T, int S, Scratch& s, F&& f) {
   const size_t H = lo.H, M = (size_t)B * T, CS = (size_t)B * S, FH = (size_t)lo.FM * H, R = lo.R;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o = align64(o + n); return r; };
   auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
-  s->dh = take(M * H); s->xn = take(M * H); s->ga = take(M * H); s->gq = take(M * H);
-  s->big = take(M * mx(2 * FH, 3 * H)); s->da = take(M * FH);
-  s->stat = take(2 * mx(M, CS)); s->delta = take(M * lo.HEADS);
-  s->dkv = take(CS * 2 * H); s->crn = take(CS * R); s->dcr = take(CS * R); s->dcp = take(CS * R); s->dctx = take(CS * H);
-  s->dmod = take((size_t)B * lo.L * 4 * H); s->dtc = take((size_t)B * H); s->e = take((size_t)B * H); s->a1 = take((size_t)B * H);
-  s->u1 = take((size_t)B * H); s->du1 = take((size_t)B * H);
+  f(EDTTS_SCRATCH_DH, s.dh, M * H); f(EDTTS_SCRATCH_XN, s.xn, M * H); f(EDTTS_SCRATCH_GA, s.ga, M * H); f(EDTTS_SCRATCH_GQ, s.gq, M * H);
+  f(EDTTS_SCRATCH_BIG, s.big, M * mx(2 * FH, 3 * H)); f(EDTTS_SCRATCH_DA, s.da, M * FH);
+  f(EDTTS_SCRATCH_STAT, s.stat, 2 * mx(M, CS)); f(EDTTS_SCRATCH_DELTA, s.delta, M * lo.HEADS);
+  f(EDTTS_SCRATCH_DKV, s.dkv, CS * 2 * H); f(EDTTS_SCRATCH_CRN, s.crn, CS * R); f(EDTTS_SCRATCH_DCR, s.dcr, CS * R);
+  f(EDTTS_SCRATCH_DCP, s.dcp, CS * R); f(EDTTS_SCRATCH_DCTX, s.dctx, CS * H);
+  f(EDTTS_SCRATCH_DMOD, s.dmod, (size_t)B * lo.L * 4 * H); f(EDTTS_SCRATCH_DTC, s.dtc, (size_t)B * H); f(EDTTS_SCRATCH_E, s.e, (size_t)B * H);
+  f(EDTTS_SCRATCH_A1, s.a1, (size_t)B * H); f(EDTTS_SCRATCH_U1, s.u1, (size_t)B * H); f(EDTTS_SCRATCH_DU1, s.du1, (size_t)B * H);
   // partial slabs: the largest of the dW partials (slab count of its row sum x [N][K]), the bias partials and the norm partials
   size_t part = 0;
   auto dwp = [&](size_t rows, size_t n, size_t k) {
@@ -795,9 +798,18 @@ static void make_train_scratch(const Layout& lo, int B, int T, int S, TrainScrat
   part = mx(part, (CS + cr - 1) / cr * H);
   const size_t cpb = ((size_t)mx(T, S) + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
   part = mx(part, (size_t)B * cpb * 3 * H);                        // norm partials: [chunk][3][W]
-  s->part = take(part);
+  f(EDTTS_SCRATCH_PART, s.part, part);
+}
+static void make_train_scratch(const Layout& lo, int B, int T, int S, TrainScratch* s) {
+  size_t o = 0;
+  scratch_regions(lo, B, T, S, *s, [&](int, size_t& m, size_t n) { m = o; o = align64(o + n); });
   s->total = o;
 }
+
+// Where the backward stops (edtts_decoder_backward_until): after the last launch of site `site` of layer `layer`.  site < 0: never.
+struct BwdStop {
+  int layer = -1, site = -1;
+};
 
 // =========================================================================================================
 // TrainLauncher: forward with a tape, backward from it
@@ -980,8 +992,12 @@ struct TrainLauncher {
   static int backward(const Layout& lo, const float* blob, const float* tp, const TrainTape& tt, float* sc, const TrainScratch& ss, int B, int T,
                       int S, int window, const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_feat,
                       const float* d_eps, float* const* gs, float* d_x, float* d_sem, hipStream_t stream, const DropState* drop = nullptr,
-                      const Lens& ln = Lens{}) {
+                      const Lens& ln = Lens{}, const BwdStop stop = BwdStop{}) {
     using namespace edtts_gen;
+    // The sites of edtts_decoder_backward_until (EDTTS_BWD_*, include/edtts.h): one line of the launch list below each.  The head's and
+    // the tail's sites carry layer 0; `stop` never matches in the plain entry points (site -1), whose launch list is the whole of it.
+#define EDTTS_STOP_AFTER(layer_, site_) \
+  if (stop.site == (site_) && stop.layer == (layer_)) return EDTTS_OK
     const MmStream st{stream, lo.MM16 != 0};  // every dx / dw / recomputation below follows the layout's matmul_dtype
     // Per-utterance lengths: tr / sr mask every contraction over decoder / context rows and zero the dead
     // rows of every dX; the elementwise steps in between run on all rows (what they make of a dead row is never loaded again).
@@ -999,8 +1015,10 @@ struct TrainLauncher {
     TRY_G(colsum(st, d_eps, MEL, M, MEL, GG(G_OUT_B), part, tr));
     TRY_G(G::norm<NORM_LAYER>(st, tp + tt.hL, xn, M, H, blob + lo.fnw, blob + lo.fnb, 1e-5f));
     TRY_G(linear_bwd(st, d_eps, MEL, xn, blob + lo.s_outp, M, MEL, H, nullptr, GG(G_OUT_W), ga, part, tr));  // (its bias: summed above)
+    EDTTS_STOP_AFTER(0, EDTTS_BWD_OUT);
     TRY_G(norm_bwd<NORM_LAYER>(st, tp + tt.hL, ga, dh, false, M, H, T, blob + lo.fnw, 1e-5f, nullptr, 0, stat, part, GG(G_FN_W), GG(G_FN_B),
                                nullptr, 0, ln.t));
+    EDTTS_STOP_AFTER(0, EDTTS_BWD_FNORM);
     for (int l = L - 1; l >= 0; --l) {
       const LayerLayout& y = lo.layer[l];
       const TapeLayer& z = tt.layer[l];
@@ -1017,43 +1035,61 @@ struct TrainLauncher {
         LAUNCH_CHECK("k_bwd_drop_rows");
         dd = gq;
       }
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_DROPDOWN);
       TRY_G(linear_bwd(st, dd, H, tp + z.act, blob + y.g_down, M, H, FH, W(L_DOWN_B), W(L_DOWN_W), da, part, tr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_DOWN);
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h2, xn, M, H, blob + y.n3w, nullptr, 1e-6f, cond_row + l * row + 2 * H, T, cb));
       TRY_G(G::gemm<EPI_BIAS>(st, xn, H, blob + y.g_up, blob + y.up_b, big, 2 * FH, M, 2 * FH, H));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_UPRE);
       if (drop)
         hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu_drop, dim3(G::grid_1d(((size_t)M * FH + 3) / 4)), dim3(256), 0, st, big, da, (size_t)M, FH,
                            dra[DROP_ACT]);
       else
         hipLaunchKernelGGL(edtts_bwd::k_bwd_swiglu, dim3(G::grid_1d((size_t)M * FH)), dim3(256), 0, st, big, da, (size_t)M, FH);
       LAUNCH_CHECK("k_bwd_swiglu");
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_SWIGLU);
       TRY_G(linear_bwd(st, big, 2 * FH, xn, blob + y.g_up, M, 2 * FH, H, W(L_UP_B), W(L_UP_W), ga, part, tr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_UP);
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h2, ga, dh, true, M, H, T, blob + y.n3w, 1e-6f, cond_row + l * row + 2 * H, cb, stat, part, W(L_N3_W),
                                nullptr, dmod + l * row + 2 * H, cb, ln.t));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_N3);
       // cross-attention branch: h2 = h1 + att2 Wop^T
       TRY_G(linear_bwd(st, dh, H, tp + z.att2, blob + y.g_op, M, H, H, nullptr, W(L_OP_W), ga, part, tr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_OP);
       TRY_G(attn_bwd(st, lo, B, tp + z.qc, H, tp + z.kv, (tp + z.kv) + H, 2 * H, tp + z.att2, ga, tp + z.lse2, delta, gq, H, dkv, dkv + H, 2 * H, T,
                      S, -1, D(DROP_CROSS), ln.t, ln.s));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_CROSS);
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h1, xn, M, H, blob + y.n2w, nullptr, 1e-6f));
       TRY_G(linear_bwd(st, gq, H, xn, blob + y.g_qp, M, H, H, nullptr, W(L_QP_W), ga, part, tr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_QP);
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h1, ga, dh, true, M, H, T, blob + y.n2w, 1e-6f, nullptr, 0, stat, part, W(L_N2_W), nullptr, nullptr, 0, ln.t));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_N2);
       // ... and its context chain: context -> kv_down -> kv_norm -> kv_up -> K|V
       TRY_G(G::norm<NORM_RMS>(st, tp + z.crp, crn, CS, R, blob + y.kvn, nullptr, 1e-6f));
       TRY_G(linear_bwd(st, dkv, 2 * H, crn, blob + y.kvu, CS, 2 * H, R, nullptr, W(L_KVU_W), dcr, part, sr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_KVU);
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.crp, dcr, dcp, false, CS, R, S, blob + y.kvn, 1e-6f, nullptr, 0, stat, part, W(L_KVN_W), nullptr,
                                nullptr, 0, ln.s));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_KVN);
       TRY_G(linear_bwd(st, dcp, R, tp + tt.ctx, blob + y.kvd, CS, R, H, nullptr, W(L_KVD_W), dctx, part, sr, true));  // (dctx: summed over layers)
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_KVD);
       // self-attention branch: h1 = h0 + att1 Wproj^T + b
       TRY_G(linear_bwd(st, dh, H, tp + z.att1, blob + y.g_proj, M, H, H, W(L_PROJ_B), W(L_PROJ_W), ga, part, tr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_PROJ);
       const Act qkv = tp + z.qkv;
       TRY_G(attn_bwd(st, lo, B, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, tp + z.att1, ga, tp + z.lse1, delta, big, 3 * H, big + H, big + 2 * H,
                      3 * H, T, T, window, D(DROP_ATTN), ln.t, ln.t));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_SELF);
       TRY_G(G::norm<NORM_RMS>(st, tp + z.h0, xn, M, H, blob + y.n1w, nullptr, 1e-6f, cond_row + l * row, T, cb));
       TRY_G(linear_bwd(st, big, 3 * H, xn, blob + y.s_qkv, M, 3 * H, H, nullptr, W(L_QKV_W), ga, part, tr));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_QKV);
       TRY_G(norm_bwd<NORM_RMS>(st, tp + z.h0, ga, dh, true, M, H, T, blob + y.n1w, 1e-6f, cond_row + l * row, cb, stat, part, W(L_N1_W), nullptr,
                                dmod + l * row, cb, ln.t));
+      EDTTS_STOP_AFTER(l, EDTTS_BWD_N1);
     }
     // in_proj
     TRY_G(linear_bwd(st, dh, H, x, blob + lo.inp, M, H, MEL, GG(G_INP_B), GG(G_INP_W), d_x, part, tr));
+    EDTTS_STOP_AFTER(0, EDTTS_BWD_INP);
     // context sources
     if (sem_feat) {
       TRY_G(linear_bwd(st, dctx, H, sem_feat, blob + lo.semp, CS, H, lo.SD, GG(G_SEMP_B), GG(G_SEMP_W), d_sem, part, sr));
@@ -1066,8 +1102,9 @@ struct TrainLauncher {
       hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NTOK), dim3(256), 0, st, sem_idx, CS, lo.NTOK, dctx, H, GG(G_TOK), ln.s, S);
       LAUNCH_CHECK("k_bwd_scatter_rows");
     }
+    if (GG(G_STEP) && !step_idx) HIP_TRY(hipMemsetAsync(GG(G_STEP), 0, (size_t)lo.NSTEP * H * sizeof(float), st));  // (likewise)
+    EDTTS_STOP_AFTER(0, EDTTS_BWD_SEM);
     // conditioning path: AdaLN projections, then the time MLP and step_emb
-    if (GG(G_STEP) && !step_idx) HIP_TRY(hipMemsetAsync(GG(G_STEP), 0, (size_t)lo.NSTEP * H * sizeof(float), st));
     bool any_proj = false;
     for (int l = 0; l < L; ++l)
       any_proj = any_proj || gs[G_COUNT + l * L_COUNT + L_N1P_W] || gs[G_COUNT + l * L_COUNT + L_N1P_B] ||
@@ -1086,12 +1123,14 @@ struct TrainLauncher {
         TRY_G(linear_bwd(st, dm, cb, tcond, blob + (which ? y.ada3T : y.ada1T), B, 2 * H, H, gb, gw, dtc, part, RowLens{}, true, true));
       }
     }
+    EDTTS_STOP_AFTER(0, EDTTS_BWD_ADA);
     if (!any_time) return EDTTS_OK;
     if (GG(G_STEP) && step_idx) {
       hipLaunchKernelGGL(edtts_bwd::k_bwd_scatter_rows, dim3(lo.NSTEP), dim3(256), 0, st, step_idx, B, lo.NSTEP, dtc, H, GG(G_STEP),
                          (const int64_t*)nullptr, 0);
       LAUNCH_CHECK("k_bwd_scatter_rows");
     }
+    EDTTS_STOP_AFTER(0, EDTTS_BWD_STEP);
     // t_cond = W3 GELU(W1 e + b1) + b3: recompute e, the pre-activation and the hidden row
     hipLaunchKernelGGL(edtts_bwd::k_bwd_time_emb, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, t, blob + lo.freqs, B, H, e);
     LAUNCH_CHECK("k_bwd_time_emb");
@@ -1107,7 +1146,24 @@ struct TrainLauncher {
     TRY_G(linear_bwd(st, dtc, H, u1, blob + lo.t3T, B, H, H, GG(G_T3_B), GG(G_T3_W), du1, part, RowLens{}, false, true));
     hipLaunchKernelGGL(edtts_bwd::k_bwd_gelu_grad, dim3(G::grid_1d((size_t)B * H)), dim3(256), 0, st, du1, a1, B * H);
     LAUNCH_CHECK("k_bwd_gelu_grad");
-    return linear_bwd(st, du1, H, e, nullptr, B, H, H, GG(G_T1_B), GG(G_T1_W), nullptr, part);
+    return linear_bwd(st, du1, H, e, nullptr, B, H, H, GG(G_T1_B), GG(G_T1_W), nullptr, part);  // (EDTTS_BWD_TIME: the call's end)
+#undef EDTTS_STOP_AFTER
+  }
+  // Which of the tail's optional sites a call with these gradient slots has (the launch list above skips the others)
+  static bool has_site(const Layout& lo, float* const* gs, const int64_t* step_idx, bool dropping, int site) {
+    using namespace edtts_gen;
+    bool any_proj = false;
+    for (int l = 0; l < lo.L; ++l)
+      any_proj = any_proj || gs[G_COUNT + l * L_COUNT + L_N1P_W] || gs[G_COUNT + l * L_COUNT + L_N1P_B] ||
+                 gs[G_COUNT + l * L_COUNT + L_N3P_W] || gs[G_COUNT + l * L_COUNT + L_N3P_B];
+    const bool any_time = gs[G_T1_W] || gs[G_T1_B] || gs[G_T3_W] || gs[G_T3_B] || gs[G_STEP];
+    switch (site) {
+      case EDTTS_BWD_DROPDOWN: return dropping;
+      case EDTTS_BWD_ADA: return any_proj || any_time;
+      case EDTTS_BWD_STEP: return any_time && gs[G_STEP] && step_idx;
+      case EDTTS_BWD_TIME: return any_time;
+      default: return site >= 0 && site < EDTTS_BWD_COUNT;
+    }
   }
 };
 
@@ -1148,7 +1204,8 @@ static int decoder_forward_train_impl(const EdttsDims* dims, const void* packed,
 static int decoder_backward_impl(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
                                  const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                                  const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
-                                 const EdttsDropout* drop, const uint64_t* key, const int64_t* t_len, const int64_t* s_len, void* stream);
+                                 const EdttsDropout* drop, const uint64_t* key, const int64_t* t_len, const int64_t* s_len, void* stream,
+                                 BwdStop stop = BwdStop{});
 static int dropout_mask_impl(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, const uint64_t* key,
                              uint8_t* keep, void* stream);
 
@@ -1197,6 +1254,22 @@ int edtts_train_scratch_bytes(const EdttsDims* dims, int B, int T, int S, size_t
   TrainScratch ss;
   make_train_scratch(lo, B, T, S, &ss);
   *out_bytes = ss.total * sizeof(float);
+  return EDTTS_OK;
+}
+
+int edtts_train_scratch_region(const EdttsDims* dims, int B, int T, int S, int which, size_t* offset_bytes, size_t* bytes) {
+  Layout lo;
+  TRY_G(train_layout(dims, "edtts_train_scratch_region", &lo));
+  if (!offset_bytes || !bytes) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  TRY_G(check_shapes(lo, B, T, S));
+  TrainScratch ss;
+  make_train_scratch(lo, B, T, S, &ss);
+  bool found = false;
+  const TrainScratch& cs = ss;
+  scratch_regions(lo, B, T, S, cs, [&](int w, const size_t& m, size_t n) {
+    if (w == which) { *offset_bytes = m * sizeof(float); *bytes = n * sizeof(float); found = true; }
+  });
+  if (!found) return fail(EDTTS_ERR_ARG, "edtts_train_scratch_region: which=%d is not one of EDTTS_SCRATCH_DH .. EDTTS_SCRATCH_PART", which);
   return EDTTS_OK;
 }
 
@@ -1286,6 +1359,16 @@ int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* 
                                d_sem_features, scratch, drop, nullptr, t_len, s_len, stream);
 }
 
+int edtts_decoder_backward_until(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                 const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
+                                 const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
+                                 const EdttsDropout* drop, const int64_t* t_len, const int64_t* s_len, int stop_layer, int stop_site,
+                                 void* stream) {
+  if (stop_site < 0) return fail(EDTTS_ERR_ARG, "edtts_decoder_backward_until: stop_site %d is not one of EDTTS_BWD_*", stop_site);
+  return decoder_backward_impl(dims, packed, workspace, tape, B, T, S, x, t, step_idx, sem_idx, sem_features, d_eps, grad_slots, n_slots, d_x,
+                               d_sem_features, scratch, drop, nullptr, t_len, s_len, stream, BwdStop{stop_layer, stop_site});
+}
+
 int edtts_decoder_backward_dev(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
                                const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                                const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
@@ -1314,7 +1397,8 @@ int edtts_dropout_mask_dev(const EdttsDims* dims, int site, int layer, int B, in
 static int decoder_backward_impl(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
                                  const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx, const float* sem_features,
                                  const float* d_eps, void* const* grad_slots, int n_slots, float* d_x, float* d_sem_features, void* scratch,
-                                 const EdttsDropout* drop, const uint64_t* key, const int64_t* t_len, const int64_t* s_len, void* stream) {
+                                 const EdttsDropout* drop, const uint64_t* key, const int64_t* t_len, const int64_t* s_len, void* stream,
+                                 BwdStop stop) {
   Layout lo;
   TRY_G(train_layout(dims, "edtts_decoder_backward", &lo));
   DropState ds;
@@ -1324,6 +1408,17 @@ static int decoder_backward_impl(const EdttsDims* dims, const void* packed, void
   if (!packed || !workspace || !tape || !x || !t || !d_eps || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   if (n_slots != G_COUNT + lo.L * L_COUNT) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", G_COUNT + lo.L * L_COUNT, n_slots);
   TRY_G(check_shapes(lo, B, T, S));
+  if (stop.site >= 0) {  // (edtts_decoder_backward_until; every other entry point passes "never")
+    if (stop.layer < 0 || stop.layer >= lo.L)
+      return fail(EDTTS_ERR_ARG, "edtts_decoder_backward_until: stop_layer %d outside [0, %d)", stop.layer, lo.L);
+    if (stop.site >= EDTTS_BWD_COUNT) return fail(EDTTS_ERR_ARG, "edtts_decoder_backward_until: stop_site %d is not one of EDTTS_BWD_*", stop.site);
+    const bool per_layer = stop.site >= EDTTS_BWD_DROPDOWN && stop.site <= EDTTS_BWD_N1;
+    if (!per_layer && stop.layer != 0)
+      return fail(EDTTS_ERR_ARG, "edtts_decoder_backward_until: stop_site %d belongs to no layer, stop_layer must be 0", stop.site);
+    if (!TrainLauncher::has_site(lo, reinterpret_cast<float* const*>(grad_slots), step_idx, dropping, stop.site))
+      return fail(EDTTS_ERR_ARG, "edtts_decoder_backward_until: this call has no site %d (dropout, step_idx or the gradient slots it needs are absent)",
+                  stop.site);
+  }
   TrainTape tt;
   make_tape(lo, B, T, S, &tt);
   TrainScratch ss;
@@ -1331,7 +1426,7 @@ static int decoder_backward_impl(const EdttsDims* dims, const void* packed, void
   TRY_G(launch_len_check(t_len, s_len, B, T, S, (float*)workspace, (hipStream_t)stream));  // (the index-error word: the only use of `workspace`)
   return TrainLauncher::backward(lo, (const float*)packed, (const float*)tape, tt, (float*)scratch, ss, B, T, S, dims->window, x, t, step_idx,
                                  sem_features ? nullptr : sem_idx, sem_features, d_eps, reinterpret_cast<float* const*>(grad_slots), d_x,
-                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr, Lens{t_len, s_len});
+                                 d_sem_features, (hipStream_t)stream, dropping ? &ds : nullptr, Lens{t_len, s_len}, stop);
 }
 
 static int dropout_mask_impl(const EdttsDims* dims, int site, int layer, int B, int T, int S, const EdttsDropout* drop, const uint64_t* key,

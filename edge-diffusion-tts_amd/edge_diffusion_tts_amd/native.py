@@ -131,6 +131,14 @@ TAPE_NARROWED = ("kv", "qkv", "qc", "act")  # what EDTTS_TAPE_BF16 stores as bf1
 # the whole-model members (always fp32; edtts_train_tape_region answers the same for every layer)
 TAPE_GLOBALS = ("cond", "tcond", "ctx", "hl")
 EDTTS_TAPE_COND, EDTTS_TAPE_TCOND, EDTTS_TAPE_CTX, EDTTS_TAPE_HL = range(12, 16)
+# the sites of the backward's launch list, as edtts_decoder_backward_until names them (include/edtts.h: EDTTS_BWD_*), in launch
+# order: the head, the per-layer sites (layers L-1 .. 0), the tail
+BWD_SITES = ("out", "fnorm", "dropdown", "down", "upre", "swiglu", "up", "n3", "op", "cross", "qp", "n2", "kvu", "kvn", "kvd", "proj",
+             "self", "qkv", "n1", "inp", "sem", "ada", "step", "time")
+BWD_LAYER_SITES = BWD_SITES[2:19]
+# the members of the backward's scratch, as edtts_train_scratch_region names them (include/edtts.h: EDTTS_SCRATCH_*)
+SCRATCH_REGIONS = ("dh", "xn", "ga", "gq", "big", "da", "stat", "delta", "dkv", "crn", "dcr", "dcp", "dctx", "dmod", "dtc", "e", "a1", "u1",
+                   "du1", "part")
 
 
 class EdttsError(RuntimeError):
@@ -173,6 +181,9 @@ _ABI = {
     "edtts_decoder_forward_train_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, drp, vp, vp, vp)),
     "edtts_decoder_backward_len": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, drp, vp, vp,
                                              vp)),
+    "edtts_decoder_backward_until": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, drp, vp, vp,
+                                               i32, i32, vp)),
+    "edtts_train_scratch_region": (_STATUS, (dp, i32, i32, i32, i32, p_sz, p_sz)),
     "edtts_decoder_forward_train_dev": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, ddp, vp, vp, vp)),
     "edtts_decoder_backward_dev": (_STATUS, (dp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, p_vp, i32, vp, vp, vp, ddp, vp, vp,
                                              vp)),
@@ -414,6 +425,16 @@ def train_scratch_bytes(dims: EdttsDims, B: int, T: int, S: int) -> int:
     return _size_query(lib().edtts_train_scratch_bytes, C.byref(dims), B, T, S)
 
 
+def train_scratch_region(dims: EdttsDims, B: int, T: int, S: int, which) -> tuple:
+    """(offset in bytes, bytes) of one member of the backward's scratch (all fp32); ``which``: a name of SCRATCH_REGIONS or its
+    EDTTS_SCRATCH_* number (include/edtts.h: edtts_train_scratch_region; a diagnostic query)."""
+    if isinstance(which, str):
+        which = SCRATCH_REGIONS.index(which)
+    off, n = sz(), sz()
+    lib().edtts_train_scratch_region(C.byref(dims), B, T, S, int(which), C.byref(off), C.byref(n))
+    return int(off.value), int(n.value)
+
+
 def train_dw_slab_rows(rows: int) -> int:
     """Rows per partial slab of a weight gradient that sums over `rows` rows (include/edtts.h: edtts_train_dw_slab_rows)."""
     return int(lib().edtts_train_dw_slab_rows(int(rows)))
@@ -474,11 +495,13 @@ def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
                      step_idx: Optional[torch.Tensor], sem_idx: Optional[torch.Tensor], sem_features: Optional[torch.Tensor], S: int,
                      d_eps: torch.Tensor, grads: Sequence[Optional[torch.Tensor]], d_x: Optional[torch.Tensor],
                      d_sem_features: Optional[torch.Tensor], drop=None, t_len: Optional[torch.Tensor] = None,
-                     s_len: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> None:
+                     s_len: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, until=None) -> None:
     """edtts_decoder_backward: writes the gradient of every non-None entry of `grads` (slot order), d_x and d_sem_features.
     ``drop``: what the forward that filled `tape` was given (None: the plain export, else edtts_decoder_backward_drop).
     ``t_len`` / ``s_len``: the lengths that forward was given (device int64 [B] or None; with either, edtts_decoder_backward_len
-    runs).  ``scratch``: the caller's own (uint8, at least train_scratch_bytes) instead of one allocated here."""
+    runs).  ``scratch``: the caller's own (uint8, at least train_scratch_bytes) instead of one allocated here.
+    ``until``: (layer, site) -- edtts_decoder_backward_until: the same launches, stopped after the last one of that site (a name of
+    BWD_SITES or its EDTTS_BWD_* number; layer 0 for the head's and the tail's sites).  A diagnostic; not with a DropKey."""
     B, T, M = x.shape
     ptrs = _slot_ptrs(grads, "grad")
     nbytes = train_scratch_bytes(dims, B, T, S)
@@ -492,7 +515,15 @@ def decoder_backward(dims: EdttsDims, packed: torch.Tensor, workspace: torch.Ten
             _dev_ptr(sem_idx, torch.int64, "sem_idx"), _dev_ptr(sem_features, torch.float32, "sem_features"),
             _dev_ptr(d_eps, torch.float32, "d_eps"), ptrs, len(grads), _dev_ptr(d_x, torch.float32, "d_x"),
             _dev_ptr(d_sem_features, torch.float32, "d_sem_features"), scratch.data_ptr())
-    if isinstance(drop, EdttsDropoutDev):
+    if until is not None:
+        if isinstance(drop, EdttsDropoutDev):
+            raise EdttsError("decoder_backward: until= takes an EdttsDropout or a (p, seed) pair, not a DropKey")
+        layer, site = until
+        if isinstance(site, str):
+            site = BWD_SITES.index(site)
+        lib().edtts_decoder_backward_until(*args, None if drop is None else C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
+                                           _dev_ptr(s_len, torch.int64, "sem_lengths"), int(layer), int(site), _stream(x.device))
+    elif isinstance(drop, EdttsDropoutDev):
         lib().edtts_decoder_backward_dev(*args, C.byref(drop), _dev_ptr(t_len, torch.int64, "x_lengths"),
                                          _dev_ptr(s_len, torch.int64, "sem_lengths"), _stream(x.device))
     elif t_len is not None or s_len is not None:

@@ -347,6 +347,66 @@ int edtts_decoder_backward_len(const EdttsDims* dims, const void* packed, void* 
                                float* d_sem_features, void* scratch, const EdttsDropout* drop, const int64_t* t_len,
                                const int64_t* s_len, void* stream);
 
+/* ---- diagnostic entry points: a backward that stops, and the scratch's members by name ------------------
+ * For tests and tools that audit the backward launch by launch; a trainer needs neither.
+ *
+ * edtts_decoder_backward_until takes the arguments of edtts_decoder_backward_len plus (stop_layer, stop_site) before `stream`.  It
+ * makes exactly the launches of that call, in the same order and with the same arguments, and returns after the last launch of the
+ * named site: what the sites before it wrote -- scratch members and gradient destinations -- is bitwise what the whole call writes
+ * there at that moment, and the destinations of later sites are not touched.  A site is one line of the backward's launch list, in
+ * launch order: the head (OUT, FNORM; stop_layer 0), the per-layer sites DROPDOWN .. N1 for layers L-1 .. 0, and the tail (INP .. TIME;
+ * stop_layer 0).  Stopping at the last site the call has is the whole call.  EDTTS_ERR_ARG: stop_layer outside [0, layers) (or not 0
+ * for a head or tail site), stop_site out of range, or a site the call does not have -- DROPDOWN without dropout, ADA with neither an
+ * AdaLN-projection nor a time-path gradient slot, STEP without step_idx or the step_emb slot, TIME without a time-path slot.  The
+ * plain entry points do not change: no added launch, memset, synchronisation or allocation.  Graph-capturable as they are. */
+enum {
+  EDTTS_BWD_OUT = 0,       /* dctx zero-fill; out_proj bias sum; final-norm recompute -> xn; out_proj dW; dX -> ga */
+  EDTTS_BWD_FNORM = 1,     /* final LayerNorm backward: ga -> dh, gain and bias gradients */
+  EDTTS_BWD_DROPDOWN = 2,  /* (dropout only) the masked copy of dh -> gq */
+  EDTTS_BWD_DOWN = 3,      /* ffn.net.3: bias sum, dW, dX -> da */
+  EDTTS_BWD_UPRE = 4,      /* norm3 recompute -> xn; up projection -> big (value | gate pre-activations) */
+  EDTTS_BWD_SWIGLU = 5,    /* big <- SwiGLU gradient of (big, da), in place */
+  EDTTS_BWD_UP = 6,        /* ffn.net.0: bias sum, dW, dX -> ga */
+  EDTTS_BWD_N3 = 7,        /* norm3 backward: dh += ..., gain gradient, dmod (dscale | dshift) */
+  EDTTS_BWD_OP = 8,        /* cross out_proj: dW, dX -> ga */
+  EDTTS_BWD_CROSS = 9,     /* cross-attention backward: delta, dq -> gq, dk | dv -> dkv */
+  EDTTS_BWD_QP = 10,       /* norm2 recompute -> xn; q_proj dW, dX -> ga */
+  EDTTS_BWD_N2 = 11,       /* norm2 backward: dh += ..., gain gradient */
+  EDTTS_BWD_KVU = 12,      /* kv_norm recompute -> crn; kv_up dW, dX -> dcr */
+  EDTTS_BWD_KVN = 13,      /* kv_norm backward: dcr -> dcp, gain gradient */
+  EDTTS_BWD_KVD = 14,      /* kv_down: dW, dctx += dX */
+  EDTTS_BWD_PROJ = 15,     /* attn.proj: bias sum, dW, dX -> ga */
+  EDTTS_BWD_SELF = 16,     /* self-attention backward: delta, dq | dk | dv -> big */
+  EDTTS_BWD_QKV = 17,      /* norm1 recompute -> xn; qkv dW, dX -> ga */
+  EDTTS_BWD_N1 = 18,       /* norm1 backward: dh += ..., gain gradient, dmod */
+  EDTTS_BWD_INP = 19,      /* in_proj: bias sum, dW, dX -> d_x */
+  EDTTS_BWD_SEM = 20,      /* sem_proj gradients and d_sem_features, or the token_emb scatter; zero-fills of what does not enter */
+  EDTTS_BWD_ADA = 21,      /* per layer and norm the AdaLN projections: bias sum, dW, dtc += dX */
+  EDTTS_BWD_STEP = 22,     /* the step_emb scatter of dtc */
+  EDTTS_BWD_TIME = 23,     /* the time MLP: recomputation (e, a1, u1) and its gradients */
+  EDTTS_BWD_COUNT = 24
+};
+int edtts_decoder_backward_until(const EdttsDims* dims, const void* packed, void* workspace, const void* tape, int B, int T, int S,
+                                 const float* x, const int64_t* t, const int64_t* step_idx, const int64_t* sem_idx,
+                                 const float* sem_features, const float* d_eps, void* const* grad_slots, int n_slots, float* d_x,
+                                 float* d_sem_features, void* scratch, const EdttsDropout* drop, const int64_t* t_len,
+                                 const int64_t* s_len, int stop_layer, int stop_site, void* stream);
+
+/* Where one member of the backward's scratch lies (a host query): *offset_bytes from the scratch's start (a multiple of 256) and
+ * *bytes without the alignment padding behind it; all members are fp32.  Rows and pitches: DH, XN, GA, GQ [B T][hidden]; BIG
+ * [B T][max(2 ffn_mult hidden, 3 hidden)] (used at pitch 2 ffn_mult hidden by the FFN, 3 hidden by the self-attention); DA
+ * [B T][ffn_mult hidden]; STAT 2 max(B T, B S) (norm_bwd's per-row statistics); DELTA [B][heads][T]; DKV [B S][2 hidden]; CRN, DCR,
+ * DCP [B S][hidden / 2]; DCTX [B S][hidden]; DMOD [B][layers][2][2 hidden] (dscale | dshift, as EDTTS_TAPE_COND); DTC, E, A1, U1, DU1
+ * [B][hidden]; PART the partial slabs of the cut reductions.  edtts_train_scratch_bytes is the end of PART, rounded up to 256.
+ * EDTTS_ERR_ARG for `which` out of range. */
+enum {
+  EDTTS_SCRATCH_DH = 0, EDTTS_SCRATCH_XN = 1, EDTTS_SCRATCH_GA = 2, EDTTS_SCRATCH_GQ = 3, EDTTS_SCRATCH_BIG = 4, EDTTS_SCRATCH_DA = 5,
+  EDTTS_SCRATCH_STAT = 6, EDTTS_SCRATCH_DELTA = 7, EDTTS_SCRATCH_DKV = 8, EDTTS_SCRATCH_CRN = 9, EDTTS_SCRATCH_DCR = 10,
+  EDTTS_SCRATCH_DCP = 11, EDTTS_SCRATCH_DCTX = 12, EDTTS_SCRATCH_DMOD = 13, EDTTS_SCRATCH_DTC = 14, EDTTS_SCRATCH_E = 15,
+  EDTTS_SCRATCH_A1 = 16, EDTTS_SCRATCH_U1 = 17, EDTTS_SCRATCH_DU1 = 18, EDTTS_SCRATCH_PART = 19
+};
+int edtts_train_scratch_region(const EdttsDims* dims, int B, int T, int S, int which, size_t* offset_bytes, size_t* bytes);
+
 /* ---- dropout key in device memory --------------------------------------------------------------------
  * The *_dev twins take the arguments of edtts_decoder_forward_train_len, edtts_decoder_backward_len and edtts_dropout_mask with an
  * EdttsDropoutDev in place of the EdttsDropout: p (and with it thr and the scale) stays a host value, the Philox key is one uint64
