@@ -5,8 +5,8 @@
 // launch_len_check, which the launchers and the C ABI at the end of this file (edtts_mel_to_spec*, edtts_griffin_lim*) call.
 //
 // Bounds: the inverse-mel product is a small GEMM ([513 x 80] per frame: 82 kFLOP/frame, HBM traffic 320 B in / 2 KB out per
-// frame); Griffin-Lim is FFT-bound: per iteration and frame one 1024-point inverse and one forward complex FFT (2 x 51 kFLOP)
-// in LDS plus 4 KB (frame buffer) + 8 KB (phase state) + 4 KB (spectrum) of HBM traffic -> ~25 FLOP/B: HBM-bound on MI355X
+// frame); Griffin-Lim is FFT-bound: per iteration and frame one 1024-point inverse and one forward complex FFT (2 x 51 kFLOP, in
+// fp64: see cplxd below) in LDS plus 4 KB (frame buffer) + 8 KB (phase state) + 4 KB (spectrum) of HBM traffic -> ~25 FLOP/B: HBM-bound on MI355X
 // (ridge 20 FLOP/B for fp32 vector math); the iteration state is laid out frame-major so that every access is a contiguous row.
 //
 // Ragged batches (edtts_mel_to_spec_len, edtts_griffin_lim_len): rows padded to a common T carry their own frame
@@ -25,13 +25,28 @@ constexpr int kNfft = 1024, kBins = kNfft / 2 + 1, kThreads = 256;
 struct cplx {
   float re, im;
 };
-EDTTS_DEV cplx cmul(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+// The two transforms of Griffin-Lim run in fp64 between their fp32 operands and their fp32 results: the phase
+// update divides by |a|, so a bin of the rebuilt spectrum far below its row's level turns the transforms' own rounding into a phase
+// error 1 / |a| times as large.  In fp64 what is left is the rounding of the stored operands.
+struct cplxd {
+  double re, im;
+};
+EDTTS_DEV cplxd cmul(cplxd a, cplxd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+
+// tw[q] = exp(-2 pi i q / 1024), q < 512, in fp64 in the block's LDS (the fp32 host table would put an fp32 rounding back into every
+// butterfly): thread tid evaluates q = tid and derives q + 256 = q turned by -i.  Visible after fft1024's first barrier.
+EDTTS_DEV void twiddle64(cplxd* tw, int tid) {
+  double s, c;
+  sincospi(-(double)tid * (1.0 / (kNfft / 2)), &s, &c);
+  tw[tid] = {c, s};
+  tw[tid + kThreads] = {s, -c};
+}
 
 // 1024-point complex FFT in LDS, radix-2 Stockham autosort (natural order in and out), 256 threads x 2 butterflies per stage.
-// tw[q] = exp(-2 pi i q / 1024), q < 512 (host table, evaluated in fp64); INV conjugates it (no 1/N scaling here).
+// tw: twiddle64's table; INV conjugates it (no 1/N scaling here).
 // x holds the input; returns the buffer (x or y) that holds the result.  Callers synchronise before reading.
 template <bool INV>
-EDTTS_DEV cplx* fft1024(cplx* x, cplx* y, const cplx* __restrict__ tw, int tid) {
+EDTTS_DEV cplxd* fft1024(cplxd* x, cplxd* y, const cplxd* tw, int tid) {
   constexpr int N = kNfft, T = N / 2;
 #pragma unroll 1
   for (int p = 1; p < N; p <<= 1) {
@@ -41,13 +56,13 @@ EDTTS_DEV cplx* fft1024(cplx* x, cplx* y, const cplx* __restrict__ tw, int tid) 
       const int i = tid + u * kThreads;      // butterfly index in [0, 512)
       const int k = i & (p - 1);
       const int j = ((i - k) << 1) + k;
-      cplx w = tw[k * (T / p)];              // exp(-i pi k / p)
+      cplxd w = tw[k * (T / p)];             // exp(-i pi k / p)
       if (INV) w.im = -w.im;
-      const cplx u0 = x[i], u1 = cmul(w, x[i + T]);
+      const cplxd u0 = x[i], u1 = cmul(w, x[i + T]);
       y[j] = {u0.re + u1.re, u0.im + u1.im};
       y[j + p] = {u0.re - u1.re, u0.im - u1.im};
     }
-    cplx* t = x; x = y; y = t;
+    cplxd* t = x; x = y; y = t;
   }
   __syncthreads();
   return x;
@@ -157,22 +172,22 @@ __global__ __launch_bounds__(kThreads) void k_gl_init(const float* __restrict__ 
 
 // frames[b][t][n] = window[n] * irfft(mag * angles)[n]      (torch.istft: per-frame inverse real FFT, "backward" normalisation)
 __global__ __launch_bounds__(kThreads) void k_gl_istft(const float* __restrict__ mag, const cplx* __restrict__ ang, const float* __restrict__ window,
-                                                       const cplx* __restrict__ tw, int T, const int64_t* __restrict__ t_len,
-                                                       float* __restrict__ frames) {
-  __shared__ cplx bufa[kNfft], bufb[kNfft];
+                                                       int T, const int64_t* __restrict__ t_len, float* __restrict__ frames) {
+  __shared__ cplxd bufa[kNfft], bufb[kNfft], tw[kNfft / 2];  // 40 KB
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
   if (t >= utt_len(t_len, b, T)) return;  // a padded frame: the whole block leaves before the first barrier
+  twiddle64(tw, tid);
   const size_t row = ((size_t)b * T + t) * kBins;
   for (int f = tid; f < kBins; f += kThreads) {
-    const float m = mag[row + f];
-    cplx v = {m * ang[row + f].re, m * ang[row + f].im};
-    if (f == 0 || f == kNfft / 2) v.im = 0.f;  // a real signal's DC / Nyquist bins (irfft ignores their imaginary parts)
+    const double m = mag[row + f];
+    cplxd v = {m * ang[row + f].re, m * ang[row + f].im};  // exact: products of two fp32 values
+    if (f == 0 || f == kNfft / 2) v.im = 0.0;  // a real signal's DC / Nyquist bins (irfft ignores their imaginary parts)
     bufa[f] = v;
     if (f > 0 && f < kNfft / 2) bufa[kNfft - f] = {v.re, -v.im};  // Hermitian extension
   }
-  cplx* r = fft1024<true>(bufa, bufb, tw, tid);
+  cplxd* r = fft1024<true>(bufa, bufb, tw, tid);
   float* out = frames + ((size_t)b * T + t) * kNfft;
-  for (int n = tid; n < kNfft; n += kThreads) out[n] = r[n].re * (1.0f / kNfft) * window[n];
+  for (int n = tid; n < kNfft; n += kThreads) out[n] = (float)(r[n].re * (1.0 / kNfft) * window[n]);
 }
 
 // wave[b][p] = sum_t frames[b][t][p - t hop] / sum_t window^2[p - t hop]   over the frames that cover padded position p
@@ -200,13 +215,14 @@ __global__ __launch_bounds__(kThreads) void k_gl_ola(const float* __restrict__ f
 
 // rebuilt = stft(x, center=True, reflect), x = wave[n_fft/2 : n_fft/2 + Lx];  then the momentum phase update
 //   a = rebuilt - mom * tprev;  angles = a / (|a| + 1e-16);  tprev = rebuilt          (torchaudio.functional.griffinlim)
-__global__ __launch_bounds__(kThreads) void k_gl_stft(const float* __restrict__ wave, const float* __restrict__ window, const cplx* __restrict__ tw,
-                                                      int T, int hop, int Lp, float mom, const int64_t* __restrict__ t_len, cplx* __restrict__ ang,
+__global__ __launch_bounds__(kThreads) void k_gl_stft(const float* __restrict__ wave, const float* __restrict__ window, int T, int hop, int Lp,
+                                                      float mom, const int64_t* __restrict__ t_len, cplx* __restrict__ ang,
                                                       cplx* __restrict__ tprev) {
-  __shared__ cplx bufa[kNfft], bufb[kNfft];
+  __shared__ cplxd bufa[kNfft], bufb[kNfft], tw[kNfft / 2];  // 40 KB
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
   const int Tb = utt_len(t_len, b, T);
   if (t >= Tb) return;  // a padded frame: the whole block leaves before the first barrier
+  twiddle64(tw, tid);
   const int Lx = hop * (Tb - 1);  // the row's own signal: the reflection is at its own end
   const float* x = wave + (size_t)b * Lp + kNfft / 2;
   for (int n = tid; n < kNfft; n += kThreads) {
@@ -214,12 +230,12 @@ __global__ __launch_bounds__(kThreads) void k_gl_stft(const float* __restrict__ 
     if (idx < 0) idx = -idx;
     if (idx >= Lx) idx = 2 * (Lx - 1) - idx;
     idx = idx < 0 ? 0 : idx;  // (signals shorter than the pad are not supported by torch either)
-    bufa[n] = {x[idx] * window[n], 0.f};
+    bufa[n] = {(double)x[idx] * window[n], 0.0};  // exact
   }
-  cplx* r = fft1024<false>(bufa, bufb, tw, tid);
+  cplxd* r = fft1024<false>(bufa, bufb, tw, tid);
   const size_t row = ((size_t)b * T + t) * kBins;
   for (int f = tid; f < kBins; f += kThreads) {
-    const cplx rb = r[f], tp = tprev[row + f];
+    const cplx rb = {(float)r[f].re, (float)r[f].im}, tp = tprev[row + f];  // the update reads what tprev will hold
     const cplx a = {rb.re - mom * tp.re, rb.im - mom * tp.im};
     const float inv = 1.0f / (sqrtf(a.re * a.re + a.im * a.im) + 1e-16f);
     ang[row + f] = {a.re * inv, a.im * inv};
@@ -249,6 +265,8 @@ static int melpost_len_check(const int64_t* t_len, int B, int T, int t_min, void
 }
 
 // Both Griffin-Lim entry points.  t_len == nullptr: every row has T frames, the draws are keyed by (seed, element of the batch).
+// twiddle (the fp32 table exp(-2 pi i q / n_fft), q < n_fft / 2) stays in the ABI and is checked, but is no longer read: the
+// transforms run in fp64 and build their table themselves (twiddle64).
 static int griffin_lim_run(const float* spec, int B, int T, int n_fft, int hop, const float* window, const float* twiddle, int n_iter,
                            float momentum, float power, const float* angles0, uint64_t seed, const int64_t* t_len, const uint64_t* seeds,
                            void* idx_err, float* scratch, float* wave_out, void* stream) {
@@ -267,16 +285,15 @@ static int griffin_lim_run(const float* spec, int B, int T, int n_fft, int hop, 
   cplx* tprev = ang + bt * kBins;
   float* frames = reinterpret_cast<float*>(tprev + bt * kBins);
   float* wave = frames + bt * n_fft;
-  const cplx* tw = reinterpret_cast<const cplx*>(twiddle);
   const float mom = momentum / (1.0f + momentum);
   hipLaunchKernelGGL(k_gl_init, dim3(T, B), dim3(kThreads), 0, st, spec, angles0, T, 1.0f / power, (unsigned long long)seed, t_len,
                      reinterpret_cast<const unsigned long long*>(seeds), mag, ang, tprev);
   LAUNCH_CHECK("k_gl_init");
   int gx = (Lp + kThreads - 1) / kThreads;
   for (int it = 0; it <= n_iter; ++it) {
-    hipLaunchKernelGGL(k_gl_istft, dim3(T, B), dim3(kThreads), 0, st, mag, ang, window, tw, T, t_len, frames);
+    hipLaunchKernelGGL(k_gl_istft, dim3(T, B), dim3(kThreads), 0, st, mag, ang, window, T, t_len, frames);
     hipLaunchKernelGGL(k_gl_ola, dim3(gx, B), dim3(kThreads), 0, st, frames, window, T, hop, Lp, t_len, wave);
-    if (it < n_iter) hipLaunchKernelGGL(k_gl_stft, dim3(T, B), dim3(kThreads), 0, st, wave, window, tw, T, hop, Lp, mom, t_len, ang, tprev);
+    if (it < n_iter) hipLaunchKernelGGL(k_gl_stft, dim3(T, B), dim3(kThreads), 0, st, wave, window, T, hop, Lp, mom, t_len, ang, tprev);
   }
   LAUNCH_CHECK("griffin-lim kernels");
   // torch.istft trims the centre padding: n_fft / 2 at the start, and (length = None) as much at the end

@@ -8,6 +8,7 @@ raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -720,15 +721,45 @@ def mel_to_spec(mel: torch.Tensor, mean: Optional[torch.Tensor], std: Optional[t
     return spec
 
 
+def griffin_lim_scratch_floats(B: int, T: int, n_fft: int, hop: int) -> int:
+    return _size_query(lib().edtts_griffin_lim_scratch_floats, B, T, n_fft, hop)
+
+
+def griffin_lim_scratch_layout(B: int, T: int, n_fft: int, hop: int):
+    """[(member, offset in floats, shape)] of the Griffin-Lim scratch in its order (csrc/edtts_melpost.h: griffin_lim_run).  The
+    complex members are (re, im) pairs of floats: with B T odd they start at an odd float offset, which a complex64 view cannot."""
+    bins, bt = n_fft // 2 + 1, B * T
+    shapes = (("mag", (B, T, bins)), ("ang", (B, T, bins, 2)), ("tprev", (B, T, bins, 2)), ("frames", (B, T, n_fft)),
+              ("wave", (B, n_fft + hop * (T - 1))))
+    out, off = [], 0
+    for name, shape in shapes:
+        out.append((name, off, shape))
+        off += math.prod(shape)
+    return out
+
+
+def griffin_lim_scratch_views(scratch: torch.Tensor, B: int, T: int, n_fft: int, hop: int) -> dict:
+    """The five members of a scratch that griffin_lim(..., scratch=scratch) ran on, as views: mag [B, T, bins], ang and tprev
+    [B, T, bins, 2] (the phases and the previous rebuilt spectrum as (re, im)), frames [B, T, n_fft], wave [B, n_fft + hop (T - 1)]
+    (the padded signal; the returned waveform is its columns n_fft / 2 onwards)."""
+    return {name: scratch[off:off + math.prod(shape)].view(shape) for name, off, shape in griffin_lim_scratch_layout(B, T, n_fft, hop)}
+
+
 def griffin_lim(spec: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, twiddle: torch.Tensor, n_iter: int, momentum: float,
                 power: float, angles0: Optional[torch.Tensor], seed: int = 0, t_len: Optional[torch.Tensor] = None,
-                seeds: Optional[torch.Tensor] = None, idx_err: Optional[torch.Tensor] = None) -> torch.Tensor:
+                seeds: Optional[torch.Tensor] = None, idx_err: Optional[torch.Tensor] = None,
+                scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """spec [B, n_fft // 2 + 1, T] -> wave [B, hop * (T - 1)] (include/edtts.h: edtts_griffin_lim).  angles0: fp32 [B, F, T, 2] or None
     (library draws from `seed`).  With t_len (device int64 [B]) edtts_griffin_lim_len runs: seeds (device int64 [B]) replace `seed`,
-    idx_err is the int32 word a bad length is flagged in."""
+    idx_err is the int32 word a bad length is flagged in.  ``scratch``: the caller's own (fp32, at least griffin_lim_scratch_floats)
+    instead of one allocated here; griffin_lim_scratch_views names what the call leaves in it."""
     B, _, T = spec.shape
     f = torch.float32
-    scratch = torch.empty(_size_query(lib().edtts_griffin_lim_scratch_floats, B, T, n_fft, hop), dtype=f, device=spec.device)
+    need = griffin_lim_scratch_floats(B, T, n_fft, hop)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=f, device=spec.device)
+    elif scratch.numel() < need or _dev_ptr(scratch, f, "scratch") is None:
+        raise EdttsError(f"scratch: expected at least {need} floats, got {scratch.numel()}")
     wave = torch.empty(B, hop * (T - 1), dtype=f, device=spec.device)
     head = (_dev_ptr(spec, f, "specgram"), B, T, n_fft, hop, _dev_ptr(window, f, "window"), _dev_ptr(twiddle, f, "twiddle"), n_iter,
             float(momentum), float(power), _dev_ptr(angles0, f, "angles0"))

@@ -22,18 +22,19 @@ def ref_fb(n_mels=80, sr=16000, f_min=0.0, f_max=8000.0):
     return melscale_fbanks(513, f_min, f_max, n_mels, sr)
 
 
-def ref_mel(wav, hop=160, dtype=torch.float64, fb=None):
-    """wav [B, L] (CPU) -> power mel [B, n_mels, T] computed in `dtype` (fp32 = what torchaudio itself computes)."""
+def ref_mel(wav, hop=160, dtype=torch.float64, fb=None, power=2.0):
+    """wav [B, L] (CPU) -> power (or, power = 1.0, magnitude) mel [B, n_mels, T] computed in `dtype` (fp32 = what torchaudio itself
+    computes); fb: the filter bank [513, n_mels], default ref_fb()."""
     fb = ref_fb() if fb is None else fb
     x = wav.to(dtype)
     spec = torch.stft(x, 1024, hop, 1024, window=torch.hann_window(1024, dtype=dtype), center=True, pad_mode="reflect",
                       normalized=False, onesided=True, return_complex=True)
-    p = spec.abs() ** 2
+    p = spec.abs() ** 2 if power == 2.0 else spec.abs() ** power
     return torch.matmul(p.transpose(-1, -2), fb.to(dtype)).transpose(-1, -2)
 
 
-def ref_log_mel(wav, hop=160, dtype=torch.float64):
-    return torch.log(torch.clamp(ref_mel(wav, hop, dtype), min=1e-5)).transpose(1, 2)
+def ref_log_mel(wav, hop=160, dtype=torch.float64, *, fb=None, power=2.0):
+    return torch.log(torch.clamp(ref_mel(wav, hop, dtype, fb, power), min=1e-5)).transpose(1, 2)
 
 
 def ref_stats(log_mel):
@@ -180,6 +181,51 @@ def test_the_issue_tap_counts():
         h, w = audio.sinc_resample_kernel(orig // g, 16000 // g)
         taps[orig] = (orig // g, 16000 // g, h.shape[1])
     assert taps == {22050: (441, 320, 459), 24000: (3, 2, 23), 44100: (441, 160, 475), 48000: (3, 1, 41), 8000: (1, 2, 15)}
+
+
+# (orig, new) -> (taps, p-tiles per group PT, groups, grid.y, dynamic LDS bytes) of k_resample: the paths test_audio_gpu.py's
+# test_resample_launch_geometries is meant to reach
+GEOMETRY = {
+    (16000, 22050): (334, 1, 28, 7, 42304),   # upsampling: 28 one-tile groups, 7 grid rows
+    (16000, 44100): (174, 1, 28, 7, 21184),
+    (44100, 40000): (455, 5, 5, 2, 58272),    # PT = 5 with a second grid row, 57 KB of LDS
+    (11025, 16000): (455, 5, 8, 2, 58272),
+    (16000, 48000): (15, 1, 1, 1, 192),       # K padded from 15 to 16
+    (32000, 48000): (16, 1, 1, 1, 320),       # K = 16: no remainder
+    (48000, 44100): (174, 5, 2, 1, 21184),
+    (22050, 16000): (459, 5, 4, 1, 58288),    # the rates of test_resample_parity
+    (44100, 16000): (475, 5, 2, 1, 58352),
+    (24000, 16000): (23, 1, 1, 1, 480),
+    (48000, 16000): (41, 1, 1, 1, 560),
+    (8000, 16000): (15, 1, 1, 1, 192),
+}
+
+
+def resample_geometry(orig, new):
+    """edtts_resample's launch arithmetic (csrc/edtts_audio.h) on the product's sinc table."""
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    h, w = audio.sinc_resample_kernel(o, n)
+    taps = h.shape[1]
+    assert taps == 2 * w + o
+    Kp, Np = (taps + 3) & ~3, (n + 15) & ~15
+    tiles = Np // 16
+    PT = 5 if tiles % 5 == 0 else 1
+    groups = tiles // PT
+    return taps, PT, groups, (groups + 3) // 4, (16 * 2 * o + Kp) * 4
+
+
+def test_resample_launch_geometries():
+    import os
+    src = open(os.path.join(os.path.dirname(audio.__file__), "..", "csrc", "edtts_audio.h")).read()
+    # the lines resample_geometry restates: a retune of the tile grouping has to come through here
+    for line in ("constexpr int kRsMB = 2;", "const int Kp = (taps + 3) & ~3, Np = (new_freq + 15) & ~15;",
+                 "const int tiles = Np / 16, PT = tiles % 5 == 0 ? 5 : 1, n_groups = tiles / PT;",
+                 "const size_t lds = (size_t)(16 * kRsMB * orig + Kp) * sizeof(float);", "(unsigned)((n_groups + 3) / 4)"):
+        assert line in src, line
+    for rates, want in GEOMETRY.items():
+        assert resample_geometry(*rates) == want, rates
+        assert want[4] <= 64 * 1024
 
 
 def test_length_arithmetic():
