@@ -376,11 +376,21 @@ static int hub_ws(const HubLayout& L, int B, int T_audio, HubWs& W) {
 static bool hub_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static unsigned hub_grid(size_t n) { const size_t nb = (n + 255) / 256; return (unsigned)(nb > 8192 ? 8192 : (nb < 1 ? 1 : nb)); }
 
-template <int EPI>
-static int hub_gemm(hipStream_t st, HGemmArgs a, int B, int G) {
+// Where a forward stops (edtts_hubert_forward_until): after the last launch of site `site` (EDTTS_HUB_*, include/edtts.h) with index
+// `index`; site < 0: never.  tile: 0 = hub_gemm's own rule, 2 | 4 = that TW for every GEMM launch of the call.
+struct HubStop {
+  int site = -1, index = 0, tile = 0;
+};
+static bool hub_wide_tile(int M, int N, int G, int B, int tile) {
   const int n_sm = 256;  // MI355X compute units: below two 128-tiles per CU the 64-wide tile (4x the blocks) is used
-  const long long big = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128) * G * B;
-  if (big >= 2 * n_sm && a.N > 64) {  // (N <= 64, the positional conv's groups: a 128-wide tile would be half empty)
+  const long long big = (long long)((M + 127) / 128) * ((N + 127) / 128) * G * B;
+  if (tile) return tile == 4;
+  return big >= 2 * n_sm && N > 64;  // (N <= 64, the positional conv's groups: a 128-wide tile would be half empty)
+}
+
+template <int EPI>
+static int hub_gemm(hipStream_t st, HGemmArgs a, int B, int G, int tile = 0) {
+  if (hub_wide_tile(a.M, a.N, G, B, tile)) {
     a.ntn = (a.N + 127) / 128;
     hipLaunchKernelGGL((k_hub_gemm<EPI, 4>), dim3((a.M + 127) / 128, a.ntn * G, B), dim3(256), 0, st, a);
   } else {
@@ -392,11 +402,12 @@ static int hub_gemm(hipStream_t st, HGemmArgs a, int B, int G) {
 }
 // a plain row-major GEMM: Y[M][ldy] = epi(X[M][K] W[N][K]^T)
 template <int EPI>
-static int hub_dense(hipStream_t st, const float* X, const float* W, const float* bias, float* Y, const float* R, int M, int N, int K) {
+static int hub_dense(hipStream_t st, const float* X, const float* W, const float* bias, float* Y, const float* R, int M, int N, int K,
+                     int tile = 0) {
   HGemmArgs a{};
   a.X = X; a.ldrow = K; a.Cin = K; a.stride = 1; a.Tin = M;
   a.W = W; a.K = K; a.bias = bias; a.Y = Y; a.R = R; a.ldy = N; a.M = M; a.N = N;
-  return hub_gemm<EPI>(st, a, 1, 1);
+  return hub_gemm<EPI>(st, a, 1, 1, tile);
 }
 static int hub_norm(hipStream_t st, const float* x, float* y, int rows, int W, const float* g, const float* b, float eps) {
   edtts_gen::NormArgs a{x, y, g, b, nullptr, rows, W, W, 1, 0, eps};
@@ -404,6 +415,35 @@ static int hub_norm(hipStream_t st, const float* x, float* y, int rows, int W, c
   LAUNCH_CHECK("k_gen_norm");
   return EDTTS_OK;
 }
+
+static const char* const kHubSiteNames[EDTTS_HUB_COUNT] = {"LENS", "GNSTAT", "CONV0", "CONV", "FPNORM", "FPROJ", "POS", "ENCNORM", "QKV",
+                                                           "VT", "ATTN", "OPROJ", "LN1", "FF1", "FF2", "LN2", "ZERO"};
+// a stop that names a site the call does not have is refused (the forward would otherwise run to its end unnoticed)
+static int hub_stop_check(const HubLayout& L, bool bf16, bool with_lengths, const HubStop& s) {
+  const char* fn = "edtts_hubert_forward_until";
+  if (s.tile != 0 && s.tile != 2 && s.tile != 4) return fail(EDTTS_ERR_ARG, "%s: tile=%d: expected 0 (the launcher's rule), 2 or 4", fn, s.tile);
+  if (s.site < 0 || s.site >= EDTTS_HUB_COUNT)
+    return fail(EDTTS_ERR_ARG, "%s: stop_site=%d: expected an EDTTS_HUB_* site in [0, %d)", fn, s.site, (int)EDTTS_HUB_COUNT);
+  const char* nm = kHubSiteNames[s.site];
+  if ((s.site == EDTTS_HUB_LENS || s.site == EDTTS_HUB_ZERO) && !with_lengths)
+    return fail(EDTTS_ERR_ARG, "%s: site EDTTS_HUB_%s exists only with lengths", fn, nm);
+  if (s.site == EDTTS_HUB_VT && !bf16) return fail(EDTTS_ERR_ARG, "%s: site EDTTS_HUB_VT exists only under EDTTS_HUBERT_BF16", fn);
+  if (s.site == EDTTS_HUB_CONV) {
+    if (s.index < 1 || s.index >= L.nc)
+      return fail(EDTTS_ERR_ARG, "%s: site EDTTS_HUB_CONV: stop_index=%d: expected a conv layer in [1, %d)", fn, s.index, L.nc);
+  } else if (s.site >= EDTTS_HUB_QKV && s.site <= EDTTS_HUB_LN2) {
+    if (s.index < 0 || s.index >= L.L)
+      return fail(EDTTS_ERR_ARG, "%s: site EDTTS_HUB_%s: stop_index=%d: expected an encoder layer in [0, %d)", fn, nm, s.index, L.L);
+  } else if (s.index != 0) {
+    return fail(EDTTS_ERR_ARG, "%s: site EDTTS_HUB_%s has no index: stop_index=%d, expected 0", fn, nm, s.index);
+  }
+  return EDTTS_OK;
+}
+#define EDTTS_HUB_STOP_AFTER(site_, index_) \
+  if (stop.site == (site_) && stop.index == (index_)) return EDTTS_OK
+
+static int hub_forward32(const HubLayout& L, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths, float* out,
+                         void* workspace, hipStream_t st, const HubStop stop);
 
 }  // namespace edtts_hub
 
@@ -500,9 +540,20 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
   if (!packed || !wav || !out || !workspace) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
   if (!hub_al16(packed) || !hub_al16(out) || !hub_al16(workspace)) return fail(EDTTS_ERR_ARG, "packed, out and workspace must be 16-byte aligned");
+  return hub_forward32(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream, HubStop{});
+}
+
+}  // extern "C"
+
+namespace edtts_hub {
+
+// The fp32 forward's launch list.  The sites of edtts_hubert_forward_until (EDTTS_HUB_*, include/edtts.h): one line below each; `stop`
+// never matches in the plain entry point (site -1), whose launch list is the whole of it.
+static int hub_forward32(const HubLayout& L, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths, float* out,
+                         void* workspace, hipStream_t st, const HubStop stop) {
   HubWs ws;
   TRY_G(hub_ws(L, B, T_audio, ws));
-  hipStream_t st = (hipStream_t)stream;
+  const int tile = stop.tile;
   const float* P = (const float*)packed;
   char* wb = (char*)workspace;
   const int T = ws.T[L.nc - 1], H = L.H, M = B * T;
@@ -515,6 +566,7 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
     for (int i = 0; i < L.nc; ++i) { geo.k[i] = L.k[i]; geo.s[i] = L.s[i]; }
     hipLaunchKernelGGL(k_hub_lens, dim3((B + 63) / 64), dim3(64), 0, st, lengths, B, T_audio, hub_min_samples(L), geo, len0, flen);
     LAUNCH_CHECK("k_hub_lens");
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LENS, 0);
   }
   float* stats = (float*)(wb + ws.stats);
   float* buf[2] = {(float*)(wb + ws.buf0), (float*)(wb + ws.buf1)};
@@ -527,9 +579,11 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
   hipLaunchKernelGGL(k_hub_gn_final, dim3((B * L.C[0] + 255) / 256), dim3(256), 0, st, part, ws.nch, L.C[0], len0, ws.T[0], 1e-5f,
                      P + L.gn_w, P + L.gn_b, stats, B);
   LAUNCH_CHECK("k_hub_gn_final");
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_GNSTAT, 0);
   hipLaunchKernelGGL(k_hub_conv0, dim3(hub_grid((size_t)B * ws.T[0] * L.C[0] / 4)), dim3(256), 0, st, wav, T_audio, P + L.conv0,
                      L.C[0], L.k[0], L.s[0], len0, ws.T[0], stats, buf[0], B);
   LAUNCH_CHECK("k_hub_conv0");
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_CONV0, 0);
   // conv1.. as implicit GEMMs + GELU, ping-ponging between the two buffers
   for (int c = 1; c < L.nc; ++c) {
     HGemmArgs a{};
@@ -537,14 +591,17 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
     a.Tin = ws.T[c - 1];
     a.W = P + L.conv[c]; a.K = L.k[c] * L.C[c - 1];
     a.Y = buf[c & 1]; a.ybs = (long long)ws.T[c] * L.C[c]; a.ldy = L.C[c]; a.M = ws.T[c]; a.N = L.C[c];
-    TRY_G(hub_gemm<HEPI_GELU>(st, a, B, 1));
+    TRY_G(hub_gemm<HEPI_GELU>(st, a, B, 1, tile));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_CONV, c);
   }
   // feature projection: LayerNorm -> Linear (+ bias) -> h
   const int CL = L.C[L.nc - 1];
   float* feat = buf[(L.nc - 1) & 1];
   float* fn = buf[L.nc & 1];
   TRY_G(hub_norm(st, feat, fn, M, CL, P + L.fp_w, P + L.fp_b, L.eps));
-  TRY_G(hub_dense<HEPI_BIAS>(st, fn, P + L.proj_w, P + L.proj_b, h, nullptr, M, H, CL));
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FPNORM, 0);
+  TRY_G(hub_dense<HEPI_BIAS>(st, fn, P + L.proj_w, P + L.proj_b, h, nullptr, M, H, CL, tile));
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FPROJ, 0);
   // att = h + GELU(pos_conv(h) + bias), one GEMM per group; zero rows outside [0, frames_b)
   {
     HGemmArgs a{};
@@ -552,19 +609,28 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
     a.nvalid = flen; a.Tin = T;
     a.W = P + L.pos_w; a.K = L.pk * L.Cg; a.bias = P + L.pos_b;
     a.Y = att; a.R = h; a.ybs = (long long)T * H; a.ldy = H; a.M = T; a.N = L.Cg;
-    TRY_G(hub_gemm<HEPI_GELU_RESID>(st, a, B, L.pg));
+    TRY_G(hub_gemm<HEPI_GELU_RESID>(st, a, B, L.pg, tile));
   }
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_POS, 0);
   TRY_G(hub_norm(st, att, L.L ? h : out, M, H, P + L.enc_w, P + L.enc_b, L.eps));
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_ENCNORM, 0);
   for (int l = 0; l < L.L; ++l) {
     const float* Y = P + (size_t)l * L.layer;
-    TRY_G(hub_dense<HEPI_BIAS>(st, h, Y + L.qkv_w, Y + L.qkv_b, big, nullptr, M, 3 * H, H));
+    TRY_G(hub_dense<HEPI_BIAS>(st, h, Y + L.qkv_w, Y + L.qkv_b, big, nullptr, M, 3 * H, H, tile));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_QKV, l);
     TRY_G(GenericLauncher::attn(st, AttnShape(H, L.heads, L.DH), B, big, 3 * H, big + H, big + 2 * H, 3 * H, att, T, T, -1, flen, flen, false,
                                 false));
-    TRY_G(hub_dense<HEPI_RESID>(st, att, Y + L.o_w, Y + L.o_b, h, h, M, H, H));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_ATTN, l);
+    TRY_G(hub_dense<HEPI_RESID>(st, att, Y + L.o_w, Y + L.o_b, h, h, M, H, H, tile));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_OPROJ, l);
     TRY_G(hub_norm(st, h, h, M, H, Y + L.ln1_w, Y + L.ln1_b, L.eps));
-    TRY_G(hub_dense<HEPI_GELU>(st, h, Y + L.ff1_w, Y + L.ff1_b, big, nullptr, M, L.I, H));
-    TRY_G(hub_dense<HEPI_RESID>(st, big, Y + L.ff2_w, Y + L.ff2_b, h, h, M, H, L.I));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LN1, l);
+    TRY_G(hub_dense<HEPI_GELU>(st, h, Y + L.ff1_w, Y + L.ff1_b, big, nullptr, M, L.I, H, tile));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FF1, l);
+    TRY_G(hub_dense<HEPI_RESID>(st, big, Y + L.ff2_w, Y + L.ff2_b, h, h, M, H, L.I, tile));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FF2, l);
     TRY_G(hub_norm(st, h, l + 1 < L.L ? h : out, M, H, Y + L.ln2_w, Y + L.ln2_b, L.eps));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LN2, l);
   }
   if (flen) {
     hipLaunchKernelGGL(k_hub_zero_past, dim3(hub_grid((size_t)M * H / 4)), dim3(256), 0, st, out, flen, B, T, H);
@@ -573,4 +639,4 @@ int edtts_hubert_forward(const EdttsHubertDims* dims, const void* packed, const 
   return EDTTS_OK;
 }
 
-}  // extern "C"
+}  // namespace edtts_hub

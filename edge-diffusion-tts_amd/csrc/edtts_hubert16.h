@@ -367,10 +367,8 @@ static int hub_ws16(const HubLayout& L, int B, int T_audio, HubWs16& W) {
 }
 
 template <int EPI, bool XBF, bool YBF>
-static int hub_gemm16(hipStream_t st, HGemm16Args a, int B, int G) {
-  const int n_sm = 256;  // the rule of hub_gemm: below two 128-tiles per CU the 64-wide tile
-  const long long big = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128) * G * B;
-  if (big >= 2 * n_sm && a.N > 64) {
+static int hub_gemm16(hipStream_t st, HGemm16Args a, int B, int G, int tile = 0) {
+  if (hub_wide_tile(a.M, a.N, G, B, tile)) {  // the rule of hub_gemm: below two 128-tiles per CU the 64-wide tile
     a.ntn = (a.N + 127) / 128;
     hipLaunchKernelGGL((k_hub_gemm16<EPI, 4, XBF, YBF>), dim3((a.M + 127) / 128, a.ntn * G, B), dim3(256), 0, st, a);
   } else {
@@ -382,11 +380,12 @@ static int hub_gemm16(hipStream_t st, HGemm16Args a, int B, int G) {
 }
 // a plain row-major GEMM: Y[M][N] = epi(X[M][K] W[N][K]^T)
 template <int EPI, bool XBF, bool YBF>
-static int hub_dense16(hipStream_t st, const void* X, const __bf16* W, const float* bias, void* Y, const float* R, int M, int N, int K) {
+static int hub_dense16(hipStream_t st, const void* X, const __bf16* W, const float* bias, void* Y, const float* R, int M, int N, int K,
+                       int tile = 0) {
   HGemm16Args a{};
   a.X = X; a.ldrow = K; a.Cin = K; a.stride = 1; a.Tin = M;
   a.W = W; a.K = K; a.bias = bias; a.Y = Y; a.R = R; a.ldy = N; a.M = M; a.N = N;
-  return hub_gemm16<EPI, XBF, YBF>(st, a, 1, 1);
+  return hub_gemm16<EPI, XBF, YBF>(st, a, 1, 1, tile);
 }
 
 static int hub_pack16(const HubLayout& L, const void* const* slots, void* packed, hipStream_t st) {
@@ -438,10 +437,12 @@ static int hub_pack16(const HubLayout& L, const void* const* slots, void* packed
   return EDTTS_OK;
 }
 
+// The bf16 forward's launch list, with the stop sites of hub_forward32 (and EDTTS_HUB_VT).
 static int hub_forward16(const HubLayout& L, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths, float* out,
-                         void* workspace, hipStream_t st) {
+                         void* workspace, hipStream_t st, const HubStop stop = HubStop{}) {
   HubWs16 ws;
   TRY_G(hub_ws16(L, B, T_audio, ws));
+  const int tile = stop.tile;
   const float* P = (const float*)packed;
   auto PW = [&](size_t off) { return (const __bf16*)(P + off); };
   char* wb = (char*)workspace;
@@ -455,6 +456,7 @@ static int hub_forward16(const HubLayout& L, const void* packed, const float* wa
     for (int i = 0; i < L.nc; ++i) { geo.k[i] = L.k[i]; geo.s[i] = L.s[i]; }
     hipLaunchKernelGGL(k_hub_lens, dim3((B + 63) / 64), dim3(64), 0, st, lengths, B, T_audio, hub_min_samples(L), geo, len0, flen);
     LAUNCH_CHECK("k_hub_lens");
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LENS, 0);
   }
   float* stats = (float*)(wb + ws.stats);
   void* buf[2] = {wb + ws.buf0, wb + ws.buf1};
@@ -468,6 +470,7 @@ static int hub_forward16(const HubLayout& L, const void* packed, const float* wa
   hipLaunchKernelGGL(k_hub_gn_final, dim3((B * L.C[0] + 255) / 256), dim3(256), 0, st, part, ws.nch, L.C[0], len0, ws.T[0], 1e-5f,
                      P + L.gn_w, P + L.gn_b, stats, B);
   LAUNCH_CHECK("k_hub_gn_final");
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_GNSTAT, 0);
   const dim3 g0(hub_grid((size_t)B * ws.T[0] * L.C[0] / 4));
   if (L.nc > 1) {
     hipLaunchKernelGGL(k_hub_conv0_16, g0, dim3(256), 0, st, wav, T_audio, P + L.conv0, L.C[0], L.k[0], L.s[0], len0, ws.T[0], stats,
@@ -478,36 +481,44 @@ static int hub_forward16(const HubLayout& L, const void* packed, const float* wa
                        (float*)buf[0], B);
     LAUNCH_CHECK("k_hub_conv0");
   }
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_CONV0, 0);
   for (int c = 1; c < L.nc; ++c) {
     HGemm16Args a{};
     a.X = buf[(c - 1) & 1]; a.xbs = (long long)ws.T[c - 1] * L.C[c - 1]; a.ldrow = L.C[c - 1]; a.Cin = L.C[c - 1]; a.stride = L.s[c];
     a.Tin = ws.T[c - 1];
     a.W = PW(L.conv[c]); a.K = L.k[c] * L.C[c - 1];
     a.Y = buf[c & 1]; a.ybs = (long long)ws.T[c] * L.C[c]; a.ldy = L.C[c]; a.M = ws.T[c]; a.N = L.C[c];
-    if (c + 1 < L.nc) TRY_G((hub_gemm16<HEPI_GELU, true, true>(st, a, B, 1)));
-    else TRY_G((hub_gemm16<HEPI_GELU, true, false>(st, a, B, 1)));
+    if (c + 1 < L.nc) TRY_G((hub_gemm16<HEPI_GELU, true, true>(st, a, B, 1, tile)));
+    else TRY_G((hub_gemm16<HEPI_GELU, true, false>(st, a, B, 1, tile)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_CONV, c);
   }
   // feature projection: LayerNorm (fp32) -> Linear (+ bias) -> h
   const int CL = L.C[L.nc - 1];
   float* feat = (float*)buf[(L.nc - 1) & 1];
   float* fn = (float*)buf[L.nc & 1];
   TRY_G(hub_norm(st, feat, fn, M, CL, P + L.fp_w, P + L.fp_b, L.eps));
-  TRY_G((hub_dense16<HEPI_BIAS, false, false>(st, fn, PW(L.proj_w), P + L.proj_b, h, nullptr, M, H, CL)));
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FPNORM, 0);
+  TRY_G((hub_dense16<HEPI_BIAS, false, false>(st, fn, PW(L.proj_w), P + L.proj_b, h, nullptr, M, H, CL, tile)));
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FPROJ, 0);
   {
     HGemm16Args a{};
     a.X = h; a.xbs = (long long)T * H; a.ldrow = H; a.Cin = L.Cg; a.stride = 1; a.pad = L.pk / 2; a.xg = L.Cg;
     a.nvalid = flen; a.Tin = T;
     a.W = PW(L.pos_w); a.K = L.pk * L.Cg; a.bias = P + L.pos_b;
     a.Y = att; a.R = h; a.ybs = (long long)T * H; a.ldy = H; a.M = T; a.N = L.Cg;
-    TRY_G((hub_gemm16<HEPI_GELU_RESID, false, false>(st, a, B, L.pg)));
+    TRY_G((hub_gemm16<HEPI_GELU_RESID, false, false>(st, a, B, L.pg, tile)));
   }
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_POS, 0);
   TRY_G(hub_norm(st, att, L.L ? h : out, M, H, P + L.enc_w, P + L.enc_b, L.eps));
+  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_ENCNORM, 0);
   HAttn16Args aa{big, vt, att16, flen, H, L.heads, L.DH, T, ws.Tp, 1.4426950408889634f / sqrtf((float)L.DH)};
   for (int l = 0; l < L.L; ++l) {
     const size_t y = (size_t)l * L.layer;
-    TRY_G((hub_dense16<HEPI_BIAS, false, true>(st, h, PW(y + L.qkv_w), P + y + L.qkv_b, big, nullptr, M, 3 * H, H)));
+    TRY_G((hub_dense16<HEPI_BIAS, false, true>(st, h, PW(y + L.qkv_w), P + y + L.qkv_b, big, nullptr, M, 3 * H, H, tile)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_QKV, l);
     hipLaunchKernelGGL(k_hub_vt, dim3(ws.Tp / 32, L.heads, B), dim3(256), 0, st, aa);
     LAUNCH_CHECK("k_hub_vt");
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_VT, l);
     const dim3 grid((T + 63) / 64, L.heads, B);
     TRY_G(with_head_tiles<8>(L.DH, [&](auto dt) -> int {  // head_dim = 32 KT: an even count of 16-wide tiles (hub_layout16)
       constexpr int DT = decltype(dt)::value;
@@ -519,11 +530,17 @@ static int hub_forward16(const HubLayout& L, const void* packed, const float* wa
         return fail(EDTTS_ERR_UNSUPPORTED, "head_dim=%d: compute_dtype bf16 needs a multiple of 32 up to 128", L.DH);
       }
     }));
-    TRY_G((hub_dense16<HEPI_RESID, true, false>(st, att16, PW(y + L.o_w), P + y + L.o_b, h, h, M, H, H)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_ATTN, l);
+    TRY_G((hub_dense16<HEPI_RESID, true, false>(st, att16, PW(y + L.o_w), P + y + L.o_b, h, h, M, H, H, tile)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_OPROJ, l);
     TRY_G(hub_norm(st, h, h, M, H, P + y + L.ln1_w, P + y + L.ln1_b, L.eps));
-    TRY_G((hub_dense16<HEPI_GELU, false, true>(st, h, PW(y + L.ff1_w), P + y + L.ff1_b, big, nullptr, M, L.I, H)));
-    TRY_G((hub_dense16<HEPI_RESID, true, false>(st, big, PW(y + L.ff2_w), P + y + L.ff2_b, h, h, M, H, L.I)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LN1, l);
+    TRY_G((hub_dense16<HEPI_GELU, false, true>(st, h, PW(y + L.ff1_w), P + y + L.ff1_b, big, nullptr, M, L.I, H, tile)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FF1, l);
+    TRY_G((hub_dense16<HEPI_RESID, true, false>(st, big, PW(y + L.ff2_w), P + y + L.ff2_b, h, h, M, H, L.I, tile)));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FF2, l);
     TRY_G(hub_norm(st, h, l + 1 < L.L ? h : out, M, H, P + y + L.ln2_w, P + y + L.ln2_b, L.eps));
+    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LN2, l);
   }
   if (flen) {
     hipLaunchKernelGGL(k_hub_zero_past, dim3(hub_grid((size_t)M * H / 4)), dim3(256), 0, st, out, flen, B, T, H);
@@ -591,6 +608,54 @@ int edtts_hubert_forward_dt(const EdttsHubertDims* dims, int compute_dtype, cons
   if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
   if (!hub_al16(packed) || !hub_al16(out) || !hub_al16(workspace)) return fail(EDTTS_ERR_ARG, "packed, out and workspace must be 16-byte aligned");
   return hub_forward16(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream);
+}
+
+int edtts_hubert_forward_until(const EdttsHubertDims* dims, int compute_dtype, const void* packed, const float* wav, int B, int T_audio,
+                               const int64_t* lengths, float* out, void* workspace, int stop_site, int stop_index, int tile, void* stream) {
+  using namespace edtts_hub;
+  TRY_G(hub_dtype(compute_dtype));
+  const bool bf16 = compute_dtype == EDTTS_HUBERT_BF16;
+  HubLayout L;
+  TRY_G(bf16 ? hub_layout16(dims, L) : hub_layout(dims, L));
+  if (!packed || !wav || !out || !workspace) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
+  if (!hub_al16(packed) || !hub_al16(out) || !hub_al16(workspace)) return fail(EDTTS_ERR_ARG, "packed, out and workspace must be 16-byte aligned");
+  HubStop stop;
+  stop.site = stop_site; stop.index = stop_index; stop.tile = tile;
+  TRY_G(hub_stop_check(L, bf16, lengths != nullptr, stop));
+  if (bf16) return hub_forward16(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream, stop);
+  return hub_forward32(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream, stop);
+}
+
+int edtts_hubert_workspace_region(const EdttsHubertDims* dims, int compute_dtype, int B, int T_audio, int which, size_t* offset_bytes,
+                                  size_t* bytes) {
+  using namespace edtts_hub;
+  TRY_G(hub_dtype(compute_dtype));
+  const bool bf16 = compute_dtype == EDTTS_HUBERT_BF16;
+  HubLayout L;
+  TRY_G(bf16 ? hub_layout16(dims, L) : hub_layout(dims, L));
+  if (!offset_bytes || !bytes) return fail(EDTTS_ERR_ARG, "offset_bytes/bytes is NULL");
+  if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
+  // the members' offsets in layout order, closed by the total: a member reaches up to the next one's offset
+  size_t at[EDTTS_HUB_WS_COUNT + 1];
+  int n = 0;
+  if (bf16) {
+    HubWs16 W;
+    TRY_G(hub_ws16(L, B, T_audio, W));
+    const size_t o[] = {W.lens, W.stats, W.part, W.buf0, W.buf1, W.h, W.att, W.big, W.vt, W.total};
+    for (size_t v : o) at[n++] = v;
+  } else {
+    HubWs W;
+    TRY_G(hub_ws(L, B, T_audio, W));
+    const size_t o[] = {W.lens, W.stats, W.part, W.buf0, W.buf1, W.h, W.att, W.big, W.total};
+    for (size_t v : o) at[n++] = v;
+  }
+  if (which < 0 || which >= n - 1)
+    return fail(EDTTS_ERR_ARG, "edtts_hubert_workspace_region: which=%d: expected an EDTTS_HUB_WS_* member in [0, %d)%s", which, n - 1,
+                bf16 ? "" : " (EDTTS_HUB_WS_VT exists only under EDTTS_HUBERT_BF16)");
+  *offset_bytes = at[which];
+  *bytes = at[which + 1] - at[which];
+  return EDTTS_OK;
 }
 
 }  // extern "C"

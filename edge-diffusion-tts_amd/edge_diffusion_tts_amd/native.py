@@ -261,6 +261,8 @@ _ABI = {
     "edtts_hubert_pack_dt": (_STATUS, (hdp, i32, p_vp, i32, vp, vp)),
     "edtts_hubert_workspace_bytes_dt": (_STATUS, (hdp, i32, i32, i32, p_sz)),
     "edtts_hubert_forward_dt": (_STATUS, (hdp, i32, vp, vp, i32, i32, vp, vp, vp, vp)),
+    "edtts_hubert_forward_until": (_STATUS, (hdp, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp)),
+    "edtts_hubert_workspace_region": (_STATUS, (hdp, i32, i32, i32, i32, p_sz, p_sz)),
     "edtts_melspec": (_STATUS, (vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp)),
     "edtts_mel_segment_stats": (_STATUS, (vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp)),
     "edtts_logmel_stats": (_STATUS, (vp, i32, i32, i32, i32, vp, i32, vp, vp, vp)),
@@ -1386,13 +1388,84 @@ def hubert_pack(dims: EdttsHubertDims, tensors: Sequence[torch.Tensor], packed: 
         lib().edtts_hubert_pack(C.byref(dims), ptrs, len(tensors), _dev_ptr(packed, torch.uint8, "packed"), _stream(packed.device))
 
 
+# the sites of the backbone's launch list, as edtts_hubert_forward_until names them (include/edtts.h: EDTTS_HUB_*), in launch order
+HUB_SITES = ("lens", "gnstat", "conv0", "conv", "fpnorm", "fproj", "pos", "encnorm", "qkv", "vt", "attn", "oproj", "ln1", "ff1", "ff2",
+             "ln2", "zero")
+HUB_LAYER_SITES = HUB_SITES[8:16]
+HUB_GEMM_SITES = ("conv", "fproj", "pos", "qkv", "oproj", "ff1", "ff2")
+# the members of the backbone's workspace, as edtts_hubert_workspace_region names them (include/edtts.h: EDTTS_HUB_WS_*)
+HUB_WS_REGIONS = ("lens", "stats", "part", "buf0", "buf1", "h", "att", "big", "vt")
+HUB_GN_CHUNK = 256  # conv0 frames per partial sum of the GroupNorm statistics (csrc/edtts_hubert.h: kGnChunk)
+
+
+def hubert_last_site(dims: EdttsHubertDims, with_lengths: bool) -> Tuple[str, int]:
+    """(site, index) of the last launch of a whole forward."""
+    if with_lengths:
+        return "zero", 0
+    return ("ln2", dims.num_layers - 1) if dims.num_layers else ("encnorm", 0)
+
+
+def hubert_workspace_region(dims: EdttsHubertDims, B: int, T_audio: int, compute_dtype: int, which) -> Tuple[int, int]:
+    """(offset, bytes) of a workspace member (a name of HUB_WS_REGIONS or its EDTTS_HUB_WS_* number)."""
+    w = HUB_WS_REGIONS.index(which) if isinstance(which, str) else int(which)
+    off, n = C.c_size_t(0), C.c_size_t(0)
+    lib().edtts_hubert_workspace_region(C.byref(dims), int(compute_dtype), int(B), int(T_audio), w, C.byref(off), C.byref(n))
+    return int(off.value), int(n.value)
+
+
+def hubert_workspace_views(dims: EdttsHubertDims, B: int, T_audio: int, compute_dtype: int, workspace: torch.Tensor) -> dict:
+    """Typed views of `workspace` (uint8), one per thing a site of HUB_SITES writes (include/edtts.h, "where each site's output lies"):
+    lens int64 [2][B] (conv0 frames | output frames), stats fp32 [B][2][C0], part fp64 [B][chunks][C0][2], conv: a list with stage
+    i's output [B][T_i][C_i] (bf16 under compute_dtype bf16 for every stage but the last), fpnorm fp32 [B][T][C_last], h and att fp32
+    [B][T][H], qkv [B][T][3H] and ff [B][T][I] (fp32; bf16 under bf16), and under bf16 att16 [B][T][H] and vt [B][heads][head_dim][Tp]."""
+    bf = bool(compute_dtype)
+    reg = {}
+    for name in HUB_WS_REGIONS[:8 + bf]:
+        off, n = hubert_workspace_region(dims, B, T_audio, compute_dtype, name)
+        reg[name] = workspace[off:off + n]
+    nc, H, I = dims.n_conv, dims.hidden, dims.intermediate
+    Ts, n = [], int(T_audio)
+    for i in range(nc):
+        n = (n - dims.conv_kernel[i]) // dims.conv_stride[i] + 1
+        Ts.append(n)
+    T, C0 = Ts[-1], dims.conv_dim[0]
+
+    def view(raw, dtype, *shape):
+        count = 1
+        for s in shape:
+            count *= s
+        return raw.view(dtype)[:count].view(*shape)
+
+    f, h16 = torch.float32, torch.bfloat16
+    out = dict(lens=view(reg["lens"], torch.int64, 2, B), stats=view(reg["stats"], f, B, 2, C0),
+               part=view(reg["part"], torch.float64, B, (Ts[0] + HUB_GN_CHUNK - 1) // HUB_GN_CHUNK, C0, 2))
+    buf = (reg["buf0"], reg["buf1"])
+    out["conv"] = [view(buf[i & 1], h16 if bf and i + 1 < nc else f, B, Ts[i], dims.conv_dim[i]) for i in range(nc)]
+    out["fpnorm"] = view(buf[nc & 1], f, B, T, dims.conv_dim[nc - 1])
+    out["h"], out["att"] = view(reg["h"], f, B, T, H), view(reg["att"], f, B, T, H)
+    out["qkv"], out["ff"] = view(reg["big"], h16 if bf else f, B, T, 3 * H), view(reg["big"], h16 if bf else f, B, T, I)
+    if bf:
+        out["att16"] = view(reg["att"], h16, B, T, H)
+        out["vt"] = view(reg["vt"], h16, B, dims.heads, H // dims.heads, (T + 31) // 32 * 32)
+    return out
+
+
 def hubert_forward(dims: EdttsHubertDims, packed: torch.Tensor, wav: torch.Tensor, lengths: Optional[torch.Tensor], out: torch.Tensor,
-                   workspace: torch.Tensor, compute_dtype: int = 0) -> None:
-    """wav [B, T_audio] -> out [B, T_feat, hidden] on the current stream (include/edtts.h: edtts_hubert_forward / _forward_dt)."""
+                   workspace: torch.Tensor, compute_dtype: int = 0, until=None, tile: int = 0) -> None:
+    """wav [B, T_audio] -> out [B, T_feat, hidden] on the current stream (include/edtts.h: edtts_hubert_forward / _forward_dt).
+
+    ``until``: (site, index) -- edtts_hubert_forward_until: the same launches, stopped after the last one of that site (a name of
+    HUB_SITES or its EDTTS_HUB_* number; index: the conv layer of "conv", the encoder layer of HUB_LAYER_SITES, else 0).  ``tile``:
+    0 or the forced GEMM tile width (2: 64 x 64, 4: 128 x 128).  Diagnostics; the whole forward is ``until=None, tile=0``."""
     B, T = wav.shape
     args = (_dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(wav, torch.float32, "wav"), B, T,
             _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(out, torch.float32, "out"),
             _dev_ptr(workspace, torch.uint8, "workspace"), _stream(wav.device))
+    if until is not None or tile:
+        site, index = hubert_last_site(dims, lengths is not None) if until is None else until
+        site = HUB_SITES.index(site) if isinstance(site, str) else int(site)
+        lib().edtts_hubert_forward_until(C.byref(dims), int(compute_dtype), *args[:-1], site, int(index), int(tile), args[-1])
+        return
     if compute_dtype:
         lib().edtts_hubert_forward_dt(C.byref(dims), int(compute_dtype), *args)
     else:

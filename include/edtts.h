@@ -1033,8 +1033,75 @@ int edtts_hubert_pack_dt(const EdttsHubertDims* dims, int compute_dtype, const v
 int edtts_hubert_workspace_bytes_dt(const EdttsHubertDims* dims, int compute_dtype, int B, int T_audio, size_t* out_bytes);
 int edtts_hubert_forward_dt(const EdttsHubertDims* dims, int compute_dtype, const void* packed, const float* wav, int B, int T_audio,
                             const int64_t* lengths, float* out, void* workspace, void* stream);
+/* The backbone's launch list, site by site (a diagnostic: tests/hubert_audit_util.py audits every site against fp64).
+ * edtts_hubert_forward_until takes the arguments of edtts_hubert_forward_dt plus (stop_site, stop_index, tile) before `stream`.  It
+ * makes the launches of edtts_hubert_forward_dt -- same kernels, same arguments, same order -- and returns after the last launch of
+ * site `stop_site`; stop_index is the conv layer (1 .. n_conv - 1) for EDTTS_HUB_CONV, the encoder layer for EDTTS_HUB_QKV ..
+ * EDTTS_HUB_LN2 and 0 otherwise.  A site the call does not have is EDTTS_ERR_ARG with a message that names it: EDTTS_HUB_VT under
+ * fp32, EDTTS_HUB_LENS / _ZERO without lengths, an index out of range.  tile 0 keeps the GEMM launchers' own choice of tile (128 x
+ * 128 when that leaves at least two tiles per compute unit and N > 64, else 64 x 64); 2 or 4 forces the 64- or the 128-wide tile for
+ * every GEMM launch of the call (results are bitwise independent of the tile); any other value is EDTTS_ERR_ARG.  The plain entry
+ * points are "no stop, tile 0".  Graph capture of a stopped call is not supported.
+ * Where each site's output lies (members as edtts_hubert_workspace_region names them; T_i: frames after conv stage i of T_audio
+ * samples, T = T_feat, H = hidden; "16": bf16 under EDTTS_HUBERT_BF16, fp32 otherwise):
+ *   LENS     lens     int64 [2][B]: conv0 frames | output frames per utterance
+ *   GNSTAT   stats    fp32 [B][2][C0]: scale = gamma rstd | shift = beta - mean scale (part: fp64 [B][chunks][C0][2], chunks = ceil(T_0 / 256))
+ *   CONV0    buf0     [B][T_0][C0], 16 when n_conv > 1; rows past an utterance's conv0 frames are 0
+ *   CONV i   buf(i&1) [B][T_i][C_i], 16 for i < n_conv - 1, fp32 for the last stage (a LayerNorm reads it)
+ *   FPNORM   buf(n_conv&1) fp32 [B][T][C_last] (the buffer the last conv did not write)
+ *   FPROJ    h        fp32 [B][T][H]
+ *   POS      att      fp32 [B][T][H]: h + GELU(pos_conv(h) + bias)
+ *   ENCNORM  h        fp32 [B][T][H]; `out` when num_layers = 0
+ *   QKV      big      [B T][3H] 16: q | k | v rows
+ *   VT       vt       bf16 [B][heads][head_dim][Tp], Tp = T rounded up to 32: V^T in the key-slot order of csrc/edtts_hubert16.h inside
+ *                     every 32-key chunk, zeros past an utterance's count; chunks wholly past it are not written
+ *   ATTN     att      [B][T][H] 16; 64-query blocks wholly past an utterance's count are not written
+ *   OPROJ    h        fp32, in place (the residual)          LN1  h  fp32, in place
+ *   FF1      big      [B T][intermediate] 16                  FF2  h  fp32, in place (the residual)
+ *   LN2      h        fp32, in place; `out` for the last layer
+ *   ZERO     out      rows past an utterance's count set to 0
+ * Rows past an utterance's frame count hold whatever the row-local steps made of the padding; nothing live reads them. */
+enum {
+  EDTTS_HUB_LENS = 0,     /* (lengths only) k_hub_lens */
+  EDTTS_HUB_GNSTAT = 1,   /* k_hub_gn_part + k_hub_gn_final */
+  EDTTS_HUB_CONV0 = 2,    /* k_hub_conv0 / k_hub_conv0_16 */
+  EDTTS_HUB_CONV = 3,     /* conv stage stop_index = 1 .. n_conv - 1 */
+  EDTTS_HUB_FPNORM = 4,   /* the feature projection's LayerNorm */
+  EDTTS_HUB_FPROJ = 5,    /* the feature projection */
+  EDTTS_HUB_POS = 6,      /* the positional conv, GELU and residual */
+  EDTTS_HUB_ENCNORM = 7,  /* the encoder's LayerNorm */
+  EDTTS_HUB_QKV = 8,      /* per layer from here to EDTTS_HUB_LN2 */
+  EDTTS_HUB_VT = 9,       /* (bf16 only) k_hub_vt */
+  EDTTS_HUB_ATTN = 10,
+  EDTTS_HUB_OPROJ = 11,
+  EDTTS_HUB_LN1 = 12,
+  EDTTS_HUB_FF1 = 13,
+  EDTTS_HUB_FF2 = 14,
+  EDTTS_HUB_LN2 = 15,
+  EDTTS_HUB_ZERO = 16,    /* (lengths only) k_hub_zero_past */
+  EDTTS_HUB_COUNT = 17
+};
+int edtts_hubert_forward_until(const EdttsHubertDims* dims, int compute_dtype, const void* packed, const float* wav, int B, int T_audio,
+                               const int64_t* lengths, float* out, void* workspace, int stop_site, int stop_index, int tile, void* stream);
+/* Offset and extent (up to the next member: the member's bytes rounded up to 256) of workspace member `which` for one (dims,
+ * compute_dtype, B, T_audio), answered by the code that lays the workspace out.  EDTTS_HUB_WS_VT exists under EDTTS_HUBERT_BF16 only
+ * (EDTTS_ERR_ARG otherwise).  No GPU call. */
+enum {
+  EDTTS_HUB_WS_LENS = 0,
+  EDTTS_HUB_WS_STATS = 1,
+  EDTTS_HUB_WS_PART = 2,
+  EDTTS_HUB_WS_BUF0 = 3,
+  EDTTS_HUB_WS_BUF1 = 4,
+  EDTTS_HUB_WS_H = 5,
+  EDTTS_HUB_WS_ATT = 6,
+  EDTTS_HUB_WS_BIG = 7,
+  EDTTS_HUB_WS_VT = 8,
+  EDTTS_HUB_WS_COUNT = 9
+};
+int edtts_hubert_workspace_region(const EdttsHubertDims* dims, int compute_dtype, int B, int T_audio, int which, size_t* offset_bytes,
+                                  size_t* bytes);
 
-/* ---- audio front end  (the torchaudio ops the reference calls at every entry point: generate_sample.py:75-116,
+/* ---- audio front end (the torchaudio ops the reference calls at every entry point: generate_sample.py:75-116,
  * data/collate.py:34-60, inference_pipeline.py:206-207, 354-355) -------------------------------------------------------------------
  * edtts_melspec: torchaudio.transforms.MelSpectrogram(n_fft = win_length = 1024, hop, center=True, pad_mode="reflect", periodic Hann
  * window, onesided, norm=None, mel_scale="htk", power 2 or 1) of wav [B, L] -> mode EDTTS_MEL_POWER: the mel [B, n_mels, T] (torch
