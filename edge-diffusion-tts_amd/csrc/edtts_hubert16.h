@@ -1,4 +1,5 @@
-// edtts_hubert16.h -- the bf16 compute path of the HuBERT backbone (included by edtts_kernels.hip after edtts_hubert.h).
+// edtts_hubert16.h -- the kernels of the HuBERT backbone's bf16 compute path (included by edtts_kernels.hip after edtts_hubert.h;
+// edtts_hubert_host.h launches them).
 //
 // Same forward as edtts_hubert.h with the two operands of every contraction after conv0 rounded to bf16 (round to nearest even,
 // v_cvt_pk_bf16_f32) and the products on v_mfma_f32_16x16x32_bf16 with fp32 accumulators:
@@ -286,376 +287,4 @@ __global__ __launch_bounds__(256) void k_hub_attn16(HAttn16Args a) {
     *reinterpret_cast<edtts16::f2s*>(orow + 16 * t) = edtts16::pack4(acc[t] * inv);
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------------
-// The blob of the bf16 path: HubLayout's tensors in HubLayout's order, offsets in floats; a matrix that feeds an MFMA is bf16 (half
-// the floats), conv0 / GroupNorm / biases / norm parameters stay fp32.
-static int hub_layout16(const EdttsHubertDims* d, HubLayout& L) {
-  const int rc = hub_layout(d, L);
-  if (rc != EDTTS_OK) return rc;
-  for (int i = 0; i < L.nc; ++i)
-    if (L.C[i] % 8) return fail(EDTTS_ERR_UNSUPPORTED, "conv_dim[%d]=%d: compute_dtype bf16 needs a multiple of 8", i, L.C[i]);
-  if (L.H % 8) return fail(EDTTS_ERR_UNSUPPORTED, "hidden_size=%d: compute_dtype bf16 needs a multiple of 8", L.H);
-  if (L.DH % 32)
-    return fail(EDTTS_ERR_UNSUPPORTED, "head_dim=%d (hidden_size=%d / num_attention_heads=%d): compute_dtype bf16 needs a multiple of 32",
-                L.DH, L.H, L.heads);
-  if (L.I % 8) return fail(EDTTS_ERR_UNSUPPORTED, "intermediate_size=%d: compute_dtype bf16 needs a multiple of 8", L.I);
-  if (L.Cg % 8)
-    return fail(EDTTS_ERR_UNSUPPORTED, "num_conv_pos_embedding_groups=%d: compute_dtype bf16 needs hidden_size / groups a multiple of 8", L.pg);
-  size_t o = 0;
-  auto take = [&](size_t n) { const size_t at = o; o += al64(n); return at; };
-  auto half = [&](size_t n) { return take((n + 1) / 2); };
-  L.conv0 = take((size_t)L.C[0] * L.k[0]);
-  L.gn_w = take(L.C[0]);
-  L.gn_b = take(L.C[0]);
-  for (int i = 1; i < L.nc; ++i) L.conv[i] = half((size_t)L.C[i] * L.k[i] * L.C[i - 1]);
-  const int CL = L.C[L.nc - 1];
-  L.fp_w = take(CL); L.fp_b = take(CL);
-  L.proj_w = half((size_t)L.H * CL); L.proj_b = take(L.H);
-  L.pos_w = half((size_t)L.H * L.pk * L.Cg); L.pos_b = take(L.H);
-  L.enc_w = take(L.H); L.enc_b = take(L.H);
-  const size_t l0 = o;
-  L.qkv_w = half((size_t)3 * L.H * L.H); L.qkv_b = take(3 * L.H);
-  L.o_w = half((size_t)L.H * L.H); L.o_b = take(L.H);
-  L.ln1_w = take(L.H); L.ln1_b = take(L.H);
-  L.ff1_w = half((size_t)L.I * L.H); L.ff1_b = take(L.I);
-  L.ff2_w = half((size_t)L.H * L.I); L.ff2_b = take(L.H);
-  L.ln2_w = take(L.H); L.ln2_b = take(L.H);
-  L.layer = o - l0;
-  L.total = l0 + (size_t)L.L * L.layer;
-  return EDTTS_OK;
-}
-
-struct HubWs16 {
-  int T[kMaxConv];
-  int nch, Tp;
-  size_t lens, stats, part, buf0, buf1, h, att, big, vt, total;  // bytes
-};
-// element size of conv stage i's output: bf16 when the next conv reads it, fp32 when the feature projection's LayerNorm does
-static size_t hub_esz16(const HubLayout& L, int i) { return i + 1 < L.nc ? 2 : 4; }
-static int hub_ws16(const HubLayout& L, int B, int T_audio, HubWs16& W) {
-  HubWs W32;
-  const int rc = hub_ws(L, B, T_audio, W32);  // (the frame counts and the fp32 path's argument checks)
-  if (rc != EDTTS_OK) return rc;
-  W = HubWs16{};
-  for (int i = 0; i < L.nc; ++i) W.T[i] = W32.T[i];
-  W.nch = W32.nch;
-  const int T = W.T[L.nc - 1];
-  W.Tp = (T + 31) & ~31;
-  size_t s0 = 0, s1 = 0;
-  for (int i = 0; i < L.nc; ++i) {
-    const size_t sz = (size_t)B * W.T[i] * L.C[i] * hub_esz16(L, i);
-    if (i % 2 == 0) s0 = sz > s0 ? sz : s0;
-    else s1 = sz > s1 ? sz : s1;
-  }
-  const size_t fp = (size_t)B * T * L.C[L.nc - 1] * 4;
-  if (L.nc % 2 == 1) s1 = fp > s1 ? fp : s1;
-  else s0 = fp > s0 ? fp : s0;
-  const size_t M = (size_t)B * T, wide = (size_t)(3 * L.H > L.I ? 3 * L.H : L.I);
-  size_t o = 0;
-  auto take = [&](size_t n) { const size_t at = o; o += al256(n); return at; };
-  W.lens = take((size_t)2 * B * 8);
-  W.stats = take((size_t)B * L.C[0] * 2 * 4);
-  W.part = take((size_t)B * W.nch * L.C[0] * 2 * 8);
-  W.buf0 = take(s0);
-  W.buf1 = take(s1);
-  W.h = take(M * L.H * 4);
-  W.att = take(M * L.H * 4);   // the positional conv's output (fp32), then every layer's attention output (bf16)
-  W.big = take(M * wide * 2);  // q | k | v rows, then the FFN intermediate (bf16)
-  W.vt = take((size_t)B * L.H * W.Tp * 2);
-  W.total = o;
-  return EDTTS_OK;
-}
-
-template <int EPI, bool XBF, bool YBF>
-static int hub_gemm16(hipStream_t st, HGemm16Args a, int B, int G, int tile = 0) {
-  if (hub_wide_tile(a.M, a.N, G, B, tile)) {  // the rule of hub_gemm: below two 128-tiles per CU the 64-wide tile
-    a.ntn = (a.N + 127) / 128;
-    hipLaunchKernelGGL((k_hub_gemm16<EPI, 4, XBF, YBF>), dim3((a.M + 127) / 128, a.ntn * G, B), dim3(256), 0, st, a);
-  } else {
-    a.ntn = (a.N + 63) / 64;
-    hipLaunchKernelGGL((k_hub_gemm16<EPI, 2, XBF, YBF>), dim3((a.M + 63) / 64, a.ntn * G, B), dim3(256), 0, st, a);
-  }
-  LAUNCH_CHECK("k_hub_gemm16");
-  return EDTTS_OK;
-}
-// a plain row-major GEMM: Y[M][N] = epi(X[M][K] W[N][K]^T)
-template <int EPI, bool XBF, bool YBF>
-static int hub_dense16(hipStream_t st, const void* X, const __bf16* W, const float* bias, void* Y, const float* R, int M, int N, int K,
-                       int tile = 0) {
-  HGemm16Args a{};
-  a.X = X; a.ldrow = K; a.Cin = K; a.stride = 1; a.Tin = M;
-  a.W = W; a.K = K; a.bias = bias; a.Y = Y; a.R = R; a.ldy = N; a.M = M; a.N = N;
-  return hub_gemm16<EPI, XBF, YBF>(st, a, 1, 1, tile);
-}
-
-static int hub_pack16(const HubLayout& L, const void* const* slots, void* packed, hipStream_t st) {
-  float* P = (float*)packed;
-  const float* const* s = (const float* const*)slots;
-  int i = 0;
-  auto copy = [&](size_t off, size_t n) -> int {
-    HIP_TRY(hipMemcpyAsync(P + off, s[i++], n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return EDTTS_OK;
-  };
-  auto mat = [&](size_t off, int co, int ci, int k) -> int {
-    hipLaunchKernelGGL(k_hub_pack16, dim3(hub_grid((size_t)co * ci * k)), dim3(256), 0, st, s[i++], (__bf16*)(P + off), co, ci, k);
-    LAUNCH_CHECK("k_hub_pack16");
-    return EDTTS_OK;
-  };
-  const int H = L.H, CL = L.C[L.nc - 1];
-  hipLaunchKernelGGL(k_hub_pack_conv, dim3(hub_grid((size_t)L.C[0] * L.k[0])), dim3(256), 0, st, s[i++], P + L.conv0, 1, L.C[0], L.k[0]);
-  LAUNCH_CHECK("k_hub_pack_conv");
-  TRY_G(copy(L.gn_w, L.C[0]));
-  TRY_G(copy(L.gn_b, L.C[0]));
-  for (int c = 1; c < L.nc; ++c) TRY_G(mat(L.conv[c], L.C[c], L.C[c - 1], L.k[c]));
-  TRY_G(copy(L.fp_w, CL));
-  TRY_G(copy(L.fp_b, CL));
-  TRY_G(mat(L.proj_w, H, CL, 1));
-  TRY_G(copy(L.proj_b, H));
-  TRY_G(mat(L.pos_w, H, L.Cg, L.pk));
-  TRY_G(copy(L.pos_b, H));
-  TRY_G(copy(L.enc_w, H));
-  TRY_G(copy(L.enc_b, H));
-  for (int l = 0; l < L.L; ++l) {
-    const size_t b0 = (size_t)l * L.layer;
-    for (int p = 0; p < 3; ++p) {  // q, k, v -> one [3H][H] matrix and a [3H] bias
-      hipLaunchKernelGGL(k_hub_pack16, dim3(hub_grid((size_t)H * H)), dim3(256), 0, st, s[i++],
-                         (__bf16*)(P + b0 + L.qkv_w) + (size_t)p * H * H, H, H, 1);
-      LAUNCH_CHECK("k_hub_pack16");
-      TRY_G(copy(b0 + L.qkv_b + (size_t)p * H, H));
-    }
-    TRY_G(mat(b0 + L.o_w, H, H, 1));
-    TRY_G(copy(b0 + L.o_b, H));
-    TRY_G(copy(b0 + L.ln1_w, H));
-    TRY_G(copy(b0 + L.ln1_b, H));
-    TRY_G(mat(b0 + L.ff1_w, L.I, H, 1));
-    TRY_G(copy(b0 + L.ff1_b, L.I));
-    TRY_G(mat(b0 + L.ff2_w, H, L.I, 1));
-    TRY_G(copy(b0 + L.ff2_b, H));
-    TRY_G(copy(b0 + L.ln2_w, H));
-    TRY_G(copy(b0 + L.ln2_b, H));
-  }
-  return EDTTS_OK;
-}
-
-// The bf16 forward's launch list, with the stop sites of hub_forward32 (and EDTTS_HUB_VT).
-static int hub_forward16(const HubLayout& L, const void* packed, const float* wav, int B, int T_audio, const int64_t* lengths, float* out,
-                         void* workspace, hipStream_t st, const HubStop stop = HubStop{}) {
-  HubWs16 ws;
-  TRY_G(hub_ws16(L, B, T_audio, ws));
-  const int tile = stop.tile;
-  const float* P = (const float*)packed;
-  auto PW = [&](size_t off) { return (const __bf16*)(P + off); };
-  char* wb = (char*)workspace;
-  const int T = ws.T[L.nc - 1], H = L.H, M = B * T;
-  int64_t *len0 = nullptr, *flen = nullptr;
-  if (lengths) {
-    len0 = (int64_t*)(wb + ws.lens);
-    flen = len0 + B;
-    ConvGeo geo{};
-    geo.n = L.nc;
-    for (int i = 0; i < L.nc; ++i) { geo.k[i] = L.k[i]; geo.s[i] = L.s[i]; }
-    hipLaunchKernelGGL(k_hub_lens, dim3((B + 63) / 64), dim3(64), 0, st, lengths, B, T_audio, hub_min_samples(L), geo, len0, flen);
-    LAUNCH_CHECK("k_hub_lens");
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LENS, 0);
-  }
-  float* stats = (float*)(wb + ws.stats);
-  void* buf[2] = {wb + ws.buf0, wb + ws.buf1};
-  float *h = (float*)(wb + ws.h), *att = (float*)(wb + ws.att);
-  __bf16 *att16 = (__bf16*)(wb + ws.att), *big = (__bf16*)(wb + ws.big), *vt = (__bf16*)(wb + ws.vt);
-  // conv0 + GroupNorm + GELU -> buf[0] (bf16 when a conv reads it)
-  double* part = (double*)(wb + ws.part);
-  hipLaunchKernelGGL(k_hub_gn_part, dim3((L.C[0] + 63) / 64, ws.nch, B), dim3(256), 0, st, wav, T_audio, P + L.conv0, L.C[0], L.k[0],
-                     L.s[0], len0, ws.T[0], part);
-  LAUNCH_CHECK("k_hub_gn_part");
-  hipLaunchKernelGGL(k_hub_gn_final, dim3((B * L.C[0] + 255) / 256), dim3(256), 0, st, part, ws.nch, L.C[0], len0, ws.T[0], 1e-5f,
-                     P + L.gn_w, P + L.gn_b, stats, B);
-  LAUNCH_CHECK("k_hub_gn_final");
-  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_GNSTAT, 0);
-  const dim3 g0(hub_grid((size_t)B * ws.T[0] * L.C[0] / 4));
-  if (L.nc > 1) {
-    hipLaunchKernelGGL(k_hub_conv0_16, g0, dim3(256), 0, st, wav, T_audio, P + L.conv0, L.C[0], L.k[0], L.s[0], len0, ws.T[0], stats,
-                       (__bf16*)buf[0], B);
-    LAUNCH_CHECK("k_hub_conv0_16");
-  } else {
-    hipLaunchKernelGGL(k_hub_conv0, g0, dim3(256), 0, st, wav, T_audio, P + L.conv0, L.C[0], L.k[0], L.s[0], len0, ws.T[0], stats,
-                       (float*)buf[0], B);
-    LAUNCH_CHECK("k_hub_conv0");
-  }
-  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_CONV0, 0);
-  for (int c = 1; c < L.nc; ++c) {
-    HGemm16Args a{};
-    a.X = buf[(c - 1) & 1]; a.xbs = (long long)ws.T[c - 1] * L.C[c - 1]; a.ldrow = L.C[c - 1]; a.Cin = L.C[c - 1]; a.stride = L.s[c];
-    a.Tin = ws.T[c - 1];
-    a.W = PW(L.conv[c]); a.K = L.k[c] * L.C[c - 1];
-    a.Y = buf[c & 1]; a.ybs = (long long)ws.T[c] * L.C[c]; a.ldy = L.C[c]; a.M = ws.T[c]; a.N = L.C[c];
-    if (c + 1 < L.nc) TRY_G((hub_gemm16<HEPI_GELU, true, true>(st, a, B, 1, tile)));
-    else TRY_G((hub_gemm16<HEPI_GELU, true, false>(st, a, B, 1, tile)));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_CONV, c);
-  }
-  // feature projection: LayerNorm (fp32) -> Linear (+ bias) -> h
-  const int CL = L.C[L.nc - 1];
-  float* feat = (float*)buf[(L.nc - 1) & 1];
-  float* fn = (float*)buf[L.nc & 1];
-  TRY_G(hub_norm(st, feat, fn, M, CL, P + L.fp_w, P + L.fp_b, L.eps));
-  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FPNORM, 0);
-  TRY_G((hub_dense16<HEPI_BIAS, false, false>(st, fn, PW(L.proj_w), P + L.proj_b, h, nullptr, M, H, CL, tile)));
-  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FPROJ, 0);
-  {
-    HGemm16Args a{};
-    a.X = h; a.xbs = (long long)T * H; a.ldrow = H; a.Cin = L.Cg; a.stride = 1; a.pad = L.pk / 2; a.xg = L.Cg;
-    a.nvalid = flen; a.Tin = T;
-    a.W = PW(L.pos_w); a.K = L.pk * L.Cg; a.bias = P + L.pos_b;
-    a.Y = att; a.R = h; a.ybs = (long long)T * H; a.ldy = H; a.M = T; a.N = L.Cg;
-    TRY_G((hub_gemm16<HEPI_GELU_RESID, false, false>(st, a, B, L.pg, tile)));
-  }
-  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_POS, 0);
-  TRY_G(hub_norm(st, att, L.L ? h : out, M, H, P + L.enc_w, P + L.enc_b, L.eps));
-  EDTTS_HUB_STOP_AFTER(EDTTS_HUB_ENCNORM, 0);
-  HAttn16Args aa{big, vt, att16, flen, H, L.heads, L.DH, T, ws.Tp, 1.4426950408889634f / sqrtf((float)L.DH)};
-  for (int l = 0; l < L.L; ++l) {
-    const size_t y = (size_t)l * L.layer;
-    TRY_G((hub_dense16<HEPI_BIAS, false, true>(st, h, PW(y + L.qkv_w), P + y + L.qkv_b, big, nullptr, M, 3 * H, H, tile)));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_QKV, l);
-    hipLaunchKernelGGL(k_hub_vt, dim3(ws.Tp / 32, L.heads, B), dim3(256), 0, st, aa);
-    LAUNCH_CHECK("k_hub_vt");
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_VT, l);
-    const dim3 grid((T + 63) / 64, L.heads, B);
-    TRY_G(with_head_tiles<8>(L.DH, [&](auto dt) -> int {  // head_dim = 32 KT: an even count of 16-wide tiles (hub_layout16)
-      constexpr int DT = decltype(dt)::value;
-      if constexpr (DT % 2 == 0) {
-        hipLaunchKernelGGL(k_hub_attn16<DT / 2>, grid, dim3(256), 0, st, aa);
-        LAUNCH_CHECK("k_hub_attn16");
-        return EDTTS_OK;
-      } else {
-        return fail(EDTTS_ERR_UNSUPPORTED, "head_dim=%d: compute_dtype bf16 needs a multiple of 32 up to 128", L.DH);
-      }
-    }));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_ATTN, l);
-    TRY_G((hub_dense16<HEPI_RESID, true, false>(st, att16, PW(y + L.o_w), P + y + L.o_b, h, h, M, H, H, tile)));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_OPROJ, l);
-    TRY_G(hub_norm(st, h, h, M, H, P + y + L.ln1_w, P + y + L.ln1_b, L.eps));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LN1, l);
-    TRY_G((hub_dense16<HEPI_GELU, false, true>(st, h, PW(y + L.ff1_w), P + y + L.ff1_b, big, nullptr, M, L.I, H, tile)));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FF1, l);
-    TRY_G((hub_dense16<HEPI_RESID, true, false>(st, big, PW(y + L.ff2_w), P + y + L.ff2_b, h, h, M, H, L.I, tile)));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_FF2, l);
-    TRY_G(hub_norm(st, h, l + 1 < L.L ? h : out, M, H, P + y + L.ln2_w, P + y + L.ln2_b, L.eps));
-    EDTTS_HUB_STOP_AFTER(EDTTS_HUB_LN2, l);
-  }
-  if (flen) {
-    hipLaunchKernelGGL(k_hub_zero_past, dim3(hub_grid((size_t)M * H / 4)), dim3(256), 0, st, out, flen, B, T, H);
-    LAUNCH_CHECK("k_hub_zero_past");
-  }
-  return EDTTS_OK;
-}
-
-static int hub_dtype(int compute_dtype) {
-  if (compute_dtype != EDTTS_HUBERT_FP32 && compute_dtype != EDTTS_HUBERT_BF16)
-    return fail(EDTTS_ERR_ARG, "compute_dtype=%d: expected EDTTS_HUBERT_FP32 (0) or EDTTS_HUBERT_BF16 (1)", compute_dtype);
-  return EDTTS_OK;
-}
-
 }  // namespace edtts_hub
-
-extern "C" {
-
-int edtts_hubert_packed_bytes_dt(const EdttsHubertDims* dims, int compute_dtype, size_t* out_bytes) {
-  TRY_G(edtts_hub::hub_dtype(compute_dtype));
-  if (compute_dtype == EDTTS_HUBERT_FP32) return edtts_hubert_packed_bytes(dims, out_bytes);
-  edtts_hub::HubLayout L;
-  TRY_G(edtts_hub::hub_layout16(dims, L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  *out_bytes = L.total * sizeof(float);
-  return EDTTS_OK;
-}
-
-int edtts_hubert_workspace_bytes_dt(const EdttsHubertDims* dims, int compute_dtype, int B, int T_audio, size_t* out_bytes) {
-  TRY_G(edtts_hub::hub_dtype(compute_dtype));
-  if (compute_dtype == EDTTS_HUBERT_FP32) return edtts_hubert_workspace_bytes(dims, B, T_audio, out_bytes);
-  edtts_hub::HubLayout L;
-  TRY_G(edtts_hub::hub_layout16(dims, L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
-  edtts_hub::HubWs16 W;
-  TRY_G(edtts_hub::hub_ws16(L, B, T_audio, W));
-  *out_bytes = W.total;
-  return EDTTS_OK;
-}
-
-int edtts_hubert_pack_dt(const EdttsHubertDims* dims, int compute_dtype, const void* const* slots, int n_slots, void* packed, void* stream) {
-  using namespace edtts_hub;
-  TRY_G(hub_dtype(compute_dtype));
-  if (compute_dtype == EDTTS_HUBERT_FP32) return edtts_hubert_pack(dims, slots, n_slots, packed, stream);
-  HubLayout L;
-  TRY_G(hub_layout16(dims, L));
-  const int want = 3 + (L.nc - 1) + 8 + 16 * L.L;
-  if (!slots || !packed) return fail(EDTTS_ERR_ARG, "slots/packed is NULL");
-  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", want, n_slots);
-  for (int i = 0; i < n_slots; ++i)
-    if (!slots[i]) return fail(EDTTS_ERR_ARG, "weight slot %d is NULL", i);
-  if (!hub_al16(packed)) return fail(EDTTS_ERR_ARG, "packed must be 16-byte aligned");
-  return hub_pack16(L, slots, packed, (hipStream_t)stream);
-}
-
-int edtts_hubert_forward_dt(const EdttsHubertDims* dims, int compute_dtype, const void* packed, const float* wav, int B, int T_audio,
-                            const int64_t* lengths, float* out, void* workspace, void* stream) {
-  using namespace edtts_hub;
-  TRY_G(hub_dtype(compute_dtype));
-  if (compute_dtype == EDTTS_HUBERT_FP32) return edtts_hubert_forward(dims, packed, wav, B, T_audio, lengths, out, workspace, stream);
-  HubLayout L;
-  TRY_G(hub_layout16(dims, L));
-  if (!packed || !wav || !out || !workspace) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
-  if (!hub_al16(packed) || !hub_al16(out) || !hub_al16(workspace)) return fail(EDTTS_ERR_ARG, "packed, out and workspace must be 16-byte aligned");
-  return hub_forward16(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream);
-}
-
-int edtts_hubert_forward_until(const EdttsHubertDims* dims, int compute_dtype, const void* packed, const float* wav, int B, int T_audio,
-                               const int64_t* lengths, float* out, void* workspace, int stop_site, int stop_index, int tile, void* stream) {
-  using namespace edtts_hub;
-  TRY_G(hub_dtype(compute_dtype));
-  const bool bf16 = compute_dtype == EDTTS_HUBERT_BF16;
-  HubLayout L;
-  TRY_G(bf16 ? hub_layout16(dims, L) : hub_layout(dims, L));
-  if (!packed || !wav || !out || !workspace) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
-  if (!hub_al16(packed) || !hub_al16(out) || !hub_al16(workspace)) return fail(EDTTS_ERR_ARG, "packed, out and workspace must be 16-byte aligned");
-  HubStop stop;
-  stop.site = stop_site; stop.index = stop_index; stop.tile = tile;
-  TRY_G(hub_stop_check(L, bf16, lengths != nullptr, stop));
-  if (bf16) return hub_forward16(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream, stop);
-  return hub_forward32(L, packed, wav, B, T_audio, lengths, out, workspace, (hipStream_t)stream, stop);
-}
-
-int edtts_hubert_workspace_region(const EdttsHubertDims* dims, int compute_dtype, int B, int T_audio, int which, size_t* offset_bytes,
-                                  size_t* bytes) {
-  using namespace edtts_hub;
-  TRY_G(hub_dtype(compute_dtype));
-  const bool bf16 = compute_dtype == EDTTS_HUBERT_BF16;
-  HubLayout L;
-  TRY_G(bf16 ? hub_layout16(dims, L) : hub_layout(dims, L));
-  if (!offset_bytes || !bytes) return fail(EDTTS_ERR_ARG, "offset_bytes/bytes is NULL");
-  if (B < 1 || T_audio < 1) return fail(EDTTS_ERR_ARG, "B=%d T_audio=%d: need >= 1", B, T_audio);
-  // the members' offsets in layout order, closed by the total: a member reaches up to the next one's offset
-  size_t at[EDTTS_HUB_WS_COUNT + 1];
-  int n = 0;
-  if (bf16) {
-    HubWs16 W;
-    TRY_G(hub_ws16(L, B, T_audio, W));
-    const size_t o[] = {W.lens, W.stats, W.part, W.buf0, W.buf1, W.h, W.att, W.big, W.vt, W.total};
-    for (size_t v : o) at[n++] = v;
-  } else {
-    HubWs W;
-    TRY_G(hub_ws(L, B, T_audio, W));
-    const size_t o[] = {W.lens, W.stats, W.part, W.buf0, W.buf1, W.h, W.att, W.big, W.total};
-    for (size_t v : o) at[n++] = v;
-  }
-  if (which < 0 || which >= n - 1)
-    return fail(EDTTS_ERR_ARG, "edtts_hubert_workspace_region: which=%d: expected an EDTTS_HUB_WS_* member in [0, %d)%s", which, n - 1,
-                bf16 ? "" : " (EDTTS_HUB_WS_VT exists only under EDTTS_HUBERT_BF16)");
-  *offset_bytes = at[which];
-  *bytes = at[which + 1] - at[which];
-  return EDTTS_OK;
-}
-
-}  // extern "C"

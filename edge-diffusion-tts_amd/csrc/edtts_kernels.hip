@@ -2847,8 +2847,9 @@ static int check_shapes(const Layout& lo, int B, int T, int S) {
 #include "edtts_generic_attn16.h"  // ... their attention on bf16 MFMAs (EDTTS_ATTN_BF16) <- edtts_generic.h, edtts_generic_bwd.h, edtts_bf16.h
 #include "edtts_semantic.h"      // SemanticEncoder: proj, FSQ / VQ <- edtts_generic.h: DropArgs
 #include "edtts_semantic_bwd.h"  // ... its training <- edtts_generic_bwd.h: k_bwd_*, drop_state
-#include "edtts_hubert.h"        // NativeHubert, fp32 <- edtts_generic.h: k_gen_norm, k_gen_attn
-#include "edtts_hubert16.h"      // ... its bf16 MFMA path <- edtts_hubert.h
+#include "edtts_hubert.h"        // NativeHubert: the fp32 kernels
+#include "edtts_hubert16.h"      // ... the bf16 MFMA kernels <- edtts_hubert.h: gelu, HEPI_*
+#include "edtts_hubert_host.h"   // ... layout, workspace, packing, launch list, edtts_hubert_* <- both; edtts_generic.h: k_gen_norm, attn
 #include "edtts_audio.h"         // MelSpectrogram, log-mel statistics, Resample <- edtts_melpost.h: melpost::cplx
 #include "edtts_optim.h"         // FusedAdamW: k_opt_*, edtts_optim_*
 #include "edtts_keys.h"          // KeyStream: k_keys_advance, edtts_keys_* <- edtts_device.h: philox4x32_10

@@ -178,6 +178,32 @@ def last_norm(cs):
     return ("ln2", cs.layers - 1) if cs.layers else ("encnorm", 0)
 
 
+# ------------------------------------------------------------------------------------------------------------ layouts
+LAYOUT_GOLDEN = os.path.join(os.path.dirname(GOLDEN), "hubert_layout.json")
+
+
+def layout_records():
+    """What the library's size queries answer (no GPU): {"case dtype BxT_audio": {"packed": bytes, "workspace": bytes, "regions":
+    {member: [offset, bytes]}}} for every case at its first three shapes and hubert-base (nine layers) at 16 x 160000, in every
+    compute dtype the case is legal in.  tests/golden/hubert_layout.json holds what the library answered before its two host-side
+    descriptions (one per dtype) became one (tests/golden/make_hubert_layout.py)."""
+    from edge_diffusion_tts_amd import native
+    with torch.device("meta"):
+        base = NativeHubert({}, 9).dims
+    calls = [(name, module(case(name)).dims, [tuple(sh.wav.shape) for sh in shapes(name)[:3]]) for name in ("F",) + ECASES + ("A1",)]
+    calls.append(("base9", base, [(16, 160000)]))
+    out = {}
+    for name, d, bts in calls:
+        for dtype, dt in native.HUBERT_DTYPES.items():
+            if dt and name not in BF16_LEGAL + ("base9",):
+                continue
+            for B, T_audio in bts:
+                regs = {n: list(native.hubert_workspace_region(d, B, T_audio, dt, n)) for n in native.HUB_WS_REGIONS[:8 + dt]}
+                out[f"{name} {dtype} {B}x{T_audio}"] = {"packed": native.hubert_packed_bytes(d, dt),
+                                                        "workspace": native.hubert_workspace_bytes(d, B, T_audio, dt), "regions": regs}
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------ small pieces
 def gelu64(x):
     return 0.5 * x * (1.0 + torch.erf(x * math.sqrt(0.5)))

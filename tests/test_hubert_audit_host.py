@@ -2,6 +2,7 @@
 are the model (the fixture's stored fp64 outputs; transformers in fp64 where it is installed), an fp32 emulation of either compute
 dtype meets every bar on every case, each seeded mutant of it misses the bar of its own site, and the measured allowances are what
 the constants say.  No GPU."""
+import json
 import os
 import re
 
@@ -144,6 +145,17 @@ def test_the_fold_bar_holds_the_cpu_fold():
         cs = HU.case(name)
         err = (HU.fold_pos(cs).double() - HU.fold_pos(cs, torch.float64)).abs()
         assert float((err / HU.fold_bar(cs)).max()) <= 1.0
+
+
+def test_layouts_are_the_recorded_ones():
+    """The blob and workspace layouts of both compute dtypes are those of the library before the host side described them once
+    (tests/golden/hubert_layout.json, recorded from that library): every size and every member's offset and extent, exactly."""
+    with open(HU.LAYOUT_GOLDEN) as f:
+        want = json.load(f)
+    got = HU.layout_records()
+    assert sorted(got) == sorted(want) and len(want) == (1 + 15 + 1) + (1 + 12) + 2  # fp32: F (one B x T_audio), E1-E5, A1; bf16: F, E1 E3 E4 E5; base
+    for key in want:
+        assert got[key] == want[key], key
 
 
 def test_workspace_regions():
