@@ -1,8 +1,10 @@
-// edtts_semantic_bwd.h -- training the semantic head: proj and FSQEncoder under autograd (included by edtts_kernels.hip behind
-// edtts_semantic.h).
+// edtts_semantic_bwd.h -- training the semantic head: proj and FSQEncoder / VectorQuantizer under autograd (included by
+// edtts_kernels.hip behind edtts_semantic.h; DESIGN.md sections 21, 23 and 37).
 //
-// The training forward is k_sem_encode<true> (edtts_semantic.h): the inference chain, which also writes the tape
-//   y1 = proj.0(h) before GELU [M][S], z [M][S] (both only with a proj), zb = tanh(proj_down(z)) [M][16]       (M = B T_feat)
+// The training forward is k_sem_encode<true> (edtts_semantic.h): the inference chain, which also writes the tape (M = B T_feat rows)
+//   FSQ: y1 = proj.0(h) before GELU [M][S] | z [M][S] (both only with a proj) | zb = tanh(proj_down(z)) [M][16]
+//   VQ:  y1 | z (both only with a proj) | r = c - z [M][S] | sq [M] = sum_s r^2 per frame
+// (r, not c: the EMA update overwrites the codebook before the backward runs, and both gradients are functions of r alone)
 // and multiplies the LayerNorm output by the head's dropout mask (stream word 0x40000, positions as drop_row4 maps them).
 //
 //   k_sem_bwd_frames   the frame-local part of the backward in the forward's layout (64 frames per block, frame = lane & 15, the
@@ -12,59 +14,93 @@
 //                      (statistics recomputed from y1 in fp64; the per-frame sums cross the four lane groups with __shfl_xor) ->
 //                      erf-GELU derivative -> dy1.  It leaves du, zq_low, dz, the post-dropout LayerNorm output a, the masked da, x^ and dy1
 //                      for the sums over frames, zero for frames at or past lengths[b].
+//                      <true>, the VQ head: dz = G - coef[0] r, then the proj backward of the FSQ instantiation
 //   k_sem_pack_fragT   the transposed matrices in fragment order (the training blob)
+//   k_sem_vq_loss     sq -> vq_loss = L + commit L, L = sum sq / (N S): one block, fixed order, fp64 accumulation, rounded once
+//   k_sem_codesum     out[K][S] = sum_m [idx[m] = k] X[m][:] as a one-hot GEMM on v_mfma_f32_16x16x4_f32: the one-hot A operand is
+//                     made in registers from idx (a product by 1.0 or 0.0 is exact), a block owns one tile of 16 codes and one
+//                     slab of dw_slab_rows(M) rows, which its four waves walk 64 rows at a time; a 4-row k-step in which no id
+//                     falls into the tile is skipped (one ballot per 64 rows).  Waves are added in wave order, slabs in ascending
+//                     order by k_bwd_slabsum: no float atomics.
+//                     X = z for ema_w, X = r for the codebook gradient.
+//   k_sem_vq_ema      counts and the code sums of z -> ema_cluster_size, ema_w, codebook.weight (one wave per code)
+//   k_sem_vq_coef     N from the lengths and g = d vq_loss -> coef[0] = g commit 2 / (N S), coef[1] = g 2 / (N S)
+//   k_sem_vq_dcb      d codebook = coef[1] x the code sums of r (rows of unused codes: exactly 0)
 // The sums over frames reuse section 19's kernels (TrainLauncher::dw / colsum, k_bwd_norm_cols): fixed orders, no float atomics.
+//
+// The host side is written once for both quantizers: L.vq decides which members a layout has and which kernel instance runs.
 namespace edtts_sem {
 
-// Training blob (floats): Wu^T [16][S], Wd^T [S][16], W3^T [S][S], each rt-major in fragment order.
+// Training blob (floats), each matrix rt-major in fragment order: FSQ Wu^T [16][S] | Wd^T [S][16], then with a proj W3^T [S][S]
+// (a VQ head without a proj has nothing to pack).
 struct SemTrainLayout {
   size_t wuT, wdT, w3T, total;
 };
-static void sem_train_layout(const SemLayout& L, SemTrainLayout& R) {
-  size_t o = 0;
-  auto take = [&](size_t floats) { size_t r = o; o += (floats + 3) & ~(size_t)3; return r; };
-  R.wuT = take((size_t)L.nt * 64 * 4);
-  R.wdT = take((size_t)L.nt * 64 * 4);
-  R.w3T = L.in_dim ? take((size_t)L.nt * L.nt * 64 * 4) : 0;
-  R.total = o;
-}
-// Tape (floats): with a proj y1 | z | zb, without one zb alone (z is then the caller's input).
-struct SemTape {
-  size_t y1, z, zb, total;
-};
-static void sem_tape(const SemLayout& L, size_t M, SemTape& t) {
-  const size_t MS = L.in_dim ? M * L.S : 0;
-  t.y1 = 0;
-  t.z = MS;
-  t.zb = 2 * MS;
-  t.total = 2 * MS + 16 * M;
-}
-// The backward's scratch (floats): du | zq_low [M][16], dz | gm [M][S], with a proj a | dam | xh | dy1 [M][S] and stat [M][2], then
-// the partial sums of the reductions.
-struct SemScratch {
-  size_t du, zql, dz, gm, a, dam, xh, dy1, stat, part, total;
-};
-static void sem_scratch(const SemLayout& L, int B, int T, SemScratch& s) {
-  const size_t M = (size_t)B * T, S = L.S, MS = M * S;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
-  auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
-  s.du = take(16 * M); s.zql = take(16 * M); s.dz = take(MS); s.gm = take(MS);
-  s.a = s.dam = s.xh = s.dy1 = s.stat = 0;
-  if (L.in_dim) {
-    s.a = take(MS); s.dam = take(MS); s.xh = take(MS); s.dy1 = take(MS); s.stat = take(2 * M);
+static SemTrainLayout sem_train_layout(const SemLayout& L) {
+  SemTrainLayout R{};
+  auto take = [&](size_t floats) { size_t r = R.total; R.total += (floats + 3) & ~(size_t)3; return r; };
+  if (!L.vq) {
+    R.wuT = take((size_t)L.nt * 64 * 4);
+    R.wdT = take((size_t)L.nt * 64 * 4);
   }
+  if (L.in_dim) R.w3T = take((size_t)L.nt * L.nt * 64 * 4);
+  return R;
+}
+
+// The tape and the backward's scratch, each stated once (as tape_regions / scratch_regions state the decoder's, edtts_generic_bwd.h):
+// f(which, member, n) for every member the head has, in memory order -- `which` its EDTTS_SEM_TAPE_* / EDTTS_SEM_SCRATCH_* name,
+// `member` its place in the struct, n its float count.  sem_tape / sem_scratch lay the memory out from the walk,
+// edtts_sem_train_region answers from it, the launchers reach the members through the offsets it filled.  The members of the other
+// quantizer, and those of a proj the head does not have, stay 0.
+struct SemTape {
+  size_t y1, z, zb, r, sq, total;
+};
+template <class Tape, class F>
+static void sem_tape_regions(const SemLayout& L, size_t M, Tape& t, F&& f) {
+  const size_t MS = M * L.S;
+  if (L.in_dim) { f(EDTTS_SEM_TAPE_Y1, t.y1, MS); f(EDTTS_SEM_TAPE_Z, t.z, MS); }  // (without a proj z is the caller's input)
+  if (L.vq) { f(EDTTS_SEM_TAPE_R, t.r, MS); f(EDTTS_SEM_TAPE_SQ, t.sq, M); }
+  else f(EDTTS_SEM_TAPE_ZB, t.zb, 16 * M);
+}
+// (the members follow each other directly: all but sq, the last one, are multiples of 16 floats)
+static SemTape sem_tape(const SemLayout& L, size_t M) {
+  SemTape t{};
+  sem_tape_regions(L, M, t, [&](int, size_t& m, size_t n) { m = t.total; t.total += n; });
+  return t;
+}
+// Scratch of the backward (and of the VQ head's EMA update): FSQ du | zq_low [M][16], dz | gm [M][S]; VQ coef [4] | csum [K][S] (the
+// summed slabs of a code sum) and, with a proj, dz; with a proj a | dam | xh | dy1 [M][S] and stat [M][2]; then the partial sums of
+// the reductions.  Every member starts on a multiple of 4 floats.
+struct SemScratch {
+  size_t du, zql, coef, csum, dz, gm, a, dam, xh, dy1, stat, part, total;
+};
+template <class Scratch, class F>
+static void sem_scratch_regions(const SemLayout& L, int B, int T, Scratch& s, F&& f) {
+  const size_t M = (size_t)B * T, S = L.S, MS = M * S;
+  auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
+  if (L.vq) { f(EDTTS_SEM_SCRATCH_COEF, s.coef, 4); f(EDTTS_SEM_SCRATCH_CSUM, s.csum, (size_t)L.K * S); }
+  else { f(EDTTS_SEM_SCRATCH_DU, s.du, 16 * M); f(EDTTS_SEM_SCRATCH_ZQL, s.zql, 16 * M); }
+  if (!L.vq || L.in_dim) f(EDTTS_SEM_SCRATCH_DZ, s.dz, MS);  // (a VQ head without a proj: dz is the caller's d_z and nothing else)
+  if (!L.vq) f(EDTTS_SEM_SCRATCH_GM, s.gm, MS);
+  if (L.in_dim) {
+    f(EDTTS_SEM_SCRATCH_A, s.a, MS); f(EDTTS_SEM_SCRATCH_DAM, s.dam, MS); f(EDTTS_SEM_SCRATCH_XH, s.xh, MS);
+    f(EDTTS_SEM_SCRATCH_DY1, s.dy1, MS); f(EDTTS_SEM_SCRATCH_STAT, s.stat, 2 * M);
+  }
+  // partial sums: the largest of the slab partials [slabs][N][K] of a cut sum over frames, the bias partials and the LayerNorm partials
+  const size_t r = edtts_bwd::dw_slab_rows((int)M), ns = (M + r - 1) / r;
   size_t part = 0;
-  auto dwp = [&](size_t n, size_t k) {
-    const size_t r = edtts_bwd::dw_slab_rows((int)M), ns = (M + r - 1) / r;
-    if (ns > 1) part = mx(part, ns * n * k);
-  };
-  dwp(S, 16); dwp(16, S);
-  if (L.in_dim) { dwp(S, S); dwp(S, L.in_dim); }
-  part = mx(part, (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows * S);                                        // bias partials
+  if (ns > 1) {
+    part = ns * S * (L.vq ? (size_t)L.K : 16);                         // VQ: code-sum slabs; FSQ: proj_down / proj_up dW slabs
+    if (L.in_dim) part = mx(part, ns * S * mx(S, (size_t)L.in_dim));  // proj's dW slabs
+  }
+  if (!L.vq || L.in_dim) part = mx(part, (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows * S);                     // bias partials
   if (L.in_dim) part = mx(part, (size_t)B * (((size_t)T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk) * 3 * S);  // LayerNorm partials
-  s.part = take(part);
-  s.total = o;
+  f(EDTTS_SEM_SCRATCH_PART, s.part, part);
+}
+static SemScratch sem_scratch(const SemLayout& L, int B, int T) {
+  SemScratch s{};
+  sem_scratch_regions(L, B, T, s, [&](int, size_t& m, size_t n) { m = s.total; s.total += (n + 3) & ~(size_t)3; });
+  return s;
 }
 
 // dst (fragment order, rt-major) <- M^T for M [K][R] row-major: the packed matrix has R rows and K columns
@@ -268,341 +304,6 @@ __global__ __launch_bounds__(256) void k_sem_bwd_frames(SemBwdArgs a) {
   }
 }
 
-}  // namespace edtts_sem
-
-// =========================================================================================================
-// launchers and the C ABI
-// =========================================================================================================
-// dims -> layouts of a trainable head (FSQ only)
-static int sem_train_dims(const EdttsSemDims* dims, const char* who, edtts_sem::SemLayout& L) {
-  TRY_G(edtts_sem::sem_layout(dims, L));
-  if (L.vq)
-    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training covers the FSQ quantizer only (a VQ head trains through edtts_sem_vq_*)", who);
-  return EDTTS_OK;
-}
-// the head's one dropout site: stream word 0x40000 (include/edtts.h, "Philox stream ids")
-static int sem_drop(const edtts_sem::SemLayout& L, const EdttsDropout* drop, const char* who, DropArgs* dr, bool* on,
-                    const uint64_t* key = nullptr) {
-  DropState ds{};
-  TRY_G(drop_state(drop, who, &ds, on, key));
-  if (*on && !L.in_dim) return fail(EDTTS_ERR_ARG, "%s: dropout p=%g given, but a head without proj (in_dim 0) has no dropout site", who, (double)drop->p);
-  *dr = DropArgs{ds.k0, ds.k1, 0x40000u, ds.thr, ds.scale, ds.key};
-  return EDTTS_OK;
-}
-static int sem_shape(int B, int T) {
-  if (B < 0 || T < 0 || (long long)B * T > 0x7fffffffLL - edtts_sem::kFrames) return fail(EDTTS_ERR_ARG, "B=%d T=%d out of range", B, T);
-  return EDTTS_OK;
-}
-// No frames: every sum over frames is empty.  gs holds proj's six slots (only with a proj), then the quantizer's own, of `quant` floats.
-static int sem_zero_grads(hipStream_t st, const edtts_sem::SemLayout& L, float* const* gs, std::initializer_list<size_t> quant) {
-  const size_t S = L.S;
-  int i = 0;
-  auto zero = [&](size_t n) -> int {
-    if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n * sizeof(float), st));
-    ++i;
-    return EDTTS_OK;
-  };
-  if (L.in_dim)
-    for (size_t n : {S * L.in_dim, S, S, S, S * S, S}) TRY_G(zero(n));
-  for (size_t n : quant) TRY_G(zero(n));
-  return EDTTS_OK;
-}
-// proj's gradient sums over the M = B T frames that k_sem_bwd_frames left in `a`, in state-dict slot order (gs[0 .. 5])
-static int sem_proj_sums(hipStream_t st, const edtts_sem::SemLayout& L, const edtts_sem::SemBwdArgs& a, const float* h, int B, int T,
-                         float* const* gs, float* part) {
-  using TL = TrainLauncher;
-  const int S = L.S, M = B * T;
-  TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));  // proj.0.weight = dy1^T h
-  TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
-  if (gs[2] || gs[3]) {                                                  // LayerNorm gain = sum dam o x^, bias = sum dam
-    const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
-    edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
-    hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<edtts_gen::NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
-    LAUNCH_CHECK("k_bwd_norm_cols");
-    if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
-    if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
-  }
-  TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));               // final Linear weight = dz^T a
-  return TL::colsum(st, a.dz, S, M, S, gs[5], part);
-}
-
-// The bodies of the three entry points that draw masks: `key` is the seed in device memory (the *_dev twins) or nullptr.
-static int sem_encode_train_impl(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
-                                 float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, const uint64_t* key, void* stream);
-static int sem_backward_impl(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
-                             int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
-                             const EdttsDropout* drop, const uint64_t* key, void* stream);
-static int sem_dropout_mask_impl(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, const uint64_t* key, uint8_t* keep,
-                                 void* stream);
-
-extern "C" {
-
-int edtts_sem_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_train_packed_bytes", L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  edtts_sem::SemTrainLayout R;
-  edtts_sem::sem_train_layout(L, R);
-  *out_bytes = R.total * sizeof(float);
-  return EDTTS_OK;
-}
-
-int edtts_sem_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream) {
-  using namespace edtts_sem;
-  SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_train_pack", L));
-  const int want = (L.in_dim ? 6 : 0) + 4;
-  if (!slots || !packed_train) return fail(EDTTS_ERR_ARG, "slots/packed_train is NULL");
-  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", want, n_slots);
-  for (int i = 0; i < n_slots; ++i)
-    if (!slots[i]) return fail(EDTTS_ERR_ARG, "weight slot %d is NULL", i);
-  SemTrainLayout R;
-  sem_train_layout(L, R);
-  hipStream_t st = (hipStream_t)stream;
-  float* P = (float*)packed_train;
-  const float* const* s = (const float* const*)slots;
-  const int q = L.in_dim ? 6 : 0;
-  auto fragT = [&](const float* M, int Rr, int K, int nrt, int nkb, size_t off) -> int {
-    const long long n = (long long)nrt * nkb * 256;
-    hipLaunchKernelGGL(k_sem_pack_fragT, dim3((unsigned)min((n + 255) / 256, 4096LL)), dim3(256), 0, st, M, Rr, K, nrt, nkb, P + off);
-    LAUNCH_CHECK("k_sem_pack_fragT");
-    return EDTTS_OK;
-  };
-  TRY_G(fragT(s[q + 2], L.D, L.S, 1, L.nt, R.wuT));  // proj_up.weight [S][D]   -> Wu^T [D][S]
-  TRY_G(fragT(s[q], L.S, L.D, L.nt, 1, R.wdT));      // proj_down.weight [D][S] -> Wd^T [S][D]
-  if (L.in_dim) TRY_G(fragT(s[4], L.S, L.S, L.nt, L.nt, R.w3T));
-  return EDTTS_OK;
-}
-
-int edtts_sem_train_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_train_tape_bytes", L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  TRY_G(sem_shape(B, T));
-  edtts_sem::SemTape tt;
-  edtts_sem::sem_tape(L, (size_t)B * T, tt);
-  *out_bytes = tt.total * sizeof(float);
-  return EDTTS_OK;
-}
-
-int edtts_sem_train_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_train_scratch_bytes", L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  TRY_G(sem_shape(B, T));
-  edtts_sem::SemScratch ss;
-  edtts_sem::sem_scratch(L, B, T, ss);
-  *out_bytes = ss.total * sizeof(float);
-  return EDTTS_OK;
-}
-
-int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
-                           float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, void* stream) {
-  return sem_encode_train_impl(dims, packed, h, B, T, lengths, idx, z_q, counts, tape, drop, nullptr, stream);
-}
-
-int edtts_sem_encode_train_dev(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
-                               float* z_q, int32_t* counts, void* tape, const EdttsDropoutDev* drop, void* stream) {
-  EdttsDropout host;
-  const uint64_t* key;
-  TRY_G(drop_dev(drop, "edtts_sem_encode_train_dev", &host, &key));
-  return sem_encode_train_impl(dims, packed, h, B, T, lengths, idx, z_q, counts, tape, drop ? &host : nullptr, key, stream);
-}
-
-int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
-                       const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
-                       const EdttsDropout* drop, void* stream) {
-  return sem_backward_impl(dims, packed, packed_train, tape, h, B, T, lengths, d_zq, grad_slots, n_slots, d_z, scratch, drop, nullptr, stream);
-}
-
-int edtts_sem_backward_dev(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
-                           const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
-                           const EdttsDropoutDev* drop, void* stream) {
-  EdttsDropout host;
-  const uint64_t* key;
-  TRY_G(drop_dev(drop, "edtts_sem_backward_dev", &host, &key));
-  return sem_backward_impl(dims, packed, packed_train, tape, h, B, T, lengths, d_zq, grad_slots, n_slots, d_z, scratch, drop ? &host : nullptr,
-                           key, stream);
-}
-
-int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream) {
-  return sem_dropout_mask_impl(dims, B, T, drop, nullptr, keep, stream);
-}
-
-int edtts_sem_dropout_mask_dev(const EdttsSemDims* dims, int B, int T, const EdttsDropoutDev* drop, uint8_t* keep, void* stream) {
-  EdttsDropout host;
-  const uint64_t* key;
-  TRY_G(drop_dev(drop, "edtts_sem_dropout_mask_dev", &host, &key));
-  return sem_dropout_mask_impl(dims, B, T, drop ? &host : nullptr, key, keep, stream);
-}
-
-}  // extern "C"
-
-static int sem_encode_train_impl(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
-                                 float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, const uint64_t* key, void* stream) {
-  using namespace edtts_sem;
-  SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_encode_train", L));
-  DropArgs dr{};
-  bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_encode_train", &dr, &dropping, key));
-  TRY_G(sem_shape(B, T));
-  if (!packed || !h || !idx || !tape) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  hipStream_t st = (hipStream_t)stream;
-  SemTape tt;
-  sem_tape(L, (size_t)B * T, tt);
-  float* tp = (float*)tape;
-  EncTrainArgs a{};
-  unsigned blocks;
-  TRY_G(enc_begin(L, packed, h, B, T, lengths, idx, L.in_dim ? tp + tt.z : nullptr, z_q, counts, st, a, &blocks));
-  if (blocks == 0) return EDTTS_OK;
-  a.t_y1 = tp + tt.y1;
-  a.t_zb = tp + tt.zb;
-  a.dr = dr;
-  a.dropping = dropping;
-  hipLaunchKernelGGL(k_sem_encode<true>, dim3(blocks), dim3(256), 0, st, a);
-  LAUNCH_CHECK("k_sem_encode<train>");
-  return EDTTS_OK;
-}
-
-static int sem_backward_impl(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
-                             int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
-                             const EdttsDropout* drop, const uint64_t* key, void* stream) {
-  using namespace edtts_sem;
-  using TL = TrainLauncher;
-  SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_backward", L));
-  DropArgs dr{};
-  bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_backward", &dr, &dropping, key));
-  TRY_G(sem_shape(B, T));
-  const int want = (L.in_dim ? 6 : 0) + 4;
-  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", want, n_slots);
-  if (L.in_dim && d_z) return fail(EDTTS_ERR_ARG, "edtts_sem_backward: d_z is the input gradient of a head without proj (in_dim 0)");
-  if (!packed || !packed_train || !tape || !h || !d_zq || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  hipStream_t st = (hipStream_t)stream;
-  float* const* gs = reinterpret_cast<float* const*>(grad_slots);
-  const int S = L.S, D = L.D, M = B * T, q = L.in_dim ? 6 : 0;
-  if (M == 0) return sem_zero_grads(st, L, gs, {(size_t)D * S, (size_t)D, (size_t)S * D, (size_t)S});
-  SemTrainLayout R;
-  sem_train_layout(L, R);
-  SemTape tt;
-  sem_tape(L, (size_t)M, tt);
-  SemScratch ss;
-  sem_scratch(L, B, T, ss);
-  const float* tp = (const float*)tape;
-  float* sc = (float*)scratch;
-  SemBwdArgs a{};
-  a.p = (const float*)packed;
-  a.pt = (const float*)packed_train;
-  a.g = d_zq;
-  a.len = (const long long*)lengths;
-  a.t_y1 = tp + tt.y1;
-  a.t_zb = tp + tt.zb;
-  a.du = sc + ss.du; a.zql = sc + ss.zql;
-  a.dz = L.in_dim ? sc + ss.dz : d_z;
-  a.gm = lengths ? sc + ss.gm : nullptr;
-  a.a = sc + ss.a; a.dam = sc + ss.dam; a.xh = sc + ss.xh; a.dy1 = sc + ss.dy1; a.stat = sc + ss.stat;
-  a.N = M; a.T = T; a.in_dim = L.in_dim; a.S = S; a.nt = L.nt; a.D = D;
-  a.lng = L.lng; a.lnb = L.lnb; a.half = L.half; a.lev = L.lev;
-  a.wuT = R.wuT; a.wdT = R.wdT; a.w3T = R.w3T;
-  a.dr = dr;
-  a.dropping = dropping;
-  hipLaunchKernelGGL(k_sem_bwd_frames<false>, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
-  LAUNCH_CHECK("k_sem_bwd_frames");
-  // the sums over frames, in state-dict slot order
-  float* part = sc + ss.part;
-  const float* G = lengths ? sc + ss.gm : d_zq;
-  const float* z = L.in_dim ? tp + tt.z : h;
-  if (L.in_dim) TRY_G(sem_proj_sums(st, L, a, h, B, T, gs, part));
-  TRY_G(TL::dw(st, a.du, 16, z, S, M, D, S, gs[q], part));                  // proj_down.weight = du^T z
-  TRY_G(TL::colsum(st, a.du, 16, M, D, gs[q + 1], part));
-  TRY_G(TL::dw(st, G, S, a.zql, 16, M, S, D, gs[q + 2], part));             // proj_up.weight = G^T zq_low
-  TRY_G(TL::colsum(st, G, S, M, S, gs[q + 3], part));
-  return EDTTS_OK;
-}
-
-static int sem_dropout_mask_impl(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, const uint64_t* key, uint8_t* keep,
-                                 void* stream) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_train_dims(dims, "edtts_sem_dropout_mask", L));
-  if (!drop) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: drop is NULL");
-  if (!L.in_dim) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: a head without proj (in_dim 0) has no dropout site");
-  DropArgs dr{};
-  bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_dropout_mask", &dr, &dropping, key));
-  if (!dropping) dr = DropArgs{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0x40000u, 0u, 1.0f};  // p == 0: everything kept
-  TRY_G(sem_shape(B, T));
-  if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
-  const size_t rows = (size_t)B * T;
-  if (rows == 0) return EDTTS_OK;
-  hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * (L.S / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows, L.S,
-                     T, 0, dr);
-  LAUNCH_CHECK("k_drop_mask");
-  return EDTTS_OK;
-}
-
-// =========================================================================================================
-// training the VQ head: VectorQuantizer in training mode under autograd
-// =========================================================================================================
-// The training forward is k_sem_encode<true> with a.vq set: the inference chain, which also writes the tape
-//   y1 | z (both only with a proj) | r = c - z, each [M][S], then sq [M] = sum_s r^2 per frame           (M = B T_feat)
-// (r, not c: the EMA update overwrites the codebook before the backward runs, and both gradients are functions of r alone).
-//
-//   k_sem_vq_loss     sq -> vq_loss = L + commit L, L = sum sq / (N S): one block, fixed order, fp64 accumulation, rounded once
-//   k_sem_codesum     out[K][S] = sum_m [idx[m] = k] X[m][:] as a one-hot GEMM on v_mfma_f32_16x16x4_f32: the one-hot A operand is
-//                     made in registers from idx (a product by 1.0 or 0.0 is exact), a block owns one tile of 16 codes and one
-//                     slab of dw_slab_rows(M) rows, which its four waves walk 64 rows at a time; a 4-row k-step in which no id
-//                     falls into the tile is skipped (one ballot per 64 rows).  Waves are added in wave order, slabs in ascending
-//                     order by k_bwd_slabsum: no float atomics.
-//                     X = z for ema_w, X = r for the codebook gradient.
-//   k_sem_vq_ema      counts and the code sums of z -> ema_cluster_size, ema_w, codebook.weight (one wave per code)
-//   k_sem_vq_coef     N from the lengths and g = d vq_loss -> coef[0] = g commit 2 / (N S), coef[1] = g 2 / (N S)
-//   k_sem_vq_dcb      d codebook = coef[1] x the code sums of r (rows of unused codes: exactly 0)
-//   k_sem_bwd_frames<true>   dz = G - coef[0] r, then the proj backward of the FSQ instantiation
-namespace edtts_sem {
-
-// Training blob (floats): W3^T [S][S] rt-major in fragment order (nothing without a proj).
-static size_t sem_vq_train_floats(const SemLayout& L) { return L.in_dim ? (size_t)L.nt * L.nt * 64 * 4 : 0; }
-// Tape (floats): with a proj y1 | z | r, without one r alone; then sq [M].
-struct SemVqTape {
-  size_t y1, z, r, sq, total;
-};
-static void sem_vq_tape(const SemLayout& L, size_t M, SemVqTape& t) {
-  const size_t MS = M * L.S;
-  t.y1 = 0;
-  t.z = L.in_dim ? MS : 0;
-  t.r = L.in_dim ? 2 * MS : 0;
-  t.sq = t.r + MS;
-  t.total = t.sq + M;
-}
-// Scratch of the EMA update and the backward (floats): coef [4], csum [K][S] (the summed slabs), with a proj dz | a | dam | xh | dy1
-// [M][S] and stat [M][2], then the partial sums of the reductions.
-struct SemVqScratch {
-  size_t coef, csum, dz, a, dam, xh, dy1, stat, part, total;
-};
-static void sem_vq_scratch(const SemLayout& L, int B, int T, SemVqScratch& s) {
-  const size_t M = (size_t)B * T, S = L.S, MS = M * S;
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
-  auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
-  s.coef = take(4);
-  s.csum = take((size_t)L.K * S);
-  s.dz = s.a = s.dam = s.xh = s.dy1 = s.stat = 0;
-  if (L.in_dim) {
-    s.dz = take(MS); s.a = take(MS); s.dam = take(MS); s.xh = take(MS); s.dy1 = take(MS); s.stat = take(2 * M);
-  }
-  const size_t r = edtts_bwd::dw_slab_rows((int)M), ns = (M + r - 1) / r;
-  size_t part = ns > 1 ? ns * (size_t)L.K * S : 0;                                                              // code-sum slabs
-  if (L.in_dim) {
-    if (ns > 1) part = mx(part, ns * S * mx(S, (size_t)L.in_dim));                                              // dW slabs
-    part = mx(part, (M + edtts_bwd::kColRows - 1) / edtts_bwd::kColRows * S);                                   // bias partials
-    part = mx(part, (size_t)B * (((size_t)T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk) * 3 * S);     // LayerNorm partials
-  }
-  s.part = take(part);
-  s.total = o;
-}
-
 // the number of valid frames: sum of the clamped lengths (len null: B T), every thread of the block gets it
 EDTTS_DEV long long vq_valid_frames(const long long* len, int B, int T, long long* sl) {
   const int tid = threadIdx.x;
@@ -765,99 +466,368 @@ static int vq_codesum(hipStream_t st, const SemLayout& L, const long long* idx, 
 
 }  // namespace edtts_sem
 
-// dims -> layout of a trainable VQ head
-static int sem_vq_dims(const EdttsSemDims* dims, const char* who, edtts_sem::SemLayout& L) {
+// =========================================================================================================
+// launchers and the C ABI
+// =========================================================================================================
+// dims -> layout of a trainable head of the quantizer the entry point serves (vq: an edtts_sem_vq_* call)
+static int sem_train_open(const EdttsSemDims* dims, const char* who, bool vq, edtts_sem::SemLayout& L) {
   TRY_G(edtts_sem::sem_layout(dims, L));
-  if (!L.vq) return fail(EDTTS_ERR_UNSUPPORTED, "%s: the VQ quantizer only (an FSQ head trains through edtts_sem_encode_train / edtts_sem_backward)", who);
+  if (L.vq && !vq)
+    return fail(EDTTS_ERR_UNSUPPORTED, "%s: training covers the FSQ quantizer only (a VQ head trains through edtts_sem_vq_*)", who);
+  if (!L.vq && vq)
+    return fail(EDTTS_ERR_UNSUPPORTED, "%s: the VQ quantizer only (an FSQ head trains through edtts_sem_encode_train / edtts_sem_backward)", who);
   return EDTTS_OK;
 }
-static int sem_vq_commit(double commit, const char* who) {
-  if (!(commit >= 0.0) || !(commit <= 1e6)) return fail(EDTTS_ERR_ARG, "%s: commit=%g outside [0, 1e6]", who, commit);
+// the head's one dropout site: stream word 0x40000 (include/edtts.h, "Philox stream ids")
+static int sem_drop(const edtts_sem::SemLayout& L, const EdttsDropout* drop, const char* who, DropArgs* dr, bool* on,
+                    const uint64_t* key = nullptr) {
+  DropState ds{};
+  TRY_G(drop_state(drop, who, &ds, on, key));
+  if (*on && !L.in_dim) return fail(EDTTS_ERR_ARG, "%s: dropout p=%g given, but a head without proj (in_dim 0) has no dropout site", who, (double)drop->p);
+  *dr = DropArgs{ds.k0, ds.k1, 0x40000u, ds.thr, ds.scale, ds.key};
+  return EDTTS_OK;
+}
+static int sem_shape(int B, int T) {
+  if (B < 0 || T < 0 || (long long)B * T > 0x7fffffffLL - edtts_sem::kFrames) return fail(EDTTS_ERR_ARG, "B=%d T=%d out of range", B, T);
+  return EDTTS_OK;
+}
+// state-dict slots: proj's six (only with a proj), then the quantizer's own
+static int sem_n_slots(const edtts_sem::SemLayout& L) { return (L.in_dim ? 6 : 0) + (L.vq ? 1 : 4); }
+
+// What a training forward or backward starts with, in this order: the dims, a VQ call's commit, the dropout, the shape.
+struct SemCall {
+  edtts_sem::SemLayout L;
+  DropArgs dr{};
+  bool dropping;
+};
+static int sem_call_open(const EdttsSemDims* dims, const char* who, bool vq, double commit, const EdttsDropout* drop, const uint64_t* key, int B,
+                         int T, SemCall& c) {
+  TRY_G(sem_train_open(dims, who, vq, c.L));
+  if (vq && (!(commit >= 0.0) || !(commit <= 1e6))) return fail(EDTTS_ERR_ARG, "%s: commit=%g outside [0, 1e6]", who, commit);
+  TRY_G(sem_drop(c.L, drop, who, &c.dr, &c.dropping, key));
+  return sem_shape(B, T);
+}
+// ... and a backward: then its slot count and d_z
+static int sem_bwd_open(const EdttsSemDims* dims, const char* who, bool vq, double commit, const EdttsDropout* drop, const uint64_t* key, int B,
+                        int T, int n_slots, const float* d_z, SemCall& c) {
+  TRY_G(sem_call_open(dims, who, vq, commit, drop, key, B, T, c));
+  if (n_slots != sem_n_slots(c.L)) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", sem_n_slots(c.L), n_slots);
+  if (c.L.in_dim && d_z) return fail(EDTTS_ERR_ARG, "%s: d_z is the input gradient of a head without proj (in_dim 0)", who);
+  return EDTTS_OK;
+}
+
+// The six byte-count queries: the training blob, or the tape / the scratch of B x T frames.
+enum SemSized { SEM_BLOB, SEM_TAPE, SEM_SCRATCH };
+static int sem_train_bytes(const EdttsSemDims* dims, const char* who, bool vq, SemSized what, int B, int T, size_t* out_bytes) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_train_open(dims, who, vq, L));
+  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
+  if (what != SEM_BLOB) TRY_G(sem_shape(B, T));
+  const size_t n = what == SEM_BLOB ? sem_train_layout(L).total : what == SEM_TAPE ? sem_tape(L, (size_t)B * T).total : sem_scratch(L, B, T).total;
+  *out_bytes = n * sizeof(float);
+  return EDTTS_OK;
+}
+
+// The training blob of either head from its (checked) slots: every slot non-NULL, then one k_sem_pack_fragT per matrix.
+static int sem_pack_train(const edtts_sem::SemLayout& L, const void* const* slots, int n_slots, void* packed_train, void* stream) {
+  using namespace edtts_sem;
+  for (int i = 0; i < n_slots; ++i)
+    if (!slots[i]) return fail(EDTTS_ERR_ARG, "weight slot %d is NULL", i);
+  const SemTrainLayout R = sem_train_layout(L);
+  hipStream_t st = (hipStream_t)stream;
+  float* P = (float*)packed_train;
+  const float* const* s = (const float* const*)slots;
+  const int q = L.in_dim ? 6 : 0;
+  auto fragT = [&](const float* M, int Rr, int K, int nrt, int nkb, size_t off) -> int {
+    const long long n = (long long)nrt * nkb * 256;
+    hipLaunchKernelGGL(k_sem_pack_fragT, dim3((unsigned)min((n + 255) / 256, 4096LL)), dim3(256), 0, st, M, Rr, K, nrt, nkb, P + off);
+    LAUNCH_CHECK("k_sem_pack_fragT");
+    return EDTTS_OK;
+  };
+  if (!L.vq) {
+    TRY_G(fragT(s[q + 2], L.D, L.S, 1, L.nt, R.wuT));  // proj_up.weight [S][D]   -> Wu^T [D][S]
+    TRY_G(fragT(s[q], L.S, L.D, L.nt, 1, R.wdT));      // proj_down.weight [D][S] -> Wd^T [S][D]
+  }
+  if (L.in_dim) TRY_G(fragT(s[4], L.S, L.S, L.nt, L.nt, R.w3T));  // final Linear weight [S][S] -> W3^T
+  return EDTTS_OK;
+}
+
+// The training forward of either head behind its checks: enc_begin, the tape's pointers, k_sem_encode<true>.  *blocks == 0: no
+// frames, nothing launched.  tt: the tape's layout, for what the caller launches behind it.
+static int sem_encode_train_run(const SemCall& c, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                                float* z_q, int32_t* counts, void* tape, hipStream_t st, edtts_sem::SemTape& tt, unsigned* blocks) {
+  using namespace edtts_sem;
+  const SemLayout& L = c.L;
+  tt = sem_tape(L, (size_t)B * T);
+  float* tp = (float*)tape;  // (null only when a VQ call has no frames: every offset is then 0, and nothing is launched)
+  EncTrainArgs a{};
+  TRY_G(enc_begin(L, packed, h, B, T, lengths, idx, L.in_dim ? tp + tt.z : nullptr, z_q, counts, st, a, blocks));
+  if (*blocks == 0) return EDTTS_OK;
+  a.t_y1 = tp + tt.y1;
+  if (L.vq) {
+    a.t_r = tp + tt.r;
+    a.t_sq = tp + tt.sq;
+  } else {
+    a.t_zb = tp + tt.zb;
+  }
+  a.dr = c.dr;
+  a.dropping = c.dropping;
+  hipLaunchKernelGGL(k_sem_encode<true>, dim3(*blocks), dim3(256), 0, st, a);
+  LAUNCH_CHECK(L.vq ? "k_sem_encode<train, vq>" : "k_sem_encode<train>");
+  return EDTTS_OK;
+}
+
+// k_sem_bwd_frames' arguments from the layouts and the call's pointers; what the other instantiation reads stays null / 0.
+static edtts_sem::SemBwdArgs sem_bwd_args(const SemCall& c, const edtts_sem::SemTape& tt, const edtts_sem::SemScratch& ss, const void* packed,
+                                          const void* packed_train, const void* tape, void* scratch, const int64_t* lengths, const float* d_zq,
+                                          float* d_z, int M, int T) {
+  using namespace edtts_sem;
+  const SemLayout& L = c.L;
+  const SemTrainLayout R = sem_train_layout(L);
+  const float* tp = (const float*)tape;
+  float* sc = (float*)scratch;
+  SemBwdArgs a{};
+  a.p = (const float*)packed;
+  a.pt = (const float*)packed_train;
+  a.g = d_zq;
+  a.len = (const long long*)lengths;
+  a.t_y1 = tp + tt.y1;
+  if (L.vq) {
+    a.t_r = tp + tt.r;
+    a.coef = sc + ss.coef;
+  } else {
+    a.t_zb = tp + tt.zb;
+    a.du = sc + ss.du; a.zql = sc + ss.zql;
+    a.gm = lengths ? sc + ss.gm : nullptr;
+  }
+  a.dz = L.in_dim ? sc + ss.dz : d_z;
+  a.a = sc + ss.a; a.dam = sc + ss.dam; a.xh = sc + ss.xh; a.dy1 = sc + ss.dy1; a.stat = sc + ss.stat;
+  a.N = M; a.T = T; a.in_dim = L.in_dim; a.S = L.S; a.nt = L.nt; a.D = L.D;
+  a.lng = L.lng; a.lnb = L.lnb; a.half = L.half; a.lev = L.lev;
+  a.wuT = R.wuT; a.wdT = R.wdT; a.w3T = R.w3T;
+  a.dr = c.dr;
+  a.dropping = c.dropping;
+  return a;
+}
+
+// No frames: every sum over frames is empty.  gs holds proj's six slots (only with a proj), then the quantizer's own, of `quant` floats.
+static int sem_zero_grads(hipStream_t st, const edtts_sem::SemLayout& L, float* const* gs, std::initializer_list<size_t> quant) {
+  const size_t S = L.S;
+  int i = 0;
+  auto zero = [&](size_t n) -> int {
+    if (gs[i]) HIP_TRY(hipMemsetAsync(gs[i], 0, n * sizeof(float), st));
+    ++i;
+    return EDTTS_OK;
+  };
+  if (L.in_dim)
+    for (size_t n : {S * L.in_dim, S, S, S, S * S, S}) TRY_G(zero(n));
+  for (size_t n : quant) TRY_G(zero(n));
+  return EDTTS_OK;
+}
+// proj's gradient sums over the M = B T frames that k_sem_bwd_frames left in `a`, in state-dict slot order (gs[0 .. 5])
+static int sem_proj_sums(hipStream_t st, const edtts_sem::SemLayout& L, const edtts_sem::SemBwdArgs& a, const float* h, int B, int T,
+                         float* const* gs, float* part) {
+  using TL = TrainLauncher;
+  const int S = L.S, M = B * T;
+  TRY_G(TL::dw(st, a.dy1, S, h, L.in_dim, M, S, L.in_dim, gs[0], part));  // proj.0.weight = dy1^T h
+  TRY_G(TL::colsum(st, a.dy1, S, M, S, gs[1], part));
+  if (gs[2] || gs[3]) {                                                  // LayerNorm gain = sum dam o x^, bias = sum dam
+    const int cpb = (T + edtts_bwd::kNormChunk - 1) / edtts_bwd::kNormChunk;
+    edtts_bwd::NormBwdArgs na{a.xh, a.dam, nullptr, a.p + L.lng, nullptr, a.stat, part, M, S, T, 0, 0, 1e-5f};
+    hipLaunchKernelGGL(edtts_bwd::k_bwd_norm_cols<edtts_gen::NORM_LAYER>, dim3((S + 63) / 64, B * cpb), dim3(256), 0, st, na);
+    LAUNCH_CHECK("k_bwd_norm_cols");
+    if (gs[2]) TRY_G(TL::slabsum(st, part, gs[2], (size_t)S, B * cpb, (size_t)3 * S));
+    if (gs[3]) TRY_G(TL::slabsum(st, part + S, gs[3], (size_t)S, B * cpb, (size_t)3 * S));
+  }
+  TRY_G(TL::dw(st, a.dz, S, a.a, S, M, S, S, gs[4], part));               // final Linear weight = dz^T a
+  return TL::colsum(st, a.dz, S, M, S, gs[5], part);
+}
+
+// The bodies of the three FSQ entry points that draw masks: `key` is the seed in device memory (the *_dev twins) or nullptr.
+static int sem_encode_train_impl(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                                 float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, const uint64_t* key, void* stream) {
+  SemCall c;
+  TRY_G(sem_call_open(dims, "edtts_sem_encode_train", false, 0.0, drop, key, B, T, c));
+  if (!packed || !h || !idx || !tape) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  edtts_sem::SemTape tt;
+  unsigned blocks;
+  return sem_encode_train_run(c, packed, h, B, T, lengths, idx, z_q, counts, tape, (hipStream_t)stream, tt, &blocks);
+}
+
+static int sem_backward_impl(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B,
+                             int T, const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                             const EdttsDropout* drop, const uint64_t* key, void* stream) {
+  using namespace edtts_sem;
+  using TL = TrainLauncher;
+  SemCall c;
+  TRY_G(sem_bwd_open(dims, "edtts_sem_backward", false, 0.0, drop, key, B, T, n_slots, d_z, c));
+  if (!packed || !packed_train || !tape || !h || !d_zq || !grad_slots || !scratch) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  const SemLayout& L = c.L;
+  hipStream_t st = (hipStream_t)stream;
+  float* const* gs = reinterpret_cast<float* const*>(grad_slots);
+  const int S = L.S, D = L.D, M = B * T, q = L.in_dim ? 6 : 0;
+  if (M == 0) return sem_zero_grads(st, L, gs, {(size_t)D * S, (size_t)D, (size_t)S * D, (size_t)S});
+  const SemTape tt = sem_tape(L, (size_t)M);
+  const SemScratch ss = sem_scratch(L, B, T);
+  const SemBwdArgs a = sem_bwd_args(c, tt, ss, packed, packed_train, tape, scratch, lengths, d_zq, d_z, M, T);
+  hipLaunchKernelGGL(k_sem_bwd_frames<false>, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
+  LAUNCH_CHECK("k_sem_bwd_frames");
+  // the sums over frames, in state-dict slot order
+  float* part = (float*)scratch + ss.part;
+  const float* G = lengths ? a.gm : d_zq;
+  const float* z = L.in_dim ? (const float*)tape + tt.z : h;
+  if (L.in_dim) TRY_G(sem_proj_sums(st, L, a, h, B, T, gs, part));
+  TRY_G(TL::dw(st, a.du, 16, z, S, M, D, S, gs[q], part));                  // proj_down.weight = du^T z
+  TRY_G(TL::colsum(st, a.du, 16, M, D, gs[q + 1], part));
+  TRY_G(TL::dw(st, G, S, a.zql, 16, M, S, D, gs[q + 2], part));             // proj_up.weight = G^T zq_low
+  TRY_G(TL::colsum(st, G, S, M, S, gs[q + 3], part));
+  return EDTTS_OK;
+}
+
+static int sem_dropout_mask_impl(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, const uint64_t* key, uint8_t* keep,
+                                 void* stream) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_open(dims, "edtts_sem_dropout_mask", false, L));
+  if (!drop) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: drop is NULL");
+  if (!L.in_dim) return fail(EDTTS_ERR_ARG, "edtts_sem_dropout_mask: a head without proj (in_dim 0) has no dropout site");
+  DropArgs dr{};
+  bool dropping;
+  TRY_G(sem_drop(L, drop, "edtts_sem_dropout_mask", &dr, &dropping, key));
+  if (!dropping) dr = DropArgs{(unsigned)drop->seed, (unsigned)(drop->seed >> 32), 0x40000u, 0u, 1.0f};  // p == 0: everything kept
+  TRY_G(sem_shape(B, T));
+  if (!keep) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
+  const size_t rows = (size_t)B * T;
+  if (rows == 0) return EDTTS_OK;
+  hipLaunchKernelGGL(edtts_bwd::k_drop_mask, dim3(GenericLauncher::grid_1d(rows * (L.S / 4))), dim3(256), 0, (hipStream_t)stream, keep, rows, L.S,
+                     T, 0, dr);
+  LAUNCH_CHECK("k_drop_mask");
   return EDTTS_OK;
 }
 
 extern "C" {
 
+int edtts_sem_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes) {
+  return sem_train_bytes(dims, "edtts_sem_train_packed_bytes", false, SEM_BLOB, 0, 0, out_bytes);
+}
+int edtts_sem_train_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  return sem_train_bytes(dims, "edtts_sem_train_tape_bytes", false, SEM_TAPE, B, T, out_bytes);
+}
+int edtts_sem_train_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  return sem_train_bytes(dims, "edtts_sem_train_scratch_bytes", false, SEM_SCRATCH, B, T, out_bytes);
+}
 int edtts_sem_vq_train_packed_bytes(const EdttsSemDims* dims, size_t* out_bytes) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_train_packed_bytes", L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  *out_bytes = edtts_sem::sem_vq_train_floats(L) * sizeof(float);
+  return sem_train_bytes(dims, "edtts_sem_vq_train_packed_bytes", true, SEM_BLOB, 0, 0, out_bytes);
+}
+int edtts_sem_vq_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  return sem_train_bytes(dims, "edtts_sem_vq_tape_bytes", true, SEM_TAPE, B, T, out_bytes);
+}
+int edtts_sem_vq_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
+  return sem_train_bytes(dims, "edtts_sem_vq_scratch_bytes", true, SEM_SCRATCH, B, T, out_bytes);
+}
+
+int edtts_sem_train_region(const EdttsSemDims* dims, int B, int T, int which, size_t* offset_bytes, size_t* bytes) {
+  using namespace edtts_sem;
+  SemLayout L;
+  TRY_G(sem_layout(dims, L));
+  if (!offset_bytes || !bytes) return fail(EDTTS_ERR_ARG, "offset_bytes/bytes is NULL");
+  TRY_G(sem_shape(B, T));
+  static const char* const names[EDTTS_SEM_REGION_COUNT] = {"TAPE_Y1",     "TAPE_Z",      "TAPE_ZB",    "TAPE_R",      "TAPE_SQ",     "SCRATCH_DU",
+                                                            "SCRATCH_ZQL", "SCRATCH_DZ",  "SCRATCH_GM", "SCRATCH_A",   "SCRATCH_DAM", "SCRATCH_XH",
+                                                            "SCRATCH_DY1", "SCRATCH_STAT", "SCRATCH_PART", "SCRATCH_COEF", "SCRATCH_CSUM"};
+  if (which < 0 || which >= EDTTS_SEM_REGION_COUNT)
+    return fail(EDTTS_ERR_ARG, "edtts_sem_train_region: which=%d: expected an EDTTS_SEM_TAPE_* / EDTTS_SEM_SCRATCH_* member in [0, %d)", which,
+                EDTTS_SEM_REGION_COUNT);
+  bool found = false;
+  auto pick = [&](int w, const size_t& m, size_t n) {
+    if (w == which) { *offset_bytes = m * sizeof(float); *bytes = n * sizeof(float); found = true; }
+  };
+  const SemTape tt = sem_tape(L, (size_t)B * T);
+  sem_tape_regions(L, (size_t)B * T, tt, pick);
+  const SemScratch ss = sem_scratch(L, B, T);
+  sem_scratch_regions(L, B, T, ss, pick);
+  if (!found)
+    return fail(EDTTS_ERR_ARG, "edtts_sem_train_region: EDTTS_SEM_%s is not a member of this head's layout (%s %s a proj)", names[which],
+                L.vq ? "EDTTS_SEM_VQ" : "EDTTS_SEM_FSQ", L.in_dim ? "with" : "without");
   return EDTTS_OK;
+}
+
+int edtts_sem_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream) {
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_open(dims, "edtts_sem_train_pack", false, L));
+  if (!slots || !packed_train) return fail(EDTTS_ERR_ARG, "slots/packed_train is NULL");
+  if (n_slots != sem_n_slots(L)) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", sem_n_slots(L), n_slots);
+  return sem_pack_train(L, slots, n_slots, packed_train, stream);
 }
 
 int edtts_sem_vq_train_pack(const EdttsSemDims* dims, const void* const* slots, int n_slots, void* packed_train, void* stream) {
-  using namespace edtts_sem;
-  SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_train_pack", L));
-  const int want = (L.in_dim ? 6 : 0) + 1;
-  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", want, n_slots);
+  edtts_sem::SemLayout L;
+  TRY_G(sem_train_open(dims, "edtts_sem_vq_train_pack", true, L));
+  if (n_slots != sem_n_slots(L)) return fail(EDTTS_ERR_ARG, "expected %d weight slots, got %d", sem_n_slots(L), n_slots);
   if (!L.in_dim) return EDTTS_OK;  // nothing to pack
   if (!slots || !packed_train) return fail(EDTTS_ERR_ARG, "slots/packed_train is NULL");
-  for (int i = 0; i < n_slots; ++i)
-    if (!slots[i]) return fail(EDTTS_ERR_ARG, "weight slot %d is NULL", i);
-  const long long n = (long long)L.nt * L.nt * 256;
-  hipLaunchKernelGGL(k_sem_pack_fragT, dim3((unsigned)min((n + 255) / 256, 4096LL)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)slots[4], L.S, L.S, L.nt, L.nt, (float*)packed_train);
-  LAUNCH_CHECK("k_sem_pack_fragT");
-  return EDTTS_OK;
+  return sem_pack_train(L, slots, n_slots, packed_train, stream);
 }
 
-int edtts_sem_vq_tape_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_tape_bytes", L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  TRY_G(sem_shape(B, T));
-  edtts_sem::SemVqTape tt;
-  edtts_sem::sem_vq_tape(L, (size_t)B * T, tt);
-  *out_bytes = tt.total * sizeof(float);
-  return EDTTS_OK;
+int edtts_sem_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                           float* z_q, int32_t* counts, void* tape, const EdttsDropout* drop, void* stream) {
+  return sem_encode_train_impl(dims, packed, h, B, T, lengths, idx, z_q, counts, tape, drop, nullptr, stream);
 }
 
-int edtts_sem_vq_scratch_bytes(const EdttsSemDims* dims, int B, int T, size_t* out_bytes) {
-  edtts_sem::SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_scratch_bytes", L));
-  if (!out_bytes) return fail(EDTTS_ERR_ARG, "out_bytes is NULL");
-  TRY_G(sem_shape(B, T));
-  edtts_sem::SemVqScratch ss;
-  edtts_sem::sem_vq_scratch(L, B, T, ss);
-  *out_bytes = ss.total * sizeof(float);
-  return EDTTS_OK;
+int edtts_sem_encode_train_dev(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
+                               float* z_q, int32_t* counts, void* tape, const EdttsDropoutDev* drop, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_sem_encode_train_dev", &host, &key));
+  return sem_encode_train_impl(dims, packed, h, B, T, lengths, idx, z_q, counts, tape, drop ? &host : nullptr, key, stream);
 }
 
+int edtts_sem_backward(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
+                       const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                       const EdttsDropout* drop, void* stream) {
+  return sem_backward_impl(dims, packed, packed_train, tape, h, B, T, lengths, d_zq, grad_slots, n_slots, d_z, scratch, drop, nullptr, stream);
+}
+
+int edtts_sem_backward_dev(const EdttsSemDims* dims, const void* packed, const void* packed_train, const void* tape, const float* h, int B, int T,
+                           const int64_t* lengths, const float* d_zq, void* const* grad_slots, int n_slots, float* d_z, void* scratch,
+                           const EdttsDropoutDev* drop, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_sem_backward_dev", &host, &key));
+  return sem_backward_impl(dims, packed, packed_train, tape, h, B, T, lengths, d_zq, grad_slots, n_slots, d_z, scratch, drop ? &host : nullptr,
+                           key, stream);
+}
+
+int edtts_sem_dropout_mask(const EdttsSemDims* dims, int B, int T, const EdttsDropout* drop, uint8_t* keep, void* stream) {
+  return sem_dropout_mask_impl(dims, B, T, drop, nullptr, keep, stream);
+}
+
+int edtts_sem_dropout_mask_dev(const EdttsSemDims* dims, int B, int T, const EdttsDropoutDev* drop, uint8_t* keep, void* stream) {
+  EdttsDropout host;
+  const uint64_t* key;
+  TRY_G(drop_dev(drop, "edtts_sem_dropout_mask_dev", &host, &key));
+  return sem_dropout_mask_impl(dims, B, T, drop ? &host : nullptr, key, keep, stream);
+}
+
+// ---- the VQ head
 int edtts_sem_vq_encode_train(const EdttsSemDims* dims, const void* packed, const float* h, int B, int T, const int64_t* lengths, int64_t* idx,
                               float* z_q, int32_t* counts, float* loss, void* tape, int training, double commit, const EdttsDropout* drop,
                               void* stream) {
   using namespace edtts_sem;
-  SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_encode_train", L));
-  TRY_G(sem_vq_commit(commit, "edtts_sem_vq_encode_train"));
-  DropArgs dr{};
-  bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_vq_encode_train", &dr, &dropping));
-  TRY_G(sem_shape(B, T));
+  SemCall c;
+  TRY_G(sem_call_open(dims, "edtts_sem_vq_encode_train", true, commit, drop, nullptr, B, T, c));
   const int N = B * T;
   if (!packed || !loss || (N > 0 && (!h || !idx || !z_q || !tape))) return fail(EDTTS_ERR_ARG, "NULL pointer argument");  // (no frames: nothing to point at)
   hipStream_t st = (hipStream_t)stream;
-  SemVqTape tt;
-  sem_vq_tape(L, (size_t)N, tt);
-  float* tp = (float*)tape;  // (null only when there are no frames: every offset is then 0, and nothing is launched)
-  EncTrainArgs a{};
+  SemTape tt;
   unsigned blocks;
-  TRY_G(enc_begin(L, packed, h, B, T, lengths, idx, L.in_dim ? tp + tt.z : nullptr, z_q, counts, st, a, &blocks));
+  TRY_G(sem_encode_train_run(c, packed, h, B, T, lengths, idx, z_q, counts, tape, st, tt, &blocks));
   if (blocks == 0) {
     HIP_TRY(hipMemsetAsync(loss, 0, sizeof(float), st));
     return EDTTS_OK;
   }
-  a.t_y1 = tp + tt.y1;
-  a.t_r = tp + tt.r;
-  a.t_sq = tp + tt.sq;
-  a.dr = dr;
-  a.dropping = dropping;
-  hipLaunchKernelGGL(k_sem_encode<true>, dim3(blocks), dim3(256), 0, st, a);
-  LAUNCH_CHECK("k_sem_encode<train, vq>");
-  hipLaunchKernelGGL(k_sem_vq_loss, dim3(1), dim3(256), 0, st, tp + tt.sq, N, (const long long*)lengths, B, T, L.S, (float)commit, training,
-                     loss);
+  hipLaunchKernelGGL(k_sem_vq_loss, dim3(1), dim3(256), 0, st, (const float*)tape + tt.sq, N, (const long long*)lengths, B, T, c.L.S, (float)commit,
+                     training, loss);
   LAUNCH_CHECK("k_sem_vq_loss");
   return EDTTS_OK;
 }
@@ -867,7 +837,7 @@ int edtts_sem_vq_ema_update(const EdttsSemDims* dims, const int64_t* idx, const 
                             void* scratch, void* stream) {
   using namespace edtts_sem;
   SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_ema_update", L));
+  TRY_G(sem_train_open(dims, "edtts_sem_vq_ema_update", true, L));
   if (!(decay > 0.0) || !(decay <= 1.0)) return fail(EDTTS_ERR_ARG, "edtts_sem_vq_ema_update: decay=%g outside (0, 1]", decay);
   if (!(epsilon >= 0.0)) return fail(EDTTS_ERR_ARG, "edtts_sem_vq_ema_update: epsilon=%g < 0", epsilon);
   TRY_G(sem_shape(B, T));
@@ -875,8 +845,7 @@ int edtts_sem_vq_ema_update(const EdttsSemDims* dims, const int64_t* idx, const 
   const int M = B * T;
   if (M > 0 && (!idx || !z)) return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   hipStream_t st = (hipStream_t)stream;
-  SemVqScratch ss;
-  sem_vq_scratch(L, B, T, ss);
+  const SemScratch ss = sem_scratch(L, B, T);
   float* sc = (float*)scratch;
   if (M == 0) HIP_TRY(hipMemsetAsync(sc + ss.csum, 0, (size_t)L.K * L.S * sizeof(float), st));
   else TRY_G(vq_codesum(st, L, (const long long*)idx, z, (const long long*)lengths, M, T, sc + ss.csum, sc + ss.part));
@@ -890,46 +859,22 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
                           const int64_t* idx, int B, int T, const int64_t* lengths, const float* d_zq, const float* d_loss, double commit,
                           void* const* grad_slots, int n_slots, float* d_z, void* scratch, const EdttsDropout* drop, void* stream) {
   using namespace edtts_sem;
-  SemLayout L;
-  TRY_G(sem_vq_dims(dims, "edtts_sem_vq_backward", L));
-  TRY_G(sem_vq_commit(commit, "edtts_sem_vq_backward"));
-  DropArgs dr{};
-  bool dropping;
-  TRY_G(sem_drop(L, drop, "edtts_sem_vq_backward", &dr, &dropping));
-  TRY_G(sem_shape(B, T));
-  const int want = (L.in_dim ? 6 : 0) + 1;
-  if (n_slots != want) return fail(EDTTS_ERR_ARG, "expected %d gradient slots, got %d", want, n_slots);
-  if (L.in_dim && d_z) return fail(EDTTS_ERR_ARG, "edtts_sem_vq_backward: d_z is the input gradient of a head without proj (in_dim 0)");
+  SemCall c;
+  TRY_G(sem_bwd_open(dims, "edtts_sem_vq_backward", true, commit, drop, nullptr, B, T, n_slots, d_z, c));
+  const SemLayout& L = c.L;
   const int S = L.S, M = B * T, q = L.in_dim ? 6 : 0;
   if (!grad_slots || (M > 0 && (!tape || !h || !idx || !scratch || (L.in_dim && (!packed || !packed_train)))))
     return fail(EDTTS_ERR_ARG, "NULL pointer argument");
   hipStream_t st = (hipStream_t)stream;
   float* const* gs = reinterpret_cast<float* const*>(grad_slots);
   if (M == 0) return sem_zero_grads(st, L, gs, {(size_t)L.K * S});
-  SemVqTape tt;
-  sem_vq_tape(L, (size_t)M, tt);
-  SemVqScratch ss;
-  sem_vq_scratch(L, B, T, ss);
-  const float* tp = (const float*)tape;
+  const SemTape tt = sem_tape(L, (size_t)M);
+  const SemScratch ss = sem_scratch(L, B, T);
   float* sc = (float*)scratch;
   hipLaunchKernelGGL(k_sem_vq_coef, dim3(1), dim3(256), 0, st, d_loss, (const long long*)lengths, B, T, S, (float)commit, sc + ss.coef);
   LAUNCH_CHECK("k_sem_vq_coef");
   if (L.in_dim || d_z) {
-    SemBwdArgs a{};
-    a.p = (const float*)packed;
-    a.pt = (const float*)packed_train;
-    a.g = d_zq;
-    a.len = (const long long*)lengths;
-    a.t_y1 = tp + tt.y1;
-    a.t_r = tp + tt.r;
-    a.coef = sc + ss.coef;
-    a.dz = L.in_dim ? sc + ss.dz : d_z;
-    a.a = sc + ss.a; a.dam = sc + ss.dam; a.xh = sc + ss.xh; a.dy1 = sc + ss.dy1; a.stat = sc + ss.stat;
-    a.N = M; a.T = T; a.in_dim = L.in_dim; a.S = S; a.nt = L.nt;
-    a.lng = L.lng; a.lnb = L.lnb;
-    a.w3T = 0;
-    a.dr = dr;
-    a.dropping = dropping;
+    const SemBwdArgs a = sem_bwd_args(c, tt, ss, packed, packed_train, tape, scratch, lengths, d_zq, d_z, M, T);
     hipLaunchKernelGGL(k_sem_bwd_frames<true>, dim3((M + kFrames - 1) / kFrames), dim3(256), 0, st, a);
     LAUNCH_CHECK("k_sem_bwd_frames<vq>");
     if (L.in_dim) TRY_G(sem_proj_sums(st, L, a, h, B, T, gs, sc + ss.part));
@@ -939,7 +884,7 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
     if (!d_loss) {
       HIP_TRY(hipMemsetAsync(gs[q], 0, n * sizeof(float), st));
     } else {
-      TRY_G(vq_codesum(st, L, (const long long*)idx, tp + tt.r, (const long long*)lengths, M, T, sc + ss.csum, sc + ss.part));
+      TRY_G(vq_codesum(st, L, (const long long*)idx, (const float*)tape + tt.r, (const long long*)lengths, M, T, sc + ss.csum, sc + ss.part));
       hipLaunchKernelGGL(k_sem_vq_dcb, dim3(GenericLauncher::grid_1d(n)), dim3(256), 0, st, sc + ss.csum, sc + ss.coef, n, gs[q]);
       LAUNCH_CHECK("k_sem_vq_dcb");
     }

@@ -114,9 +114,10 @@ class _VQGrad(torch.autograd.Function):
         ctx.blob, ctx.tblob, ctx.commit, ctx.training = blob, tblob, commit, training
         ctx.x = x
         if training and vq.decay > 0:
-            S = dims.semantic_dim
-            # z: the tape's second region with a proj (y1 | z | r | sq, include/edtts.h), the input itself without one
-            z = tape.view(torch.float32)[B * T * S: 2 * B * T * S].view(B, T, S) if dims.in_dim else x
+            z = x  # without a proj the input itself; with one, where the library says the tape holds z
+            if dims.in_dim:
+                off, n = native.sem_train_region(dims, B, T, "tape.z")
+                z = tape[off:off + n].view(torch.float32).view(B, T, dims.semantic_dim)
             vq._ema_update(dims, idx, z, lengths, counts)
             owner._pack.invalidate()
             vq._pack.invalidate()

@@ -245,6 +245,7 @@ _ABI = {
     "edtts_sem_vq_encode_train": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, f64, drp, vp)),
     "edtts_sem_vq_ema_update": (_STATUS, (sdp, vp, vp, i32, i32, vp, vp, f64, f64, vp, vp, vp, vp, vp)),
     "edtts_sem_vq_backward": (_STATUS, (sdp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f64, p_vp, i32, vp, vp, drp, vp)),
+    "edtts_sem_train_region": (_STATUS, (sdp, i32, i32, i32, p_sz, p_sz)),
     "edtts_optim_chunk_size": (_VALUE, ()),
     "edtts_optim_chunk_table": (_STATUS, (p_i64, i32, i32, p_i32, p_i64, p_i32, p_i32)),
     "edtts_optim_scratch_bytes": (_STATUS, (i32, i32, p_sz)),
@@ -1232,23 +1233,28 @@ def sem_train_scratch_bytes(dims: EdttsSemDims, B: int, T: int) -> int:
     return _size_query(lib().edtts_sem_train_scratch_bytes, C.byref(dims), B, T)
 
 
+def _sem_train_out(dims: EdttsSemDims, h: torch.Tensor, want_counts: bool = True):
+    """(B, T, idx int64 [B, T], z_q [B, T, semantic_dim], counts int32 [num_codes] or None): what a training forward of either head fills."""
+    B, T, D = h.shape
+    _check_sem_width(dims, D)
+    idx = torch.empty((B, T), dtype=torch.int64, device=h.device)
+    zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=h.device)
+    counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=h.device) if want_counts else None
+    return B, T, idx, zq, counts
+
+
 def sem_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tensor, tape: torch.Tensor, lengths: Optional[torch.Tensor] = None,
                      want_counts: bool = True, drop=None):
     """edtts_sem_encode_train: h [B, T, in_dim] (z [B, T, semantic_dim] when dims.in_dim is 0; contiguous, 16-byte aligned) ->
     (idx, z_q, counts or None) as sem_encode, with the backward's tape written to `tape` (uint8, sem_train_tape_bytes).  ``drop``:
     None, an EdttsDropout or a (p, seed) pair."""
-    B, T, D = h.shape
-    _check_sem_width(dims, D)
-    dev = h.device
-    idx = torch.empty((B, T), dtype=torch.int64, device=dev)
-    zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
-    counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=dev) if want_counts else None
+    B, T, idx, zq, counts = _sem_train_out(dims, h, want_counts)
     drop = _dropout(drop)
     fn = lib().edtts_sem_encode_train_dev if isinstance(drop, EdttsDropoutDev) else lib().edtts_sem_encode_train
     fn(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
        _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), zq.data_ptr(),
        None if counts is None else counts.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"),
-       None if drop is None else C.byref(drop), _stream(dev))
+       None if drop is None else C.byref(drop), _stream(h.device))
     return idx, zq, counts
 
 
@@ -1310,18 +1316,13 @@ def sem_vq_encode_train(dims: EdttsSemDims, packed: torch.Tensor, h: torch.Tenso
     """edtts_sem_vq_encode_train: h [B, T, in_dim] (z [B, T, semantic_dim] when dims.in_dim is 0; contiguous, 16-byte aligned) ->
     (idx, z_q, counts, vq_loss 0-dim) with the backward's tape written to `tape` (uint8, sem_vq_tape_bytes).  ``drop``: None, an
     EdttsDropout or a (p, seed) pair."""
-    B, T, D = h.shape
-    _check_sem_width(dims, D)
-    dev = h.device
-    idx = torch.empty((B, T), dtype=torch.int64, device=dev)
-    zq = torch.empty((B, T, dims.semantic_dim), dtype=torch.float32, device=dev)
-    counts = torch.empty((sem_num_codes(dims),), dtype=torch.int32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
+    B, T, idx, zq, counts = _sem_train_out(dims, h)
+    loss = torch.empty((), dtype=torch.float32, device=h.device)
     drop = _dropout(drop)
     lib().edtts_sem_vq_encode_train(C.byref(dims), _dev_ptr(packed, torch.uint8, "packed"), _dev_ptr(h, torch.float32, "features"), B, T,
                                     _dev_ptr(lengths, torch.int64, "lengths"), idx.data_ptr(), zq.data_ptr(), counts.data_ptr(),
                                     loss.data_ptr(), _dev_ptr(tape, torch.uint8, "tape"), int(bool(training)), float(commit),
-                                    None if drop is None else C.byref(drop), _stream(dev))
+                                    None if drop is None else C.byref(drop), _stream(h.device))
     return idx, zq, counts, loss
 
 
@@ -1354,6 +1355,21 @@ def sem_vq_backward(dims: EdttsSemDims, packed: Optional[torch.Tensor], packed_t
                                 _dev_ptr(lengths, torch.int64, "lengths"), _dev_ptr(d_zq, f, "d_zq"), _dev_ptr(d_loss, f, "d_loss"),
                                 float(commit), ptrs, len(grads), _dev_ptr(d_z, f, "d_z"), scratch.data_ptr(),
                                 None if drop is None else C.byref(drop), _stream(h.device))
+
+
+# the members of a head's tape and of its backward's scratch, as edtts_sem_train_region names them (include/edtts.h: EDTTS_SEM_TAPE_* /
+# EDTTS_SEM_SCRATCH_*)
+SEM_TRAIN_REGIONS = ("tape.y1", "tape.z", "tape.zb", "tape.r", "tape.sq", "scratch.du", "scratch.zql", "scratch.dz", "scratch.gm", "scratch.a",
+                     "scratch.dam", "scratch.xh", "scratch.dy1", "scratch.stat", "scratch.part", "scratch.coef", "scratch.csum")
+
+
+def sem_train_region(dims: EdttsSemDims, B: int, T: int, which) -> Tuple[int, int]:
+    """(offset, bytes) of a member of the tape ("tape.*") or of the scratch ("scratch.*") of a head of either quantizer: a name of
+    SEM_TRAIN_REGIONS or its EDTTS_SEM_* number.  A member the head does not have raises."""
+    w = SEM_TRAIN_REGIONS.index(which) if isinstance(which, str) else int(which)
+    off, n = C.c_size_t(0), C.c_size_t(0)
+    lib().edtts_sem_train_region(C.byref(dims), int(B), int(T), w, C.byref(off), C.byref(n))
+    return int(off.value), int(n.value)
 
 
 # ---------------------------------------------------------------------------------------------- HuBERT backbone

@@ -866,6 +866,23 @@ int edtts_sem_vq_backward(const EdttsSemDims* dims, const void* packed, const vo
                           const int64_t* idx, int B, int T, const int64_t* lengths, const float* d_zq, const float* d_loss,
                           double commit, void* const* grad_slots, int n_slots, float* d_z, void* scratch, const EdttsDropout* drop,
                           void* stream);
+/* Offset and bytes of member `which` of the tape (EDTTS_SEM_TAPE_*: offsets into `tape`) or of the scratch (EDTTS_SEM_SCRATCH_*:
+ * offsets into `scratch`) of a head of either quantizer for one (dims, B, T), answered by the code that lays both out.  In memory
+ * order, M = B * T:
+ *     FSQ tape:     y1 [M][S] | z [M][S] (both only with a proj) | zb [M][16]
+ *     VQ tape:      y1 | z (both only with a proj) | r [M][S] | sq [M]
+ *     FSQ scratch:  du | zql [M][16] | dz | gm [M][S] | with a proj a | dam | xh | dy1 [M][S] | stat [M][2] | part
+ *     VQ scratch:   coef [4] | csum [K][S] | with a proj dz | a | dam | xh | dy1 [M][S] | stat [M][2] | part
+ * Tape members follow each other directly; every scratch member starts on a multiple of 4 floats; `part` holds the partial sums of
+ * the reductions.  A member the head does not have (the other quantizer's, or a proj's without a proj) is EDTTS_ERR_ARG by name, as
+ * is `which` out of range.  No GPU call. */
+enum {
+  EDTTS_SEM_TAPE_Y1 = 0, EDTTS_SEM_TAPE_Z = 1, EDTTS_SEM_TAPE_ZB = 2, EDTTS_SEM_TAPE_R = 3, EDTTS_SEM_TAPE_SQ = 4,
+  EDTTS_SEM_SCRATCH_DU = 5, EDTTS_SEM_SCRATCH_ZQL = 6, EDTTS_SEM_SCRATCH_DZ = 7, EDTTS_SEM_SCRATCH_GM = 8, EDTTS_SEM_SCRATCH_A = 9,
+  EDTTS_SEM_SCRATCH_DAM = 10, EDTTS_SEM_SCRATCH_XH = 11, EDTTS_SEM_SCRATCH_DY1 = 12, EDTTS_SEM_SCRATCH_STAT = 13,
+  EDTTS_SEM_SCRATCH_PART = 14, EDTTS_SEM_SCRATCH_COEF = 15, EDTTS_SEM_SCRATCH_CSUM = 16, EDTTS_SEM_REGION_COUNT = 17
+};
+int edtts_sem_train_region(const EdttsSemDims* dims, int B, int T, int which, size_t* offset_bytes, size_t* bytes);
 
 /* ---- the optimiser step  (train_v2.py:299-309 and edge_diffusion_tts/train.py:160-170,245-249,279-281: clip_grad_norm_(params,
  * cfg.grad_clip) then AdamW.step(); training/consistency.py:45-50: ConsistencyTrainer.update_teacher, lerp_ over every parameter) ---

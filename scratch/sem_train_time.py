@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "edge-diffusion-tts_amd"))
+sys.path.insert(0, os.environ.get("EDTTS_PKG_ROOT", os.path.join(REPO, "edge-diffusion-tts_amd")))
 from edge_diffusion_tts_amd import CFG, native  # noqa: E402
 from edge_diffusion_tts_amd.encoder import SemanticEncoder  # noqa: E402
 from edge_diffusion_tts_amd.synth import synth_hubert_features, synth_semantic_head  # noqa: E402
@@ -37,15 +37,15 @@ class EagerHead(nn.Module):
         self.proj = nn.Sequential(nn.Linear(IN_DIM, S), nn.GELU(), nn.LayerNorm(S), nn.Dropout(0.0), nn.Linear(S, S))
         self.proj_down, self.proj_up = nn.Linear(S, len(LEVELS)), nn.Linear(len(LEVELS), S)
         lv = torch.tensor(LEVELS, dtype=torch.float32)
-        self.register_buffer("half", (lv - 1) / 2)
+        self.register_buffer("half_lv", (lv - 1) / 2)  # ("half" is a method of nn.Module)
         self.register_buffer("top", lv - 1)
         self.register_buffer("basis", torch.cumprod(torch.tensor([1] + LEVELS[:-1]), 0))
 
     def forward(self, h):
         zb = torch.tanh(self.proj_down(self.proj(h)))
-        q = torch.minimum(torch.clamp(torch.round((zb + 1) * self.half), min=0), self.top) / self.half - 1
+        q = torch.minimum(torch.clamp(torch.round((zb + 1) * self.half_lv), min=0), self.top) / self.half_lv - 1
         zq_low = zb + (q - zb).detach()
-        idx = (((zq_low + 1) * self.half).round().long() * self.basis).sum(-1)
+        idx = (((zq_low + 1) * self.half_lv).round().long() * self.basis).sum(-1)
         return self.proj_up(zq_low), idx
 
 
